@@ -115,41 +115,60 @@ def cpu_baseline(substrate, pack, obs, nact, worlds_per_core=16, budget_steps=10
   }
 
 
+def _python_tool(name):
+  """The command that runs ROCm's Python tool `name` (rocprofv3, rocm-smi) with this
+  interpreter, or None if it is not installed.  The scripts start with `#!/usr/bin/env
+  python3`: started by name, /usr/bin/env would exec() python3 in its own place."""
+  import shutil
+  path = shutil.which(name) or f"/opt/rocm/bin/{name}"
+  if not os.path.exists(path):
+    return None
+  return [sys.executable, os.path.realpath(path)]
+
+
 def _measure_traffic(argv, kernel_substr, timeout_s=120):
-  """HBM bytes per launch of the kernels matching `kernel_substr`: two
-  `rocprofv3 --pmc` passes (one counter each, MI355X_MICROARCH.md) over a short
-  child run of this script with the same workload flags.  None if rocprofv3 is
-  missing or a pass fails."""
+  """HBM bytes per launch of the kernels matching `kernel_substr`: two rocprofv3 PMC
+  passes (one counter each, MI355X_MICROARCH.md), each over a short child run of this
+  script with the same workload flags.  None if rocprofv3 is missing or a pass fails."""
   import glob
   import shutil
   import sqlite3
   import subprocess
   import tempfile
-  rocprof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
-  if not os.path.exists(rocprof):
+  rocprof = _python_tool("rocprofv3")
+  if rocprof is None:
     return None
   vals = {}
+  counters = ("FETCH_SIZE", "WRITE_SIZE")
   tmp = tempfile.mkdtemp(prefix="mp_pmc_", dir="/tmp")
   env = dict(os.environ, TMPDIR="/tmp")
   try:
-    for counter in ("FETCH_SIZE", "WRITE_SIZE"):
-      out = os.path.join(tmp, counter)
-      cmd = [rocprof, "--pmc", counter, "-d", out, "-o", "r", "--", sys.executable,
-             os.path.abspath(__file__), "--steps", "12", "--warmup", "2", "--no-cpu-baseline",
-             "--no-traffic", "--no-substrate-api", "--no-rollout-api", "--no-steady-state",
-             "--no-configs", "--no-box-fill"] + argv
-      try:
-        subprocess.run(cmd, cwd="/tmp", env=env, timeout=timeout_s, stdout=subprocess.DEVNULL,
-                       stderr=subprocess.DEVNULL, check=True)
-      except (subprocess.SubprocessError, OSError):
-        return None
-      dbs = glob.glob(os.path.join(out, "**", "*.db"), recursive=True)
-      if not dbs:
-        return None
-      rows = sqlite3.connect(dbs[0]).execute(
-          "select kernel_name, avg(value) from counters_collection where counter_name = ? "
-          "group by kernel_name", (counter,)).fetchall()
-      hit = [v for k, v in rows if kernel_substr in k]
+    # Both passes from one input file (one `pmc:` line each, output under pmc_<pass>/):
+    # rocprofv3 then starts the program as a child process for every pass, where a single
+    # --pmc on its command line would make it exec() the program in its own place.
+    passes = os.path.join(tmp, "passes.txt")
+    with open(passes, "w") as f:
+      f.write("".join(f"pmc: {c}\n" for c in counters))
+    cmd = rocprof + ["-i", passes, "-d", tmp, "-o", "r", "--", sys.executable,
+           os.path.abspath(__file__), "--steps", "12", "--warmup", "2", "--no-cpu-baseline",
+           "--no-traffic", "--no-substrate-api", "--no-rollout-api", "--no-steady-state",
+           "--no-configs", "--no-box-fill"] + argv
+    try:
+      subprocess.run(cmd, cwd="/tmp", env=env, timeout=len(counters) * timeout_s,
+                     stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
+    except (subprocess.SubprocessError, OSError):
+      return None
+    dbs = glob.glob(os.path.join(tmp, "**", "*.db"), recursive=True)
+    for counter in counters:
+      hit = []
+      for db in dbs:
+        try:
+          rows = sqlite3.connect(db).execute(
+              "select kernel_name, avg(value) from counters_collection where counter_name = ? "
+              "group by kernel_name", (counter,)).fetchall()
+        except sqlite3.Error:
+          continue
+        hit += [v for k, v in rows if kernel_substr in k]
       if not hit:
         return None
       vals[counter] = max(hit)   # KiB per dispatch
@@ -364,6 +383,39 @@ def rollout_api_bench(num_worlds, steps, warmup, device, slots=32):
   return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: everything written, at most
+
+
+def dump_outputs(eng, kind, view, out_dir):
+  """`--dump-outputs DIR`: what the timed path handed its caller after its last step (the
+  bound view and the scalar outputs of that step) as DIR/<name>.npy, float32 / float64.
+  A view larger than the budget is written for a fixed sample of worlds (seed 0, sorted;
+  the same worlds in every file, listed in world_index.npy), so that two builds run with
+  the same arguments can be compared output for output."""
+  import numpy as np
+  import torch
+  from meltingpot_amd import engine as E
+  N = eng.N
+  scalars = {"reward": E.OBS_REWARD, "discount": E.OBS_DISCOUNT, "step_type": E.OBS_STEP_TYPE}
+  scalar_elems = sum(int(np.prod(eng.shapes[k][0])) // N for k in scalars.values())
+  per_world = (view.numel() // N) * 4 + scalar_elems * 8 + 8
+  keep = min(N, DUMP_BUDGET_BYTES // per_world)
+  if keep < 1:
+    raise SystemExit(f"bench.py: one world's outputs ({per_world} B) exceed --dump-outputs' "
+                     f"{DUMP_BUDGET_BYTES} B")
+  idx = np.arange(N) if keep == N else np.sort(np.random.default_rng(0).choice(N, keep, replace=False))
+  sel = torch.from_numpy(idx).to(view.device)
+  out = {"world_index": idx.astype(np.float64),
+         ("world_rgb" if kind == E.OBS_WORLD_RGB else "rgb"):
+             view.index_select(0, sel).cpu().numpy().astype(np.float32)}
+  for name, k in scalars.items():
+    out[name] = eng.observe(k).index_select(0, sel).cpu().numpy().astype(np.float64)
+  os.makedirs(out_dir, exist_ok=True)
+  for name, a in out.items():
+    np.save(os.path.join(out_dir, f"{name}.npy"), a)
+  assert sum(a.nbytes for a in out.values()) <= DUMP_BUDGET_BYTES
+
+
 def _free_port():
   import socket
   with socket.socket() as s:
@@ -452,9 +504,9 @@ def box_state(device_index):
   them.  Diagnostic only; any failure leaves the field out."""
   import subprocess
   try:
-    out = subprocess.run(["rocm-smi", "-d", str(device_index), "--showcomputepartition",
-                          "--showmemorypartition", "--showclocks", "--showpower", "--showperflevel",
-                          "--json"], capture_output=True, text=True, timeout=10)
+    out = subprocess.run(_python_tool("rocm-smi") + [
+        "-d", str(device_index), "--showcomputepartition", "--showmemorypartition", "--showclocks",
+        "--showpower", "--showperflevel", "--json"], capture_output=True, text=True, timeout=10)
     cards = json.loads(out.stdout)
     card = cards.get(f"card{device_index}") or next(iter(cards.values()))
     keep = ("partition", "sclk", "mclk", "fclk", "socclk", "power", "performance level")
@@ -538,10 +590,18 @@ def main():
   ap.add_argument("--rendezvous-only", action="store_true",
                   help="tests: launch / meet / shard / report over gloo without an engine "
                        "(runs without a GPU; prints value null)")
+  ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                  help="after the timed steps, write what the last of them computed (the bound "
+                       "view of a fixed sample of worlds, reward, discount, step type) as "
+                       "DIR/<name>.npy, float32 / float64, at most 64 MB; one GPU only")
   args = ap.parse_args()
 
   if args.gpus < 1:
     raise SystemExit("bench.py: --gpus must be >= 1")
+  if args.steps < 1 or args.warmup < 0:
+    raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+  if args.dump_outputs and args.gpus != 1:
+    raise SystemExit("bench.py: --dump-outputs runs on one GPU (--gpus 1)")
   if "WORLD_SIZE" not in os.environ and args.gpus > 1:
     sys.exit(_launch_ranks(args.gpus, args.one_device, args.rendezvous_only))
   if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -662,6 +722,8 @@ def main():
 
   kernels_ms = {"frame": launch_ms}
   window_counters = eng.counters()   # (of the warm-up + the timed region: read before anything else steps)
+  if args.dump_outputs:
+    dump_outputs(eng, kind, obs, args.dump_outputs)   # (the last timed step's: nothing has stepped since)
   steady = None
   if (world_size == 1 and not args.cold and not args.host_actions and not dev_plan and
       not args.no_steady_state):

@@ -15,9 +15,9 @@ import numpy as np
 import pytest
 
 import util  # noqa: F401
+import refdata
 from meltingpot_amd import substrate
 
-HAVE_REFERENCE = os.path.isdir("/root/reference/meltingpot")
 NAMES = sorted(substrate.SUBSTRATES)
 
 
@@ -95,12 +95,10 @@ def test_substrate_on_the_hip_engine(name):
     assert tuple(ts.reward.shape) == (5, len(roles))
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="no reference tree on this box")
 @pytest.mark.parametrize("name", NAMES)
 def test_registered_config_is_the_reference_config(name):
   """configs/substrates/<name>.py:get_config(): roles, per-player timestep spec, action set."""
-  from meltingpot_amd import refshim
-  ref = refshim.load_config_module(name).get_config()
+  ref = refdata.load_config_module(name).get_config()
   f = substrate.get_factory(name)
   cfg = substrate.get_config(name)
   assert f.valid_roles() == frozenset(ref.valid_roles)
@@ -116,7 +114,6 @@ def test_registered_config_is_the_reference_config(name):
   assert list(cfg.global_observation_names) == list(ref.global_observation_names)
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="no reference tree on this box")
 @pytest.mark.parametrize("name", NAMES)
 def test_reference_config_object_lowered_at_run_time(name, monkeypatch):
   """meltingpot/substrate.py:98-113 with the REFERENCE's config object of every registered
@@ -127,9 +124,8 @@ def test_reference_config_object_lowered_at_run_time(name, monkeypatch):
   inside build(): not compared)."""
   import random
   from oracle_engine import OracleBatchEngine
-  from meltingpot_amd import refshim
   monkeypatch.setattr(substrate.engine_lib, "Engine", OracleBatchEngine)
-  mod = refshim.load_config_module(name)
+  mod = refdata.load_config_module(name)
   config = mod.get_config()
   with config.unlocked():
     config.lab2d_settings_builder = lambda *, roles, config: mod.build(roles, config)

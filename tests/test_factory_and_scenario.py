@@ -18,10 +18,11 @@ import numpy as np
 import pytest
 
 import util  # noqa: F401
-from meltingpot_amd import builder, engine, pack as pack_lib, substrate
+import refdata
+from meltingpot_amd import builder, engine, pack as pack_lib, refshim, substrate
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-HAVE_REFERENCE = os.path.isdir("/root/reference/meltingpot")
+HAVE_REFERENCE = os.path.isdir(os.path.join(refshim.DEFAULT_REFERENCE_ROOT, "meltingpot"))
 needs_reference = pytest.mark.skipif(not HAVE_REFERENCE, reason="no reference tree on this box")
 
 
@@ -63,14 +64,12 @@ def test_factory_methods_follow_the_reference():
     substrate.get_factory_from_config({"name": "clean_up"})
 
 
-@needs_reference
 @pytest.mark.parametrize("name", ["clean_up", "commons_harvest__open", "territory__rooms", "coins",
                                   "bach_or_stravinsky_in_the_matrix__repeated"])
 def test_factory_agrees_with_the_reference_config(name):
   """get_factory(name) of this package against the reference's own config module:
   roles, per-player timestep spec, action spec."""
-  from meltingpot_amd import refshim
-  ref = refshim.load_config_module(name).get_config()
+  ref = refdata.load_config_module(name).get_config()
   f = substrate.get_factory(name)
   assert f.valid_roles() == frozenset(ref.valid_roles)
   assert len(f.default_player_roles()) == len(ref.default_player_roles)
@@ -160,13 +159,11 @@ def test_build_substrate_runs_the_settings_it_is_given(oracle_backed, modified_s
                                                                      "fireZap": 0, "fireClean": 0}])
 
 
-@needs_reference
 def test_a_modified_reference_config_runs_the_modified_map(oracle_backed):
   """meltingpot/substrate.py:75-113 with the REFERENCE's config object: get the config, edit
   what it builds (here: the ASCII map its module holds and AppleGrow's rate through the
   settings builder), build_from_config — the substrate that runs is the edited one."""
-  from meltingpot_amd import refshim
-  mod = refshim.load_config_module("clean_up")
+  mod = refdata.load_config_module("clean_up")
   config = mod.get_config()
   stock_map = mod.ASCII_MAP
 

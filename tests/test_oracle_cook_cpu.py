@@ -2,17 +2,15 @@
 configs/substrates/collaborative_cooking.py + seven layout modules): the committed packs against
 the reference configs, and the oracle's restatement of the rules — a scripted soup from the
 first tomato to the shared reward, and conservation of items over rollouts on stocked kitchens."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
 import util
-from meltingpot_amd import engine, lower, pack, refshim
+import refdata
+from meltingpot_amd import engine, lower, pack
 from oracle import oracle
 
-HAVE_REFERENCE = os.path.isdir("/root/reference/meltingpot")
 LAYOUTS = ("asymmetric", "circuit", "cramped", "crowded", "figure_eight", "forced", "ring")
 ACCEPTED, DROPPED, COLLECTED = 17, 18, 19
 EMPTY, TOMATO, DISH, SOUP = range(4)
@@ -37,14 +35,13 @@ def _names(t):
   return [n.decode() for n in bytes(t["state_names"]).split(b"\0")]
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_committed_pack_is_what_the_reference_config_lowers_to(layout):
   name = f"collaborative_cooking__{layout}"
-  mod = refshim.load_config_module(name)
+  mod = refdata.load_config_module(name)
   roles = tuple(mod.get_config().default_player_roles)
-  settings, _, config = refshim.build_settings(name, roles)
-  base = sys.modules["meltingpot.configs.substrates.collaborative_cooking"]
+  settings, _, config = refdata.build_settings(name, roles)
+  base = refdata.load_config_module("collaborative_cooking")
   committed = engine.load_pack(name)
   assert pack.dumps(lower.lower(name, settings, base.ACTION_SET)) == committed, "run tools/make_packs.py"
   t = pack.loads(committed)

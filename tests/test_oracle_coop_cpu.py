@@ -2,16 +2,15 @@
 committed pack against the reference config, and the oracle's restatement of the rules —
 invariants over rollouts with plentiful ore, and scripted situations with hand-computed
 expectations (two miners on one gold ore, the mining window running out, both on one iron)."""
-import os
 
 import numpy as np
 import pytest
 
 import util
-from meltingpot_amd import lower, pack, refshim
+import refdata
+from meltingpot_amd import lower, pack
 from oracle import oracle
 
-HAVE_REFERENCE = os.path.isdir("/root/reference/meltingpot")
 MINING, EXTRACTION, PAIR = 13, 14, 15
 
 
@@ -24,9 +23,8 @@ def rich(pack_bytes, iron=0.02, gold=0.02):
   return util.patch_pack(pack_bytes, tables={"cm_thr": thr})
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="reference tree not present (GPU box)")
 def test_committed_pack_is_what_the_reference_config_lowers_to(coop_mining_pack):
-  settings, mod, config = refshim.build_settings("coop_mining", ("default",) * 8)
+  settings, mod, config = refdata.build_settings("coop_mining", ("default",) * 8)
   assert pack.dumps(lower.lower("coop_mining", settings, mod.ACTION_SET, default_players=6)) == (
       coop_mining_pack), "run tools/make_packs.py"
   t = pack.loads(coop_mining_pack)
@@ -46,7 +44,7 @@ def test_committed_pack_is_what_the_reference_config_lowers_to(coop_mining_pack)
   assert list(t["cm_thr"]) == [lower.prob_threshold(p) for p in (0.0002, 0.00008, 0.2)]
   assert bytes(t["hit_names"]) == b"mine\0" and bytes(t["action_names"]) == b"move\0turn\0mine\0"
   # the two roles build the same substrate
-  s2, _, _ = refshim.build_settings("coop_mining", ("target",) * 8)
+  s2, _, _ = refdata.build_settings("coop_mining", ("target",) * 8)
   assert pack.dumps(lower.lower("coop_mining", s2, mod.ACTION_SET, default_players=6)) == coop_mining_pack
 
 

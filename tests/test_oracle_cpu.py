@@ -9,18 +9,17 @@ import numpy as np
 import pytest
 
 import util
-from meltingpot_amd import engine, lower, pack, refshim
+import refdata
+from meltingpot_amd import engine, lower, pack
 from oracle import oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "clean_up_1000_steps.json")
 
 
-@pytest.mark.skipif(not os.path.isdir(refshim.DEFAULT_REFERENCE_ROOT),
-                    reason="reference tree not present (GPU box)")
 def test_committed_pack_is_what_the_reference_config_lowers_to(clean_up_pack):
   # tools/make_packs.py: lowered for the config's 15 avatar colours, 7 play by default
-  settings, mod, _ = refshim.build_settings("clean_up", ("default",) * 15)
+  settings, mod, _ = refdata.build_settings("clean_up", ("default",) * 15)
   blob = pack.dumps(lower.lower("clean_up", settings, mod.ACTION_SET, default_players=7))
   assert blob == clean_up_pack, "run tools/make_packs.py"
 
@@ -172,10 +171,8 @@ def test_cleaning_reduces_dirt_and_counts_others(clean_up_pack):
 # ---------------------------------------------------------------- commons_harvest__open
 
 
-@pytest.mark.skipif(not os.path.isdir(refshim.DEFAULT_REFERENCE_ROOT),
-                    reason="reference tree not present (GPU box)")
 def test_committed_commons_pack_is_what_the_reference_config_lowers_to(commons_pack):
-  settings, mod, _ = refshim.build_settings("commons_harvest__open", ("default",) * 16)
+  settings, mod, _ = refdata.build_settings("commons_harvest__open", ("default",) * 16)
   blob = pack.dumps(lower.lower("commons_harvest__open", settings, mod.ACTION_SET))
   assert blob == commons_pack, "run tools/make_packs.py"
 
@@ -236,10 +233,8 @@ def test_commons_density_regrow_invariants(commons_pack):
   assert total > 100 and seen_dess
 
 
-@pytest.mark.skipif(not os.path.isdir(refshim.DEFAULT_REFERENCE_ROOT),
-                    reason="reference tree not present (GPU box)")
 def test_lowering_refuses_components_it_does_not_implement(commons_closed_pack):
-  settings, mod, _ = refshim.build_settings("commons_harvest__closed", ("default",) * 16)
+  settings, mod, _ = refdata.build_settings("commons_harvest__closed", ("default",) * 16)
   assert pack.dumps(lower.lower("x", settings, mod.ACTION_SET)) == commons_closed_pack
   # a component the engine has no rule for is refused by name ...
   import copy
@@ -250,7 +245,7 @@ def test_lowering_refuses_components_it_does_not_implement(commons_closed_pack):
     lower.lower("x", alien, mod.ACTION_SET)
   # ... Role / RoleBasedRewardTile only while they are inert: the partnership map
   # lowers with the default roles, not with a rewarded role on an avatar
-  settings, mod, _ = refshim.build_settings("commons_harvest__partnership", ("default",) * 7)
+  settings, mod, _ = refdata.build_settings("commons_harvest__partnership", ("default",) * 7)
   lower.lower("x", settings, mod.ACTION_SET)
   rewarded = copy.deepcopy(dict(settings))
   for obj in rewarded["simulation"]["gameObjects"]:
@@ -267,13 +262,11 @@ def test_lowering_refuses_components_it_does_not_implement(commons_closed_pack):
 
 # ---------------------------------------------------------------- territory__rooms
 
-@pytest.mark.skipif(not os.path.isdir(refshim.DEFAULT_REFERENCE_ROOT),
-                    reason="reference tree not present (GPU box)")
 def test_committed_territory_pack_is_what_the_reference_config_lowers_to(territory_pack):
   import sys
-  settings, _, _ = refshim.build_settings("territory__rooms", ("default",) * 9)
+  settings, _, _ = refdata.build_settings("territory__rooms", ("default",) * 9)
   # territory__rooms re-uses its base config's action table (territory.py:592-602)
-  action_set = sys.modules["meltingpot.configs.substrates.territory"].ACTION_SET
+  action_set = refdata.load_config_module("territory").ACTION_SET
   blob = pack.dumps(lower.lower("territory__rooms", settings, action_set))
   assert blob == territory_pack, "run tools/make_packs.py"
 
@@ -401,12 +394,10 @@ def test_territory_graduated_sanctions(territory_pack):
   assert levels_seen == {1, 2} and frozen_frames > 0 and removed
 
 
-@pytest.mark.skipif(not os.path.isdir(refshim.DEFAULT_REFERENCE_ROOT),
-                    reason="reference tree not present (GPU box)")
 def test_committed_territory_open_pack_is_what_the_reference_config_lowers_to(territory_open_pack):
   import sys
-  settings, _, _ = refshim.build_settings("territory__open", ("default",) * 9)
-  action_set = sys.modules["meltingpot.configs.substrates.territory"].ACTION_SET
+  settings, _, _ = refdata.build_settings("territory__open", ("default",) * 9)
+  action_set = refdata.load_config_module("territory").ACTION_SET
   blob = pack.dumps(lower.lower("territory__open", settings, action_set))
   assert blob == territory_open_pack, "run tools/make_packs.py"
   hdr = pack.loads(blob)["hdr"]
@@ -414,7 +405,7 @@ def test_committed_territory_open_pack_is_what_the_reference_config_lowers_to(te
   assert (hdr[lower.HDR_H], hdr[lower.HDR_W], hdr[lower.HDR_P]) == (23, 39, 9)
   # territory__inside_out places optional resources and spawn points with
   # 'choice' map characters, drawn once per episode (prefab_utils.lua:101-103)
-  settings, _, _ = refshim.build_settings("territory__inside_out", ("default",) * 5)
+  settings, _, _ = refdata.build_settings("territory__inside_out", ("default",) * 5)
   t = pack.loads(pack.dumps(lower.lower("territory__inside_out", settings, action_set)))
   assert len(t["choice_n"]) == 48 + 64 + 16            # 'A', 'B' and 'Q' cells
   assert sorted(set(t["choice_n"].tolist())) == [3, 4, 7]  # odds 2:1, 1:3, 1:6
@@ -423,8 +414,6 @@ def test_committed_territory_open_pack_is_what_the_reference_config_lowers_to(te
 
 # ---------------------------------------------------------------- coins
 
-@pytest.mark.skipif(not os.path.isdir(refshim.DEFAULT_REFERENCE_ROOT),
-                    reason="reference tree not present (GPU box)")
 def test_committed_coins_pack_is_what_the_reference_config_lowers_to(coins_pack):
   """coins.py draws the map size and the two coin colours with Python's `random`
   inside build(): the committed pack holds every map the generator can draw (one
@@ -432,7 +421,7 @@ def test_committed_coins_pack_is_what_the_reference_config_lowers_to(coins_pack)
   per-world draw of the 20 ordered colour pairs)."""
   import random
   random.seed(0)
-  settings, mod, config = refshim.build_settings("coins", ("default",) * 2)
+  settings, mod, config = refdata.build_settings("coins", ("default",) * 2)
   settings = lower.coins_with_every_map(settings, mod, config)
   blob = pack.dumps(lower.lower("coins", settings, mod.ACTION_SET))
   assert blob == coins_pack, "run tools/make_packs.py"

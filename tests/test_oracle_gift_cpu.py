@@ -3,16 +3,15 @@ configs/substrates/gift_refinements.py): the committed pack against the referenc
 the oracle's restatement of the rules — an independent Python model of the inventories run
 next to oracle rollouts with plentiful tokens (consume, pick, refine-and-gift in the order
 the frame delivers them), and a scripted gift with hand-computed expectations."""
-import os
 
 import numpy as np
 import pytest
 
 import util
-from meltingpot_amd import engine, lower, pack, refshim
+import refdata
+from meltingpot_amd import engine, lower, pack
 from oracle import oracle
 
-HAVE_REFERENCE = os.path.isdir("/root/reference/meltingpot")
 GIFT = 16
 GIFT_HEAVY = [1, 4, 1, 1, 1, 2, 2, 5, 2]   # weights over the ACTION_SET: gifts often, consumes rarely
 
@@ -36,9 +35,8 @@ def decode_gift(a, b):
   return (a & 15) - 1, (a >> 4) - 1, (b & 15) - 1, b >> 4
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="reference tree not present (GPU box)")
 def test_committed_pack_is_what_the_reference_config_lowers_to(gift_pack):
-  settings, mod, config = refshim.build_settings("gift_refinements", ("default",) * 8)
+  settings, mod, config = refdata.build_settings("gift_refinements", ("default",) * 8)
   assert pack.dumps(lower.lower("gift_refinements", settings, mod.ACTION_SET, default_players=6)) == (
       gift_pack), "run tools/make_packs.py"
   t = pack.loads(gift_pack)
@@ -57,7 +55,7 @@ def test_committed_pack_is_what_the_reference_config_lowers_to(gift_pack):
   assert list(t["gr_thr"]) == [lower.prob_threshold(p) for p in (0.0002, 0.2)]
   assert bytes(t["hit_names"]) == b"gift\0"
   assert bytes(t["action_names"]) == b"move\0turn\0refineAndGift\0consumeTokens\0"
-  s2, _, _ = refshim.build_settings("gift_refinements", ("target",) * 8)
+  s2, _, _ = refdata.build_settings("gift_refinements", ("target",) * 8)
   assert pack.dumps(lower.lower("gift_refinements", s2, mod.ACTION_SET, default_players=6)) == gift_pack
 
 

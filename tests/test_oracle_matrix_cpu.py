@@ -11,10 +11,10 @@ import numpy as np
 import pytest
 
 import util
-from meltingpot_amd import engine, lower, pack, refshim
+import refdata
+from meltingpot_amd import engine, lower, pack
 from oracle import oracle
 
-HAVE_REFERENCE = os.path.isdir(refshim.DEFAULT_REFERENCE_ROOT)
 GAMES = ("prisoners_dilemma", "chicken", "stag_hunt", "pure_coordination",
          "rationalizable_coordination", "bach_or_stravinsky", "running_with_scissors")
 NAMES = [f"{g}_in_the_matrix__{v}" for g in GAMES for v in ("repeated", "arena")] + [
@@ -26,23 +26,21 @@ NOOP, FORWARD, BACKWARD, STEP_LEFT, STEP_RIGHT, TURN_LEFT, TURN_RIGHT, INTERACT 
 N, E, S, W = range(4)
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("name", NAMES)
 def test_committed_pack_is_what_the_reference_config_lowers_to(name):
-  cfg = refshim.load_config_module(name).get_config()
+  cfg = refdata.load_config_module(name).get_config()
   roles = tuple(cfg.default_player_roles)
-  settings, mod, _ = refshim.build_settings(name, roles)
+  settings, mod, _ = refdata.build_settings(name, roles)
   tables = lower.lower(name, settings, mod.ACTION_SET)
   if len(cfg.valid_roles) > 1:   # tools/make_packs.py: per-(role, player) constants
     per_role = {}
     for role in sorted(cfg.valid_roles):
-      s2, _, _ = refshim.build_settings(name, (role,) * len(roles))
+      s2, _, _ = refdata.build_settings(name, (role,) * len(roles))
       per_role[role] = lower.lower(name, s2, mod.ACTION_SET)
     lower.add_role_tables(tables, roles, per_role)
   assert pack.dumps(tables) == engine.load_pack(name), "run tools/make_packs.py"
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("name,roles", [
     ("bach_or_stravinsky_in_the_matrix__repeated", ("default", "default")),
     ("bach_or_stravinsky_in_the_matrix__repeated", ("stravinsky_fan", "bach_fan")),
@@ -57,22 +55,21 @@ def test_a_role_assignment_is_the_pack_the_reference_builds_for_it(name, roles):
   build(roles) lowers to (bach_or_stravinsky_in_the_matrix__repeated.py:473-497)."""
   base = pack.loads(engine.load_pack(name))
   names = engine.pack_role_names(engine.load_pack(name))
-  assert names == tuple(sorted(refshim.load_config_module(name).get_config().valid_roles))
+  assert names == tuple(sorted(refdata.load_config_module(name).get_config().valid_roles))
   got = lower.apply_roles(base, [names.index(r) for r in roles])
-  settings, mod, _ = refshim.build_settings(name, roles)
+  settings, mod, _ = refdata.build_settings(name, roles)
   want = lower.lower(name, settings, mod.ACTION_SET)
   for k, v in want.items():
     assert np.array_equal(got[k].reshape(-1), np.asarray(v).reshape(-1)), k
   assert engine.pack_role_names(engine.load_pack(PD)) is None
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("name", NAMES)
 def test_pack_constants_are_the_configs(name):
-  mod = refshim.load_config_module(name)
+  mod = refdata.load_config_module(name)
   cfg = mod.get_config()
   roles = tuple(cfg.default_player_roles)
-  settings, _, _ = refshim.build_settings(name, roles)
+  settings, _, _ = refdata.build_settings(name, roles)
   t = pack.loads(engine.load_pack(name))
   hdr, mi, mf = t["hdr"], t["mx_i32"], t["mx_f64"]
   R = int(mi[0])

@@ -6,16 +6,15 @@ oracle rollouts on a map that starts full of mushrooms; the invariant the HIP ke
 (the Lua's set of potential sites = the mushrooms that waited when the frame began, its counter
 that size minus the mushrooms the map starts with); scripted meals with hand-computed
 expectations."""
-import os
 
 import numpy as np
 import pytest
 
 import util
-from meltingpot_amd import engine, lower, pack, refshim
+import refdata
+from meltingpot_amd import engine, lower, pack
 from oracle import oracle
 
-HAVE_REFERENCE = os.path.isdir("/root/reference/meltingpot")
 EAT, ZAP, SANCTION, REMOVAL, SET_LEVEL = 20, 1, 6, 7, 8
 ZAP_HEAVY = [1, 4, 1, 1, 1, 2, 2, 5]   # weights over the ACTION_SET: walks forward, zaps often
 NAME = "externality_mushrooms__dense"
@@ -66,11 +65,9 @@ def unpack_avatar(v):
   return v & 15, (v >> 4) & 255, (v >> 12) & 15, (v >> 16) & 255, (v >> 24) & 1, (v >> 25) & 1
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="reference tree not present (GPU box)")
 def test_committed_pack_is_what_the_reference_config_lowers_to(mushroom_pack):
-  import sys
-  settings, mod, config = refshim.build_settings(NAME, ("default",) * 5)
-  action_set = sys.modules["meltingpot.configs.substrates.externality_mushrooms"].ACTION_SET
+  settings, mod, config = refdata.build_settings(NAME, ("default",) * 5)
+  action_set = refdata.load_config_module("externality_mushrooms").ACTION_SET
   assert pack.dumps(lower.lower(NAME, settings, action_set)) == mushroom_pack, "run tools/make_packs.py"
   t = pack.loads(mushroom_pack)
   hdr = t["hdr"]

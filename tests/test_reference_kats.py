@@ -16,16 +16,15 @@ and the frame schedule of the four lowered levels — derived by
 against the order in which the oracle actually runs its updaters.
 """
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
 import util
-from meltingpot_amd import lower, refshim
+import refdata
+from meltingpot_amd import lower
 from oracle import schedule
 
-HAVE_REFERENCE = os.path.isdir(refshim.DEFAULT_REFERENCE_ROOT)
 
 
 # ------------------------------------------------------------ prefab_utils_test.lua
@@ -250,19 +249,19 @@ def test_get_positions():
   assert _positions(ascii_map, "W") == sorted(walls)
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="needs the reference tree")
 @pytest.mark.parametrize("name,players", [("clean_up", 7), ("territory__rooms", 9),
                                           ("commons_harvest__open", 16)])
 def test_map_visitor_agrees_with_the_reference_function(name, players):
-  """... and the reference's own function (imported from the reference tree) on the ASCII
-  maps of the lowered configs: every character at the same (x, y)."""
-  import sys
-  settings, _, _ = refshim.build_settings(name, ("default",) * players)
-  gou = sys.modules["meltingpot.utils.substrates.game_object_utils"]
+  """... and the reference's own function (game_object_utils.
+  get_game_object_positions_from_map, its answers recorded by tests/tools/
+  make_reference_fixture.py) on the ASCII maps of the lowered configs: every character
+  at the same (x, y)."""
+  settings, _, _ = refdata.build_settings(name, ("default",) * players)
   ascii_map = settings["simulation"]["map"]
+  recorded = refdata.map_positions(name, players)
+  assert sorted(recorded) == sorted(set(ascii_map) - {"\n"})
   for ch in sorted(set(ascii_map) - {"\n"}):
-    ref = sorted((t.position.x, t.position.y)
-                 for t in gou.get_game_object_positions_from_map(ascii_map, ch))
+    ref = [tuple(p) for p in recorded[ch]]
     assert ref == _positions(ascii_map, ch), (name, ch)
 
 
@@ -370,7 +369,6 @@ def _collapse(order):
   return out
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("name,players", [
     ("clean_up", 7), ("commons_harvest__open", 7), ("territory__rooms", 9), ("coins", 2),
     ("coop_mining", 6), ("gift_refinements", 6),
@@ -389,7 +387,7 @@ def test_the_oracle_runs_its_updaters_in_the_order_the_registry_gives(name, play
   from meltingpot_amd import engine
   from oracle import oracle as oracle_lib
   random.seed(0)
-  settings, _, _ = refshim.build_settings(name, ("default",) * players)
+  settings, _, _ = refdata.build_settings(name, ("default",) * players)
   sim = settings["simulation"]
   objects = ([sim["scene"]] if "scene" in sim else []) + list(sim["gameObjects"])
   objects += [sim["prefabs"][p] for p, _, _ in lower.build_game_object_configs(
@@ -406,11 +404,10 @@ def test_the_oracle_runs_its_updaters_in_the_order_the_registry_gives(name, play
   assert got == want, (got, want)
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="reference tree not present (GPU box)")
 def test_component_updater_tables_carry_the_configs_constants():
   """startFrame / probability of the registrations come from the component kwargs
   the pack's thresholds were lowered from."""
-  settings, _, _ = refshim.build_settings("clean_up", ("default",) * 7)
+  settings, _, _ = refdata.build_settings("clean_up", ("default",) * 7)
   avatar = settings["simulation"]["gameObjects"][0]
   kw = {c["component"]: c.get("kwargs", {}) for c in avatar["components"]}
   regs = dict(schedule.COMPONENT_UPDATERS["Zapper"](kw["Zapper"]))

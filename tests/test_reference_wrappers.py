@@ -31,8 +31,9 @@ import util
 from meltingpot_amd import engine, lab2d_env, refshim, substrate
 from oracle_engine import OracleEngine
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(refshim.DEFAULT_REFERENCE_ROOT),
-                                reason="reference tree not present (GPU box)")
+# (the two lab2d_environment tests stand on this package alone)
+needs_reference = pytest.mark.skipif(not os.path.isdir(refshim.DEFAULT_REFERENCE_ROOT),
+                                     reason="reference tree not present (GPU box)")
 
 
 def _reference_stack(name, roles, seed, action_table=None):
@@ -50,6 +51,7 @@ def _reference_stack(name, roles, seed, action_table=None):
   return ref, cfg, ref.substrate.Substrate(env)
 
 
+@needs_reference
 @pytest.mark.parametrize("name,players", [
     ("clean_up", 7), ("clean_up", 3), ("commons_harvest__open", 7),
     ("commons_harvest__open", 16), ("territory__rooms", 9), ("coins", 2)])
@@ -66,6 +68,7 @@ def test_reference_assert_step_matches_specs(name, players):
     assert [s.name for s in env.reward_spec()] == ["REWARD"] * players
 
 
+@needs_reference
 @pytest.mark.parametrize("name", [
     "prisoners_dilemma_in_the_matrix__repeated", "running_with_scissors_in_the_matrix__arena",
     "bach_or_stravinsky_in_the_matrix__repeated", "stag_hunt_in_the_matrix__arena",
@@ -91,6 +94,7 @@ def test_reference_assert_step_matches_specs_in_the_matrix(name):
     assert np.all(ts.observation[0]["INTERACTION_INVENTORIES"] == -1.0)
 
 
+@needs_reference
 def test_reference_stack_timesteps_are_the_oracles():
   """30 steps through the reference wrappers: per-player lists, None discount ->
   0., COLLECTIVE_REWARD = sum of rewards (collective_reward_wrapper.py:49) — and
@@ -123,6 +127,7 @@ def test_reference_stack_timesteps_are_the_oracles():
   env.close()
 
 
+@needs_reference
 def test_reference_stack_validates_actions_and_emits_observables():
   ref, cfg, env = _reference_stack("clean_up", ("default",) * 7, seed=5)
   seen = {"action": [], "timestep": [], "events": [], "done": []}
@@ -186,6 +191,7 @@ COMPOSITE_TABLE = (
 )
 
 
+@needs_reference
 def test_reference_discrete_action_wrapper_with_a_custom_table():
   """The reference's discrete_action_wrapper.Wrapper(env, action_table=custom),
   unmodified, on this repo's flat environment: composite rows reach the world as

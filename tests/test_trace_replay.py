@@ -16,6 +16,7 @@ import util
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import replay_trace  # noqa: E402
+from meltingpot_amd import refshim  # noqa: E402
 
 
 def _actions(seed, steps, players, weights):
@@ -133,7 +134,7 @@ def test_teacher_forced_masked_replay(clean_up_pack):
 # dmlab2d.Lab2d / dmlab2d.Environment underneath are the stand-in (the product's
 # lab2d_env.Environment on an oracle-backed world).
 
-HAVE_REFERENCE = os.path.isdir("/root/reference/meltingpot")
+HAVE_REFERENCE = os.path.isdir(os.path.join(refshim.DEFAULT_REFERENCE_ROOT, "meltingpot"))
 needs_reference = pytest.mark.skipif(not HAVE_REFERENCE, reason="reference tree not present (GPU box)")
 
 
