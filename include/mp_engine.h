@@ -160,7 +160,20 @@ typedef enum {
                                 row_inventory, col_inventory), exact f64: an event row
                                 {MP_EVENT_INTERACTION, row, col} of a step says which
                                 players' entries are this step's */
-  MP_OBS_KINDS = 21
+  /* Pooled per-agent RGB: "N.RGB" cut down by an area filter, u8 [N][P][VH*S/k][VW*S/k][3] for
+   * k = 2, 4, 8 — byte (y, x, c) is the k x k block average of the full image I of MP_OBS_RGB,
+   * rounded half up: (sum_{i,j<k} I[y*k+i][x*k+j][c] + k*k/2) / (k*k).  Everything the full image
+   * shows is pooled as it is (OutOfBounds, the black view of a dead avatar, beams, facings,
+   * per-viewer sprite maps).  The frame launch draws it straight from the cells' images: the full
+   * image is never written.  Bound (mp_bind_output / _ring / mp_place_output) it is drawn by the
+   * launch that steps the worlds, alone or together with MP_OBS_WORLD_RGB; at most ONE per-agent
+   * view can be bound at a time — binding a pooled kind while MP_OBS_RGB or another pooled kind is
+   * bound (or MP_OBS_RGB while a pooled kind is) is MP_ERR_INVALID.  Buffers of these kinds (and
+   * mp_observe's `dst`) must be 16-byte aligned.  mp_box_fill does not take them. */
+  MP_OBS_RGB_POOL2 = 21,     /* u8 [N][P][VH*S/2][VW*S/2][3]  (clean_up: 44 x 44) */
+  MP_OBS_RGB_POOL4 = 22,     /* u8 [N][P][VH*S/4][VW*S/4][3]  (22 x 22) */
+  MP_OBS_RGB_POOL8 = 23,     /* u8 [N][P][VH*S/8][VW*S/8][3]  (11 x 11: one pixel a cell) */
+  MP_OBS_KINDS = 24
 } MpObsKind;
 
 typedef struct MpEngine MpEngine;

@@ -139,8 +139,23 @@ struct Ctrl {
   uint32_t claim_w[kClaimRing];      // first world of that batch, kNoBatch = the pool was empty
 };
 
+// Pooled per-agent views (MP_OBS_RGB_POOL2/4/8: k x k box average of the 88 x 88 image, rounded
+// half up; `pool` = k, 0 = the full view).  A cell's pooled image is (8/k) x (8/k) pixels; the
+// pooled image of every atlas image is a table in LDS behind the wave scratch (kPoolImgBytes each:
+// its rows packed, 3 bytes a pixel), and a pass's pooled span is assembled in the wave's scratch,
+// which then holds the span (at most 12 KiB / k^2 plus its offset inside a 16-byte line) instead of
+// composited images.
+__host__ __device__ constexpr int pool_img_bytes(int k) { return ((64 / (k * k)) * 3 + 3) & ~3; }
+__host__ __device__ inline int wave_scratch_bytes(const DevTables& t, int pool_k) {
+  const int s = t.scratch_cells * 256;
+  if (pool_k == 0) return s;
+  const int need = (12288 / (pool_k * pool_k) + 31) & ~15;
+  return s > need ? s : need;
+}
+
 __host__ __device__ inline FrameLds frame_lds_layout(const DevTables& t, int slots, int feeders,
-                                                     int nwaves, int slot_scratch_bytes) {
+                                                     int nwaves, int slot_scratch_bytes,
+                                                     int pool_k = 0) {
   FrameLds r;
   int off = 0;
   r.atlas = off; off += t.n_images * kSpriteStride;
@@ -158,7 +173,9 @@ __host__ __device__ inline FrameLds frame_lds_layout(const DevTables& t, int slo
   r.ovlist = off; off += nwaves * 64;                                    // per-wave list of cells with overlays
   r.offtab = off; off += 2 * 64 * 4;                                     // per view
   r.ctrl = off; off += (int)sizeof(Ctrl);
-  r.scratch = off; off += nwaves * t.scratch_cells * 256;                // per-wave composited images
+  if (pool_k) off = (off + 15) & ~15;   // (the pooled span is staged as 16-byte lines)
+  r.scratch = off; off += nwaves * wave_scratch_bytes(t, pool_k);          // per-wave composited images
+  if (pool_k) off += (t.n_images * pool_img_bytes(pool_k) + 15) & ~15;       // pooled atlas (pooled views)
   r.total = off;
   return r;
 }
@@ -325,6 +342,44 @@ __device__ inline void blend_row(uint32_t* acc, const uint8_t* row) {
   }
 }
 
+// One pooled pixel row of a cell (8/k pixels, 0x00BBGGRR each) -> its 3 * 8/k packed bytes at
+// `dst` in LDS.  The span is staged at its offset inside a 16-byte line and bound pooled views are
+// 16-byte aligned (mp_bind_output), so a k = 2 row (12 B) is 4-byte and a k = 4 row (6 B) 2-byte
+// aligned.
+template <int kPool>
+__device__ inline void put_pooled_row(uint8_t* dst, const uint32_t* px) {
+  if constexpr (kPool == 2) {
+    uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+    d[0] = px[0] | (px[1] << 24);
+    d[1] = (px[1] >> 8) | (px[2] << 16);
+    d[2] = (px[2] >> 16) | (px[3] << 8);
+  } else if constexpr (kPool == 4) {
+    uint16_t* d = reinterpret_cast<uint16_t*>(dst);
+    d[0] = (uint16_t)px[0];
+    d[1] = (uint16_t)((px[0] >> 16) | (px[1] << 8));
+    d[2] = (uint16_t)(px[1] >> 8);
+  } else {
+    dst[0] = (uint8_t)px[0];
+    dst[1] = (uint8_t)(px[0] >> 8);
+    dst[2] = (uint8_t)(px[0] >> 16);
+  }
+}
+// ... and the same row copied from the pooled atlas (packed rows, same alignment rules).
+template <int kPool>
+__device__ inline void copy_pooled_row(uint8_t* dst, const uint8_t* src) {
+  if constexpr (kPool == 2) {
+    const uint32_t* a = reinterpret_cast<const uint32_t*>(src);
+    uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+    d[0] = a[0]; d[1] = a[1]; d[2] = a[2];
+  } else if constexpr (kPool == 4) {
+    const uint16_t* a = reinterpret_cast<const uint16_t*>(src);
+    uint16_t* d = reinterpret_cast<uint16_t*>(dst);
+    d[0] = a[0]; d[1] = a[1]; d[2] = a[2];
+  } else {
+    dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
+  }
+}
+
 __device__ inline uint32_t fast_div(uint32_t n, uint32_t d, float rcp) {
   uint32_t q = (uint32_t)((float)n * rcp);
   if (q * d > n) --q;
@@ -455,8 +510,10 @@ __device__ inline void report_stall(const DevTables& t, int lane, uint32_t site,
 
 // kViews: 0 = the per-agent view (out_a), 1 = WORLD.RGB (out_w), 2 = both in one launch
 // (the last plan.world_waves renderer waves draw WORLD.RGB, the others the per-agent view,
-// from the same LDS-resident records)
-template <class Tables, class Sites, int kViews>
+// from the same LDS-resident records).  kPool: 0 = the per-agent view is the full image;
+// 2, 4, 8 = it is pooled by that factor (MP_OBS_RGB_POOL*) — an instantiation of its own: the
+// code of the full views is not touched by it.
+template <class Tables, class Sites, int kViews, int kPool = 0>
 __global__ __launch_bounds__(max_threads<Tables>()) void k_frame(DevTables t, Tables c,
                                                        stepk::StepArgs args,
                                                        uint8_t* __restrict__ out_a,
@@ -721,6 +778,28 @@ __global__ __launch_bounds__(max_threads<Tables>()) void k_frame(DevTables t, Ta
       offtab[lane] = (uint32_t)sr * 8u * row_bytes + cx * 24u;
     FRAME_STAGE(2, ks);
     if (!arrive_and_wait(&ctrl->blob_waves, (uint32_t)n_render_waves)) return;
+    if constexpr (kPool != 0) {
+      // the pooled atlas: every (image, pooled pixel) of the packed opaque images, from the atlas
+      // just staged (an overlay's RGBA image gets a table entry too, never read); the renderers
+      // meet a second time at the same counter
+      constexpr int kN = 8 / kPool, kQ = kN * kN;
+      uint8_t* ptab = smem + lo.scratch + (uint32_t)kWaves * (uint32_t)wave_scratch_bytes(t, kPool);
+      const int items = t.n_images * kQ;
+      for (int i = tid; i < items; i += n_render_waves * 64) {
+        const int img = i / kQ, q = i - img * kQ, qy = q / kN, qx = q - qy * kN;
+        const uint8_t* src = atlas + img * kSpriteStride + qy * kPool * 32 + qx * kPool * 3;
+        uint32_t sum[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int y = 0; y < kPool; ++y)
+#pragma unroll
+          for (int x = 0; x < kPool * 3; ++x) sum[x % 3] += src[y * 32 + x];
+        uint8_t* dst = ptab + img * pool_img_bytes(kPool) + q * 3;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+          dst[ch] = (uint8_t)((sum[ch] + (uint32_t)(kPool * kPool / 2)) / (uint32_t)(kPool * kPool));
+      }
+      if (!arrive_and_wait(&ctrl->blob_waves, 2u * (uint32_t)n_render_waves)) return;
+    }
   }
   FRAME_STAGE(3, npb);
 
@@ -966,7 +1045,15 @@ __global__ __launch_bounds__(max_threads<Tables>()) void k_frame(DevTables t, Ta
   const uint32_t magic_spw = kv.magic_spw;
   const int py = lane & 7, sub = lane >> 3;
   uint8_t* atlas_row = atlas + py * 32;
-  const uint32_t scratch_off = (uint32_t)(lo.scratch - lo.atlas) + (uint32_t)(wave * t.scratch_cells) * 256u;
+  const uint32_t scratch_off =
+      kPool ? (uint32_t)(lo.scratch - lo.atlas) + (uint32_t)(wave * wave_scratch_bytes(t, kPool))
+            : (uint32_t)(lo.scratch - lo.atlas) + (uint32_t)(wave * t.scratch_cells) * 256u;
+  // pooled per-agent view (kPool): a pooled pixel row of a cell is kPN pixels, a pooled strip kPN
+  // rows; lane = cell in phase 1 puts its pooled image at pstage + my_poff
+  constexpr int kPN = kPool ? 8 / kPool : 1;
+  const uint32_t prow = (uint32_t)row_cells * (uint32_t)(kPN * 3), pstrip = prow * (uint32_t)kPN;
+  const uint32_t my_poff = (uint32_t)sr * pstrip + cx * (uint32_t)(kPN * 3);
+  const uint8_t* ptab = smem + lo.scratch + (uint32_t)kWaves * (uint32_t)wave_scratch_bytes(t, kPool);
 
   // Copy phase geometry.  A pass's span (R strips x 8 pixel rows) is written as
   // 16-byte chunks, lane-contiguous: chunk q = bytes [16q, 16q + 16) of the span.
@@ -1002,6 +1089,10 @@ __global__ __launch_bounds__(max_threads<Tables>()) void k_frame(DevTables t, Ta
   // One pass: strips [s0, s0 + R) of the batch whose records start at `wlds`.
   auto render_pass = [&](const uint32_t s0, const uint32_t nstrips, const uint8_t* wlds,
                          uint8_t* out_block) {
+    // (pooled: the pass's span starts at g0; byte i of it is staged at pst + i, the same offset
+    // inside a 16-byte line as in the output)
+    uint8_t* const g0 = kPool ? out_block + (size_t)s0 * pstrip : nullptr;
+    uint8_t* const pst = kPool ? atlas + scratch_off + ((uint32_t)(uintptr_t)g0 & 15u) : nullptr;
     // ---- phase 1 (lane = cell): resolve the draw list top -> bottom; a lane is
     // done at its first opaque sprite (everything below is hidden).  All plane
     // bytes are fetched first and all table entries second, so the pass pays two
@@ -1166,9 +1257,104 @@ __global__ __launch_bounds__(max_threads<Tables>()) void k_frame(DevTables t, Ta
       if (has_ov) r.base |= kSkipCopy;
       if (!live) r.base |= kSkipCopy | kDeadCell;
       recs[lane] = r;
+      if constexpr (kPool != 0) {
+        // a cell that shows ONE image: its pooled image from the pooled atlas, straight into the span
+        if (!wv && live && !has_ov) {
+          const uint8_t* src = ptab + base_img * (uint32_t)pool_img_bytes(kPool);
+#pragma unroll
+          for (int j = 0; j < kPN; ++j)
+            copy_pooled_row<kPool>(pst + my_poff + (uint32_t)j * prow, src + j * kPN * 3);
+        }
+      }
     }
 
     FRAME_STAGE(20, n_ov);   // (developer timeline: phase 1 done)
+    if constexpr (kPool != 0) {
+      if (!wv) {
+        // ---- pooled: the composited cells, eight per sub-pass (eight lanes per cell, one per
+        // pixel row) — resolved per pixel exactly as phase 2b does, then each row summed over
+        // groups of k pixels and the k rows of a pooled row over their lanes (__shfl_xor inside
+        // the cell's eight lanes), rounded half up; the first lane of each k rows puts the row
+        constexpr uint32_t kHalf = (uint32_t)(kPool * kPool / 2);
+        constexpr int kS2 = kPool == 2 ? 2 : kPool == 4 ? 4 : 6;   // / k^2
+        for (int k0 = 0; k0 < n_ov; k0 += 8) {
+          const int k = k0 + sub;
+          const bool valid = k < n_ov;
+          const int c = valid ? ovlist[k] : 0;
+          const CellRec r = recs[c];
+          const uint8_t* row = atlas_row + (r.base & ~kSkipCopy);
+          const uint4 a = *reinterpret_cast<const uint4*>(row);
+          const uint2 bb = *reinterpret_cast<const uint2*>(row + 16);
+          uint32_t w[6] = {a.x, a.y, a.z, a.w, bb.x, bb.y};
+          uint32_t acc[8];
+          unpack_row(w, acc);
+          uint32_t o0 = valid ? r.ov0 : 0u, o1 = r.ov1, o2 = r.ov2;
+          while (o0 != 0) {
+            const uint32_t e = o0 & 4095u;
+            o0 = (o0 >> 12) | (o1 << 20);
+            o1 = (o1 >> 12) | (o2 << 20);
+            o2 >>= 12;
+            const uint8_t* orow = atlas_row + (e & 1023u) * kSpriteStride;
+            if ((e >> 10) & FLAG_PARTIAL) blend_row<2>(acc, orow);
+            else blend_row<1>(acc, orow);
+          }
+          // R and B summed in the two 16-bit halves of one word (64 x 255 < 2^16), G alone
+          uint32_t rb[kPN], gs[kPN];
+#pragma unroll
+          for (int j = 0; j < kPN; ++j) {
+            rb[j] = 0u; gs[j] = 0u;
+#pragma unroll
+            for (int i = 0; i < kPool; ++i) {
+              rb[j] += acc[j * kPool + i] & 0xff00ffu;
+              gs[j] += (acc[j * kPool + i] >> 8) & 255u;
+            }
+          }
+#pragma unroll
+          for (int m = 1; m < kPool; m <<= 1)
+#pragma unroll
+            for (int j = 0; j < kPN; ++j) {
+              rb[j] += (uint32_t)__shfl_xor((int)rb[j], m);
+              gs[j] += (uint32_t)__shfl_xor((int)gs[j], m);
+            }
+          if (valid && (py & (kPool - 1)) == 0) {
+            uint32_t px[kPN];
+#pragma unroll
+            for (int j = 0; j < kPN; ++j)
+              px[j] = (((rb[j] & 0xffffu) + kHalf) >> kS2) | (((gs[j] + kHalf) >> kS2) << 8) |
+                      ((((rb[j] >> 16) + kHalf) >> kS2) << 16);
+            const uint32_t csr = fast_div((uint32_t)c, (uint32_t)row_cells, 1.0f / (float)row_cells);
+            const uint32_t ccx = (uint32_t)c - csr * (uint32_t)row_cells;
+            put_pooled_row<kPool>(pst + csr * pstrip + ccx * (uint32_t)(kPN * 3) +
+                                      (uint32_t)(py / kPool) * prow, px);
+          }
+        }
+        stepk::wsync();   // (the span is whole in LDS)
+        // ---- the span leaves: the 16-byte lines inside it as lane-contiguous 16-byte stores, the
+        // bytes before the first and after the last whole line one byte a lane — nothing outside
+        // [g0, g0 + len) is written (the neighbouring spans are other passes')
+        const uint32_t nstr = nstrips - s0 < (uint32_t)R ? nstrips - s0 : (uint32_t)R;
+        const uint32_t len = nstr * pstrip;
+        const uint32_t lead = (16u - ((uint32_t)(uintptr_t)g0 & 15u)) & 15u;
+        const uint32_t head = lead < len ? lead : len;
+        const uint32_t nch = len > lead ? (len - lead) >> 4 : 0u;
+        const uint32_t tail0 = lead + nch * 16u;
+        uint8_t* gb = g0 + lead;
+        {
+          const uint64_t gp = reinterpret_cast<uint64_t>(gb);
+          gb = reinterpret_cast<uint8_t*>(
+              ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(gp >> 32)) << 32) |
+              (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)gp));
+        }
+        for (uint32_t q = (uint32_t)lane; q < nch; q += 64u) {
+          const uint4 v = *reinterpret_cast<const uint4*>(pst + lead + q * 16u);
+          store_chunk<kNt>(gb, q * 16u, make_uint2(v.x, v.y), make_uint2(v.z, v.w), sc1);
+        }
+        const uint32_t tb = tail0 + (uint32_t)lane - 16u;
+        if ((uint32_t)lane < head) g0[lane] = pst[lane];
+        else if (lane >= 16 && lane < 32 && tb < len) g0[tb] = pst[tb];
+        return;
+      }
+    }
     uint8_t* span = out_block + (size_t)s0 * 8 * row_bytes;
     {
       // the span base is wave-uniform: keep it in SGPRs (saddr form of the stores)
@@ -1355,9 +1541,15 @@ __global__ __launch_bounds__(max_threads<Tables>()) void k_frame(DevTables t, Ta
     // developer build: when did this workgroup draw its first pass (tools/gpu_frame_ends.py)
     if (lane == 0 && ticket == 0) t.claim[2 + 2 * blockIdx.x] = (uint32_t)wall_clock64();
 #endif
-    if (s0 < nstrips)
+    if constexpr (kPool != 0) {
+      if (s0 < nstrips)
+        render_pass(s0, nstrips, smem + lo.records + r0 * wstride,
+                    wv ? out + (size_t)w0 * strips_per_world * 8 * row_bytes
+                       : out + (size_t)w0 * strips_per_world * pstrip);
+    } else if (s0 < nstrips) {
       render_pass(s0, nstrips, smem + lo.records + r0 * wstride,
                   out + (size_t)w0 * strips_per_world * 8 * row_bytes);
+    }
     prev_buf = kb_now;
     for (int i = 0; i < pace; ++i) __builtin_amdgcn_s_sleep(8);
     FRAME_STAGE(9, ticket);
@@ -1389,9 +1581,15 @@ static int slot_scratch_bytes(const DevTables& t, const SubstrateTables& s) {
 static int gcd_int(int a, int b) { while (b) { const int r = a % b; a = b; b = r; } return a; }
 
 // views: 0 = per-agent RGB, 1 = WORLD.RGB, 2 = both in one launch
+// pool_k: the per-agent view is pooled by k (2, 4, 8: MP_OBS_RGB_POOL*), 1 = the full image.  The
+// geometry is chosen as for the full view: a renderer's cost of a pooled pass is its per-cell
+// resolve, which pooling does not shrink, so neither the batch / feeder choice nor the share of
+// renderer waves between two views is scaled by the bytes written; pool_k only enters the LDS
+// layout (pooled atlas, span staging) the ring is fitted beside.
 FramePlan plan_frame(const DevTables& t, const SubstrateTables& s, int num_worlds,
-                     bool with_step, int views, int num_cus, const MpDevOptions* dev) {
+                     bool with_step, int views, int num_cus, const MpDevOptions* dev, int pool_k) {
   FramePlan p = {};
+  const int lds_pool = pool_k > 1 ? pool_k : 0;   // (frame_lds_layout's argument)
   const bool world_view = views == 1;
   const int max_waves = ((with_step && s.substrate == MPK_SUBSTRATE_THE_MATRIX) ? kMatrixThreads
                                                                                 : kDrawThreads) / 64;
@@ -1505,7 +1703,7 @@ FramePlan plan_frame(const DevTables& t, const SubstrateTables& s, int num_world
     }
   };
   fit_feeders();
-  while (frame_lds_layout(t, NB * B, p.feeders, p.nwaves, p.slot_scratch).total > 160 * 1024) {
+  while (frame_lds_layout(t, NB * B, p.feeders, p.nwaves, p.slot_scratch, lds_pool).total > 160 * 1024) {
     if (NB > 2) --NB;
     else if (B > 1) --B;
     else break;
@@ -1513,7 +1711,7 @@ FramePlan plan_frame(const DevTables& t, const SubstrateTables& s, int num_world
   }
   // (a developer override of the staging area can still be too big: fewer waves)
   while (p.nwaves > 4 &&
-         frame_lds_layout(t, NB * B, p.feeders, p.nwaves, p.slot_scratch).total > 160 * 1024) {
+         frame_lds_layout(t, NB * B, p.feeders, p.nwaves, p.slot_scratch, lds_pool).total > 160 * 1024) {
     --p.nwaves;
     fit_feeders();
   }
@@ -1566,8 +1764,8 @@ FramePlan plan_frame(const DevTables& t, const SubstrateTables& s, int num_world
   return p;
 }
 
-int frame_lds_bytes(const DevTables& t, const FramePlan& p) {
-  return frame_lds_layout(t, p.NB * p.B, p.feeders, p.nwaves, p.slot_scratch).total;
+int frame_lds_bytes(const DevTables& t, const FramePlan& p, int pool_k) {
+  return frame_lds_layout(t, p.NB * p.B, p.feeders, p.nwaves, p.slot_scratch, pool_k > 1 ? pool_k : 0).total;
 }
 
 // The world-independent part of a workgroup's LDS image (bytes [0, world) of
@@ -1648,10 +1846,11 @@ uint32_t render_visible_layers(const DevTables& t, const uint8_t* blob, const in
 namespace {
 
 // Everything a launch derives from its plan (FrameConsts): the divisions, on the host.
-FrameConsts frame_consts(const DevTables& t, const FramePlan& p, int num_worlds, bool with_step) {
+FrameConsts frame_consts(const DevTables& t, const FramePlan& p, int num_worlds, bool with_step,
+                         int pool_k) {
   FrameConsts K = {};
   K.p = p;
-  K.lo = frame_lds_layout(t, p.NB * p.B, p.feeders, p.nwaves, p.slot_scratch);
+  K.lo = frame_lds_layout(t, p.NB * p.B, p.feeders, p.nwaves, p.slot_scratch, pool_k);
   K.N = num_worlds;
   K.nbt = (num_worlds + p.B - 1) / p.B;
   K.chains = p.feeders / gcd_int(p.feeders, p.B);
@@ -1684,10 +1883,33 @@ FrameConsts frame_consts(const DevTables& t, const FramePlan& p, int num_worlds,
   return K;
 }
 
+template <class Tables, class Sites, int kPool>
+void launch_pooled(const DevTables& t, const Tables& c, const stepk::StepArgs& args, uint8_t* out_a,
+                   uint8_t* out_w, const FramePlan& p, hipStream_t stream) {
+  FrameConsts K = frame_consts(t, p, args.num_worlds, !std::is_same<Tables, NoTables>::value, kPool);
+  const size_t lds = (size_t)K.lo.total;
+  if (out_w) {
+    K.npb_all = K.npb[0] + K.npb[1];
+    hipLaunchKernelGGL((k_frame<Tables, Sites, 2, kPool>), dim3(p.groups), dim3(p.nwaves * 64), lds,
+                       stream, t, c, args, out_a, out_w, K);
+  } else {
+    K.npb_all = K.npb[0];
+    hipLaunchKernelGGL((k_frame<Tables, Sites, 0, kPool>), dim3(p.groups), dim3(p.nwaves * 64), lds,
+                       stream, t, c, args, out_a, out_w, K);
+  }
+}
+
+// pool_k > 1: out_a is the per-agent view pooled by pool_k (MP_OBS_RGB_POOL*)
 template <class Tables, class Sites>
 void launch_one(const DevTables& t, const Tables& c, const stepk::StepArgs& args, uint8_t* out_a,
-                uint8_t* out_w, const FramePlan& p, hipStream_t stream) {
-  FrameConsts K = frame_consts(t, p, args.num_worlds, !std::is_same<Tables, NoTables>::value);
+                uint8_t* out_w, const FramePlan& p, hipStream_t stream, int pool_k) {
+  if (out_a && pool_k > 1) {
+    if (pool_k == 2) launch_pooled<Tables, Sites, 2>(t, c, args, out_a, out_w, p, stream);
+    else if (pool_k == 4) launch_pooled<Tables, Sites, 4>(t, c, args, out_a, out_w, p, stream);
+    else launch_pooled<Tables, Sites, 8>(t, c, args, out_a, out_w, p, stream);
+    return;
+  }
+  FrameConsts K = frame_consts(t, p, args.num_worlds, !std::is_same<Tables, NoTables>::value, 0);
   const size_t lds = (size_t)K.lo.total;
   if (out_a && out_w) {
     K.npb_all = K.npb[0] + K.npb[1];
@@ -1706,13 +1928,19 @@ void launch_one(const DevTables& t, const Tables& c, const stepk::StepArgs& args
 
 template <class Tables, class Sites>
 int allow_lds() {
-  hipError_t r[3] = {
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_frame<Tables, Sites, 0>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_frame<Tables, Sites, 1>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_frame<Tables, Sites, 2>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)};
+  const void* k[9] = {
+      reinterpret_cast<const void*>(&k_frame<Tables, Sites, 0>),
+      reinterpret_cast<const void*>(&k_frame<Tables, Sites, 1>),
+      reinterpret_cast<const void*>(&k_frame<Tables, Sites, 2>),
+      reinterpret_cast<const void*>(&k_frame<Tables, Sites, 0, 2>),
+      reinterpret_cast<const void*>(&k_frame<Tables, Sites, 2, 2>),
+      reinterpret_cast<const void*>(&k_frame<Tables, Sites, 0, 4>),
+      reinterpret_cast<const void*>(&k_frame<Tables, Sites, 2, 4>),
+      reinterpret_cast<const void*>(&k_frame<Tables, Sites, 0, 8>),
+      reinterpret_cast<const void*>(&k_frame<Tables, Sites, 2, 8>)};
+  hipError_t r[9];
+  for (int i = 0; i < 9; ++i)
+    r[i] = hipFuncSetAttribute(k[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   for (hipError_t e : r)
     if (e != hipSuccess) return (int)e;
   return 0;
@@ -1743,44 +1971,45 @@ int prepare_frame() {
 // names no world ...), or stepped first (one environment step or reset of all worlds
 // + the views of the result).  `p` is the plan for exactly these views; p.parity
 // alternates between consecutive frame launches of an engine (DevTables::claim).
+// pool_k > 1: `out_a` is the per-agent view pooled by that factor (2, 4, 8).
 void launch_frame(const DevTables& t, const SubstrateTables* s, const stepk::StepArgs& args,
-                  uint8_t* out_a, uint8_t* out_w, const FramePlan& p, hipStream_t stream) {
+                  uint8_t* out_a, uint8_t* out_w, const FramePlan& p, hipStream_t stream, int pool_k) {
   if (!s) {
-    launch_one<NoTables, NoSites>(t, NoTables(), args, out_a, out_w, p, stream);
+    launch_one<NoTables, NoSites>(t, NoTables(), args, out_a, out_w, p, stream, pool_k);
     return;
   }
 #if defined(MP_FRAME_ISA_SUBSET)
   // developer build (tools/isa_stats.sh quick): the draw-only and the clean_up kernels alone
   if (s->substrate == MPK_SUBSTRATE_CLEAN_UP)
-    launch_one<CleanUpTables, stepk::CleanUpSites>(t, s->cu, args, out_a, out_w, p, stream);
+    launch_one<CleanUpTables, stepk::CleanUpSites>(t, s->cu, args, out_a, out_w, p, stream, pool_k);
 #else
   switch (s->substrate) {
     case MPK_SUBSTRATE_CLEAN_UP:
-      launch_one<CleanUpTables, stepk::CleanUpSites>(t, s->cu, args, out_a, out_w, p, stream);
+      launch_one<CleanUpTables, stepk::CleanUpSites>(t, s->cu, args, out_a, out_w, p, stream, pool_k);
       break;
     case MPK_SUBSTRATE_COMMONS_HARVEST:
-      launch_one<CommonsTables, stepk::CommonsSites>(t, s->ch, args, out_a, out_w, p, stream);
+      launch_one<CommonsTables, stepk::CommonsSites>(t, s->ch, args, out_a, out_w, p, stream, pool_k);
       break;
     case MPK_SUBSTRATE_TERRITORY:
-      launch_one<TerritoryTables, stepk::TerritorySites>(t, s->tr, args, out_a, out_w, p, stream);
+      launch_one<TerritoryTables, stepk::TerritorySites>(t, s->tr, args, out_a, out_w, p, stream, pool_k);
       break;
     case MPK_SUBSTRATE_COINS:
-      launch_one<CoinsTables, stepk::CoinsSites>(t, s->co, args, out_a, out_w, p, stream);
+      launch_one<CoinsTables, stepk::CoinsSites>(t, s->co, args, out_a, out_w, p, stream, pool_k);
       break;
     case MPK_SUBSTRATE_THE_MATRIX:
-      launch_one<MatrixTables, stepk::MatrixSites>(t, s->mx, args, out_a, out_w, p, stream);
+      launch_one<MatrixTables, stepk::MatrixSites>(t, s->mx, args, out_a, out_w, p, stream, pool_k);
       break;
     case MPK_SUBSTRATE_COOP_MINING:
-      launch_one<CoopTables, stepk::CoopSites>(t, s->cm, args, out_a, out_w, p, stream);
+      launch_one<CoopTables, stepk::CoopSites>(t, s->cm, args, out_a, out_w, p, stream, pool_k);
       break;
     case MPK_SUBSTRATE_GIFT_REFINEMENTS:
-      launch_one<GiftTables, stepk::GiftSites>(t, s->gr, args, out_a, out_w, p, stream);
+      launch_one<GiftTables, stepk::GiftSites>(t, s->gr, args, out_a, out_w, p, stream, pool_k);
       break;
     case MPK_SUBSTRATE_COLLABORATIVE_COOKING:
-      launch_one<CookTables, stepk::CookSites>(t, s->cc, args, out_a, out_w, p, stream);
+      launch_one<CookTables, stepk::CookSites>(t, s->cc, args, out_a, out_w, p, stream, pool_k);
       break;
     case MPK_SUBSTRATE_EXTERNALITY_MUSHROOMS:
-      launch_one<MushroomTables, stepk::MushroomSites>(t, s->em, args, out_a, out_w, p, stream);
+      launch_one<MushroomTables, stepk::MushroomSites>(t, s->em, args, out_a, out_w, p, stream, pool_k);
       break;
   }
 #endif

@@ -32,8 +32,9 @@ void launch_layer_view(const DevTables& t, const uint8_t* state, int32_t* out, i
 constexpr int kFaultWords = 64 + 4 * 16 * 64 * 2;   // fault words + the timeline build's log
 // views: 0 = per-agent RGB, 1 = WORLD.RGB, 2 = both in one launch
 FramePlan plan_frame(const DevTables& t, const SubstrateTables& s, int num_worlds,
-                     bool with_step, int views, int num_cus, const MpDevOptions* dev);
-int frame_lds_bytes(const DevTables& t, const FramePlan& p);
+                     bool with_step, int views, int num_cus, const MpDevOptions* dev,
+                     int pool_k = 1);   // pool_k: the per-agent view pooled by 2, 4, 8 (1: full)
+int frame_lds_bytes(const DevTables& t, const FramePlan& p, int pool_k = 1);
 int render_blob_bytes(const DevTables& t);
 int prepare_frame();
 void build_render_blob(const DevTables& t, const uint8_t* images, const uint16_t* img_slot,
@@ -43,7 +44,8 @@ void build_render_blob(const DevTables& t, const uint8_t* images, const uint16_t
                        uint8_t* blob);
 uint32_t render_visible_layers(const DevTables& t, const uint8_t* blob, const int32_t* state_layer);
 void launch_frame(const DevTables& t, const SubstrateTables* s, const stepk::StepArgs& args,
-                  uint8_t* out_a, uint8_t* out_w, const FramePlan& p, hipStream_t stream);
+                  uint8_t* out_a, uint8_t* out_w, const FramePlan& p, hipStream_t stream,
+                  int pool_k = 1);
 
 namespace {
 
@@ -141,10 +143,37 @@ struct MpEngine {
   std::vector<FramePlan> ring_plan[3];   // [views]: the plan mp_tune kept for each slot (empty: plan[1][views])
   void point_ring(int slot, bool pixels_only = false) {
     for (int k = 0; k < MP_OBS_KINDS; ++k)
-      if (ring[k].base && (!pixels_only || k == MP_OBS_RGB || k == MP_OBS_WORLD_RGB))
+      if (ring[k].base && (!pixels_only || is_pixel_kind(k)))
         bound[k] = ring[k].base + (uint64_t)slot * ring[k].stride;
   }
-  bool ring_has_pixels() const { return ring[MP_OBS_RGB].base || ring[MP_OBS_WORLD_RGB].base; }
+  bool ring_has_pixels() const {
+    for (int k = 0; k < MP_OBS_KINDS; ++k)
+      if (ring[k].base && is_pixel_kind(k)) return true;
+    return false;
+  }
+  // The per-agent view: MP_OBS_RGB or one of the pooled kinds (at most one of them is bound,
+  // mp_bind_output) — what the frame launch draws into its out_a, pooled by pool_k()
+  static int pool_of(int kind) {
+    return kind == MP_OBS_RGB_POOL2 ? 2 : kind == MP_OBS_RGB_POOL4 ? 4 : kind == MP_OBS_RGB_POOL8 ? 8 : 1;
+  }
+  static bool is_pixel_kind(int kind) {
+    return kind == MP_OBS_RGB || kind == MP_OBS_WORLD_RGB || pool_of(kind) > 1;
+  }
+  int agent_kind() const {
+    for (int k : {MP_OBS_RGB_POOL2, MP_OBS_RGB_POOL4, MP_OBS_RGB_POOL8})
+      if (bound[k]) return k;
+    return MP_OBS_RGB;
+  }
+  uint8_t* agent_view() const { return (uint8_t*)bound[agent_kind()]; }
+  int pool_k() const { return pool_of(agent_kind()); }
+  // [k = 2, 4, 8][drawing only, stepping + drawing][agents, -, both]: the plans of the pooled views
+  // (pool_ok: the pack's pooled atlas and span staging fit the LDS beside a ring of records)
+  FramePlan pool_plan[3][2][3] = {};
+  bool pool_ok[3] = {};
+  static int pool_index(int k) { return k == 2 ? 0 : k == 4 ? 1 : 2; }
+  FramePlan& frame_plan(int stepping, int views, int k) {
+    return k > 1 ? pool_plan[pool_index(k)][stepping][views] : plan[stepping][views];
+  }
   int32_t* d_actions = nullptr;    // staging for mp_step_host
   int32_t* d_fields = nullptr;     // staging for mp_step_fields_host
   uint8_t* d_mask = nullptr;       // staging for mp_reset
@@ -477,12 +506,13 @@ int sync_and_check(MpEngine* e, const char* who) {
 }
 
 // Draw-only launch: the views of the records as they are.
-void draw(MpEngine* e, uint8_t* rgb, uint8_t* wrgb) {
+// (pool_k > 1: `rgb` is the per-agent view pooled by pool_k)
+void draw(MpEngine* e, uint8_t* rgb, uint8_t* wrgb, int pool_k = 1) {
   stepk::StepArgs args = {};
   args.state = e->d_state; args.num_worlds = e->N;
-  FramePlan p = e->plan[0][rgb && wrgb ? 2 : wrgb ? 1 : 0];
+  FramePlan p = e->frame_plan(0, rgb && wrgb ? 2 : wrgb ? 1 : 0, rgb ? pool_k : 1);
   p.parity = e->frame_launches++ & 1;
-  launch_frame(e->t, nullptr, args, rgb, wrgb, p, e->stream);
+  launch_frame(e->t, nullptr, args, rgb, wrgb, p, e->stream, rgb ? pool_k : 1);
 }
 
 int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask) {
@@ -497,19 +527,21 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask) {
   args.out = e->outputs();
   // One persistent launch steps the worlds and renders the bound views — one or
   // both — from the records while they are in LDS (frame.hip).
-  uint8_t* rgb = (uint8_t*)e->bound[MP_OBS_RGB];
+  // (the per-agent view is MP_OBS_RGB or a pooled kind: pool_k)
+  uint8_t* rgb = e->agent_view();
   uint8_t* wrgb = (uint8_t*)e->bound[MP_OBS_WORLD_RGB];
+  const int pk = rgb ? e->pool_k() : 1;
   const int views = rgb && wrgb ? 2 : wrgb ? 1 : 0;
   if ((!rgb && !wrgb) || !e->fuse(rgb == nullptr)) {
     launch_step(e->t, e->sub, args, e->stream);
-    if (rgb) draw(e, rgb, nullptr);
+    if (rgb) draw(e, rgb, nullptr, pk);
     if (wrgb) draw(e, nullptr, wrgb);
   } else {
     // (the plan follows the buffer: a ring remembers one per slot, mp_tune)
     FramePlan p = ringing && e->ring_plan[views].size() == (size_t)e->ring_slots
-                      ? e->ring_plan[views][(size_t)slot] : e->plan[1][views];
+                      ? e->ring_plan[views][(size_t)slot] : e->frame_plan(1, views, pk);
     p.parity = e->frame_launches++ & 1;
-    launch_frame(e->t, &e->sub, args, rgb, wrgb, p, e->stream);
+    launch_frame(e->t, &e->sub, args, rgb, wrgb, p, e->stream, pk);
   }
   // "N.LAYER", when bound: one more (small) launch on the stepped records
   if (e->bound[MP_OBS_LAYER])
@@ -550,6 +582,19 @@ int check_device_pointer(MpEngine* e, const void* ptr, const char* who) {
   return MP_OK;
 }
 
+// One per-agent view at a time: MP_OBS_RGB or one pooled kind (the frame launch draws one of them
+// beside WORLD.RGB); a pooled view's buffer is 16-byte aligned (its span is staged by lines).
+int check_agent_view(MpEngine* e, int kind, const void* ptr, const char* who) {
+  if (kind != MP_OBS_RGB && MpEngine::pool_of(kind) == 1) return MP_OK;
+  for (int k : {MP_OBS_RGB, MP_OBS_RGB_POOL2, MP_OBS_RGB_POOL4, MP_OBS_RGB_POOL8})
+    if (k != kind && e->bound[k])
+      return fail(MP_ERR_INVALID, "%s: kind %d is bound; one per-agent view (MP_OBS_RGB or one "
+                  "MP_OBS_RGB_POOL*) at a time — unbind it first", who, k);
+  if (MpEngine::pool_of(kind) > 1 && ((uintptr_t)ptr & 15) != 0)
+    return fail(MP_ERR_INVALID, "%s: a pooled view's buffer must be 16-byte aligned (%p)", who, ptr);
+  return MP_OK;
+}
+
 // mp_bind_output on a kind that was bound as a ring: the kind leaves the ring
 void drop_ring_kind(MpEngine* e, int kind) {
   if (!e->ring[kind].base) return;
@@ -576,6 +621,11 @@ uint64_t mp_obs_bytes(const MpEngine* e, MpObsKind kind) {
     case MP_OBS_RGB:
       return N * P * (e->t.vf + e->t.vb + 1) * S * (e->t.vl + e->t.vr + 1) * S * 3;
     case MP_OBS_WORLD_RGB: return N * e->t.H * S * e->t.W * S * 3;
+    case MP_OBS_RGB_POOL2: case MP_OBS_RGB_POOL4: case MP_OBS_RGB_POOL8: {
+      const uint64_t k = (uint64_t)MpEngine::pool_of(kind);
+      if (!e->pool_ok[MpEngine::pool_index((int)k)]) return 0;
+      return N * P * ((e->t.vf + e->t.vb + 1) * S / k) * ((e->t.vl + e->t.vr + 1) * S / k) * 3;
+    }
     case MP_OBS_REWARD: case MP_OBS_READY_TO_SHOOT: case MP_OBS_AUX0: return N * P * 8;
     case MP_OBS_STEP_TYPE: return N * 4;
     case MP_OBS_DISCOUNT: case MP_OBS_COLLECTIVE_REWARD: return N * 8;
@@ -1808,6 +1858,19 @@ static int create_impl(MpEngine* e, const void* pack, uint64_t pack_len,
       if (frame_lds_bytes(t, pl) > 160 * 1024)
         return fail(MP_ERR_PACK, "mp_create: renderer needs %d B of LDS", frame_lds_bytes(t, pl));
     }
+    // the pooled per-agent views (MP_OBS_RGB_POOL*): their plans, sized for the bytes they write;
+    // a pack whose pooled atlas does not fit beside a ring of records does not offer them
+    // (8 x 8 sprites only: the pooled image of a cell is 8/k pixels square)
+    for (int i = 0; i < 3; ++i) {
+      const int k = 2 << i;
+      e->pool_ok[i] = t.sprite_size == 8;
+      for (int v = 0; v < 6 && e->pool_ok[i]; ++v) {
+        if ((v >> 1) == 1) continue;   // (WORLD.RGB alone has no per-agent view)
+        FramePlan& pl = e->pool_plan[i][v & 1][v >> 1];
+        pl = plan_frame(t, e->sub, e->N, (v & 1) != 0, v >> 1, e->num_cus, dev, k);
+        if (frame_lds_bytes(t, pl, k) > 160 * 1024) e->pool_ok[i] = false;
+      }
+    }
     if (int rc = prepare_frame())
       return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) failed: %d", rc);
     if (dev && dev->verbose)
@@ -1851,16 +1914,16 @@ int mp_info(const MpEngine* e, MpInfo* out) {
   out->world_state_bytes = e->t.world_stride;
   // the launch form of a step with the views bound right now (the per-agent view
   // if none is)
-  out->fused = e->fuse(!e->bound[MP_OBS_RGB] && e->bound[MP_OBS_WORLD_RGB]) ? 1 : 0;
+  out->fused = e->fuse(!e->agent_view() && e->bound[MP_OBS_WORLD_RGB]) ? 1 : 0;
   out->num_resources = e->inventory_types();
   out->num_action_fields = e->t.nfields;
   {
-    const bool a = e->bound[MP_OBS_RGB] != nullptr, w = e->bound[MP_OBS_WORLD_RGB] != nullptr;
+    const bool a = e->agent_view() != nullptr, w = e->bound[MP_OBS_WORLD_RGB] != nullptr;
     const int views = a && w ? 2 : w ? 1 : 0;
     // (with a tuned ring: the plan of the slot the next submission writes)
     const FramePlan& p = e->ring_slots > 0 && e->ring_plan[views].size() == (size_t)e->ring_slots
                              ? e->ring_plan[views][(size_t)(e->ring_cursor % (uint64_t)e->ring_slots)]
-                             : e->plan[1][views];
+                             : const_cast<MpEngine*>(e)->frame_plan(1, views, a ? e->pool_k() : 1);
     out->plan_batch_worlds = p.B; out->plan_ring_batches = p.NB; out->plan_owned_batches = p.ks;
     out->plan_pooled_batches = p.pool; out->plan_groups = p.groups;
     out->plan_store_sc1 = p.store_sc1;
@@ -1898,7 +1961,13 @@ int mp_bind_output(MpEngine* e, MpObsKind kind, void* device_ptr) {
   if (device_ptr && mp_obs_bytes(e, kind) == 0)
     return fail(MP_ERR_UNSUPPORTED, "mp_bind_output: this substrate has no observation %d", (int)kind);
   if (device_ptr)
+    if (int rc = check_agent_view(e, kind, device_ptr, "mp_bind_output")) return rc;
+  if (device_ptr)
     if (int rc = check_device_pointer(e, device_ptr, "mp_bind_output")) return rc;
+  // (a ring's tuned plans were sized for the per-agent view bound then: full and pooled views
+  // lay LDS out differently, so a change of that kind drops them — mp_tune makes new ones)
+  if ((kind == MP_OBS_RGB || MpEngine::pool_of(kind) > 1) && e->bound[kind] != device_ptr)
+    for (auto& v : e->ring_plan) v.clear();
   e->bound[kind] = device_ptr;
   drop_ring_kind(e, kind);
   return MP_OK;
@@ -1920,6 +1989,7 @@ int mp_bind_output_ring(MpEngine* e, MpObsKind kind, void* base, uint64_t slot_s
     return fail(MP_ERR_INVALID, "mp_bind_output_ring: a slot stride of %llu bytes for an observation of %llu "
                 "(must hold it and be a multiple of 256)", (unsigned long long)slot_stride_bytes,
                 (unsigned long long)bytes);
+  if (int rc = check_agent_view(e, kind, base, "mp_bind_output_ring")) return rc;
   if (int rc = check_device_pointer(e, base, "mp_bind_output_ring")) return rc;
   if (int rc = check_device_pointer(e, (const char*)base + (uint64_t)(slots - 1) * slot_stride_bytes + bytes - 1,
                                     "mp_bind_output_ring (last byte of the last slot)")) return rc;
@@ -2037,6 +2107,14 @@ int mp_observe(MpEngine* e, MpObsKind kind, void* dst) {
       return MP_OK;
     case MP_OBS_WORLD_RGB:
       draw(e, nullptr, (uint8_t*)dst);
+      HIP_TRY(hipGetLastError());
+      return MP_OK;
+    case MP_OBS_RGB_POOL2: case MP_OBS_RGB_POOL4: case MP_OBS_RGB_POOL8:
+      if (mp_obs_bytes(e, kind) == 0)
+        return fail(MP_ERR_UNSUPPORTED, "mp_observe: this substrate has no observation %d", (int)kind);
+      if (((uintptr_t)dst & 15) != 0)
+        return fail(MP_ERR_INVALID, "mp_observe: a pooled view's buffer must be 16-byte aligned (%p)", dst);
+      draw(e, (uint8_t*)dst, nullptr, MpEngine::pool_of(kind));
       HIP_TRY(hipGetLastError());
       return MP_OK;
     case MP_OBS_LAYER:
@@ -2501,7 +2579,7 @@ struct ProbeState {
     }
     copied = true;
     for (int k = 0; k < MP_OBS_KINDS; ++k)
-      if (k != MP_OBS_RGB && k != MP_OBS_WORLD_RGB) { rebind[k] = e->bound[k]; e->bound[k] = nullptr; }
+      if (!MpEngine::is_pixel_kind(k)) { rebind[k] = e->bound[k]; e->bound[k] = nullptr; }
     return MP_OK;
   }
   int restore() {
@@ -2519,7 +2597,7 @@ struct ProbeState {
       const hipError_t r = hipStreamSynchronize(e->stream);
       if (first == hipSuccess) first = r;
       for (int k = 0; k < MP_OBS_KINDS; ++k)
-        if (k != MP_OBS_RGB && k != MP_OBS_WORLD_RGB) e->bound[k] = rebind[k];
+        if (!MpEngine::is_pixel_kind(k)) e->bound[k] = rebind[k];
       copied = false;
       if (first != hipSuccess) {
         (void)hipGetLastError();
@@ -2557,15 +2635,16 @@ static int tune_impl(MpEngine* e, double* us_per_launch, bool* stepped, bool qui
   if (us_per_launch) *us_per_launch = 0.0;
   // a ring: every slot is its own buffer (its own physical pages), the plan follows each
   const int slots = e->ring_slots > 0 && e->ring_has_pixels() ? e->ring_slots : 1;
-  uint8_t* rgb = (uint8_t*)e->bound[MP_OBS_RGB];
+  uint8_t* rgb = e->agent_view();
   uint8_t* wrgb = (uint8_t*)e->bound[MP_OBS_WORLD_RGB];
   if ((!rgb && !wrgb) || !e->fuse(rgb == nullptr)) return MP_OK;
   const int views = rgb && wrgb ? 2 : wrgb ? 1 : 0;
+  const int pk = rgb ? e->pool_k() : 1;   // (a pooled per-agent view has plans of its own)
   // (everything in flight finishes first: a tune between two steps sees whole records)
   if (int rc = sync_and_check(e, "mp_tune")) return rc;
-  FramePlan& plan = e->plan[1][views];
+  FramePlan& plan = e->frame_plan(1, views, pk);
   const FramePlan before = plan;
-  const FramePlan stock = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, nullptr);
+  const FramePlan stock = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, nullptr, pk);
   // the candidates: the stock plan; the same ring cut into single worlds; that with
   // half of every workgroup's share pooled; the stock plan with sc1 stores.  (Same
   // number of LDS record slots: the composite cache was sized for the stock plan.)
@@ -2581,8 +2660,8 @@ static int tune_impl(MpEngine* e, double* us_per_launch, bool* stepped, bool qui
       d.batch_worlds = 1;
       d.ring_batches = lds_slots;
       d.static_pct = pct;
-      const FramePlan p = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d);
-      if (frame_lds_bytes(e->t, p) <= frame_lds_bytes(e->t, stock) &&
+      const FramePlan p = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d, pk);
+      if (frame_lds_bytes(e->t, p, pk) <= frame_lds_bytes(e->t, stock, pk) &&
           (p.B != stock.B || p.NB != stock.NB || p.pool != stock.pool))
         cand.push_back(p);
     }
@@ -2596,13 +2675,13 @@ static int tune_impl(MpEngine* e, double* us_per_launch, bool* stepped, bool qui
       d.batch_worlds = 1;
       d.ring_batches = lds_slots;
       d.team = 1;
-      const FramePlan p = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d);
-      if (p.team && frame_lds_bytes(e->t, p) <= frame_lds_bytes(e->t, stock)) {
+      const FramePlan p = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d, pk);
+      if (p.team && frame_lds_bytes(e->t, p, pk) <= frame_lds_bytes(e->t, stock, pk)) {
         cand.push_back(p);
         if (!quick && views != 1 && stock.feeders >= 4) {   // ... and with half the feeders (see below)
           d.feeders = stock.feeders / 2;
-          const FramePlan h = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d);
-          if (h.team && h.feeders != p.feeders && frame_lds_bytes(e->t, h) <= frame_lds_bytes(e->t, stock))
+          const FramePlan h = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d, pk);
+          if (h.team && h.feeders != p.feeders && frame_lds_bytes(e->t, h, pk) <= frame_lds_bytes(e->t, stock, pk))
             cand.push_back(h);
         }
       }
@@ -2626,8 +2705,8 @@ static int tune_impl(MpEngine* e, double* us_per_launch, bool* stepped, bool qui
       d.struct_size = sizeof d;
       d.max_composites = -1;
       d.feeders = stock.feeders / 2;
-      const FramePlan p = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d);
-      if (frame_lds_bytes(e->t, p) <= frame_lds_bytes(e->t, stock) && p.feeders != stock.feeders)
+      const FramePlan p = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d, pk);
+      if (frame_lds_bytes(e->t, p, pk) <= frame_lds_bytes(e->t, stock, pk) && p.feeders != stock.feeders)
         cand.push_back(p);
     }
   }
@@ -2762,7 +2841,7 @@ int mp_place_output(MpEngine* e, MpObsKind kind, int32_t candidates, uint64_t ma
   if (!e || !device_ptr) return fail(MP_ERR_INVALID, "mp_place_output: NULL argument");
   *device_ptr = nullptr;
   if (report) memset(report, 0, sizeof *report);
-  if (kind != MP_OBS_RGB && kind != MP_OBS_WORLD_RGB)
+  if (!MpEngine::is_pixel_kind(kind))
     return fail(MP_ERR_INVALID, "mp_place_output: kind %d is not a pixel view", (int)kind);
   if (e->ring[kind].base)
     return fail(MP_ERR_INVALID, "mp_place_output: kind %d is bound as a ring; unbind it first", (int)kind);

@@ -46,6 +46,29 @@ OBS_MATRIX_CUMULANTS = 19
 # *_in_the_matrix: f64 [N, P, 2], (row_reward, col_reward) of the latest interaction of
 # player p — the rest of the 'interaction' event's payload (include/mp_engine.h)
 OBS_INTERACTION_REWARDS = 20
+# "N.RGB" pooled by k = 2, 4, 8 (k x k box average, rounded half up: `pool_rgb`), u8
+# [N, P, VH * S / k, VW * S / k, 3]; drawn by the frame launch itself, the full image is never
+# written.  One per-agent view (OBS_RGB or one pooled kind) can be bound at a time.
+OBS_RGB_POOL2 = 21
+OBS_RGB_POOL4 = 22
+OBS_RGB_POOL8 = 23
+OBS_RGB_POOL = {2: OBS_RGB_POOL2, 4: OBS_RGB_POOL4, 8: OBS_RGB_POOL8}
+# the pixel views (placed / tuned like one another when large)
+PIXEL_KINDS = (OBS_RGB, OBS_WORLD_RGB, OBS_RGB_POOL2, OBS_RGB_POOL4, OBS_RGB_POOL8)
+
+
+def pool_rgb(images, k: int) -> np.ndarray:
+  """What OBS_RGB_POOL<k> holds for full images `images` (u8 [..., H, W, 3], H and W
+  multiples of k): every byte the k x k block average of the full image, rounded half up —
+  (sum + k*k // 2) // (k*k), the rule lower._fit applies to sprite art."""
+  a = np.asarray(images)
+  if k == 1:
+    return a.astype(np.uint8, copy=True)
+  *lead, h, w, c = a.shape
+  if h % k or w % k:
+    raise ValueError(f"an image of {h} x {w} does not pool by {k}")
+  s = a.astype(np.uint32).reshape(*lead, h // k, k, w // k, k, c).sum(axis=(-4, -2))
+  return ((s + (k * k) // 2) // (k * k)).astype(np.uint8)
 
 
 def matrix_cumulant_names(num_resources: int):
@@ -367,6 +390,8 @@ class Engine:
         OBS_INTERACTION_INVENTORIES: ((self.N, self.P, 2, info.num_resources), torch.float64),
         OBS_MATRIX_CUMULANTS: ((self.N, self.P, 1 + 3 * info.num_resources), torch.float64),
         OBS_INTERACTION_REWARDS: ((self.N, self.P, 2), torch.float64),
+        **{kind: ((self.N, self.P, info.view_h * S // k, info.view_w * S // k, 3), torch.uint8)
+           for k, kind in OBS_RGB_POOL.items()},
     }
     self._bound: Dict[int, "torch.Tensor"] = {}
 
@@ -567,7 +592,7 @@ class Engine:
     `self.placements` <= 1).  A large pixel view the caller brings gets the launch
     plan tuned to it (mp_tune: a few dry launches)."""
     shape, dtype = self.shapes[kind]
-    big = (kind in (OBS_RGB, OBS_WORLD_RGB) and
+    big = (kind in PIXEL_KINDS and
            int(np.prod(shape)) >= self.PLACE_MIN_BYTES)
     if tensor is None:
       if big and self.placements > 1:
@@ -621,7 +646,7 @@ class Engine:
     _check(self._L, self._L.mp_bind_output_ring(self._h, kind, tensor.data_ptr(), stride,
                                                 tensor.shape[0]), "mp_bind_output_ring")
     self._bound[kind] = tensor
-    big = kind in (OBS_RGB, OBS_WORLD_RGB) and int(np.prod(shape)) >= self.PLACE_MIN_BYTES
+    big = kind in PIXEL_KINDS and int(np.prod(shape)) >= self.PLACE_MIN_BYTES
     if tune and big and self.placements > 0:
       _check(self._L, self._L.mp_tune(self._h, None), "mp_tune")
     return tensor
@@ -634,7 +659,7 @@ class Engine:
     t = self._torch
     item = t.empty((), dtype=dtype).element_size()
     n = int(np.prod(shape))
-    if (kind in (OBS_RGB, OBS_WORLD_RGB) and n * item >= self.PLACE_MIN_BYTES and
+    if (kind in PIXEL_KINDS and n * item >= self.PLACE_MIN_BYTES and
         self.placements > 0 and (n * item) % 256 == 0):
       # a large pixel view: scattered 2 MB chunks, like a placed single buffer — the frame
       # launch writes those evenly; an ordinary allocation is physically contiguous in large

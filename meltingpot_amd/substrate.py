@@ -596,7 +596,8 @@ class Substrate:
                auto_reset: bool = True, world_offset: int = 0,
                debug_observations: bool = False,
                action_table: Optional[Sequence[Mapping[str, int]]] = None,
-               rollout_length: int = 0, check_device_actions: bool = False):
+               rollout_length: int = 0, check_device_actions: bool = False,
+               rgb_pool: int = 1):
     """`action_table`: the discrete actions, as in the reference's
     `build_substrate(..., action_table)` (utils/substrates/substrate.py:107-139,
     discrete_action_wrapper.py:77-109): row i is what discrete action i does,
@@ -612,7 +613,16 @@ class Substrate:
     (wrappers/multiplayer_wrapper.py:108-118, substrate.py:74-81) and a rollout just
     stores them; here submission t (every reset() and step()) writes slot t % T of
     [T, N, ...] tensors, the returned `RolloutTimeStep` holds views of its slot
-    (`.slot`), and nothing is cloned, synchronised or re-tuned between steps."""
+    (`.slot`), and nothing is cloned, synchronised or re-tuned between steps.
+
+    `rgb_pool` = k in (2, 4, 8): "RGB" is the player's view cut down by k with an area filter
+    (k x k box average, rounded half up: `engine.pool_rgb`), e.g. (11, 11, 3) for an 88 x 88 view
+    at k = 8, in the observations and in `observation_spec()`.  The engine draws the pooled
+    view itself (MP_OBS_RGB_POOL<k>): the full image is never written.  1 (default): the full
+    view."""
+    if rgb_pool not in (1, 2, 4, 8) or isinstance(rgb_pool, bool):
+      raise ValueError(f"rgb_pool must be 1, 2, 4 or 8, got {rgb_pool!r}")
+    self._rgb_pool = int(rgb_pool)
     invalid = set(roles) - config.valid_roles  # configs/substrates/__init__.py:42-45
     if invalid:
       raise ValueError(f"Invalid roles: {invalid!r}. Must be one of "
@@ -653,7 +663,7 @@ class Substrate:
       names, ranges = action_fields(self._eng)
       self._action_rows = validate_action_table(action_table, names, ranges)
     E = engine_lib
-    self._kinds = {"RGB": E.OBS_RGB, "WORLD.RGB": E.OBS_WORLD_RGB,
+    self._kinds = {"RGB": E.OBS_RGB_POOL.get(self._rgb_pool, E.OBS_RGB), "WORLD.RGB": E.OBS_WORLD_RGB,
                    "READY_TO_SHOOT": E.OBS_READY_TO_SHOOT,
                    "COLLECTIVE_REWARD": E.OBS_COLLECTIVE_REWARD,
                    "INVENTORY": E.OBS_INVENTORY,
@@ -836,6 +846,9 @@ class Substrate:
   def observation_spec(self) -> List[Mapping[str, Array]]:
     spec = dict(self._config.timestep_spec)
     spec["COLLECTIVE_REWARD"] = Array((), np.float64, "COLLECTIVE_REWARD")
+    if self._rgb_pool > 1 and "RGB" in spec:
+      h, w, c = spec["RGB"].shape
+      spec["RGB"] = Array((h // self._rgb_pool, w // self._rgb_pool, c), spec["RGB"].dtype, "RGB")
     return [dict(spec) for _ in self._roles]
 
   def action_spec(self) -> List[DiscreteArray]:
