@@ -299,6 +299,7 @@ const char* mp_last_error(void);
  * dmlab2d.Environment(env, names, seed) (builder.py:182-187) and Lua api:init
  * (api_factory.lua:53-67).  `pack` is an MPK1 blob (include/mp_pack.h): the
  * lowered form of the settings dict the reference passes to builder.builder().
+ * A malformed pack is refused with MP_ERR_PACK before any device call.
  * All worlds start un-reset; call mp_reset before the first mp_step. */
 int mp_create(const void* pack, uint64_t pack_len, const MpConfig* cfg,
               MpEngine** out);

@@ -5,7 +5,6 @@
 // wrappers/base.py:38-84).  No CPU execution path exists here: every call that
 // would compute needs a HIP device and fails loudly without one.
 #include <chrono>
-#include <functional>
 #include <map>
 #include <mutex>
 #include "../../include/mp_engine.h"
@@ -19,9 +18,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/mp_pack.h"
+#include "pack_decode.h"
 #include "step_common.h"
-#include "step_matrix.h"   // MxPlayer (record layout)
 
 void launch_step(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
                  hipStream_t stream);
@@ -47,8 +45,6 @@ void launch_frame(const DevTables& t, const SubstrateTables* s, const stepk::Ste
                   uint8_t* out_a, uint8_t* out_w, const FramePlan& p, hipStream_t stream,
                   int pool_k = 1);
 
-namespace {
-
 thread_local std::string g_error;
 
 int fail(int code, const char* fmt, ...) {
@@ -68,36 +64,6 @@ int fail(int code, const char* fmt, ...) {
       return fail(MP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
-template <class T> struct MpkType;
-template <> struct MpkType<uint8_t> { static constexpr uint32_t code = MPK_U8; };
-template <> struct MpkType<char> { static constexpr uint32_t code = MPK_U8; };
-template <> struct MpkType<int32_t> { static constexpr uint32_t code = MPK_I32; };
-template <> struct MpkType<double> { static constexpr uint32_t code = MPK_F64; };
-template <> struct MpkType<uint64_t> { static constexpr uint32_t code = MPK_U64; };
-template <> struct MpkType<uint32_t> { static constexpr uint32_t code = MPK_U32; };
-
-// Table `name` of element type T (NULL if absent or of another type); payloads
-// are 16-byte aligned (mpk_validate), so int4 / uint4 reads of them are legal.
-template <class T>
-const T* table(const void* pack, const char* name, uint64_t* count = nullptr) {
-  return static_cast<const T*>(mpk_require(pack, name, MpkType<T>::code, 0, count));
-}
-
-// ... with at least `min_count` elements.
-template <class T>
-const T* table_n(const void* pack, const char* name, uint64_t min_count) {
-  return static_cast<const T*>(mpk_require(pack, name, MpkType<T>::code, min_count, nullptr));
-}
-
-// Every value of `v[0, n)` lies in [lo, hi).
-bool in_range(const int32_t* v, uint64_t n, int64_t lo, int64_t hi) {
-  for (uint64_t i = 0; i < n; ++i)
-    if (v[i] < lo || v[i] >= hi) return false;
-  return true;
-}
-
-}  // namespace
-
 struct MpEngine {
   int device = 0;
   int N = 0;
@@ -106,15 +72,6 @@ struct MpEngine {
   int substrate = 0;
   DevTables t{};
   SubstrateTables sub{};
-  CleanUpTables& cu = sub.cu;
-  CommonsTables& ch = sub.ch;
-  TerritoryTables& tr = sub.tr;
-  CoinsTables& co = sub.co;
-  MatrixTables& mx = sub.mx;
-  CoopTables& cm = sub.cm;
-  GiftTables& gr = sub.gr;
-  CookTables& cc = sub.cc;
-  MushroomTables& em = sub.em;
   // resource / token classes of "N.INVENTORY" (0: the level has no such observation)
   int inventory_types() const {
     return substrate == MPK_SUBSTRATE_THE_MATRIX ? sub.mx.R
@@ -203,13 +160,6 @@ struct MpEngine {
     return unfused != 1;
   }
   uint8_t* d_atlas = nullptr;      // de-duplicated atlas + image slots
-  int nhits = 0;
-
-  template <class T>
-  const T* dev(const void* host_table) const {
-    return reinterpret_cast<const T*>(
-        d_pack + (static_cast<const uint8_t*>(host_table) - pack.data()));
-  }
   StepOutputs outputs() const {
     StepOutputs o = own;
     if (bound[MP_OBS_REWARD]) o.reward = (double*)bound[MP_OBS_REWARD];
@@ -310,178 +260,6 @@ __global__ void k_sum_counters(const uint8_t* state, int stride, int grid_pad, i
     for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_xor(acc[k], off);
     if ((threadIdx.x & 63) == 0 && acc[k]) atomicAdd(&out[k], acc[k]);
   }
-}
-
-int find_name(const void* pack, const char* table_name, const char* want) {
-  uint64_t n = 0;
-  const char* names = table<char>(pack, table_name, &n);
-  int idx = 0;
-  for (uint64_t i = 0; i < n; ++idx) {
-    if (strcmp(names + i, want) == 0) return idx;
-    i += strlen(names + i) + 1;
-  }
-  return -1;
-}
-
-// Every table the engine dereferences: present, of the right type, long enough,
-// its indices in range — a truncated or stale pack is MP_ERR_PACK, never a wild
-// pointer.  Host-only: runs before a device is touched.
-int check_pack_tables(const void* hp, const int32_t* hdr) {
-  {
-    const int H = hdr[MPK_HDR_H], W = hdr[MPK_HDR_W], L = hdr[MPK_HDR_L];
-    const int HW = H * W, NS = hdr[MPK_HDR_NSTATES], NSP = hdr[MPK_HDR_NSPRITES], PP = hdr[MPK_HDR_P];
-    const int nobj = hdr[MPK_HDR_NOBJ], nhits = hdr[MPK_HDR_NHITS], nact = hdr[MPK_HDR_NACT];
-    const int vl = hdr[MPK_HDR_VL], vr = hdr[MPK_HDR_VR], vf = hdr[MPK_HDR_VF], vb = hdr[MPK_HDR_VB];
-    const int topology = hdr[MPK_HDR_TOPOLOGY], avatar_layer = hdr[MPK_HDR_AVATAR_LAYER];
-    const int nf = hdr[MPK_HDR_NFIELDS];
-    const int32_t* as = nf >= 1 && nf <= 4 ? table_n<int32_t>(hp, "action_spec", 3 * (uint64_t)nf)
-                                           : nullptr;
-    if (!as || !table<char>(hp, "action_names"))
-      return fail(MP_ERR_PACK, "mp_create: the pack has no action_spec / action_names "
-                               "(re-lower it with tools/make_packs.py)");
-    for (int a = 0; a < nf; ++a)
-      // (field 3 travels in six unsigned bits of the packed row: mp_step_fields)
-      if (as[3 * a] < (a == 3 ? 0 : -128) || as[3 * a] > as[3 * a + 2] ||
-          as[3 * a + 2] > as[3 * a + 1] || as[3 * a + 1] > (a == 3 ? 63 : 127))
-        return fail(MP_ERR_PACK, "mp_create: action_spec field %d out of range", a);
-    if (NS < 1 || NSP < 2 || nhits < 0 || nobj < 1 || hdr[MPK_HDR_MAXFRAMES] < 1 ||
-        avatar_layer < 0 || avatar_layer >= L || vl < 0 || vr < 0 || vf < 0 ||
-        vb < 0 || (vl + vr + 1) > 64 || (vf + vb + 1) > 64 ||
-        (topology != 0 && topology != 1))
-      return fail(MP_ERR_PACK, "mp_create: header fields out of range");
-    {
-      const int reach = std::max(std::max(vl, vr), std::max(vf, vb));
-      if (topology == 1 && (reach > H || reach > W))   // the renderer wraps a coordinate once
-        return fail(MP_ERR_PACK, "mp_create: a TORUS map smaller than the view's reach");
-    }
-    const uint8_t* ig = table_n<uint8_t>(hp, "init_grid", (uint64_t)L * HW);
-    const int32_t* sl = table_n<int32_t>(hp, "state_layer", NS);
-    const int32_t* ss = table_n<int32_t>(hp, "state_sprite", NS);
-    const int32_t* so = table_n<int32_t>(hp, "state_orient", NS);
-    const uint32_t* sg = table_n<uint32_t>(hp, "state_groups", NS);
-    const uint32_t* hb = table_n<uint32_t>(hp, "state_hit_block", NS);
-    const int32_t* al = table_n<int32_t>(hp, "avatar_alive_state", PP);
-    const int32_t* wa = table_n<int32_t>(hp, "avatar_wait_state", PP);
-    const int32_t* at = table_n<int32_t>(hp, "action_table", (uint64_t)nact * 4);
-    const int32_t* hs = table_n<int32_t>(hp, "hit_state", nhits);
-    const int32_t* hd = table_n<int32_t>(hp, "hit_state_dir", (uint64_t)nhits * 4);
-    const uint8_t* rgba = table_n<uint8_t>(hp, "sprite_rgba", (uint64_t)NSP * 4 * 256);
-    const int32_t* sf = table_n<int32_t>(hp, "sprite_flags", NSP);
-    const int32_t* vm = table_n<int32_t>(hp, "view_sprite_map", (uint64_t)(PP + 1) * NSP);
-    const int32_t* ob = table_n<int32_t>(hp, "objects", (uint64_t)nobj * 4);
-    uint64_t nsc = 0;
-    const int32_t* sc = table<int32_t>(hp, "spawn_cells", &nsc);
-    if (!ig || !sl || !ss || !so || !sg || !hb || !al || !wa || !at || !hs || !hd || !rgba ||
-        !sf || !vm || !ob || !sc || !table<char>(hp, "state_names") || !table<char>(hp, "hit_names"))
-      return fail(MP_ERR_PACK, "mp_create: a table of the pack is missing, mistyped or too short "
-                               "(re-lower it with tools/make_packs.py)");
-    bool ok = in_range(sl, NS, -1, L) && in_range(ss, NS, -1, NSP) && in_range(so, NS, 0, 4) &&
-              in_range(al, PP, 1, NS) && in_range(wa, PP, 1, NS) &&
-              in_range(at, (uint64_t)nact * 4, -4, 5) && in_range(hs, nhits, 1, NS) &&
-              in_range(hd, (uint64_t)nhits * 4, 1, NS) &&
-              in_range(vm, (uint64_t)(PP + 1) * NSP, 0, NSP) && in_range(sc, nsc, 0, HW);
-    for (uint64_t i = 0; ok && i < (uint64_t)L * HW; ++i) ok = ig[i] < NS;
-    for (int i = 0; ok && i < nobj; ++i)
-      ok = ob[4 * i + 1] >= 0 && ob[4 * i + 1] < W && ob[4 * i + 2] >= 0 && ob[4 * i + 2] < H &&
-           ob[4 * i + 3] >= 1 && ob[4 * i + 3] < NS;
-    if (!ok) return fail(MP_ERR_PACK, "mp_create: a table of the pack holds an index out of range");
-
-    // the level's own tables: presence, type, length; cell lists inside the map
-    struct Need { const char* name; uint32_t dtype; uint64_t min_count; };
-    struct Cells { const char* name; uint64_t max_count; };
-    std::vector<Need> need = {{"init_spawn_cells", MPK_I32, 1}, {"init_spawn_ptr", MPK_I32, 2},
-                              {"avatar_init_group", MPK_I32, (uint64_t)PP},
-                              {"init_spawn_mask", MPK_U32, 1}};
-    std::vector<Cells> cells;
-    const uint64_t P2 = (uint64_t)PP;
-    switch (hdr[MPK_HDR_SUBSTRATE]) {
-      case MPK_SUBSTRATE_CLEAN_UP:
-        need.insert(need.end(), {{"cu_states", MPK_I32, 8}, {"cu_i32", MPK_I32, 7},
-                                 {"cu_f64", MPK_F64, 6}, {"thr_misc", MPK_U64, 2},
-                                 {"apple_thr", MPK_U64, 1}, {"zapper_i32", MPK_I32, 5},
-                                 {"zapper_f64", MPK_F64, 2}});
-        cells = {{"apple_cells", 256}, {"dirt_cells", 256}, {"water_cells", 256}};
-        break;
-      case MPK_SUBSTRATE_COMMONS_HARVEST:
-        need.insert(need.end(), {{"ch_states", MPK_I32, 5}, {"ch_i32", MPK_I32, 4},
-                                 {"ch_f64", MPK_F64, 1}, {"ch_thr", MPK_U64, 2},
-                                 {"disc_offsets", MPK_I32, 2}, {"zapper_i32", MPK_I32, 5},
-                                 {"zapper_f64", MPK_F64, 2}});
-        cells = {{"apple_cells", 256}};
-        break;
-      case MPK_SUBSTRATE_TERRITORY:
-        need.insert(need.end(), {{"tr_states", MPK_I32, 10 + 2 * P2}, {"tr_i32", MPK_I32, 16},
-                                 {"tr_f64", MPK_F64, 8}, {"tr_thr", MPK_U64, 3},
-                                 {"tr_hits", MPK_I32, 1 + 2 * P2}, {"zapper_i32", MPK_I32, 5},
-                                 {"zapper_f64", MPK_F64, 2}});
-        cells = {{"resource_cells", 256}};
-        break;
-      case MPK_SUBSTRATE_COINS:
-        need.insert(need.end(), {{"co_states", MPK_I32, 3}, {"co_i32", MPK_I32, 4},
-                                 {"co_f64", MPK_F64, 8}, {"co_thr", MPK_U64, 2}});
-        cells = {{"coin_cells", 512}};
-        break;
-      case MPK_SUBSTRATE_COOP_MINING:
-        need.insert(need.end(), {{"cm_states", MPK_I32, 5}, {"cm_i32", MPK_I32, 10},
-                                 {"cm_f64", MPK_F64, 4 * P2}, {"cm_thr", MPK_U64, 3}});
-        cells = {{"ore_cells", 640}};
-        break;
-      case MPK_SUBSTRATE_COLLABORATIVE_COOKING:
-        need.insert(need.end(), {{"cc_inv_states", MPK_I32, 4}, {"cc_i32", MPK_I32, 3},
-                                 {"cc_f64", MPK_F64, 1}, {"cc_pot_states", MPK_I32, 5},
-                                 {"cc_bar_states", MPK_I32, 11}, {"cc_hits", MPK_I32, P2},
-                                 {"cc_state_kind", MPK_U8, (uint64_t)hdr[MPK_HDR_NSTATES]}});
-        cells = {{"cc_container_cells", 128}, {"cc_pot_cells", 64}, {"cc_receiver_cells", 64}};
-        break;
-      case MPK_SUBSTRATE_EXTERNALITY_MUSHROOMS:
-        need.insert(need.end(), {{"em_states", MPK_I32, 8}, {"em_i32", MPK_I32, 30},
-                                 {"em_f64", MPK_F64, 8}, {"em_thr", MPK_U64, 21},
-                                 {"zapper_i32", MPK_I32, 5}, {"zapper_f64", MPK_F64, 2}});
-        cells = {{"mushroom_cells", 256}};
-        break;
-      case MPK_SUBSTRATE_GIFT_REFINEMENTS:
-        need.insert(need.end(), {{"gr_states", MPK_I32, 2}, {"gr_i32", MPK_I32, 10},
-                                 {"gr_f64", MPK_F64, 2 * P2 + 3}, {"gr_thr", MPK_U64, 2}});
-        cells = {{"token_cells", 640}};
-        break;
-      case MPK_SUBSTRATE_THE_MATRIX: {
-        // the table lengths follow from R (resource classes) and the number of
-        // colour intervals, both in mx_i32
-        const int32_t* mi = nullptr;
-        if (!mpk_require(hp, "mx_i32", MPK_I32, 22, nullptr) ||
-            !(mi = table<int32_t>(hp, "mx_i32")) || mi[0] < 1 || mi[0] > 3 || mi[19] < 1 ||
-            mi[19] > 5 || mi[16] <= 0 || mi[18] < 1 || mi[18] > 3 || mi[21] < 0 || mi[21] >= nhits)
-          return fail(MP_ERR_PACK, "mp_create: table 'mx_i32' is missing or holds constants out of range");
-        const uint64_t R2 = (uint64_t)mi[0], NI = (uint64_t)mi[19];
-        need.insert(need.end(), {{"mx_states", MPK_I32, 8 + 2 * R2},
-                                 {"mx_f64", MPK_F64, 5 + 2 * R2 * R2 + 2 * NI},
-                                 {"mx_thr", MPK_U64, 2},
-                                 {"mx_player_i32", MPK_I32, 4 * P2},
-                                 {"mx_player_f64", MPK_F64, 4 * P2},
-                                 {"resource_class", MPK_I32, 1}});
-        cells = {{"resource_cells", 128}};
-        uint64_t ncl = 0, ncell = 0, nst = 0;
-        const int32_t* cls = table<int32_t>(hp, "resource_class", &ncl);
-        (void)table<int32_t>(hp, "resource_cells", &ncell);
-        const int32_t* st = table<int32_t>(hp, "mx_states", &nst);
-        if (!cls || ncl != ncell || !in_range(cls, ncl, 1, (int)R2 + 1))
-          return fail(MP_ERR_PACK, "mp_create: table 'resource_class' does not match 'resource_cells'");
-        if (!st || nst != 8 + 2 * R2 || !in_range(st, nst, 1, NS))
-          return fail(MP_ERR_PACK, "mp_create: table 'mx_states' holds a state out of range");
-        break;
-      }
-    }
-    for (const Need& nd : need)
-      if (!mpk_require(hp, nd.name, nd.dtype, nd.min_count, nullptr))
-        return fail(MP_ERR_PACK, "mp_create: table '%s' is missing, mistyped or too short", nd.name);
-    for (const Cells& cl : cells) {
-      uint64_t cnt = 0;
-      const int32_t* v = table<int32_t>(hp, cl.name, &cnt);
-      if (!v || cnt > cl.max_count || !in_range(v, cnt, 0, HW))
-        return fail(MP_ERR_PACK, "mp_create: table '%s' is missing, too long or leaves the map", cl.name);
-    }
-  }
-  return MP_OK;
 }
 
 // Waits for the engine's stream and reports a frame kernel that gave up on its
@@ -605,6 +383,411 @@ void drop_ring_kind(MpEngine* e, int kind) {
   if (!any) { e->ring_slots = 0; e->ring_cursor = 0; }
 }
 
+// ---- mp_create's device stage: runs on a pack decode_pack has accepted
+#define DEV_ALLOC(ptr, bytes) HIP_TRY(hipMalloc((void**)&(ptr), (bytes)))
+
+// The pack and its two derived blobs on the device; the tables: the pack decoded against it.
+int upload_pack(MpEngine* e, const MpConfig& cfg, DecodedPack* d) {
+  DEV_ALLOC(e->d_pack, e->pack.size());
+  if (int rc = decode_pack(e->pack, cfg, e->d_pack, d)) return rc;   // (the host copy's verdict)
+  HIP_TRY(hipMemcpy(e->d_pack, e->pack.data(), e->pack.size(), hipMemcpyHostToDevice));
+  DEV_ALLOC(e->d_extra, d->extra.size());
+  HIP_TRY(hipMemcpy(e->d_extra, d->extra.data(), d->extra.size(), hipMemcpyHostToDevice));
+  DEV_ALLOC(e->d_stepblob, d->step_blob.size());
+  HIP_TRY(hipMemcpy(e->d_stepblob, d->step_blob.data(), d->step_blob.size(), hipMemcpyHostToDevice));
+  e->t = d->t;
+  e->sub = d->sub;
+  e->substrate = d->sub.substrate;
+  e->t.sprite_flags8 = e->d_extra;
+  e->t.step_blob = e->d_stepblob;
+  return MP_OK;
+}
+
+// DevTables::fault in host memory (readable without a HIP call, i.e. while a kernel is stuck:
+// 64 fault words + the -DMP_FRAME_TIMELINE build's log); DevTables::claim (+ -DMP_FRAME_ENDS stamps).
+int alloc_fault_words(MpEngine* e) {
+  HIP_TRY(hipHostMalloc((void**)&e->h_fault, kFaultWords * sizeof(uint32_t), hipHostMallocMapped));
+  memset(e->h_fault, 0, kFaultWords * sizeof(uint32_t));
+  HIP_TRY(hipHostGetDevicePointer((void**)&e->t.fault, e->h_fault, 0));
+  DEV_ALLOC(e->d_claim, (2 + 2 * 1024) * sizeof(uint32_t));
+  HIP_TRY(hipMemset(e->d_claim, 0, (2 + 2 * 1024) * sizeof(uint32_t)));
+  e->t.claim = e->d_claim;
+  return MP_OK;
+}
+
+// The world records, zero but for their seeds.
+int init_state(MpEngine* e, const MpConfig& cfg) {
+  const DevTables& t = e->t;
+  const size_t state_bytes = (size_t)e->N * t.world_stride;
+  DEV_ALLOC(e->d_state, state_bytes);
+  std::vector<uint8_t> init(state_bytes, 0);
+  for (int w = 0; w < e->N; ++w) {
+    WorldTail* tail = reinterpret_cast<WorldTail*>(init.data() + (size_t)w * t.world_stride + t.grid_pad);
+    const uint64_t gw = cfg.world_offset + (uint64_t)w;
+    tail->seed = (cfg.base_seed || cfg.literal_base_seed) ? cfg.base_seed + gw
+                                                          : 0x9E3779B97F4A7C15ull * (gw + 1);
+  }
+  HIP_TRY(hipMemcpy(e->d_state, init.data(), state_bytes, hipMemcpyHostToDevice));
+  return MP_OK;
+}
+
+// The engine-owned outputs (scalars, debug observations) and the staging buffers.
+int alloc_outputs(MpEngine* e, const MpConfig& cfg) {
+  const DevTables& t = e->t;
+  const size_t NP = (size_t)e->N * t.P, N = (size_t)e->N;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+  const size_t o_reward = take(NP * 8), o_ready = take(NP * 8), o_aux = take(NP * 8),
+               o_disc = take(N * 8), o_coll = take(N * 8), o_type = take(N * 4),
+               o_pos = take(NP * 8), o_ori = take(NP * 4),
+               o_ev = take(N * MP_EVENT_ROWS * 16);
+  const bool matrix = e->substrate == MPK_SUBSTRATE_THE_MATRIX;
+  const size_t o_inv = take(NP * e->inventory_types() * 8),
+               o_int = take(matrix ? NP * 2 * e->sub.mx.R * 8 : 0),
+               o_irw = take(matrix ? NP * 2 * 8 : 0);
+  DEV_ALLOC(e->d_scalars, off);
+  e->scalars_bytes = off;
+  HIP_TRY(hipMemset(e->d_scalars, 0, off));
+  e->own.reward = (double*)(e->d_scalars + o_reward);
+  e->own.ready = (double*)(e->d_scalars + o_ready);
+  e->own.aux0 = (double*)(e->d_scalars + o_aux);
+  e->own.discount = (double*)(e->d_scalars + o_disc);
+  e->own.collective = (double*)(e->d_scalars + o_coll);
+  e->own.step_type = (int32_t*)(e->d_scalars + o_type);
+  e->own.position = (int32_t*)(e->d_scalars + o_pos);
+  e->own.orientation = (int32_t*)(e->d_scalars + o_ori);
+  e->own.events = (int32_t*)(e->d_scalars + o_ev);
+  if (e->inventory_types() > 0) e->own.inventory = (double*)(e->d_scalars + o_inv);
+  if (matrix) {
+    e->own.interaction = (double*)(e->d_scalars + o_int);
+    e->own.interaction_rewards = (double*)(e->d_scalars + o_irw);
+  }
+  if (cfg.debug_observations) {
+    size_t doff = 0;
+    auto dtake = [&](size_t bytes) { size_t o = doff; doff += (bytes + 255) & ~(size_t)255; return o; };
+    size_t o_dbg[4];
+    for (int k = 0; k < 4; ++k) o_dbg[k] = dtake(NP * 8);
+    const size_t o_zm = dtake(NP * t.P * 8);
+    const size_t o_cum = dtake(matrix ? NP * (1 + 3 * e->sub.mx.R) * 8 : 0);
+    DEV_ALLOC(e->d_debug, doff);
+    e->debug_bytes = doff;
+    HIP_TRY(hipMemset(e->d_debug, 0, doff));
+    if (mp_obs_bytes(e, MP_OBS_AUX1))   // (the substrates that have them: mp_obs_bytes)
+      for (int k = 0; k < 4; ++k) e->own.dbg[k] = (double*)(e->d_debug + o_dbg[k]);
+    if (mp_obs_bytes(e, MP_OBS_ZAP_MATRIX))
+      e->own.zap_matrix = (double*)(e->d_debug + o_zm);
+    if (matrix) e->own.cumulants = (double*)(e->d_debug + o_cum);
+  }
+  DEV_ALLOC(e->d_actions, NP * 4);
+  DEV_ALLOC(e->d_mask, N);
+  DEV_ALLOC(e->d_seeds, N * 8);
+  DEV_ALLOC(e->d_ctr, MP_CTR_COUNT * 8);
+  return MP_OK;
+}
+#undef DEV_ALLOC
+
+// The renderer's images: the de-duplicated sprite atlas (noRotate sprites and solid colours
+// have four identical facings), then the composite cache's and its (base, overlay) table.
+struct Atlas {
+  std::vector<uint8_t> images = std::vector<uint8_t>(256, 0);   // image 0: unused padding
+  std::vector<uint16_t> slots;                                  // (sprite, facing) -> image
+  std::vector<uint32_t> pair_table = std::vector<uint32_t>(kPairSlots, 0xffffffffu);
+  int count = 1, pair_probe = 0, n_composites = 0, used_slots = 0;
+
+  int add_image(const uint8_t* img, int from) {
+    for (int k = from; k < count; ++k)
+      if (memcmp(images.data() + (size_t)k * 256, img, 256) == 0) return k;
+    images.insert(images.end(), img, img + 256);
+    return count++;
+  }
+  void add_sprites(const uint8_t* rgba, const int32_t* flags, int nimg) {
+    slots.assign((size_t)nimg, 0);
+    for (int i = 0; i < nimg; ++i) {
+      uint8_t img[256];
+      memcpy(img, rgba + (size_t)i * 256, 256);
+      if (flags[i >> 2] & MPK_SPRITE_OPAQUE) {
+        // opaque images are only ever copied: store them pre-packed, 8 rows of
+        // 24 B RGB followed by 8 B of padding
+        uint8_t packed[256] = {0};
+        for (int py = 0; py < 8; ++py)
+          for (int px = 0; px < 8; ++px)
+            for (int ch = 0; ch < 3; ++ch)
+              packed[py * 32 + px * 3 + ch] = img[(py * 8 + px) * 4 + ch];
+        memcpy(img, packed, 256);
+      }
+      slots[(size_t)i] = (uint16_t)add_image(img, 1);
+    }
+  }
+  int lookup(uint32_t a, uint32_t b) const {
+    for (uint32_t h = pair_hash(a, b), k = 0; k < (uint32_t)kPairSlots; ++k) {
+      const uint32_t ent = pair_table[(h + k) & (kPairSlots - 1)];
+      if (ent == 0xffffffffu) return -1;
+      if ((ent >> 10) == ((a << 10) | b)) return (int)(ent & 1023u);
+    }
+    return -1;
+  }
+  void insert(uint32_t a, uint32_t b, uint32_t c) {
+    for (uint32_t h = pair_hash(a, b), k = 0; k < (uint32_t)kPairSlots; ++k) {
+      uint32_t& ent = pair_table[(h + k) & (kPairSlots - 1)];
+      if (ent == 0xffffffffu) {
+        ent = (a << 20) | (b << 10) | c;
+        if ((int)k + 1 > pair_probe) pair_probe = (int)k + 1;
+        return;
+      }
+    }
+  }
+  // one overlay image blended onto a packed opaque image, exactly as
+  // render.hip does it (A7: (s*a + d*(255-a) + 127) / 255; binary sprites
+  // replace where alpha > 0)
+  void blend(int base_img, int ov_img, bool partial, uint8_t* out) const {
+    memcpy(out, images.data() + (size_t)base_img * 256, 256);
+    const uint8_t* ov = images.data() + (size_t)ov_img * 256;
+    for (int py = 0; py < 8; ++py)
+      for (int px = 0; px < 8; ++px) {
+        const uint8_t* s = ov + (py * 8 + px) * 4;
+        uint8_t* d = out + py * 32 + px * 3;
+        const unsigned a = s[3];
+        for (int ch = 0; ch < 3; ++ch) {
+          if (partial) d[ch] = (uint8_t)((s[ch] * a + d[ch] * (255u - a) + 127u) / 255u);
+          else if (a) d[ch] = s[ch];
+        }
+      }
+  }
+};
+
+// An opaque look, then up to two non-opaque looks on higher layers; `cells` that can show it.
+struct Look { int layer, sprite, orient; };
+struct Stack { int n; Look l[3]; long cells; };
+
+Stack& count_stack(std::vector<Stack>& stacks, const Look* l, int n) {
+  for (auto& sk : stacks) {
+    bool eq = sk.n == n;
+    for (int k = 0; eq && k < n; ++k) eq = sk.l[k].sprite == l[k].sprite && sk.l[k].orient == l[k].orient;
+    if (eq) { sk.cells++; return sk; }
+  }
+  Stack sk; sk.n = n; sk.cells = 1;
+  for (int k = 0; k < n; ++k) sk.l[k] = l[k];
+  stacks.push_back(sk);
+  return stacks.back();
+}
+
+// Composite cache (render.hip phase 1): the (opaque base, overlay) stacks that the
+// map's static pieces can form — dirt on water, shadows on sand, claimed-resource
+// paint on its texture ... — so such cells become plain copies.  A piece's possible
+// looks are all sprite-bearing states of its prefab ("prefab.state" names); avatars,
+// their markings and beams move, so they are never part of a cached stack.
+std::vector<Stack> collect_stacks(const MpEngine* e, const int32_t* flags) {
+  const DevTables& t = e->t;
+  const void* hp = e->pack.data();
+  uint64_t names_len = 0;
+  const char* names = table<char>(hp, "state_names", &names_len);
+  const int32_t* objs = table<int32_t>(hp, "objects");
+  const int32_t* st_layer = table<int32_t>(hp, "state_layer");
+  const int32_t* st_sprite = table<int32_t>(hp, "state_sprite");
+  const int32_t* st_orient = table<int32_t>(hp, "state_orient");
+  const int nobj = table<int32_t>(hp, "hdr")[MPK_HDR_NOBJ];
+  std::vector<std::string> prefab((size_t)t.nstates);
+  for (uint64_t s = 0, off = 0; s < (uint64_t)t.nstates && off < names_len; ++s) {
+    const std::string nm(names + off);
+    off += nm.size() + 1;
+    prefab[s] = nm.substr(0, nm.find('.'));
+  }
+  std::vector<std::vector<Look>> cell_looks((size_t)t.H * t.W);
+  for (int i = 0; i < nobj; ++i) {
+    const int32_t* ob = objs + 4 * i;
+    if (ob[0] == MPK_KIND_SCENE || ob[0] == MPK_KIND_AVATAR || ob[0] == MPK_KIND_MARKING) continue;
+    for (int s = 1; s < t.nstates; ++s)
+      if (prefab[(size_t)s] == prefab[(size_t)ob[3]] && st_sprite[s] >= 0 && st_layer[s] >= 0)
+        cell_looks[(size_t)ob[2] * t.W + ob[1]].push_back({st_layer[s], st_sprite[s], st_orient[s]});
+  }
+  std::vector<Stack> stacks;
+  auto overlay = [&](const Look& l) { return !(flags[l.sprite] & (MPK_SPRITE_OPAQUE | MPK_SPRITE_EMPTY)); };
+  for (const auto& looks : cell_looks) {
+    // (sprite -1: no opaque piece below — the renderer starts from image 0,
+    // black; the *_in_the_matrix maps have no floor under their resources)
+    std::vector<Look> bases;
+    for (const Look& a : looks)
+      if (flags[a.sprite] & MPK_SPRITE_OPAQUE) bases.push_back(a);
+    if (bases.empty()) bases.push_back({-1, -1, 0});   // a cell no piece can cover
+    for (const Look& a : bases)
+      for (const Look& b : looks) {
+        if (b.layer <= a.layer || !overlay(b)) continue;
+        const Look ab[3] = {a, b, b};
+        count_stack(stacks, ab, 2);
+        for (const Look& c : looks) {
+          if (c.layer <= b.layer || !overlay(c)) continue;
+          const Look abc[3] = {a, b, c};
+          count_stack(stacks, abc, 3);
+        }
+      }
+  }
+  // stacks the lowering knows to be the common ones (territory: texture + wet +
+  // dry paint of the SAME player, 9 of 81 combinations): first in their class
+  uint64_t nh = 0;
+  const int32_t* hints = table<int32_t>(hp, "composite_hints", &nh);
+  for (uint64_t i = 0; hints && i + 2 < nh; i += 3) {
+    Look l[3]; int n = 0; bool ok = true;
+    for (int k = 0; k < 3; ++k) {
+      const int st = hints[i + k];
+      if (st == 0 && k > 0) break;
+      if (st <= 0 || st >= t.nstates || st_sprite[st] < 0 || st_layer[st] < 0) { ok = false; break; }
+      l[n++] = {st_layer[st], st_sprite[st], st_orient[st]};
+    }
+    if (!ok || n < 2 || !(flags[l[0].sprite] & MPK_SPRITE_OPAQUE)) continue;
+    for (int m = 2; m <= n; ++m) count_stack(stacks, l, m).cells = 1L << 40;
+  }
+  std::sort(stacks.begin(), stacks.end(), [](const Stack& x, const Stack& y) {
+    return x.n != y.n ? x.n < y.n : x.cells > y.cells;   // all pairs before triples
+  });
+  return stacks;
+}
+
+// The composite cache's images, most common stacks first, in the LDS the renderer's preferred
+// geometry leaves (more images must not cost worlds per workgroup: tools/sweep_env.sh).
+void fill_composites(MpEngine* e, const MpDevOptions* dev, const int32_t* flags,
+                     const std::vector<Stack>& stacks, Atlas& a) {
+  DevTables& t = e->t;
+  t.n_images = a.count;
+  int max_composites = kPairSlots;
+  for (int v = 0; v < 6; ++v) {
+    const FramePlan p0 = plan_frame(t, e->sub, e->N, (v & 1) != 0, v >> 1, e->num_cus, dev);
+    max_composites = std::min(max_composites, (160 * 1024 - frame_lds_bytes(t, p0)) / 272);
+  }
+  max_composites = std::max(0, std::min(max_composites, kPairSlots / 2));
+  if (dev && dev->max_composites >= 0) max_composites = std::min(max_composites, (int)dev->max_composites);
+  for (const Stack& sk : stacks)
+    for (int f = 0; f < 4; ++f) {
+      int base = sk.l[0].sprite < 0 ? 0 : a.slots[(size_t)sk.l[0].sprite * 4 + ((f + sk.l[0].orient) & 3)];
+      for (int k = 1; k < sk.n; ++k) {
+        const int ov = a.slots[(size_t)sk.l[k].sprite * 4 + ((f + sk.l[k].orient) & 3)];
+        int comp = a.lookup((uint32_t)base, (uint32_t)ov);
+        if (comp < 0) {
+          // (a triple extends a cached pair; it is skipped if its pair was)
+          if (k < sk.n - 1 || a.n_composites >= max_composites || a.used_slots >= kPairSlots / 2 ||
+              a.count >= 1023)
+            break;
+          uint8_t img[256];
+          a.blend(base, ov, (flags[sk.l[k].sprite] & MPK_SPRITE_PARTIAL) != 0, img);
+          const int before = a.count;
+          comp = a.add_image(img, 0);
+          a.n_composites += a.count - before;
+          a.insert((uint32_t)base, (uint32_t)ov, (uint32_t)comp);
+          ++a.used_slots;
+        }
+        base = comp;
+      }
+    }
+}
+
+// The renderer's atlas, composite cache and render blob.  (On the device side only
+// because the composite budget comes from plan_frame, which needs the CU count.)
+int build_atlas(MpEngine* e, const MpDevOptions* dev, const DecodedPack& d) {
+  DevTables& t = e->t;
+  const int32_t* flags = table<int32_t>(e->pack.data(), "sprite_flags");
+  Atlas a;
+  a.add_sprites(table<uint8_t>(e->pack.data(), "sprite_rgba"), flags, t.nsprites * 4);
+  t.scratch_cells = (dev && dev->scratch_cells > 0) ? dev->scratch_cells : 8;
+  if (!(dev && dev->no_composite_cache)) fill_composites(e, dev, flags, collect_stacks(e, flags), a);
+  if (a.count > 1023) return fail(MP_ERR_PACK, "mp_create: %d distinct sprite images", a.count);
+  t.n_images = a.count;
+  t.pair_probe = a.pair_probe;
+  // the atlas and the render blob (what every render workgroup stages besides its worlds,
+  // already in LDS layout), uploaded in one buffer
+  const void* hp = e->pack.data();
+  const int nimg = t.nsprites * 4;
+  const size_t img_bytes = (size_t)a.count * 256, slot_bytes = ((size_t)nimg * 2 + 15) & ~(size_t)15,
+               pair_bytes = (size_t)kPairSlots * 4, blob_bytes = (size_t)render_blob_bytes(t);
+  std::vector<uint8_t> flags8((size_t)t.nsprites);
+  for (int s = 0; s < t.nsprites; ++s)
+    flags8[(size_t)s] = (uint8_t)(((flags[s] & MPK_SPRITE_OPAQUE) ? 1 : 0) |
+                                  ((flags[s] & MPK_SPRITE_PARTIAL) ? 2 : 0) |
+                                  ((flags[s] & MPK_SPRITE_EMPTY) ? 4 : 0));
+  const int8_t* splayer = reinterpret_cast<const int8_t*>(d.extra.data() + 256);   // state -> player
+  // viewers 0 .. P-1, then the world view (row P_pack of the pack's table)
+  const int32_t* vmap = table<int32_t>(hp, "view_sprite_map");
+  std::vector<int32_t> vmap_p((size_t)(t.P + 1) * t.nsprites);
+  for (int v = 0; v <= t.P; ++v)
+    memcpy(vmap_p.data() + (size_t)v * t.nsprites,
+           vmap + (size_t)(v < t.P ? v : t.P_pack) * t.nsprites, (size_t)t.nsprites * 4);
+  std::vector<uint8_t> buf(img_bytes + slot_bytes + pair_bytes + blob_bytes, 0);
+  memcpy(buf.data(), a.images.data(), img_bytes);
+  memcpy(buf.data() + img_bytes, a.slots.data(), (size_t)nimg * 2);
+  memcpy(buf.data() + img_bytes + slot_bytes, a.pair_table.data(), pair_bytes);
+  uint8_t* blob = buf.data() + img_bytes + slot_bytes + pair_bytes;
+  build_render_blob(t, a.images.data(), a.slots.data(), a.pair_table.data(),
+                    table<int32_t>(hp, "state_sprite"), splayer, vmap_p.data(), flags8.data(),
+                    table<int32_t>(hp, "state_orient"), blob);
+  t.vis_layers = render_visible_layers(t, blob, table<int32_t>(hp, "state_layer"));
+  HIP_TRY(hipMalloc((void**)&e->d_atlas, buf.size()));
+  HIP_TRY(hipMemcpy(e->d_atlas, buf.data(), buf.size(), hipMemcpyHostToDevice));
+  t.atlas_compact = e->d_atlas;
+  t.img_slot = reinterpret_cast<const uint16_t*>(e->d_atlas + img_bytes);
+  t.pair_table = reinterpret_cast<const uint32_t*>(e->d_atlas + img_bytes + slot_bytes);
+  t.render_blob = e->d_atlas + img_bytes + slot_bytes + pair_bytes;
+  if (dev && dev->verbose)
+    fprintf(stderr, "mp_engine: composite cache: %d images, %d table entries, probe %d\n",
+            a.n_composites, a.used_slots, a.pair_probe);
+  return MP_OK;
+}
+
+// The frame launches' plans, plain and pooled.
+int plan_views(MpEngine* e, const MpDevOptions* dev) {
+  const DevTables& t = e->t;
+  for (int v = 0; v < 6; ++v) {
+    FramePlan& pl = e->plan[v & 1][v >> 1];
+    pl = plan_frame(t, e->sub, e->N, (v & 1) != 0, v >> 1, e->num_cus, dev);
+    // (the one refusal of a pack that needs the device: the plans follow its CU count)
+    if (frame_lds_bytes(t, pl) > 160 * 1024)
+      return fail(MP_ERR_PACK, "mp_create: renderer needs %d B of LDS", frame_lds_bytes(t, pl));
+  }
+  // the pooled per-agent views (MP_OBS_RGB_POOL*): their plans, sized for the bytes they write;
+  // a pack whose pooled atlas does not fit beside a ring of records does not offer them
+  // (8 x 8 sprites only: the pooled image of a cell is 8/k pixels square)
+  for (int i = 0; i < 3; ++i) {
+    const int k = 2 << i;
+    e->pool_ok[i] = t.sprite_size == 8;
+    for (int v = 0; v < 6 && e->pool_ok[i]; ++v) {
+      if ((v >> 1) == 1) continue;   // (WORLD.RGB alone has no per-agent view)
+      FramePlan& pl = e->pool_plan[i][v & 1][v >> 1];
+      pl = plan_frame(t, e->sub, e->N, (v & 1) != 0, v >> 1, e->num_cus, dev, k);
+      if (frame_lds_bytes(t, pl, k) > 160 * 1024) e->pool_ok[i] = false;
+    }
+  }
+  if (int rc = prepare_frame())
+    return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) failed: %d", rc);
+  if (dev && dev->verbose)
+    for (int v = 0; v < 6; ++v) {
+      const FramePlan& pl = e->plan[v & 1][v >> 1];
+      fprintf(stderr, "mp_engine: %d sprite images; frame plan %s, %s: %d buffers x %d worlds, %d of %d waves feed"
+              " (%d draw the world view), %d groups own %d batches each + %d pooled, %d B LDS\n",
+              t.n_images, (v & 1) ? "stepping + drawing" : "drawing",
+              (v >> 1) == 0 ? "agents view" : (v >> 1) == 1 ? "world view" : "both views",
+              pl.NB, pl.B, pl.feeders, pl.nwaves, pl.world_waves, pl.groups, pl.ks, pl.pool,
+              frame_lds_bytes(t, pl));
+    }
+  return MP_OK;
+}
+
+int create_on_device(MpEngine* e, const MpConfig& cfg, DecodedPack* d) {
+  const MpDevOptions* dev = cfg.dev;   // tests / tools only (include/mp_engine.h)
+  e->has_dev = dev != nullptr;
+  e->next_orders = !(dev && dev->no_next_orders);
+  e->device = cfg.device;
+  e->N = cfg.num_worlds;
+  e->auto_reset = cfg.auto_reset;
+  e->stream = (hipStream_t)cfg.stream;
+  e->unfused = cfg.unfused;   // 0 is resolved once the pack is read
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg.device) != hipSuccess ||
+      cus <= 0)
+    return fail(MP_ERR_NO_DEVICE, "mp_create: device %d does not report its compute units", cfg.device);
+  e->num_cus = cus;
+  int rc;
+  if ((rc = upload_pack(e, cfg, d)) || (rc = alloc_fault_words(e)) || (rc = init_state(e, cfg)) ||
+      (rc = alloc_outputs(e, cfg)) || (rc = build_atlas(e, dev, *d)))
+    return rc;
+  return plan_views(e, dev);
+}
 
 }  // namespace
 
@@ -651,9 +834,6 @@ uint64_t mp_obs_bytes(const MpEngine* e, MpObsKind kind) {
   }
 }
 
-static int create_impl(MpEngine* e, const void* pack, uint64_t pack_len,
-                       const MpConfig* cfg);
-
 int mp_create(const void* pack, uint64_t pack_len, const MpConfig* cfg,
               MpEngine** out) {
   if (!out) return fail(MP_ERR_INVALID, "mp_create: out is NULL");
@@ -664,32 +844,15 @@ int mp_create(const void* pack, uint64_t pack_len, const MpConfig* cfg,
     return fail(MP_ERR_INVALID, "mp_create: bad MpDevOptions (struct_size)");
   if (cfg->num_worlds <= 0)
     return fail(MP_ERR_INVALID, "mp_create: num_worlds must be positive");
-  if (mpk_validate(pack, pack_len) != 0)
-    return fail(MP_ERR_PACK, "mp_create: not a valid MPK1 pack");
-  const int32_t* hdr = table_n<int32_t>(pack, "hdr", MPK_HDR_LEN);
-  if (!hdr || hdr[MPK_HDR_VERSION] != 1)
-    return fail(MP_ERR_PACK, "mp_create: unsupported pack version");
-  if (hdr[MPK_HDR_SUBSTRATE] != MPK_SUBSTRATE_CLEAN_UP &&
-      hdr[MPK_HDR_SUBSTRATE] != MPK_SUBSTRATE_COMMONS_HARVEST &&
-      hdr[MPK_HDR_SUBSTRATE] != MPK_SUBSTRATE_TERRITORY &&
-      hdr[MPK_HDR_SUBSTRATE] != MPK_SUBSTRATE_COINS &&
-      hdr[MPK_HDR_SUBSTRATE] != MPK_SUBSTRATE_THE_MATRIX &&
-      hdr[MPK_HDR_SUBSTRATE] != MPK_SUBSTRATE_COOP_MINING &&
-      hdr[MPK_HDR_SUBSTRATE] != MPK_SUBSTRATE_GIFT_REFINEMENTS &&
-      hdr[MPK_HDR_SUBSTRATE] != MPK_SUBSTRATE_COLLABORATIVE_COOKING &&
-      hdr[MPK_HDR_SUBSTRATE] != MPK_SUBSTRATE_EXTERNALITY_MUSHROOMS)
-    return fail(MP_ERR_PACK, "mp_create: substrate %d is not supported by this build",
-                hdr[MPK_HDR_SUBSTRATE]);
-  if (hdr[MPK_HDR_P] > MP_MAX_PLAYERS || hdr[MPK_HDR_P] < 1 || hdr[MPK_HDR_SPRITE] != 8 ||
-      hdr[MPK_HDR_NSTATES] > 255 || hdr[MPK_HDR_NSPRITES] > 255 || hdr[MPK_HDR_NHITS] > 24 ||
-      hdr[MPK_HDR_H] < 1 || hdr[MPK_HDR_W] < 1 || hdr[MPK_HDR_H] * hdr[MPK_HDR_W] > 4096 ||
-      hdr[MPK_HDR_L] < 1 || hdr[MPK_HDR_NACT] < 1)
-    return fail(MP_ERR_PACK, "mp_create: pack exceeds engine limits");
-  if (cfg->num_players < 0 || cfg->num_players > hdr[MPK_HDR_P])
-    return fail(MP_ERR_INVALID, "mp_create: num_players %d, the pack holds %d avatars",
-                cfg->num_players, hdr[MPK_HDR_P]);
-
-  if (int rc = check_pack_tables(pack, hdr)) return rc;
+  if (cfg->unfused < 0 || cfg->unfused > 2)
+    return fail(MP_ERR_INVALID, "mp_create: MpConfig.unfused must be 0, 1 or 2 (got %d)", cfg->unfused);
+  // the whole pack is decoded and checked on the host (pack_decode.hip) before a device is touched
+  const int32_t* hdr = nullptr;
+  if (int rc = check_header(pack, pack_len, *cfg, &hdr)) return rc;
+  std::vector<uint8_t> copy((const uint8_t*)pack, (const uint8_t*)pack + pack_len);
+  if (int rc = apply_roles(copy, *cfg)) return rc;
+  DecodedPack d;
+  if (int rc = decode_pack(copy, *cfg, copy.data(), &d)) return rc;
 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -701,1189 +864,13 @@ int mp_create(const void* pack, uint64_t pack_len, const MpConfig* cfg,
   HIP_TRY(hipSetDevice(cfg->device));
 
   MpEngine* e = new MpEngine();
-  const int rc = create_impl(e, pack, pack_len, cfg);
+  e->pack = std::move(copy);
+  const int rc = create_on_device(e, *cfg, &d);
   if (rc != MP_OK) {
     mp_destroy(e);
     return rc;
   }
   *out = e;
-  return MP_OK;
-}
-
-static int create_impl(MpEngine* e, const void* pack, uint64_t pack_len,
-                       const MpConfig* cfg) {
-  const int32_t* hdr = nullptr;
-  const MpDevOptions* dev = cfg->dev;   // tests / tools only (include/mp_engine.h)
-  e->has_dev = dev != nullptr;
-  e->next_orders = !(dev && dev->no_next_orders);
-  e->device = cfg->device;
-  e->N = cfg->num_worlds;
-  e->auto_reset = cfg->auto_reset;
-  e->stream = (hipStream_t)cfg->stream;
-  if (cfg->unfused < 0 || cfg->unfused > 2)
-    return fail(MP_ERR_INVALID, "mp_create: MpConfig.unfused must be 0, 1 or 2 (got %d)", cfg->unfused);
-  e->unfused = cfg->unfused;   // 0 is resolved once the pack is read
-  {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) != hipSuccess ||
-        cus <= 0)
-      return fail(MP_ERR_NO_DEVICE, "mp_create: device %d does not report its compute units", cfg->device);
-    e->num_cus = cus;
-  }
-  e->pack.assign((const uint8_t*)pack, (const uint8_t*)pack + pack_len);
-  const void* hp = e->pack.data();
-  hdr = table<int32_t>(hp, "hdr");
-  e->substrate = hdr[MPK_HDR_SUBSTRATE];
-  e->sub.substrate = e->substrate;
-
-  DevTables& t = e->t;
-  t.H = hdr[MPK_HDR_H]; t.W = hdr[MPK_HDR_W]; t.L = hdr[MPK_HDR_L];
-  t.P_pack = hdr[MPK_HDR_P];
-  t.P = cfg->num_players > 0 ? cfg->num_players
-        : hdr[MPK_HDR_DEFAULT_P] > 0 && hdr[MPK_HDR_DEFAULT_P] <= t.P_pack ? hdr[MPK_HDR_DEFAULT_P]
-                                                                             : t.P_pack;
-  t.nstates = hdr[MPK_HDR_NSTATES];
-  t.nsprites = hdr[MPK_HDR_NSPRITES]; t.topology = hdr[MPK_HDR_TOPOLOGY];
-  t.max_frames = hdr[MPK_HDR_MAXFRAMES]; t.nact = hdr[MPK_HDR_NACT];
-  if (cfg->roles) {
-    // Per-player constants by role (bach_or_stravinsky: create_avatar_objects(roles),
-    // bach_or_stravinsky_in_the_matrix__repeated.py:473-497): the pack holds, per
-    // (role, player), the avatar's sprite and its row of mx_player_*; this engine's
-    // copy of the pack becomes the one lowered for the requested assignment
-    // (meltingpot_amd/lower.py: add_role_tables / apply_roles), before anything
-    // is derived from it.
-    uint64_t n_names = 0, n_rgba = 0, n_pi = 0, n_pf = 0;
-    const char* names = table<char>(hp, "role_names", &n_names);
-    const int32_t* sprite = table_n<int32_t>(hp, "role_sprite", t.P_pack);
-    const uint8_t* rgba = table<uint8_t>(hp, "role_rgba", &n_rgba);
-    const int32_t* rpi = table<int32_t>(hp, "role_player_i32", &n_pi);
-    const double* rpf = table<double>(hp, "role_player_f64", &n_pf);
-    int n_roles = 0;
-    for (uint64_t i = 0; names && i < n_names; ++i) n_roles += names[i] == 0;
-    const size_t block = (size_t)4 * hdr[MPK_HDR_SPRITE] * hdr[MPK_HDR_SPRITE] * 4;
-    const size_t PP = (size_t)t.P_pack;
-    uint64_t n_srgba = 0, n_mpi = 0, n_mpf = 0;
-    uint8_t* srgba = const_cast<uint8_t*>(table<uint8_t>(hp, "sprite_rgba", &n_srgba));
-    int32_t* mpi = const_cast<int32_t*>(table<int32_t>(hp, "mx_player_i32", &n_mpi));
-    double* mpf = const_cast<double*>(table<double>(hp, "mx_player_f64", &n_mpf));
-    if (n_roles < 1 || !sprite || !rgba || !rpi || !rpf || !srgba || !mpi || !mpf ||
-        n_rgba != n_roles * PP * block || n_pi != n_roles * PP * 4 || n_pf != n_roles * PP * 4 ||
-        n_mpi < PP * 4 || n_mpf < PP * 4 || !in_range(sprite, PP, 0, t.nsprites) ||
-        n_srgba < (size_t)t.nsprites * block)
-      return fail(MP_ERR_INVALID, "mp_create: MpConfig.roles given, but this substrate's pack holds "
-                                  "no per-role tables (its config has one valid role)");
-    for (int p = 0; p < t.P; ++p) {
-      const int r = cfg->roles[p];
-      if (r < 0 || r >= n_roles)
-        return fail(MP_ERR_INVALID, "mp_create: role %d of player %d is outside [0, %d)", r, p + 1,
-                    n_roles);
-      memcpy(srgba + (size_t)sprite[p] * block, rgba + ((size_t)r * PP + p) * block, block);
-      memcpy(mpi + 4 * p, rpi + ((size_t)r * PP + p) * 4, 4 * sizeof(int32_t));
-      memcpy(mpf + 4 * p, rpf + ((size_t)r * PP + p) * 4, 4 * sizeof(double));
-    }
-  }
-  {
-    // raw action fields (mp_step_fields): actionSpec (min, max, default) per field
-    const int32_t* spec = table_n<int32_t>(hp, "action_spec", 3 * (uint64_t)hdr[MPK_HDR_NFIELDS]);
-    t.nfields = hdr[MPK_HDR_NFIELDS];
-    t.field_lo = t.field_hi = 0;
-    for (int a = 0; a < t.nfields; ++a) {
-      t.field_lo |= ((uint32_t)spec[3 * a] & 255u) << (8 * a);
-      t.field_hi |= ((uint32_t)spec[3 * a + 1] & 255u) << (8 * a);
-    }
-  }
-  t.avatar_layer = hdr[MPK_HDR_AVATAR_LAYER]; t.sprite_size = hdr[MPK_HDR_SPRITE];
-  t.vl = hdr[MPK_HDR_VL]; t.vr = hdr[MPK_HDR_VR];
-  t.vf = hdr[MPK_HDR_VF]; t.vb = hdr[MPK_HDR_VB];
-  // territory keeps three per-cell resource planes behind the render planes, the
-  // matrix levels two and a block of per-player variables (step_matrix.h)
-  t.grid_planes = t.L + (hdr[MPK_HDR_SUBSTRATE] == MPK_SUBSTRATE_TERRITORY ? 3 : 0) +
-                  (hdr[MPK_HDR_SUBSTRATE] == MPK_SUBSTRATE_THE_MATRIX ? 2 : 0) +
-                  (hdr[MPK_HDR_SUBSTRATE] == MPK_SUBSTRATE_COOP_MINING ? 2 : 0) +
-                  (hdr[MPK_HDR_SUBSTRATE] == MPK_SUBSTRATE_COLLABORATIVE_COOKING ? 1 : 0) +
-                  (hdr[MPK_HDR_SUBSTRATE] == MPK_SUBSTRATE_EXTERNALITY_MUSHROOMS ? 1 : 0);
-  t.grid_bytes = t.grid_planes * t.H * t.W;
-  if (hdr[MPK_HDR_SUBSTRATE] == MPK_SUBSTRATE_THE_MATRIX) {
-    e->mx.player_block = (t.grid_bytes + 15) & ~15;
-    t.grid_bytes = e->mx.player_block + MP_MAX_PLAYERS * (int)sizeof(stepk::MxPlayer);
-  }
-  t.grid_pad = (t.grid_bytes + 15) & ~15;
-  t.world_stride = ((t.grid_pad + (int)sizeof(WorldTail) + 63) & ~63) +
-                   64 * (dev && dev->record_pad > 0 ? dev->record_pad : 0);
-  e->nhits = hdr[MPK_HDR_NHITS];
-#define DEV_ALLOC(ptr, bytes) HIP_TRY(hipMalloc((void**)&(ptr), (bytes)))
-  DEV_ALLOC(e->d_pack, pack_len);
-  HIP_TRY(hipMemcpy(e->d_pack, hp, pack_len, hipMemcpyHostToDevice));
-
-  uint64_t n = 0;
-  t.init_grid = e->dev<uint8_t>(table<uint8_t>(hp, "init_grid"));
-  t.state_layer = e->dev<int32_t>(table<int32_t>(hp, "state_layer"));
-  t.state_sprite = e->dev<int32_t>(table<int32_t>(hp, "state_sprite"));
-  t.alive_state = e->dev<int32_t>(table<int32_t>(hp, "avatar_alive_state"));
-  t.wait_state = e->dev<int32_t>(table<int32_t>(hp, "avatar_wait_state"));
-  t.action_table = e->dev<int32_t>(table<int32_t>(hp, "action_table"));
-  const int32_t* spawn = table<int32_t>(hp, "spawn_cells", &n);
-  t.spawn_cells = e->dev<int32_t>(spawn);
-  t.n_spawn = (int)n;
-  t.hit_state = e->dev<int32_t>(table<int32_t>(hp, "hit_state"));
-  t.hit_state_dir = e->dev<int32_t>(table<int32_t>(hp, "hit_state_dir"));
-  t.state_orient = e->dev<int32_t>(table<int32_t>(hp, "state_orient"));
-  if (!table<int32_t>(hp, "hit_state_dir") || !table<int32_t>(hp, "state_orient"))
-    return fail(MP_ERR_PACK, "mp_create: pack lacks hit_state_dir / state_orient (re-lower it)");
-  t.sprite_rgba = e->dev<uint8_t>(table<uint8_t>(hp, "sprite_rgba"));
-  t.view_sprite_map = e->dev<int32_t>(table<int32_t>(hp, "view_sprite_map"));
-  t.state_groups = e->dev<uint32_t>(table<uint32_t>(hp, "state_groups"));
-  {
-    const int32_t* opt = table<int32_t>(hp, "optional_i32", &n);
-    t.n_optional = opt ? (int)(n / 4) : 0;
-    t.optional = opt ? e->dev<int32_t>(opt) : nullptr;
-    const int32_t* cn = table<int32_t>(hp, "choice_n");
-    t.choice_n = cn ? e->dev<int32_t>(cn) : nullptr;
-    uint64_t ncn = 0;
-    (void)table<int32_t>(hp, "choice_n", &ncn);
-    if (t.n_optional > 0 && !cn)
-      return fail(MP_ERR_PACK, "mp_create: optional objects without choice_n");
-    if (opt && (n % 4) != 0) return fail(MP_ERR_PACK, "mp_create: optional_i32 is not [n][4]");
-    for (uint64_t i = 0; i < ncn; ++i)
-      if (cn[i] == 0 || cn[i] > 64 || cn[i] < -64 || ncn > 65535)
-        return fail(MP_ERR_PACK, "mp_create: choice_n out of range");
-    for (int i = 0; i < t.n_optional; ++i) {
-      const int32_t* o4 = opt + 4 * i;   // cell, plane | initial state << 8, choice, outcome mask
-      if (o4[0] < 0 || o4[0] >= t.H * t.W || o4[1] < 0 || (o4[1] & 255) >= t.L ||
-          (o4[1] >> 8) < 1 || (o4[1] >> 8) >= t.nstates || o4[2] < 0 ||
-          (uint64_t)(o4[2] & 0xffff) >= ncn || (o4[2] >> 16) > 32)
-        return fail(MP_ERR_PACK, "mp_create: optional object %d out of range", i);
-    }
-  }
-  if (t.n_spawn < t.P || t.n_spawn > 256)
-    return fail(MP_ERR_PACK, "mp_create: %d spawn points for %d players", t.n_spawn, t.P);
-
-  // derived tables: renderer sprite flags; state -> player
-  {
-    const int32_t* flags = table<int32_t>(hp, "sprite_flags");
-    const int32_t* alive = table<int32_t>(hp, "avatar_alive_state");
-    const int32_t* ssprite = table<int32_t>(hp, "state_sprite");
-    const int32_t* slayer = table<int32_t>(hp, "state_layer");
-    // [0,256) sprite flags, [256,512) state -> player, then u16 res_index[H*W]
-    // (territory: cell -> index into resource_cells, 0xffff = none)
-    std::vector<uint8_t> extra(512 + (size_t)t.H * t.W * 2, 0xff);
-    memset(extra.data(), 0, 512);
-    for (int s = 0; s < t.nsprites; ++s)
-      extra[s] = (uint8_t)(((flags[s] & MPK_SPRITE_OPAQUE) ? 1 : 0) |
-                           ((flags[s] & MPK_SPRITE_PARTIAL) ? 2 : 0));
-    int8_t* sp = reinterpret_cast<int8_t*>(extra.data() + 256);
-    for (int s = 0; s < 256; ++s) sp[s] = -1;
-    for (int p = 0; p < t.P; ++p) sp[alive[p]] = (int8_t)p;
-    uint64_t n_extra_alive = 0;
-    const int32_t* extra_alive = table<int32_t>(hp, "avatar_extra_alive", &n_extra_alive);
-    for (uint64_t i = 0; extra_alive && i + 1 < n_extra_alive; i += 2)
-      if (extra_alive[i] > 0 && extra_alive[i] < 256 && extra_alive[i + 1] < t.P)
-        sp[extra_alive[i]] = (int8_t)extra_alive[i + 1];
-    // the renderer resolves non-avatar sprites through one table shared by all
-    // viewers: only avatar sprites may be remapped per viewer (clean_up.py:630-631)
-    {
-      const int32_t* vmap = table<int32_t>(hp, "view_sprite_map");
-      std::vector<uint8_t> is_avatar_sprite((size_t)t.nsprites, 0);
-      for (int p = 0; p < t.P; ++p)
-        if (ssprite[alive[p]] >= 0) is_avatar_sprite[(size_t)ssprite[alive[p]]] = 1;
-      for (uint64_t i = 0; extra_alive && i + 1 < n_extra_alive; i += 2)
-        if (extra_alive[i] > 0 && extra_alive[i] < t.nstates && ssprite[extra_alive[i]] >= 0)
-          is_avatar_sprite[(size_t)ssprite[extra_alive[i]]] = 1;
-      for (int v = 0; v < t.P; ++v)
-        for (int s = 0; s < t.nsprites; ++s)
-          if (!is_avatar_sprite[(size_t)s] && vmap[v * t.nsprites + s] != vmap[t.P_pack * t.nsprites + s])
-            return fail(MP_ERR_PACK, "mp_create: viewer %d remaps non-avatar sprite %d", v, s);
-    }
-    // the renderer's draw list holds one opaque base + 8 overlays per cell
-    int drawn_layers = 0;
-    for (int l = 0; l < t.L; ++l) {
-      bool any = false;
-      for (int s = 1; s < t.nstates; ++s) any = any || (slayer[s] == l && ssprite[s] >= 0);
-      drawn_layers += any;
-    }
-    // (collaborative_cooking has one interact layer per avatar, each showing a sprite on the
-    // ONE cell its avatar faces: at most four of them meet on a cell)
-    if (hdr[MPK_HDR_SUBSTRATE] == MPK_SUBSTRATE_COLLABORATIVE_COOKING && t.P_pack > 4)
-      drawn_layers -= t.P_pack - 4;
-    if (drawn_layers > 9 || t.L > 12)
-      return fail(MP_ERR_PACK, "mp_create: %d sprite-bearing layers that can meet on a cell (max 9), "
-                               "%d layers (max 12)", drawn_layers, t.L);
-    DEV_ALLOC(e->d_extra, extra.size());
-    HIP_TRY(hipMemcpy(e->d_extra, extra.data(), extra.size(), hipMemcpyHostToDevice));
-    t.sprite_flags8 = e->d_extra;
-  }
-  // the step kernels' LDS tables (step_common.h): per state the BeamBlocker bits
-  // and the avatar it is the live state of; the respawn group's cells
-  {
-    const uint32_t* hb = table<uint32_t>(hp, "state_hit_block");
-    const int32_t* alive = table<int32_t>(hp, "avatar_alive_state");
-    if (!hb || !alive) return fail(MP_ERR_PACK, "mp_create: pack lacks state_hit_block");
-    std::vector<uint8_t> blob((size_t)stepk::tables_bytes(t), 0);
-    uint32_t* sinfo = reinterpret_cast<uint32_t*>(blob.data());
-    for (int s2 = 0; s2 < t.nstates; ++s2) sinfo[s2] = hb[s2] & 0xffffffu;
-    for (int p2 = 0; p2 < t.P; ++p2) {
-      if (alive[p2] <= 0 || alive[p2] >= t.nstates)
-        return fail(MP_ERR_PACK, "mp_create: avatar state out of range");
-      sinfo[alive[p2]] |= (uint32_t)(p2 + 1) << 24;
-    }
-    {
-      // more alive states of an avatar (coins: one per colour): (state, player) pairs
-      uint64_t nx = 0;
-      const int32_t* xa = table<int32_t>(hp, "avatar_extra_alive", &nx);
-      for (uint64_t i = 0; xa && i + 1 < nx; i += 2) {
-        if (xa[i] <= 0 || xa[i] >= t.nstates || xa[i + 1] < 0 || xa[i + 1] >= t.P_pack)
-          return fail(MP_ERR_PACK, "mp_create: avatar_extra_alive out of range");
-        if (xa[i + 1] < t.P) sinfo[xa[i]] |= (uint32_t)(xa[i + 1] + 1) << 24;
-      }
-    }
-    uint16_t* sp16 = reinterpret_cast<uint16_t*>(blob.data() + stepk::kSinfoBytes);
-    for (int i = 0; i < t.n_spawn; ++i) {
-      if (spawn[i] < 0 || spawn[i] >= t.H * t.W)
-        return fail(MP_ERR_PACK, "mp_create: spawn cell out of range");
-      sp16[i] = (uint16_t)spawn[i];
-    }
-    const int32_t* at = table<int32_t>(hp, "action_table");
-    int8_t* rows = reinterpret_cast<int8_t*>(blob.data() + stepk::kSinfoBytes +
-                                             stepk::spawn_bytes(t.n_spawn));
-    for (int i = 0; i < t.nact * 4; ++i) rows[i] = (int8_t)at[i];
-    // (host memory: readable without a HIP call, i.e. while a kernel is stuck)
-    // (64 fault words + the -DMP_FRAME_TIMELINE build's event log)
-    HIP_TRY(hipHostMalloc((void**)&e->h_fault, kFaultWords * sizeof(uint32_t), hipHostMallocMapped));
-    memset(e->h_fault, 0, kFaultWords * sizeof(uint32_t));
-    HIP_TRY(hipHostGetDevicePointer((void**)&t.fault, e->h_fault, 0));
-    DEV_ALLOC(e->d_claim, (2 + 2 * 1024) * sizeof(uint32_t));   // (+ the -DMP_FRAME_ENDS build's stamps)
-    HIP_TRY(hipMemset(e->d_claim, 0, (2 + 2 * 1024) * sizeof(uint32_t)));
-    t.claim = e->d_claim;
-    DEV_ALLOC(e->d_stepblob, blob.size());
-    HIP_TRY(hipMemcpy(e->d_stepblob, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    t.step_blob = e->d_stepblob;
-  }
-
-  // ---- rules shared by every substrate with the stock avatar: Zapper kwargs,
-  // beam footprint, spawn groups
-  const int32_t* slayer = table<int32_t>(hp, "state_layer");
-  const int32_t* hit_state = table<int32_t>(hp, "hit_state");
-  // beam footprint in the order the reference walks it: the centre ray, then
-  // for the left and the right side every lateral cell followed by the forward
-  // ray that starts there
-  auto make_shape = [&](int len, int rad, BeamShape* sh) -> int {
-    int cnt = 0;
-    auto add = [&](int lat, int fwd, uint32_t pred) {
-      if (cnt < 16)
-        sh->cell[cnt] = ((uint32_t)lat & 255u) | (((uint32_t)fwd & 255u) << 8) | ((pred & 0xffffu) << 16);
-      return cnt++;
-    };
-    uint32_t pred = 0;
-    for (int f = 1; f <= len; ++f) pred |= 1u << add(0, f, pred);
-    for (int side = -1; side <= 1; side += 2) {
-      uint32_t side_pred = 0;
-      for (int i = 1; i <= rad; ++i) {
-        side_pred |= 1u << add(side * i, 0, side_pred);
-        uint32_t ray_pred = side_pred;
-        for (int f = 1; f <= len - i; ++f) ray_pred |= 1u << add(side * i, f, ray_pred);
-      }
-    }
-    sh->n = cnt;
-    // (round 5: an integer division is ~45 instructions on this ISA, and the six of a
-    // clean_up step — lane / n and 64 / n for either beam — were hoisted into the 894
-    // instructions a feeder executes in front of its first world: profiles/r05_head.md)
-    sh->per = cnt > 0 ? 64 / cnt : 0;
-    sh->magic = cnt > 0 ? 65536u / (uint32_t)cnt + 1u : 0u;
-    return cnt;
-  };
-  ZapRules zap{};
-  // (coins avatars carry none, the matrix levels' GameInteractionZapper has its own tables)
-  const bool has_zapper = e->substrate != MPK_SUBSTRATE_COINS &&
-                          e->substrate != MPK_SUBSTRATE_THE_MATRIX &&
-                          e->substrate != MPK_SUBSTRATE_COOP_MINING &&
-                          e->substrate != MPK_SUBSTRATE_GIFT_REFINEMENTS &&
-                          e->substrate != MPK_SUBSTRATE_COLLABORATIVE_COOKING;
-  if (has_zapper) {
-    const int32_t* zi = table<int32_t>(hp, "zapper_i32");
-    const double* zf = table<double>(hp, "zapper_f64");
-    zap.hit = find_name(hp, "hit_names", "zapHit");
-    if (!zi || !zf || zap.hit < 0)
-      return fail(MP_ERR_PACK, "mp_create: no Zapper tables in the pack");
-    zap.cooldown = zi[0]; zap.length = zi[1]; zap.radius = zi[2];
-    zap.respawn_frames = zi[3]; zap.remove_hit = zi[4];
-    zap.penalty = zf[0]; zap.reward = zf[1];
-    zap.s_hit = hit_state[zap.hit]; zap.layer = slayer[zap.s_hit];
-    if (zap.cooldown > 255 || make_shape(zap.length, zap.radius, &zap.shape) > 16)
-      return fail(MP_ERR_PACK, "mp_create: Zapper constants out of engine range");
-  }
-  {
-    uint64_t ncells = 0;
-    const int32_t* cells = table<int32_t>(hp, "init_spawn_cells", &ncells);
-    const int32_t* ptr = table<int32_t>(hp, "init_spawn_ptr", &n);
-    const int32_t* grp = table_n<int32_t>(hp, "avatar_init_group", t.P_pack);
-    if (!cells || !ptr || !grp || n < 2 || n > 65)
-      return fail(MP_ERR_PACK, "mp_create: no spawn group tables in the pack");
-    t.n_init_groups = (int)n - 1;
-    if (ptr[0] != 0 || (uint64_t)ptr[t.n_init_groups] != ncells ||
-        !in_range(cells, ncells, 0, t.H * t.W) || !in_range(grp, t.P_pack, 0, t.n_init_groups))
-      return fail(MP_ERR_PACK, "mp_create: spawn group tables inconsistent");
-    uint64_t nm0 = 0;
-    const uint32_t* masks0 = table<uint32_t>(hp, "init_spawn_mask", &nm0);
-    // is any optional object a spawn point?  (then the reset filters the pools)
-    t.optional_spawn = 0;
-    {
-      const uint32_t* sg = table<uint32_t>(hp, "state_groups");
-      const int32_t* opt = table<int32_t>(hp, "optional_i32");
-      for (int i = 0; i < t.n_optional && masks0 && sg; ++i)
-        for (uint64_t g = 0; g < nm0; ++g)
-          if (sg[opt[4 * i + 1] >> 8] & masks0[g]) t.optional_spawn = 1;
-    }
-    for (int g = 0; g < t.n_init_groups; ++g)
-      if (ptr[g + 1] < ptr[g] ||
-          ptr[g + 1] - ptr[g] > (t.optional_spawn ? 64
-                                 // (step_mushroom.h: spawn_avatars_wide)
-                                 : e->substrate == MPK_SUBSTRATE_EXTERNALITY_MUSHROOMS ? 256 : 128))
-        return fail(MP_ERR_PACK, "mp_create: too many cells in a spawn group (%d)",
-                    ptr[g + 1] - ptr[g]);
-    t.init_spawn_cells = e->dev<int32_t>(cells);
-    t.init_spawn_ptr = e->dev<int32_t>(ptr);
-    t.avatar_init_group = e->dev<int32_t>(grp);
-    uint64_t nm = 0;
-    const uint32_t* masks = table<uint32_t>(hp, "init_spawn_mask", &nm);
-    if (!masks || (int)nm != t.n_init_groups)
-      return fail(MP_ERR_PACK, "mp_create: pack lacks init_spawn_mask (re-lower it)");
-    t.init_spawn_mask = e->dev<uint32_t>(masks);
-    // every avatar that plays needs a point of its group (base_simulation.lua:
-    // 396-445 "Insufficient spawn points!")
-    for (int g = 0; g < t.n_init_groups; ++g) {
-      int want = 0;
-      for (int p2 = 0; p2 < t.P; ++p2) want += grp[p2] == g;
-      if (!t.optional_spawn && want > ptr[g + 1] - ptr[g])
-        return fail(MP_ERR_PACK, "mp_create: %d avatars for the %d points of spawn group %d",
-                    want, ptr[g + 1] - ptr[g], g);
-    }
-    // (with 'choice' spawn points the respawn pool would have to be filtered by
-    // presence: only substrates that never respawn are accepted)
-    if (t.optional_spawn && (zap.remove_hit || e->substrate == MPK_SUBSTRATE_THE_MATRIX))
-      return fail(MP_ERR_PACK, "mp_create: optional spawn points in a level that respawns");
-  }
-  auto only_beams_on = [&](int layer, int s_beam) {
-    for (int s = 1; s < t.nstates; ++s)
-      if (s != s_beam && slayer[s] == layer) return false;
-    return true;
-  };
-  if (has_zapper && !only_beams_on(zap.layer, zap.s_hit))
-    return fail(MP_ERR_PACK, "mp_create: a piece state lives on the zap beam layer");
-
-  if (e->substrate == MPK_SUBSTRATE_THE_MATRIX) {
-    MatrixTables& c = e->mx;
-    const int32_t* st = table<int32_t>(hp, "mx_states", &n);
-    const uint64_t nst = n;
-    const int32_t* ci = table_n<int32_t>(hp, "mx_i32", 22);
-    uint64_t nf = 0;
-    const double* cf = table<double>(hp, "mx_f64", &nf);
-    const uint64_t* thr = table_n<uint64_t>(hp, "mx_thr", 2);
-    const int32_t* pi = table_n<int32_t>(hp, "mx_player_i32", 4 * (uint64_t)t.P_pack);
-    const double* pf = table_n<double>(hp, "mx_player_f64", 4 * (uint64_t)t.P_pack);
-    uint64_t ns = 0, ncl = 0;
-    const int32_t* cells = table<int32_t>(hp, "resource_cells", &ns);
-    const int32_t* cls = table<int32_t>(hp, "resource_class", &ncl);
-    if (!st || !ci || !cf || !thr || !pi || !pf || !cells || !cls || ns != ncl || ns > 128)
-      return fail(MP_ERR_PACK, "mp_create: the_matrix tables missing or out of engine range");
-    const int R = ci[0];
-    if (R < 1 || R > stepk::kMxMaxR || nst != (uint64_t)(8 + 2 * R) || ci[19] < 1 || ci[19] > 5 ||
-        nf != (uint64_t)(5 + 2 * R * R + 2 * ci[19]) || !in_range(st, nst, 1, t.nstates) ||
-        !in_range(cls, ncl, 1, R + 1) || !in_range(cells, ns, 0, t.H * t.W))
-      return fail(MP_ERR_PACK, "mp_create: the_matrix tables inconsistent");
-    c.R = R;
-    c.n_site = (int)ns;
-    c.site_cells = e->dev<int32_t>(cells); c.site_class = e->dev<int32_t>(cls);
-    c.player_i32 = e->dev<int32_t>(pi); c.player_f64 = e->dev<double>(pf);
-    c.cooldown = ci[1]; c.respawn_frames = ci[4]; c.freeze = ci[5]; c.end_on_first = ci[6];
-    c.reset_winner = ci[7]; c.reset_loser = ci[8]; c.loser_dies = ci[9]; c.winner_dies = ci[10];
-    c.zero_inventory = ci[11]; c.random_tie = ci[12]; c.disallow_unready = ci[13];
-    c.has_ee = ci[14]; c.ee_min_frames = ci[15]; c.ee_interval = ci[16];
-    c.regen_delay = ci[17]; c.initial_health = ci[18]; c.n_intervals = ci[19];
-    c.spawn_all = ci[20]; c.hit = ci[21];
-    c.reward_floor = cf[0]; c.reward_multiplier = cf[1]; c.reward_unready = cf[2];
-    for (int i = 0; i < R * R; ++i) { c.row_matrix[i] = cf[5 + i]; c.col_matrix[i] = cf[5 + R * R + i]; }
-    for (int i = 0; i < 2 * c.n_intervals; ++i) c.interval[i] = cf[5 + 2 * R * R + i];
-    c.thr_regen = thr[0]; c.thr_ee = thr[1];
-    {
-      // TheMatrix:getColorInterval asserts that an interval holds the reward
-      // (components.lua:282-290); the kernel cannot assert, so the pack must make
-      // the assertion unreachable: a reward is rewardMultiplier x a convex
-      // combination of matrix entries (or 0 with an empty inventory), and every
-      // point of that range has to lie in one of the [lo, hi) intervals.
-      double lo = 0.0, hi = 0.0;
-      for (int i = 0; i < R * R; ++i)
-        for (double v : {c.reward_multiplier * c.row_matrix[i], c.reward_multiplier * c.col_matrix[i]}) {
-          lo = std::min(lo, v); hi = std::max(hi, v);
-        }
-      auto covered = [&](double x) {
-        for (int k = 0; k < c.n_intervals; ++k)
-          if (c.interval[2 * k] <= x && x < c.interval[2 * k + 1]) return true;
-        return false;
-      };
-      // (the two extreme payoffs themselves need pure profiles on both sides;
-      // the stock intervals end exactly there, half-open, and the reference would
-      // assert if one were ever paid: the kernel reports that case through the
-      // fault words instead — sync_and_check — and every other reward is checked
-      // here: each stretch between neighbouring interval bounds inside (lo, hi))
-      std::vector<double> cuts = {lo, hi};
-      for (int k = 0; k < 2 * c.n_intervals; ++k)
-        if (c.interval[k] > lo && c.interval[k] < hi) cuts.push_back(c.interval[k]);
-      std::sort(cuts.begin(), cuts.end());
-      bool ok = true;
-      for (size_t i = 0; ok && i + 1 < cuts.size(); ++i) {
-        if (cuts[i] == cuts[i + 1]) continue;
-        ok = covered(0.5 * (cuts[i] + cuts[i + 1])) && (i == 0 || covered(cuts[i]));
-      }
-      if (!ok)
-        return fail(MP_ERR_PACK, "mp_create: resultIndicatorColorIntervals do not cover the rewards "
-                                 "(%g, %g) this matrix and rewardMultiplier can pay "
-                                 "(the reference asserts, components.lua:282-290)", lo, hi);
-    }
-    if (c.hit < 0 || c.hit >= e->nhits || c.cooldown < 1 || c.cooldown > 255 || c.freeze < 0 ||
-        c.freeze > 200 || c.initial_health < 1 || c.initial_health > 3 || c.ee_interval <= 0 ||
-        c.respawn_frames < 0 || (c.regen_delay > 250 && c.thr_regen != 0) ||
-        make_shape(ci[2], ci[3], &c.shape) > 16)
-      return fail(MP_ERR_PACK, "mp_create: the_matrix constants out of engine range");
-    if (c.regen_delay > 255) c.regen_delay = 255;   // (never reached: the rate is 0)
-    c.s_beam = hit_state[c.hit]; c.beam_layer = slayer[c.s_beam];
-    // marker states in indicator order: notReady, ready, colour 1..5 (mx_states:
-    // wait, ready, notReady, colours); resource states per class: visible, wait
-    const int mark_wait = st[0];
-    const int by_ind[7] = {st[2], st[1], st[3], st[4], st[5], st[6], st[7]};
-    c.s_mark_packed = 0;
-    c.mark_layer = slayer[st[2]];
-    for (int i = 0; i < 7; ++i) {
-      c.s_mark_packed |= (uint64_t)by_ind[i] << (8 * i);
-      // 'notReady' draws nothing but sits on the overlay layer like the others
-      if (slayer[by_ind[i]] != c.mark_layer)
-        return fail(MP_ERR_PACK, "mp_create: the_matrix marker states on different layers");
-    }
-    c.s_visible_packed = 0;
-    c.res_layer = slayer[st[8]];
-    for (int k = 0; k < R; ++k) {
-      c.s_visible_packed |= (uint32_t)st[8 + 2 * k] << (8 * k);
-      if (slayer[st[8 + 2 * k]] != c.res_layer || slayer[st[9 + 2 * k]] >= 0)
-        return fail(MP_ERR_PACK, "mp_create: the_matrix resource states on unexpected layers");
-    }
-    if (slayer[mark_wait] >= 0 || c.mark_layer < 0 || c.res_layer < 0 || c.beam_layer < 0 ||
-        c.mark_layer == t.avatar_layer || c.res_layer == t.avatar_layer ||
-        !only_beams_on(c.beam_layer, c.s_beam))
-      return fail(MP_ERR_PACK, "mp_create: the_matrix layers out of engine range");
-    // the overlay layer holds markers only, the resource layer resources only
-    for (int s2 = 1; s2 < t.nstates; ++s2) {
-      bool is_mark = false, is_res = false;
-      for (int i = 0; i < 7; ++i) is_mark = is_mark || s2 == by_ind[i];
-      for (int k = 0; k < R; ++k) is_res = is_res || s2 == st[8 + 2 * k];
-      if ((slayer[s2] == c.mark_layer && !is_mark) || (slayer[s2] == c.res_layer && !is_res))
-        return fail(MP_ERR_PACK, "mp_create: the_matrix: a foreign state on the marker / resource layer");
-    }
-    c.plane_a = t.L; c.plane_b = t.L + 1;
-    if (t.W > 255 || t.H > 255) return fail(MP_ERR_PACK, "mp_create: the_matrix map too large");
-  }
-
-  if (e->substrate == MPK_SUBSTRATE_COOP_MINING) {
-    CoopTables& c = e->cm;
-    const int32_t* st = table_n<int32_t>(hp, "cm_states", 5);
-    const int32_t* ci = table_n<int32_t>(hp, "cm_i32", 10);
-    const double* cf = table_n<double>(hp, "cm_f64", 4 * (uint64_t)t.P_pack);
-    const uint64_t* thr = table_n<uint64_t>(hp, "cm_thr", 3);
-    const int32_t* cells = table<int32_t>(hp, "ore_cells", &n);
-    if (!st || !ci || !cf || !thr || !cells || n > 640 || !in_range(cells, n, 0, t.H * t.W) ||
-        !in_range(st, 5, 1, t.nstates))
-      return fail(MP_ERR_PACK, "mp_create: coop_mining tables missing");
-    c.ore_cells = e->dev<int32_t>(cells); c.n_ore = (int)n;
-    c.reward = e->dev<double>(cf);
-    for (int k = 0; k < 3; ++k) c.thr[k] = thr[k];
-    c.s_wait = st[0]; c.s_raw[0] = st[1]; c.s_raw[1] = st[2]; c.s_partial[0] = st[3]; c.s_partial[1] = st[4];
-    c.cooldown = ci[0]; c.hit = ci[3]; c.ee_min_frames = ci[4]; c.ee_interval = ci[5];
-    c.min_miners1 = ci[8]; c.window1 = ci[9];
-    c.ore_layer = slayer[c.s_wait];
-    // (type 0: extracted by the hit that mines it — one miner, no partial state of its own;
-    // type 1's miners are a byte mask: the Lua's minNumMiners doubles as the type index)
-    if (ci[6] != 1 || c.s_partial[0] != c.s_raw[0] || c.min_miners1 < 2 || c.min_miners1 > t.P_pack ||
-        t.P_pack > 8 || c.window1 < 1 || c.window1 > 255 || c.cooldown < 1 || c.cooldown > 255 ||
-        c.hit < 0 || c.hit >= e->nhits || c.ee_interval <= 0 || c.ore_layer < 0 ||
-        c.ore_layer == t.avatar_layer || make_shape(ci[1], ci[2], &c.shape) > 16)
-      return fail(MP_ERR_PACK, "mp_create: coop_mining constants out of engine range");
-    for (int k = 1; k < 5; ++k)
-      if (slayer[st[k]] != c.ore_layer)
-        return fail(MP_ERR_PACK, "mp_create: coop_mining ore states on different layers");
-    c.s_beam = hit_state[c.hit]; c.beam_layer = slayer[c.s_beam];
-    if (c.beam_layer < 0 || c.beam_layer == c.ore_layer || c.beam_layer == t.avatar_layer)
-      return fail(MP_ERR_PACK, "mp_create: coop_mining beam layer out of engine range");
-    c.plane_m = t.L; c.plane_c = t.L + 1;
-  }
-
-  if (e->substrate == MPK_SUBSTRATE_COLLABORATIVE_COOKING) {
-    CookTables& c = e->cc;
-    const int32_t* st = table_n<int32_t>(hp, "cc_inv_states", 4);
-    const int32_t* ci = table_n<int32_t>(hp, "cc_i32", 3);
-    const double* cf = table_n<double>(hp, "cc_f64", 1);
-    const int32_t* ps = table_n<int32_t>(hp, "cc_pot_states", 5);
-    const int32_t* bs = table_n<int32_t>(hp, "cc_bar_states", 11);
-    const int32_t* hits = table_n<int32_t>(hp, "cc_hits", (uint64_t)t.P_pack);
-    const uint8_t* kind = table_n<uint8_t>(hp, "cc_state_kind", (uint64_t)t.nstates);
-    uint64_t n_cont = 0, n_pot = 0, n_recv = 0, n_ci = 0, n_ri = 0, n_rf = 0;
-    const int32_t* cont = table<int32_t>(hp, "cc_container_cells", &n_cont);
-    const int32_t* cont_i = table<int32_t>(hp, "cc_container_i32", &n_ci);
-    const int32_t* pots = table<int32_t>(hp, "cc_pot_cells", &n_pot);
-    const int32_t* recv_i = table<int32_t>(hp, "cc_receiver_i32", &n_ri);
-    const double* recv_f = table<double>(hp, "cc_receiver_f64", &n_rf);
-    table<int32_t>(hp, "cc_receiver_cells", &n_recv);
-    if (!st || !ci || !cf || !ps || !bs || !hits || !kind || (n_cont && (!cont || !cont_i)) ||
-        (n_pot && !pots) || n_cont > 128 || n_pot > 64 || n_ci != 2 * n_cont || n_ri != 2 * n_recv ||
-        n_rf != n_recv || (n_recv && (!recv_i || !recv_f)) ||
-        !in_range(cont, n_cont, 0, t.H * t.W) || !in_range(pots, n_pot, 0, t.H * t.W) ||
-        !in_range(ps, 5, 1, t.nstates) || !in_range(bs, 11, 1, t.nstates) || !in_range(st, 4, 1, t.nstates) ||
-        !in_range(hits, (uint64_t)t.P_pack, 0, e->nhits))
-      return fail(MP_ERR_PACK, "mp_create: collaborative_cooking tables missing");
-    c.state_kind = e->dev<uint8_t>(kind);
-    c.n_cont = (int)n_cont; c.n_pot = (int)n_pot;
-    c.cont_cells = n_cont ? e->dev<int32_t>(cont) : nullptr;
-    c.cont_i32 = n_cont ? e->dev<int32_t>(cont_i) : nullptr;
-    c.pot_cells = n_pot ? e->dev<int32_t>(pots) : nullptr;
-    for (int k = 0; k < 5; ++k) c.s_pot[k] = ps[k];
-    c.s_bar0 = bs[0];
-    c.s_plain0 = st[1]; c.s_off0 = st[2]; c.s_dir0 = st[3];
-    c.overlay_layer = slayer[c.s_plain0];
-    c.plane_t = t.L;
-    c.cooldown = ci[0]; c.cooking_time = ci[1]; c.bar_interval = ci[2];
-    c.pot_reward = cf[0];
-    c.recv_item = n_recv ? recv_i[0] : -1; c.recv_global = n_recv ? recv_i[1] : 0;
-    c.recv_reward = n_recv ? recv_f[0] : 0.0;
-    c.s_beam0 = hit_state[hits[0]]; c.beam_layer0 = slayer[c.s_beam0];
-    bool ok = c.s_plain0 + 4 <= t.nstates && c.s_off0 + 4 <= t.nstates && c.s_dir0 + 12 <= t.nstates &&
-              c.overlay_layer >= 0 && c.overlay_layer != t.avatar_layer && c.cooldown <= 255 &&
-              c.cooking_time >= 1 && c.cooking_time <= 30 && c.bar_interval >= 1;
-    for (int k = 0; ok && k < 11; ++k) ok = bs[k] == bs[0] + k && slayer[bs[k]] == c.overlay_layer;
-    for (int k = 0; ok && k < 4; ++k)
-      ok = slayer[c.s_plain0 + k] == c.overlay_layer && slayer[c.s_off0 + k] == c.overlay_layer;
-    for (int k = 0; ok && k < 12; ++k) ok = slayer[c.s_dir0 + k] == c.overlay_layer;
-    for (int k = 0; ok && k < 5; ++k) ok = slayer[ps[k]] == t.avatar_layer;
-    for (int p = 0; ok && p < t.P_pack; ++p)
-      ok = hit_state[hits[p]] == c.s_beam0 + p && slayer[c.s_beam0 + p] == c.beam_layer0 + p &&
-           c.beam_layer0 + p < t.L && c.beam_layer0 + p != c.overlay_layer && c.beam_layer0 + p != t.avatar_layer;
-    for (uint64_t i = 0; ok && i < n_cont; ++i) ok = cont_i[2 * i] >= 0 && cont_i[2 * i] < 4;
-    for (uint64_t i = 1; ok && i < n_recv; ++i)
-      ok = recv_i[2 * i] == recv_i[0] && recv_i[2 * i + 1] == recv_i[1] && recv_f[i] == recv_f[0];
-    if (!ok) return fail(MP_ERR_PACK, "mp_create: collaborative_cooking constants out of engine range");
-  }
-
-  if (e->substrate == MPK_SUBSTRATE_GIFT_REFINEMENTS) {
-    GiftTables& c = e->gr;
-    const int32_t* st = table_n<int32_t>(hp, "gr_states", 2);
-    const int32_t* ci = table_n<int32_t>(hp, "gr_i32", 10);
-    const double* cf = table_n<double>(hp, "gr_f64", 2 * (uint64_t)t.P_pack + 3);
-    const uint64_t* thr = table_n<uint64_t>(hp, "gr_thr", 2);
-    const int32_t* cells = table<int32_t>(hp, "token_cells", &n);
-    if (!st || !ci || !cf || !thr || !cells || n > 640 || !in_range(cells, n, 0, t.H * t.W) ||
-        !in_range(st, 2, 1, t.nstates))
-      return fail(MP_ERR_PACK, "mp_create: gift_refinements tables missing");
-    c.token_cells = e->dev<int32_t>(cells); c.n_token = (int)n;
-    c.reward = e->dev<double>(cf);
-    c.pick_reward = cf[2 * t.P_pack];
-    c.thr[0] = thr[0]; c.thr[1] = thr[1];
-    c.s_wait = st[0]; c.s_live = st[1];
-    c.cooldown = ci[0]; c.hit = ci[3]; c.ee_min_frames = ci[4]; c.ee_interval = ci[5];
-    c.capacity = ci[6]; c.ntypes = ci[7]; c.multiplier = ci[8]; c.consume_cooldown = ci[9];
-    c.token_layer = slayer[c.s_live];
-    // (an event row carries player | type << 4 and player | count << 4 in a byte each)
-    if (c.capacity < 1 || c.capacity > 15 || c.ntypes < 1 || c.ntypes > 3 || c.multiplier < 1 ||
-        c.multiplier > 255 || c.consume_cooldown < 0 || c.consume_cooldown > 255 || t.P_pack > 15 ||
-        c.cooldown < 1 || c.cooldown > 255 || c.hit < 0 || c.hit >= e->nhits || c.ee_interval <= 0 ||
-        c.token_layer < 0 || c.token_layer == t.avatar_layer || slayer[c.s_wait] != c.token_layer ||
-        make_shape(ci[1], ci[2], &c.shape) > 16)
-      return fail(MP_ERR_PACK, "mp_create: gift_refinements constants out of engine range");
-    c.s_beam = hit_state[c.hit]; c.beam_layer = slayer[c.s_beam];
-    if (c.beam_layer < 0 || c.beam_layer == c.token_layer || c.beam_layer == t.avatar_layer)
-      return fail(MP_ERR_PACK, "mp_create: gift_refinements beam layer out of engine range");
-  }
-
-  if (e->substrate == MPK_SUBSTRATE_COINS) {
-    CoinsTables& c = e->co;
-    const int32_t* st = table_n<int32_t>(hp, "co_states", 3);
-    const int32_t* ci = table_n<int32_t>(hp, "co_i32", 4);
-    const double* cf = table_n<double>(hp, "co_f64", 8);
-    const uint64_t* thr = table_n<uint64_t>(hp, "co_thr", 2);
-    const int32_t* cells = table<int32_t>(hp, "coin_cells", &n);
-    if (!st || !ci || !cf || !thr || !cells || n > 512 || t.P != 2 || t.P_pack != 2 ||
-        !in_range(st, 3, 1, t.nstates) || !in_range(cells, n, 0, t.H * t.W))
-      return fail(MP_ERR_PACK, "mp_create: coins tables missing or out of engine range");
-    c.coin_cells = e->dev<int32_t>(cells); c.n_coin = (int)n;
-    c.s_coin[0] = st[0]; c.s_coin[1] = st[1]; c.s_wait = st[2];
-    c.coin_layer = slayer[st[0]]; c.wait_layer = slayer[st[2]];
-    if (slayer[st[1]] != c.coin_layer || c.coin_layer < 0 || c.wait_layer < 0 ||
-        c.coin_layer == t.avatar_layer)
-      return fail(MP_ERR_PACK, "mp_create: coins layers out of engine range");
-    for (int p = 0; p < t.P; ++p) {
-      c.player_type[p] = ci[p];
-      for (int k = 0; k < 4; ++k) c.rew[p][k] = cf[4 * p + k];
-    }
-    c.ee_min_frames = ci[t.P]; c.ee_interval = ci[t.P + 1];
-    c.thr_regrow = thr[0]; c.thr_ee = thr[1];
-    if (c.ee_interval <= 0) return fail(MP_ERR_PACK, "mp_create: coins constants out of range");
-    const int32_t* cc = table_n<int32_t>(hp, "co_colour_coin", 5);
-    const int32_t* ca = table_n<int32_t>(hp, "co_colour_alive", 10);
-    c.has_colours = cc && ca;
-    if (c.has_colours) {
-      c.colour_coin = c.colour_alive[0] = c.colour_alive[1] = 0;
-      for (int k = 0; k < 5; ++k) {
-        c.colour_coin |= (uint64_t)(uint8_t)cc[k] << (8 * k);
-        c.colour_alive[0] |= (uint64_t)(uint8_t)ca[k] << (8 * k);
-        c.colour_alive[1] |= (uint64_t)(uint8_t)ca[5 + k] << (8 * k);
-        if (cc[k] < 1 || cc[k] >= t.nstates || slayer[cc[k]] != c.coin_layer || ca[k] < 1 ||
-            ca[k] >= t.nstates || ca[5 + k] < 1 || ca[5 + k] >= t.nstates ||
-            slayer[ca[k]] != t.avatar_layer || slayer[ca[5 + k]] != t.avatar_layer)
-          return fail(MP_ERR_PACK, "mp_create: coins colour tables out of range");
-      }
-    }
-  }
-
-  if (e->substrate == MPK_SUBSTRATE_CLEAN_UP) {
-    CleanUpTables& c = e->cu;
-    c.zap = zap;
-    const int32_t* st = table_n<int32_t>(hp, "cu_states", 8);
-    const int32_t* ci = table_n<int32_t>(hp, "cu_i32", 7);
-    const double* cf = table_n<double>(hp, "cu_f64", 6);
-    const uint64_t* misc = table_n<uint64_t>(hp, "thr_misc", 2);
-    uint64_t na = 0, nd2 = 0, nw = 0;
-    const int32_t* acells = table<int32_t>(hp, "apple_cells", &na);
-    const int32_t* dcells = table<int32_t>(hp, "dirt_cells", &nd2);
-    const int32_t* wcells = table<int32_t>(hp, "water_cells", &nw);
-    const uint64_t* athr = table<uint64_t>(hp, "apple_thr", &n);
-    c.clean_hit = find_name(hp, "hit_names", "cleanHit");
-    if (!st || !ci || !cf || !misc || !acells || !dcells || !wcells || !athr ||
-        n != nd2 + 1 || nd2 > 256 || na > 256 || nw > 256 || e->nhits != 2 || c.clean_hit < 0 ||
-        !in_range(st, 8, 1, t.nstates) || !in_range(acells, na, 0, t.H * t.W) ||
-        !in_range(dcells, nd2, 0, t.H * t.W) || !in_range(wcells, nw, 0, t.H * t.W))
-      return fail(MP_ERR_PACK, "mp_create: clean_up tables missing or inconsistent");
-    c.apple_cells = e->dev<int32_t>(acells); c.n_apple = (int)na;
-    c.dirt_cells = e->dev<int32_t>(dcells); c.n_dirt = (int)nd2;
-    c.water_cells = e->dev<int32_t>(wcells); c.n_water = (int)nw;
-    c.apple_thr = e->dev<uint64_t>(athr);
-    c.thr_dirt_spawn = misc[0]; c.thr_episode_end = misc[1];
-    c.s_apple = st[0]; c.s_apple_wait = st[1]; c.s_dirt = st[2]; c.s_dirt_wait = st[3];
-    c.s_water_packed = 0;
-    for (int i = 0; i < 4; ++i) {
-      c.s_water[i] = st[4 + i];
-      c.s_water_packed |= (uint32_t)(st[4 + i] & 255) << (8 * i);
-    }
-    c.apple_layer = slayer[c.s_apple]; c.dirt_layer = slayer[c.s_dirt];
-    c.dirt_wait_layer = slayer[c.s_dirt_wait]; c.water_layer = slayer[c.s_water[0]];
-    c.s_clean_hit = hit_state[c.clean_hit];
-    c.clean_layer = slayer[c.s_clean_hit];
-    c.clean_cooldown = ci[0]; c.clean_length = ci[1]; c.clean_radius = ci[2];
-    c.dirt_delay = ci[3]; c.ee_min_frames = ci[4]; c.ee_interval = ci[5];
-    c.anim_frames = ci[6];
-    c.eat_reward = cf[5];
-    if (c.clean_cooldown > 255 || slayer[c.s_apple_wait] >= 0 ||
-        c.apple_layer < 0 || c.dirt_layer < 0 || c.dirt_wait_layer < 0 || c.water_layer < 0 ||
-        make_shape(c.clean_length, c.clean_radius, &c.clean_shape) > 16 ||
-        !only_beams_on(c.clean_layer, c.s_clean_hit) || c.ee_interval <= 0 || c.anim_frames <= 0)
-      return fail(MP_ERR_PACK, "mp_create: clean_up constants out of engine range");
-    const uint8_t* ig = table<uint8_t>(hp, "init_grid");
-    int nd = 0;
-    for (int i = 0; i < t.H * t.W; ++i)
-      nd += ig[c.dirt_layer * t.H * t.W + i] == c.s_dirt;
-    c.n_dirt_init = nd;
-  } else if (e->substrate == MPK_SUBSTRATE_COMMONS_HARVEST) {
-    CommonsTables& c = e->ch;
-    c.zap = zap;
-    const int32_t* ci = table_n<int32_t>(hp, "ch_i32", 4);
-    const int32_t* st = table_n<int32_t>(hp, "ch_states", ci && ci[0] > 0 && ci[0] <= 32 ? 4 + ci[0] : 4);
-    const double* cf = table_n<double>(hp, "ch_f64", 1);
-    const int32_t* cells = table<int32_t>(hp, "apple_cells", &n);
-    if (!st || !ci || !cf || !cells || n > 256 || !in_range(cells, n, 0, t.H * t.W) ||
-        !in_range(st, 4, 1, t.nstates))
-      return fail(MP_ERR_PACK, "mp_create: commons_harvest tables missing");
-    c.apple_cells = e->dev<int32_t>(cells); c.n_apple = (int)n;
-    c.nk = ci[0]; c.ee_min_frames = ci[1]; c.ee_interval = ci[2];
-    if (c.nk > 32 || c.nk < 1 || ci[3] != 1 || c.ee_interval <= 0)
-      return fail(MP_ERR_PACK, "mp_create: commons_harvest constants out of engine range");
-    c.s_apple = st[0]; c.s_wait = st[1]; c.s_grass = st[2]; c.s_dess = st[3];
-    if (!in_range(st + 4, c.nk, 1, t.nstates))
-      return fail(MP_ERR_PACK, "mp_create: appleWait_k states out of range");
-    for (int k = 0; k < c.nk; ++k) c.s_wait_k[k] = st[4 + k];
-    c.live_layer = slayer[c.s_apple]; c.wait_layer = slayer[c.s_wait];
-    c.grass_layer = slayer[c.s_grass];
-    c.eat_reward = cf[0];
-    const int32_t* disc = table<int32_t>(hp, "disc_offsets", &n);
-    c.disc = e->dev<int32_t>(disc); c.ndisc = (int)(n / 2);
-    const uint64_t* thr = table<uint64_t>(hp, "ch_thr", &n);
-    if (!disc || !thr || (int)n != c.nk + 1 || c.ndisc + 1 > c.nk || c.ndisc > 64 ||
-        !in_range(disc, (uint64_t)c.ndisc * 2, -8, 9) ||
-        c.live_layer < 0 || c.wait_layer < 0 || slayer[c.s_dess] != c.grass_layer)
-      return fail(MP_ERR_PACK, "mp_create: commons_harvest tables inconsistent");
-    for (int k = 0; k < c.nk; ++k)
-      if (slayer[c.s_wait_k[k]] != c.wait_layer)
-        return fail(MP_ERR_PACK, "mp_create: appleWait_k states on different layers");
-    c.thr = e->dev<uint64_t>(thr);
-  } else if (e->substrate == MPK_SUBSTRATE_EXTERNALITY_MUSHROOMS) {
-    MushroomTables& c = e->em;
-    c.zap = zap;
-    const int32_t* st = table_n<int32_t>(hp, "em_states", 8);
-    const int32_t* ci = table_n<int32_t>(hp, "em_i32", 30);
-    const double* cf = table_n<double>(hp, "em_f64", 8);
-    const uint64_t* thr = table_n<uint64_t>(hp, "em_thr", 21);
-    const int32_t* cells = table<int32_t>(hp, "mushroom_cells", &n);
-    if (!st || !ci || !cf || !thr || !cells || n < 1 || n > 256 ||   // 4 per lane, step_mushroom.h
-        !in_range(st, 8, 1, t.nstates) || !in_range(cells, n, 0, t.H * t.W))
-      return fail(MP_ERR_PACK, "mp_create: externality_mushrooms tables missing");
-    c.site_cells = e->dev<int32_t>(cells); c.n_site = (int)n;
-    c.i32 = e->dev<int32_t>(ci); c.thr = e->dev<uint64_t>(thr);
-    c.s_type0 = st[0]; c.live_layer = slayer[st[0]];
-    c.s_mark[0] = st[5]; c.s_mark[1] = st[6]; c.mark_layer = slayer[st[5]];
-    c.plane_age = t.L;
-    c.min_potential = ci[0]; c.recovery_time = ci[2];
-    c.ee_min_frames = ci[4]; c.ee_interval = ci[5]; c.n_live_init = ci[7];
-    bool ok = st[1] == st[0] + 1 && st[2] == st[0] + 2 && st[3] == st[0] + 3 &&
-              slayer[st[4]] < 0 && slayer[st[7]] < 0 && slayer[st[6]] == c.mark_layer &&
-              c.live_layer >= 0 && c.mark_layer >= 0 && c.live_layer != t.avatar_layer &&
-              c.mark_layer != t.avatar_layer && c.live_layer != c.mark_layer &&
-              ci[1] == 1 && ci[3] == 2 && ci[6] == zap.hit && c.ee_interval > 0 &&
-              c.recovery_time >= 1 && c.recovery_time <= 255 && c.n_live_init >= 0 &&
-              c.n_live_init <= (int)n && !zap.remove_hit && zap.penalty == 0.0 && zap.reward == 0.0 &&
-              zap.respawn_frames >= 1 && t.n_optional == 0 && t.P >= 2;
-    // the mushrooms' plane and the markings' hold nothing else, every mushroom site starts
-    // on the map as the object table says
-    for (int s = 1; s < t.nstates && ok; ++s) {
-      if (slayer[s] == c.live_layer && (s < st[0] || s > st[3])) ok = false;
-      if (slayer[s] == c.mark_layer && s != st[5] && s != st[6]) ok = false;
-    }
-    c.perish_packed = 0;
-    for (int k = 0; k < 4 && ok; ++k) {
-      const int delay = ci[16 + k];   // (the age plane saturates at 255)
-      ok = ci[8 + k] >= 0 && ci[8 + k] <= 4 && ci[12 + k] >= 0 && ci[12 + k] <= 255 &&
-           delay >= 1 && (delay <= 254 || delay >= (1 << 30)) && ci[20 + k] >= -1 && ci[20 + k] < 4;
-      c.perish_packed |= (uint32_t)(delay <= 254 ? delay : 255) << (8 * k);
-    }
-    if (!ok) return fail(MP_ERR_PACK, "mp_create: externality_mushrooms constants out of engine range");
-    for (int l = 0; l < 2; ++l) {
-      c.lv_increment[l] = ci[24 + 3 * l]; c.lv_freeze[l] = ci[25 + 3 * l];
-      c.lv_remove[l] = ci[26 + 3 * l];
-      c.lv_source[l] = cf[4 + 2 * l]; c.lv_target[l] = cf[5 + 2 * l];
-      if (c.lv_freeze[l] < 0 || c.lv_freeze[l] > 255 || c.lv_increment[l] < -1 || c.lv_increment[l] > 1)
-        return fail(MP_ERR_PACK, "mp_create: externality_mushrooms sanction levels out of engine range");
-    }
-    // _rewardEveryone (components.lua:65-105) with this engine's player count
-    c.pays = 0;
-    for (int k = 0; k < 4; ++k) { c.rew_self[k] = 0.0; c.rew_other[k] = 0.0; }
-    c.rew_self[0] = cf[0]; c.pays |= 1u;
-    c.rew_self[1] = c.rew_other[1] = cf[1] / (double)t.P; c.pays |= (1u << 1) | (1u << 5);
-    c.rew_other[2] = cf[2] / (double)(t.P - 1); c.pays |= 1u << 6;
-    c.rew_self[3] = c.rew_other[3] = cf[3] / (double)t.P; c.pays |= (1u << 3) | (1u << 7);
-    c.thr_ee = thr[20];
-  } else if (e->substrate == MPK_SUBSTRATE_TERRITORY) {
-    TerritoryTables& c = e->tr;
-    c.zap = zap;
-    const int32_t* st = table_n<int32_t>(hp, "tr_states", 10 + 2 * (uint64_t)t.P_pack);
-    const int32_t* ci = table_n<int32_t>(hp, "tr_i32", 16);
-    const double* cf = table_n<double>(hp, "tr_f64", 8);
-    const uint64_t* thr = table_n<uint64_t>(hp, "tr_thr", 3);
-    const int32_t* hits = table_n<int32_t>(hp, "tr_hits", 1 + 2 * (uint64_t)t.P_pack);
-    const int32_t* hsd = table<int32_t>(hp, "hit_state_dir");
-    const int32_t* cells = table<int32_t>(hp, "resource_cells", &n);
-    if (!st || !ci || !cf || !thr || !hits || !cells || n > 256 ||   // 4 per lane, step_territory.h
-        !in_range(st, 10 + 2 * (uint64_t)t.P_pack, 1, t.nstates) ||
-        !in_range(hits, 1 + 2 * (uint64_t)t.P_pack, 0, e->nhits) ||
-        !in_range(cells, n, 0, t.H * t.W))
-      return fail(MP_ERR_PACK, "mp_create: territory tables missing");
-    c.res_cells = e->dev<int32_t>(cells); c.n_res = (int)n;
-    c.map_cells = t.H * t.W;
-    const int P = t.P_pack;   // table strides; absent players' states are never on the grid
-    c.s_res_unclaimed = st[0]; c.s_dmg_inactive = st[5]; c.s_dmg_damaged = st[6];
-    c.s_mark[0] = st[7]; c.s_mark[1] = st[8];
-    for (int p = 0; p < P; ++p) { c.s_claimed[p] = st[10 + p]; c.s_dry[p] = st[10 + P + p]; }
-    c.res_layer = slayer[st[0]]; c.tex_layer = slayer[st[2]];
-    c.ind_layer = slayer[c.s_dry[0]]; c.dmg_layer = slayer[st[5]]; c.mark_layer = slayer[st[7]];
-    c.plane_a = t.L; c.plane_b = t.L + 1; c.plane_c = t.L + 2;
-    c.initial_health = ci[0]; c.reward_delay = ci[1]; c.repair_delay = ci[2];
-    c.claim_length = ci[3]; c.claim_wait = ci[5]; c.recovery_time = ci[6];
-    c.ee_min_frames = ci[8]; c.ee_interval = ci[9];
-    if (ci[7] != 2 || ci[4] != 0 || c.initial_health > 3 || c.claim_length < 1 ||
-        c.claim_length * t.P > 64 || c.ee_interval <= 0 || zap.remove_hit || c.res_layer != t.avatar_layer ||
-        slayer[st[1]] >= 0 || slayer[st[3]] >= 0 || slayer[st[4]] >= 0 || slayer[st[9]] >= 0)
-      return fail(MP_ERR_PACK, "mp_create: territory constants out of engine range");
-    for (int l = 0; l < 2; ++l) {
-      c.lv_increment[l] = ci[10 + 3 * l]; c.lv_freeze[l] = ci[11 + 3 * l];
-      c.lv_remove[l] = ci[12 + 3 * l];
-      c.lv_source[l] = cf[4 + 2 * l]; c.lv_target[l] = cf[5 + 2 * l];
-      if (c.lv_freeze[l] > 255) return fail(MP_ERR_PACK, "mp_create: freeze too long");
-    }
-    c.reward = cf[0];
-    c.thr_reward = thr[0]; c.thr_repair = thr[1]; c.thr_ee = thr[2];
-    c.hit_zap = hits[0];
-    for (int p = 0; p < P; ++p) {
-      c.hit_brush[p] = hits[1 + p]; c.hit_claim[p] = hits[1 + P + p];
-      for (int d = 0; d < 4; ++d) c.s_brush[p][d] = hsd[c.hit_brush[p] * 4 + d];
-      c.s_claim_hit[p] = hit_state[c.hit_claim[p]];
-    }
-    c.brush_layer = slayer[c.s_brush[0][0]]; c.claim_layer = slayer[c.s_claim_hit[0]];
-    for (int s = 1; s < t.nstates; ++s) {  // hit layers hold nothing but beam sprites
-      bool is_hit = false;
-      for (int h = 0; h < e->nhits * 4; ++h) is_hit = is_hit || hsd[h] == s;
-      if (!is_hit && (slayer[s] == c.brush_layer || slayer[s] == c.claim_layer))
-        return fail(MP_ERR_PACK, "mp_create: a piece state lives on a territory hit layer");
-    }
-  }
-
-  const size_t state_bytes = (size_t)e->N * t.world_stride;
-  DEV_ALLOC(e->d_state, state_bytes);
-  {
-    std::vector<uint8_t> init(state_bytes, 0);
-    for (int w = 0; w < e->N; ++w) {
-      WorldTail* tail = reinterpret_cast<WorldTail*>(
-          init.data() + (size_t)w * t.world_stride + t.grid_pad);
-      const uint64_t gw = cfg->world_offset + (uint64_t)w;
-      tail->seed = (cfg->base_seed || cfg->literal_base_seed) ? cfg->base_seed + gw
-                                                              : 0x9E3779B97F4A7C15ull * (gw + 1);
-    }
-    HIP_TRY(hipMemcpy(e->d_state, init.data(), state_bytes, hipMemcpyHostToDevice));
-  }
-  {
-    const size_t NP = (size_t)e->N * t.P, N = (size_t)e->N;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_reward = take(NP * 8), o_ready = take(NP * 8), o_aux = take(NP * 8),
-                 o_disc = take(N * 8), o_coll = take(N * 8), o_type = take(N * 4),
-                 o_pos = take(NP * 8), o_ori = take(NP * 4),
-                 o_ev = take(N * MP_EVENT_ROWS * 16);
-    const bool matrix = e->substrate == MPK_SUBSTRATE_THE_MATRIX;
-    const size_t o_inv = take(NP * e->inventory_types() * 8),
-                 o_int = take(matrix ? NP * 2 * e->mx.R * 8 : 0),
-                 o_irw = take(matrix ? NP * 2 * 8 : 0);
-    DEV_ALLOC(e->d_scalars, off);
-    e->scalars_bytes = off;
-    HIP_TRY(hipMemset(e->d_scalars, 0, off));
-    e->own.reward = (double*)(e->d_scalars + o_reward);
-    e->own.ready = (double*)(e->d_scalars + o_ready);
-    e->own.aux0 = (double*)(e->d_scalars + o_aux);
-    e->own.discount = (double*)(e->d_scalars + o_disc);
-    e->own.collective = (double*)(e->d_scalars + o_coll);
-    e->own.step_type = (int32_t*)(e->d_scalars + o_type);
-    e->own.position = (int32_t*)(e->d_scalars + o_pos);
-    e->own.orientation = (int32_t*)(e->d_scalars + o_ori);
-    e->own.events = (int32_t*)(e->d_scalars + o_ev);
-    if (e->inventory_types() > 0) e->own.inventory = (double*)(e->d_scalars + o_inv);
-    if (matrix) {
-      e->own.interaction = (double*)(e->d_scalars + o_int);
-      e->own.interaction_rewards = (double*)(e->d_scalars + o_irw);
-    }
-    if (cfg->debug_observations) {
-      size_t doff = 0;
-      auto dtake = [&](size_t bytes) { size_t o = doff; doff += (bytes + 255) & ~(size_t)255; return o; };
-      size_t o_dbg[4];
-      for (int k = 0; k < 4; ++k) o_dbg[k] = dtake(NP * 8);
-      const size_t o_zm = dtake(NP * t.P * 8);
-      const size_t o_cum = dtake(matrix ? NP * (1 + 3 * e->mx.R) * 8 : 0);
-      DEV_ALLOC(e->d_debug, doff);
-      e->debug_bytes = doff;
-      HIP_TRY(hipMemset(e->d_debug, 0, doff));
-      if (e->substrate == MPK_SUBSTRATE_CLEAN_UP)
-        for (int k = 0; k < 4; ++k) e->own.dbg[k] = (double*)(e->d_debug + o_dbg[k]);
-      if (e->substrate == MPK_SUBSTRATE_CLEAN_UP || e->substrate == MPK_SUBSTRATE_COMMONS_HARVEST)
-        e->own.zap_matrix = (double*)(e->d_debug + o_zm);
-      if (matrix) e->own.cumulants = (double*)(e->d_debug + o_cum);
-    }
-    DEV_ALLOC(e->d_actions, NP * 4);
-    DEV_ALLOC(e->d_mask, N);
-    DEV_ALLOC(e->d_seeds, N * 8);
-    DEV_ALLOC(e->d_ctr, MP_CTR_COUNT * 8);
-  }
-#undef DEV_ALLOC
-  // renderer: de-duplicated sprite atlas (noRotate sprites and solid colours
-  // have four identical facings), opaque sprites stored with alpha cleared
-  {
-    const uint8_t* rgba = table<uint8_t>(hp, "sprite_rgba");
-    const int32_t* flags = table<int32_t>(hp, "sprite_flags");
-    const int nimg = t.nsprites * 4;
-    std::vector<uint8_t> images(256, 0);  // image 0: unused padding
-    std::vector<uint16_t> slots((size_t)nimg, 0);
-    int count = 1;
-    for (int i = 0; i < nimg; ++i) {
-      uint8_t img[256];
-      memcpy(img, rgba + (size_t)i * 256, 256);
-      if (flags[i >> 2] & MPK_SPRITE_OPAQUE) {
-        // opaque images are only ever copied: store them pre-packed, 8 rows of
-        // 24 B RGB followed by 8 B of padding
-        uint8_t packed[256] = {0};
-        for (int py = 0; py < 8; ++py)
-          for (int px = 0; px < 8; ++px)
-            for (int ch = 0; ch < 3; ++ch)
-              packed[py * 32 + px * 3 + ch] = img[(py * 8 + px) * 4 + ch];
-        memcpy(img, packed, 256);
-      }
-      int found = -1;
-      for (int k = 1; k < count && found < 0; ++k)
-        if (memcmp(images.data() + (size_t)k * 256, img, 256) == 0) found = k;
-      if (found < 0) {
-        found = count++;
-        images.insert(images.end(), img, img + 256);
-      }
-      slots[(size_t)i] = (uint16_t)found;
-    }
-    // composite cache (render.hip phase 1): pre-blend the (opaque base, overlay)
-    // stacks that the map's static pieces can form — dirt on water, shadows on
-    // sand, claimed-resource paint on its texture ... — so such cells become plain
-    // copies.  A piece's possible looks are all sprite-bearing states of its
-    // prefab ("prefab.state" names); avatars, their markings and beams move, so
-    // they are never part of a cached stack.
-    t.scratch_cells = (dev && dev->scratch_cells > 0) ? dev->scratch_cells : 8;
-    std::vector<uint32_t> pair_table(kPairSlots, 0xffffffffu);
-    int pair_probe = 0, n_composites = 0, used_slots = 0;
-    if (!(dev && dev->no_composite_cache)) {
-      uint64_t names_len = 0;
-      const char* names = table<char>(hp, "state_names", &names_len);
-      const int32_t* objs = table<int32_t>(hp, "objects");
-      const int32_t* st_layer = table<int32_t>(hp, "state_layer");
-      const int32_t* st_sprite = table<int32_t>(hp, "state_sprite");
-      const int32_t* st_orient = table<int32_t>(hp, "state_orient");
-      const int nobj = hdr[MPK_HDR_NOBJ];
-      std::vector<std::string> prefab((size_t)t.nstates);
-      {
-        uint64_t off = 0;
-        for (int s = 0; s < t.nstates && off < names_len; ++s) {
-          const std::string nm(names + off);
-          off += nm.size() + 1;
-          prefab[(size_t)s] = nm.substr(0, nm.find('.'));
-        }
-      }
-      struct Look { int layer, sprite, orient; };
-      std::vector<std::vector<Look>> cell_looks((size_t)t.H * t.W);
-      for (int i = 0; i < nobj; ++i) {
-        const int32_t* ob = objs + 4 * i;
-        if (ob[0] == MPK_KIND_SCENE || ob[0] == MPK_KIND_AVATAR || ob[0] == MPK_KIND_MARKING) continue;
-        for (int s = 1; s < t.nstates; ++s)
-          if (prefab[(size_t)s] == prefab[(size_t)ob[3]] && st_sprite[s] >= 0 && st_layer[s] >= 0)
-            cell_looks[(size_t)ob[2] * t.W + ob[1]].push_back({st_layer[s], st_sprite[s], st_orient[s]});
-      }
-      // stacks: an opaque look, then up to two non-opaque looks on higher layers
-      struct Stack { int n; Look l[3]; long cells; };
-      std::vector<Stack> stacks;
-      auto same = [](const Look& a, const Look& b) {
-        return a.sprite == b.sprite && a.orient == b.orient;
-      };
-      auto count_stack = [&](const Look* l, int n) {
-        for (auto& sk : stacks) {
-          bool eq = sk.n == n;
-          for (int k = 0; eq && k < n; ++k) eq = same(sk.l[k], l[k]);
-          if (eq) { sk.cells++; return; }
-        }
-        Stack sk; sk.n = n; sk.cells = 1;
-        for (int k = 0; k < n; ++k) sk.l[k] = l[k];
-        stacks.push_back(sk);
-      };
-      auto overlay = [&](const Look& l) {
-        return !(flags[l.sprite] & (MPK_SPRITE_OPAQUE | MPK_SPRITE_EMPTY));
-      };
-      for (const auto& looks : cell_looks) {
-        // (sprite -1: no opaque piece below — the renderer starts from image 0,
-        // black; the *_in_the_matrix maps have no floor under their resources)
-        std::vector<Look> bases;
-        for (const Look& a : looks)
-          if (flags[a.sprite] & MPK_SPRITE_OPAQUE) bases.push_back(a);
-        if (bases.empty()) bases.push_back({-1, -1, 0});   // a cell no piece can cover
-        for (const Look& a : bases) {
-          for (const Look& b : looks) {
-            if (b.layer <= a.layer || !overlay(b)) continue;
-            const Look ab[3] = {a, b, b};
-            count_stack(ab, 2);
-            for (const Look& c : looks) {
-              if (c.layer <= b.layer || !overlay(c)) continue;
-              const Look abc[3] = {a, b, c};
-              count_stack(abc, 3);
-            }
-          }
-        }
-      }
-      // stacks the lowering knows to be the common ones (territory: texture + wet +
-      // dry paint of the SAME player, 9 of 81 combinations): first in their class
-      {
-        uint64_t nh = 0;
-        const int32_t* hints = table<int32_t>(hp, "composite_hints", &nh);
-        for (uint64_t i = 0; hints && i + 2 < nh; i += 3) {
-          Look l[3]; int n = 0; bool ok = true;
-          for (int k = 0; k < 3; ++k) {
-            const int st = hints[i + k];
-            if (st == 0 && k > 0) break;
-            if (st <= 0 || st >= t.nstates || st_sprite[st] < 0 || st_layer[st] < 0) { ok = false; break; }
-            l[n++] = {st_layer[st], st_sprite[st], st_orient[st]};
-          }
-          if (!ok || n < 2 || !(flags[l[0].sprite] & MPK_SPRITE_OPAQUE)) continue;
-          for (int m = 2; m <= n; ++m) {
-            count_stack(l, m);
-            for (auto& sk : stacks) {
-              bool eq = sk.n == m;
-              for (int k = 0; eq && k < m; ++k) eq = same(sk.l[k], l[k]);
-              if (eq) sk.cells = 1L << 40;
-            }
-          }
-        }
-      }
-      std::sort(stacks.begin(), stacks.end(), [](const Stack& x, const Stack& y) {
-        return x.n != y.n ? x.n < y.n : x.cells > y.cells;   // all pairs before triples
-      });
-      auto add_image = [&](const uint8_t* img) {
-        for (int k = 0; k < count; ++k)
-          if (memcmp(images.data() + (size_t)k * 256, img, 256) == 0) return k;
-        images.insert(images.end(), img, img + 256);
-        return count++;
-      };
-      auto lookup = [&](uint32_t a, uint32_t b) -> int {
-        for (uint32_t h = pair_hash(a, b), k = 0; k < (uint32_t)kPairSlots; ++k) {
-          const uint32_t ent = pair_table[(h + k) & (kPairSlots - 1)];
-          if (ent == 0xffffffffu) return -1;
-          if ((ent >> 10) == ((a << 10) | b)) return (int)(ent & 1023u);
-        }
-        return -1;
-      };
-      auto insert = [&](uint32_t a, uint32_t b, uint32_t c) {
-        for (uint32_t h = pair_hash(a, b), k = 0; k < (uint32_t)kPairSlots; ++k) {
-          uint32_t& ent = pair_table[(h + k) & (kPairSlots - 1)];
-          if (ent == 0xffffffffu) {
-            ent = (a << 20) | (b << 10) | c;
-            if ((int)k + 1 > pair_probe) pair_probe = (int)k + 1;
-            return;
-          }
-        }
-      };
-      // one overlay image blended onto a packed opaque image, exactly as
-      // render.hip does it (A7: (s*a + d*(255-a) + 127) / 255; binary sprites
-      // replace where alpha > 0)
-      auto blend = [&](int base_img, int ov_img, bool partial, uint8_t* out) {
-        memcpy(out, images.data() + (size_t)base_img * 256, 256);
-        const uint8_t* ov = images.data() + (size_t)ov_img * 256;
-        for (int py = 0; py < 8; ++py)
-          for (int px = 0; px < 8; ++px) {
-            const uint8_t* s = ov + (py * 8 + px) * 4;
-            uint8_t* d = out + py * 32 + px * 3;
-            const unsigned a = s[3];
-            for (int ch = 0; ch < 3; ++ch) {
-              if (partial) d[ch] = (uint8_t)((s[ch] * a + d[ch] * (255u - a) + 127u) / 255u);
-              else if (a) d[ch] = s[ch];
-            }
-          }
-      };
-      // budget: whatever LDS the renderer's preferred geometry leaves free (more
-      // images must not cost worlds per workgroup: measured, tools/sweep_env.sh)
-      t.n_images = count;
-      int kMaxComposites = kPairSlots;
-      for (int v = 0; v < 6; ++v) {
-        const FramePlan p0 = plan_frame(t, e->sub, e->N, (v & 1) != 0, v >> 1, e->num_cus, dev);
-        kMaxComposites = std::min(kMaxComposites, (160 * 1024 - frame_lds_bytes(t, p0)) / 272);
-      }
-      if (kMaxComposites < 0) kMaxComposites = 0;
-      if (kMaxComposites > kPairSlots / 2) kMaxComposites = kPairSlots / 2;
-      if (dev && dev->max_composites >= 0)
-        kMaxComposites = std::min(kMaxComposites, (int)dev->max_composites);
-      for (const Stack& sk : stacks) {
-        for (int f = 0; f < 4; ++f) {
-          int base = sk.l[0].sprite < 0 ? 0 : slots[(size_t)sk.l[0].sprite * 4 + ((f + sk.l[0].orient) & 3)];
-          bool ok = true;
-          for (int k = 1; k < sk.n && ok; ++k) {
-            const int ov = slots[(size_t)sk.l[k].sprite * 4 + ((f + sk.l[k].orient) & 3)];
-            int comp = lookup((uint32_t)base, (uint32_t)ov);
-            if (comp < 0) {
-              // (a triple extends a cached pair; it is skipped if its pair was)
-              if (k < sk.n - 1 || n_composites >= kMaxComposites || used_slots >= kPairSlots / 2 ||
-                  count >= 1023) { ok = false; break; }
-              uint8_t img[256];
-              blend(base, ov, (flags[sk.l[k].sprite] & MPK_SPRITE_PARTIAL) != 0, img);
-              const int before = count;
-              comp = add_image(img);
-              n_composites += count - before;
-              insert((uint32_t)base, (uint32_t)ov, (uint32_t)comp);
-              ++used_slots;
-            }
-            base = comp;
-          }
-        }
-      }
-    }
-    if (count > 1023) return fail(MP_ERR_PACK, "mp_create: %d distinct sprite images", count);
-    t.n_images = count;
-    t.pair_probe = pair_probe;
-    const size_t img_bytes = (size_t)count * 256, slot_bytes = ((size_t)nimg * 2 + 15) & ~(size_t)15,
-                 pair_bytes = (size_t)kPairSlots * 4, blob_bytes = (size_t)render_blob_bytes(t);
-    // what every render workgroup stages besides its worlds, already in LDS layout
-    std::vector<uint8_t> blob(blob_bytes);
-    {
-      const int32_t* alive = table<int32_t>(hp, "avatar_alive_state");
-      std::vector<uint8_t> flags8((size_t)t.nsprites);
-      for (int s = 0; s < t.nsprites; ++s)
-        flags8[(size_t)s] = (uint8_t)(((flags[s] & MPK_SPRITE_OPAQUE) ? 1 : 0) |
-                                      ((flags[s] & MPK_SPRITE_PARTIAL) ? 2 : 0) |
-                                      ((flags[s] & MPK_SPRITE_EMPTY) ? 4 : 0));
-      std::vector<int8_t> splayer(256, -1);
-      for (int p = 0; p < t.P; ++p) splayer[(size_t)alive[p]] = (int8_t)p;
-      {
-        uint64_t nx = 0;
-        const int32_t* xa = table<int32_t>(hp, "avatar_extra_alive", &nx);
-        for (uint64_t i = 0; xa && i + 1 < nx; i += 2)
-          if (xa[i + 1] < t.P) splayer[(size_t)xa[i]] = (int8_t)xa[i + 1];
-      }
-      // viewers 0 .. P-1, then the world view (row P_pack of the pack's table)
-      const int32_t* vmap = table<int32_t>(hp, "view_sprite_map");
-      std::vector<int32_t> vmap_p((size_t)(t.P + 1) * t.nsprites);
-      for (int v = 0; v <= t.P; ++v)
-        memcpy(vmap_p.data() + (size_t)v * t.nsprites,
-               vmap + (size_t)(v < t.P ? v : t.P_pack) * t.nsprites, (size_t)t.nsprites * 4);
-      build_render_blob(t, images.data(), slots.data(), pair_table.data(),
-                        table<int32_t>(hp, "state_sprite"), splayer.data(),
-                        vmap_p.data(), flags8.data(),
-                        table<int32_t>(hp, "state_orient"), blob.data());
-      t.vis_layers = render_visible_layers(t, blob.data(), table<int32_t>(hp, "state_layer"));
-      // (the renderers carry a plane's byte offset in a record as 16 bits: FrameConsts::plane_off)
-      if ((t.L - 1) * t.H * t.W >= 65536)
-        return fail(MP_ERR_PACK, "mp_create: %d render planes of %d x %d cells", t.L, t.H, t.W);
-    }
-    HIP_TRY(hipMalloc((void**)&e->d_atlas, img_bytes + slot_bytes + pair_bytes + blob_bytes));
-    HIP_TRY(hipMemcpy(e->d_atlas, images.data(), img_bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->d_atlas + img_bytes, slots.data(), (size_t)nimg * 2, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->d_atlas + img_bytes + slot_bytes, pair_table.data(), pair_bytes,
-                      hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->d_atlas + img_bytes + slot_bytes + pair_bytes, blob.data(), blob_bytes,
-                      hipMemcpyHostToDevice));
-    t.atlas_compact = e->d_atlas;
-    t.img_slot = reinterpret_cast<const uint16_t*>(e->d_atlas + img_bytes);
-    t.pair_table = reinterpret_cast<const uint32_t*>(e->d_atlas + img_bytes + slot_bytes);
-    t.render_blob = e->d_atlas + img_bytes + slot_bytes + pair_bytes;
-
-    if (dev && dev->verbose)
-      fprintf(stderr, "mp_engine: composite cache: %d images, %d table entries, probe %d\n",
-              n_composites, used_slots, pair_probe);
-    for (int v = 0; v < 6; ++v) {
-      FramePlan& pl = e->plan[v & 1][v >> 1];
-      pl = plan_frame(t, e->sub, e->N, (v & 1) != 0, v >> 1, e->num_cus, dev);
-      if (frame_lds_bytes(t, pl) > 160 * 1024)
-        return fail(MP_ERR_PACK, "mp_create: renderer needs %d B of LDS", frame_lds_bytes(t, pl));
-    }
-    // the pooled per-agent views (MP_OBS_RGB_POOL*): their plans, sized for the bytes they write;
-    // a pack whose pooled atlas does not fit beside a ring of records does not offer them
-    // (8 x 8 sprites only: the pooled image of a cell is 8/k pixels square)
-    for (int i = 0; i < 3; ++i) {
-      const int k = 2 << i;
-      e->pool_ok[i] = t.sprite_size == 8;
-      for (int v = 0; v < 6 && e->pool_ok[i]; ++v) {
-        if ((v >> 1) == 1) continue;   // (WORLD.RGB alone has no per-agent view)
-        FramePlan& pl = e->pool_plan[i][v & 1][v >> 1];
-        pl = plan_frame(t, e->sub, e->N, (v & 1) != 0, v >> 1, e->num_cus, dev, k);
-        if (frame_lds_bytes(t, pl, k) > 160 * 1024) e->pool_ok[i] = false;
-      }
-    }
-    if (int rc = prepare_frame())
-      return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) failed: %d", rc);
-    if (dev && dev->verbose)
-      for (int v = 0; v < 6; ++v) {
-        const FramePlan& pl = e->plan[v & 1][v >> 1];
-        fprintf(stderr, "mp_engine: %d sprite images; frame plan %s, %s: %d buffers x %d worlds, %d of %d waves feed"
-                " (%d draw the world view), %d groups own %d batches each + %d pooled, %d B LDS\n",
-                count, (v & 1) ? "stepping + drawing" : "drawing",
-                (v >> 1) == 0 ? "agents view" : (v >> 1) == 1 ? "world view" : "both views",
-                pl.NB, pl.B, pl.feeders, pl.nwaves, pl.world_waves, pl.groups, pl.ks, pl.pool,
-                frame_lds_bytes(t, pl));
-      }
-  }
   return MP_OK;
 }
 
@@ -2173,7 +1160,7 @@ int mp_dump(MpEngine* e, uint8_t* grid, int32_t* avat, int32_t* glob) {
     if (e->substrate == MPK_SUBSTRATE_COOP_MINING) {
       // the ores' Lua-side variables, packed as oracle/coop_mining.c:coop_dump packs them:
       // the sum of the live countdowns, a position-weighted sum of the miner sets
-      const CoopTables& c = e->cm;
+      const CoopTables& c = e->sub.cm;
       const int32_t* cells = table<int32_t>(e->pack.data(), "ore_cells");
       const uint8_t* M = rec + (size_t)c.plane_m * t.H * t.W;
       const uint8_t* C = rec + (size_t)c.plane_c * t.H * t.W;
@@ -2186,7 +1173,7 @@ int mp_dump(MpEngine* e, uint8_t* grid, int32_t* avat, int32_t* glob) {
     }
     if (e->substrate == MPK_SUBSTRATE_COLLABORATIVE_COOKING) {
       // the pots' cooking times, summed as oracle/collaborative_cooking.c:cook_dump sums them
-      const CookTables& c = e->cc;
+      const CookTables& c = e->sub.cc;
       const int32_t* pots = table<int32_t>(e->pack.data(), "cc_pot_cells");
       const uint8_t* T = rec + (size_t)c.plane_t * t.H * t.W;
       uint32_t times = 0;
@@ -2200,7 +1187,7 @@ int mp_dump(MpEngine* e, uint8_t* grid, int32_t* avat, int32_t* glob) {
     }
     if (e->substrate == MPK_SUBSTRATE_THE_MATRIX) {
       // extra parity fields, same packing as oracle/the_matrix.c:matrix_dump
-      const MatrixTables& c = e->mx;
+      const MatrixTables& c = e->sub.mx;
       for (int p = 0; p < t.P; ++p) {
         int32_t* a = avat + ((size_t)w * t.P + p) * 8;
         const int f1 = tail->flag1[p];
@@ -2217,7 +1204,7 @@ int mp_dump(MpEngine* e, uint8_t* grid, int32_t* avat, int32_t* glob) {
     }
     if (e->substrate == MPK_SUBSTRATE_EXTERNALITY_MUSHROOMS) {
       // extra parity fields, same packing as oracle/externality_mushrooms.c:mushroom_dump
-      const MushroomTables& c = e->em;
+      const MushroomTables& c = e->sub.em;
       for (int p = 0; p < t.P; ++p) {
         avat[((size_t)w * t.P + p) * 8 + 5] = 0;   // (ctimer holds the marking's x here, not a timer)
         avat[((size_t)w * t.P + p) * 8 + 7] =
@@ -2240,8 +1227,8 @@ int mp_dump(MpEngine* e, uint8_t* grid, int32_t* avat, int32_t* glob) {
             tail->level[p] | (tail->freeze[p] << 4) | (tail->removal[p] << 12) |
             (tail->nozap[p] << 16) | ((tail->aflags[p] & 1) << 24) |
             (((tail->aflags[p] >> 1) & 1) << 25);
-      const uint8_t* A = rec + (size_t)e->tr.plane_a * t.H * t.W;
-      std::vector<int32_t> cells((size_t)e->tr.n_res);
+      const uint8_t* A = rec + (size_t)e->sub.tr.plane_a * t.H * t.W;
+      std::vector<int32_t> cells((size_t)e->sub.tr.n_res);
       memcpy(cells.data(), table<int32_t>(e->pack.data(), "resource_cells"),
              cells.size() * sizeof(int32_t));
       for (int32_t cell : cells) {

@@ -1,0 +1,964 @@
+// pack_decode.hip — the host stage of mp_create: every table of an MPK1 pack read and
+// range-checked into the engine's tables, without a HIP runtime call, so a truncated
+// or stale pack is MP_ERR_PACK before a device is touched, never a wild pointer.
+#include "pack_decode.h"
+
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+
+#include "step_common.h"
+#include "step_matrix.h"   // MxPlayer (record layout), kMxMaxR
+
+namespace {
+
+// ... with at least `min_count` elements.
+template <class T>
+const T* table_n(const void* pack, const char* name, uint64_t min_count) {
+  return static_cast<const T*>(mpk_require(pack, name, MpkType<T>::code, min_count, nullptr));
+}
+
+// Every value of `v[0, n)` lies in [lo, hi).
+bool in_range(const int32_t* v, uint64_t n, int64_t lo, int64_t hi) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (v[i] < lo || v[i] >= hi) return false;
+  return true;
+}
+
+int find_name(const void* pack, const char* table_name, const char* want) {
+  uint64_t n = 0;
+  const char* names = table<char>(pack, table_name, &n);
+  int idx = 0;
+  for (uint64_t i = 0; i < n; ++idx) {
+    if (strcmp(names + i, want) == 0) return idx;
+    i += strlen(names + i) + 1;
+  }
+  return -1;
+}
+
+// One decode: the bytes it reads, where the pointers it stores point, what loaders share.
+struct Src {
+  const void* hp;             // the host copy of the pack
+  const uint8_t* base;        // decode_pack's table_base
+  const int32_t *slayer, *hit_state;   // state_layer, hit_state
+  ZapRules zap;               // the stock Zapper (zeros where the substrate has none)
+  // the pointer a table read at `host` is stored as
+  template <class T> const T* at(const T* host) const {
+    return reinterpret_cast<const T*>(base + (reinterpret_cast<const uint8_t*>(host) -
+                                              static_cast<const uint8_t*>(hp)));
+  }
+};
+
+// Table `name` with at least `min` elements (*count: its length), or the refusal naming it.
+template <class T>
+bool need(const Src& s, const char* name, uint64_t min, const T*& v, uint64_t* count = nullptr) {
+  v = static_cast<const T*>(mpk_require(s.hp, name, MpkType<T>::code, min, count));
+  if (!v) fail(MP_ERR_PACK, "mp_create: table '%s' is missing, mistyped or too short", name);
+  return v != nullptr;
+}
+
+// A cell list of at most `max` cells, each inside the map.
+bool need_cells(const Src& s, const DevTables& t, const char* name, uint64_t max, const int32_t*& v, uint64_t& n) {
+  v = table<int32_t>(s.hp, name, &n);
+  if (v && n <= max && in_range(v, n, 0, t.H * t.W)) return true;
+  fail(MP_ERR_PACK, "mp_create: table '%s' is missing, too long or leaves the map", name);
+  return false;
+}
+
+// Beam footprint in the order the reference walks it: the centre ray, then for the
+// left and the right side every lateral cell followed by the forward ray that starts
+// there.  Returns the cell count (the shape holds 16).
+int make_shape(int len, int rad, BeamShape* sh) {
+  int cnt = 0;
+  auto add = [&](int lat, int fwd, uint32_t pred) {
+    if (cnt < 16)
+      sh->cell[cnt] = ((uint32_t)lat & 255u) | (((uint32_t)fwd & 255u) << 8) | ((pred & 0xffffu) << 16);
+    return cnt++;
+  };
+  uint32_t pred = 0;
+  for (int f = 1; f <= len; ++f) pred |= 1u << add(0, f, pred);
+  for (int side = -1; side <= 1; side += 2) {
+    uint32_t side_pred = 0;
+    for (int i = 1; i <= rad; ++i) {
+      side_pred |= 1u << add(side * i, 0, side_pred);
+      uint32_t ray_pred = side_pred;
+      for (int f = 1; f <= len - i; ++f) ray_pred |= 1u << add(side * i, f, ray_pred);
+    }
+  }
+  sh->n = cnt;
+  // (round 5: an integer division is ~45 instructions on this ISA; the six of a clean_up step —
+  // lane / n and 64 / n for either beam — were hoisted into a feeder's head: profiles/r05_head.md)
+  sh->per = cnt > 0 ? 64 / cnt : 0;
+  sh->magic = cnt > 0 ? 65536u / (uint32_t)cnt + 1u : 0u;
+  return cnt;
+}
+
+// No state but the beam's lives on its layer.
+bool only_beams_on(const Src& s, const DevTables& t, int layer, int s_beam) {
+  for (int st = 1; st < t.nstates; ++st)
+    if (st != s_beam && s.slayer[st] == layer) return false;
+  return true;
+}
+
+// The raw action fields (mp_step_fields): actionSpec (min, max, default) per field.
+int decode_action_fields(const Src& s, const int32_t* hdr, DevTables& t) {
+  const void* hp = s.hp;
+  const int nf = hdr[MPK_HDR_NFIELDS];
+  const int32_t* as = nf >= 1 && nf <= 4 ? table_n<int32_t>(hp, "action_spec", 3 * (uint64_t)nf) : nullptr;
+  if (!as || !table<char>(hp, "action_names"))
+    return fail(MP_ERR_PACK, "mp_create: the pack has no action_spec / action_names "
+                             "(re-lower it with tools/make_packs.py)");
+  t.nfields = nf;
+  for (int a = 0; a < nf; ++a) {
+    // (field 3 travels in six unsigned bits of the packed row: mp_step_fields)
+    if (as[3 * a] < (a == 3 ? 0 : -128) || as[3 * a] > as[3 * a + 2] ||
+        as[3 * a + 2] > as[3 * a + 1] || as[3 * a + 1] > (a == 3 ? 63 : 127))
+      return fail(MP_ERR_PACK, "mp_create: action_spec field %d out of range", a);
+    t.field_lo |= ((uint32_t)as[3 * a] & 255u) << (8 * a);
+    t.field_hi |= ((uint32_t)as[3 * a + 1] & 255u) << (8 * a);
+  }
+  return MP_OK;
+}
+
+// The tables every substrate's engine dereferences: present, of the right type, long
+// enough, their indices in range.
+int decode_common_tables(Src& s, const int32_t* hdr, DevTables& t) {
+  const void* hp = s.hp;
+  const int H = hdr[MPK_HDR_H], W = hdr[MPK_HDR_W], L = hdr[MPK_HDR_L];
+  const int HW = H * W, NS = hdr[MPK_HDR_NSTATES], NSP = hdr[MPK_HDR_NSPRITES], PP = hdr[MPK_HDR_P];
+  const int nobj = hdr[MPK_HDR_NOBJ], nhits = hdr[MPK_HDR_NHITS], nact = hdr[MPK_HDR_NACT];
+  const int vl = hdr[MPK_HDR_VL], vr = hdr[MPK_HDR_VR], vf = hdr[MPK_HDR_VF], vb = hdr[MPK_HDR_VB];
+  const int topology = hdr[MPK_HDR_TOPOLOGY], avatar_layer = hdr[MPK_HDR_AVATAR_LAYER];
+  if (NS < 1 || NSP < 2 || nhits < 0 || nobj < 1 || hdr[MPK_HDR_MAXFRAMES] < 1 ||
+      avatar_layer < 0 || avatar_layer >= L || vl < 0 || vr < 0 || vf < 0 ||
+      vb < 0 || (vl + vr + 1) > 64 || (vf + vb + 1) > 64 ||
+      (topology != 0 && topology != 1))
+    return fail(MP_ERR_PACK, "mp_create: header fields out of range");
+  const int reach = std::max(std::max(vl, vr), std::max(vf, vb));
+  if (topology == 1 && (reach > H || reach > W))   // the renderer wraps a coordinate once
+    return fail(MP_ERR_PACK, "mp_create: a TORUS map smaller than the view's reach");
+  const uint8_t* ig = table_n<uint8_t>(hp, "init_grid", (uint64_t)L * HW);
+  const int32_t* sl = table_n<int32_t>(hp, "state_layer", NS);
+  const int32_t* ss = table_n<int32_t>(hp, "state_sprite", NS);
+  const int32_t* so = table_n<int32_t>(hp, "state_orient", NS);
+  const uint32_t* sg = table_n<uint32_t>(hp, "state_groups", NS);
+  const uint32_t* hb = table_n<uint32_t>(hp, "state_hit_block", NS);
+  const int32_t* al = table_n<int32_t>(hp, "avatar_alive_state", PP);
+  const int32_t* wa = table_n<int32_t>(hp, "avatar_wait_state", PP);
+  const int32_t* at = table_n<int32_t>(hp, "action_table", (uint64_t)nact * 4);
+  const int32_t* hs = table_n<int32_t>(hp, "hit_state", nhits);
+  const int32_t* hd = table_n<int32_t>(hp, "hit_state_dir", (uint64_t)nhits * 4);
+  const uint8_t* rgba = table_n<uint8_t>(hp, "sprite_rgba", (uint64_t)NSP * 4 * 256);
+  const int32_t* sf = table_n<int32_t>(hp, "sprite_flags", NSP);
+  const int32_t* vm = table_n<int32_t>(hp, "view_sprite_map", (uint64_t)(PP + 1) * NSP);
+  const int32_t* ob = table_n<int32_t>(hp, "objects", (uint64_t)nobj * 4);
+  uint64_t nsc = 0;
+  const int32_t* sc = table<int32_t>(hp, "spawn_cells", &nsc);
+  if (!ig || !sl || !ss || !so || !sg || !hb || !al || !wa || !at || !hs || !hd || !rgba ||
+      !sf || !vm || !ob || !sc || !table<char>(hp, "state_names") || !table<char>(hp, "hit_names"))
+    return fail(MP_ERR_PACK, "mp_create: a table of the pack is missing, mistyped or too short "
+                             "(re-lower it with tools/make_packs.py)");
+  bool ok = in_range(sl, NS, -1, L) && in_range(ss, NS, -1, NSP) && in_range(so, NS, 0, 4) &&
+            in_range(al, PP, 1, NS) && in_range(wa, PP, 1, NS) &&
+            in_range(at, (uint64_t)nact * 4, -4, 5) && in_range(hs, nhits, 1, NS) &&
+            in_range(hd, (uint64_t)nhits * 4, 1, NS) &&
+            in_range(vm, (uint64_t)(PP + 1) * NSP, 0, NSP) && in_range(sc, nsc, 0, HW);
+  for (uint64_t i = 0; ok && i < (uint64_t)L * HW; ++i) ok = ig[i] < NS;
+  for (int i = 0; ok && i < nobj; ++i)
+    ok = ob[4 * i + 1] >= 0 && ob[4 * i + 1] < W && ob[4 * i + 2] >= 0 && ob[4 * i + 2] < H &&
+         ob[4 * i + 3] >= 1 && ob[4 * i + 3] < NS;
+  if (!ok) return fail(MP_ERR_PACK, "mp_create: a table of the pack holds an index out of range");
+  s.slayer = sl; s.hit_state = hs;
+  t.init_grid = s.at(ig); t.state_layer = s.at(sl); t.state_sprite = s.at(ss); t.state_orient = s.at(so);
+  t.state_groups = s.at(sg); t.alive_state = s.at(al); t.wait_state = s.at(wa);
+  t.action_table = s.at(at); t.hit_state = s.at(hs); t.hit_state_dir = s.at(hd);
+  t.sprite_rgba = s.at(rgba); t.view_sprite_map = s.at(vm);
+  t.spawn_cells = s.at(sc); t.n_spawn = (int)nsc;
+  return MP_OK;
+}
+
+// The players this engine runs: MpConfig.num_players, else the pack's default.
+int players(const int32_t* hdr, const MpConfig& cfg) {
+  const int P_pack = hdr[MPK_HDR_P], def = hdr[MPK_HDR_DEFAULT_P];
+  return cfg.num_players > 0 ? cfg.num_players : def > 0 && def <= P_pack ? def : P_pack;
+}
+
+// The header's scalars and the world record's layout.
+void decode_layout(const int32_t* hdr, const MpConfig& cfg, int hidden_planes, DecodedPack* d) {
+  DevTables& t = d->t;
+  t.H = hdr[MPK_HDR_H]; t.W = hdr[MPK_HDR_W]; t.L = hdr[MPK_HDR_L];
+  t.P_pack = hdr[MPK_HDR_P];
+  t.P = players(hdr, cfg);
+  t.nstates = hdr[MPK_HDR_NSTATES];
+  t.nsprites = hdr[MPK_HDR_NSPRITES]; t.topology = hdr[MPK_HDR_TOPOLOGY];
+  t.max_frames = hdr[MPK_HDR_MAXFRAMES]; t.nact = hdr[MPK_HDR_NACT];
+  t.avatar_layer = hdr[MPK_HDR_AVATAR_LAYER]; t.sprite_size = hdr[MPK_HDR_SPRITE];
+  t.vl = hdr[MPK_HDR_VL]; t.vr = hdr[MPK_HDR_VR]; t.vf = hdr[MPK_HDR_VF]; t.vb = hdr[MPK_HDR_VB];
+  t.grid_planes = t.L + hidden_planes;
+  t.grid_bytes = t.grid_planes * t.H * t.W;
+  if (d->sub.substrate == MPK_SUBSTRATE_THE_MATRIX) {
+    d->sub.mx.player_block = (t.grid_bytes + 15) & ~15;
+    t.grid_bytes = d->sub.mx.player_block + MP_MAX_PLAYERS * (int)sizeof(stepk::MxPlayer);
+  }
+  t.grid_pad = (t.grid_bytes + 15) & ~15;
+  t.world_stride = ((t.grid_pad + (int)sizeof(WorldTail) + 63) & ~63) +
+                   64 * (cfg.dev && cfg.dev->record_pad > 0 ? cfg.dev->record_pad : 0);
+  d->nhits = hdr[MPK_HDR_NHITS];
+}
+
+// The optional objects ('choice' map characters) and the respawn points.
+int decode_optional(const Src& s, DevTables& t) {
+  const void* hp = s.hp;
+  uint64_t n = 0, ncn = 0;
+  const int32_t* opt = table<int32_t>(hp, "optional_i32", &n);
+  t.n_optional = opt ? (int)(n / 4) : 0;
+  t.optional = opt ? s.at(opt) : nullptr;
+  const int32_t* cn = table<int32_t>(hp, "choice_n", &ncn);
+  t.choice_n = cn ? s.at(cn) : nullptr;
+  if (t.n_optional > 0 && !cn)
+    return fail(MP_ERR_PACK, "mp_create: optional objects without choice_n");
+  if (opt && (n % 4) != 0) return fail(MP_ERR_PACK, "mp_create: optional_i32 is not [n][4]");
+  for (uint64_t i = 0; i < ncn; ++i)
+    if (cn[i] == 0 || cn[i] > 64 || cn[i] < -64 || ncn > 65535)
+      return fail(MP_ERR_PACK, "mp_create: choice_n out of range");
+  for (int i = 0; i < t.n_optional; ++i) {
+    const int32_t* o4 = opt + 4 * i;   // cell, plane | initial state << 8, choice, outcome mask
+    if (o4[0] < 0 || o4[0] >= t.H * t.W || o4[1] < 0 || (o4[1] & 255) >= t.L ||
+        (o4[1] >> 8) < 1 || (o4[1] >> 8) >= t.nstates || o4[2] < 0 ||
+        (uint64_t)(o4[2] & 0xffff) >= ncn || (o4[2] >> 16) > 32)
+      return fail(MP_ERR_PACK, "mp_create: optional object %d out of range", i);
+  }
+  if (t.n_spawn < t.P || t.n_spawn > 256)
+    return fail(MP_ERR_PACK, "mp_create: %d spawn points for %d players", t.n_spawn, t.P);
+  return MP_OK;
+}
+
+// Derived tables: renderer sprite flags; state -> player.
+// [0,256) sprite flags, [256,512) state -> player, then u16 res_index[H*W]
+// (territory: cell -> index into resource_cells, 0xffff = none)
+int build_extra(const Src& s, const DevTables& t, std::vector<uint8_t>* out) {
+  const int32_t* flags = table<int32_t>(s.hp, "sprite_flags");
+  const int32_t* alive = table<int32_t>(s.hp, "avatar_alive_state");
+  const int32_t* ssprite = table<int32_t>(s.hp, "state_sprite");
+  std::vector<uint8_t>& extra = *out;
+  extra.assign(512 + (size_t)t.H * t.W * 2, 0xff);
+  memset(extra.data(), 0, 512);
+  for (int st = 0; st < t.nsprites; ++st)
+    extra[st] = (uint8_t)(((flags[st] & MPK_SPRITE_OPAQUE) ? 1 : 0) |
+                          ((flags[st] & MPK_SPRITE_PARTIAL) ? 2 : 0));
+  int8_t* sp = reinterpret_cast<int8_t*>(extra.data() + 256);
+  for (int st = 0; st < 256; ++st) sp[st] = -1;
+  for (int p = 0; p < t.P; ++p) sp[alive[p]] = (int8_t)p;
+  uint64_t n_extra_alive = 0;
+  const int32_t* extra_alive = table<int32_t>(s.hp, "avatar_extra_alive", &n_extra_alive);
+  for (uint64_t i = 0; extra_alive && i + 1 < n_extra_alive; i += 2)
+    if (extra_alive[i] > 0 && extra_alive[i] < 256 && extra_alive[i + 1] < t.P)
+      sp[extra_alive[i]] = (int8_t)extra_alive[i + 1];
+  // the renderer resolves non-avatar sprites through one table shared by all
+  // viewers: only avatar sprites may be remapped per viewer (clean_up.py:630-631)
+  const int32_t* vmap = table<int32_t>(s.hp, "view_sprite_map");
+  std::vector<uint8_t> is_avatar_sprite((size_t)t.nsprites, 0);
+  for (int p = 0; p < t.P; ++p)
+    if (ssprite[alive[p]] >= 0) is_avatar_sprite[(size_t)ssprite[alive[p]]] = 1;
+  for (uint64_t i = 0; extra_alive && i + 1 < n_extra_alive; i += 2)
+    if (extra_alive[i] > 0 && extra_alive[i] < t.nstates && ssprite[extra_alive[i]] >= 0)
+      is_avatar_sprite[(size_t)ssprite[extra_alive[i]]] = 1;
+  for (int v = 0; v < t.P; ++v)
+    for (int st = 0; st < t.nsprites; ++st)
+      if (!is_avatar_sprite[(size_t)st] && vmap[v * t.nsprites + st] != vmap[t.P_pack * t.nsprites + st])
+        return fail(MP_ERR_PACK, "mp_create: viewer %d remaps non-avatar sprite %d", v, st);
+  return MP_OK;
+}
+
+// The renderer's draw list holds one opaque base + 8 overlays per cell.
+int check_layers(const Src& s, const DevTables& t, int substrate) {
+  const int32_t* ssprite = table<int32_t>(s.hp, "state_sprite");
+  int drawn_layers = 0;
+  for (int l = 0; l < t.L; ++l) {
+    bool any = false;
+    for (int st = 1; st < t.nstates; ++st) any = any || (s.slayer[st] == l && ssprite[st] >= 0);
+    drawn_layers += any;
+  }
+  // (collaborative_cooking has one interact layer per avatar, each showing a sprite on the
+  // ONE cell its avatar faces: at most four of them meet on a cell)
+  if (substrate == MPK_SUBSTRATE_COLLABORATIVE_COOKING && t.P_pack > 4)
+    drawn_layers -= t.P_pack - 4;
+  if (drawn_layers > 9 || t.L > 12)
+    return fail(MP_ERR_PACK, "mp_create: %d sprite-bearing layers that can meet on a cell (max 9), "
+                             "%d layers (max 12)", drawn_layers, t.L);
+  // (16-bit plane offsets, FrameConsts::plane_off: unreachable while L <= 12 and H * W <= 4096, guards a raise)
+  if ((t.L - 1) * t.H * t.W >= 65536)
+    return fail(MP_ERR_PACK, "mp_create: %d render planes of %d x %d cells: plane offsets must be "
+                             "below 65536 bytes", t.L, t.H, t.W);
+  return MP_OK;
+}
+
+// The step kernels' LDS tables (step_common.h): per state the BeamBlocker bits and
+// the avatar it is the live state of; the respawn group's cells; the action rows.
+int build_step_blob(const Src& s, const DevTables& t, std::vector<uint8_t>* out) {
+  const uint32_t* hb = table<uint32_t>(s.hp, "state_hit_block");
+  const int32_t* alive = table<int32_t>(s.hp, "avatar_alive_state");
+  std::vector<uint8_t>& blob = *out;
+  blob.assign((size_t)stepk::tables_bytes(t), 0);
+  uint32_t* sinfo = reinterpret_cast<uint32_t*>(blob.data());
+  for (int s2 = 0; s2 < t.nstates; ++s2) sinfo[s2] = hb[s2] & 0xffffffu;
+  for (int p2 = 0; p2 < t.P; ++p2) sinfo[alive[p2]] |= (uint32_t)(p2 + 1) << 24;   // (in range: common tables)
+  // more alive states of an avatar (coins: one per colour): (state, player) pairs
+  uint64_t nx = 0;
+  const int32_t* xa = table<int32_t>(s.hp, "avatar_extra_alive", &nx);
+  for (uint64_t i = 0; xa && i + 1 < nx; i += 2) {
+    if (xa[i] <= 0 || xa[i] >= t.nstates || xa[i + 1] < 0 || xa[i + 1] >= t.P_pack)
+      return fail(MP_ERR_PACK, "mp_create: avatar_extra_alive out of range");
+    if (xa[i + 1] < t.P) sinfo[xa[i]] |= (uint32_t)(xa[i + 1] + 1) << 24;
+  }
+  const int32_t* spawn = table<int32_t>(s.hp, "spawn_cells");
+  uint16_t* sp16 = reinterpret_cast<uint16_t*>(blob.data() + stepk::kSinfoBytes);
+  for (int i = 0; i < t.n_spawn; ++i) sp16[i] = (uint16_t)spawn[i];   // (inside the map: common tables)
+  const int32_t* at = table<int32_t>(s.hp, "action_table");
+  int8_t* rows = reinterpret_cast<int8_t*>(blob.data() + stepk::kSinfoBytes +
+                                           stepk::spawn_bytes(t.n_spawn));
+  for (int i = 0; i < t.nact * 4; ++i) rows[i] = (int8_t)at[i];
+  return MP_OK;
+}
+
+// The stock Zapper's kwargs and where its beam is drawn.
+int load_zapper(Src& s, const DevTables& t) {
+  const int32_t* zi; const double* zf;
+  if (!need(s, "zapper_i32", 5, zi) || !need(s, "zapper_f64", 2, zf)) return MP_ERR_PACK;
+  ZapRules& zap = s.zap;
+  zap.hit = find_name(s.hp, "hit_names", "zapHit");
+  if (zap.hit < 0) return fail(MP_ERR_PACK, "mp_create: no Zapper tables in the pack");
+  zap.cooldown = zi[0]; zap.length = zi[1]; zap.radius = zi[2];
+  zap.respawn_frames = zi[3]; zap.remove_hit = zi[4];
+  zap.penalty = zf[0]; zap.reward = zf[1];
+  zap.s_hit = s.hit_state[zap.hit]; zap.layer = s.slayer[zap.s_hit];
+  if (zap.cooldown > 255 || make_shape(zap.length, zap.radius, &zap.shape) > 16)
+    return fail(MP_ERR_PACK, "mp_create: Zapper constants out of engine range");
+  if (!only_beams_on(s, t, zap.layer, zap.s_hit))
+    return fail(MP_ERR_PACK, "mp_create: a piece state lives on the zap beam layer");
+  return MP_OK;
+}
+
+// The initial spawn groups.
+int decode_spawn_groups(const Src& s, DevTables& t, int substrate) {
+  const int32_t *cells, *ptr, *grp; const uint32_t* masks; uint64_t ncells = 0, n = 0, nm = 0;
+  if (!need(s, "init_spawn_cells", 1, cells, &ncells) || !need(s, "init_spawn_ptr", 2, ptr, &n) ||
+      !need(s, "avatar_init_group", (uint64_t)t.P_pack, grp) ||
+      !need(s, "init_spawn_mask", 1, masks, &nm))
+    return MP_ERR_PACK;
+  if (n > 65) return fail(MP_ERR_PACK, "mp_create: no spawn group tables in the pack");
+  t.n_init_groups = (int)n - 1;
+  if (ptr[0] != 0 || (uint64_t)ptr[t.n_init_groups] != ncells ||
+      !in_range(cells, ncells, 0, t.H * t.W) || !in_range(grp, t.P_pack, 0, t.n_init_groups))
+    return fail(MP_ERR_PACK, "mp_create: spawn group tables inconsistent");
+  // is any optional object a spawn point?  (then the reset filters the pools)
+  const uint32_t* sg = table<uint32_t>(s.hp, "state_groups");
+  const int32_t* opt = table<int32_t>(s.hp, "optional_i32");
+  t.optional_spawn = 0;
+  for (int i = 0; i < t.n_optional; ++i)
+    for (uint64_t g = 0; g < nm; ++g)
+      if (sg[opt[4 * i + 1] >> 8] & masks[g]) t.optional_spawn = 1;
+  for (int g = 0; g < t.n_init_groups; ++g)
+    if (ptr[g + 1] < ptr[g] ||
+        ptr[g + 1] - ptr[g] > (t.optional_spawn ? 64
+                               // (step_mushroom.h: spawn_avatars_wide)
+                               : substrate == MPK_SUBSTRATE_EXTERNALITY_MUSHROOMS ? 256 : 128))
+      return fail(MP_ERR_PACK, "mp_create: too many cells in a spawn group (%d)", ptr[g + 1] - ptr[g]);
+  t.init_spawn_cells = s.at(cells);
+  t.init_spawn_ptr = s.at(ptr);
+  t.avatar_init_group = s.at(grp);
+  if ((int)nm != t.n_init_groups)
+    return fail(MP_ERR_PACK, "mp_create: pack lacks init_spawn_mask (re-lower it)");
+  t.init_spawn_mask = s.at(masks);
+  // every avatar that plays needs a point of its group (base_simulation.lua:
+  // 396-445 "Insufficient spawn points!")
+  for (int g = 0; g < t.n_init_groups; ++g) {
+    int want = 0;
+    for (int p2 = 0; p2 < t.P; ++p2) want += grp[p2] == g;
+    if (!t.optional_spawn && want > ptr[g + 1] - ptr[g])
+      return fail(MP_ERR_PACK, "mp_create: %d avatars for the %d points of spawn group %d",
+                  want, ptr[g + 1] - ptr[g], g);
+  }
+  // (with 'choice' spawn points the respawn pool would have to be filtered by
+  // presence: only substrates that never respawn are accepted)
+  if (t.optional_spawn && (s.zap.remove_hit || substrate == MPK_SUBSTRATE_THE_MATRIX))
+    return fail(MP_ERR_PACK, "mp_create: optional spawn points in a level that respawns");
+  return MP_OK;
+}
+
+// ---- one loader per substrate: its tables, their lengths and bounds, its rule constants
+
+int load_clean_up(Src& s, const DevTables& t, DecodedPack* d) {
+  CleanUpTables& c = d->sub.cu;
+  const int32_t *st, *ci, *acells, *dcells, *wcells; const double* cf;
+  const uint64_t *misc, *athr; uint64_t n = 0, na = 0, nd2 = 0, nw = 0;
+  if (!need(s, "cu_states", 8, st) || !need(s, "cu_i32", 7, ci) || !need(s, "cu_f64", 6, cf) ||
+      !need(s, "thr_misc", 2, misc) || !need(s, "apple_thr", 1, athr, &n) ||
+      !need_cells(s, t, "apple_cells", 256, acells, na) ||
+      !need_cells(s, t, "dirt_cells", 256, dcells, nd2) ||
+      !need_cells(s, t, "water_cells", 256, wcells, nw))
+    return MP_ERR_PACK;
+  c.zap = s.zap;
+  c.clean_hit = find_name(s.hp, "hit_names", "cleanHit");
+  if (n != nd2 + 1 || d->nhits != 2 || c.clean_hit < 0 || !in_range(st, 8, 1, t.nstates))
+    return fail(MP_ERR_PACK, "mp_create: clean_up tables missing or inconsistent");
+  c.apple_cells = s.at(acells); c.n_apple = (int)na;
+  c.dirt_cells = s.at(dcells); c.n_dirt = (int)nd2;
+  c.water_cells = s.at(wcells); c.n_water = (int)nw;
+  c.apple_thr = s.at(athr);
+  c.thr_dirt_spawn = misc[0]; c.thr_episode_end = misc[1];
+  c.s_apple = st[0]; c.s_apple_wait = st[1]; c.s_dirt = st[2]; c.s_dirt_wait = st[3];
+  c.s_water_packed = 0;
+  for (int i = 0; i < 4; ++i) {
+    c.s_water[i] = st[4 + i];
+    c.s_water_packed |= (uint32_t)(st[4 + i] & 255) << (8 * i);
+  }
+  c.apple_layer = s.slayer[c.s_apple]; c.dirt_layer = s.slayer[c.s_dirt];
+  c.dirt_wait_layer = s.slayer[c.s_dirt_wait]; c.water_layer = s.slayer[c.s_water[0]];
+  c.s_clean_hit = s.hit_state[c.clean_hit];
+  c.clean_layer = s.slayer[c.s_clean_hit];
+  c.clean_cooldown = ci[0]; c.clean_length = ci[1]; c.clean_radius = ci[2];
+  c.dirt_delay = ci[3]; c.ee_min_frames = ci[4]; c.ee_interval = ci[5];
+  c.anim_frames = ci[6];
+  c.eat_reward = cf[5];
+  if (c.clean_cooldown > 255 || s.slayer[c.s_apple_wait] >= 0 ||
+      c.apple_layer < 0 || c.dirt_layer < 0 || c.dirt_wait_layer < 0 || c.water_layer < 0 ||
+      make_shape(c.clean_length, c.clean_radius, &c.clean_shape) > 16 ||
+      !only_beams_on(s, t, c.clean_layer, c.s_clean_hit) || c.ee_interval <= 0 || c.anim_frames <= 0)
+    return fail(MP_ERR_PACK, "mp_create: clean_up constants out of engine range");
+  const uint8_t* ig = table<uint8_t>(s.hp, "init_grid");
+  c.n_dirt_init = 0;
+  for (int i = 0; i < t.H * t.W; ++i) c.n_dirt_init += ig[c.dirt_layer * t.H * t.W + i] == c.s_dirt;
+  return MP_OK;
+}
+
+int load_commons_harvest(Src& s, const DevTables& t, DecodedPack* d) {
+  CommonsTables& c = d->sub.ch;
+  const int32_t *st, *ci, *disc, *cells; const double* cf;
+  const uint64_t* thr; uint64_t n = 0, nd = 0, ncells = 0;
+  if (!need(s, "ch_states", 5, st) || !need(s, "ch_i32", 4, ci) || !need(s, "ch_f64", 1, cf) ||
+      !need(s, "ch_thr", 2, thr, &n) || !need(s, "disc_offsets", 2, disc, &nd) ||
+      !need_cells(s, t, "apple_cells", 256, cells, ncells))
+    return MP_ERR_PACK;
+  c.zap = s.zap;
+  if (!table_n<int32_t>(s.hp, "ch_states", ci[0] > 0 && ci[0] <= 32 ? 4 + ci[0] : 4) ||
+      !in_range(st, 4, 1, t.nstates))
+    return fail(MP_ERR_PACK, "mp_create: commons_harvest tables missing");
+  c.apple_cells = s.at(cells); c.n_apple = (int)ncells;
+  c.nk = ci[0]; c.ee_min_frames = ci[1]; c.ee_interval = ci[2];
+  if (c.nk > 32 || c.nk < 1 || ci[3] != 1 || c.ee_interval <= 0)
+    return fail(MP_ERR_PACK, "mp_create: commons_harvest constants out of engine range");
+  c.s_apple = st[0]; c.s_wait = st[1]; c.s_grass = st[2]; c.s_dess = st[3];
+  if (!in_range(st + 4, c.nk, 1, t.nstates))
+    return fail(MP_ERR_PACK, "mp_create: appleWait_k states out of range");
+  for (int k = 0; k < c.nk; ++k) c.s_wait_k[k] = st[4 + k];
+  c.live_layer = s.slayer[c.s_apple]; c.wait_layer = s.slayer[c.s_wait];
+  c.grass_layer = s.slayer[c.s_grass];
+  c.eat_reward = cf[0];
+  c.disc = s.at(disc); c.ndisc = (int)(nd / 2);
+  if ((int)n != c.nk + 1 || c.ndisc + 1 > c.nk || c.ndisc > 64 ||
+      !in_range(disc, (uint64_t)c.ndisc * 2, -8, 9) ||
+      c.live_layer < 0 || c.wait_layer < 0 || s.slayer[c.s_dess] != c.grass_layer)
+    return fail(MP_ERR_PACK, "mp_create: commons_harvest tables inconsistent");
+  for (int k = 0; k < c.nk; ++k)
+    if (s.slayer[c.s_wait_k[k]] != c.wait_layer)
+      return fail(MP_ERR_PACK, "mp_create: appleWait_k states on different layers");
+  c.thr = s.at(thr);
+  return MP_OK;
+}
+
+int load_territory(Src& s, const DevTables& t, DecodedPack* d) {
+  TerritoryTables& c = d->sub.tr;
+  const int P = t.P_pack;   // table strides; absent players' states are never on the grid
+  const int32_t *st, *ci, *hits, *cells; const double* cf; const uint64_t* thr; uint64_t n = 0;
+  if (!need(s, "tr_states", 10 + 2 * (uint64_t)P, st) || !need(s, "tr_i32", 16, ci) ||
+      !need(s, "tr_f64", 8, cf) || !need(s, "tr_thr", 3, thr) ||
+      !need(s, "tr_hits", 1 + 2 * (uint64_t)P, hits) ||
+      !need_cells(s, t, "resource_cells", 256, cells, n))   // 4 per lane, step_territory.h
+    return MP_ERR_PACK;
+  c.zap = s.zap;
+  if (!in_range(st, 10 + 2 * (uint64_t)P, 1, t.nstates) || !in_range(hits, 1 + 2 * (uint64_t)P, 0, d->nhits))
+    return fail(MP_ERR_PACK, "mp_create: territory tables missing");
+  const int32_t* hsd = table<int32_t>(s.hp, "hit_state_dir");
+  c.res_cells = s.at(cells); c.n_res = (int)n;
+  c.map_cells = t.H * t.W;
+  c.s_res_unclaimed = st[0]; c.s_dmg_inactive = st[5]; c.s_dmg_damaged = st[6];
+  c.s_mark[0] = st[7]; c.s_mark[1] = st[8];
+  for (int p = 0; p < P; ++p) { c.s_claimed[p] = st[10 + p]; c.s_dry[p] = st[10 + P + p]; }
+  c.res_layer = s.slayer[st[0]]; c.tex_layer = s.slayer[st[2]];
+  c.ind_layer = s.slayer[c.s_dry[0]]; c.dmg_layer = s.slayer[st[5]]; c.mark_layer = s.slayer[st[7]];
+  c.plane_a = t.L; c.plane_b = t.L + 1; c.plane_c = t.L + 2;
+  c.initial_health = ci[0]; c.reward_delay = ci[1]; c.repair_delay = ci[2];
+  c.claim_length = ci[3]; c.claim_wait = ci[5]; c.recovery_time = ci[6];
+  c.ee_min_frames = ci[8]; c.ee_interval = ci[9];
+  if (ci[7] != 2 || ci[4] != 0 || c.initial_health > 3 || c.claim_length < 1 ||
+      c.claim_length * t.P > 64 || c.ee_interval <= 0 || s.zap.remove_hit || c.res_layer != t.avatar_layer ||
+      s.slayer[st[1]] >= 0 || s.slayer[st[3]] >= 0 || s.slayer[st[4]] >= 0 || s.slayer[st[9]] >= 0)
+    return fail(MP_ERR_PACK, "mp_create: territory constants out of engine range");
+  for (int l = 0; l < 2; ++l) {
+    c.lv_increment[l] = ci[10 + 3 * l]; c.lv_freeze[l] = ci[11 + 3 * l];
+    c.lv_remove[l] = ci[12 + 3 * l];
+    c.lv_source[l] = cf[4 + 2 * l]; c.lv_target[l] = cf[5 + 2 * l];
+    if (c.lv_freeze[l] > 255) return fail(MP_ERR_PACK, "mp_create: freeze too long");
+  }
+  c.reward = cf[0];
+  c.thr_reward = thr[0]; c.thr_repair = thr[1]; c.thr_ee = thr[2];
+  c.hit_zap = hits[0];
+  for (int p = 0; p < P; ++p) {
+    c.hit_brush[p] = hits[1 + p]; c.hit_claim[p] = hits[1 + P + p];
+    for (int dir = 0; dir < 4; ++dir) c.s_brush[p][dir] = hsd[c.hit_brush[p] * 4 + dir];
+    c.s_claim_hit[p] = s.hit_state[c.hit_claim[p]];
+  }
+  c.brush_layer = s.slayer[c.s_brush[0][0]]; c.claim_layer = s.slayer[c.s_claim_hit[0]];
+  for (int s2 = 1; s2 < t.nstates; ++s2) {  // hit layers hold nothing but beam sprites
+    bool is_hit = false;
+    for (int h = 0; h < d->nhits * 4; ++h) is_hit = is_hit || hsd[h] == s2;
+    if (!is_hit && (s.slayer[s2] == c.brush_layer || s.slayer[s2] == c.claim_layer))
+      return fail(MP_ERR_PACK, "mp_create: a piece state lives on a territory hit layer");
+  }
+  return MP_OK;
+}
+
+int load_coins(Src& s, const DevTables& t, DecodedPack* d) {
+  CoinsTables& c = d->sub.co;
+  const int32_t *st, *ci, *cells; const double* cf; const uint64_t* thr; uint64_t n = 0;
+  if (!need(s, "co_states", 3, st) || !need(s, "co_i32", 4, ci) || !need(s, "co_f64", 8, cf) ||
+      !need(s, "co_thr", 2, thr) || !need_cells(s, t, "coin_cells", 512, cells, n))
+    return MP_ERR_PACK;
+  if (t.P != 2 || t.P_pack != 2 || !in_range(st, 3, 1, t.nstates))
+    return fail(MP_ERR_PACK, "mp_create: coins tables missing or out of engine range");
+  c.coin_cells = s.at(cells); c.n_coin = (int)n;
+  c.s_coin[0] = st[0]; c.s_coin[1] = st[1]; c.s_wait = st[2];
+  c.coin_layer = s.slayer[st[0]]; c.wait_layer = s.slayer[st[2]];
+  if (s.slayer[st[1]] != c.coin_layer || c.coin_layer < 0 || c.wait_layer < 0 ||
+      c.coin_layer == t.avatar_layer)
+    return fail(MP_ERR_PACK, "mp_create: coins layers out of engine range");
+  for (int p = 0; p < t.P; ++p) {
+    c.player_type[p] = ci[p];
+    for (int k = 0; k < 4; ++k) c.rew[p][k] = cf[4 * p + k];
+  }
+  c.ee_min_frames = ci[t.P]; c.ee_interval = ci[t.P + 1];
+  c.thr_regrow = thr[0]; c.thr_ee = thr[1];
+  if (c.ee_interval <= 0) return fail(MP_ERR_PACK, "mp_create: coins constants out of range");
+  const int32_t* cc = table_n<int32_t>(s.hp, "co_colour_coin", 5);
+  const int32_t* ca = table_n<int32_t>(s.hp, "co_colour_alive", 10);
+  c.has_colours = cc && ca;
+  if (c.has_colours) {
+    c.colour_coin = c.colour_alive[0] = c.colour_alive[1] = 0;
+    for (int k = 0; k < 5; ++k) {
+      c.colour_coin |= (uint64_t)(uint8_t)cc[k] << (8 * k);
+      c.colour_alive[0] |= (uint64_t)(uint8_t)ca[k] << (8 * k);
+      c.colour_alive[1] |= (uint64_t)(uint8_t)ca[5 + k] << (8 * k);
+      if (cc[k] < 1 || cc[k] >= t.nstates || s.slayer[cc[k]] != c.coin_layer || ca[k] < 1 ||
+          ca[k] >= t.nstates || ca[5 + k] < 1 || ca[5 + k] >= t.nstates ||
+          s.slayer[ca[k]] != t.avatar_layer || s.slayer[ca[5 + k]] != t.avatar_layer)
+        return fail(MP_ERR_PACK, "mp_create: coins colour tables out of range");
+    }
+  }
+  return MP_OK;
+}
+
+// TheMatrix:getColorInterval asserts that an interval holds the reward
+// (components.lua:282-290); the kernel cannot assert, so the pack must make
+// the assertion unreachable: a reward is rewardMultiplier x a convex
+// combination of matrix entries (or 0 with an empty inventory), and every
+// point of that range has to lie in one of the [lo, hi) intervals.
+int check_colour_intervals(const MatrixTables& c) {
+  const int R = c.R;
+  double lo = 0.0, hi = 0.0;
+  for (int i = 0; i < R * R; ++i)
+    for (double v : {c.reward_multiplier * c.row_matrix[i], c.reward_multiplier * c.col_matrix[i]}) {
+      lo = std::min(lo, v); hi = std::max(hi, v);
+    }
+  auto covered = [&](double x) {
+    for (int k = 0; k < c.n_intervals; ++k)
+      if (c.interval[2 * k] <= x && x < c.interval[2 * k + 1]) return true;
+    return false;
+  };
+  // (the two extreme payoffs themselves need pure profiles on both sides;
+  // the stock intervals end exactly there, half-open, and the reference would
+  // assert if one were ever paid: the kernel reports that case through the
+  // fault words instead — sync_and_check — and every other reward is checked
+  // here: each stretch between neighbouring interval bounds inside (lo, hi))
+  std::vector<double> cuts = {lo, hi};
+  for (int k = 0; k < 2 * c.n_intervals; ++k)
+    if (c.interval[k] > lo && c.interval[k] < hi) cuts.push_back(c.interval[k]);
+  std::sort(cuts.begin(), cuts.end());
+  bool ok = true;
+  for (size_t i = 0; ok && i + 1 < cuts.size(); ++i) {
+    if (cuts[i] == cuts[i + 1]) continue;
+    ok = covered(0.5 * (cuts[i] + cuts[i + 1])) && (i == 0 || covered(cuts[i]));
+  }
+  if (!ok)
+    return fail(MP_ERR_PACK, "mp_create: resultIndicatorColorIntervals do not cover the rewards "
+                             "(%g, %g) this matrix and rewardMultiplier can pay "
+                             "(the reference asserts, components.lua:282-290)", lo, hi);
+  return MP_OK;
+}
+
+// The marker, resource and beam states of the_matrix and the layers they live on.
+int check_matrix_layers(const Src& s, const DevTables& t, MatrixTables& c, const int32_t* st) {
+  // marker states in indicator order: notReady, ready, colour 1..5 (mx_states:
+  // wait, ready, notReady, colours); resource states per class: visible, wait
+  const int mark_wait = st[0];
+  const int by_ind[7] = {st[2], st[1], st[3], st[4], st[5], st[6], st[7]};
+  c.s_mark_packed = 0;
+  c.mark_layer = s.slayer[st[2]];
+  for (int i = 0; i < 7; ++i) {
+    c.s_mark_packed |= (uint64_t)by_ind[i] << (8 * i);
+    // 'notReady' draws nothing but sits on the overlay layer like the others
+    if (s.slayer[by_ind[i]] != c.mark_layer)
+      return fail(MP_ERR_PACK, "mp_create: the_matrix marker states on different layers");
+  }
+  c.s_visible_packed = 0;
+  c.res_layer = s.slayer[st[8]];
+  for (int k = 0; k < c.R; ++k) {
+    c.s_visible_packed |= (uint32_t)st[8 + 2 * k] << (8 * k);
+    if (s.slayer[st[8 + 2 * k]] != c.res_layer || s.slayer[st[9 + 2 * k]] >= 0)
+      return fail(MP_ERR_PACK, "mp_create: the_matrix resource states on unexpected layers");
+  }
+  if (s.slayer[mark_wait] >= 0 || c.mark_layer < 0 || c.res_layer < 0 || c.beam_layer < 0 ||
+      c.mark_layer == t.avatar_layer || c.res_layer == t.avatar_layer ||
+      !only_beams_on(s, t, c.beam_layer, c.s_beam))
+    return fail(MP_ERR_PACK, "mp_create: the_matrix layers out of engine range");
+  // the overlay layer holds markers only, the resource layer resources only
+  for (int s2 = 1; s2 < t.nstates; ++s2) {
+    bool is_mark = false, is_res = false;
+    for (int i = 0; i < 7; ++i) is_mark = is_mark || s2 == by_ind[i];
+    for (int k = 0; k < c.R; ++k) is_res = is_res || s2 == st[8 + 2 * k];
+    if ((s.slayer[s2] == c.mark_layer && !is_mark) || (s.slayer[s2] == c.res_layer && !is_res))
+      return fail(MP_ERR_PACK, "mp_create: the_matrix: a foreign state on the marker / resource layer");
+  }
+  return MP_OK;
+}
+
+int load_the_matrix(Src& s, const DevTables& t, DecodedPack* d) {
+  MatrixTables& c = d->sub.mx;
+  // the table lengths follow from R (resource classes) and the number of colour
+  // intervals, both in mx_i32
+  const int32_t* ci = table_n<int32_t>(s.hp, "mx_i32", 22);
+  if (!ci || ci[0] < 1 || ci[0] > stepk::kMxMaxR || ci[19] < 1 || ci[19] > 5 || ci[16] <= 0 ||
+      ci[18] < 1 || ci[18] > 3 || ci[21] < 0 || ci[21] >= d->nhits)
+    return fail(MP_ERR_PACK, "mp_create: table 'mx_i32' is missing or holds constants out of range");
+  const int R = ci[0];
+  const uint64_t R2 = (uint64_t)R, NI = (uint64_t)ci[19], PP = (uint64_t)t.P_pack;
+  uint64_t ncl = 0, ns = 0, nst = 0, nf = 0;
+  const int32_t* cls = table<int32_t>(s.hp, "resource_class", &ncl);
+  (void)table<int32_t>(s.hp, "resource_cells", &ns);
+  const int32_t* st = table<int32_t>(s.hp, "mx_states", &nst);
+  if (!cls || ncl != ns || !in_range(cls, ncl, 1, R + 1))
+    return fail(MP_ERR_PACK, "mp_create: table 'resource_class' does not match 'resource_cells'");
+  if (!st || nst != 8 + 2 * R2 || !in_range(st, nst, 1, t.nstates))
+    return fail(MP_ERR_PACK, "mp_create: table 'mx_states' holds a state out of range");
+  const int32_t *pi, *cells; const double *cf, *pf; const uint64_t* thr;
+  if (!need(s, "mx_f64", 5 + 2 * R2 * R2 + 2 * NI, cf, &nf) || !need(s, "mx_thr", 2, thr) ||
+      !need(s, "mx_player_i32", 4 * PP, pi) || !need(s, "mx_player_f64", 4 * PP, pf) ||
+      !need(s, "resource_class", 1, cls) || !need_cells(s, t, "resource_cells", 128, cells, ns))
+    return MP_ERR_PACK;
+  if (nf != 5 + 2 * R2 * R2 + 2 * NI)
+    return fail(MP_ERR_PACK, "mp_create: the_matrix tables inconsistent");
+  c.R = R;
+  c.n_site = (int)ns;
+  c.site_cells = s.at(cells); c.site_class = s.at(cls);
+  c.player_i32 = s.at(pi); c.player_f64 = s.at(pf);
+  c.cooldown = ci[1]; c.respawn_frames = ci[4]; c.freeze = ci[5]; c.end_on_first = ci[6];
+  c.reset_winner = ci[7]; c.reset_loser = ci[8]; c.loser_dies = ci[9]; c.winner_dies = ci[10];
+  c.zero_inventory = ci[11]; c.random_tie = ci[12]; c.disallow_unready = ci[13];
+  c.has_ee = ci[14]; c.ee_min_frames = ci[15]; c.ee_interval = ci[16];
+  c.regen_delay = ci[17]; c.initial_health = ci[18]; c.n_intervals = ci[19];
+  c.spawn_all = ci[20]; c.hit = ci[21];
+  c.reward_floor = cf[0]; c.reward_multiplier = cf[1]; c.reward_unready = cf[2];
+  for (int i = 0; i < R * R; ++i) { c.row_matrix[i] = cf[5 + i]; c.col_matrix[i] = cf[5 + R * R + i]; }
+  for (int i = 0; i < 2 * c.n_intervals; ++i) c.interval[i] = cf[5 + 2 * R * R + i];
+  c.thr_regen = thr[0]; c.thr_ee = thr[1];
+  if (int rc = check_colour_intervals(c)) return rc;
+  if (c.cooldown < 1 || c.cooldown > 255 || c.freeze < 0 || c.freeze > 200 ||
+      c.respawn_frames < 0 || (c.regen_delay > 250 && c.thr_regen != 0) ||
+      make_shape(ci[2], ci[3], &c.shape) > 16)
+    return fail(MP_ERR_PACK, "mp_create: the_matrix constants out of engine range");
+  if (c.regen_delay > 255) c.regen_delay = 255;   // (never reached: the rate is 0)
+  c.s_beam = s.hit_state[c.hit]; c.beam_layer = s.slayer[c.s_beam];
+  if (int rc = check_matrix_layers(s, t, c, st)) return rc;
+  c.plane_a = t.L; c.plane_b = t.L + 1;
+  if (t.W > 255 || t.H > 255) return fail(MP_ERR_PACK, "mp_create: the_matrix map too large");
+  return MP_OK;
+}
+
+int load_coop_mining(Src& s, const DevTables& t, DecodedPack* d) {
+  CoopTables& c = d->sub.cm;
+  const int32_t *st, *ci, *cells; const double* cf; const uint64_t* thr; uint64_t n = 0;
+  if (!need(s, "cm_states", 5, st) || !need(s, "cm_i32", 10, ci) ||
+      !need(s, "cm_f64", 4 * (uint64_t)t.P_pack, cf) || !need(s, "cm_thr", 3, thr) ||
+      !need_cells(s, t, "ore_cells", 640, cells, n))
+    return MP_ERR_PACK;
+  if (!in_range(st, 5, 1, t.nstates)) return fail(MP_ERR_PACK, "mp_create: coop_mining tables missing");
+  c.ore_cells = s.at(cells); c.n_ore = (int)n;
+  c.reward = s.at(cf);
+  for (int k = 0; k < 3; ++k) c.thr[k] = thr[k];
+  c.s_wait = st[0]; c.s_raw[0] = st[1]; c.s_raw[1] = st[2]; c.s_partial[0] = st[3]; c.s_partial[1] = st[4];
+  c.cooldown = ci[0]; c.hit = ci[3]; c.ee_min_frames = ci[4]; c.ee_interval = ci[5];
+  c.min_miners1 = ci[8]; c.window1 = ci[9];
+  c.ore_layer = s.slayer[c.s_wait];
+  // (type 0: extracted by the hit that mines it — one miner, no partial state of its own;
+  // type 1's miners are a byte mask: the Lua's minNumMiners doubles as the type index)
+  if (ci[6] != 1 || c.s_partial[0] != c.s_raw[0] || c.min_miners1 < 2 || c.min_miners1 > t.P_pack ||
+      t.P_pack > 8 || c.window1 < 1 || c.window1 > 255 || c.cooldown < 1 || c.cooldown > 255 ||
+      c.hit < 0 || c.hit >= d->nhits || c.ee_interval <= 0 || c.ore_layer < 0 ||
+      c.ore_layer == t.avatar_layer || make_shape(ci[1], ci[2], &c.shape) > 16)
+    return fail(MP_ERR_PACK, "mp_create: coop_mining constants out of engine range");
+  for (int k = 1; k < 5; ++k)
+    if (s.slayer[st[k]] != c.ore_layer)
+      return fail(MP_ERR_PACK, "mp_create: coop_mining ore states on different layers");
+  c.s_beam = s.hit_state[c.hit]; c.beam_layer = s.slayer[c.s_beam];
+  if (c.beam_layer < 0 || c.beam_layer == c.ore_layer || c.beam_layer == t.avatar_layer)
+    return fail(MP_ERR_PACK, "mp_create: coop_mining beam layer out of engine range");
+  c.plane_m = t.L; c.plane_c = t.L + 1;
+  return MP_OK;
+}
+
+int load_collaborative_cooking(Src& s, const DevTables& t, DecodedPack* d) {
+  CookTables& c = d->sub.cc;
+  const int32_t *st, *ci, *ps, *bs, *hits, *cont, *pots, *recv; const double* cf;
+  const uint8_t* kind; uint64_t n_cont = 0, n_pot = 0, n_recv = 0, n_ci = 0, n_ri = 0, n_rf = 0;
+  if (!need(s, "cc_inv_states", 4, st) || !need(s, "cc_i32", 3, ci) || !need(s, "cc_f64", 1, cf) ||
+      !need(s, "cc_pot_states", 5, ps) || !need(s, "cc_bar_states", 11, bs) ||
+      !need(s, "cc_hits", (uint64_t)t.P_pack, hits) ||
+      !need(s, "cc_state_kind", (uint64_t)t.nstates, kind) ||
+      !need_cells(s, t, "cc_container_cells", 128, cont, n_cont) ||
+      !need_cells(s, t, "cc_pot_cells", 64, pots, n_pot) ||
+      !need_cells(s, t, "cc_receiver_cells", 64, recv, n_recv))
+    return MP_ERR_PACK;
+  const int32_t* cont_i = table<int32_t>(s.hp, "cc_container_i32", &n_ci);
+  const int32_t* recv_i = table<int32_t>(s.hp, "cc_receiver_i32", &n_ri);
+  const double* recv_f = table<double>(s.hp, "cc_receiver_f64", &n_rf);
+  if (n_ci != 2 * n_cont || n_ri != 2 * n_recv || n_rf != n_recv || !in_range(ps, 5, 1, t.nstates) ||
+      !in_range(bs, 11, 1, t.nstates) || !in_range(st, 4, 1, t.nstates) ||
+      !in_range(hits, (uint64_t)t.P_pack, 0, d->nhits))
+    return fail(MP_ERR_PACK, "mp_create: collaborative_cooking tables missing");
+  c.state_kind = s.at(kind);
+  c.n_cont = (int)n_cont; c.n_pot = (int)n_pot;
+  c.cont_cells = n_cont ? s.at(cont) : nullptr;
+  c.cont_i32 = n_cont ? s.at(cont_i) : nullptr;
+  c.pot_cells = n_pot ? s.at(pots) : nullptr;
+  for (int k = 0; k < 5; ++k) c.s_pot[k] = ps[k];
+  c.s_bar0 = bs[0];
+  c.s_plain0 = st[1]; c.s_off0 = st[2]; c.s_dir0 = st[3];
+  c.overlay_layer = s.slayer[c.s_plain0];
+  c.plane_t = t.L;
+  c.cooldown = ci[0]; c.cooking_time = ci[1]; c.bar_interval = ci[2];
+  c.pot_reward = cf[0];
+  c.recv_item = n_recv ? recv_i[0] : -1; c.recv_global = n_recv ? recv_i[1] : 0;
+  c.recv_reward = n_recv ? recv_f[0] : 0.0;
+  c.s_beam0 = s.hit_state[hits[0]]; c.beam_layer0 = s.slayer[c.s_beam0];
+  bool ok = c.s_plain0 + 4 <= t.nstates && c.s_off0 + 4 <= t.nstates && c.s_dir0 + 12 <= t.nstates &&
+            c.overlay_layer >= 0 && c.overlay_layer != t.avatar_layer && c.cooldown <= 255 &&
+            c.cooking_time >= 1 && c.cooking_time <= 30 && c.bar_interval >= 1;
+  for (int k = 0; ok && k < 11; ++k) ok = bs[k] == bs[0] + k && s.slayer[bs[k]] == c.overlay_layer;
+  for (int k = 0; ok && k < 4; ++k)
+    ok = s.slayer[c.s_plain0 + k] == c.overlay_layer && s.slayer[c.s_off0 + k] == c.overlay_layer;
+  for (int k = 0; ok && k < 12; ++k) ok = s.slayer[c.s_dir0 + k] == c.overlay_layer;
+  for (int k = 0; ok && k < 5; ++k) ok = s.slayer[ps[k]] == t.avatar_layer;
+  for (int p = 0; ok && p < t.P_pack; ++p)
+    ok = s.hit_state[hits[p]] == c.s_beam0 + p && s.slayer[c.s_beam0 + p] == c.beam_layer0 + p &&
+         c.beam_layer0 + p < t.L && c.beam_layer0 + p != c.overlay_layer && c.beam_layer0 + p != t.avatar_layer;
+  for (uint64_t i = 0; ok && i < n_cont; ++i) ok = cont_i[2 * i] >= 0 && cont_i[2 * i] < 4;
+  for (uint64_t i = 1; ok && i < n_recv; ++i)
+    ok = recv_i[2 * i] == recv_i[0] && recv_i[2 * i + 1] == recv_i[1] && recv_f[i] == recv_f[0];
+  if (!ok) return fail(MP_ERR_PACK, "mp_create: collaborative_cooking constants out of engine range");
+  return MP_OK;
+}
+
+int load_gift_refinements(Src& s, const DevTables& t, DecodedPack* d) {
+  GiftTables& c = d->sub.gr;
+  const int32_t *st, *ci, *cells; const double* cf; const uint64_t* thr; uint64_t n = 0;
+  if (!need(s, "gr_states", 2, st) || !need(s, "gr_i32", 10, ci) ||
+      !need(s, "gr_f64", 2 * (uint64_t)t.P_pack + 3, cf) || !need(s, "gr_thr", 2, thr) ||
+      !need_cells(s, t, "token_cells", 640, cells, n))
+    return MP_ERR_PACK;
+  if (!in_range(st, 2, 1, t.nstates)) return fail(MP_ERR_PACK, "mp_create: gift_refinements tables missing");
+  c.token_cells = s.at(cells); c.n_token = (int)n;
+  c.reward = s.at(cf);
+  c.pick_reward = cf[2 * t.P_pack];
+  c.thr[0] = thr[0]; c.thr[1] = thr[1];
+  c.s_wait = st[0]; c.s_live = st[1];
+  c.cooldown = ci[0]; c.hit = ci[3]; c.ee_min_frames = ci[4]; c.ee_interval = ci[5];
+  c.capacity = ci[6]; c.ntypes = ci[7]; c.multiplier = ci[8]; c.consume_cooldown = ci[9];
+  c.token_layer = s.slayer[c.s_live];
+  // (an event row carries player | type << 4 and player | count << 4 in a byte each)
+  if (c.capacity < 1 || c.capacity > 15 || c.ntypes < 1 || c.ntypes > 3 || c.multiplier < 1 ||
+      c.multiplier > 255 || c.consume_cooldown < 0 || c.consume_cooldown > 255 || t.P_pack > 15 ||
+      c.cooldown < 1 || c.cooldown > 255 || c.hit < 0 || c.hit >= d->nhits || c.ee_interval <= 0 ||
+      c.token_layer < 0 || c.token_layer == t.avatar_layer || s.slayer[c.s_wait] != c.token_layer ||
+      make_shape(ci[1], ci[2], &c.shape) > 16)
+    return fail(MP_ERR_PACK, "mp_create: gift_refinements constants out of engine range");
+  c.s_beam = s.hit_state[c.hit]; c.beam_layer = s.slayer[c.s_beam];
+  if (c.beam_layer < 0 || c.beam_layer == c.token_layer || c.beam_layer == t.avatar_layer)
+    return fail(MP_ERR_PACK, "mp_create: gift_refinements beam layer out of engine range");
+  return MP_OK;
+}
+
+int load_externality_mushrooms(Src& s, const DevTables& t, DecodedPack* d) {
+  MushroomTables& c = d->sub.em;
+  const ZapRules& zap = s.zap;
+  const int32_t *st, *ci, *cells; const double* cf; const uint64_t* thr; uint64_t n = 0;
+  if (!need(s, "em_states", 8, st) || !need(s, "em_i32", 30, ci) || !need(s, "em_f64", 8, cf) ||
+      !need(s, "em_thr", 21, thr) || !need_cells(s, t, "mushroom_cells", 256, cells, n))   // 4 per lane, step_mushroom.h
+    return MP_ERR_PACK;
+  c.zap = zap;
+  if (n < 1 || !in_range(st, 8, 1, t.nstates))
+    return fail(MP_ERR_PACK, "mp_create: externality_mushrooms tables missing");
+  c.site_cells = s.at(cells); c.n_site = (int)n;
+  c.i32 = s.at(ci); c.thr = s.at(thr);
+  c.s_type0 = st[0]; c.live_layer = s.slayer[st[0]];
+  c.s_mark[0] = st[5]; c.s_mark[1] = st[6]; c.mark_layer = s.slayer[st[5]];
+  c.plane_age = t.L;
+  c.min_potential = ci[0]; c.recovery_time = ci[2];
+  c.ee_min_frames = ci[4]; c.ee_interval = ci[5]; c.n_live_init = ci[7];
+  bool ok = st[1] == st[0] + 1 && st[2] == st[0] + 2 && st[3] == st[0] + 3 &&
+            s.slayer[st[4]] < 0 && s.slayer[st[7]] < 0 && s.slayer[st[6]] == c.mark_layer &&
+            c.live_layer >= 0 && c.mark_layer >= 0 && c.live_layer != t.avatar_layer &&
+            c.mark_layer != t.avatar_layer && c.live_layer != c.mark_layer &&
+            ci[1] == 1 && ci[3] == 2 && ci[6] == zap.hit && c.ee_interval > 0 &&
+            c.recovery_time >= 1 && c.recovery_time <= 255 && c.n_live_init >= 0 &&
+            c.n_live_init <= (int)n && !zap.remove_hit && zap.penalty == 0.0 && zap.reward == 0.0 &&
+            zap.respawn_frames >= 1 && t.n_optional == 0 && t.P >= 2;
+  // the mushrooms' plane and the markings' hold nothing else, every mushroom site starts
+  // on the map as the object table says
+  for (int s2 = 1; s2 < t.nstates && ok; ++s2) {
+    if (s.slayer[s2] == c.live_layer && (s2 < st[0] || s2 > st[3])) ok = false;
+    if (s.slayer[s2] == c.mark_layer && s2 != st[5] && s2 != st[6]) ok = false;
+  }
+  c.perish_packed = 0;
+  for (int k = 0; k < 4 && ok; ++k) {
+    const int delay = ci[16 + k];   // (the age plane saturates at 255)
+    ok = ci[8 + k] >= 0 && ci[8 + k] <= 4 && ci[12 + k] >= 0 && ci[12 + k] <= 255 &&
+         delay >= 1 && (delay <= 254 || delay >= (1 << 30)) && ci[20 + k] >= -1 && ci[20 + k] < 4;
+    c.perish_packed |= (uint32_t)(delay <= 254 ? delay : 255) << (8 * k);
+  }
+  if (!ok) return fail(MP_ERR_PACK, "mp_create: externality_mushrooms constants out of engine range");
+  for (int l = 0; l < 2; ++l) {
+    c.lv_increment[l] = ci[24 + 3 * l]; c.lv_freeze[l] = ci[25 + 3 * l];
+    c.lv_remove[l] = ci[26 + 3 * l];
+    c.lv_source[l] = cf[4 + 2 * l]; c.lv_target[l] = cf[5 + 2 * l];
+    if (c.lv_freeze[l] < 0 || c.lv_freeze[l] > 255 || c.lv_increment[l] < -1 || c.lv_increment[l] > 1)
+      return fail(MP_ERR_PACK, "mp_create: externality_mushrooms sanction levels out of engine range");
+  }
+  // _rewardEveryone (components.lua:65-105) with this engine's player count
+  c.pays = 0;
+  for (int k = 0; k < 4; ++k) { c.rew_self[k] = 0.0; c.rew_other[k] = 0.0; }
+  c.rew_self[0] = cf[0]; c.pays |= 1u;
+  c.rew_self[1] = c.rew_other[1] = cf[1] / (double)t.P; c.pays |= (1u << 1) | (1u << 5);
+  c.rew_other[2] = cf[2] / (double)(t.P - 1); c.pays |= 1u << 6;
+  c.rew_self[3] = c.rew_other[3] = cf[3] / (double)t.P; c.pays |= (1u << 3) | (1u << 7);
+  c.thr_ee = thr[20];
+  return MP_OK;
+}
+
+// The substrates this build runs: loader, hidden planes behind the render planes (territory:
+// three per-cell resource planes, the matrix levels two and a block of per-player variables)
+// and the stock Zapper (coins avatars carry none, GameInteractionZapper has its own tables).
+struct Substrate {
+  int (*load)(Src&, const DevTables&, DecodedPack*);
+  int hidden_planes;
+  bool zapper;
+};
+
+int substrate_of(int id, Substrate* out) {
+  switch (id) {
+    case MPK_SUBSTRATE_CLEAN_UP: *out = {load_clean_up, 0, true}; return MP_OK;
+    case MPK_SUBSTRATE_COMMONS_HARVEST: *out = {load_commons_harvest, 0, true}; return MP_OK;
+    case MPK_SUBSTRATE_TERRITORY: *out = {load_territory, 3, true}; return MP_OK;
+    case MPK_SUBSTRATE_COINS: *out = {load_coins, 0, false}; return MP_OK;
+    case MPK_SUBSTRATE_THE_MATRIX: *out = {load_the_matrix, 2, false}; return MP_OK;
+    case MPK_SUBSTRATE_COOP_MINING: *out = {load_coop_mining, 2, false}; return MP_OK;
+    case MPK_SUBSTRATE_COLLABORATIVE_COOKING: *out = {load_collaborative_cooking, 1, false}; return MP_OK;
+    case MPK_SUBSTRATE_GIFT_REFINEMENTS: *out = {load_gift_refinements, 0, false}; return MP_OK;
+    case MPK_SUBSTRATE_EXTERNALITY_MUSHROOMS: *out = {load_externality_mushrooms, 1, true}; return MP_OK;
+    default: return fail(MP_ERR_PACK, "mp_create: substrate %d is not supported by this build", id);
+  }
+}
+
+}  // namespace
+
+int check_header(const void* pack, uint64_t pack_len, const MpConfig& cfg, const int32_t** out) {
+  if (mpk_validate(pack, pack_len) != 0)
+    return fail(MP_ERR_PACK, "mp_create: not a valid MPK1 pack");
+  const int32_t* hdr = table_n<int32_t>(pack, "hdr", MPK_HDR_LEN);
+  if (!hdr || hdr[MPK_HDR_VERSION] != 1)
+    return fail(MP_ERR_PACK, "mp_create: unsupported pack version");
+  Substrate sub;
+  if (int rc = substrate_of(hdr[MPK_HDR_SUBSTRATE], &sub)) return rc;
+  if (hdr[MPK_HDR_P] > MP_MAX_PLAYERS || hdr[MPK_HDR_P] < 1 || hdr[MPK_HDR_SPRITE] != 8 ||
+      hdr[MPK_HDR_NSTATES] > 255 || hdr[MPK_HDR_NSPRITES] > 255 || hdr[MPK_HDR_NHITS] > 24 ||
+      hdr[MPK_HDR_H] < 1 || hdr[MPK_HDR_W] < 1 || hdr[MPK_HDR_H] * hdr[MPK_HDR_W] > 4096 ||
+      hdr[MPK_HDR_L] < 1 || hdr[MPK_HDR_NACT] < 1)
+    return fail(MP_ERR_PACK, "mp_create: pack exceeds engine limits");
+  if (cfg.num_players < 0 || cfg.num_players > hdr[MPK_HDR_P])
+    return fail(MP_ERR_INVALID, "mp_create: num_players %d, the pack holds %d avatars",
+                cfg.num_players, hdr[MPK_HDR_P]);
+  *out = hdr;
+  return MP_OK;
+}
+
+int apply_roles(std::vector<uint8_t>& pack, const MpConfig& cfg) {
+  if (!cfg.roles) return MP_OK;
+  // Per-player constants by role (bach_or_stravinsky: create_avatar_objects(roles),
+  // bach_or_stravinsky_in_the_matrix__repeated.py:473-497): the pack holds, per (role, player),
+  // the avatar's sprite and its row of mx_player_*; the host copy becomes the one lowered for
+  // the requested assignment (meltingpot_amd/lower.py: add_role_tables / apply_roles).
+  const void* hp = pack.data();
+  const int32_t* hdr = table<int32_t>(hp, "hdr");
+  const int P = players(hdr, cfg), nsprites = hdr[MPK_HDR_NSPRITES];
+  const size_t PP = (size_t)hdr[MPK_HDR_P];
+  uint64_t n_names = 0, n_rgba = 0, n_pi = 0, n_pf = 0;
+  const char* names = table<char>(hp, "role_names", &n_names);
+  const int32_t* sprite = table_n<int32_t>(hp, "role_sprite", PP);
+  const uint8_t* rgba = table<uint8_t>(hp, "role_rgba", &n_rgba);
+  const int32_t* rpi = table<int32_t>(hp, "role_player_i32", &n_pi);
+  const double* rpf = table<double>(hp, "role_player_f64", &n_pf);
+  int n_roles = 0;
+  for (uint64_t i = 0; names && i < n_names; ++i) n_roles += names[i] == 0;
+  const size_t block = (size_t)4 * hdr[MPK_HDR_SPRITE] * hdr[MPK_HDR_SPRITE] * 4;
+  uint64_t n_srgba = 0, n_mpi = 0, n_mpf = 0;
+  uint8_t* srgba = const_cast<uint8_t*>(table<uint8_t>(hp, "sprite_rgba", &n_srgba));
+  int32_t* mpi = const_cast<int32_t*>(table<int32_t>(hp, "mx_player_i32", &n_mpi));
+  double* mpf = const_cast<double*>(table<double>(hp, "mx_player_f64", &n_mpf));
+  if (n_roles < 1 || !sprite || !rgba || !rpi || !rpf || !srgba || !mpi || !mpf ||
+      n_rgba != n_roles * PP * block || n_pi != n_roles * PP * 4 || n_pf != n_roles * PP * 4 ||
+      n_mpi < PP * 4 || n_mpf < PP * 4 || !in_range(sprite, PP, 0, nsprites) ||
+      n_srgba < (size_t)nsprites * block)
+    return fail(MP_ERR_INVALID, "mp_create: MpConfig.roles given, but this substrate's pack holds "
+                                "no per-role tables (its config has one valid role)");
+  for (int p = 0; p < P; ++p) {
+    const int r = cfg.roles[p];
+    if (r < 0 || r >= n_roles)
+      return fail(MP_ERR_INVALID, "mp_create: role %d of player %d is outside [0, %d)", r, p + 1,
+                  n_roles);
+    memcpy(srgba + (size_t)sprite[p] * block, rgba + ((size_t)r * PP + p) * block, block);
+    memcpy(mpi + 4 * p, rpi + ((size_t)r * PP + p) * 4, 4 * sizeof(int32_t));
+    memcpy(mpf + 4 * p, rpf + ((size_t)r * PP + p) * 4, 4 * sizeof(double));
+  }
+  return MP_OK;
+}
+
+int decode_pack(const std::vector<uint8_t>& pack, const MpConfig& cfg, const uint8_t* table_base,
+                DecodedPack* d) {
+  *d = DecodedPack();
+  const int32_t* hdr = table<int32_t>(pack.data(), "hdr");
+  Src s{pack.data(), table_base, nullptr, nullptr, ZapRules{}};
+  Substrate spec;
+  if (int rc = substrate_of(hdr[MPK_HDR_SUBSTRATE], &spec)) return rc;
+  d->sub.substrate = hdr[MPK_HDR_SUBSTRATE];
+  if (int rc = decode_action_fields(s, hdr, d->t)) return rc;
+  decode_layout(hdr, cfg, spec.hidden_planes, d);
+  if (int rc = decode_common_tables(s, hdr, d->t)) return rc;
+  if (int rc = decode_optional(s, d->t)) return rc;
+  if (int rc = build_extra(s, d->t, &d->extra)) return rc;
+  if (int rc = check_layers(s, d->t, d->sub.substrate)) return rc;
+  if (int rc = build_step_blob(s, d->t, &d->step_blob)) return rc;
+  if (spec.zapper)
+    if (int rc = load_zapper(s, d->t)) return rc;
+  if (int rc = decode_spawn_groups(s, d->t, d->sub.substrate)) return rc;
+  return spec.load(s, d->t, d);
+}

@@ -89,20 +89,36 @@ def test_product_never_imports_the_oracle():
         assert "liboracle" not in src, f
 
 
-def _create_rc(blob, num_players=0):
+def _create_rc(blob, num_players=0, roles=None):
   L = engine.load_library()
   cfg = engine.MpConfig(ctypes.sizeof(engine.MpConfig), 0, 2, 1, 0, 0, None, num_players, 0, 0, 0)
+  if roles is not None:
+    cfg.roles = (ctypes.c_int32 * len(roles))(*roles)
   h = ctypes.c_void_p()
   buf = ctypes.create_string_buffer(bytes(blob), len(blob))
   rc = L.mp_create(buf, len(blob), ctypes.byref(cfg), ctypes.byref(h))
   return rc, L.mp_last_error().decode()
 
 
+def _variant(t, **kw):
+  """mp_create's verdict on the pack tables `t` with each named table edited by its function."""
+  from meltingpot_amd import pack
+  bad = dict(t)
+  for k, fn in kw.items():
+    v = t[k].copy(); fn(v); bad[k] = v
+  return _create_rc(pack.dumps(bad))
+
+
+def _set(index, value):
+  return lambda v: v.__setitem__(index, value)
+
+
 def test_malformed_packs_are_refused_before_a_device_is_touched(clean_up_pack, territory_pack):
   """mp_create takes arbitrary bytes: truncated blobs, overflowing counts, missing
   or mistyped tables and out-of-range indices must come back as MP_ERR_PACK (-2),
   never as a crash.  (Without a GPU a well-formed pack gets as far as
-  MP_ERR_NO_DEVICE, -3: everything below is checked on the host first.)"""
+  MP_ERR_NO_DEVICE, -3: everything below is checked on the host first, rule constants
+  included.)"""
   import struct
   import torch
   from meltingpot_amd import lower, pack
@@ -141,7 +157,7 @@ def test_malformed_packs_are_refused_before_a_device_is_touched(clean_up_pack, t
   assert _create_rc(pack.dumps(bad))[0] == -2
   bad = dict(t); bad["cu_i32"] = t["cu_i32"].copy(); bad["cu_i32"][5] = 0     # ee_interval: % 0
   rc, msg = _create_rc(pack.dumps(bad))
-  assert rc in (-2, good)   # a rule constant: checked with the device's tables when there is one
+  assert rc == -2 and "clean_up constants out of engine range" in msg, msg
   bad = dict(t); bad["hdr"] = t["hdr"].copy(); bad["hdr"][lower.HDR_NHITS] = 30
   assert _create_rc(pack.dumps(bad))[0] == -2
   # player counts
@@ -150,7 +166,7 @@ def test_malformed_packs_are_refused_before_a_device_is_touched(clean_up_pack, t
   t3 = pack.loads(territory_pack)
   bad = dict(t3); bad["resource_cells"] = t3["resource_cells"].copy(); bad["resource_cells"][0] = 10**6
   rc, msg = _create_rc(pack.dumps(bad))
-  assert rc in (-2, good)
+  assert rc == -2 and "table 'resource_cells' is missing, too long or leaves the map" in msg, msg
 
 
 def test_malformed_matrix_packs_are_refused():
@@ -168,10 +184,7 @@ def test_malformed_matrix_packs_are_refused():
     rc, msg = _create_rc(pack.dumps(bad))
     assert rc == -2, (name, rc, msg)
   def variant(**kw):
-    bad = dict(t)
-    for k, fn in kw.items():
-      v = t[k].copy(); fn(v); bad[k] = v
-    return _create_rc(pack.dumps(bad))[0]
+    return _variant(t, **kw)[0]
   assert variant(mx_i32=lambda v: v.__setitem__(0, 4)) == -2       # R > 3
   assert variant(mx_i32=lambda v: v.__setitem__(0, 2)) == -2       # R that the tables do not fit
   assert variant(mx_i32=lambda v: v.__setitem__(16, 0)) == -2      # intervalLength 0: % 0
@@ -187,8 +200,8 @@ def test_malformed_matrix_packs_are_refused():
 
 
 def test_malformed_mushroom_packs_are_refused():
-  """externality_mushrooms: tables missing, short or leaving the map are refused on the host;
-  the rule constants with the device's tables (tests/test_gpu_mushroom.py)."""
+  """externality_mushrooms: tables missing, short or leaving the map are refused on the host
+  (its rule constants: test_mushroom_rule_constants_out_of_engine_range_are_refused)."""
   import torch
   from meltingpot_amd import engine, pack
   good = -3 if not torch.cuda.is_available() else 0
@@ -207,3 +220,68 @@ def test_malformed_mushroom_packs_are_refused():
   bad = dict(t); bad["mushroom_cells"] = np.concatenate([t["mushroom_cells"]] * 2)   # 462 sites: four a lane
   assert _create_rc(pack.dumps(bad))[0] == -2
 
+
+
+@pytest.mark.parametrize("name, table, index, value, message", [
+    ("commons_harvest__open", "ch_i32", 0, 33, "commons_harvest constants"),   # 33 regrowth classes
+    ("territory__open", "tr_i32", 7, 3, "territory constants"),                # three health levels
+    ("coop_mining", "cm_i32", 6, 2, "coop_mining constants"),                  # a third ore type
+    ("collaborative_cooking__ring", "cc_i32", 1, 31, "collaborative_cooking constants"),  # cooking time
+    ("gift_refinements", "gr_i32", 6, 16, "gift_refinements constants"),       # capacity beyond 4 bits
+    ("externality_mushrooms__dense", "em_i32", 1, 2, "externality_mushrooms constants"),  # health 2
+])
+def test_rule_constants_out_of_engine_range_are_refused_on_the_host(name, table, index, value, message):
+  """A substrate's rule constants are checked before a device is touched (MP_ERR_PACK, not
+  MP_ERR_NO_DEVICE, on a machine without one)."""
+  from meltingpot_amd import pack
+  rc, msg = _variant(pack.loads(engine.load_pack(name)), **{table: _set(index, value)})
+  assert rc == -2 and message in msg, msg
+
+
+def test_player_counts_and_roles_a_pack_cannot_run_are_refused_on_the_host():
+  rc, msg = _create_rc(engine.load_pack("coins"), num_players=1)
+  assert rc == -2 and "coins tables missing or out of engine range" in msg, msg
+  blob = engine.load_pack("bach_or_stravinsky_in_the_matrix__arena")
+  roles = [0] * 16   # (MP_MAX_PLAYERS)
+  roles[1] = 99
+  rc, msg = _create_rc(blob, roles=roles)
+  assert rc == -1 and "role 99 of player 2 is outside" in msg, msg
+
+
+def test_colour_intervals_with_a_gap_are_refused():
+  """TheMatrix:getColorInterval asserts (components.lua:282-290): a pack whose intervals
+  leave a gap inside the payable range is refused by mp_create (what it reports at run
+  time: tests/test_gpu_matrix.py)."""
+  from meltingpot_amd import pack
+  t = pack.loads(engine.load_pack("prisoners_dilemma_in_the_matrix__repeated"))
+  R, NI = int(t["mx_i32"][0]), int(t["mx_i32"][19])
+  def gap(f):
+    iv = f[5 + 2 * R * R:5 + 2 * R * R + 2 * NI].reshape(NI, 2)
+    iv[1] = (1.5, 2.0)                                 # nothing holds [1.0, 1.5)
+  rc, msg = _variant(t, mx_f64=gap)
+  assert rc == -2 and "resultIndicatorColorIntervals" in msg, msg
+
+
+def test_mushroom_rule_constants_out_of_engine_range_are_refused():
+  """What step_mushroom.h builds on is checked at mp_create: a zap destroys a mushroom
+  (health 1), two sanction levels, consecutive mushroom states, delays that fit the age
+  plane, a Zapper that pays nothing and leaves removal to the marking."""
+  import torch
+  from meltingpot_amd import pack
+  good = -3 if not torch.cuda.is_available() else 0
+  blob = engine.load_pack("externality_mushrooms__dense")
+  t = pack.loads(blob)
+  def refused(**kw):
+    rc, msg = _variant(t, **kw)
+    assert rc == -2 and re.search("externality_mushrooms|Zapper", msg), (kw, rc, msg)
+  refused(em_i32=_set(1, 2))           # initialHealth 2
+  refused(em_i32=_set(3, 3))           # three levels
+  refused(em_i32=_set(5, 0))           # intervalLength 0
+  refused(em_i32=_set(16, 300))        # a delay the age byte cannot count
+  refused(em_i32=_set(8, 9))           # nine spores
+  refused(em_i32=_set(20, 4))          # typeToDestroy out of range
+  refused(em_i32=_set(25, 300))        # a freeze beyond a byte
+  refused(em_states=lambda v: v.__setitem__(1, int(v[0]) + 2))   # types not consecutive
+  refused(zapper_i32=_set(4, 1))       # Zapper removes
+  refused(zapper_f64=_set(0, -1.0))    # Zapper pays
+  assert _create_rc(blob)[0] == good
