@@ -97,7 +97,12 @@ typedef enum {
 
 typedef enum {
   MP_OBS_RGB = 0,            /* "N.RGB"        u8  [N][P][VH*S][VW*S][3] */
-  MP_OBS_WORLD_RGB = 1,      /* "WORLD.RGB"    u8  [N][H*S][W*S][3] */
+  MP_OBS_WORLD_RGB = 1,      /* "WORLD.RGB"    u8  [N][H*S][W*S][3]; with MpConfig.world_pool
+                                k = 2, 4, 8: u8 [N][H*S/k][W*S/k][3], byte (y, x, c) the k x k
+                                block average of the full image, rounded half up (the rule of
+                                MP_OBS_RGB_POOL*), drawn straight from the cells' images in every
+                                launch that draws this kind; its buffers (and mp_observe's `dst`)
+                                must then be 16-byte aligned, and mp_box_fill does not take it */
   MP_OBS_REWARD = 2,         /* "N.REWARD"     f64 [N][P] */
   MP_OBS_READY_TO_SHOOT = 3, /* "N.READY_TO_SHOOT" f64 [N][P] */
   MP_OBS_AUX0 = 4,           /* substrate metric 0, f64 [N][P]
@@ -251,6 +256,12 @@ typedef struct {
                             column player and avatar colour, configs/substrates/
                             bach_or_stravinsky_in_the_matrix__repeated.py:473-497);
                             MP_ERR_INVALID for a pack without per-role tables */
+  int32_t world_pool;    /* 0 or 1: MP_OBS_WORLD_RGB is the full image; 2, 4, 8: it is that image
+                            pooled by this factor, for this engine everywhere the kind is used
+                            (mp_obs_bytes, mp_bind_output / _ring, mp_observe, mp_tune,
+                            mp_place_output); other values are MP_ERR_INVALID.  Appended to the
+                            ABI-8 layout: mp_create also takes struct_size =
+                            offsetof(MpConfig, world_pool) (72 bytes), which reads as 1 */
 } MpConfig;
 
 typedef struct {

@@ -10,6 +10,7 @@
 #include "../../include/mp_engine.h"
 
 #include <stdarg.h>
+#include <stddef.h>
 #include <sys/types.h>
 #include <stdio.h>
 #include <string.h>
@@ -31,8 +32,11 @@ constexpr int kFaultWords = 64 + 4 * 16 * 64 * 2;   // fault words + the timelin
 // views: 0 = per-agent RGB, 1 = WORLD.RGB, 2 = both in one launch
 FramePlan plan_frame(const DevTables& t, const SubstrateTables& s, int num_worlds,
                      bool with_step, int views, int num_cus, const MpDevOptions* dev,
-                     int pool_k = 1);   // pool_k: the per-agent view pooled by 2, 4, 8 (1: full)
-int frame_lds_bytes(const DevTables& t, const FramePlan& p, int pool_k = 1);
+                     int pool_k = 1,    // pool_k: the per-agent view pooled by 2, 4, 8 (1: full)
+                     int world_k = 1);  // world_k: WORLD.RGB pooled by 2, 4, 8 (1: full)
+// (views: what the plan draws, 0 / 1 / 2 as plan_frame's; a factor enters only with its view)
+int frame_lds_bytes(const DevTables& t, const FramePlan& p, int pool_k = 1, int world_k = 1,
+                    int views = 2);
 int render_blob_bytes(const DevTables& t);
 int prepare_frame();
 void build_render_blob(const DevTables& t, const uint8_t* images, const uint16_t* img_slot,
@@ -43,7 +47,7 @@ void build_render_blob(const DevTables& t, const uint8_t* images, const uint16_t
 uint32_t render_visible_layers(const DevTables& t, const uint8_t* blob, const int32_t* state_layer);
 void launch_frame(const DevTables& t, const SubstrateTables* s, const stepk::StepArgs& args,
                   uint8_t* out_a, uint8_t* out_w, const FramePlan& p, hipStream_t stream,
-                  int pool_k = 1);
+                  int pool_k = 1, int world_k = 1);
 
 thread_local std::string g_error;
 
@@ -123,6 +127,9 @@ struct MpEngine {
   }
   uint8_t* agent_view() const { return (uint8_t*)bound[agent_kind()]; }
   int pool_k() const { return pool_of(agent_kind()); }
+  // MpConfig.world_pool: MP_OBS_WORLD_RGB is pooled by this factor (2, 4, 8) everywhere, 1 = full.
+  // A property of the engine: its plans (plan, pool_plan, ring_plan) are made for it.
+  int world_pool = 1;
   // [k = 2, 4, 8][drawing only, stepping + drawing][agents, -, both]: the plans of the pooled views
   // (pool_ok: the pack's pooled atlas and span staging fit the LDS beside a ring of records)
   FramePlan pool_plan[3][2][3] = {};
@@ -290,7 +297,7 @@ void draw(MpEngine* e, uint8_t* rgb, uint8_t* wrgb, int pool_k = 1) {
   args.state = e->d_state; args.num_worlds = e->N;
   FramePlan p = e->frame_plan(0, rgb && wrgb ? 2 : wrgb ? 1 : 0, rgb ? pool_k : 1);
   p.parity = e->frame_launches++ & 1;
-  launch_frame(e->t, nullptr, args, rgb, wrgb, p, e->stream, rgb ? pool_k : 1);
+  launch_frame(e->t, nullptr, args, rgb, wrgb, p, e->stream, rgb ? pool_k : 1, e->world_pool);
 }
 
 int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask) {
@@ -319,7 +326,7 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask) {
     FramePlan p = ringing && e->ring_plan[views].size() == (size_t)e->ring_slots
                       ? e->ring_plan[views][(size_t)slot] : e->frame_plan(1, views, pk);
     p.parity = e->frame_launches++ & 1;
-    launch_frame(e->t, &e->sub, args, rgb, wrgb, p, e->stream, pk);
+    launch_frame(e->t, &e->sub, args, rgb, wrgb, p, e->stream, pk, e->world_pool);
   }
   // "N.LAYER", when bound: one more (small) launch on the stepped records
   if (e->bound[MP_OBS_LAYER])
@@ -370,6 +377,14 @@ int check_agent_view(MpEngine* e, int kind, const void* ptr, const char* who) {
                   "MP_OBS_RGB_POOL*) at a time — unbind it first", who, k);
   if (MpEngine::pool_of(kind) > 1 && ((uintptr_t)ptr & 15) != 0)
     return fail(MP_ERR_INVALID, "%s: a pooled view's buffer must be 16-byte aligned (%p)", who, ptr);
+  return MP_OK;
+}
+
+// A pooled WORLD.RGB (MpConfig.world_pool) is staged by 16-byte lines too.
+int check_world_view(MpEngine* e, int kind, const void* ptr, const char* who) {
+  if (kind == MP_OBS_WORLD_RGB && e->world_pool > 1 && ((uintptr_t)ptr & 15) != 0)
+    return fail(MP_ERR_INVALID, "%s: a pooled WORLD.RGB buffer (MpConfig.world_pool = %d) must be "
+                "16-byte aligned (%p)", who, e->world_pool, ptr);
   return MP_OK;
 }
 
@@ -650,8 +665,9 @@ void fill_composites(MpEngine* e, const MpDevOptions* dev, const int32_t* flags,
   t.n_images = a.count;
   int max_composites = kPairSlots;
   for (int v = 0; v < 6; ++v) {
-    const FramePlan p0 = plan_frame(t, e->sub, e->N, (v & 1) != 0, v >> 1, e->num_cus, dev);
-    max_composites = std::min(max_composites, (160 * 1024 - frame_lds_bytes(t, p0)) / 272);
+    const FramePlan p0 = plan_frame(t, e->sub, e->N, (v & 1) != 0, v >> 1, e->num_cus, dev, 1, e->world_pool);
+    max_composites = std::min(max_composites,
+                              (160 * 1024 - frame_lds_bytes(t, p0, 1, e->world_pool, v >> 1)) / 272);
   }
   max_composites = std::max(0, std::min(max_composites, kPairSlots / 2));
   if (dev && dev->max_composites >= 0) max_composites = std::min(max_composites, (int)dev->max_composites);
@@ -740,6 +756,17 @@ int plan_views(MpEngine* e, const MpDevOptions* dev) {
     if (frame_lds_bytes(t, pl) > 160 * 1024)
       return fail(MP_ERR_PACK, "mp_create: renderer needs %d B of LDS", frame_lds_bytes(t, pl));
   }
+  // a pooled WORLD.RGB (MpConfig.world_pool): the plans that draw it, with its pooled atlas and span
+  // staging in LDS; a pack where they do not fit beside a ring of records does not offer it
+  if (e->world_pool > 1)
+    for (int v = 2; v < 6; ++v) {
+      FramePlan& pl = e->plan[v & 1][v >> 1];
+      pl = plan_frame(t, e->sub, e->N, (v & 1) != 0, v >> 1, e->num_cus, dev, 1, e->world_pool);
+      const int need = frame_lds_bytes(t, pl, 1, e->world_pool, v >> 1);
+      if (need > 160 * 1024)
+        return fail(MP_ERR_UNSUPPORTED, "mp_create: WORLD.RGB pooled by %d (MpConfig.world_pool) needs "
+                    "%d B of LDS", e->world_pool, need);
+    }
   // the pooled per-agent views (MP_OBS_RGB_POOL*): their plans, sized for the bytes they write;
   // a pack whose pooled atlas does not fit beside a ring of records does not offer them
   // (8 x 8 sprites only: the pooled image of a cell is 8/k pixels square)
@@ -749,8 +776,8 @@ int plan_views(MpEngine* e, const MpDevOptions* dev) {
     for (int v = 0; v < 6 && e->pool_ok[i]; ++v) {
       if ((v >> 1) == 1) continue;   // (WORLD.RGB alone has no per-agent view)
       FramePlan& pl = e->pool_plan[i][v & 1][v >> 1];
-      pl = plan_frame(t, e->sub, e->N, (v & 1) != 0, v >> 1, e->num_cus, dev, k);
-      if (frame_lds_bytes(t, pl, k) > 160 * 1024) e->pool_ok[i] = false;
+      pl = plan_frame(t, e->sub, e->N, (v & 1) != 0, v >> 1, e->num_cus, dev, k, e->world_pool);
+      if (frame_lds_bytes(t, pl, k, e->world_pool, v >> 1) > 160 * 1024) e->pool_ok[i] = false;
     }
   }
   if (int rc = prepare_frame())
@@ -763,7 +790,7 @@ int plan_views(MpEngine* e, const MpDevOptions* dev) {
               t.n_images, (v & 1) ? "stepping + drawing" : "drawing",
               (v >> 1) == 0 ? "agents view" : (v >> 1) == 1 ? "world view" : "both views",
               pl.NB, pl.B, pl.feeders, pl.nwaves, pl.world_waves, pl.groups, pl.ks, pl.pool,
-              frame_lds_bytes(t, pl));
+              frame_lds_bytes(t, pl, 1, e->world_pool, v >> 1));
     }
   return MP_OK;
 }
@@ -777,6 +804,7 @@ int create_on_device(MpEngine* e, const MpConfig& cfg, DecodedPack* d) {
   e->auto_reset = cfg.auto_reset;
   e->stream = (hipStream_t)cfg.stream;
   e->unfused = cfg.unfused;   // 0 is resolved once the pack is read
+  e->world_pool = cfg.world_pool > 1 ? cfg.world_pool : 1;   // (mp_create checked it)
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg.device) != hipSuccess ||
       cus <= 0)
@@ -803,7 +831,10 @@ uint64_t mp_obs_bytes(const MpEngine* e, MpObsKind kind) {
   switch (kind) {
     case MP_OBS_RGB:
       return N * P * (e->t.vf + e->t.vb + 1) * S * (e->t.vl + e->t.vr + 1) * S * 3;
-    case MP_OBS_WORLD_RGB: return N * e->t.H * S * e->t.W * S * 3;
+    case MP_OBS_WORLD_RGB: {
+      const uint64_t k = (uint64_t)e->world_pool;   // (MpConfig.world_pool; 1 = the full image)
+      return N * (e->t.H * S / k) * (e->t.W * S / k) * 3;
+    }
     case MP_OBS_RGB_POOL2: case MP_OBS_RGB_POOL4: case MP_OBS_RGB_POOL8: {
       const uint64_t k = (uint64_t)MpEngine::pool_of(kind);
       if (!e->pool_ok[MpEngine::pool_index((int)k)]) return 0;
@@ -838,14 +869,23 @@ int mp_create(const void* pack, uint64_t pack_len, const MpConfig* cfg,
               MpEngine** out) {
   if (!out) return fail(MP_ERR_INVALID, "mp_create: out is NULL");
   *out = nullptr;
-  if (!cfg || cfg->struct_size != sizeof(MpConfig))
+  // (an MpConfig of the ABI-8 layout, which ends before world_pool, reads as world_pool = 1)
+  if (!cfg || (cfg->struct_size != sizeof(MpConfig) && cfg->struct_size != offsetof(MpConfig, world_pool)))
     return fail(MP_ERR_INVALID, "mp_create: bad MpConfig (struct_size)");
+  MpConfig cfg_copy = {};
+  memcpy(&cfg_copy, cfg, cfg->struct_size);
+  if (cfg->struct_size < sizeof(MpConfig)) cfg_copy.world_pool = 1;
+  cfg = &cfg_copy;
   if (cfg->dev && cfg->dev->struct_size != sizeof(MpDevOptions))
     return fail(MP_ERR_INVALID, "mp_create: bad MpDevOptions (struct_size)");
   if (cfg->num_worlds <= 0)
     return fail(MP_ERR_INVALID, "mp_create: num_worlds must be positive");
   if (cfg->unfused < 0 || cfg->unfused > 2)
     return fail(MP_ERR_INVALID, "mp_create: MpConfig.unfused must be 0, 1 or 2 (got %d)", cfg->unfused);
+  if (cfg->world_pool != 0 && cfg->world_pool != 1 && cfg->world_pool != 2 && cfg->world_pool != 4 &&
+      cfg->world_pool != 8)
+    return fail(MP_ERR_INVALID, "mp_create: MpConfig.world_pool must be 0, 1, 2, 4 or 8 (got %d)",
+                cfg->world_pool);
   // the whole pack is decoded and checked on the host (pack_decode.hip) before a device is touched
   const int32_t* hdr = nullptr;
   if (int rc = check_header(pack, pack_len, *cfg, &hdr)) return rc;
@@ -853,6 +893,9 @@ int mp_create(const void* pack, uint64_t pack_len, const MpConfig* cfg,
   if (int rc = apply_roles(copy, *cfg)) return rc;
   DecodedPack d;
   if (int rc = decode_pack(copy, *cfg, copy.data(), &d)) return rc;
+  if (cfg->world_pool > 1 && d.t.sprite_size != 8)   // (the pooled image of a cell is 8/k pixels square)
+    return fail(MP_ERR_UNSUPPORTED, "mp_create: MpConfig.world_pool needs 8 x 8 sprites (the pack's are %d x %d)",
+                d.t.sprite_size, d.t.sprite_size);
 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -950,6 +993,8 @@ int mp_bind_output(MpEngine* e, MpObsKind kind, void* device_ptr) {
   if (device_ptr)
     if (int rc = check_agent_view(e, kind, device_ptr, "mp_bind_output")) return rc;
   if (device_ptr)
+    if (int rc = check_world_view(e, kind, device_ptr, "mp_bind_output")) return rc;
+  if (device_ptr)
     if (int rc = check_device_pointer(e, device_ptr, "mp_bind_output")) return rc;
   // (a ring's tuned plans were sized for the per-agent view bound then: full and pooled views
   // lay LDS out differently, so a change of that kind drops them — mp_tune makes new ones)
@@ -977,6 +1022,7 @@ int mp_bind_output_ring(MpEngine* e, MpObsKind kind, void* base, uint64_t slot_s
                 "(must hold it and be a multiple of 256)", (unsigned long long)slot_stride_bytes,
                 (unsigned long long)bytes);
   if (int rc = check_agent_view(e, kind, base, "mp_bind_output_ring")) return rc;
+  if (int rc = check_world_view(e, kind, base, "mp_bind_output_ring")) return rc;
   if (int rc = check_device_pointer(e, base, "mp_bind_output_ring")) return rc;
   if (int rc = check_device_pointer(e, (const char*)base + (uint64_t)(slots - 1) * slot_stride_bytes + bytes - 1,
                                     "mp_bind_output_ring (last byte of the last slot)")) return rc;
@@ -1093,6 +1139,7 @@ int mp_observe(MpEngine* e, MpObsKind kind, void* dst) {
       HIP_TRY(hipGetLastError());
       return MP_OK;
     case MP_OBS_WORLD_RGB:
+      if (int rc = check_world_view(e, kind, dst, "mp_observe")) return rc;
       draw(e, nullptr, (uint8_t*)dst);
       HIP_TRY(hipGetLastError());
       return MP_OK;
@@ -1631,7 +1678,7 @@ static int tune_impl(MpEngine* e, double* us_per_launch, bool* stepped, bool qui
   if (int rc = sync_and_check(e, "mp_tune")) return rc;
   FramePlan& plan = e->frame_plan(1, views, pk);
   const FramePlan before = plan;
-  const FramePlan stock = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, nullptr, pk);
+  const FramePlan stock = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, nullptr, pk, e->world_pool);
   // the candidates: the stock plan; the same ring cut into single worlds; that with
   // half of every workgroup's share pooled; the stock plan with sc1 stores.  (Same
   // number of LDS record slots: the composite cache was sized for the stock plan.)
@@ -1647,8 +1694,8 @@ static int tune_impl(MpEngine* e, double* us_per_launch, bool* stepped, bool qui
       d.batch_worlds = 1;
       d.ring_batches = lds_slots;
       d.static_pct = pct;
-      const FramePlan p = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d, pk);
-      if (frame_lds_bytes(e->t, p, pk) <= frame_lds_bytes(e->t, stock, pk) &&
+      const FramePlan p = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d, pk, e->world_pool);
+      if (frame_lds_bytes(e->t, p, pk, e->world_pool, views) <= frame_lds_bytes(e->t, stock, pk, e->world_pool, views) &&
           (p.B != stock.B || p.NB != stock.NB || p.pool != stock.pool))
         cand.push_back(p);
     }
@@ -1662,13 +1709,13 @@ static int tune_impl(MpEngine* e, double* us_per_launch, bool* stepped, bool qui
       d.batch_worlds = 1;
       d.ring_batches = lds_slots;
       d.team = 1;
-      const FramePlan p = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d, pk);
-      if (p.team && frame_lds_bytes(e->t, p, pk) <= frame_lds_bytes(e->t, stock, pk)) {
+      const FramePlan p = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d, pk, e->world_pool);
+      if (p.team && frame_lds_bytes(e->t, p, pk, e->world_pool, views) <= frame_lds_bytes(e->t, stock, pk, e->world_pool, views)) {
         cand.push_back(p);
         if (!quick && views != 1 && stock.feeders >= 4) {   // ... and with half the feeders (see below)
           d.feeders = stock.feeders / 2;
-          const FramePlan h = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d, pk);
-          if (h.team && h.feeders != p.feeders && frame_lds_bytes(e->t, h, pk) <= frame_lds_bytes(e->t, stock, pk))
+          const FramePlan h = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d, pk, e->world_pool);
+          if (h.team && h.feeders != p.feeders && frame_lds_bytes(e->t, h, pk, e->world_pool, views) <= frame_lds_bytes(e->t, stock, pk, e->world_pool, views))
             cand.push_back(h);
         }
       }
@@ -1692,8 +1739,8 @@ static int tune_impl(MpEngine* e, double* us_per_launch, bool* stepped, bool qui
       d.struct_size = sizeof d;
       d.max_composites = -1;
       d.feeders = stock.feeders / 2;
-      const FramePlan p = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d, pk);
-      if (frame_lds_bytes(e->t, p, pk) <= frame_lds_bytes(e->t, stock, pk) && p.feeders != stock.feeders)
+      const FramePlan p = plan_frame(e->t, e->sub, e->N, true, views, e->num_cus, &d, pk, e->world_pool);
+      if (frame_lds_bytes(e->t, p, pk, e->world_pool, views) <= frame_lds_bytes(e->t, stock, pk, e->world_pool, views) && p.feeders != stock.feeders)
         cand.push_back(p);
     }
   }
@@ -1955,6 +2002,9 @@ int mp_box_fill(MpEngine* e, MpObsKind kind, int32_t reps, MpBoxFill* out) {
   memset(out, 0, sizeof *out);
   if (kind != MP_OBS_RGB && kind != MP_OBS_WORLD_RGB)
     return fail(MP_ERR_INVALID, "mp_box_fill: kind %d is not a pixel view", (int)kind);
+  if (kind == MP_OBS_WORLD_RGB && e->world_pool > 1)
+    return fail(MP_ERR_INVALID, "mp_box_fill: WORLD.RGB is pooled by %d (MpConfig.world_pool)",
+                e->world_pool);
   if (e->ring[kind].base || !e->bound[kind])
     return fail(MP_ERR_INVALID, "mp_box_fill: kind %d is not bound to one buffer", (int)kind);
   if (reps < 1) reps = 1;

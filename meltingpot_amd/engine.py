@@ -167,6 +167,9 @@ class MpConfig(ctypes.Structure):
       ("literal_base_seed", ctypes.c_int32),
       ("dev", ctypes.POINTER(MpDevOptions)),
       ("roles", ctypes.POINTER(ctypes.c_int32)),
+      # 0 / 1: OBS_WORLD_RGB is the full image; 2, 4, 8: pooled by that factor (`pool_rgb`).
+      # Appended to the ABI-8 layout, whose struct_size mp_create still takes (as 1).
+      ("world_pool", ctypes.c_int32),
   ]
 
 
@@ -302,7 +305,8 @@ class Engine:
                base_seed: int = 0, literal_seed: bool = False, num_players: int = 0,
                debug_observations: bool = False, unfused: Optional[bool] = None,
                dev: Optional[Dict[str, int]] = None,
-               roles: Optional[Sequence[int]] = None, placements: int = 8):
+               roles: Optional[Sequence[int]] = None, placements: int = 8,
+               world_pool: int = 1):
     """`num_players` = 0: the pack's default count (its header; all the avatars
     it holds unless tools/make_packs.py says otherwise); else the first
     `num_players` avatars play (the reference's num_players = len(roles)).
@@ -315,7 +319,12 @@ class Engine:
     tools/ only (launch-plan overrides; results never depend on them).  `roles`:
     one index per player into the pack's "role_names" (MpConfig.roles; only for
     substrates whose config has more than one valid role) — see
-    `pack_role_names`."""
+    `pack_role_names`.  `world_pool` = k in (2, 4, 8): OBS_WORLD_RGB is the world
+    image pooled by k (`pool_rgb`), drawn so by every launch (MpConfig.world_pool); 1 = full."""
+    if (isinstance(world_pool, bool) or not isinstance(world_pool, (int, np.integer)) or
+        int(world_pool) not in (0, 1, 2, 4, 8)):
+      raise ValueError(f"world_pool must be 1, 2, 4 or 8 (got {world_pool!r})")
+    self.world_pool = max(1, int(world_pool))   # (0 means the full image, as in MpConfig)
     import torch  # device memory + streams only
     self._torch = torch
     # candidates `place` tries for a bound pixel view (1: the first allocation, its
@@ -339,7 +348,7 @@ class Engine:
                    1 if auto_reset else 0, world_offset, int(base_seed) % (1 << 64), stream,
                    int(num_players), 1 if debug_observations else 0,
                    0 if unfused is None else (1 if unfused else 2),
-                   1 if literal_seed else 0, None, None)
+                   1 if literal_seed else 0, None, None, self.world_pool)
     if roles is not None:
       if num_players and len(roles) != num_players:
         raise ValueError(f"{len(roles)} roles for {num_players} players")
@@ -369,7 +378,8 @@ class Engine:
     S = info.sprite_size
     self.shapes = {
         OBS_RGB: ((self.N, self.P, info.view_h * S, info.view_w * S, 3), torch.uint8),
-        OBS_WORLD_RGB: ((self.N, info.map_h * S, info.map_w * S, 3), torch.uint8),
+        OBS_WORLD_RGB: ((self.N, info.map_h * S // self.world_pool, info.map_w * S // self.world_pool,
+                         3), torch.uint8),
         OBS_REWARD: ((self.N, self.P), torch.float64),
         OBS_READY_TO_SHOOT: ((self.N, self.P), torch.float64),
         OBS_AUX0: ((self.N, self.P), torch.float64),

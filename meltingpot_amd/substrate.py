@@ -597,7 +597,7 @@ class Substrate:
                debug_observations: bool = False,
                action_table: Optional[Sequence[Mapping[str, int]]] = None,
                rollout_length: int = 0, check_device_actions: bool = False,
-               rgb_pool: int = 1):
+               rgb_pool: int = 1, world_rgb_pool: int = 1):
     """`action_table`: the discrete actions, as in the reference's
     `build_substrate(..., action_table)` (utils/substrates/substrate.py:107-139,
     discrete_action_wrapper.py:77-109): row i is what discrete action i does,
@@ -619,10 +619,17 @@ class Substrate:
     (k x k box average, rounded half up: `engine.pool_rgb`), e.g. (11, 11, 3) for an 88 x 88 view
     at k = 8, in the observations and in `observation_spec()`.  The engine draws the pooled
     view itself (MP_OBS_RGB_POOL<k>): the full image is never written.  1 (default): the full
-    view."""
+    view.
+
+    `world_rgb_pool` = k in (2, 4, 8): the same for "WORLD.RGB", the whole map — e.g. (21, 30, 3)
+    for clean_up's 168 x 240 image at k = 8 (MpConfig.world_pool: the engine draws it pooled,
+    the full image is never written).  The two factors are independent."""
     if rgb_pool not in (1, 2, 4, 8) or isinstance(rgb_pool, bool):
       raise ValueError(f"rgb_pool must be 1, 2, 4 or 8, got {rgb_pool!r}")
+    if world_rgb_pool not in (1, 2, 4, 8) or isinstance(world_rgb_pool, bool):
+      raise ValueError(f"world_rgb_pool must be 1, 2, 4 or 8, got {world_rgb_pool!r}")
     self._rgb_pool = int(rgb_pool)
+    self._world_rgb_pool = int(world_rgb_pool)
     invalid = set(roles) - config.valid_roles  # configs/substrates/__init__.py:42-45
     if invalid:
       raise ValueError(f"Invalid roles: {invalid!r}. Must be one of "
@@ -652,11 +659,13 @@ class Substrate:
     env_seed = resolve_env_seed(env_seed)
     # num_players = len(roles) (configs/substrates/clean_up.py:847): the first
     # len(roles) avatars of the committed pack play
+    # (world_pool only when asked for: the engine's default is the full image)
+    pooled = {"world_pool": self._world_rgb_pool} if self._world_rgb_pool > 1 else {}
     self._eng = engine_lib.Engine(
         pack_bytes, num_worlds, device=device, auto_reset=auto_reset,
         world_offset=world_offset, base_seed=env_seed, literal_seed=True,
         num_players=len(self._roles),
-        debug_observations=debug_observations, roles=role_ids)
+        debug_observations=debug_observations, roles=role_ids, **pooled)
     self._env_seed = env_seed
     self._action_rows = self._action_rows_dev = None
     if action_table is not None:
@@ -849,6 +858,10 @@ class Substrate:
     if self._rgb_pool > 1 and "RGB" in spec:
       h, w, c = spec["RGB"].shape
       spec["RGB"] = Array((h // self._rgb_pool, w // self._rgb_pool, c), spec["RGB"].dtype, "RGB")
+    if self._world_rgb_pool > 1 and "WORLD.RGB" in spec:
+      k = self._world_rgb_pool
+      h, w, c = spec["WORLD.RGB"].shape
+      spec["WORLD.RGB"] = Array((h // k, w // k, c), spec["WORLD.RGB"].dtype, "WORLD.RGB")
     return [dict(spec) for _ in self._roles]
 
   def action_spec(self) -> List[DiscreteArray]:

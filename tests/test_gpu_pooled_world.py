@@ -1,0 +1,316 @@
+"""Pooled WORLD.RGB on the GPU (MpConfig.world_pool = 2, 4, 8): drawn by the launch that steps the
+worlds, every byte equal to the oracle's world image pooled in numpy (`engine.pool_rgb`) — for
+every pack, beside the per-agent view (none, full, pooled by the same or another factor) under
+forced plans and in the two-launch form, at the benchmarked sizes against a same-seed engine with
+the full views, through mp_observe, in a rollout ring, in a placed buffer and behind
+`Substrate(..., world_rgb_pool=k)`.  No fault word may be set after any of it."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import util
+from meltingpot_amd import engine, substrate
+
+pytestmark = pytest.mark.gpu
+
+ASSETS = os.path.join(os.path.dirname(engine.__file__), "assets")
+PACKS = sorted(f[:-4] for f in os.listdir(ASSETS) if f.endswith(".mpk"))
+KS = (2, 4, 8)
+POOL_OF = {k: f for f, k in engine.OBS_RGB_POOL.items()}
+
+
+def _no_faults(eng):
+  assert not eng.fault_words()[:6].any(), eng.fault_words()[:6]
+
+
+def _run_against_oracle(name, n, steps, setups, dev=None, seed=0, looks=(), unfused=None):
+  """One engine per entry of `setups` — (world_pool, per-agent kind or None) — WORLD.RGB and that
+  per-agent view bound together, stepped with the same random actions as n oracles; state,
+  rewards and every bound view compared at each step in `looks` and at the end."""
+  pack = engine.load_pack(name)
+  engs = [engine.Engine(pack, n, device=0, dev=dev, world_pool=kw, unfused=unfused)
+          for kw, _ in setups]
+  bufs = []
+  for e, (kw, agent) in zip(engs, setups):
+    b = {engine.OBS_WORLD_RGB: e.bind(engine.OBS_WORLD_RGB)}
+    if agent is not None:
+      b[agent] = e.bind(agent)
+    bufs.append(b)
+  oracles = util.make_oracles(pack, n)
+  for e in engs:
+    e.reset()
+  for o in oracles:
+    o.reset()
+  rng = np.random.default_rng(seed)
+  P, nact = engs[0].P, engs[0].num_actions
+  acts = rng.integers(0, nact, size=(steps, n, P), dtype=np.int32)
+  dacts = torch.from_numpy(acts).to(engs[0].device)
+  looks = set(looks) | {steps}
+  try:
+    for s in range(steps):
+      for e in engs:
+        e.step(dacts[s])
+      for w, o in enumerate(oracles):
+        o.step(acts[s, w])
+      if s + 1 not in looks:
+        continue
+      world = {w: o.render_world() for w, o in enumerate(oracles)}
+      agents = None
+      for e, b, (kw, agent) in zip(engs, bufs, setups):
+        grid, avat, glob = e.dump()
+        rew = e.observe(engine.OBS_REWARD).cpu().numpy()
+        host = {k: t.cpu().numpy() for k, t in b.items()}
+        if agent is not None and agents is None:
+          agents = {w: np.stack([o.render_agent(p) for p in range(P)]) for w, o in enumerate(oracles)}
+        for w, o in enumerate(oracles):
+          og, oa, ogl = o.dump()
+          assert np.array_equal(grid[w], og) and np.array_equal(avat[w], oa), (name, s, w)
+          assert np.array_equal(glob[w], ogl), (name, s, w)
+          assert np.array_equal(rew[w], o.rewards()), (name, s, w)
+          assert np.array_equal(host[engine.OBS_WORLD_RGB][w], engine.pool_rgb(world[w], kw)), \
+              (name, kw, s, w)
+          if agent is not None:
+            want = agents[w] if agent == engine.OBS_RGB else engine.pool_rgb(agents[w], POOL_OF[agent])
+            assert np.array_equal(host[agent][w], want), (name, kw, agent, s, w)
+        _no_faults(e)
+  finally:
+    for o in oracles:
+      o.close()
+    for e in engs:
+      e.close()
+
+
+@pytest.mark.parametrize("name", PACKS)
+def test_every_pack_world_pooled_alone(name):
+  """1.  8 worlds x 24 random steps (beams included), WORLD.RGB alone, each factor."""
+  _run_against_oracle(name, 8, 24, [(k, None) for k in KS], looks=(1, 12))
+
+
+# (world factor, per-agent view): none, full, pooled by the same factor, pooled by another
+MIXED = [(8, None), (4, engine.OBS_RGB), (2, engine.OBS_RGB_POOL2), (2, engine.OBS_RGB_POOL8),
+         (8, engine.OBS_RGB_POOL4), (4, engine.OBS_RGB_POOL4)]
+
+
+@pytest.mark.parametrize("name", ["clean_up", "territory__rooms", "coins",
+                                  "collaborative_cooking__cramped"])
+@pytest.mark.parametrize("dev", [
+    {"batch_worlds": 1, "ring_batches": 6, "static_pct": 50, "max_groups": 4},
+    {"batch_worlds": 3, "ring_batches": 2, "max_groups": 8, "world_waves": 1},
+    {"max_groups": 5, "scratch_cells": 1, "world_waves": 2},
+])
+def test_world_pooled_beside_agent_views_forced_plans(name, dev):
+  """2.  Odd world counts, several batches per workgroup, single-world batches, a tiny staging
+  area, the renderer waves shared out by hand; passes that cross world boundaries."""
+  _run_against_oracle(name, 37, 6, MIXED, dev=dev, seed=1, looks=(1,))
+
+
+@pytest.mark.parametrize("name", ["clean_up", "coins", "collaborative_cooking__cramped"])
+def test_world_pooled_unfused(name):
+  """2b.  MpConfig.unfused = 1: the rules in one launch, each view drawn by a draw-only launch."""
+  _run_against_oracle(name, 21, 8, MIXED[:4], seed=3, looks=(1,), unfused=True)
+
+
+def _pool_dev(x, k):
+  """engine.pool_rgb on the device (exact integer arithmetic), for the big comparisons."""
+  *lead, h, w, c = x.shape
+  s = x.to(torch.int32).reshape(*lead, h // k, k, w // k, k, c).sum(dim=(-4, -2))
+  return ((s + (k * k) // 2) // (k * k)).to(torch.uint8)
+
+
+@pytest.mark.parametrize("name,n", [("clean_up", 4096), ("territory__rooms", 8192)])
+def test_benchmarked_sizes_world_pooled_equals_pooled_full(name, n):
+  """3.  At the benchmarked sizes, with the plan mp_tune keeps (and the stock plan), the pooled
+  WORLD.RGB — alone and beside a pooled per-agent view — equals the full engine's pooled."""
+  pack = engine.load_pack(name)
+  steps = 2
+  full = engine.Engine(pack, n, device=0)
+  wf, af = full.bind(engine.OBS_WORLD_RGB), full.bind(engine.OBS_RGB)
+  full.reset()
+  rng = np.random.default_rng(5)
+  acts = torch.from_numpy(rng.integers(0, full.num_actions, size=(steps, n, full.P),
+                                       dtype=np.int32)).to(full.device)
+  want_w, want_a = [], []
+  for s in range(steps):
+    full.step(acts[s])
+    want_w.append({k: _pool_dev(wf, k) for k in KS})
+    want_a.append(_pool_dev(af, 8))
+  _no_faults(full)
+  full.close()
+  del wf, af
+  torch.cuda.empty_cache()
+  for kw, agent, tune in [(8, None, True), (2, None, True), (4, None, False),
+                          (2, engine.OBS_RGB_POOL8, True), (8, engine.OBS_RGB_POOL8, True)]:
+    e = engine.Engine(pack, n, device=0, world_pool=kw)
+    out = e.bind(engine.OBS_WORLD_RGB)
+    a = e.bind(agent) if agent is not None else None
+    if tune:
+      e.tune()
+    e.reset()
+    for s in range(steps):
+      e.step(acts[s])
+      assert torch.equal(out, want_w[s][kw]), (name, kw, agent, s)
+      if a is not None:
+        assert torch.equal(a, want_a[s]), (name, kw, agent, s)
+    _no_faults(e)
+    e.close()
+    del out, a
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("name", ["clean_up", "coins", "collaborative_cooking__cramped",
+                                  "territory__rooms"])
+def test_observe_world_pooled_without_a_bound_view(name):
+  """4.  mp_observe draws the pooled world view from the records (the render-only launch)."""
+  pack = engine.load_pack(name)
+  n, steps = 11, 12
+  engs = {k: engine.Engine(pack, n, device=0, world_pool=k) for k in KS}
+  oracles = util.make_oracles(pack, n)
+  for e in engs.values():
+    e.reset()
+  for o in oracles:
+    o.reset()
+  rng = np.random.default_rng(7)
+  P, nact = engs[2].P, engs[2].num_actions
+  acts = rng.integers(0, nact, size=(steps, n, P), dtype=np.int32)
+  for s in range(steps):
+    for e in engs.values():
+      e.step(torch.from_numpy(acts[s]).to(e.device))
+    for w, o in enumerate(oracles):
+      o.step(acts[s, w])
+  world = np.stack([o.render_world() for o in oracles])
+  for k, e in engs.items():
+    got = e.observe(engine.OBS_WORLD_RGB).cpu().numpy()
+    assert got.shape == (n, world.shape[1] // k, world.shape[2] // k, 3)
+    assert np.array_equal(got, engine.pool_rgb(world, k)), (name, k)
+    _no_faults(e)
+    e.close()
+  for o in oracles:
+    o.close()
+
+
+@pytest.mark.parametrize("name,kw", [("clean_up", 8), ("coins", 4), ("collaborative_cooking__cramped", 2)])
+def test_rollout_ring_of_pooled_world(name, kw):
+  """5.  A tuned ring of T slots: slot t % T holds submission t's pooled world view."""
+  pack = engine.load_pack(name)
+  n, T, steps = 9, 3, 7
+  e = engine.Engine(pack, n, device=0, world_pool=kw)
+  ring = e.bind_ring(engine.OBS_WORLD_RGB, slots=T, tune=True)
+  oracles = util.make_oracles(pack, n)
+  e.reset()
+  for o in oracles:
+    o.reset()
+  seen = [np.stack([engine.pool_rgb(o.render_world(), kw) for o in oracles])]
+  rng = np.random.default_rng(4)
+  acts = rng.integers(0, e.num_actions, size=(steps, n, e.P), dtype=np.int32)
+  for s in range(steps):
+    e.step(torch.from_numpy(acts[s]).to(e.device))
+    for w, o in enumerate(oracles):
+      o.step(acts[s, w])
+    seen.append(np.stack([engine.pool_rgb(o.render_world(), kw) for o in oracles]))
+  got = ring.cpu().numpy()
+  for t in range(steps + 1 - T, steps + 1):
+    assert np.array_equal(got[t % T], seen[t]), t
+  _no_faults(e)
+  for o in oracles:
+    o.close()
+  e.close()
+
+
+def test_placed_pooled_world_view():
+  """mp_place_output on a pooled world view: the placed buffer is drawn exactly."""
+  pack = engine.load_pack("clean_up")
+  n, steps = 64, 5
+  e = engine.Engine(pack, n, device=0, world_pool=2)
+  out = e.place(engine.OBS_WORLD_RGB, candidates=3)
+  assert out.data_ptr() % 16 == 0
+  oracles = util.make_oracles(pack, n)
+  e.reset()
+  for o in oracles:
+    o.reset()
+  rng = np.random.default_rng(8)
+  acts = rng.integers(0, e.num_actions, size=(steps, n, e.P), dtype=np.int32)
+  for s in range(steps):
+    e.step(torch.from_numpy(acts[s]).to(e.device))
+    for w, o in enumerate(oracles):
+      o.step(acts[s, w])
+  got = out.cpu().numpy()
+  for w, o in enumerate(oracles):
+    assert np.array_equal(got[w], engine.pool_rgb(o.render_world(), 2)), w
+  _no_faults(e)
+  for o in oracles:
+    o.close()
+  e.close()
+
+
+def test_box_fill_and_misaligned_buffers_are_refused():
+  e = engine.Engine(engine.load_pack("coins"), 8, device=0, world_pool=8)
+  shape, dtype = e.shapes[engine.OBS_WORLD_RGB]
+  assert shape == (8, 17, 17, 3)
+  nbytes = int(np.prod(shape))
+  raw = torch.empty(nbytes + 32, dtype=torch.uint8, device=e.device)
+  off = (16 - raw.data_ptr() % 16) % 16 + 1   # 1 byte past a 16-byte line
+  bad = raw[off:off + nbytes].view(shape)
+  with pytest.raises(ValueError, match="16-byte aligned"):
+    e.bind(engine.OBS_WORLD_RGB, bad)
+  with pytest.raises(ValueError, match="16-byte aligned"):
+    e.observe(engine.OBS_WORLD_RGB, bad)
+  e.bind(engine.OBS_WORLD_RGB)
+  with pytest.raises(ValueError, match="world_pool"):
+    e.box_fill(engine.OBS_WORLD_RGB)
+  e.reset()
+  _no_faults(e)
+  e.close()
+
+
+def test_api_shapes_and_spec():
+  """6.  The drop-in surface: both factors, batched, the one-world host mirror and a ring."""
+  roles = ("default",) * 7
+  env = substrate.build("clean_up", roles=roles, num_worlds=16, rgb_pool=8, world_rgb_pool=2)
+  ts = env.reset()
+  assert tuple(ts.observation["RGB"].shape) == (16, 7, 11, 11, 3)
+  assert tuple(ts.observation["WORLD.RGB"].shape) == (16, 84, 120, 3)
+  spec = env.observation_spec()[0]
+  assert spec["WORLD.RGB"].shape == (84, 120, 3) and spec["WORLD.RGB"].dtype == np.uint8
+  assert spec["RGB"].shape == (11, 11, 3)
+  _no_faults(env.engine)
+  env.close()
+  one = substrate.build("clean_up", roles=roles, world_rgb_pool=8)
+  ts = one.reset()
+  ts = one.step([0] * 7)
+  for obs in ts.observation:
+    assert obs["WORLD.RGB"].shape == (21, 30, 3) and obs["RGB"].shape == (88, 88, 3)
+  _no_faults(one.engine)
+  one.close()
+  ringed = substrate.build("clean_up", roles=roles, num_worlds=4, world_rgb_pool=4, rollout_length=3)
+  ringed.reset()
+  ringed.step(torch.zeros((4, 7), dtype=torch.int32, device="cuda"))
+  assert tuple(ringed.rollout["observation"]["WORLD.RGB"].shape) == (3, 4, 42, 60, 3)
+  _no_faults(ringed.engine)
+  ringed.close()
+
+
+def _assert_step_matches_specs(env):
+  env.reset()
+  action = [int(spec.maximum) for spec in env.action_spec()]
+  timestep = env.step(action)
+  observation_specs = env.observation_spec()
+  assert len(observation_specs) == len(timestep.observation)
+  for observation, spec in zip(timestep.observation, observation_specs):
+    assert set(spec) == set(observation)
+    for key in spec:
+      spec[key].validate(observation[key])
+
+
+@pytest.mark.parametrize("name", sorted(substrate.SUBSTRATES))
+def test_conformance_with_world_rgb_pool(name):
+  """6.  The per-substrate conformance check with world_rgb_pool=8 (rgb_pool=4 beside it)."""
+  factory = substrate.get_factory(name)
+  with factory.build(factory.default_player_roles(), rgb_pool=4, world_rgb_pool=8) as env:
+    _assert_step_matches_specs(env)
+    spec = env.observation_spec()[0]
+    full = factory.timestep_spec().observation
+    assert spec["WORLD.RGB"].shape == (full["WORLD.RGB"].shape[0] // 8, full["WORLD.RGB"].shape[1] // 8, 3)
+    assert spec["RGB"].shape == (full["RGB"].shape[0] // 4, full["RGB"].shape[1] // 4, 3)
+    _no_faults(env.engine)
