@@ -139,8 +139,12 @@ typedef enum {
                                 sprite index (after the viewer's spriteMap) of the
                                 piece or beam in each cell-layer, 0 = nothing;
                                 cells outside the map hold OutOfBounds in every
-                                layer.  Bound, it is refreshed by
-                                one more small launch per step. */
+                                layer.  Bound (mp_bind_output or
+                                mp_bind_output_ring), it is written by the launch
+                                that resets or steps the worlds, from each record
+                                while it is in LDS: no launch of its own.
+                                mp_observe reads it from the records in HBM.
+                                mp_place_output does not take this kind. */
   MP_OBS_INVENTORY = 17,     /* "N.INVENTORY" f64 [N][P][R]: TheMatrix.playerResources
                                 (the_matrix/components.lua:942-963); gift_refinements:
                                 Inventory.inventory (gift_refinements/components.lua:239-353);
@@ -349,7 +353,8 @@ int mp_bind_output(MpEngine* eng, MpObsKind kind, void* device_ptr);
  * pixel views and remembers a plan per slot.  mp_observe of a ring-bound scalar kind
  * reads the slot written last.  base == NULL unbinds the kind (like mp_bind_output
  * with NULL; so does mp_bind_output on the kind).  MpInfo.ring_slots / ring_next
- * report the position. */
+ * report the position.  MP_OBS_LAYER may be a ring kind like any other; mp_tune's
+ * probe launches do not write it, so every LAYER slot keeps the step that wrote it. */
 int mp_bind_output_ring(MpEngine* eng, MpObsKind kind, void* base,
                         uint64_t slot_stride_bytes, int32_t slots);
 

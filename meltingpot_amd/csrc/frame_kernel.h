@@ -973,6 +973,13 @@ __global__ __launch_bounds__(max_threads<Tables>()) void k_frame(DevTables t, Ta
             stepk::wsync();
             const stepk::Action act = stepk::lookup_action(t, wd, act_id, args.mode);
             stepk::step_world(t, c, sites, wd, act, args);
+            // "N.LAYER", when bound: by this feeder from the slot's record, which finish() has
+            // already published — the renderers draw it meanwhile, and only this feeder refills
+            // the slot (profiles/r09_layer_obs.md)
+            if (args.out.layer) {
+              stepk::wsync();
+              stepk::write_layer(t, rec, args.out, w, lane_w);
+            }
           } else {
             stepk::load_record(t, rec, args.state + (size_t)w * fc.wstride, lane);
           }

@@ -379,7 +379,16 @@ struct StepOutputs {
   double* interaction;   // [N][P][2][R]  "N.INTERACTION_INVENTORIES"
   double* cumulants;     // [N][P][1 + 3 R] MP_OBS_MATRIX_CUMULANTS (debug: NULL unless bound)
   double* interaction_rewards;   // [N][P][2] MP_OBS_INTERACTION_REWARDS
+  // "N.LAYER" (MP_OBS_LAYER), written by the launch that steps the worlds when bound (NULL
+  // otherwise): [N][P][VH][VW][L] int32, and its values [P][kLayerLutRow] (stepk::write_layer)
+  int32_t* layer;
+  const int32_t* layer_lut;
 };
+
+// A viewer's row of StepOutputs::layer_lut: the LAYER value of every state a record byte can
+// hold (0 for state 0 and states without a sprite, else 1 + the viewer's remapped sprite), and
+// at [256] the OutOfBounds value an off-grid or dead viewer sees on every layer (A6).
+constexpr int kLayerLutRow = 257;
 
 // ---------------------------------------------------------------------------
 // Philox4x32-10 (Salmon et al., SC'11), the engine's counter-based generator.

@@ -101,6 +101,7 @@ struct MpEngine {
   int ring_slots = 0;              // 0: no kind is ring-bound
   uint64_t ring_cursor = 0;        // submissions since the ring was bound
   bool ring_hold = false;          // mp_tune: submissions stay on the slot it pointed at
+  bool layer_hold = false;         // mp_tune: submissions leave a bound "N.LAYER" alone
   std::vector<FramePlan> ring_plan[3];   // [views]: the plan mp_tune kept for each slot (empty: plan[1][views])
   void point_ring(int slot, bool pixels_only = false) {
     for (int k = 0; k < MP_OBS_KINDS; ++k)
@@ -167,6 +168,7 @@ struct MpEngine {
     return unfused != 1;
   }
   uint8_t* d_atlas = nullptr;      // de-duplicated atlas + image slots
+  int32_t* d_layer_lut = nullptr;  // StepOutputs::layer_lut [P][kLayerLutRow]
   StepOutputs outputs() const {
     StepOutputs o = own;
     if (bound[MP_OBS_REWARD]) o.reward = (double*)bound[MP_OBS_REWARD];
@@ -187,6 +189,7 @@ struct MpEngine {
     if (bound[MP_OBS_MATRIX_CUMULANTS]) o.cumulants = (double*)bound[MP_OBS_MATRIX_CUMULANTS];
     if (bound[MP_OBS_INTERACTION_REWARDS])
       o.interaction_rewards = (double*)bound[MP_OBS_INTERACTION_REWARDS];
+    if (bound[MP_OBS_LAYER] && !layer_hold) { o.layer = (int32_t*)bound[MP_OBS_LAYER]; o.layer_lut = d_layer_lut; }
     return o;
   }
 };
@@ -311,7 +314,8 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask) {
   if (ringing) { e->point_ring(slot); ++e->ring_cursor; }
   args.out = e->outputs();
   // One persistent launch steps the worlds and renders the bound views — one or
-  // both — from the records while they are in LDS (frame.hip).
+  // both — from the records while they are in LDS (frame.hip).  A bound "N.LAYER" is
+  // written by the launch that steps (args.out.layer): its feeders, or the step kernels.
   // (the per-agent view is MP_OBS_RGB or a pooled kind: pool_k)
   uint8_t* rgb = e->agent_view();
   uint8_t* wrgb = (uint8_t*)e->bound[MP_OBS_WORLD_RGB];
@@ -328,9 +332,6 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask) {
     p.parity = e->frame_launches++ & 1;
     launch_frame(e->t, &e->sub, args, rgb, wrgb, p, e->stream, pk, e->world_pool);
   }
-  // "N.LAYER", when bound: one more (small) launch on the stepped records
-  if (e->bound[MP_OBS_LAYER])
-    launch_layer_view(e->t, e->d_state, (int32_t*)e->bound[MP_OBS_LAYER], e->N, e->stream);
   HIP_TRY(hipGetLastError());
   return MP_OK;
 }
@@ -746,6 +747,27 @@ int build_atlas(MpEngine* e, const MpDevOptions* dev, const DecodedPack& d) {
   return MP_OK;
 }
 
+// "N.LAYER"'s value of every (viewer, record byte) — what k_layer_view looks up per dword:
+// 1 + the viewer's remapped sprite of the state, 0 for state 0 and states without a sprite
+// (and bytes no state has); [256]: OutOfBounds (sprite 0), what an off-grid viewer sees.
+int upload_layer_lut(MpEngine* e) {
+  const DevTables& t = e->t;
+  const void* hp = e->pack.data();
+  const int32_t* ssprite = table<int32_t>(hp, "state_sprite");
+  const int32_t* vmap = table<int32_t>(hp, "view_sprite_map");
+  std::vector<int32_t> lut((size_t)t.P * kLayerLutRow, 0);
+  for (int p = 0; p < t.P; ++p) {
+    const int32_t* remap = vmap + (size_t)p * t.nsprites;
+    int32_t* row = lut.data() + (size_t)p * kLayerLutRow;
+    for (int s = 1; s < t.nstates && s < 256; ++s)
+      row[s] = ssprite[s] >= 0 ? 1 + remap[ssprite[s]] : 0;
+    row[256] = 1 + remap[0];
+  }
+  HIP_TRY(hipMalloc((void**)&e->d_layer_lut, lut.size() * 4));
+  HIP_TRY(hipMemcpy(e->d_layer_lut, lut.data(), lut.size() * 4, hipMemcpyHostToDevice));
+  return MP_OK;
+}
+
 // The frame launches' plans, plain and pooled.
 int plan_views(MpEngine* e, const MpDevOptions* dev) {
   const DevTables& t = e->t;
@@ -812,7 +834,7 @@ int create_on_device(MpEngine* e, const MpConfig& cfg, DecodedPack* d) {
   e->num_cus = cus;
   int rc;
   if ((rc = upload_pack(e, cfg, d)) || (rc = alloc_fault_words(e)) || (rc = init_state(e, cfg)) ||
-      (rc = alloc_outputs(e, cfg)) || (rc = build_atlas(e, dev, *d)))
+      (rc = alloc_outputs(e, cfg)) || (rc = build_atlas(e, dev, *d)) || (rc = upload_layer_lut(e)))
     return rc;
   return plan_views(e, dev);
 }
@@ -923,7 +945,8 @@ void mp_destroy(MpEngine* e) {
   (void)hipStreamSynchronize(e->stream);
   if (e->h_fault) (void)hipHostFree(e->h_fault);
   void* bufs[] = {e->d_pack, e->d_extra, e->d_stepblob, e->d_debug, e->d_state, e->d_scalars,
-                  e->d_actions, e->d_fields, e->d_mask, e->d_seeds, e->d_atlas, e->d_ctr, e->d_claim};
+                  e->d_actions, e->d_fields, e->d_mask, e->d_seeds, e->d_atlas, e->d_ctr, e->d_claim,
+                  e->d_layer_lut};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   for (int i = 0; i < MpEngine::kHostSlots; ++i)
@@ -1013,8 +1036,6 @@ int mp_bind_output_ring(MpEngine* e, MpObsKind kind, void* base, uint64_t slot_s
   const uint64_t bytes = mp_obs_bytes(e, kind);
   if (bytes == 0)
     return fail(MP_ERR_UNSUPPORTED, "mp_bind_output_ring: this substrate has no observation %d", (int)kind);
-  if (kind == MP_OBS_LAYER)
-    return fail(MP_ERR_UNSUPPORTED, "mp_bind_output_ring: N.LAYER is not offered as a ring");
   if (slots < 1 || slots > (1 << 20))
     return fail(MP_ERR_INVALID, "mp_bind_output_ring: %d slots", (int)slots);
   if (slot_stride_bytes < bytes || (slot_stride_bytes & 255) != 0)
@@ -1588,7 +1609,9 @@ struct ProbeState {
   uint8_t* part(int k) const {
     return k == 0 ? e->d_state : k == 1 ? (uint8_t*)e->d_ctr : k == 2 ? e->d_scalars : e->d_debug;
   }
-  void hold_ring() { was_held = e->ring_hold; e->ring_hold = true; held = true; }
+  // (and a bound "N.LAYER" is not written by the probe's launches: dry ones would put the records'
+  // LAYER into whichever ring slot is being timed, stepping ones the probe's steps')
+  void hold_ring() { was_held = e->ring_hold; e->ring_hold = true; e->layer_hold = true; held = true; }
   // MP_OK with copied == false: no room for the copy — the probe runs dry
   int save() {
     const size_t total = parts[0] + parts[1] + parts[2] + parts[3];
@@ -1641,6 +1664,7 @@ struct ProbeState {
     if (saved) { (void)hipFree(saved); saved = nullptr; }
     if (held) {
       e->ring_hold = was_held;
+      e->layer_hold = false;
       held = false;
       if (e->ring_slots > 0 && !e->ring_hold) {   // ring kinds point at the slot written last again
         const uint64_t last = e->ring_cursor ? (e->ring_cursor - 1) % (uint64_t)e->ring_slots : 0;

@@ -771,6 +771,73 @@ __device__ inline void finish(const DevTables& t, const World& wd, WorldTail* ta
   }
 }
 
+// ---- "N.LAYER" (avatar_library.lua:246-257; A17) from the record in LDS
+// n / d in one multiply: magic = 2^32 / d + 1 (0 for d == 1), exact while n * d < 2^32 (a world's
+// LAYER block is 16 x 31 x 31 x 16 dwords at most, and a wrapped coordinate < 3 W).
+__device__ inline uint32_t magic_of(uint32_t d) { return d > 1 ? 0xffffffffu / d + 1u : 0u; }
+__device__ inline uint32_t div_by(uint32_t n, uint32_t magic) { return magic ? __umulhi(n, magic) : n; }
+
+// The world's [P][VH][VW][L] int32 block of StepOutputs::layer, from the record this wave has in
+// LDS (`rec`: planes + WorldTail, final) — no HBM read but the 1 KB value table, which stays in the
+// caches.  The block is contiguous and starts on any dword: up to three dwords before its first
+// 16-byte boundary, then 16-byte chunks, lane-contiguous (four chunks a lane per round: their
+// loads are all in flight before the first store), then up to three dwords.  A dword's (viewer,
+// window cell, layer) is worked out per dword.  Values as k_layer_view's: 1 + the viewer's
+// remapped sprite, 0 for nothing; OutOfBounds on every layer for a viewer off the grid or dead
+// (A6); TORUS wraps.
+__device__ inline void write_layer(const DevTables& t, const uint8_t* rec, const StepOutputs& out,
+                                   int w, int lane) {
+  const uint32_t L = (uint32_t)t.L, VW = (uint32_t)(t.vl + t.vr + 1), VH = (uint32_t)(t.vf + t.vb + 1);
+  const uint32_t n = (uint32_t)t.P * VH * VW * L;
+  const uint32_t mL = magic_of(L), mVW = magic_of(VW), mVH = magic_of(VH);
+  const uint32_t mW = magic_of((uint32_t)t.W), mH = magic_of((uint32_t)t.H);
+  // (TORUS: x + ox >= 0 in every window column, so the wrap is one unsigned remainder)
+  const int ox = t.W * ((t.vl + t.W - 1) / t.W), oy = t.H * ((t.vf + t.H - 1) / t.H);
+  const bool torus = t.topology == 1;
+  const int W = t.W, H = t.H, HW = t.H * t.W;
+  const WorldTail* tail = reinterpret_cast<const WorldTail*>(rec + t.grid_pad);
+  const int32_t* lut = out.layer_lut;
+  auto value = [&](uint32_t e) -> int32_t {
+    const uint32_t cell = div_by(e, mL), l = e - cell * L;
+    const uint32_t r = div_by(cell, mVW), vx = cell - r * VW;
+    const uint32_t p = div_by(r, mVH), vy = r - p * VH;
+    int x = (int)tail->ax[p] + (int)vx - t.vl, y = (int)tail->ay[p] + (int)vy - t.vf;
+    bool in;
+    if (torus) {
+      const uint32_t xx = (uint32_t)(x + ox), yy = (uint32_t)(y + oy);
+      x = (int)(xx - div_by(xx, mW) * (uint32_t)W);
+      y = (int)(yy - div_by(yy, mH) * (uint32_t)H);
+      in = true;
+    } else {
+      in = x >= 0 && x < W && y >= 0 && y < H;
+    }
+    const int s = in && tail->aalive[p] ? (int)rec[(int)l * HW + y * W + x] : 256;
+    return lut[p * kLayerLutRow + (uint32_t)s];
+  };
+  int32_t* blk = out.layer + (size_t)w * n;
+  const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(blk) >> 2) & 3u;
+  const uint32_t head = ((4u - mis) & 3u) < n ? ((4u - mis) & 3u) : n;
+  if ((uint32_t)lane < head) blk[lane] = value((uint32_t)lane);
+  const uint32_t nq = (n - head) >> 2;
+  int4* q = reinterpret_cast<int4*>(blk + head);
+  for (uint32_t c0 = 0; c0 < nq; c0 += 4 * 64) {
+    int4 v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t c = c0 + (uint32_t)(k * 64 + lane);
+      const uint32_t e = head + 4u * (c < nq ? c : nq - 1u);
+      v[k] = int4{value(e), value(e + 1), value(e + 2), value(e + 3)};
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t c = c0 + (uint32_t)(k * 64 + lane);
+      if (c < nq) q[c] = v[k];
+    }
+  }
+  const uint32_t rest = head + 4u * nq + (uint32_t)lane;
+  if (rest < n) blk[rest] = value(rest);
+}
+
 // Decides reset / step / frozen for this launch (wave-uniform).
 //   returns 0: nothing to do, 1: reset, 2: step
 __device__ inline int dispatch(const DevTables& t, const WorldTail* tail, int lane, int w,

@@ -2,7 +2,7 @@
 // worlds per workgroup (they share the read-only LDS tables).  They run the same wave-level step functions
 // (step_<substrate>.h) as the fused step + render kernels of frame.hip, and are
 // what an engine launches when no RGB observation is bound to a step (and for
-// mp_reset).  Reference path replaced: api:advance / api:start
+// mp_reset).  A bound "N.LAYER" is written by the wave that stepped the world.  Reference path replaced: api:advance / api:start
 // (lua/modules/api_factory.lua:85-111) — see step_clean_up.h.
 #include "../../include/mp_pack.h"
 #include "step_clean_up.h"
@@ -59,6 +59,12 @@ __device__ inline void run_one_world(const DevTables& t, const Tables& c, const 
   const Action act = lookup_action(t, wd, act_id, args.mode);
   init_extra(t, c, wd.extra, lane);
   step_world(t, c, sites, wd, act, args);
+  // "N.LAYER", when bound: from the record while it is in LDS (frozen and masked-out worlds
+  // included: their record is the one in HBM)
+  if (args.out.layer) {
+    wsync();
+    write_layer(t, wd.rec, args.out, w, lane);
+  }
 }
 
 __global__ __launch_bounds__(kWorldsPerGroup * 64) void k_step_clean_up(DevTables t, CleanUpTables c, StepArgs args) {
@@ -90,9 +96,10 @@ __global__ __launch_bounds__(kWorldsPerGroup * 64) void k_step_territory(DevTabl
 }
 
 // "N.LAYER" (avatar_library.lua:246-257): the player's layer view with
-// orientation 'N', as sprite ids (A17; oracle/render.c: orc_layer_view).  A debug
-// observation read straight from the records in HBM: one thread per (world,
-// player, window cell).
+// orientation 'N', as sprite ids (A17; oracle/render.c: orc_layer_view), read straight
+// from the records in HBM: one thread per (world, player, window cell).  What
+// mp_observe(MP_OBS_LAYER) launches; a bound LAYER is written by the launch that steps
+// the worlds instead (stepk::write_layer).
 __global__ void k_layer_view(DevTables t, const uint8_t* __restrict__ state,
                              int32_t* __restrict__ out, int num_worlds) {
   const int VW = t.vl + t.vr + 1, VH = t.vf + t.vb + 1, HW = t.H * t.W;

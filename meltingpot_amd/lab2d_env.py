@@ -29,12 +29,15 @@ from meltingpot_amd import substrate as substrate_lib
 class Environment:
 
   def __init__(self, name: str, roles, *, env_seed=None, device: int = 0, engine=None,
-               config=None):
+               config=None, layer: bool = False):
     """`engine`: an object with the `engine.Engine` interface for one world
     (default: a HIP engine on `device` with the committed pack of substrate `name`;
     the conformance tests pass a stand-in driven by the CPU oracle where there is no
     GPU).  `config`: the observation names and specs of a pack lowered at run time
-    (`meltingpot_amd.builder`: `name` is then the level, `engine` runs that pack)."""
+    (`meltingpot_amd.builder`: `name` is then the level, `engine` runs that pack).
+    `layer`: offer "N.LAYER" too (avatar_library.lua:246-257), the avatar's window with
+    orientation 'N' as int32 sprite ids [VH, VW, L] — also offered when the config names
+    "LAYER" among its individual observations."""
     if config is not None and engine is None:
       raise ValueError("a run-time config needs the engine created on its pack")
     self._cfg = config if config is not None else substrate_lib.get_config(name)
@@ -58,6 +61,10 @@ class Environment:
     # actionOrder and actionSpec of the avatars (avatar_library.lua:205-223), as
     # lowered into the pack: the fields of dmlab2d's raw action surface
     self._names, self._ranges = substrate_lib.action_fields(self._eng)
+    # the per-player observations: the config's, and "LAYER" when asked for
+    self._individual = list(self._cfg.individual_observation_names)
+    if layer and "LAYER" not in self._individual:
+      self._individual.append("LAYER")
 
   # -- dmlab2d.Environment surface -----------------------------------------
   def action_spec(self) -> Dict[str, substrate_lib.BoundedArray]:
@@ -71,8 +78,12 @@ class Environment:
   def observation_spec(self) -> Dict[str, substrate_lib.Array]:
     spec = {}
     for p in range(self._P):
-      for n in self._cfg.individual_observation_names:
-        spec[f"{p + 1}.{n}"] = self._cfg.timestep_spec[n].replace(name=f"{p + 1}.{n}")
+      for n in self._individual:
+        if n == "LAYER":   # (dmlab2d's layer view: an Int32Tensor [VH, VW, L])
+          spec[f"{p + 1}.{n}"] = substrate_lib.layer_spec(self._eng.pack_bytes).replace(
+              name=f"{p + 1}.{n}")
+        else:
+          spec[f"{p + 1}.{n}"] = self._cfg.timestep_spec[n].replace(name=f"{p + 1}.{n}")
       spec[f"{p + 1}.REWARD"] = substrate_lib.Array((), np.float64, f"{p + 1}.REWARD")
     for n in self._cfg.global_observation_names:
       spec[n] = self._cfg.timestep_spec[n]
@@ -129,14 +140,13 @@ class Environment:
     obs = {}
     per = {"RGB": E.OBS_RGB, "READY_TO_SHOOT": E.OBS_READY_TO_SHOOT,
            "INVENTORY": E.OBS_INVENTORY,
-           "INTERACTION_INVENTORIES": E.OBS_INTERACTION_INVENTORIES}
+           "INTERACTION_INVENTORIES": E.OBS_INTERACTION_INVENTORIES, "LAYER": E.OBS_LAYER}
     if self._cfg.aux0_name:
       per[self._cfg.aux0_name] = E.OBS_AUX0
-    host = {n: self._eng.observe_host(per[n])[0]
-            for n in self._cfg.individual_observation_names}
+    host = {n: self._eng.observe_host(per[n])[0] for n in self._individual}
     reward = self._eng.observe_host(E.OBS_REWARD)[0]
     for p in range(self._P):
-      for n in self._cfg.individual_observation_names:
+      for n in self._individual:
         obs[f"{p + 1}.{n}"] = host[n][p]
       obs[f"{p + 1}.REWARD"] = reward[p]
     if "WORLD.RGB" in self._cfg.global_observation_names:

@@ -677,7 +677,10 @@ class Substrate:
                    "COLLECTIVE_REWARD": E.OBS_COLLECTIVE_REWARD,
                    "INVENTORY": E.OBS_INVENTORY,
                    "INTERACTION_INVENTORIES": E.OBS_INTERACTION_INVENTORIES,
-                   "POSITION": E.OBS_POSITION, "ORIENTATION": E.OBS_ORIENTATION}
+                   "POSITION": E.OBS_POSITION, "ORIENTATION": E.OBS_ORIENTATION,
+                   # the symbolic view (avatar_library.lua:246-257): written by the step's own
+                   # launch, from the records while they are in LDS
+                   "LAYER": E.OBS_LAYER}
     if config.aux0_name:
       self._kinds[config.aux0_name] = E.OBS_AUX0
     if config.name.split("__")[0] == "clean_up":
@@ -862,6 +865,8 @@ class Substrate:
       k = self._world_rgb_pool
       h, w, c = spec["WORLD.RGB"].shape
       spec["WORLD.RGB"] = Array((h // k, w // k, c), spec["WORLD.RGB"].dtype, "WORLD.RGB")
+    if "LAYER" in self._config.individual_observation_names:
+      spec["LAYER"] = layer_spec(self._eng.pack_bytes)
     return [dict(spec) for _ in self._roles]
 
   def action_spec(self) -> List[DiscreteArray]:
@@ -939,6 +944,16 @@ _EXTRA_SPECS = {"POSITION": Array((2,), np.int32, "POSITION"),
                 "NUM_OTHERS_WHO_ATE_THIS_STEP": Array((), np.float64, "NUM_OTHERS_WHO_ATE_THIS_STEP")}
 
 
+def layer_spec(pack_bytes: bytes) -> Array:
+  """"LAYER" of a pack (avatar_library.lua:246-257, A17): the player's window with orientation
+  'N' as int32 sprite ids, one per render layer — (VH, VW, L); 0 is nothing, 1 + k sprite k."""
+  from meltingpot_amd import lower, pack as pack_lib
+  hdr = pack_lib.loads(pack_bytes)["hdr"]
+  return Array((int(hdr[lower.HDR_VF]) + int(hdr[lower.HDR_VB]) + 1,
+                int(hdr[lower.HDR_VL]) + int(hdr[lower.HDR_VR]) + 1, int(hdr[lower.HDR_L])),
+               np.int32, "LAYER")
+
+
 def timestep_spec_of(observation_spec: Mapping[str, Array]) -> TimeStep:
   """utils/substrates/specs.py:149-166 `specs.timestep`: the spec of the timestep ONE
   player sees — step_type / reward / discount specs + the observation specs, each
@@ -983,6 +998,8 @@ def build_substrate(*, lab2d_settings: Mapping[str, Any],
   for n in list(individual) + list(global_observations):
     if n in _EXTRA_SPECS:
       spec[n] = _EXTRA_SPECS[n]
+  if "LAYER" in individual:
+    spec["LAYER"] = layer_spec(pack_bytes)
   config = SubstrateConfig(
       name=level, action_set=table, individual_observation_names=individual,
       global_observation_names=list(global_observations),
@@ -1073,7 +1090,8 @@ def check_config_against_pack(config: SubstrateConfig, pack_bytes: bytes, num_pl
   S = int(hdr[lower.HDR_SPRITE])
   want = {"RGB": ((int(hdr[lower.HDR_VF]) + int(hdr[lower.HDR_VB]) + 1) * S,
                   (int(hdr[lower.HDR_VL]) + int(hdr[lower.HDR_VR]) + 1) * S, 3),
-          "WORLD.RGB": (int(hdr[lower.HDR_H]) * S, int(hdr[lower.HDR_W]) * S, 3)}
+          "WORLD.RGB": (int(hdr[lower.HDR_H]) * S, int(hdr[lower.HDR_W]) * S, 3),
+          "LAYER": layer_spec(pack_bytes).shape}
   for n, shape in want.items():
     if n in config.timestep_spec and tuple(config.timestep_spec[n].shape) != shape:
       raise ValueError(

@@ -1,0 +1,211 @@
+""""LAYER" (avatar_library.lua:246-257; A17) as a policy input, without a GPU: the C ABI it goes
+through is unchanged, and the product's `Substrate`, `build_substrate`, an edited
+`SubstrateConfig` and `lab2d_env.Environment` offer it — run on the CPU oracle behind the engine
+interface (test infrastructure: tests/oracle_engine.py, with the oracle's layer view added here)."""
+import os
+import pickle
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from meltingpot_amd import _build, builder, engine, lab2d_env, substrate
+from oracle_engine import OracleBatchEngine, OracleEngine
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+
+
+class LayerBatchEngine(OracleBatchEngine):
+  """OracleBatchEngine with MP_OBS_LAYER: every world's `Oracle.layer_view` of every player."""
+
+  def __init__(self, pack_bytes, num_worlds, **kw):
+    super().__init__(pack_bytes, num_worlds, **kw)
+    vh, vw, L = substrate.layer_spec(self.pack_bytes).shape
+    self.shapes[engine.OBS_LAYER] = ((self.N, self.P, vh, vw, L), torch.int32)
+
+  def _value(self, kind):
+    if kind == engine.OBS_LAYER:
+      return np.stack([np.stack([o.layer_view(p) for p in range(self.P)]) for o in self._o])
+    return super()._value(kind)
+
+
+class LayerEngine(OracleEngine):
+  def observe_host(self, kind):
+    if kind == engine.OBS_LAYER:
+      return np.stack([self._o.layer_view(p) for p in range(self.P)])[None]
+    return super().observe_host(kind)
+
+
+@pytest.fixture
+def layer_backed(monkeypatch):
+  monkeypatch.setattr(substrate.engine_lib, "Engine", LayerBatchEngine)
+  return LayerBatchEngine
+
+
+@pytest.fixture(scope="module")
+def settings():
+  with open(os.path.join(HERE, "golden", "clean_up_modified_settings.pkl"), "rb") as f:
+    return pickle.load(f)["lab2d_settings"]
+
+
+def _oracles(pack_bytes, n, seed, players):
+  from oracle import oracle as oracle_lib
+  return [oracle_lib.Oracle(pack_bytes, seed + w, players) for w in range(n)]
+
+
+def test_the_c_abi_does_not_grow():
+  """The LAYER ring goes through the existing entry point and kind."""
+  header = open(os.path.join(ROOT, "include", "mp_engine.h")).read()
+  assert re.search(r"#define MP_ABI_VERSION 8\b", header)
+  assert "MP_OBS_KINDS = 24" in header or re.search(r"MP_OBS_KINDS\s*=\s*24", header)
+  assert re.search(r"MP_OBS_LAYER\s*=\s*16", header)
+  path = _build.build_engine()
+  out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True,
+                       check=True).stdout
+  names = {line.split()[-1] for line in out.splitlines()
+           if line.split() and line.split()[-2] in ("T", "D", "B", "R")}
+  assert names == set(engine.ABI_SYMBOLS) and len(names) == 30
+  assert "mp_*;" in open(os.path.join(ROOT, "meltingpot_amd", "csrc", "exports.map")).read()
+  assert engine.MP_ABI_VERSION == 8 and engine.OBS_LAYER == 16
+
+
+def test_layer_spec_of_every_committed_pack():
+  for name in substrate.SUBSTRATES:
+    pack = engine.load_pack(name)
+    spec = substrate.layer_spec(pack)
+    from meltingpot_amd import lower, pack as pack_lib
+    hdr = pack_lib.loads(pack)["hdr"]
+    assert spec.dtype == np.int32 and spec.name == "LAYER"
+    assert spec.shape == (int(hdr[lower.HDR_VF]) + int(hdr[lower.HDR_VB]) + 1,
+                          int(hdr[lower.HDR_VL]) + int(hdr[lower.HDR_VR]) + 1,
+                          int(hdr[lower.HDR_L])), name
+
+
+def test_default_observation_lists_do_not_name_layer():
+  for name in substrate.SUBSTRATES:
+    cfg = substrate.get_config(name)
+    assert "LAYER" not in cfg.individual_observation_names, name
+    assert "LAYER" not in cfg.global_observation_names, name
+
+
+def test_build_substrate_with_layer(layer_backed, settings):
+  """build_substrate(individual_observations=["RGB", "LAYER"]): batched int32 [N, P, VH, VW, L]
+  leaves equal to the oracle's layer view, and the spec (VH, VW, L) int32."""
+  cfg = substrate.get_config("clean_up")
+  env = substrate.build_substrate(lab2d_settings=settings, individual_observations=["RGB", "LAYER"],
+                                  global_observations=[], action_table=cfg.action_set,
+                                  num_worlds=2, env_seed=30)
+  _, pack_bytes, _ = builder.lower_settings(settings, action_set=cfg.action_set)
+  refs = _oracles(pack_bytes, 2, 30, 7)
+  try:
+    spec = env.observation_spec()[0]["LAYER"]
+    assert spec.shape == (11, 11, substrate.layer_spec(pack_bytes).shape[2])
+    assert spec.dtype == np.int32
+    ts = env.reset()
+    for o in refs:
+      o.reset()
+    assert set(ts.observation) == {"RGB", "LAYER", "COLLECTIVE_REWARD"}
+    rng = np.random.default_rng(0)
+    for _ in range(4):
+      lay = ts.observation["LAYER"]
+      assert tuple(lay.shape) == (2, 7) + spec.shape and lay.dtype == torch.int32
+      for w, o in enumerate(refs):
+        for p in range(7):
+          assert np.array_equal(lay[w, p].numpy(), o.layer_view(p))
+      a = rng.integers(0, 9, size=(2, 7)).astype(np.int32)
+      ts = env.step(a)
+      for w, o in enumerate(refs):
+        o.step(a[w])
+  finally:
+    env.close()
+    for o in refs:
+      o.close()
+
+
+def test_edited_substrate_config_names_layer(layer_backed):
+  """get_config(name) with "LAYER" added: build_from_config and get_factory_from_config, batched,
+  unbatched (per-player numpy leaves) and as a rollout ring."""
+  cfg = substrate.get_config("territory__rooms")
+  cfg.individual_observation_names = list(cfg.individual_observation_names) + ["LAYER"]
+  roles = cfg.default_player_roles
+  P = len(roles)
+  want = substrate.layer_spec(engine.load_pack("territory__rooms"))
+  env = substrate.build_from_config(cfg, roles=roles, num_worlds=2)
+  try:
+    assert env.observation_spec()[0]["LAYER"] == want
+    ts = env.reset()
+    assert tuple(ts.observation["LAYER"].shape) == (2, P) + want.shape
+  finally:
+    env.close()
+  one = substrate.get_factory_from_config(cfg).build(roles)
+  try:
+    one.reset()
+    ts = one.step([0] * P)
+    for obs in ts.observation:
+      assert obs["LAYER"].shape == want.shape and obs["LAYER"].dtype == np.int32
+      want.validate(obs["LAYER"])
+  finally:
+    one.close()
+  ringed = substrate.build_from_config(cfg, roles=roles, num_worlds=2, rollout_length=3)
+  try:
+    ringed.reset()
+    for _ in range(4):
+      ts = ringed.step(np.zeros((2, P), np.int32))
+    lay = ringed.rollout["observation"]["LAYER"]
+    assert tuple(lay.shape) == (3, 2, P) + want.shape
+    assert torch.equal(ts.observation["LAYER"], lay[ringed.slot])
+  finally:
+    ringed.close()
+
+
+def test_an_edited_config_with_a_wrong_layer_shape_is_refused():
+  cfg = substrate.get_config("clean_up")
+  cfg.individual_observation_names = list(cfg.individual_observation_names) + ["LAYER"]
+  cfg.timestep_spec = dict(cfg.timestep_spec)
+  cfg.timestep_spec["LAYER"] = substrate.Array((9, 9, 4), np.int32, "LAYER")
+  with pytest.raises(ValueError, match="LAYER"):
+    substrate.build_from_config(cfg, roles=("default",) * 7)
+
+
+def test_unknown_observations_are_still_refused(layer_backed, settings):
+  cfg = substrate.get_config("clean_up")
+  with pytest.raises(ValueError, match="HUNGER"):
+    substrate.build_substrate(lab2d_settings=settings, individual_observations=["LAYER", "HUNGER"],
+                              global_observations=[], action_table=cfg.action_set)
+
+
+def test_lab2d_env_offers_n_layer():
+  """"N.LAYER" in the flat dmlab2d surface: asked for with layer=True, spec (VH, VW, L) int32."""
+  pack = engine.load_pack("clean_up")
+  raw = lab2d_env.Environment("clean_up", ("default",) * 7, engine=LayerEngine(pack, 5, 7),
+                              layer=True)
+  plain = lab2d_env.Environment("clean_up", ("default",) * 7, engine=OracleEngine(pack, 5, 7))
+  try:
+    spec = raw.observation_spec()
+    assert "1.LAYER" not in plain.observation_spec()
+    L = substrate.layer_spec(pack).shape[2]
+    for p in range(1, 8):
+      assert spec[f"{p}.LAYER"] == substrate.Array((11, 11, L), np.int32, f"{p}.LAYER")
+    ts = raw.reset()
+    assert set(ts.observation) == set(spec)
+    ts = raw.step({"1.move": 1, "2.fireZap": 1})
+    from oracle import oracle as oracle_lib
+    o = oracle_lib.Oracle(pack, 5, 7)
+    o.reset()
+    fields = np.zeros((7, len(raw._names)), np.int32)
+    for p in range(7):
+      for a, (n, (lo, hi, default)) in enumerate(zip(raw._names, raw._ranges)):
+        fields[p, a] = default
+    fields[0, raw._names.index("move")] = 1
+    fields[1, raw._names.index("fireZap")] = 1
+    o.step_fields(fields)
+    for p in range(7):
+      spec[f"{p + 1}.LAYER"].validate(ts.observation[f"{p + 1}.LAYER"])
+      assert np.array_equal(ts.observation[f"{p + 1}.LAYER"], o.layer_view(p))
+    o.close()
+  finally:
+    raw.close()
+    plain.close()
