@@ -26,8 +26,9 @@ from __future__ import annotations
 
 import dataclasses
 import enum
+import math
 import os
-from typing import Any, Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple
+from typing import Any, Callable, Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -581,6 +582,12 @@ def validate_action_table(action_table, names, ranges) -> np.ndarray:
   return rows
 
 
+def _check_pool_factor(arg: str, k) -> int:
+  if k not in (1, 2, 4, 8) or isinstance(k, bool):
+    raise ValueError(f"{arg} must be 1, 2, 4 or 8, got {k!r}")
+  return int(k)
+
+
 class Substrate:
   """N worlds of one substrate behind the reference's `Substrate` interface.
 
@@ -597,7 +604,8 @@ class Substrate:
                debug_observations: bool = False,
                action_table: Optional[Sequence[Mapping[str, int]]] = None,
                rollout_length: int = 0, check_device_actions: bool = False,
-               rgb_pool: int = 1, world_rgb_pool: int = 1):
+               rgb_pool: int = 1, world_rgb_pool: int = 1,
+               _leaves: Optional[Callable[[str, tuple, Any, Any], Any]] = None):
     """`action_table`: the discrete actions, as in the reference's
     `build_substrate(..., action_table)` (utils/substrates/substrate.py:107-139,
     discrete_action_wrapper.py:77-109): row i is what discrete action i does,
@@ -623,13 +631,14 @@ class Substrate:
 
     `world_rgb_pool` = k in (2, 4, 8): the same for "WORLD.RGB", the whole map — e.g. (21, 30, 3)
     for clean_up's 168 x 240 image at k = 8 (MpConfig.world_pool: the engine draws it pooled,
-    the full image is never written).  The two factors are independent."""
-    if rgb_pool not in (1, 2, 4, 8) or isinstance(rgb_pool, bool):
-      raise ValueError(f"rgb_pool must be 1, 2, 4 or 8, got {rgb_pool!r}")
-    if world_rgb_pool not in (1, 2, 4, 8) or isinstance(world_rgb_pool, bool):
-      raise ValueError(f"world_rgb_pool must be 1, 2, 4 or 8, got {world_rgb_pool!r}")
-    self._rgb_pool = int(rgb_pool)
-    self._world_rgb_pool = int(world_rgb_pool)
+    the full image is never written).  The two factors are independent.
+
+    `_leaves` (private; `MixtureSubstrate`): called as `_leaves(name, shape, dtype, device)` with
+    the engine's shape of each leaf of a batched substrate, it returns the tensor to bind instead
+    of one the engine allocates — [n, ...], or [T, n, ...] with a ring — e.g. a slice of a
+    tensor that several substrates share."""
+    self._rgb_pool = _check_pool_factor("rgb_pool", rgb_pool)
+    self._world_rgb_pool = _check_pool_factor("world_rgb_pool", world_rgb_pool)
     invalid = set(roles) - config.valid_roles  # configs/substrates/__init__.py:42-45
     if invalid:
       raise ValueError(f"Invalid roles: {invalid!r}. Must be one of "
@@ -647,6 +656,8 @@ class Substrate:
     if self._T and not self._batched:
       raise ValueError("rollout_length needs a batched substrate (device tensors); the "
                        "one-world form already returns fresh numpy arrays every step")
+    if _leaves is not None and not self._batched:
+      raise ValueError("caller-provided leaves need a batched substrate")
     self._submissions = 0
     self._check_device_actions = bool(check_device_actions)
     if not self._roles:
@@ -698,12 +709,15 @@ class Substrate:
     kinds = {n: self._kinds[n] for n in names}
     kinds.update({"#reward": E.OBS_REWARD, "#discount": E.OBS_DISCOUNT,
                   "#step_type": E.OBS_STEP_TYPE})
+    # (None: the engine allocates the leaf itself)
+    take = ((lambda n, k: None) if _leaves is None else
+            (lambda n, k: _leaves(n, *self._eng.shapes[k], self._eng.device)))
     if self._batched and self._T:
       # the rollout ring: one [T, N, ...] tensor per leaf, written slot by slot
-      bound = {n: self._eng.bind_ring(k, slots=self._T) for n, k in kinds.items()}
+      bound = {n: self._eng.bind_ring(k, take(n, k), slots=self._T) for n, k in kinds.items()}
       self._host = None
     elif self._batched:
-      bound = {n: self._eng.bind(k) for n, k in kinds.items()}
+      bound = {n: self._eng.bind(k, take(n, k)) for n, k in kinds.items()}
       self._host = None
     else:
       # one world, numpy leaves: every output lives in one device buffer that is
@@ -810,6 +824,13 @@ class Substrate:
       a = a.reshape(1, self._eng.P)
     self._observables.action.on_next(action)
     self._eng.use_current_stream()
+    self._submit(a)
+    return self._emit(self._timestep())
+
+  def _submit(self, a):
+    """One step of the engine on actions `a` as `step` prepared them (an int32 device tensor
+    or a host array [N, P])."""
+    t = self._eng._torch
     if self._action_rows is None:
       self._eng.step(a)
     else:
@@ -829,7 +850,6 @@ class Substrate:
           raise ValueError(f"actions must be in [0, {K})")
         self._eng.step_fields(self._action_rows[a])
     self._submissions += 1
-    return self._emit(self._timestep())
 
   def observables(self) -> SubstrateObservables:
     """substrate.py:102-104.  `events` emits (name, payload) like the reference —
@@ -856,17 +876,8 @@ class Substrate:
     return self._eng.events(world)
 
   def observation_spec(self) -> List[Mapping[str, Array]]:
-    spec = dict(self._config.timestep_spec)
-    spec["COLLECTIVE_REWARD"] = Array((), np.float64, "COLLECTIVE_REWARD")
-    if self._rgb_pool > 1 and "RGB" in spec:
-      h, w, c = spec["RGB"].shape
-      spec["RGB"] = Array((h // self._rgb_pool, w // self._rgb_pool, c), spec["RGB"].dtype, "RGB")
-    if self._world_rgb_pool > 1 and "WORLD.RGB" in spec:
-      k = self._world_rgb_pool
-      h, w, c = spec["WORLD.RGB"].shape
-      spec["WORLD.RGB"] = Array((h // k, w // k, c), spec["WORLD.RGB"].dtype, "WORLD.RGB")
-    if "LAYER" in self._config.individual_observation_names:
-      spec["LAYER"] = layer_spec(self._eng.pack_bytes)
+    spec = observation_spec_of(self._config, self._eng.pack_bytes, self._rgb_pool,
+                               self._world_rgb_pool)
     return [dict(spec) for _ in self._roles]
 
   def action_spec(self) -> List[DiscreteArray]:
@@ -954,6 +965,43 @@ def layer_spec(pack_bytes: bytes) -> Array:
                np.int32, "LAYER")
 
 
+def observation_spec_of(config: SubstrateConfig, pack_bytes: bytes, rgb_pool: int = 1,
+                        world_rgb_pool: int = 1) -> Dict[str, Array]:
+  """One player's observation spec of a `Substrate` built from `config` and `pack_bytes` with
+  these pooling factors (what its `observation_spec()` hands out per player)."""
+  spec = dict(config.timestep_spec)
+  spec["COLLECTIVE_REWARD"] = Array((), np.float64, "COLLECTIVE_REWARD")
+  if rgb_pool > 1 and "RGB" in spec:
+    h, w, c = spec["RGB"].shape
+    spec["RGB"] = Array((h // rgb_pool, w // rgb_pool, c), spec["RGB"].dtype, "RGB")
+  if world_rgb_pool > 1 and "WORLD.RGB" in spec:
+    k = world_rgb_pool
+    h, w, c = spec["WORLD.RGB"].shape
+    spec["WORLD.RGB"] = Array((h // k, w // k, c), spec["WORLD.RGB"].dtype, "WORLD.RGB")
+  if "LAYER" in config.individual_observation_names:
+    spec["LAYER"] = layer_spec(pack_bytes)
+  return spec
+
+
+def select_observations(config: SubstrateConfig, pack_bytes: bytes,
+                        individual_observations: Sequence[str],
+                        global_observations: Sequence[str]):
+  """`build_substrate`'s choice of leaves (multiplayer_wrapper.py:108-167): the config's
+  individual observations that are asked for, in the config's order, then the other names
+  asked for (POSITION, LAYER, ... — unknown ones are refused when the substrate is built);
+  the global ones as given.  Returns (individual, global, timestep_spec)."""
+  individual = [n for n in config.individual_observation_names if n in set(individual_observations)]
+  individual += [n for n in individual_observations if n not in individual]   # (unknown ones: refused below)
+  spec = dict(config.timestep_spec)
+  for n in list(individual) + list(global_observations):
+    if n in _EXTRA_SPECS:
+      spec[n] = _EXTRA_SPECS[n]
+  if "LAYER" in individual:
+    spec["LAYER"] = layer_spec(pack_bytes)
+  wanted = set(individual) | set(global_observations)
+  return individual, list(global_observations), {n: sp for n, sp in spec.items() if n in wanted}
+
+
 def timestep_spec_of(observation_spec: Mapping[str, Array]) -> TimeStep:
   """utils/substrates/specs.py:149-166 `specs.timestep`: the spec of the timestep ONE
   player sees — step_type / reward / discount specs + the observation specs, each
@@ -992,19 +1040,11 @@ def build_substrate(*, lab2d_settings: Mapping[str, Any],
   names = tuple(n.decode() for n in bytes(tables["action_names"]).split(b"\0")[:-1])
   ranges = tuple(tuple(int(v) for v in row) for row in tables["action_spec"].reshape(-1, 3))
   validate_action_table(table, names, ranges)   # discrete_action_wrapper.py:28-49
-  individual = [n for n in config.individual_observation_names if n in set(individual_observations)]
-  individual += [n for n in individual_observations if n not in individual]   # (unknown ones: refused below)
-  spec = dict(config.timestep_spec)
-  for n in list(individual) + list(global_observations):
-    if n in _EXTRA_SPECS:
-      spec[n] = _EXTRA_SPECS[n]
-  if "LAYER" in individual:
-    spec["LAYER"] = layer_spec(pack_bytes)
+  individual, global_names, spec = select_observations(config, pack_bytes, individual_observations,
+                                                       global_observations)
   config = SubstrateConfig(
       name=level, action_set=table, individual_observation_names=individual,
-      global_observation_names=list(global_observations),
-      timestep_spec={n: sp for n, sp in spec.items()
-                     if n in set(individual) | set(global_observations)},
+      global_observation_names=global_names, timestep_spec=spec,
       valid_roles=config.valid_roles, default_player_roles=config.default_player_roles,
       aux0_name=config.aux0_name)
   return Substrate(config, config.default_player_roles, pack_bytes,
@@ -1156,3 +1196,415 @@ def build_from_config(config, *, roles: Sequence[str], num_worlds: int = 1,
   config DESCRIBES (`get_factory_from_config`): a reference config's own lab2d
   settings lowered at run time, or a `SubstrateConfig` checked against its pack."""
   return get_factory_from_config(config).build(roles, num_worlds=num_worlds, **kwargs)
+
+
+# --------------------------------------------------------------------------
+# Mixtures: several layouts of one level behind one batched Substrate
+
+
+# Every pixel leaf of a member starts on a 16-byte boundary: the engine stages a pooled view
+# (MP_OBS_RGB_POOL*, a pooled WORLD.RGB) by 16-byte lines and refuses any other buffer; a full
+# view is a multiple of 192 bytes a world (3 x 8 x 8 a cell), so it never adds to the granule.
+_PIXEL_ALIGN = 16
+_PIXEL_LEAVES = ("RGB", "WORLD.RGB")
+
+
+def leaf_bytes_per_world(config: SubstrateConfig, pack_bytes: bytes, num_players: int,
+                         rgb_pool: int = 1, world_rgb_pool: int = 1) -> Dict[str, int]:
+  """Bytes of one world of every leaf a batched `Substrate` of `config` binds (the
+  observations, "COLLECTIVE_REWARD" and the "#reward", "#discount", "#step_type" leaves)."""
+  spec = observation_spec_of(config, pack_bytes, rgb_pool, world_rgb_pool)
+  out = {}
+  for n, sp in spec.items():
+    count = num_players if n in config.individual_observation_names else 1
+    out[n] = count * int(np.prod(sp.shape, dtype=np.int64)) * sp.dtype.itemsize
+  out.update({"#reward": 8 * num_players, "#discount": 8, "#step_type": 4})
+  return out
+
+
+def world_granule(bytes_per_world: Mapping[str, int]) -> int:
+  """The smallest world count g such that a member that starts at a multiple of g worlds
+  starts every leaf on the boundary the engine wants of it: 16 bytes for the pixel views,
+  the element for the rest (which any offset gives).  E.g. clean_up's RGB pooled by 8 is
+  11 x 11 x 3 x 7 = 2541 B a world: g = 16."""
+  g = 1
+  for n, b in bytes_per_world.items():
+    if n in _PIXEL_LEAVES and b:
+      need = _PIXEL_ALIGN // math.gcd(int(b), _PIXEL_ALIGN)
+      g = g * need // math.gcd(g, need)
+  return g
+
+
+def split_worlds(num_worlds, members: int, granule: int) -> List[int]:
+  """World counts of `members` members: `num_worlds` is one count per member, each rounded UP
+  to a multiple of `granule`, or a total split as evenly as the granule allows (whole granules,
+  the first members one more; at least one granule each, so the total can grow by less than
+  `granule` — or to `members * granule`)."""
+  if isinstance(num_worlds, (int, np.integer)) and not isinstance(num_worlds, bool):
+    if num_worlds < 1:
+      raise ValueError(f"num_worlds must be positive, got {num_worlds}")
+    units = max(members, -(-int(num_worlds) // granule))
+    base, extra = divmod(units, members)
+    return [(base + (1 if i < extra else 0)) * granule for i in range(members)]
+  counts = [int(n) for n in num_worlds]
+  if len(counts) != members:
+    raise ValueError(f"{len(counts)} world counts for {members} members")
+  if any(n < 1 for n in counts):
+    raise ValueError(f"every member needs at least one world, got num_worlds={counts}")
+  return [-(-n // granule) * granule for n in counts]
+
+
+class _SharedLeaves:
+  """One tensor per leaf for all N worlds of a mixture ([T, N, ...] with a ring), allocated
+  when the first member asks for it; member i binds worlds [off_i, off_i + n_i) of it.
+
+  A ring's slot holds all N worlds; when N x bytes-per-world is not a multiple of 256 (the
+  slot stride mp_bind_output_ring takes) the slot is padded and the leaf is a strided view of
+  the padded allocation, so that `leaf[t]` is still [N, ...]."""
+
+  def __init__(self, total: int, slots: int):
+    self.total, self.slots = total, slots
+    self.leaves: Dict[str, Any] = {}
+
+  def _allocate(self, name, world_shape, dtype, device):
+    import torch
+    item = torch.empty((), dtype=dtype).element_size()
+    per_world = int(np.prod(world_shape, dtype=np.int64)) * item
+    # large pixel leaves from scattered 2 MB chunks, like the engine's own views (memory.py)
+    mapped = name in _PIXEL_LEAVES and device.type == "cuda"
+    if mapped:
+      from meltingpot_amd import memory
+      ctx = memory.mapped_allocations(device)
+    else:
+      import contextlib
+      ctx = contextlib.nullcontext()
+    shape = (self.total,) + tuple(world_shape)
+    with ctx:
+      if not self.slots:
+        return torch.empty(shape, dtype=dtype, device=device)
+      stride = -(-self.total * per_world // 256) * 256
+      if stride == self.total * per_world:
+        return torch.empty((self.slots,) + shape, dtype=dtype, device=device)
+      flat = torch.empty(self.slots * stride // item, dtype=dtype, device=device)
+    inner = torch.empty(shape, dtype=dtype, device="meta").stride()
+    return flat.as_strided((self.slots,) + shape, (stride // item,) + tuple(inner))
+
+  def take(self, name: str, shape, dtype, offset: int, device):
+    """The slice of leaf `name` for a member whose engine wants `shape` ([n, ...]) at world
+    `offset`."""
+    n, world_shape = int(shape[0]), tuple(shape[1:])
+    leaf = self.leaves.get(name)
+    if leaf is None:
+      leaf = self.leaves[name] = self._allocate(name, world_shape, dtype, device)
+    have = tuple(leaf.shape[2:] if self.slots else leaf.shape[1:])
+    if have != world_shape or leaf.dtype != dtype:
+      raise ValueError(f"leaf {name!r}: one member's engine writes {world_shape} {dtype}, another's "
+                       f"{have} {leaf.dtype}")
+    return leaf[:, offset:offset + n] if self.slots else leaf[offset:offset + n]
+
+
+class MixtureSubstrate:
+  """Several substrates of one level — layouts, maps, payoffs — stepped as ONE batched
+  `Substrate` of N = sum(n_i) worlds (`build_mixture`).
+
+  Member i owns worlds [off_i, off_i + n_i) (`member_slice(i)`, `member_of_world`); its engine
+  writes straight into that slice of every leaf, so the leaves are [N, P, ...] / [N, ...]
+  tensors (and, with `rollout_length=T`, slots of [T, N, ...] rings) that nothing copies or
+  concatenates.  A step is each member's own step launch on the current stream, in member order.
+  Mixture world g is world g - off_i of member i, created with world_offset + off_i: it is the
+  world a one-world `Substrate` of that member built with `world_offset=g` (same env_seed) runs."""
+
+  def __init__(self, members: Sequence[Substrate], names: Sequence[str], offsets: Sequence[int],
+               counts: Sequence[int], leaves: _SharedLeaves, check_device_actions: bool):
+    self._members = tuple(members)
+    self._names = tuple(names)
+    self._offsets = tuple(int(o) for o in offsets)
+    self._counts = tuple(int(n) for n in counts)
+    self._shared = leaves
+    self._N = sum(self._counts)
+    self._T = leaves.slots
+    self._check_device_actions = bool(check_device_actions)
+    self._submissions = 0
+    first = self._members[0]
+    self._P = first.num_players
+    self._obs = {n: leaves.leaves[n] for n in first._obs}
+    self._reward = leaves.leaves["#reward"]
+    self._discount = leaves.leaves["#discount"]
+    self._step_type = leaves.leaves["#step_type"]
+    t = first._eng._torch
+    self._member_of_world = t.repeat_interleave(
+        t.arange(len(self._members), dtype=t.int32),
+        t.tensor(self._counts, dtype=t.int64)).to(first._eng.device)
+    self._closed = False
+    self._observables = SubstrateObservables(Subject(), Subject(), Subject(), Subject())
+
+  # -- the mixture -----------------------------------------------------------
+  @property
+  def members(self) -> Tuple[str, ...]:
+    """The members' substrate names, in world order."""
+    return self._names
+
+  @property
+  def member_of_world(self):
+    """int32 [N] device tensor: the member index of every world."""
+    return self._member_of_world
+
+  def member_slice(self, i: int) -> slice:
+    """Worlds [off_i, off_i + n_i) of member i, as a slice of the leading world axis."""
+    return slice(self._offsets[i], self._offsets[i] + self._counts[i])
+
+  @property
+  def engines(self) -> Tuple[engine_lib.Engine, ...]:
+    return tuple(m.engine for m in self._members)
+
+  def counters(self) -> Dict[str, int]:
+    """mp_counters summed over the members."""
+    out: Dict[str, int] = {}
+    for m in self._members:
+      for k, v in m.engine.counters().items():
+        out[k] = out.get(k, 0) + v
+    return out
+
+  # -- the batched Substrate surface ----------------------------------------
+  @property
+  def num_worlds(self) -> int:
+    return self._N
+
+  @property
+  def num_players(self) -> int:
+    return self._P
+
+  @property
+  def rollout(self) -> Optional[Dict[str, Any]]:
+    """As `Substrate.rollout`: the [T, N, ...] rings of all members, None without a ring."""
+    if not self._T:
+      return None
+    return {"step_type": self._step_type, "reward": self._reward,
+            "discount": self._discount, "observation": dict(self._obs)}
+
+  @property
+  def slot(self) -> int:
+    """As `Substrate.slot` (every submission goes to every member: their rings move together)."""
+    return self._members[0].slot if self._T else -1
+
+  def reset(self) -> TimeStep:
+    for m in self._members:
+      m._eng.use_current_stream()
+      m._eng.reset()
+      m._submissions += 1
+    self._submissions += 1
+    return self._emit(self._timestep())
+
+  def observation(self):
+    return self._timestep().observation
+
+  def step(self, action) -> TimeStep:
+    """`action`: int [N, P], a device tensor (member i gets rows [off_i, off_i + n_i), a view)
+    or a host array."""
+    t = self._members[0]._eng._torch
+    if isinstance(action, t.Tensor) and action.is_cuda:
+      a = action.to(t.int32).contiguous()
+      if tuple(a.shape) != (self._N, self._P):
+        raise ValueError(f"actions must have shape {(self._N, self._P)}, got {tuple(a.shape)}")
+      if self._check_device_actions:
+        K = self.action_spec()[0].num_values
+        if bool(((a < 0) | (a >= K)).any()):
+          raise ValueError(f"actions must be in [0, {K})")
+    else:
+      a = np.asarray(action)
+      if a.shape != (self._N, self._P):
+        raise ValueError(f"actions must have shape {(self._N, self._P)}, got {a.shape}")
+    self._observables.action.on_next(action)
+    for m, off, n in zip(self._members, self._offsets, self._counts):
+      m._eng.use_current_stream()
+      m._submit(a[off:off + n])
+    self._submissions += 1
+    return self._emit(self._timestep())
+
+  def _member_at(self, world: int):
+    if not 0 <= world < self._N:
+      raise IndexError(f"world {world} outside [0, {self._N})")
+    i = int(np.searchsorted(self._offsets, world, side="right")) - 1
+    return self._members[i], world - self._offsets[i]
+
+  def events(self, world: int = 0):
+    """`Substrate.events` of mixture world `world`."""
+    m, w = self._member_at(int(world))
+    return m.events(w)
+
+  def observables(self) -> SubstrateObservables:
+    """As `Substrate.observables`; `events_batched` emits (mixture world, (name, payload))."""
+    return self._observables
+
+  def _emit(self, timestep: TimeStep) -> TimeStep:
+    self._observables.timestep.on_next(timestep)
+    batched = self._observables.events_batched
+    if batched._observers:
+      for m, off in zip(self._members, self._offsets):
+        for w, events in enumerate(m.engine.events_all()):
+          for event in events:
+            batched.on_next((off + w, event))
+    if self._observables.events._observers:
+      for event in self.events(0):
+        self._observables.events.on_next(event)
+    return timestep
+
+  def observation_spec(self) -> List[Mapping[str, Array]]:
+    return self._members[0].observation_spec()
+
+  def action_spec(self) -> List[DiscreteArray]:
+    return self._members[0].action_spec()
+
+  def reward_spec(self) -> List[Array]:
+    return self._members[0].reward_spec()
+
+  def discount_spec(self) -> BoundedArray:
+    return self._members[0].discount_spec()
+
+  def close(self):
+    if not self._closed:
+      self._closed = True
+      for m in self._members:
+        m.close()
+      self._shared.leaves.clear()
+      for subject in (self._observables.action, self._observables.timestep,
+                      self._observables.events, self._observables.events_batched):
+        subject.on_completed()
+
+  def __enter__(self):
+    return self
+
+  def __exit__(self, *exc):
+    self.close()
+
+  def _timestep(self) -> TimeStep:
+    if self._T:
+      s = self.slot if self._submissions else 0
+      ts = RolloutTimeStep(self._step_type[s], self._reward[s], self._discount[s],
+                           {n: v[s] for n, v in self._obs.items()})
+      ts.slot = s
+      return ts
+    return TimeStep(self._step_type, self._reward, self._discount, dict(self._obs))
+
+
+_MIXTURE_KWARGS = frozenset({"env_seed", "auto_reset", "debug_observations", "action_table",
+                             "rollout_length", "rgb_pool", "world_rgb_pool",
+                             "check_device_actions", "device"})
+
+
+def build_mixture(names: Sequence[str], *, roles: Optional[Sequence[str]] = None,
+                  num_worlds, world_offset: int = 0,
+                  individual_observations: Optional[Sequence[str]] = None,
+                  global_observations: Optional[Sequence[str]] = None,
+                  **substrate_kwargs) -> MixtureSubstrate:
+  """Several registered substrates of one level as one batched substrate (`MixtureSubstrate`).
+
+  `names`: the members, in world order.  `roles`: one role per player, valid for every member
+  (default: each member's default roles — they must be as many).  `num_worlds`: one count per
+  member, or a total split as evenly as possible; counts are rounded UP to the world granule
+  (`world_granule`: the member offsets must keep the pooled views 16-byte aligned — 1 for full
+  views, up to 16 with `rgb_pool` / `world_rgb_pool`; `split_worlds`).  `world_offset`: mixture
+  world g is seeded as global world world_offset + g.  `individual_observations` /
+  `global_observations` narrow the stock observation names as in `build_substrate`.  Further
+  keyword arguments are a batched `Substrate`'s: env_seed, auto_reset, debug_observations,
+  action_table, rollout_length, rgb_pool, world_rgb_pool, check_device_actions, device.
+
+  The members must agree, as their configs and specs say, on the number of players, the
+  number of discrete actions and the shape and dtype of every leaf: ValueError otherwise,
+  naming the leaf and the members."""
+  unknown = set(substrate_kwargs) - _MIXTURE_KWARGS
+  if unknown:
+    raise TypeError(f"build_mixture got unexpected keyword arguments {sorted(unknown)} "
+                    f"(it takes {sorted(_MIXTURE_KWARGS)})")
+  names = [str(n) for n in names]
+  if not names:
+    raise ValueError("a mixture needs at least one substrate name")
+  for n in names:
+    if n not in SUBSTRATES:
+      raise ValueError(f"{n} not in {sorted(SUBSTRATES)} (substrates with a HIP engine in this build).")
+  kw = dict(substrate_kwargs)
+  rgb_pool = _check_pool_factor("rgb_pool", kw.get("rgb_pool", 1))
+  world_rgb_pool = _check_pool_factor("world_rgb_pool", kw.get("world_rgb_pool", 1))
+  packs = {n: engine_lib.load_pack(n) for n in set(names)}
+
+  # the members' configs, narrowed like build_substrate's
+  configs = []
+  for n in names:
+    c = get_config(n)
+    if individual_observations is not None or global_observations is not None:
+      ind, glob, spec = select_observations(
+          c, packs[n],
+          c.individual_observation_names if individual_observations is None else individual_observations,
+          c.global_observation_names if global_observations is None else global_observations)
+      c = SubstrateConfig(name=c.name, action_set=c.action_set, individual_observation_names=ind,
+                          global_observation_names=glob, timestep_spec=spec,
+                          valid_roles=c.valid_roles, default_player_roles=c.default_player_roles,
+                          aux0_name=c.aux0_name, per_role_constants=c.per_role_constants)
+    configs.append(c)
+
+  # compatibility, from the configs and specs
+  member_roles = [tuple(roles) if roles is not None else c.default_player_roles for c in configs]
+  players = {n: len(r) for n, r in zip(names, member_roles)}
+  if len(set(players.values())) > 1:
+    raise ValueError(f"the members of a mixture must have the same number of players: {players}")
+  for n, c, r in zip(names, configs, member_roles):
+    invalid = set(r) - c.valid_roles
+    if invalid:
+      raise ValueError(f"Invalid roles for {n}: {invalid!r}. Must be one of {c.valid_roles!r}")
+  if "action_table" not in kw:
+    actions = {n: c.action_spec.num_values for n, c in zip(names, configs)}
+    if len(set(actions.values())) > 1:
+      raise ValueError(f"the members of a mixture must have the same action_spec(): {actions} "
+                       "discrete actions (a common action_table=... gives them one)")
+  specs = {n: observation_spec_of(c, packs[n], rgb_pool, world_rgb_pool)
+           for n, c in zip(names, configs)}
+  differ = {}
+  for leaf in sorted(set().union(*specs.values())):
+    seen = {n: (tuple(s[leaf].shape), str(s[leaf].dtype)) if leaf in s else None
+            for n, s in specs.items()}
+    if len(set(seen.values())) > 1:
+      differ[leaf] = seen
+  if differ:
+    individual = sorted(l for l in differ if any(l in c.individual_observation_names for c in configs))
+    drop = ([f"individual_observations=[...] without {individual}"] if individual else []) + (
+        ["global_observations=()"] if set(differ) - set(individual) - {"COLLECTIVE_REWARD"} else [])
+    raise ValueError(
+        "the members of a mixture must have the same leaves; " + "; ".join(
+            f"leaf {leaf!r} differs: " + ", ".join(
+                f"{n} {'has none' if v is None else f'{v[0]} {v[1]}'}" for n, v in seen.items())
+            for leaf, seen in differ.items()) +
+        f". Drop it with {' and '.join(drop)} (as in build_substrate)")
+
+  P = len(member_roles[0])
+  granule = max(world_granule(leaf_bytes_per_world(c, packs[n], P, rgb_pool, world_rgb_pool))
+                for n, c in zip(names, configs))
+  # (every member has the same leaves and bytes per world: one granule fits all)
+  counts = split_worlds(num_worlds, len(names), granule)
+  total = sum(counts)
+  if total < 2:
+    raise ValueError("a mixture is batched (device tensors): it needs at least two worlds; "
+                     "build a one-world Substrate with substrate.build(...)")
+  offsets = [int(v) for v in np.cumsum([0] + counts[:-1])]
+  T = int(kw.get("rollout_length", 0) or 0)
+  if T < 0:
+    raise ValueError("rollout_length must not be negative")
+  kw["env_seed"] = resolve_env_seed(kw.get("env_seed"))   # (one seed for every member)
+  check = bool(kw.pop("check_device_actions", False))
+  shared = _SharedLeaves(total, T)
+  members = []
+  try:
+    for n, c, r, off, cnt in zip(names, configs, member_roles, offsets, counts):
+      m = Substrate(c, r, packs[n], num_worlds=cnt, batched=True,
+                    world_offset=int(world_offset) + off,
+                    _leaves=(lambda leaf, shape, dtype, device, off=off:
+                             shared.take(leaf, shape, dtype, off, device)),
+                    **kw)
+      members.append(m)
+      # the launch plan that suits the slices this engine writes (after all of them are bound)
+      if hasattr(m.engine, "tune") and any(k in _PIXEL_LEAVES for k in m._obs):
+        m.engine.tune()
+  except BaseException:
+    for m in members:
+      m.close()
+    raise
+  return MixtureSubstrate(members, names, offsets, counts, shared, check)
