@@ -423,6 +423,70 @@ uint64_t mp_snapshot_bytes(const MpEngine* eng);
 int mp_snapshot(MpEngine* eng, void* host_buf, uint64_t bytes);
 int mp_restore(MpEngine* eng, const void* host_buf, uint64_t bytes);
 
+/* World states as device data: save chosen worlds' records into rows of a caller-owned device
+ * buffer, and start any worlds from such rows — forks, rewinds, restarts from states of
+ * interest, the same world replayed many times.  A row is a world's whole record
+ * (MpInfo.world_state_bytes = S bytes): its grid, avatars, timers, seed, episode and step.  Every
+ * random draw is keyed by the record's own seed and counted by its episode and step, so a loaded
+ * world continues exactly as the world it was saved from would under the same actions —
+ * auto-resets included (episode e + 1 of the source's seed).
+ *
+ * The library's exported entry points do not grow: these operations go through the two state
+ * entry points above, as a request.  A call of mp_snapshot or mp_restore whose `bytes` is
+ * sizeof(MpWorldStates) (no engine's snapshot is that small) takes `host_buf` as a HOST
+ * MpWorldStates with struct_size = sizeof(MpWorldStates); every other call is what it always
+ * was.  A request is enqueued on the engine's stream and does not synchronise.
+ * include/mp_world_states.h wraps the three operations as inline C functions
+ * (state fingerprint, save worlds, load worlds).
+ *
+ * MP_STATES_FINGERPRINT (mp_snapshot): `fingerprint` := a 64-bit hash of everything that decides a
+ * record's layout and meaning (the pack with its roles applied, the player count, the record's
+ * geometry with MpDevOptions.record_pad, the library's record layout).  Rows load only into an
+ * engine with the same fingerprint — any N, any world_offset, another instance.
+ *
+ * MP_STATES_SAVE (mp_snapshot): row i of `bank` (device uint8 [count][S], bank_bytes >= count * S)
+ * = the record of world worlds[i] (device int32 [count]; NULL = every world, count = N);
+ * `fingerprint` := the engine's.  MP_ERR_INVALID, before any launch: NULL / non-positive
+ * arguments, bank_bytes < count * S, a buffer that is not device memory of the engine's device
+ * or whose [ptr, ptr + count * S) is not inside one allocation, an engine that has never been
+ * reset (mp_reset, mp_restore or a load).  A world index outside [0, N) is never read: its row is
+ * left as it was and the next synchronising call returns MP_ERR_INVALID.
+ *
+ * MP_STATES_LOAD (mp_restore): ONE launch shaped like a masked mp_reset.  src (device int32 [N]):
+ * src[w] = r >= 0 starts world w from row r of `bank` (device uint8 [bank_rows][S]); -1 leaves
+ * world w as a masked reset leaves a world outside its mask.  Several worlds may take one row.
+ * `fingerprint`: the rows' (MP_STATES_SAVE's).  Every bound view (RGB, RGB_POOL*, WORLD.RGB,
+ * LAYER) is drawn by the launch, and it writes the rollout ring's next slot like any
+ * submission.  A loaded world keeps its OWN cumulative counters (WorldTail::ctr and reward_fx,
+ * which only feed mp_counters): mp_counters goes on counting the work this engine did.  What
+ * the launch writes for a loaded world:
+ *   (A) functions of the record, equal to what the source's last launch wrote:
+ *       MP_OBS_RGB, MP_OBS_RGB_POOL2/4/8, MP_OBS_WORLD_RGB, MP_OBS_LAYER, MP_OBS_READY_TO_SHOOT,
+ *       MP_OBS_POSITION, MP_OBS_ORIENTATION, MP_OBS_INVENTORY;
+ *   (B) transition kinds, as a reset writes them (STEP_TYPE = FIRST): MP_OBS_REWARD,
+ *       MP_OBS_COLLECTIVE_REWARD, MP_OBS_STEP_TYPE, MP_OBS_DISCOUNT, MP_OBS_EVENTS, MP_OBS_AUX0,
+ *       MP_OBS_AUX1..4, MP_OBS_ZAP_MATRIX, MP_OBS_INTERACTION_INVENTORIES,
+ *       MP_OBS_MATRIX_CUMULANTS, MP_OBS_INTERACTION_REWARDS (which a reset leaves as it was).
+ *   A row saved from a finished world loads finished: STEP_TYPE LAST, discount 0, reward 0,
+ *   no events (what a frozen world reports); its next mp_step auto-resets it or leaves it
+ *   frozen.  MP_ERR_INVALID, before any launch: NULL arguments, bank_rows <= 0, a fingerprint
+ *   that is not this engine's, a bank or src that is not device memory of the engine's device
+ *   or that does not lie inside one allocation.  An src[w] that is neither -1 nor a row is never
+ *   read: world w is left as it was and the next synchronising call returns MP_ERR_INVALID.
+ *   (The reference has no equivalent: SURVEY.md §5 "checkpoint / resume".) */
+enum { MP_STATES_FINGERPRINT = 1, MP_STATES_SAVE = 2, MP_STATES_LOAD = 3 };
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(MpWorldStates) */
+  int32_t op;              /* MP_STATES_* */
+  uint64_t fingerprint;    /* LOAD: the rows' (in); FINGERPRINT, SAVE: the engine's (out) */
+  const int32_t* worlds;   /* SAVE: device int32 [count], NULL = every world */
+  const int32_t* src;      /* LOAD: device int32 [N] */
+  void* bank;              /* SAVE: written; LOAD: read — device uint8 [rows][S] */
+  uint64_t bank_bytes;     /* SAVE: bytes of `bank` */
+  int32_t count;           /* SAVE: rows to write */
+  int32_t bank_rows;       /* LOAD: rows of `bank` */
+} MpWorldStates;
+
 /* Throughput / event counters accumulated on device since creation
  * (synchronises).  These are what the multi-GPU bench all-reduces. */
 enum {

@@ -18,6 +18,7 @@
 #include "step_cook.h"
 #include "step_matrix.h"
 #include "step_territory.h"
+#include "step_load.h"
 
 // Cache policy of the observation stores (gfx950 sc0 / sc1 / nt bits), per
 // instantiation (kNt).  The FUSED launch stores its pixels non-temporal: its
@@ -980,7 +981,7 @@ __global__ __launch_bounds__(max_threads<Tables>()) void k_frame(DevTables t, Ta
             stepk::begin_step(wd.sc, lane_w);
             stepk::wsync();
             const stepk::Action act = stepk::lookup_action(t, wd, act_id, args.mode);
-            stepk::step_world(t, c, sites, wd, act, args);
+            stepk::step_or_load(t, c, sites, wd, act, args);   // (mp_load_worlds: step_load.h)
             // "N.LAYER", when bound: by this feeder from the slot's record, which finish() has
             // already published — the renderers draw it meanwhile, and only this feeder refills
             // the slot (profiles/r09_layer_obs.md)

@@ -436,8 +436,21 @@ __host__ __device__ inline uint32_t philox_bounded(Philox4 o, uint32_t n) {
 }
 
 // STEP: `actions` are ids into ACTION_SET [N][P]; FIELDS: raw action fields
-// [N][P][nfields] in actionOrder (mp_step_fields)
-enum { STEP_MODE_STEP = 0, STEP_MODE_RESET = 1, STEP_MODE_FIELDS = 2 };
+// [N][P][nfields] in actionOrder (mp_step_fields); LOAD: world w takes the record of row
+// StepArgs::src[w] of StepArgs::bank (mp_load_worlds, stepk::load_world).  The odd modes
+// read no actions.
+enum { STEP_MODE_STEP = 0, STEP_MODE_RESET = 1, STEP_MODE_FIELDS = 2, STEP_MODE_LOAD = 3 };
+
+// Version of the record layout above (WorldTail, the grid planes, what each level keeps in its
+// hidden planes and tail bytes): a term of mp_state_fingerprint, so rows saved by a library with
+// another layout are refused.  Bump it with any change to what a record holds or means.
+#define MP_RECORD_LAYOUT_VERSION 1u
+
+// DevTables::fault words of the world-state entry points (mp_save_worlds / mp_load_worlds): an
+// index outside its range that a launch skipped — word 9 = world (or row) + 1, word 10 = the
+// index, word 11 = 1 for a load's src[], 2 for a save's world list.  The next synchronising call
+// reports it (MP_ERR_INVALID) and clears it.
+enum { FAULT_STATE_INDEX = 9 };
 
 
 #endif  // MP_COMMON_H_

@@ -159,6 +159,8 @@ struct MpEngine {
   int next_orders = 1;             // StepArgs::next_orders (MpDevOptions.no_next_orders turns it off)
   bool has_dev = false;            // MpConfig.dev given: the plans are the caller's, mp_tune keeps them
   bool touched = false;            // reset / stepped / restored since creation (mp_tune: may it really step?)
+  bool has_state = false;          // reset, restored or loaded since creation (MP_STATES_SAVE)
+  uint64_t fingerprint = 0;        // MP_STATES_FINGERPRINT: what a record's layout and meaning depend on
   int unfused = 0;                 // MpConfig.unfused: 0 the engine's choice, 1 two launches, 2 one
   // The engine's choice (MpConfig.unfused = 0): one launch, always.  (Round 2 drew
   // views under 64 KB a world — the two-player games — in a second launch: a CU
@@ -275,6 +277,44 @@ __global__ void k_sum_counters(const uint8_t* state, int stride, int grid_pad, i
   }
 }
 
+// MP_STATES_SAVE: row i of `dst` = the record of world worlds[i] (NULL: world i), one wave per row,
+// in 16-byte lines with eight lines of a lane in flight.  A world index outside [0, n) is reported
+// through the fault words and its row left as it was.
+__global__ __launch_bounds__(256) void k_save_worlds(DevTables t, const uint8_t* __restrict__ state, int n,
+                                                     const int32_t* __restrict__ worlds, int count,
+                                                     uint8_t* __restrict__ dst) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  if (row >= count) return;
+  const int w = worlds ? __builtin_amdgcn_readfirstlane(worlds[row]) : row;
+  if (w < 0 || w >= n) {
+    if (lane == 0) {   // (the words of step_load.h: report_state_index)
+      t.fault[FAULT_STATE_INDEX + 1] = (uint32_t)w;
+      t.fault[FAULT_STATE_INDEX + 2] = 2u;
+      t.fault[FAULT_STATE_INDEX] = (uint32_t)row + 1u;
+    }
+    return;
+  }
+  const int nvec = t.world_stride >> 4;
+  const uint4* src = reinterpret_cast<const uint4*>(state + (size_t)w * t.world_stride);
+  uint4* out = reinterpret_cast<uint4*>(dst + (size_t)row * t.world_stride);
+  for (int i0 = 0; i0 < nvec; i0 += 8 * 64) {
+    uint4 v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int i = i0 + k * 64 + lane;
+      v[k] = src[i < nvec ? i : nvec - 1];
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) stepk::issued(v[k]);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int i = i0 + k * 64 + lane;
+      if (i < nvec) out[i] = v[k];
+    }
+  }
+}
+
 // Waits for the engine's stream and reports a frame kernel that gave up on its
 // pipeline (frame.hip: report_stall) — an engine bug, surfaced instead of hung on.
 int sync_and_check(MpEngine* e, const char* who) {
@@ -293,6 +333,17 @@ int sync_and_check(MpEngine* e, const char* who) {
                 "(the reference asserts there, the_matrix/components.lua:282-290); the indicator "
                 "shows the first colour", who, world);
   }
+  if (f[FAULT_STATE_INDEX] != 0) {
+    const uint32_t at = f[FAULT_STATE_INDEX] - 1, index = f[FAULT_STATE_INDEX + 1];
+    const bool load = f[FAULT_STATE_INDEX + 2] == 1;
+    e->h_fault[FAULT_STATE_INDEX] = 0;   // reported once; the engine stays usable
+    return load ? fail(MP_ERR_INVALID,
+                       "%s: MP_STATES_LOAD: src[%u] = %d is neither -1 nor a row of the bank; world %u "
+                       "was left as it was", who, at, (int)index, at)
+                : fail(MP_ERR_INVALID,
+                       "%s: MP_STATES_SAVE: worlds[%u] = %d is not a world of this engine; row %u was "
+                       "left as it was", who, at, (int)index, at);
+  }
   return MP_OK;
 }
 
@@ -306,9 +357,11 @@ void draw(MpEngine* e, uint8_t* rgb, uint8_t* wrgb, int pool_k = 1) {
   launch_frame(e->t, nullptr, args, rgb, wrgb, p, e->stream, rgb ? pool_k : 1, e->world_pool);
 }
 
-int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask) {
+int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
+           const uint8_t* bank = nullptr, const int32_t* src = nullptr, int bank_rows = 0) {
   stepk::StepArgs args;
   args.state = e->d_state; args.actions = actions; args.reset_mask = mask;
+  args.bank = bank; args.src = src; args.bank_rows = bank_rows;
   args.mode = mode; args.auto_reset = e->auto_reset; args.num_worlds = e->N;
   args.next_orders = e->next_orders;
   // the rollout ring: this submission's slot (a pointer store per ring-bound kind)
@@ -342,6 +395,10 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask) {
 void retired_va(int64_t* bytes, int64_t* limit);   // (mapped views, below)
 bool in_mapped_view(const void* p);
 
+// A bank of world-state rows (MP_STATES_SAVE / MP_STATES_LOAD): device memory of the engine's
+// device, [ptr, ptr + bytes) inside one allocation.
+int check_bank(MpEngine* e, const void* ptr, uint64_t bytes, const char* who);
+
 // A bound buffer is written by every launch from then on: a pointer the device cannot
 // write (a host array, a stale tensor) would fault the GPU in the middle of a step — it is
 // refused here instead.  Memory this library mapped itself is known by range (the runtime's
@@ -368,6 +425,31 @@ int check_device_pointer(MpEngine* e, const void* ptr, const char* who) {
   if ((attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeArray) && attr.device != e->device)
     return fail(MP_ERR_INVALID, "%s: %p lives on device %d, the engine on device %d", who, ptr,
                 attr.device, e->device);
+  return MP_OK;
+}
+
+int check_bank(MpEngine* e, const void* ptr, uint64_t bytes, const char* who) {
+  if (int rc = check_device_pointer(e, ptr, who)) return rc;
+  if (in_mapped_view(ptr)) {
+    if (!in_mapped_view((const char*)ptr + bytes - 1))
+      return fail(MP_ERR_INVALID, "%s: [%p, +%llu bytes) leaves the mapped view it starts in", who, ptr,
+                  (unsigned long long)bytes);
+    return MP_OK;
+  }
+  hipPointerAttribute_t attr = {};
+  const hipError_t rc = hipPointerGetAttributes(&attr, ptr);
+  (void)hipGetLastError();
+  if (rc == hipSuccess && attr.type == hipMemoryTypeHost)
+    return fail(MP_ERR_INVALID, "%s: %p is host memory; world states live in device memory", who, ptr);
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)ptr) != hipSuccess || !base) {
+    (void)hipGetLastError();
+    return fail(MP_ERR_INVALID, "%s: %p is not in a device allocation the runtime knows", who, ptr);
+  }
+  if ((uint64_t)((const char*)ptr - (const char*)base) + bytes > (uint64_t)size)
+    return fail(MP_ERR_INVALID, "%s: [%p, +%llu bytes) runs past the end of its allocation (%p, %zu bytes)",
+                who, ptr, (unsigned long long)bytes, base, size);
   return MP_OK;
 }
 
@@ -400,6 +482,23 @@ void drop_ring_kind(MpEngine* e, int kind) {
   bool any = false;
   for (int k = 0; k < MP_OBS_KINDS; ++k) any = any || e->ring[k].base;
   if (!any) { e->ring_slots = 0; e->ring_cursor = 0; }
+}
+
+// MP_STATES_FINGERPRINT: FNV-1a over what decides a record's layout and meaning — the pack as the
+// engine runs it (roles applied), the player count, the record's geometry (grid_pad, world_stride:
+// MpDevOptions.record_pad included) and MP_RECORD_LAYOUT_VERSION.
+uint64_t state_fingerprint(const std::vector<uint8_t>& pack, const DevTables& t) {
+  uint64_t h = 0xcbf29ce484222325ull;
+  auto mix = [&](const void* p, size_t n) {
+    for (size_t i = 0; i < n; ++i) { h ^= ((const uint8_t*)p)[i]; h *= 0x100000001b3ull; }
+  };
+  const uint32_t words[4] = {MP_RECORD_LAYOUT_VERSION, (uint32_t)t.P, (uint32_t)t.grid_pad,
+                             (uint32_t)t.world_stride};
+  mix(words, sizeof(words));
+  const uint64_t n = pack.size();
+  mix(&n, sizeof(n));
+  mix(pack.data(), pack.size());
+  return h;
 }
 
 // ---- mp_create's device stage: runs on a pack decode_pack has accepted
@@ -943,6 +1042,7 @@ int mp_create(const void* pack, uint64_t pack_len, const MpConfig* cfg,
     mp_destroy(e);
     return rc;
   }
+  e->fingerprint = state_fingerprint(e->pack, e->t);
   *out = e;
   return MP_OK;
 }
@@ -1073,6 +1173,7 @@ int mp_bind_output_ring(MpEngine* e, MpObsKind kind, void* base, uint64_t slot_s
 int mp_reset(MpEngine* e, const uint64_t* seeds, const uint8_t* mask) {
   if (!e) return fail(MP_ERR_INVALID, "mp_reset: NULL engine");
   e->touched = true;
+  e->has_state = true;
   HIP_TRY(hipSetDevice(e->device));
   const uint8_t* dmask = nullptr;
   if (mask) {
@@ -1315,11 +1416,36 @@ int mp_dump(MpEngine* e, uint8_t* grid, int32_t* avat, int32_t* glob) {
   return MP_OK;
 }
 
+// An MpWorldStates request (include/mp_engine.h): what mp_snapshot / mp_restore do when `bytes` is
+// sizeof(MpWorldStates) — no engine's snapshot is that small (a record is >= 448 bytes).
+static int save_worlds(MpEngine* e, const int32_t* worlds, int32_t count, void* dst, uint64_t dst_bytes);
+static int load_worlds(MpEngine* e, const void* bank, int32_t bank_rows, const int32_t* src,
+                       uint64_t fingerprint);
+static int world_states(MpEngine* e, MpWorldStates* r, bool restore) {
+  if (r->struct_size != sizeof(MpWorldStates))
+    return fail(MP_ERR_INVALID, "MpWorldStates: struct_size %u, expected %zu", r->struct_size,
+                sizeof(MpWorldStates));
+  if (restore != (r->op == MP_STATES_LOAD))
+    return fail(MP_ERR_INVALID, "MpWorldStates: op %d goes to %s", r->op,
+                r->op == MP_STATES_LOAD ? "mp_restore" : "mp_snapshot");
+  switch (r->op) {
+    case MP_STATES_FINGERPRINT: r->fingerprint = e->fingerprint; return MP_OK;
+    case MP_STATES_SAVE: {
+      const int rc = save_worlds(e, r->worlds, r->count, r->bank, r->bank_bytes);
+      if (rc == MP_OK) r->fingerprint = e->fingerprint;
+      return rc;
+    }
+    case MP_STATES_LOAD: return load_worlds(e, r->bank, r->bank_rows, r->src, r->fingerprint);
+    default: return fail(MP_ERR_INVALID, "MpWorldStates: unknown op %d", r->op);
+  }
+}
+
 uint64_t mp_snapshot_bytes(const MpEngine* e) {
   return e ? (uint64_t)e->N * e->t.world_stride : 0;
 }
 
 int mp_snapshot(MpEngine* e, void* buf, uint64_t bytes) {
+  if (e && buf && bytes == sizeof(MpWorldStates)) return world_states(e, (MpWorldStates*)buf, false);
   if (!e || !buf || bytes != mp_snapshot_bytes(e))
     return fail(MP_ERR_INVALID, "mp_snapshot: bad buffer");
   HIP_TRY(hipSetDevice(e->device));
@@ -1329,13 +1455,58 @@ int mp_snapshot(MpEngine* e, void* buf, uint64_t bytes) {
 }
 
 int mp_restore(MpEngine* e, const void* buf, uint64_t bytes) {
+  if (e && buf && bytes == sizeof(MpWorldStates)) {
+    MpWorldStates r;   // (read only: a load writes nothing back)
+    memcpy(&r, buf, sizeof r);
+    return world_states(e, &r, true);
+  }
   if (!e || !buf || bytes != mp_snapshot_bytes(e))
     return fail(MP_ERR_INVALID, "mp_restore: bad buffer");
   HIP_TRY(hipSetDevice(e->device));
   e->touched = true;
+  e->has_state = true;
   if (int rc = sync_and_check(e, "mp_restore")) return rc;
   HIP_TRY(hipMemcpy(e->d_state, buf, bytes, hipMemcpyHostToDevice));
   return MP_OK;
+}
+
+static int save_worlds(MpEngine* e, const int32_t* worlds, int32_t count, void* dst, uint64_t dst_bytes) {
+  if (!e || !dst || count <= 0)
+    return fail(MP_ERR_INVALID, "MP_STATES_SAVE: NULL engine or buffer, or no rows");
+  if (!worlds && count != e->N)
+    return fail(MP_ERR_INVALID, "MP_STATES_SAVE: without a world list every world is saved (count %d, "
+                "the engine has %d)", count, e->N);
+  const uint64_t stride = (uint64_t)e->t.world_stride, bytes = (uint64_t)count * stride;
+  if (dst_bytes < bytes)
+    return fail(MP_ERR_INVALID, "MP_STATES_SAVE: %d rows of %llu bytes need %llu bytes, the buffer has %llu",
+                count, (unsigned long long)stride, (unsigned long long)bytes, (unsigned long long)dst_bytes);
+  if (!e->has_state)
+    return fail(MP_ERR_INVALID, "MP_STATES_SAVE: the engine has never been reset; there is no state to save");
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = check_bank(e, dst, bytes, "MP_STATES_SAVE")) return rc;
+  if (worlds)
+    if (int rc = check_bank(e, worlds, (uint64_t)count * 4, "MP_STATES_SAVE (world list)")) return rc;
+  hipLaunchKernelGGL(k_save_worlds, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream, e->t,
+                     (const uint8_t*)e->d_state, e->N, worlds, (int)count, (uint8_t*)dst);
+  HIP_TRY(hipGetLastError());
+  return MP_OK;
+}
+
+static int load_worlds(MpEngine* e, const void* bank, int32_t bank_rows, const int32_t* src,
+                       uint64_t fingerprint) {
+  if (!e || !bank || !src || bank_rows <= 0)
+    return fail(MP_ERR_INVALID, "MP_STATES_LOAD: NULL engine, bank or src, or an empty bank");
+  if (fingerprint != e->fingerprint)
+    return fail(MP_ERR_INVALID, "MP_STATES_LOAD: the rows' state fingerprint %016llx is not this engine's "
+                "(%016llx): they were saved by an engine of another pack, player count or record layout",
+                (unsigned long long)fingerprint, (unsigned long long)e->fingerprint);
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = check_bank(e, bank, (uint64_t)bank_rows * (uint64_t)e->t.world_stride, "MP_STATES_LOAD"))
+    return rc;
+  if (int rc = check_bank(e, src, (uint64_t)e->N * 4, "MP_STATES_LOAD (src)")) return rc;
+  e->touched = true;
+  e->has_state = true;
+  return submit(e, STEP_MODE_LOAD, nullptr, nullptr, (const uint8_t*)bank, src, bank_rows);
 }
 
 int mp_counters(MpEngine* e, uint64_t out[MP_CTR_COUNT]) {

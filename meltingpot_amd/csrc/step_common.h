@@ -190,7 +190,7 @@ struct Action { int move = 0, turn = 0, fire0 = 0, fire1 = 0, bad = 0; };
 constexpr int kFieldsTag = 0x40000000;
 __device__ inline int fetch_action_id(const DevTables& t, const int32_t* actions, int mode,
                                       int w, int lane) {
-  if (mode == STEP_MODE_RESET || lane >= t.P) return 0;
+  if ((mode & 1) || lane >= t.P) return 0;   // (RESET, LOAD: no actions)
   if (mode == STEP_MODE_FIELDS) {
     const int32_t* f = actions + ((size_t)w * t.P + lane) * t.nfields;
     int v[4];
@@ -210,7 +210,7 @@ __device__ inline int fetch_action_id(const DevTables& t, const int32_t* actions
 }
 __device__ inline Action lookup_action(const DevTables& t, const World& wd, int act, int mode) {
   Action r;
-  if (mode == STEP_MODE_RESET || wd.lane >= t.P) return r;
+  if ((mode & 1) || wd.lane >= t.P) return r;
   uint32_t row;
   if (mode == STEP_MODE_FIELDS) {
     if (act < 0) { r.bad = 1; return r; }
@@ -865,6 +865,11 @@ struct StepArgs {
   int mode, auto_reset, num_worlds;
   int next_orders;   // 1: finish() leaves the next step's shuffled orders in the record
   StepOutputs out;
+  // STEP_MODE_LOAD (mp_load_worlds): world w takes row src[w] of bank[bank_rows][world_stride]
+  // (-1: left alone, as a masked reset leaves the worlds outside its mask); step_load.h
+  const uint8_t* bank;
+  const int32_t* src;
+  int bank_rows;
 };
 
 // Substrates without LDS extras behind the marks (territory overloads both).

@@ -14,6 +14,7 @@
 #include "step_cook.h"
 #include "step_matrix.h"
 #include "step_territory.h"
+#include "step_load.h"
 
 namespace {
 
@@ -59,7 +60,7 @@ __device__ inline void run_one_world(const DevTables& t, const Tables& c, const 
 #endif
   const Action act = lookup_action(t, wd, act_id, args.mode);
   init_extra(t, c, wd.extra, lane);
-  step_world(t, c, sites, wd, act, args);
+  step_or_load(t, c, sites, wd, act, args);   // (mp_load_worlds: step_load.h)
   // "N.LAYER", when bound: from the record while it is in LDS (frozen and masked-out worlds
   // included: their record is the one in HBM)
   if (args.out.layer) {

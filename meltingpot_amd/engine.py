@@ -197,6 +197,29 @@ class MpBoxFill(ctypes.Structure):
               ("groups", ctypes.c_int32), ("waves", ctypes.c_int32), ("span_bytes", ctypes.c_uint32)]
 
 
+# World-state requests (include/mp_engine.h: MpWorldStates), carried by mp_snapshot / mp_restore
+MP_STATES_FINGERPRINT, MP_STATES_SAVE, MP_STATES_LOAD = 1, 2, 3
+
+
+class MpWorldStates(ctypes.Structure):
+  _fields_ = [("struct_size", ctypes.c_uint32), ("op", ctypes.c_int32),
+              ("fingerprint", ctypes.c_uint64), ("worlds", ctypes.c_void_p),
+              ("src", ctypes.c_void_p), ("bank", ctypes.c_void_p), ("bank_bytes", ctypes.c_uint64),
+              ("count", ctypes.c_int32), ("bank_rows", ctypes.c_int32)]
+
+
+def world_states_request(L, handle, op: int, **fields) -> MpWorldStates:
+  """Runs one MpWorldStates request on engine `handle` (MP_STATES_LOAD through mp_restore, the
+  others through mp_snapshot) and returns it (with its outputs); raises like every call."""
+  req = MpWorldStates(ctypes.sizeof(MpWorldStates), op)
+  for k, v in fields.items():
+    setattr(req, k, v)
+  call = L.mp_restore if op == MP_STATES_LOAD else L.mp_snapshot
+  _check(L, call(handle, ctypes.addressof(req), ctypes.sizeof(req)),
+         "mp_restore (MP_STATES_LOAD)" if op == MP_STATES_LOAD else "mp_snapshot (MpWorldStates)")
+  return req
+
+
 class EngineError(RuntimeError):
   pass
 
@@ -788,6 +811,66 @@ class Engine:
     buf = np.ascontiguousarray(buf, np.uint8)
     _check(self._L, self._L.mp_restore(self._h, buf.ctypes.data, buf.size),
            "mp_restore")
+
+  # -- world states (include/mp_engine.h: MpWorldStates requests) --
+  @property
+  def state_fingerprint(self) -> int:
+    """MP_STATES_FINGERPRINT: rows saved by this engine load into engines with the same value."""
+    return int(world_states_request(self._L, self._h, MP_STATES_FINGERPRINT).fingerprint)
+
+  def _device_ints(self, values, what: str):
+    """`values` as a contiguous int32 tensor on the engine's device."""
+    t = self._torch
+    if isinstance(values, t.Tensor):
+      if values.dtype not in (t.int8, t.int16, t.int32, t.int64, t.uint8):
+        raise ValueError(f"{what} must hold integers (got {values.dtype})")
+      return values.to(device=self.device, dtype=t.int32).contiguous().reshape(-1)
+    a = np.asarray(values)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+      raise ValueError(f"{what} must hold integers (got {a.dtype})")
+    return t.from_numpy(np.ascontiguousarray(a.reshape(-1), np.int32)).to(self.device)
+
+  def save_worlds(self, worlds=None, out=None):
+    """Row i of a uint8 [M, S] device tensor = the record of world worlds[i] (None: every world,
+    M = N); S = info.world_state_bytes.  `out`: the tensor to write (allocated when None).
+    Enqueued on the current stream; does not synchronise."""
+    t = self._torch
+    self.use_current_stream()
+    S = int(self.info.world_state_bytes)
+    w = None if worlds is None else self._device_ints(worlds, "worlds")
+    M = self.N if w is None else int(w.numel())
+    if M < 1:
+      raise ValueError("save_worlds: no worlds to save")
+    if out is None:
+      out = t.empty((M, S), dtype=t.uint8, device=self.device)
+    elif (not isinstance(out, t.Tensor) or out.dtype != t.uint8 or tuple(out.shape) != (M, S) or
+          not out.is_contiguous()):
+      raise ValueError(f"save_worlds: out must be a contiguous uint8 tensor of shape {(M, S)}")
+    world_states_request(self._L, self._h, MP_STATES_SAVE, worlds=None if w is None else w.data_ptr(),
+                         count=M, bank=out.data_ptr(), bank_bytes=out.numel())
+    self._state_args = w   # (kept until the next call: the launch may not have run yet)
+    return out
+
+  def load_worlds(self, bank, src, fingerprint: Optional[int] = None):
+    """World w starts from row src[w] of `bank` (uint8 [M, S] device tensor from save_worlds, of
+    this engine or another with the same state_fingerprint); src[w] = -1 leaves world w alone.
+    One launch, shaped like a masked reset: the bound views and ring slot are written by it.
+    `fingerprint`: the rows' (default: this engine's).  Enqueued on the current stream."""
+    t = self._torch
+    S = int(self.info.world_state_bytes)
+    if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
+        bank.shape[1] != S or not bank.is_contiguous()):
+      raise ValueError(f"load_worlds: bank must be a contiguous uint8 tensor [M, {S}]")
+    if bank.shape[0] < 1:
+      raise ValueError("load_worlds: the bank has no rows")
+    s = self._device_ints(src, "src")
+    if s.numel() != self.N:
+      raise ValueError(f"load_worlds: src must have {self.N} entries (got {s.numel()})")
+    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    self.use_current_stream()
+    world_states_request(self._L, self._h, MP_STATES_LOAD, bank=bank.data_ptr(),
+                         bank_rows=int(bank.shape[0]), src=s.data_ptr(), fingerprint=fp)
+    self._state_args = s
 
   def counters(self) -> Dict[str, int]:
     out = np.zeros(len(COUNTER_NAMES), np.uint64)

@@ -83,6 +83,57 @@ class RolloutTimeStep(TimeStep):
     return out
 
 
+class WorldStates:
+  """Saved worlds (`Substrate.save_state`): `data`, a uint8 [M, S] tensor on the engine's device
+  whose row i is one world's whole record, and `fingerprint`, the engine's state fingerprint
+  (MP_STATES_FINGERPRINT) — rows load into any substrate of the same level, player count and
+  roles (`Substrate.load_state`), of any num_worlds.  `states[idx]` selects rows (an int, a
+  slice, a sequence or an integer tensor) and is again a WorldStates."""
+
+  def __init__(self, data, fingerprint: int):
+    import torch
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8:
+      raise ValueError(f"WorldStates.data must be a uint8 tensor (got {getattr(data, 'dtype', type(data))})")
+    if data.dim() != 2 or data.shape[0] < 1 or data.shape[1] < 1:
+      raise ValueError(f"WorldStates.data must have shape [M, S] with M, S >= 1 (got {tuple(data.shape)})")
+    fingerprint = int(fingerprint)
+    if not 0 <= fingerprint < (1 << 64):
+      raise ValueError(f"a state fingerprint is a 64-bit unsigned value (got {fingerprint})")
+    self.data = data.contiguous()
+    self.fingerprint = fingerprint
+
+  def __len__(self) -> int:
+    return int(self.data.shape[0])
+
+  @property
+  def row_bytes(self) -> int:
+    return int(self.data.shape[1])
+
+  def __getitem__(self, idx) -> "WorldStates":
+    import torch
+    if isinstance(idx, (int, np.integer)):
+      rows = self.data[int(idx)].unsqueeze(0)
+    elif isinstance(idx, slice):
+      rows = self.data[idx]
+    else:
+      index = idx if isinstance(idx, torch.Tensor) else torch.as_tensor(np.asarray(idx, np.int64))
+      if index.dtype == torch.bool or index.dim() != 1:
+        raise ValueError("WorldStates rows are selected by an int, a slice or a 1-D list of ints")
+      rows = self.data[index.to(self.data.device, torch.int64)]
+    return WorldStates(rows, self.fingerprint)
+
+  def check(self, fingerprint: int, row_bytes: int):
+    """ValueError unless these rows were saved by an engine with this fingerprint and row size."""
+    if self.fingerprint != int(fingerprint):
+      raise ValueError(f"world states of fingerprint {self.fingerprint:016x} do not fit this substrate "
+                       f"({int(fingerprint):016x}): another level, player count, roles or library")
+    if self.row_bytes != int(row_bytes):
+      raise ValueError(f"world states have rows of {self.row_bytes} bytes, this substrate {row_bytes}")
+
+  def __repr__(self):
+    return f"WorldStates({len(self)} x {self.row_bytes} B, fingerprint {self.fingerprint:016x})"
+
+
 class Array:
   """dm_env.specs.Array look-alike."""
 
@@ -789,6 +840,28 @@ class Substrate:
     """wrappers/base.py:60-62 `observation()`: the observation of the last reset() /
     step() again (the leaves of the last TimeStep)."""
     return self._timestep().observation
+
+  def save_state(self, worlds=None) -> WorldStates:
+    """The records of `worlds` (None: every world, in order) as device rows — a copy on the
+    device, ordered on the current stream, no host synchronisation."""
+    self._eng.use_current_stream()
+    return WorldStates(self._eng.save_worlds(worlds), self._eng.state_fingerprint)
+
+  def load_state(self, states: WorldStates, src) -> TimeStep:
+    """World w continues from row src[w] of `states` (-1: world w is left as it is), as the
+    world the row was saved from would: same seed, episode, step and future under the same
+    actions.  One submission, like a masked reset: the returned TimeStep is FIRST for loaded
+    worlds (LAST for a row saved from a finished episode), with the observations of their
+    records; `src` has num_worlds entries (an int is enough for one world)."""
+    if not isinstance(states, WorldStates):
+      raise ValueError("load_state takes the WorldStates of save_state")
+    states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
+    if isinstance(src, (int, np.integer)):
+      src = [int(src)]
+    self._eng.use_current_stream()
+    self._eng.load_worlds(states.data, src, states.fingerprint)
+    self._submissions += 1
+    return self._emit(self._timestep())
 
   # dmlab2d properties (wrappers/base.py:64-84): Melting Pot's levels register none —
   # the calls exist and answer like dmlab2d does for an unknown key
