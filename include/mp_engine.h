@@ -487,6 +487,62 @@ typedef struct {
   int32_t bank_rows;       /* LOAD: rows of `bank` */
 } MpWorldStates;
 
+/* Action sequences: K steps of every world in ONE submission, bit-identical to K calls of the
+ * single-step entry points (mp_step, or mp_step_fields with fields = 1) with the same actions,
+ * which also hands back the transition of every one of the K steps.  For planners that fork a
+ * state into many worlds and run a K-step action sequence in each, action repeat, replaying a
+ * recorded trace, fast-forwarding.  Like the world states it rides an existing entry point as a
+ * request: a call of mp_restore whose `bytes` is sizeof(MpStepMany) (neither sizeof(MpWorldStates)
+ * nor any engine's snapshot size: a record is >= 448 bytes) takes `host_buf` as a HOST MpStepMany
+ * with struct_size = sizeof(MpStepMany).  The request is enqueued on the engine's stream like a
+ * step and does not synchronise; it marks the engine as in use, as a step does.
+ * include/mp_step_many.h wraps it as an inline C function.
+ *
+ * After the request (A = the actions of the K steps):
+ *  1. every world's record, the counters, every in-place or bound scalar output, the events of the
+ *     last step, a bound MP_OBS_LAYER and every bound pixel view hold exactly the bytes they hold
+ *     after K single steps with A[0] .. A[K - 1].  Auto-reset included: a world whose episode ends
+ *     at step k uses step k + 1 as its reset (that step's actions are ignored) and goes on in the
+ *     new episode; with auto_reset = 0 it stays frozen and reports what a frozen world reports to
+ *     the end of the sequence.  Out-of-range action ids are NOOPs counted in MP_CTR_BAD_ACTIONS.
+ *  2. per_step[i], each optional (NULL: not asked for), stacked along a leading K:
+ *       [0] MP_OBS_REWARD f64 [K][N][P]      [1] MP_OBS_COLLECTIVE_REWARD f64 [K][N]
+ *       [2] MP_OBS_STEP_TYPE i32 [K][N]      [3] MP_OBS_DISCOUNT f64 [K][N]
+ *       [4] MP_OBS_EVENTS i32 [K][N][MP_EVENT_ROWS][4]
+ *     Row k is what the in-place buffer of that kind holds after step k of the sequential loop
+ *     (EVENTS: the header row and the rows it counts; rows beyond the count are not written).
+ *     These are the kinds every path of a step (step, reset, frozen) writes for a started world;
+ *     no other kind has per-step rows.  A world that has never been reset writes nothing.  The
+ *     in-place (or bound) buffers of the five kinds hold step K's values either way.
+ *  3. it is one submission: with a rollout ring bound it writes ONE slot, the state after step K.
+ *     Pixel views and LAYER are drawn once, from the final records (the K-step kernel, then the
+ *     draw-only launches).
+ *  4. `actions` is device memory: discrete ids int32 [K][N][P] (fields = 0) or raw fields int32
+ *     [K][N][P][A] (fields = 1).  actions_step_bytes is the distance between two steps' blocks
+ *     (0: the same [N][P] block every step, which is action repeat); per_step_bytes[i] the
+ *     distance between two steps' rows of per_step[i].  Distances larger than a block let several
+ *     engines read and write their own columns of shared [K][N total] tensors.
+ *  5. 1 <= steps <= MP_STEP_MANY_MAX.
+ *  6. MP_ERR_INVALID before any launch, the engine left as it was: NULL engine or actions; a wrong
+ *     struct_size; steps out of range; fields neither 0 nor 1; an engine that has never been reset
+ *     (mp_reset, mp_restore or a load); an actions_step_bytes that is neither 0 nor a multiple of
+ *     4 >= one step's block; a per_step_bytes[i] smaller than one step's rows or not a multiple of
+ *     the element size (8, 8, 4, 8; 16 for EVENTS, whose rows are stored as int4); a buffer not
+ *     aligned to its element size (EVENTS: 16 bytes); any buffer that is not device memory of the
+ *     engine's device or whose extent [ptr, ptr + (steps - 1) * distance + block) does not lie
+ *     inside one allocation. */
+#define MP_STEP_MANY_MAX 4096
+typedef struct {
+  uint32_t struct_size;        /* = sizeof(MpStepMany) */
+  int32_t steps;               /* K */
+  int32_t fields;              /* 0: discrete ids [K][N][P]; 1: raw fields [K][N][P][A] */
+  int32_t reserved;
+  const int32_t* actions;      /* device */
+  uint64_t actions_step_bytes; /* 0: the same block every step */
+  void* per_step[5];           /* device or NULL: REWARD, COLLECTIVE_REWARD, STEP_TYPE, DISCOUNT, EVENTS */
+  uint64_t per_step_bytes[5];  /* distance between two steps' rows of each */
+} MpStepMany;
+
 /* Throughput / event counters accumulated on device since creation
  * (synchronises).  These are what the multi-GPU bench all-reduces. */
 enum {

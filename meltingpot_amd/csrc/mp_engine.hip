@@ -24,9 +24,13 @@
 
 void launch_step(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
                  hipStream_t stream);
+void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
+                      int steps, long long actions_step, void* const rows[5],
+                      const uint64_t row_bytes[5], hipStream_t stream);
 int step_lds_bytes(const DevTables& t, const SubstrateTables& s, int wpg);
 int step_worlds_per_group(const DevTables& t, const SubstrateTables& s);
 int prepare_step();
+int prepare_step_many();
 void launch_layer_view(const DevTables& t, const uint8_t* state, int32_t* out, int num_worlds,
                        hipStream_t stream);
 
@@ -357,8 +361,11 @@ void draw(MpEngine* e, uint8_t* rgb, uint8_t* wrgb, int pool_k = 1) {
   launch_frame(e->t, nullptr, args, rgb, wrgb, p, e->stream, rgb ? pool_k : 1, e->world_pool);
 }
 
+// (`many`: an MpStepMany request, checked by step_many — K steps by the K-step kernels, then the
+// draw-only launches of the unfused path)
 int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
-           const uint8_t* bank = nullptr, const int32_t* src = nullptr, int bank_rows = 0) {
+           const uint8_t* bank = nullptr, const int32_t* src = nullptr, int bank_rows = 0,
+           const MpStepMany* many = nullptr) {
   stepk::StepArgs args;
   args.state = e->d_state; args.actions = actions; args.reset_mask = mask;
   args.bank = bank; args.src = src; args.bank_rows = bank_rows;
@@ -377,8 +384,12 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
   uint8_t* wrgb = (uint8_t*)e->bound[MP_OBS_WORLD_RGB];
   const int pk = rgb ? e->pool_k() : 1;
   const int views = rgb && wrgb ? 2 : wrgb ? 1 : 0;
-  if ((!rgb && !wrgb) || !e->fuse(rgb == nullptr)) {
-    launch_step(e->t, e->sub, args, e->stream);
+  if (many || (!rgb && !wrgb) || !e->fuse(rgb == nullptr)) {
+    if (many)
+      launch_step_many(e->t, e->sub, args, many->steps, (long long)(many->actions_step_bytes / 4),
+                       many->per_step, many->per_step_bytes, e->stream);
+    else
+      launch_step(e->t, e->sub, args, e->stream);
     if (rgb) draw(e, rgb, nullptr, pk);
     if (wrgb) draw(e, nullptr, wrgb);
   } else {
@@ -911,6 +922,8 @@ int plan_views(MpEngine* e, const MpDevOptions* dev) {
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) failed: %d", rc);
   if (int rc = prepare_step())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the step kernels failed: %d", rc);
+  if (int rc = prepare_step_many())
+    return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the K-step kernels failed: %d", rc);
   if (dev && dev->verbose)
     for (int v = 0; v < 6; ++v) {
       const FramePlan& pl = e->plan[v & 1][v >> 1];
@@ -1440,6 +1453,52 @@ static int world_states(MpEngine* e, MpWorldStates* r, bool restore) {
   }
 }
 
+// An MpStepMany request (include/mp_engine.h): what mp_restore does when `bytes` is
+// sizeof(MpStepMany).  Everything is checked here, before the one submission.
+static int step_many(MpEngine* e, const MpStepMany* r) {
+  if (!e || !r->actions) return fail(MP_ERR_INVALID, "MpStepMany: NULL engine or actions");
+  if (r->struct_size != sizeof(MpStepMany))
+    return fail(MP_ERR_INVALID, "MpStepMany: struct_size %u, expected %zu", r->struct_size, sizeof(MpStepMany));
+  if (r->steps < 1 || r->steps > MP_STEP_MANY_MAX)
+    return fail(MP_ERR_INVALID, "MpStepMany: steps %d is outside [1, %d]", r->steps, MP_STEP_MANY_MAX);
+  if (r->fields != 0 && r->fields != 1)
+    return fail(MP_ERR_INVALID, "MpStepMany: fields %d is neither 0 (discrete ids) nor 1 (raw fields)", r->fields);
+  if (!e->has_state)
+    return fail(MP_ERR_INVALID, "MpStepMany: the engine has never been reset; there is nothing to step");
+  const uint64_t K = (uint64_t)r->steps, N = (uint64_t)e->N, P = (uint64_t)e->t.P;
+  const uint64_t ablock = N * P * (r->fields ? (uint64_t)e->t.nfields : 1u) * 4u;
+  if (r->actions_step_bytes != 0 && (r->actions_step_bytes < ablock || r->actions_step_bytes % 4))
+    return fail(MP_ERR_INVALID, "MpStepMany: actions_step_bytes %llu is neither 0 nor a multiple of 4 that "
+                "holds one step's block of %llu bytes", (unsigned long long)r->actions_step_bytes,
+                (unsigned long long)ablock);
+  if ((uintptr_t)r->actions & 3)
+    return fail(MP_ERR_INVALID, "MpStepMany: actions %p is not 4-byte aligned", (const void*)r->actions);
+  static const char* const kName[5] = {"REWARD", "COLLECTIVE_REWARD", "STEP_TYPE", "DISCOUNT", "EVENTS"};
+  const uint64_t elem[5] = {8, 8, 4, 8, 16};
+  const uint64_t block[5] = {N * P * 8, N * 8, N * 4, N * 8, N * (uint64_t)MP_EVENT_ROWS * 16};
+  for (int i = 0; i < 5; ++i) {
+    if (!r->per_step[i]) continue;
+    if (r->per_step_bytes[i] < block[i] || r->per_step_bytes[i] % elem[i])
+      return fail(MP_ERR_INVALID, "MpStepMany: per_step_bytes of %s is %llu; it must be a multiple of %llu "
+                  "that holds one step's rows of %llu bytes", kName[i], (unsigned long long)r->per_step_bytes[i],
+                  (unsigned long long)elem[i], (unsigned long long)block[i]);
+    if ((uintptr_t)r->per_step[i] % elem[i])
+      return fail(MP_ERR_INVALID, "MpStepMany: the %s buffer %p is not %llu-byte aligned", kName[i],
+                  r->per_step[i], (unsigned long long)elem[i]);
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = check_bank(e, r->actions, (K - 1) * r->actions_step_bytes + ablock, "MpStepMany (actions)"))
+    return rc;
+  for (int i = 0; i < 5; ++i) {
+    if (!r->per_step[i]) continue;
+    char who[48];
+    snprintf(who, sizeof who, "MpStepMany (%s)", kName[i]);
+    if (int rc = check_bank(e, r->per_step[i], (K - 1) * r->per_step_bytes[i] + block[i], who)) return rc;
+  }
+  e->touched = true;
+  return submit(e, r->fields ? STEP_MODE_FIELDS : STEP_MODE_STEP, r->actions, nullptr, nullptr, nullptr, 0, r);
+}
+
 uint64_t mp_snapshot_bytes(const MpEngine* e) {
   return e ? (uint64_t)e->N * e->t.world_stride : 0;
 }
@@ -1459,6 +1518,11 @@ int mp_restore(MpEngine* e, const void* buf, uint64_t bytes) {
     MpWorldStates r;   // (read only: a load writes nothing back)
     memcpy(&r, buf, sizeof r);
     return world_states(e, &r, true);
+  }
+  if (buf && bytes == sizeof(MpStepMany)) {
+    MpStepMany r;   // (read only: nothing is written back)
+    memcpy(&r, buf, sizeof r);
+    return step_many(e, &r);
   }
   if (!e || !buf || bytes != mp_snapshot_bytes(e))
     return fail(MP_ERR_INVALID, "mp_restore: bad buffer");

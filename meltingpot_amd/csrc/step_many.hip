@@ -1,0 +1,198 @@
+// step_many.hip — the K-step form of the stand-alone step kernels (MpStepMany,
+// include/mp_engine.h): one wavefront per world as in step_kernels.hip, with the world's record
+// resident in LDS across K steps of one launch.  A unit of its own: the single-step kernels and
+// k_frame are compiled from exactly what they were compiled from before.
+#include "../../include/mp_pack.h"
+#include "step_clean_up.h"
+#include "step_coins.h"
+#include "step_commons.h"
+#include "step_coop.h"
+#include "step_gift.h"
+#include "step_mushroom.h"
+#include "step_cook.h"
+#include "step_matrix.h"
+#include "step_territory.h"
+#include "step_load.h"
+
+int step_lds_bytes(const DevTables& t, const SubstrateTables& s, int wpg);   // (step_kernels.hip)
+int step_worlds_per_group(const DevTables& t, const SubstrateTables& s);
+
+namespace {
+
+using namespace stepk;
+
+constexpr int kWorldsPerGroup = 4;   // (step_kernels.hip)
+
+// What a K-step launch gets besides StepArgs: args.actions is step 0's block, step k's lies
+// actions_step int32 further (0: the same block every step).  row[i] (NULL: not asked for) is
+// row 0 of the caller's per-step buffer of kind i, row_bytes[i] the distance between two rows.
+struct ManyArgs {
+  int steps;
+  long long actions_step;
+  uint8_t* row[5];          // REWARD, COLLECTIVE_REWARD, STEP_TYPE, DISCOUNT, EVENTS
+  long long row_bytes[5];
+};
+
+template <class T>
+__device__ inline T* row_of(uint8_t* base, long long bytes, int k, T* in_place) {
+  return base ? reinterpret_cast<T*>(base + (long long)k * bytes) : in_place;
+}
+
+// The K-step form of run_one_world: the tables, the site lists and the record are loaded once,
+// the marks and the level's extras set up once (as a feeder of k_frame does for the worlds it
+// steps one after the other on one scratch), and per step only the event scratch is cleared, the
+// action looked up and the level's step run on the record in LDS.  Step k + 1's action ids are
+// requested before step k's work.  finish() still stores the record after every step: those are
+// stores nobody waits for, and the next step works on the LDS copy; the record HBM holds in the
+// end is step K's.  The five per-step kinds go to row k of the caller's buffers where given; the
+// wave then copies row K - 1 to the in-place buffers, every lane reading back exactly the words
+// it stored itself (program order of one thread: no fence, no second launch).
+template <class Tables, class Sites>
+__device__ inline void run_many(const DevTables& t, const Tables& c, const StepArgs& args0,
+                                const ManyArgs& m, int extra) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int w = blockIdx.x * ((int)blockDim.x >> 6) + wave;
+  uint8_t* tables = smem;
+  const int per_world = t.world_stride + scratch_bytes(t) + extra;
+  uint8_t* mine = smem + tables_bytes(t) + wave * per_world;
+  const bool live = w < args0.num_worlds;
+  World wd = make_world(t, mine, tables, mine + t.world_stride, args0.state, live ? w : 0, lane);
+  wd.next_orders = args0.next_orders;
+  int act_id = 0;
+  Sites sites = Sites();
+  if (live) {
+    act_id = fetch_action_id(t, args0.actions, args0.mode, w, lane);
+    sites = load_sites(c, lane);
+    load_record(t, wd.rec, wd.gw, lane);
+  }
+  load_tables(t, tables, (int)threadIdx.x, (int)blockDim.x);
+  clear_marks(t, wd.mark, lane);
+  begin_step(wd.sc, lane);
+  __syncthreads();
+  if (!live) return;
+  init_extra(t, c, wd.extra, lane);
+  StepArgs args = args0;
+  const int K = m.steps;
+  for (int k = 0; k < K; ++k) {
+    int next_id = 0;
+    if (k + 1 < K)
+      next_id = fetch_action_id(t, args0.actions + (long long)(k + 1) * m.actions_step, args0.mode, w, lane);
+    if (k) {
+      wsync();   // finish() has read the record for its write-back
+      begin_step(wd.sc, lane);
+      wsync();
+    }
+    // (one step's code is one step's: a lane index the compiler cannot see through keeps it from
+    // hoisting every step-invariant value out of the loop and holding them all in registers)
+    int lane_k = lane;
+    asm volatile("" : "+v"(lane_k));
+    wd.lane = lane_k;
+    args.out.reward = row_of(m.row[0], m.row_bytes[0], k, args0.out.reward);
+    args.out.collective = row_of(m.row[1], m.row_bytes[1], k, args0.out.collective);
+    args.out.step_type = row_of(m.row[2], m.row_bytes[2], k, args0.out.step_type);
+    args.out.discount = row_of(m.row[3], m.row_bytes[3], k, args0.out.discount);
+    args.out.events = row_of(m.row[4], m.row_bytes[4], k, args0.out.events);
+    const Action act = lookup_action(t, wd, act_id, args0.mode);
+    step_world(t, c, sites, wd, act, args);
+    act_id = next_id;
+  }
+  wsync();
+  const WorldTail* tail = reinterpret_cast<const WorldTail*>(wd.rec + t.grid_pad);
+  // step K's values of the five kinds, in place too (a world never reset wrote nothing)
+  if (__builtin_amdgcn_readfirstlane((int)tail->started)) {
+    const size_t o = (size_t)w * t.P + lane;
+    if (m.row[0] && lane < t.P) args0.out.reward[o] = args.out.reward[o];
+    if (lane == 0) {
+      if (m.row[1]) args0.out.collective[w] = args.out.collective[w];
+      if (m.row[2]) args0.out.step_type[w] = args.out.step_type[w];
+      if (m.row[3]) args0.out.discount[w] = args.out.discount[w];
+    }
+    if (m.row[4]) {
+      const int4* src = reinterpret_cast<const int4*>(args.out.events) + (size_t)w * MP_EVENT_ROWS;
+      int4* dst = reinterpret_cast<int4*>(args0.out.events) + (size_t)w * MP_EVENT_ROWS;
+      int n = 0;
+      if (lane == 0) { const int4 h = src[0]; dst[0] = h; n = h.x; }
+      n = __builtin_amdgcn_readfirstlane(n);
+      n = n < 0 ? 0 : n > MP_EVENT_ROWS - 1 ? MP_EVENT_ROWS - 1 : n;
+      for (int i = lane; i < n; i += 64) dst[1 + i] = src[1 + i];   // (row 1 + i: lane i % 64's own store)
+    }
+  }
+  if (args0.out.layer) write_layer(t, wd.rec, args0.out, w, lane);
+}
+
+#define MP_STEP_MANY_KERNEL(name, TablesT, SitesT, extra)                                            \
+  __global__ __launch_bounds__(kWorldsPerGroup * 64) void name(DevTables t, TablesT c, StepArgs args, \
+                                                               ManyArgs m) {                         \
+    run_many<TablesT, SitesT>(t, c, args, m, extra);                                                 \
+  }
+MP_STEP_MANY_KERNEL(k_step_many_clean_up, CleanUpTables, CleanUpSites, 0)
+MP_STEP_MANY_KERNEL(k_step_many_commons, CommonsTables, CommonsSites, 0)
+MP_STEP_MANY_KERNEL(k_step_many_coins, CoinsTables, CoinsSites, 0)
+MP_STEP_MANY_KERNEL(k_step_many_coop, CoopTables, CoopSites, 0)
+MP_STEP_MANY_KERNEL(k_step_many_gift, GiftTables, GiftSites, 0)
+MP_STEP_MANY_KERNEL(k_step_many_cook, CookTables, CookSites, 0)
+MP_STEP_MANY_KERNEL(k_step_many_mushroom, MushroomTables, MushroomSites, extra_bytes(c))
+MP_STEP_MANY_KERNEL(k_step_many_matrix, MatrixTables, MatrixSites, 0)
+MP_STEP_MANY_KERNEL(k_step_many_territory, TerritoryTables, TerritorySites, extra_bytes(c))
+#undef MP_STEP_MANY_KERNEL
+
+}  // namespace
+
+// The K-step kernels may take all 160 KB of a CU's LDS, like the single-step ones.
+int prepare_step_many() {
+  const void* km[9] = {
+      reinterpret_cast<const void*>(&k_step_many_clean_up), reinterpret_cast<const void*>(&k_step_many_commons),
+      reinterpret_cast<const void*>(&k_step_many_coins), reinterpret_cast<const void*>(&k_step_many_territory),
+      reinterpret_cast<const void*>(&k_step_many_matrix), reinterpret_cast<const void*>(&k_step_many_coop),
+      reinterpret_cast<const void*>(&k_step_many_gift), reinterpret_cast<const void*>(&k_step_many_cook),
+      reinterpret_cast<const void*>(&k_step_many_mushroom)};
+  for (const void* f : km)
+    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+      return 1;
+  return 0;
+}
+
+// K steps of every world in one launch (MpStepMany): the geometry of launch_step.  `rows` and
+// `row_bytes` are the five per-step buffers (NULL: not asked for) and their step distances,
+// `actions_step` the distance between two steps' action blocks in int32.
+void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
+                      int steps, long long actions_step, void* const rows[5],
+                      const uint64_t row_bytes[5], hipStream_t stream) {
+  ManyArgs m;
+  m.steps = steps; m.actions_step = actions_step;
+  for (int i = 0; i < 5; ++i) { m.row[i] = (uint8_t*)rows[i]; m.row_bytes[i] = (long long)row_bytes[i]; }
+  const int wpg = step_worlds_per_group(t, s);
+  const size_t lds = (size_t)step_lds_bytes(t, s, wpg);
+  const dim3 grid((args.num_worlds + wpg - 1) / wpg), block(wpg * 64);
+  switch (s.substrate) {
+    case MPK_SUBSTRATE_CLEAN_UP:
+      hipLaunchKernelGGL(k_step_many_clean_up, grid, block, lds, stream, t, s.cu, args, m);
+      break;
+    case MPK_SUBSTRATE_COMMONS_HARVEST:
+      hipLaunchKernelGGL(k_step_many_commons, grid, block, lds, stream, t, s.ch, args, m);
+      break;
+    case MPK_SUBSTRATE_COINS:
+      hipLaunchKernelGGL(k_step_many_coins, grid, block, lds, stream, t, s.co, args, m);
+      break;
+    case MPK_SUBSTRATE_TERRITORY:
+      hipLaunchKernelGGL(k_step_many_territory, grid, block, lds, stream, t, s.tr, args, m);
+      break;
+    case MPK_SUBSTRATE_THE_MATRIX:
+      hipLaunchKernelGGL(k_step_many_matrix, grid, block, lds, stream, t, s.mx, args, m);
+      break;
+    case MPK_SUBSTRATE_COOP_MINING:
+      hipLaunchKernelGGL(k_step_many_coop, grid, block, lds, stream, t, s.cm, args, m);
+      break;
+    case MPK_SUBSTRATE_GIFT_REFINEMENTS:
+      hipLaunchKernelGGL(k_step_many_gift, grid, block, lds, stream, t, s.gr, args, m);
+      break;
+    case MPK_SUBSTRATE_COLLABORATIVE_COOKING:
+      hipLaunchKernelGGL(k_step_many_cook, grid, block, lds, stream, t, s.cc, args, m);
+      break;
+    case MPK_SUBSTRATE_EXTERNALITY_MUSHROOMS:
+      hipLaunchKernelGGL(k_step_many_mushroom, grid, block, lds, stream, t, s.em, args, m);
+      break;
+  }
+}

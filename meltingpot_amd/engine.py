@@ -220,6 +220,55 @@ def world_states_request(L, handle, op: int, **fields) -> MpWorldStates:
   return req
 
 
+# Action sequences (include/mp_engine.h: MpStepMany), carried by mp_restore
+STEP_MANY_MAX = 4096   # MP_STEP_MANY_MAX
+STEP_MANY_KINDS = ("reward", "collective_reward", "step_type", "discount", "events")
+
+
+class MpStepMany(ctypes.Structure):
+  _fields_ = [("struct_size", ctypes.c_uint32), ("steps", ctypes.c_int32),
+              ("fields", ctypes.c_int32), ("reserved", ctypes.c_int32),
+              ("actions", ctypes.c_void_p), ("actions_step_bytes", ctypes.c_uint64),
+              ("per_step", ctypes.c_void_p * 5), ("per_step_bytes", ctypes.c_uint64 * 5)]
+
+
+def check_step_many(shape, dtype, num_worlds: int, num_players: int, *, repeat=None,
+                    num_fields: Optional[int] = None) -> int:
+  """The shape and dtype rules of Engine.step_many's actions, without an engine: returns K.
+  [K, N, P] integers (or [K, N, P, A] with num_fields = A), or one block [N, P] ([N, P, A]) with
+  repeat = K; 1 <= K <= STEP_MANY_MAX.  ValueError otherwise."""
+  shape = tuple(int(d) for d in shape)
+  block = (num_worlds, num_players) + ((int(num_fields),) if num_fields else ())
+  name = str(dtype)
+  if "int" not in name or "float" in name:
+    raise ValueError(f"step_many: actions must hold integers (got {name})")
+  if repeat is not None:
+    if shape != block:
+      raise ValueError(f"step_many: with repeat= the actions are one block of shape {block} (got {shape})")
+    K = int(repeat)
+  else:
+    if len(shape) != len(block) + 1 or shape[1:] != block:
+      raise ValueError(f"step_many: actions must have shape (K,) + {block} (got {shape})")
+    K = shape[0]
+  if not 1 <= K <= STEP_MANY_MAX:
+    raise ValueError(f"step_many: K = {K} is outside [1, {STEP_MANY_MAX}]")
+  return K
+
+
+def _step_distance(tensor, what: str) -> int:
+  """Bytes between tensor[k] and tensor[k + 1] of a tensor that may be non-contiguous along its
+  first dimension only (a column slice [:, a:b] of a wider tensor)."""
+  if not tensor[0].is_contiguous():
+    raise ValueError(f"step_many: {what} may be non-contiguous along K only (each step's block "
+                     f"must be contiguous; strides {tuple(tensor.stride())})")
+  block = int(tensor[0].numel())
+  if tensor.shape[0] == 1:
+    return block * tensor.element_size()
+  if tensor.stride(0) < block:
+    raise ValueError(f"step_many: the steps of {what} overlap (stride {tensor.stride(0)} < {block})")
+  return int(tensor.stride(0)) * tensor.element_size()
+
+
 class EngineError(RuntimeError):
   pass
 
@@ -777,6 +826,66 @@ class Engine:
         raise ValueError(f"fields must have shape {shape}")
       _check(self._L, self._L.mp_step_fields_host(self._h, a.ctypes.data),
              "mp_step_fields_host")
+
+  def step_many(self, actions, *, repeat: Optional[int] = None, fields: bool = False,
+                keep=("reward", "collective_reward", "step_type", "discount"), events: bool = False,
+                out=None):
+    """K steps of every world in ONE launch, bit-identical to K calls of step() (fields=True:
+    step_fields()) with actions[0] .. actions[K - 1]; returns the per-step transitions.
+
+    actions: integers [K, N, P] ([K, N, P, A] with fields=True), or one block [N, P] with
+    repeat=K (action repeat).  A device int32 tensor is read in place and may be
+    non-contiguous along K only (a column slice [:, a:b] of a wider tensor); a host array is
+    uploaded once.  1 <= K <= STEP_MANY_MAX.
+    keep: which of "reward" f64 [K, N, P], "collective_reward" f64 [K, N], "step_type" i32
+    [K, N], "discount" f64 [K, N] to stack per step; events=True adds "events" i32
+    [K, N, EVENT_ROWS, 4] (rows beyond a header's count are not written).  Returned as a dict
+    by name; out= (a previous result) reuses its tensors.  The in-place / bound buffers hold
+    step K's values as after K steps; pixel views, LAYER and a ring slot are written once, from
+    the final state.  Enqueued on the current stream; does not synchronise."""
+    t = self._torch
+    A = int(self.info.num_action_fields) if fields else None
+    if isinstance(actions, t.Tensor) and actions.is_cuda:
+      if actions.dtype != t.int32:
+        raise ValueError(f"step_many: a device tensor of actions must be int32 (got {actions.dtype})")
+      K = check_step_many(actions.shape, actions.dtype, self.N, self.P, repeat=repeat, num_fields=A)
+      if actions.device != self.device:
+        raise ValueError(f"step_many: actions live on {actions.device}, the engine on {self.device}")
+    else:
+      a = actions.cpu().numpy() if isinstance(actions, t.Tensor) else np.asarray(actions)
+      K = check_step_many(a.shape, a.dtype, self.N, self.P, repeat=repeat, num_fields=A)
+      actions = t.from_numpy(np.ascontiguousarray(a, np.int32)).to(self.device)
+    astep = 0 if repeat is not None else _step_distance(actions, "actions")
+    if repeat is not None and not actions.is_contiguous():
+      raise ValueError("step_many: the repeated block of actions must be contiguous")
+    names = [k for k in STEP_MANY_KINDS if k in tuple(keep) or (k == "events" and events)]
+    unknown = [k for k in keep if k not in STEP_MANY_KINDS[:4]]
+    if unknown:
+      raise ValueError(f"step_many: keep= knows {STEP_MANY_KINDS[:4]} (got {unknown})")
+    shapes = {"reward": ((K, self.N, self.P), t.float64), "collective_reward": ((K, self.N), t.float64),
+              "step_type": ((K, self.N), t.int32), "discount": ((K, self.N), t.float64),
+              "events": ((K, self.N, EVENT_ROWS, 4), t.int32)}
+    self.use_current_stream()
+    req = MpStepMany(ctypes.sizeof(MpStepMany), K, 1 if fields else 0, 0)
+    req.actions = actions.data_ptr()
+    req.actions_step_bytes = astep
+    result = {}
+    for name in names:
+      shape, dtype = shapes[name]
+      buf = None if out is None else out.get(name)
+      if buf is None:
+        buf = t.empty(shape, dtype=dtype, device=self.device)
+      elif (not isinstance(buf, t.Tensor) or buf.dtype != dtype or tuple(buf.shape) != shape or
+            buf.device != self.device):
+        raise ValueError(f"step_many: out[{name!r}] must be a {dtype} tensor of shape {shape} on {self.device}")
+      i = STEP_MANY_KINDS.index(name)
+      req.per_step[i] = buf.data_ptr()
+      req.per_step_bytes[i] = _step_distance(buf, f"out[{name!r}]")
+      result[name] = buf
+    _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
+           "mp_restore (MpStepMany)")
+    self._state_args = (actions, result)   # (kept until the next call: the launch may not have run yet)
+    return result
 
   def observe(self, kind: int, out=None):
     if out is None:

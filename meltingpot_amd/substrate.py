@@ -83,6 +83,31 @@ class RolloutTimeStep(TimeStep):
     return out
 
 
+class StepManyResult(NamedTuple):
+  """What `Substrate.step_many` returns: the transitions of all K steps as device tensors
+  stacked along a leading K, and the TimeStep of the last one."""
+  step_type: Any           # int32 [K, N]
+  reward: Any              # float64 [K, N, P]
+  discount: Any            # float64 [K, N]
+  collective_reward: Any   # float64 [K, N]
+  events: Any              # int32 [K, N, EVENT_ROWS, 4] (events=True) or None
+  timestep: TimeStep       # what the K-th step() would have returned
+
+
+def _many_actions(t, actions, repeat, N: int, P: int, num_actions: Optional[int]):
+  """`actions` of a step_many call as the engine takes them: an int32 device tensor (as it is:
+  it may be a column slice) or a host array; shape-checked, range-checked when asked."""
+  if isinstance(actions, t.Tensor) and actions.is_cuda:
+    a = actions.to(t.int32)
+    K = engine_lib.check_step_many(a.shape, a.dtype, N, P, repeat=repeat)
+    if num_actions is not None and bool(((a < 0) | (a >= num_actions)).any()):
+      raise ValueError(f"actions must be in [0, {num_actions})")
+  else:
+    a = np.asarray(actions)
+    K = engine_lib.check_step_many(a.shape, a.dtype, N, P, repeat=repeat)
+  return a, K
+
+
 class WorldStates:
   """Saved worlds (`Substrate.save_state`): `data`, a uint8 [M, S] tensor on the engine's device
   whose row i is one world's whole record, and `fingerprint`, the engine's state fingerprint
@@ -924,6 +949,50 @@ class Substrate:
         self._eng.step_fields(self._action_rows[a])
     self._submissions += 1
 
+  def step_many(self, actions, repeat: Optional[int] = None, events: bool = False) -> StepManyResult:
+    """K steps in ONE launch, bit-identical to K calls of `step` (batched substrates).
+    `actions`: ints [K, N, P] (a device tensor is read in place; it may be a column slice
+    [:, a:b] of a wider one), or one block [N, P] with `repeat=K`.  Returns the per-step
+    `step_type` [K, N], `reward` [K, N, P], `discount` [K, N], `collective_reward` [K, N],
+    `events` (the raw int32 [K, N, EVENT_ROWS, 4] tensor with events=True, else None) and
+    `timestep`, the TimeStep the K-th `step` would have returned.  It is one submission: with
+    `rollout_length=T` it writes one slot (the state after step K), and observations are
+    those of the final state.  `observables()`: the action subject gets the whole sequence
+    once; the timestep and events subjects get the last step's."""
+    if not self._batched:
+      raise ValueError("step_many steps a batch of worlds: build the substrate with num_worlds > 1")
+    t = self._eng._torch
+    limit = None
+    if self._check_device_actions:
+      limit = len(self._action_rows) if self._action_rows is not None else self._eng.num_actions
+    a, _ = _many_actions(t, actions, repeat, self._eng.N, self._eng.P, limit)
+    self._observables.action.on_next(actions)
+    self._eng.use_current_stream()
+    r = self._submit_many(a, repeat, events, None)
+    return StepManyResult(r["step_type"], r["reward"], r["discount"], r["collective_reward"],
+                          r.get("events"), self._emit(self._timestep()))
+
+  def _submit_many(self, a, repeat, events, out):
+    """One K-step launch of the engine on actions `a` as `_many_actions` prepared them."""
+    t = self._eng._torch
+    if self._action_rows is None:
+      r = self._eng.step_many(a, repeat=repeat, events=events, out=out)
+    else:
+      # a custom table: its rows go to the engine as raw fields, as in `_submit`
+      K = len(self._action_rows)
+      if isinstance(a, t.Tensor):
+        if self._action_rows_dev is None:
+          self._action_rows_dev = t.from_numpy(self._action_rows).to(self._eng.device)
+        f = self._action_rows_dev[a.long().clamp_(0, K - 1)].contiguous()
+      else:
+        a = a.astype(np.int64)
+        if ((a < 0) | (a >= K)).any():
+          raise ValueError(f"actions must be in [0, {K})")
+        f = self._action_rows[a]
+      r = self._eng.step_many(f, repeat=repeat, fields=True, events=events, out=out)
+    self._submissions += 1
+    return r
+
   def observables(self) -> SubstrateObservables:
     """substrate.py:102-104.  `events` emits (name, payload) like the reference —
     of world 0 when the substrate is batched; `events_batched` (batched substrates)
@@ -1493,6 +1562,32 @@ class MixtureSubstrate:
       m._submit(a[off:off + n])
     self._submissions += 1
     return self._emit(self._timestep())
+
+  def step_many(self, actions, repeat: Optional[int] = None, events: bool = False) -> StepManyResult:
+    """As `Substrate.step_many`, over the members: one K-step launch per member, each reading
+    its columns [:, off_i:off_i + n_i] of `actions` and writing its columns of the shared
+    [K, N, ...] per-step tensors (nothing is copied or concatenated)."""
+    first = self._members[0]
+    t = first._eng._torch
+    limit = self.action_spec()[0].num_values if self._check_device_actions else None
+    a, K = _many_actions(t, actions, repeat, self._N, self._P, limit)
+    dev = first._eng.device
+    out = {"reward": t.empty((K, self._N, self._P), dtype=t.float64, device=dev),
+           "collective_reward": t.empty((K, self._N), dtype=t.float64, device=dev),
+           "step_type": t.empty((K, self._N), dtype=t.int32, device=dev),
+           "discount": t.empty((K, self._N), dtype=t.float64, device=dev)}
+    if events:
+      out["events"] = t.empty((K, self._N, engine_lib.EVENT_ROWS, 4), dtype=t.int32, device=dev)
+    self._observables.action.on_next(actions)
+    for m, off, n in zip(self._members, self._offsets, self._counts):
+      m._eng.use_current_stream()
+      cols = a[off:off + n] if repeat is not None else a[:, off:off + n]
+      if repeat is not None and isinstance(cols, t.Tensor):
+        cols = cols.contiguous()
+      m._submit_many(cols, repeat, events, {k: v[:, off:off + n] for k, v in out.items()})
+    self._submissions += 1
+    return StepManyResult(out["step_type"], out["reward"], out["discount"], out["collective_reward"],
+                          out.get("events"), self._emit(self._timestep()))
 
   def _member_at(self, world: int):
     if not 0 <= world < self._N:
