@@ -221,6 +221,9 @@ typedef struct {
                                serves unevenly) */
   int32_t team;             /* 1: with single-world batches (batch_worlds = 1, nothing pooled), the workgroups
                                of an XCD share one contiguous range of worlds and deal it among themselves */
+  int32_t generic_kernel;   /* 1: the generic frame kernels even for a committed pack that has kernels with its
+                               constants compiled in (MpKernelVariant).  Appended: mp_create also takes
+                               struct_size = offsetof(MpDevOptions, generic_kernel), which reads as 0 */
 } MpDevOptions;
 
 typedef struct {
@@ -328,6 +331,35 @@ int mp_create(const void* pack, uint64_t pack_len, const MpConfig* cfg,
 void mp_destroy(MpEngine* eng);
 
 int mp_info(const MpEngine* eng, MpInfo* out);
+
+/* Which frame kernels step and draw an engine's worlds (same results either way).  The packs
+ * committed with the package whose scalars — map, view and record geometry, layer and state ids,
+ * beam shapes, cooldowns, thresholds — are compiled into kernels of their own (clean_up with its
+ * default player count) run those; every other pack, and such a pack edited in any byte, created
+ * with another player count or with MpDevOptions.record_pad / generic_kernel, runs the generic
+ * kernels, which take the same values as arguments.
+ *
+ * The question travels as a request struct through mp_snapshot, like MpWorldStates: call
+ * mp_snapshot(eng, &req, sizeof(MpKernelVariant)) with struct_size = sizeof(MpKernelVariant);
+ * include/mp_kernel_variant.h wraps it as an inline C function.  MP_OK and `variant` set, or a
+ * negative MP_ERR_*.
+ *   eng != NULL: what `eng` runs (the other members are ignored).
+ *   eng == NULL: what mp_create on `pack` / `pack_len` / `cfg` WOULD select, decided on the host
+ *     alone (no device is touched; errors as mp_create's for a bad pack or config).  With `fields`
+ *     != NULL also writes, NUL-terminated, the pack's value of every scalar a stock kernel folds,
+ *     one "<group> <member> <C literal>" line each plus "hash <FNV-1a of the pack>" — what
+ *     tools/make_stock_header.py turns into csrc/stock_<level>.h; MP_ERR_UNSUPPORTED for a level
+ *     without stock kernels, MP_ERR_INVALID if `fields_cap` bytes do not hold it. */
+enum { MP_KERNEL_GENERIC = 0, MP_KERNEL_STOCK = 1 };
+typedef struct {
+  uint32_t struct_size;   /* = sizeof(MpKernelVariant) */
+  int32_t variant;        /* out: MP_KERNEL_* */
+  const void* pack;       /* the host-only question (eng == NULL) */
+  uint64_t pack_len;
+  const MpConfig* cfg;
+  char* fields;           /* NULL, or where the folded fields' text goes */
+  uint64_t fields_cap;
+} MpKernelVariant;
 
 /* Work submitted after this call is enqueued on `stream` (a hipStream_t); it is
  * ordered after everything the engine has enqueued on its previous stream. */

@@ -416,10 +416,16 @@ int allow_lds() {
 
 }  // namespace
 
+// frame_stock.hip: the clean_up kernels with the committed pack's constants compiled in
+int prepare_frame_stock();
+void launch_frame_stock(const DevTables& t, const CleanUpTables& c, const stepk::StepArgs& args,
+                        uint8_t* out_a, uint8_t* out_w, const FramePlan& p, hipStream_t stream);
+
 // The frame kernels use up to 160 KB of dynamic LDS; declare it (a no-op where
 // the runtime grants it anyway).  Called once per engine, with its device current.
 int prepare_frame() {
   int rc = prepare_frame_wpool<2>();
+  if (!rc) rc = prepare_frame_stock();
   if (!rc) rc = prepare_frame_wpool<4>();
   if (!rc) rc = prepare_frame_wpool<8>();
   if (!rc) rc = allow_lds<NoTables, NoSites>();
@@ -443,7 +449,8 @@ int prepare_frame() {
 // + the views of the result).  `p` is the plan for exactly these views; p.parity
 // alternates between consecutive frame launches of an engine (DevTables::claim).
 // pool_k > 1: `out_a` is the per-agent view pooled by that factor (2, 4, 8); world_k > 1: `out_w`
-// is WORLD.RGB pooled by that factor (the instantiations of frame_wpool<k>.hip).
+// is WORLD.RGB pooled by that factor (the instantiations of frame_wpool<k>.hip).  The pooled
+// views and the draw-only launch have no stock form.
 void launch_frame(const DevTables& t, const SubstrateTables* s, const stepk::StepArgs& args,
                   uint8_t* out_a, uint8_t* out_w, const FramePlan& p, hipStream_t stream, int pool_k,
                   int world_k) {
@@ -455,6 +462,11 @@ void launch_frame(const DevTables& t, const SubstrateTables* s, const stepk::Ste
   }
   if (!s) {
     launch_one<NoTables, NoSites>(t, NoTables(), args, out_a, out_w, p, stream, pool_k);
+    return;
+  }
+  // the committed pack (mp_create: SubstrateTables::stock), full views: its constants compiled in
+  if (s->stock == MP_KERNEL_STOCK && s->substrate == MPK_SUBSTRATE_CLEAN_UP && !(out_a && pool_k > 1)) {
+    launch_frame_stock(t, s->cu, args, out_a, out_w, p, stream);
     return;
   }
 #if defined(MP_FRAME_ISA_SUBSET)

@@ -480,7 +480,13 @@ __device__ inline int pool_scratch_bytes(const DevTables& t) {
 // 2, 4, 8 = it is pooled by that factor (MP_OBS_RGB_POOL*) — an instantiation of its own: the
 // code of the full views is not touched by it.  kWPool: 0 = WORLD.RGB is the full image; 2, 4, 8
 // = it is pooled by that factor (MpConfig.world_pool; the instantiations of frame_wpool*.hip).
-template <class Tables, class Sites, int kViews, int kPool = 0, int kWPool = 0>
+// Stock: NoStock, or the constants of a committed pack (stock.h) assigned to `t` and `c` at the
+// first line — an instantiation of its own (frame_stock.hip) in which they are immediates.
+struct NoStock {
+  template <class Tables>
+  __device__ static inline void pin(DevTables&, Tables&) {}
+};
+template <class Tables, class Sites, int kViews, int kPool = 0, int kWPool = 0, class Stock = NoStock>
 __global__ __launch_bounds__(max_threads<Tables>()) void k_frame(DevTables t, Tables c,
                                                        stepk::StepArgs args,
                                                        uint8_t* __restrict__ out_a,
@@ -488,6 +494,7 @@ __global__ __launch_bounds__(max_threads<Tables>()) void k_frame(DevTables t, Ta
                                                        FrameConsts K) {
   constexpr bool kStep = !std::is_same<Tables, NoTables>::value;
   constexpr bool kNt = nt_stores<kStep>();
+  Stock::pin(t, c);
 #if defined(MP_FRAME_TIMELINE)
   const uint64_t tl_entry = wall_clock64();
 #endif

@@ -349,6 +349,7 @@ struct MatrixTables {
 // The rule constants of the engine's substrate (one member is in use).
 struct SubstrateTables {
   int32_t substrate;   // MPK_SUBSTRATE_*
+  int32_t stock;       // MP_KERNEL_*: the frame kernels this engine's stepping launches run (stock.h; host side only)
   CleanUpTables cu;
   CommonsTables ch;
   TerritoryTables tr;

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "pack_decode.h"
+#include "stock.h"
 #include "step_common.h"
 
 void launch_step(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
@@ -881,6 +882,23 @@ int upload_layer_lut(MpEngine* e) {
   return MP_OK;
 }
 
+// FNV-1a of a pack's bytes (stock.h: MP_STOCK_*_PACK_HASH).
+uint64_t pack_hash(const std::vector<uint8_t>& pack) {
+  uint64_t h = 0xcbf29ce484222325ull;
+  for (uint8_t b : pack) { h ^= b; h *= 0x100000001b3ull; }
+  return h;
+}
+
+// Which frame kernels an engine on this decoded pack runs (MpKernelVariant): the stock ones only
+// if the pack is the committed one byte for byte and every folded field equals the header's.
+int select_kernels(const std::vector<uint8_t>& pack, const DecodedPack& d, const MpDevOptions* dev) {
+  if (dev && dev->generic_kernel) return MP_KERNEL_GENERIC;
+  if (d.sub.substrate == MPK_SUBSTRATE_CLEAN_UP && pack_hash(pack) == MP_STOCK_CLEAN_UP_PACK_HASH &&
+      StockCleanUp::matches(d.t, d.sub.cu))
+    return MP_KERNEL_STOCK;
+  return MP_KERNEL_GENERIC;
+}
+
 // The frame launches' plans, plain and pooled.
 int plan_views(MpEngine* e, const MpDevOptions* dev) {
   const DevTables& t = e->t;
@@ -953,10 +971,71 @@ int create_on_device(MpEngine* e, const MpConfig& cfg, DecodedPack* d) {
     return fail(MP_ERR_NO_DEVICE, "mp_create: device %d does not report its compute units", cfg.device);
   e->num_cus = cus;
   int rc;
-  if ((rc = upload_pack(e, cfg, d)) || (rc = alloc_fault_words(e)) || (rc = init_state(e, cfg)) ||
+  if ((rc = upload_pack(e, cfg, d))) return rc;
+  e->sub.stock = select_kernels(e->pack, *d, dev);   // (host values only: the verdict of an MpKernelVariant request without an engine)
+  if ((rc = alloc_fault_words(e)) || (rc = init_state(e, cfg)) ||
       (rc = alloc_outputs(e, cfg)) || (rc = build_atlas(e, dev, *d)) || (rc = upload_layer_lut(e)))
     return rc;
   return plan_views(e, dev);
+}
+
+// mp_create's host stage: the config checked and copied (older, shorter layouts of MpConfig and
+// MpDevOptions completed), the pack copied, roles applied, decoded and checked.  No HIP call.
+struct HostStage {
+  MpConfig cfg = {};
+  MpDevOptions dev = {};
+  std::vector<uint8_t> pack;
+  DecodedPack d;
+};
+
+int host_stage(const void* pack, uint64_t pack_len, const MpConfig* cfg, HostStage* h) {
+  // (an MpConfig of the ABI-8 layout, which ends before world_pool, reads as world_pool = 1)
+  if (!cfg || (cfg->struct_size != sizeof(MpConfig) && cfg->struct_size != offsetof(MpConfig, world_pool)))
+    return fail(MP_ERR_INVALID, "mp_create: bad MpConfig (struct_size)");
+  memcpy(&h->cfg, cfg, cfg->struct_size);
+  if (cfg->struct_size < sizeof(MpConfig)) h->cfg.world_pool = 1;
+  cfg = &h->cfg;
+  if (cfg->dev) {
+    // (MpDevOptions before generic_kernel was appended reads as generic_kernel = 0)
+    if (cfg->dev->struct_size != sizeof(MpDevOptions) &&
+        cfg->dev->struct_size != offsetof(MpDevOptions, generic_kernel))
+      return fail(MP_ERR_INVALID, "mp_create: bad MpDevOptions (struct_size)");
+    memcpy(&h->dev, cfg->dev, cfg->dev->struct_size);
+    h->dev.struct_size = sizeof(MpDevOptions);
+    h->cfg.dev = &h->dev;
+  }
+  if (cfg->num_worlds <= 0)
+    return fail(MP_ERR_INVALID, "mp_create: num_worlds must be positive");
+  if (cfg->unfused < 0 || cfg->unfused > 2)
+    return fail(MP_ERR_INVALID, "mp_create: MpConfig.unfused must be 0, 1 or 2 (got %d)", cfg->unfused);
+  if (cfg->world_pool != 0 && cfg->world_pool != 1 && cfg->world_pool != 2 && cfg->world_pool != 4 &&
+      cfg->world_pool != 8)
+    return fail(MP_ERR_INVALID, "mp_create: MpConfig.world_pool must be 0, 1, 2, 4 or 8 (got %d)",
+                cfg->world_pool);
+  // the whole pack is decoded and checked on the host (pack_decode.hip) before a device is touched
+  const int32_t* hdr = nullptr;
+  if (int rc = check_header(pack, pack_len, *cfg, &hdr)) return rc;
+  h->pack.assign((const uint8_t*)pack, (const uint8_t*)pack + pack_len);
+  if (int rc = apply_roles(h->pack, *cfg)) return rc;
+  if (int rc = decode_pack(h->pack, *cfg, h->pack.data(), &h->d)) return rc;
+  if (cfg->world_pool > 1 && h->d.t.sprite_size != 8)   // (the pooled image of a cell is 8/k pixels square)
+    return fail(MP_ERR_UNSUPPORTED, "mp_create: MpConfig.world_pool needs 8 x 8 sprites (the pack's are %d x %d)",
+                h->d.t.sprite_size, h->d.t.sprite_size);
+  return MP_OK;
+}
+
+// MpKernelVariant::fields: the C literal of a folded member's value, by its type.
+void literal(std::string* out, int32_t v) { *out += std::to_string(v); }
+void literal(std::string* out, uint32_t v) { *out += std::to_string(v) + "u"; }
+void literal(std::string* out, uint64_t v) {
+  char b[32];
+  snprintf(b, sizeof b, "0x%llxull", (unsigned long long)v);
+  *out += b;
+}
+void literal(std::string* out, double v) {
+  char b[48];
+  snprintf(b, sizeof b, "%a", v);   // (hexadecimal: exact)
+  *out += b;
 }
 
 }  // namespace
@@ -1011,33 +1090,11 @@ int mp_create(const void* pack, uint64_t pack_len, const MpConfig* cfg,
               MpEngine** out) {
   if (!out) return fail(MP_ERR_INVALID, "mp_create: out is NULL");
   *out = nullptr;
-  // (an MpConfig of the ABI-8 layout, which ends before world_pool, reads as world_pool = 1)
-  if (!cfg || (cfg->struct_size != sizeof(MpConfig) && cfg->struct_size != offsetof(MpConfig, world_pool)))
-    return fail(MP_ERR_INVALID, "mp_create: bad MpConfig (struct_size)");
-  MpConfig cfg_copy = {};
-  memcpy(&cfg_copy, cfg, cfg->struct_size);
-  if (cfg->struct_size < sizeof(MpConfig)) cfg_copy.world_pool = 1;
-  cfg = &cfg_copy;
-  if (cfg->dev && cfg->dev->struct_size != sizeof(MpDevOptions))
-    return fail(MP_ERR_INVALID, "mp_create: bad MpDevOptions (struct_size)");
-  if (cfg->num_worlds <= 0)
-    return fail(MP_ERR_INVALID, "mp_create: num_worlds must be positive");
-  if (cfg->unfused < 0 || cfg->unfused > 2)
-    return fail(MP_ERR_INVALID, "mp_create: MpConfig.unfused must be 0, 1 or 2 (got %d)", cfg->unfused);
-  if (cfg->world_pool != 0 && cfg->world_pool != 1 && cfg->world_pool != 2 && cfg->world_pool != 4 &&
-      cfg->world_pool != 8)
-    return fail(MP_ERR_INVALID, "mp_create: MpConfig.world_pool must be 0, 1, 2, 4 or 8 (got %d)",
-                cfg->world_pool);
-  // the whole pack is decoded and checked on the host (pack_decode.hip) before a device is touched
-  const int32_t* hdr = nullptr;
-  if (int rc = check_header(pack, pack_len, *cfg, &hdr)) return rc;
-  std::vector<uint8_t> copy((const uint8_t*)pack, (const uint8_t*)pack + pack_len);
-  if (int rc = apply_roles(copy, *cfg)) return rc;
-  DecodedPack d;
-  if (int rc = decode_pack(copy, *cfg, copy.data(), &d)) return rc;
-  if (cfg->world_pool > 1 && d.t.sprite_size != 8)   // (the pooled image of a cell is 8/k pixels square)
-    return fail(MP_ERR_UNSUPPORTED, "mp_create: MpConfig.world_pool needs 8 x 8 sprites (the pack's are %d x %d)",
-                d.t.sprite_size, d.t.sprite_size);
+  HostStage h;
+  if (int rc = host_stage(pack, pack_len, cfg, &h)) return rc;
+  cfg = &h.cfg;
+  std::vector<uint8_t>& copy = h.pack;
+  DecodedPack& d = h.d;
 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -1503,7 +1560,40 @@ uint64_t mp_snapshot_bytes(const MpEngine* e) {
   return e ? (uint64_t)e->N * e->t.world_stride : 0;
 }
 
+static_assert(sizeof(MpKernelVariant) != sizeof(MpWorldStates) && sizeof(MpKernelVariant) != sizeof(MpStepMany),
+              "mp_snapshot / mp_restore tell their requests apart by size");
+// An MpKernelVariant request (carried by mp_snapshot; `e` may be NULL: the host-only question).
+static int kernel_variant(const MpEngine* e, MpKernelVariant* r) {
+  if (r->struct_size != sizeof(MpKernelVariant))
+    return fail(MP_ERR_INVALID, "MpKernelVariant: struct_size %u, expected %zu", r->struct_size, sizeof(MpKernelVariant));
+  if (e) { r->variant = e->sub.stock; return MP_OK; }
+  char* fields = r->fields;
+  const uint64_t fields_cap = r->fields_cap;
+  HostStage h;
+  if (int rc = host_stage(r->pack, r->pack_len, r->cfg, &h)) return rc;
+  if (fields) {
+    if (h.d.sub.substrate != MPK_SUBSTRATE_CLEAN_UP)
+      return fail(MP_ERR_UNSUPPORTED, "MpKernelVariant: no stock kernels for this level");
+    std::string text;
+#define MP_FIELD_T(f) text += "t " #f " "; literal(&text, h.d.t.f); text += "\n";
+#define MP_FIELD_C(f) text += "c " #f " "; literal(&text, h.d.sub.cu.f); text += "\n";
+    MP_STOCK_DEV_FIELDS(MP_FIELD_T)
+    MP_STOCK_CLEAN_UP_FIELDS(MP_FIELD_C)
+#undef MP_FIELD_T
+#undef MP_FIELD_C
+    text += "hash ";
+    literal(&text, pack_hash(h.pack));
+    text += "\n";
+    if (text.size() + 1 > fields_cap)
+      return fail(MP_ERR_INVALID, "MpKernelVariant: fields needs %zu bytes", text.size() + 1);
+    memcpy(fields, text.c_str(), text.size() + 1);
+  }
+  r->variant = select_kernels(h.pack, h.d, h.cfg.dev);
+  return MP_OK;
+}
+
 int mp_snapshot(MpEngine* e, void* buf, uint64_t bytes) {
+  if (buf && bytes == sizeof(MpKernelVariant)) return kernel_variant(e, (MpKernelVariant*)buf);
   if (e && buf && bytes == sizeof(MpWorldStates)) return world_states(e, (MpWorldStates*)buf, false);
   if (!e || !buf || bytes != mp_snapshot_bytes(e))
     return fail(MP_ERR_INVALID, "mp_snapshot: bad buffer");

@@ -141,6 +141,9 @@ ABI_SYMBOLS = (
     "mp_bind_output_ring", "mp_set_retired_va_limit",
     "mp_torch_alloc", "mp_torch_free", "mp_box_fill")
 
+# MpKernelVariant.variant: the frame kernels an engine runs
+KERNEL_GENERIC, KERNEL_STOCK = 0, 1
+
 
 class MpDevOptions(ctypes.Structure):
   """Test / development overrides of the launch plan (include/mp_engine.h);
@@ -149,7 +152,7 @@ class MpDevOptions(ctypes.Structure):
       "batch_worlds", "waves", "feeders", "max_groups", "scratch_cells",
       "no_composite_cache", "max_composites", "verbose", "late_feeder_prio",
       "ring_batches", "static_pct", "world_waves", "store_sc1", "head", "no_next_orders",
-      "record_pad", "pace", "team")]
+      "record_pad", "pace", "team", "generic_kernel")]
 
 
 class MpConfig(ctypes.Structure):
@@ -199,6 +202,15 @@ class MpBoxFill(ctypes.Structure):
 
 # World-state requests (include/mp_engine.h: MpWorldStates), carried by mp_snapshot / mp_restore
 MP_STATES_FINGERPRINT, MP_STATES_SAVE, MP_STATES_LOAD = 1, 2, 3
+
+
+class MpKernelVariant(ctypes.Structure):
+  """Which frame kernels an engine runs / a pack would get (include/mp_engine.h), carried by
+  mp_snapshot."""
+  _fields_ = [("struct_size", ctypes.c_uint32), ("variant", ctypes.c_int32),
+              ("pack", ctypes.c_void_p), ("pack_len", ctypes.c_uint64),
+              ("cfg", ctypes.POINTER(MpConfig)), ("fields", ctypes.c_void_p),
+              ("fields_cap", ctypes.c_uint64)]
 
 
 class MpWorldStates(ctypes.Structure):
@@ -359,6 +371,34 @@ def load_library(build: bool = True) -> ctypes.CDLL:
   return L
 
 
+def kernel_variant(pack_bytes: bytes, *, num_players: int = 0,
+                   dev: Optional[Dict[str, int]] = None) -> int:
+  """KERNEL_STOCK if an engine created on this pack would run the frame kernels that have the
+  committed pack's constants compiled in, KERNEL_GENERIC otherwise — mp_create's own selection,
+  made on the host (an MpKernelVariant request without an engine: no GPU needed)."""
+  return pack_fields(pack_bytes, num_players=num_players, dev=dev)[0]
+
+
+def pack_fields(pack_bytes: bytes, *, num_players: int = 0, dev: Optional[Dict[str, int]] = None,
+                want_fields: bool = False):
+  """(variant, text): `kernel_variant`'s answer and, with `want_fields`, the pack's value of every
+  scalar a stock kernel folds as "<group> <member> <C literal>" lines (tools/make_stock_header.py)."""
+  L = load_library()
+  cfg = MpConfig(ctypes.sizeof(MpConfig), 0, 1, 1, 0, 0, None, int(num_players))
+  if dev:
+    opts = MpDevOptions(ctypes.sizeof(MpDevOptions), max_composites=-1)
+    for k, v in dev.items():
+      setattr(opts, k, int(v))
+    cfg.dev = ctypes.pointer(opts)
+  buf = ctypes.create_string_buffer(pack_bytes, len(pack_bytes))
+  out = ctypes.create_string_buffer(1 << 16) if want_fields else None
+  req = MpKernelVariant(ctypes.sizeof(MpKernelVariant), 0, ctypes.addressof(buf), len(pack_bytes),
+                        ctypes.pointer(cfg), ctypes.addressof(out) if out else None,
+                        len(out) if out else 0)
+  _check(L, L.mp_snapshot(None, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpKernelVariant)")
+  return req.variant, (out.value.decode() if out else "")
+
+
 def _check(L, rc: int, what: str):
   if rc == 0:
     return
@@ -494,7 +534,17 @@ class Engine:
             "owned_batches": info.plan_owned_batches, "pooled_batches": info.plan_pooled_batches,
             "workgroups": info.plan_groups, "sc1_stores": info.plan_store_sc1,
             "feeders": info.plan_feeders, "waves": info.plan_waves, "pace": info.plan_pace,
-            "xcd_teams": info.plan_team, "late_feeder_priority": info.plan_late_priority}
+            "xcd_teams": info.plan_team, "late_feeder_priority": info.plan_late_priority,
+            # 1: the stepping launches of the full views run the kernels with the committed pack's
+            # constants compiled in (MpKernelVariant)
+            "stock": self._kernel_variant()}
+
+  def _kernel_variant(self) -> int:
+    req = MpKernelVariant(ctypes.sizeof(MpKernelVariant))
+    # (an older build under MP_ENGINE_LIB does not know the request: generic kernels only)
+    if self._L.mp_snapshot(self._h, ctypes.addressof(req), ctypes.sizeof(req)) != 0:
+      return KERNEL_GENERIC
+    return int(req.variant)
 
   # -- lifetime ------------------------------------------------------------
   def close(self):
