@@ -575,6 +575,64 @@ typedef struct {
   uint64_t per_step_bytes[5];  /* distance between two steps' rows of each */
 } MpStepMany;
 
+/* Action sequences with per-step rows of the observations: an MpStepMany request that may ask for
+ * rows of ANY non-pixel kind.  It rides mp_restore in the same way, by its own size: `bytes` =
+ * sizeof(MpStepTrajectory), `host_buf` a HOST MpStepTrajectory with struct_size set to it.
+ * include/mp_step_trajectory.h wraps it as an inline C function.  An MpStepMany request keeps
+ * doing exactly what it does.
+ *
+ * Everything MpStepMany promises holds (its points 1, 3, 4 and 5: records, counters, in-place and
+ * bound buffers, a bound LAYER, bound pixel views and the one ring slot hold what they hold after
+ * K single steps; a world never reset writes nothing; one submission).  rows[0 .. num_rows) is a
+ * HOST array naming each wanted kind once, among
+ *   MP_OBS_REWARD, READY_TO_SHOOT, AUX0, STEP_TYPE, DISCOUNT, COLLECTIVE_REWARD, POSITION,
+ *   ORIENTATION, EVENTS, AUX1..AUX4, ZAP_MATRIX, LAYER, INVENTORY, INTERACTION_INVENTORIES,
+ *   MATRIX_CUMULANTS, INTERACTION_REWARDS,
+ * with `rows` the device buffer of row 0, laid out as the kind's [N]... behind a leading K, and
+ * `step_bytes` the distance between two rows: at least one step's block (mp_obs_bytes) and a
+ * multiple of the element size (4 for STEP_TYPE, POSITION, ORIENTATION and LAYER, 16 for EVENTS,
+ * 8 otherwise), to which the buffer is aligned too; larger distances are the columns of a shared
+ * [K][N total] tensor.  Row k of kind X is, byte for byte, what the in-place (or bound) buffer of
+ * X holds after the k-th call of the loop of single steps started from the same engine state
+ * (EVENTS: the header row and the rows it counts).  For LAYER it is what a bound LAYER buffer
+ * would hold after step k; LAYER need not be bound, and a bound one gets the final state as ever.
+ *
+ * The carry rule.  A single step leaves a kind's buffer as it was wherever it does not write it,
+ * and the rows show exactly that: where step k writes nothing row k equals row k - 1, and row 0
+ * equals the buffer as it was before the request.  A frozen world (done, auto_reset = 0) writes
+ * REWARD, COLLECTIVE_REWARD, STEP_TYPE, DISCOUNT and the EVENTS header only, so its
+ * READY_TO_SHOOT, AUX0, POSITION, ORIENTATION, inventories and debug kinds repeat what the
+ * episode's last step left; MP_OBS_INTERACTION_REWARDS and MP_OBS_INTERACTION_INVENTORIES change
+ * at an interaction and are carried from step to step (and over a reset, as far as a reset leaves
+ * them) until the next one.  LAYER is a function of the record and is written at every step of a
+ * started world.
+ *
+ * Refused before any launch, the engine left as it was: everything MpStepMany refuses (its point
+ * 6, with this request's name); num_rows < 0, or > 0 with rows NULL; a kind outside
+ * [0, MP_OBS_KINDS) or named twice, or a NULL buffer: MP_ERR_INVALID; a pixel kind (MP_OBS_RGB,
+ * MP_OBS_RGB_POOL*, MP_OBS_WORLD_RGB): MP_ERR_INVALID — intermediate frames are what mp_step with
+ * a rollout ring (mp_bind_output_ring) draws; a kind the substrate does not produce
+ * (mp_obs_bytes == 0), or a debug kind (AUX1..4, ZAP_MATRIX, MATRIX_CUMULANTS) that is not being
+ * produced (neither bound nor MpConfig.debug_observations; mp_observe's rule): MP_ERR_UNSUPPORTED;
+ * a step_bytes or an alignment as above, a buffer that is not device memory of the engine's
+ * device or whose extent [rows, rows + (steps - 1) * step_bytes + block) does not lie inside one
+ * allocation: MP_ERR_INVALID. */
+typedef struct {
+  int32_t kind;                /* MpObsKind */
+  int32_t reserved;
+  void* rows;                  /* device: row 0 */
+  uint64_t step_bytes;         /* distance between two rows */
+} MpStepRow;
+typedef struct {
+  uint32_t struct_size;        /* = sizeof(MpStepTrajectory) */
+  int32_t steps;               /* K */
+  int32_t fields;              /* 0: discrete ids [K][N][P]; 1: raw fields [K][N][P][A] */
+  int32_t num_rows;
+  const int32_t* actions;      /* device */
+  uint64_t actions_step_bytes; /* 0: the same block every step */
+  const MpStepRow* rows;       /* HOST array [num_rows] */
+} MpStepTrajectory;
+
 /* Throughput / event counters accumulated on device since creation
  * (synchronises).  These are what the multi-GPU bench all-reduces. */
 enum {

@@ -13,6 +13,7 @@
 #include "step_matrix.h"
 #include "step_territory.h"
 #include "step_load.h"
+#include "step_many.h"
 
 int step_lds_bytes(const DevTables& t, const SubstrateTables& s, int wpg);   // (step_kernels.hip)
 int step_worlds_per_group(const DevTables& t, const SubstrateTables& s);
@@ -47,9 +48,41 @@ __device__ inline T* row_of(uint8_t* base, long long bytes, int k, T* in_place) 
 // end is step K's.  The five per-step kinds go to row k of the caller's buffers where given; the
 // wave then copies row K - 1 to the in-place buffers, every lane reading back exactly the words
 // it stored itself (program order of one thread: no fence, no second launch).
-template <class Tables, class Sites>
+//
+// Rows (an MpStepTrajectory request, `r`): per-step rows of the other non-pixel kinds, row k =
+// what the in-place buffer of the kind holds after step k of the loop of single steps.  That
+// buffer KEEPS its value where a step does not write the kind, so the rows carry it:
+//  * r.fin (READY_TO_SHOOT, AUX0, POSITION, ORIENTATION) are retargeted to row k like the five.
+//    finish() writes them on every path but the frozen one (dispatch(): done without
+//    auto-reset), element w * P + lane from lane `lane` (the_matrix's second store of READY
+//    too).  Before a frozen step each lane copies its own element from row k - 1 (k = 0: from
+//    the in-place buffer, stored by an earlier launch) to row k: it loads what it stored
+//    itself, by finish() or by this copy one step earlier, so program order of one thread
+//    covers it, and a step that is not frozen pays nothing.  Row K - 1 goes to the in-place
+//    buffers in the end, lane by lane, as for the five.
+//  * r.level: a level writes these where and when its rules say (INTERACTION_REWARDS from the
+//    two lanes of an interaction, the zap matrix from the lane of the beam cell that hit), so
+//    the step keeps writing the in-place buffer and the wave copies the world's slice of it to
+//    row k after the step.  Here a lane does load words that OTHER lanes of its wave stored
+//    during the step.  wsync() between the step and the loads orders them: a release and an
+//    acquire fence at workgroup scope around a wave barrier.  Workgroup scope is enough, since
+//    the stores and the loads come from one wave on one CU, and on gfx950 it costs no
+//    instruction: outside threadgroup-split mode the compiler lowers these fences to a wait for
+//    LDS only, because a CU's write-through vector L1 performs the vector memory instructions
+//    of a wave in the order they were issued, so a load issued behind a store of the same CU
+//    sees it (no L1 invalidate, no L2 write-back: nothing another CU could observe, tens of
+//    cycles where the agent-scope forms cost microseconds).  The fences are still needed: they
+//    are what keeps the compiler from moving the loads.  What the copy does cost is its own
+//    s_waitcnt before the stores to row k: vmcnt counts loads and stores in one order, so the
+//    loaded words arrive behind the record's write-back of finish().  Only a request that names
+//    one of these kinds pays that.  The loop-top wsync() keeps the next step's stores to the
+//    in-place buffer behind these loads.
+//  * r.layer: write_layer() on row k from the record in LDS after every step of a started
+//    world, a frozen one included (the same bytes again).
+// Which kinds are asked for is wave-uniform: every branch on it is a scalar one.
+template <bool Rows, class Tables, class Sites>
 __device__ inline void run_many(const DevTables& t, const Tables& c, const StepArgs& args0,
-                                const ManyArgs& m, int extra) {
+                                const ManyArgs& m, const StepRows* rp, int extra) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
@@ -89,6 +122,27 @@ __device__ inline void run_many(const DevTables& t, const Tables& c, const StepA
     int lane_k = lane;
     asm volatile("" : "+v"(lane_k));
     wd.lane = lane_k;
+    if constexpr (Rows) {
+      const StepRows& r = *rp;
+      const WorldTail* tl = reinterpret_cast<const WorldTail*>(wd.rec + t.grid_pad);
+      // (dispatch()'s frozen path, which this step is going to take)
+      const bool frozen = __builtin_amdgcn_readfirstlane((int)(tl->started && tl->done)) && !args0.auto_reset;
+      const StepOutputs prev = args.out;   // row k - 1, or the in-place buffers
+      args.out.ready = row_of(r.fin[0], r.fin_bytes[0], k, args0.out.ready);
+      args.out.aux0 = row_of(r.fin[1], r.fin_bytes[1], k, args0.out.aux0);
+      args.out.position = row_of(r.fin[2], r.fin_bytes[2], k, args0.out.position);
+      args.out.orientation = row_of(r.fin[3], r.fin_bytes[3], k, args0.out.orientation);
+      if (frozen && lane_k < t.P) {
+        const size_t o = (size_t)w * t.P + lane_k;
+        if (r.fin[0]) args.out.ready[o] = prev.ready[o];
+        if (r.fin[1]) args.out.aux0[o] = prev.aux0[o];
+        if (r.fin[2]) {
+          args.out.position[o * 2 + 0] = prev.position[o * 2 + 0];
+          args.out.position[o * 2 + 1] = prev.position[o * 2 + 1];
+        }
+        if (r.fin[3]) args.out.orientation[o] = prev.orientation[o];
+      }
+    }
     args.out.reward = row_of(m.row[0], m.row_bytes[0], k, args0.out.reward);
     args.out.collective = row_of(m.row[1], m.row_bytes[1], k, args0.out.collective);
     args.out.step_type = row_of(m.row[2], m.row_bytes[2], k, args0.out.step_type);
@@ -97,6 +151,27 @@ __device__ inline void run_many(const DevTables& t, const Tables& c, const StepA
     const Action act = lookup_action(t, wd, act_id, args0.mode);
     step_world(t, c, sites, wd, act, args);
     act_id = next_id;
+    if constexpr (Rows) {
+      const StepRows& r = *rp;
+      if (r.layer || r.n_level) {
+        wsync();   // the record in LDS is final; the step's stores to the level kinds come before the loads below
+        const WorldTail* tl = reinterpret_cast<const WorldTail*>(wd.rec + t.grid_pad);
+        if (__builtin_amdgcn_readfirstlane((int)tl->started)) {
+          for (int i = 0; i < r.n_level; ++i) {
+            const long long n = r.level[i].count;
+            const double* src = r.level[i].src + (size_t)w * n;
+            double* dst = reinterpret_cast<double*>(r.level[i].row + (long long)k * r.level[i].bytes) + (size_t)w * n;
+            for (int j = lane_k; j < n; j += 64) dst[j] = src[j];
+          }
+          if (r.layer) {
+            StepOutputs lo = args0.out;
+            lo.layer = reinterpret_cast<int32_t*>(r.layer + (long long)k * r.layer_bytes);
+            lo.layer_lut = r.layer_lut;
+            write_layer(t, wd.rec, lo, w, lane_k);
+          }
+        }
+      }
+    }
   }
   wsync();
   const WorldTail* tail = reinterpret_cast<const WorldTail*>(wd.rec + t.grid_pad);
@@ -118,6 +193,18 @@ __device__ inline void run_many(const DevTables& t, const Tables& c, const StepA
       n = n < 0 ? 0 : n > MP_EVENT_ROWS - 1 ? MP_EVENT_ROWS - 1 : n;
       for (int i = lane; i < n; i += 64) dst[1 + i] = src[1 + i];   // (row 1 + i: lane i % 64's own store)
     }
+    if constexpr (Rows) {
+      const StepRows& r = *rp;
+      if (lane < t.P) {   // (element o: this lane's own store, by finish() or by the frozen steps' copy)
+        if (r.fin[0]) args0.out.ready[o] = args.out.ready[o];
+        if (r.fin[1]) args0.out.aux0[o] = args.out.aux0[o];
+        if (r.fin[2]) {
+          args0.out.position[o * 2 + 0] = args.out.position[o * 2 + 0];
+          args0.out.position[o * 2 + 1] = args.out.position[o * 2 + 1];
+        }
+        if (r.fin[3]) args0.out.orientation[o] = args.out.orientation[o];
+      }
+    }
   }
   if (args0.out.layer) write_layer(t, wd.rec, args0.out, w, lane);
 }
@@ -125,7 +212,7 @@ __device__ inline void run_many(const DevTables& t, const Tables& c, const StepA
 #define MP_STEP_MANY_KERNEL(name, TablesT, SitesT, extra)                                            \
   __global__ __launch_bounds__(kWorldsPerGroup * 64) void name(DevTables t, TablesT c, StepArgs args, \
                                                                ManyArgs m) {                         \
-    run_many<TablesT, SitesT>(t, c, args, m, extra);                                                 \
+    run_many<false, TablesT, SitesT>(t, c, args, m, nullptr, extra);                                 \
   }
 MP_STEP_MANY_KERNEL(k_step_many_clean_up, CleanUpTables, CleanUpSites, 0)
 MP_STEP_MANY_KERNEL(k_step_many_commons, CommonsTables, CommonsSites, 0)
@@ -138,61 +225,71 @@ MP_STEP_MANY_KERNEL(k_step_many_matrix, MatrixTables, MatrixSites, 0)
 MP_STEP_MANY_KERNEL(k_step_many_territory, TerritoryTables, TerritorySites, extra_bytes(c))
 #undef MP_STEP_MANY_KERNEL
 
+// The same with the rows of an MpStepTrajectory request: a second family, so that an MpStepMany
+// request runs exactly the code it ran before there was one.
+#define MP_STEP_ROWS_KERNEL(name, TablesT, SitesT, extra)                                            \
+  __global__ __launch_bounds__(kWorldsPerGroup * 64) void name(DevTables t, TablesT c, StepArgs args, \
+                                                               ManyArgs m, StepRows r) {             \
+    run_many<true, TablesT, SitesT>(t, c, args, m, &r, extra);                                       \
+  }
+MP_STEP_ROWS_KERNEL(k_step_rows_clean_up, CleanUpTables, CleanUpSites, 0)
+MP_STEP_ROWS_KERNEL(k_step_rows_commons, CommonsTables, CommonsSites, 0)
+MP_STEP_ROWS_KERNEL(k_step_rows_coins, CoinsTables, CoinsSites, 0)
+MP_STEP_ROWS_KERNEL(k_step_rows_coop, CoopTables, CoopSites, 0)
+MP_STEP_ROWS_KERNEL(k_step_rows_gift, GiftTables, GiftSites, 0)
+MP_STEP_ROWS_KERNEL(k_step_rows_cook, CookTables, CookSites, 0)
+MP_STEP_ROWS_KERNEL(k_step_rows_mushroom, MushroomTables, MushroomSites, extra_bytes(c))
+MP_STEP_ROWS_KERNEL(k_step_rows_matrix, MatrixTables, MatrixSites, 0)
+MP_STEP_ROWS_KERNEL(k_step_rows_territory, TerritoryTables, TerritorySites, extra_bytes(c))
+#undef MP_STEP_ROWS_KERNEL
+
 }  // namespace
 
 // The K-step kernels may take all 160 KB of a CU's LDS, like the single-step ones.
 int prepare_step_many() {
-  const void* km[9] = {
-      reinterpret_cast<const void*>(&k_step_many_clean_up), reinterpret_cast<const void*>(&k_step_many_commons),
-      reinterpret_cast<const void*>(&k_step_many_coins), reinterpret_cast<const void*>(&k_step_many_territory),
-      reinterpret_cast<const void*>(&k_step_many_matrix), reinterpret_cast<const void*>(&k_step_many_coop),
-      reinterpret_cast<const void*>(&k_step_many_gift), reinterpret_cast<const void*>(&k_step_many_cook),
-      reinterpret_cast<const void*>(&k_step_many_mushroom)};
+  const void* km[18] = {
+#define MP_BOTH(level) reinterpret_cast<const void*>(&k_step_many_##level), reinterpret_cast<const void*>(&k_step_rows_##level)
+      MP_BOTH(clean_up), MP_BOTH(commons), MP_BOTH(coins), MP_BOTH(territory), MP_BOTH(matrix),
+      MP_BOTH(coop), MP_BOTH(gift), MP_BOTH(cook), MP_BOTH(mushroom)};
+#undef MP_BOTH
   for (const void* f : km)
     if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
       return 1;
   return 0;
 }
 
-// K steps of every world in one launch (MpStepMany): the geometry of launch_step.  `rows` and
-// `row_bytes` are the five per-step buffers (NULL: not asked for) and their step distances,
-// `actions_step` the distance between two steps' action blocks in int32.
+// K steps of every world in one launch (MpStepMany, MpStepTrajectory): the geometry of
+// launch_step.  `rows` and `row_bytes` are the five per-step buffers (NULL: not asked for) and
+// their step distances, `actions_step` the distance between two steps' action blocks in int32,
+// `more` the rows of the other kinds (NULL: an MpStepMany request, which runs k_step_many_*).
 void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
                       int steps, long long actions_step, void* const rows[5],
-                      const uint64_t row_bytes[5], hipStream_t stream) {
+                      const uint64_t row_bytes[5], const StepRows* more, hipStream_t stream) {
   ManyArgs m;
   m.steps = steps; m.actions_step = actions_step;
   for (int i = 0; i < 5; ++i) { m.row[i] = (uint8_t*)rows[i]; m.row_bytes[i] = (long long)row_bytes[i]; }
   const int wpg = step_worlds_per_group(t, s);
   const size_t lds = (size_t)step_lds_bytes(t, s, wpg);
   const dim3 grid((args.num_worlds + wpg - 1) / wpg), block(wpg * 64);
-  switch (s.substrate) {
-    case MPK_SUBSTRATE_CLEAN_UP:
-      hipLaunchKernelGGL(k_step_many_clean_up, grid, block, lds, stream, t, s.cu, args, m);
-      break;
-    case MPK_SUBSTRATE_COMMONS_HARVEST:
-      hipLaunchKernelGGL(k_step_many_commons, grid, block, lds, stream, t, s.ch, args, m);
-      break;
-    case MPK_SUBSTRATE_COINS:
-      hipLaunchKernelGGL(k_step_many_coins, grid, block, lds, stream, t, s.co, args, m);
-      break;
-    case MPK_SUBSTRATE_TERRITORY:
-      hipLaunchKernelGGL(k_step_many_territory, grid, block, lds, stream, t, s.tr, args, m);
-      break;
-    case MPK_SUBSTRATE_THE_MATRIX:
-      hipLaunchKernelGGL(k_step_many_matrix, grid, block, lds, stream, t, s.mx, args, m);
-      break;
-    case MPK_SUBSTRATE_COOP_MINING:
-      hipLaunchKernelGGL(k_step_many_coop, grid, block, lds, stream, t, s.cm, args, m);
-      break;
-    case MPK_SUBSTRATE_GIFT_REFINEMENTS:
-      hipLaunchKernelGGL(k_step_many_gift, grid, block, lds, stream, t, s.gr, args, m);
-      break;
-    case MPK_SUBSTRATE_COLLABORATIVE_COOKING:
-      hipLaunchKernelGGL(k_step_many_cook, grid, block, lds, stream, t, s.cc, args, m);
-      break;
-    case MPK_SUBSTRATE_EXTERNALITY_MUSHROOMS:
-      hipLaunchKernelGGL(k_step_many_mushroom, grid, block, lds, stream, t, s.em, args, m);
-      break;
+  StepRows r = {};
+  if (more) {   // (the level kinds' sources: this submission's buffers)
+    r = *more;
+    for (int i = 0; i < r.n_level; ++i) r.level[i].src = level_source(args.out, r.level[i].which);
   }
+#define MP_LAUNCH(level, tables)                                                                  \
+  if (more) hipLaunchKernelGGL(k_step_rows_##level, grid, block, lds, stream, t, tables, args, m, r); \
+  else hipLaunchKernelGGL(k_step_many_##level, grid, block, lds, stream, t, tables, args, m);    \
+  break;
+  switch (s.substrate) {
+    case MPK_SUBSTRATE_CLEAN_UP: MP_LAUNCH(clean_up, s.cu)
+    case MPK_SUBSTRATE_COMMONS_HARVEST: MP_LAUNCH(commons, s.ch)
+    case MPK_SUBSTRATE_COINS: MP_LAUNCH(coins, s.co)
+    case MPK_SUBSTRATE_TERRITORY: MP_LAUNCH(territory, s.tr)
+    case MPK_SUBSTRATE_THE_MATRIX: MP_LAUNCH(matrix, s.mx)
+    case MPK_SUBSTRATE_COOP_MINING: MP_LAUNCH(coop, s.cm)
+    case MPK_SUBSTRATE_GIFT_REFINEMENTS: MP_LAUNCH(gift, s.gr)
+    case MPK_SUBSTRATE_COLLABORATIVE_COOKING: MP_LAUNCH(cook, s.cc)
+    case MPK_SUBSTRATE_EXTERNALITY_MUSHROOMS: MP_LAUNCH(mushroom, s.em)
+  }
+#undef MP_LAUNCH
 }

@@ -244,6 +244,62 @@ class MpStepMany(ctypes.Structure):
               ("per_step", ctypes.c_void_p * 5), ("per_step_bytes", ctypes.c_uint64 * 5)]
 
 
+# ... with per-step rows of any non-pixel kind (MpStepTrajectory)
+class MpStepRow(ctypes.Structure):
+  _fields_ = [("kind", ctypes.c_int32), ("reserved", ctypes.c_int32), ("rows", ctypes.c_void_p),
+              ("step_bytes", ctypes.c_uint64)]
+
+
+class MpStepTrajectory(ctypes.Structure):
+  _fields_ = [("struct_size", ctypes.c_uint32), ("steps", ctypes.c_int32),
+              ("fields", ctypes.c_int32), ("num_rows", ctypes.c_int32),
+              ("actions", ctypes.c_void_p), ("actions_step_bytes", ctypes.c_uint64),
+              ("rows", ctypes.POINTER(MpStepRow))]
+
+
+# the kinds a step_many request may stack per step: every kind but the pixel ones
+STEP_ROW_KINDS = tuple(k for k in range(OBS_RGB_POOL8 + 1) if k not in PIXEL_KINDS)
+_STEP_MANY_KIND_OF = {"reward": OBS_REWARD, "collective_reward": OBS_COLLECTIVE_REWARD,
+                      "step_type": OBS_STEP_TYPE, "discount": OBS_DISCOUNT, "events": OBS_EVENTS}
+
+
+def check_step_rows(observations, *, steps: Optional[int] = None, shapes=None, out=None,
+                    taken=()) -> tuple:
+  """The kind, shape and dtype rules of Engine.step_many's observations=, without an engine:
+  returns the kinds as a tuple of ints.  Each is an OBS_* kind other than a pixel kind, named
+  once (`taken`: kinds the call already stacks under keep= / events=).  With `steps` = K,
+  `shapes` (kind -> (shape, dtype), as Engine.shapes) and `out` (kind -> tensor) every given
+  tensor must have the kind's dtype and shape (K,) + shape, with steps that do not overlap.
+  ValueError otherwise."""
+  kinds = []
+  for kind in observations:
+    if isinstance(kind, bool) or not isinstance(kind, (int, np.integer)):
+      raise ValueError(f"step_many: observations= takes OBS_* kinds (got {kind!r})")
+    kind = int(kind)
+    if kind in PIXEL_KINDS:
+      raise ValueError(f"step_many: kind {kind} is a pixel kind; a K-step launch draws no frames. "
+                       "Intermediate frames are what step() with a rollout ring "
+                       "(bind_ring) writes")
+    if kind not in STEP_ROW_KINDS:
+      raise ValueError(f"step_many: {kind} is no observation kind")
+    if kind in kinds or kind in taken:
+      raise ValueError(f"step_many: kind {kind} is named twice")
+    kinds.append(kind)
+  if out is not None and shapes is not None and steps is not None:
+    for kind in kinds:
+      buf = out.get(kind)
+      if buf is None:
+        continue
+      shape, dtype = shapes[kind]
+      want = (int(steps),) + tuple(int(d) for d in shape)
+      if (not hasattr(buf, "stride") or str(buf.dtype) != str(dtype) or
+          tuple(int(d) for d in buf.shape) != want):
+        raise ValueError(f"step_many: out[{kind}] must be a {dtype} tensor of shape {want} "
+                         f"(got {getattr(buf, 'dtype', type(buf))} {tuple(getattr(buf, 'shape', ()))})")
+      _step_distance(buf, f"out[{kind}]")
+  return tuple(kinds)
+
+
 def check_step_many(shape, dtype, num_worlds: int, num_players: int, *, repeat=None,
                     num_fields: Optional[int] = None) -> int:
   """The shape and dtype rules of Engine.step_many's actions, without an engine: returns K.
@@ -879,7 +935,7 @@ class Engine:
 
   def step_many(self, actions, *, repeat: Optional[int] = None, fields: bool = False,
                 keep=("reward", "collective_reward", "step_type", "discount"), events: bool = False,
-                out=None):
+                observations=(), out=None):
     """K steps of every world in ONE launch, bit-identical to K calls of step() (fields=True:
     step_fields()) with actions[0] .. actions[K - 1]; returns the per-step transitions.
 
@@ -891,8 +947,15 @@ class Engine:
     [K, N], "discount" f64 [K, N] to stack per step; events=True adds "events" i32
     [K, N, EVENT_ROWS, 4] (rows beyond a header's count are not written).  Returned as a dict
     by name; out= (a previous result) reuses its tensors.  The in-place / bound buffers hold
-    step K's values as after K steps; pixel views, LAYER and a ring slot are written once, from
-    the final state.  Enqueued on the current stream; does not synchronise."""
+    step K's values as after K steps; pixel views, a bound LAYER and a ring slot are written
+    once, from the final state.
+    observations: OBS_* kinds other than the pixel kinds (OBS_LAYER, OBS_READY_TO_SHOOT,
+    OBS_POSITION, OBS_INVENTORY, ...) to stack per step as well, each returned under its kind as
+    a tensor of shape (K,) + self.shapes[kind]: row k is what the kind's in-place (or bound)
+    buffer holds after step k of the loop of step(), carried from row k - 1 wherever step k
+    writes nothing (a frozen world; OBS_INTERACTION_REWARDS between interactions).  OBS_LAYER
+    need not be bound.  A debug kind must be produced (bound, or debug_observations).
+    Enqueued on the current stream; does not synchronise."""
     t = self._torch
     A = int(self.info.num_action_fields) if fields else None
     if isinstance(actions, t.Tensor) and actions.is_cuda:
@@ -915,6 +978,9 @@ class Engine:
     shapes = {"reward": ((K, self.N, self.P), t.float64), "collective_reward": ((K, self.N), t.float64),
               "step_type": ((K, self.N), t.int32), "discount": ((K, self.N), t.float64),
               "events": ((K, self.N, EVENT_ROWS, 4), t.int32)}
+    kinds = check_step_rows(observations, taken=[_STEP_MANY_KIND_OF[n] for n in names])
+    if kinds:
+      return self._step_trajectory(actions, astep, K, fields, names, shapes, kinds, out)
     self.use_current_stream()
     req = MpStepMany(ctypes.sizeof(MpStepMany), K, 1 if fields else 0, 0)
     req.actions = actions.data_ptr()
@@ -934,6 +1000,34 @@ class Engine:
       result[name] = buf
     _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
            "mp_restore (MpStepMany)")
+    self._state_args = (actions, result)   # (kept until the next call: the launch may not have run yet)
+    return result
+
+  def _step_trajectory(self, actions, astep, K, fields, names, shapes, kinds, out):
+    """step_many with observations=: one MpStepTrajectory request (include/mp_engine.h)."""
+    t = self._torch
+    wanted = [(name, _STEP_MANY_KIND_OF[name]) + shapes[name] for name in names]
+    wanted += [(kind, kind, (K,) + tuple(self.shapes[kind][0]), self.shapes[kind][1]) for kind in kinds]
+    rows = (MpStepRow * len(wanted))()
+    result = {}
+    for i, (key, kind, shape, dtype) in enumerate(wanted):
+      buf = None if out is None else out.get(key)
+      if buf is None:
+        buf = t.empty(shape, dtype=dtype, device=self.device)
+      elif (not isinstance(buf, t.Tensor) or buf.dtype != dtype or tuple(buf.shape) != shape or
+            buf.device != self.device):
+        raise ValueError(f"step_many: out[{key!r}] must be a {dtype} tensor of shape {shape} on {self.device}")
+      rows[i].kind = kind
+      rows[i].rows = buf.data_ptr()
+      rows[i].step_bytes = _step_distance(buf, f"out[{key!r}]")
+      result[key] = buf
+    self.use_current_stream()
+    req = MpStepTrajectory(ctypes.sizeof(MpStepTrajectory), K, 1 if fields else 0, len(wanted))
+    req.actions = actions.data_ptr()
+    req.actions_step_bytes = astep
+    req.rows = rows
+    _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
+           "mp_restore (MpStepTrajectory)")
     self._state_args = (actions, result)   # (kept until the next call: the launch may not have run yet)
     return result
 

@@ -94,6 +94,36 @@ class StepManyResult(NamedTuple):
   timestep: TimeStep       # what the K-th step() would have returned
 
 
+class StepManyTrajectory(StepManyResult):
+  """What `Substrate.step_many` returns with `observations=`: the same six fields (it IS a
+  StepManyResult) plus `.observation`, a dict from each asked leaf's name to its per-step
+  device tensor [K, N, ...]: row k is the leaf after step k of the loop of `step`.  Like
+  `RolloutTimeStep.slot`, `.observation` is an attribute beside the tuple's fields: `_replace`
+  carries it; `_make`, slicing, `tuple()` and pickling give a plain tuple without it."""
+  observation: Any = None
+
+  def _replace(self, **kwargs):   # (a NamedTuple's _replace builds a fresh tuple: carry the dict)
+    out = super()._replace(**kwargs)
+    out.observation = self.observation
+    return out
+
+
+_FIVE_NAMES = {engine_lib.OBS_REWARD: "reward", engine_lib.OBS_COLLECTIVE_REWARD: "collective_reward",
+               engine_lib.OBS_STEP_TYPE: "step_type", engine_lib.OBS_DISCOUNT: "discount",
+               engine_lib.OBS_EVENTS: "events"}
+
+
+def _many_result(r, leaves, timestep):
+  """The result of a step_many call from the engine's dict `r` (`leaves`: asked name -> kind)."""
+  fields = (r["step_type"], r["reward"], r["discount"], r["collective_reward"], r.get("events"), timestep)
+  if not leaves:
+    return StepManyResult(*fields)
+  out = StepManyTrajectory(*fields)
+  # (a leaf that is one of the five per-step kinds is the tensor the call stacks anyway)
+  out.observation = {n: r[_FIVE_NAMES[k]] if k in _FIVE_NAMES else r[k] for n, k in leaves.items()}
+  return out
+
+
 def _many_actions(t, actions, repeat, N: int, P: int, num_actions: Optional[int]):
   """`actions` of a step_many call as the engine takes them: an int32 device tensor (as it is:
   it may be a column slice) or a host array; shape-checked, range-checked when asked."""
@@ -949,7 +979,33 @@ class Substrate:
         self._eng.step_fields(self._action_rows[a])
     self._submissions += 1
 
-  def step_many(self, actions, repeat: Optional[int] = None, events: bool = False) -> StepManyResult:
+  def step_leaves(self) -> Dict[str, int]:
+    """The leaves `step_many(observations=...)` can stack per step: this substrate's own
+    observation names other than the pixel ones, with their engine kinds."""
+    return {n: self._kinds[n] for n in self._obs if self._kinds[n] not in engine_lib.PIXEL_KINDS}
+
+  def _many_leaves(self, observations) -> Dict[str, int]:
+    """`observations` of a step_many call as name -> kind (True: every leaf of `step_leaves`)."""
+    offered = self.step_leaves()
+    if observations is True:
+      return offered
+    if observations is None or observations is False:
+      return {}
+    if isinstance(observations, str):
+      observations = (observations,)
+    leaves = {}
+    for n in observations:
+      if n not in offered:
+        what = ("a pixel leaf: step_many draws no intermediate frames (step with rollout_length=T does)"
+                if n in self._obs else "no leaf of this substrate")
+        raise ValueError(f"step_many: observation {n!r} is {what}; it can stack {sorted(offered)}")
+      if n in leaves:
+        raise ValueError(f"step_many: observation {n!r} is named twice")
+      leaves[n] = offered[n]
+    return leaves
+
+  def step_many(self, actions, repeat: Optional[int] = None, events: bool = False,
+                observations=()) -> StepManyResult:
     """K steps in ONE launch, bit-identical to K calls of `step` (batched substrates).
     `actions`: ints [K, N, P] (a device tensor is read in place; it may be a column slice
     [:, a:b] of a wider one), or one block [N, P] with `repeat=K`.  Returns the per-step
@@ -958,9 +1014,15 @@ class Substrate:
     `timestep`, the TimeStep the K-th `step` would have returned.  It is one submission: with
     `rollout_length=T` it writes one slot (the state after step K), and observations are
     those of the final state.  `observables()`: the action subject gets the whole sequence
-    once; the timestep and events subjects get the last step's."""
+    once; the timestep and events subjects get the last step's.
+    `observations`: names among this substrate's non-pixel leaves (`step_leaves()`: "LAYER",
+    "READY_TO_SHOOT", "INVENTORY", ...), or True for all of them: the result is then a
+    `StepManyTrajectory`, whose `.observation[name]` is that leaf of every step, [K, N, ...],
+    row k what `step` k would have left in the leaf (kept from the row before wherever a
+    step does not write it, e.g. while a world is frozen)."""
     if not self._batched:
       raise ValueError("step_many steps a batch of worlds: build the substrate with num_worlds > 1")
+    leaves = self._many_leaves(observations)
     t = self._eng._torch
     limit = None
     if self._check_device_actions:
@@ -968,15 +1030,19 @@ class Substrate:
     a, _ = _many_actions(t, actions, repeat, self._eng.N, self._eng.P, limit)
     self._observables.action.on_next(actions)
     self._eng.use_current_stream()
-    r = self._submit_many(a, repeat, events, None)
-    return StepManyResult(r["step_type"], r["reward"], r["discount"], r["collective_reward"],
-                          r.get("events"), self._emit(self._timestep()))
+    r = self._submit_many(a, repeat, events, None, leaves)
+    return _many_result(r, leaves, self._emit(self._timestep()))
 
-  def _submit_many(self, a, repeat, events, out):
-    """One K-step launch of the engine on actions `a` as `_many_actions` prepared them."""
+  def _submit_many(self, a, repeat, events, out, leaves=None):
+    """One K-step launch of the engine on actions `a` as `_many_actions` prepared them
+    (`leaves`: name -> kind of the observations to stack per step)."""
     t = self._eng._torch
+    more = {}
+    if leaves:
+      more["observations"] = tuple(dict.fromkeys(
+          k for k in leaves.values() if k not in _FIVE_NAMES))
     if self._action_rows is None:
-      r = self._eng.step_many(a, repeat=repeat, events=events, out=out)
+      r = self._eng.step_many(a, repeat=repeat, events=events, out=out, **more)
     else:
       # a custom table: its rows go to the engine as raw fields, as in `_submit`
       K = len(self._action_rows)
@@ -989,7 +1055,7 @@ class Substrate:
         if ((a < 0) | (a >= K)).any():
           raise ValueError(f"actions must be in [0, {K})")
         f = self._action_rows[a]
-      r = self._eng.step_many(f, repeat=repeat, fields=True, events=events, out=out)
+      r = self._eng.step_many(f, repeat=repeat, fields=True, events=events, out=out, **more)
     self._submissions += 1
     return r
 
@@ -1563,11 +1629,17 @@ class MixtureSubstrate:
     self._submissions += 1
     return self._emit(self._timestep())
 
-  def step_many(self, actions, repeat: Optional[int] = None, events: bool = False) -> StepManyResult:
+  def step_leaves(self) -> Dict[str, int]:
+    return self._members[0].step_leaves()
+
+  def step_many(self, actions, repeat: Optional[int] = None, events: bool = False,
+                observations=()) -> StepManyResult:
     """As `Substrate.step_many`, over the members: one K-step launch per member, each reading
     its columns [:, off_i:off_i + n_i] of `actions` and writing its columns of the shared
-    [K, N, ...] per-step tensors (nothing is copied or concatenated)."""
+    [K, N, ...] per-step tensors, those of `observations` included (nothing is copied or
+    concatenated)."""
     first = self._members[0]
+    leaves = first._many_leaves(observations)
     t = first._eng._torch
     limit = self.action_spec()[0].num_values if self._check_device_actions else None
     a, K = _many_actions(t, actions, repeat, self._N, self._P, limit)
@@ -1578,16 +1650,19 @@ class MixtureSubstrate:
            "discount": t.empty((K, self._N), dtype=t.float64, device=dev)}
     if events:
       out["events"] = t.empty((K, self._N, engine_lib.EVENT_ROWS, 4), dtype=t.int32, device=dev)
+    for kind in leaves.values():
+      if kind not in _FIVE_NAMES:
+        shape, dtype = first._eng.shapes[kind]
+        out[kind] = t.empty((K, self._N) + tuple(shape[1:]), dtype=dtype, device=dev)
     self._observables.action.on_next(actions)
     for m, off, n in zip(self._members, self._offsets, self._counts):
       m._eng.use_current_stream()
       cols = a[off:off + n] if repeat is not None else a[:, off:off + n]
       if repeat is not None and isinstance(cols, t.Tensor):
         cols = cols.contiguous()
-      m._submit_many(cols, repeat, events, {k: v[:, off:off + n] for k, v in out.items()})
+      m._submit_many(cols, repeat, events, {k: v[:, off:off + n] for k, v in out.items()}, leaves)
     self._submissions += 1
-    return StepManyResult(out["step_type"], out["reward"], out["discount"], out["collective_reward"],
-                          out.get("events"), self._emit(self._timestep()))
+    return _many_result(out, leaves, self._emit(self._timestep()))
 
   def _member_at(self, world: int):
     if not 0 <= world < self._N:
