@@ -26,8 +26,6 @@
 
 void launch_step(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
                  hipStream_t stream);
-int step_lds_bytes(const DevTables& t, const SubstrateTables& s, int wpg);
-int step_worlds_per_group(const DevTables& t, const SubstrateTables& s);
 int prepare_step();
 void launch_layer_view(const DevTables& t, const uint8_t* state, int32_t* out, int num_worlds,
                        hipStream_t stream);
@@ -359,11 +357,11 @@ void draw(MpEngine* e, uint8_t* rgb, uint8_t* wrgb, int pool_k = 1) {
   launch_frame(e->t, nullptr, args, rgb, wrgb, p, e->stream, rgb ? pool_k : 1, e->world_pool);
 }
 
-// (`many`: an MpStepMany request, checked by step_many — K steps by the K-step kernels, then the
-// draw-only launches of the unfused path; `more`: the other rows of an MpStepTrajectory request)
+// (`many`: a K-step request, checked by step_request — K steps by the K-step kernels, then the
+// draw-only launches of the unfused path; NULL: a single step)
 int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
            const uint8_t* bank = nullptr, const int32_t* src = nullptr, int bank_rows = 0,
-           const MpStepMany* many = nullptr, const StepRows* more = nullptr) {
+           const StepManyLaunch* many = nullptr) {
   stepk::StepArgs args;
   args.state = e->d_state; args.actions = actions; args.reset_mask = mask;
   args.bank = bank; args.src = src; args.bank_rows = bank_rows;
@@ -384,8 +382,7 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
   const int views = rgb && wrgb ? 2 : wrgb ? 1 : 0;
   if (many || (!rgb && !wrgb) || !e->fuse(rgb == nullptr)) {
     if (many)
-      launch_step_many(e->t, e->sub, args, many->steps, (long long)(many->actions_step_bytes / 4),
-                       many->per_step, many->per_step_bytes, more, e->stream);
+      launch_step_many(e->t, e->sub, args, *many, e->stream);
     else
       launch_step(e->t, e->sub, args, e->stream);
     if (rgb) draw(e, rgb, nullptr, pk);
@@ -1507,154 +1504,111 @@ static int world_states(MpEngine* e, MpWorldStates* r, bool restore) {
   }
 }
 
-// An MpStepMany request (include/mp_engine.h): what mp_restore does when `bytes` is
-// sizeof(MpStepMany).  Everything is checked here, before the one submission.  (`who`: the
-// request's name in the messages — an MpStepTrajectory request is checked as the MpStepMany of
-// its five kinds; `more`: its other rows, checked by step_trajectory.)
-static int step_many(MpEngine* e, const MpStepMany* r, const char* who = "MpStepMany",
-                     const StepRows* more = nullptr) {
-  if (!e || !r->actions) return fail(MP_ERR_INVALID, "%s: NULL engine or actions", who);
-  if (r->struct_size != sizeof(MpStepMany))
-    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", who, r->struct_size, sizeof(MpStepMany));
-  if (r->steps < 1 || r->steps > MP_STEP_MANY_MAX)
-    return fail(MP_ERR_INVALID, "%s: steps %d is outside [1, %d]", who, r->steps, MP_STEP_MANY_MAX);
-  if (r->fields != 0 && r->fields != 1)
-    return fail(MP_ERR_INVALID, "%s: fields %d is neither 0 (discrete ids) nor 1 (raw fields)", who, r->fields);
+// A K-step request (include/mp_engine.h: MpStepMany, MpStepTrajectory), whichever struct it came
+// in: `r` names the rows it wants, `who` is the request's own name in the messages.  Everything is
+// checked here, against kStepRowKinds (step_many.h) and mp_obs_bytes, before the one submission.
+static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r) {
+  if (!e || !r.actions) return fail(MP_ERR_INVALID, "%s: NULL engine or actions", who);
+  if (r.steps < 1 || r.steps > MP_STEP_MANY_MAX)
+    return fail(MP_ERR_INVALID, "%s: steps %d is outside [1, %d]", who, r.steps, MP_STEP_MANY_MAX);
+  if (r.fields != 0 && r.fields != 1)
+    return fail(MP_ERR_INVALID, "%s: fields %d is neither 0 (discrete ids) nor 1 (raw fields)", who, r.fields);
   if (!e->has_state)
     return fail(MP_ERR_INVALID, "%s: the engine has never been reset; there is nothing to step", who);
-  const uint64_t K = (uint64_t)r->steps, N = (uint64_t)e->N, P = (uint64_t)e->t.P;
-  const uint64_t ablock = N * P * (r->fields ? (uint64_t)e->t.nfields : 1u) * 4u;
-  if (r->actions_step_bytes != 0 && (r->actions_step_bytes < ablock || r->actions_step_bytes % 4))
+  const uint64_t K = (uint64_t)r.steps, N = (uint64_t)e->N, P = (uint64_t)e->t.P;
+  const uint64_t ablock = N * P * (r.fields ? (uint64_t)e->t.nfields : 1u) * 4u;
+  if (r.actions_step_bytes != 0 && (r.actions_step_bytes < ablock || r.actions_step_bytes % 4))
     return fail(MP_ERR_INVALID, "%s: actions_step_bytes %llu is neither 0 nor a multiple of 4 that "
-                "holds one step's block of %llu bytes", who, (unsigned long long)r->actions_step_bytes,
+                "holds one step's block of %llu bytes", who, (unsigned long long)r.actions_step_bytes,
                 (unsigned long long)ablock);
-  if ((uintptr_t)r->actions & 3)
-    return fail(MP_ERR_INVALID, "%s: actions %p is not 4-byte aligned", who, (const void*)r->actions);
-  static const char* const kName[5] = {"REWARD", "COLLECTIVE_REWARD", "STEP_TYPE", "DISCOUNT", "EVENTS"};
-  const uint64_t elem[5] = {8, 8, 4, 8, 16};
-  const uint64_t block[5] = {N * P * 8, N * 8, N * 4, N * 8, N * (uint64_t)MP_EVENT_ROWS * 16};
-  for (int i = 0; i < 5; ++i) {
-    if (!r->per_step[i]) continue;
-    if (r->per_step_bytes[i] < block[i] || r->per_step_bytes[i] % elem[i])
-      return fail(MP_ERR_INVALID, "%s: per_step_bytes of %s is %llu; it must be a multiple of %llu "
-                  "that holds one step's rows of %llu bytes", who, kName[i], (unsigned long long)r->per_step_bytes[i],
-                  (unsigned long long)elem[i], (unsigned long long)block[i]);
-    if ((uintptr_t)r->per_step[i] % elem[i])
-      return fail(MP_ERR_INVALID, "%s: the %s buffer %p is not %llu-byte aligned", who, kName[i],
-                  r->per_step[i], (unsigned long long)elem[i]);
-  }
+  if ((uintptr_t)r.actions & 3)
+    return fail(MP_ERR_INVALID, "%s: actions %p is not 4-byte aligned", who, (const void*)r.actions);
+  if (r.num_rows < 0 || r.num_rows > MP_OBS_KINDS || (r.num_rows > 0 && !r.rows))
+    return fail(MP_ERR_INVALID, "%s: num_rows %d with rows %p; every kind may be named once", who,
+                r.num_rows, (const void*)r.rows);
   HIP_TRY(hipSetDevice(e->device));
   char name[64];
   snprintf(name, sizeof name, "%s (actions)", who);
-  if (int rc = check_bank(e, r->actions, (K - 1) * r->actions_step_bytes + ablock, name))
-    return rc;
-  for (int i = 0; i < 5; ++i) {
-    if (!r->per_step[i]) continue;
-    snprintf(name, sizeof name, "%s (%s)", who, kName[i]);
-    if (int rc = check_bank(e, r->per_step[i], (K - 1) * r->per_step_bytes[i] + block[i], name)) return rc;
-  }
-  e->touched = true;
-  return submit(e, r->fields ? STEP_MODE_FIELDS : STEP_MODE_STEP, r->actions, nullptr, nullptr, nullptr, 0, r, more);
-}
-
-// An MpStepTrajectory request (include/mp_engine.h): what mp_restore does when `bytes` is
-// sizeof(MpStepTrajectory).  The rows of MpStepMany's five kinds become an MpStepMany, which
-// step_many checks and submits; the other kinds are checked here and handed on as StepRows
-// (none of them asked for: the request runs what an MpStepMany runs).
-static int step_trajectory(MpEngine* e, const MpStepTrajectory* r) {
-  static const char kWho[] = "MpStepTrajectory";
-  if (!e || !r->actions) return fail(MP_ERR_INVALID, "%s: NULL engine or actions", kWho);
-  if (r->struct_size != sizeof(MpStepTrajectory))
-    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r->struct_size, sizeof(MpStepTrajectory));
-  if (r->steps < 1 || r->steps > MP_STEP_MANY_MAX)
-    return fail(MP_ERR_INVALID, "%s: steps %d is outside [1, %d]", kWho, r->steps, MP_STEP_MANY_MAX);
-  if (r->num_rows < 0 || r->num_rows > MP_OBS_KINDS || (r->num_rows > 0 && !r->rows))
-    return fail(MP_ERR_INVALID, "%s: num_rows %d with rows %p; every kind may be named once", kWho,
-                r->num_rows, (const void*)r->rows);
-  MpStepMany m = {};
-  m.struct_size = sizeof m; m.steps = r->steps; m.fields = r->fields;
-  m.actions = r->actions; m.actions_step_bytes = r->actions_step_bytes;
-  StepRows more = {};
-  more.layer_lut = e->d_layer_lut;
+  if (int rc = check_bank(e, r.actions, (K - 1) * r.actions_step_bytes + ablock, name)) return rc;
+  StepManyLaunch l = {};
+  l.many.steps = r.steps;
+  l.many.actions_step = (long long)(r.actions_step_bytes / 4);
+  l.rows.layer_lut = e->d_layer_lut;
   const StepOutputs o = e->outputs();
-  const uint64_t K = (uint64_t)r->steps;
   bool seen[MP_OBS_KINDS] = {};
-  bool any = false;
-  HIP_TRY(hipSetDevice(e->device));
-  for (int i = 0; i < r->num_rows; ++i) {
-    const MpStepRow& row = r->rows[i];
+  for (int i = 0; i < r.num_rows; ++i) {
+    const MpStepRow& row = r.rows[i];
     const int kind = row.kind;
     if (kind < 0 || kind >= MP_OBS_KINDS)
-      return fail(MP_ERR_INVALID, "%s: rows[%d] names kind %d, which is no observation kind", kWho, i, kind);
+      return fail(MP_ERR_INVALID, "%s: rows[%d] names kind %d, which is no observation kind", who, i, kind);
     if (MpEngine::is_pixel_kind(kind))
       return fail(MP_ERR_INVALID, "%s: rows[%d] names pixel kind %d; a K-step launch draws no frames — "
                   "intermediate frames are what mp_step with a rollout ring (mp_bind_output_ring) writes",
-                  kWho, i, kind);
-    if (seen[kind]) return fail(MP_ERR_INVALID, "%s: kind %d is named twice", kWho, kind);
+                  who, i, kind);
+    const StepRowKind& k = kStepRowKinds.of[kind];
+    if (!k.name) return fail(MP_ERR_INVALID, "%s: kind %d has no per-step rows", who, kind);
+    if (seen[kind]) return fail(MP_ERR_INVALID, "%s: %s (kind %d) is named twice", who, k.name, kind);
     seen[kind] = true;
-    const uint64_t block = mp_obs_bytes(e, (MpObsKind)kind);
+    const uint64_t block = mp_obs_bytes(e, (MpObsKind)kind), elem = (uint64_t)k.elem;
     if (block == 0)
-      return fail(MP_ERR_UNSUPPORTED, "%s: this substrate has no observation %d", kWho, kind);
-    if (!row.rows) return fail(MP_ERR_INVALID, "%s: rows[%d] (kind %d) has no buffer", kWho, i, kind);
-    int five = -1, fin = -1, which = -1;
-    uint64_t elem = 8;
-    switch (kind) {
-      case MP_OBS_REWARD: five = 0; break;
-      case MP_OBS_COLLECTIVE_REWARD: five = 1; break;
-      case MP_OBS_STEP_TYPE: five = 2; break;
-      case MP_OBS_DISCOUNT: five = 3; break;
-      case MP_OBS_EVENTS: five = 4; break;
-      case MP_OBS_READY_TO_SHOOT: fin = 0; break;
-      case MP_OBS_AUX0: fin = 1; break;
-      case MP_OBS_POSITION: fin = 2; elem = 4; break;
-      case MP_OBS_ORIENTATION: fin = 3; elem = 4; break;
-      case MP_OBS_LAYER: elem = 4; break;
-      case MP_OBS_AUX1: case MP_OBS_AUX2: case MP_OBS_AUX3: case MP_OBS_AUX4:
-        which = kLevelDbg0 + (kind - MP_OBS_AUX1);
-        break;
-      case MP_OBS_ZAP_MATRIX: which = kLevelZapMatrix; break;
-      case MP_OBS_INVENTORY: which = kLevelInventory; break;
-      case MP_OBS_INTERACTION_INVENTORIES: which = kLevelInteraction; break;
-      case MP_OBS_MATRIX_CUMULANTS: which = kLevelCumulants; break;
-      case MP_OBS_INTERACTION_REWARDS: which = kLevelInteractionRewards; break;
-      default: return fail(MP_ERR_INVALID, "%s: kind %d has no per-step rows", kWho, kind);
-    }
-    if (five >= 0) {   // (step_many checks these)
-      m.per_step[five] = row.rows;
-      m.per_step_bytes[five] = row.step_bytes;
-      continue;
-    }
+      return fail(MP_ERR_UNSUPPORTED, "%s: this substrate has no observation %s (kind %d)", who, k.name, kind);
+    if (!row.rows) return fail(MP_ERR_INVALID, "%s: rows[%d] (%s) has no buffer", who, i, k.name);
     // (produced or not does not depend on the ring slot: a ring-bound kind is bound in every slot)
-    if (which >= 0 && !level_source(o, which))
+    if (k.place == kRowLevel && !level_source(o, kind))
       return fail(MP_ERR_UNSUPPORTED,
-                  "%s: observation %d is not produced (a debug observation: bind it, or create the "
-                  "engine with debug_observations)", kWho, kind);
+                  "%s: observation %s (kind %d) is not produced (a debug observation: bind it, or create "
+                  "the engine with debug_observations)", who, k.name, kind);
     if (row.step_bytes < block || row.step_bytes % elem)
-      return fail(MP_ERR_INVALID, "%s: step_bytes of kind %d is %llu; it must be a multiple of %llu that "
-                  "holds one step's rows of %llu bytes", kWho, kind, (unsigned long long)row.step_bytes,
+      return fail(MP_ERR_INVALID, "%s: step_bytes of %s is %llu; it must be a multiple of %llu that "
+                  "holds one step's rows of %llu bytes", who, k.name, (unsigned long long)row.step_bytes,
                   (unsigned long long)elem, (unsigned long long)block);
     if ((uintptr_t)row.rows % elem)
-      return fail(MP_ERR_INVALID, "%s: the buffer %p of kind %d is not %llu-byte aligned", kWho, row.rows,
-                  kind, (unsigned long long)elem);
-    char name[64];
-    snprintf(name, sizeof name, "%s (kind %d)", kWho, kind);
+      return fail(MP_ERR_INVALID, "%s: the %s buffer %p is not %llu-byte aligned", who, k.name, row.rows,
+                  (unsigned long long)elem);
+    snprintf(name, sizeof name, "%s (%s)", who, k.name);
     if (int rc = check_bank(e, row.rows, (K - 1) * row.step_bytes + block, name)) return rc;
-    any = true;
-    if (fin >= 0) {
-      more.fin[fin] = (uint8_t*)row.rows;
-      more.fin_bytes[fin] = (long long)row.step_bytes;
-    } else if (kind == MP_OBS_LAYER) {
-      more.layer = (uint8_t*)row.rows;
-      more.layer_bytes = (long long)row.step_bytes;
-    } else {
-      StepRows::Level& lv = more.level[more.n_level++];
-      lv.which = which;   // (launch_step_many resolves the buffer: a rollout ring moves it per submission)
-      lv.row = (uint8_t*)row.rows;
-      lv.bytes = (long long)row.step_bytes;
-      lv.count = (long long)(block / 8 / (uint64_t)e->N);
+    uint8_t* const base = (uint8_t*)row.rows;
+    const long long bytes = (long long)row.step_bytes;
+    l.any_rows = l.any_rows || k.place != kRowFive;
+    switch (k.place) {
+      case kRowFive: l.many.row[k.slot] = base; l.many.row_bytes[k.slot] = bytes; break;
+      case kRowFin: l.rows.fin[k.slot] = base; l.rows.fin_bytes[k.slot] = bytes; break;
+      case kRowLayer: l.rows.layer = base; l.rows.layer_bytes = bytes; break;
+      default: {
+        StepRows::Level& lv = l.rows.level[l.rows.n_level++];
+        lv.which = kind;   // (launch_step_many resolves the buffer: a rollout ring moves it per submission)
+        lv.row = base;
+        lv.bytes = bytes;
+        lv.count = (long long)(block / 8 / N);
+      }
     }
   }
-  return step_many(e, &m, kWho, any ? &more : nullptr);
+  e->touched = true;
+  return submit(e, r.fields ? STEP_MODE_FIELDS : STEP_MODE_STEP, r.actions, nullptr, nullptr, nullptr, 0, &l);
+}
+
+// What mp_restore does when `bytes` is sizeof(MpStepMany): every non-NULL per_step[i] is one row
+// of the i-th of the five kinds.
+static int many_request(MpEngine* e, const MpStepMany& r) {
+  static const char kWho[] = "MpStepMany";
+  if (r.struct_size != sizeof(MpStepMany))
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpStepMany));
+  MpStepRow rows[5];
+  MpStepTrajectory t = {sizeof t, r.steps, r.fields, 0, r.actions, r.actions_step_bytes, rows};
+  for (int kind = 0; kind < MP_OBS_KINDS; ++kind) {
+    const StepRowKind& k = kStepRowKinds.of[kind];
+    if (k.place == kRowFive && r.per_step[k.slot])
+      rows[t.num_rows++] = {kind, 0, r.per_step[k.slot], r.per_step_bytes[k.slot]};
+  }
+  return step_request(e, kWho, t);
+}
+
+// ... and when it is sizeof(MpStepTrajectory): the request as it stands.
+static int trajectory_request(MpEngine* e, const MpStepTrajectory& r) {
+  static const char kWho[] = "MpStepTrajectory";
+  if (r.struct_size != sizeof(MpStepTrajectory))
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpStepTrajectory));
+  return step_request(e, kWho, r);
 }
 
 uint64_t mp_snapshot_bytes(const MpEngine* e) {
@@ -1715,12 +1669,12 @@ int mp_restore(MpEngine* e, const void* buf, uint64_t bytes) {
   if (buf && bytes == sizeof(MpStepMany)) {
     MpStepMany r;   // (read only: nothing is written back)
     memcpy(&r, buf, sizeof r);
-    return step_many(e, &r);
+    return many_request(e, r);
   }
   if (buf && bytes == sizeof(MpStepTrajectory)) {
     MpStepTrajectory r;   // (read only: nothing is written back)
     memcpy(&r, buf, sizeof r);
-    return step_trajectory(e, &r);
+    return trajectory_request(e, r);
   }
   if (!e || !buf || bytes != mp_snapshot_bytes(e))
     return fail(MP_ERR_INVALID, "mp_restore: bad buffer");

@@ -1,11 +1,63 @@
-// step_many.h — what the host hands the K-step kernels (step_many.hip) besides StepArgs.
+// step_many.h — what the host hands the K-step kernels (step_many.hip) besides StepArgs, and the
+// one description of a per-step row that the host's check (mp_engine.hip: step_request) reads.
 #ifndef MP_STEP_MANY_H_INTERNAL_
 #define MP_STEP_MANY_H_INTERNAL_
 
 #include "step_common.h"
 
-// The per-step rows of an MpStepTrajectory request beyond MpStepMany's five: row 0 of the
-// caller's buffer of each kind (NULL: not asked for) and the distance between two rows in bytes.
+// The geometry of the stand-alone step kernels (step_kernels.hip), which the K-step ones share.
+int step_lds_bytes(const DevTables& t, const SubstrateTables& s, int wpg);
+int step_worlds_per_group(const DevTables& t, const SubstrateTables& s);
+
+// Every kind a K-step launch can stack per step, by MpObsKind: its name in messages, its element
+// size (a row distance is a multiple of it, a buffer aligned to it) and where its rows go — slot
+// `slot` of ManyArgs::row (the five kinds of MpStepMany) or of StepRows::fin, StepRows::layer, or
+// one of StepRows::level.  name == NULL: no per-step rows (the pixel kinds).
+enum StepRowPlace { kRowFive = 1, kRowFin, kRowLayer, kRowLevel };
+struct StepRowKind {
+  const char* name;
+  int elem;
+  int place;
+  int slot;
+};
+struct StepRowKinds { StepRowKind of[MP_OBS_KINDS]; };
+constexpr StepRowKinds make_step_row_kinds() {
+  StepRowKinds k = {};
+  k.of[MP_OBS_REWARD] = {"REWARD", 8, kRowFive, 0};
+  k.of[MP_OBS_COLLECTIVE_REWARD] = {"COLLECTIVE_REWARD", 8, kRowFive, 1};
+  k.of[MP_OBS_STEP_TYPE] = {"STEP_TYPE", 4, kRowFive, 2};
+  k.of[MP_OBS_DISCOUNT] = {"DISCOUNT", 8, kRowFive, 3};
+  k.of[MP_OBS_EVENTS] = {"EVENTS", 16, kRowFive, 4};   // (rows are stored as int4)
+  k.of[MP_OBS_READY_TO_SHOOT] = {"READY_TO_SHOOT", 8, kRowFin, 0};
+  k.of[MP_OBS_AUX0] = {"AUX0", 8, kRowFin, 1};
+  k.of[MP_OBS_POSITION] = {"POSITION", 4, kRowFin, 2};
+  k.of[MP_OBS_ORIENTATION] = {"ORIENTATION", 4, kRowFin, 3};
+  k.of[MP_OBS_LAYER] = {"LAYER", 4, kRowLayer, 0};
+  k.of[MP_OBS_AUX1] = {"AUX1", 8, kRowLevel, 0};
+  k.of[MP_OBS_AUX2] = {"AUX2", 8, kRowLevel, 0};
+  k.of[MP_OBS_AUX3] = {"AUX3", 8, kRowLevel, 0};
+  k.of[MP_OBS_AUX4] = {"AUX4", 8, kRowLevel, 0};
+  k.of[MP_OBS_ZAP_MATRIX] = {"ZAP_MATRIX", 8, kRowLevel, 0};
+  k.of[MP_OBS_INVENTORY] = {"INVENTORY", 8, kRowLevel, 0};
+  k.of[MP_OBS_INTERACTION_INVENTORIES] = {"INTERACTION_INVENTORIES", 8, kRowLevel, 0};
+  k.of[MP_OBS_MATRIX_CUMULANTS] = {"MATRIX_CUMULANTS", 8, kRowLevel, 0};
+  k.of[MP_OBS_INTERACTION_REWARDS] = {"INTERACTION_REWARDS", 8, kRowLevel, 0};
+  return k;
+}
+constexpr StepRowKinds kStepRowKinds = make_step_row_kinds();
+
+// What a K-step launch gets besides StepArgs: args.actions is step 0's block, step k's lies
+// actions_step int32 further (0: the same block every step).  row[i] (NULL: not asked for) is
+// row 0 of the caller's per-step buffer of kind i, row_bytes[i] the distance between two rows.
+struct ManyArgs {
+  int steps;
+  long long actions_step;
+  uint8_t* row[5];          // REWARD, COLLECTIVE_REWARD, STEP_TYPE, DISCOUNT, EVENTS
+  long long row_bytes[5];
+};
+
+// The per-step rows of a request beyond MpStepMany's five: row 0 of the caller's buffer of each
+// kind (NULL: not asked for) and the distance between two rows in bytes.
 // Three groups, by who writes the kind in a step (step_many.hip: run_many):
 //   fin    the kinds finish() writes for every world that is reset or stepped, element
 //          w * P + lane from lane `lane`: READY_TO_SHOOT, AUX0, POSITION, ORIENTATION;
@@ -14,18 +66,19 @@
 //          from whichever lane it happens in (AUX1..4, ZAP_MATRIX, INVENTORY,
 //          INTERACTION_INVENTORIES, MATRIX_CUMULANTS, INTERACTION_REWARDS): all f64, `count`
 //          values a world, `src` the in-place (or bound) buffer the step writes.  The host
-//          names the buffer by `which` (kLevel*); launch_step_many resolves `src` from the
-//          StepOutputs of THIS submission (a rollout ring points them at a new slot each time).
-enum { kLevelDbg0 = 0, kLevelZapMatrix = 4, kLevelInventory, kLevelInteraction, kLevelCumulants,
-       kLevelInteractionRewards };
-inline const double* level_source(const StepOutputs& o, int which) {
-  switch (which) {
-    case kLevelZapMatrix: return o.zap_matrix;
-    case kLevelInventory: return o.inventory;
-    case kLevelInteraction: return o.interaction;
-    case kLevelCumulants: return o.cumulants;
-    case kLevelInteractionRewards: return o.interaction_rewards;
-    default: return o.dbg[which & 3];
+//          names the buffer by its kind (`which`: the MP_OBS_* value); launch_step_many resolves
+//          `src` from the StepOutputs of THIS submission (a rollout ring points them at a new
+//          slot each time).
+inline const double* level_source(const StepOutputs& o, int kind) {
+  switch (kind) {
+    case MP_OBS_AUX1: case MP_OBS_AUX2: case MP_OBS_AUX3: case MP_OBS_AUX4:
+      return o.dbg[kind - MP_OBS_AUX1];
+    case MP_OBS_ZAP_MATRIX: return o.zap_matrix;
+    case MP_OBS_INVENTORY: return o.inventory;
+    case MP_OBS_INTERACTION_INVENTORIES: return o.interaction;
+    case MP_OBS_MATRIX_CUMULANTS: return o.cumulants;
+    case MP_OBS_INTERACTION_REWARDS: return o.interaction_rewards;
+    default: return nullptr;
   }
 }
 
@@ -45,12 +98,17 @@ struct StepRows {
   } level[9];
 };
 
-// K steps of every world in one launch: `rows` / `row_bytes` are MpStepMany's five per-step
-// buffers (NULL: not asked for), `actions_step` the distance between two steps' action blocks in
-// int32.  more == NULL runs the kernels an MpStepMany request has always run.
+// One checked K-step request, as submit() hands it to launch_step_many: the five kinds' rows,
+// the rows of the other kinds, and whether there is one of those (any_rows == false runs the
+// kernels an MpStepMany request has always run).
+struct StepManyLaunch {
+  ManyArgs many;
+  StepRows rows;
+  bool any_rows;
+};
+
 void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
-                      int steps, long long actions_step, void* const rows[5],
-                      const uint64_t row_bytes[5], const StepRows* more, hipStream_t stream);
+                      const StepManyLaunch& l, hipStream_t stream);
 int prepare_step_many();
 
 #endif  // MP_STEP_MANY_H_INTERNAL_

@@ -15,24 +15,11 @@
 #include "step_load.h"
 #include "step_many.h"
 
-int step_lds_bytes(const DevTables& t, const SubstrateTables& s, int wpg);   // (step_kernels.hip)
-int step_worlds_per_group(const DevTables& t, const SubstrateTables& s);
-
 namespace {
 
 using namespace stepk;
 
 constexpr int kWorldsPerGroup = 4;   // (step_kernels.hip)
-
-// What a K-step launch gets besides StepArgs: args.actions is step 0's block, step k's lies
-// actions_step int32 further (0: the same block every step).  row[i] (NULL: not asked for) is
-// row 0 of the caller's per-step buffer of kind i, row_bytes[i] the distance between two rows.
-struct ManyArgs {
-  int steps;
-  long long actions_step;
-  uint8_t* row[5];          // REWARD, COLLECTIVE_REWARD, STEP_TYPE, DISCOUNT, EVENTS
-  long long row_bytes[5];
-};
 
 template <class T>
 __device__ inline T* row_of(uint8_t* base, long long bytes, int k, T* in_place) {
@@ -259,23 +246,16 @@ int prepare_step_many() {
 }
 
 // K steps of every world in one launch (MpStepMany, MpStepTrajectory): the geometry of
-// launch_step.  `rows` and `row_bytes` are the five per-step buffers (NULL: not asked for) and
-// their step distances, `actions_step` the distance between two steps' action blocks in int32,
-// `more` the rows of the other kinds (NULL: an MpStepMany request, which runs k_step_many_*).
+// launch_step.  l.any_rows == false: only rows of the five kinds, which runs k_step_many_*.
 void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
-                      int steps, long long actions_step, void* const rows[5],
-                      const uint64_t row_bytes[5], const StepRows* more, hipStream_t stream) {
-  ManyArgs m;
-  m.steps = steps; m.actions_step = actions_step;
-  for (int i = 0; i < 5; ++i) { m.row[i] = (uint8_t*)rows[i]; m.row_bytes[i] = (long long)row_bytes[i]; }
+                      const StepManyLaunch& l, hipStream_t stream) {
+  const ManyArgs& m = l.many;
+  const bool more = l.any_rows;
   const int wpg = step_worlds_per_group(t, s);
   const size_t lds = (size_t)step_lds_bytes(t, s, wpg);
   const dim3 grid((args.num_worlds + wpg - 1) / wpg), block(wpg * 64);
-  StepRows r = {};
-  if (more) {   // (the level kinds' sources: this submission's buffers)
-    r = *more;
-    for (int i = 0; i < r.n_level; ++i) r.level[i].src = level_source(args.out, r.level[i].which);
-  }
+  StepRows r = l.rows;   // (the level kinds' sources: this submission's buffers)
+  for (int i = 0; i < r.n_level; ++i) r.level[i].src = level_source(args.out, r.level[i].which);
 #define MP_LAUNCH(level, tables)                                                                  \
   if (more) hipLaunchKernelGGL(k_step_rows_##level, grid, block, lds, stream, t, tables, args, m, r); \
   else hipLaunchKernelGGL(k_step_many_##level, grid, block, lds, stream, t, tables, args, m);    \

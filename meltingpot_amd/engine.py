@@ -234,7 +234,11 @@ def world_states_request(L, handle, op: int, **fields) -> MpWorldStates:
 
 # Action sequences (include/mp_engine.h: MpStepMany), carried by mp_restore
 STEP_MANY_MAX = 4096   # MP_STEP_MANY_MAX
-STEP_MANY_KINDS = ("reward", "collective_reward", "step_type", "discount", "events")
+# the five kinds step_many returns by name, in MpStepMany.per_step's order
+STEP_MANY_NAMES = {"reward": OBS_REWARD, "collective_reward": OBS_COLLECTIVE_REWARD,
+                   "step_type": OBS_STEP_TYPE, "discount": OBS_DISCOUNT, "events": OBS_EVENTS}
+STEP_MANY_KINDS = tuple(STEP_MANY_NAMES)
+_STEP_MANY_KIND_OF = STEP_MANY_NAMES
 
 
 class MpStepMany(ctypes.Structure):
@@ -259,8 +263,14 @@ class MpStepTrajectory(ctypes.Structure):
 
 # the kinds a step_many request may stack per step: every kind but the pixel ones
 STEP_ROW_KINDS = tuple(k for k in range(OBS_RGB_POOL8 + 1) if k not in PIXEL_KINDS)
-_STEP_MANY_KIND_OF = {"reward": OBS_REWARD, "collective_reward": OBS_COLLECTIVE_REWARD,
-                      "step_type": OBS_STEP_TYPE, "discount": OBS_DISCOUNT, "events": OBS_EVENTS}
+
+
+def step_row(shapes, key):
+  """A key of step_many's result (one of STEP_MANY_NAMES, or an OBS_* kind) as (kind, shape of
+  one world's part of a row, dtype), from `shapes` (Engine.shapes)."""
+  kind = STEP_MANY_NAMES.get(key, key)
+  shape, dtype = shapes[kind]
+  return kind, tuple(shape[1:]), dtype
 
 
 def check_step_rows(observations, *, steps: Optional[int] = None, shapes=None, out=None,
@@ -975,42 +985,12 @@ class Engine:
     unknown = [k for k in keep if k not in STEP_MANY_KINDS[:4]]
     if unknown:
       raise ValueError(f"step_many: keep= knows {STEP_MANY_KINDS[:4]} (got {unknown})")
-    shapes = {"reward": ((K, self.N, self.P), t.float64), "collective_reward": ((K, self.N), t.float64),
-              "step_type": ((K, self.N), t.int32), "discount": ((K, self.N), t.float64),
-              "events": ((K, self.N, EVENT_ROWS, 4), t.int32)}
-    kinds = check_step_rows(observations, taken=[_STEP_MANY_KIND_OF[n] for n in names])
-    if kinds:
-      return self._step_trajectory(actions, astep, K, fields, names, shapes, kinds, out)
-    self.use_current_stream()
-    req = MpStepMany(ctypes.sizeof(MpStepMany), K, 1 if fields else 0, 0)
-    req.actions = actions.data_ptr()
-    req.actions_step_bytes = astep
+    kinds = check_step_rows(observations, taken=[STEP_MANY_NAMES[n] for n in names])
+    rows = (MpStepRow * (len(names) + len(kinds)))()
     result = {}
-    for name in names:
-      shape, dtype = shapes[name]
-      buf = None if out is None else out.get(name)
-      if buf is None:
-        buf = t.empty(shape, dtype=dtype, device=self.device)
-      elif (not isinstance(buf, t.Tensor) or buf.dtype != dtype or tuple(buf.shape) != shape or
-            buf.device != self.device):
-        raise ValueError(f"step_many: out[{name!r}] must be a {dtype} tensor of shape {shape} on {self.device}")
-      i = STEP_MANY_KINDS.index(name)
-      req.per_step[i] = buf.data_ptr()
-      req.per_step_bytes[i] = _step_distance(buf, f"out[{name!r}]")
-      result[name] = buf
-    _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
-           "mp_restore (MpStepMany)")
-    self._state_args = (actions, result)   # (kept until the next call: the launch may not have run yet)
-    return result
-
-  def _step_trajectory(self, actions, astep, K, fields, names, shapes, kinds, out):
-    """step_many with observations=: one MpStepTrajectory request (include/mp_engine.h)."""
-    t = self._torch
-    wanted = [(name, _STEP_MANY_KIND_OF[name]) + shapes[name] for name in names]
-    wanted += [(kind, kind, (K,) + tuple(self.shapes[kind][0]), self.shapes[kind][1]) for kind in kinds]
-    rows = (MpStepRow * len(wanted))()
-    result = {}
-    for i, (key, kind, shape, dtype) in enumerate(wanted):
+    for i, key in enumerate(names + list(kinds)):
+      kind, per_world, dtype = step_row(self.shapes, key)
+      shape = (K, self.N) + per_world
       buf = None if out is None else out.get(key)
       if buf is None:
         buf = t.empty(shape, dtype=dtype, device=self.device)
@@ -1022,7 +1002,7 @@ class Engine:
       rows[i].step_bytes = _step_distance(buf, f"out[{key!r}]")
       result[key] = buf
     self.use_current_stream()
-    req = MpStepTrajectory(ctypes.sizeof(MpStepTrajectory), K, 1 if fields else 0, len(wanted))
+    req = MpStepTrajectory(ctypes.sizeof(MpStepTrajectory), K, 1 if fields else 0, len(rows))
     req.actions = actions.data_ptr()
     req.actions_step_bytes = astep
     req.rows = rows

@@ -108,9 +108,7 @@ class StepManyTrajectory(StepManyResult):
     return out
 
 
-_FIVE_NAMES = {engine_lib.OBS_REWARD: "reward", engine_lib.OBS_COLLECTIVE_REWARD: "collective_reward",
-               engine_lib.OBS_STEP_TYPE: "step_type", engine_lib.OBS_DISCOUNT: "discount",
-               engine_lib.OBS_EVENTS: "events"}
+_FIVE_NAMES = {kind: name for name, kind in engine_lib.STEP_MANY_NAMES.items()}
 
 
 def _many_result(r, leaves, timestep):
@@ -1644,16 +1642,12 @@ class MixtureSubstrate:
     limit = self.action_spec()[0].num_values if self._check_device_actions else None
     a, K = _many_actions(t, actions, repeat, self._N, self._P, limit)
     dev = first._eng.device
-    out = {"reward": t.empty((K, self._N, self._P), dtype=t.float64, device=dev),
-           "collective_reward": t.empty((K, self._N), dtype=t.float64, device=dev),
-           "step_type": t.empty((K, self._N), dtype=t.int32, device=dev),
-           "discount": t.empty((K, self._N), dtype=t.float64, device=dev)}
-    if events:
-      out["events"] = t.empty((K, self._N, engine_lib.EVENT_ROWS, 4), dtype=t.int32, device=dev)
-    for kind in leaves.values():
-      if kind not in _FIVE_NAMES:
-        shape, dtype = first._eng.shapes[kind]
-        out[kind] = t.empty((K, self._N) + tuple(shape[1:]), dtype=dtype, device=dev)
+    keys = list(engine_lib.STEP_MANY_KINDS[:5 if events else 4])
+    keys += [kind for kind in leaves.values() if kind not in _FIVE_NAMES]
+    out = {}
+    for key in keys:
+      _, per_world, dtype = engine_lib.step_row(first._eng.shapes, key)
+      out[key] = t.empty((K, self._N) + per_world, dtype=dtype, device=dev)
     self._observables.action.on_next(actions)
     for m, off, n in zip(self._members, self._offsets, self._counts):
       m._eng.use_current_stream()

@@ -485,3 +485,29 @@ def test_refusals_launch_nothing_and_leave_the_engine_as_it_was():
   _same_rows(got, ref, "after refusals")
   _same_engines(e, bufs, twin, tb, "after refusals")
   e.close(); twin.close()
+
+
+# ---- 10. the raw request ------------------------------------------------------------------------
+def test_a_raw_request_equals_engine_step_many():
+  """Engine.step_many sends an MpStepTrajectory; an MpStepMany request as a C caller sends it
+  (all five rows; a block of actions per step, then one block repeated) gives the same rows and
+  leaves the same engine."""
+  pack = engine.load_pack("clean_up")
+  n, K = 16, 9
+  e, bufs = _engine(pack, n)
+  twin, tb = _engine(pack, n)
+  P, nact = e.P, e.num_actions
+  A = torch.from_numpy(util.random_actions(np.random.default_rng(23), K, n, P, nact)).to(e.device)
+  e.reset(); twin.reset()
+  e.step(A[0]); twin.step(A[0])
+  e.use_current_stream()
+  for repeat in (False, True):
+    ref = twin.step_many(A[1], repeat=K, events=True) if repeat else twin.step_many(A, events=True)
+    got = {name: torch.zeros_like(v) for name, v in ref.items()}
+    rows = {f"row{i}": (got[name].data_ptr(), got[name][0].numel() * got[name].element_size())
+            for i, name in enumerate(FIVE)}
+    assert _request(e, steps=K, actions=(A[1] if repeat else A).data_ptr(),
+                    actions_step_bytes=0 if repeat else n * P * 4, **rows) == 0, e._L.mp_last_error()
+    _same_rows(got, ref, ("raw", repeat))
+    _same_engines(e, bufs, twin, tb, ("raw", repeat))
+  e.close(); twin.close()

@@ -1,7 +1,8 @@
 """Times `Engine.step_many(observations=...)` (per-step rows of LAYER and the scalar observations,
 K steps in one launch) against what it replaces, on one box; the method of tools/time_step_many.py
 (child processes, a warm-up, events around work that ends in a synchronise, configurations
-alternated round by round, medians and ranges).
+alternated round by round, medians and ranges; beside the GPU time per step, the host's wall time
+per call).
 
   python tools/time_step_trajectory.py --parent-lib PATH [--rounds 5] [--steps 2048] [--out FILE.json]
 
@@ -119,10 +120,13 @@ def main():
       if key == "fault":
         continue
       v = [g[key]["us_per_step"] for g in rounds]
-      summary[f"{label} | {key}"] = {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v))}
+      # (host: wall time of one call's enqueue, where the Python and C checks of a request show)
+      h = [g[key]["host_us_per_step"] * int(key.split("=")[1]) for g in rounds]
+      summary[f"{label} | {key}"] = {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v)),
+                                     "host_us_per_call": float(np.median(h))}
   res["summary"] = summary
   for k, v in summary.items():
-    print(f"{k:70s} {v['median']:8.2f}  [{v['min']:.2f}, {v['max']:.2f}]")
+    print(f"{k:70s} {v['median']:8.2f}  [{v['min']:.2f}, {v['max']:.2f}]  host {v['host_us_per_call']:8.2f} us a call")
   line = json.dumps(res)
   if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
