@@ -1,0 +1,34 @@
+"""One engine driven through a long, seeded, arbitrary sequence of API calls — resets, masked
+re-seeds, device / host / raw-field steps, step_many with and without rows, saves, loads, snapshots,
+restores and views bound and unbound in between — against the oracle-backed model of
+tests/engine_model.py after EVERY call (records, transition kinds, record-function kinds, step_many's
+rows, bad_actions, every bound view and ring slot), and against a twin engine of the other launch
+form (unfused, generic kernels, no view bound) on every output kind the level produces and on the
+saved records: tests/api_programs.py.  One program per committed (seed, profile): three per level
+(n = 5, 13, 37; one with a rollout ring, one with WORLD.RGB pooled by 8) on packs whose episodes
+end after 17 frames, and two on the committed clean_up pack, where the kernels with its constants
+compiled in run."""
+import pytest
+
+import api_programs as ap
+from meltingpot_amd import engine
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.mark.parametrize("seed,profile", ap.COMMITTED, ids=[p["name"] for _, p in ap.COMMITTED])
+def test_program(seed, profile):
+  program = ap.make_program(seed, profile)
+  eng, twin = ap.make_engines(profile)
+  model = ap.make_model(profile)
+  try:
+    if profile["stock"]:
+      assert eng.plan["stock"] == engine.KERNEL_STOCK
+      assert twin.plan["stock"] == engine.KERNEL_GENERIC
+    else:
+      assert eng.plan["stock"] == engine.KERNEL_GENERIC
+    assert ap.run_program(program, eng, model, twin) == len(program)
+    if profile["ring"]:
+      assert eng.ring["slots"] == ap.RING_SLOTS
+  finally:
+    eng.close(); twin.close(); model.close()
