@@ -519,6 +519,62 @@ typedef struct {
   int32_t bank_rows;       /* LOAD: rows of `bank` */
 } MpWorldStates;
 
+/* Observations of bank rows: the views of saved world states, drawn without loading them into a
+ * world.  For a replay buffer that keeps states and draws the minibatch it samples, a planner that
+ * wants the pixels of a few leaves, a video of one world of a rollout kept as states.  Like the
+ * requests above it rides mp_snapshot and is recognised by its size: `bytes` =
+ * sizeof(MpStatesObserve), `host_buf` a HOST MpStatesObserve with struct_size set to it.
+ * include/mp_states_observe.h wraps it as an inline C function.
+ *
+ * `dst` is laid out as the kind's [N]... layout (MpObsKind) with `count` in place of N.  Element i
+ * is a function of row rows[i] of `bank` (rows == NULL: row i) alone:
+ *   the pixel kinds (MP_OBS_RGB, MP_OBS_RGB_POOL2/4/8, MP_OBS_WORLD_RGB at the engine's
+ *   MpConfig.world_pool) and MP_OBS_LAYER: byte for byte what mp_observe(kind) writes for a world
+ *   whose record is that row;
+ *   MP_OBS_READY_TO_SHOOT, MP_OBS_POSITION, MP_OBS_ORIENTATION, MP_OBS_INVENTORY: what
+ *   MP_STATES_LOAD writes for a world loaded from that row.
+ * These are the kinds of MP_STATES_LOAD's group of record functions; a transition kind (its other
+ * group) is not a function of the record and is refused.  Rows saved from finished episodes and
+ * rows with dead avatars are drawn like any other; `count` may be smaller or larger than the
+ * engine's N and rows may repeat.
+ *
+ * The request is enqueued on the engine's stream and does not synchronise.  It writes nothing of
+ * the engine's: not its records or counters, not an in-place or bound output, not a ring slot or
+ * the ring's position, not the kept plans, and mp_tune still regards an engine nothing else has
+ * been done with as such.  It is legal on an engine that has never been reset: the rows may come
+ * from another engine with the same fingerprint.  With `rows` the pixel kinds and LAYER copy the
+ * rows next to each other into a scratch the engine owns and draw from it.  The scratch grows on
+ * demand and lives until mp_destroy; a request that has to grow it (the first one with `rows`,
+ * and every one that needs more than any before it) frees and allocates device memory, which
+ * waits for the device — every other request only enqueues.
+ *
+ * Refused before any launch, the engine left as it was — MP_ERR_INVALID: NULL bank or dst;
+ * count < 1 or bank_rows < 1; rows == NULL with count > bank_rows; a bank that is not 16-byte
+ * aligned; a wrong struct_size; a fingerprint that is not the engine's;
+ * dst_bytes < count x the kind's bytes per world; a pooled view (MP_OBS_RGB_POOL*, a pooled
+ * MP_OBS_WORLD_RGB) whose dst is not 16-byte aligned, any other dst not aligned to the kind's
+ * element size; a bank, rows or dst that is not device memory of the engine's device or does not
+ * lie inside one allocation; a kind outside [0, MP_OBS_KINDS); a transition kind.
+ * MP_ERR_UNSUPPORTED: a kind the level does not have (mp_obs_bytes == 0); a pixel kind whose draw
+ * plan for `count` worlds does not fit the LDS beside the engine's composite cache.
+ * A rows[i] outside [0, bank_rows) is never read: element i of dst is left as it was and the next
+ * synchronising call returns MP_ERR_INVALID.  Two limits of that: the pixel kinds and LAYER, which
+ * draw every element of dst from the gathered rows, keep eight such elements of a request as they
+ * were (any eight; a further one holds what an empty record shows); and of several such indices
+ * one is reported, with a position and a value that may belong to two different ones. */
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(MpStatesObserve) */
+  int32_t kind;            /* MpObsKind */
+  uint64_t fingerprint;    /* in: the rows' (MP_STATES_SAVE's) */
+  const void* bank;        /* device uint8 [bank_rows][S] */
+  const int32_t* rows;     /* device int32 [count], NULL = rows 0 .. count - 1 */
+  void* dst;               /* device: the kind's layout with count in place of N */
+  uint64_t dst_bytes;
+  int32_t bank_rows;
+  int32_t count;
+  uint64_t reserved;       /* 0 */
+} MpStatesObserve;
+
 /* Action sequences: K steps of every world in ONE submission, bit-identical to K calls of the
  * single-step entry points (mp_step, or mp_step_fields with fields = 1) with the same actions,
  * which also hands back the transition of every one of the K steps.  For planners that fork a
@@ -616,9 +672,19 @@ typedef struct {
  * produced (neither bound nor MpConfig.debug_observations; mp_observe's rule): MP_ERR_UNSUPPORTED;
  * a step_bytes or an alignment as above, a buffer that is not device memory of the engine's
  * device or whose extent [rows, rows + (steps - 1) * step_bytes + block) does not lie inside one
- * allocation: MP_ERR_INVALID. */
+ * allocation: MP_ERR_INVALID.
+ *
+ * Per-step world states.  A row may also name MP_STEP_ROW_STATE, which is no observation kind:
+ * row k is uint8 [N][S] (S = MpInfo.world_state_bytes), for a started world byte for byte what
+ * MP_STATES_SAVE of that world gives after the k-th call of the loop of single steps — counters
+ * and the cached visiting orders included, over auto-reset steps and frozen steps alike; a world
+ * never reset writes nothing.  Beam search, branching from the middle of a sequence, a rollout
+ * kept as states whose observations an MpStatesObserve request draws later.  Checked like every
+ * row, with element size 16: step_bytes >= N * S and a multiple of 16, the buffer 16-byte
+ * aligned.  num_rows may therefore reach MP_OBS_KINDS + 1. */
+#define MP_STEP_ROW_STATE 0x100
 typedef struct {
-  int32_t kind;                /* MpObsKind */
+  int32_t kind;                /* MpObsKind, or MP_STEP_ROW_STATE */
   int32_t reserved;
   void* rows;                  /* device: row 0 */
   uint64_t step_bytes;         /* distance between two rows */

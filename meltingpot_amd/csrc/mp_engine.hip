@@ -23,6 +23,7 @@
 #include "stock.h"
 #include "step_common.h"
 #include "step_many.h"
+#include "state_obs.h"
 
 void launch_step(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
                  hipStream_t stream);
@@ -173,6 +174,12 @@ struct MpEngine {
     return unfused != 1;
   }
   uint8_t* d_atlas = nullptr;      // de-duplicated atlas + image slots
+  // An MpStatesObserve request's own memory (grown on demand, freed by mp_destroy): the rows a
+  // pixel kind gathers for the draw-only launch, and the stash of state_obs.h
+  uint8_t* d_obs_rows = nullptr;
+  uint64_t obs_rows_bytes = 0;
+  uint8_t* d_obs_stash = nullptr;
+  uint64_t obs_stash_bytes = 0;
   int32_t* d_layer_lut = nullptr;  // StepOutputs::layer_lut [P][kLayerLutRow]
   StepOutputs outputs() const {
     StepOutputs o = own;
@@ -336,7 +343,12 @@ int sync_and_check(MpEngine* e, const char* who) {
   if (f[FAULT_STATE_INDEX] != 0) {
     const uint32_t at = f[FAULT_STATE_INDEX] - 1, index = f[FAULT_STATE_INDEX + 1];
     const bool load = f[FAULT_STATE_INDEX + 2] == 1;
+    const bool observe = f[FAULT_STATE_INDEX + 2] == kFaultObserveRow;
     e->h_fault[FAULT_STATE_INDEX] = 0;   // reported once; the engine stays usable
+    if (observe)
+      return fail(MP_ERR_INVALID,
+                  "%s: MpStatesObserve: rows[%u] = %d is not a row of the bank; element %u of the "
+                  "destination was left as it was", who, at, (int)index, at);
     return load ? fail(MP_ERR_INVALID,
                        "%s: MP_STATES_LOAD: src[%u] = %d is neither -1 nor a row of the bank; world %u "
                        "was left as it was", who, at, (int)index, at)
@@ -1118,7 +1130,7 @@ void mp_destroy(MpEngine* e) {
   if (e->h_fault) (void)hipHostFree(e->h_fault);
   void* bufs[] = {e->d_pack, e->d_extra, e->d_stepblob, e->d_debug, e->d_state, e->d_scalars,
                   e->d_actions, e->d_fields, e->d_mask, e->d_seeds, e->d_atlas, e->d_ctr, e->d_claim,
-                  e->d_layer_lut};
+                  e->d_layer_lut, e->d_obs_rows, e->d_obs_stash};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   for (int i = 0; i < MpEngine::kHostSlots; ++i)
@@ -1523,7 +1535,7 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r)
                 (unsigned long long)ablock);
   if ((uintptr_t)r.actions & 3)
     return fail(MP_ERR_INVALID, "%s: actions %p is not 4-byte aligned", who, (const void*)r.actions);
-  if (r.num_rows < 0 || r.num_rows > MP_OBS_KINDS || (r.num_rows > 0 && !r.rows))
+  if (r.num_rows < 0 || r.num_rows > MP_OBS_KINDS + 1 || (r.num_rows > 0 && !r.rows))
     return fail(MP_ERR_INVALID, "%s: num_rows %d with rows %p; every kind may be named once", who,
                 r.num_rows, (const void*)r.rows);
   HIP_TRY(hipSetDevice(e->device));
@@ -1535,21 +1547,23 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r)
   l.many.actions_step = (long long)(r.actions_step_bytes / 4);
   l.rows.layer_lut = e->d_layer_lut;
   const StepOutputs o = e->outputs();
-  bool seen[MP_OBS_KINDS] = {};
+  bool seen[MP_OBS_KINDS + 1] = {};
   for (int i = 0; i < r.num_rows; ++i) {
     const MpStepRow& row = r.rows[i];
-    const int kind = row.kind;
-    if (kind < 0 || kind >= MP_OBS_KINDS)
+    const int kind = row.kind, index = step_row_index(kind);
+    if (index < 0)
       return fail(MP_ERR_INVALID, "%s: rows[%d] names kind %d, which is no observation kind", who, i, kind);
     if (MpEngine::is_pixel_kind(kind))
       return fail(MP_ERR_INVALID, "%s: rows[%d] names pixel kind %d; a K-step launch draws no frames — "
                   "intermediate frames are what mp_step with a rollout ring (mp_bind_output_ring) writes",
                   who, i, kind);
-    const StepRowKind& k = kStepRowKinds.of[kind];
+    const StepRowKind& k = kStepRowKinds.of[index];
     if (!k.name) return fail(MP_ERR_INVALID, "%s: kind %d has no per-step rows", who, kind);
-    if (seen[kind]) return fail(MP_ERR_INVALID, "%s: %s (kind %d) is named twice", who, k.name, kind);
-    seen[kind] = true;
-    const uint64_t block = mp_obs_bytes(e, (MpObsKind)kind), elem = (uint64_t)k.elem;
+    if (seen[index]) return fail(MP_ERR_INVALID, "%s: %s (kind %d) is named twice", who, k.name, kind);
+    seen[index] = true;
+    // (MP_STEP_ROW_STATE: a row is the N records)
+    const uint64_t block = k.place == kRowState ? mp_snapshot_bytes(e) : mp_obs_bytes(e, (MpObsKind)kind);
+    const uint64_t elem = (uint64_t)k.elem;
     if (block == 0)
       return fail(MP_ERR_UNSUPPORTED, "%s: this substrate has no observation %s (kind %d)", who, k.name, kind);
     if (!row.rows) return fail(MP_ERR_INVALID, "%s: rows[%d] (%s) has no buffer", who, i, k.name);
@@ -1574,6 +1588,7 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r)
       case kRowFive: l.many.row[k.slot] = base; l.many.row_bytes[k.slot] = bytes; break;
       case kRowFin: l.rows.fin[k.slot] = base; l.rows.fin_bytes[k.slot] = bytes; break;
       case kRowLayer: l.rows.layer = base; l.rows.layer_bytes = bytes; break;
+      case kRowState: l.state.row = base; l.state.bytes = bytes; break;
       default: {
         StepRows::Level& lv = l.rows.level[l.rows.n_level++];
         lv.which = kind;   // (launch_step_many resolves the buffer: a rollout ring moves it per submission)
@@ -1611,10 +1626,127 @@ static int trajectory_request(MpEngine* e, const MpStepTrajectory& r) {
   return step_request(e, kWho, r);
 }
 
+// An MpStatesObserve request (include/mp_engine.h; carried by mp_snapshot): observations of rows
+// of a bank, enqueued on the engine's stream.  Everything is checked before the first launch, and
+// nothing of the engine's is written but its own scratch and the parity of the claim counters
+// (which a draw-only launch of mp_observe moves on in the same way).
+static int grow_obs_buffer(uint8_t** buf, uint64_t* have, uint64_t need) {
+  if (*have >= need) return MP_OK;
+  // (hipFree waits for the launches that may still read the old one)
+  if (*buf) { HIP_TRY(hipFree(*buf)); *buf = nullptr; *have = 0; }
+  HIP_TRY(hipMalloc((void**)buf, need));
+  *have = need;
+  return MP_OK;
+}
+
+static int states_observe(MpEngine* e, const MpStatesObserve& r) {
+  static const char kWho[] = "MpStatesObserve";
+  if (!e) return fail(MP_ERR_INVALID, "%s: NULL engine", kWho);
+  if (r.struct_size != sizeof(MpStatesObserve))
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpStatesObserve));
+  if (!r.bank || !r.dst) return fail(MP_ERR_INVALID, "%s: NULL bank or dst", kWho);
+  if (r.count < 1 || r.bank_rows < 1)
+    return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", kWho, r.count, r.bank_rows);
+  if (!r.rows && r.count > r.bank_rows)
+    return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are drawn (count %d, the bank "
+                "has %d rows)", kWho, r.count, r.bank_rows);
+  if (r.fingerprint != e->fingerprint)
+    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this engine's (%016llx): "
+                "they were saved by an engine of another pack, player count or record layout", kWho,
+                (unsigned long long)r.fingerprint, (unsigned long long)e->fingerprint);
+  const int kind = r.kind;
+  if (kind < 0 || kind >= MP_OBS_KINDS)
+    return fail(MP_ERR_INVALID, "%s: kind %d is no observation kind", kWho, kind);
+  const bool pixel = MpEngine::is_pixel_kind(kind);
+  uint64_t elem = 1;   // what dst is aligned to
+  switch (kind) {
+    case MP_OBS_LAYER: case MP_OBS_POSITION: case MP_OBS_ORIENTATION: elem = 4; break;
+    case MP_OBS_READY_TO_SHOOT: case MP_OBS_INVENTORY: elem = 8; break;
+    default:
+      if (!pixel)
+        return fail(MP_ERR_INVALID, "%s: kind %d is not a function of the record (a transition kind: what a "
+                    "step or a reset reports, which no saved state holds)", kWho, kind);
+  }
+  const bool pooled = MpEngine::pool_of(kind) > 1 || (kind == MP_OBS_WORLD_RGB && e->world_pool > 1);
+  if (pooled) elem = 16;   // (mp_observe's rule: a pooled span is staged by 16-byte lines)
+  const uint64_t per = mp_obs_bytes(e, (MpObsKind)kind) / (uint64_t)e->N;
+  if (per == 0)
+    return fail(MP_ERR_UNSUPPORTED, "%s: this substrate has no observation %d", kWho, kind);
+  const uint64_t count = (uint64_t)r.count, need = count * per;
+  if (r.dst_bytes < need)
+    return fail(MP_ERR_INVALID, "%s: %d elements of %llu bytes need %llu bytes, dst has %llu", kWho, r.count,
+                (unsigned long long)per, (unsigned long long)need, (unsigned long long)r.dst_bytes);
+  if ((uintptr_t)r.dst % elem)
+    return fail(MP_ERR_INVALID, "%s: dst %p is not %llu-byte aligned%s", kWho, r.dst, (unsigned long long)elem,
+                pooled ? " (a pooled view's buffer)" : "");
+  if (r.rows && ((uintptr_t)r.rows & 3))
+    return fail(MP_ERR_INVALID, "%s: rows %p is not 4-byte aligned", kWho, (const void*)r.rows);
+  if ((uintptr_t)r.bank & 15)   // (records are read in 16-byte lines)
+    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", kWho, r.bank);
+  HIP_TRY(hipSetDevice(e->device));
+  const uint64_t S = (uint64_t)e->t.world_stride;
+  if (int rc = check_bank(e, r.bank, (uint64_t)r.bank_rows * S, "MpStatesObserve (bank)")) return rc;
+  if (r.rows)
+    if (int rc = check_bank(e, r.rows, count * 4, "MpStatesObserve (rows)")) return rc;
+  if (int rc = check_bank(e, r.dst, need, "MpStatesObserve (dst)")) return rc;
+  const uint8_t* bank = (const uint8_t*)r.bank;
+  if (!pixel && kind != MP_OBS_LAYER) {
+    launch_state_obs(e->t, e->sub, kind, bank, r.bank_rows, r.rows, r.count, r.dst, e->stream);
+    HIP_TRY(hipGetLastError());
+    return MP_OK;
+  }
+  // LAYER and the pixel kinds are drawn by launches that take contiguous records: k_layer_view and
+  // the draw-only frame launch.  The engine's own draw plan serves N worlds; another count gets a
+  // plan of its own, which must fit the LDS beside the composite cache (sized at mp_create for
+  // the engine's plans; plan_frame shrinks its ring down to two single-world batches to fit).
+  const bool agents = kind != MP_OBS_WORLD_RGB;
+  const int views = agents ? 0 : 1, pk = agents ? MpEngine::pool_of(kind) : 1;
+  FramePlan p = {};
+  if (pixel) {
+    p = r.count == e->N ? e->frame_plan(0, views, pk)
+                        : plan_frame(e->t, e->sub, r.count, false, views, e->num_cus, nullptr, pk, e->world_pool);
+    const int lds = frame_lds_bytes(e->t, p, pk, e->world_pool, views);
+    if (lds > 160 * 1024)
+      return fail(MP_ERR_UNSUPPORTED, "%s: a draw plan for %d rows of kind %d needs %d B of LDS beside this "
+                  "engine's composite cache", kWho, r.count, kind, lds);
+  }
+  // With a row list: the rows copied next to each other into the engine's scratch first.
+  const uint8_t* state = bank;
+  if (r.rows) {
+    if (int rc = grow_obs_buffer(&e->d_obs_rows, &e->obs_rows_bytes, count * S)) return rc;
+    const uint64_t stash = 64 + (uint64_t)kObsStashSlots * per;
+    if (e->obs_stash_bytes < stash) {
+      if (int rc = grow_obs_buffer(&e->d_obs_stash, &e->obs_stash_bytes, stash)) return rc;
+      HIP_TRY(hipMemsetAsync(e->d_obs_stash, 0, 64, e->stream));
+    }
+    launch_gather_rows(e->t, bank, r.bank_rows, r.rows, r.count, e->d_obs_rows, (const uint8_t*)r.dst, per,
+                       e->d_obs_stash, e->stream);
+    state = e->d_obs_rows;
+  }
+  if (pixel) {
+    stepk::StepArgs args = {};
+    args.state = const_cast<uint8_t*>(state);
+    args.num_worlds = r.count;
+    p.parity = e->frame_launches++ & 1;
+    uint8_t* out = (uint8_t*)r.dst;
+    launch_frame(e->t, nullptr, args, agents ? out : nullptr, agents ? nullptr : out, p, e->stream, pk,
+                 e->world_pool);
+  } else {
+    launch_layer_view(e->t, state, (int32_t*)r.dst, r.count, e->stream);
+  }
+  if (r.rows) launch_restore_stash((uint8_t*)r.dst, per, e->d_obs_stash, e->stream);
+  HIP_TRY(hipGetLastError());
+  return MP_OK;
+}
+
 uint64_t mp_snapshot_bytes(const MpEngine* e) {
   return e ? (uint64_t)e->N * e->t.world_stride : 0;
 }
 
+static_assert(sizeof(MpStatesObserve) == 64 && sizeof(MpStatesObserve) != sizeof(MpKernelVariant) &&
+                  sizeof(MpStatesObserve) != sizeof(MpWorldStates) && sizeof(MpStatesObserve) != sizeof(MpStepMany) &&
+                  sizeof(MpStatesObserve) != sizeof(MpStepTrajectory),
+              "mp_snapshot / mp_restore tell their requests apart by size");
 static_assert(sizeof(MpKernelVariant) != sizeof(MpWorldStates) && sizeof(MpKernelVariant) != sizeof(MpStepMany) &&
                   sizeof(MpStepTrajectory) != sizeof(MpKernelVariant) && sizeof(MpStepTrajectory) != sizeof(MpWorldStates) &&
                   sizeof(MpStepTrajectory) != sizeof(MpStepMany) && sizeof(MpStepTrajectory) < 448,
@@ -1652,6 +1784,11 @@ static int kernel_variant(const MpEngine* e, MpKernelVariant* r) {
 int mp_snapshot(MpEngine* e, void* buf, uint64_t bytes) {
   if (buf && bytes == sizeof(MpKernelVariant)) return kernel_variant(e, (MpKernelVariant*)buf);
   if (e && buf && bytes == sizeof(MpWorldStates)) return world_states(e, (MpWorldStates*)buf, false);
+  if (buf && bytes == sizeof(MpStatesObserve)) {
+    MpStatesObserve r;   // (read only: nothing is written back)
+    memcpy(&r, buf, sizeof r);
+    return states_observe(e, r);
+  }
   if (!e || !buf || bytes != mp_snapshot_bytes(e))
     return fail(MP_ERR_INVALID, "mp_snapshot: bad buffer");
   HIP_TRY(hipSetDevice(e->device));

@@ -12,15 +12,21 @@ int step_worlds_per_group(const DevTables& t, const SubstrateTables& s);
 // Every kind a K-step launch can stack per step, by MpObsKind: its name in messages, its element
 // size (a row distance is a multiple of it, a buffer aligned to it) and where its rows go — slot
 // `slot` of ManyArgs::row (the five kinds of MpStepMany) or of StepRows::fin, StepRows::layer, or
-// one of StepRows::level.  name == NULL: no per-step rows (the pixel kinds).
-enum StepRowPlace { kRowFive = 1, kRowFin, kRowLayer, kRowLevel };
+// one of StepRows::level.  name == NULL: no per-step rows (the pixel kinds).  The last entry,
+// index kStepRowStateIndex, is MP_STEP_ROW_STATE: the world's record itself (StateRows), which
+// is no observation kind (step_row_index maps a request's kind to its entry).
+enum StepRowPlace { kRowFive = 1, kRowFin, kRowLayer, kRowLevel, kRowState };
+constexpr int kStepRowStateIndex = MP_OBS_KINDS;
+constexpr int step_row_index(int kind) {
+  return kind == MP_STEP_ROW_STATE ? kStepRowStateIndex : kind >= 0 && kind < MP_OBS_KINDS ? kind : -1;
+}
 struct StepRowKind {
   const char* name;
   int elem;
   int place;
   int slot;
 };
-struct StepRowKinds { StepRowKind of[MP_OBS_KINDS]; };
+struct StepRowKinds { StepRowKind of[MP_OBS_KINDS + 1]; };
 constexpr StepRowKinds make_step_row_kinds() {
   StepRowKinds k = {};
   k.of[MP_OBS_REWARD] = {"REWARD", 8, kRowFive, 0};
@@ -42,6 +48,7 @@ constexpr StepRowKinds make_step_row_kinds() {
   k.of[MP_OBS_INTERACTION_INVENTORIES] = {"INTERACTION_INVENTORIES", 8, kRowLevel, 0};
   k.of[MP_OBS_MATRIX_CUMULANTS] = {"MATRIX_CUMULANTS", 8, kRowLevel, 0};
   k.of[MP_OBS_INTERACTION_REWARDS] = {"INTERACTION_REWARDS", 8, kRowLevel, 0};
+  k.of[kStepRowStateIndex] = {"STATE", 16, kRowState, 0};   // (a record is copied in 16-byte lines)
   return k;
 }
 constexpr StepRowKinds kStepRowKinds = make_step_row_kinds();
@@ -58,7 +65,7 @@ struct ManyArgs {
 
 // The per-step rows of a request beyond MpStepMany's five: row 0 of the caller's buffer of each
 // kind (NULL: not asked for) and the distance between two rows in bytes.
-// Three groups, by who writes the kind in a step (step_many.hip: run_many):
+// Three groups of observation kinds, by who writes the kind in a step (step_many.hip: run_many):
 //   fin    the kinds finish() writes for every world that is reset or stepped, element
 //          w * P + lane from lane `lane`: READY_TO_SHOOT, AUX0, POSITION, ORIENTATION;
 //   layer  MP_OBS_LAYER, a function of the record (`layer_lut`: StepOutputs::layer_lut);
@@ -98,13 +105,23 @@ struct StepRows {
   } level[9];
 };
 
+// The per-step world states (MP_STEP_ROW_STATE): row k = uint8 [N][world_stride], the records
+// after step k (`row`: row 0, NULL: not asked for; `bytes`: the distance between two rows).  An
+// argument of its own, of a kernel family of its own (k_step_states_<level>): StepRows and the
+// kernels that take only it are what they were.
+struct StateRows {
+  uint8_t* row;
+  long long bytes;
+};
+
 // One checked K-step request, as submit() hands it to launch_step_many: the five kinds' rows,
-// the rows of the other kinds, and whether there is one of those (any_rows == false runs the
-// kernels an MpStepMany request has always run).
+// the rows of the other kinds, whether there is one of those (any_rows == false runs the
+// kernels an MpStepMany request has always run), and the state rows.
 struct StepManyLaunch {
   ManyArgs many;
   StepRows rows;
   bool any_rows;
+  StateRows state;
 };
 
 void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,

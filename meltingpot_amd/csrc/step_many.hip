@@ -66,10 +66,18 @@ __device__ inline T* row_of(uint8_t* base, long long bytes, int k, T* in_place) 
 //    in-place buffer behind these loads.
 //  * r.layer: write_layer() on row k from the record in LDS after every step of a started
 //    world, a frozen one included (the same bytes again).
+//  * the state rows (MP_STEP_ROW_STATE, `sp`, States = true: the k_step_states_* family):
+//    store_record() of the record in LDS to row k after every step of a started world — the
+//    bytes finish() has just written back to the world's own record, so what MP_STATES_SAVE
+//    would copy from there.  It reads the LDS record behind the same wsync() as the layer row;
+//    the loop-top wsync() keeps the next step's writes behind it.  A family of its own: with the
+//    row as one more runtime branch of k_step_rows_*, that family's LAYER rows cost 9 % more on
+//    clean_up (profiles/r16_observe_states.md); this way its code is what it was.
 // Which kinds are asked for is wave-uniform: every branch on it is a scalar one.
-template <bool Rows, class Tables, class Sites>
+template <bool Rows, bool States, class Tables, class Sites>
 __device__ inline void run_many(const DevTables& t, const Tables& c, const StepArgs& args0,
-                                const ManyArgs& m, const StepRows* rp, int extra) {
+                                const ManyArgs& m, const StepRows* rp, int extra,
+                                const StateRows* sp = nullptr) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
@@ -140,7 +148,7 @@ __device__ inline void run_many(const DevTables& t, const Tables& c, const StepA
     act_id = next_id;
     if constexpr (Rows) {
       const StepRows& r = *rp;
-      if (r.layer || r.n_level) {
+      if (States || r.layer || r.n_level) {
         wsync();   // the record in LDS is final; the step's stores to the level kinds come before the loads below
         const WorldTail* tl = reinterpret_cast<const WorldTail*>(wd.rec + t.grid_pad);
         if (__builtin_amdgcn_readfirstlane((int)tl->started)) {
@@ -156,6 +164,8 @@ __device__ inline void run_many(const DevTables& t, const Tables& c, const StepA
             lo.layer_lut = r.layer_lut;
             write_layer(t, wd.rec, lo, w, lane_k);
           }
+          if constexpr (States)
+            store_record(t, wd.rec, sp->row + (long long)k * sp->bytes + (size_t)w * t.world_stride, lane_k);
         }
       }
     }
@@ -199,7 +209,7 @@ __device__ inline void run_many(const DevTables& t, const Tables& c, const StepA
 #define MP_STEP_MANY_KERNEL(name, TablesT, SitesT, extra)                                            \
   __global__ __launch_bounds__(kWorldsPerGroup * 64) void name(DevTables t, TablesT c, StepArgs args, \
                                                                ManyArgs m) {                         \
-    run_many<false, TablesT, SitesT>(t, c, args, m, nullptr, extra);                                 \
+    run_many<false, false, TablesT, SitesT>(t, c, args, m, nullptr, extra);                          \
   }
 MP_STEP_MANY_KERNEL(k_step_many_clean_up, CleanUpTables, CleanUpSites, 0)
 MP_STEP_MANY_KERNEL(k_step_many_commons, CommonsTables, CommonsSites, 0)
@@ -217,7 +227,7 @@ MP_STEP_MANY_KERNEL(k_step_many_territory, TerritoryTables, TerritorySites, extr
 #define MP_STEP_ROWS_KERNEL(name, TablesT, SitesT, extra)                                            \
   __global__ __launch_bounds__(kWorldsPerGroup * 64) void name(DevTables t, TablesT c, StepArgs args, \
                                                                ManyArgs m, StepRows r) {             \
-    run_many<true, TablesT, SitesT>(t, c, args, m, &r, extra);                                       \
+    run_many<true, false, TablesT, SitesT>(t, c, args, m, &r, extra);                                \
   }
 MP_STEP_ROWS_KERNEL(k_step_rows_clean_up, CleanUpTables, CleanUpSites, 0)
 MP_STEP_ROWS_KERNEL(k_step_rows_commons, CommonsTables, CommonsSites, 0)
@@ -230,12 +240,32 @@ MP_STEP_ROWS_KERNEL(k_step_rows_matrix, MatrixTables, MatrixSites, 0)
 MP_STEP_ROWS_KERNEL(k_step_rows_territory, TerritoryTables, TerritorySites, extra_bytes(c))
 #undef MP_STEP_ROWS_KERNEL
 
+// ... and with the per-step world states (MP_STEP_ROW_STATE) beside whatever other rows are asked
+// for: a third family, so that the two above run exactly the code they ran before there was one.
+#define MP_STEP_STATES_KERNEL(name, TablesT, SitesT, extra)                                          \
+  __global__ __launch_bounds__(kWorldsPerGroup * 64) void name(DevTables t, TablesT c, StepArgs args, \
+                                                               ManyArgs m, StepRows r, StateRows s) { \
+    run_many<true, true, TablesT, SitesT>(t, c, args, m, &r, extra, &s);                             \
+  }
+MP_STEP_STATES_KERNEL(k_step_states_clean_up, CleanUpTables, CleanUpSites, 0)
+MP_STEP_STATES_KERNEL(k_step_states_commons, CommonsTables, CommonsSites, 0)
+MP_STEP_STATES_KERNEL(k_step_states_coins, CoinsTables, CoinsSites, 0)
+MP_STEP_STATES_KERNEL(k_step_states_coop, CoopTables, CoopSites, 0)
+MP_STEP_STATES_KERNEL(k_step_states_gift, GiftTables, GiftSites, 0)
+MP_STEP_STATES_KERNEL(k_step_states_cook, CookTables, CookSites, 0)
+MP_STEP_STATES_KERNEL(k_step_states_mushroom, MushroomTables, MushroomSites, extra_bytes(c))
+MP_STEP_STATES_KERNEL(k_step_states_matrix, MatrixTables, MatrixSites, 0)
+MP_STEP_STATES_KERNEL(k_step_states_territory, TerritoryTables, TerritorySites, extra_bytes(c))
+#undef MP_STEP_STATES_KERNEL
+
 }  // namespace
 
 // The K-step kernels may take all 160 KB of a CU's LDS, like the single-step ones.
 int prepare_step_many() {
-  const void* km[18] = {
-#define MP_BOTH(level) reinterpret_cast<const void*>(&k_step_many_##level), reinterpret_cast<const void*>(&k_step_rows_##level)
+  const void* km[27] = {
+#define MP_BOTH(level)                                                                             \
+  reinterpret_cast<const void*>(&k_step_many_##level), reinterpret_cast<const void*>(&k_step_rows_##level), \
+      reinterpret_cast<const void*>(&k_step_states_##level)
       MP_BOTH(clean_up), MP_BOTH(commons), MP_BOTH(coins), MP_BOTH(territory), MP_BOTH(matrix),
       MP_BOTH(coop), MP_BOTH(gift), MP_BOTH(cook), MP_BOTH(mushroom)};
 #undef MP_BOTH
@@ -246,7 +276,8 @@ int prepare_step_many() {
 }
 
 // K steps of every world in one launch (MpStepMany, MpStepTrajectory): the geometry of
-// launch_step.  l.any_rows == false: only rows of the five kinds, which runs k_step_many_*.
+// launch_step.  l.any_rows == false: only rows of the five kinds, which runs k_step_many_*;
+// l.state.row: the state rows, which runs k_step_states_*.
 void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
                       const StepManyLaunch& l, hipStream_t stream) {
   const ManyArgs& m = l.many;
@@ -257,7 +288,9 @@ void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk:
   StepRows r = l.rows;   // (the level kinds' sources: this submission's buffers)
   for (int i = 0; i < r.n_level; ++i) r.level[i].src = level_source(args.out, r.level[i].which);
 #define MP_LAUNCH(level, tables)                                                                  \
-  if (more) hipLaunchKernelGGL(k_step_rows_##level, grid, block, lds, stream, t, tables, args, m, r); \
+  if (l.state.row)                                                                                \
+    hipLaunchKernelGGL(k_step_states_##level, grid, block, lds, stream, t, tables, args, m, r, l.state); \
+  else if (more) hipLaunchKernelGGL(k_step_rows_##level, grid, block, lds, stream, t, tables, args, m, r); \
   else hipLaunchKernelGGL(k_step_many_##level, grid, block, lds, stream, t, tables, args, m);    \
   break;
   switch (s.substrate) {

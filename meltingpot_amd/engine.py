@@ -232,6 +232,29 @@ def world_states_request(L, handle, op: int, **fields) -> MpWorldStates:
   return req
 
 
+# Observations of bank rows (include/mp_engine.h: MpStatesObserve), carried by mp_snapshot
+class MpStatesObserve(ctypes.Structure):
+  _fields_ = [("struct_size", ctypes.c_uint32), ("kind", ctypes.c_int32),
+              ("fingerprint", ctypes.c_uint64), ("bank", ctypes.c_void_p), ("rows", ctypes.c_void_p),
+              ("dst", ctypes.c_void_p), ("dst_bytes", ctypes.c_uint64), ("bank_rows", ctypes.c_int32),
+              ("count", ctypes.c_int32), ("reserved", ctypes.c_uint64)]
+
+
+# the kinds that are functions of a world's record: what observe_states draws from saved rows
+STATE_OBS_KINDS = PIXEL_KINDS + (OBS_LAYER, OBS_READY_TO_SHOOT, OBS_POSITION, OBS_ORIENTATION,
+                                 OBS_INVENTORY)
+
+
+def states_observe_request(L, handle, **fields) -> MpStatesObserve:
+  """Runs one MpStatesObserve request on engine `handle`; raises like every call."""
+  req = MpStatesObserve(ctypes.sizeof(MpStatesObserve))
+  for k, v in fields.items():
+    setattr(req, k, v)
+  _check(L, L.mp_snapshot(handle, ctypes.addressof(req), ctypes.sizeof(req)),
+         "mp_snapshot (MpStatesObserve)")
+  return req
+
+
 # Action sequences (include/mp_engine.h: MpStepMany), carried by mp_restore
 STEP_MANY_MAX = 4096   # MP_STEP_MANY_MAX
 # the five kinds step_many returns by name, in MpStepMany.per_step's order
@@ -260,6 +283,9 @@ class MpStepTrajectory(ctypes.Structure):
               ("actions", ctypes.c_void_p), ("actions_step_bytes", ctypes.c_uint64),
               ("rows", ctypes.POINTER(MpStepRow))]
 
+
+# MpStepRow.kind of the per-step world states (MP_STEP_ROW_STATE): no observation kind
+STEP_ROW_STATE = 0x100
 
 # the kinds a step_many request may stack per step: every kind but the pixel ones
 STEP_ROW_KINDS = tuple(k for k in range(OBS_RGB_POOL8 + 1) if k not in PIXEL_KINDS)
@@ -945,7 +971,7 @@ class Engine:
 
   def step_many(self, actions, *, repeat: Optional[int] = None, fields: bool = False,
                 keep=("reward", "collective_reward", "step_type", "discount"), events: bool = False,
-                observations=(), out=None):
+                observations=(), out=None, states=False):
     """K steps of every world in ONE launch, bit-identical to K calls of step() (fields=True:
     step_fields()) with actions[0] .. actions[K - 1]; returns the per-step transitions.
 
@@ -965,6 +991,10 @@ class Engine:
     buffer holds after step k of the loop of step(), carried from row k - 1 wherever step k
     writes nothing (a frozen world; OBS_INTERACTION_REWARDS between interactions).  OBS_LAYER
     need not be bound.  A debug kind must be produced (bound, or debug_observations).
+    states: True (or a tensor under out["states"]) adds "states", uint8 [K, N, S] with S =
+    info.world_state_bytes: row k of a started world is what save_worlds() gives after step k of
+    the loop (a world never reset writes nothing).  Each [k] loads with load_worlds and draws
+    with observe_states like any bank.
     Enqueued on the current stream; does not synchronise."""
     t = self._torch
     A = int(self.info.num_action_fields) if fields else None
@@ -986,10 +1016,15 @@ class Engine:
     if unknown:
       raise ValueError(f"step_many: keep= knows {STEP_MANY_KINDS[:4]} (got {unknown})")
     kinds = check_step_rows(observations, taken=[STEP_MANY_NAMES[n] for n in names])
-    rows = (MpStepRow * (len(names) + len(kinds)))()
+    states = bool(states) or (out is not None and out.get("states") is not None)
+    keys = names + list(kinds) + (["states"] if states else [])
+    rows = (MpStepRow * len(keys))()
     result = {}
-    for i, key in enumerate(names + list(kinds)):
-      kind, per_world, dtype = step_row(self.shapes, key)
+    for i, key in enumerate(keys):
+      if key == "states":
+        kind, per_world, dtype = STEP_ROW_STATE, (int(self.info.world_state_bytes),), t.uint8
+      else:
+        kind, per_world, dtype = step_row(self.shapes, key)
       shape = (K, self.N) + per_world
       buf = None if out is None else out.get(key)
       if buf is None:
@@ -1104,6 +1139,45 @@ class Engine:
     world_states_request(self._L, self._h, MP_STATES_LOAD, bank=bank.data_ptr(),
                          bank_rows=int(bank.shape[0]), src=s.data_ptr(), fingerprint=fp)
     self._state_args = s
+
+  def observe_states(self, bank, kind: int, rows=None, out=None, fingerprint: Optional[int] = None):
+    """Observation `kind` of rows of `bank` (uint8 [M, S] device tensor from save_worlds or
+    step_many(states=True)[k], of this engine or another with the same state_fingerprint),
+    drawn where the rows lie: no world is loaded and nothing of the engine's — records, outputs,
+    ring, plans — is written.  rows: the rows to draw, in order, repeats allowed (None: every row
+    of the bank).  Returns a tensor of shape (count,) + self.shapes[kind][0][1:] (`out`: the tensor to
+    write).  `kind` is one of STATE_OBS_KINDS: a pixel view, OBS_LAYER, OBS_READY_TO_SHOOT,
+    OBS_POSITION, OBS_ORIENTATION, OBS_INVENTORY — equal to what observe() / a load_worlds of the
+    row gives; the transition kinds are not functions of a record and are refused.
+    `fingerprint`: the rows' (default: this engine's).  Enqueued on the current stream."""
+    t = self._torch
+    S = int(self.info.world_state_bytes)
+    if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
+        bank.shape[1] != S or not bank.is_contiguous()):
+      raise ValueError(f"observe_states: bank must be a contiguous uint8 tensor [M, {S}]")
+    if bank.shape[0] < 1:
+      raise ValueError("observe_states: the bank has no rows")
+    if isinstance(kind, bool) or not isinstance(kind, (int, np.integer)) or int(kind) not in self.shapes:
+      raise ValueError(f"observe_states: {kind!r} is no observation kind")
+    kind = int(kind)
+    r = None if rows is None else self._device_ints(rows, "rows")
+    count = int(bank.shape[0]) if r is None else int(r.numel())
+    if count < 1:
+      raise ValueError("observe_states: no rows to draw")
+    shape, dtype = self.shapes[kind]
+    shape = (count,) + tuple(int(d) for d in shape[1:])
+    if out is None:
+      out = t.empty(shape, dtype=dtype, device=self.device)
+    elif (not isinstance(out, t.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or
+          not out.is_contiguous() or out.device != self.device):
+      raise ValueError(f"observe_states: out must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    self.use_current_stream()
+    states_observe_request(self._L, self._h, kind=kind, fingerprint=fp, bank=bank.data_ptr(),
+                           bank_rows=int(bank.shape[0]), rows=None if r is None else r.data_ptr(),
+                           count=count, dst=out.data_ptr(), dst_bytes=out.numel() * out.element_size())
+    self._state_args = (bank, r, out)   # (kept until the next call: the launch may not have run yet)
+    return out
 
   def counters(self) -> Dict[str, int]:
     out = np.zeros(len(COUNTER_NAMES), np.uint64)

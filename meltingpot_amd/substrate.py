@@ -99,26 +99,35 @@ class StepManyTrajectory(StepManyResult):
   StepManyResult) plus `.observation`, a dict from each asked leaf's name to its per-step
   device tensor [K, N, ...]: row k is the leaf after step k of the loop of `step`.  Like
   `RolloutTimeStep.slot`, `.observation` is an attribute beside the tuple's fields: `_replace`
-  carries it; `_make`, slicing, `tuple()` and pickling give a plain tuple without it."""
+  carries it; `_make`, slicing, `tuple()` and pickling give a plain tuple without it.
+  With `states=True` it also has `.states`: the worlds' records after every step as a
+  `WorldStates` of K x N rows (step k of world w is row k * N + w), a view of the engine's
+  uint8 [K, N, S] tensor; carried like `.observation` (None when not asked for)."""
   observation: Any = None
+  states: Any = None
 
   def _replace(self, **kwargs):   # (a NamedTuple's _replace builds a fresh tuple: carry the dict)
     out = super()._replace(**kwargs)
     out.observation = self.observation
+    out.states = self.states
     return out
 
 
 _FIVE_NAMES = {kind: name for name, kind in engine_lib.STEP_MANY_NAMES.items()}
 
 
-def _many_result(r, leaves, timestep):
-  """The result of a step_many call from the engine's dict `r` (`leaves`: asked name -> kind)."""
+def _many_result(r, leaves, timestep, fingerprint=None):
+  """The result of a step_many call from the engine's dict `r` (`leaves`: asked name -> kind;
+  `fingerprint`: the engine's, when the call asked for the per-step states)."""
   fields = (r["step_type"], r["reward"], r["discount"], r["collective_reward"], r.get("events"), timestep)
-  if not leaves:
+  if not leaves and fingerprint is None:
     return StepManyResult(*fields)
   out = StepManyTrajectory(*fields)
   # (a leaf that is one of the five per-step kinds is the tensor the call stacks anyway)
   out.observation = {n: r[_FIVE_NAMES[k]] if k in _FIVE_NAMES else r[k] for n, k in leaves.items()}
+  if fingerprint is not None:
+    rows = r["states"]
+    out.states = WorldStates(rows.view(rows.shape[0] * rows.shape[1], rows.shape[2]), fingerprint)
   return out
 
 
@@ -916,6 +925,49 @@ class Substrate:
     self._submissions += 1
     return self._emit(self._timestep())
 
+  # the leaves that are functions of a world's record (engine_lib.STATE_OBS_KINDS)
+  _STATE_LEAVES = ("RGB", "WORLD.RGB", "LAYER", "READY_TO_SHOOT", "POSITION", "ORIENTATION", "INVENTORY")
+
+  def state_leaves(self) -> Dict[str, int]:
+    """The leaves `observe_states` can draw from saved states, with their engine kinds: "RGB"
+    (at this substrate's rgb_pool), "WORLD.RGB" (at its world_rgb_pool), "LAYER",
+    "READY_TO_SHOOT", "POSITION", "ORIENTATION" and, where the level has one, "INVENTORY"."""
+    return {n: self._kinds[n] for n in self._STATE_LEAVES
+            if n != "INVENTORY" or int(self._eng.info.num_resources) > 0}
+
+  def _state_leaves(self, observations) -> Dict[str, int]:
+    """`observations` of an observe_states call as name -> kind (None: those among this
+    substrate's own leaves)."""
+    offered = self.state_leaves()
+    if observations is None:
+      return {n: k for n, k in offered.items() if n in self._obs}
+    if isinstance(observations, str):
+      observations = (observations,)
+    leaves = {}
+    for n in observations:
+      if n not in offered:
+        what = ("a transition leaf: what a step or a reset reports, which no saved state holds"
+                if n in self._kinds and n != "INVENTORY" else "no leaf of this substrate")
+        raise ValueError(f"observe_states: observation {n!r} is {what}; it can draw {sorted(offered)}")
+      leaves[n] = offered[n]
+    return leaves
+
+  def observe_states(self, states: WorldStates, observations=None, rows=None) -> Dict[str, Any]:
+    """The observations of saved states (`save_state`, or `step_many(states=True).states`),
+    drawn from the rows as they lie: no world of this substrate is loaded or changed, no slot of
+    a rollout is written.  `observations`: names among `state_leaves()` (default: those among
+    this substrate's own leaves); `rows`: the rows to draw, in order, repeats allowed (default:
+    all R of them).  Returns a dict from name to a device tensor [R, ...] ([R, P, ...] for a
+    per-player leaf) that holds, for each row, what the leaf held right after the step (or
+    reset) the row was saved behind.  Ordered on the current stream; no host synchronisation."""
+    leaves = self._state_leaves(observations)
+    if not isinstance(states, WorldStates):
+      raise ValueError("observe_states takes the WorldStates of save_state or step_many(states=True)")
+    states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
+    self._eng.use_current_stream()
+    return {n: self._eng.observe_states(states.data, k, rows=rows, fingerprint=states.fingerprint)
+            for n, k in leaves.items()}
+
   # dmlab2d properties (wrappers/base.py:64-84): Melting Pot's levels register none —
   # the calls exist and answer like dmlab2d does for an unknown key
   def list_property(self, key: str = ""):
@@ -1003,7 +1055,7 @@ class Substrate:
     return leaves
 
   def step_many(self, actions, repeat: Optional[int] = None, events: bool = False,
-                observations=()) -> StepManyResult:
+                observations=(), states: bool = False) -> StepManyResult:
     """K steps in ONE launch, bit-identical to K calls of `step` (batched substrates).
     `actions`: ints [K, N, P] (a device tensor is read in place; it may be a column slice
     [:, a:b] of a wider one), or one block [N, P] with `repeat=K`.  Returns the per-step
@@ -1017,7 +1069,11 @@ class Substrate:
     "READY_TO_SHOOT", "INVENTORY", ...), or True for all of them: the result is then a
     `StepManyTrajectory`, whose `.observation[name]` is that leaf of every step, [K, N, ...],
     row k what `step` k would have left in the leaf (kept from the row before wherever a
-    step does not write it, e.g. while a world is frozen)."""
+    step does not write it, e.g. while a world is frozen).
+    `states=True`: the result (a `StepManyTrajectory`) has `.states`, the worlds' records after
+    every step as a `WorldStates` of K x N rows — step k of world w is row k * N + w, what
+    `save_state` would have given after `step` k; it loads with `load_state` and draws with
+    `observe_states` like any other."""
     if not self._batched:
       raise ValueError("step_many steps a batch of worlds: build the substrate with num_worlds > 1")
     leaves = self._many_leaves(observations)
@@ -1028,14 +1084,15 @@ class Substrate:
     a, _ = _many_actions(t, actions, repeat, self._eng.N, self._eng.P, limit)
     self._observables.action.on_next(actions)
     self._eng.use_current_stream()
-    r = self._submit_many(a, repeat, events, None, leaves)
-    return _many_result(r, leaves, self._emit(self._timestep()))
+    r = self._submit_many(a, repeat, events, None, leaves, bool(states))
+    return _many_result(r, leaves, self._emit(self._timestep()),
+                        self._eng.state_fingerprint if states else None)
 
-  def _submit_many(self, a, repeat, events, out, leaves=None):
+  def _submit_many(self, a, repeat, events, out, leaves=None, states=False):
     """One K-step launch of the engine on actions `a` as `_many_actions` prepared them
-    (`leaves`: name -> kind of the observations to stack per step)."""
+    (`leaves`: name -> kind of the observations to stack per step; `states`: the records too)."""
     t = self._eng._torch
-    more = {}
+    more = {"states": True} if states else {}
     if leaves:
       more["observations"] = tuple(dict.fromkeys(
           k for k in leaves.values() if k not in _FIVE_NAMES))
@@ -1631,11 +1688,14 @@ class MixtureSubstrate:
     return self._members[0].step_leaves()
 
   def step_many(self, actions, repeat: Optional[int] = None, events: bool = False,
-                observations=()) -> StepManyResult:
+                observations=(), states: bool = False) -> StepManyResult:
     """As `Substrate.step_many`, over the members: one K-step launch per member, each reading
     its columns [:, off_i:off_i + n_i] of `actions` and writing its columns of the shared
     [K, N, ...] per-step tensors, those of `observations` included (nothing is copied or
-    concatenated)."""
+    concatenated).  There is no `states=True` here: the members' records differ in size."""
+    if states:
+      raise ValueError("step_many: a mixture has no per-step states (states=True): its members' records "
+                       "differ in size and fingerprint; step the members' substrates on their own")
     first = self._members[0]
     leaves = first._many_leaves(observations)
     t = first._eng._torch

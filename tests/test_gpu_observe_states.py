@@ -1,0 +1,309 @@
+"""Observations of saved world states (MpStatesObserve, Engine.observe_states): the views of rows
+of a bank, drawn where the rows lie.  Every result is compared byte for byte — with what the
+launches that wrote the rows left in the bound leaves, with `pool_rgb` of the full views, with the
+CPU oracle replayed to the same steps — on one pack per level kernel, on rows with dead avatars,
+rows of finished episodes and rows of fresh ones, for contiguous rows, gathered rows, more rows
+than the engine has worlds and a single row.  The engine that draws is left exactly as it was, rows
+travel between engines of one fingerprint, and every refusal happens on the host."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import states_recipe as recipe
+import util
+from meltingpot_amd import engine
+
+pytestmark = pytest.mark.gpu
+
+E = engine
+N, SAVE_AT = recipe.N, recipe.SAVE_AT
+GATHER = [4, 0, 0, 2]
+
+
+def _same(got, want, what):
+  assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape)
+  assert torch.equal(got, want), (what, (got != want).nonzero()[:4].tolist())
+
+
+def _same_leaf(kind, got, want, what):
+  """Equal leaves; of EVENTS the header row and the rows it counts, in any order (rows beyond the
+  count are not written)."""
+  if kind != E.OBS_EVENTS:
+    return _same(got, want, what)
+  for a, b in zip(got.cpu().numpy(), want.cpu().numpy()):
+    n = int(a[0, 0])
+    assert tuple(a[0]) == tuple(b[0]) and sorted(map(tuple, a[1:1 + n].tolist())) == sorted(map(tuple, b[1:1 + n].tolist())), what
+
+
+def _no_faults(eng):
+  assert not eng.fault_words()[:10].any(), eng.fault_words()[:10]
+
+
+# 1. against the launches that wrote the rows
+@pytest.mark.parametrize("name", recipe.PACKS)
+def test_rows_are_drawn_as_the_launches_that_wrote_them_drew_them(name):
+  road = recipe.road(name)
+  assert (road["step_type"][16] == 2).all() and (road["step_type"][17] == 0).all()
+  if name in recipe.DEAD_AVATARS:
+    assert any(road["dead"][s] for s in SAVE_AT)   # rows with a dead avatar are among those compared
+  e = engine.Engine(recipe.pack(name), N, device=0)   # never reset: the rows are another engine's
+  assert e.state_fingerprint == road["fingerprint"]
+  gather = torch.tensor(GATHER, device=e.device)
+  for kind in road["kinds"]:
+    for s in SAVE_AT:
+      bank, want = road["banks"][s], road["views"][s][kind]
+      _same(e.observe_states(bank, kind), want, (name, kind, s))
+      _same(e.observe_states(bank, kind, rows=GATHER), want[gather], (name, kind, s, "rows"))
+    # all five saves in one bank: R = 25 > N rows in one call, and one row alone
+    _same(e.observe_states(road["all"], kind), road["all_views"][kind], (name, kind, "25 rows"))
+    _same(e.observe_states(road["all"][13:14], kind), road["all_views"][kind][13:14], (name, kind, "one row"))
+    _same(e.observe_states(road["all"], kind, rows=[13]), road["all_views"][kind][13:14], (name, kind, "rows=[13]"))
+  e.sync()
+  _no_faults(e)
+  e.close()
+
+
+# 2. the pooled kinds
+@pytest.mark.parametrize("name,world_pool", [("clean_up", 1), ("collaborative_cooking__cramped", 8)])
+def test_pooled_kinds_equal_pool_rgb_of_the_full_views(name, world_pool):
+  road = recipe.road(name)
+  e = engine.Engine(recipe.pack(name), N, device=0, world_pool=world_pool)
+  full = {k: road["all_views"][k].cpu().numpy() for k in (E.OBS_RGB, E.OBS_WORLD_RGB)}
+  rng = np.random.default_rng(11)
+  picks = {1: [17], 5: [3, 24, 9, 9, 15], 37: rng.integers(0, 25, size=37).tolist()}
+  kinds = [(kind, E.OBS_RGB, k) for k, kind in E.OBS_RGB_POOL.items()] + [(E.OBS_WORLD_RGB, E.OBS_WORLD_RGB, world_pool)]
+  for kind, source, k in kinds:
+    pooled = engine.pool_rgb(full[source], k)
+    for count, rows in picks.items():
+      got = e.observe_states(road["all"], kind, rows=rows)
+      assert got.shape[0] == count
+      assert np.array_equal(got.cpu().numpy(), pooled[rows]), (name, kind, count)
+    assert np.array_equal(e.observe_states(road["all"], kind).cpu().numpy(), pooled), (name, kind, "contiguous")
+  e.sync()
+  _no_faults(e)
+  e.close()
+
+
+# 3. straight against the oracle
+@pytest.mark.parametrize("name", ["clean_up", "commons_harvest__open"])
+def test_rows_are_drawn_as_the_oracle_draws_its_worlds(name):
+  road = recipe.road(name)
+  e = engine.Engine(recipe.pack(name), N, device=0)
+  A = road["actions"]
+  for s in (8, 17):
+    got = {k: e.observe_states(road["banks"][s], k).cpu().numpy()
+           for k in (E.OBS_RGB, E.OBS_WORLD_RGB, E.OBS_LAYER)}
+    for w, o in enumerate(util.make_oracles(recipe.pack(name), N)):
+      o.reset()
+      for k in range(s):
+        if o.done:   # step 17: the step after LAST restarts the episode
+          o.reset()
+        else:
+          o.step(A[k, w])
+      assert np.array_equal(got[E.OBS_WORLD_RGB][w], o.render_world()), (name, s, w)
+      for p in range(o.P):
+        assert np.array_equal(got[E.OBS_RGB][w, p], o.render_agent(p)), (name, s, w, p)
+        assert np.array_equal(got[E.OBS_LAYER][w, p], o.layer_view(p)), (name, s, w, p)
+      o.close()
+  e.close()
+
+
+# 4. the engine is left as it was
+def _draw_everything(e, road):
+  for kind in road["kinds"] + (E.OBS_RGB_POOL4,):
+    e.observe_states(road["banks"][8], kind)
+    e.observe_states(road["all"], kind, rows=[7, 7, 21, 0, 13, 2, 19])
+
+
+def test_the_engine_is_left_as_it_was():
+  name = "clean_up"
+  road = recipe.road(name)
+  A = torch.from_numpy(road["actions"]).to("cuda:0")
+  ring = (E.OBS_RGB, E.OBS_LAYER, E.OBS_REWARD)
+  plain = (E.OBS_WORLD_RGB, E.OBS_READY_TO_SHOOT, E.OBS_POSITION, E.OBS_ORIENTATION, E.OBS_STEP_TYPE,
+           E.OBS_EVENTS)
+
+  def build():
+    eng = engine.Engine(recipe.pack(name), N, device=0)
+    bufs = {k: eng.bind_ring(k, slots=3) for k in ring}
+    bufs.update({k: eng.bind(k) for k in plain})
+    eng.reset()
+    for s in range(5):
+      eng.step(A[s])
+    return eng, bufs
+
+  e, bufs = build()
+  twin, twin_bufs = build()
+  before = (e.snapshot(), e.counters(), e.ring, {k: v.clone() for k, v in bufs.items()}, e.plan)
+  _draw_everything(e, road)
+  _draw_everything(e, road)
+  after = (e.snapshot(), e.counters(), e.ring, bufs, e.plan)
+  assert np.array_equal(before[0], after[0]) and before[1] == after[1] and before[2] == after[2]
+  assert before[4] == after[4]
+  for k in bufs:
+    _same_leaf(k, after[3][k], before[3][k], ("bound buffer", k))
+  for s in range(5, 13):   # the next 8 steps: as on the twin that never drew a row
+    e.step(A[s])
+    twin.step(A[s])
+    if s % 3 == 0:
+      _draw_everything(e, road)
+    for k in bufs:
+      _same_leaf(k, bufs[k], twin_bufs[k], ("step", s, k))
+  assert np.array_equal(e.snapshot(), twin.snapshot()) and e.counters() == twin.counters()
+  assert e.ring == twin.ring
+  _no_faults(e)
+  e.close(); twin.close()
+
+
+def test_an_engine_that_only_drew_rows_is_still_probed_with_real_steps():
+  road = recipe.road("clean_up")
+  probes = []
+  for draws in (False, True):
+    e = engine.Engine(recipe.pack("clean_up"), 64, device=0)
+    if draws:
+      _draw_everything(e, road)
+    e.place(E.OBS_WORLD_RGB, candidates=2)
+    probes.append(e.placement[E.OBS_WORLD_RGB]["probe"])
+    if draws:   # ... and the probe left the rows' views as drawable as before
+      _same(e.observe_states(road["banks"][8], E.OBS_LAYER), road["views"][8][E.OBS_LAYER], "after the probe")
+    e.close()
+  assert probes[0] == probes[1] == "stepped behind a copy", probes
+
+
+# 5. rows travel
+def test_rows_of_another_engine_are_drawn_and_rows_of_another_level_refused():
+  name = "clean_up"
+  road = recipe.road(name)
+  other = engine.Engine(recipe.pack(name), 3, device=0, world_offset=11)
+  kinds = recipe.record_kinds(other)
+  bufs = {k: other.bind(k) for k in kinds}
+  A = torch.from_numpy(recipe.actions(other.P, other.num_actions, n=3)).to(other.device)
+  other.reset()
+  for s in range(8):
+    other.step(A[s])
+  bank = other.save_worlds()
+  e = engine.Engine(recipe.pack(name), N, device=0)
+  for kind in kinds:
+    _same(e.observe_states(bank, kind, fingerprint=other.state_fingerprint), bufs[kind], ("travel", kind))
+  # an engine of two worlds draws 25 rows (more than its own draw plan holds)
+  small = engine.Engine(recipe.pack(name), 2, device=0)
+  for kind in (E.OBS_RGB, E.OBS_WORLD_RGB, E.OBS_LAYER, E.OBS_POSITION):
+    _same(small.observe_states(road["all"], kind), road["all_views"][kind], ("25 rows on 2 worlds", kind))
+    rows = list(range(24, -1, -1))
+    _same(small.observe_states(road["all"], kind, rows=rows), road["all_views"][kind].flip(0),
+          ("25 gathered rows on 2 worlds", kind))
+  small.sync()
+  _no_faults(small)
+  # rows of another level
+  foreign = engine.Engine(recipe.pack("coins"), 2, device=0)
+  foreign.reset()
+  rows = foreign.save_worlds()
+  padded = torch.zeros((2, e.info.world_state_bytes), dtype=torch.uint8, device=e.device)
+  with pytest.raises(ValueError, match="fingerprint"):
+    e.observe_states(padded, E.OBS_RGB, fingerprint=foreign.state_fingerprint)
+  with pytest.raises(ValueError, match="bank must be"):
+    e.observe_states(rows, E.OBS_RGB, fingerprint=foreign.state_fingerprint)
+  for eng in (other, e, small, foreign):
+    eng.close()
+
+
+# 6. refusals, through the raw request
+def _rc(e, **fields):
+  req = E.MpStatesObserve(ctypes.sizeof(E.MpStatesObserve))
+  for k, v in fields.items():
+    setattr(req, k, v)
+  return e._L.mp_snapshot(e._h, ctypes.addressof(req), ctypes.sizeof(req))
+
+
+def test_refusals_happen_on_the_host_and_leave_everything_alone():
+  name = "clean_up"
+  road = recipe.road(name)
+  e = engine.Engine(recipe.pack(name), N, device=0)
+  e.reset()
+  L = e._L
+  S = e.info.world_state_bytes
+  bank, fp = road["banks"][8], e.state_fingerprint
+  rows = torch.tensor([1, 0], dtype=torch.int32, device=e.device)
+  per = {k: int(np.prod(e.shapes[k][0][1:])) * torch.empty((), dtype=e.shapes[k][1]).element_size()
+         for k in e.shapes}
+  dst = torch.full((N * per[E.OBS_RGB] + 64,), 0xAB, dtype=torch.uint8, device=e.device)
+  snap = e.snapshot()
+  ok = dict(kind=E.OBS_POSITION, fingerprint=fp, bank=bank.data_ptr(), bank_rows=N, count=N,
+            dst=dst.data_ptr(), dst_bytes=dst.numel())
+
+  def refused(what, code=E.MP_ERR_INVALID, **kw):
+    assert _rc(e, **dict(ok, **kw)) == code, (what, L.mp_last_error())
+    return L.mp_last_error()
+
+  refused("NULL bank", bank=None)
+  refused("NULL dst", dst=None)
+  refused("count", count=0)
+  refused("count", count=-3)
+  refused("bank_rows", bank_rows=0)
+  refused("struct_size", struct_size=60)
+  assert b"fingerprint" in refused("fingerprint", fingerprint=fp ^ 1)
+  refused("dst_bytes", dst_bytes=N * per[E.OBS_POSITION] - 1)
+  refused("dst_bytes of a pixel kind", kind=E.OBS_RGB, dst_bytes=N * per[E.OBS_RGB] - 1)
+  refused("more rows than the bank has", count=N + 1)
+  assert b"16-byte" in refused("pooled alignment", kind=E.OBS_RGB_POOL2, dst=dst.data_ptr() + 8)
+  refused("element alignment", kind=E.OBS_POSITION, dst=dst.data_ptr() + 2)
+  refused("element alignment", kind=E.OBS_READY_TO_SHOOT, dst=dst.data_ptr() + 4)
+  refused("element alignment", kind=E.OBS_LAYER, dst=dst.data_ptr() + 1)
+  host = torch.zeros((N, S), dtype=torch.uint8)
+  pinned = torch.zeros((N, S), dtype=torch.uint8).pin_memory()
+  for b in (host, pinned):
+    refused("a bank in host memory", bank=b.data_ptr())
+  refused("rows in host memory", rows=torch.zeros(N, dtype=torch.int32).data_ptr())
+  refused("dst in host memory", dst=host.data_ptr(), dst_bytes=host.numel())
+  assert b"allocation" in refused("bank past its allocation", bank_rows=1 << 30, rows=rows.data_ptr(), count=2)
+  refused("rows past their allocation", rows=rows.data_ptr(), count=1 << 28, dst_bytes=1 << 40)
+  for kind in (-1, 24, 99):
+    refused("kind out of range", kind=kind)
+  for kind in (E.OBS_REWARD, E.OBS_AUX0, E.OBS_STEP_TYPE, E.OBS_DISCOUNT, E.OBS_COLLECTIVE_REWARD, E.OBS_EVENTS,
+               E.OBS_AUX1, E.OBS_ZAP_MATRIX, E.OBS_INTERACTION_INVENTORIES, E.OBS_MATRIX_CUMULANTS,
+               E.OBS_INTERACTION_REWARDS):
+    assert b"not a function of the record" in refused("transition kind", kind=kind), kind
+  refused("a kind the level does not have", code=-5, kind=E.OBS_INVENTORY)   # MP_ERR_UNSUPPORTED
+  assert L.mp_snapshot(None, ctypes.addressof(E.MpStatesObserve(64)), 64) == E.MP_ERR_INVALID
+  # nothing was launched: dst and the engine are as they were
+  e.sync()
+  assert bool((dst == 0xAB).all()) and np.array_equal(e.snapshot(), snap)
+  _no_faults(e)
+  # a rows[i] outside the bank is never read: its element stays, the next sync() says so, once
+  bad = torch.tensor([3, 99, 1, -1, 3], dtype=torch.int32, device=e.device)
+  keep = torch.tensor([0, 2, 4], device=e.device)
+  for kind in (E.OBS_POSITION, E.OBS_READY_TO_SHOOT, E.OBS_LAYER, E.OBS_RGB, E.OBS_WORLD_RGB, E.OBS_RGB_POOL8):
+    shape, dtype = e.shapes[kind]
+    out = torch.full((5,) + tuple(shape[1:]), 7, dtype=dtype, device=e.device)
+    e.observe_states(bank, kind, rows=bad, out=out)
+    with pytest.raises(ValueError, match=r"MpStatesObserve: rows\[\d\] = (99|-1) is not a row"):
+      e.sync()
+    e.sync()   # reported once
+    assert bool((out[1] == 7).all()) and bool((out[3] == 7).all()), kind
+    want = e.observe_states(bank, kind, rows=[3, 1, 3])
+    _same(out[keep], want, ("the rows that are rows", kind))
+  # the kinds drawn from gathered rows keep eight such elements of a request (any eight); a ninth
+  # and a tenth hold what an empty record shows, and the next request starts with eight again
+  many = torch.tensor([3, 99, -1, 5, -7, 1 << 20, 1, 25, -2, 77, N, -1 << 30], dtype=torch.int32, device=e.device)
+  good, bad = [0, 6], [1, 2, 3, 4, 5, 7, 8, 9, 10, 11]
+  empty = torch.zeros((1, S), dtype=torch.uint8, device=e.device)
+  for kind in (E.OBS_RGB, E.OBS_LAYER, E.OBS_RGB, E.OBS_WORLD_RGB):
+    shape, dtype = e.shapes[kind]
+    blank = e.observe_states(empty, kind)[0]
+    assert not bool((blank == 7).all())
+    out = torch.full((12,) + tuple(shape[1:]), 7, dtype=dtype, device=e.device)
+    e.observe_states(bank, kind, rows=many, out=out)
+    with pytest.raises(ValueError, match="MpStatesObserve: rows"):
+      e.sync()
+    e.sync()
+    _same(out[good], e.observe_states(bank, kind, rows=[3, 1]), ("ten bad indices", kind))
+    kept = [i for i in bad if bool((out[i] == 7).all())]
+    assert len(kept) == 8, (kind, kept)
+    for i in set(bad) - set(kept):
+      _same(out[i], blank, ("beyond the eighth", kind, i))
+  e.sync()
+  assert np.array_equal(e.snapshot(), snap)
+  _no_faults(e)
+  e.close()
