@@ -575,6 +575,103 @@ typedef struct {
   uint64_t reserved;       /* 0 */
 } MpStatesObserve;
 
+/* The layout of a record, told by the library: what the bytes of a saved row are, so that a
+ * caller can read and edit world states by field.  Rides mp_snapshot, recognised by its size:
+ * `bytes` = sizeof(MpStateLayout), `host_buf` a HOST MpStateLayout with struct_size set to it.
+ * include/mp_state_check.h wraps it as an inline C function.
+ *   eng != NULL: the engine's layout (pack / pack_len / cfg are ignored).
+ *   eng == NULL: the layout an engine created with mp_create(pack, pack_len, cfg) would have,
+ *     worked out on the host alone (no device is touched; errors as mp_create's).
+ * A row is uint8 [world_stride]: grid_planes planes of H x W bytes, layer-major — the L render
+ * planes (a byte is a state id of the pack, 0 = nothing) and behind them the level's hidden planes
+ * — then whatever the level keeps up to grid_bytes (the matrix games' player block, at
+ * player_block, else -1), padding up to grid_pad, and at grid_pad the tail: tail_bytes bytes whose
+ * named fields `fields[0 .. num_fields)` lists with offset (from grid_pad), element size and
+ * element count.  The names and offsets come from the one list of the tail's members the library
+ * itself is compiled from.  `fields` may be NULL (num_fields is still set); fields_cap smaller than
+ * num_fields is MP_ERR_INVALID. */
+typedef struct {
+  char name[16];
+  int32_t offset;          /* bytes from grid_pad */
+  int32_t elem_bytes;      /* 1, 2, 4 or 8 */
+  int32_t count;           /* elements: 16 for a per-avatar array, 1 for a scalar */
+  int32_t reserved;
+} MpStateField;
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(MpStateLayout) */
+  uint32_t layout_version; /* out: MP_RECORD_LAYOUT_VERSION of the library */
+  const void* pack;        /* the host-only question (eng == NULL) */
+  uint64_t pack_len;
+  const MpConfig* cfg;
+  /* out */
+  int32_t map_h, map_w, num_layers, num_players, num_states;
+  int32_t grid_planes, grid_bytes, grid_pad, world_stride, tail_bytes;
+  int32_t max_frames, avatar_layer, substrate, player_block;
+  int32_t reserved[2];
+  uint64_t fingerprint;    /* out: MP_STATES_FINGERPRINT's value */
+  MpStateField* fields;    /* HOST array [fields_cap], or NULL */
+  int32_t fields_cap;
+  int32_t num_fields;      /* out */
+} MpStateLayout;
+
+/* Is a record well-formed?  Rows that came from MP_STATES_SAVE or MP_STEP_ROW_STATE always are;
+ * rows a caller edited, or built, may not be, and a step uses a record's bytes as cell
+ * coordinates, state ids and table indices.  The check judges a row against the rules below
+ * WITHOUT loading it; nothing of the engine's is written.  Rides mp_snapshot, recognised by its
+ * size: `bytes` = sizeof(MpStatesCheck), `host_buf` a HOST MpStatesCheck with struct_size set to
+ * it.  include/mp_state_check.h wraps the three forms as inline C functions.
+ *
+ * A verdict is two int32: (rule, offset word).  (0, 0): well-formed.  Otherwise the
+ * lexicographically smallest pair among the row's violations; the offset word is the byte offset
+ * in the row of the offending byte (for rule 7: sub-code << 24 | byte offset):
+ *   1  a byte of a render plane is >= the pack's state count
+ *   2  a non-zero byte of render plane l is a state of another layer
+ *   3  a tail value out of range: aori >= 4, aalive > 1 (avatars < num_players only), done, cont
+ *      or started not 0 or 1, step outside [0, max_frames]
+ *   4  a living avatar with ax >= W or ay >= H, or whose cell of the avatar plane does not hold
+ *      one of its own avatar states
+ *   5  an avatar state of avatar p in a cell other than (ax[p], ay[p]), or anywhere while p is
+ *      not alive
+ *   6  orders_step neither 0 nor step + 1; or, with orders_step != 0, a stream of next_orders
+ *      whose nibbles over the positions < num_players are not a permutation of the avatars
+ *   7  a level's own rule (DESIGN.md section 3.9 lists them with the source lines they protect)
+ * Never judged: the padding, the bytes of avatars >= num_players, ctr[], reward_fx.
+ *
+ * MP_CHECK_ROWS (eng != NULL): out (device int32 [count][2]) element i := the verdict of row
+ *   rows[i] (device int32 [count]; NULL: row i, count <= bank_rows) of `bank` (device uint8
+ *   [bank_rows][S]).  Enqueued on the engine's stream, no synchronisation.  A rows[i] outside the
+ *   bank is never read: element i is (-1, rows[i]) and the next synchronising call returns
+ *   MP_ERR_INVALID.
+ * MP_CHECK_HOST (eng == NULL; pack, pack_len, cfg as for mp_create): the same verdicts of HOST
+ *   rows into a HOST out, by the same rule functions compiled for the host; no device is touched.
+ *   A rows[i] outside the bank gives (-1, rows[i]).
+ * MP_CHECK_FILTER (eng != NULL): for a checked load.  rows = src (device int32 [N], as
+ *   MP_STATES_LOAD takes it), count = N, out = checked (device int32 [N]): checked[w] := src[w]
+ *   when row src[w] is well-formed, and also when src[w] is -1 or no row of the bank (the load
+ *   handles both); -1 otherwise — the world is then left alone by a load from `checked`, and the
+ *   next synchronising call returns MP_ERR_INVALID naming the world, the row and the rule (of
+ *   several refused worlds one is named).  The engine stays usable.
+ * Refused before any launch, MP_ERR_INVALID: NULL bank or out, count < 1 or bank_rows < 1, an
+ * unknown op, a fingerprint that is not the engine's (host form: the pack's), out_bytes too
+ * small, a bank that is not 16-byte aligned, rows or out not 4-byte aligned, device memory that
+ * is not the engine's device's or not inside one allocation, count != N for a filter. */
+enum { MP_CHECK_ROWS = 1, MP_CHECK_HOST = 2, MP_CHECK_FILTER = 3 };
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(MpStatesCheck) */
+  int32_t op;              /* MP_CHECK_* */
+  uint64_t fingerprint;    /* in: the rows' */
+  const void* pack;        /* MP_CHECK_HOST */
+  uint64_t pack_len;
+  const MpConfig* cfg;
+  const void* bank;        /* uint8 [bank_rows][S] */
+  int32_t bank_rows;
+  int32_t count;
+  const int32_t* rows;     /* int32 [count] or NULL (FILTER: src[N]) */
+  void* out;               /* int32 [count][2] (FILTER: int32 [N]) */
+  uint64_t out_bytes;
+  uint64_t reserved;       /* 0 */
+} MpStatesCheck;
+
 /* Action sequences: K steps of every world in ONE submission, bit-identical to K calls of the
  * single-step entry points (mp_step, or mp_step_fields with fields = 1) with the same actions,
  * which also hands back the transition of every one of the K steps.  For planners that fork a
@@ -826,7 +923,15 @@ int mp_box_fill(MpEngine* eng, MpObsKind kind, int32_t reps, MpBoxFill* out);
  * reports it as MP_ERR_HIP until mp_reset(eng, seeds, NULL) — a reset of ALL
  * worlds — clears it (the worlds of a stalled launch are incomplete; resetting
  * them makes the engine usable again).  Word 8: 1 + the world that paid an
- * interaction reward outside every colour interval (the_matrix; reported once).  The words live in host memory: this call never touches the
+ * interaction reward outside every colour interval (the_matrix; reported once).
+ * Words 9-11: an index a world-state launch skipped, or a row a checked load refused (word 9 =
+ * world or position + 1, word 10 = the index or row, word 11 = what: 1 a load's src[], 2 a save's
+ * world list, 3 an MpStatesObserve's rows[], 4 | rule << 8 a row an MpStatesCheck filter refused,
+ * 5 an MpStatesCheck's rows[]); of several such reports of one launch the three words may belong
+ * to different ones.  Words 12-15: the refused row of a checked load once more, claimed by ONE
+ * refused world of the launch (word 12 = world + 1, 13 = the row, 14 = the rule, 15 = the offset
+ * word), reported first.  Each is reported once by the next synchronising call (MP_ERR_INVALID)
+ * and cleared.  The words live in host memory: this call never touches the
  * device, so it answers even while a kernel is stuck.  (Words 16.. are used by
  * the -DMP_FRAME_TRACE developer build.) */
 int mp_fault_words(const MpEngine* eng, uint32_t out[64]);

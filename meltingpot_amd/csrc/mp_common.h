@@ -449,7 +449,8 @@ enum { STEP_MODE_STEP = 0, STEP_MODE_RESET = 1, STEP_MODE_FIELDS = 2, STEP_MODE_
 
 // DevTables::fault words of the world-state entry points (mp_save_worlds / mp_load_worlds): an
 // index outside its range that a launch skipped — word 9 = world (or row) + 1, word 10 = the
-// index, word 11 = 1 for a load's src[], 2 for a save's world list.  The next synchronising call
+// index, word 11 = 1 for a load's src[], 2 for a save's world list (3: state_obs.h; 4, 5 and
+// words 12-15, a checked load's refused row: state_check.h).  The next synchronising call
 // reports it (MP_ERR_INVALID) and clears it.
 enum { FAULT_STATE_INDEX = 9 };
 

@@ -24,6 +24,7 @@
 #include "step_common.h"
 #include "step_many.h"
 #include "state_obs.h"
+#include "state_check.h"
 
 void launch_step(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
                  hipStream_t stream);
@@ -181,6 +182,10 @@ struct MpEngine {
   uint8_t* d_obs_stash = nullptr;
   uint64_t obs_stash_bytes = 0;
   int32_t* d_layer_lut = nullptr;  // StepOutputs::layer_lut [P][kLayerLutRow]
+  // An MpStatesCheck request's view of the pack (state_check.h): built by mp_create's host stage,
+  // and its copy in device memory for k_check_states
+  state_check::CheckTables check = {};
+  state_check::CheckTables* d_check = nullptr;
   StepOutputs outputs() const {
     StepOutputs o = own;
     if (bound[MP_OBS_REWARD]) o.reward = (double*)bound[MP_OBS_REWARD];
@@ -340,11 +345,28 @@ int sync_and_check(MpEngine* e, const char* who) {
                 "(the reference asserts there, the_matrix/components.lua:282-290); the indicator "
                 "shows the first colour", who, world);
   }
+  if (f[kFaultCheckWorld] != 0) {
+    // a row a checked load refused (state_check.h): words of its own, which the load that follows
+    // the filter cannot overwrite with an index it reports itself
+    const uint32_t world = f[kFaultCheckWorld] - 1, row = f[kFaultCheckWorld + 1], rule = f[kFaultCheckWorld + 2],
+                   offset_word = f[kFaultCheckWorld + 3];
+    e->h_fault[kFaultCheckWorld] = 0;   // reported once; the engine stays usable
+    if ((f[FAULT_STATE_INDEX + 2] & 255u) == kFaultCheckRefused) e->h_fault[FAULT_STATE_INDEX] = 0;
+    return fail(MP_ERR_INVALID,
+                "%s: checked MP_STATES_LOAD: row %d, which src[%u] names, is not a well-formed record "
+                "(rule %u, offset word 0x%x); world %u was left as it was", who, (int)row, world, rule,
+                offset_word, world);
+  }
   if (f[FAULT_STATE_INDEX] != 0) {
     const uint32_t at = f[FAULT_STATE_INDEX] - 1, index = f[FAULT_STATE_INDEX + 1];
     const bool load = f[FAULT_STATE_INDEX + 2] == 1;
     const bool observe = f[FAULT_STATE_INDEX + 2] == kFaultObserveRow;
+    const uint32_t what = f[FAULT_STATE_INDEX + 2];
     e->h_fault[FAULT_STATE_INDEX] = 0;   // reported once; the engine stays usable
+    if (what == kFaultCheckRow)
+      return fail(MP_ERR_INVALID,
+                  "%s: MpStatesCheck: rows[%u] = %d is not a row of the bank; element %u of out is (-1, %d)",
+                  who, at, (int)index, at, (int)index);
     if (observe)
       return fail(MP_ERR_INVALID,
                   "%s: MpStatesObserve: rows[%u] = %d is not a row of the bank; element %u of the "
@@ -985,6 +1007,13 @@ int create_on_device(MpEngine* e, const MpConfig& cfg, DecodedPack* d) {
   return plan_views(e, dev);
 }
 
+// The rules' tables of an MpStatesCheck request where k_check_states reads them.
+int upload_check_tables(MpEngine* e) {
+  HIP_TRY(hipMalloc((void**)&e->d_check, sizeof(state_check::CheckTables)));
+  HIP_TRY(hipMemcpy(e->d_check, &e->check, sizeof(state_check::CheckTables), hipMemcpyHostToDevice));
+  return MP_OK;
+}
+
 // mp_create's host stage: the config checked and copied (older, shorter layouts of MpConfig and
 // MpDevOptions completed), the pack copied, roles applied, decoded and checked.  No HIP call.
 struct HostStage {
@@ -1112,8 +1141,10 @@ int mp_create(const void* pack, uint64_t pack_len, const MpConfig* cfg,
   HIP_TRY(hipSetDevice(cfg->device));
 
   MpEngine* e = new MpEngine();
+  build_check_tables(d, &e->check);   // (of the host decode: create_on_device decodes against the device copy)
   e->pack = std::move(copy);
-  const int rc = create_on_device(e, *cfg, &d);
+  int rc = create_on_device(e, *cfg, &d);
+  if (rc == MP_OK) rc = upload_check_tables(e);
   if (rc != MP_OK) {
     mp_destroy(e);
     return rc;
@@ -1130,7 +1161,7 @@ void mp_destroy(MpEngine* e) {
   if (e->h_fault) (void)hipHostFree(e->h_fault);
   void* bufs[] = {e->d_pack, e->d_extra, e->d_stepblob, e->d_debug, e->d_state, e->d_scalars,
                   e->d_actions, e->d_fields, e->d_mask, e->d_seeds, e->d_atlas, e->d_ctr, e->d_claim,
-                  e->d_layer_lut, e->d_obs_rows, e->d_obs_stash};
+                  e->d_layer_lut, e->d_obs_rows, e->d_obs_stash, e->d_check};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   for (int i = 0; i < MpEngine::kHostSlots; ++i)
@@ -1743,6 +1774,108 @@ uint64_t mp_snapshot_bytes(const MpEngine* e) {
   return e ? (uint64_t)e->N * e->t.world_stride : 0;
 }
 
+// An MpStateLayout request (include/mp_engine.h; carried by mp_snapshot; `e` may be NULL: the
+// host-only question).  The tail's fields are state_check.h's list of WorldTail's members.
+static int state_layout(const MpEngine* e, MpStateLayout* r) {
+  static const char kWho[] = "MpStateLayout";
+  if (r->struct_size != sizeof(MpStateLayout))
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r->struct_size, sizeof(MpStateLayout));
+  MpStateField* fields = r->fields;
+  const int32_t cap = r->fields_cap;
+  state_check::CheckTables ck;
+  uint64_t fingerprint;
+  int player_block = -1;
+  if (e) {
+    ck = e->check;
+    fingerprint = e->fingerprint;
+    if (e->substrate == MPK_SUBSTRATE_THE_MATRIX) player_block = e->sub.mx.player_block;
+  } else {
+    HostStage h;
+    if (int rc = host_stage(r->pack, r->pack_len, r->cfg, &h)) return rc;
+    build_check_tables(h.d, &ck);
+    fingerprint = state_fingerprint(h.pack, h.d.t);
+    if (h.d.sub.substrate == MPK_SUBSTRATE_THE_MATRIX) player_block = h.d.sub.mx.player_block;
+  }
+  if (fields && cap < state_check::kNumTailFields)
+    return fail(MP_ERR_INVALID, "%s: fields_cap %d, the tail has %d fields", kWho, cap, state_check::kNumTailFields);
+  r->layout_version = MP_RECORD_LAYOUT_VERSION;
+  r->map_h = ck.H; r->map_w = ck.W; r->num_layers = ck.L; r->num_players = ck.P; r->num_states = ck.nstates;
+  r->grid_planes = ck.grid_planes; r->grid_bytes = ck.grid_bytes; r->grid_pad = ck.grid_pad;
+  r->world_stride = ck.world_stride; r->tail_bytes = (int32_t)sizeof(WorldTail);
+  r->max_frames = ck.max_frames; r->avatar_layer = ck.avatar_layer; r->substrate = ck.substrate;
+  r->player_block = player_block;
+  r->reserved[0] = r->reserved[1] = 0;
+  r->fingerprint = fingerprint;
+  r->num_fields = state_check::kNumTailFields;
+  for (int i = 0; fields && i < state_check::kNumTailFields; ++i) {
+    const state_check::TailField& f = state_check::kTailFields[i];
+    memset(&fields[i], 0, sizeof fields[i]);
+    snprintf(fields[i].name, sizeof fields[i].name, "%s", f.name);
+    fields[i].offset = f.offset; fields[i].elem_bytes = f.elem; fields[i].count = f.count;
+  }
+  return MP_OK;
+}
+
+// An MpStatesCheck request (include/mp_engine.h; carried by mp_snapshot).  Everything is checked
+// before the one launch; the launch writes `out` and, for a refused row or a bad index, the
+// fault words — nothing else of the engine's.
+static int states_check(MpEngine* e, const MpStatesCheck& r) {
+  static const char kWho[] = "MpStatesCheck";
+  if (r.struct_size != sizeof(MpStatesCheck))
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpStatesCheck));
+  if (r.op != MP_CHECK_ROWS && r.op != MP_CHECK_HOST && r.op != MP_CHECK_FILTER)
+    return fail(MP_ERR_INVALID, "%s: unknown op %d", kWho, r.op);
+  if ((r.op == MP_CHECK_HOST) != (e == nullptr))
+    return fail(MP_ERR_INVALID, "%s: MP_CHECK_HOST goes without an engine, the other forms with one", kWho);
+  if (!r.bank || !r.out) return fail(MP_ERR_INVALID, "%s: NULL bank or out", kWho);
+  if (r.count < 1 || r.bank_rows < 1)
+    return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", kWho, r.count, r.bank_rows);
+  if (!r.rows && (r.op == MP_CHECK_FILTER || r.count > r.bank_rows))
+    return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are judged (count %d, the bank has "
+                "%d rows); a filter needs its src", kWho, r.count, r.bank_rows);
+  const uint64_t count = (uint64_t)r.count, need = count * (r.op == MP_CHECK_FILTER ? 4u : 8u);
+  if (r.out_bytes < need)
+    return fail(MP_ERR_INVALID, "%s: %d verdicts need %llu bytes, out has %llu", kWho, r.count,
+                (unsigned long long)need, (unsigned long long)r.out_bytes);
+  if (((uintptr_t)r.out & 3) || ((uintptr_t)r.rows & 3))
+    return fail(MP_ERR_INVALID, "%s: rows %p and out %p must be 4-byte aligned", kWho, (const void*)r.rows, r.out);
+  if (r.op == MP_CHECK_HOST) {
+    HostStage h;
+    if (int rc = host_stage(r.pack, r.pack_len, r.cfg, &h)) return rc;
+    const uint64_t fingerprint = state_fingerprint(h.pack, h.d.t);
+    if (r.fingerprint != fingerprint)
+      return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this pack's (%016llx)", kWho,
+                  (unsigned long long)r.fingerprint, (unsigned long long)fingerprint);
+    state_check::CheckTables ck;
+    build_check_tables(h.d, &ck);
+    check_rows_host(ck, (const uint8_t*)r.bank, r.bank_rows, r.rows, r.count, (int32_t*)r.out);
+    return MP_OK;
+  }
+  if (r.fingerprint != e->fingerprint)
+    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this engine's (%016llx): "
+                "they were saved by an engine of another pack, player count or record layout", kWho,
+                (unsigned long long)r.fingerprint, (unsigned long long)e->fingerprint);
+  if (r.op == MP_CHECK_FILTER && r.count != e->N)
+    return fail(MP_ERR_INVALID, "%s: a filter takes the src of a load, one entry per world (count %d, the "
+                "engine has %d worlds)", kWho, r.count, e->N);
+  if ((uintptr_t)r.bank & 15)   // (records are read in 16-byte lines)
+    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", kWho, r.bank);
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = check_bank(e, r.bank, (uint64_t)r.bank_rows * (uint64_t)e->t.world_stride, "MpStatesCheck (bank)"))
+    return rc;
+  if (r.rows)
+    if (int rc = check_bank(e, r.rows, count * 4, "MpStatesCheck (rows)")) return rc;
+  if (int rc = check_bank(e, r.out, need, "MpStatesCheck (out)")) return rc;
+  if (r.op == MP_CHECK_FILTER)
+    launch_filter_states(e->d_check, (const uint8_t*)r.bank, r.bank_rows, r.rows, r.count, (int32_t*)r.out,
+                         e->t.fault, e->stream);
+  else
+    launch_check_states(e->d_check, (const uint8_t*)r.bank, r.bank_rows, r.rows, r.count, (int32_t*)r.out,
+                        e->t.fault, e->stream);
+  HIP_TRY(hipGetLastError());
+  return MP_OK;
+}
+
 static_assert(sizeof(MpStatesObserve) == 64 && sizeof(MpStatesObserve) != sizeof(MpKernelVariant) &&
                   sizeof(MpStatesObserve) != sizeof(MpWorldStates) && sizeof(MpStatesObserve) != sizeof(MpStepMany) &&
                   sizeof(MpStatesObserve) != sizeof(MpStepTrajectory),
@@ -1751,6 +1884,16 @@ static_assert(sizeof(MpKernelVariant) != sizeof(MpWorldStates) && sizeof(MpKerne
                   sizeof(MpStepTrajectory) != sizeof(MpKernelVariant) && sizeof(MpStepTrajectory) != sizeof(MpWorldStates) &&
                   sizeof(MpStepTrajectory) != sizeof(MpStepMany) && sizeof(MpStepTrajectory) < 448,
               "mp_snapshot / mp_restore tell their requests apart by size");
+static_assert(sizeof(MpStateLayout) == 120 && sizeof(MpStatesCheck) == 88 && sizeof(MpStateField) == 32,
+              "the layouts include/mp_engine.h documents");
+#define MP_SIZE_DIFFERS(A)                                                                          \
+  (sizeof(A) != sizeof(MpStatesObserve) && sizeof(A) != sizeof(MpKernelVariant) &&                  \
+   sizeof(A) != sizeof(MpWorldStates) && sizeof(A) != sizeof(MpStepMany) && sizeof(A) != sizeof(MpStepTrajectory))
+static_assert(MP_SIZE_DIFFERS(MpStateLayout) && MP_SIZE_DIFFERS(MpStatesCheck) &&
+                  sizeof(MpStateLayout) != sizeof(MpStatesCheck) && sizeof(MpStateLayout) < 448 &&
+                  sizeof(MpStatesCheck) < 448,
+              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
+#undef MP_SIZE_DIFFERS
 // An MpKernelVariant request (carried by mp_snapshot; `e` may be NULL: the host-only question).
 static int kernel_variant(const MpEngine* e, MpKernelVariant* r) {
   if (r->struct_size != sizeof(MpKernelVariant))
@@ -1788,6 +1931,12 @@ int mp_snapshot(MpEngine* e, void* buf, uint64_t bytes) {
     MpStatesObserve r;   // (read only: nothing is written back)
     memcpy(&r, buf, sizeof r);
     return states_observe(e, r);
+  }
+  if (buf && bytes == sizeof(MpStateLayout)) return state_layout(e, (MpStateLayout*)buf);
+  if (buf && bytes == sizeof(MpStatesCheck)) {
+    MpStatesCheck r;   // (read only: the verdicts go to r.out)
+    memcpy(&r, buf, sizeof r);
+    return states_check(e, r);
   }
   if (!e || !buf || bytes != mp_snapshot_bytes(e))
     return fail(MP_ERR_INVALID, "mp_snapshot: bad buffer");

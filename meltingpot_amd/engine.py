@@ -255,6 +255,186 @@ def states_observe_request(L, handle, **fields) -> MpStatesObserve:
   return req
 
 
+# The layout of a record and the check of edited records (include/mp_engine.h: MpStateLayout,
+# MpStatesCheck), carried by mp_snapshot
+class MpStateField(ctypes.Structure):
+  _fields_ = [("name", ctypes.c_char * 16), ("offset", ctypes.c_int32), ("elem_bytes", ctypes.c_int32),
+              ("count", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+_LAYOUT_INTS = ("map_h", "map_w", "num_layers", "num_players", "num_states", "grid_planes", "grid_bytes",
+                "grid_pad", "world_stride", "tail_bytes", "max_frames", "avatar_layer", "substrate",
+                "player_block")
+
+
+class MpStateLayout(ctypes.Structure):
+  _fields_ = ([("struct_size", ctypes.c_uint32), ("layout_version", ctypes.c_uint32),
+               ("pack", ctypes.c_void_p), ("pack_len", ctypes.c_uint64), ("cfg", ctypes.POINTER(MpConfig))] +
+              [(n, ctypes.c_int32) for n in _LAYOUT_INTS] + [("reserved", ctypes.c_int32 * 2)] +
+              [("fingerprint", ctypes.c_uint64), ("fields", ctypes.POINTER(MpStateField)),
+               ("fields_cap", ctypes.c_int32), ("num_fields", ctypes.c_int32)])
+
+
+MP_CHECK_ROWS, MP_CHECK_HOST, MP_CHECK_FILTER = 1, 2, 3
+
+
+class MpStatesCheck(ctypes.Structure):
+  _fields_ = [("struct_size", ctypes.c_uint32), ("op", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
+              ("pack", ctypes.c_void_p), ("pack_len", ctypes.c_uint64), ("cfg", ctypes.POINTER(MpConfig)),
+              ("bank", ctypes.c_void_p), ("bank_rows", ctypes.c_int32), ("count", ctypes.c_int32),
+              ("rows", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_bytes", ctypes.c_uint64),
+              ("reserved", ctypes.c_uint64)]
+
+
+# The rules of a check (include/mp_engine.h: MpStatesCheck).  A verdict is
+# (rule, offset word): (0, 0) for a well-formed row.
+RULE_OK = 0
+RULE_STATE_RANGE = 1     # a render plane's byte is no state of the pack
+RULE_STATE_LAYER = 2     # a render plane's byte is a state of another layer
+RULE_TAIL_RANGE = 3      # aori, aalive, done, cont, started, step
+RULE_AVATAR_CELL = 4     # a living avatar is off the map, or not where the tail says
+RULE_AVATAR_STRAY = 5    # an avatar's state where the tail does not put that avatar
+RULE_ORDERS = 6          # the cached visiting orders
+RULE_LEVEL = 7           # a level's own rule; the offset word's top byte is its sub-code
+RULE_NAMES = {RULE_OK: "well-formed", RULE_STATE_RANGE: "a plane byte that is no state of the pack",
+              RULE_STATE_LAYER: "a state in another layer's plane", RULE_TAIL_RANGE: "a tail value out of range",
+              RULE_AVATAR_CELL: "a living avatar that is not where the tail says",
+              RULE_AVATAR_STRAY: "an avatar state where the tail does not put that avatar",
+              RULE_ORDERS: "the cached visiting orders", RULE_LEVEL: "a level rule"}
+# RULE_LEVEL sub-codes
+LEVEL_BYTE_FIELD = 1     # + k: per-avatar byte array k of the tail outside the level's range (1 .. 14)
+LEVEL_AUX_COUNT = 16
+LEVEL_PLANE0, LEVEL_PLANE1 = 17, 18
+LEVEL_MARKER_OFF_MAP, LEVEL_MARKER_CELL, LEVEL_FOLLOWER = 19, 20, 21
+LEVEL_NAMES = {LEVEL_AUX_COUNT: "aux_count outside the level's table", LEVEL_PLANE0: "a plane byte the level cannot take",
+               LEVEL_PLANE1: "a plane byte the level cannot take",
+               LEVEL_MARKER_OFF_MAP: "a marker on the map whose position is no cell",
+               LEVEL_MARKER_CELL: "a marker on the map whose cell of the marker plane is empty",
+               LEVEL_FOLLOWER: "an avatar without its connected piece on its cell"}
+
+
+def level_offset(sub: int, offset: int) -> int:
+  """The offset word of a RULE_LEVEL verdict."""
+  return (int(sub) << 24) | (int(offset) & 0xffffff)
+
+
+class StateLayout:
+  """What the bytes of a saved row are (an MpStateLayout request): `H`, `W`, `L` (render planes),
+  `P`, `nstates`, `grid_planes` (render + hidden), `grid_bytes`, `grid_pad` (where the tail
+  starts), `world_stride` (a row's bytes), `tail_bytes`, `max_frames`, `avatar_layer`,
+  `player_block` (the matrix games' per-player block, else -1), `layout_version`, `fingerprint`,
+  and `fields`: name -> (offset from grid_pad, element bytes, element count) of every member of
+  the tail, as the library itself lists them."""
+
+  def __init__(self, req: MpStateLayout, fields):
+    self.H, self.W, self.L, self.P = req.map_h, req.map_w, req.num_layers, req.num_players
+    self.nstates = req.num_states
+    for n in _LAYOUT_INTS[5:]:
+      setattr(self, n, int(getattr(req, n)))
+    self.layout_version = int(req.layout_version)
+    self.fingerprint = int(req.fingerprint)
+    self.fields = {f.name.decode(): (int(f.offset), int(f.elem_bytes), int(f.count)) for f in fields}
+
+  def field_offset(self, name: str, index: int = 0) -> int:
+    """Byte offset in a row of element `index` of tail field `name`."""
+    off, elem, count = self.fields[name]
+    if not 0 <= index < count:
+      raise IndexError(f"{name} has {count} elements")
+    return self.grid_pad + off + elem * index
+
+  def cell_offset(self, plane: int, x: int, y: int) -> int:
+    """Byte offset in a row of cell (x, y) of plane `plane`."""
+    return (plane * self.H + y) * self.W + x
+
+  def describe(self, rule: int, offset: int) -> str:
+    """A verdict in words: the rule, and the field or the plane and cell its offset names."""
+    rule, offset = int(rule), int(offset) & 0xffffffff
+    if rule == RULE_OK:
+      return "well-formed"
+    if rule == -1:
+      return f"row index {offset - (1 << 32) if offset >= 1 << 31 else offset} is no row of the bank"
+    what = RULE_NAMES.get(rule, f"rule {rule}")
+    if rule == RULE_LEVEL:
+      sub, offset = offset >> 24, offset & 0xffffff
+      what = LEVEL_NAMES.get(sub, "a per-avatar byte outside the level's range")
+    return f"rule {rule}: {what} at {self.where(offset)}"
+
+  def where(self, offset: int) -> str:
+    """The plane and cell, or the tail field and element, of byte `offset` of a row."""
+    hw = self.H * self.W
+    if offset < self.grid_planes * hw:
+      plane, cell = divmod(offset, hw)
+      kind = "plane" if plane < self.L else "hidden plane"
+      return f"{kind} {plane} cell (x={cell % self.W}, y={cell // self.W})"
+    if offset < self.grid_pad:
+      return f"byte {offset} (behind the planes)"
+    t = offset - self.grid_pad
+    for name, (off, elem, count) in self.fields.items():
+      if off <= t < off + elem * count:
+        return f"{name}[{(t - off) // elem}]" if count > 1 else name
+    return f"byte {offset}"
+
+
+def _layout_request(L, handle, pack_bytes=None, num_players: int = 0, dev=None) -> StateLayout:
+  fields = (MpStateField * 64)()
+  req = MpStateLayout(ctypes.sizeof(MpStateLayout))
+  req.fields = ctypes.cast(fields, ctypes.POINTER(MpStateField))
+  req.fields_cap = 64
+  keep = None
+  if handle is None:
+    keep = _host_config(pack_bytes, num_players, dev)
+    req.pack, req.pack_len, req.cfg = ctypes.addressof(keep[0]), len(pack_bytes), ctypes.pointer(keep[1])
+  _check(L, L.mp_snapshot(handle, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpStateLayout)")
+  return StateLayout(req, fields[:req.num_fields])
+
+
+def _host_config(pack_bytes: bytes, num_players: int = 0, dev=None):
+  """(pack buffer, MpConfig, options) of a host-only request; keep the tuple alive over the call."""
+  cfg = MpConfig(ctypes.sizeof(MpConfig), 0, 1, 1, 0, 0, None, int(num_players))
+  opts = None
+  if dev:
+    opts = MpDevOptions(ctypes.sizeof(MpDevOptions), max_composites=-1)
+    for k, v in dev.items():
+      setattr(opts, k, int(v))
+    cfg.dev = ctypes.pointer(opts)
+  return ctypes.create_string_buffer(pack_bytes, len(pack_bytes)), cfg, opts
+
+
+def state_layout(pack_bytes: bytes, *, num_players: int = 0, dev: Optional[Dict[str, int]] = None) -> StateLayout:
+  """The layout of the rows an engine created on this pack would save, worked out on the host (an
+  MpStateLayout request without an engine: no GPU needed)."""
+  return _layout_request(load_library(), None, pack_bytes, num_players, dev)
+
+
+def check_states_host(pack_bytes: bytes, rows, *, fingerprint: Optional[int] = None, which=None,
+                      num_players: int = 0, dev: Optional[Dict[str, int]] = None) -> np.ndarray:
+  """Verdicts int32 [R, 2] = (rule, offset word) of host rows (uint8 [M, S] array) against the
+  pack, by the library's host-only check (MP_CHECK_HOST: the kernel's own rule functions compiled
+  for the host; no GPU needed).  `which`: the rows to judge (default: all).  `fingerprint`: the
+  rows' (default: the pack's)."""
+  L = load_library()
+  bank = np.ascontiguousarray(rows, np.uint8)
+  if bank.ndim != 2 or bank.shape[0] < 1:
+    raise ValueError("check_states_host: rows must be a uint8 array [M, S]")
+  keep = _host_config(pack_bytes, num_players, dev)
+  layout = _layout_request(L, None, pack_bytes, num_players, dev)
+  if bank.shape[1] != layout.world_stride:
+    raise ValueError(f"check_states_host: rows of {bank.shape[1]} bytes, the pack's are {layout.world_stride}")
+  idx = None if which is None else np.ascontiguousarray(np.asarray(which).reshape(-1), np.int32)
+  count = bank.shape[0] if idx is None else int(idx.size)
+  if count < 1:
+    raise ValueError("check_states_host: no rows to judge")
+  out = np.zeros((count, 2), np.int32)
+  req = MpStatesCheck(ctypes.sizeof(MpStatesCheck), MP_CHECK_HOST,
+                      layout.fingerprint if fingerprint is None else int(fingerprint))
+  req.pack, req.pack_len, req.cfg = ctypes.addressof(keep[0]), len(pack_bytes), ctypes.pointer(keep[1])
+  req.bank, req.bank_rows, req.count = bank.ctypes.data, int(bank.shape[0]), count
+  req.rows = None if idx is None else idx.ctypes.data
+  req.out, req.out_bytes = out.ctypes.data, out.nbytes
+  _check(L, L.mp_snapshot(None, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpStatesCheck)")
+  return out
+
+
 # Action sequences (include/mp_engine.h: MpStepMany), carried by mp_restore
 STEP_MANY_MAX = 4096   # MP_STEP_MANY_MAX
 # the five kinds step_many returns by name, in MpStepMany.per_step's order
@@ -1119,11 +1299,54 @@ class Engine:
     self._state_args = w   # (kept until the next call: the launch may not have run yet)
     return out
 
-  def load_worlds(self, bank, src, fingerprint: Optional[int] = None):
+  def state_layout(self) -> StateLayout:
+    """What the bytes of this engine's rows are (an MpStateLayout request)."""
+    if getattr(self, "_layout", None) is None:
+      self._layout = _layout_request(self._L, self._h)
+    return self._layout
+
+  def check_states(self, bank, rows=None, out=None, fingerprint: Optional[int] = None):
+    """Verdicts int32 [R, 2] = (rule, offset word) of rows of `bank` (uint8 [M, S] device tensor),
+    judged where they lie by one launch: (0, 0) is a well-formed row, anything else names the
+    smallest rule the row breaks (RULE_*) and the byte (`state_layout().describe`).  rows: the
+    rows to judge, in order, repeats allowed (None: every row).  Nothing of the engine's is
+    written.  `fingerprint`: the rows' (default: this engine's).  Enqueued on the current stream;
+    does not synchronise."""
+    t = self._torch
+    S = int(self.info.world_state_bytes)
+    if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
+        bank.shape[1] != S or not bank.is_contiguous()):
+      raise ValueError(f"check_states: bank must be a contiguous uint8 tensor [M, {S}]")
+    if bank.shape[0] < 1:
+      raise ValueError("check_states: the bank has no rows")
+    r = None if rows is None else self._device_ints(rows, "rows")
+    count = int(bank.shape[0]) if r is None else int(r.numel())
+    if count < 1:
+      raise ValueError("check_states: no rows to judge")
+    if out is None:
+      out = t.empty((count, 2), dtype=t.int32, device=self.device)
+    elif (not isinstance(out, t.Tensor) or out.dtype != t.int32 or tuple(out.shape) != (count, 2) or
+          not out.is_contiguous() or out.device != self.device):
+      raise ValueError(f"check_states: out must be a contiguous int32 tensor of shape {(count, 2)} on {self.device}")
+    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    self.use_current_stream()
+    req = MpStatesCheck(ctypes.sizeof(MpStatesCheck), MP_CHECK_ROWS, fp)
+    req.bank, req.bank_rows, req.count = bank.data_ptr(), int(bank.shape[0]), count
+    req.rows = None if r is None else r.data_ptr()
+    req.out, req.out_bytes = out.data_ptr(), out.numel() * 4
+    _check(self._L, self._L.mp_snapshot(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
+           "mp_snapshot (MpStatesCheck)")
+    self._check_args = (bank, r, out)   # (kept until the next call: the launch may not have run yet)
+    return out
+
+  def load_worlds(self, bank, src, fingerprint: Optional[int] = None, check: bool = False):
     """World w starts from row src[w] of `bank` (uint8 [M, S] device tensor from save_worlds, of
     this engine or another with the same state_fingerprint); src[w] = -1 leaves world w alone.
     One launch, shaped like a masked reset: the bound views and ring slot are written by it.
-    `fingerprint`: the rows' (default: this engine's).  Enqueued on the current stream."""
+    `fingerprint`: the rows' (default: this engine's).  check=True: the rows src names are judged
+    first (`check_states`' rules, one more launch) and a world whose row is malformed is left as
+    it is; the next synchronising call (`sync`) raises ValueError naming the world, the row and
+    the rule.  Enqueued on the current stream."""
     t = self._torch
     S = int(self.info.world_state_bytes)
     if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
@@ -1136,9 +1359,19 @@ class Engine:
       raise ValueError(f"load_worlds: src must have {self.N} entries (got {s.numel()})")
     fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
     self.use_current_stream()
+    if check:
+      checked = t.empty_like(s)
+      req = MpStatesCheck(ctypes.sizeof(MpStatesCheck), MP_CHECK_FILTER, fp)
+      req.bank, req.bank_rows, req.count = bank.data_ptr(), int(bank.shape[0]), self.N
+      req.rows, req.out, req.out_bytes = s.data_ptr(), checked.data_ptr(), self.N * 4
+      _check(self._L, self._L.mp_snapshot(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
+             "mp_snapshot (MpStatesCheck)")
+      loaded = checked
+    else:
+      loaded = s
     world_states_request(self._L, self._h, MP_STATES_LOAD, bank=bank.data_ptr(),
-                         bank_rows=int(bank.shape[0]), src=s.data_ptr(), fingerprint=fp)
-    self._state_args = s
+                         bank_rows=int(bank.shape[0]), src=loaded.data_ptr(), fingerprint=fp)
+    self._state_args = (s, loaded)   # (kept until the next call: the launches may not have run yet)
 
   def observe_states(self, bank, kind: int, rows=None, out=None, fingerprint: Optional[int] = None):
     """Observation `kind` of rows of `bank` (uint8 [M, S] device tensor from save_worlds or

@@ -150,7 +150,10 @@ class WorldStates:
   whose row i is one world's whole record, and `fingerprint`, the engine's state fingerprint
   (MP_STATES_FINGERPRINT) — rows load into any substrate of the same level, player count and
   roles (`Substrate.load_state`), of any num_worlds.  `states[idx]` selects rows (an int, a
-  slice, a sequence or an integer tensor) and is again a WorldStates."""
+  slice, a sequence or an integer tensor) and is again a WorldStates.
+  `edited` says that somebody may have written into `data` through `Substrate.state_fields`:
+  `load_state` then checks the rows it loads.  The constructor and everything the engine hands
+  out leave it False; `states[idx]` carries it along."""
 
   def __init__(self, data, fingerprint: int):
     import torch
@@ -163,6 +166,7 @@ class WorldStates:
       raise ValueError(f"a state fingerprint is a 64-bit unsigned value (got {fingerprint})")
     self.data = data.contiguous()
     self.fingerprint = fingerprint
+    self.edited = False
 
   def __len__(self) -> int:
     return int(self.data.shape[0])
@@ -182,7 +186,9 @@ class WorldStates:
       if index.dtype == torch.bool or index.dim() != 1:
         raise ValueError("WorldStates rows are selected by an int, a slice or a 1-D list of ints")
       rows = self.data[index.to(self.data.device, torch.int64)]
-    return WorldStates(rows, self.fingerprint)
+    out = WorldStates(rows, self.fingerprint)
+    out.edited = self.edited
+    return out
 
   def check(self, fingerprint: int, row_bytes: int):
     """ValueError unless these rows were saved by an engine with this fingerprint and row size."""
@@ -194,6 +200,90 @@ class WorldStates:
 
   def __repr__(self):
     return f"WorldStates({len(self)} x {self.row_bytes} B, fingerprint {self.fingerprint:016x})"
+
+
+# what Python calls the tail fields whose C names are abbreviations (every other field keeps its
+# C name); offsets, sizes and counts are the library's (engine_lib.StateLayout.fields)
+_FIELD_NAMES = {"ax": "avatar_x", "ay": "avatar_y", "aori": "orientation", "aalive": "alive"}
+
+
+class SubstrateStateLayout:
+  """`Engine.state_layout()` plus the pack's names: `layer_names` in plane order (the L render
+  planes), `state_names` by state id with `state_id(name)`, `state_layers[state]` (the plane a
+  state lives in, -1: never on the map), `avatar_states[p]` = (alive_state, wait_state) of player p, `avatar_layer`, `hidden_planes` (the level's private planes behind
+  the render planes).  Every attribute of the engine's layout (H, W, L, P, nstates, grid_planes,
+  grid_pad, world_stride, fields, fingerprint, describe(), ...) is reachable here too."""
+
+  def __init__(self, layout, tables):
+    self._layout = layout
+    split = lambda name: tuple(n.decode() for n in bytes(tables[name]).split(b"\0")[:-1])
+    self.layer_names = split("layer_names")[:layout.L]
+    self.state_names = split("state_names")[:layout.nstates]
+    self.state_layers = tuple(int(v) for v in tables["state_layer"][:layout.nstates])   # (-1: never on the map)
+    alive = [int(v) for v in tables["avatar_alive_state"]]
+    wait = [int(v) for v in tables["avatar_wait_state"]]
+    self.avatar_states = tuple((alive[p], wait[p]) for p in range(layout.P))
+    self.hidden_planes = layout.grid_planes - layout.L
+
+  def __getattr__(self, name):
+    return getattr(self._layout, name)
+
+  def state_id(self, name: str) -> int:
+    """The state id (a plane byte) of the state called `name` ("avatar1.player1", ...)."""
+    try:
+      return self.state_names.index(name)
+    except ValueError:
+      raise KeyError(f"no state {name!r} in this pack") from None
+
+
+class StateFields:
+  """Named views of the rows of a `WorldStates` (`Substrate.state_fields`).  Every attribute is a
+  view that shares memory with `states.data` — reading costs nothing, writing edits the rows:
+    grid                 uint8 [R, grid_planes, H, W]: state ids per plane and cell, the level's
+                         hidden planes behind the L render planes
+    avatar_x, avatar_y, orientation, alive, and the other per-avatar byte arrays of the tail
+                         (ztimer, ctimer, flag0, flag1, freeze, removal, aflags, nozap, level,
+                         tsince)   uint8 [R, P]
+    achange              int32 [R, P]
+    step, frame, done, cont, aux_count, group_change, episode, started, reward_fx, orders_step
+                         int32 [R]
+    seed                 int64 [R] (the bit pattern of the u64)
+    ctr                  int32 [R, 8]
+    next_orders          int16 [R, P]
+  `names` lists them.  What each field means is the record's own documentation (DESIGN.md §3.9;
+  csrc/mp_common.h: WorldTail)."""
+
+  def __init__(self, data, layout):
+    import torch
+    R = int(data.shape[0])
+    if data.dim() != 2 or int(data.shape[1]) != layout.world_stride or not data.is_contiguous():
+      raise ValueError(f"state rows must be a contiguous uint8 [R, {layout.world_stride}] tensor")
+    dtypes = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+    planes = layout.grid_planes * layout.H * layout.W
+    self.grid = data[:, :planes].view(R, layout.grid_planes, layout.H, layout.W)
+    names = ["grid"]
+    for cname, (off, elem, count) in layout.fields.items():
+      lo = layout.grid_pad + off
+      # (a column slice of the rows reinterpreted: the row stride and every offset are multiples
+      # of the element size)
+      v = data[:, lo:lo + elem * count].view(dtypes[elem])
+      if count == 1:
+        v = v[:, 0]
+      elif count == 16:   # a per-avatar array: the avatars that play
+        v = v[:, :layout.P]
+      name = _FIELD_NAMES.get(cname, cname)
+      setattr(self, name, v)
+      names.append(name)
+    self.names = tuple(names)
+
+
+def _resolve_check(states, check: Optional[bool]) -> bool:
+  """load_state's `check`: None means "iff the rows may have been edited"."""
+  if check is None:
+    return bool(getattr(states, "edited", False))
+  if not isinstance(check, (bool, np.bool_)):
+    raise ValueError(f"check must be None, True or False (got {check!r})")
+  return bool(check)
 
 
 class Array:
@@ -909,19 +999,60 @@ class Substrate:
     self._eng.use_current_stream()
     return WorldStates(self._eng.save_worlds(worlds), self._eng.state_fingerprint)
 
-  def load_state(self, states: WorldStates, src) -> TimeStep:
+  def state_layout(self) -> SubstrateStateLayout:
+    """What the bytes of this substrate's saved rows are: the engine's layout (planes, tail
+    fields with their offsets, as the library lists them) with the pack's layer and state names."""
+    if getattr(self, "_state_layout", None) is None:
+      from meltingpot_amd import pack as pack_lib
+      self._state_layout = SubstrateStateLayout(self._eng.state_layout(), pack_lib.loads(self._eng.pack_bytes))
+    return self._state_layout
+
+  def state_fields(self, states: WorldStates) -> StateFields:
+    """The rows of `states` by named field: views that share memory with `states.data`, for
+    reading (how many apples are left in each row?) and for editing (start every world with an
+    empty orchard).  Marks `states` as edited, so that `load_state` checks what it loads; ask
+    `check_states` yourself any time.  Edit the planes and the tail so that they agree — an
+    avatar's state byte lies at (avatar_x, avatar_y) of the avatar layer's plane — and after
+    changing `seed`, `episode` or `step` set `orders_step` to 0: the cached visiting orders are a
+    function of those three and are drawn again when absent."""
+    if not isinstance(states, WorldStates):
+      raise ValueError("state_fields takes the WorldStates of save_state or step_many(states=True)")
+    states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
+    fields = StateFields(states.data, self.state_layout())
+    states.edited = True
+    return fields
+
+  def check_states(self, states: WorldStates, rows=None):
+    """Is every row a record this level's kernels can take?  int32 [R, 2] device tensor of
+    (rule, offset word) per row — (0, 0) for a well-formed row, else the smallest rule it breaks
+    (engine.RULE_*) and where (`state_layout().describe(rule, offset)`).  The rows are judged
+    where they lie; nothing of this substrate changes.  No host synchronisation."""
+    if not isinstance(states, WorldStates):
+      raise ValueError("check_states takes the WorldStates of save_state or step_many(states=True)")
+    states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
+    self._eng.use_current_stream()
+    return self._eng.check_states(states.data, rows=rows, fingerprint=states.fingerprint)
+
+  def load_state(self, states: WorldStates, src, check: Optional[bool] = None) -> TimeStep:
     """World w continues from row src[w] of `states` (-1: world w is left as it is), as the
     world the row was saved from would: same seed, episode, step and future under the same
     actions.  One submission, like a masked reset: the returned TimeStep is FIRST for loaded
     worlds (LAST for a row saved from a finished episode), with the observations of their
-    records; `src` has num_worlds entries (an int is enough for one world)."""
+    records; `src` has num_worlds entries (an int is enough for one world).
+    check: None checks the rows iff `states.edited` (they went through `state_fields`); True /
+    False force it.  A checked load leaves a world whose row is malformed as it is, and the next
+    synchronising call raises ValueError naming the world, the row and the rule."""
     if not isinstance(states, WorldStates):
       raise ValueError("load_state takes the WorldStates of save_state")
     states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
     if isinstance(src, (int, np.integer)):
       src = [int(src)]
+    check = _resolve_check(states, check)
     self._eng.use_current_stream()
-    self._eng.load_worlds(states.data, src, states.fingerprint)
+    if check:
+      self._eng.load_worlds(states.data, src, states.fingerprint, check=True)
+    else:   # (exactly the call, and the launches, of a load before there was a check)
+      self._eng.load_worlds(states.data, src, states.fingerprint)
     self._submissions += 1
     return self._emit(self._timestep())
 
