@@ -672,6 +672,83 @@ typedef struct {
   uint64_t reserved;       /* 0 */
 } MpStatesCheck;
 
+/* Are two records the same state?  Comparing rows byte for byte says "different" of equal states:
+ * ctr[] and reward_fx are the bookkeeping of the engine a row was loaded into, the cached visiting
+ * orders (orders_step, next_orders) may be present or absent, and the padding and the bytes of
+ * avatars >= num_players hold whatever an edit left.  The hash is a 64-bit function of exactly the
+ * bytes a state's future and its observations depend on, computed on the device where the rows
+ * lie, 8 bytes a row: transposition tables and duplicate pruning in tree search, proof that a
+ * regenerated rollout is the recorded one, exploration cells from a chosen subset of planes and
+ * fields.  Rides mp_snapshot, recognised by its size: `bytes` = sizeof(MpStatesHash), `host_buf` a
+ * HOST MpStatesHash with struct_size set to it.  include/mp_state_hash.h wraps the forms as
+ * inline C functions.
+ *
+ * The function.  A row is S = world_stride bytes (a multiple of 16).  With w_j the little-endian
+ * u32 at byte 4 j, m_j the u32 with 0xFF in every INCLUDED byte of that word, and
+ *   fmix64(h): h ^= h >> 33; h *= 0xff51afd7ed558ccd; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53;
+ *              h ^= h >> 33   (u64),
+ *   c_j = fmix64((u64)(j + 1) << 32 | (w_j & m_j))   for every j with m_j != 0,
+ *   H   = fmix64(sum_j c_j mod 2^64).
+ * fmix64 is a bijection: changing one included byte always changes H, changing an excluded byte
+ * never does.  Hashes compare only between rows of one fingerprint, hashed with one spec.
+ *
+ * Included bytes.  flags == 0, the default spec, "the state": every byte of the grid_planes planes;
+ * the level's block [player_block, grid_bytes) where the level has one; every field of the tail
+ * but ctr, reward_fx, orders_step and next_orders — of the 16-element (per-avatar) fields only the
+ * elements < num_players.  flags & MP_HASH_CUSTOM: the planes whose bit is set in plane_mask (bit l
+ * = grid plane l; a pack with more than 64 planes is refused), the fields whose bit is set in
+ * field_mask (bit i = fields[i] of MpStateLayout; ctr and next_orders may be named), per-avatar
+ * fields still cut to < num_players, and the level's block with MP_HASH_PLAYER_BLOCK.  Never
+ * included: what lies between the planes and the level's block, the padding up to grid_pad, what
+ * follows the tail's last field.
+ *
+ * MP_HASH_ROWS (eng != NULL): out (device u64 [count]) element i := H of row rows[i] (device int32
+ *   [count]; NULL: row i, count <= bank_rows) of `bank` (device uint8 [bank_rows][S]).  Enqueued on
+ *   the engine's stream, no synchronisation.  A rows[i] outside the bank is never read: element i
+ *   of out keeps what it held, and the next synchronising call returns MP_ERR_INVALID.
+ * MP_HASH_WORLDS (eng != NULL): the same over the engine's own records where they lie (bank and
+ *   bank_rows are ignored): rows is a list of worlds (NULL: every world, count = N).  Refused on
+ *   an engine that has never been reset, like MP_STATES_SAVE.  fingerprint is ignored.
+ * MP_HASH_HOST (eng == NULL; pack, pack_len, cfg as for mp_create): H of HOST rows into a HOST
+ *   out, by the same function compiled for the host; no device is touched.  Every rows[i] inside
+ *   the bank is hashed; if one lies outside, its element keeps what it held and the call returns
+ *   MP_ERR_INVALID naming the first.
+ * MP_HASH_MASK (eng != NULL, or NULL with pack, pack_len, cfg): out (HOST uint8 [S], out_bytes >=
+ *   S) := the spec's byte mask, 0xFF where a byte counts.  Nothing else is read.
+ * The engine keeps the default spec's mask on the device from mp_create on, and the mask of the
+ * most recent custom spec: a request with the default spec or with the custom spec of the request
+ * before only enqueues.  A request with a NEW custom spec waits for the engine's stream once, to
+ * replace that mask (as an MpStatesObserve request that has to grow its scratch does).
+ * Refused before any launch, MP_ERR_INVALID, the engine left as it was: NULL bank or out, count <
+ * 1 or bank_rows < 1, rows == NULL with count > bank_rows (WORLDS: count != N), an unknown op or
+ * flag, a fingerprint that is not the engine's (host form: the pack's), out_bytes too small, a
+ * bank that is not 16-byte aligned, an out that is not 8-byte aligned, rows not 4-byte aligned,
+ * device memory that is not the engine's device's or not inside one allocation, a plane_mask or
+ * field_mask bit that names no plane or no field, MP_HASH_PLAYER_BLOCK on a level without one, a
+ * custom spec that includes no byte.  The request writes `out` and, for a bad index, the fault
+ * words — nothing else of the engine's; an engine nothing else has touched is still untouched to
+ * mp_tune. */
+enum { MP_HASH_ROWS = 1, MP_HASH_WORLDS = 2, MP_HASH_HOST = 3, MP_HASH_MASK = 4 };
+enum { MP_HASH_CUSTOM = 1, MP_HASH_PLAYER_BLOCK = 2 };
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(MpStatesHash) */
+  int32_t op;              /* MP_HASH_* */
+  uint64_t fingerprint;    /* in: the rows' (ROWS, HOST) */
+  const void* pack;        /* MP_HASH_HOST, MP_HASH_MASK without an engine */
+  uint64_t pack_len;
+  const MpConfig* cfg;
+  const void* bank;        /* uint8 [bank_rows][S] (ROWS, HOST) */
+  int32_t bank_rows;
+  int32_t count;
+  const int32_t* rows;     /* int32 [count] or NULL (WORLDS: a world list) */
+  void* out;               /* u64 [count] (MASK: uint8 [S]) */
+  uint64_t out_bytes;
+  uint64_t plane_mask;     /* MP_HASH_CUSTOM: bit l = grid plane l */
+  uint32_t field_mask;     /* MP_HASH_CUSTOM: bit i = tail field i of MpStateLayout */
+  int32_t flags;           /* 0: the default spec; MP_HASH_CUSTOM [| MP_HASH_PLAYER_BLOCK] */
+  uint64_t reserved;       /* 0 */
+} MpStatesHash;
+
 /* Action sequences: K steps of every world in ONE submission, bit-identical to K calls of the
  * single-step entry points (mp_step, or mp_step_fields with fields = 1) with the same actions,
  * which also hands back the transition of every one of the K steps.  For planners that fork a
@@ -778,10 +855,22 @@ typedef struct {
  * never reset writes nothing.  Beam search, branching from the middle of a sequence, a rollout
  * kept as states whose observations an MpStatesObserve request draws later.  Checked like every
  * row, with element size 16: step_bytes >= N * S and a multiple of 16, the buffer 16-byte
- * aligned.  num_rows may therefore reach MP_OBS_KINDS + 1. */
+ * aligned.  num_rows may therefore reach MP_OBS_KINDS + 1.
+ *
+ * Per-step state hashes.  A row may name MP_STEP_ROW_HASH, no observation kind either: row k is
+ * u64 [N], for a started world H (MpStatesHash, the default spec) of what MP_STEP_ROW_STATE's row
+ * k holds — 8 bytes a world-step where the state row costs S, and the same for every level, so
+ * that engines of different levels can share one [K][N total] tensor.  Written over auto-reset
+ * steps and frozen steps alike; a world never reset writes nothing.  Checked like every row, with
+ * element size 8: step_bytes >= N * 8 and a multiple of 8, the buffer 8-byte aligned.  The row
+ * always has the default spec (MpStepRow has no room for one).  (The row's value is not 0x101:
+ * requests that named 0x101 were refused before there was this row, and still are.)  The limit on
+ * num_rows stays MP_OBS_KINDS + 1: the pixel kinds can never be named, so no valid request comes
+ * near it. */
 #define MP_STEP_ROW_STATE 0x100
+#define MP_STEP_ROW_HASH 0x102
 typedef struct {
-  int32_t kind;                /* MpObsKind, or MP_STEP_ROW_STATE */
+  int32_t kind;                /* MpObsKind, MP_STEP_ROW_STATE or MP_STEP_ROW_HASH */
   int32_t reserved;
   void* rows;                  /* device: row 0 */
   uint64_t step_bytes;         /* distance between two rows */
@@ -927,8 +1016,8 @@ int mp_box_fill(MpEngine* eng, MpObsKind kind, int32_t reps, MpBoxFill* out);
  * Words 9-11: an index a world-state launch skipped, or a row a checked load refused (word 9 =
  * world or position + 1, word 10 = the index or row, word 11 = what: 1 a load's src[], 2 a save's
  * world list, 3 an MpStatesObserve's rows[], 4 | rule << 8 a row an MpStatesCheck filter refused,
- * 5 an MpStatesCheck's rows[]); of several such reports of one launch the three words may belong
- * to different ones.  Words 12-15: the refused row of a checked load once more, claimed by ONE
+ * 5 an MpStatesCheck's rows[], 6 an MpStatesHash's rows[] or world list); of several such reports
+ * of one launch the three words may belong to different ones.  Words 12-15: the refused row of a checked load once more, claimed by ONE
  * refused world of the launch (word 12 = world + 1, 13 = the row, 14 = the rule, 15 = the offset
  * word), reported first.  Each is reported once by the next synchronising call (MP_ERR_INVALID)
  * and cleared.  The words live in host memory: this call never touches the

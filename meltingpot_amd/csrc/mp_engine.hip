@@ -25,6 +25,7 @@
 #include "step_many.h"
 #include "state_obs.h"
 #include "state_check.h"
+#include "state_hash.h"
 
 void launch_step(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
                  hipStream_t stream);
@@ -186,6 +187,15 @@ struct MpEngine {
   // and its copy in device memory for k_check_states
   state_check::CheckTables check = {};
   state_check::CheckTables* d_check = nullptr;
+  // An MpStatesHash request's byte masks as u32 [world_stride / 4] in device memory (state_hash.h):
+  // the default spec's from creation (MP_STEP_ROW_HASH reads it too), and the most recent custom
+  // spec's, replaced behind a wait for the stream when a request brings another
+  uint32_t* d_hash_mask = nullptr;
+  uint32_t* d_hash_custom = nullptr;
+  state_hash::Spec hash_custom = {};   // (custom == 0: none yet)
+  state_hash::Layout hash_layout() const {
+    return state_hash::layout_of(check, substrate == MPK_SUBSTRATE_THE_MATRIX ? sub.mx.player_block : -1);
+  }
   StepOutputs outputs() const {
     StepOutputs o = own;
     if (bound[MP_OBS_REWARD]) o.reward = (double*)bound[MP_OBS_REWARD];
@@ -363,6 +373,10 @@ int sync_and_check(MpEngine* e, const char* who) {
     const bool observe = f[FAULT_STATE_INDEX + 2] == kFaultObserveRow;
     const uint32_t what = f[FAULT_STATE_INDEX + 2];
     e->h_fault[FAULT_STATE_INDEX] = 0;   // reported once; the engine stays usable
+    if (what == kFaultHashRow)
+      return fail(MP_ERR_INVALID,
+                  "%s: MpStatesHash: rows[%u] = %d is not a row of the bank (MP_HASH_WORLDS: no world of this "
+                  "engine); element %u of out was left as it was", who, at, (int)index, at);
     if (what == kFaultCheckRow)
       return fail(MP_ERR_INVALID,
                   "%s: MpStatesCheck: rows[%u] = %d is not a row of the bank; element %u of out is (-1, %d)",
@@ -1014,6 +1028,17 @@ int upload_check_tables(MpEngine* e) {
   return MP_OK;
 }
 
+// The default spec's byte mask of an MpStatesHash request where k_hash_rows and the K-step kernels
+// read it.
+int upload_hash_mask(MpEngine* e) {
+  const state_hash::Layout l = e->hash_layout();
+  std::vector<uint32_t> words((size_t)l.world_stride / 4);
+  state_hash::build_byte_mask(l, state_hash::Spec{}, reinterpret_cast<uint8_t*>(words.data()));
+  HIP_TRY(hipMalloc((void**)&e->d_hash_mask, (size_t)l.world_stride));
+  HIP_TRY(hipMemcpy(e->d_hash_mask, words.data(), (size_t)l.world_stride, hipMemcpyHostToDevice));
+  return MP_OK;
+}
+
 // mp_create's host stage: the config checked and copied (older, shorter layouts of MpConfig and
 // MpDevOptions completed), the pack copied, roles applied, decoded and checked.  No HIP call.
 struct HostStage {
@@ -1145,6 +1170,7 @@ int mp_create(const void* pack, uint64_t pack_len, const MpConfig* cfg,
   e->pack = std::move(copy);
   int rc = create_on_device(e, *cfg, &d);
   if (rc == MP_OK) rc = upload_check_tables(e);
+  if (rc == MP_OK) rc = upload_hash_mask(e);
   if (rc != MP_OK) {
     mp_destroy(e);
     return rc;
@@ -1161,7 +1187,8 @@ void mp_destroy(MpEngine* e) {
   if (e->h_fault) (void)hipHostFree(e->h_fault);
   void* bufs[] = {e->d_pack, e->d_extra, e->d_stepblob, e->d_debug, e->d_state, e->d_scalars,
                   e->d_actions, e->d_fields, e->d_mask, e->d_seeds, e->d_atlas, e->d_ctr, e->d_claim,
-                  e->d_layer_lut, e->d_obs_rows, e->d_obs_stash, e->d_check};
+                  e->d_layer_lut, e->d_obs_rows, e->d_obs_stash, e->d_check, e->d_hash_mask,
+                  e->d_hash_custom};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   for (int i = 0; i < MpEngine::kHostSlots; ++i)
@@ -1566,6 +1593,8 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r)
                 (unsigned long long)ablock);
   if ((uintptr_t)r.actions & 3)
     return fail(MP_ERR_INVALID, "%s: actions %p is not 4-byte aligned", who, (const void*)r.actions);
+  // (the limit has not grown with MP_STEP_ROW_HASH: the pixel kinds are never rows, so a request that
+  // names every kind it can, once, and both extra rows stays below it)
   if (r.num_rows < 0 || r.num_rows > MP_OBS_KINDS + 1 || (r.num_rows > 0 && !r.rows))
     return fail(MP_ERR_INVALID, "%s: num_rows %d with rows %p; every kind may be named once", who,
                 r.num_rows, (const void*)r.rows);
@@ -1578,7 +1607,7 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r)
   l.many.actions_step = (long long)(r.actions_step_bytes / 4);
   l.rows.layer_lut = e->d_layer_lut;
   const StepOutputs o = e->outputs();
-  bool seen[MP_OBS_KINDS + 1] = {};
+  bool seen[kStepRowCount] = {};
   for (int i = 0; i < r.num_rows; ++i) {
     const MpStepRow& row = r.rows[i];
     const int kind = row.kind, index = step_row_index(kind);
@@ -1592,8 +1621,9 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r)
     if (!k.name) return fail(MP_ERR_INVALID, "%s: kind %d has no per-step rows", who, kind);
     if (seen[index]) return fail(MP_ERR_INVALID, "%s: %s (kind %d) is named twice", who, k.name, kind);
     seen[index] = true;
-    // (MP_STEP_ROW_STATE: a row is the N records)
-    const uint64_t block = k.place == kRowState ? mp_snapshot_bytes(e) : mp_obs_bytes(e, (MpObsKind)kind);
+    // (MP_STEP_ROW_STATE: a row is the N records; MP_STEP_ROW_HASH: their N hashes)
+    const uint64_t block = k.place == kRowState ? mp_snapshot_bytes(e)
+                           : k.place == kRowHash ? N * 8u : mp_obs_bytes(e, (MpObsKind)kind);
     const uint64_t elem = (uint64_t)k.elem;
     if (block == 0)
       return fail(MP_ERR_UNSUPPORTED, "%s: this substrate has no observation %s (kind %d)", who, k.name, kind);
@@ -1620,6 +1650,7 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r)
       case kRowFin: l.rows.fin[k.slot] = base; l.rows.fin_bytes[k.slot] = bytes; break;
       case kRowLayer: l.rows.layer = base; l.rows.layer_bytes = bytes; break;
       case kRowState: l.state.row = base; l.state.bytes = bytes; break;
+      case kRowHash: l.hash.row = base; l.hash.bytes = bytes; l.hash.mask = e->d_hash_mask; break;
       default: {
         StepRows::Level& lv = l.rows.level[l.rows.n_level++];
         lv.which = kind;   // (launch_step_many resolves the buffer: a rollout ring moves it per submission)
@@ -1876,6 +1907,115 @@ static int states_check(MpEngine* e, const MpStatesCheck& r) {
   return MP_OK;
 }
 
+// An MpStatesHash request (include/mp_engine.h; carried by mp_snapshot; `e` is NULL for the host
+// form).  Everything is checked before the one launch; the launch writes `out` and, for a bad
+// index, the fault words — nothing else of the engine's, and `touched` stays what it was.
+static int states_hash(MpEngine* e, const MpStatesHash& r) {
+  static const char kWho[] = "MpStatesHash";
+  if (r.struct_size != sizeof(MpStatesHash))
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpStatesHash));
+  if (r.op != MP_HASH_ROWS && r.op != MP_HASH_WORLDS && r.op != MP_HASH_HOST && r.op != MP_HASH_MASK)
+    return fail(MP_ERR_INVALID, "%s: unknown op %d", kWho, r.op);
+  if ((r.op == MP_HASH_HOST && e) || ((r.op == MP_HASH_ROWS || r.op == MP_HASH_WORLDS) && !e))
+    return fail(MP_ERR_INVALID, "%s: MP_HASH_HOST goes without an engine, MP_HASH_ROWS and MP_HASH_WORLDS with one", kWho);
+  if ((r.flags & ~(MP_HASH_CUSTOM | MP_HASH_PLAYER_BLOCK)) != 0 ||
+      (!(r.flags & MP_HASH_CUSTOM) && (r.flags != 0 || r.plane_mask != 0 || r.field_mask != 0)))
+    return fail(MP_ERR_INVALID, "%s: flags %d with plane_mask %llx and field_mask %x: the default spec is all "
+                "zeros, a custom one has MP_HASH_CUSTOM", kWho, r.flags, (unsigned long long)r.plane_mask, r.field_mask);
+  if (!r.out) return fail(MP_ERR_INVALID, "%s: NULL out", kWho);
+  const state_hash::Spec spec = {r.plane_mask, r.field_mask, r.flags & MP_HASH_CUSTOM ? 1 : 0,
+                                 r.flags & MP_HASH_PLAYER_BLOCK ? 1 : 0};
+  const bool rows_op = r.op == MP_HASH_ROWS || r.op == MP_HASH_HOST;
+  if (rows_op && !r.bank) return fail(MP_ERR_INVALID, "%s: NULL bank", kWho);
+  if (r.op != MP_HASH_MASK) {
+    if (r.count < 1 || (rows_op && r.bank_rows < 1))
+      return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", kWho, r.count, r.bank_rows);
+    if (rows_op && !r.rows && r.count > r.bank_rows)
+      return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are hashed (count %d, the bank has "
+                  "%d rows)", kWho, r.count, r.bank_rows);
+    if (r.op == MP_HASH_WORLDS && !r.rows && r.count != e->N)
+      return fail(MP_ERR_INVALID, "%s: without a world list every world is hashed (count %d, the engine has %d)",
+                  kWho, r.count, e->N);
+    if (r.out_bytes < (uint64_t)r.count * 8u)
+      return fail(MP_ERR_INVALID, "%s: %d hashes need %llu bytes, out has %llu", kWho, r.count,
+                  (unsigned long long)r.count * 8u, (unsigned long long)r.out_bytes);
+    if (((uintptr_t)r.out & 7) || ((uintptr_t)r.rows & 3))
+      return fail(MP_ERR_INVALID, "%s: out %p must be 8-byte aligned, rows %p 4-byte aligned", kWho, r.out,
+                  (const void*)r.rows);
+  }
+  // the layout and the fingerprint: the engine's, or the pack's by the host stage
+  state_hash::Layout lay;
+  uint64_t fingerprint;
+  if (e) {
+    lay = e->hash_layout();
+    fingerprint = e->fingerprint;
+  } else {
+    HostStage h;
+    if (int rc = host_stage(r.pack, r.pack_len, r.cfg, &h)) return rc;
+    lay = hash_layout_of(h.d);
+    fingerprint = state_fingerprint(h.pack, h.d.t);
+  }
+  if (const char* why = state_hash::spec_error(lay, spec))
+    return fail(MP_ERR_INVALID, "%s: %s (plane_mask %llx over %d planes, field_mask %x over %d fields)", kWho, why,
+                (unsigned long long)r.plane_mask, lay.grid_planes, r.field_mask, state_hash::TF_COUNT);
+  const uint64_t S = (uint64_t)lay.world_stride;
+  if (r.op == MP_HASH_MASK) {
+    if (r.out_bytes < S)
+      return fail(MP_ERR_INVALID, "%s: the mask of a row is %llu bytes, out has %llu", kWho,
+                  (unsigned long long)S, (unsigned long long)r.out_bytes);
+    state_hash::build_byte_mask(lay, spec, (uint8_t*)r.out);
+    return MP_OK;
+  }
+  if (rows_op && r.fingerprint != fingerprint)
+    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this %s (%016llx): they were "
+                "saved by an engine of another pack, player count or record layout", kWho,
+                (unsigned long long)r.fingerprint, e ? "engine's" : "pack's", (unsigned long long)fingerprint);
+  if (r.op == MP_HASH_HOST) {
+    std::vector<uint32_t> words((size_t)S / 4);
+    state_hash::build_byte_mask(lay, spec, reinterpret_cast<uint8_t*>(words.data()));
+    const int bad = hash_rows_host(words.data(), (const uint8_t*)r.bank, r.bank_rows, (int)S, r.rows, r.count,
+                                   (uint64_t*)r.out);
+    if (bad >= 0)
+      return fail(MP_ERR_INVALID, "%s: rows[%d] = %d is not a row of the bank; element %d of out was left as it "
+                  "was", kWho, bad, r.rows ? r.rows[bad] : bad, bad);
+    return MP_OK;
+  }
+  if (r.op == MP_HASH_WORLDS && !e->has_state)
+    return fail(MP_ERR_INVALID, "%s: the engine has never been reset; there is no state to hash", kWho);
+  if (rows_op && ((uintptr_t)r.bank & 15))   // (records are read in 16-byte lines)
+    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", kWho, r.bank);
+  HIP_TRY(hipSetDevice(e->device));
+  const uint64_t count = (uint64_t)r.count;
+  if (rows_op)
+    if (int rc = check_bank(e, r.bank, (uint64_t)r.bank_rows * S, "MpStatesHash (bank)")) return rc;
+  if (r.rows)
+    if (int rc = check_bank(e, r.rows, count * 4, "MpStatesHash (rows)")) return rc;
+  if (int rc = check_bank(e, r.out, count * 8, "MpStatesHash (out)")) return rc;
+  const uint32_t* mask = e->d_hash_mask;
+  if (spec.custom) {
+    if (!state_hash::same_spec(spec, e->hash_custom)) {
+      // another custom spec: its mask replaces the last one's, which launches in flight may still
+      // read — behind a wait for the stream (the request's one synchronisation, once per new spec)
+      std::vector<uint32_t> words((size_t)S / 4);
+      state_hash::build_byte_mask(lay, spec, reinterpret_cast<uint8_t*>(words.data()));
+      if (!e->d_hash_custom) HIP_TRY(hipMalloc((void**)&e->d_hash_custom, (size_t)S));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+      e->hash_custom = state_hash::Spec{};
+      HIP_TRY(hipMemcpy(e->d_hash_custom, words.data(), (size_t)S, hipMemcpyHostToDevice));
+      e->hash_custom = spec;
+    }
+    mask = e->d_hash_custom;
+  }
+  if (rows_op)
+    launch_hash_rows(mask, (const uint8_t*)r.bank, r.bank_rows, (int)S, r.rows, r.count, (uint64_t*)r.out,
+                     e->t.fault, e->stream);
+  else
+    launch_hash_rows(mask, (const uint8_t*)e->d_state, e->N, (int)S, r.rows, r.count, (uint64_t*)r.out,
+                     e->t.fault, e->stream);
+  HIP_TRY(hipGetLastError());
+  return MP_OK;
+}
+
 static_assert(sizeof(MpStatesObserve) == 64 && sizeof(MpStatesObserve) != sizeof(MpKernelVariant) &&
                   sizeof(MpStatesObserve) != sizeof(MpWorldStates) && sizeof(MpStatesObserve) != sizeof(MpStepMany) &&
                   sizeof(MpStatesObserve) != sizeof(MpStepTrajectory),
@@ -1892,6 +2032,9 @@ static_assert(sizeof(MpStateLayout) == 120 && sizeof(MpStatesCheck) == 88 && siz
 static_assert(MP_SIZE_DIFFERS(MpStateLayout) && MP_SIZE_DIFFERS(MpStatesCheck) &&
                   sizeof(MpStateLayout) != sizeof(MpStatesCheck) && sizeof(MpStateLayout) < 448 &&
                   sizeof(MpStatesCheck) < 448,
+              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
+static_assert(sizeof(MpStatesHash) == 104 && MP_SIZE_DIFFERS(MpStatesHash) &&
+                  sizeof(MpStatesHash) != sizeof(MpStateLayout) && sizeof(MpStatesHash) != sizeof(MpStatesCheck),
               "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
 #undef MP_SIZE_DIFFERS
 // An MpKernelVariant request (carried by mp_snapshot; `e` may be NULL: the host-only question).
@@ -1937,6 +2080,11 @@ int mp_snapshot(MpEngine* e, void* buf, uint64_t bytes) {
     MpStatesCheck r;   // (read only: the verdicts go to r.out)
     memcpy(&r, buf, sizeof r);
     return states_check(e, r);
+  }
+  if (buf && bytes == sizeof(MpStatesHash)) {
+    MpStatesHash r;   // (read only: the hashes go to r.out)
+    memcpy(&r, buf, sizeof r);
+    return states_hash(e, r);
   }
   if (!e || !buf || bytes != mp_snapshot_bytes(e))
     return fail(MP_ERR_INVALID, "mp_snapshot: bad buffer");

@@ -14,11 +14,16 @@ int step_worlds_per_group(const DevTables& t, const SubstrateTables& s);
 // `slot` of ManyArgs::row (the five kinds of MpStepMany) or of StepRows::fin, StepRows::layer, or
 // one of StepRows::level.  name == NULL: no per-step rows (the pixel kinds).  The last entry,
 // index kStepRowStateIndex, is MP_STEP_ROW_STATE: the world's record itself (StateRows), which
-// is no observation kind (step_row_index maps a request's kind to its entry).
-enum StepRowPlace { kRowFive = 1, kRowFin, kRowLayer, kRowLevel, kRowState };
+// is no observation kind (step_row_index maps a request's kind to its entry); behind it, index
+// kStepRowHashIndex, MP_STEP_ROW_HASH: the record's 64-bit hash (HashRows).
+enum StepRowPlace { kRowFive = 1, kRowFin, kRowLayer, kRowLevel, kRowState, kRowHash };
 constexpr int kStepRowStateIndex = MP_OBS_KINDS;
+constexpr int kStepRowHashIndex = MP_OBS_KINDS + 1;
+constexpr int kStepRowCount = MP_OBS_KINDS + 2;
 constexpr int step_row_index(int kind) {
-  return kind == MP_STEP_ROW_STATE ? kStepRowStateIndex : kind >= 0 && kind < MP_OBS_KINDS ? kind : -1;
+  return kind == MP_STEP_ROW_STATE  ? kStepRowStateIndex
+         : kind == MP_STEP_ROW_HASH ? kStepRowHashIndex
+         : kind >= 0 && kind < MP_OBS_KINDS ? kind : -1;
 }
 struct StepRowKind {
   const char* name;
@@ -26,7 +31,7 @@ struct StepRowKind {
   int place;
   int slot;
 };
-struct StepRowKinds { StepRowKind of[MP_OBS_KINDS + 1]; };
+struct StepRowKinds { StepRowKind of[kStepRowCount]; };
 constexpr StepRowKinds make_step_row_kinds() {
   StepRowKinds k = {};
   k.of[MP_OBS_REWARD] = {"REWARD", 8, kRowFive, 0};
@@ -49,6 +54,7 @@ constexpr StepRowKinds make_step_row_kinds() {
   k.of[MP_OBS_MATRIX_CUMULANTS] = {"MATRIX_CUMULANTS", 8, kRowLevel, 0};
   k.of[MP_OBS_INTERACTION_REWARDS] = {"INTERACTION_REWARDS", 8, kRowLevel, 0};
   k.of[kStepRowStateIndex] = {"STATE", 16, kRowState, 0};   // (a record is copied in 16-byte lines)
+  k.of[kStepRowHashIndex] = {"HASH", 8, kRowHash, 0};     // (one u64 a world)
   return k;
 }
 constexpr StepRowKinds kStepRowKinds = make_step_row_kinds();
@@ -114,14 +120,25 @@ struct StateRows {
   long long bytes;
 };
 
+// The per-step state hashes (MP_STEP_ROW_HASH): row k = u64 [N], the hash (state_hash.h, the
+// default spec, whose mask `mask` is: device u32 [world_stride / 4]) of the records after step k.
+// An argument of its own, of a kernel family of its own (k_step_hashes_<level>), which also
+// writes the state rows when the request names both.
+struct HashRows {
+  uint8_t* row;
+  long long bytes;
+  const uint32_t* mask;
+};
+
 // One checked K-step request, as submit() hands it to launch_step_many: the five kinds' rows,
 // the rows of the other kinds, whether there is one of those (any_rows == false runs the
-// kernels an MpStepMany request has always run), and the state rows.
+// kernels an MpStepMany request has always run), the state rows and the hash rows.
 struct StepManyLaunch {
   ManyArgs many;
   StepRows rows;
   bool any_rows;
   StateRows state;
+  HashRows hash;
 };
 
 void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,

@@ -14,6 +14,7 @@
 #include "step_territory.h"
 #include "step_load.h"
 #include "step_many.h"
+#include "state_hash.h"
 
 namespace {
 
@@ -73,11 +74,18 @@ __device__ inline T* row_of(uint8_t* base, long long bytes, int k, T* in_place) 
 //    the loop-top wsync() keeps the next step's writes behind it.  A family of its own: with the
 //    row as one more runtime branch of k_step_rows_*, that family's LAYER rows cost 9 % more on
 //    clean_up (profiles/r16_observe_states.md); this way its code is what it was.
+//  * the hash rows (MP_STEP_ROW_HASH, `hp`, Hashes = true: the k_step_hashes_* family): the hash
+//    of the record in LDS (state_hash.h: every lane's share of the masked words, a wave-wide
+//    sum, 8 bytes from lane 0) to element w of row k, behind the same wsync() and under the same
+//    `started` test as the state row — so row k is the hash of what the state row's row k holds.
+//    The mask's lines come from device memory (L2 after the first wave).  A request that names
+//    both rows runs this family too: whether the record is stored as well is a runtime test
+//    here and nowhere else (`sp->row`), and the three families above are what they were.
 // Which kinds are asked for is wave-uniform: every branch on it is a scalar one.
-template <bool Rows, bool States, class Tables, class Sites>
+template <bool Rows, bool States, class Tables, class Sites, bool Hashes = false>
 __device__ inline void run_many(const DevTables& t, const Tables& c, const StepArgs& args0,
                                 const ManyArgs& m, const StepRows* rp, int extra,
-                                const StateRows* sp = nullptr) {
+                                const StateRows* sp = nullptr, const HashRows* hp = nullptr) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
@@ -148,7 +156,7 @@ __device__ inline void run_many(const DevTables& t, const Tables& c, const StepA
     act_id = next_id;
     if constexpr (Rows) {
       const StepRows& r = *rp;
-      if (States || r.layer || r.n_level) {
+      if (States || Hashes || r.layer || r.n_level) {
         wsync();   // the record in LDS is final; the step's stores to the level kinds come before the loads below
         const WorldTail* tl = reinterpret_cast<const WorldTail*>(wd.rec + t.grid_pad);
         if (__builtin_amdgcn_readfirstlane((int)tl->started)) {
@@ -166,6 +174,14 @@ __device__ inline void run_many(const DevTables& t, const Tables& c, const StepA
           }
           if constexpr (States)
             store_record(t, wd.rec, sp->row + (long long)k * sp->bytes + (size_t)w * t.world_stride, lane_k);
+          if constexpr (Hashes) {
+            if (sp->row)
+              store_record(t, wd.rec, sp->row + (long long)k * sp->bytes + (size_t)w * t.world_stride, lane_k);
+            const uint64_t sum =
+                state_hash::wave_sum(state_hash::hash_share(hp->mask, wd.rec, t.world_stride >> 4, lane_k, 64));
+            if (lane_k == 0)
+              reinterpret_cast<uint64_t*>(hp->row + (long long)k * hp->bytes)[w] = state_hash::fmix64(sum);
+          }
         }
       }
     }
@@ -258,14 +274,34 @@ MP_STEP_STATES_KERNEL(k_step_states_matrix, MatrixTables, MatrixSites, 0)
 MP_STEP_STATES_KERNEL(k_step_states_territory, TerritoryTables, TerritorySites, extra_bytes(c))
 #undef MP_STEP_STATES_KERNEL
 
+// ... and with the per-step state hashes (MP_STEP_ROW_HASH), beside the state rows where the
+// request names both: a fourth family, so that the three above run exactly the code they ran before
+// there was one.
+#define MP_STEP_HASHES_KERNEL(name, TablesT, SitesT, extra)                                          \
+  __global__ __launch_bounds__(kWorldsPerGroup * 64) void name(DevTables t, TablesT c, StepArgs args, \
+                                                               ManyArgs m, StepRows r, StateRows s,  \
+                                                               HashRows h) {                         \
+    run_many<true, false, TablesT, SitesT, true>(t, c, args, m, &r, extra, &s, &h);                  \
+  }
+MP_STEP_HASHES_KERNEL(k_step_hashes_clean_up, CleanUpTables, CleanUpSites, 0)
+MP_STEP_HASHES_KERNEL(k_step_hashes_commons, CommonsTables, CommonsSites, 0)
+MP_STEP_HASHES_KERNEL(k_step_hashes_coins, CoinsTables, CoinsSites, 0)
+MP_STEP_HASHES_KERNEL(k_step_hashes_coop, CoopTables, CoopSites, 0)
+MP_STEP_HASHES_KERNEL(k_step_hashes_gift, GiftTables, GiftSites, 0)
+MP_STEP_HASHES_KERNEL(k_step_hashes_cook, CookTables, CookSites, 0)
+MP_STEP_HASHES_KERNEL(k_step_hashes_mushroom, MushroomTables, MushroomSites, extra_bytes(c))
+MP_STEP_HASHES_KERNEL(k_step_hashes_matrix, MatrixTables, MatrixSites, 0)
+MP_STEP_HASHES_KERNEL(k_step_hashes_territory, TerritoryTables, TerritorySites, extra_bytes(c))
+#undef MP_STEP_HASHES_KERNEL
+
 }  // namespace
 
 // The K-step kernels may take all 160 KB of a CU's LDS, like the single-step ones.
 int prepare_step_many() {
-  const void* km[27] = {
+  const void* km[36] = {
 #define MP_BOTH(level)                                                                             \
   reinterpret_cast<const void*>(&k_step_many_##level), reinterpret_cast<const void*>(&k_step_rows_##level), \
-      reinterpret_cast<const void*>(&k_step_states_##level)
+      reinterpret_cast<const void*>(&k_step_states_##level), reinterpret_cast<const void*>(&k_step_hashes_##level)
       MP_BOTH(clean_up), MP_BOTH(commons), MP_BOTH(coins), MP_BOTH(territory), MP_BOTH(matrix),
       MP_BOTH(coop), MP_BOTH(gift), MP_BOTH(cook), MP_BOTH(mushroom)};
 #undef MP_BOTH
@@ -277,7 +313,8 @@ int prepare_step_many() {
 
 // K steps of every world in one launch (MpStepMany, MpStepTrajectory): the geometry of
 // launch_step.  l.any_rows == false: only rows of the five kinds, which runs k_step_many_*;
-// l.state.row: the state rows, which runs k_step_states_*.
+// l.state.row: the state rows, which runs k_step_states_*; l.hash.row: the hash rows (with or
+// without the state rows), which runs k_step_hashes_*.
 void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
                       const StepManyLaunch& l, hipStream_t stream) {
   const ManyArgs& m = l.many;
@@ -288,7 +325,9 @@ void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk:
   StepRows r = l.rows;   // (the level kinds' sources: this submission's buffers)
   for (int i = 0; i < r.n_level; ++i) r.level[i].src = level_source(args.out, r.level[i].which);
 #define MP_LAUNCH(level, tables)                                                                  \
-  if (l.state.row)                                                                                \
+  if (l.hash.row)                                                                                 \
+    hipLaunchKernelGGL(k_step_hashes_##level, grid, block, lds, stream, t, tables, args, m, r, l.state, l.hash); \
+  else if (l.state.row)                                                                           \
     hipLaunchKernelGGL(k_step_states_##level, grid, block, lds, stream, t, tables, args, m, r, l.state); \
   else if (more) hipLaunchKernelGGL(k_step_rows_##level, grid, block, lds, stream, t, tables, args, m, r); \
   else hipLaunchKernelGGL(k_step_many_##level, grid, block, lds, stream, t, tables, args, m);    \

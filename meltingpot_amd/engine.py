@@ -435,6 +435,111 @@ def check_states_host(pack_bytes: bytes, rows, *, fingerprint: Optional[int] = N
   return out
 
 
+# The hash of world records (include/mp_engine.h: MpStatesHash), carried by mp_snapshot
+MP_HASH_ROWS, MP_HASH_WORLDS, MP_HASH_HOST, MP_HASH_MASK = 1, 2, 3, 4
+MP_HASH_CUSTOM, MP_HASH_PLAYER_BLOCK = 1, 2
+# the tail fields the default spec leaves out: the destination engine's bookkeeping, and the
+# cached visiting orders, which may be present or absent
+HASH_BOOKKEEPING = ("ctr", "reward_fx", "orders_step", "next_orders")
+
+
+class MpStatesHash(ctypes.Structure):
+  _fields_ = [("struct_size", ctypes.c_uint32), ("op", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
+              ("pack", ctypes.c_void_p), ("pack_len", ctypes.c_uint64), ("cfg", ctypes.POINTER(MpConfig)),
+              ("bank", ctypes.c_void_p), ("bank_rows", ctypes.c_int32), ("count", ctypes.c_int32),
+              ("rows", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_bytes", ctypes.c_uint64),
+              ("plane_mask", ctypes.c_uint64), ("field_mask", ctypes.c_uint32), ("flags", ctypes.c_int32),
+              ("reserved", ctypes.c_uint64)]
+
+
+def hash_spec(layout: StateLayout, planes=None, fields=None):
+  """(plane_mask, field_mask, flags) of an MpStatesHash request.  `planes`: an iterable of grid
+  plane indices; `fields`: an iterable of tail field names (`layout.fields`' keys), plus
+  "player_block" for the level's block.  Both None: the default spec, "the state".  If one is
+  given, a None other means none of them.  ValueError for a plane or a name the layout has not."""
+  if planes is None and fields is None:
+    return 0, 0, 0
+  plane_mask, field_mask, flags = 0, 0, MP_HASH_CUSTOM
+  for p in (() if planes is None else planes):
+    if isinstance(p, bool) or not isinstance(p, (int, np.integer)) or not 0 <= int(p) < layout.grid_planes:
+      raise ValueError(f"hash: {p!r} is no grid plane (the rows have {layout.grid_planes})")
+    if int(p) >= 64:
+      raise ValueError("hash: a custom spec names planes below 64")
+    plane_mask |= 1 << int(p)
+  names = list(layout.fields)
+  if isinstance(fields, str):
+    fields = (fields,)
+  for f in (() if fields is None else fields):
+    if f == "player_block":
+      if layout.player_block < 0:
+        raise ValueError("hash: this level keeps no player block")
+      flags |= MP_HASH_PLAYER_BLOCK
+    elif f in names:
+      field_mask |= 1 << names.index(f)
+    else:
+      raise ValueError(f"hash: {f!r} is no field of the tail; it has {names} (and 'player_block')")
+  if plane_mask == 0 and field_mask == 0 and not flags & MP_HASH_PLAYER_BLOCK:
+    raise ValueError("hash: the spec includes no byte")
+  return plane_mask, field_mask, flags
+
+
+def _hash_request(op: int, spec, fingerprint: int = 0) -> MpStatesHash:
+  req = MpStatesHash(ctypes.sizeof(MpStatesHash), op, int(fingerprint))
+  req.plane_mask, req.field_mask, req.flags = spec
+  return req
+
+
+def state_hash_mask(pack_bytes: bytes, planes=None, fields=None, num_players: int = 0,
+                    dev: Optional[Dict[str, int]] = None) -> np.ndarray:
+  """The byte mask of a hash spec, uint8 [S]: 0xFF where a byte of a row counts (MP_HASH_MASK
+  without an engine: no GPU needed).  `planes`, `fields`: see `hash_spec`."""
+  L = load_library()
+  layout = _layout_request(L, None, pack_bytes, num_players, dev)
+  keep = _host_config(pack_bytes, num_players, dev)
+  out = np.zeros(layout.world_stride, np.uint8)
+  req = _hash_request(MP_HASH_MASK, hash_spec(layout, planes, fields))
+  req.pack, req.pack_len, req.cfg = ctypes.addressof(keep[0]), len(pack_bytes), ctypes.pointer(keep[1])
+  req.out, req.out_bytes = out.ctypes.data, out.nbytes
+  _check(L, L.mp_snapshot(None, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpStatesHash)")
+  return out
+
+
+def hash_states_host(pack_bytes: bytes, rows, which=None, planes=None, fields=None, num_players: int = 0,
+                     dev: Optional[Dict[str, int]] = None, fingerprint: Optional[int] = None,
+                     out: Optional[np.ndarray] = None) -> np.ndarray:
+  """int64 [R]: the 64-bit state hash (the u64's bits) of host rows (uint8 [M, S] array) by the
+  library's host-only form (MP_HASH_HOST: the kernel's own function compiled for the host; no GPU
+  needed).  `which`: the rows to hash, in order, repeats allowed (default: all); an index outside
+  the bank raises ValueError and leaves its element of `out` as it was.  `planes`, `fields`: the
+  spec (`hash_spec`; both None: "the state").  `fingerprint`: the rows' (default: the pack's).
+  Hashes compare only between rows of one fingerprint, hashed with one spec."""
+  L = load_library()
+  bank = np.ascontiguousarray(rows, np.uint8)
+  if bank.ndim != 2 or bank.shape[0] < 1:
+    raise ValueError("hash_states_host: rows must be a uint8 array [M, S]")
+  keep = _host_config(pack_bytes, num_players, dev)
+  layout = _layout_request(L, None, pack_bytes, num_players, dev)
+  if bank.shape[1] != layout.world_stride:
+    raise ValueError(f"hash_states_host: rows of {bank.shape[1]} bytes, the pack's are {layout.world_stride}")
+  idx = None if which is None else np.ascontiguousarray(np.asarray(which).reshape(-1), np.int32)
+  count = bank.shape[0] if idx is None else int(idx.size)
+  if count < 1:
+    raise ValueError("hash_states_host: no rows to hash")
+  if out is None:
+    out = np.zeros(count, np.int64)
+  elif (not isinstance(out, np.ndarray) or out.dtype != np.int64 or out.shape != (count,) or
+        not out.flags.c_contiguous):
+    raise ValueError(f"hash_states_host: out must be a contiguous int64 array of shape {(count,)}")
+  req = _hash_request(MP_HASH_HOST, hash_spec(layout, planes, fields),
+                      layout.fingerprint if fingerprint is None else fingerprint)
+  req.pack, req.pack_len, req.cfg = ctypes.addressof(keep[0]), len(pack_bytes), ctypes.pointer(keep[1])
+  req.bank, req.bank_rows, req.count = bank.ctypes.data, int(bank.shape[0]), count
+  req.rows = None if idx is None else idx.ctypes.data
+  req.out, req.out_bytes = out.ctypes.data, out.nbytes
+  _check(L, L.mp_snapshot(None, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpStatesHash)")
+  return out
+
+
 # Action sequences (include/mp_engine.h: MpStepMany), carried by mp_restore
 STEP_MANY_MAX = 4096   # MP_STEP_MANY_MAX
 # the five kinds step_many returns by name, in MpStepMany.per_step's order
@@ -466,6 +571,8 @@ class MpStepTrajectory(ctypes.Structure):
 
 # MpStepRow.kind of the per-step world states (MP_STEP_ROW_STATE): no observation kind
 STEP_ROW_STATE = 0x100
+# ... and of the per-step state hashes (MP_STEP_ROW_HASH)
+STEP_ROW_HASH = 0x102
 
 # the kinds a step_many request may stack per step: every kind but the pixel ones
 STEP_ROW_KINDS = tuple(k for k in range(OBS_RGB_POOL8 + 1) if k not in PIXEL_KINDS)
@@ -1151,7 +1258,7 @@ class Engine:
 
   def step_many(self, actions, *, repeat: Optional[int] = None, fields: bool = False,
                 keep=("reward", "collective_reward", "step_type", "discount"), events: bool = False,
-                observations=(), out=None, states=False):
+                observations=(), out=None, states=False, hashes=False):
     """K steps of every world in ONE launch, bit-identical to K calls of step() (fields=True:
     step_fields()) with actions[0] .. actions[K - 1]; returns the per-step transitions.
 
@@ -1175,6 +1282,9 @@ class Engine:
     info.world_state_bytes: row k of a started world is what save_worlds() gives after step k of
     the loop (a world never reset writes nothing).  Each [k] loads with load_worlds and draws
     with observe_states like any bank.
+    hashes: True (or a tensor under out["hashes"]) adds "hashes", int64 [K, N]: row k of a started
+    world is hash_worlds() after step k of the loop — the hash (default spec) of what the state
+    row's row k holds, at 8 bytes a world-step (a world never reset writes nothing).
     Enqueued on the current stream; does not synchronise."""
     t = self._torch
     A = int(self.info.num_action_fields) if fields else None
@@ -1197,12 +1307,15 @@ class Engine:
       raise ValueError(f"step_many: keep= knows {STEP_MANY_KINDS[:4]} (got {unknown})")
     kinds = check_step_rows(observations, taken=[STEP_MANY_NAMES[n] for n in names])
     states = bool(states) or (out is not None and out.get("states") is not None)
-    keys = names + list(kinds) + (["states"] if states else [])
+    hashes = bool(hashes) or (out is not None and out.get("hashes") is not None)
+    keys = names + list(kinds) + (["states"] if states else []) + (["hashes"] if hashes else [])
     rows = (MpStepRow * len(keys))()
     result = {}
     for i, key in enumerate(keys):
       if key == "states":
         kind, per_world, dtype = STEP_ROW_STATE, (int(self.info.world_state_bytes),), t.uint8
+      elif key == "hashes":
+        kind, per_world, dtype = STEP_ROW_HASH, (), t.int64
       else:
         kind, per_world, dtype = step_row(self.shapes, key)
       shape = (K, self.N) + per_world
@@ -1338,6 +1451,60 @@ class Engine:
            "mp_snapshot (MpStatesCheck)")
     self._check_args = (bank, r, out)   # (kept until the next call: the launch may not have run yet)
     return out
+
+  def _hash(self, what: str, op: int, bank, index, out, planes, fields, fingerprint: int):
+    """One MpStatesHash request (`index`: the rows or worlds, or None; `bank`: None for the
+    engine's own records)."""
+    t = self._torch
+    r = None if index is None else self._device_ints(index, "rows" if bank is not None else "worlds")
+    count = (int(bank.shape[0]) if bank is not None else self.N) if r is None else int(r.numel())
+    if count < 1:
+      raise ValueError(f"{what}: nothing to hash")
+    if out is None:
+      out = t.empty((count,), dtype=t.int64, device=self.device)
+    elif (not isinstance(out, t.Tensor) or out.dtype != t.int64 or tuple(out.shape) != (count,) or
+          not out.is_contiguous() or out.device != self.device):
+      raise ValueError(f"{what}: out must be a contiguous int64 tensor of shape {(count,)} on {self.device}")
+    spec = hash_spec(self.state_layout(), planes, fields)
+    self.use_current_stream()
+    req = _hash_request(op, spec, fingerprint)
+    if bank is not None:
+      req.bank, req.bank_rows = bank.data_ptr(), int(bank.shape[0])
+    req.count = count
+    req.rows = None if r is None else r.data_ptr()
+    req.out, req.out_bytes = out.data_ptr(), count * 8
+    _check(self._L, self._L.mp_snapshot(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
+           "mp_snapshot (MpStatesHash)")
+    self._hash_args = (bank, r, out)   # (kept until the next call: the launch may not have run yet)
+    return out
+
+  def hash_states(self, bank, rows=None, out=None, planes=None, fields=None, fingerprint: Optional[int] = None):
+    """int64 [R] device tensor: the 64-bit state hash (the u64's bits) of rows of `bank` (uint8
+    [M, S] device tensor from save_worlds or step_many(states=True)), computed where the rows lie
+    by one launch.  Two records hash alike iff they agree in every byte a state's future and its
+    observations depend on: ctr[] and reward_fx (the destination engine's bookkeeping), the
+    cached visiting orders, the padding and the bytes of avatars >= P do not count.  `torch.unique(
+    h, return_inverse=True)` is the dedup.  rows: the rows to hash, in order, repeats allowed (None:
+    every row).  planes / fields: a custom spec (`hash_spec`) — an iterable of grid planes, an
+    iterable of tail field names plus "player_block"; both None: "the state".  The first request
+    with a NEW custom spec waits for the stream once to install its mask; the default spec and a
+    repeated custom spec only enqueue.  Nothing of the engine's is written.  Hashes compare only
+    between rows of one fingerprint, hashed with one spec.  `fingerprint`: the rows' (default:
+    this engine's).  Enqueued on the current stream; does not synchronise."""
+    t = self._torch
+    S = int(self.info.world_state_bytes)
+    if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
+        bank.shape[1] != S or not bank.is_contiguous()):
+      raise ValueError(f"hash_states: bank must be a contiguous uint8 tensor [M, {S}]")
+    if bank.shape[0] < 1:
+      raise ValueError("hash_states: the bank has no rows")
+    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    return self._hash("hash_states", MP_HASH_ROWS, bank, rows, out, planes, fields, fp)
+
+  def hash_worlds(self, worlds=None, out=None, planes=None, fields=None):
+    """int64 [M] device tensor: `hash_states` of the records of `worlds` (None: every world, M =
+    N) where they lie — equal to hash_states(save_worlds(worlds)) without the copy."""
+    return self._hash("hash_worlds", MP_HASH_WORLDS, None, worlds, out, planes, fields, 0)
 
   def load_worlds(self, bank, src, fingerprint: Optional[int] = None, check: bool = False):
     """World w starts from row src[w] of `bank` (uint8 [M, S] device tensor from save_worlds, of

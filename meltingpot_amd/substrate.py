@@ -102,14 +102,18 @@ class StepManyTrajectory(StepManyResult):
   carries it; `_make`, slicing, `tuple()` and pickling give a plain tuple without it.
   With `states=True` it also has `.states`: the worlds' records after every step as a
   `WorldStates` of K x N rows (step k of world w is row k * N + w), a view of the engine's
-  uint8 [K, N, S] tensor; carried like `.observation` (None when not asked for)."""
+  uint8 [K, N, S] tensor; carried like `.observation` (None when not asked for).
+  With `hashes=True` it has `.hashes`: int64 [K, N], the state hash (`Substrate.hash_worlds`) of
+  every world after every step; carried likewise."""
   observation: Any = None
   states: Any = None
+  hashes: Any = None
 
   def _replace(self, **kwargs):   # (a NamedTuple's _replace builds a fresh tuple: carry the dict)
     out = super()._replace(**kwargs)
     out.observation = self.observation
     out.states = self.states
+    out.hashes = self.hashes
     return out
 
 
@@ -120,7 +124,7 @@ def _many_result(r, leaves, timestep, fingerprint=None):
   """The result of a step_many call from the engine's dict `r` (`leaves`: asked name -> kind;
   `fingerprint`: the engine's, when the call asked for the per-step states)."""
   fields = (r["step_type"], r["reward"], r["discount"], r["collective_reward"], r.get("events"), timestep)
-  if not leaves and fingerprint is None:
+  if not leaves and fingerprint is None and r.get("hashes") is None:
     return StepManyResult(*fields)
   out = StepManyTrajectory(*fields)
   # (a leaf that is one of the five per-step kinds is the tensor the call stacks anyway)
@@ -128,7 +132,18 @@ def _many_result(r, leaves, timestep, fingerprint=None):
   if fingerprint is not None:
     rows = r["states"]
     out.states = WorldStates(rows.view(rows.shape[0] * rows.shape[1], rows.shape[2]), fingerprint)
+  out.hashes = r.get("hashes")
   return out
+
+
+def _hash_fields(fields):
+  """`fields` of a hash call with `StateFields`' names (avatar_x, ...) as the tail's own (ax, ...)."""
+  if fields is None:
+    return None
+  if isinstance(fields, str):
+    fields = (fields,)
+  c_names = {py: c for c, py in _FIELD_NAMES.items()}
+  return tuple(c_names.get(f, f) for f in fields)
 
 
 def _many_actions(t, actions, repeat, N: int, P: int, num_actions: Optional[int]):
@@ -1033,6 +1048,39 @@ class Substrate:
     self._eng.use_current_stream()
     return self._eng.check_states(states.data, rows=rows, fingerprint=states.fingerprint)
 
+  def hash_states(self, states: WorldStates, rows=None, planes=None, fields=None):
+    """Are two saved states the same state?  int64 [R] device tensor: a 64-bit hash of every row
+    (`rows`: the rows to hash, in order, repeats allowed; default all), computed on the device
+    where the rows lie.  Equal hashes mean equal states (up to a 2^-64 collision), and different
+    hashes always mean different states — where comparing `states.data` byte for byte calls
+    equal states different: the event counters and the reward sum (`ctr`, `reward_fx`) are the
+    bookkeeping of whichever substrate a row was loaded into, the cached visiting orders
+    (`orders_step`, `next_orders`) may be present or absent, and the padding and the bytes of
+    avatars >= num_players hold whatever an edit left.  None of those count; every plane, the
+    level's player block and every other tail field do.  `torch.unique(h, return_inverse=True)`
+    is the dedup of a search frontier.
+    `planes` / `fields`: hash a chosen part instead — an iterable of grid planes
+    (`state_fields(...).grid`'s second axis), an iterable of field names (`StateFields.names`, or
+    the tail's own; "player_block" for the matrix games' block); if one is given, None for the
+    other means none of them.  An exploration "cell", e.g. the apple plane plus the avatars'
+    positions.  Unknown names are a ValueError.  The first call with a NEW custom part waits for
+    the stream once; repeats, and the default, only enqueue.
+    Hashes compare only within one fingerprint (one level, player count, roles and library) and
+    one choice of planes and fields.  Nothing of this substrate changes; no host
+    synchronisation."""
+    if not isinstance(states, WorldStates):
+      raise ValueError("hash_states takes the WorldStates of save_state or step_many(states=True)")
+    states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
+    self._eng.use_current_stream()
+    return self._eng.hash_states(states.data, rows=rows, planes=planes, fields=_hash_fields(fields),
+                                 fingerprint=states.fingerprint)
+
+  def hash_worlds(self, worlds=None, planes=None, fields=None):
+    """int64 [N] device tensor (`worlds`: a list, default every world): `hash_states` of the
+    worlds as they are now, without saving them — `hash_states(save_state(worlds))`."""
+    self._eng.use_current_stream()
+    return self._eng.hash_worlds(worlds, planes=planes, fields=_hash_fields(fields))
+
   def load_state(self, states: WorldStates, src, check: Optional[bool] = None) -> TimeStep:
     """World w continues from row src[w] of `states` (-1: world w is left as it is), as the
     world the row was saved from would: same seed, episode, step and future under the same
@@ -1186,7 +1234,7 @@ class Substrate:
     return leaves
 
   def step_many(self, actions, repeat: Optional[int] = None, events: bool = False,
-                observations=(), states: bool = False) -> StepManyResult:
+                observations=(), states: bool = False, hashes: bool = False) -> StepManyResult:
     """K steps in ONE launch, bit-identical to K calls of `step` (batched substrates).
     `actions`: ints [K, N, P] (a device tensor is read in place; it may be a column slice
     [:, a:b] of a wider one), or one block [N, P] with `repeat=K`.  Returns the per-step
@@ -1204,7 +1252,12 @@ class Substrate:
     `states=True`: the result (a `StepManyTrajectory`) has `.states`, the worlds' records after
     every step as a `WorldStates` of K x N rows — step k of world w is row k * N + w, what
     `save_state` would have given after `step` k; it loads with `load_state` and draws with
-    `observe_states` like any other."""
+    `observe_states` like any other.
+    `hashes=True`: the result (a `StepManyTrajectory`) has `.hashes`, int64 [K, N]: the state
+    hash (`hash_worlds`, the default part) of every world after every step — what `hash_states`
+    gives of `.states`' rows, at 8 bytes a world-step instead of a record.  Stored at collection
+    time it proves that a regenerated rollout is the original.  Hashes compare only within one
+    fingerprint."""
     if not self._batched:
       raise ValueError("step_many steps a batch of worlds: build the substrate with num_worlds > 1")
     leaves = self._many_leaves(observations)
@@ -1215,15 +1268,18 @@ class Substrate:
     a, _ = _many_actions(t, actions, repeat, self._eng.N, self._eng.P, limit)
     self._observables.action.on_next(actions)
     self._eng.use_current_stream()
-    r = self._submit_many(a, repeat, events, None, leaves, bool(states))
+    r = self._submit_many(a, repeat, events, None, leaves, bool(states), bool(hashes))
     return _many_result(r, leaves, self._emit(self._timestep()),
                         self._eng.state_fingerprint if states else None)
 
-  def _submit_many(self, a, repeat, events, out, leaves=None, states=False):
+  def _submit_many(self, a, repeat, events, out, leaves=None, states=False, hashes=False):
     """One K-step launch of the engine on actions `a` as `_many_actions` prepared them
-    (`leaves`: name -> kind of the observations to stack per step; `states`: the records too)."""
+    (`leaves`: name -> kind of the observations to stack per step; `states`: the records too;
+    `hashes`: their hashes)."""
     t = self._eng._torch
     more = {"states": True} if states else {}
+    if hashes:
+      more["hashes"] = True
     if leaves:
       more["observations"] = tuple(dict.fromkeys(
           k for k in leaves.values() if k not in _FIVE_NAMES))
@@ -1818,12 +1874,38 @@ class MixtureSubstrate:
   def step_leaves(self) -> Dict[str, int]:
     return self._members[0].step_leaves()
 
+  def hash_worlds(self, worlds=None, planes=None, fields=None):
+    """int64 [N] device tensor: every member's `Substrate.hash_worlds` of its own worlds, in
+    world order (`worlds`: a list of mixture worlds, default all).  A hash compares only with
+    hashes of the SAME member: the members' fingerprints differ."""
+    t = self._members[0]._eng._torch
+    if worlds is None:
+      out = t.empty((self._N,), dtype=t.int64, device=self._members[0]._eng.device)
+      for m, off, n in zip(self._members, self._offsets, self._counts):
+        m._eng.use_current_stream()
+        m._eng.hash_worlds(None, out=out[off:off + n], planes=planes, fields=_hash_fields(fields))
+      return out
+    picked = [self._member_at(int(w)) for w in np.asarray(worlds).reshape(-1)]
+    if not picked:
+      raise ValueError("hash_worlds: no worlds to hash")
+    # one launch per member that owns some of them, each writing its own positions of the result
+    out = t.empty((len(picked),), dtype=t.int64, device=self._members[0]._eng.device)
+    for m in self._members:
+      at = [i for i, (owner, _) in enumerate(picked) if owner is m]
+      if at:
+        h = m.hash_worlds([picked[i][1] for i in at], planes=planes, fields=fields)
+        out[t.as_tensor(at, device=out.device)] = h
+    return out
+
   def step_many(self, actions, repeat: Optional[int] = None, events: bool = False,
-                observations=(), states: bool = False) -> StepManyResult:
+                observations=(), states: bool = False, hashes: bool = False) -> StepManyResult:
     """As `Substrate.step_many`, over the members: one K-step launch per member, each reading
     its columns [:, off_i:off_i + n_i] of `actions` and writing its columns of the shared
     [K, N, ...] per-step tensors, those of `observations` included (nothing is copied or
-    concatenated).  There is no `states=True` here: the members' records differ in size."""
+    concatenated).  There is no `states=True` here: the members' records differ in size.
+    `hashes=True` is there: a hash is 8 bytes for every member, so `.hashes` is one int64
+    [K, N] tensor whose columns the members write — a per-step state identity of every world
+    (comparable within one member only: the members' fingerprints differ)."""
     if states:
       raise ValueError("step_many: a mixture has no per-step states (states=True): its members' records "
                        "differ in size and fingerprint; step the members' substrates on their own")
@@ -1839,6 +1921,8 @@ class MixtureSubstrate:
     for key in keys:
       _, per_world, dtype = engine_lib.step_row(first._eng.shapes, key)
       out[key] = t.empty((K, self._N) + per_world, dtype=dtype, device=dev)
+    if hashes:
+      out["hashes"] = t.empty((K, self._N), dtype=t.int64, device=dev)
     self._observables.action.on_next(actions)
     for m, off, n in zip(self._members, self._offsets, self._counts):
       m._eng.use_current_stream()
