@@ -885,6 +885,68 @@ typedef struct {
   const MpStepRow* rows;       /* HOST array [num_rows] */
 } MpStepTrajectory;
 
+/* Episode starts: where an auto-reset episode begins.  An engine with auto_reset = 1 restarts a
+ * finished world from the pack's map; with a registration it restarts it from a row of a bank of
+ * saved states instead, chosen by a device tensor the caller may rewrite at any time — curricula
+ * and prioritised level replay, Go-Explore restarts, training on the middle of long episodes,
+ * evaluation from a fixed set of situations, also in the middle of a K-step launch.  Rides
+ * mp_restore, recognised by its size: `bytes` = sizeof(MpEpisodeStarts), `host_buf` a HOST
+ * MpEpisodeStarts with struct_size set to it.  include/mp_episode_starts.h wraps it as inline C
+ * functions.  A request with bank == NULL clears the registration.
+ *
+ * The registration names `bank` (device uint8 [bank_rows][S]), `rows` (device int32 [N]) and,
+ * optionally, `verdicts` (device int32 [bank_rows][2], as MP_CHECK_ROWS writes them for the whole
+ * bank).  The engine reads all three in place, in stream order, in every later stepping
+ * submission: the caller keeps them alive and may rewrite `rows` (and the bank, and the verdicts)
+ * whenever it likes.  The bank is never written.
+ *
+ * In any step (mp_step, mp_step_fields, their host forms, each of the K steps of an MpStepMany /
+ * MpStepTrajectory request), for a world w that auto-resets in that step (started, done), with
+ * r = rows[w] read at that moment:
+ *   r == -1: the level's own reset, byte for byte what happens without a registration.
+ *   0 <= r < bank_rows, and verdicts NULL or verdicts[r] == (0, 0): the world starts from row r.
+ *     Its record and every output are what MP_STATES_LOAD writes for a world loaded from that row
+ *     (the kinds that are functions of the record; the transition kinds as a reset writes them,
+ *     STEP_TYPE FIRST; a row saved from a finished episode reports LAST, as a load does), on top of
+ *     what the replaced auto-reset step left.
+ *   anything else (an index outside [-1, bank_rows), or a row whose verdict is not (0, 0)): the
+ *     row is never read, the world takes the level's own reset, and the next synchronising call
+ *     returns MP_ERR_INVALID naming the world, the index and the rule; the engine stays usable.
+ * The defining identity (fresh = 0): a step with a registration leaves every record, counter,
+ * in-place or bound output and event row exactly as a step without one followed by
+ * MP_STATES_LOAD with src[w] = rows[w] for the worlds that were done before the step and -1
+ * elsewhere.  So the destination keeps its own ctr[] and reward_fx, and the start counts as the
+ * episode start it replaces (MP_CTR_EPISODES + 1).  In a K-step request, row k of a step that
+ * starts a world holds the start's values; rows of kinds a start does not write carry from row
+ * k - 1 by the carry rule above.
+ * fresh = 1: the started record is the row except that `seed` is the destination world's own,
+ * `episode` is the destination's episode + 1 (what its own reset would have set) and
+ * `orders_step` is 0 — as gathering the rows, editing those three fields and loading.  Worlds that
+ * start from one row then draw differently; with fresh = 0 they share every environment draw.
+ * Not affected: mp_reset (masked or not), MP_STATES_LOAD, MP_STATES_SAVE, MpStatesObserve,
+ * MpStatesHash, MpStatesCheck, frozen worlds, mp_tune, mp_place_output and mp_box_fill.  The
+ * registration is engine configuration, not part of a record: mp_snapshot does not carry it and
+ * mp_restore of a snapshot leaves it in place.
+ * While a registration is set a step with a bound pixel view is two launches (the step kernels,
+ * then the draw-only launch per view) and MpInfo.fused reports 0; clearing it returns the engine
+ * to the launches it had.  Ring slots are pointed and advanced as ever.
+ * Refused, MP_ERR_INVALID, nothing changed: a wrong struct_size; an engine with auto_reset = 0;
+ * bank_rows <= 0; NULL rows; fresh neither 0 nor 1; a fingerprint that is not the engine's; a bank
+ * that is not 16-byte aligned, rows or verdicts not 4-byte aligned; bank, rows or verdicts that
+ * are not device memory of the engine's device inside one allocation.  MP_ERR_UNSUPPORTED: an
+ * engine created with MpConfig.unfused = 2 (it promised one launch a step). */
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(MpEpisodeStarts) */
+  int32_t fresh;           /* 0: a started world is the world the row was saved from; 1: see above */
+  uint64_t fingerprint;    /* the rows' */
+  const void* bank;        /* device uint8 [bank_rows][S]; NULL clears the registration */
+  const int32_t* rows;     /* device int32 [N] */
+  const int32_t* verdicts; /* device int32 [bank_rows][2], or NULL */
+  int32_t bank_rows;
+  int32_t reserved;        /* 0 */
+  uint64_t reserved2[3];   /* 0 */
+} MpEpisodeStarts;
+
 /* Throughput / event counters accumulated on device since creation
  * (synchronises).  These are what the multi-GPU bench all-reduces. */
 enum {

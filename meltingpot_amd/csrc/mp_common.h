@@ -453,6 +453,9 @@ enum { STEP_MODE_STEP = 0, STEP_MODE_RESET = 1, STEP_MODE_FIELDS = 2, STEP_MODE_
 // words 12-15, a checked load's refused row: state_check.h).  The next synchronising call
 // reports it (MP_ERR_INVALID) and clears it.
 enum { FAULT_STATE_INDEX = 9 };
+// ... and of a registered episode start a stepping launch skipped (step_load.h: report_start):
+// words 32-35 = world + 1, rows[world], the rule of the row's verdict (0: a bad index), its offset word.
+constexpr int kFaultStartWorld = 32;
 
 
 #endif  // MP_COMMON_H_

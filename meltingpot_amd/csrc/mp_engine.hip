@@ -29,6 +29,9 @@
 
 void launch_step(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
                  hipStream_t stream);
+void launch_step_starts(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
+                        const stepk::StartArgs& st, hipStream_t stream);   // (step_starts.hip)
+int prepare_step_starts();
 int prepare_step();
 void launch_layer_view(const DevTables& t, const uint8_t* state, int32_t* out, int num_worlds,
                        hipStream_t stream);
@@ -165,6 +168,12 @@ struct MpEngine {
   bool has_state = false;          // reset, restored or loaded since creation (MP_STATES_SAVE)
   uint64_t fingerprint = 0;        // MP_STATES_FINGERPRINT: what a record's layout and meaning depend on
   int unfused = 0;                 // MpConfig.unfused: 0 the engine's choice, 1 two launches, 2 one
+  // The registered episode starts (an MpEpisodeStarts request; step_load.h: start_world): while set,
+  // a stepping submission runs the k_step_starts_* / k_many_starts_* families and draws the bound
+  // views in launches of their own.  starts_hold: mp_tune's probes step without it.
+  stepk::StartArgs starts{};
+  bool has_starts = false, starts_hold = false;
+  bool starting() const { return has_starts && !starts_hold; }
   // The engine's choice (MpConfig.unfused = 0): one launch, always.  (Round 2 drew
   // views under 64 KB a world — the two-player games — in a second launch: a CU
   // then has 64 worlds to step for 2 us of drawing each, and with 4-8 feeders the
@@ -367,6 +376,20 @@ int sync_and_check(MpEngine* e, const char* who) {
                 "(rule %u, offset word 0x%x); world %u was left as it was", who, (int)row, world, rule,
                 offset_word, world);
   }
+  if (f[kFaultStartWorld] != 0) {
+    // a registered episode start a stepping launch skipped (step_load.h: report_start)
+    const uint32_t world = f[kFaultStartWorld] - 1, index = f[kFaultStartWorld + 1], rule = f[kFaultStartWorld + 2],
+                   offset_word = f[kFaultStartWorld + 3];
+    e->h_fault[kFaultStartWorld] = 0;   // reported once; the engine stays usable
+    if (rule == 0 && offset_word == 0)
+      return fail(MP_ERR_INVALID,
+                  "%s: MpEpisodeStarts: rows[%u] = %d is neither -1 nor a row of the bank; world %u took the "
+                  "level's own reset", who, world, (int)index, world);
+    return fail(MP_ERR_INVALID,
+                "%s: MpEpisodeStarts: row %d, which rows[%u] names, is not a well-formed record (rule %u, "
+                "offset word 0x%x); world %u took the level's own reset", who, (int)index, world, rule,
+                offset_word, world);
+  }
   if (f[FAULT_STATE_INDEX] != 0) {
     const uint32_t at = f[FAULT_STATE_INDEX] - 1, index = f[FAULT_STATE_INDEX + 1];
     const bool load = f[FAULT_STATE_INDEX + 2] == 1;
@@ -428,11 +451,19 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
   uint8_t* wrgb = (uint8_t*)e->bound[MP_OBS_WORLD_RGB];
   const int pk = rgb ? e->pool_k() : 1;
   const int views = rgb && wrgb ? 2 : wrgb ? 1 : 0;
-  if (many || (!rgb && !wrgb) || !e->fuse(rgb == nullptr)) {
-    if (many)
-      launch_step_many(e->t, e->sub, args, *many, e->stream);
-    else
+  // (registered episode starts: the step kernels' own family, then the draw-only launches)
+  const stepk::StartArgs* starts =
+      e->starting() && (mode == STEP_MODE_STEP || mode == STEP_MODE_FIELDS) ? &e->starts : nullptr;
+  if (many || starts || (!rgb && !wrgb) || !e->fuse(rgb == nullptr)) {
+    if (many) {
+      StepManyLaunch l = *many;
+      l.starts = starts;
+      launch_step_many(e->t, e->sub, args, l, e->stream);
+    } else if (starts) {
+      launch_step_starts(e->t, e->sub, args, *starts, e->stream);
+    } else {
       launch_step(e->t, e->sub, args, e->stream);
+    }
     if (rgb) draw(e, rgb, nullptr, pk);
     if (wrgb) draw(e, nullptr, wrgb);
   } else {
@@ -984,6 +1015,8 @@ int plan_views(MpEngine* e, const MpDevOptions* dev) {
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the step kernels failed: %d", rc);
   if (int rc = prepare_step_many())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the K-step kernels failed: %d", rc);
+  if (int rc = prepare_step_starts())
+    return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the episode-start kernels failed: %d", rc);
   if (dev && dev->verbose)
     for (int v = 0; v < 6; ++v) {
       const FramePlan& pl = e->plan[v & 1][v >> 1];
@@ -1209,7 +1242,7 @@ int mp_info(const MpEngine* e, MpInfo* out) {
   out->world_state_bytes = e->t.world_stride;
   // the launch form of a step with the views bound right now (the per-agent view
   // if none is)
-  out->fused = e->fuse(!e->agent_view() && e->bound[MP_OBS_WORLD_RGB]) ? 1 : 0;
+  out->fused = !e->has_starts && e->fuse(!e->agent_view() && e->bound[MP_OBS_WORLD_RGB]) ? 1 : 0;
   out->num_resources = e->inventory_types();
   out->num_action_fields = e->t.nfields;
   {
@@ -2016,6 +2049,52 @@ static int states_hash(MpEngine* e, const MpStatesHash& r) {
   return MP_OK;
 }
 
+// An MpEpisodeStarts request (include/mp_engine.h; carried by mp_restore): registers, replaces or
+// clears the engine's episode starts.  No launch; everything is checked before anything changes.
+static int episode_starts(MpEngine* e, const MpEpisodeStarts& r) {
+  static const char kWho[] = "MpEpisodeStarts";
+  if (!e) return fail(MP_ERR_INVALID, "%s: NULL engine", kWho);
+  if (r.struct_size != sizeof(MpEpisodeStarts))
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpEpisodeStarts));
+  if (!r.bank) {   // clears the registration: the engine's launches are what they were
+    e->has_starts = false;
+    e->starts = stepk::StartArgs{};
+    return MP_OK;
+  }
+  if (!e->auto_reset)
+    return fail(MP_ERR_INVALID, "%s: the engine was created with auto_reset = 0: no world ever starts an "
+                "episode by itself", kWho);
+  if (e->unfused == 2)
+    return fail(MP_ERR_UNSUPPORTED, "%s: the engine was created with MpConfig.unfused = 2 (one launch a step); "
+                "a step with registered episode starts is the step kernels' launch and one per view", kWho);
+  if (r.bank_rows <= 0) return fail(MP_ERR_INVALID, "%s: bank_rows %d: the bank has no rows", kWho, r.bank_rows);
+  if (!r.rows) return fail(MP_ERR_INVALID, "%s: NULL rows", kWho);
+  if (r.fresh != 0 && r.fresh != 1)
+    return fail(MP_ERR_INVALID, "%s: fresh %d is neither 0 nor 1", kWho, r.fresh);
+  if (r.fingerprint != e->fingerprint)
+    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this engine's (%016llx): "
+                "they were saved by an engine of another pack, player count or record layout", kWho,
+                (unsigned long long)r.fingerprint, (unsigned long long)e->fingerprint);
+  if ((uintptr_t)r.bank & 15)   // (records are read in 16-byte lines)
+    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", kWho, r.bank);
+  if (((uintptr_t)r.rows & 3) || ((uintptr_t)r.verdicts & 3))
+    return fail(MP_ERR_INVALID, "%s: rows %p and verdicts %p must be 4-byte aligned", kWho, (const void*)r.rows,
+                (const void*)r.verdicts);
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = check_bank(e, r.bank, (uint64_t)r.bank_rows * (uint64_t)e->t.world_stride, "MpEpisodeStarts (bank)"))
+    return rc;
+  if (int rc = check_bank(e, r.rows, (uint64_t)e->N * 4, "MpEpisodeStarts (rows)")) return rc;
+  if (r.verdicts)
+    if (int rc = check_bank(e, r.verdicts, (uint64_t)r.bank_rows * 8, "MpEpisodeStarts (verdicts)")) return rc;
+  e->starts.bank = (const uint8_t*)r.bank;
+  e->starts.rows = r.rows;
+  e->starts.verdicts = r.verdicts;
+  e->starts.bank_rows = r.bank_rows;
+  e->starts.fresh = r.fresh;
+  e->has_starts = true;
+  return MP_OK;
+}
+
 static_assert(sizeof(MpStatesObserve) == 64 && sizeof(MpStatesObserve) != sizeof(MpKernelVariant) &&
                   sizeof(MpStatesObserve) != sizeof(MpWorldStates) && sizeof(MpStatesObserve) != sizeof(MpStepMany) &&
                   sizeof(MpStatesObserve) != sizeof(MpStepTrajectory),
@@ -2035,6 +2114,10 @@ static_assert(MP_SIZE_DIFFERS(MpStateLayout) && MP_SIZE_DIFFERS(MpStatesCheck) &
               "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
 static_assert(sizeof(MpStatesHash) == 104 && MP_SIZE_DIFFERS(MpStatesHash) &&
                   sizeof(MpStatesHash) != sizeof(MpStateLayout) && sizeof(MpStatesHash) != sizeof(MpStatesCheck),
+              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
+static_assert(sizeof(MpEpisodeStarts) == 72 && MP_SIZE_DIFFERS(MpEpisodeStarts) &&
+                  sizeof(MpEpisodeStarts) != sizeof(MpStateLayout) && sizeof(MpEpisodeStarts) != sizeof(MpStatesCheck) &&
+                  sizeof(MpEpisodeStarts) != sizeof(MpStatesHash),
               "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
 #undef MP_SIZE_DIFFERS
 // An MpKernelVariant request (carried by mp_snapshot; `e` may be NULL: the host-only question).
@@ -2109,6 +2192,11 @@ int mp_restore(MpEngine* e, const void* buf, uint64_t bytes) {
     MpStepTrajectory r;   // (read only: nothing is written back)
     memcpy(&r, buf, sizeof r);
     return trajectory_request(e, r);
+  }
+  if (buf && bytes == sizeof(MpEpisodeStarts)) {
+    MpEpisodeStarts r;   // (read only: nothing is written back)
+    memcpy(&r, buf, sizeof r);
+    return episode_starts(e, r);
   }
   if (!e || !buf || bytes != mp_snapshot_bytes(e))
     return fail(MP_ERR_INVALID, "mp_restore: bad buffer");
@@ -2395,6 +2483,12 @@ struct Events {   // RAII: a pair of timing events
 };
 
 int timed_launches_us(MpEngine* e, bool real, int reps, double* us) {
+  // (a probe never starts a world from the registered bank: it times the engine's own launches)
+  struct HoldStarts {
+    MpEngine* e; bool was;
+    explicit HoldStarts(MpEngine* eng) : e(eng), was(eng->starts_hold) { e->starts_hold = true; }
+    ~HoldStarts() { e->starts_hold = was; }
+  } hold(e);
   Events ev;
   if (int rc = ev.create()) return rc;
   int rc = MP_OK;

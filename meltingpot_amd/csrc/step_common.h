@@ -872,6 +872,18 @@ struct StepArgs {
   int bank_rows;
 };
 
+// Registered episode starts (include/mp_episode_starts.h; step_load.h: start_world): what the
+// k_step_starts_* / k_many_starts_* families get besides StepArgs: a world that
+// auto-resets in a step takes row rows[w] of `bank` instead of the level's own first frame.
+// An argument of its own: StepArgs, and every kernel that takes only it, are what they were.
+struct StartArgs {
+  const uint8_t* bank;       // [bank_rows][world_stride], read in place, never written
+  const int32_t* rows;       // [N], read when the world's episode ends (-1: the level's own reset)
+  const int32_t* verdicts;   // [bank_rows][2] as MP_CHECK_ROWS writes them, or NULL: every row is taken
+  int bank_rows;
+  int fresh;                 // 1: the started world keeps its own seed and episode count
+};
+
 // Substrates without LDS extras behind the marks (territory overloads both).
 template <class Tables>
 __host__ __device__ inline int extra_bytes(const Tables&) { return 0; }

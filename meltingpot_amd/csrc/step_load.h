@@ -178,12 +178,96 @@ __device__ inline void load_world(const DevTables& t, const Tables& c, const Wor
   store_record(t, rec, wd.gw, lane);
 }
 
-// A stepping launch's work for one world: STEP_MODE_LOAD's, or the level's step / reset.
-template <class Tables, class Sites>
+// ---- registered episode starts (include/mp_episode_starts.h: MpEpisodeStarts) ------------------
+// A start the launch skipped (the world took the level's own reset): words of their own, which
+// the next synchronising call reports — word 32 = world + 1 (ONE world of a launch claims it, a
+// compare-and-swap from 0, and writes the other three), 33 = rows[world], 34 = the rule of the
+// row's verdict (0: the index is neither -1 nor a row of the bank), 35 = its offset word
+// (mp_common.h: kFaultStartWorld).
+__device__ inline void report_start(const DevTables& t, int lane, int w, int index, int rule, int offset) {
+  if (lane == 0 && atomicCAS(&t.fault[kFaultStartWorld], 0u, (uint32_t)w + 1u) == 0u) {
+    t.fault[kFaultStartWorld + 1] = (uint32_t)index;
+    t.fault[kFaultStartWorld + 2] = (uint32_t)rule;
+    t.fault[kFaultStartWorld + 3] = (uint32_t)offset;
+  }
+}
+
+// Does this step start the world's next episode?  dispatch()'s own test for returning 1 in
+// STEP_MODE_STEP / STEP_MODE_FIELDS (wave-uniform), asked BEFORE the step runs.
+__device__ inline bool starts_here(const WorldTail* tail, const StepArgs& args) {
+  if (args.mode & 1) return false;   // (RESET, LOAD: an explicit reset or load is not an episode start)
+  return __builtin_amdgcn_readfirstlane((int)(tail->started && tail->done)) != 0 && args.auto_reset != 0;
+}
+
+// The row world `w` starts from, or -1 for the level's own reset: rows[w], read now; an index
+// outside [-1, bank_rows) or a row whose verdict is not (0, 0) is reported and never read.
+__device__ inline int start_row(const DevTables& t, const StartArgs& st, int w, int lane) {
+  const int r = __builtin_amdgcn_readfirstlane(st.rows[w]);
+  if (r == -1) return -1;
+  if (r < -1 || r >= st.bank_rows) {
+    report_start(t, lane, w, r, 0, 0);
+    return -1;
+  }
+  if (st.verdicts) {
+    const int rule = __builtin_amdgcn_readfirstlane(st.verdicts[2 * (size_t)r]);
+    const int offset = __builtin_amdgcn_readfirstlane(st.verdicts[2 * (size_t)r + 1]);
+    if (rule != 0 || offset != 0) {
+      report_start(t, lane, w, r, rule, offset);
+      return -1;
+    }
+  }
+  return r;
+}
+
+// The episode start of the world of `wd`, whose rows[w] start_row() has just accepted, run BEHIND
+// the level's own reset of the same step.  The reset has done what an episode start does to the
+// world's own words (episode + 1, MP_CTR_EPISODES + 1) and has written every kind a reset writes;
+// this is load_world itself on top of it, with the registration's bank and rows as the load's bank
+// and src — so a step with a registration leaves exactly what step() and then MP_STATES_LOAD
+// leave, and load_world is the text it was.  With `fresh` the seed and the episode count the
+// reset left are put back into the loaded record (the orders the row cached were drawn under the
+// row's: orders_step 0 has them drawn again) and the record is written back once more.
+template <class Tables>
+__device__ inline void start_world(const DevTables& t, const Tables& c, const World& wd,
+                                   const StepArgs& args, const StartArgs& st) {
+  const int lane = wd.lane;
+  WorldTail* tail = reinterpret_cast<WorldTail*>(wd.rec + t.grid_pad);
+  wsync();   // the reset's finish() has read the record for its write-back
+  uint32_t keep = 0;   // lane 0, 1: the seed's halves; lane 2: the episode count
+  if (lane < 2) keep = (uint32_t)(tail->seed >> (32 * lane));
+  else if (lane == 2) keep = tail->episode;
+  StepArgs la = args;
+  la.bank = st.bank; la.src = st.rows; la.bank_rows = st.bank_rows;
+  load_world(t, c, wd, la);
+  if (st.fresh) {
+    const uint32_t lo = (uint32_t)rdlane((int)keep, 0), hi = (uint32_t)rdlane((int)keep, 1);
+    const uint32_t ep = (uint32_t)rdlane((int)keep, 2);
+    if (lane == 0) {
+      tail->seed = ((uint64_t)hi << 32) | lo;
+      tail->episode = ep;
+      tail->orders_step = 0u;
+    }
+    wsync();
+    store_record(t, wd.rec, wd.gw, lane);
+  }
+}
+
+// A stepping launch's work for one world: STEP_MODE_LOAD's, or the level's step / reset — and,
+// in the families of the registered episode starts (kStarts), the start behind an auto-reset.
+template <bool kStarts = false, class Tables, class Sites>
 __device__ inline void step_or_load(const DevTables& t, const Tables& c, const Sites& sites,
-                                    const World& wd, const Action& act, const StepArgs& args) {
-  if (args.mode == STEP_MODE_LOAD) load_world(t, c, wd, args);
-  else step_world(t, c, sites, wd, act, args);
+                                    const World& wd, const Action& act, const StepArgs& args,
+                                    const StartArgs* st = nullptr) {
+  if (args.mode == STEP_MODE_LOAD) {
+    load_world(t, c, wd, args);
+  } else if constexpr (kStarts) {
+    const WorldTail* tail = reinterpret_cast<const WorldTail*>(wd.rec + t.grid_pad);
+    const int r = starts_here(tail, args) ? start_row(t, *st, wd.w, wd.lane) : -1;
+    step_world(t, c, sites, wd, act, args);
+    if (r >= 0) start_world(t, c, wd, args, *st);
+  } else {
+    step_world(t, c, sites, wd, act, args);
+  }
 }
 
 }  // namespace stepk

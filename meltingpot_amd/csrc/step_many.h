@@ -139,6 +139,7 @@ struct StepManyLaunch {
   bool any_rows;
   StateRows state;
   HashRows hash;
+  const stepk::StartArgs* starts;   // the engine's registered episode starts (submit() sets it), or NULL
 };
 
 void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,

@@ -82,10 +82,18 @@ __device__ inline T* row_of(uint8_t* base, long long bytes, int k, T* in_place) 
 //    both rows runs this family too: whether the record is stored as well is a runtime test
 //    here and nowhere else (`sp->row`), and the three families above are what they were.
 // Which kinds are asked for is wave-uniform: every branch on it is a scalar one.
-template <bool Rows, bool States, class Tables, class Sites, bool Hashes = false>
+//  * registered episode starts (MpEpisodeStarts, `st`, Starts = true: the k_many_starts_* family): a
+//    step in which a world auto-resets runs start_world() behind the level's reset (step_load.h),
+//    with the outputs of row k — so row k of every kind a start writes holds the start's values,
+//    the level kinds are copied from the in-place buffer the start wrote, and LAYER, the state row
+//    and the hash row come from the started record in LDS.  ONE family for every combination of
+//    rows: which rows are asked for is a runtime test here (r.fin[i], r.layer, sp->row, hp->row),
+//    as the state row is in k_step_hashes_*, and the four families above are what they were.
+template <bool Rows, bool States, class Tables, class Sites, bool Hashes = false, bool Starts = false>
 __device__ inline void run_many(const DevTables& t, const Tables& c, const StepArgs& args0,
                                 const ManyArgs& m, const StepRows* rp, int extra,
-                                const StateRows* sp = nullptr, const HashRows* hp = nullptr) {
+                                const StateRows* sp = nullptr, const HashRows* hp = nullptr,
+                                const StartArgs* st = nullptr) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
@@ -152,11 +160,12 @@ __device__ inline void run_many(const DevTables& t, const Tables& c, const StepA
     args.out.discount = row_of(m.row[3], m.row_bytes[3], k, args0.out.discount);
     args.out.events = row_of(m.row[4], m.row_bytes[4], k, args0.out.events);
     const Action act = lookup_action(t, wd, act_id, args0.mode);
-    step_world(t, c, sites, wd, act, args);
+    if constexpr (Starts) step_or_load<true>(t, c, sites, wd, act, args, st);
+    else step_world(t, c, sites, wd, act, args);
     act_id = next_id;
     if constexpr (Rows) {
       const StepRows& r = *rp;
-      if (States || Hashes || r.layer || r.n_level) {
+      if (States || (Hashes && !Starts) || (Starts && (sp->row || hp->row)) || r.layer || r.n_level) {
         wsync();   // the record in LDS is final; the step's stores to the level kinds come before the loads below
         const WorldTail* tl = reinterpret_cast<const WorldTail*>(wd.rec + t.grid_pad);
         if (__builtin_amdgcn_readfirstlane((int)tl->started)) {
@@ -177,10 +186,12 @@ __device__ inline void run_many(const DevTables& t, const Tables& c, const StepA
           if constexpr (Hashes) {
             if (sp->row)
               store_record(t, wd.rec, sp->row + (long long)k * sp->bytes + (size_t)w * t.world_stride, lane_k);
+            if (!Starts || hp->row) {
             const uint64_t sum =
                 state_hash::wave_sum(state_hash::hash_share(hp->mask, wd.rec, t.world_stride >> 4, lane_k, 64));
             if (lane_k == 0)
               reinterpret_cast<uint64_t*>(hp->row + (long long)k * hp->bytes)[w] = state_hash::fmix64(sum);
+            }
           }
         }
       }
@@ -294,14 +305,34 @@ MP_STEP_HASHES_KERNEL(k_step_hashes_matrix, MatrixTables, MatrixSites, 0)
 MP_STEP_HASHES_KERNEL(k_step_hashes_territory, TerritoryTables, TerritorySites, extra_bytes(c))
 #undef MP_STEP_HASHES_KERNEL
 
+// ... and with registered episode starts (MpEpisodeStarts), whatever rows the request names: a fifth
+// family, so that the four above run exactly the code they ran before there was one.
+#define MP_MANY_STARTS_KERNEL(name, TablesT, SitesT, extra)                                          \
+  __global__ __launch_bounds__(kWorldsPerGroup * 64) void name(DevTables t, TablesT c, StepArgs args, \
+                                                               ManyArgs m, StepRows r, StateRows s,  \
+                                                               HashRows h, StartArgs st) {           \
+    run_many<true, false, TablesT, SitesT, true, true>(t, c, args, m, &r, extra, &s, &h, &st);       \
+  }
+MP_MANY_STARTS_KERNEL(k_many_starts_clean_up, CleanUpTables, CleanUpSites, 0)
+MP_MANY_STARTS_KERNEL(k_many_starts_commons, CommonsTables, CommonsSites, 0)
+MP_MANY_STARTS_KERNEL(k_many_starts_coins, CoinsTables, CoinsSites, 0)
+MP_MANY_STARTS_KERNEL(k_many_starts_coop, CoopTables, CoopSites, 0)
+MP_MANY_STARTS_KERNEL(k_many_starts_gift, GiftTables, GiftSites, 0)
+MP_MANY_STARTS_KERNEL(k_many_starts_cook, CookTables, CookSites, 0)
+MP_MANY_STARTS_KERNEL(k_many_starts_mushroom, MushroomTables, MushroomSites, extra_bytes(c))
+MP_MANY_STARTS_KERNEL(k_many_starts_matrix, MatrixTables, MatrixSites, 0)
+MP_MANY_STARTS_KERNEL(k_many_starts_territory, TerritoryTables, TerritorySites, extra_bytes(c))
+#undef MP_MANY_STARTS_KERNEL
+
 }  // namespace
 
 // The K-step kernels may take all 160 KB of a CU's LDS, like the single-step ones.
 int prepare_step_many() {
-  const void* km[36] = {
+  const void* km[45] = {
 #define MP_BOTH(level)                                                                             \
   reinterpret_cast<const void*>(&k_step_many_##level), reinterpret_cast<const void*>(&k_step_rows_##level), \
-      reinterpret_cast<const void*>(&k_step_states_##level), reinterpret_cast<const void*>(&k_step_hashes_##level)
+      reinterpret_cast<const void*>(&k_step_states_##level), reinterpret_cast<const void*>(&k_step_hashes_##level), \
+      reinterpret_cast<const void*>(&k_many_starts_##level)
       MP_BOTH(clean_up), MP_BOTH(commons), MP_BOTH(coins), MP_BOTH(territory), MP_BOTH(matrix),
       MP_BOTH(coop), MP_BOTH(gift), MP_BOTH(cook), MP_BOTH(mushroom)};
 #undef MP_BOTH
@@ -314,7 +345,8 @@ int prepare_step_many() {
 // K steps of every world in one launch (MpStepMany, MpStepTrajectory): the geometry of
 // launch_step.  l.any_rows == false: only rows of the five kinds, which runs k_step_many_*;
 // l.state.row: the state rows, which runs k_step_states_*; l.hash.row: the hash rows (with or
-// without the state rows), which runs k_step_hashes_*.
+// without the state rows), which runs k_step_hashes_*; l.starts: the engine's registered episode
+// starts, which runs k_many_starts_* whatever the rows.
 void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
                       const StepManyLaunch& l, hipStream_t stream) {
   const ManyArgs& m = l.many;
@@ -325,7 +357,9 @@ void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk:
   StepRows r = l.rows;   // (the level kinds' sources: this submission's buffers)
   for (int i = 0; i < r.n_level; ++i) r.level[i].src = level_source(args.out, r.level[i].which);
 #define MP_LAUNCH(level, tables)                                                                  \
-  if (l.hash.row)                                                                                 \
+  if (l.starts)                                                                                   \
+    hipLaunchKernelGGL(k_many_starts_##level, grid, block, lds, stream, t, tables, args, m, r, l.state, l.hash, *l.starts); \
+  else if (l.hash.row)                                                                                 \
     hipLaunchKernelGGL(k_step_hashes_##level, grid, block, lds, stream, t, tables, args, m, r, l.state, l.hash); \
   else if (l.state.row)                                                                           \
     hipLaunchKernelGGL(k_step_states_##level, grid, block, lds, stream, t, tables, args, m, r, l.state); \

@@ -646,6 +646,44 @@ def check_step_many(shape, dtype, num_worlds: int, num_players: int, *, repeat=N
   return K
 
 
+# Registered episode starts (include/mp_engine.h: MpEpisodeStarts), carried by mp_restore
+class MpEpisodeStarts(ctypes.Structure):
+  _fields_ = [("struct_size", ctypes.c_uint32), ("fresh", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
+              ("bank", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("verdicts", ctypes.c_void_p),
+              ("bank_rows", ctypes.c_int32), ("reserved", ctypes.c_int32), ("reserved2", ctypes.c_uint64 * 3)]
+
+
+def check_episode_starts(bank, rows, verdicts, num_worlds: int, state_bytes: int, device) -> int:
+  """The argument rules of Engine.set_episode_starts, without an engine: `bank` a contiguous uint8
+  tensor [M, state_bytes] with M >= 1, `rows` a contiguous int32 tensor [num_worlds], `verdicts`
+  None or a contiguous int32 tensor [M, 2], all on `device`.  Returns M.  ValueError otherwise."""
+  import torch
+  device = torch.device(device)
+  def on_device(x):
+    return x.device.type == device.type and (device.index is None or x.device.index == device.index)
+  def describe(x):
+    return f"{getattr(x, 'dtype', type(x).__name__)} {tuple(getattr(x, 'shape', ()))}"
+  if (not isinstance(bank, torch.Tensor) or bank.dtype != torch.uint8 or bank.dim() != 2 or
+      int(bank.shape[1]) != int(state_bytes) or not bank.is_contiguous()):
+    raise ValueError(f"set_episode_starts: bank must be a contiguous uint8 tensor [M, {int(state_bytes)}] "
+                     f"(got {describe(bank)})")
+  M = int(bank.shape[0])
+  if M < 1:
+    raise ValueError("set_episode_starts: the bank has no rows")
+  if (not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or tuple(rows.shape) != (int(num_worlds),) or
+      not rows.is_contiguous()):
+    raise ValueError(f"set_episode_starts: rows must be a contiguous int32 tensor [{int(num_worlds)}], one row "
+                     f"index per world (got {describe(rows)})")
+  if verdicts is not None and (not isinstance(verdicts, torch.Tensor) or verdicts.dtype != torch.int32 or
+                               tuple(verdicts.shape) != (M, 2) or not verdicts.is_contiguous()):
+    raise ValueError(f"set_episode_starts: verdicts must be a contiguous int32 tensor [{M}, 2], check_states of "
+                     f"the whole bank (got {describe(verdicts)})")
+  for name, x in (("bank", bank), ("rows", rows), ("verdicts", verdicts)):
+    if x is not None and not on_device(x):
+      raise ValueError(f"set_episode_starts: {name} lives on {x.device}, the engine on {device}")
+  return M
+
+
 def _step_distance(tensor, what: str) -> int:
   """Bytes between tensor[k] and tensor[k + 1] of a tensor that may be non-contiguous along its
   first dimension only (a column slice [:, a:b] of a wider tensor)."""
@@ -895,6 +933,7 @@ class Engine:
            for k, kind in OBS_RGB_POOL.items()},
     }
     self._bound: Dict[int, "torch.Tensor"] = {}
+    self._episode_starts = None
 
   @property
   def fused(self) -> bool:
@@ -1539,6 +1578,46 @@ class Engine:
     world_states_request(self._L, self._h, MP_STATES_LOAD, bank=bank.data_ptr(),
                          bank_rows=int(bank.shape[0]), src=loaded.data_ptr(), fingerprint=fp)
     self._state_args = (s, loaded)   # (kept until the next call: the launches may not have run yet)
+
+  # -- episode starts (include/mp_engine.h: an MpEpisodeStarts request) --
+  def set_episode_starts(self, bank, rows, *, fresh: bool = False, verdicts=None,
+                         fingerprint: Optional[int] = None):
+    """From now on a world that auto-resets starts from row rows[w] of `bank` (uint8 [M, S] device
+    tensor from save_worlds or step_many(states=True)) instead of the level's own first frame;
+    rows[w] = -1 keeps the level's reset.  `rows`: int32 [N] device tensor, read by every later
+    step (each of the K steps of step_many too) at the moment a world's episode ends — rewrite it
+    whenever you like.  A started world is what load_worlds of the row gives (FIRST, the row's
+    observations; the world keeps its own counters), and the start counts as an episode.
+    verdicts: check_states(bank) of the whole bank — a row whose verdict is not (0, 0) is never
+    read.  A bad index or a refused row gives the level's own reset, and the next synchronising
+    call raises ValueError naming world, index and rule.  fresh=True: the started world keeps its
+    own seed and episode count, so worlds that share a row draw differently.  `fingerprint`: the
+    rows' (default: this engine's).  The engine keeps references to the tensors and never writes
+    the bank.  While set, a step with a bound pixel view is two launches (`fused` is False).
+    No launch; does not synchronise."""
+    M = check_episode_starts(bank, rows, verdicts, self.N, int(self.info.world_state_bytes), self.device)
+    if not isinstance(fresh, (bool, np.bool_)):
+      raise ValueError(f"set_episode_starts: fresh must be True or False (got {fresh!r})")
+    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    req = MpEpisodeStarts(ctypes.sizeof(MpEpisodeStarts), 1 if fresh else 0, fp)
+    req.bank, req.rows, req.bank_rows = bank.data_ptr(), rows.data_ptr(), M
+    req.verdicts = None if verdicts is None else verdicts.data_ptr()
+    _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
+           "mp_restore (MpEpisodeStarts)")
+    self._episode_starts = {"bank": bank, "rows": rows, "verdicts": verdicts, "fresh": bool(fresh),
+                            "fingerprint": fp}
+
+  def clear_episode_starts(self):
+    """Episodes start from the level's own map again; the engine's launches are what they were."""
+    req = MpEpisodeStarts(ctypes.sizeof(MpEpisodeStarts))
+    _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
+           "mp_restore (MpEpisodeStarts)")
+    self._episode_starts = None
+
+  @property
+  def episode_starts(self):
+    """The registration as a dict (bank, rows, verdicts, fresh, fingerprint), or None."""
+    return None if self._episode_starts is None else dict(self._episode_starts)
 
   def observe_states(self, bank, kind: int, rows=None, out=None, fingerprint: Optional[int] = None):
     """Observation `kind` of rows of `bank` (uint8 [M, S] device tensor from save_worlds or

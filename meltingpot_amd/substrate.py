@@ -1104,6 +1104,45 @@ class Substrate:
     self._submissions += 1
     return self._emit(self._timestep())
 
+  def set_episode_starts(self, states: Optional[WorldStates], rows=None, *, fresh: bool = False,
+                         check: Optional[bool] = None):
+    """Where auto-reset episodes begin.  From now on a world whose episode has ended starts from
+    row rows[w] of `states` instead of the level's own first frame — in `step` and in every one
+    of the K steps of `step_many` — as `load_state` of that row would start it: FIRST (LAST for a
+    row saved from a finished episode), the row's observations, the row's seed, episode and
+    future.  Returns `rows`, the int32 [num_worlds] device tensor the engine reads each time an
+    episode ends (allocated and filled with -1 when None: -1 keeps the level's own reset), so
+
+        rows = env.set_episode_starts(bank)
+        rows[:] = torch.randint(len(bank), rows.shape)   # any time, no call needed
+
+    fresh=True: a started world keeps its own seed and its own episode count (and draws its
+    visiting orders anew), so worlds that start from one row diverge — what training wants; the
+    default replays the saved world, what evaluation and tests want.
+    check: None checks iff `states.edited` (they went through `state_fields`); True / False force
+    it.  A check is one `check_states` launch over the whole bank, now; a world whose row it
+    refused — or whose index is neither -1 nor a row — takes the level's own reset, and the next
+    synchronising call raises ValueError naming the world, the row and the rule.  Rows edited
+    after this call are not judged again: call it again.
+    `states` None clears the registration.  The substrate keeps `states` and `rows` alive and
+    never writes the bank.  While a registration is set a step with pixel leaves is two launches
+    instead of one.  No host synchronisation."""
+    self._eng.use_current_stream()
+    if states is None:
+      self._eng.clear_episode_starts()
+      return None
+    if not isinstance(states, WorldStates):
+      raise ValueError("set_episode_starts takes the WorldStates of save_state or step_many(states=True)")
+    states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
+    t = self._eng._torch
+    if rows is None:
+      rows = t.full((self.num_worlds,), -1, dtype=t.int32, device=self._eng.device)
+    check = _resolve_check(states, check)
+    verdicts = self._eng.check_states(states.data, fingerprint=states.fingerprint) if check else None
+    self._eng.set_episode_starts(states.data, rows, fresh=fresh, verdicts=verdicts,
+                                 fingerprint=states.fingerprint)
+    return rows
+
   # the leaves that are functions of a world's record (engine_lib.STATE_OBS_KINDS)
   _STATE_LEAVES = ("RGB", "WORLD.RGB", "LAYER", "READY_TO_SHOOT", "POSITION", "ORIENTATION", "INVENTORY")
 
@@ -1873,6 +1912,27 @@ class MixtureSubstrate:
 
   def step_leaves(self) -> Dict[str, int]:
     return self._members[0].step_leaves()
+
+  def set_episode_starts(self, states_per_member, rows=None, *, fresh: bool = False,
+                         check: Optional[bool] = None):
+    """`Substrate.set_episode_starts` per member: `states_per_member[i]` is member i's bank (a
+    `WorldStates` of that member's fingerprint) or None (member i keeps, or returns to, the
+    level's own reset).  Returns ONE int32 [N] device tensor `rows` (allocated and filled with -1
+    when None): member i reads its slice `rows[member_slice(i)]` in place, nothing is copied, and
+    an entry is a row of THAT member's bank."""
+    states_per_member = list(states_per_member)
+    if len(states_per_member) != len(self._members):
+      raise ValueError(f"set_episode_starts: {len(self._members)} members, {len(states_per_member)} banks")
+    t = self._members[0]._eng._torch
+    device = self._members[0]._eng.device
+    if rows is None:
+      rows = t.full((self._N,), -1, dtype=t.int32, device=device)
+    elif (not isinstance(rows, t.Tensor) or rows.dtype != t.int32 or tuple(rows.shape) != (self._N,) or
+          not rows.is_contiguous()):
+      raise ValueError(f"set_episode_starts: rows must be a contiguous int32 tensor [{self._N}]")
+    for m, states, off, n in zip(self._members, states_per_member, self._offsets, self._counts):
+      m.set_episode_starts(states, None if states is None else rows[off:off + n], fresh=fresh, check=check)
+    return rows
 
   def hash_worlds(self, worlds=None, planes=None, fields=None):
     """int64 [N] device tensor: every member's `Substrate.hash_worlds` of its own worlds, in
