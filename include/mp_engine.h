@@ -575,6 +575,62 @@ typedef struct {
   uint64_t reserved;       /* 0 */
 } MpStatesObserve;
 
+/* Sampled views of bank rows: ONE player's view of each sampled row — the (step, world, player)
+ * triples a multi-agent learner draws from a replay buffer that keeps states.  Where
+ * MpStatesObserve draws every player of a row, this request writes the sampled views alone: P x
+ * fewer bytes, and no [count][P]... intermediate to index afterwards.  It rides mp_snapshot and is
+ * recognised by its size: `bytes` = sizeof(MpStatesView), `host_buf` a HOST MpStatesView with
+ * struct_size set to it.  include/mp_states_view.h wraps it as an inline C function.
+ *
+ * Element i of `dst` is the view of player players[i] of row rows[i] of `bank` (rows == NULL: row
+ * i).  `dst` has the kind's per-player layout with the [N][P] axes replaced by [count]:
+ *   MP_OBS_RGB             u8  [count][VH*S][VW*S][3]
+ *   MP_OBS_RGB_POOLk       u8  [count][VH*S/k][VW*S/k][3]
+ *   MP_OBS_LAYER           i32 [count][VH][VW][L]
+ *   MP_OBS_READY_TO_SHOOT  f64 [count]
+ *   MP_OBS_POSITION        i32 [count][2]
+ *   MP_OBS_ORIENTATION     i32 [count]
+ *   MP_OBS_INVENTORY       f64 [count][R]
+ * and element i is, byte for byte, element [i][players[i]] of what an MpStatesObserve request
+ * with the same `rows` writes.  Rows may repeat, (row, player) pairs may repeat, and `count` has no
+ * relation to the engine's N.  `dst` needs the alignment of the kind's element size only: 1 for
+ * every pixel kind, the pooled ones included (a pooled view of clean_up is 363 bytes: views start
+ * on any byte), 4 for LAYER, POSITION and ORIENTATION, 8 for the f64 kinds.
+ *
+ * The request is enqueued on the engine's stream and does not synchronise; no path of it
+ * allocates or frees device memory.  Every record is read from the bank row where it lies.  It
+ * writes nothing of the engine's: not its records or counters, not an in-place or bound output, not
+ * a ring slot or the ring's position, not the kept plans, not the scratch or the stash of
+ * MpStatesObserve, and mp_tune still regards an engine nothing else has been done with as such.
+ * It is legal on an engine that has never been reset.
+ *
+ * Refused before any launch, the engine left as it was — MP_ERR_INVALID: everything
+ * MpStatesObserve refuses (NULL bank or dst; count < 1 or bank_rows < 1; rows == NULL with count >
+ * bank_rows; a bank that is not 16-byte aligned; a wrong struct_size; a fingerprint that is not
+ * the engine's; dst_bytes < count x the kind's bytes per view; a dst not aligned to the kind's
+ * element size; a bank, rows, players or dst that is not device memory of the engine's device or
+ * does not lie inside one allocation; a kind outside [0, MP_OBS_KINDS); a transition kind); NULL
+ * players; MP_OBS_WORLD_RGB, which is not a per-player kind; nonzero reserved words.
+ * MP_ERR_UNSUPPORTED: a kind the level does not have (mp_obs_bytes == 0); a record and a row of
+ * view cells that do not fit the LDS beside the renderer's tables.
+ * A rows[i] outside [0, bank_rows) or a players[i] outside [0, P) is never used as an index:
+ * element i of dst is left as it was — every such element of a request, however many — and the
+ * next synchronising call returns MP_ERR_INVALID once, naming MpStatesView, rows[i] or players[i]
+ * and the value (of several such indices one is reported); the engine stays usable. */
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(MpStatesView) */
+  int32_t kind;            /* MpObsKind: a per-player kind that is a function of the record */
+  uint64_t fingerprint;    /* in: the rows' (MP_STATES_SAVE's) */
+  const void* bank;        /* device uint8 [bank_rows][S] */
+  const int32_t* rows;     /* device int32 [count], NULL = rows 0 .. count - 1 */
+  const int32_t* players;  /* device int32 [count] */
+  void* dst;               /* device: the kind's per-player layout, [count] elements */
+  uint64_t dst_bytes;
+  int32_t bank_rows;
+  int32_t count;
+  uint64_t reserved[2];    /* 0 */
+} MpStatesView;
+
 /* The layout of a record, told by the library: what the bytes of a saved row are, so that a
  * caller can read and edit world states by field.  Rides mp_snapshot, recognised by its size:
  * `bytes` = sizeof(MpStateLayout), `host_buf` a HOST MpStateLayout with struct_size set to it.
@@ -1078,7 +1134,8 @@ int mp_box_fill(MpEngine* eng, MpObsKind kind, int32_t reps, MpBoxFill* out);
  * Words 9-11: an index a world-state launch skipped, or a row a checked load refused (word 9 =
  * world or position + 1, word 10 = the index or row, word 11 = what: 1 a load's src[], 2 a save's
  * world list, 3 an MpStatesObserve's rows[], 4 | rule << 8 a row an MpStatesCheck filter refused,
- * 5 an MpStatesCheck's rows[], 6 an MpStatesHash's rows[] or world list); of several such reports
+ * 5 an MpStatesCheck's rows[], 6 an MpStatesHash's rows[] or world list, 7 an MpStatesView's
+ * rows[], 8 an MpStatesView's players[] — whose three words belong together); of several such reports
  * of one launch the three words may belong to different ones.  Words 12-15: the refused row of a checked load once more, claimed by ONE
  * refused world of the launch (word 12 = world + 1, 13 = the row, 14 = the rule, 15 = the offset
  * word), reported first.  Each is reported once by the next synchronising call (MP_ERR_INVALID)

@@ -24,6 +24,7 @@
 #include "step_common.h"
 #include "step_many.h"
 #include "state_obs.h"
+#include "state_view.h"
 #include "state_check.h"
 #include "state_hash.h"
 
@@ -396,6 +397,11 @@ int sync_and_check(MpEngine* e, const char* who) {
     const bool observe = f[FAULT_STATE_INDEX + 2] == kFaultObserveRow;
     const uint32_t what = f[FAULT_STATE_INDEX + 2];
     e->h_fault[FAULT_STATE_INDEX] = 0;   // reported once; the engine stays usable
+    if (what == kFaultViewRow || what == kFaultViewPlayer)
+      return fail(MP_ERR_INVALID,
+                  "%s: MpStatesView: %s[%u] = %d is %s; element %u of the destination was left as it was",
+                  who, what == kFaultViewRow ? "rows" : "players", at, (int)index,
+                  what == kFaultViewRow ? "not a row of the bank" : "not a player of this engine", at);
     if (what == kFaultHashRow)
       return fail(MP_ERR_INVALID,
                   "%s: MpStatesHash: rows[%u] = %d is not a row of the bank (MP_HASH_WORLDS: no world of this "
@@ -1015,6 +1021,8 @@ int plan_views(MpEngine* e, const MpDevOptions* dev) {
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the step kernels failed: %d", rc);
   if (int rc = prepare_step_many())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the K-step kernels failed: %d", rc);
+  if (int rc = prepare_state_view())
+    return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the sampled-view kernels failed: %d", rc);
   if (int rc = prepare_step_starts())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the episode-start kernels failed: %d", rc);
   if (dev && dev->verbose)
@@ -1834,6 +1842,81 @@ static int states_observe(MpEngine* e, const MpStatesObserve& r) {
   return MP_OK;
 }
 
+// An MpStatesView request (include/mp_engine.h; carried by mp_snapshot): one player's view of each
+// sampled row, enqueued on the engine's stream.  Everything is checked before the launch; nothing
+// of the engine's is written and no device memory is allocated or freed.
+static int states_view(MpEngine* e, const MpStatesView& r) {
+  static const char kWho[] = "MpStatesView";
+  if (!e) return fail(MP_ERR_INVALID, "%s: NULL engine", kWho);
+  if (r.struct_size != sizeof(MpStatesView))
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpStatesView));
+  if (r.reserved[0] || r.reserved[1]) return fail(MP_ERR_INVALID, "%s: the reserved words must be 0", kWho);
+  if (!r.bank || !r.dst) return fail(MP_ERR_INVALID, "%s: NULL bank or dst", kWho);
+  if (!r.players) return fail(MP_ERR_INVALID, "%s: NULL players", kWho);
+  if (r.count < 1 || r.bank_rows < 1)
+    return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", kWho, r.count, r.bank_rows);
+  if (!r.rows && r.count > r.bank_rows)
+    return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are drawn (count %d, the bank "
+                "has %d rows)", kWho, r.count, r.bank_rows);
+  if (r.fingerprint != e->fingerprint)
+    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this engine's (%016llx): "
+                "they were saved by an engine of another pack, player count or record layout", kWho,
+                (unsigned long long)r.fingerprint, (unsigned long long)e->fingerprint);
+  const int kind = r.kind;
+  if (kind < 0 || kind >= MP_OBS_KINDS)
+    return fail(MP_ERR_INVALID, "%s: kind %d is no observation kind", kWho, kind);
+  if (kind == MP_OBS_WORLD_RGB)
+    return fail(MP_ERR_INVALID, "%s: MP_OBS_WORLD_RGB is not a per-player kind (MpStatesObserve draws it)", kWho);
+  const bool pixel = MpEngine::is_pixel_kind(kind);
+  uint64_t elem = 1;   // what dst is aligned to (a pixel kind, pooled or not: any byte)
+  switch (kind) {
+    case MP_OBS_LAYER: case MP_OBS_POSITION: case MP_OBS_ORIENTATION: elem = 4; break;
+    case MP_OBS_READY_TO_SHOOT: case MP_OBS_INVENTORY: elem = 8; break;
+    default:
+      if (!pixel)
+        return fail(MP_ERR_INVALID, "%s: kind %d is not a function of the record (a transition kind: what a "
+                    "step or a reset reports, which no saved state holds)", kWho, kind);
+  }
+  const uint64_t per = mp_obs_bytes(e, (MpObsKind)kind) / ((uint64_t)e->N * (uint64_t)e->t.P);
+  if (per == 0)
+    return fail(MP_ERR_UNSUPPORTED, "%s: this substrate has no observation %d", kWho, kind);
+  const uint64_t count = (uint64_t)r.count, need = count * per;
+  if (r.dst_bytes < need)
+    return fail(MP_ERR_INVALID, "%s: %d elements of %llu bytes need %llu bytes, dst has %llu", kWho, r.count,
+                (unsigned long long)per, (unsigned long long)need, (unsigned long long)r.dst_bytes);
+  if ((uintptr_t)r.dst % elem)
+    return fail(MP_ERR_INVALID, "%s: dst %p is not %llu-byte aligned", kWho, r.dst, (unsigned long long)elem);
+  if (r.rows && ((uintptr_t)r.rows & 3))
+    return fail(MP_ERR_INVALID, "%s: rows %p is not 4-byte aligned", kWho, (const void*)r.rows);
+  if ((uintptr_t)r.players & 3)
+    return fail(MP_ERR_INVALID, "%s: players %p is not 4-byte aligned", kWho, (const void*)r.players);
+  if ((uintptr_t)r.bank & 15)   // (records are read in 16-byte lines)
+    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", kWho, r.bank);
+  HIP_TRY(hipSetDevice(e->device));
+  const uint64_t S = (uint64_t)e->t.world_stride;
+  if (int rc = check_bank(e, r.bank, (uint64_t)r.bank_rows * S, "MpStatesView (bank)")) return rc;
+  if (r.rows)
+    if (int rc = check_bank(e, r.rows, count * 4, "MpStatesView (rows)")) return rc;
+  if (int rc = check_bank(e, r.players, count * 4, "MpStatesView (players)")) return rc;
+  if (int rc = check_bank(e, r.dst, need, "MpStatesView (dst)")) return rc;
+  const uint8_t* bank = (const uint8_t*)r.bank;
+  if (!pixel && kind != MP_OBS_LAYER) {
+    launch_state_view_scalar(e->t, e->sub, kind, bank, r.bank_rows, r.rows, r.players, r.count, r.dst, e->stream);
+    HIP_TRY(hipGetLastError());
+    return MP_OK;
+  }
+  const StateViewPlan p = state_view_plan(e->t, kind, r.count, e->num_cus);
+  if (p.waves < 1)
+    return fail(MP_ERR_UNSUPPORTED, "%s: one wave's record and row of view cells need %d B of LDS beside the "
+                "renderer's tables", kWho, p.lds);
+  if ((uint64_t)p.view_bytes != per)   // (the launch's stride through dst is the one dst_bytes was checked with)
+    return fail(MP_ERR_HIP, "%s: a view of kind %d is %llu bytes to the engine and %u to the kernel", kWho, kind,
+                (unsigned long long)per, p.view_bytes);
+  launch_state_view(e->t, p, kind, bank, r.bank_rows, r.rows, r.players, r.count, r.dst, e->d_layer_lut, e->stream);
+  HIP_TRY(hipGetLastError());
+  return MP_OK;
+}
+
 uint64_t mp_snapshot_bytes(const MpEngine* e) {
   return e ? (uint64_t)e->N * e->t.world_stride : 0;
 }
@@ -2119,6 +2202,10 @@ static_assert(sizeof(MpEpisodeStarts) == 72 && MP_SIZE_DIFFERS(MpEpisodeStarts) 
                   sizeof(MpEpisodeStarts) != sizeof(MpStateLayout) && sizeof(MpEpisodeStarts) != sizeof(MpStatesCheck) &&
                   sizeof(MpEpisodeStarts) != sizeof(MpStatesHash),
               "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
+static_assert(sizeof(MpStatesView) == 80 && MP_SIZE_DIFFERS(MpStatesView) &&
+                  sizeof(MpStatesView) != sizeof(MpStateLayout) && sizeof(MpStatesView) != sizeof(MpStatesCheck) &&
+                  sizeof(MpStatesView) != sizeof(MpStatesHash) && sizeof(MpStatesView) != sizeof(MpEpisodeStarts),
+              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
 #undef MP_SIZE_DIFFERS
 // An MpKernelVariant request (carried by mp_snapshot; `e` may be NULL: the host-only question).
 static int kernel_variant(const MpEngine* e, MpKernelVariant* r) {
@@ -2157,6 +2244,11 @@ int mp_snapshot(MpEngine* e, void* buf, uint64_t bytes) {
     MpStatesObserve r;   // (read only: nothing is written back)
     memcpy(&r, buf, sizeof r);
     return states_observe(e, r);
+  }
+  if (buf && bytes == sizeof(MpStatesView)) {
+    MpStatesView r;   // (read only: nothing is written back)
+    memcpy(&r, buf, sizeof r);
+    return states_view(e, r);
   }
   if (buf && bytes == sizeof(MpStateLayout)) return state_layout(e, (MpStateLayout*)buf);
   if (buf && bytes == sizeof(MpStatesCheck)) {

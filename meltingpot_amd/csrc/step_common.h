@@ -777,6 +777,43 @@ __device__ inline void finish(const DevTables& t, const World& wd, WorldTail* ta
 __device__ inline uint32_t magic_of(uint32_t d) { return d > 1 ? 0xffffffffu / d + 1u : 0u; }
 __device__ inline uint32_t div_by(uint32_t n, uint32_t magic) { return magic ? __umulhi(n, magic) : n; }
 
+// What write_layer works out once per world for its values: the reciprocals of the map's extents
+// and the offsets that make a TORUS coordinate non-negative.
+struct LayerWindow {
+  uint32_t mW, mH;
+  int ox, oy;
+  bool torus;
+  int W, H, HW;
+};
+__device__ inline LayerWindow layer_window(const DevTables& t) {
+  LayerWindow g;
+  g.mW = magic_of((uint32_t)t.W); g.mH = magic_of((uint32_t)t.H);
+  // (TORUS: x + ox >= 0 in every window column, so the wrap is one unsigned remainder)
+  g.ox = t.W * ((t.vl + t.W - 1) / t.W); g.oy = t.H * ((t.vf + t.H - 1) / t.H);
+  g.torus = t.topology == 1;
+  g.W = t.W; g.H = t.H; g.HW = t.H * t.W;
+  return g;
+}
+// "N.LAYER"'s value at window cell (vx, vy), layer l of viewer p: the planes at `rec`, the viewer
+// in `tail`, `lut` = StepOutputs::layer_lut.  Shared by write_layer (every viewer of a world) and
+// state_view.hip (one viewer of a saved row).
+__device__ inline int32_t layer_value(const DevTables& t, const LayerWindow& g, const uint8_t* rec,
+                                      const WorldTail* tail, const int32_t* lut, uint32_t p,
+                                      uint32_t vx, uint32_t vy, uint32_t l) {
+  int x = (int)tail->ax[p] + (int)vx - t.vl, y = (int)tail->ay[p] + (int)vy - t.vf;
+  bool in;
+  if (g.torus) {
+    const uint32_t xx = (uint32_t)(x + g.ox), yy = (uint32_t)(y + g.oy);
+    x = (int)(xx - div_by(xx, g.mW) * (uint32_t)g.W);
+    y = (int)(yy - div_by(yy, g.mH) * (uint32_t)g.H);
+    in = true;
+  } else {
+    in = x >= 0 && x < g.W && y >= 0 && y < g.H;
+  }
+  const int s = in && tail->aalive[p] ? (int)rec[(int)l * g.HW + y * g.W + x] : 256;
+  return lut[p * kLayerLutRow + (uint32_t)s];
+}
+
 // The world's [P][VH][VW][L] int32 block of StepOutputs::layer, from the record this wave has in
 // LDS (`rec`: planes + WorldTail, final) — no HBM read but the 1 KB value table, which stays in the
 // caches.  The block is contiguous and starts on any dword: up to three dwords before its first
@@ -790,29 +827,14 @@ __device__ inline void write_layer(const DevTables& t, const uint8_t* rec, const
   const uint32_t L = (uint32_t)t.L, VW = (uint32_t)(t.vl + t.vr + 1), VH = (uint32_t)(t.vf + t.vb + 1);
   const uint32_t n = (uint32_t)t.P * VH * VW * L;
   const uint32_t mL = magic_of(L), mVW = magic_of(VW), mVH = magic_of(VH);
-  const uint32_t mW = magic_of((uint32_t)t.W), mH = magic_of((uint32_t)t.H);
-  // (TORUS: x + ox >= 0 in every window column, so the wrap is one unsigned remainder)
-  const int ox = t.W * ((t.vl + t.W - 1) / t.W), oy = t.H * ((t.vf + t.H - 1) / t.H);
-  const bool torus = t.topology == 1;
-  const int W = t.W, H = t.H, HW = t.H * t.W;
+  const LayerWindow g = layer_window(t);
   const WorldTail* tail = reinterpret_cast<const WorldTail*>(rec + t.grid_pad);
   const int32_t* lut = out.layer_lut;
   auto value = [&](uint32_t e) -> int32_t {
     const uint32_t cell = div_by(e, mL), l = e - cell * L;
     const uint32_t r = div_by(cell, mVW), vx = cell - r * VW;
     const uint32_t p = div_by(r, mVH), vy = r - p * VH;
-    int x = (int)tail->ax[p] + (int)vx - t.vl, y = (int)tail->ay[p] + (int)vy - t.vf;
-    bool in;
-    if (torus) {
-      const uint32_t xx = (uint32_t)(x + ox), yy = (uint32_t)(y + oy);
-      x = (int)(xx - div_by(xx, mW) * (uint32_t)W);
-      y = (int)(yy - div_by(yy, mH) * (uint32_t)H);
-      in = true;
-    } else {
-      in = x >= 0 && x < W && y >= 0 && y < H;
-    }
-    const int s = in && tail->aalive[p] ? (int)rec[(int)l * HW + y * W + x] : 256;
-    return lut[p * kLayerLutRow + (uint32_t)s];
+    return layer_value(t, g, rec, tail, lut, p, vx, vy, l);
   };
   int32_t* blk = out.layer + (size_t)w * n;
   const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(blk) >> 2) & 3u;

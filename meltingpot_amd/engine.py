@@ -255,6 +255,24 @@ def states_observe_request(L, handle, **fields) -> MpStatesObserve:
   return req
 
 
+# Sampled (row, player) views of bank rows (include/mp_engine.h: MpStatesView), carried by mp_snapshot
+class MpStatesView(ctypes.Structure):
+  _fields_ = [("struct_size", ctypes.c_uint32), ("kind", ctypes.c_int32),
+              ("fingerprint", ctypes.c_uint64), ("bank", ctypes.c_void_p), ("rows", ctypes.c_void_p),
+              ("players", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("dst_bytes", ctypes.c_uint64),
+              ("bank_rows", ctypes.c_int32), ("count", ctypes.c_int32), ("reserved", ctypes.c_uint64 * 2)]
+
+
+def states_view_request(L, handle, **fields) -> MpStatesView:
+  """Runs one MpStatesView request on engine `handle`; raises like every call."""
+  req = MpStatesView(ctypes.sizeof(MpStatesView))
+  for k, v in fields.items():
+    setattr(req, k, v)
+  _check(L, L.mp_snapshot(handle, ctypes.addressof(req), ctypes.sizeof(req)),
+         "mp_snapshot (MpStatesView)")
+  return req
+
+
 # The layout of a record and the check of edited records (include/mp_engine.h: MpStateLayout,
 # MpStatesCheck), carried by mp_snapshot
 class MpStateField(ctypes.Structure):
@@ -1656,6 +1674,55 @@ class Engine:
                            bank_rows=int(bank.shape[0]), rows=None if r is None else r.data_ptr(),
                            count=count, dst=out.data_ptr(), dst_bytes=out.numel() * out.element_size())
     self._state_args = (bank, r, out)   # (kept until the next call: the launch may not have run yet)
+    return out
+
+  def observe_views(self, bank, kind: int, players, rows=None, out=None,
+                    fingerprint: Optional[int] = None):
+    """Observation `kind` of ONE player of each sampled row of `bank` (as observe_states' bank):
+    element i is the view of player players[i] of row rows[i] (None: rows 0 .. count - 1) — the
+    (state, player) samples of a replay minibatch, without the other players' views and without
+    an [R, P, ...] intermediate.  Returns a tensor of shape (count,) + self.shapes[kind][0][2:]
+    (`out`: the tensor to write; a pixel kind's may start on any byte), equal to
+    observe_states(bank, kind, rows)[arange(count), players].  `kind`: a per-player kind of
+    STATE_OBS_KINDS (not OBS_WORLD_RGB).  Rows and (row, player) pairs may repeat.  Nothing of the
+    engine's is written and no device memory of the engine's is allocated.  A row or player index
+    out of range leaves its element as it was; the next synchronising call raises ValueError.
+    `fingerprint`: the rows' (default: this engine's).  Enqueued on the current stream."""
+    t = self._torch
+    S = int(self.info.world_state_bytes)
+    if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
+        bank.shape[1] != S or not bank.is_contiguous()):
+      raise ValueError(f"observe_views: bank must be a contiguous uint8 tensor [M, {S}]")
+    if bank.shape[0] < 1:
+      raise ValueError("observe_views: the bank has no rows")
+    if isinstance(kind, bool) or not isinstance(kind, (int, np.integer)) or int(kind) not in self.shapes:
+      raise ValueError(f"observe_views: {kind!r} is no observation kind")
+    kind = int(kind)
+    if kind == OBS_WORLD_RGB:
+      raise ValueError("observe_views: OBS_WORLD_RGB is not a per-player kind (observe_states draws it)")
+    if players is None:
+      raise ValueError("observe_views: players is required")
+    p = self._device_ints(players, "players")
+    r = None if rows is None else self._device_ints(rows, "rows")
+    count = int(p.numel())
+    if count < 1:
+      raise ValueError("observe_views: no views to draw")
+    if r is not None and int(r.numel()) != count:
+      raise ValueError(f"observe_views: rows has {int(r.numel())} entries, players {count}")
+    shape, dtype = self.shapes[kind]
+    shape = (count,) + tuple(int(d) for d in shape[2:])
+    if out is None:
+      out = t.empty(shape, dtype=dtype, device=self.device)
+    elif (not isinstance(out, t.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or
+          not out.is_contiguous() or out.device != self.device):
+      raise ValueError(f"observe_views: out must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    self.use_current_stream()
+    states_view_request(self._L, self._h, kind=kind, fingerprint=fp, bank=bank.data_ptr(),
+                        bank_rows=int(bank.shape[0]), rows=None if r is None else r.data_ptr(),
+                        players=p.data_ptr(), count=count, dst=out.data_ptr(),
+                        dst_bytes=out.numel() * out.element_size())
+    self._state_args = (bank, r, p, out)   # (kept until the next call: the launch may not have run yet)
     return out
 
   def counters(self) -> Dict[str, int]:

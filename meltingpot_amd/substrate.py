@@ -1170,21 +1170,37 @@ class Substrate:
       leaves[n] = offered[n]
     return leaves
 
-  def observe_states(self, states: WorldStates, observations=None, rows=None) -> Dict[str, Any]:
+  def observe_states(self, states: WorldStates, observations=None, rows=None,
+                     players=None) -> Dict[str, Any]:
     """The observations of saved states (`save_state`, or `step_many(states=True).states`),
     drawn from the rows as they lie: no world of this substrate is loaded or changed, no slot of
     a rollout is written.  `observations`: names among `state_leaves()` (default: those among
     this substrate's own leaves); `rows`: the rows to draw, in order, repeats allowed (default:
     all R of them).  Returns a dict from name to a device tensor [R, ...] ([R, P, ...] for a
     per-player leaf) that holds, for each row, what the leaf held right after the step (or
-    reset) the row was saved behind.  Ordered on the current stream; no host synchronisation."""
+    reset) the row was saved behind.  `players` (R ints, one per drawn row): the sampled
+    (state, player) views of a replay minibatch — every leaf holds player players[i]'s value
+    of row i alone and drops its P axis ("RGB" [R, H, W, 3], "LAYER" [R, VH, VW, L], "POSITION"
+    [R, 2]), equal to the [arange(R), players] elements of the call without `players`; only the
+    sampled views are drawn.  "WORLD.RGB" has no player axis and is left out of the default set
+    then.  Ordered on the current stream; no host synchronisation."""
+    if players is not None and observations is not None:
+      named = (observations,) if isinstance(observations, str) else tuple(observations)
+      if "WORLD.RGB" in named:
+        raise ValueError("observe_states: \"WORLD.RGB\" is one image per world, not per player: it cannot be "
+                         "drawn with players=; draw it in a call of its own")
     leaves = self._state_leaves(observations)
     if not isinstance(states, WorldStates):
       raise ValueError("observe_states takes the WorldStates of save_state or step_many(states=True)")
     states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
     self._eng.use_current_stream()
-    return {n: self._eng.observe_states(states.data, k, rows=rows, fingerprint=states.fingerprint)
-            for n, k in leaves.items()}
+    if players is None:
+      return {n: self._eng.observe_states(states.data, k, rows=rows, fingerprint=states.fingerprint)
+              for n, k in leaves.items()}
+    p = self._eng._device_ints(players, "players")
+    r = None if rows is None else self._eng._device_ints(rows, "rows")
+    return {n: self._eng.observe_views(states.data, k, p, rows=r, fingerprint=states.fingerprint)
+            for n, k in leaves.items() if n != "WORLD.RGB"}
 
   # dmlab2d properties (wrappers/base.py:64-84): Melting Pot's levels register none —
   # the calls exist and answer like dmlab2d does for an unknown key
