@@ -1003,6 +1003,62 @@ typedef struct {
   uint64_t reserved2[3];   /* 0 */
 } MpEpisodeStarts;
 
+/* Stepping some of the worlds: an MpStepTrajectory request under a device mask that says, per step
+ * and per world, whether the world runs — rollouts of different depths, a tree search that expands
+ * only the leaves picked this round, worlds that stop after their first episode while the engine
+ * keeps auto_reset = 1.  Rides mp_restore, recognised by its size: `bytes` = sizeof(MpStepActive),
+ * `host_buf` a HOST MpStepActive with struct_size set to it.  include/mp_step_active.h wraps it as
+ * inline C functions.  Every other request and entry point keeps doing exactly what it does.
+ *
+ * `active` is device memory, uint8 [K][N]; any non-zero byte means "active".  active_step_bytes is
+ * the distance between two steps' rows: 0 means the same [N] row is read at every step, otherwise
+ * it is >= N; larger distances let several engines read their own columns of one [K][N total]
+ * tensor, as actions_step_bytes does.  steps = 1 is the masked single step; num_rows = 0 is
+ * allowed; the five kinds of MpStepMany are named as rows of their MpObsKind.
+ *
+ * In step k:
+ *   an active world (active[k][w] != 0) does exactly what it does in an MpStepTrajectory request:
+ *     step, auto-reset, registered episode start (rows[w] read at that moment), frozen step, or
+ *     nothing for a world never reset.  The action of an auto-reset step is ignored as ever.
+ *   a skipped world is not touched: no byte of its record (the cached visiting orders, ctr[],
+ *     reward_fx and done included), none of its elements of any in-place or bound non-pixel
+ *     output, none of its event rows.  It adds nothing to mp_counters.  A world paused on LAST
+ *     stays on LAST and takes its reset, or its registered start, in the first later step in which
+ *     it is active.
+ * The defining identity: a K-step request with a mask leaves every record, counter, in-place or
+ * bound output, event row and per-step row exactly as the loop of K one-step requests with the
+ * rows active[0] .. active[K - 1] leaves them.
+ * Per-step rows (every kind of MpStepTrajectory, MP_STEP_ROW_STATE and MP_STEP_ROW_HASH) follow
+ * the carry rule above: row k of a skipped step equals row k - 1, and row 0 equals the buffer as
+ * it was before the request.  The rewards of a skipped step therefore REPEAT: a caller that sums
+ * them multiplies by the mask.  A state row or hash row of a skipped step holds the unchanged
+ * record or its hash.
+ * Bound pixel views are drawn once after the request by the draw-only launches, for all worlds: a
+ * skipped world's pixels are redrawn from its unchanged record and hold the same bytes.  The call
+ * is therefore the step kernels plus one draw per view, whatever MpInfo.fused says, and it does
+ * not change MpInfo.fused: the mask is per call, not a registration, and the engine's next
+ * unmasked step is the launch it was.
+ *
+ * Refused before any launch, the engine left as it was.  MP_ERR_INVALID: everything
+ * MpStepTrajectory refuses, with this request's name; NULL active; an active_step_bytes that is
+ * neither 0 nor >= N; an `active` that is not device memory of the engine's device or whose extent
+ * [active, active + (steps - 1) * active_step_bytes + N) does not lie inside one allocation;
+ * non-zero reserved words.  MP_ERR_UNSUPPORTED: a rollout ring is bound (mp_bind_output_ring: a
+ * slot row of a skipped world has no defined content); an engine created with MpConfig.unfused = 2
+ * that has a pixel view bound (it promised one launch a step). */
+typedef struct {
+  uint32_t struct_size;        /* = sizeof(MpStepActive) */
+  int32_t steps;               /* K */
+  int32_t fields;              /* 0: discrete ids [K][N][P]; 1: raw fields [K][N][P][A] */
+  int32_t num_rows;
+  const int32_t* actions;      /* device */
+  uint64_t actions_step_bytes; /* 0: the same block every step */
+  const MpStepRow* rows;       /* HOST array [num_rows] */
+  const uint8_t* active;       /* device uint8 [K][N]: non-zero = world w runs step k */
+  uint64_t active_step_bytes;  /* 0: the same row every step; otherwise >= N */
+  uint64_t reserved[5];        /* 0 */
+} MpStepActive;
+
 /* Throughput / event counters accumulated on device since creation
  * (synchronises).  These are what the multi-GPU bench all-reduces. */
 enum {

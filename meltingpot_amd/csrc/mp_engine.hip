@@ -464,7 +464,8 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
     if (many) {
       StepManyLaunch l = *many;
       l.starts = starts;
-      launch_step_many(e->t, e->sub, args, l, e->stream);
+      if (l.active.active) launch_step_active(e->t, e->sub, args, l, e->stream);   // (MpStepActive)
+      else launch_step_many(e->t, e->sub, args, l, e->stream);
     } else if (starts) {
       launch_step_starts(e->t, e->sub, args, *starts, e->stream);
     } else {
@@ -1025,6 +1026,8 @@ int plan_views(MpEngine* e, const MpDevOptions* dev) {
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the sampled-view kernels failed: %d", rc);
   if (int rc = prepare_step_starts())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the episode-start kernels failed: %d", rc);
+  if (int rc = prepare_step_active())
+    return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the masked K-step kernels failed: %d", rc);
   if (dev && dev->verbose)
     for (int v = 0; v < 6; ++v) {
       const FramePlan& pl = e->plan[v & 1][v >> 1];
@@ -1615,10 +1618,12 @@ static int world_states(MpEngine* e, MpWorldStates* r, bool restore) {
   }
 }
 
-// A K-step request (include/mp_engine.h: MpStepMany, MpStepTrajectory), whichever struct it came
-// in: `r` names the rows it wants, `who` is the request's own name in the messages.  Everything is
-// checked here, against kStepRowKinds (step_many.h) and mp_obs_bytes, before the one submission.
-static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r) {
+// A K-step request (include/mp_engine.h: MpStepMany, MpStepTrajectory, MpStepActive), whichever
+// struct it came in: `r` names the rows it wants, `who` is the request's own name in the messages,
+// `mask` (MpStepActive only) the device mask and the distance between two of its rows.  Everything
+// is checked here, against kStepRowKinds (step_many.h) and mp_obs_bytes, before the one submission.
+static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r,
+                        const ActiveArgs* mask = nullptr) {
   if (!e || !r.actions) return fail(MP_ERR_INVALID, "%s: NULL engine or actions", who);
   if (r.steps < 1 || r.steps > MP_STEP_MANY_MAX)
     return fail(MP_ERR_INVALID, "%s: steps %d is outside [1, %d]", who, r.steps, MP_STEP_MANY_MAX);
@@ -1644,6 +1649,22 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r)
   snprintf(name, sizeof name, "%s (actions)", who);
   if (int rc = check_bank(e, r.actions, (K - 1) * r.actions_step_bytes + ablock, name)) return rc;
   StepManyLaunch l = {};
+  if (mask) {
+    if (!mask->active) return fail(MP_ERR_INVALID, "%s: NULL active", who);
+    if (mask->step != 0 && (uint64_t)mask->step < N)
+      return fail(MP_ERR_INVALID, "%s: active_step_bytes %llu is neither 0 nor at least one step's row of %llu "
+                  "bytes", who, (unsigned long long)mask->step, (unsigned long long)N);
+    snprintf(name, sizeof name, "%s (active)", who);
+    if (int rc = check_bank(e, mask->active, (K - 1) * (uint64_t)mask->step + N, name)) return rc;
+    // (a slot row of a skipped world has no defined content)
+    if (e->ring_slots > 0)
+      return fail(MP_ERR_UNSUPPORTED, "%s: a rollout ring is bound (mp_bind_output_ring); a masked step "
+                  "writes no ring slot — unbind the ring first", who);
+    if (e->unfused == 2 && (e->agent_view() || e->bound[MP_OBS_WORLD_RGB]))
+      return fail(MP_ERR_UNSUPPORTED, "%s: the engine was created with MpConfig.unfused = 2 (one launch a "
+                  "step) and has a pixel view bound; a masked step is the step kernels and a draw per view", who);
+    l.active = *mask;
+  }
   l.many.steps = r.steps;
   l.many.actions_step = (long long)(r.actions_step_bytes / 4);
   l.rows.layer_lut = e->d_layer_lut;
@@ -1727,6 +1748,20 @@ static int trajectory_request(MpEngine* e, const MpStepTrajectory& r) {
   if (r.struct_size != sizeof(MpStepTrajectory))
     return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpStepTrajectory));
   return step_request(e, kWho, r);
+}
+
+// ... and when it is sizeof(MpStepActive): the same request under a device mask.
+static int active_request(MpEngine* e, const MpStepActive& r) {
+  static const char kWho[] = "MpStepActive";
+  if (r.struct_size != sizeof(MpStepActive))
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpStepActive));
+  for (uint64_t word : r.reserved)
+    if (word != 0) return fail(MP_ERR_INVALID, "%s: the reserved words must be 0", kWho);
+  if (r.active_step_bytes > (1ull << 40))
+    return fail(MP_ERR_INVALID, "%s: active_step_bytes %llu", kWho, (unsigned long long)r.active_step_bytes);
+  const MpStepTrajectory t = {sizeof t, r.steps, r.fields, r.num_rows, r.actions, r.actions_step_bytes, r.rows};
+  const ActiveArgs mask = {r.active, (long long)r.active_step_bytes};
+  return step_request(e, kWho, t, &mask);
 }
 
 // An MpStatesObserve request (include/mp_engine.h; carried by mp_snapshot): observations of rows
@@ -2206,6 +2241,11 @@ static_assert(sizeof(MpStatesView) == 80 && MP_SIZE_DIFFERS(MpStatesView) &&
                   sizeof(MpStatesView) != sizeof(MpStateLayout) && sizeof(MpStatesView) != sizeof(MpStatesCheck) &&
                   sizeof(MpStatesView) != sizeof(MpStatesHash) && sizeof(MpStatesView) != sizeof(MpEpisodeStarts),
               "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
+static_assert(sizeof(MpStepActive) == 96 && MP_SIZE_DIFFERS(MpStepActive) &&
+                  sizeof(MpStepActive) != sizeof(MpStateLayout) && sizeof(MpStepActive) != sizeof(MpStatesCheck) &&
+                  sizeof(MpStepActive) != sizeof(MpStatesHash) && sizeof(MpStepActive) != sizeof(MpEpisodeStarts) &&
+                  sizeof(MpStepActive) != sizeof(MpStatesView) && sizeof(MpStepActive) < 448,
+              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
 #undef MP_SIZE_DIFFERS
 // An MpKernelVariant request (carried by mp_snapshot; `e` may be NULL: the host-only question).
 static int kernel_variant(const MpEngine* e, MpKernelVariant* r) {
@@ -2289,6 +2329,11 @@ int mp_restore(MpEngine* e, const void* buf, uint64_t bytes) {
     MpEpisodeStarts r;   // (read only: nothing is written back)
     memcpy(&r, buf, sizeof r);
     return episode_starts(e, r);
+  }
+  if (buf && bytes == sizeof(MpStepActive)) {
+    MpStepActive r;   // (read only: nothing is written back)
+    memcpy(&r, buf, sizeof r);
+    return active_request(e, r);
   }
   if (!e || !buf || bytes != mp_snapshot_bytes(e))
     return fail(MP_ERR_INVALID, "mp_restore: bad buffer");

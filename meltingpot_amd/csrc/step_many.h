@@ -130,9 +130,18 @@ struct HashRows {
   const uint32_t* mask;
 };
 
+// The mask of an MpStepActive request (step_active.hip): world w runs step k where
+// active[k * step + w] != 0 (`step`: the distance between two steps' rows in bytes, 0: the same
+// row every step).  active == NULL: no mask, which is every other K-step request.
+struct ActiveArgs {
+  const uint8_t* active;
+  long long step;
+};
+
 // One checked K-step request, as submit() hands it to launch_step_many: the five kinds' rows,
 // the rows of the other kinds, whether there is one of those (any_rows == false runs the
-// kernels an MpStepMany request has always run), the state rows and the hash rows.
+// kernels an MpStepMany request has always run), the state rows and the hash rows — and the mask
+// of an MpStepActive request, with which submit() hands it to launch_step_active instead.
 struct StepManyLaunch {
   ManyArgs many;
   StepRows rows;
@@ -140,10 +149,15 @@ struct StepManyLaunch {
   StateRows state;
   HashRows hash;
   const stepk::StartArgs* starts;   // the engine's registered episode starts (submit() sets it), or NULL
+  ActiveArgs active;
 };
 
 void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
                       const StepManyLaunch& l, hipStream_t stream);
 int prepare_step_many();
+// (step_active.hip)
+void launch_step_active(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
+                        const StepManyLaunch& l, hipStream_t stream);
+int prepare_step_active();
 
 #endif  // MP_STEP_MANY_H_INTERNAL_

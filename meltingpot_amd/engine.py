@@ -664,6 +664,46 @@ def check_step_many(shape, dtype, num_worlds: int, num_players: int, *, repeat=N
   return K
 
 
+# ... under a device mask that says, per step and per world, whether the world runs (MpStepActive)
+class MpStepActive(ctypes.Structure):
+  _fields_ = [("struct_size", ctypes.c_uint32), ("steps", ctypes.c_int32),
+              ("fields", ctypes.c_int32), ("num_rows", ctypes.c_int32),
+              ("actions", ctypes.c_void_p), ("actions_step_bytes", ctypes.c_uint64),
+              ("rows", ctypes.POINTER(MpStepRow)), ("active", ctypes.c_void_p),
+              ("active_step_bytes", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 5)]
+
+
+def check_step_active(active, steps: int, num_worlds: int):
+  """The dtype and shape rules of the active= mask of Engine.step / Engine.step_many, without an
+  engine: bytes (uint8) or booleans of shape [K, N] with K = `steps`, or [N] (the same row at
+  every step).  A torch tensor is taken as it is and may be a column slice [:, a:b] of a wider
+  one (each row contiguous, rows at least N apart); a numpy array must be uint8 or bool; a
+  nested list may hold booleans or integers.  Returns (mask, step_bytes): the tensor itself, or
+  a contiguous numpy uint8 array for host data, and the distance between two steps' rows in
+  bytes (0: one row for every step).  ValueError otherwise."""
+  K, N = int(steps), int(num_worlds)
+  def bad(got):
+    return ValueError(f"active= must be a uint8 or bool mask of shape ({K}, {N}) or ({N},) (got {got})")
+  if hasattr(active, "data_ptr"):   # a torch tensor
+    name, shape = str(active.dtype), tuple(int(d) for d in active.shape)
+    if name not in ("torch.uint8", "torch.bool") or shape not in ((K, N), (N,)):
+      raise bad(f"{name} {shape}")
+    if N > 1 and int(active.stride(-1)) != 1:
+      raise ValueError(f"active=: a step's row must be contiguous (strides {tuple(active.stride())})")
+    if len(shape) == 1:
+      return active, 0
+    if K > 1 and int(active.stride(0)) < N:
+      raise ValueError(f"active=: the steps' rows overlap (stride {int(active.stride(0))} < {N})")
+    return active, (int(active.stride(0)) if K > 1 else N)
+  listed = not isinstance(active, np.ndarray)
+  a = np.asarray(active)
+  ok = a.dtype in (np.uint8, np.bool_) or (listed and a.dtype.kind in "iu")
+  if not ok or a.shape not in ((K, N), (N,)):
+    raise bad(f"{a.dtype} {a.shape}")
+  a = np.ascontiguousarray(a != 0, np.uint8)
+  return a, (0 if a.ndim == 1 else N)
+
+
 # Registered episode starts (include/mp_engine.h: MpEpisodeStarts), carried by mp_restore
 class MpEpisodeStarts(ctypes.Structure):
   _fields_ = [("struct_size", ctypes.c_uint32), ("fresh", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
@@ -1282,9 +1322,17 @@ class Engine:
       mp = mask.ctypes.data
     _check(self._L, self._L.mp_reset(self._h, sp, mp), "mp_reset")
 
-  def step(self, actions):
-    """actions: int32 cuda tensor [N, P] of discrete action ids."""
+  def step(self, actions, active=None):
+    """actions: int32 cuda tensor [N, P] of discrete action ids.
+    active: a mask [N] (see step_many): only the worlds it selects step, the others are not
+    touched.  It is the K = 1 masked request of step_many."""
     t = self._torch
+    if active is not None:
+      a = actions if isinstance(actions, t.Tensor) else np.asarray(actions)
+      if tuple(a.shape) != (self.N, self.P):
+        raise ValueError(f"actions must have shape {(self.N, self.P)}")
+      self.step_many(a[None], keep=(), active=active)
+      return
     if isinstance(actions, t.Tensor) and actions.is_cuda:
       assert actions.dtype == t.int32 and actions.is_contiguous()
       assert tuple(actions.shape) == (self.N, self.P)
@@ -1315,7 +1363,7 @@ class Engine:
 
   def step_many(self, actions, *, repeat: Optional[int] = None, fields: bool = False,
                 keep=("reward", "collective_reward", "step_type", "discount"), events: bool = False,
-                observations=(), out=None, states=False, hashes=False):
+                observations=(), out=None, states=False, hashes=False, active=None):
     """K steps of every world in ONE launch, bit-identical to K calls of step() (fields=True:
     step_fields()) with actions[0] .. actions[K - 1]; returns the per-step transitions.
 
@@ -1342,6 +1390,14 @@ class Engine:
     hashes: True (or a tensor under out["hashes"]) adds "hashes", int64 [K, N]: row k of a started
     world is hash_worlds() after step k of the loop — the hash (default spec) of what the state
     row's row k holds, at 8 bytes a world-step (a world never reset writes nothing).
+    active: a mask of the world-steps to run, uint8 or bool [K, N], or [N] (the same row at every
+    step); a device tensor is read in place and may be a column slice [:, a:b], a host array or
+    a nested list is uploaded once.  World w runs step k only where active[k, w] is non-zero;
+    elsewhere it is not touched (its record, counters, in-place outputs and events stay what they
+    were), and row k of everything stacked per step repeats row k - 1 (row 0: the buffer as it was
+    before the call) — so rewards of skipped steps REPEAT: sum them under the mask.  The result
+    equals the loop of step(actions[k], active=active[k]).  Refused with a rollout ring bound.
+    None: exactly the request issued without it.
     Enqueued on the current stream; does not synchronise."""
     t = self._torch
     A = int(self.info.num_action_fields) if fields else None
@@ -1358,6 +1414,13 @@ class Engine:
     astep = 0 if repeat is not None else _step_distance(actions, "actions")
     if repeat is not None and not actions.is_contiguous():
       raise ValueError("step_many: the repeated block of actions must be contiguous")
+    mask = None
+    if active is not None:
+      mask, mask_step = check_step_active(active, K, self.N)
+      if isinstance(mask, np.ndarray):
+        mask = t.from_numpy(mask).to(self.device)
+      elif mask.device != self.device:
+        raise ValueError(f"step_many: active= lives on {mask.device}, the engine on {self.device}")
     names = [k for k in STEP_MANY_KINDS if k in tuple(keep) or (k == "events" and events)]
     unknown = [k for k in keep if k not in STEP_MANY_KINDS[:4]]
     if unknown:
@@ -1387,13 +1450,18 @@ class Engine:
       rows[i].step_bytes = _step_distance(buf, f"out[{key!r}]")
       result[key] = buf
     self.use_current_stream()
-    req = MpStepTrajectory(ctypes.sizeof(MpStepTrajectory), K, 1 if fields else 0, len(rows))
+    if active is not None:
+      req = MpStepActive(ctypes.sizeof(MpStepActive), K, 1 if fields else 0, len(rows))
+      req.active = mask.data_ptr()
+      req.active_step_bytes = mask_step
+    else:
+      req = MpStepTrajectory(ctypes.sizeof(MpStepTrajectory), K, 1 if fields else 0, len(rows))
     req.actions = actions.data_ptr()
     req.actions_step_bytes = astep
     req.rows = rows
     _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
-           "mp_restore (MpStepTrajectory)")
-    self._state_args = (actions, result)   # (kept until the next call: the launch may not have run yet)
+           f"mp_restore ({type(req).__name__})")
+    self._state_args = (actions, result, mask)   # (kept until the next call: the launch may not have run yet)
     return result
 
   def observe(self, kind: int, out=None):

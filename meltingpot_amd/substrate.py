@@ -146,6 +146,29 @@ def _hash_fields(fields):
   return tuple(c_names.get(f, f) for f in fields)
 
 
+def _step_mask(t, active, lengths, K: int, N: int, device, ring: bool):
+  """The mask of a masked step / step_many call as a device tensor the engines read in place
+  ([K, N] or [N], uint8 or bool), or None for an unmasked call.  `lengths`: int [N], world w runs
+  steps 0 .. lengths[w] - 1 — arange(K)[:, None] < lengths[None], built on the device without a
+  synchronisation.  `ring`: the substrate was built with rollout_length=T."""
+  if active is None and lengths is None:
+    return None
+  if active is not None and lengths is not None:
+    raise ValueError("give either active= or lengths=, not both")
+  if ring:
+    raise ValueError("a masked step cannot write a rollout ring (rollout_length=T): a slot row of a skipped "
+                     "world has no defined content; build the substrate without rollout_length")
+  if lengths is not None:
+    n = lengths if isinstance(lengths, t.Tensor) else t.as_tensor(np.asarray(lengths))
+    if n.dtype.is_floating_point or n.dtype == t.bool or tuple(n.shape) != (N,):
+      raise ValueError(f"lengths= must be an int tensor of shape ({N},) (got {n.dtype} {tuple(n.shape)})")
+    return t.arange(K, device=device)[:, None] < n.to(device)[None]
+  mask, _ = engine_lib.check_step_active(active, K, N)
+  if isinstance(mask, np.ndarray):
+    mask = t.from_numpy(mask).to(device)
+  return mask
+
+
 def _many_actions(t, actions, repeat, N: int, P: int, num_actions: Optional[int]):
   """`actions` of a step_many call as the engine takes them: an int32 device tensor (as it is:
   it may be a column slice) or a host array; shape-checked, range-checked when asked."""
@@ -1215,10 +1238,16 @@ class Substrate:
   def write_property(self, key: str, value):
     raise KeyError(key)
 
-  def step(self, action) -> TimeStep:
+  def step(self, action, active=None) -> TimeStep:
     """Substrate.step (substrate.py:74-81).  `action`: P ints (unbatched), or
-    an int tensor / array [N, P] (batched)."""
+    an int tensor / array [N, P] (batched).
+    `active` (batched substrates): a uint8 or bool mask [N]; only the worlds it selects step.
+    The others are not touched, and their elements of the returned TimeStep's leaves are what
+    they were."""
     t = self._eng._torch
+    if active is not None and not self._batched:
+      raise ValueError("active= selects worlds of a batch: build the substrate with num_worlds > 1")
+    mask = _step_mask(t, active, None, 1, self._eng.N, self._eng.device, self._T > 0)
     if self._batched:
       if isinstance(action, t.Tensor) and action.is_cuda:
         a = action.to(t.int32).contiguous()
@@ -1236,13 +1265,16 @@ class Substrate:
       a = a.reshape(1, self._eng.P)
     self._observables.action.on_next(action)
     self._eng.use_current_stream()
-    self._submit(a)
+    self._submit(a, mask)
     return self._emit(self._timestep())
 
-  def _submit(self, a):
+  def _submit(self, a, active=None):
     """One step of the engine on actions `a` as `step` prepared them (an int32 device tensor
-    or a host array [N, P])."""
+    or a host array [N, P]); `active`: the device mask [N] of a masked step."""
     t = self._eng._torch
+    if active is not None:
+      self._submit_many(a[None], None, False, None, active=active, keep=())
+      return
     if self._action_rows is None:
       self._eng.step(a)
     else:
@@ -1289,7 +1321,8 @@ class Substrate:
     return leaves
 
   def step_many(self, actions, repeat: Optional[int] = None, events: bool = False,
-                observations=(), states: bool = False, hashes: bool = False) -> StepManyResult:
+                observations=(), states: bool = False, hashes: bool = False,
+                active=None, lengths=None) -> StepManyResult:
     """K steps in ONE launch, bit-identical to K calls of `step` (batched substrates).
     `actions`: ints [K, N, P] (a device tensor is read in place; it may be a column slice
     [:, a:b] of a wider one), or one block [N, P] with `repeat=K`.  Returns the per-step
@@ -1312,7 +1345,13 @@ class Substrate:
     hash (`hash_worlds`, the default part) of every world after every step — what `hash_states`
     gives of `.states`' rows, at 8 bytes a world-step instead of a record.  Stored at collection
     time it proves that a regenerated rollout is the original.  Hashes compare only within one
-    fingerprint."""
+    fingerprint.
+    `active`: a uint8 or bool mask [K, N] (or [N], the same row at every step; a device tensor is
+    read in place): world w runs step k only where it is non-zero and is not touched elsewhere.
+    Row k of every per-step tensor then repeats row k - 1 (row 0: the leaf as it was), so the
+    rewards of skipped steps repeat: sum them under the mask.  `lengths`: an int tensor [N]
+    instead — world w runs steps 0 .. lengths[w] - 1 (rollouts of different depths).  Not with
+    `rollout_length=T`."""
     if not self._batched:
       raise ValueError("step_many steps a batch of worlds: build the substrate with num_worlds > 1")
     leaves = self._many_leaves(observations)
@@ -1320,19 +1359,24 @@ class Substrate:
     limit = None
     if self._check_device_actions:
       limit = len(self._action_rows) if self._action_rows is not None else self._eng.num_actions
-    a, _ = _many_actions(t, actions, repeat, self._eng.N, self._eng.P, limit)
+    a, K = _many_actions(t, actions, repeat, self._eng.N, self._eng.P, limit)
+    mask = _step_mask(t, active, lengths, K, self._eng.N, self._eng.device, self._T > 0)
     self._observables.action.on_next(actions)
     self._eng.use_current_stream()
-    r = self._submit_many(a, repeat, events, None, leaves, bool(states), bool(hashes))
+    r = self._submit_many(a, repeat, events, None, leaves, bool(states), bool(hashes), active=mask)
     return _many_result(r, leaves, self._emit(self._timestep()),
                         self._eng.state_fingerprint if states else None)
 
-  def _submit_many(self, a, repeat, events, out, leaves=None, states=False, hashes=False):
+  def _submit_many(self, a, repeat, events, out, leaves=None, states=False, hashes=False, active=None,
+                   **more):
     """One K-step launch of the engine on actions `a` as `_many_actions` prepared them
     (`leaves`: name -> kind of the observations to stack per step; `states`: the records too;
-    `hashes`: their hashes)."""
+    `hashes`: their hashes; `active`: the device mask of a masked call)."""
     t = self._eng._torch
-    more = {"states": True} if states else {}
+    if states:
+      more["states"] = True
+    if active is not None:
+      more["active"] = active
     if hashes:
       more["hashes"] = True
     if leaves:
@@ -1903,10 +1947,13 @@ class MixtureSubstrate:
   def observation(self):
     return self._timestep().observation
 
-  def step(self, action) -> TimeStep:
+  def step(self, action, active=None) -> TimeStep:
     """`action`: int [N, P], a device tensor (member i gets rows [off_i, off_i + n_i), a view)
-    or a host array."""
+    or a host array.  `active`: a mask [N] as `Substrate.step` takes it; member i reads its
+    elements [off_i, off_i + n_i) of it in place."""
     t = self._members[0]._eng._torch
+    mask = _step_mask(t, active, None, 1, self._N, self._members[0]._eng.device,
+                      any(m._T > 0 for m in self._members))
     if isinstance(action, t.Tensor) and action.is_cuda:
       a = action.to(t.int32).contiguous()
       if tuple(a.shape) != (self._N, self._P):
@@ -1922,7 +1969,7 @@ class MixtureSubstrate:
     self._observables.action.on_next(action)
     for m, off, n in zip(self._members, self._offsets, self._counts):
       m._eng.use_current_stream()
-      m._submit(a[off:off + n])
+      m._submit(a[off:off + n], None if mask is None else mask[..., off:off + n])
     self._submissions += 1
     return self._emit(self._timestep())
 
@@ -1974,14 +2021,17 @@ class MixtureSubstrate:
     return out
 
   def step_many(self, actions, repeat: Optional[int] = None, events: bool = False,
-                observations=(), states: bool = False, hashes: bool = False) -> StepManyResult:
+                observations=(), states: bool = False, hashes: bool = False,
+                active=None, lengths=None) -> StepManyResult:
     """As `Substrate.step_many`, over the members: one K-step launch per member, each reading
     its columns [:, off_i:off_i + n_i] of `actions` and writing its columns of the shared
     [K, N, ...] per-step tensors, those of `observations` included (nothing is copied or
     concatenated).  There is no `states=True` here: the members' records differ in size.
     `hashes=True` is there: a hash is 8 bytes for every member, so `.hashes` is one int64
     [K, N] tensor whose columns the members write — a per-step state identity of every world
-    (comparable within one member only: the members' fingerprints differ)."""
+    (comparable within one member only: the members' fingerprints differ).
+    `active` / `lengths`: as `Substrate.step_many` takes them, over all N worlds; every member
+    reads its columns of the one mask in place."""
     if states:
       raise ValueError("step_many: a mixture has no per-step states (states=True): its members' records "
                        "differ in size and fingerprint; step the members' substrates on their own")
@@ -1991,6 +2041,7 @@ class MixtureSubstrate:
     limit = self.action_spec()[0].num_values if self._check_device_actions else None
     a, K = _many_actions(t, actions, repeat, self._N, self._P, limit)
     dev = first._eng.device
+    mask = _step_mask(t, active, lengths, K, self._N, dev, any(m._T > 0 for m in self._members))
     keys = list(engine_lib.STEP_MANY_KINDS[:5 if events else 4])
     keys += [kind for kind in leaves.values() if kind not in _FIVE_NAMES]
     out = {}
@@ -2005,7 +2056,8 @@ class MixtureSubstrate:
       cols = a[off:off + n] if repeat is not None else a[:, off:off + n]
       if repeat is not None and isinstance(cols, t.Tensor):
         cols = cols.contiguous()
-      m._submit_many(cols, repeat, events, {k: v[:, off:off + n] for k, v in out.items()}, leaves)
+      m._submit_many(cols, repeat, events, {k: v[:, off:off + n] for k, v in out.items()}, leaves,
+                     active=None if mask is None else mask[..., off:off + n])
     self._submissions += 1
     return _many_result(out, leaves, self._emit(self._timestep()))
 
