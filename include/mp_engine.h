@@ -1059,6 +1059,78 @@ typedef struct {
   uint64_t reserved[5];        /* 0 */
 } MpStepActive;
 
+/* Stopping worlds inside a K-step request: an MpStepActive request in which a world that ends its
+ * episode, or is paid, stops THERE for the rest of the request — returns that end with the
+ * episode, "repeat this action until something happens", closed-loop evaluation without a host
+ * synchronisation per step.  Rides mp_restore, recognised by its size: `bytes` =
+ * sizeof(MpStepUntil), `host_buf` a HOST MpStepUntil with struct_size set to it.
+ * include/mp_step_until.h wraps it as inline C functions.  Every other request and entry point
+ * keeps doing exactly what it does; an MpStepActive request runs the kernels it ran.
+ *
+ * The ten leading fields are MpStepActive's, at its offsets, with one difference: `active` may be
+ * NULL, which is a mask of all ones (active_step_bytes is then ignored and must be 0).
+ *
+ * The defining identity: the request equals the loop over k of the one-step MpStepActive request
+ * with the mask
+ *     m_k[w] = active[k][w] != 0 && stopped[w] == 0
+ * where, after each such step, for the worlds that ran it,
+ *     reason = (MP_STOP_LAST   if STEP_TYPE[w] == 2 after the step and `stop` has the bit)
+ *            | (MP_STOP_REWARD if REWARD[w][p] != 0 for some player p after the step, likewise)
+ *     if (reason) stopped[w] = reason
+ * Everything MpStepActive says of a skipped world-step holds for the steps a stopped world skips:
+ * it is not touched, its rows repeat by the carry rule, it stands on the step that stopped it, and
+ * a world stopped on LAST takes its reset, or its registered episode start, in the first active
+ * step of a later request in which its `stopped` byte is 0.  A world frozen on LAST
+ * (MpConfig.auto_reset = 0) that runs a step is left on LAST with reward 0, so with MP_STOP_LAST it
+ * stops again after one step.  A world never reset runs nothing and never stops.
+ *
+ *   stopped  device uint8 [N], read and written, or NULL.  On entry any non-zero byte means "this
+ *            world does not run in this request"; that byte is left as it is.  A world that stops
+ *            gets its reason bits.  One tensor handed to request after request makes a condition
+ *            persistent: chunks of a long plan, K = 1 closed loops, action repeat.  NULL: every
+ *            world starts unstopped and the reasons are not kept.
+ *   ran      device int32 [N], written, or NULL: the number of steps world w ran in this request.
+ *   returns  device float64 [N][P], written, or NULL: the discounted sum of REWARD over the steps
+ *            that ran, in step order — g = 1; for each step that ran: ret = ret + g * r;
+ *            g = g * gamma — every multiply and every add rounded to float64 on its own (no fused
+ *            multiply-add), so it equals that loop in IEEE arithmetic bit for bit.  It is this
+ *            request's sum: a caller that chunks a plan adds the chunks' sums itself.
+ * stop = 0 with ran / returns is MpStepActive plus the count and the sum under the mask.
+ * Bound pixel views are drawn once after the request for all worlds, and MpInfo.fused stays what
+ * it was, as for MpStepActive.
+ *
+ * Refused before any launch, the engine left as it was.  MP_ERR_INVALID: everything MpStepActive
+ * refuses (but a NULL active), with this request's name; stop outside the two bits; non-zero pad
+ * or reserved words; a gamma that is not finite; a NULL active with a non-zero active_step_bytes;
+ * stopped, ran or returns that is not device memory of the engine's device or whose extent (N, 4 N
+ * and 8 N P bytes) does not lie inside one allocation; a ran that is not 4-byte or a returns that
+ * is not 8-byte aligned; stopped, ran or returns overlapping each other, the actions, the mask or a
+ * row buffer of the request (they are written while other worlds' waves still read and write
+ * those).  MP_ERR_UNSUPPORTED: a rollout ring is bound; an engine created with
+ * MpConfig.unfused = 2 that has a pixel view bound. */
+enum {
+  MP_STOP_LAST = 1,     /* the step left STEP_TYPE == 2 */
+  MP_STOP_REWARD = 2,   /* the step left a non-zero REWARD for some player */
+};
+typedef struct {
+  uint32_t struct_size;        /* = sizeof(MpStepUntil) */
+  int32_t steps;               /* K */
+  int32_t fields;              /* 0: discrete ids [K][N][P]; 1: raw fields [K][N][P][A] */
+  int32_t num_rows;
+  const int32_t* actions;      /* device */
+  uint64_t actions_step_bytes; /* 0: the same block every step */
+  const MpStepRow* rows;       /* HOST array [num_rows] */
+  const uint8_t* active;       /* device uint8 [K][N], or NULL: all ones */
+  uint64_t active_step_bytes;  /* 0: the same row every step; otherwise >= N */
+  uint32_t stop;               /* MP_STOP_* bits; 0: nothing stops a world */
+  uint32_t pad;                /* 0 */
+  uint8_t* stopped;            /* device uint8 [N], read and written, or NULL */
+  int32_t* ran;                /* device int32 [N], written, or NULL */
+  double* returns;             /* device float64 [N][P], written, or NULL */
+  double gamma;                /* finite; 1.0: the plain sum */
+  uint64_t reserved[5];        /* 0 */
+} MpStepUntil;
+
 /* Throughput / event counters accumulated on device since creation
  * (synchronises).  These are what the multi-GPU bench all-reduces. */
 enum {

@@ -5,6 +5,7 @@
 // wrappers/base.py:38-84).  No CPU execution path exists here: every call that
 // would compute needs a HIP device and fails loudly without one.
 #include <chrono>
+#include <cmath>
 #include <map>
 #include <mutex>
 #include "../../include/mp_engine.h"
@@ -23,6 +24,7 @@
 #include "stock.h"
 #include "step_common.h"
 #include "step_many.h"
+#include "step_until.h"
 #include "state_obs.h"
 #include "state_view.h"
 #include "state_check.h"
@@ -438,7 +440,7 @@ void draw(MpEngine* e, uint8_t* rgb, uint8_t* wrgb, int pool_k = 1) {
 // draw-only launches of the unfused path; NULL: a single step)
 int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
            const uint8_t* bank = nullptr, const int32_t* src = nullptr, int bank_rows = 0,
-           const StepManyLaunch* many = nullptr) {
+           const StepManyLaunch* many = nullptr, const UntilArgs* until = nullptr) {
   stepk::StepArgs args;
   args.state = e->d_state; args.actions = actions; args.reset_mask = mask;
   args.bank = bank; args.src = src; args.bank_rows = bank_rows;
@@ -464,7 +466,8 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
     if (many) {
       StepManyLaunch l = *many;
       l.starts = starts;
-      if (l.active.active) launch_step_active(e->t, e->sub, args, l, e->stream);   // (MpStepActive)
+      if (until) launch_step_until(e->t, e->sub, args, l, *until, e->stream);   // (MpStepUntil)
+      else if (l.active.active) launch_step_active(e->t, e->sub, args, l, e->stream);   // (MpStepActive)
       else launch_step_many(e->t, e->sub, args, l, e->stream);
     } else if (starts) {
       launch_step_starts(e->t, e->sub, args, *starts, e->stream);
@@ -1028,6 +1031,8 @@ int plan_views(MpEngine* e, const MpDevOptions* dev) {
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the episode-start kernels failed: %d", rc);
   if (int rc = prepare_step_active())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the masked K-step kernels failed: %d", rc);
+  if (int rc = prepare_step_until())
+    return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the stopping K-step kernels failed: %d", rc);
   if (dev && dev->verbose)
     for (int v = 0; v < 6; ++v) {
       const FramePlan& pl = e->plan[v & 1][v >> 1];
@@ -1618,12 +1623,13 @@ static int world_states(MpEngine* e, MpWorldStates* r, bool restore) {
   }
 }
 
-// A K-step request (include/mp_engine.h: MpStepMany, MpStepTrajectory, MpStepActive), whichever
-// struct it came in: `r` names the rows it wants, `who` is the request's own name in the messages,
-// `mask` (MpStepActive only) the device mask and the distance between two of its rows.  Everything
-// is checked here, against kStepRowKinds (step_many.h) and mp_obs_bytes, before the one submission.
+// A K-step request (include/mp_engine.h: MpStepMany, MpStepTrajectory, MpStepActive, MpStepUntil),
+// whichever struct it came in: `r` names the rows it wants, `who` is the request's own name in the
+// messages, `mask` (MpStepActive, MpStepUntil) the device mask and the distance between two of its
+// rows, `until` (MpStepUntil only, whose mask may be NULL) the stop state.  Everything is checked
+// here, against kStepRowKinds (step_many.h) and mp_obs_bytes, before the one submission.
 static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r,
-                        const ActiveArgs* mask = nullptr) {
+                        const ActiveArgs* mask = nullptr, const UntilArgs* until = nullptr) {
   if (!e || !r.actions) return fail(MP_ERR_INVALID, "%s: NULL engine or actions", who);
   if (r.steps < 1 || r.steps > MP_STEP_MANY_MAX)
     return fail(MP_ERR_INVALID, "%s: steps %d is outside [1, %d]", who, r.steps, MP_STEP_MANY_MAX);
@@ -1650,12 +1656,31 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r,
   if (int rc = check_bank(e, r.actions, (K - 1) * r.actions_step_bytes + ablock, name)) return rc;
   StepManyLaunch l = {};
   if (mask) {
-    if (!mask->active) return fail(MP_ERR_INVALID, "%s: NULL active", who);
+    if (!mask->active && !until) return fail(MP_ERR_INVALID, "%s: NULL active", who);
+    if (!mask->active && mask->step != 0)
+      return fail(MP_ERR_INVALID, "%s: active_step_bytes %llu with a NULL active", who, (unsigned long long)mask->step);
     if (mask->step != 0 && (uint64_t)mask->step < N)
       return fail(MP_ERR_INVALID, "%s: active_step_bytes %llu is neither 0 nor at least one step's row of %llu "
                   "bytes", who, (unsigned long long)mask->step, (unsigned long long)N);
     snprintf(name, sizeof name, "%s (active)", who);
-    if (int rc = check_bank(e, mask->active, (K - 1) * (uint64_t)mask->step + N, name)) return rc;
+    if (mask->active)
+      if (int rc = check_bank(e, mask->active, (K - 1) * (uint64_t)mask->step + N, name)) return rc;
+    if (until) {
+      // (stopped, ran, returns: written by the launch — device memory, whole extents)
+      if ((uintptr_t)until->ran & 3)
+        return fail(MP_ERR_INVALID, "%s: ran %p is not 4-byte aligned", who, (const void*)until->ran);
+      if ((uintptr_t)until->returns & 7)
+        return fail(MP_ERR_INVALID, "%s: returns %p is not 8-byte aligned", who, (const void*)until->returns);
+      snprintf(name, sizeof name, "%s (stopped)", who);
+      if (until->stopped)
+        if (int rc = check_bank(e, until->stopped, N, name)) return rc;
+      snprintf(name, sizeof name, "%s (ran)", who);
+      if (until->ran)
+        if (int rc = check_bank(e, until->ran, N * 4u, name)) return rc;
+      snprintf(name, sizeof name, "%s (returns)", who);
+      if (until->returns)
+        if (int rc = check_bank(e, until->returns, N * P * 8u, name)) return rc;
+    }
     // (a slot row of a skipped world has no defined content)
     if (e->ring_slots > 0)
       return fail(MP_ERR_UNSUPPORTED, "%s: a rollout ring is bound (mp_bind_output_ring); a masked step "
@@ -1722,8 +1747,31 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r,
       }
     }
   }
+  if (until) {
+    // stopped, ran and returns are written while other waves still read the actions, the mask and
+    // `stopped`, and write the rows: none of the three may overlap anything else the request names
+    struct Range { const char* what; uintptr_t at; uint64_t bytes; };
+    std::vector<Range> all = {{"actions", (uintptr_t)r.actions, (K - 1) * r.actions_step_bytes + ablock}};
+    if (mask && mask->active) all.push_back({"active", (uintptr_t)mask->active, (K - 1) * (uint64_t)mask->step + N});
+    for (int i = 0; i < r.num_rows; ++i) {
+      const int index = step_row_index(r.rows[i].kind);
+      const StepRowKind& k = kStepRowKinds.of[index];
+      const uint64_t block = k.place == kRowState ? mp_snapshot_bytes(e)
+                             : k.place == kRowHash ? N * 8u : mp_obs_bytes(e, (MpObsKind)r.rows[i].kind);
+      all.push_back({k.name, (uintptr_t)r.rows[i].rows, (K - 1) * r.rows[i].step_bytes + block});
+    }
+    const size_t first = all.size();
+    if (until->stopped) all.push_back({"stopped", (uintptr_t)until->stopped, N});
+    if (until->ran) all.push_back({"ran", (uintptr_t)until->ran, N * 4u});
+    if (until->returns) all.push_back({"returns", (uintptr_t)until->returns, N * P * 8u});
+    for (size_t i = first; i < all.size(); ++i)
+      for (size_t j = 0; j < i; ++j)
+        if (all[i].at < all[j].at + all[j].bytes && all[j].at < all[i].at + all[i].bytes)
+          return fail(MP_ERR_INVALID, "%s: %s overlaps %s; stopped, ran and returns must not overlap each other "
+                      "or any other buffer of the request", who, all[i].what, all[j].what);
+  }
   e->touched = true;
-  return submit(e, r.fields ? STEP_MODE_FIELDS : STEP_MODE_STEP, r.actions, nullptr, nullptr, nullptr, 0, &l);
+  return submit(e, r.fields ? STEP_MODE_FIELDS : STEP_MODE_STEP, r.actions, nullptr, nullptr, nullptr, 0, &l, until);
 }
 
 // What mp_restore does when `bytes` is sizeof(MpStepMany): every non-NULL per_step[i] is one row
@@ -1762,6 +1810,25 @@ static int active_request(MpEngine* e, const MpStepActive& r) {
   const MpStepTrajectory t = {sizeof t, r.steps, r.fields, r.num_rows, r.actions, r.actions_step_bytes, r.rows};
   const ActiveArgs mask = {r.active, (long long)r.active_step_bytes};
   return step_request(e, kWho, t, &mask);
+}
+
+// ... and when it is sizeof(MpStepUntil): the masked request with a stop state.
+static int until_request(MpEngine* e, const MpStepUntil& r) {
+  static const char kWho[] = "MpStepUntil";
+  if (r.struct_size != sizeof(MpStepUntil))
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpStepUntil));
+  if (r.pad != 0) return fail(MP_ERR_INVALID, "%s: pad must be 0", kWho);
+  for (uint64_t word : r.reserved)
+    if (word != 0) return fail(MP_ERR_INVALID, "%s: the reserved words must be 0", kWho);
+  if (r.stop & ~(uint32_t)(MP_STOP_LAST | MP_STOP_REWARD))
+    return fail(MP_ERR_INVALID, "%s: stop %u has bits beyond MP_STOP_LAST | MP_STOP_REWARD", kWho, r.stop);
+  if (!std::isfinite(r.gamma)) return fail(MP_ERR_INVALID, "%s: gamma %g is not finite", kWho, r.gamma);
+  if (r.active_step_bytes > (1ull << 40))
+    return fail(MP_ERR_INVALID, "%s: active_step_bytes %llu", kWho, (unsigned long long)r.active_step_bytes);
+  const MpStepTrajectory t = {sizeof t, r.steps, r.fields, r.num_rows, r.actions, r.actions_step_bytes, r.rows};
+  const ActiveArgs mask = {r.active, (long long)r.active_step_bytes};
+  const UntilArgs until = {r.stop, r.stopped, r.ran, r.returns, r.gamma};
+  return step_request(e, kWho, t, &mask, &until);
 }
 
 // An MpStatesObserve request (include/mp_engine.h; carried by mp_snapshot): observations of rows
@@ -2246,6 +2313,15 @@ static_assert(sizeof(MpStepActive) == 96 && MP_SIZE_DIFFERS(MpStepActive) &&
                   sizeof(MpStepActive) != sizeof(MpStatesHash) && sizeof(MpStepActive) != sizeof(MpEpisodeStarts) &&
                   sizeof(MpStepActive) != sizeof(MpStatesView) && sizeof(MpStepActive) < 448,
               "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
+static_assert(sizeof(MpStepUntil) == 136 && MP_SIZE_DIFFERS(MpStepUntil) &&
+                  sizeof(MpStepUntil) != sizeof(MpStateLayout) && sizeof(MpStepUntil) != sizeof(MpStatesCheck) &&
+                  sizeof(MpStepUntil) != sizeof(MpStatesHash) && sizeof(MpStepUntil) != sizeof(MpEpisodeStarts) &&
+                  sizeof(MpStepUntil) != sizeof(MpStatesView) && sizeof(MpStepUntil) != sizeof(MpStepActive) &&
+                  sizeof(MpStepUntil) < 448,
+              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
+static_assert(offsetof(MpStepUntil, active_step_bytes) == offsetof(MpStepActive, active_step_bytes) &&
+                  offsetof(MpStepUntil, stop) == offsetof(MpStepActive, reserved),
+              "MpStepUntil's leading fields are MpStepActive's");
 #undef MP_SIZE_DIFFERS
 // An MpKernelVariant request (carried by mp_snapshot; `e` may be NULL: the host-only question).
 static int kernel_variant(const MpEngine* e, MpKernelVariant* r) {
@@ -2334,6 +2410,11 @@ int mp_restore(MpEngine* e, const void* buf, uint64_t bytes) {
     MpStepActive r;   // (read only: nothing is written back)
     memcpy(&r, buf, sizeof r);
     return active_request(e, r);
+  }
+  if (buf && bytes == sizeof(MpStepUntil)) {
+    MpStepUntil r;   // (read only: nothing is written back)
+    memcpy(&r, buf, sizeof r);
+    return until_request(e, r);
   }
   if (!e || !buf || bytes != mp_snapshot_bytes(e))
     return fail(MP_ERR_INVALID, "mp_restore: bad buffer");

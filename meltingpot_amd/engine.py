@@ -704,6 +704,64 @@ def check_step_active(active, steps: int, num_worlds: int):
   return a, (0 if a.ndim == 1 else N)
 
 
+# ... in which a world that ends its episode, or is paid, stops there (MpStepUntil)
+MP_STOP_LAST, MP_STOP_REWARD = 1, 2
+STOP_NAMES = {"last": MP_STOP_LAST, "reward": MP_STOP_REWARD}
+
+
+class MpStepUntil(ctypes.Structure):
+  _fields_ = [("struct_size", ctypes.c_uint32), ("steps", ctypes.c_int32),
+              ("fields", ctypes.c_int32), ("num_rows", ctypes.c_int32),
+              ("actions", ctypes.c_void_p), ("actions_step_bytes", ctypes.c_uint64),
+              ("rows", ctypes.POINTER(MpStepRow)), ("active", ctypes.c_void_p),
+              ("active_step_bytes", ctypes.c_uint64), ("stop", ctypes.c_uint32), ("pad", ctypes.c_uint32),
+              ("stopped", ctypes.c_void_p), ("ran", ctypes.c_void_p), ("returns", ctypes.c_void_p),
+              ("gamma", ctypes.c_double), ("reserved", ctypes.c_uint64 * 5)]
+
+
+def check_step_until(num_worlds: int, num_players: int, *, until=None, stopped=None, ran=None,
+                     returns=None, gamma=1.0, device=None) -> int:
+  """The rules of the until=, stopped=, returns= and gamma= arguments of Engine.step_many (and of
+  the ran / returns tensors it reuses from out=), without an engine.  until: None, "last",
+  "reward" or an iterable of these names.  stopped: a contiguous uint8 tensor [N].  ran: a
+  contiguous int32 tensor [N].  returns: None, a bool, or a contiguous float64 tensor [N, P].
+  gamma: a finite number.  device: where the tensors must live (None: not checked).  Returns the
+  MP_STOP_* bits of until=.  ValueError, naming the argument, otherwise."""
+  N, P = int(num_worlds), int(num_players)
+  try:
+    names = () if until is None else (until,) if isinstance(until, str) else tuple(until)
+  except TypeError:
+    raise ValueError(f"until= knows {tuple(STOP_NAMES)} or an iterable of them (got {until!r})") from None
+  stop = 0
+  for name in names:
+    if not isinstance(name, str) or name not in STOP_NAMES:
+      raise ValueError(f"until= knows {tuple(STOP_NAMES)} (got {name!r})")
+    stop |= STOP_NAMES[name]
+  def tensor(value, arg, dtype, shape):
+    if not hasattr(value, "data_ptr"):
+      raise ValueError(f"{arg}= must be a {dtype} tensor of shape {shape} (got {type(value).__name__})")
+    got = tuple(int(d) for d in value.shape)
+    if str(value.dtype) != f"torch.{dtype}" or got != shape:
+      raise ValueError(f"{arg}= must be a {dtype} tensor of shape {shape} (got {value.dtype} {got})")
+    if not value.is_contiguous():
+      raise ValueError(f"{arg}= must be contiguous (strides {tuple(value.stride())})")
+    if device is not None and value.device != device:
+      raise ValueError(f"{arg}= lives on {value.device}, the engine on {device}")
+  if stopped is not None:
+    tensor(stopped, "stopped", "uint8", (N,))
+  if ran is not None:
+    tensor(ran, "ran", "int32", (N,))
+  if returns is not None and not isinstance(returns, (bool, np.bool_)):
+    tensor(returns, "returns", "float64", (N, P))
+  try:
+    finite = bool(np.isfinite(float(gamma)))
+  except (TypeError, ValueError):
+    finite = False
+  if not finite:
+    raise ValueError(f"gamma= must be a finite number (got {gamma!r})")
+  return stop
+
+
 # Registered episode starts (include/mp_engine.h: MpEpisodeStarts), carried by mp_restore
 class MpEpisodeStarts(ctypes.Structure):
   _fields_ = [("struct_size", ctypes.c_uint32), ("fresh", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
@@ -1363,7 +1421,8 @@ class Engine:
 
   def step_many(self, actions, *, repeat: Optional[int] = None, fields: bool = False,
                 keep=("reward", "collective_reward", "step_type", "discount"), events: bool = False,
-                observations=(), out=None, states=False, hashes=False, active=None):
+                observations=(), out=None, states=False, hashes=False, active=None,
+                until=None, stopped=None, returns=False, gamma: float = 1.0):
     """K steps of every world in ONE launch, bit-identical to K calls of step() (fields=True:
     step_fields()) with actions[0] .. actions[K - 1]; returns the per-step transitions.
 
@@ -1398,8 +1457,31 @@ class Engine:
     before the call) — so rewards of skipped steps REPEAT: sum them under the mask.  The result
     equals the loop of step(actions[k], active=active[k]).  Refused with a rollout ring bound.
     None: exactly the request issued without it.
+    until: "last", "reward" or an iterable of both: a world stops INSIDE the call on the step that
+    leaves it on LAST (step_type 2), or that pays some player a non-zero reward, and skips the
+    steps behind it exactly as active= skips a step (it stands on the step that stopped it; its
+    rows repeat).  The call equals the loop of step(actions[k], active=active[k] & (stopped == 0))
+    with stopped updated from what each step left.
+    stopped: a device uint8 tensor [N], read and written in place: a world whose byte is non-zero
+    on entry does not run in this call and keeps its byte; a world that stops gets its reason bits
+    (MP_STOP_LAST = 1, MP_STOP_REWARD = 2).  Hand the same tensor to call after call and the
+    condition persists without the host; zero a byte and the world runs again (a world stopped on
+    LAST then takes its reset, or its registered episode start).  None: every world starts
+    unstopped and a new tensor is returned.
+    returns: True, or a float64 tensor [N, P] to write in place: the sum over the steps world w
+    ran, in step order, of gamma ** j * reward (j counts the steps that ran), every multiply and add
+    rounded in float64 on its own.  It is this call's sum.
+    With any of until=, stopped=, returns= the result gains "stopped" (uint8 [N]) and "ran" (int32
+    [N]: the steps each world ran in this call; out["ran"] is reused), and "returns" when asked
+    for; with none of them the call issues exactly the request it issues without them.
     Enqueued on the current stream; does not synchronise."""
     t = self._torch
+    stopping = until is not None or stopped is not None or (returns is not None and returns is not False)
+    if stopping:
+      stop = check_step_until(self.N, self.P, until=until, stopped=stopped, returns=returns, gamma=gamma,
+                              ran=None if out is None else out.get("ran"), device=self.device)
+    elif float(gamma) != 1.0:
+      raise ValueError("step_many: gamma= goes with returns=")
     A = int(self.info.num_action_fields) if fields else None
     if isinstance(actions, t.Tensor) and actions.is_cuda:
       if actions.dtype != t.int32:
@@ -1450,7 +1532,31 @@ class Engine:
       rows[i].step_bytes = _step_distance(buf, f"out[{key!r}]")
       result[key] = buf
     self.use_current_stream()
-    if active is not None:
+    if stopping:
+      ran = None if out is None else out.get("ran")
+      if ran is None:
+        ran = t.empty((self.N,), dtype=t.int32, device=self.device)
+      if stopped is None:
+        stopped = t.zeros((self.N,), dtype=t.uint8, device=self.device)
+      if returns is True:
+        returns = None if out is None else out.get("returns")
+        if returns is None:
+          returns = t.empty((self.N, self.P), dtype=t.float64, device=self.device)
+        else:
+          check_step_until(self.N, self.P, returns=returns, device=self.device)
+      req = MpStepUntil(ctypes.sizeof(MpStepUntil), K, 1 if fields else 0, len(rows))
+      if active is not None:
+        req.active = mask.data_ptr()
+        req.active_step_bytes = mask_step
+      req.stop = stop
+      req.stopped = stopped.data_ptr()
+      req.ran = ran.data_ptr()
+      req.gamma = float(gamma)
+      result["stopped"], result["ran"] = stopped, ran
+      if returns is not None and returns is not False:
+        req.returns = returns.data_ptr()
+        result["returns"] = returns
+    elif active is not None:
       req = MpStepActive(ctypes.sizeof(MpStepActive), K, 1 if fields else 0, len(rows))
       req.active = mask.data_ptr()
       req.active_step_bytes = mask_step

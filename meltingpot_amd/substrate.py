@@ -117,6 +117,26 @@ class StepManyTrajectory(StepManyResult):
     return out
 
 
+class StepManyUntil(StepManyTrajectory):
+  """What `Substrate.step_many` returns with `until=`, `stopped=` or `returns=`: a
+  `StepManyTrajectory` (its `.observation` is empty, `.states` and `.hashes` None, where they were
+  not asked for) plus `.ran`, int32 [N]: the steps each world ran in this call; `.stopped`, uint8
+  [N]: 0, or the reason bits of the step that stopped the world (1: it left the world on LAST, 2:
+  it paid a player), the tensor handed in where one was; and `.returns`, float64 [N, P]: the
+  discounted sum of the rewards of the steps that ran (None when not asked for).  Carried like
+  `.observation`."""
+  ran: Any = None
+  stopped: Any = None
+  returns: Any = None
+
+  def _replace(self, **kwargs):
+    out = super()._replace(**kwargs)
+    out.ran = self.ran
+    out.stopped = self.stopped
+    out.returns = self.returns
+    return out
+
+
 _FIVE_NAMES = {kind: name for name, kind in engine_lib.STEP_MANY_NAMES.items()}
 
 
@@ -124,9 +144,13 @@ def _many_result(r, leaves, timestep, fingerprint=None):
   """The result of a step_many call from the engine's dict `r` (`leaves`: asked name -> kind;
   `fingerprint`: the engine's, when the call asked for the per-step states)."""
   fields = (r["step_type"], r["reward"], r["discount"], r["collective_reward"], r.get("events"), timestep)
-  if not leaves and fingerprint is None and r.get("hashes") is None:
+  if not leaves and fingerprint is None and r.get("hashes") is None and "ran" not in r:
     return StepManyResult(*fields)
-  out = StepManyTrajectory(*fields)
+  if "ran" in r:   # (a call with until=, stopped= or returns=)
+    out = StepManyUntil(*fields)
+    out.ran, out.stopped, out.returns = r["ran"], r["stopped"], r.get("returns")
+  else:
+    out = StepManyTrajectory(*fields)
   # (a leaf that is one of the five per-step kinds is the tensor the call stacks anyway)
   out.observation = {n: r[_FIVE_NAMES[k]] if k in _FIVE_NAMES else r[k] for n, k in leaves.items()}
   if fingerprint is not None:
@@ -167,6 +191,43 @@ def _step_mask(t, active, lengths, K: int, N: int, device, ring: bool):
   if isinstance(mask, np.ndarray):
     mask = t.from_numpy(mask).to(device)
   return mask
+
+
+def _step_until(t, until, stopped, returns, gamma, N: int, P: int, device, ring: bool):
+  """The stop arguments of a step_many call as the engines take them: None for a call without
+  them, else the dict of `until`, `stopped`, `returns`, `gamma` and `ran` — the [N] / [N, P] device
+  tensors allocated here where the caller gave none, so that the members of a mixture write their
+  rows of ONE tensor each.  `ring`: the substrate was built with rollout_length=T."""
+  if until is None and stopped is None and (returns is None or returns is False):
+    if float(gamma) != 1.0:
+      raise ValueError("gamma= goes with returns=")
+    return None
+  if ring:
+    raise ValueError("a call that stops worlds cannot write a rollout ring (rollout_length=T): a slot row of "
+                     "a stopped world has no defined content; build the substrate without rollout_length")
+  if isinstance(until, str):
+    until = (until,)
+  elif until is not None:
+    until = tuple(until)
+  engine_lib.check_step_until(N, P, until=until, stopped=stopped, returns=returns, gamma=gamma, device=device)
+  if stopped is None:
+    stopped = t.zeros((N,), dtype=t.uint8, device=device)
+  if returns is True:
+    returns = t.empty((N, P), dtype=t.float64, device=device)
+  return {"until": until, "stopped": stopped, "returns": returns, "gamma": float(gamma),
+          "ran": t.empty((N,), dtype=t.int32, device=device)}
+
+
+def _until_slice(stop, out, off: int, n: int):
+  """(`more`, `out`) of one member's launch: its rows [off, off + n) of the stop tensors of
+  `_step_until`, in place."""
+  if stop is None:
+    return {}, out
+  more = {"until": stop["until"], "stopped": stop["stopped"][off:off + n], "gamma": stop["gamma"],
+          "returns": False if stop["returns"] is None or stop["returns"] is False else stop["returns"][off:off + n]}
+  out = dict(out or {})
+  out["ran"] = stop["ran"][off:off + n]
+  return more, out
 
 
 def _many_actions(t, actions, repeat, N: int, P: int, num_actions: Optional[int]):
@@ -1322,7 +1383,8 @@ class Substrate:
 
   def step_many(self, actions, repeat: Optional[int] = None, events: bool = False,
                 observations=(), states: bool = False, hashes: bool = False,
-                active=None, lengths=None) -> StepManyResult:
+                active=None, lengths=None, until=None, stopped=None, returns=False,
+                gamma: float = 1.0) -> StepManyResult:
     """K steps in ONE launch, bit-identical to K calls of `step` (batched substrates).
     `actions`: ints [K, N, P] (a device tensor is read in place; it may be a column slice
     [:, a:b] of a wider one), or one block [N, P] with `repeat=K`.  Returns the per-step
@@ -1351,7 +1413,16 @@ class Substrate:
     Row k of every per-step tensor then repeats row k - 1 (row 0: the leaf as it was), so the
     rewards of skipped steps repeat: sum them under the mask.  `lengths`: an int tensor [N]
     instead — world w runs steps 0 .. lengths[w] - 1 (rollouts of different depths).  Not with
-    `rollout_length=T`."""
+    `rollout_length=T`.
+    `until`: "last", "reward" or both: a world stops inside the call on the step that leaves it on
+    LAST (so a sum of its rewards ends with its episode), or that pays some player; it stands on
+    that step and skips the steps behind it as `active` skips a step.  `stopped`: a device uint8
+    tensor [N], read and written in place — a world whose byte is non-zero does not run and keeps
+    it, a world that stops gets 1 (LAST) | 2 (reward) — which makes the condition persist over
+    calls without the host; zero a byte and the world runs again.  `returns=True` (or a float64
+    tensor [N, P]): the discounted sum, with `gamma`, of the rewards of the steps each world ran.
+    With any of the three the result is a `StepManyUntil` with `.ran`, `.stopped`, `.returns`.
+    They combine with `active` / `lengths` and everything above.  Not with `rollout_length=T`."""
     if not self._batched:
       raise ValueError("step_many steps a batch of worlds: build the substrate with num_worlds > 1")
     leaves = self._many_leaves(observations)
@@ -1361,9 +1432,12 @@ class Substrate:
       limit = len(self._action_rows) if self._action_rows is not None else self._eng.num_actions
     a, K = _many_actions(t, actions, repeat, self._eng.N, self._eng.P, limit)
     mask = _step_mask(t, active, lengths, K, self._eng.N, self._eng.device, self._T > 0)
+    stop = _step_until(t, until, stopped, returns, gamma, self._eng.N, self._eng.P, self._eng.device,
+                       self._T > 0)
+    more, out = _until_slice(stop, None, 0, self._eng.N)
     self._observables.action.on_next(actions)
     self._eng.use_current_stream()
-    r = self._submit_many(a, repeat, events, None, leaves, bool(states), bool(hashes), active=mask)
+    r = self._submit_many(a, repeat, events, out, leaves, bool(states), bool(hashes), active=mask, **more)
     return _many_result(r, leaves, self._emit(self._timestep()),
                         self._eng.state_fingerprint if states else None)
 
@@ -2022,7 +2096,8 @@ class MixtureSubstrate:
 
   def step_many(self, actions, repeat: Optional[int] = None, events: bool = False,
                 observations=(), states: bool = False, hashes: bool = False,
-                active=None, lengths=None) -> StepManyResult:
+                active=None, lengths=None, until=None, stopped=None, returns=False,
+                gamma: float = 1.0) -> StepManyResult:
     """As `Substrate.step_many`, over the members: one K-step launch per member, each reading
     its columns [:, off_i:off_i + n_i] of `actions` and writing its columns of the shared
     [K, N, ...] per-step tensors, those of `observations` included (nothing is copied or
@@ -2031,7 +2106,9 @@ class MixtureSubstrate:
     [K, N] tensor whose columns the members write — a per-step state identity of every world
     (comparable within one member only: the members' fingerprints differ).
     `active` / `lengths`: as `Substrate.step_many` takes them, over all N worlds; every member
-    reads its columns of the one mask in place."""
+    reads its columns of the one mask in place.
+    `until` / `stopped` / `returns` / `gamma`: likewise; `stopped` [N], `.ran` [N] and `.returns`
+    [N, P] are one tensor each, whose rows the members read and write in place."""
     if states:
       raise ValueError("step_many: a mixture has no per-step states (states=True): its members' records "
                        "differ in size and fingerprint; step the members' substrates on their own")
@@ -2042,6 +2119,8 @@ class MixtureSubstrate:
     a, K = _many_actions(t, actions, repeat, self._N, self._P, limit)
     dev = first._eng.device
     mask = _step_mask(t, active, lengths, K, self._N, dev, any(m._T > 0 for m in self._members))
+    stop = _step_until(t, until, stopped, returns, gamma, self._N, self._P, dev,
+                       any(m._T > 0 for m in self._members))
     keys = list(engine_lib.STEP_MANY_KINDS[:5 if events else 4])
     keys += [kind for kind in leaves.values() if kind not in _FIVE_NAMES]
     out = {}
@@ -2056,9 +2135,14 @@ class MixtureSubstrate:
       cols = a[off:off + n] if repeat is not None else a[:, off:off + n]
       if repeat is not None and isinstance(cols, t.Tensor):
         cols = cols.contiguous()
-      m._submit_many(cols, repeat, events, {k: v[:, off:off + n] for k, v in out.items()}, leaves,
-                     active=None if mask is None else mask[..., off:off + n])
+      more, rows = _until_slice(stop, {k: v[:, off:off + n] for k, v in out.items()}, off, n)
+      m._submit_many(cols, repeat, events, rows, leaves,
+                     active=None if mask is None else mask[..., off:off + n], **more)
     self._submissions += 1
+    if stop is not None:
+      out["ran"], out["stopped"] = stop["ran"], stop["stopped"]
+      if stop["returns"] is not None and stop["returns"] is not False:
+        out["returns"] = stop["returns"]
     return _many_result(out, leaves, self._emit(self._timestep()))
 
   def _member_at(self, world: int):
