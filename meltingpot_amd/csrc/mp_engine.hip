@@ -30,15 +30,6 @@
 #include "state_check.h"
 #include "state_hash.h"
 
-void launch_step(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
-                 hipStream_t stream);
-void launch_step_starts(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
-                        const stepk::StartArgs& st, hipStream_t stream);   // (step_starts.hip)
-int prepare_step_starts();
-int prepare_step();
-void launch_layer_view(const DevTables& t, const uint8_t* state, int32_t* out, int num_worlds,
-                       hipStream_t stream);
-
 // frame.hip
 constexpr int kFaultWords = 64 + 4 * 16 * 64 * 2;   // fault words + the timeline build's log
 // views: 0 = per-agent RGB, 1 = WORLD.RGB, 2 = both in one launch

@@ -9,6 +9,17 @@
 int step_lds_bytes(const DevTables& t, const SubstrateTables& s, int wpg);
 int step_worlds_per_group(const DevTables& t, const SubstrateTables& s);
 
+// One step of every world (step_kernels.hip), the same with the engine's registered episode
+// starts (step_starts.hip), and mp_observe's LAYER from the records in HBM (step_kernels.hip).
+void launch_step(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
+                 hipStream_t stream);
+int prepare_step();
+void launch_step_starts(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
+                        const stepk::StartArgs& st, hipStream_t stream);
+int prepare_step_starts();
+void launch_layer_view(const DevTables& t, const uint8_t* state, int32_t* out, int num_worlds,
+                       hipStream_t stream);
+
 // Every kind a K-step launch can stack per step, by MpObsKind: its name in messages, its element
 // size (a row distance is a multiple of it, a buffer aligned to it) and where its rows go — slot
 // `slot` of ManyArgs::row (the five kinds of MpStepMany) or of StepRows::fin, StepRows::layer, or

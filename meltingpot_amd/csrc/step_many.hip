@@ -2,93 +2,32 @@
 // include/mp_engine.h): one wavefront per world as in step_kernels.hip, with the world's record
 // resident in LDS across K steps of one launch.  A unit of its own: the single-step kernels and
 // k_frame are compiled from exactly what they were compiled from before.
-#include "../../include/mp_pack.h"
-#include "step_clean_up.h"
-#include "step_coins.h"
-#include "step_commons.h"
-#include "step_coop.h"
-#include "step_gift.h"
-#include "step_mushroom.h"
-#include "step_cook.h"
-#include "step_matrix.h"
-#include "step_territory.h"
-#include "step_load.h"
-#include "step_many.h"
-#include "state_hash.h"
+#include "step_levels.h"
+#include "step_rows.h"
 
 namespace {
 
 using namespace stepk;
 
-constexpr int kWorldsPerGroup = 4;   // (step_kernels.hip)
-
-template <class T>
-__device__ inline T* row_of(uint8_t* base, long long bytes, int k, T* in_place) {
-  return base ? reinterpret_cast<T*>(base + (long long)k * bytes) : in_place;
-}
-
-// The K-step form of run_one_world: the tables, the site lists and the record are loaded once,
-// the marks and the level's extras set up once (as a feeder of k_frame does for the worlds it
-// steps one after the other on one scratch), and per step only the event scratch is cleared, the
-// action looked up and the level's step run on the record in LDS.  Step k + 1's action ids are
-// requested before step k's work.  finish() still stores the record after every step: those are
-// stores nobody waits for, and the next step works on the LDS copy; the record HBM holds in the
-// end is step K's.  The five per-step kinds go to row k of the caller's buffers where given; the
-// wave then copies row K - 1 to the in-place buffers, every lane reading back exactly the words
-// it stored itself (program order of one thread: no fence, no second launch).
-//
-// Rows (an MpStepTrajectory request, `r`): per-step rows of the other non-pixel kinds, row k =
-// what the in-place buffer of the kind holds after step k of the loop of single steps.  That
-// buffer KEEPS its value where a step does not write the kind, so the rows carry it:
-//  * r.fin (READY_TO_SHOOT, AUX0, POSITION, ORIENTATION) are retargeted to row k like the five.
-//    finish() writes them on every path but the frozen one (dispatch(): done without
-//    auto-reset), element w * P + lane from lane `lane` (the_matrix's second store of READY
-//    too).  Before a frozen step each lane copies its own element from row k - 1 (k = 0: from
-//    the in-place buffer, stored by an earlier launch) to row k: it loads what it stored
-//    itself, by finish() or by this copy one step earlier, so program order of one thread
-//    covers it, and a step that is not frozen pays nothing.  Row K - 1 goes to the in-place
-//    buffers in the end, lane by lane, as for the five.
-//  * r.level: a level writes these where and when its rules say (INTERACTION_REWARDS from the
-//    two lanes of an interaction, the zap matrix from the lane of the beam cell that hit), so
-//    the step keeps writing the in-place buffer and the wave copies the world's slice of it to
-//    row k after the step.  Here a lane does load words that OTHER lanes of its wave stored
-//    during the step.  wsync() between the step and the loads orders them: a release and an
-//    acquire fence at workgroup scope around a wave barrier.  Workgroup scope is enough, since
-//    the stores and the loads come from one wave on one CU, and on gfx950 it costs no
-//    instruction: outside threadgroup-split mode the compiler lowers these fences to a wait for
-//    LDS only, because a CU's write-through vector L1 performs the vector memory instructions
-//    of a wave in the order they were issued, so a load issued behind a store of the same CU
-//    sees it (no L1 invalidate, no L2 write-back: nothing another CU could observe, tens of
-//    cycles where the agent-scope forms cost microseconds).  The fences are still needed: they
-//    are what keeps the compiler from moving the loads.  What the copy does cost is its own
-//    s_waitcnt before the stores to row k: vmcnt counts loads and stores in one order, so the
-//    loaded words arrive behind the record's write-back of finish().  Only a request that names
-//    one of these kinds pays that.  The loop-top wsync() keeps the next step's stores to the
-//    in-place buffer behind these loads.
-//  * r.layer: write_layer() on row k from the record in LDS after every step of a started
-//    world, a frozen one included (the same bytes again).
-//  * the state rows (MP_STEP_ROW_STATE, `sp`, States = true: the k_step_states_* family):
-//    store_record() of the record in LDS to row k after every step of a started world — the
-//    bytes finish() has just written back to the world's own record, so what MP_STATES_SAVE
-//    would copy from there.  It reads the LDS record behind the same wsync() as the layer row;
-//    the loop-top wsync() keeps the next step's writes behind it.  A family of its own: with the
-//    row as one more runtime branch of k_step_rows_*, that family's LAYER rows cost 9 % more on
-//    clean_up (profiles/r16_observe_states.md); this way its code is what it was.
-//  * the hash rows (MP_STEP_ROW_HASH, `hp`, Hashes = true: the k_step_hashes_* family): the hash
-//    of the record in LDS (state_hash.h: every lane's share of the masked words, a wave-wide
-//    sum, 8 bytes from lane 0) to element w of row k, behind the same wsync() and under the same
-//    `started` test as the state row — so row k is the hash of what the state row's row k holds.
-//    The mask's lines come from device memory (L2 after the first wave).  A request that names
-//    both rows runs this family too: whether the record is stored as well is a runtime test
-//    here and nowhere else (`sp->row`), and the three families above are what they were.
-// Which kinds are asked for is wave-uniform: every branch on it is a scalar one.
-//  * registered episode starts (MpEpisodeStarts, `st`, Starts = true: the k_many_starts_* family): a
+// K steps of one world (step_rows.h documents the loop, the rows, the carry rule and the fences).
+// Five kernel families, each added so that the ones before it run exactly the code they ran:
+//  * k_step_many_* (Rows = false): rows of the five kinds only, an MpStepMany request.
+//  * k_step_rows_* (Rows): the rows of an MpStepTrajectory request, `rp`.
+//  * k_step_states_* (States): the state rows too, always.  With the row as one more runtime
+//    branch of k_step_rows_*, that family's LAYER rows cost 9 % more on clean_up
+//    (profiles/r16_observe_states.md).
+//  * k_step_hashes_* (Hashes): the hash rows, always; a request that names both rows runs this
+//    family too: whether the record is stored as well is a runtime test (sp->row).
+//  * k_many_starts_* (Starts, with Hashes): registered episode starts (MpEpisodeStarts, `st`).  A
 //    step in which a world auto-resets runs start_world() behind the level's reset (step_load.h),
 //    with the outputs of row k — so row k of every kind a start writes holds the start's values,
 //    the level kinds are copied from the in-place buffer the start wrote, and LAYER, the state row
 //    and the hash row come from the started record in LDS.  ONE family for every combination of
-//    rows: which rows are asked for is a runtime test here (r.fin[i], r.layer, sp->row, hp->row),
-//    as the state row is in k_step_hashes_*, and the four families above are what they were.
+//    rows: which rows are asked for is a runtime test (r.fin[i], r.layer, sp->row, hp->row).
+// The frozen carry, the level copy and the final copy are carry_fin, carry_five and copy_level_rows
+// of step_rows.h written out: with the calls the four row families were scheduled differently and
+// k_step_rows_clean_up's LAYER rows took 0.5 % longer (profiles/r23_kstep_refactor.md), so a change
+// to the carry rule is made there AND here.
 template <bool Rows, bool States, class Tables, class Sites, bool Hashes = false, bool Starts = false>
 __device__ inline void run_many(const DevTables& t, const Tables& c, const StepArgs& args0,
                                 const ManyArgs& m, const StepRows* rp, int extra,
@@ -233,113 +172,56 @@ __device__ inline void run_many(const DevTables& t, const Tables& c, const StepA
   if (args0.out.layer) write_layer(t, wd.rec, args0.out, w, lane);
 }
 
-#define MP_STEP_MANY_KERNEL(name, TablesT, SitesT, extra)                                            \
-  __global__ __launch_bounds__(kWorldsPerGroup * 64) void name(DevTables t, TablesT c, StepArgs args, \
-                                                               ManyArgs m) {                         \
-    run_many<false, false, TablesT, SitesT>(t, c, args, m, nullptr, extra);                          \
+#define MP_STEP_MANY_KERNEL(level, TablesT, SitesT, sub, member)                                     \
+  __global__ __launch_bounds__(kWorldsPerGroup * 64) void k_step_many_##level(DevTables t, TablesT c, \
+                                                                             StepArgs args, ManyArgs m) { \
+    run_many<false, false, TablesT, SitesT>(t, c, args, m, nullptr, extra_bytes(c));                 \
   }
-MP_STEP_MANY_KERNEL(k_step_many_clean_up, CleanUpTables, CleanUpSites, 0)
-MP_STEP_MANY_KERNEL(k_step_many_commons, CommonsTables, CommonsSites, 0)
-MP_STEP_MANY_KERNEL(k_step_many_coins, CoinsTables, CoinsSites, 0)
-MP_STEP_MANY_KERNEL(k_step_many_coop, CoopTables, CoopSites, 0)
-MP_STEP_MANY_KERNEL(k_step_many_gift, GiftTables, GiftSites, 0)
-MP_STEP_MANY_KERNEL(k_step_many_cook, CookTables, CookSites, 0)
-MP_STEP_MANY_KERNEL(k_step_many_mushroom, MushroomTables, MushroomSites, extra_bytes(c))
-MP_STEP_MANY_KERNEL(k_step_many_matrix, MatrixTables, MatrixSites, 0)
-MP_STEP_MANY_KERNEL(k_step_many_territory, TerritoryTables, TerritorySites, extra_bytes(c))
+MP_STEP_LEVELS(MP_STEP_MANY_KERNEL)
 #undef MP_STEP_MANY_KERNEL
 
-// The same with the rows of an MpStepTrajectory request: a second family, so that an MpStepMany
-// request runs exactly the code it ran before there was one.
-#define MP_STEP_ROWS_KERNEL(name, TablesT, SitesT, extra)                                            \
-  __global__ __launch_bounds__(kWorldsPerGroup * 64) void name(DevTables t, TablesT c, StepArgs args, \
-                                                               ManyArgs m, StepRows r) {             \
-    run_many<true, false, TablesT, SitesT>(t, c, args, m, &r, extra);                                \
+#define MP_STEP_ROWS_KERNEL(level, TablesT, SitesT, sub, member)                                     \
+  __global__ __launch_bounds__(kWorldsPerGroup * 64) void k_step_rows_##level(                       \
+      DevTables t, TablesT c, StepArgs args, ManyArgs m, StepRows r) {                               \
+    run_many<true, false, TablesT, SitesT>(t, c, args, m, &r, extra_bytes(c));                       \
   }
-MP_STEP_ROWS_KERNEL(k_step_rows_clean_up, CleanUpTables, CleanUpSites, 0)
-MP_STEP_ROWS_KERNEL(k_step_rows_commons, CommonsTables, CommonsSites, 0)
-MP_STEP_ROWS_KERNEL(k_step_rows_coins, CoinsTables, CoinsSites, 0)
-MP_STEP_ROWS_KERNEL(k_step_rows_coop, CoopTables, CoopSites, 0)
-MP_STEP_ROWS_KERNEL(k_step_rows_gift, GiftTables, GiftSites, 0)
-MP_STEP_ROWS_KERNEL(k_step_rows_cook, CookTables, CookSites, 0)
-MP_STEP_ROWS_KERNEL(k_step_rows_mushroom, MushroomTables, MushroomSites, extra_bytes(c))
-MP_STEP_ROWS_KERNEL(k_step_rows_matrix, MatrixTables, MatrixSites, 0)
-MP_STEP_ROWS_KERNEL(k_step_rows_territory, TerritoryTables, TerritorySites, extra_bytes(c))
+MP_STEP_LEVELS(MP_STEP_ROWS_KERNEL)
 #undef MP_STEP_ROWS_KERNEL
 
-// ... and with the per-step world states (MP_STEP_ROW_STATE) beside whatever other rows are asked
-// for: a third family, so that the two above run exactly the code they ran before there was one.
-#define MP_STEP_STATES_KERNEL(name, TablesT, SitesT, extra)                                          \
-  __global__ __launch_bounds__(kWorldsPerGroup * 64) void name(DevTables t, TablesT c, StepArgs args, \
-                                                               ManyArgs m, StepRows r, StateRows s) { \
-    run_many<true, true, TablesT, SitesT>(t, c, args, m, &r, extra, &s);                             \
+#define MP_STEP_STATES_KERNEL(level, TablesT, SitesT, sub, member)                                   \
+  __global__ __launch_bounds__(kWorldsPerGroup * 64) void k_step_states_##level(                     \
+      DevTables t, TablesT c, StepArgs args, ManyArgs m, StepRows r, StateRows s) {                  \
+    run_many<true, true, TablesT, SitesT>(t, c, args, m, &r, extra_bytes(c), &s);                    \
   }
-MP_STEP_STATES_KERNEL(k_step_states_clean_up, CleanUpTables, CleanUpSites, 0)
-MP_STEP_STATES_KERNEL(k_step_states_commons, CommonsTables, CommonsSites, 0)
-MP_STEP_STATES_KERNEL(k_step_states_coins, CoinsTables, CoinsSites, 0)
-MP_STEP_STATES_KERNEL(k_step_states_coop, CoopTables, CoopSites, 0)
-MP_STEP_STATES_KERNEL(k_step_states_gift, GiftTables, GiftSites, 0)
-MP_STEP_STATES_KERNEL(k_step_states_cook, CookTables, CookSites, 0)
-MP_STEP_STATES_KERNEL(k_step_states_mushroom, MushroomTables, MushroomSites, extra_bytes(c))
-MP_STEP_STATES_KERNEL(k_step_states_matrix, MatrixTables, MatrixSites, 0)
-MP_STEP_STATES_KERNEL(k_step_states_territory, TerritoryTables, TerritorySites, extra_bytes(c))
+MP_STEP_LEVELS(MP_STEP_STATES_KERNEL)
 #undef MP_STEP_STATES_KERNEL
 
-// ... and with the per-step state hashes (MP_STEP_ROW_HASH), beside the state rows where the
-// request names both: a fourth family, so that the three above run exactly the code they ran before
-// there was one.
-#define MP_STEP_HASHES_KERNEL(name, TablesT, SitesT, extra)                                          \
-  __global__ __launch_bounds__(kWorldsPerGroup * 64) void name(DevTables t, TablesT c, StepArgs args, \
-                                                               ManyArgs m, StepRows r, StateRows s,  \
-                                                               HashRows h) {                         \
-    run_many<true, false, TablesT, SitesT, true>(t, c, args, m, &r, extra, &s, &h);                  \
+#define MP_STEP_HASHES_KERNEL(level, TablesT, SitesT, sub, member)                                   \
+  __global__ __launch_bounds__(kWorldsPerGroup * 64) void k_step_hashes_##level(                     \
+      DevTables t, TablesT c, StepArgs args, ManyArgs m, StepRows r, StateRows s, HashRows h) {      \
+    run_many<true, false, TablesT, SitesT, true>(t, c, args, m, &r, extra_bytes(c), &s, &h);         \
   }
-MP_STEP_HASHES_KERNEL(k_step_hashes_clean_up, CleanUpTables, CleanUpSites, 0)
-MP_STEP_HASHES_KERNEL(k_step_hashes_commons, CommonsTables, CommonsSites, 0)
-MP_STEP_HASHES_KERNEL(k_step_hashes_coins, CoinsTables, CoinsSites, 0)
-MP_STEP_HASHES_KERNEL(k_step_hashes_coop, CoopTables, CoopSites, 0)
-MP_STEP_HASHES_KERNEL(k_step_hashes_gift, GiftTables, GiftSites, 0)
-MP_STEP_HASHES_KERNEL(k_step_hashes_cook, CookTables, CookSites, 0)
-MP_STEP_HASHES_KERNEL(k_step_hashes_mushroom, MushroomTables, MushroomSites, extra_bytes(c))
-MP_STEP_HASHES_KERNEL(k_step_hashes_matrix, MatrixTables, MatrixSites, 0)
-MP_STEP_HASHES_KERNEL(k_step_hashes_territory, TerritoryTables, TerritorySites, extra_bytes(c))
+MP_STEP_LEVELS(MP_STEP_HASHES_KERNEL)
 #undef MP_STEP_HASHES_KERNEL
 
-// ... and with registered episode starts (MpEpisodeStarts), whatever rows the request names: a fifth
-// family, so that the four above run exactly the code they ran before there was one.
-#define MP_MANY_STARTS_KERNEL(name, TablesT, SitesT, extra)                                          \
-  __global__ __launch_bounds__(kWorldsPerGroup * 64) void name(DevTables t, TablesT c, StepArgs args, \
-                                                               ManyArgs m, StepRows r, StateRows s,  \
-                                                               HashRows h, StartArgs st) {           \
-    run_many<true, false, TablesT, SitesT, true, true>(t, c, args, m, &r, extra, &s, &h, &st);       \
+#define MP_MANY_STARTS_KERNEL(level, TablesT, SitesT, sub, member)                                   \
+  __global__ __launch_bounds__(kWorldsPerGroup * 64) void k_many_starts_##level(                     \
+      DevTables t, TablesT c, StepArgs args, ManyArgs m, StepRows r, StateRows s, HashRows h, StartArgs st) { \
+    run_many<true, false, TablesT, SitesT, true, true>(t, c, args, m, &r, extra_bytes(c), &s, &h, &st); \
   }
-MP_MANY_STARTS_KERNEL(k_many_starts_clean_up, CleanUpTables, CleanUpSites, 0)
-MP_MANY_STARTS_KERNEL(k_many_starts_commons, CommonsTables, CommonsSites, 0)
-MP_MANY_STARTS_KERNEL(k_many_starts_coins, CoinsTables, CoinsSites, 0)
-MP_MANY_STARTS_KERNEL(k_many_starts_coop, CoopTables, CoopSites, 0)
-MP_MANY_STARTS_KERNEL(k_many_starts_gift, GiftTables, GiftSites, 0)
-MP_MANY_STARTS_KERNEL(k_many_starts_cook, CookTables, CookSites, 0)
-MP_MANY_STARTS_KERNEL(k_many_starts_mushroom, MushroomTables, MushroomSites, extra_bytes(c))
-MP_MANY_STARTS_KERNEL(k_many_starts_matrix, MatrixTables, MatrixSites, 0)
-MP_MANY_STARTS_KERNEL(k_many_starts_territory, TerritoryTables, TerritorySites, extra_bytes(c))
+MP_STEP_LEVELS(MP_MANY_STARTS_KERNEL)
 #undef MP_MANY_STARTS_KERNEL
 
 }  // namespace
 
-// The K-step kernels may take all 160 KB of a CU's LDS, like the single-step ones.
 int prepare_step_many() {
-  const void* km[45] = {
-#define MP_BOTH(level)                                                                             \
+#define MP_LEVEL(level, TablesT, SitesT, sub, member)                                              \
   reinterpret_cast<const void*>(&k_step_many_##level), reinterpret_cast<const void*>(&k_step_rows_##level), \
       reinterpret_cast<const void*>(&k_step_states_##level), reinterpret_cast<const void*>(&k_step_hashes_##level), \
-      reinterpret_cast<const void*>(&k_many_starts_##level)
-      MP_BOTH(clean_up), MP_BOTH(commons), MP_BOTH(coins), MP_BOTH(territory), MP_BOTH(matrix),
-      MP_BOTH(coop), MP_BOTH(gift), MP_BOTH(cook), MP_BOTH(mushroom)};
-#undef MP_BOTH
-  for (const void* f : km)
-    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return 1;
-  return 0;
+      reinterpret_cast<const void*>(&k_many_starts_##level),
+  const void* const k[] = {MP_STEP_LEVELS(MP_LEVEL)};
+#undef MP_LEVEL
+  return step_take_all_lds(k);
 }
 
 // K steps of every world in one launch (MpStepMany, MpStepTrajectory): the geometry of
@@ -350,32 +232,20 @@ int prepare_step_many() {
 void launch_step_many(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
                       const StepManyLaunch& l, hipStream_t stream) {
   const ManyArgs& m = l.many;
-  const bool more = l.any_rows;
-  const int wpg = step_worlds_per_group(t, s);
-  const size_t lds = (size_t)step_lds_bytes(t, s, wpg);
-  const dim3 grid((args.num_worlds + wpg - 1) / wpg), block(wpg * 64);
-  StepRows r = l.rows;   // (the level kinds' sources: this submission's buffers)
-  for (int i = 0; i < r.n_level; ++i) r.level[i].src = level_source(args.out, r.level[i].which);
-#define MP_LAUNCH(level, tables)                                                                  \
-  if (l.starts)                                                                                   \
-    hipLaunchKernelGGL(k_many_starts_##level, grid, block, lds, stream, t, tables, args, m, r, l.state, l.hash, *l.starts); \
-  else if (l.hash.row)                                                                                 \
-    hipLaunchKernelGGL(k_step_hashes_##level, grid, block, lds, stream, t, tables, args, m, r, l.state, l.hash); \
-  else if (l.state.row)                                                                           \
-    hipLaunchKernelGGL(k_step_states_##level, grid, block, lds, stream, t, tables, args, m, r, l.state); \
-  else if (more) hipLaunchKernelGGL(k_step_rows_##level, grid, block, lds, stream, t, tables, args, m, r); \
-  else hipLaunchKernelGGL(k_step_many_##level, grid, block, lds, stream, t, tables, args, m);    \
-  break;
-  switch (s.substrate) {
-    case MPK_SUBSTRATE_CLEAN_UP: MP_LAUNCH(clean_up, s.cu)
-    case MPK_SUBSTRATE_COMMONS_HARVEST: MP_LAUNCH(commons, s.ch)
-    case MPK_SUBSTRATE_COINS: MP_LAUNCH(coins, s.co)
-    case MPK_SUBSTRATE_TERRITORY: MP_LAUNCH(territory, s.tr)
-    case MPK_SUBSTRATE_THE_MATRIX: MP_LAUNCH(matrix, s.mx)
-    case MPK_SUBSTRATE_COOP_MINING: MP_LAUNCH(coop, s.cm)
-    case MPK_SUBSTRATE_GIFT_REFINEMENTS: MP_LAUNCH(gift, s.gr)
-    case MPK_SUBSTRATE_COLLABORATIVE_COOKING: MP_LAUNCH(cook, s.cc)
-    case MPK_SUBSTRATE_EXTERNALITY_MUSHROOMS: MP_LAUNCH(mushroom, s.em)
+  const StepGeometry g = step_geometry(t, s, args.num_worlds);
+  const StepRows r = step_rows_of(l, args.out);
+#define MP_LAUNCH(kernel, ...) hipLaunchKernelGGL(kernel, g.grid, g.block, g.lds, stream, t, tables, args, __VA_ARGS__)
+#define MP_LEVEL(level, TablesT, SitesT, sub, member)                                              \
+  case sub: {                                                                                      \
+    const TablesT& tables = s.member;                                                              \
+    if (l.starts) MP_LAUNCH(k_many_starts_##level, m, r, l.state, l.hash, *l.starts);              \
+    else if (l.hash.row) MP_LAUNCH(k_step_hashes_##level, m, r, l.state, l.hash);                  \
+    else if (l.state.row) MP_LAUNCH(k_step_states_##level, m, r, l.state);                         \
+    else if (l.any_rows) MP_LAUNCH(k_step_rows_##level, m, r);                                     \
+    else MP_LAUNCH(k_step_many_##level, m);                                                        \
+    break;                                                                                         \
   }
+  switch (s.substrate) { MP_STEP_LEVELS(MP_LEVEL) }
+#undef MP_LEVEL
 #undef MP_LAUNCH
 }

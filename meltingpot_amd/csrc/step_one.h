@@ -4,8 +4,6 @@
 #ifndef MP_STEP_ONE_H_
 #define MP_STEP_ONE_H_
 
-constexpr int kWorldsPerGroup = 4;   // waves of a workgroup at most; they share the LDS tables
-
 template <class Tables, class Sites, bool kStarts = false>
 __device__ inline void run_one_world(const DevTables& t, const Tables& c, const StepArgs& args,
                                      int extra, const StartArgs* st = nullptr) {
