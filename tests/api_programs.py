@@ -7,7 +7,15 @@ arguments), deterministic, no GPU code.  `run_program(program, engine, model, tw
 to all of them; "engine" is only an interface here (reset / step / step_fields / step_many /
 save_worlds / load_worlds / snapshot / restore / bind / bind_ring / unbind / observe_host / dump /
 counters / fault_words / ring / _bound), which the model satisfies too — so the CPU suite runs the
-runner model against model, and against deliberately wrong models."""
+runner model against model, and against deliberately wrong models.
+
+A profile names the op `classes` its programs draw from.  The first set (COMMITTED) draws from the
+thirteen OP_CLASSES.  The STATE programs (STATE_COMMITTED) add masked steps, masked and stopping
+K-step calls with a persistent `stopped`, per-step state rows that become banks, registered episode
+starts whose `rows` are rewritten in place, and four read-only classes that draw, hash and check
+saved states; there the twin runs the other form of every new K-step call (see `_Side`).  The
+model does not state fresh=True starts: it says which worlds it speaks for (`ModelEngine.exact`),
+and the runner compares those."""
 import zlib
 
 import numpy as np
@@ -58,14 +66,108 @@ def _profiles():
 
 
 PROFILES = _profiles()
+for _p in PROFILES:
+  _p["classes"] = OP_CLASSES   # the op classes a profile's programs draw from
 # the committed set: (program seed, profile), chosen so that every ordered pair of distinct op
 # classes is adjacent somewhere in it (tests/test_api_programs_cpu.py prints the table)
 COMMITTED = [(1000 + i, p) for i, p in enumerate(PROFILES)]
 
+# ---- the state programs: masks, stops, episode starts and reads of saved states
+# mutating classes (unstop and starts_rows are no engine call: they rewrite the caller's tensors)
+NEW_MUTATING = ("step_active", "many_active", "many_until", "unstop", "step_many_states",
+                "starts_set", "starts_rows", "starts_clear")
+# read-only classes: the runner compares everything after every op, so "nothing of the engine's is
+# written" is checked by running them
+READ_ONLY = ("observe_rows", "observe_views", "hash", "check")
+MUTATING = OP_CLASSES + NEW_MUTATING
+STATE_CLASSES = MUTATING + READ_ONLY
+NEW_STEP_CLASSES = ("step_active", "many_active", "many_until", "step_many_states")
+ALL_STEP_CLASSES = STEP_CLASSES + NEW_STEP_CLASSES
+STATE_MIN_OPS, STATE_MAX_OPS, STATE_MAX_WORLD_STEPS = 70, 110, 260
+STATE_K = MANY_K + (65,)   # 65: the mask column of a lane crosses a 64-bit word
+STATES_K = (1, 2, 7)       # step_many_states: its K x N rows become a bank
+GAMMAS = (1.0, 0.97, 0.5)
+UNTILS = (("last",), ("reward",), ("last", "reward"))
+HASH_SPECS = (None, dict(planes=(0,)), dict(fields=("ax", "ay", "aori", "aalive")),
+              dict(planes=(0,), fields=("step", "done")))
+STATE_WORLD_COUNTS = (6, 23)   # remainders 2 and 3 of a workgroup of four worlds
+LONG_EPISODES = {"coins": 33, "territory__inside_out": 33}   # MAXFRAMES where rewards are rare
+# action weights over each level's ACTION_SET (1: forward; 7: zap / interact / mine; 8: clean / consume)
+ACTION_WEIGHTS = {
+    "clean_up": [1, 4, 1, 1, 1, 2, 2, 2, 4],
+    "coins": [1, 4, 1, 1, 1, 1, 1],
+    "collaborative_cooking__cramped": [1, 3, 1, 1, 1, 3, 3, 6],   # INTERACT_HEAVY
+    "commons_harvest__open": [1, 4, 1, 1, 1, 2, 2, 4],
+    "coop_mining": [1, 3, 1, 1, 1, 2, 2, 5],                      # MINE_HEAVY
+    "externality_mushrooms__dense": [1, 4, 1, 1, 1, 2, 2, 5],     # ZAP_HEAVY
+    "gift_refinements": [1, 4, 1, 1, 1, 2, 2, 5, 2],              # GIFT_HEAVY
+    "territory__inside_out": None,                                # (weight 4 on forward)
+    "prisoners_dilemma_in_the_matrix__repeated": [1, 4, 1, 1, 1, 2, 2, 4],
+}
+
+
+def _state_profiles():
+  out = []
+  for li, pack in enumerate(LEVEL_PACKS):
+    hdr = pack_lib.loads(E.load_pack(pack))["hdr"]
+    default_p = int(hdr[20]) or int(hdr[7])
+    fewer = "in_the_matrix" not in pack and pack != "coins"
+    for j, n in enumerate(STATE_WORLD_COUNTS):
+      pooled = j == li % 2
+      out.append(dict(
+          name=f"{pack}-states-n{n}", pack=pack, stock=False, rich=True, n=n, ring=0,
+          world_pool=8 if pooled else 1, auto_reset=True,
+          unfused=True if j == (li // 2) % 2 else None,
+          num_players=max(1, default_p - 1) if fewer and j == (li // 4) % 2 else 0,
+          views=(E.OBS_WORLD_RGB, E.OBS_LAYER) if pooled else (E.OBS_RGB,),
+          frames=LONG_EPISODES.get(pack, EPISODE_FRAMES), classes=STATE_CLASSES))
+  out.append(dict(name="stock_clean_up-states-n23", pack="clean_up", stock=True, rich=False, n=23, ring=0,
+                  world_pool=1, auto_reset=True, unfused=None, num_players=0, views=(E.OBS_WORLD_RGB,),
+                  frames=0, classes=STATE_CLASSES))
+  return out
+
+
+STATE_PROFILES = _state_profiles()
+# (program seed, profile): seeds searched on the model alone so that the conditions of
+# tests/test_api_programs_cpu.py hold (the search is tests/tools/search_state_programs.py)
+STATE_SEEDS = [2001, 2005, 2001, 2007, 2005, 2003, 2000, 2002, 2001, 2003, 2000, 2011, 2001, 2003, 2029, 2019,
+               2003, 2000, 2000]
+STATE_COMMITTED = list(zip(STATE_SEEDS, STATE_PROFILES))
+
+
+def rich_pack(name, raw):
+  """The level's variant that pays often, where the parity tests have one; else the pack itself."""
+  if name == "clean_up":
+    return util.fertile_clean_up(raw)
+  if name == "collaborative_cooking__cramped":
+    from test_oracle_cook_cpu import stocked
+    return stocked(raw)
+  if name == "coop_mining":
+    from test_oracle_coop_cpu import rich
+    return rich(raw)
+  if name == "gift_refinements":
+    from test_oracle_gift_cpu import rich
+    return rich(raw)
+  if name == "externality_mushrooms__dense":
+    from test_oracle_mushroom_cpu import lush
+    return lush(raw)
+  if name == "prisoners_dilemma_in_the_matrix__repeated":
+    return util.matrix_variant(raw, taste=[(0, 1.0, 0.5)], unready=-1.0)
+  return raw
+
+
+_PACKS = {}
+
 
 def profile_pack(profile):
-  raw = E.load_pack(profile["pack"])
-  return raw if profile["stock"] else util.patch_pack(raw, MAXFRAMES=EPISODE_FRAMES)
+  if profile["name"] not in _PACKS:
+    raw = E.load_pack(profile["pack"])
+    if not profile["stock"]:
+      if profile.get("rich"):
+        raw = rich_pack(profile["pack"], raw)
+      raw = util.patch_pack(raw, MAXFRAMES=profile.get("frames", EPISODE_FRAMES))
+    _PACKS[profile["name"]] = raw
+  return _PACKS[profile["name"]]
 
 
 def bound_scalars(profile):
@@ -105,20 +207,93 @@ def _fields(rng, g, shape):
   return rng.integers(g["lo"], g["hi"] + 1, size=tuple(shape) + (g["A"],), dtype=np.int32)
 
 
-def _attempt(rng, profile, g):
-  N, P = g["N"], g["P"]
-  length = int(rng.integers(MIN_OPS, MAX_OPS + 1))
-  ops = [dict(op="reset_all")]
-  budget, banks, have_snap, host_run_done = MAX_WORLD_STEPS, [], False, False
-  bound = set(profile["views"])
-  pooled = int(rng.choice(list(E.OBS_RGB_POOL.values())))
-  agent_kinds = (E.OBS_RGB, pooled)
-  while len(ops) < length:
-    allowed = [c for c in OP_CLASSES if c != ops[-1]["op"] and
-               not (c == "load" and not banks) and not (c == "restore" and not have_snap) and
-               not (c in STEP_CLASSES and budget < 1) and
-               not (c == "step_host" and not host_run_done and (budget < HOST_RUN or len(ops) + HOST_RUN > length))]
-    c = str(rng.choice(allowed))
+class _Gen:
+  """The state of one draw of a program: the ops so far and what the next op may be."""
+
+  def __init__(self, rng, profile, g, length, budget):
+    self.rng, self.profile, self.g, self.length, self.budget = rng, profile, g, length, budget
+    self.ops = [dict(op="reset_all")]
+    self.banks, self.have_snap, self.host_run_done = [], False, False
+    self.bound = set(profile["views"])
+    self.pooled = int(rng.choice(list(E.OBS_RGB_POOL.values())))
+    self.agent_kinds = (E.OBS_RGB, self.pooled)
+    self.registered = None     # the rows of the bank a registration names
+    self.rows_of = None        # ... of the last `rows` tensor handed out (it outlives a clear)
+    self.wide_reads = 0
+    w = ACTION_WEIGHTS.get(profile["pack"]) if profile.get("rich") or "states" in profile["name"] else None
+    if "states" in profile["name"] and w is None:
+      w = [1, 4] + [1] * (g["nact"] - 2)
+    self.weights = None if w is None else np.asarray(w, np.float64) / sum(w)
+    assert self.weights is None or len(self.weights) == g["nact"], profile["name"]
+
+  def blocked(self, c):
+    ops, budget, length = self.ops, self.budget, self.length
+    return (c == ops[-1]["op"] or (c in ("load", "starts_set", "observe_rows", "observe_views", "check") and not self.banks) or
+            (c == "restore" and not self.have_snap) or (c in ALL_STEP_CLASSES and budget < 1) or
+            (c == "starts_clear" and self.registered is None) or (c == "starts_rows" and self.rows_of is None) or
+            (c == "step_host" and not self.host_run_done and (budget < HOST_RUN or len(ops) + HOST_RUN > length)))
+
+  def ids(self, shape, bad=0.0):
+    if self.weights is None:
+      return _ids(self.rng, self.g, shape, bad)
+    rng, nact = self.rng, self.g["nact"]
+    a = rng.choice(nact, size=shape, p=self.weights).astype(np.int32)
+    if bad:
+      out = rng.choice(np.array([-1, nact, nact + 3, -5, 100], np.int32), size=shape)
+      a = np.where(rng.random(shape) < bad, out, a).astype(np.int32)
+    return a
+
+  def _many(self, c, ks, weights):
+    """The action block of a K-step op: K, plain / repeat / slice, ids or raw fields."""
+    rng, g = self.rng, self.g
+    N, P = g["N"], g["P"]
+    ks = [k for k in ks if k <= self.budget]
+    p = np.array(weights[:len(ks)], np.float64)
+    K = int(rng.choice(ks, p=p / p.sum()))
+    form = str(rng.choice(["plain", "repeat", "slice"], p=[0.5, 0.25, 0.25]))
+    fields = bool(rng.random() < 0.25)
+    lead = () if form == "repeat" else (K,)
+    wide = N + 3 if form == "slice" else N
+    acts = _fields(rng, g, lead + (wide, P)) if fields else self.ids(lead + (wide, P), bad=0.01)
+    self.budget -= K
+    return dict(op=c, K=K, form=form, fields=fields, actions=acts, lo=int(rng.integers(0, 4)) if form == "slice" else 0)
+
+  def _row_kinds(self):
+    rng, kinds = self.rng, self.g["row_kinds"]
+    pick = rng.random(len(kinds)) < 0.5
+    pick[rng.integers(len(pick))] = True
+    return tuple(int(k) for k, p in zip(kinds, pick) if p)
+
+  def _mask(self, op, forms, p):
+    """Adds a mask of one of `forms` to the K-step op."""
+    rng, N, K = self.rng, self.g["N"], op["K"]
+    form = str(rng.choice(forms, p=np.array(p) / sum(p)))
+    op.update(mask_form=form, mlo=0, mask_dtype=str(rng.choice(["uint8", "bool"])))
+    if form == "kn":
+      op["mask"] = (rng.random((K, N)) < 0.6).astype(np.uint8)
+    elif form == "n":
+      op["mask"] = (rng.random(N) < 0.6).astype(np.uint8)
+    elif form == "prefix":
+      lengths = rng.integers(0, K + 1, size=N)
+      op["mask"] = (np.arange(K)[:, None] < lengths[None]).astype(np.uint8)
+    elif form == "slice":
+      op["mask"] = (rng.random((K, N + 3)) < 0.6).astype(np.uint8)
+      op["mlo"] = int(rng.integers(0, 4))
+    elif form == "zeros":
+      op["mask"] = np.zeros((K, N), np.uint8)
+    else:
+      op["mask"] = None
+
+  def _pick_rows(self, count, rows_in_bank):
+    """`count` bank rows with repeats, out of at most three distinct ones (each distinct row is
+    replayed on an oracle once)."""
+    rng = self.rng
+    distinct = rng.choice(rows_in_bank, size=min(3, rows_in_bank), replace=False)
+    return rng.choice(distinct, size=count).astype(np.int32)
+
+  def draw(self, c):
+    rng, g, ops = self.rng, self.g, self.ops
+    N, P = g["N"], g["P"]
     if c == "reset_all":
       ops.append(dict(op=c))
     elif c in ("masked_reset", "masked_reseed"):
@@ -129,65 +304,186 @@ def _attempt(rng, profile, g):
         op["seeds"] = rng.integers(1, 1 << 62, size=N, dtype=np.uint64)
       ops.append(op)
     elif c == "step_dev":
-      ops.append(dict(op=c, actions=_ids(rng, g, (N, P), bad=0.01)))
-      budget -= 1
+      ops.append(dict(op=c, actions=self.ids((N, P), bad=0.01)))
+      self.budget -= 1
     elif c == "step_host":
-      run = 1 if host_run_done else HOST_RUN + int(rng.integers(0, 2))
-      run = min(run, budget, length - len(ops))
+      run = 1 if self.host_run_done else HOST_RUN + int(rng.integers(0, 2))
+      run = min(run, self.budget, self.length - len(ops))
       for _ in range(run):
-        ops.append(dict(op=c, actions=_ids(rng, g, (N, P))))
-      budget -= run
-      host_run_done = host_run_done or run >= HOST_RUN
+        ops.append(dict(op=c, actions=self.ids((N, P))))
+      self.budget -= run
+      self.host_run_done = self.host_run_done or run >= HOST_RUN
     elif c == "step_fields":
       ops.append(dict(op=c, fields=_fields(rng, g, (N, P)), host=bool(rng.integers(2))))
-      budget -= 1
+      self.budget -= 1
     elif c in ("step_many", "step_many_rows"):
-      ks = [k for k in MANY_K if k <= budget]
-      K = int(rng.choice(ks, p=np.array([3, 3, 3, 1][:len(ks)]) / sum([3, 3, 3, 1][:len(ks)])))
-      form = str(rng.choice(["plain", "repeat", "slice"], p=[0.5, 0.25, 0.25]))
-      fields = bool(rng.random() < 0.25)
-      lead = () if form == "repeat" else (K,)
-      wide = N + 3 if form == "slice" else N
-      acts = _fields(rng, g, lead + (wide, P)) if fields else _ids(rng, g, lead + (wide, P), bad=0.01)
-      op = dict(op=c, K=K, form=form, fields=fields, actions=acts, lo=int(rng.integers(0, 4)) if form == "slice" else 0)
+      op = self._many(c, MANY_K, [3, 3, 3, 1])
       if c == "step_many_rows":
-        pick = rng.random(len(g["row_kinds"])) < 0.5
-        pick[rng.integers(len(pick))] = True
-        op["observations"] = tuple(int(k) for k, p in zip(g["row_kinds"], pick) if p)
+        op["observations"] = self._row_kinds()
       ops.append(op)
-      budget -= K
     elif c == "save":
       m = int(rng.integers(1, N + 1))
       ops.append(dict(op=c, worlds=rng.choice(N, size=m, replace=False).astype(np.int32)))
-      banks.append(m)
+      self.banks.append(m)
     elif c == "load":
-      b = int(rng.integers(len(banks)))
-      src = rng.integers(0, banks[b], size=N).astype(np.int32)   # (with duplicates)
+      b = int(rng.integers(len(self.banks)))
+      src = rng.integers(0, self.banks[b], size=N).astype(np.int32)   # (with duplicates)
       src[rng.random(N) < 0.3] = -1
       i, j = rng.choice(N, size=2, replace=False)
-      src[i], src[j] = -1, int(rng.integers(banks[b]))
+      src[i], src[j] = -1, int(rng.integers(self.banks[b]))
       ops.append(dict(op=c, bank=b, src=src))
     elif c == "snapshot":
       ops.append(dict(op=c))
-      have_snap = True
+      self.have_snap = True
     elif c == "restore":
       ops.append(dict(op=c))
     elif c == "rebind":
-      kind = int(rng.choice([E.OBS_RGB, pooled, E.OBS_WORLD_RGB, E.OBS_LAYER]))
-      other = [k for k in agent_kinds if k != kind and k in bound]
-      if kind in bound:
+      kind = int(rng.choice([E.OBS_RGB, self.pooled, E.OBS_WORLD_RGB, E.OBS_LAYER]))
+      other = [k for k in self.agent_kinds if k != kind and k in self.bound]
+      if kind in self.bound:
         bind = False
-      elif kind in agent_kinds and other:   # one per-agent view at a time: the other one leaves
+      elif kind in self.agent_kinds and other:   # one per-agent view at a time: the other one leaves
         kind, bind = other[0], False
       else:
         bind = True
-      (bound.add if bind else bound.discard)(kind)
+      (self.bound.add if bind else self.bound.discard)(kind)
       ops.append(dict(op=c, kind=kind, bind=bind))
-  return ops
+    # ---- the state classes
+    elif c == "step_active":
+      mask = (rng.random(N) < 0.6).astype(np.uint8)
+      host = bool(rng.integers(2))
+      ops.append(dict(op=c, actions=self.ids((N, P), bad=0.0 if host else 0.01), host=host, mask=mask,
+                      mask_dtype=str(rng.choice(["uint8", "bool", "list"]))))
+      self.budget -= 1
+    elif c == "many_active":
+      op = self._many(c, STATE_K, [3, 3, 3, 2, 1])
+      self._mask(op, ["kn", "n", "prefix", "slice", "zeros"], [7, 4, 4, 4, 1])
+      op["observations"] = self._row_kinds() if rng.random() < 0.5 else None
+      ops.append(op)
+    elif c == "many_until":
+      op = self._many(c, STATE_K, [1, 2, 3, 3, 1])
+      self._mask(op, ["none", "kn", "n", "prefix", "slice"], [4, 3, 1, 2, 2])
+      op["observations"] = self._row_kinds() if rng.random() < 0.3 else None
+      op["until"] = UNTILS[int(rng.integers(len(UNTILS)))]
+      op["returns"] = bool(rng.random() < 0.7)
+      op["gamma"] = float(rng.choice(GAMMAS)) if op["returns"] else 1.0
+      op["use_stopped"] = bool(rng.random() < 0.6)
+      ops.append(op)
+    elif c == "unstop":
+      mask = (rng.random(N) < 0.5).astype(np.uint8)
+      mask[rng.integers(N)] = 1
+      ops.append(dict(op=c, mask=mask))
+    elif c == "step_many_states":
+      op = self._many(c, STATES_K, [2, 3, 3])
+      self._mask(op, ["none", "kn", "prefix"], [2, 2, 1])
+      ops.append(op)
+      self.banks.append(op["K"] * N)
+    elif c == "starts_set":
+      b = int(rng.integers(len(self.banks)))
+      rows = self._start_rows(self.banks[b])
+      # finished_world: where the bank holds a row saved from a finished episode, that world takes it
+      # (the runner asks the model which rows those are: `resolve`)
+      ops.append(dict(op=c, bank=b, rows=rows, fresh=bool(rng.random() < 0.2),
+                      finished_world=int(rng.integers(N))))
+      self.registered = self.rows_of = self.banks[b]
+    elif c == "starts_rows":
+      ops.append(dict(op=c, rows=self._start_rows(self.rows_of)))
+    elif c == "starts_clear":
+      ops.append(dict(op=c))
+      self.registered = None
+    elif c == "observe_rows":
+      b = int(rng.integers(len(self.banks)))
+      kinds = list(E.PIXEL_KINDS) + list(g["row_kinds"])
+      wide = self.wide_reads == 0   # one read of a program has more rows than worlds
+      self.wide_reads += 1
+      count = N + 2 if wide else int(rng.integers(1, min(N, 6) + 1))
+      ops.append(dict(op=c, bank=b, kind=int(rng.choice(kinds)), rows=self._pick_rows(count, self.banks[b])))
+    elif c == "observe_views":
+      b = int(rng.integers(len(self.banks)))
+      kinds = [k for k in E.PIXEL_KINDS if k != E.OBS_WORLD_RGB] + list(g["row_kinds"])
+      count = int(rng.integers(1, min(N, 6) + 1))
+      ops.append(dict(op=c, bank=b, kind=int(rng.choice(kinds)), rows=self._pick_rows(count, self.banks[b]),
+                      players=rng.integers(0, P, size=count).astype(np.int32), offset=int(rng.integers(0, 16))))
+    elif c == "hash":
+      b = int(rng.integers(-1, len(self.banks)))   # -1: hash_worlds
+      rows = None if b < 0 or rng.random() < 0.3 else self._pick_rows(int(rng.integers(1, 9)), self.banks[b])
+      ops.append(dict(op=c, bank=b, rows=rows, spec=int(rng.integers(len(HASH_SPECS)))))
+    elif c == "check":
+      b = int(rng.integers(len(self.banks)))
+      ops.append(dict(op=c, bank=b, row=int(rng.integers(self.banks[b])), player=int(rng.integers(P)),
+                      field=str(rng.choice(["orientation", "avatar_x"]))))
+    else:
+      raise ValueError(c)
+
+  def _start_rows(self, rows_in_bank):
+    """`rows` of a registration: valid indices and -1s, several worlds on one row."""
+    rng, N = self.rng, self.g["N"]
+    rows = self._pick_rows(N, rows_in_bank)
+    rows[rng.random(N) < 0.3] = -1
+    i, j, k = rng.choice(N, size=3, replace=False)
+    rows[i] = rows[j] = int(rng.integers(rows_in_bank))
+    rows[k] = -1
+    return rows.astype(np.int32)
+
+
+def _attempt(rng, profile, g):
+  length = int(rng.integers(MIN_OPS, MAX_OPS + 1))
+  gen = _Gen(rng, profile, g, length, MAX_WORLD_STEPS)
+  while len(gen.ops) < length:
+    allowed = [c for c in OP_CLASSES if not gen.blocked(c)]
+    gen.draw(str(rng.choice(allowed)))
+  return gen.ops
+
+
+def required_pairs():
+  """The adjacencies the state programs owe: every ordered pair of distinct mutating classes with a
+  new class in it, and every read-only class behind every new mutating class."""
+  pairs = [(a, b) for a in MUTATING for b in MUTATING if a != b and (a in NEW_MUTATING or b in NEW_MUTATING)]
+  return pairs + [(a, r) for a in NEW_MUTATING for r in READ_ONLY]
+
+
+def assigned_pairs(profile):
+  """The share of `required_pairs` that the program of `profile` must hold: the generator steers
+  its draws toward them, deterministically."""
+  i = [p["name"] for p in STATE_PROFILES].index(profile["name"])
+  return required_pairs()[i::len(STATE_PROFILES)]
+
+
+def _attempt_states(rng, profile, g):
+  """A program over STATE_CLASSES; None if this draw misses a class, a pair or the host run."""
+  gen = _Gen(rng, profile, g, STATE_MAX_OPS, STATE_MAX_WORLD_STEPS)
+  todo = set(assigned_pairs(profile))
+  classes = profile["classes"]
+  while len(gen.ops) < STATE_MAX_OPS:
+    seen = {op["op"] for op in gen.ops}
+    if len(gen.ops) >= STATE_MIN_OPS and not todo and seen == set(classes) and gen.host_run_done:
+      break
+    allowed = [c for c in classes if not gen.blocked(c)]
+    prev = gen.ops[-1]["op"]
+    closing = [c for c in allowed if (prev, c) in todo]      # an owed pair that this draw completes
+    opening = [c for c in allowed if any(a == c for a, _ in todo)]
+    missing = [c for c in allowed if c not in seen]
+    if closing:
+      c = str(rng.choice(closing))
+    elif opening and rng.random() < 0.6:
+      c = str(rng.choice(opening))
+    elif missing and rng.random() < 0.5:
+      c = str(rng.choice(missing))
+    else:
+      c = str(rng.choice(allowed))
+    before = len(gen.ops)
+    gen.draw(c)
+    todo.discard((prev, c))
+    for a, b in zip(gen.ops[before:-1], gen.ops[before + 1:]):   # (a run of host steps)
+      todo.discard((a["op"], b["op"]))
+  seen = {op["op"] for op in gen.ops}
+  if todo or seen != set(classes) or not gen.host_run_done:
+    return None
+  return gen.ops
 
 
 def world_steps(program):
-  return sum(op.get("K", 1) for op in program if op["op"] in STEP_CLASSES)
+  return sum(op.get("K", 1) for op in program if op["op"] in ALL_STEP_CLASSES)
 
 
 def longest_host_run(program):
@@ -199,30 +495,33 @@ def longest_host_run(program):
 
 
 def make_program(seed, profile):
-  """The program of (seed, profile): deterministic; the first draw that holds every op class."""
+  """The program of (seed, profile): deterministic; the first draw that holds every op class of
+  the profile (and, for a state profile, the adjacencies it owes)."""
   g = _geometry(profile)
+  states = set(profile["classes"]) != set(OP_CLASSES)
   for attempt in range(1000):
     rng = np.random.default_rng([int(seed), zlib.crc32(profile["name"].encode()), attempt])
-    ops = _attempt(rng, profile, g)
-    if {op["op"] for op in ops} == set(OP_CLASSES) and longest_host_run(ops) >= HOST_RUN:
+    ops = _attempt_states(rng, profile, g) if states else _attempt(rng, profile, g)
+    if ops is not None and {op["op"] for op in ops} == set(profile["classes"]) and longest_host_run(ops) >= HOST_RUN:
       prog = Program(ops)
       prog.seed, prog.profile = int(seed), profile
       return prog
   raise AssertionError(f"no program for seed {seed}, profile {profile['name']}")
 
 
-def pair_counts(programs):
+def pair_counts(programs, classes=OP_CLASSES):
   """[from, to] counts of adjacent op classes over `programs`."""
-  idx = {c: i for i, c in enumerate(OP_CLASSES)}
-  table = np.zeros((len(OP_CLASSES),) * 2, np.int64)
+  idx = {c: i for i, c in enumerate(classes)}
+  table = np.zeros((len(classes),) * 2, np.int64)
   for prog in programs:
     for a, b in zip(prog[:-1], prog[1:]):
       table[idx[a["op"]], idx[b["op"]]] += 1
   return table
 
 
-def format_pair_table(table):
-  short = [c.replace("step_", "s_").replace("masked_", "m_") for c in OP_CLASSES]
+def format_pair_table(table, classes=OP_CLASSES):
+  short = [c.replace("step_", "s_").replace("masked_", "m_").replace("observe_", "o_").replace("starts_", "st_")
+           for c in classes]
   lines = ["| from \\ to | " + " | ".join(short) + " |", "|---|" + "---|" * len(short)]
   for i, c in enumerate(short):
     lines.append(f"| {c} | " + " | ".join("." if i == j else str(int(v)) for j, v in enumerate(table[i])) + " |")
@@ -293,14 +592,67 @@ def first_difference(kind, got, want, leading=("world",)):
   return f"{head}, index {at[len(leading):].tolist()}: {got[tuple(at)]!r} != {want[tuple(at)]!r}"
 
 
-class _Side:
-  """One engine of a run and what the program keeps for it."""
+def stop_bits(until):
+  return sum(E.STOP_NAMES[n] for n in (until or ()))
 
-  def __init__(self, eng):
+
+def op_blocks(op, n):
+  """The K action blocks [N, P(, A)] of a K-step op, on the host."""
+  a = op["actions"]
+  if op["form"] == "repeat":
+    return [a] * op["K"]
+  if op["form"] == "slice":
+    a = a[:, op["lo"]:op["lo"] + n]
+  return [a[k] for k in range(op["K"])]
+
+
+def op_mask(op, n):
+  """bool [K, N] of a K-step op's mask, or None."""
+  m = op.get("mask")
+  if m is None:
+    return None
+  if op["mask_form"] == "slice":
+    m = m[:, op["mlo"]:op["mlo"] + n]
+  return np.broadcast_to(m != 0, (op["K"], n))
+
+
+def resolve(op, model_side):
+  """The op as every side runs it.  A `starts_set` names a world that takes a row saved from a
+  finished episode where the bank has one: which rows those are is the model's to say."""
+  if op["op"] != "starts_set":
+    return op
+  finished = [i for i, row in enumerate(model_side.banks[op["bank"]]) if row["finished"]]
+  if not finished:
+    return op
+  rows = op["rows"].copy()
+  rows[op["finished_world"]] = finished[0]
+  return dict(op, rows=rows)
+
+
+class _Side:
+  """One engine of a run and what the program keeps for it: its banks, its snapshot, the persistent
+  `stopped` bytes and the `rows` of its registration.  The TWIN runs the other form of every
+  K-step op of the state classes — the host loop of step(A[k], active=m_k) with `stopped` kept on
+  the host — and never registers episode starts: after each of its steps it performs the defining
+  identity, load_worlds of the row of each world that was done and ran (for fresh=True the
+  gather-and-edit of seed, episode and orders_step)."""
+
+  def __init__(self, eng, twin=False):
     self.eng = eng
+    self.twin = twin
+    self.real = hasattr(eng, "_L")   # an engine.Engine (device tensors), not a model
     self.banks = []
     self.snap = None
-    self.rows = None     # what the last step_many returned
+    self.rows = None       # what the last step_many returned
+    self.read = None       # what the last read-only op returned
+    self.reg = None        # the registration: {"bank", "fresh"}
+    self.start_rows = None
+    n = eng.N
+    if self.real and not twin:
+      import torch
+      self.stopped = torch.zeros(n, dtype=torch.uint8, device=eng.device)
+    else:
+      self.stopped = np.zeros(n, np.uint8)
 
   def dev(self, a):
     if hasattr(self.eng, "to_device"):
@@ -308,29 +660,165 @@ class _Side:
     import torch
     return torch.from_numpy(np.ascontiguousarray(a)).to(self.eng.device)
 
+  # ---- the twin's single step, with the identity of a registration
+  def _tail(self, name):
+    lay = self.eng.state_layout()
+    off, elem, count = lay.fields[name]
+    raw = self.eng.save_worlds()[:, lay.grid_pad + off:lay.grid_pad + off + elem * count].cpu().numpy()
+    return np.ascontiguousarray(raw).view({1: np.uint8, 4: np.int32, 8: np.uint64}[elem])
+
+  def _twin_step(self, block, m, fields):
+    """One step of the twin: `block` [N, P(, A)] on the host, `m` bool [N] or None."""
+    eng = self.eng
+    done = self._tail("done")[:, 0] != 0 if self.reg else None
+    if m is None:
+      (eng.step_fields if fields else eng.step)(self.dev(block))
+    elif fields:
+      eng.step_many(self.dev(block[None]), fields=True, keep=(), active=self.dev(m.astype(np.uint8)))
+    else:
+      eng.step(self.dev(block), active=self.dev(m.astype(np.uint8)))
+    if self.reg:
+      took = done & (self.start_rows >= 0)
+      if m is not None:
+        took &= m
+      if took.any():
+        self._identity(took)
+
+  def _identity(self, took):
+    import torch
+    eng, bank, rows = self.eng, self.banks[self.reg["bank"]], self.start_rows
+    if not self.reg["fresh"]:
+      eng.load_worlds(bank, np.where(took, rows, -1).astype(np.int32))
+      return
+    from meltingpot_amd import substrate
+    lay = eng.state_layout()
+    own = substrate.StateFields(eng.save_worlds(), lay)   # (the twin's own reset has just set episode + 1)
+    gathered = bank[torch.from_numpy(np.where(took, rows, 0)).to(eng.device).long()].clone()
+    f = substrate.StateFields(gathered, lay)
+    f.seed[:] = own.seed
+    f.episode[:] = own.episode
+    f.orders_step[:] = 0
+    eng.load_worlds(gathered, np.where(took, np.arange(eng.N), -1).astype(np.int32))
+
+  def _twin_loop(self, op):
+    """A K-step op as the host loop of single steps; returns ran / stopped / returns / states /
+    hashes where the op asks for them."""
+    eng, c = self.eng, op["op"]
+    n = eng.N
+    blocks, M = op_blocks(op, n), op_mask(op, n)
+    stopping = c == "many_until"
+    stop = stop_bits(op.get("until"))
+    states = c == "step_many_states"
+    if stopping:
+      stopped = self.stopped if op["use_stopped"] else np.zeros(n, np.uint8)
+      ran, ret, g = np.zeros(n, np.int32), np.zeros((n, eng.P), np.float64), np.ones(n, np.float64)
+    rows = {"states": [], "hashes": []} if states else {}
+    for k, block in enumerate(blocks):
+      m = None if M is None else M[k].copy()
+      if stopping:
+        m = (stopped == 0) if m is None else m & (stopped == 0)
+      self._twin_step(block, m, op["fields"])
+      if stopping:
+        reward, kind = eng.observe_host(E.OBS_REWARD), eng.observe_host(E.OBS_STEP_TYPE)
+        for w in np.nonzero(m)[0]:
+          ran[w] += 1
+          ret[w] = ret[w] + g[w] * reward[w]
+          g[w] = g[w] * np.float64(op["gamma"])
+          reason = ((E.MP_STOP_LAST if (stop & E.MP_STOP_LAST) and kind[w] == 2 else 0) |
+                    (E.MP_STOP_REWARD if (stop & E.MP_STOP_REWARD) and (reward[w] != 0).any() else 0))
+          if reason:
+            stopped[w] = reason
+      if states:
+        rows["states"].append(eng.save_worlds().clone())
+        rows["hashes"].append(_host(eng.hash_worlds()))
+    if stopping:
+      rows.update(stopped=stopped.copy(), ran=ran)
+      if op["returns"]:
+        rows["returns"] = ret
+    return rows
+
+  # ---- the ops
+  def _mask_arg(self, op):
+    m = op["mask"]
+    if op["mask_dtype"] == "list":
+      return (m != 0).tolist()
+    d = self.dev(m if op["mask_dtype"] == "uint8" else m != 0)
+    if op.get("mask_form") == "slice":
+      d = d[:, op["mlo"]:op["mlo"] + self.eng.N]
+    return d
+
+  def _many(self, op):
+    """A K-step op of any class, as the engine's own K-step call."""
+    eng, c = self.eng, op["op"]
+    acts = self.dev(op["actions"])
+    if op["form"] == "slice":   # a column slice of a wider tensor: non-contiguous along K only
+      acts = acts[:, op["lo"]:op["lo"] + eng.N]
+    kw = dict(fields=op["fields"], repeat=op["K"] if op["form"] == "repeat" else None)
+    if op.get("observations") is not None:
+      kw.update(events=True, observations=op["observations"])
+    if op.get("mask") is not None:
+      kw["active"] = self._mask_arg(op)
+    if c == "many_until":
+      kw.update(until=op["until"], returns=op["returns"], gamma=op["gamma"])
+      if op["use_stopped"]:
+        kw["stopped"] = self.stopped
+    if c == "step_many_states":
+      kw.update(states=True, hashes=True)
+    res = dict(eng.step_many(acts, **kw))
+    if c == "many_until" and op["use_stopped"] and res["stopped"] is not self.stopped:
+      raise Mismatch("step_many did not hand back the caller's `stopped`")
+    return res
+
   def apply(self, op, ring, views=True):
     eng, c = self.eng, op["op"]
-    self.rows = None
+    self.rows = self.read = None
+    looped = self.twin and (self.reg is not None or c in NEW_STEP_CLASSES)
     if c == "reset_all":
       eng.reset()
     elif c == "masked_reset":
       eng.reset(None, op["mask"])
     elif c == "masked_reseed":
       eng.reset(op["seeds"], op["mask"])
+    elif c in ("step_dev", "step_host") and looped:
+      self._twin_step(op["actions"], None, False)
+    elif c == "step_fields" and looped:
+      self._twin_step(op["fields"], None, True)
     elif c == "step_dev":
       eng.step(self.dev(op["actions"]))
     elif c == "step_host":
       eng.step(op["actions"])
     elif c == "step_fields":
       eng.step_fields(op["fields"] if op["host"] else self.dev(op["fields"]))
-    elif c in ("step_many", "step_many_rows"):
-      acts = self.dev(op["actions"])
-      if op["form"] == "slice":   # a column slice of a wider tensor: non-contiguous along K only
-        acts = acts[:, op["lo"]:op["lo"] + eng.N]
-      kw = dict(fields=op["fields"], repeat=op["K"] if op["form"] == "repeat" else None)
-      if c == "step_many_rows":
-        kw.update(events=True, observations=op["observations"])
-      self.rows = {k: _host(v) for k, v in eng.step_many(acts, **kw).items()}
+    elif c == "step_active" and looped:
+      self._twin_step(op["actions"], op["mask"] != 0, False)
+    elif c == "step_active":
+      eng.step(op["actions"] if op["host"] else self.dev(op["actions"]), active=self._mask_arg(op))
+    elif c in ("step_many", "step_many_rows", "many_active", "many_until", "step_many_states"):
+      res = self._twin_loop(op) if looped else self._many(op)
+      if c == "step_many_states":
+        states = res.pop("states")
+        if self.real:
+          import torch
+          states = (torch.stack(states) if isinstance(states, list) else states).reshape(op["K"] * eng.N, -1)
+        else:
+          states = [row for step in states for row in step]
+        self.banks.append(states)
+      self.rows = {k: np.array(_host(v)) for k, v in res.items()}   # (copies: `stopped` is the caller's)
+    elif c == "unstop":
+      self.stopped *= self.dev(1 - op["mask"]) if self.real and not self.twin else (1 - op["mask"])
+    elif c == "starts_set":
+      self.reg = dict(bank=op["bank"], fresh=op["fresh"])
+      if self.twin:
+        self.start_rows = op["rows"].copy()
+      else:
+        self.start_rows = self.dev(op["rows"].copy())
+        eng.set_episode_starts(self.banks[op["bank"]], self.start_rows, fresh=op["fresh"])
+    elif c == "starts_rows":   # the caller's tensor, rewritten in place: no engine call
+      self.start_rows[:] = op["rows"] if self.twin else self.dev(op["rows"])
+    elif c == "starts_clear":
+      self.reg = None
+      if not self.twin:
+        eng.clear_episode_starts()
     elif c == "save":
       self.banks.append(eng.save_worlds(op["worlds"]))
     elif c == "load":
@@ -342,8 +830,57 @@ class _Side:
     elif c == "rebind":
       if views:
         bind_view(eng, op["kind"], ring) if op["bind"] else eng.unbind(op["kind"])
+    elif c == "observe_rows":
+      self.read = _host(eng.observe_states(self.banks[op["bank"]], op["kind"], rows=self._ints(op["rows"])))
+    elif c == "observe_views":
+      self.read = self._observe_views(op)
+    elif c == "hash":
+      spec = HASH_SPECS[op["spec"]] or {}
+      if op["bank"] < 0:
+        self.read = _host(eng.hash_worlds(**spec))
+      else:
+        rows = None if op["rows"] is None else self._ints(op["rows"])
+        self.read = _host(eng.hash_states(self.banks[op["bank"]], rows, **spec))
+    elif c == "check":
+      self.read = self._check(op) if self.real and not self.twin else None
     else:
       raise ValueError(c)
+
+  def _ints(self, a):
+    return self.dev(np.asarray(a, np.int32))
+
+  def _observe_views(self, op):
+    eng = self.eng
+    bank, kind = self.banks[op["bank"]], op["kind"]
+    if not self.real or kind not in E.PIXEL_KINDS:
+      return _host(eng.observe_views(bank, kind, self._ints(op["players"]), rows=self._ints(op["rows"])))
+    # a pixel kind's `out` may start on any byte: inside a wider buffer, with guard bytes around it
+    import torch
+    shape = (len(op["rows"]),) + tuple(int(d) for d in eng.shapes[kind][0][2:])
+    size, lo = int(np.prod(shape)), op["offset"]
+    wide = torch.full((size + 48,), 0xA5, dtype=torch.uint8, device=eng.device)
+    out = wide[lo:lo + size].view(shape)
+    eng.observe_views(bank, kind, self._ints(op["players"]), rows=self._ints(op["rows"]), out=out)
+    guard = wide.cpu().numpy()
+    if (guard[:lo] != 0xA5).any() or (guard[lo + size:] != 0xA5).any():
+      raise Mismatch(f"observe_views kind {kind}: a guard byte around `out` (offset {lo}) was written")
+    return guard[lo:lo + size].reshape(shape).copy()
+
+  def _check(self, op):
+    """(verdicts of the whole bank, device verdict of a broken clone of one row, the host's)."""
+    from meltingpot_amd import substrate
+    eng = self.eng
+    bank = self.banks[op["bank"]]
+    verdicts = _host(eng.check_states(bank))
+    clone = bank[op["row"]:op["row"] + 1].clone()
+    f = substrate.StateFields(clone, eng.state_layout())
+    alive = f.alive[0].cpu().numpy() != 0
+    if op["field"] == "avatar_x" and alive.any():   # a living avatar off the map
+      p = int(np.nonzero(alive)[0][op["player"] % int(alive.sum())])
+      f.avatar_x[0, p] = 255
+    else:
+      f.orientation[0, op["player"]] = 7
+    return verdicts, _host(eng.check_states(clone)), clone.cpu().numpy()
 
 
 def _check_faults(eng, where):
@@ -352,39 +889,112 @@ def _check_faults(eng, where):
     raise FaultStop(f"{where}: fault words {words.tolist()}; nothing more is launched")
 
 
-def compare_with_model(eng, model, rows, model_rows, fail):
-  """Everything the model speaks about, engine against model; `fail(kind, text)` raises."""
+def _bits(x):
+  """float64 arrays compared bit for bit (-0.0 is not 0.0)."""
+  x = np.asarray(x)
+  return x.view(np.int64) if x.dtype == np.float64 else x
+
+
+def compare_with_model(eng, model, rows, model_rows, fail, worlds=None, row_worlds=None, record_worlds=None):
+  """Everything the model speaks about, engine against model; `fail(kind, text)` raises.
+  `worlds`: the worlds the model speaks for (None: all) — the reported world is an index into it;
+  `row_worlds`: those it spoke for through the whole call, whose per-step rows compare;
+  `record_worlds`: those whose record it states (a restore puts records back, not buffers)."""
+  def of(x, axis=0, worlds=worlds):
+    return np.asarray(x) if worlds is None else np.take(np.asarray(x), worlds, axis=axis)
+
+  note = "" if worlds is None else f" (of worlds {np.asarray(worlds).tolist()})"
   for name, got, want in zip(("record grid", "record avatars", "record globals"), eng.dump(), model.dump()):
-    d = first_difference(name, got, want)
+    d = first_difference(name, of(got, 0, record_worlds), of(want, 0, record_worlds))
     if d:
-      fail(name, d)
+      fail(name, d + ("" if record_worlds is None else f" (of worlds {np.asarray(record_worlds).tolist()})"))
   for kind in model.scalar_kinds:
-    d = first_difference(kind, eng.observe_host(kind), model.observe_host(kind))
+    d = first_difference(kind, of(eng.observe_host(kind)), of(model.observe_host(kind)))
     if d:
-      fail(f"kind {kind}", d)
-  if (rows is None) != (model_rows is None) or (rows is not None and set(rows) != set(model_rows)):
+      fail(f"kind {kind}", d + note)
+  real = hasattr(eng, "_L")
+  skip = {"hashes"} if real else set()   # (a model's hash is a stand-in: run_program checks the engine's)
+  if (rows is None) != (model_rows is None) or (rows is not None and set(rows) - skip != set(model_rows) - skip):
     fail("step_many rows", f"keys {rows and sorted(map(str, rows))} != {model_rows and sorted(map(str, model_rows))}")
   for key in rows or ():
-    d = first_difference(key, rows[key], model_rows[key], leading=("step", "world"))
+    if key in skip:
+      continue
+    if key in ("stopped", "ran", "returns"):   # [N] or [N, P]
+      d = first_difference(key, _bits(of(rows[key], 0, row_worlds)), _bits(of(model_rows[key], 0, row_worlds)))
+    else:
+      d = first_difference(key, of(rows[key], 1, row_worlds), of(model_rows[key], 1, row_worlds), leading=("step", "world"))
     if d:
-      fail(f"step_many row {key}", d)
-  got, want = eng.counters()["bad_actions"], model.counters()["bad_actions"]
-  if got != want:
-    fail("bad_actions", f"{got} != {want}")
+      fail(f"step_many {'result' if key in ('stopped', 'ran', 'returns') else 'row'} {key}",
+           d + ("" if row_worlds is None else f" (of worlds {np.asarray(row_worlds).tolist()})"))
+  if worlds is None:   # (the count is the engine's, over all its worlds)
+    got, want = eng.counters()["bad_actions"], model.counters()["bad_actions"]
+    if got != want:
+      fail("bad_actions", f"{got} != {want}")
   if dict(eng.ring) != dict(model.ring):
     fail("ring position", f"{dict(eng.ring)} != {dict(model.ring)}")
   for kind, want in model._bound.items():
     # (a ring kind: every slot — the one written last holds the model's, the others did not change)
     ring_kind = np.asarray(want).ndim == len(model.shapes[kind][0]) + 1
-    d = first_difference(kind, _host(eng._bound[kind]), want, leading=("slot", "world") if ring_kind else ("world",))
+    d = first_difference(kind, of(_host(eng._bound[kind]), int(ring_kind)), of(want, int(ring_kind)),
+                         leading=("slot", "world") if ring_kind else ("world",))
     if d:
-      fail(f"{'ring' if ring_kind else 'bound'} kind {kind} (last slot {eng.ring['last']})", d)
+      fail(f"{'ring' if ring_kind else 'bound'} kind {kind} (last slot {eng.ring['last']})", d + note)
 
 
-def compare_views_with_model(eng, model, fail, kinds=engine_model.VIEW_KINDS):
-  """Every view kind drawn by mp_observe from the records, against the model's."""
+def compare_reads(op, side, model_side, twin_side, fail):
+  """A read-only op's result: against the model's `state_value` / `view_of` for the rows the model
+  speaks for, against the twin's, and the hash's and the check's own conditions."""
+  c, eng, model = op["op"], side.eng, model_side.eng
+  if c in ("observe_rows", "observe_views"):
+    mrows = [model_side.banks[op["bank"]][int(i)] for i in op["rows"]]
+    keep = np.array([r.get("exact", True) for r in mrows])
+    d = first_difference(op["kind"], side.read[keep], model_side.read[keep], leading=("row",))
+    if d:
+      fail(f"{c} kind {op['kind']}", d)
+    if twin_side is not None:
+      d = first_difference(op["kind"], side.read, twin_side.read, leading=("row",))
+      if d:
+        fail(f"twin: {c} kind {op['kind']}", d)
+  elif c == "hash" and side.real:
+    spec = HASH_SPECS[op["spec"]] or {}
+    bank = eng.save_worlds() if op["bank"] < 0 else side.banks[op["bank"]]
+    which = None if op["bank"] < 0 or op["rows"] is None else op["rows"]
+    pack = profile_pack(side.profile)
+    host = E.hash_states_host(pack, bank.cpu().numpy(), which=which, num_players=side.profile["num_players"], **spec)
+    if not np.array_equal(side.read, host):
+      fail("hash", f"device {side.read.tolist()} != hash_states_host {host.tolist()}")
+    if twin_side is not None and not np.array_equal(side.read, twin_side.read):
+      fail("twin: hash", f"{side.read.tolist()} != {twin_side.read.tolist()}")
+    if not spec:   # "the state": equal model rows hash alike, rows whose dumps differ do not
+      mbank = model.save_worlds() if op["bank"] < 0 else model_side.banks[op["bank"]]
+      mrows = [mbank[int(i)] for i in (range(len(mbank)) if which is None else which)]
+      keys = [model.row_key(r) if r.get("exact", True) else None for r in mrows]
+      dumps = model.row_dumps(mrows)
+      for i in range(len(mrows)):
+        for j in range(i):
+          if keys[i] is None or keys[j] is None:
+            continue
+          if keys[i] == keys[j] and side.read[i] != side.read[j]:
+            fail("hash", f"elements {j} and {i} are one state (same seed, same log) and hash differently")
+          differ = any(not np.array_equal(dumps[i][t], dumps[j][t]) for t in (0, 1))
+          if differ and side.read[i] == side.read[j]:
+            fail("hash", f"elements {j} and {i} differ in grid or avatars and hash alike")
+  elif c == "check" and side.real:
+    verdicts, broken, clone = side.read
+    if verdicts.any():   # every state reached by play is well formed
+      r = int(np.argwhere(verdicts.any(1))[0][0])
+      fail("check", f"row {r} of bank {op['bank']}: {eng.state_layout().describe(*verdicts[r])}")
+    host = E.check_states_host(profile_pack(side.profile), clone, num_players=side.profile["num_players"])
+    if not np.array_equal(broken, host) or not broken.any():
+      fail("check", f"a row with {op['field']} broken: device verdict {broken.tolist()}, host {host.tolist()}")
+
+
+def compare_views_with_model(eng, model, fail, kinds=engine_model.VIEW_KINDS, worlds=None):
+  """Every view kind drawn by mp_observe from the records, against the model's (`worlds`: the
+  worlds the model speaks for; None: all)."""
+  pick = (lambda x: x) if worlds is None else (lambda x: np.take(x, worlds, axis=0))
   for kind in kinds:
-    d = first_difference(kind, eng.observe_host(kind), model.view_value(kind))
+    d = first_difference(kind, pick(eng.observe_host(kind)), pick(model.view_value(kind)))
     if d:
       fail(f"observed kind {kind}", d)
 
@@ -411,13 +1021,62 @@ def compare_with_twin(eng, twin, locate, fail):
     fail("twin: save_worlds", first_difference("rows", _host(a), _host(b), leading=("world",)))
 
 
-def run_program(program, engine, model, twin=None, stop_after=None):
+def compare_many_with_twin(op, side, twin_side, locate, fail):
+  """A K-step op of the state classes: the engine's one call against the twin's host loop."""
+  import torch
+  from test_gpu_world_states import _no_counters
+  for key in ("ran", "stopped", "returns", "hashes"):
+    if key in (twin_side.rows or ()):
+      d = first_difference(key, _bits(side.rows[key]), _bits(twin_side.rows[key]),
+                           leading=("step", "world") if key == "hashes" else ("world",))
+      if d:
+        fail(f"twin: step_many result {key}", d)
+  if op["op"] == "step_many_states":
+    a, b = _no_counters(side.banks[-1], locate), _no_counters(twin_side.banks[-1], locate)
+    if not torch.equal(a, b):
+      fail("twin: step_many states", first_difference("rows", _host(a), _host(b), leading=("row",)))
+    # hashes[k, w] is hash_states of states[k, w]
+    again = _host(side.eng.hash_states(side.banks[-1])).reshape(side.rows["hashes"].shape)
+    d = first_difference("hashes", side.rows["hashes"], again, leading=("step", "world"))
+    if d:
+      fail("step_many hashes against hash_states of its states", d)
+
+
+def _cover(cover, op, model_side, taken_before):
+  """What a run contained that only the runner sees (the rest is the model's own `cover`)."""
+  c, model = op["op"], model_side.eng
+  if c == "restore" and np.asarray(model_side.stopped).any():
+    cover["restore while a stopped byte is set"] += 1
+  if c == "masked_reseed" and model_side.reg is not None:
+    cover["masked_reseed while a registration is set"] += 1
+  if c == "starts_rows" and model_side.reg is not None:
+    model_side.rewritten = True
+  if c == "starts_set":
+    model_side.rewritten = False
+  if getattr(model_side, "rewritten", False) and model.cover["registered start"] > taken_before:
+    cover["starts_rows rewrite between registration and use"] += 1
+    model_side.rewritten = False
+  if c in ("load", "observe_rows", "observe_views") and model_side.states_banks.get(op["bank"]):
+    cover[("load" if c == "load" else "observe_*") + " from a step_many_states bank"] += 1
+  if c in ("observe_rows", "observe_views"):
+    rows = [model_side.banks[op["bank"]][int(i)] for i in op["rows"]]
+    if any((d[1][:, 3] == 0).any() and not r["finished"] for r, d in zip(rows, model.row_dumps(rows))):
+      cover["a row with a dead avatar among the drawn rows"] += 1
+
+
+def run_program(program, engine, model, twin=None, stop_after=None, cover=None):
   """Applies each op of `program` (its first `stop_after`, if given) to `engine`, `model` and
   `twin`, comparing after every op; raises Mismatch / FaultStop naming seed, profile, op and kind.
-  Returns the number of ops run."""
+  `cover`: a Counter that takes what the run contained.  Returns the number of ops run."""
+  import collections
   profile = program.profile
   ring = profile["ring"]
-  sides = [_Side(engine), _Side(model)] + ([_Side(twin)] if twin is not None else [])
+  sides = [_Side(engine), _Side(model)] + ([_Side(twin, twin=True)] if twin is not None else [])
+  for side in sides:
+    side.profile = profile
+  side, model_side, twin_side = sides[0], sides[1], sides[2] if twin is not None else None
+  model_side.states_banks = {}
+  cover = collections.Counter() if cover is None else cover
   locate = None
   ran = 0
   for i, op in enumerate(program[:stop_after]):
@@ -426,26 +1085,100 @@ def run_program(program, engine, model, twin=None, stop_after=None):
     def fail(kind, text):
       raise Mismatch(f"{where}: {kind}: {text}")
 
-    for k, side in enumerate(sides):
-      side.apply(op, ring, views=k < 2)   # (the twin binds no view)
+    op = resolve(op, model_side)
+    taken_before = model.cover["registered start"] if hasattr(model, "cover") else 0
+    exact_before = model.speaks.copy() if hasattr(model, "speaks") else None
+    for k, s in enumerate(sides):
+      s.apply(op, ring, views=k < 2)   # (the twin binds no view)
+    if op["op"] == "step_many_states":
+      model_side.states_banks[len(model_side.banks) - 1] = True
     # (dump synchronises; a fault word ends the run before anything else is launched)
     engine.dump()
     _check_faults(engine, where)
     if twin is not None:
       twin.dump()
       _check_faults(twin, where + " (twin)")
-    compare_with_model(engine, model, sides[0].rows, sides[1].rows, fail)
+    exact = getattr(model, "speaks", None)
+    worlds = None if exact is None or exact.all() else np.nonzero(exact)[0]
+    # (a world the model did not speak for when the call began may be one it speaks for now — it
+    # restarted from a row — but its rows of the steps before that are not the model's)
+    both = None if exact is None or (exact & exact_before).all() else np.nonzero(exact & exact_before)[0]
+    records = None if exact is None or model.exact.all() else np.nonzero(model.exact)[0]
+    compare_with_model(engine, model, side.rows, model_side.rows, fail, worlds, both, records)
+    if both is not None:
+      # a `stopped` byte decided while the model did not speak for its world is the engine's to say
+      # (the twin checks it): the model's side takes it over, so that the world compares again once
+      # the model speaks for it
+      other = np.setdiff1d(np.arange(engine.N), both)
+      model_side.stopped[other] = _host(side.stopped)[other]
+    d = first_difference("stopped", _host(side.stopped), _host(model_side.stopped))
+    if d:
+      fail("the caller's `stopped`", d)
     if op["op"] in ("load", "restore"):   # (mp_observe draws from the records: a restore is no launch)
-      compare_views_with_model(engine, model, fail)
+      compare_views_with_model(engine, model, fail, worlds=records)
+    if op["op"] in READ_ONLY:
+      compare_reads(op, side, model_side, twin_side, fail)
+    if hasattr(model, "cover"):
+      _cover(cover, op, model_side, taken_before)
     if twin is not None:
       if locate is None:   # (world 0 still has its first seed: it locates the counters' bytes)
         locate = engine.save_worlds().clone()
       compare_with_twin(engine, twin, locate, fail)
+      if op["op"] in NEW_STEP_CLASSES:
+        compare_many_with_twin(op, side, twin_side, locate, fail)
+      if not np.array_equal(_host(side.stopped), twin_side.stopped):
+        fail("twin: the caller's `stopped`", f"{_host(side.stopped).tolist()} != {twin_side.stopped.tolist()}")
     ran += 1
   if ran:
-    compare_views_with_model(engine, model, fail)
+    compare_views_with_model(engine, model, fail, worlds=records)
     _check_faults(engine, "end of program")
+  if hasattr(model, "cover"):
+    cover.update(model.cover)
+    cover["inexact worlds at the end"] += int((~model.exact).sum())
   return ran
+
+
+def program_cover(program):
+  """What a run of `program` contains, by the model alone (no engine is looked at): a Counter."""
+  import collections
+  profile = program.profile
+  model = make_model(profile)
+  side = _Side(model)
+  side.profile, side.states_banks = profile, {}
+  cover = collections.Counter()
+  try:
+    for op in program:
+      op = resolve(op, side)
+      taken_before = model.cover["registered start"]
+      side.apply(op, profile["ring"])
+      if op["op"] == "step_many_states":
+        side.states_banks[len(side.banks) - 1] = True
+      _cover(cover, op, side, taken_before)
+    cover.update(model.cover)
+    cover["inexact worlds at the end"] += int((~model.exact).sum())
+  finally:
+    model.close()
+  return cover
+
+
+# what the model's run of a level's two programs must contain (the reward conditions apart)
+COVER_CONDITIONS = (
+    "stopped by LAST with steps left to skip",
+    "paused on LAST, restarts in a later active step",
+    "registered start inside step k >= 1 of a K-step call",
+    "two worlds take one row in one step beside a world with -1",
+    "starts_rows rewrite between registration and use",
+    "restore while a stopped byte is set",
+    "masked_reseed while a registration is set",
+    "load from a step_many_states bank",
+    "observe_* from a step_many_states bank",
+)
+DEAD_AVATAR_CONDITION = "a row with a dead avatar among the drawn rows"
+REWARD_CONDITIONS = (
+    "stopped by REWARD with steps left to skip",
+    "returns with gamma != 1 paid after the first step the world ran",
+    "non-zero reward on the step that leaves LAST",
+)
 
 
 # ------------------------------------------------------------------------- engines of a profile

@@ -1,8 +1,11 @@
 """Test infrastructure: a plain Python model of `engine.Engine` made of CPU oracles, for the
 program tests (tests/api_programs.py).  It answers the calls a learner or a planner makes —
 reset, masked reset, re-seed, step, step_fields, step_many with rows, save_worlds / load_worlds,
-snapshot / restore, bind / bind_ring / unbind — and says what every output of include/mp_engine.h
-it models must hold afterwards.
+snapshot / restore, bind / bind_ring / unbind, and, composed in the same _advance / step /
+step_many: masks (active=), stops (until=, stopped=, returns=, gamma=), registered episode starts
+(set_episode_starts / clear_episode_starts), per-step state rows (states=) and reads of bank rows
+(state_value, view_of) — and says what every output of include/mp_engine.h it models must hold
+afterwards.
 
 Per world it keeps a live `oracle.Oracle` and the world's LOG, (seed, [("reset",) | ("step", a) |
 ("fields", f), ...]): what the oracle was fed since it was created.  A world is copied (load,
@@ -20,10 +23,19 @@ What it models, after mp_engine.h:
     the submission, and a world that writes nothing leaves that slot's bytes as they were;
   * the views (RGB, RGB_POOL2/4/8, WORLD.RGB, LAYER) as functions of the records of ALL worlds,
     drawn into what is bound (the ring slot) by every submission;
-  * mp_counters' bad_actions (kept by the destination of a load, rewound by a restore).
+  * mp_counters' bad_actions (kept by the destination of a load, rewound by a restore);
+  * a world skipped by a mask or a stop state: nothing of it is written, its element of a bound
+    LAYER included (only pixel views are redrawn for all worlds); a world paused on LAST restarts in
+    its next active step; `stopped` and `rows` are the caller's arrays, read and written in place;
+  * a registered start: the level's reset and on top of it what a load of the row writes.
+    fresh=True is NOT modelled (the oracle takes no state): `exact` says which worlds the model
+    speaks for.
 It says nothing about the kinds under the carry rule that no record holds (AUX0 - AUX4, ZAP_MATRIX,
 INTERACTION_INVENTORIES, INTERACTION_REWARDS, MATRIX_CUMULANTS): the twin engine of
 api_programs.run_program covers those."""
+import collections
+import zlib
+
 import numpy as np
 
 from meltingpot_amd import engine as E
@@ -98,6 +110,20 @@ class ModelEngine:
     self._cursor = 0
     self._slot = 0
     self._bad = np.zeros(self.N, np.int64)
+    self._touched = None
+    self.starts = None   # the registration: (bank, rows [N])
+    self._fresh = False
+    # exact[w]: the model speaks for world w.  A world that took a fresh=True start is one the
+    # oracle cannot state (it has no state load); it stays inexact until it is re-seeded, and a row
+    # saved from it, or a world loaded from such a row, is inexact too
+    self.exact = np.ones(self.N, bool)
+    # ... and for its output buffers, which a restore leaves as the launch before wrote them: they
+    # are the model's again once an exact world has written them (a step, a reset, a load)
+    self._buf_exact = np.ones(self.N, bool)
+    self._paused = np.zeros(self.N, bool)   # skipped while on LAST, in front of its restart
+    self.cover = collections.Counter()      # what a run contained (tests/test_api_programs_cpu.py)
+    self._step_starts = []                  # (world, row index or -1) of the restarts of this step
+    self._replays = {}   # row_key -> the oracle its log was replayed into
 
   # -- the interface the runner drives on both sides (numpy in, numpy out here)
   def to_device(self, a):
@@ -107,9 +133,9 @@ class ModelEngine:
     return oracle_lib.Oracle(self.pack_bytes, int(seed), self._num_players)
 
   def close(self):
-    for o in self._o:
+    for o in list(self._o) + list(self._replays.values()):
       o.close()
-    self._o = []
+    self._o, self._replays = [], {}
 
   # -- buffers
   def bind(self, kind, tensor=None):
@@ -180,6 +206,20 @@ class ModelEngine:
     self._write_transition(w, 0, np.zeros(self.P), self._reset_events)
     self._write_record_kinds(w)
 
+  @property
+  def speaks(self):
+    """bool [N]: the worlds whose record AND output buffers the model states."""
+    return self.exact & self._buf_exact
+
+  def _wrote_load(self, w, row):
+    self._buf_exact[w] = row.get("exact", True)
+    if row["finished"]:   # loads finished: what a frozen world reports
+      self._write_transition(w, 2, np.zeros(self.P), [])
+    else:                 # as a reset writes them
+      self._write_transition(w, 0, np.zeros(self.P), self._reset_events)
+    self._write_record_kinds(w)
+    self._buf_exact[w] = self.exact[w]
+
   def _frozen_rewards(self, w):
     return np.zeros(self.P)
 
@@ -187,27 +227,44 @@ class ModelEngine:
     self._write_transition(w, 2, self._frozen_rewards(w), [])
 
   # -- submissions
-  def _begin(self):
+  def _begin(self, masked=False):
+    """masked: a submission under a mask or a stop state (MpStepActive, MpStepUntil), which does
+    not touch the worlds it skips."""
+    self._touched = set() if masked else None
     if self._slots:
       self._slot = self._cursor % self._slots
       self._cursor += 1
 
   def view_value(self, kind):
     """A view kind as the function of the records it is, for every world."""
+    return self._kind_of(kind, self._o)
+
+  def _kind_of(self, kind, oracles):
+    """A kind that is a function of the record (a view or a record scalar), of `oracles`."""
+    if kind in self.record_scalars:
+      return np.asarray(self._of_records(kind, oracles), self.shapes[kind][1])
     if kind == E.OBS_WORLD_RGB:
-      return E.pool_rgb(self._of_records(kind, self._o), self.world_pool)
+      return E.pool_rgb(self._of_records(kind, oracles), self.world_pool)
     if kind == E.OBS_LAYER:
-      return np.stack([np.stack([o.layer_view(p) for p in range(self.P)]) for o in self._o])
-    rgb = self._of_records(E.OBS_RGB, self._o)
+      return np.stack([np.stack([o.layer_view(p) for p in range(self.P)]) for o in oracles])
+    rgb = self._of_records(E.OBS_RGB, oracles)
     if kind == E.OBS_RGB:
       return rgb
     return E.pool_rgb(rgb, {v: k for k, v in E.OBS_RGB_POOL.items()}[kind])
 
   def _end(self):
-    """Every bound view is drawn by the submission, from all the records."""
+    """Every bound view is drawn by the submission, from all the records — but a bound LAYER is a
+    non-pixel output, which a masked submission writes for the worlds that ran only: a skipped
+    world's elements keep their bytes (they differ from its record's right after a restore)."""
     for kind, out in self._bound.items():
       if kind in VIEW_KINDS:
-        (out[self._slot] if kind in self._ring_kinds else out)[...] = self.view_value(kind)
+        value = self.view_value(kind)
+        target = out[self._slot] if kind in self._ring_kinds else out
+        if kind == E.OBS_LAYER and self._touched is not None:
+          for w in self._touched:
+            target[w] = value[w]
+        else:
+          target[...] = value
 
   def _reset_world(self, w):
     self._o[w].reset()
@@ -220,6 +277,7 @@ class ModelEngine:
     self._seed[w] = int(seed)
     self._o[w] = self._oracle(seed)
     self._log[w] = []
+    self.exact[w] = True
 
   def reset(self, seeds=None, mask=None):
     self._begin()
@@ -231,17 +289,55 @@ class ModelEngine:
       self._reset_world(w)
     self._end()
 
+  def _start_row(self, w):
+    """The row world w starts its next episode from (None: the level's own reset): `rows` is read at
+    this moment, the end of the world's episode."""
+    if self.starts is None:
+      return None
+    bank, rows = self.starts
+    return bank[int(rows[w])] if rows[w] >= 0 else None
+
+  def _restart(self, w):
+    """World w, done, starts its next episode: the level's reset, or its registered row."""
+    row = self._start_row(w)
+    self._reset_world(w)   # (what the replaced auto-reset step left)
+    if self._paused[w]:
+      self.cover["paused on LAST, restarts in a later active step"] += 1
+    self._step_starts.append((w, -1 if row is None else int(self.starts[1][w])))
+    if row is not None:    # ... and on top of it what a load of the row writes
+      self._become(w, row)
+      self._wrote_load(w, row)
+      if self._fresh:
+        self.exact[w] = self._buf_exact[w] = False
+      self.cover["registered start"] += 1
+      if self._in_many >= 1:
+        self.cover["registered start inside step k >= 1 of a K-step call"] += 1
+
+  def _end_step(self):
+    """After every single step (each of a K-step call's): what its restarts were."""
+    taken = collections.Counter(r for _, r in self._step_starts if r >= 0)
+    if any(n >= 2 for n in taken.values()) and any(r < 0 for _, r in self._step_starts) and self.starts is not None:
+      self.cover["two worlds take one row in one step beside a world with -1"] += 1
+    self._step_starts = []
+
   def _advance(self, w, entry, auto_reset=None):
-    """One step of world w; `entry`: ("step", ids [P]) or ("fields", f [P, A])."""
+    """One step of world w; `entry`: ("step", ids [P]) or ("fields", f [P, A]).  False: a world
+    never reset, which runs nothing."""
     o = self._o[w]
     if not self._started[w]:
-      return
+      return False
     if o.done:
       if self._auto_reset if auto_reset is None else auto_reset:
-        self._reset_world(w)
+        self._restart(w)
       else:
         self._wrote_frozen(w)
-      return
+      self._paused[w] = False
+      if self._touched is not None:
+        self._touched.add(w)
+      return True
+    self._paused[w] = False
+    if self._touched is not None:
+      self._touched.add(w)
     if entry[0] == "step":
       a = np.array(entry[1], np.int32)
       bad = (a < 0) | (a >= self.num_actions)
@@ -254,51 +350,149 @@ class ModelEngine:
     self._log[w].append((entry[0], a))
     self._write_transition(w, 1 if cont else 2, o.rewards(), o.events())
     self._write_record_kinds(w)
+    self._buf_exact[w] = self.exact[w]
+    if not cont and np.any(o.rewards() != 0):
+      self.cover["non-zero reward on the step that leaves LAST"] += 1
+    return True
 
-  def step(self, actions):
+  def step(self, actions, active=None):
+    """active: a mask [N]; a world outside it is not touched (it writes nothing)."""
     a = np.asarray(actions, np.int32).reshape(self.N, self.P)
-    self._begin()
+    self._begin(masked=active is not None)
     for w in range(self.N):
-      self._advance(w, ("step", a[w]))
+      if active is None or active[w]:
+        self._advance(w, ("step", a[w]))
+      else:
+        self._skipped(w)
+    self._end_step()
     self._end()
 
-  def step_fields(self, fields):
+  def step_fields(self, fields, active=None):
+    """active: as step()'s (the engine's form of it is the K = 1 request of step_many)."""
     f = np.asarray(fields, np.int32).reshape(self.N, self.P, self.num_action_fields)
-    self._begin()
+    self._begin(masked=active is not None)
     for w in range(self.N):
-      self._advance(w, ("fields", f[w]))
+      if active is None or active[w]:
+        self._advance(w, ("fields", f[w]))
+      else:
+        self._skipped(w)
+    self._end_step()
     self._end()
 
   def _many_auto_reset(self):
     return self._auto_reset
 
+  _in_many = -1   # the step of the K-step call that is running (-1: none)
+
+  def _skipped(self, w, by_mask=True):
+    """World w skips a step (masked out or stopped): it is not touched."""
+    if by_mask and self._started[w] and self._o[w].done:
+      self._paused[w] = True
+
+  def _stops(self, w, stop):
+    """The reason bits that stop world w after a step it ran (0: it goes on)."""
+    paid = bool((self._target(E.OBS_REWARD)[w] != 0).any())
+    last = int(self._target(E.OBS_STEP_TYPE)[w]) == 2
+    return (E.MP_STOP_LAST if (stop & E.MP_STOP_LAST) and last else 0) | \
+           (E.MP_STOP_REWARD if (stop & E.MP_STOP_REWARD) and paid else 0)
+
+  def _discount(self, g, gamma, k, w):
+    """The weight of the next step world w runs, after one that ran as step k of the call."""
+    return g * np.float64(gamma)
+
   def step_many(self, actions, *, repeat=None, fields=False, events=False, observations=(),
-                keep=("reward", "collective_reward", "step_type", "discount")):
+                keep=("reward", "collective_reward", "step_type", "discount"), active=None,
+                until=None, stop=None, stopped=None, returns=False, gamma=1.0, states=False, hashes=False):
     """The loop over single steps as ONE submission; returns the per-step rows under the keys of
-    `engine.Engine.step_many` (a row of LAYER is the function of the records after that step)."""
+    `engine.Engine.step_many` (a row of LAYER is the function of the records after that step).
+    active: a mask [K, N] or [N]: world w runs step k only where it is non-zero.
+    until (names, as the engine takes them) or stop (MP_STOP_* bits): a world that a step leaves on
+    LAST, or pays, skips the rest of the call.  stopped: the caller's array [N], read and written in
+    place (None: a new one).  With any of until / stop / stopped / returns the result gains
+    "stopped" and "ran" (the steps each world ran), and with returns "returns" [N, P]: g = 1; per
+    step that ran ret = ret + g * r; g = g * gamma, each rounded in float64 on its own.
+    states: "states", a list of K lists of the N worlds' rows (`_row`) after every step — each is a
+    bank like save_worlds'.  hashes: "hashes" int64 [K, N], `hash_states` of those rows."""
     a = np.asarray(actions, np.int32)
     K = int(repeat) if repeat is not None else a.shape[0]
+    if stop is None:
+      names = () if until is None else (until,) if isinstance(until, str) else tuple(until)
+      stop = sum(E.STOP_NAMES[n] for n in set(names))
+    stopping = bool(stop) or until is not None or stopped is not None or returns is not False
+    mask = None if active is None else np.broadcast_to(np.asarray(active) != 0, (K, self.N))
     names = [k for k in E.STEP_MANY_KINDS if k in tuple(keep) or (k == "events" and events)]
     keys = names + [int(k) for k in observations]
     rows = {key: [] for key in keys}
-    self._begin()
+    state_rows, hash_rows = [], []
+    stopped = np.zeros(self.N, np.uint8) if stopped is None else stopped
+    ran = np.zeros(self.N, np.int32)
+    ret = np.zeros((self.N, self.P), np.float64)
+    g = np.ones(self.N, np.float64)
+    self._begin(masked=mask is not None or stopping)
     for k in range(K):
       block = a if repeat is not None else a[k]
+      self._in_many = k
       for w in range(self.N):
-        self._advance(w, ("fields" if fields else "step", block[w]), auto_reset=self._many_auto_reset())
+        if stopping and stopped[w]:
+          self._skipped(w, by_mask=False)
+          continue
+        if mask is not None and not mask[k, w]:
+          self._skipped(w)
+          continue
+        if not self._advance(w, ("fields" if fields else "step", block[w]), auto_reset=self._many_auto_reset()):
+          continue
+        ran[w] += 1
+        ret[w] = ret[w] + g[w] * self._target(E.OBS_REWARD)[w]
+        g[w] = self._discount(g[w], gamma, k, w)
+        if returns is not False and float(gamma) != 1.0 and ran[w] >= 2 and np.any(self._target(E.OBS_REWARD)[w] != 0):
+          self.cover["returns with gamma != 1 paid after the first step the world ran"] += 1
+        reason = self._stops(w, stop)
+        if reason:
+          stopped[w] = reason
+          if k + 1 < K and (mask is None or mask[k + 1:, w].any()):
+            for bit, name in ((E.MP_STOP_LAST, "LAST"), (E.MP_STOP_REWARD, "REWARD")):
+              if reason & bit:
+                self.cover[f"stopped by {name} with steps left to skip"] += 1
       for key in keys:
         kind = E.STEP_MANY_NAMES.get(key, key)
         rows[key].append(self.view_value(kind) if kind == E.OBS_LAYER else self._target(kind).copy())
+      if states:
+        state_rows.append([self._row(w) for w in range(self.N)])
+      if hashes:
+        hash_rows.append([self._hash_of(self._o[w]) for w in range(self.N)])
+      self._end_step()
+    self._in_many = -1
     self._end()
-    return {key: np.stack(v) for key, v in rows.items()}
+    out = {key: np.stack(v) for key, v in rows.items()}
+    if states:
+      out["states"] = state_rows
+    if hashes:
+      out["hashes"] = np.array(hash_rows, np.int64)
+    if stopping:
+      out.update(stopped=stopped, ran=ran)
+      if returns is not False:
+        out["returns"] = ret
+    return out
+
+  # -- episode starts
+  def set_episode_starts(self, bank, rows, fresh=False):
+    """From now on a world that auto-resets starts from row rows[w] of `bank` (-1: the level's
+    reset); `rows` is the caller's array, read when a world's episode ends.  fresh=True is not
+    modelled (the oracle takes no state): such a world is the fresh=False one here, and the
+    program runner stops comparing it."""
+    assert self._auto_reset, "a registration needs auto_reset"
+    self.starts, self._fresh = (bank, rows), bool(fresh)
+
+  def clear_episode_starts(self):
+    self.starts = None
 
   # -- world states
   def _row(self, w):
     return {"seed": self._seed[w], "log": list(self._log[w]), "finished": self._o[w].done,
-            "started": self._started[w]}
+            "started": self._started[w], "exact": bool(self.exact[w])}
 
-  def _become(self, w, row):
-    """World w becomes a copy of `row`: its log replayed into a fresh oracle."""
+  def _replay(self, row):
+    """A fresh oracle that `row`'s log was replayed into."""
     o = self._oracle(row["seed"])
     for entry in row["log"]:
       if entry[0] == "reset":
@@ -308,9 +502,16 @@ class ModelEngine:
       else:
         o.step_fields(entry[1])
     assert o.done == row["finished"], "a replayed log did not end where the live world did"
+    return o
+
+  def _become(self, w, row):
+    """World w becomes a copy of `row`: its log replayed into a fresh oracle."""
+    o = self._replay(row)
     self._o[w].close()
     self._o[w], self._seed[w], self._log[w] = o, row["seed"], list(row["log"])
     self._started[w] = row["started"]
+    self.exact[w] = row.get("exact", True)
+    self._paused[w] = False
 
   def save_worlds(self, worlds=None):
     return [self._row(int(w)) for w in (range(self.N) if worlds is None else np.asarray(worlds))]
@@ -328,11 +529,7 @@ class ModelEngine:
       if row is None:
         continue
       self._become(w, row)
-      if row["finished"]:   # loads finished: what a frozen world reports
-        self._write_transition(w, 2, np.zeros(self.P), [])
-      else:                 # as a reset writes them
-        self._write_transition(w, 0, np.zeros(self.P), self._reset_events)
-      self._write_record_kinds(w)
+      self._wrote_load(w, row)
     self._end()
 
   def snapshot(self):
@@ -345,6 +542,52 @@ class ModelEngine:
     for w, row in enumerate(rows):
       self._become(w, row)
     self._bad = bad.copy()
+
+  # -- reading saved states: nothing of the engine's is written
+  @staticmethod
+  def row_key(row):
+    """What makes two rows the same state: the seed and the log."""
+    return (int(row["seed"]), tuple((e[0],) + tuple(np.asarray(x).tobytes() for x in e[1:]) for e in row["log"]))
+
+  def _replayed(self, row):
+    """The oracle of `row`, replayed once per distinct row and kept."""
+    key = self.row_key(row)
+    if key not in self._replays:
+      self._replays[key] = self._replay(row)
+    return self._replays[key]
+
+  def state_value(self, rows, kind):
+    """Record-function `kind` of bank rows `rows` (a list): [len(rows), ...]."""
+    return self._kind_of(kind, [self._replayed(r) for r in rows])
+
+  def view_of(self, rows, players, kind):
+    """Per-player `kind` of player players[i] of rows[i]: [len(rows), ...]."""
+    return self.state_value(rows, kind)[np.arange(len(rows)), np.asarray(players)]
+
+  def row_dumps(self, rows):
+    return [self._replayed(r).dump() for r in rows]
+
+  def observe_states(self, bank, kind, rows=None):
+    return self.state_value(bank if rows is None else [bank[int(i)] for i in np.asarray(rows)], kind)
+
+  def observe_views(self, bank, kind, players, rows=None):
+    players = np.asarray(players)
+    picked = [bank[int(i)] for i in (range(len(players)) if rows is None else np.asarray(rows))]
+    return self.view_of(picked, players, kind)
+
+  @staticmethod
+  def _hash_of(o):
+    """The model's stand-in for the engine's state hash (equal for equal states of one model)."""
+    grid, avatars, glob = o.dump()
+    h = zlib.crc32(np.ascontiguousarray(avatars).tobytes(), zlib.crc32(np.ascontiguousarray(grid).tobytes()))
+    return np.int64(h | (zlib.adler32(np.ascontiguousarray(glob).tobytes()) << 32) & 0x7FFFFFFF00000000)
+
+  def hash_worlds(self, planes=None, fields=None):
+    return np.array([self._hash_of(o) for o in self._o], np.int64)
+
+  def hash_states(self, bank, rows=None, planes=None, fields=None):
+    picked = bank if rows is None else [bank[int(i)] for i in np.asarray(rows)]
+    return np.array([self._hash_of(self._replayed(r)) for r in picked], np.int64)
 
   # -- reading
   def observe_host(self, kind):

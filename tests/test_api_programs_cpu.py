@@ -1,10 +1,18 @@
 """The program tests without a GPU: the generator's promises, the coverage of the committed set, the
 model against an independent restatement of itself, and the runner against deliberately wrong
-models — each must be reported at the first op where it can show."""
+models — each must be reported at the first op where it can show.  For the STATE programs also:
+the first set's programs are op for op what they were (CRCs), every adjacency with a new class is
+held, and the model's own runs contain the crossings the programs are there for (printed under
+`pytest -s`; profiles/r24_state_programs.md)."""
+import collections
+import functools
+import zlib
+
 import numpy as np
 import pytest
 
 import api_programs as ap
+import states_recipe
 from engine_model import ModelEngine
 from meltingpot_amd import engine as E
 
@@ -136,30 +144,65 @@ class ScratchModel(ModelEngine):
         self._hist[w].append(("reset", None if seeds is None else int(seeds[w])))
     super().reset(seeds, mask)
 
-  def step(self, actions):
+  def step(self, actions, active=None):
     a = np.asarray(actions, np.int32)
     for w in range(self.N):
-      self._hist[w].append(("step", a[w].copy()))
-    super().step(a)
+      if active is None or active[w]:
+        self._hist[w].append(("step", a[w].copy()))
+    super().step(a, active)
 
-  def step_fields(self, fields):
+  def step_fields(self, fields, active=None):
     f = np.asarray(fields, np.int32)
     for w in range(self.N):
-      self._hist[w].append(("fields", f[w].copy()))
-    super().step_fields(f)
+      if active is None or active[w]:
+        self._hist[w].append(("fields", f[w].copy()))
+    super().step_fields(f, active)
 
   def step_many(self, actions, *, repeat=None, fields=False, events=False, observations=(),
-                keep=("reward", "collective_reward", "step_type", "discount")):
+                keep=("reward", "collective_reward", "step_type", "discount"), active=None, until=None,
+                stopped=None, returns=False, gamma=1.0, states=False, hashes=False):
+    """The defining identity, unrolled: the loop of step(A[k], active=M[k] & (stopped == 0)) with
+    `stopped` updated on the "host" from what each step left."""
     assert not self._slots
     a = np.asarray(actions, np.int32)
     K = int(repeat) if repeat is not None else a.shape[0]
     keys = list(keep) + (["events"] if events else []) + [int(k) for k in observations]
     rows = {key: [] for key in keys}
+    stopping = until is not None or stopped is not None or returns is not False
+    stop = sum(E.STOP_NAMES[n] for n in ((until,) if isinstance(until, str) else until or ()))
+    stopped = np.zeros(self.N, np.uint8) if stopped is None else stopped
+    ran, ret, g = np.zeros(self.N, np.int32), np.zeros((self.N, self.P)), np.ones(self.N)
+    out_states, out_hashes = [], []
     for k in range(K):
-      (self.step_fields if fields else self.step)(a if repeat is not None else a[k])
+      block = a if repeat is not None else a[k]
+      m = np.ones(self.N, bool) if active is None else np.asarray(active)[k] != 0 if np.ndim(active) == 2 else np.asarray(active) != 0
+      if stopping:
+        m = m & (stopped == 0)
+      (self.step_fields if fields else self.step)(block, active=None if m.all() else m)
+      reward, kind = self.observe_host(E.OBS_REWARD), self.observe_host(E.OBS_STEP_TYPE)
+      for w in np.nonzero(m)[0]:
+        ran[w] += 1
+        ret[w] = ret[w] + g[w] * reward[w]
+        g[w] = g[w] * np.float64(gamma)
+        reason = (1 if stop & 1 and kind[w] == 2 else 0) | (2 if stop & 2 and (reward[w] != 0).any() else 0)
+        if reason and stopping:
+          stopped[w] = reason
       for key in keys:
         rows[key].append(self.observe_host(E.STEP_MANY_NAMES.get(key, key)))
-    return {key: np.stack(v) for key, v in rows.items()}
+      if states:
+        out_states.append(self.save_worlds())
+      if hashes:
+        out_hashes.append(self.hash_worlds())
+    out = {key: np.stack(v) for key, v in rows.items()}
+    if states:
+      out["states"] = out_states
+    if hashes:
+      out["hashes"] = np.array(out_hashes, np.int64)
+    if stopping:
+      out.update(stopped=stopped, ran=ran)
+      if returns is not False:
+        out["returns"] = ret
+    return out
 
   def _row(self, w):
     return dict(super()._row(w), hist=list(self._hist[w]))
@@ -179,6 +222,8 @@ class ScratchModel(ModelEngine):
     self._o[w], self._seed[w], self._log[w] = one._o[0], one._seed[0], one._log[0]
     one._o = []
     self._started[w] = row["started"]
+    self.exact[w] = row.get("exact", True)
+    self._paused[w] = False
     self._hist[w] = list(hist)
 
 
@@ -285,5 +330,313 @@ def test_the_runner_reports_a_wrong_model_at_its_first_op(wrong, classes, name, 
   text = str(err.value)
   assert f"program seed {seed}, profile {name}, op {first}: {prog[first]['op']}" in text, text
   assert "world" in text or "bad_actions" in text
+  # a prefix that stops short of the op passes
+  assert ap.run_program(prog, ap.make_model(profile, wrong), ap.make_model(profile), stop_after=first) == first
+
+
+# ================================================================== the state programs
+# CRC-32 of "\n".join(short_form(op)) of each committed program of the first set, as the generator
+# wrote it before the state classes were added: those 29 programs stay op for op what they were
+FIRST_SET_CRCS = [
+    4229355257, 2548632098, 3766868341, 402132235, 2269418939, 74637082, 1292735000, 2397877344,
+    3355606509, 3136088153, 946387555, 139620854, 3277654155, 1143666235, 3869652750, 3137392074,
+    3630345819, 2909569933, 2884176625, 1941212377, 3781382393, 3925682546, 1392560469, 2038339635,
+    2426985218, 1545311275, 2224218350, 3564122540, 677060799]
+# ... and of every argument's bytes (short_form abbreviates a large array to its shape)
+FIRST_SET_BYTES_CRCS = [
+    2218820954, 1087914836, 693833364, 2217402031, 640452086, 658944506, 3774009416, 2608778444,
+    2177914804, 1057346918, 715140307, 1940672399, 1462608127, 192815018, 1923028878, 1441881605,
+    3443458307, 1188046538, 3366471218, 3842153393, 2954082966, 2612787414, 3963182066, 77860825,
+    1191621424, 3415859352, 2449972944, 2053290610, 3506065503]
+
+
+def _bytes_crc(prog):
+  c = 0
+  for op in prog:
+    for k, v in op.items():
+      c = zlib.crc32(np.ascontiguousarray(v).tobytes() if isinstance(v, np.ndarray) else repr(v).encode(),
+                     zlib.crc32(k.encode(), c))
+  return c
+
+
+def test_the_first_set_is_op_for_op_what_it_was():
+  programs = [ap.make_program(s, p) for s, p in ap.COMMITTED]
+  assert all(p["classes"] == ap.OP_CLASSES for _, p in ap.COMMITTED)
+  assert [zlib.crc32("\n".join(ap.short_form(op) for op in prog).encode()) for prog in programs] == FIRST_SET_CRCS
+  assert [_bytes_crc(prog) for prog in programs] == FIRST_SET_BYTES_CRCS
+
+
+STATE_IDS = [p["name"] for _, p in ap.STATE_COMMITTED]
+
+
+@functools.lru_cache(maxsize=None)
+def _state_program(name):
+  seed, profile = next((s, p) for s, p in ap.STATE_COMMITTED if p["name"] == name)
+  return ap.make_program(seed, profile)
+
+
+@functools.lru_cache(maxsize=None)
+def _state_cover(name):
+  """What the model's run of a state program contains (computed once, shared, read-only)."""
+  return ap.program_cover(_state_program(name))
+
+
+def test_the_state_set_is_the_one_the_issue_names():
+  profiles = [p for _, p in ap.STATE_COMMITTED]
+  assert len(set(STATE_IDS)) == len(profiles) == 2 * len(ap.LEVEL_PACKS) + 1
+  assert all(p["auto_reset"] and not p["ring"] and p["classes"] == ap.STATE_CLASSES for p in profiles)
+  for pack in ap.LEVEL_PACKS:
+    two = [p for p in profiles if p["pack"] == pack and not p["stock"]]
+    assert sorted(p["n"] for p in two) == [6, 23] and [n % 4 for n in (6, 23)] == [2, 3]
+    assert all(p["frames"] == (33 if pack in ("coins", "territory__inside_out") else 17) for p in two)
+    pooled = [p for p in two if p["world_pool"] == 8]
+    assert len(pooled) == 1 and set(pooled[0]["views"]) == {E.OBS_WORLD_RGB, E.OBS_LAYER}
+    other = [p for p in two if p["world_pool"] == 1]
+    assert len(other) == 1 and other[0]["views"] == (E.OBS_RGB,)
+    assert sorted(p["unfused"] is True for p in two) == [False, True]
+    if "in_the_matrix" not in pack and pack != "coins":
+      assert sum(1 for p in two if p["num_players"]) == 1
+    # the pack is the level's variant that pays often, where the parity tests have one
+    raw = E.load_pack(pack)
+    rich = pack in ("clean_up", "collaborative_cooking__cramped", "coop_mining", "gift_refinements",
+                    "externality_mushrooms__dense", "prisoners_dilemma_in_the_matrix__repeated")
+    assert (ap.rich_pack(pack, raw) != raw) == rich, pack
+  stock = [p for p in profiles if p["stock"]]
+  assert len(stock) == 1 and stock[0]["pack"] == "clean_up" and stock[0]["n"] == 23
+  assert ap.profile_pack(stock[0]) == E.load_pack("clean_up")
+  # both kinds of registration, the all-zeros mask, K = 65 and a read wider than the worlds occur
+  ops = [op for name in STATE_IDS for op in _state_program(name)]
+  assert {op["fresh"] for op in ops if op["op"] == "starts_set"} == {False, True}
+  assert any(op.get("mask_form") == "zeros" for op in ops)
+  assert any(op.get("K") == 65 and op.get("mask") is not None for op in ops)
+  assert {op["mask_dtype"] for op in ops if op["op"] == "step_active"} == {"uint8", "bool", "list"}
+  assert {op["until"] for op in ops if op["op"] == "many_until"} == set(ap.UNTILS)
+  assert {op["gamma"] for op in ops if op["op"] == "many_until" and op["returns"]} == set(ap.GAMMAS)
+
+
+@pytest.mark.parametrize("name", STATE_IDS)
+def test_state_programs_are_deterministic_and_within_bounds(name):
+  seed, profile = next((s, p) for s, p in ap.STATE_COMMITTED if p["name"] == name)
+  prog, again = _state_program(name), ap.make_program(seed, profile)
+  assert len(prog) == len(again) and all(_same_op(a, b) for a, b in zip(prog, again))
+  assert prog[0]["op"] == "reset_all"
+  assert {op["op"] for op in prog} == set(profile["classes"]) == set(ap.STATE_CLASSES)
+  assert ap.STATE_MIN_OPS <= len(prog) <= ap.STATE_MAX_OPS
+  assert ap.world_steps(prog) <= ap.STATE_MAX_WORLD_STEPS
+  assert ap.longest_host_run(prog) >= ap.HOST_RUN
+  adjacent = {(a["op"], b["op"]) for a, b in zip(prog[:-1], prog[1:])}
+  assert set(ap.assigned_pairs(profile)) <= adjacent
+  g = ap._geometry(profile)
+  N, P, A = g["N"], g["P"], g["A"]
+  banks, registered, wide = [], None, 0
+  for op in prog:
+    c = op["op"]
+    if c in ("many_active", "many_until", "step_many_states"):
+      K = op["K"]
+      assert K in (ap.STATES_K if c == "step_many_states" else ap.STATE_K)
+      lead = () if op["form"] == "repeat" else (K,)
+      E.check_step_many(lead + (N, P) + ((A,) if op["fields"] else ()), op["actions"].dtype, N, P,
+                        repeat=K if op["form"] == "repeat" else None, num_fields=A if op["fields"] else None)
+      m = ap.op_mask(op, N)
+      assert (m is None) == (op["mask_form"] == "none") and (m is None or m.shape == (K, N))
+      assert c != "many_active" or m is not None
+      if op["mask_form"] == "slice":
+        assert op["mask"].shape == (K, N + 3) and 0 <= op["mlo"] <= 3
+      if c == "many_until":
+        E.check_step_until(N, P, until=op["until"], returns=op["returns"], gamma=op["gamma"])
+        assert op["returns"] or op["gamma"] == 1.0
+    if c == "step_active":
+      assert op["actions"].shape == (N, P) and op["mask"].shape == (N,)
+    if c in ("save", "step_many_states"):
+      banks.append(len(op["worlds"]) if c == "save" else op["K"] * N)
+    if c in ("load", "observe_rows", "observe_views", "check", "starts_set") or (c == "hash" and op["bank"] >= 0):
+      assert 0 <= op["bank"] < len(banks)
+    if c in ("starts_set", "starts_rows"):
+      registered = banks[op["bank"]] if c == "starts_set" else registered
+      rows = op["rows"]
+      assert rows.shape == (N,) and rows.dtype == np.int32 and rows.min() == -1 and rows.max() < registered
+      valid = rows[rows >= 0]
+      assert len(valid) > len(set(valid.tolist())), "several worlds share one row"
+    if c in ("observe_rows", "observe_views") or (c == "hash" and op["rows"] is not None):
+      assert op["rows"].min() >= 0 and op["rows"].max() < banks[op["bank"]]
+    if c == "observe_rows":
+      wide += len(op["rows"]) > N
+    if c == "observe_views":
+      assert len(op["players"]) == len(op["rows"]) and op["players"].max() < P and 0 <= op["offset"] <= 15
+      assert op["kind"] != E.OBS_WORLD_RGB
+    if c == "check":
+      assert 0 <= op["row"] < banks[op["bank"]]
+  assert wide == 1, "one read of a program has more rows than worlds"
+
+
+def test_every_pair_with_a_state_class_is_adjacent_somewhere():
+  programs = [ap.make_program(s, p) for s, p in ap.COMMITTED] + [_state_program(n) for n in STATE_IDS]
+  table = ap.pair_counts(programs, ap.STATE_CLASSES)
+  print(ap.format_pair_table(table, ap.STATE_CLASSES))
+  states = programs[len(ap.COMMITTED):]
+  print("state programs: ops", sum(len(p) for p in states), "world-steps", sum(ap.world_steps(p) for p in states))
+  idx = {c: i for i, c in enumerate(ap.STATE_CLASSES)}
+  missing = [(a, b) for a in ap.MUTATING for b in ap.MUTATING if a != b and table[idx[a], idx[b]] == 0]
+  assert not missing, missing
+  missing = [(a, r) for a in ap.NEW_MUTATING for r in ap.READ_ONLY if table[idx[a], idx[r]] == 0]
+  assert not missing, missing
+
+
+def _level_cover(pack):
+  total = collections.Counter()
+  for n in ap.STATE_WORLD_COUNTS:
+    total.update(_state_cover(f"{pack}-states-n{n}"))
+  return total
+
+
+def test_the_models_runs_hold_the_crossings_on_every_level():
+  """Conditions on the inputs, by the model alone: what a level's two programs contain."""
+  conditions = ap.COVER_CONDITIONS + (ap.DEAD_AVATAR_CONDITION,)
+  print("| level | " + " | ".join(conditions) + " | inexact worlds at the end |")
+  print("|---|" + "---|" * (len(conditions) + 1))
+  covers = {pack: _level_cover(pack) for pack in ap.LEVEL_PACKS}
+  for pack, cover in covers.items():
+    print(f"| {pack} | " + " | ".join(str(cover[k]) for k in conditions) + f" | {cover['inexact worlds at the end']} of 29 |")
+  for pack, cover in covers.items():
+    for k in ap.COVER_CONDITIONS:
+      assert cover[k] > 0, (pack, k)
+    if pack in states_recipe.DEAD_AVATARS:
+      assert cover[ap.DEAD_AVATAR_CONDITION] > 0, pack
+    assert cover["inexact worlds at the end"] < 29, pack   # (the model still speaks for some world)
+
+
+# the levels whose two programs hold the reward conditions (the search found seeds for all nine)
+REWARD_LEVELS = ap.LEVEL_PACKS
+
+
+def test_the_models_runs_pay_rewards_where_it_matters():
+  print("| level | " + " | ".join(ap.REWARD_CONDITIONS) + " |")
+  print("|---|" + "---|" * len(ap.REWARD_CONDITIONS))
+  for pack in ap.LEVEL_PACKS:
+    cover = _level_cover(pack)
+    print(f"| {pack} | " + " | ".join(str(cover[k]) for k in ap.REWARD_CONDITIONS) + " |")
+  assert len(REWARD_LEVELS) >= 6
+  for pack in REWARD_LEVELS:
+    cover = _level_cover(pack)
+    for k in ap.REWARD_CONDITIONS:
+      assert cover[k] > 0, (pack, k)
+
+
+@pytest.mark.parametrize("name", ["coins-states-n6", "commons_harvest__open-states-n6",
+                                  "prisoners_dilemma_in_the_matrix__repeated-states-n6"])
+def test_the_model_equals_its_restatement_on_state_programs(name):
+  prog = _state_program(name)
+  profile = prog.profile
+  a, b = ap.make_model(profile), ap.make_model(profile, ScratchModel)
+  assert ap.run_program(prog, a, b) == len(prog)
+  a.close(); b.close()
+
+
+# ---- the runner against wrong models of the state classes
+class SkippedWritesItsLeaves(ModelEngine):
+  def _skipped(self, w, by_mask=True):
+    super()._skipped(w, by_mask)
+    if self._started[w]:
+      self._write_transition(w, int(self._target(E.OBS_STEP_TYPE)[w]), np.zeros(self.P), [])
+
+
+class StoppedRunsOneMoreStep(ModelEngine):
+  _late = None
+
+  def _stops(self, w, stop):
+    self._late = {} if self._late is None else self._late
+    now, before = super()._stops(w, stop), self._late.pop(w, 0)
+    if now and not before:
+      self._late[w] = now
+    return before
+
+
+class GammaCountsTheCallsSteps(ModelEngine):
+  def _discount(self, g, gamma, k, w):
+    out = np.float64(1.0)
+    for _ in range(k + 1):
+      out = out * np.float64(gamma)
+    return out
+
+
+class RowsAreReadAtRegistration(ModelEngine):
+  def set_episode_starts(self, bank, rows, fresh=False):
+    super().set_episode_starts(bank, np.array(rows), fresh)
+
+
+class PausedOnLastNeverRestarts(ModelEngine):
+  def _restart(self, w):
+    if self._paused[w]:
+      self._wrote_frozen(w)
+    else:
+      super()._restart(w)
+
+
+class RestoreRewindsStopped(ModelEngine):
+  _seen = _kept = None
+
+  def step_many(self, actions, **kw):
+    if kw.get("stopped") is not None:
+      self._seen = kw["stopped"]
+    return super().step_many(actions, **kw)
+
+  def snapshot(self):
+    self._kept = None if self._seen is None else self._seen.copy()
+    return super().snapshot()
+
+  def restore(self, snap):
+    super().restore(snap)
+    if self._seen is not None:
+      self._seen[:] = 0 if self._kept is None else self._kept
+
+
+class ObserveRowsLoadsWorldZero(ModelEngine):
+  def observe_states(self, bank, kind, rows=None):
+    first = bank[0] if rows is None else bank[int(np.asarray(rows)[0])]
+    self._become(0, first)
+    return super().observe_states(bank, kind, rows)
+
+
+MASKED = ("step_active", "many_active", "many_until", "step_many_states")
+# (wrong model, op classes at which it can first show, the state program that shows it)
+WRONG_STATE_MODELS = [
+    (SkippedWritesItsLeaves, MASKED, "clean_up-states-n6"),
+    (StoppedRunsOneMoreStep, ("many_until",), "clean_up-states-n6"),
+    (GammaCountsTheCallsSteps, ("many_until",), "externality_mushrooms__dense-states-n6"),
+    (RowsAreReadAtRegistration, ap.ALL_STEP_CLASSES, "commons_harvest__open-states-n6"),
+    (PausedOnLastNeverRestarts, ap.ALL_STEP_CLASSES, "clean_up-states-n6"),
+    (RestoreRewindsStopped, ("restore",), "clean_up-states-n6"),
+    (ObserveRowsLoadsWorldZero, ("observe_rows",), "clean_up-states-n6"),
+]
+
+
+def _state_trace(program, model):
+  """What the runner looks at, after every op, of a model run alone (it does not know which worlds
+  the model speaks for: a program in which a wrong model first shows in a world that took a
+  fresh=True start is not one to choose)."""
+  side = ap._Side(model)
+  side.profile, side.states_banks = program.profile, {}
+  out = []
+  for op in program:
+    op = ap.resolve(op, side)
+    side.apply(op, 0)
+    out.append((model.dump(), [model.observe_host(k) for k in model.scalar_kinds], side.rows, side.read,
+                side.stopped.copy(), model.counters(), {k: np.array(v) for k, v in model._bound.items()}))
+  return out
+
+
+@pytest.mark.parametrize("wrong,classes,name", WRONG_STATE_MODELS, ids=[w[0].__name__ for w in WRONG_STATE_MODELS])
+def test_the_runner_reports_a_wrong_state_model_at_its_first_op(wrong, classes, name):
+  prog = _state_program(name)
+  profile = prog.profile
+  right, bad = _state_trace(prog, ap.make_model(profile)), _state_trace(prog, ap.make_model(profile, wrong))
+  first = next((i for i, (x, y) in enumerate(zip(right, bad)) if not _equal(x, y)), None)
+  assert first is not None, "this program never shows the wrong model: choose another"
+  assert prog[first]["op"] in classes, (first, prog[first]["op"])
+  with pytest.raises(ap.Mismatch) as err:
+    ap.run_program(prog, ap.make_model(profile, wrong), ap.make_model(profile))
+  text = str(err.value)
+  assert f"program seed {prog.seed}, profile {name}, op {first}: {prog[first]['op']}" in text, text
+  print(wrong.__name__, "->", text[:300])
   # a prefix that stops short of the op passes
   assert ap.run_program(prog, ap.make_model(profile, wrong), ap.make_model(profile), stop_after=first) == first

@@ -105,36 +105,14 @@ def _same_events(a, b, what):
 
 
 # ---- 1. against the oracle ------------------------------------------------------------------------
-class StartsModel(ModelEngine):
-  """The model with registered episode starts: a world that would auto-reset with rows[w] >= 0
-  takes the level's reset (what the replaced step left) and then becomes the row, writing what a
-  load writes."""
-  starts = None   # (the model's rows of the bank, rows [N])
-
-  def _advance(self, w, entry, auto_reset=None):
-    auto = self._auto_reset if auto_reset is None else auto_reset
-    if (self.starts is not None and self._started[w] and self._o[w].done and auto and
-        self.starts[1][w] >= 0):
-      bank, rows = self.starts
-      self._reset_world(w)
-      row = bank[int(rows[w])]
-      self._become(w, row)
-      if row["finished"]:
-        self._write_transition(w, 2, np.zeros(self.P), [])
-      else:
-        self._write_transition(w, 0, np.zeros(self.P), self._reset_events)
-      self._write_record_kinds(w)
-      return
-    super()._advance(w, entry, auto_reset)
-
-
+# (the model of registered episode starts is ModelEngine's own: tests/engine_model.py)
 _MODEL_BANKS = {}
 
 
 def _model_bank(name):
   """The model's own rows of the recipe's bank: the recipe's run, replayed on the oracles."""
   if name not in _MODEL_BANKS:
-    m = StartsModel(R.pack(name), N, auto_reset=True)
+    m = ModelEngine(R.pack(name), N, auto_reset=True)
     A = R.actions(m.P, m.num_actions)
     m.reset()
     rows = []
@@ -167,11 +145,11 @@ def test_step_and_step_many_against_the_oracle(name):
   mbank = _model_bank(name)
   for many in (False, True):
     e, bank, rows, drows, info = _registered(name, views)
-    m = StartsModel(R.pack(name), N, auto_reset=True)
+    m = ModelEngine(R.pack(name), N, auto_reset=True)
     for kind in views:
       m.bind(kind)
     m.reset()
-    m.starts = (mbank, rows)
+    m.set_episode_starts(mbank, rows)
     A = _actions(e)
     dA = torch.from_numpy(A).to(e.device)
     if many:
@@ -200,9 +178,9 @@ def test_step_and_step_many_against_the_oracle(name):
 def test_a_rollout_ring_against_the_oracle(name):
   T = 4
   e, bank, rows, drows, info = _registered(name)
-  m = StartsModel(R.pack(name), N, auto_reset=True)
+  m = ModelEngine(R.pack(name), N, auto_reset=True)
   m.reset()
-  m.starts = (_model_bank(name), rows)
+  m.set_episode_starts(_model_bank(name), rows)
   kinds = (E.OBS_WORLD_RGB, E.OBS_REWARD, E.OBS_STEP_TYPE)
   rings = {k: e.bind_ring(k, slots=T, tune=False) for k in kinds}
   mrings = {k: m.bind_ring(k, slots=T) for k in kinds}

@@ -256,42 +256,13 @@ def test_a_masked_world_is_the_unmasked_world_of_its_own_steps(name):
 
 
 # ---- 5. against the oracle ------------------------------------------------------------------------
-class ActiveModel(ModelEngine):
-  """The model under a mask: only the active worlds advance; the others write nothing.  Bound views
-  are drawn from all the records by every submission, as ever."""
-
-  def step(self, actions, active=None):
-    a = np.asarray(actions, np.int32).reshape(self.N, self.P)
-    self._begin()
-    for w in range(self.N):
-      if active is None or active[w]:
-        self._advance(w, ("step", a[w]))
-    self._end()
-
-  def step_many(self, actions, *, active=None, events=False, observations=(),
-                keep=("reward", "collective_reward", "step_type", "discount")):
-    a = np.asarray(actions, np.int32)
-    names = [k for k in E.STEP_MANY_KINDS if k in tuple(keep) or (k == "events" and events)]
-    keys = names + [int(k) for k in observations]
-    rows = {key: [] for key in keys}
-    self._begin()
-    for k in range(a.shape[0]):
-      for w in range(self.N):
-        if active is None or active[k][w]:
-          self._advance(w, ("step", a[k][w]))
-      for key in keys:
-        kind = E.STEP_MANY_NAMES.get(key, key)
-        rows[key].append(self.view_value(kind) if kind == E.OBS_LAYER else self._target(kind).copy())
-    self._end()
-    return {key: np.stack(v) for key, v in rows.items()}
-
-
+# (the model under a mask is ModelEngine's own: tests/engine_model.py)
 @pytest.mark.parametrize("name", R.PACKS)
 def test_step_and_step_many_against_the_oracle(name):
   views = (E.OBS_RGB, E.OBS_WORLD_RGB, E.OBS_LAYER) if name in PIXEL_PACKS else ()
   for many in (False, True):
     e = engine.Engine(R.pack(name), N, device=0)
-    m = ActiveModel(R.pack(name), N, auto_reset=True)
+    m = ModelEngine(R.pack(name), N, auto_reset=True)
     for kind in views:
       e.bind(kind).zero_()
       m.bind(kind)

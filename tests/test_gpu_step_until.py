@@ -15,9 +15,10 @@ import pytest
 import torch
 
 import states_recipe as R
+from engine_model import ModelEngine
 from meltingpot_amd import engine, substrate
 from test_gpu_episode_starts import PIXEL_PACKS, _plan, _same_as_model, _same_events
-from test_gpu_step_active import (KITCHEN, MASK, ActiveModel, _actions, _all_rows, _close, _engine, _keys,
+from test_gpu_step_active import (KITCHEN, MASK, _actions, _all_rows, _close, _engine, _keys,
                                   _leaves, _obs_kinds, _same, _same_engines, _same_leaves, _same_rows)
 
 pytestmark = pytest.mark.gpu
@@ -289,46 +290,12 @@ def test_everything_stopped_touches_nothing(name):
 
 
 # ---- 6. against the oracle --------------------------------------------------------------------------
-class UntilModel(ActiveModel):
-  """The model with a stop state: a world runs step k where the mask says so and it has not stopped;
-  after a step it ran, LAST or a non-zero reward (where asked for) stops it."""
-
-  def step_many(self, actions, *, active=None, stop=0, stopped=None, gamma=1.0, events=False, observations=(),
-                keep=("reward", "collective_reward", "step_type", "discount")):
-    a = np.asarray(actions, np.int32)
-    names = [k for k in E.STEP_MANY_KINDS if k in tuple(keep) or (k == "events" and events)]
-    keys = names + [int(k) for k in observations]
-    rows = {key: [] for key in keys}
-    stopped = np.zeros(self.N, np.uint8) if stopped is None else stopped
-    ran = np.zeros(self.N, np.int32)
-    ret = np.zeros((self.N, self.P), np.float64)
-    g = np.ones(self.N, np.float64)
-    self._begin()
-    for k in range(a.shape[0]):
-      for w in range(self.N):
-        if (active is None or active[k][w]) and not stopped[w] and self._started[w]:
-          self._advance(w, ("step", a[k][w]))
-          ran[w] += 1
-          r, kind = self._target(E.OBS_REWARD)[w], int(self._target(E.OBS_STEP_TYPE)[w])
-          ret[w] = ret[w] + g[w] * r
-          g[w] = g[w] * np.float64(gamma)
-          reason = (LAST if (stop & LAST) and kind == 2 else 0) | (REWARD if (stop & REWARD) and (r != 0).any() else 0)
-          if reason:
-            stopped[w] = reason
-      for key in keys:
-        kind = E.STEP_MANY_NAMES.get(key, key)
-        rows[key].append(self.view_value(kind) if kind == E.OBS_LAYER else self._target(kind).copy())
-    self._end()
-    out = {key: np.stack(v) for key, v in rows.items()}
-    out.update(stopped=stopped, ran=ran, returns=ret)
-    return out
-
-
+# (the model with a stop state is ModelEngine's own: tests/engine_model.py)
 @pytest.mark.parametrize("name", R.PACKS)
 def test_step_many_against_the_oracle(name):
   views = (E.OBS_RGB, E.OBS_WORLD_RGB, E.OBS_LAYER) if name in PIXEL_PACKS else ()
   e = engine.Engine(R.pack(name), N, device=0)
-  m = UntilModel(R.pack(name), N, auto_reset=True)
+  m = ModelEngine(R.pack(name), N, auto_reset=True)
   for kind in views:
     e.bind(kind).zero_()
     m.bind(kind)
@@ -340,7 +307,8 @@ def test_step_many_against_the_oracle(name):
   record = tuple(k for k in m.record_scalars)
   got = e.step_many(dA, active=dM, until=("last", "reward"), returns=True, gamma=0.97, events=True,
                     observations=record)
-  ref = m.step_many(A, active=MASK, stop=LAST | REWARD, gamma=0.97, events=True, observations=record)
+  ref = m.step_many(A, active=MASK, stop=LAST | REWARD, returns=True, gamma=0.97, events=True,
+                    observations=record)
   for key in ("reward", "collective_reward", "step_type", "discount") + record:
     assert np.array_equal(got[key].cpu().numpy(), ref[key]), (name, key)
   for k in range(K):
