@@ -16,12 +16,19 @@ import subprocess
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.path.join(_HERE, "liboracle.so")
+# MP_ORACLE_LIB names another build of the same sources to load instead (the Makefile's `cov`
+# target: tests/tools/oracle_coverage.py); subprocesses that replay worlds inherit it
+_LIB_PATH = os.environ.get("MP_ORACLE_LIB") or os.path.join(_HERE, "liboracle.so")
 _lib = None
 
 
 def build(force: bool = False) -> str:
-  """Compiles liboracle.so with gcc (Makefile in this directory)."""
+  """Compiles liboracle.so with gcc (Makefile in this directory); a library named by
+  MP_ORACLE_LIB is its owner's to build."""
+  if os.environ.get("MP_ORACLE_LIB"):
+    if not os.path.exists(_LIB_PATH):
+      raise FileNotFoundError(f"MP_ORACLE_LIB={_LIB_PATH} does not exist")
+    return _LIB_PATH
   if force or not os.path.exists(_LIB_PATH):
     subprocess.run(["make", "-s", "-C", _HERE] + (["-B"] if force else []),
                    check=True)

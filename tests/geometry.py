@@ -74,14 +74,21 @@ def _avatar_views(settings):
 
 
 def settings(name, width=None, height=None, topology=None, view=None, open_edges=False,
-             roles=None):
+             roles=None, spawn_points=None):
   """The recorded lab2d settings of `name` with the edits applied.  `view`: (left, right,
-  forward, backward) of every Avatar."""
+  forward, backward) of every Avatar.  `spawn_points`: (character, k): only the first k cells of
+  that character keep it (in reading order), the others become the level's floor — a map with
+  few spawn points."""
   stock_roles, border, floor = LEVELS[name]
   s, _, _ = refdata.build_settings(name, roles or stock_roles)
   sim = s["simulation"]
   if width or height or open_edges:
     sim["map"] = resize_map(sim["map"], width, height, border, floor, open_edges)
+  if spawn_points is not None:
+    char, keep = spawn_points
+    assert char != floor and sim["map"].count(char) >= keep > 0, spawn_points
+    head, *rest = sim["map"].split(char)
+    sim["map"] = head + "".join((char if i < keep else floor) + part for i, part in enumerate(rest))
   if topology is not None:
     s["topology"] = topology
   if view is not None:
@@ -94,10 +101,10 @@ def settings(name, width=None, height=None, topology=None, view=None, open_edges
 
 @functools.lru_cache(maxsize=None)
 def pack(name, width=None, height=None, topology=None, view=None, open_edges=False,
-         roles=None):
+         roles=None, spawn_points=None):
   """Lowered pack bytes of `settings(...)`, with the config's ACTION_SET."""
   from meltingpot_amd import builder, substrate
-  s = settings(name, width, height, topology, view, open_edges, roles)
+  s = settings(name, width, height, topology, view, open_edges, roles, spawn_points)
   _, blob, _ = builder.lower_settings(s, action_set=substrate.get_config(name).action_set)
   return blob
 

@@ -79,6 +79,21 @@ def _held(o, t, p):
   return -1
 
 
+def soup_ops():
+  """The script of test_a_scripted_soup, stated once (the test below plays exactly these, and
+  tests/situations.py runs them on the GPU): ("place", p, x, y, orient) and ("step", interact of
+  player 0, interact of player 1)."""
+  ops = [("place", 1, 5, 2, 0)]
+  for rep in range(3):
+    ops += [("place", 0, 3, 1, 3), ("step", 1, 0), ("place", 0, 4, 1, 0), ("step", 0, 0), ("step", 1, 0),
+            ("step", 0, 0)]
+  ops += [("step", 0, 0)] * 23
+  ops += [("place", 0, 3, 2, 2), ("step", 0, 0), ("step", 1, 0), ("place", 0, 4, 1, 0), ("step", 0, 0),
+          ("step", 1, 0), ("place", 1, 3, 1, 0), ("place", 0, 5, 2, 2), ("step", 0, 0), ("step", 1, 0),
+          ("step", 0, 0)]
+  return ops
+
+
 def test_a_scripted_soup():
   """cramped: three tomatoes from the dispenser into the pot, one at a time; the pot cooks for 20
   ticks while its bar fills; a dish from the dish dispenser takes the soup; the delivery location
@@ -88,15 +103,23 @@ def test_a_scripted_soup():
   names = _names(t)
   o = oracle.Oracle(pk, util.world_seed(0), 2); o.reset()
   F = lambda move=0, turn=0, interact=0: [move, turn, interact]
-  step = lambda a0, a1=F(): o.step_fields(np.array([a0, a1], np.int32))
+  ops = iter(soup_ops())
+
+  def step(a0, a1=F()):
+    assert next(ops) == ("step", a0[2], a1[2]) and not (a0[0] or a0[1] or a1[0] or a1[1])
+    return o.step_fields(np.array([a0, a1], np.int32))
+
+  def place(*where):
+    assert next(ops) == ("place",) + where
+    return o.place_avatar(*where)
   pot_state = lambda: names[int(o.dump()[0][4, 0, 4])]
   bar_state = lambda: names[int(o.dump()[0][5, 0, 4])]
-  assert o.place_avatar(1, 5, 2, 0)
+  assert place(1, 5, 2, 0)
   for rep in range(3):
-    assert o.place_avatar(0, 3, 1, 3)            # facing W: the tomato dispenser at (2, 1)
+    assert place(0, 3, 1, 3)            # facing W: the tomato dispenser at (2, 1)
     step(F(interact=1))
     assert _held(o, t, 0) == TOMATO and o.events() == []
-    assert o.place_avatar(0, 4, 1, 0)            # facing N: the pot at (4, 0)
+    assert place(0, 4, 1, 0)            # facing N: the pot at (4, 0)
     step(F())                                    # (the beam's cooldown of one frame)
     step(F(interact=1))
     assert _held(o, t, 0) == EMPTY and o.events() == [(DROPPED, 1, TOMATO)]
@@ -109,19 +132,27 @@ def test_a_scripted_soup():
   assert pot_state().endswith("cooked") and bars[-1].endswith("loading_bar_10")
   assert bars[0].endswith("loading_bar_0") and bars[5].endswith("loading_bar_3")
   # the dispenser still holds its tomato; a second interaction in one frame finds a container used
-  assert o.place_avatar(0, 3, 2, 2)              # facing S: the dish dispenser at (3, 3)
+  assert place(0, 3, 2, 2)              # facing S: the dish dispenser at (3, 3)
   step(F()); step(F(interact=1))
   assert _held(o, t, 0) == DISH
-  assert o.place_avatar(0, 4, 1, 0)
+  assert place(0, 4, 1, 0)
   step(F()); step(F(interact=1))
   assert _held(o, t, 0) == SOUP and o.events() == [(COLLECTED, 1, SOUP)]
   assert pot_state().endswith("empty_empty_empty")
-  assert o.place_avatar(1, 3, 1, 0) and o.place_avatar(0, 5, 2, 2)   # facing S: the delivery location at (5, 3)
+  assert place(1, 3, 1, 0) and place(0, 5, 2, 2)   # facing S: the delivery location at (5, 3)
   step(F()); step(F(interact=1))
   assert o.rewards().tolist() == [20.0, 20.0] and o.events() == [(ACCEPTED, 1, SOUP)]
   assert _held(o, t, 0) == EMPTY
   step(F())
   assert o.rewards().tolist() == [0.0, 0.0]
+  assert next(ops, None) is None
+
+
+# The scene of test_two_avatars_one_counter_in_one_frame, stated once (tests/situations.py runs it
+# on the GPU): circuit's island counters (3, 2) .. (6, 2) are reachable from above and below;
+# player 0 above counter (4, 2) facing S, player 1 below it facing N: (x, y, orient)
+COUNTER_LAYOUT = "collaborative_cooking__circuit"
+COUNTER_PLACES = ((4, 1, 2), (4, 3, 0))
 
 
 def test_two_avatars_one_counter_in_one_frame():
@@ -138,11 +169,11 @@ def test_two_avatars_one_counter_in_one_frame():
     # on the counter (4, 3) reached from (4, 2) by one and ... skip unless both can stand.
     break
   # circuit: the island counters (3, 2) .. (6, 2) are reachable from above and below
-  pk = stocked(engine.load_pack("collaborative_cooking__circuit"))
+  pk = stocked(engine.load_pack(COUNTER_LAYOUT))
   t = pack.loads(pk)
   for seed in range(16):
     o = oracle.Oracle(pk, util.world_seed(seed), 2); o.reset()
-    assert o.place_avatar(0, 4, 1, 2) and o.place_avatar(1, 4, 3, 0)   # above facing S, below facing N: counter (4, 2)
+    assert all(o.place_avatar(p, *place) for p, place in enumerate(COUNTER_PLACES))
     before = [_held(o, t, p) for p in range(2)]
     assert before == [EMPTY, EMPTY]
     o.step_fields(np.array([[0, 0, 1], [0, 0, 1]], np.int32))

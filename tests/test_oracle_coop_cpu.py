@@ -106,6 +106,23 @@ def test_rules_hold_over_rollouts_with_plentiful_ore(coop_mining_pack):
   assert seen[MINING] > 200 and seen[EXTRACTION] > 100 and gold_extractions >= 3, (seen, gold_extractions)
 
 
+# The scripted scenes, stated once: tests/situations.py runs the same ones on the GPU.
+NOOP, MINE = 0, 7
+ORE_CELL = 10 * 27 + 5          # row 10, "WOOOOOOOOOWOOOOO...": x = 5 is ore, so are x = 4 and x = 6
+# A stands left of the ore facing east, B right of it facing west, C far away: (x, y, orient)
+SCENE_PLACES = ((4, 10, 1), (6, 10, 3), (20, 20, 0))
+_IDLE = (NOOP, NOOP, NOOP)
+# gold: A alone, the window of 3 frames runs out; A again and B two frames later, inside the window
+GOLD_SCRIPT = ((MINE, NOOP, NOOP), _IDLE, _IDLE, _IDLE, (MINE, NOOP, NOOP), _IDLE, (NOOP, MINE, NOOP))
+# iron: both in one frame (after the cooldown of 3 frames)
+IRON_SCRIPT = (_IDLE, _IDLE, _IDLE, (MINE, MINE, NOOP))
+
+
+def scripted_pack(coop_mining_pack):
+  """The pack of the scripted scenes: nothing grows, no episode end."""
+  return util.patch_pack(coop_mining_pack, tables={"cm_thr": [0, 0, 0]})
+
+
 def _scripted(pk, players=3):
   """A world whose avatars the test places: returns (oracle, tables, a free ore cell with
   free cells to its left and right and two rows below)."""
@@ -126,29 +143,28 @@ def test_two_miners_extract_gold_and_one_alone_does_not(coop_mining_pack):
   get 8.0 in B's frame, two pair events, the ore is gone."""
   if not hasattr(oracle.Oracle, "set_cell_state"):
     pytest.skip("oracle without the set_cell_state test hook")
-  pk = util.patch_pack(coop_mining_pack, tables={"cm_thr": [0, 0, 0]})   # nothing grows, no episode end
+  pk = scripted_pack(coop_mining_pack)
   o, t = _scripted(pk)
   s_wait, s_iron, s_gold, _, s_part = (int(x) for x in t["cm_states"])
-  cell = 13 * 27 + 4          # row 13: "WOOWWWWOOOO...": (x=1,2 ore) -> use row 10 instead
-  cell = 10 * 27 + 5          # "WOOOOOOOOOWOOOOO...": x=5 is ore, so are x=4 and x=6
+  cell = ORE_CELL
   ore_layer = int(t["state_layer"][s_wait])
   state_at = lambda: int(o.dump()[0][ore_layer, cell // 27, cell % 27])
-  NOOP, MINE = 0, 7
-  # A stands left of the ore facing east, B right of it facing west, C far away
-  assert o.place_avatar(0, 4, 10, 1) and o.place_avatar(1, 6, 10, 3) and o.place_avatar(2, 20, 20, 0)
+  assert all(o.place_avatar(p, *place) for p, place in enumerate(SCENE_PLACES))
   _set_ore(o, t, cell, s_gold)
-  o.step(np.array([MINE, NOOP, NOOP], np.int32))
+  gold, iron = iter(GOLD_SCRIPT), iter(IRON_SCRIPT)
+  o.step(np.array(next(gold), np.int32))
   assert state_at() == s_part and list(o.rewards()) == [0, 0, 0]
   assert o.events() == [(MINING, 1, 2)]
   for k in range(2):
-    o.step(np.array([NOOP, NOOP, NOOP], np.int32)); assert state_at() == s_part
-  o.step(np.array([NOOP, NOOP, NOOP], np.int32))
+    o.step(np.array(next(gold), np.int32)); assert state_at() == s_part
+  o.step(np.array(next(gold), np.int32))
   assert state_at() == s_gold                      # the window ran out: back to raw
   assert int(o.dump()[2][6]) == 0                  # ... and the miners are forgotten
   # A mines again (its cooldown of 3 is over), B two frames later
-  o.step(np.array([MINE, NOOP, NOOP], np.int32)); assert state_at() == s_part
-  o.step(np.array([NOOP, NOOP, NOOP], np.int32))
-  o.step(np.array([NOOP, MINE, NOOP], np.int32))
+  o.step(np.array(next(gold), np.int32)); assert state_at() == s_part
+  o.step(np.array(next(gold), np.int32))
+  o.step(np.array(next(gold), np.int32))
+  assert next(gold, None) is None
   assert list(o.rewards()) == [8.0, 8.0, 0.0] and state_at() == s_wait
   assert sorted(o.events()) == sorted([(MINING, 2, 2), (EXTRACTION, 1, 2), (EXTRACTION, 2, 2),
                                        (PAIR, 1, (2 << 2) | 2), (PAIR, 2, (1 << 2) | 2)])
@@ -156,7 +172,8 @@ def test_two_miners_extract_gold_and_one_alone_does_not(coop_mining_pack):
   # first hit queues is processed a flush later: the second still finds ironRaw)
   _set_ore(o, t, cell, s_iron)
   for _ in range(3):
-    o.step(np.array([NOOP, NOOP, NOOP], np.int32))
-  o.step(np.array([MINE, MINE, NOOP], np.int32))
+    o.step(np.array(next(iron), np.int32))
+  o.step(np.array(next(iron), np.int32))
+  assert next(iron, None) is None
   assert list(o.rewards()) == [1.0, 1.0, 0.0] and state_at() == s_wait
   o.close()

@@ -123,6 +123,14 @@ def test_rules_hold_over_rollouts_with_plentiful_tokens(gift_pack):
       gifts, refined, picked, consumed, capped)
 
 
+# The scene of test_a_scripted_refinement_chain, stated once (tests/situations.py runs it on the
+# GPU): player 0 at (3, 1) facing E, player 1 at (7, 1) facing W, a live token at (4, 1), then the
+# script of action ids (1 FORWARD, 7 refineAndGift, 8 consumeTokens)
+CHAIN_PLACES = ((3, 1, 1), (7, 1, 3))
+CHAIN_TOKEN = (4, 1)
+CHAIN_SCRIPT = ((1, 0), (7, 0), (0, 7), (0, 0), (0, 0), (7, 0), (8, 8))
+
+
 def test_a_scripted_refinement_chain(gift_pack):
   """Player 0 picks a raw token and faces player 1 three cells away: the gift turns it into
   five tokens of the next type (event: source type 1, the recipient now holds 5); player 1
@@ -133,27 +141,29 @@ def test_a_scripted_refinement_chain(gift_pack):
   s_live = int(t["gr_states"][1])
   W = int(t["hdr"][lower.HDR_W])
   # an open row of the map: y = 1, x = 1 .. 25 are token cells (gift_refinements.py:71)
-  assert o.place_avatar(0, 3, 1, 1)      # facing E
-  assert o.place_avatar(1, 7, 1, 3)      # facing W
-  cell = 1 * W + 4
+  assert all(o.place_avatar(p, *place) for p, place in enumerate(CHAIN_PLACES))   # facing E, facing W
+  cell = CHAIN_TOKEN[1] * W + CHAIN_TOKEN[0]
   assert cell in t["token_cells"]
-  assert o.set_cell_state(int(t["state_layer"][s_live]), 4, 1, s_live)
-  noop = np.zeros(2, np.int32)
-  o.step(np.array([1, 0], np.int32))                 # 0 steps E onto the live token: picked
+  assert o.set_cell_state(int(t["state_layer"][s_live]), *CHAIN_TOKEN, s_live)
+  script = iter(CHAIN_SCRIPT)
+  noop = np.array(CHAIN_SCRIPT[3], np.int32)
+  assert not noop.any()
+  o.step(np.array(next(script), np.int32))           # 0 steps E onto the live token: picked
   inv = o.inventories()[0]
   assert inv.tolist() == [[1, 0, 0], [0, 0, 0]]
-  o.step(np.array([7, 0], np.int32))                 # 0 gifts: 1 x type 1 -> 5 x type 2
+  o.step(np.array(next(script), np.int32))           # 0 gifts: 1 x type 1 -> 5 x type 2
   assert o.inventories()[0].tolist() == [[0, 0, 0], [0, 5, 0]]
   ev = [e for e in o.events() if e[0] == GIFT]
   assert [decode_gift(a, b) for _, a, b in ev] == [(0, 0, 1, 5)]
   assert o.ready_to_shoot().tolist() == [0.0, 1.0]
-  o.step(np.array([0, 7], np.int32))                 # 1 gifts back: 1 x type 2 -> 5 x type 3
+  o.step(np.array(next(script), np.int32))           # 1 gifts back: 1 x type 2 -> 5 x type 3
   assert o.inventories()[0].tolist() == [[0, 0, 5], [0, 4, 0]]
   assert [decode_gift(a, b) for _, a, b in o.events() if _ == GIFT] == [(1, 1, 0, 5)]
-  o.step(noop); o.step(noop)
-  o.step(np.array([7, 0], np.int32))                 # 0 gifts a type-3 token: passed on as it is
+  o.step(np.array(next(script), np.int32)); o.step(np.array(next(script), np.int32))
+  o.step(np.array(next(script), np.int32))           # 0 gifts a type-3 token: passed on as it is
   assert o.inventories()[0].tolist() == [[0, 0, 4], [0, 4, 1]]
   assert [decode_gift(a, b) for _, a, b in o.events() if _ == GIFT] == [(0, 2, 1, 1)]
-  o.step(np.array([8, 8], np.int32))                 # both consume
+  o.step(np.array(next(script), np.int32))           # both consume
+  assert next(script, None) is None
   assert o.rewards().tolist() == [4.0, 5.0]
   assert o.inventories()[0].tolist() == [[0, 0, 0], [0, 0, 0]]

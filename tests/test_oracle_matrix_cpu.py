@@ -127,16 +127,22 @@ def _step(o, *acts):
   return o.step(np.asarray(acts, np.int32))
 
 
+# The placements of the scripted interaction, stated once (tests/situations.py runs the scenes on
+# the GPU): under the two resources, one FORWARD collects them; then face to face on row 6
+COLLECT_PLACES = ((7, 6, N), (15, 6, N))
+FACING_PLACES = ((9, 6, E), (11, 6, W))
+
+
 def _setup_interaction(o):
   """prisoners_dilemma__repeated map (…repeated.py:52-68): row 5 is
   'W      11a   a22      W', row 6 is free.  Player 1 collects a class-1 resource
   at (7, 5), player 2 a class-2 one at (15, 5); then they face each other on row 6."""
-  assert o.place_avatar(0, 7, 6, N) and o.place_avatar(1, 15, 6, N)
+  assert all(o.place_avatar(p, *place) for p, place in enumerate(COLLECT_PLACES))
   _step(o, FORWARD, FORWARD)
   inv, _ = o.inventories()
   assert inv.tolist() == [[2.0, 1.0], [1.0, 2.0]]      # start at 1 of each (components.lua:233-237)
   assert sorted(o.events()) == [(12, 1, 1), (12, 2, 2)]  # collected_resource (player, class)
-  assert o.place_avatar(0, 9, 6, E) and o.place_avatar(1, 11, 6, W)
+  assert all(o.place_avatar(p, *place) for p, place in enumerate(FACING_PLACES))
 
 
 def test_collecting_fills_the_inventory_and_shows_the_ready_marker():
@@ -304,7 +310,7 @@ def test_zero_initial_inventory_and_tie_breaking():
 
 def test_unready_players_cannot_be_interacted_with():
   o = _oracle()
-  assert o.place_avatar(0, 9, 6, E) and o.place_avatar(1, 11, 6, W)
+  assert all(o.place_avatar(p, *place) for p, place in enumerate(FACING_PLACES))
   _step(o, INTERACT, NOOP)     # nobody has collected anything (disallowUnreadyInteractions)
   assert not [e for e in o.events() if e[0] == 11]
   _, inter = o.inventories()
