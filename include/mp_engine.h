@@ -1131,6 +1131,75 @@ typedef struct {
   uint64_t reserved[5];        /* 0 */
 } MpStepUntil;
 
+/* Stepping the worlds a device index list names: an MpStepUntil request whose launch has one wave
+ * per ENTRY of the list instead of one per world of the engine — a tree search or a population
+ * that keeps a pool of N worlds and acts on M of them a round hands over [K][M][P] actions and
+ * gets [K][M] rows back, and the launch is ceil(M / 4) workgroups whatever N is.  Rides
+ * mp_restore, recognised by its size: `bytes` = sizeof(MpStepListed), `host_buf` a HOST
+ * MpStepListed with struct_size set to it.  include/mp_step_listed.h wraps it as inline C
+ * functions.  Every other request and entry point keeps doing exactly what it does, and an engine
+ * that never gets a list allocates nothing for it.
+ *
+ * The leading fields are MpStepUntil's, at its offsets; then `worlds`, device int32 [count], read
+ * in place by the launch: entry i is stepped by wave i.  count = M is the host's; nothing about
+ * the geometry is read from device memory.
+ *
+ * The defining identity.  Let mask[k][w] = 1 iff some entry i has worlds[i] == w and
+ * active[k][i] != 0 (all ones with a NULL active), and full_actions[k][worlds[i]] = actions[k][i].
+ * The request leaves every record, counter (mp_counters), in-place or bound non-pixel output,
+ * event row and `stopped` byte exactly as the MpStepUntil request over all N worlds with that mask
+ * and those actions leaves them.  Every per-call tensor is the gather of that request's:
+ *   actions  [K][M][P] ([K][M][P][A] with fields = 1); actions_step_bytes as ever, sized for M.
+ *   active   device uint8 [K][M] (active_step_bytes 0: one row [M] for every step; otherwise
+ *            >= M), or NULL: all ones.
+ *   rows     every kind's row k is [M][...]: row[k][i] == full_row[k][worlds[i]], the carry rule
+ *            included (row 0 of a skipped step is carried from the world's in-place buffer into
+ *            column i).  MP_STEP_ROW_STATE rows are [M][S], MP_STEP_ROW_HASH rows u64 [M].
+ *   ran      device int32 [M], returns device float64 [M][P]: by entry.
+ *   stopped  the exception: uint8 [N], indexed by WORLD, as argument and as result — the one
+ *            tensor meant to persist over requests, which may name different lists.
+ * The episode-start registration (rows [N]), next_orders and every in-place buffer are by world,
+ * as ever.  An unlisted world is a skipped world in every step: nothing of it is touched.  Bound
+ * pixel views are redrawn once after the request for all N worlds, as for a masked request;
+ * MpInfo.fused and the next unlisted step are what they were.
+ *
+ * Bad entries.  worlds[i] outside [0, N) is never used as an index.  An entry that repeats an
+ * earlier entry's world runs nothing: the lowest i steps the world (ownership is decided by a
+ * small claim launch in front of the step kernels, so two waves never hold one record).  In both
+ * cases element i of every per-call tensor (rows, ran, returns) is left as it was, and the next
+ * synchronising call returns MP_ERR_INVALID once, naming this request, the entry and the value
+ * (one of several bad entries is named); the engine stays usable.
+ *
+ * Refused before any launch, the engine left as it was.  MP_ERR_INVALID: everything MpStepUntil
+ * refuses, with this request's name and the extents sized for M; NULL worlds; count < 1 or
+ * count > N (more entries than worlds must repeat one); a worlds that is not 4-byte aligned
+ * device memory of the engine's device with [worlds, worlds + count) inside one allocation; a
+ * worlds that overlaps a row buffer, stopped, ran or returns; non-zero reserved words.
+ * MP_ERR_UNSUPPORTED, as for a mask: a rollout ring is bound; an engine created with
+ * MpConfig.unfused = 2 that has a pixel view bound. */
+typedef struct {
+  uint32_t struct_size;        /* = sizeof(MpStepListed) */
+  int32_t steps;               /* K */
+  int32_t fields;              /* 0: discrete ids [K][M][P]; 1: raw fields [K][M][P][A] */
+  int32_t num_rows;
+  const int32_t* actions;      /* device */
+  uint64_t actions_step_bytes; /* 0: the same block every step */
+  const MpStepRow* rows;       /* HOST array [num_rows]; every buffer has M columns */
+  const uint8_t* active;       /* device uint8 [K][M], or NULL: all ones */
+  uint64_t active_step_bytes;  /* 0: the same row every step; otherwise >= M */
+  uint32_t stop;               /* MP_STOP_* bits; 0: nothing stops a world */
+  uint32_t pad;                /* 0 */
+  uint8_t* stopped;            /* device uint8 [N] (by world), read and written, or NULL */
+  int32_t* ran;                /* device int32 [M], written, or NULL */
+  double* returns;             /* device float64 [M][P], written, or NULL */
+  double gamma;                /* finite; 1.0: the plain sum */
+  uint64_t reserved[5];        /* 0 */
+  const int32_t* worlds;       /* device int32 [count]: the world of entry i */
+  int32_t count;               /* M: 1 <= M <= N */
+  int32_t reserved2;           /* 0 */
+  uint64_t reserved3[3];       /* 0 */
+} MpStepListed;
+
 /* Throughput / event counters accumulated on device since creation
  * (synchronises).  These are what the multi-GPU bench all-reduces. */
 enum {

@@ -25,6 +25,7 @@
 #include "step_common.h"
 #include "step_many.h"
 #include "step_until.h"
+#include "step_listed.h"
 #include "state_obs.h"
 #include "state_view.h"
 #include "state_check.h"
@@ -195,6 +196,10 @@ struct MpEngine {
   // spec's, replaced behind a wait for the stream when a request brings another
   uint32_t* d_hash_mask = nullptr;
   uint32_t* d_hash_custom = nullptr;
+  // An MpStepListed request's claim table (step_listed.h), u64 [N], allocated and zeroed by the
+  // first such request, and the generation of the most recent one
+  unsigned long long* d_listed_claim = nullptr;
+  uint32_t listed_generation = 0;
   state_hash::Spec hash_custom = {};   // (custom == 0: none yet)
   state_hash::Layout hash_layout() const {
     return state_hash::layout_of(check, substrate == MPK_SUBSTRATE_THE_MATRIX ? sub.mx.player_block : -1);
@@ -395,6 +400,11 @@ int sync_and_check(MpEngine* e, const char* who) {
                   "%s: MpStatesView: %s[%u] = %d is %s; element %u of the destination was left as it was",
                   who, what == kFaultViewRow ? "rows" : "players", at, (int)index,
                   what == kFaultViewRow ? "not a row of the bank" : "not a player of this engine", at);
+    if (what == kFaultListedWorld || what == kFaultListedRepeat)
+      return fail(MP_ERR_INVALID,
+                  "%s: MpStepListed: worlds[%u] = %d %s; the entry ran nothing and element %u of every per-call "
+                  "tensor was left as it was", who, at, (int)index,
+                  what == kFaultListedWorld ? "is not a world of this engine" : "repeats an earlier entry's world", at);
     if (what == kFaultHashRow)
       return fail(MP_ERR_INVALID,
                   "%s: MpStatesHash: rows[%u] = %d is not a row of the bank (MP_HASH_WORLDS: no world of this "
@@ -431,7 +441,8 @@ void draw(MpEngine* e, uint8_t* rgb, uint8_t* wrgb, int pool_k = 1) {
 // draw-only launches of the unfused path; NULL: a single step)
 int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
            const uint8_t* bank = nullptr, const int32_t* src = nullptr, int bank_rows = 0,
-           const StepManyLaunch* many = nullptr, const UntilArgs* until = nullptr) {
+           const StepManyLaunch* many = nullptr, const UntilArgs* until = nullptr,
+           const ListArgs* list = nullptr) {
   stepk::StepArgs args;
   args.state = e->d_state; args.actions = actions; args.reset_mask = mask;
   args.bank = bank; args.src = src; args.bank_rows = bank_rows;
@@ -457,7 +468,8 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
     if (many) {
       StepManyLaunch l = *many;
       l.starts = starts;
-      if (until) launch_step_until(e->t, e->sub, args, l, *until, e->stream);   // (MpStepUntil)
+      if (list) launch_step_listed(e->t, e->sub, args, l, *until, *list, e->stream);   // (MpStepListed)
+      else if (until) launch_step_until(e->t, e->sub, args, l, *until, e->stream);   // (MpStepUntil)
       else if (l.active.active) launch_step_active(e->t, e->sub, args, l, e->stream);   // (MpStepActive)
       else launch_step_many(e->t, e->sub, args, l, e->stream);
     } else if (starts) {
@@ -1022,6 +1034,8 @@ int plan_views(MpEngine* e, const MpDevOptions* dev) {
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the episode-start kernels failed: %d", rc);
   if (int rc = prepare_step_active())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the masked K-step kernels failed: %d", rc);
+  if (int rc = prepare_step_listed())
+    return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the listed K-step kernels failed: %d", rc);
   if (int rc = prepare_step_until())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the stopping K-step kernels failed: %d", rc);
   if (dev && dev->verbose)
@@ -1228,7 +1242,7 @@ void mp_destroy(MpEngine* e) {
   void* bufs[] = {e->d_pack, e->d_extra, e->d_stepblob, e->d_debug, e->d_state, e->d_scalars,
                   e->d_actions, e->d_fields, e->d_mask, e->d_seeds, e->d_atlas, e->d_ctr, e->d_claim,
                   e->d_layer_lut, e->d_obs_rows, e->d_obs_stash, e->d_check, e->d_hash_mask,
-                  e->d_hash_custom};
+                  e->d_hash_custom, e->d_listed_claim};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   for (int i = 0; i < MpEngine::kHostSlots; ++i)
@@ -1617,10 +1631,13 @@ static int world_states(MpEngine* e, MpWorldStates* r, bool restore) {
 // A K-step request (include/mp_engine.h: MpStepMany, MpStepTrajectory, MpStepActive, MpStepUntil),
 // whichever struct it came in: `r` names the rows it wants, `who` is the request's own name in the
 // messages, `mask` (MpStepActive, MpStepUntil) the device mask and the distance between two of its
-// rows, `until` (MpStepUntil only, whose mask may be NULL) the stop state.  Everything is checked
+// rows, `until` (MpStepUntil, MpStepListed, whose mask may be NULL) the stop state, `list`
+// (MpStepListed only) the world list: the actions, the mask, the rows, ran and returns then have
+// list->count columns where the others have N (`stopped` stays by world).  Everything is checked
 // here, against kStepRowKinds (step_many.h) and mp_obs_bytes, before the one submission.
 static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r,
-                        const ActiveArgs* mask = nullptr, const UntilArgs* until = nullptr) {
+                        const ActiveArgs* mask = nullptr, const UntilArgs* until = nullptr,
+                        ListArgs* list = nullptr) {
   if (!e || !r.actions) return fail(MP_ERR_INVALID, "%s: NULL engine or actions", who);
   if (r.steps < 1 || r.steps > MP_STEP_MANY_MAX)
     return fail(MP_ERR_INVALID, "%s: steps %d is outside [1, %d]", who, r.steps, MP_STEP_MANY_MAX);
@@ -1629,7 +1646,16 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r,
   if (!e->has_state)
     return fail(MP_ERR_INVALID, "%s: the engine has never been reset; there is nothing to step", who);
   const uint64_t K = (uint64_t)r.steps, N = (uint64_t)e->N, P = (uint64_t)e->t.P;
-  const uint64_t ablock = N * P * (r.fields ? (uint64_t)e->t.nfields : 1u) * 4u;
+  if (list) {
+    if (!list->worlds) return fail(MP_ERR_INVALID, "%s: NULL worlds", who);
+    if (list->count < 1 || (uint64_t)list->count > N)
+      return fail(MP_ERR_INVALID, "%s: count %d is outside [1, %llu] (more entries than worlds must repeat one)", who,
+                  list->count, (unsigned long long)N);
+    if ((uintptr_t)list->worlds & 3)
+      return fail(MP_ERR_INVALID, "%s: worlds %p is not 4-byte aligned", who, (const void*)list->worlds);
+  }
+  const uint64_t C = list ? (uint64_t)list->count : N;   // the columns of every per-call tensor
+  const uint64_t ablock = C * P * (r.fields ? (uint64_t)e->t.nfields : 1u) * 4u;
   if (r.actions_step_bytes != 0 && (r.actions_step_bytes < ablock || r.actions_step_bytes % 4))
     return fail(MP_ERR_INVALID, "%s: actions_step_bytes %llu is neither 0 nor a multiple of 4 that "
                 "holds one step's block of %llu bytes", who, (unsigned long long)r.actions_step_bytes,
@@ -1645,17 +1671,20 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r,
   char name[64];
   snprintf(name, sizeof name, "%s (actions)", who);
   if (int rc = check_bank(e, r.actions, (K - 1) * r.actions_step_bytes + ablock, name)) return rc;
+  snprintf(name, sizeof name, "%s (worlds)", who);
+  if (list)
+    if (int rc = check_bank(e, list->worlds, C * 4u, name)) return rc;
   StepManyLaunch l = {};
   if (mask) {
     if (!mask->active && !until) return fail(MP_ERR_INVALID, "%s: NULL active", who);
     if (!mask->active && mask->step != 0)
       return fail(MP_ERR_INVALID, "%s: active_step_bytes %llu with a NULL active", who, (unsigned long long)mask->step);
-    if (mask->step != 0 && (uint64_t)mask->step < N)
+    if (mask->step != 0 && (uint64_t)mask->step < C)
       return fail(MP_ERR_INVALID, "%s: active_step_bytes %llu is neither 0 nor at least one step's row of %llu "
-                  "bytes", who, (unsigned long long)mask->step, (unsigned long long)N);
+                  "bytes", who, (unsigned long long)mask->step, (unsigned long long)C);
     snprintf(name, sizeof name, "%s (active)", who);
     if (mask->active)
-      if (int rc = check_bank(e, mask->active, (K - 1) * (uint64_t)mask->step + N, name)) return rc;
+      if (int rc = check_bank(e, mask->active, (K - 1) * (uint64_t)mask->step + C, name)) return rc;
     if (until) {
       // (stopped, ran, returns: written by the launch — device memory, whole extents)
       if ((uintptr_t)until->ran & 3)
@@ -1667,10 +1696,10 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r,
         if (int rc = check_bank(e, until->stopped, N, name)) return rc;
       snprintf(name, sizeof name, "%s (ran)", who);
       if (until->ran)
-        if (int rc = check_bank(e, until->ran, N * 4u, name)) return rc;
+        if (int rc = check_bank(e, until->ran, C * 4u, name)) return rc;
       snprintf(name, sizeof name, "%s (returns)", who);
       if (until->returns)
-        if (int rc = check_bank(e, until->returns, N * P * 8u, name)) return rc;
+        if (int rc = check_bank(e, until->returns, C * P * 8u, name)) return rc;
     }
     // (a slot row of a skipped world has no defined content)
     if (e->ring_slots > 0)
@@ -1700,8 +1729,9 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r,
     if (seen[index]) return fail(MP_ERR_INVALID, "%s: %s (kind %d) is named twice", who, k.name, kind);
     seen[index] = true;
     // (MP_STEP_ROW_STATE: a row is the N records; MP_STEP_ROW_HASH: their N hashes)
-    const uint64_t block = k.place == kRowState ? mp_snapshot_bytes(e)
-                           : k.place == kRowHash ? N * 8u : mp_obs_bytes(e, (MpObsKind)kind);
+    // (every kind's block is N equal parts: with a list a row holds C of them)
+    const uint64_t block = (k.place == kRowState ? mp_snapshot_bytes(e)
+                            : k.place == kRowHash ? N * 8u : mp_obs_bytes(e, (MpObsKind)kind)) / N * C;
     const uint64_t elem = (uint64_t)k.elem;
     if (block == 0)
       return fail(MP_ERR_UNSUPPORTED, "%s: this substrate has no observation %s (kind %d)", who, k.name, kind);
@@ -1734,7 +1764,7 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r,
         lv.which = kind;   // (launch_step_many resolves the buffer: a rollout ring moves it per submission)
         lv.row = base;
         lv.bytes = bytes;
-        lv.count = (long long)(block / 8 / N);
+        lv.count = (long long)(block / 8 / C);
       }
     }
   }
@@ -1743,26 +1773,45 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r,
     // `stopped`, and write the rows: none of the three may overlap anything else the request names
     struct Range { const char* what; uintptr_t at; uint64_t bytes; };
     std::vector<Range> all = {{"actions", (uintptr_t)r.actions, (K - 1) * r.actions_step_bytes + ablock}};
-    if (mask && mask->active) all.push_back({"active", (uintptr_t)mask->active, (K - 1) * (uint64_t)mask->step + N});
+    if (mask && mask->active) all.push_back({"active", (uintptr_t)mask->active, (K - 1) * (uint64_t)mask->step + C});
     for (int i = 0; i < r.num_rows; ++i) {
       const int index = step_row_index(r.rows[i].kind);
       const StepRowKind& k = kStepRowKinds.of[index];
-      const uint64_t block = k.place == kRowState ? mp_snapshot_bytes(e)
-                             : k.place == kRowHash ? N * 8u : mp_obs_bytes(e, (MpObsKind)r.rows[i].kind);
+      const uint64_t block = (k.place == kRowState ? mp_snapshot_bytes(e)
+                              : k.place == kRowHash ? N * 8u : mp_obs_bytes(e, (MpObsKind)r.rows[i].kind)) / N * C;
       all.push_back({k.name, (uintptr_t)r.rows[i].rows, (K - 1) * r.rows[i].step_bytes + block});
+      // (the list is read by every wave while the rows are written)
+      if (list && (uintptr_t)list->worlds < all.back().at + all.back().bytes &&
+          all.back().at < (uintptr_t)list->worlds + C * 4u)
+        return fail(MP_ERR_INVALID, "%s: worlds overlaps the %s buffer, which the request writes", who, k.name);
     }
+    if (list) all.push_back({"worlds", (uintptr_t)list->worlds, C * 4u});
     const size_t first = all.size();
     if (until->stopped) all.push_back({"stopped", (uintptr_t)until->stopped, N});
-    if (until->ran) all.push_back({"ran", (uintptr_t)until->ran, N * 4u});
-    if (until->returns) all.push_back({"returns", (uintptr_t)until->returns, N * P * 8u});
+    if (until->ran) all.push_back({"ran", (uintptr_t)until->ran, C * 4u});
+    if (until->returns) all.push_back({"returns", (uintptr_t)until->returns, C * P * 8u});
     for (size_t i = first; i < all.size(); ++i)
       for (size_t j = 0; j < i; ++j)
         if (all[i].at < all[j].at + all[j].bytes && all[j].at < all[i].at + all[i].bytes)
           return fail(MP_ERR_INVALID, "%s: %s overlaps %s; stopped, ran and returns must not overlap each other "
                       "or any other buffer of the request", who, all[i].what, all[j].what);
   }
+  if (list) {
+    // the claim table: the first listed request's allocation (zeroed: generation 0 is nobody's)
+    if (!e->d_listed_claim) {
+      HIP_TRY(hipMalloc((void**)&e->d_listed_claim, N * 8u));
+      HIP_TRY(hipMemsetAsync(e->d_listed_claim, 0, N * 8u, e->stream));
+    }
+    if (++e->listed_generation == 0) {   // (2^32 requests later: start over from a cleared table)
+      HIP_TRY(hipMemsetAsync(e->d_listed_claim, 0, N * 8u, e->stream));
+      e->listed_generation = 1;
+    }
+    list->claim = e->d_listed_claim;
+    list->generation = e->listed_generation;
+  }
   e->touched = true;
-  return submit(e, r.fields ? STEP_MODE_FIELDS : STEP_MODE_STEP, r.actions, nullptr, nullptr, nullptr, 0, &l, until);
+  return submit(e, r.fields ? STEP_MODE_FIELDS : STEP_MODE_STEP, r.actions, nullptr, nullptr, nullptr, 0, &l, until,
+                list);
 }
 
 // What mp_restore does when `bytes` is sizeof(MpStepMany): every non-NULL per_step[i] is one row
@@ -1820,6 +1869,28 @@ static int until_request(MpEngine* e, const MpStepUntil& r) {
   const ActiveArgs mask = {r.active, (long long)r.active_step_bytes};
   const UntilArgs until = {r.stop, r.stopped, r.ran, r.returns, r.gamma};
   return step_request(e, kWho, t, &mask, &until);
+}
+
+// ... and when it is sizeof(MpStepListed): the stopping request of the worlds a device list names.
+static int listed_request(MpEngine* e, const MpStepListed& r) {
+  static const char kWho[] = "MpStepListed";
+  if (r.struct_size != sizeof(MpStepListed))
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpStepListed));
+  if (r.pad != 0 || r.reserved2 != 0) return fail(MP_ERR_INVALID, "%s: pad and reserved2 must be 0", kWho);
+  for (uint64_t word : r.reserved)
+    if (word != 0) return fail(MP_ERR_INVALID, "%s: the reserved words must be 0", kWho);
+  for (uint64_t word : r.reserved3)
+    if (word != 0) return fail(MP_ERR_INVALID, "%s: the reserved words must be 0", kWho);
+  if (r.stop & ~(uint32_t)(MP_STOP_LAST | MP_STOP_REWARD))
+    return fail(MP_ERR_INVALID, "%s: stop %u has bits beyond MP_STOP_LAST | MP_STOP_REWARD", kWho, r.stop);
+  if (!std::isfinite(r.gamma)) return fail(MP_ERR_INVALID, "%s: gamma %g is not finite", kWho, r.gamma);
+  if (r.active_step_bytes > (1ull << 40))
+    return fail(MP_ERR_INVALID, "%s: active_step_bytes %llu", kWho, (unsigned long long)r.active_step_bytes);
+  const MpStepTrajectory t = {sizeof t, r.steps, r.fields, r.num_rows, r.actions, r.actions_step_bytes, r.rows};
+  const ActiveArgs mask = {r.active, (long long)r.active_step_bytes};
+  const UntilArgs until = {r.stop, r.stopped, r.ran, r.returns, r.gamma};
+  ListArgs list = {r.worlds, r.count, nullptr, 0u};
+  return step_request(e, kWho, t, &mask, &until, &list);
 }
 
 // An MpStatesObserve request (include/mp_engine.h; carried by mp_snapshot): observations of rows
@@ -2313,6 +2384,16 @@ static_assert(sizeof(MpStepUntil) == 136 && MP_SIZE_DIFFERS(MpStepUntil) &&
 static_assert(offsetof(MpStepUntil, active_step_bytes) == offsetof(MpStepActive, active_step_bytes) &&
                   offsetof(MpStepUntil, stop) == offsetof(MpStepActive, reserved),
               "MpStepUntil's leading fields are MpStepActive's");
+static_assert(sizeof(MpStepListed) == 176 && MP_SIZE_DIFFERS(MpStepListed) &&
+                  sizeof(MpStepListed) != sizeof(MpStateLayout) && sizeof(MpStepListed) != sizeof(MpStatesCheck) &&
+                  sizeof(MpStepListed) != sizeof(MpStatesHash) && sizeof(MpStepListed) != sizeof(MpEpisodeStarts) &&
+                  sizeof(MpStepListed) != sizeof(MpStatesView) && sizeof(MpStepListed) != sizeof(MpStepActive) &&
+                  sizeof(MpStepListed) != sizeof(MpStepUntil) && sizeof(MpStepListed) < 448,
+              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
+static_assert(offsetof(MpStepListed, gamma) == offsetof(MpStepUntil, gamma) &&
+                  offsetof(MpStepListed, reserved) == offsetof(MpStepUntil, reserved) &&
+                  offsetof(MpStepListed, worlds) == sizeof(MpStepUntil),
+              "MpStepListed's leading fields are MpStepUntil's");
 #undef MP_SIZE_DIFFERS
 // An MpKernelVariant request (carried by mp_snapshot; `e` may be NULL: the host-only question).
 static int kernel_variant(const MpEngine* e, MpKernelVariant* r) {
@@ -2406,6 +2487,11 @@ int mp_restore(MpEngine* e, const void* buf, uint64_t bytes) {
     MpStepUntil r;   // (read only: nothing is written back)
     memcpy(&r, buf, sizeof r);
     return until_request(e, r);
+  }
+  if (buf && bytes == sizeof(MpStepListed)) {
+    MpStepListed r;   // (read only: nothing is written back)
+    memcpy(&r, buf, sizeof r);
+    return listed_request(e, r);
   }
   if (!e || !buf || bytes != mp_snapshot_bytes(e))
     return fail(MP_ERR_INVALID, "mp_restore: bad buffer");

@@ -1,7 +1,7 @@
 // step_levels.h — the nine levels of the stand-alone step kernels, listed ONCE, and what every
 // unit that defines one kernel a level shares on the host side: the launch geometry and the LDS
-// attribute.  Included by the five step units (step_kernels.hip, step_starts.hip, step_many.hip,
-// step_active.hip, step_until.hip) and by nothing else.
+// attribute.  Included by the six step units (step_kernels.hip, step_starts.hip, step_many.hip,
+// step_active.hip, step_until.hip, step_listed.hip) and by nothing else.
 #ifndef MP_STEP_LEVELS_H_
 #define MP_STEP_LEVELS_H_
 

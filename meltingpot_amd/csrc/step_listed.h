@@ -1,0 +1,33 @@
+// step_listed.h — what the host hands the K-step kernels of a world list (step_listed.hip)
+// besides a checked StepManyLaunch and the stop state: the list of an MpStepListed request
+// (include/mp_engine.h) and the engine's claim table.  A header of its own: step_many.h,
+// step_until.h, and every unit that includes only them, are what they were.
+#ifndef MP_STEP_LISTED_H_INTERNAL_
+#define MP_STEP_LISTED_H_INTERNAL_
+
+#include "step_until.h"
+
+// worlds: device int32 [count], entry i is stepped by wave i.  claim: device u64 [N], the
+// engine's; tag = generation << 32 | ~i of the entry that owns world w in this request (the claim
+// launch in front of the step kernels takes the maximum, so the lowest i of a generation wins; the
+// generation grows with every request, so the table is never cleared).
+struct ListArgs {
+  const int32_t* worlds;
+  int count;
+  unsigned long long* claim;
+  uint32_t generation;
+};
+
+// DevTables::fault word FAULT_STATE_INDEX + 2 of an entry a listed launch skipped (word 9 = entry
+// + 1, word 10 = worlds[entry]; mp_common.h; 3: state_obs.h, 4 and 5: state_check.h, 6:
+// state_hash.h, 7 and 8: state_view.h): a value that is no world, a world an earlier entry names.
+constexpr uint32_t kFaultListedWorld = 9u;
+constexpr uint32_t kFaultListedRepeat = 10u;
+
+// The claim launch and then the step kernels: ceil(count / worlds per group) workgroups.
+void launch_step_listed(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
+                        const StepManyLaunch& l, const UntilArgs& u, const ListArgs& list,
+                        hipStream_t stream);
+int prepare_step_listed();
+
+#endif  // MP_STEP_LISTED_H_INTERNAL_

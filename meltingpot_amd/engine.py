@@ -762,6 +762,84 @@ def check_step_until(num_worlds: int, num_players: int, *, until=None, stopped=N
   return stop
 
 
+# ... launched with one wave per entry of a device list of world indices (MpStepListed)
+class MpStepListed(ctypes.Structure):
+  _fields_ = MpStepUntil._fields_ + [("worlds", ctypes.c_void_p), ("count", ctypes.c_int32),
+                                     ("reserved2", ctypes.c_int32), ("reserved3", ctypes.c_uint64 * 3)]
+
+
+def check_step_listed(worlds, num_worlds: int, num_players: int, *, actions=None, repeat=None,
+                      num_fields: Optional[int] = None, active=None, lengths=None, out=None,
+                      shapes=None) -> int:
+  """The rules of the worlds= list of Engine.step / Engine.step_many, and of the tensors that go with
+  it, without an engine: returns M, the number of entries.  worlds: 1-D integers (a tensor, an
+  array or a list), 1 <= M <= num_worlds (more entries than worlds must repeat one); the VALUES are
+  checked on the device.  Everything else the call takes per world has M columns, not N — actions
+  ([K, M, P], or [M, P] with repeat=K; anything with .shape and .dtype, or array-like), active
+  ([K, M] or [M]), lengths (integers [M]) and, with `shapes` (kind -> (shape, dtype), as
+  Engine.shapes), every tensor of `out` (a step_many result: rows (K, M) + shape[1:], "ran" [M],
+  "returns" [M, P]; its "stopped" stays [N]).  ValueError otherwise."""
+  N, P = int(num_worlds), int(num_players)
+  if hasattr(worlds, "data_ptr"):
+    name, shape = str(worlds.dtype), tuple(int(d) for d in worlds.shape)
+    ok = name in ("torch.int8", "torch.int16", "torch.int32", "torch.int64", "torch.uint8")
+  else:
+    w = np.asarray(worlds)
+    name, shape = str(w.dtype), w.shape
+    ok = np.issubdtype(w.dtype, np.integer) and w.dtype != np.bool_
+  if len(shape) == 1 and int(shape[0]) == 0:   # (an empty list has no dtype to speak of)
+    raise ValueError("worlds= names no world")
+  if not ok or len(shape) != 1:
+    raise ValueError(f"worlds= must be 1-D integers, one world index per entry (got {name} {tuple(shape)})")
+  M = int(shape[0])
+  if M < 1:
+    raise ValueError("worlds= names no world")
+  if M > N:
+    raise ValueError(f"worlds= has {M} entries for {N} worlds: more entries than worlds must repeat one")
+  K = None
+  if actions is not None:
+    a = actions if hasattr(actions, "shape") and hasattr(actions, "dtype") else np.asarray(actions)
+    try:
+      K = check_step_many(a.shape, a.dtype, M, P, repeat=repeat, num_fields=num_fields)
+    except ValueError as e:
+      raise ValueError(f"{e}; with worlds= the actions have one column per entry ({M}), not per world") from None
+  elif repeat is not None:
+    K = int(repeat)
+  if active is not None:
+    if K is None:
+      raise ValueError("check_step_listed: active= is checked against the actions' K")
+    check_step_active(active, K, M)
+  if lengths is not None:
+    n = lengths if hasattr(lengths, "shape") else np.asarray(lengths)
+    kind = str(n.dtype)
+    if "int" not in kind or tuple(int(d) for d in n.shape) != (M,):
+      raise ValueError(f"lengths= must be an int tensor of shape ({M},), one per entry of worlds= (got {kind} "
+                       f"{tuple(n.shape)})")
+  if out is not None:
+    for key, buf in out.items():
+      if buf is None or key == "stopped":
+        continue
+      if key == "ran":
+        want = (M,)
+      elif key == "returns":
+        want = (M, P)
+      elif key == "hashes":
+        want = None if K is None else (K, M)
+      elif key == "states":
+        want = None if K is None else (K, M, int(buf.shape[-1]))
+      elif shapes is not None and K is not None:
+        kind = STEP_MANY_NAMES.get(key, key)
+        if kind not in shapes:
+          continue
+        want = (K, M) + tuple(int(d) for d in shapes[kind][0][1:])
+      else:
+        want = None
+      if want is not None and tuple(int(d) for d in buf.shape) != want:
+        raise ValueError(f"out[{key!r}] must have shape {want} with worlds= of {M} entries (got "
+                         f"{tuple(int(d) for d in buf.shape)})")
+  return M
+
+
 # Registered episode starts (include/mp_engine.h: MpEpisodeStarts), carried by mp_restore
 class MpEpisodeStarts(ctypes.Structure):
   _fields_ = [("struct_size", ctypes.c_uint32), ("fresh", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
@@ -1380,11 +1458,21 @@ class Engine:
       mp = mask.ctypes.data
     _check(self._L, self._L.mp_reset(self._h, sp, mp), "mp_reset")
 
-  def step(self, actions, active=None):
+  def step(self, actions, active=None, worlds=None):
     """actions: int32 cuda tensor [N, P] of discrete action ids.
     active: a mask [N] (see step_many): only the worlds it selects step, the others are not
-    touched.  It is the K = 1 masked request of step_many."""
+    touched.  It is the K = 1 masked request of step_many.
+    worlds: a list of M world indices (see step_many): actions [M, P], entry i steps world
+    worlds[i] and no other world is touched (active, if given, is then [M]).  It is the K = 1
+    listed request of step_many."""
     t = self._torch
+    if worlds is not None:
+      a = actions if isinstance(actions, t.Tensor) else np.asarray(actions)
+      M = check_step_listed(worlds, self.N, self.P)
+      if tuple(a.shape) != (M, self.P):
+        raise ValueError(f"actions must have shape {(M, self.P)}, one row per entry of worlds=")
+      self.step_many(a[None], keep=(), active=active, worlds=worlds)
+      return
     if active is not None:
       a = actions if isinstance(actions, t.Tensor) else np.asarray(actions)
       if tuple(a.shape) != (self.N, self.P):
@@ -1422,7 +1510,7 @@ class Engine:
   def step_many(self, actions, *, repeat: Optional[int] = None, fields: bool = False,
                 keep=("reward", "collective_reward", "step_type", "discount"), events: bool = False,
                 observations=(), out=None, states=False, hashes=False, active=None,
-                until=None, stopped=None, returns=False, gamma: float = 1.0):
+                until=None, stopped=None, returns=False, gamma: float = 1.0, worlds=None):
     """K steps of every world in ONE launch, bit-identical to K calls of step() (fields=True:
     step_fields()) with actions[0] .. actions[K - 1]; returns the per-step transitions.
 
@@ -1474,31 +1562,54 @@ class Engine:
     With any of until=, stopped=, returns= the result gains "stopped" (uint8 [N]) and "ran" (int32
     [N]: the steps each world ran in this call; out["ran"] is reused), and "returns" when asked
     for; with none of them the call issues exactly the request it issues without them.
+    worlds: a list of M world indices, 1 <= M <= N — a device int32 tensor [M] is read in place, a
+    host list or array is uploaded once.  The launch then has one wave per ENTRY (ceil(M / 4)
+    workgroups whatever N is) and entry i steps world worlds[i]; a world no entry names is not
+    touched, as under a mask.  Everything per world above has M columns, by entry: actions
+    [K, M, P], active [K, M] or [M], every stacked tensor (K, M) + ..., "states" [K, M, S],
+    "hashes" [K, M], "ran" [M], "returns" [M, P], and row k of entry i is what the masked call over
+    all N worlds leaves in row k of world worlds[i].  "stopped" stays [N], by WORLD: it is the
+    tensor that persists over calls, which may name different lists; it is part of the result
+    only with until=, stopped= or returns=.  An entry that is no world, or that repeats an earlier
+    entry's world (the lowest entry steps it), runs nothing and leaves its elements of every
+    tensor as they were; the next synchronising call raises ValueError once, naming it.  Refused
+    with a rollout ring bound.  None: exactly the request issued without it.
     Enqueued on the current stream; does not synchronise."""
     t = self._torch
+    listed = worlds is not None
+    C = self.N   # the columns of every per-call tensor: N, or the entries of worlds=
+    if listed:
+      C = check_step_listed(worlds, self.N, self.P)
+      if isinstance(worlds, t.Tensor) and worlds.device != self.device:
+        raise ValueError(f"step_many: worlds= lives on {worlds.device}, the engine on {self.device}")
+      if isinstance(worlds, t.Tensor) and worlds.dtype == t.int32 and worlds.is_contiguous():
+        wl = worlds
+      else:
+        wl = self._device_ints(worlds, "worlds")
     stopping = until is not None or stopped is not None or (returns is not None and returns is not False)
     if stopping:
-      stop = check_step_until(self.N, self.P, until=until, stopped=stopped, returns=returns, gamma=gamma,
-                              ran=None if out is None else out.get("ran"), device=self.device)
+      stop = check_step_until(self.N, self.P, until=until, stopped=stopped, gamma=gamma, device=self.device)
+      check_step_until(C, self.P, returns=returns, ran=None if out is None else out.get("ran"),
+                       device=self.device)
     elif float(gamma) != 1.0:
       raise ValueError("step_many: gamma= goes with returns=")
     A = int(self.info.num_action_fields) if fields else None
     if isinstance(actions, t.Tensor) and actions.is_cuda:
       if actions.dtype != t.int32:
         raise ValueError(f"step_many: a device tensor of actions must be int32 (got {actions.dtype})")
-      K = check_step_many(actions.shape, actions.dtype, self.N, self.P, repeat=repeat, num_fields=A)
+      K = check_step_many(actions.shape, actions.dtype, C, self.P, repeat=repeat, num_fields=A)
       if actions.device != self.device:
         raise ValueError(f"step_many: actions live on {actions.device}, the engine on {self.device}")
     else:
       a = actions.cpu().numpy() if isinstance(actions, t.Tensor) else np.asarray(actions)
-      K = check_step_many(a.shape, a.dtype, self.N, self.P, repeat=repeat, num_fields=A)
+      K = check_step_many(a.shape, a.dtype, C, self.P, repeat=repeat, num_fields=A)
       actions = t.from_numpy(np.ascontiguousarray(a, np.int32)).to(self.device)
     astep = 0 if repeat is not None else _step_distance(actions, "actions")
     if repeat is not None and not actions.is_contiguous():
       raise ValueError("step_many: the repeated block of actions must be contiguous")
     mask = None
     if active is not None:
-      mask, mask_step = check_step_active(active, K, self.N)
+      mask, mask_step = check_step_active(active, K, C)
       if isinstance(mask, np.ndarray):
         mask = t.from_numpy(mask).to(self.device)
       elif mask.device != self.device:
@@ -1520,7 +1631,7 @@ class Engine:
         kind, per_world, dtype = STEP_ROW_HASH, (), t.int64
       else:
         kind, per_world, dtype = step_row(self.shapes, key)
-      shape = (K, self.N) + per_world
+      shape = (K, C) + per_world
       buf = None if out is None else out.get(key)
       if buf is None:
         buf = t.empty(shape, dtype=dtype, device=self.device)
@@ -1535,16 +1646,17 @@ class Engine:
     if stopping:
       ran = None if out is None else out.get("ran")
       if ran is None:
-        ran = t.empty((self.N,), dtype=t.int32, device=self.device)
+        ran = t.empty((C,), dtype=t.int32, device=self.device)
       if stopped is None:
         stopped = t.zeros((self.N,), dtype=t.uint8, device=self.device)
       if returns is True:
         returns = None if out is None else out.get("returns")
         if returns is None:
-          returns = t.empty((self.N, self.P), dtype=t.float64, device=self.device)
+          returns = t.empty((C, self.P), dtype=t.float64, device=self.device)
         else:
-          check_step_until(self.N, self.P, returns=returns, device=self.device)
-      req = MpStepUntil(ctypes.sizeof(MpStepUntil), K, 1 if fields else 0, len(rows))
+          check_step_until(C, self.P, returns=returns, device=self.device)
+      kind = MpStepListed if listed else MpStepUntil
+      req = kind(ctypes.sizeof(kind), K, 1 if fields else 0, len(rows))
       if active is not None:
         req.active = mask.data_ptr()
         req.active_step_bytes = mask_step
@@ -1556,6 +1668,12 @@ class Engine:
       if returns is not None and returns is not False:
         req.returns = returns.data_ptr()
         result["returns"] = returns
+    elif listed:   # (the stopping request with nothing that stops a world)
+      req = MpStepListed(ctypes.sizeof(MpStepListed), K, 1 if fields else 0, len(rows))
+      req.gamma = 1.0
+      if active is not None:
+        req.active = mask.data_ptr()
+        req.active_step_bytes = mask_step
     elif active is not None:
       req = MpStepActive(ctypes.sizeof(MpStepActive), K, 1 if fields else 0, len(rows))
       req.active = mask.data_ptr()
@@ -1565,9 +1683,12 @@ class Engine:
     req.actions = actions.data_ptr()
     req.actions_step_bytes = astep
     req.rows = rows
+    if listed:
+      req.worlds = wl.data_ptr()
+      req.count = C
     _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
            f"mp_restore ({type(req).__name__})")
-    self._state_args = (actions, result, mask)   # (kept until the next call: the launch may not have run yet)
+    self._state_args = (actions, result, mask, wl if listed else None)   # (kept until the next call: the launch may not have run yet)
     return result
 
   def observe(self, kind: int, out=None):

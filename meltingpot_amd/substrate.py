@@ -193,11 +193,27 @@ def _step_mask(t, active, lengths, K: int, N: int, device, ring: bool):
   return mask
 
 
-def _step_until(t, until, stopped, returns, gamma, N: int, P: int, device, ring: bool):
+def _step_list(t, worlds, lengths, batched: bool, N: int, P: int, ring: bool) -> Optional[int]:
+  """The worlds= list of a step / step_many call: None for a call without it, else M, its number
+  of entries (the engine reads or uploads the list itself).  `ring`: the substrate was built with
+  rollout_length=T."""
+  if worlds is None:
+    return None
+  if not batched:
+    raise ValueError("worlds= selects worlds of a batch: build the substrate with num_worlds > 1")
+  if ring:
+    raise ValueError("a call with worlds= cannot write a rollout ring (rollout_length=T): a slot row of an "
+                     "unlisted world has no defined content; build the substrate without rollout_length")
+  return engine_lib.check_step_listed(worlds, N, P, lengths=lengths)
+
+
+def _step_until(t, until, stopped, returns, gamma, N: int, P: int, device, ring: bool,
+                entries: Optional[int] = None):
   """The stop arguments of a step_many call as the engines take them: None for a call without
   them, else the dict of `until`, `stopped`, `returns`, `gamma` and `ran` — the [N] / [N, P] device
   tensors allocated here where the caller gave none, so that the members of a mixture write their
-  rows of ONE tensor each.  `ring`: the substrate was built with rollout_length=T."""
+  rows of ONE tensor each.  `ring`: the substrate was built with rollout_length=T.  `entries`: M of
+  a call with worlds=, whose `returns` and `ran` are by entry ([M, P], [M]; `stopped` stays [N])."""
   if until is None and stopped is None and (returns is None or returns is False):
     if float(gamma) != 1.0:
       raise ValueError("gamma= goes with returns=")
@@ -209,13 +225,18 @@ def _step_until(t, until, stopped, returns, gamma, N: int, P: int, device, ring:
     until = (until,)
   elif until is not None:
     until = tuple(until)
-  engine_lib.check_step_until(N, P, until=until, stopped=stopped, returns=returns, gamma=gamma, device=device)
+  if entries is None:
+    entries = N
+    engine_lib.check_step_until(N, P, until=until, stopped=stopped, returns=returns, gamma=gamma, device=device)
+  else:
+    engine_lib.check_step_until(N, P, until=until, stopped=stopped, gamma=gamma, device=device)
+    engine_lib.check_step_until(entries, P, returns=returns, device=device)
   if stopped is None:
     stopped = t.zeros((N,), dtype=t.uint8, device=device)
   if returns is True:
-    returns = t.empty((N, P), dtype=t.float64, device=device)
+    returns = t.empty((entries, P), dtype=t.float64, device=device)
   return {"until": until, "stopped": stopped, "returns": returns, "gamma": float(gamma),
-          "ran": t.empty((N,), dtype=t.int32, device=device)}
+          "ran": t.empty((entries,), dtype=t.int32, device=device)}
 
 
 def _until_slice(stop, out, off: int, n: int):
@@ -1299,16 +1320,22 @@ class Substrate:
   def write_property(self, key: str, value):
     raise KeyError(key)
 
-  def step(self, action, active=None) -> TimeStep:
+  def step(self, action, active=None, worlds=None) -> TimeStep:
     """Substrate.step (substrate.py:74-81).  `action`: P ints (unbatched), or
     an int tensor / array [N, P] (batched).
     `active` (batched substrates): a uint8 or bool mask [N]; only the worlds it selects step.
     The others are not touched, and their elements of the returned TimeStep's leaves are what
-    they were."""
+    they were.
+    `worlds` (batched substrates): M world indices (a device int32 tensor is read in place);
+    `action` is then [M, P] (and `active` [M]) and entry i steps world worlds[i].  The launch has
+    one wave per entry, whatever N is; the other worlds are not touched.  The returned TimeStep
+    is the full [N] one, with the listed worlds updated."""
     t = self._eng._torch
     if active is not None and not self._batched:
       raise ValueError("active= selects worlds of a batch: build the substrate with num_worlds > 1")
-    mask = _step_mask(t, active, None, 1, self._eng.N, self._eng.device, self._T > 0)
+    entries = _step_list(t, worlds, None, self._batched, self._eng.N, self._eng.P, self._T > 0)
+    mask = _step_mask(t, active, None, 1, self._eng.N if entries is None else entries, self._eng.device,
+                      self._T > 0)
     if self._batched:
       if isinstance(action, t.Tensor) and action.is_cuda:
         a = action.to(t.int32).contiguous()
@@ -1326,7 +1353,12 @@ class Substrate:
       a = a.reshape(1, self._eng.P)
     self._observables.action.on_next(action)
     self._eng.use_current_stream()
-    self._submit(a, mask)
+    if entries is not None:
+      if tuple(a.shape) != (entries, self._eng.P):
+        raise ValueError(f"actions must have shape {(entries, self._eng.P)}, one row per entry of worlds=")
+      self._submit_many(a[None], None, False, None, active=mask, keep=(), worlds=worlds)
+    else:
+      self._submit(a, mask)
     return self._emit(self._timestep())
 
   def _submit(self, a, active=None):
@@ -1384,7 +1416,7 @@ class Substrate:
   def step_many(self, actions, repeat: Optional[int] = None, events: bool = False,
                 observations=(), states: bool = False, hashes: bool = False,
                 active=None, lengths=None, until=None, stopped=None, returns=False,
-                gamma: float = 1.0) -> StepManyResult:
+                gamma: float = 1.0, worlds=None) -> StepManyResult:
     """K steps in ONE launch, bit-identical to K calls of `step` (batched substrates).
     `actions`: ints [K, N, P] (a device tensor is read in place; it may be a column slice
     [:, a:b] of a wider one), or one block [N, P] with `repeat=K`.  Returns the per-step
@@ -1422,7 +1454,17 @@ class Substrate:
     calls without the host; zero a byte and the world runs again.  `returns=True` (or a float64
     tensor [N, P]): the discounted sum, with `gamma`, of the rewards of the steps each world ran.
     With any of the three the result is a `StepManyUntil` with `.ran`, `.stopped`, `.returns`.
-    They combine with `active` / `lengths` and everything above.  Not with `rollout_length=T`."""
+    They combine with `active` / `lengths` and everything above.  Not with `rollout_length=T`.
+    `worlds`: M world indices (a device int32 tensor is read in place; a list or array is uploaded
+    once): the launch has one wave per ENTRY, whatever N is, and entry i steps world worlds[i]; an
+    unlisted world is not touched.  Everything per world above then has M columns, by entry:
+    `actions` [K, M, P], `active` [K, M] / `lengths` [M], every per-step tensor [K, M, ...] (row k
+    of entry i is what the masked call over all worlds gives for world worlds[i]), `.states` K x M
+    rows (step k of entry i is row k * M + i), `.hashes` [K, M], `.ran` [M], `.returns` [M, P] —
+    but `stopped` and `.stopped` stay [N], by world, since that tensor persists over calls that
+    name different lists, and `.timestep` is the full [N] TimeStep.  An entry that is no world, or
+    repeats an earlier entry's world, runs nothing; the next synchronising call raises ValueError
+    once.  Not with `rollout_length=T`."""
     if not self._batched:
       raise ValueError("step_many steps a batch of worlds: build the substrate with num_worlds > 1")
     leaves = self._many_leaves(observations)
@@ -1430,11 +1472,15 @@ class Substrate:
     limit = None
     if self._check_device_actions:
       limit = len(self._action_rows) if self._action_rows is not None else self._eng.num_actions
-    a, K = _many_actions(t, actions, repeat, self._eng.N, self._eng.P, limit)
-    mask = _step_mask(t, active, lengths, K, self._eng.N, self._eng.device, self._T > 0)
+    entries = _step_list(t, worlds, lengths, True, self._eng.N, self._eng.P, self._T > 0)
+    columns = self._eng.N if entries is None else entries
+    a, K = _many_actions(t, actions, repeat, columns, self._eng.P, limit)
+    mask = _step_mask(t, active, lengths, K, columns, self._eng.device, self._T > 0)
     stop = _step_until(t, until, stopped, returns, gamma, self._eng.N, self._eng.P, self._eng.device,
-                       self._T > 0)
+                       self._T > 0, entries)
     more, out = _until_slice(stop, None, 0, self._eng.N)
+    if entries is not None:
+      more["worlds"] = worlds
     self._observables.action.on_next(actions)
     self._eng.use_current_stream()
     r = self._submit_many(a, repeat, events, out, leaves, bool(states), bool(hashes), active=mask, **more)
@@ -2021,11 +2067,14 @@ class MixtureSubstrate:
   def observation(self):
     return self._timestep().observation
 
-  def step(self, action, active=None) -> TimeStep:
+  def step(self, action, active=None, worlds=None) -> TimeStep:
     """`action`: int [N, P], a device tensor (member i gets rows [off_i, off_i + n_i), a view)
     or a host array.  `active`: a mask [N] as `Substrate.step` takes it; member i reads its
     elements [off_i, off_i + n_i) of it in place."""
     t = self._members[0]._eng._torch
+    if worlds is not None:
+      raise ValueError("worlds= is not offered by a mixture: splitting a global list per member on the device "
+                       "is not built; step the members' substrates on their own, or use active=")
     mask = _step_mask(t, active, None, 1, self._N, self._members[0]._eng.device,
                       any(m._T > 0 for m in self._members))
     if isinstance(action, t.Tensor) and action.is_cuda:
@@ -2097,7 +2146,7 @@ class MixtureSubstrate:
   def step_many(self, actions, repeat: Optional[int] = None, events: bool = False,
                 observations=(), states: bool = False, hashes: bool = False,
                 active=None, lengths=None, until=None, stopped=None, returns=False,
-                gamma: float = 1.0) -> StepManyResult:
+                gamma: float = 1.0, worlds=None) -> StepManyResult:
     """As `Substrate.step_many`, over the members: one K-step launch per member, each reading
     its columns [:, off_i:off_i + n_i] of `actions` and writing its columns of the shared
     [K, N, ...] per-step tensors, those of `observations` included (nothing is copied or
@@ -2109,6 +2158,9 @@ class MixtureSubstrate:
     reads its columns of the one mask in place.
     `until` / `stopped` / `returns` / `gamma`: likewise; `stopped` [N], `.ran` [N] and `.returns`
     [N, P] are one tensor each, whose rows the members read and write in place."""
+    if worlds is not None:
+      raise ValueError("worlds= is not offered by a mixture: splitting a global list per member on the device "
+                       "is not built; step the members' substrates on their own, or use active=")
     if states:
       raise ValueError("step_many: a mixture has no per-step states (states=True): its members' records "
                        "differ in size and fingerprint; step the members' substrates on their own")
