@@ -1200,6 +1200,120 @@ typedef struct {
   uint64_t reserved3[3];       /* 0 */
 } MpStepListed;
 
+/* Episode statistics on the device: per-player returns, episode lengths and per-player event counts
+ * of every finished episode, folded into tensors the caller owns by ONE launch of k_episode_stats
+ * behind every submission — no event row ever goes to the host.  Rides mp_restore, recognised by its
+ * size: `bytes` = sizeof(MpEpisodeStats), `host_buf` a HOST MpEpisodeStats with struct_size set to
+ * it.  include/mp_episode_stats.h wraps the four ops as inline C functions.
+ *
+ * A column (MpEventColumn) counts the events of one MpEventType per credited player: the 1-based
+ * player is ((payload >> player_shift) & player_mask) of payload a (player_payload = 0) or b (1); a
+ * value outside [1, P] credits nobody.  filter_payload != 0 adds the test
+ * ((payload >> filter_shift) & filter_mask) == filter_value on payload a (1) or b (2): ore type,
+ * item, class, mushroom type, level, coin types, and the halves of the packed payloads of types 15
+ * and 16.  A PAIR column also takes a second 1-based player, ((other >> other_shift) & other_mask)
+ * of the OTHER payload, and counts into [P][P] at (credited, other); an event whose second player is
+ * outside [1, P] is not counted.  At most MP_STATS_MAX_COLUMNS columns and MP_STATS_MAX_PAIRS pair
+ * columns; shifts < 32.
+ *
+ * The statistics, device tensors with the world axis leading (C = num_columns, C2 = num_pairs):
+ *   open u8 [N]; episodes i32 [N]; dropped i32 [N];
+ *   running, last: returns f64 [N][P], length i32 [N], counts i32 [N][C][P], pairs i32 [N][C2][P][P];
+ *   total:         returns f64 [N][P], length i64 [N], counts i64 [N][C][P], pairs i64 [N][C2][P][P].
+ * (counts may be NULL with C = 0, pairs with C2 = 0.)
+ *
+ * The rule, for one world and one step that ran, with the STEP_TYPE st, the REWARD r[P] and the
+ * event rows E the step left (tally(E): every row the header counts, against every column):
+ *   st == FIRST (reset, auto-reset step, load, registered start):
+ *       running := 0, open := 1, running.counts / pairs += tally(E)
+ *   otherwise, if open:
+ *       running.returns[p] += r[p] (one f64 add a step, in step order), running.length += 1,
+ *       running.counts / pairs += tally(E);
+ *       if st == LAST: last := running, total += running, episodes += 1, open := 0
+ *   otherwise nothing (a frozen world on LAST, a row loaded from a finished episode, an episode not
+ *   seen from its FIRST).
+ *   dropped += E's header `dropped`, on every step that ran.
+ * An episode cut short by mp_reset or a load is dropped: its running is zeroed, nothing is counted.
+ * One wave owns a world's statistics and walks its steps in order; there is no global atomic, so
+ * every value is bitwise reproducible.
+ *
+ * Which steps ran: a world never reset ran nothing; a masked mp_reset: the mask; MP_STATES_LOAD: the
+ * worlds whose src[w] is a row; MpStepMany / MpStepTrajectory: all K steps; MpStepActive: the steps
+ * whose mask byte is non-zero; MpStepUntil / MpStepListed: the first ran[i] active steps of column i
+ * (a list: of the entries that own their world, statistics by world worlds[i], rows by column i).
+ *
+ * MP_STATS_REGISTER (eng != NULL): from now on every submission (mp_reset, mp_step*, the K-step
+ *   requests, MP_STATES_LOAD) is followed on the engine's stream, without synchronisation, by one
+ *   launch that folds what the submission wrote into the tensors named here, read and written in
+ *   place; the caller keeps them alive and zeroes them first (or not: they are accumulators).  A
+ *   single step reads the engine's in-place (or bound, or ring-slot) REWARD, STEP_TYPE and EVENTS.
+ *   A K-step request on a registered engine must name the REWARD and STEP_TYPE rows, the EVENTS row
+ *   when C + C2 > 0 (without one `dropped` is not counted for that request), and, for MpStepUntil and
+ *   MpStepListed, `ran`: MP_ERR_INVALID before any launch otherwise.  mp_tune's probes are not
+ *   folded.  The registration is engine configuration: a snapshot does not carry it.
+ * MP_STATS_CLEAR (eng != NULL): the engine issues exactly the launches it issued before.
+ * MP_STATS_TALLY (eng != NULL): the pure tally, no episode logic.  `events` is device int32
+ *   [steps][count][MP_EVENT_ROWS][4]; running.counts (device int32 [count][C][P]) and running.pairs
+ *   (device int32 [count][C2][P][P]) := the tally over the steps that ran: all, or those with a
+ *   non-zero `active` byte (device u8 [steps][count], or NULL), of them the first ran[i] (device i32
+ *   [count], or NULL).  Everything else of the request is ignored.  Enqueued, no synchronisation.
+ * MP_STATS_HOST (eng == NULL): the rule above applied by the same functions compiled for the host
+ *   to HOST rows — step_type i32 [steps][count], reward f64 [steps][count][num_players], events i32
+ *   [steps][count][MP_EVENT_ROWS][4] (NULL with no columns), active / ran as for the tally — over
+ *   HOST statistics of `count` worlds.  No device is touched.
+ * Refused before any launch, MP_ERR_INVALID: a wrong struct_size, an unknown op, num_columns or
+ * num_pairs outside their limits, NULL columns with a count > 0, a shift >= 32, a payload selector
+ * out of range, non-zero reserved words; a NULL tensor the op needs; REGISTER / TALLY: a tensor
+ * that is not device memory of the engine's device, whose extent is not inside one allocation, or
+ * that is not aligned to its element; TALLY / HOST: steps or count < 1, HOST: num_players outside
+ * [1, 16]. */
+#define MP_STATS_MAX_COLUMNS 32
+#define MP_STATS_MAX_PAIRS 4
+enum { MP_STATS_REGISTER = 1, MP_STATS_CLEAR = 2, MP_STATS_TALLY = 3, MP_STATS_HOST = 4 };
+typedef struct {
+  int32_t type;            /* MpEventType */
+  uint8_t player_payload;  /* 0: the credited player is in payload a; 1: in b */
+  uint8_t player_shift;
+  uint8_t filter_payload;  /* 0: no test; 1: test payload a; 2: test payload b */
+  uint8_t filter_shift;
+  uint32_t player_mask;
+  uint32_t filter_mask;
+  uint32_t filter_value;
+  uint8_t other_shift;     /* pair columns: the second player, from the other payload */
+  uint8_t reserved[3];     /* 0 */
+  uint32_t other_mask;
+  uint32_t reserved2;      /* 0 */
+} MpEventColumn;
+typedef struct {
+  double* returns;         /* f64 [N][P] */
+  void* length;            /* i32 [N] (total: i64 [N]) */
+  void* counts;            /* i32 [N][C][P] (total: i64) */
+  void* pairs;             /* i32 [N][C2][P][P] (total: i64) */
+} MpStatsBank;
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(MpEpisodeStats) */
+  int32_t op;              /* MP_STATS_* */
+  int32_t num_columns;     /* C  <= MP_STATS_MAX_COLUMNS */
+  int32_t num_pairs;       /* C2 <= MP_STATS_MAX_PAIRS */
+  const MpEventColumn* columns; /* HOST [num_columns] */
+  const MpEventColumn* pairs;   /* HOST [num_pairs] */
+  uint8_t* open;           /* u8 [N] */
+  int32_t* episodes;       /* i32 [N] */
+  int32_t* dropped;        /* i32 [N] */
+  MpStatsBank running, last, total;
+  /* TALLY and HOST: the rows */
+  int32_t steps;           /* K */
+  int32_t count;           /* the rows' columns (worlds) */
+  int32_t num_players;     /* HOST: P */
+  int32_t reserved;        /* 0 */
+  const int32_t* step_type;
+  const double* reward;
+  const int32_t* events;
+  const uint8_t* active;   /* u8 [steps][count], or NULL */
+  const int32_t* ran;      /* i32 [count], or NULL */
+  uint64_t reserved2[2];   /* 0 */
+} MpEpisodeStats;
+
 /* Throughput / event counters accumulated on device since creation
  * (synchronises).  These are what the multi-GPU bench all-reduces. */
 enum {

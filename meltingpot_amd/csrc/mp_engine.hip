@@ -30,6 +30,7 @@
 #include "state_view.h"
 #include "state_check.h"
 #include "state_hash.h"
+#include "episode_stats.h"
 
 // frame.hip
 constexpr int kFaultWords = 64 + 4 * 16 * 64 * 2;   // fault words + the timeline build's log
@@ -169,6 +170,12 @@ struct MpEngine {
   stepk::StartArgs starts{};
   bool has_starts = false, starts_hold = false;
   bool starting() const { return has_starts && !starts_hold; }
+  // The registered episode statistics (an MpEpisodeStats request; episode_stats.h): while set, every
+  // submission is followed by one launch of k_episode_stats.  stats_hold: mp_tune's probes are not folded.
+  episode_stats::Columns stats_cols{};
+  episode_stats::Banks stats{};
+  bool has_stats = false, stats_hold = false;
+  bool folding() const { return has_stats && !stats_hold; }
   // The engine's choice (MpConfig.unfused = 0): one launch, always.  (Round 2 drew
   // views under 64 KB a world — the two-player games — in a second launch: a CU
   // then has 64 worlds to step for 2 us of drawing each, and with 4-8 feeders the
@@ -487,6 +494,33 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
     launch_frame(e->t, &e->sub, args, rgb, wrgb, p, e->stream, pk, e->world_pool);
   }
   HIP_TRY(hipGetLastError());
+  if (e->folding()) {
+    // the statistics launch: what this submission wrote, folded into the caller's tensors
+    episode_stats::Rows r = {};
+    r.P = e->t.P;
+    r.num_worlds = e->N;
+    r.started = e->d_state + e->t.grid_pad + offsetof(WorldTail, started);
+    r.started_stride = e->t.world_stride;
+    if (many) {   // (step_request has checked that the rows and `ran` are there)
+      const ManyArgs& m = many->many;
+      r.columns = list ? list->count : e->N;
+      r.K = m.steps;
+      r.reward = (const double*)m.row[0]; r.reward_bytes = m.row_bytes[0];
+      r.step_type = (const int32_t*)m.row[2]; r.step_type_bytes = m.row_bytes[2];
+      r.events = (const int32_t*)m.row[4]; r.events_bytes = m.row_bytes[4];
+      r.active = many->active.active; r.active_bytes = m.steps > 1 ? many->active.step : 0;
+      if (until) r.ran = until->ran;
+      if (list) { r.worlds = list->worlds; r.claim = list->claim; r.generation = list->generation; }
+    } else {      // K = 1: the in-place buffers (bound ones, the ring slot just written)
+      r.columns = e->N;
+      r.K = 1;
+      r.reward = args.out.reward; r.step_type = args.out.step_type; r.events = args.out.events;
+      if (mode == STEP_MODE_RESET) r.sel8 = mask;
+      if (mode == STEP_MODE_LOAD) { r.sel32 = src; r.sel_rows = bank_rows; }
+    }
+    launch_episode_stats(e->stats_cols, e->stats, r, false, e->stream);
+    HIP_TRY(hipGetLastError());
+  }
   return MP_OK;
 }
 
@@ -1796,6 +1830,18 @@ static int step_request(MpEngine* e, const char* who, const MpStepTrajectory& r,
           return fail(MP_ERR_INVALID, "%s: %s overlaps %s; stopped, ran and returns must not overlap each other "
                       "or any other buffer of the request", who, all[i].what, all[j].what);
   }
+  if (e->folding()) {
+    // registered episode statistics (MpEpisodeStats): the launch behind this one reads these
+    if (!l.many.row[0] || !l.many.row[2])
+      return fail(MP_ERR_INVALID, "%s: episode statistics are registered (MpEpisodeStats); the request must name "
+                  "the REWARD and STEP_TYPE rows", who);
+    if (!l.many.row[4] && e->stats_cols.C + e->stats_cols.C2 > 0)
+      return fail(MP_ERR_INVALID, "%s: episode statistics with event columns are registered (MpEpisodeStats); "
+                  "the request must name the EVENTS row", who);
+    if (until && !until->ran)
+      return fail(MP_ERR_INVALID, "%s: episode statistics are registered (MpEpisodeStats); the request must "
+                  "name ran (which steps ran is read from it)", who);
+  }
   if (list) {
     // the claim table: the first listed request's allocation (zeroed: generation 0 is nobody's)
     if (!e->d_listed_claim) {
@@ -2342,6 +2388,135 @@ static int episode_starts(MpEngine* e, const MpEpisodeStarts& r) {
   return MP_OK;
 }
 
+// An MpEpisodeStats request (include/mp_engine.h; carried by mp_restore): registers or clears the
+// engine's episode statistics (no launch), tallies event rows on the device (one launch), or applies
+// the rule to host rows (`e` may be NULL: no device is touched).  Everything is checked first.
+static int episode_stats_request(MpEngine* e, const MpEpisodeStats& r) {
+  static const char kWho[] = "MpEpisodeStats";
+  if (r.struct_size != sizeof(MpEpisodeStats))
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpEpisodeStats));
+  if (r.op < MP_STATS_REGISTER || r.op > MP_STATS_HOST) return fail(MP_ERR_INVALID, "%s: unknown op %d", kWho, r.op);
+  if (r.op == MP_STATS_HOST ? e != nullptr : e == nullptr)
+    return fail(MP_ERR_INVALID, "%s: %s", kWho, e ? "MP_STATS_HOST takes no engine" : "NULL engine");
+  if (r.reserved != 0 || r.reserved2[0] != 0 || r.reserved2[1] != 0)
+    return fail(MP_ERR_INVALID, "%s: the reserved words must be 0", kWho);
+  if (r.op == MP_STATS_CLEAR) {   // the engine's launches are what they were
+    e->has_stats = false;
+    e->stats = episode_stats::Banks{};
+    e->stats_cols = episode_stats::Columns{};
+    return MP_OK;
+  }
+  if (r.num_columns < 0 || r.num_columns > MP_STATS_MAX_COLUMNS)
+    return fail(MP_ERR_INVALID, "%s: num_columns %d is outside [0, %d]", kWho, r.num_columns, MP_STATS_MAX_COLUMNS);
+  if (r.num_pairs < 0 || r.num_pairs > MP_STATS_MAX_PAIRS)
+    return fail(MP_ERR_INVALID, "%s: num_pairs %d is outside [0, %d]", kWho, r.num_pairs, MP_STATS_MAX_PAIRS);
+  if ((r.num_columns > 0 && !r.columns) || (r.num_pairs > 0 && !r.pairs))
+    return fail(MP_ERR_INVALID, "%s: NULL columns or pairs with a count above 0", kWho);
+  episode_stats::Columns cols = {};
+  cols.C = r.num_columns;
+  cols.C2 = r.num_pairs;
+  for (int i = 0; i < r.num_columns + r.num_pairs; ++i) {
+    const bool pair = i >= r.num_columns;
+    const MpEventColumn& c = pair ? r.pairs[i - r.num_columns] : r.columns[i];
+    const char* what = pair ? "pairs" : "columns";
+    const int at = pair ? i - r.num_columns : i;
+    if (c.player_payload > 1 || c.filter_payload > 2)
+      return fail(MP_ERR_INVALID, "%s: %s[%d] names a payload that is neither a nor b", kWho, what, at);
+    if (c.player_shift > 31 || c.filter_shift > 31 || c.other_shift > 31)
+      return fail(MP_ERR_INVALID, "%s: %s[%d] has a shift of 32 or more", kWho, what, at);
+    if (c.reserved[0] || c.reserved[1] || c.reserved[2] || c.reserved2)
+      return fail(MP_ERR_INVALID, "%s: %s[%d]: the reserved words must be 0", kWho, what, at);
+    (pair ? cols.pair[at] : cols.col[at]) = c;
+  }
+  const bool events_needed = r.num_columns + r.num_pairs > 0;
+  if (r.op == MP_STATS_TALLY || r.op == MP_STATS_HOST) {
+    if (r.steps < 1 || r.count < 1)
+      return fail(MP_ERR_INVALID, "%s: steps %d and count %d must be at least 1", kWho, r.steps, r.count);
+    if (r.op == MP_STATS_TALLY ? !r.events : events_needed && !r.events)
+      return fail(MP_ERR_INVALID, "%s: NULL events", kWho);
+    if ((r.num_columns > 0 && !r.running.counts) || (r.num_pairs > 0 && !r.running.pairs))
+      return fail(MP_ERR_INVALID, "%s: NULL counts or pairs for the columns named", kWho);
+  }
+  if (r.op == MP_STATS_HOST && (r.num_players < 1 || r.num_players > MP_MAX_PLAYERS))
+    return fail(MP_ERR_INVALID, "%s: num_players %d is outside [1, %d]", kWho, r.num_players, MP_MAX_PLAYERS);
+  const uint64_t P = r.op == MP_STATS_HOST ? (uint64_t)r.num_players : (uint64_t)e->t.P;
+  const uint64_t CP = (uint64_t)r.num_columns * P, PP = (uint64_t)r.num_pairs * P * P;
+  episode_stats::Banks b = {r.open, r.episodes, r.dropped, r.running, r.last, r.total};
+  if (r.op == MP_STATS_REGISTER || r.op == MP_STATS_HOST) {
+    const MpStatsBank* banks[3] = {&r.running, &r.last, &r.total};
+    if (!r.open || !r.episodes || !r.dropped) return fail(MP_ERR_INVALID, "%s: NULL open, episodes or dropped", kWho);
+    for (const MpStatsBank* k : banks)
+      if (!k->returns || !k->length || (r.num_columns > 0 && !k->counts) || (r.num_pairs > 0 && !k->pairs))
+        return fail(MP_ERR_INVALID, "%s: a bank (running, last, total) lacks a tensor", kWho);
+  }
+  if (r.op == MP_STATS_HOST) {
+    if (!r.step_type || !r.reward) return fail(MP_ERR_INVALID, "%s: NULL step_type or reward", kWho);
+    episode_stats::Rows rows = {};
+    rows.columns = r.count; rows.K = r.steps; rows.P = (int)P;
+    rows.step_type = r.step_type; rows.step_type_bytes = (long long)r.count * 4;
+    rows.reward = r.reward; rows.reward_bytes = (long long)r.count * (long long)P * 8;
+    rows.events = r.events; rows.events_bytes = (long long)r.count * MP_EVENT_ROWS * 16;
+    rows.active = r.active; rows.active_bytes = r.count;
+    rows.ran = r.ran;
+    episode_stats_host(cols, b, rows);
+    return MP_OK;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  // every tensor: device memory of the engine's device, aligned, its whole extent in one allocation
+  struct Tensor { const char* what; const void* at; uint64_t bytes; uint64_t align; };
+  std::vector<Tensor> all;
+  if (r.op == MP_STATS_TALLY) {
+    const uint64_t K = (uint64_t)r.steps, M = (uint64_t)r.count;
+    all.push_back({"events", r.events, K * M * MP_EVENT_ROWS * 16u, 16});
+    if (r.active) all.push_back({"active", r.active, K * M, 1});
+    if (r.ran) all.push_back({"ran", r.ran, M * 4u, 4});
+    if (CP) all.push_back({"counts", r.running.counts, M * CP * 4u, 4});
+    if (PP) all.push_back({"pairs", r.running.pairs, M * PP * 4u, 4});
+  } else {
+    const uint64_t N = (uint64_t)e->N;
+    all.push_back({"open", r.open, N, 1});
+    all.push_back({"episodes", r.episodes, N * 4u, 4});
+    all.push_back({"dropped", r.dropped, N * 4u, 4});
+    const MpStatsBank* banks[3] = {&r.running, &r.last, &r.total};
+    static const char* const names[3][4] = {{"running.returns", "running.length", "running.counts", "running.pairs"},
+                                            {"last.returns", "last.length", "last.counts", "last.pairs"},
+                                            {"total.returns", "total.length", "total.counts", "total.pairs"}};
+    for (int k = 0; k < 3; ++k) {
+      const uint64_t elem = k == 2 ? 8u : 4u;
+      all.push_back({names[k][0], banks[k]->returns, N * P * 8u, 8});
+      all.push_back({names[k][1], banks[k]->length, N * elem, elem});
+      if (CP) all.push_back({names[k][2], banks[k]->counts, N * CP * elem, elem});
+      if (PP) all.push_back({names[k][3], banks[k]->pairs, N * PP * elem, elem});
+    }
+  }
+  char name[64];
+  for (const Tensor& t : all) {
+    if ((uintptr_t)t.at % t.align)
+      return fail(MP_ERR_INVALID, "%s: %s %p is not %llu-byte aligned", kWho, t.what, t.at, (unsigned long long)t.align);
+    snprintf(name, sizeof name, "%s (%s)", kWho, t.what);
+    if (int rc = check_bank(e, t.at, t.bytes, name)) return rc;
+  }
+  if (r.op == MP_STATS_TALLY) {
+    episode_stats::Rows rows = {};
+    rows.columns = r.count; rows.K = r.steps; rows.P = (int)P;
+    rows.events = r.events; rows.events_bytes = (long long)r.count * MP_EVENT_ROWS * 16;
+    rows.active = r.active; rows.active_bytes = r.count;
+    rows.ran = r.ran;
+    launch_episode_stats(cols, b, rows, true, e->stream);
+    HIP_TRY(hipGetLastError());
+    return MP_OK;
+  }
+  e->stats_cols = cols;
+  e->stats = b;
+  e->has_stats = true;
+  return MP_OK;
+}
+
+static_assert(sizeof(MpEpisodeStats) == 224 && sizeof(MpEventColumn) == 32 && sizeof(MpStatsBank) == 32 &&
+                  sizeof(MpEpisodeStats) != sizeof(MpStepListed) && sizeof(MpEpisodeStats) != sizeof(MpStepUntil) &&
+                  sizeof(MpEpisodeStats) != sizeof(MpStepActive) && sizeof(MpEpisodeStats) != sizeof(MpStateLayout) &&
+                  sizeof(MpEpisodeStats) != sizeof(MpStepMany) && sizeof(MpEpisodeStats) < 448,
+              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
 static_assert(sizeof(MpStatesObserve) == 64 && sizeof(MpStatesObserve) != sizeof(MpKernelVariant) &&
                   sizeof(MpStatesObserve) != sizeof(MpWorldStates) && sizeof(MpStatesObserve) != sizeof(MpStepMany) &&
                   sizeof(MpStatesObserve) != sizeof(MpStepTrajectory),
@@ -2492,6 +2667,11 @@ int mp_restore(MpEngine* e, const void* buf, uint64_t bytes) {
     MpStepListed r;   // (read only: nothing is written back)
     memcpy(&r, buf, sizeof r);
     return listed_request(e, r);
+  }
+  if (buf && bytes == sizeof(MpEpisodeStats)) {
+    MpEpisodeStats r;   // (read only: nothing is written back)
+    memcpy(&r, buf, sizeof r);
+    return episode_stats_request(e, r);
   }
   if (!e || !buf || bytes != mp_snapshot_bytes(e))
     return fail(MP_ERR_INVALID, "mp_restore: bad buffer");
@@ -2829,7 +3009,11 @@ struct ProbeState {
   }
   // (and a bound "N.LAYER" is not written by the probe's launches: dry ones would put the records'
   // LAYER into whichever ring slot is being timed, stepping ones the probe's steps')
-  void hold_ring() { was_held = e->ring_hold; e->ring_hold = true; e->layer_hold = true; held = true; }
+  bool was_stats = false;   // (the probe's launches are not folded into registered episode statistics)
+  void hold_ring() {
+    was_held = e->ring_hold; e->ring_hold = true; e->layer_hold = true; held = true;
+    was_stats = e->stats_hold; e->stats_hold = true;
+  }
   // MP_OK with copied == false: no room for the copy — the probe runs dry
   int save() {
     const size_t total = parts[0] + parts[1] + parts[2] + parts[3];
@@ -2883,6 +3067,7 @@ struct ProbeState {
     if (held) {
       e->ring_hold = was_held;
       e->layer_hold = false;
+      e->stats_hold = was_stats;
       held = false;
       if (e->ring_slots > 0 && !e->ring_hold) {   // ring kinds point at the slot written last again
         const uint64_t last = e->ring_cursor ? (e->ring_cursor - 1) % (uint64_t)e->ring_slots : 0;

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -878,6 +879,245 @@ def check_episode_starts(bank, rows, verdicts, num_worlds: int, state_bytes: int
   return M
 
 
+# Episode statistics on the device (include/mp_engine.h: MpEpisodeStats), carried by mp_restore
+STATS_MAX_COLUMNS, STATS_MAX_PAIRS = 32, 4
+MP_STATS_REGISTER, MP_STATS_CLEAR, MP_STATS_TALLY, MP_STATS_HOST = 1, 2, 3, 4
+
+
+class MpEventColumn(ctypes.Structure):
+  _fields_ = [("type", ctypes.c_int32), ("player_payload", ctypes.c_uint8), ("player_shift", ctypes.c_uint8),
+              ("filter_payload", ctypes.c_uint8), ("filter_shift", ctypes.c_uint8),
+              ("player_mask", ctypes.c_uint32), ("filter_mask", ctypes.c_uint32), ("filter_value", ctypes.c_uint32),
+              ("other_shift", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3), ("other_mask", ctypes.c_uint32),
+              ("reserved2", ctypes.c_uint32)]
+
+
+class MpStatsBank(ctypes.Structure):
+  _fields_ = [("returns", ctypes.c_void_p), ("length", ctypes.c_void_p), ("counts", ctypes.c_void_p),
+              ("pairs", ctypes.c_void_p)]
+
+
+class MpEpisodeStats(ctypes.Structure):
+  _fields_ = [("struct_size", ctypes.c_uint32), ("op", ctypes.c_int32), ("num_columns", ctypes.c_int32),
+              ("num_pairs", ctypes.c_int32), ("columns", ctypes.c_void_p), ("pairs", ctypes.c_void_p),
+              ("open", ctypes.c_void_p), ("episodes", ctypes.c_void_p), ("dropped", ctypes.c_void_p),
+              ("running", MpStatsBank), ("last", MpStatsBank), ("total", MpStatsBank),
+              ("steps", ctypes.c_int32), ("count", ctypes.c_int32), ("num_players", ctypes.c_int32),
+              ("reserved", ctypes.c_int32), ("step_type", ctypes.c_void_p), ("reward", ctypes.c_void_p),
+              ("events", ctypes.c_void_p), ("active", ctypes.c_void_p), ("ran", ctypes.c_void_p),
+              ("reserved2", ctypes.c_uint64 * 2)]
+
+
+_FULL = 0xFFFFFFFF
+# event name -> payload key -> (payload: 0 a / 1 b, shift, mask): where each key of EVENT_TYPES lies
+# in a raw event row (gift's two roles are the host's: they are no payload)
+EVENT_FIELDS = {
+    "zap": {"source": (0, 0, _FULL), "target": (1, 0, _FULL)},
+    "edible_consumed": {"player_index": (0, 0, _FULL)},
+    "player_cleaned": {"player_index": (0, 0, _FULL)},
+    "claimed_resource": {"player_index": (0, 0, _FULL)},
+    "destroyed_resource": {"player_index": (0, 0, _FULL), "class": (1, 0, _FULL)},
+    "sanctioning": {"source": (0, 0, _FULL), "target": (1, 0, _FULL)},
+    "removal_due_to_sanctioning": {"source": (0, 0, _FULL), "target": (1, 0, _FULL)},
+    "set_sanctioning_level": {"player_index": (0, 0, _FULL), "level": (1, 0, _FULL)},
+    "AvatarStarted": {},
+    "coin_consumed": {"player_index": (0, 0, _FULL), "types": (1, 0, _FULL), "player_coin_type": (1, 1, _FULL >> 1),
+                      "coin_type": (1, 0, 1)},
+    "interaction": {"row_player_idx": (0, 0, _FULL), "col_player_idx": (1, 0, _FULL)},
+    "collected_resource": {"player_index": (0, 0, _FULL), "class": (1, 0, _FULL)},
+    "mining": {"player": (0, 0, _FULL), "ore_type": (1, 0, _FULL)},
+    "extraction": {"player": (0, 0, _FULL), "ore_type": (1, 0, _FULL)},
+    "extraction_pair": {"player_a": (0, 0, _FULL), "player_b": (1, 2, _FULL >> 2), "ore_type": (1, 0, 3)},
+    "gift": {"gifter_index": (0, 0, 15), "source_type": (0, 4, _FULL >> 4), "receipient_index": (1, 0, 15),
+             "received_amount": (1, 4, _FULL >> 4)},
+    "eating_mushroom": {"player_index": (0, 0, _FULL), "mushroom_type": (1, 0, _FULL)},
+    "receiver_accepted_item": {"player_index": (0, 0, _FULL), "item": (1, 0, _FULL)},
+    "item_dropped_into_pot": {"player_index": (0, 0, _FULL), "item": (1, 0, _FULL)},
+    "cooked_food_collected_from_pot": {"player_index": (0, 0, _FULL), "cooked_item": (1, 0, _FULL)},
+}
+EVENT_PLAYER_KEYS = ("source", "target", "player_index", "row_player_idx", "col_player_idx", "player", "player_a",
+                     "player_b", "gifter_index", "receipient_index")
+_EVENT_IDS = {name: type_ for type_, (name, _) in EVENT_TYPES.items()}
+# MPK_SUBSTRATE_* -> the event types the level's rules can push (the push_event sites of
+# csrc/step_<level>.h and step_common.h's zap)
+LEVEL_EVENT_TYPES = {
+    1: (9, 1, 2, 3),                  # clean_up
+    2: (9, 1, 2),                     # commons_harvest
+    3: (9, 1, 4, 5, 6, 7, 8),         # territory
+    4: (9, 1, 10),                    # coins
+    5: (9, 1, 5, 11, 12),             # *_in_the_matrix
+    6: (9, 1, 13, 14, 15),            # coop_mining
+    7: (9, 1, 16),                    # gift_refinements
+    8: (9, 1, 17, 18, 19),            # collaborative_cooking
+    9: (9, 1, 6, 7, 8, 20),           # externality_mushrooms
+}
+_COLUMN_NAME = re.compile(r"^(\w+)\.(\w+)(?:>(\w+))?(?:\[(\w+)=(-?\d+)\])?$")
+
+
+def parse_event_column(name: str):
+  """A column name as (MpEventColumn, is_pair): "zap.source" counts zap events per source player,
+  "zap.target" per target, "mining.player[ore_type=2]" only those whose ore_type is 2, and
+  "zap.source>target" is a pair column, [P, P] at (source, target).  ValueError for a name that does
+  not parse, an unknown event or key, a key that holds no player, or a pair whose two players lie in
+  one payload."""
+  m = _COLUMN_NAME.match(name) if isinstance(name, str) else None
+  if not m:
+    raise ValueError(f"event column {name!r}: expected \"event.key\", \"event.key[key=value]\" or \"event.key>key\"")
+  event, key, other, fkey, fvalue = m.groups()
+  if event not in EVENT_FIELDS:
+    raise ValueError(f"event column {name!r}: unknown event {event!r} (known: {sorted(EVENT_FIELDS)})")
+  fields = EVENT_FIELDS[event]
+  for k in (key, other):
+    if k is not None and (k not in fields or k not in EVENT_PLAYER_KEYS):
+      players = [f for f in fields if f in EVENT_PLAYER_KEYS]
+      raise ValueError(f"event column {name!r}: {k!r} is no player-valued key of {event!r} (it has {players})")
+  col = MpEventColumn()
+  col.type = _EVENT_IDS[event]
+  col.player_payload, col.player_shift, col.player_mask = fields[key]
+  if other is not None:
+    payload, col.other_shift, col.other_mask = fields[other]
+    if payload == col.player_payload:
+      raise ValueError(f"event column {name!r}: {key!r} and {other!r} lie in the same payload")
+  if fkey is not None:
+    if fkey not in fields:
+      raise ValueError(f"event column {name!r}: {fkey!r} is no key of {event!r} (it has {sorted(fields)})")
+    payload, col.filter_shift, col.filter_mask = fields[fkey]
+    col.filter_payload = payload + 1
+    if int(fvalue) < 0 or int(fvalue) > col.filter_mask:
+      raise ValueError(f"event column {name!r}: {fkey!r} cannot be {fvalue}")
+    col.filter_value = int(fvalue)
+  return col, other is not None
+
+
+def level_event_columns(substrate: int):
+  """The default columns of a level (MPK_SUBSTRATE_*): for every event type its rules can push, one
+  unfiltered column per player-valued payload key; no pair columns."""
+  names = []
+  for type_ in LEVEL_EVENT_TYPES[int(substrate)]:
+    event, _ = EVENT_TYPES[type_]
+    names += [f"{event}.{key}" for key in EVENT_FIELDS[event] if key in EVENT_PLAYER_KEYS]
+  return tuple(names)
+
+
+def _column_array(names, limit: int, pair: bool, what: str):
+  names = tuple(names)
+  if len(names) > limit:
+    raise ValueError(f"{what}: at most {limit} {'pair ' if pair else ''}columns (got {len(names)})")
+  cols = (MpEventColumn * max(len(names), 1))()
+  for i, name in enumerate(names):
+    cols[i], is_pair = parse_event_column(name)
+    if is_pair != pair:
+      raise ValueError(f"{what}: {name!r} is {'a pair column: name it in pairs=' if is_pair else 'no pair column'}")
+  return names, cols
+
+
+STATS_BANKS = ("running", "last", "total")
+
+
+def episode_stats_arrays(num_worlds: int, num_players: int, num_columns: int, num_pairs: int, empty):
+  """The statistics tensors of an MpEpisodeStats request, zeroed, as a dict: `empty(shape, dtype
+  name)` allocates one ("uint8", "int32", "int64", "float64")."""
+  N, P, C, C2 = int(num_worlds), int(num_players), int(num_columns), int(num_pairs)
+  out = {"open": empty((N,), "uint8"), "episodes": empty((N,), "int32"), "dropped": empty((N,), "int32")}
+  for bank in STATS_BANKS:
+    ints = "int64" if bank == "total" else "int32"
+    out[bank] = {"returns": empty((N, P), "float64"), "length": empty((N,), ints),
+                 "counts": empty((N, C, P), ints), "pairs": empty((N, C2, P, P), ints)}
+  return out
+
+
+def _stats_request(op: int, cols, ncols: int, pairs, npairs: int, arrays, ptr) -> MpEpisodeStats:
+  req = MpEpisodeStats(ctypes.sizeof(MpEpisodeStats), op, ncols, npairs)
+  req.columns = ctypes.addressof(cols) if ncols else None
+  req.pairs = ctypes.addressof(pairs) if npairs else None
+  if arrays is not None:
+    req.open, req.episodes, req.dropped = ptr(arrays["open"]), ptr(arrays["episodes"]), ptr(arrays["dropped"])
+    for bank in STATS_BANKS:
+      b = getattr(req, bank)
+      b.returns, b.length = ptr(arrays[bank]["returns"]), ptr(arrays[bank]["length"])
+      b.counts = ptr(arrays[bank]["counts"]) if ncols else None
+      b.pairs = ptr(arrays[bank]["pairs"]) if npairs else None
+  return req
+
+
+def episode_stats_host(stats, step_type, reward, events, columns=(), pairs=(), active=None, ran=None):
+  """The rule of MpEpisodeStats applied on the host, by the library's own functions compiled for the
+  host (no engine, no device): folds K steps of n worlds — step_type int32 [K, n], reward float64
+  [K, n, P], events int32 [K, n, EVENT_ROWS, 4] (None with no columns), active uint8 [K, n] or
+  None, ran int32 [n] or None — into `stats`, numpy arrays laid out as episode_stats_arrays gives
+  them (see numpy_episode_stats), in place.  Returns `stats`."""
+  L = load_library()
+  names, cols = _column_array(columns, STATS_MAX_COLUMNS, False, "episode_stats_host")
+  pnames, pcols = _column_array(pairs, STATS_MAX_PAIRS, True, "episode_stats_host")
+  step_type = np.ascontiguousarray(step_type, np.int32)
+  K, n = step_type.shape
+  reward = np.ascontiguousarray(reward, np.float64)
+  P = int(reward.shape[2])
+  if reward.shape != (K, n, P):
+    raise ValueError(f"episode_stats_host: reward must be [K, n, P] = {(K, n, P)} (got {reward.shape})")
+  keep = [step_type, reward]
+  def host(x, dtype, shape, what):
+    if x is None:
+      return None
+    x = np.ascontiguousarray(x, dtype)
+    if x.shape != shape:
+      raise ValueError(f"episode_stats_host: {what} must have shape {shape} (got {x.shape})")
+    keep.append(x)
+    return x.ctypes.data
+  def ptr(a):
+    if not isinstance(a, np.ndarray) or not a.flags.c_contiguous:
+      raise ValueError("episode_stats_host: the statistics must be contiguous numpy arrays")
+    return a.ctypes.data
+  want = episode_stats_arrays(n, P, len(names), len(pnames), lambda shape, dtype: (shape, dtype))
+  for key, value in want.items():
+    for sub, (shape, dtype) in (value.items() if isinstance(value, dict) else [(None, value)]):
+      a = stats[key] if sub is None else stats[key][sub]
+      if not isinstance(a, np.ndarray) or a.shape != shape or a.dtype != np.dtype(dtype):
+        raise ValueError(f"episode_stats_host: stats[{key!r}]{'' if sub is None else '[' + repr(sub) + ']'} must be a "
+                         f"{dtype} array of shape {shape}")
+  req = _stats_request(MP_STATS_HOST, cols, len(names), pcols, len(pnames), stats, ptr)
+  req.steps, req.count, req.num_players = K, n, P
+  req.step_type, req.reward = step_type.ctypes.data, reward.ctypes.data
+  req.events = host(events, np.int32, (K, n, EVENT_ROWS, 4), "events")
+  req.active = host(active, np.uint8, (K, n), "active")
+  req.ran = host(ran, np.int32, (n,), "ran")
+  _check(L, L.mp_restore(None, ctypes.addressof(req), ctypes.sizeof(req)), "mp_restore (MpEpisodeStats)")
+  return stats
+
+
+def numpy_episode_stats(num_worlds: int, num_players: int, num_columns: int, num_pairs: int = 0):
+  """Zeroed host statistics for episode_stats_host."""
+  return episode_stats_arrays(num_worlds, num_players, num_columns, num_pairs,
+                              lambda shape, dtype: np.zeros(shape, dtype))
+
+
+class EpisodeStats:
+  """The live statistics tensors of a registration (Engine.set_episode_stats): `.open` uint8 [N],
+  `.episodes` and `.dropped` int32 [N], and the banks `.running`, `.last`, `.total`, each a dict of
+  "returns" float64 [N, P], "length" [N], "counts" [N, C, P], "pairs" [N, C2, P, P] (int32; int64
+  in total).  `.columns` / `.pairs` are the names; `.index(name)` a column's (or pair's) index.
+  The tensors are written by the device behind every submission: read them in stream order."""
+
+  def __init__(self, columns, pairs, arrays):
+    self.columns, self.pair_columns = tuple(columns), tuple(pairs)
+    self.arrays = arrays
+    self.open, self.episodes, self.dropped = arrays["open"], arrays["episodes"], arrays["dropped"]
+    self.running, self.last, self.total = arrays["running"], arrays["last"], arrays["total"]
+
+  def index(self, name: str) -> int:
+    if name in self.columns:
+      return self.columns.index(name)
+    if name in self.pair_columns:
+      return self.pair_columns.index(name)
+    raise ValueError(f"{name!r} is no registered column (columns {self.columns}, pairs {self.pair_columns})")
+
+  def slice(self, lo: int, hi: int) -> "EpisodeStats":
+    """Worlds [lo, hi) of every tensor, in place (a mixture hands each member its slice)."""
+    cut = {k: ({s: v[lo:hi] for s, v in a.items()} if isinstance(a, dict) else a[lo:hi])
+           for k, a in self.arrays.items()}
+    return EpisodeStats(self.columns, self.pair_columns, cut)
+
+
 def _step_distance(tensor, what: str) -> int:
   """Bytes between tensor[k] and tensor[k + 1] of a tensor that may be non-contiguous along its
   first dimension only (a column slice [:, a:b] of a wider tensor)."""
@@ -1128,6 +1368,8 @@ class Engine:
     }
     self._bound: Dict[int, "torch.Tensor"] = {}
     self._episode_starts = None
+    self._stats = None           # the registered EpisodeStats (set_episode_stats)
+    self._stats_scratch = {}     # the rows a K-step request carries for it without being asked
 
   @property
   def fused(self) -> bool:
@@ -1621,10 +1863,23 @@ class Engine:
     kinds = check_step_rows(observations, taken=[STEP_MANY_NAMES[n] for n in names])
     states = bool(states) or (out is not None and out.get("states") is not None)
     hashes = bool(hashes) or (out is not None and out.get("hashes") is not None)
-    keys = names + list(kinds) + (["states"] if states else []) + (["hashes"] if hashes else [])
+    # (registered episode statistics read the REWARD, STEP_TYPE and EVENTS rows of the launch: rows
+    # nobody asked for go to scratch tensors of the engine's and stay out of the result)
+    hidden = []
+    if self._stats is not None:
+      need = ["reward", "step_type"] + (["events"] if self._stats.columns or self._stats.pair_columns else [])
+      hidden = [n for n in need if n not in names and STEP_MANY_NAMES[n] not in kinds]
+    keys = names + list(kinds) + (["states"] if states else []) + (["hashes"] if hashes else []) + hidden
     rows = (MpStepRow * len(keys))()
     result = {}
     for i, key in enumerate(keys):
+      if i >= len(keys) - len(hidden):
+        kind, per_world, dtype = step_row(self.shapes, key)
+        buf = self._stats_scratch.get(key)
+        if buf is None or tuple(buf.shape) != (K, C) + per_world:
+          buf = self._stats_scratch[key] = t.empty((K, C) + per_world, dtype=dtype, device=self.device)
+        rows[i].kind, rows[i].rows, rows[i].step_bytes = kind, buf.data_ptr(), _step_distance(buf, key)
+        continue
       if key == "states":
         kind, per_world, dtype = STEP_ROW_STATE, (int(self.info.world_state_bytes),), t.uint8
       elif key == "hashes":
@@ -1671,6 +1926,11 @@ class Engine:
     elif listed:   # (the stopping request with nothing that stops a world)
       req = MpStepListed(ctypes.sizeof(MpStepListed), K, 1 if fields else 0, len(rows))
       req.gamma = 1.0
+      if self._stats is not None:   # (which steps ran is read from it)
+        ran = self._stats_scratch.get("ran")
+        if ran is None or tuple(ran.shape) != (C,):
+          ran = self._stats_scratch["ran"] = t.empty((C,), dtype=t.int32, device=self.device)
+        req.ran = ran.data_ptr()
       if active is not None:
         req.active = mask.data_ptr()
         req.active_step_bytes = mask_step
@@ -1931,6 +2191,124 @@ class Engine:
   def episode_starts(self):
     """The registration as a dict (bank, rows, verdicts, fresh, fingerprint), or None."""
     return None if self._episode_starts is None else dict(self._episode_starts)
+
+  # -- episode statistics (include/mp_engine.h: an MpEpisodeStats request) --
+  def event_columns(self):
+    """The default columns of this engine's level: for every event type its rules can push, one
+    unfiltered column per player-valued payload key ("zap.source", "zap.target", ...)."""
+    return level_event_columns(int(self.info.substrate))
+
+  def _torch_ptr(self, x):
+    return x.data_ptr()
+
+  def set_episode_stats(self, columns="default", pairs=(), out: Optional[EpisodeStats] = None) -> EpisodeStats:
+    """From now on every submission (reset, step, step_fields, step_many in every form,
+    load_worlds) is followed on the same stream, without synchronisation, by ONE launch that folds
+    what it wrote into per-world statistics on the device: per-player returns, lengths and event
+    counts of the running episode, of the last finished one and of all finished ones (the rule:
+    include/mp_engine.h, MpEpisodeStats).  columns: names like "zap.source",
+    "mining.player[ore_type=2]" ("default": event_columns(); (): returns and lengths only);
+    pairs: pair columns like "zap.source>target".  out: an EpisodeStats whose tensors to use (a
+    mixture hands each member a slice of one set); None allocates zeroed ones.  Returns the
+    EpisodeStats; read its tensors in stream order.  A K-step call then carries the REWARD,
+    STEP_TYPE and (with columns) EVENTS rows even when not asked for: the EVENTS row is K x
+    columns x 2 KB.  None clears the registration (clear_episode_stats)."""
+    if columns is None:
+      self.clear_episode_stats()
+      return None
+    t = self._torch
+    names, cols = _column_array(self.event_columns() if isinstance(columns, str) and columns == "default" else columns,
+                                STATS_MAX_COLUMNS, False, "set_episode_stats")
+    pnames, pcols = _column_array(pairs, STATS_MAX_PAIRS, True, "set_episode_stats")
+    want = episode_stats_arrays(self.N, self.P, len(names), len(pnames),
+                                lambda shape, dtype: (shape, getattr(t, dtype)))
+    if out is None:
+      arrays = episode_stats_arrays(self.N, self.P, len(names), len(pnames),
+                                    lambda shape, dtype: t.zeros(shape, dtype=getattr(t, dtype), device=self.device))
+      out = EpisodeStats(names, pnames, arrays)
+    else:
+      if tuple(out.columns) != names or tuple(out.pair_columns) != pnames:
+        raise ValueError("set_episode_stats: out= was made for other columns")
+      for key, value in want.items():
+        for sub, (shape, dtype) in (value.items() if isinstance(value, dict) else [(None, value)]):
+          a = out.arrays[key] if sub is None else out.arrays[key][sub]
+          if (not isinstance(a, t.Tensor) or tuple(a.shape) != shape or a.dtype != dtype or
+              a.device != self.device or not a.is_contiguous()):
+            raise ValueError(f"set_episode_stats: out.{key}{'' if sub is None else '[' + repr(sub) + ']'} must be "
+                             f"a contiguous {dtype} tensor of shape {shape} on {self.device}")
+    req = _stats_request(MP_STATS_REGISTER, cols, len(names), pcols, len(pnames), out.arrays, self._torch_ptr)
+    _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
+           "mp_restore (MpEpisodeStats)")
+    self._stats = out
+    self._stats_scratch = {}
+    return out
+
+  def clear_episode_stats(self):
+    """No statistics launch any more: the engine issues exactly the launches it issued before."""
+    req = MpEpisodeStats(ctypes.sizeof(MpEpisodeStats), MP_STATS_CLEAR)
+    _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
+           "mp_restore (MpEpisodeStats)")
+    self._stats = None
+    self._stats_scratch = {}
+
+  @property
+  def episode_stats(self) -> Optional[EpisodeStats]:
+    return self._stats
+
+  episode_stats_host = staticmethod(episode_stats_host)
+
+  def tally_events(self, events_rows, columns=None, active=None, ran=None, out=None, pairs=()):
+    """Event counts of raw event rows, on the device: events_rows int32 [K, M, EVENT_ROWS, 4] (what
+    step_many(events=True) returns; [M, EVENT_ROWS, 4] is K = 1) -> int32 [M, C, P], the rows of
+    every column (None: event_columns()) summed over the steps that ran: all of them, or those
+    where active ([K, M] uint8 / bool) is non-zero, of them the first ran[i] (int32 [M]).  With
+    pairs= returns (counts, pairs int32 [M, C2, P, P]).  The kernel of the episode statistics
+    without the episode logic; one launch, no synchronisation."""
+    t = self._torch
+    names, cols = _column_array(self.event_columns() if columns is None else columns, STATS_MAX_COLUMNS, False,
+                                "tally_events")
+    pnames, pcols = _column_array(pairs, STATS_MAX_PAIRS, True, "tally_events")
+    ev = events_rows
+    if not isinstance(ev, t.Tensor):
+      ev = t.from_numpy(np.ascontiguousarray(ev, np.int32)).to(self.device)
+    if ev.dim() == 3:
+      ev = ev[None]
+    if (ev.dtype != t.int32 or ev.dim() != 4 or tuple(ev.shape[2:]) != (EVENT_ROWS, 4) or ev.device != self.device):
+      raise ValueError(f"tally_events: events_rows must be int32 [K, M, {EVENT_ROWS}, 4] on {self.device}")
+    ev = ev.contiguous()
+    K, M = int(ev.shape[0]), int(ev.shape[1])
+    if K < 1 or M < 1:
+      raise ValueError("tally_events: no event rows")
+    def dev(x, dtype, shape, what):
+      if x is None:
+        return None
+      if not isinstance(x, t.Tensor):
+        x = t.from_numpy(np.ascontiguousarray(x)).to(self.device)
+      if x.dtype == t.bool:
+        x = x.to(t.uint8)
+      if x.dtype != dtype or tuple(x.shape) != shape or x.device != self.device:
+        raise ValueError(f"tally_events: {what} must be a {dtype} tensor of shape {shape} on {self.device}")
+      return x.contiguous()
+    active = dev(active, t.uint8, (K, M), "active")
+    ran = dev(ran, t.int32, (M,), "ran")
+    shape = (M, len(names), self.P)
+    if out is None:
+      out = t.empty(shape, dtype=t.int32, device=self.device)
+    elif (not isinstance(out, t.Tensor) or out.dtype != t.int32 or tuple(out.shape) != shape or
+          out.device != self.device or not out.is_contiguous()):
+      raise ValueError(f"tally_events: out must be a contiguous int32 tensor of shape {shape} on {self.device}")
+    pout = t.empty((M, len(pnames), self.P, self.P), dtype=t.int32, device=self.device)
+    self.use_current_stream()
+    req = _stats_request(MP_STATS_TALLY, cols, len(names), pcols, len(pnames), None, None)
+    req.running.counts = out.data_ptr() if names else None
+    req.running.pairs = pout.data_ptr() if pnames else None
+    req.events, req.steps, req.count = ev.data_ptr(), K, M
+    req.active = None if active is None else active.data_ptr()
+    req.ran = None if ran is None else ran.data_ptr()
+    _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
+           "mp_restore (MpEpisodeStats)")
+    self._tally_args = (ev, active, ran, out, pout)   # (kept until the next call: the launch may not have run yet)
+    return (out, pout) if pnames else out
 
   def observe_states(self, bank, kind: int, rows=None, out=None, fingerprint: Optional[int] = None):
     """Observation `kind` of rows of `bank` (uint8 [M, S] device tensor from save_worlds or

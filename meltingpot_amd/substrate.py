@@ -1248,8 +1248,43 @@ class Substrate:
                                  fingerprint=states.fingerprint)
     return rows
 
+  def event_columns(self):
+    """The default statistics columns of this level: for every event type its rules can push, one
+    unfiltered column per player-valued payload key ("zap.source", "zap.target", ...)."""
+    return self._eng.event_columns()
+
+  def set_episode_stats(self, columns="default", pairs=(), out=None):
+    """Per-episode returns, lengths and event counts per player, kept on the device.  From now on
+    every reset, step, step_many and load_state is followed on the same stream by one launch that
+    folds what it wrote into the tensors of the returned `EpisodeStats`: `.running`, `.last` and
+    `.total` (dicts of "returns" [N, P], "length" [N], "counts" [N, C, P], "pairs" [N, C2, P, P]),
+    `.episodes`, `.open`, `.dropped`, `.columns`, `.index(name)`.  Episodes that end in the middle
+    of a step_many launch are counted like any other; no event row goes to the host.
+    columns: names like "zap.source", "player_cleaned.player_index", "mining.player[ore_type=2]"
+    ("default": `event_columns()`; (): returns and lengths only); pairs: pair columns like
+    "zap.source>target".  With columns a step_many call carries the EVENTS row (K x worlds x 2 KB)
+    even when events=False; it stays out of the result.  None clears the registration."""
+    if columns is None:
+      self._eng.clear_episode_stats()
+      return None
+    if not self._batched:
+      raise ValueError("set_episode_stats keeps statistics of a batch of worlds: build the substrate with "
+                       "num_worlds > 1")
+    self._eng.use_current_stream()
+    return self._eng.set_episode_stats(columns, pairs, out)
+
+  def tally_events(self, res_or_rows, columns=None, active=None, ran=None, out=None, pairs=()):
+    """`Engine.tally_events` of a step_many result (its `.events`, from events=True) or of a raw
+    int32 [K, M, EVENT_ROWS, 4] tensor: int32 [M, C, P] event counts per column and player, summed
+    over the steps that ran, on the device."""
+    rows = getattr(res_or_rows, "events", res_or_rows)
+    if rows is None:
+      raise ValueError("tally_events: the result holds no event rows: call step_many(events=True)")
+    self._eng.use_current_stream()
+    return self._eng.tally_events(rows, columns, active=active, ran=ran, out=out, pairs=pairs)
+
   # the leaves that are functions of a world's record (engine_lib.STATE_OBS_KINDS)
-  _STATE_LEAVES = ("RGB", "WORLD.RGB", "LAYER", "READY_TO_SHOOT", "POSITION", "ORIENTATION", "INVENTORY")
+  _STATE_LEAVES =("RGB", "WORLD.RGB", "LAYER", "READY_TO_SHOOT", "POSITION", "ORIENTATION", "INVENTORY")
 
   def state_leaves(self) -> Dict[str, int]:
     """The leaves `observe_states` can draw from saved states, with their engine kinds: "RGB"
@@ -2119,6 +2154,32 @@ class MixtureSubstrate:
     for m, states, off, n in zip(self._members, states_per_member, self._offsets, self._counts):
       m.set_episode_starts(states, None if states is None else rows[off:off + n], fresh=fresh, check=check)
     return rows
+
+  def event_columns(self):
+    return self._members[0].event_columns()
+
+  def set_episode_stats(self, columns="default", pairs=()):
+    """`Substrate.set_episode_stats` for the mixture: ONE set of [N, ...] statistics tensors, of
+    which member i registers its slice `[member_slice(i)]` in place (the world axis leads every
+    tensor, so a slice is contiguous).  None clears every member's registration."""
+    if columns is None:
+      for m in self._members:
+        m.set_episode_stats(None)
+      return None
+    eng = self._members[0]._eng
+    t = eng._torch
+    if isinstance(columns, str) and columns == "default":
+      columns = self.event_columns()
+    names, _ = engine_lib._column_array(columns, engine_lib.STATS_MAX_COLUMNS, False, "set_episode_stats")
+    pnames, _ = engine_lib._column_array(pairs, engine_lib.STATS_MAX_PAIRS, True, "set_episode_stats")
+    arrays = engine_lib.episode_stats_arrays(
+        self._N, self._P, len(names), len(pnames),
+        lambda shape, dtype: t.zeros(shape, dtype=getattr(t, dtype), device=eng.device))
+    stats = engine_lib.EpisodeStats(names, pnames, arrays)
+    for m, off, n in zip(self._members, self._offsets, self._counts):
+      m._eng.use_current_stream()
+      m._eng.set_episode_stats(names, pnames, out=stats.slice(off, off + n))
+    return stats
 
   def hash_worlds(self, worlds=None, planes=None, fields=None):
     """int64 [N] device tensor: every member's `Substrate.hash_worlds` of its own worlds, in
