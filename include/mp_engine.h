@@ -631,6 +631,85 @@ typedef struct {
   uint64_t reserved[2];    /* 0 */
 } MpStatesView;
 
+/* EGO_LAYER: the layer view in the avatar's OWN frame, as "RGB" shows it.  MP_OBS_LAYER is the
+ * reference's "N.LAYER" (avatar_library.lua:247-257, orientation = 'N'): its window is not turned
+ * with the avatar, so an avatar that faces east gets the cells to its north while its "RGB" shows
+ * the cells to its east.  EGO_LAYER is the layer observation the reference renders "RGB" from
+ * (avatar_library.lua:264-275, no orientation = 'N') and throws away: cell (i, j) of it names
+ * the sprites under cell (i, j) of "RGB".  It is no MpObsKind: it rides mp_snapshot as a request of
+ * its own and is recognised by its size: `bytes` = sizeof(MpEgoLayer), `host_buf` a HOST
+ * MpEgoLayer with struct_size set to it.  include/mp_ego_layer.h wraps it as inline C functions.
+ *
+ * Definition.  For a record (a bank row or a live world) and a viewer p, EGO_LAYER is int32
+ * [VH][VW][L], MP_OBS_LAYER's shape (VH = forward + backward + 1, VW = left + right + 1).  With
+ * vo = orientation[p], dx = vx - left, dy = vy - forward, the world offset (ax, ay) of window cell
+ * (vx, vy) follows the renderer's table: vo 0: (dx, dy); 1: (-dy, dx); 2: (-dx, -dy); 3: (dy, -dx).
+ * The world cell is (avatar_x[p] + ax, avatar_y[p] + ay); TORUS wraps both coordinates, otherwise
+ * a cell off the map is out of bounds.  The value at layer l is the one N.LAYER gives for that
+ * world cell: 1 + the viewer's remapped sprite of the state in plane l (0 for nothing), the
+ * OutOfBounds id on every layer of a cell off the map, and on every layer of every cell when the
+ * viewer is dead or off the grid (A6).  For a viewer that faces north EGO_LAYER equals
+ * MP_OBS_LAYER element for element.
+ * The ids are N.LAYER's (A17): the registration index behind the viewer's sprite map, with NO
+ * facing encoded.  The window is turned, the ids are not: an avatar q's facing in viewer p's frame
+ * is (ORIENTATION[q] - ORIENTATION[p]) & 3, and the pseudo-states of oriented beams and of kitchen
+ * inventories keep their absolute ids.
+ *
+ * MP_EGO_DRAW: element i of `dst` is the view of row rows[i] (NULL: row i) of `bank` (device
+ *   uint8 [bank_rows][S], 16-byte aligned); a NULL bank means the engine's own worlds as they are
+ *   now (rows[] are then world indices, bank_rows is ignored, the engine must have been reset).
+ *   players == NULL: dst is int32 [count][P][VH][VW][L], every viewer of each row; otherwise
+ *   players is device int32 [count] and dst is [count][VH][VW][L], the view of player players[i]
+ *   of row rows[i].  Rows and (row, player) pairs may repeat and `count` has no relation to the
+ *   engine's N.  `dst` is 4-byte aligned.  Stream-ordered, no synchronisation, no allocation;
+ *   nothing of the engine's is written.  `fingerprint`: the rows' (with a NULL bank: the engine's).
+ *   A rows[i] that is no row (no world) or a players[i] outside [0, P) is never used as an index:
+ *   element i of dst is left as it was — every such element — and the next synchronising call
+ *   returns MP_ERR_INVALID once, naming MpEgoLayer, rows[i] or players[i] and the value (of several
+ *   such indices one is reported); the engine stays usable.
+ * MP_EGO_REGISTER: `dst` names a device int32 [N][P][VH][VW][L] (slots == 0), or a ring: slot s
+ *   is at dst + s * slot_stride bytes, and `slots` must equal the engine's ring slots
+ *   (mp_bind_output_ring).  While registered, every submission (reset, step, step_fields, every
+ *   K-step request, a load) is followed on the same stream by ONE launch that redraws all N
+ *   worlds from their records into dst, or into the ring slot that submission wrote.  The value
+ *   is a function of the record, so a masked, stopped or listed call needs no special case: a
+ *   world that did not run is redrawn to the bytes it had.  dst_bytes covers the tensor (the last
+ *   slot's end for a ring); the pointer is validated like a bound buffer.  mp_tune's probe
+ *   submissions do not write it.  A NULL dst clears the registration: the engine's launches are
+ *   then what they were.  An engine without a registration issues the launches it issued before.
+ * MP_EGO_HOST (eng == NULL; pack, pack_len, cfg as for mp_create): MP_EGO_DRAW of HOST rows into
+ *   a HOST dst, computed by the library without a device (bank must not be NULL).  A bad index
+ *   returns MP_ERR_INVALID at once, naming it; the elements before it are written.
+ *
+ * Refused before any launch, the engine left as it was — MP_ERR_INVALID: a wrong struct_size or
+ * op; an engine with MP_EGO_HOST, none with the others; MP_EGO_HOST without a pack; NULL dst (draw,
+ * host); count < 1, or bank_rows < 1 with a bank; rows == NULL with count above the rows there
+ * are; a fingerprint that is not the engine's (the pack's); dst_bytes short of what is written; a
+ * dst, rows or players that is not 4-byte aligned, a bank that is not 16-byte aligned; memory
+ * that is not the engine's device's or leaves its allocation; a ring whose slots are not the
+ * engine's or whose stride is short of a slot or no multiple of 4; nonzero reserved words.
+ * MP_ERR_UNSUPPORTED: a record whose render planes do not fit one wave's share of the LDS. */
+enum { MP_EGO_DRAW = 1, MP_EGO_REGISTER = 2, MP_EGO_HOST = 3 };
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(MpEgoLayer) */
+  int32_t op;              /* MP_EGO_* */
+  uint64_t fingerprint;    /* in (draw, host): the rows' */
+  const void* bank;        /* uint8 [bank_rows][S]; NULL (draw): the engine's worlds */
+  const int32_t* rows;     /* int32 [count], NULL = rows 0 .. count - 1 */
+  const int32_t* players;  /* int32 [count], NULL = every viewer of each row */
+  void* dst;               /* int32: see the op */
+  uint64_t dst_bytes;
+  int32_t bank_rows;
+  int32_t count;
+  uint64_t slot_stride;    /* MP_EGO_REGISTER with a ring: bytes between two slots */
+  int32_t slots;           /* MP_EGO_REGISTER: 0, or the ring's slots */
+  int32_t reserved;        /* 0 */
+  const void* pack;        /* MP_EGO_HOST */
+  uint64_t pack_len;
+  const MpConfig* cfg;
+  uint64_t reserved2[3];   /* 0 */
+} MpEgoLayer;
+
 /* The layout of a record, told by the library: what the bytes of a saved row are, so that a
  * caller can read and edit world states by field.  Rides mp_snapshot, recognised by its size:
  * `bytes` = sizeof(MpStateLayout), `host_buf` a HOST MpStateLayout with struct_size set to it.
@@ -1446,7 +1525,8 @@ int mp_box_fill(MpEngine* eng, MpObsKind kind, int32_t reps, MpBoxFill* out);
  * world or position + 1, word 10 = the index or row, word 11 = what: 1 a load's src[], 2 a save's
  * world list, 3 an MpStatesObserve's rows[], 4 | rule << 8 a row an MpStatesCheck filter refused,
  * 5 an MpStatesCheck's rows[], 6 an MpStatesHash's rows[] or world list, 7 an MpStatesView's
- * rows[], 8 an MpStatesView's players[] — whose three words belong together); of several such reports
+ * rows[], 8 an MpStatesView's players[], 11 an MpEgoLayer's rows[], 12 an MpEgoLayer's players[]
+ * — whose three words belong together); of several such reports
  * of one launch the three words may belong to different ones.  Words 12-15: the refused row of a checked load once more, claimed by ONE
  * refused world of the launch (word 12 = world + 1, 13 = the row, 14 = the rule, 15 = the offset
  * word), reported first.  Each is reported once by the next synchronising call (MP_ERR_INVALID)

@@ -31,6 +31,7 @@
 #include "state_check.h"
 #include "state_hash.h"
 #include "episode_stats.h"
+#include "ego_layer.h"
 
 // frame.hip
 constexpr int kFaultWords = 64 + 4 * 16 * 64 * 2;   // fault words + the timeline build's log
@@ -176,6 +177,13 @@ struct MpEngine {
   episode_stats::Banks stats{};
   bool has_stats = false, stats_hold = false;
   bool folding() const { return has_stats && !stats_hold; }
+  // The registered EGO_LAYER leaf (an MpEgoLayer request; ego_layer.h): while set, every submission
+  // is followed by one launch that redraws every world's view.  ego_slots > 0: a ring, slot s at
+  // ego_dst + s * ego_stride bytes.  mp_tune's probes do not write it (ring_hold, layer_hold).
+  int32_t* ego_dst = nullptr;
+  uint64_t ego_stride = 0;
+  int ego_slots = 0;
+  bool drawing_ego() const { return ego_dst && !ring_hold && !layer_hold; }
   // The engine's choice (MpConfig.unfused = 0): one launch, always.  (Round 2 drew
   // views under 64 KB a world — the two-player games — in a second launch: a CU
   // then has 64 worlds to step for 2 us of drawing each, and with 4-8 feeders the
@@ -407,6 +415,12 @@ int sync_and_check(MpEngine* e, const char* who) {
                   "%s: MpStatesView: %s[%u] = %d is %s; element %u of the destination was left as it was",
                   who, what == kFaultViewRow ? "rows" : "players", at, (int)index,
                   what == kFaultViewRow ? "not a row of the bank" : "not a player of this engine", at);
+    if (what == kFaultEgoRow || what == kFaultEgoPlayer)
+      return fail(MP_ERR_INVALID,
+                  "%s: MpEgoLayer: %s[%u] = %d is %s; element %u of the destination was left as it was",
+                  who, what == kFaultEgoRow ? "rows" : "players", at, (int)index,
+                  what == kFaultEgoRow ? "not a row of the bank (with no bank: no world of this engine)"
+                                       : "not a player of this engine", at);
     if (what == kFaultListedWorld || what == kFaultListedRepeat)
       return fail(MP_ERR_INVALID,
                   "%s: MpStepListed: worlds[%u] = %d %s; the entry ran nothing and element %u of every per-call "
@@ -519,6 +533,19 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
       if (mode == STEP_MODE_LOAD) { r.sel32 = src; r.sel_rows = bank_rows; }
     }
     launch_episode_stats(e->stats_cols, e->stats, r, false, e->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  if (e->drawing_ego()) {
+    // the EGO_LAYER launch: every world's view, redrawn from the records this submission left
+    ego_layer::Args a = {};
+    a.g = ego_layer::window_of(e->t);
+    a.src = e->d_state; a.src_rows = e->N; a.count = e->N;
+    a.stride = e->t.world_stride; a.grid_pad = e->t.grid_pad;
+    a.dst = e->ego_slots > 0
+                ? (int32_t*)((uint8_t*)e->ego_dst + (uint64_t)(slot % e->ego_slots) * e->ego_stride)
+                : e->ego_dst;
+    a.lut = e->d_layer_lut; a.fault = e->t.fault;
+    ego_layer::launch(a, ego_layer::plan_of(a.g, e->N, e->num_cus), e->stream);
     HIP_TRY(hipGetLastError());
   }
   return MP_OK;
@@ -1064,6 +1091,8 @@ int plan_views(MpEngine* e, const MpDevOptions* dev) {
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the K-step kernels failed: %d", rc);
   if (int rc = prepare_state_view())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the sampled-view kernels failed: %d", rc);
+  if (int rc = ego_layer::prepare())
+    return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the EGO_LAYER kernels failed: %d", rc);
   if (int rc = prepare_step_starts())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the episode-start kernels failed: %d", rc);
   if (int rc = prepare_step_active())
@@ -2512,6 +2541,150 @@ static int episode_stats_request(MpEngine* e, const MpEpisodeStats& r) {
   return MP_OK;
 }
 
+// An MpEgoLayer request (include/mp_engine.h; carried by mp_snapshot; `e` is NULL for the host
+// form): draws EGO_LAYER of bank rows or of the engine's worlds (one launch), registers or clears
+// the leaf (no launch), or applies the function to host rows.  Everything is checked first.
+static int ego_layer_request(MpEngine* e, const MpEgoLayer& r) {
+  static const char kWho[] = "MpEgoLayer";
+  if (r.struct_size != sizeof(MpEgoLayer))
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpEgoLayer));
+  if (r.op != MP_EGO_DRAW && r.op != MP_EGO_REGISTER && r.op != MP_EGO_HOST)
+    return fail(MP_ERR_INVALID, "%s: unknown op %d", kWho, r.op);
+  if (r.op == MP_EGO_HOST ? e != nullptr : e == nullptr)
+    return fail(MP_ERR_INVALID, "%s: %s", kWho, e ? "MP_EGO_HOST takes no engine" : "NULL engine");
+  if (r.reserved != 0 || r.reserved2[0] != 0 || r.reserved2[1] != 0 || r.reserved2[2] != 0)
+    return fail(MP_ERR_INVALID, "%s: the reserved words must be 0", kWho);
+  if (r.op == MP_EGO_HOST && (!r.pack || !r.cfg))
+    return fail(MP_ERR_INVALID, "%s: MP_EGO_HOST needs the pack and its config (NULL pack or cfg)", kWho);
+  if (r.op == MP_EGO_REGISTER && !r.dst) {   // clears the registration: the engine's launches are what they were
+    e->ego_dst = nullptr;
+    e->ego_stride = 0;
+    e->ego_slots = 0;
+    return MP_OK;
+  }
+  if (!r.dst) return fail(MP_ERR_INVALID, "%s: NULL dst", kWho);
+  if ((uintptr_t)r.dst & 3) return fail(MP_ERR_INVALID, "%s: dst %p is not 4-byte aligned", kWho, r.dst);
+  // the tables and the fingerprint: the engine's, or the pack's by the host stage
+  HostStage h;
+  std::vector<int32_t> host_lut;
+  const DevTables* t;
+  uint64_t fingerprint;
+  if (e) {
+    t = &e->t;
+    fingerprint = e->fingerprint;
+  } else {
+    if (int rc = host_stage(r.pack, r.pack_len, r.cfg, &h)) return rc;
+    t = &h.d.t;
+    fingerprint = state_fingerprint(h.pack, h.d.t);
+    // (upload_layer_lut's table, from the pack as the host stage left it)
+    const int32_t* ssprite = table<int32_t>(h.pack.data(), "state_sprite");
+    const int32_t* vmap = table<int32_t>(h.pack.data(), "view_sprite_map");
+    host_lut.assign((size_t)t->P * kLayerLutRow, 0);
+    for (int p = 0; p < t->P; ++p) {
+      const int32_t* remap = vmap + (size_t)p * t->nsprites;
+      int32_t* row = host_lut.data() + (size_t)p * kLayerLutRow;
+      for (int s = 1; s < t->nstates && s < 256; ++s) row[s] = ssprite[s] >= 0 ? 1 + remap[ssprite[s]] : 0;
+      row[256] = 1 + remap[0];
+    }
+  }
+  const ego_layer::Window g = ego_layer::window_of(*t);
+  const uint64_t view = (uint64_t)g.VH * (uint64_t)g.VW * (uint64_t)g.L * 4u, world = view * (uint64_t)g.P;
+  if ((t->grid_pad & 15) || (t->world_stride & 15) || (int64_t)g.L * g.HW > (int64_t)t->grid_pad)
+    return fail(MP_ERR_UNSUPPORTED, "%s: a record of %d bytes with %d bytes of planes is not read in 16-byte lines",
+                kWho, t->world_stride, t->grid_pad);
+  if (r.op == MP_EGO_REGISTER) {
+    const uint64_t N = (uint64_t)e->N, block = N * world;
+    if (r.slots < 0) return fail(MP_ERR_INVALID, "%s: slots %d", kWho, r.slots);
+    if (r.slots > 0 && r.slots != e->ring_slots)
+      return fail(MP_ERR_INVALID, "%s: a ring of %d slots, the engine's ring has %d (mp_bind_output_ring; one "
+                  "position for all of them)", kWho, r.slots, e->ring_slots);
+    if (r.slots > 0 && (r.slot_stride < block || (r.slot_stride & 3)))
+      return fail(MP_ERR_INVALID, "%s: slot_stride %llu: a slot is %llu bytes, and slots lie 4-byte aligned", kWho,
+                  (unsigned long long)r.slot_stride, (unsigned long long)block);
+    const uint64_t need = r.slots > 0 ? (uint64_t)(r.slots - 1) * r.slot_stride + block : block;
+    if (r.dst_bytes < need)
+      return fail(MP_ERR_INVALID, "%s: the leaf of %d worlds%s needs %llu bytes, dst has %llu", kWho, e->N,
+                  r.slots > 0 ? " in every slot" : "", (unsigned long long)need, (unsigned long long)r.dst_bytes);
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = check_device_pointer(e, r.dst, "MpEgoLayer (dst)")) return rc;
+    if (int rc = check_bank(e, r.dst, need, "MpEgoLayer (dst)")) return rc;
+    if (ego_layer::plan_of(g, e->N, e->num_cus).waves < 1)
+      return fail(MP_ERR_UNSUPPORTED, "%s: one wave's render planes need %d B of LDS", kWho,
+                  ego_layer::plan_of(g, e->N, e->num_cus).lds);
+    e->ego_dst = (int32_t*)r.dst;
+    e->ego_stride = r.slots > 0 ? r.slot_stride : 0;
+    e->ego_slots = r.slots;
+    return MP_OK;
+  }
+  const bool live = r.op == MP_EGO_DRAW && !r.bank;
+  if (r.op == MP_EGO_HOST && !r.bank) return fail(MP_ERR_INVALID, "%s: NULL bank", kWho);
+  const int32_t src_rows = live ? e->N : r.bank_rows;
+  if (r.count < 1 || src_rows < 1)
+    return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", kWho, r.count, src_rows);
+  if (!r.rows && r.count > src_rows)
+    return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are drawn (count %d, there are %d "
+                "rows)", kWho, r.count, src_rows);
+  if (r.fingerprint != fingerprint)
+    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this %s (%016llx): they were "
+                "saved by an engine of another pack, player count or record layout", kWho,
+                (unsigned long long)r.fingerprint, e ? "engine's" : "pack's", (unsigned long long)fingerprint);
+  const uint64_t count = (uint64_t)r.count, need = count * (r.players ? view : world);
+  if (r.dst_bytes < need)
+    return fail(MP_ERR_INVALID, "%s: %d elements of %llu bytes need %llu bytes, dst has %llu", kWho, r.count,
+                (unsigned long long)(r.players ? view : world), (unsigned long long)need,
+                (unsigned long long)r.dst_bytes);
+  if (((uintptr_t)r.rows & 3) || ((uintptr_t)r.players & 3))
+    return fail(MP_ERR_INVALID, "%s: rows %p and players %p must be 4-byte aligned", kWho, (const void*)r.rows,
+                (const void*)r.players);
+  ego_layer::Args a = {};
+  a.g = g;
+  a.rows = r.rows; a.players = r.players; a.dst = (int32_t*)r.dst;
+  a.src_rows = src_rows; a.count = r.count;
+  a.stride = t->world_stride; a.grid_pad = t->grid_pad;
+  if (r.op == MP_EGO_HOST) {
+    a.src = (const uint8_t*)r.bank;
+    a.lut = host_lut.data();
+    uint32_t what = 0;
+    const int bad = ego_layer::host(a, &what);
+    if (bad >= 0)
+      return fail(MP_ERR_INVALID, "%s: %s[%d] = %d is %s; the elements from %d on were left as they were", kWho,
+                  what == kFaultEgoRow ? "rows" : "players", bad,
+                  what == kFaultEgoRow ? (r.rows ? r.rows[bad] : bad) : r.players[bad],
+                  what == kFaultEgoRow ? "not a row of the bank" : "not a player of this pack", bad);
+    return MP_OK;
+  }
+  if (live && !e->has_state)
+    return fail(MP_ERR_INVALID, "%s: the engine has never been reset; there is no state to draw", kWho);
+  if (!live && ((uintptr_t)r.bank & 15))   // (records are read in 16-byte lines)
+    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", kWho, r.bank);
+  HIP_TRY(hipSetDevice(e->device));
+  if (!live)
+    if (int rc = check_bank(e, r.bank, (uint64_t)r.bank_rows * (uint64_t)t->world_stride, "MpEgoLayer (bank)"))
+      return rc;
+  if (r.rows)
+    if (int rc = check_bank(e, r.rows, count * 4, "MpEgoLayer (rows)")) return rc;
+  if (r.players)
+    if (int rc = check_bank(e, r.players, count * 4, "MpEgoLayer (players)")) return rc;
+  if (int rc = check_bank(e, r.dst, need, "MpEgoLayer (dst)")) return rc;
+  const ego_layer::Plan p = ego_layer::plan_of(g, r.count, e->num_cus);
+  if (p.waves < 1)
+    return fail(MP_ERR_UNSUPPORTED, "%s: one wave's render planes need %d B of LDS", kWho, p.lds);
+  a.src = live ? e->d_state : (const uint8_t*)r.bank;
+  a.lut = e->d_layer_lut; a.fault = e->t.fault;
+  ego_layer::launch(a, p, e->stream);
+  HIP_TRY(hipGetLastError());
+  return MP_OK;
+}
+
+static_assert(sizeof(MpEgoLayer) == 128 && sizeof(MpEgoLayer) != sizeof(MpStepMany) &&
+                  sizeof(MpEgoLayer) != sizeof(MpStateLayout) && sizeof(MpEgoLayer) != sizeof(MpStepUntil) &&
+                  sizeof(MpEgoLayer) != sizeof(MpStatesHash) && sizeof(MpEgoLayer) != sizeof(MpStepActive) &&
+                  sizeof(MpEgoLayer) != sizeof(MpStepListed) && sizeof(MpEgoLayer) != sizeof(MpEpisodeStats) &&
+                  sizeof(MpEgoLayer) != sizeof(MpStatesCheck) && sizeof(MpEgoLayer) != sizeof(MpStatesView) &&
+                  sizeof(MpEgoLayer) != sizeof(MpEpisodeStarts) && sizeof(MpEgoLayer) != sizeof(MpStatesObserve) &&
+                  sizeof(MpEgoLayer) != sizeof(MpWorldStates) && sizeof(MpEgoLayer) != sizeof(MpKernelVariant) &&
+                  sizeof(MpEgoLayer) != sizeof(MpStepTrajectory) && sizeof(MpEgoLayer) < 448,
+              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
 static_assert(sizeof(MpEpisodeStats) == 224 && sizeof(MpEventColumn) == 32 && sizeof(MpStatsBank) == 32 &&
                   sizeof(MpEpisodeStats) != sizeof(MpStepListed) && sizeof(MpEpisodeStats) != sizeof(MpStepUntil) &&
                   sizeof(MpEpisodeStats) != sizeof(MpStepActive) && sizeof(MpEpisodeStats) != sizeof(MpStateLayout) &&
@@ -2612,6 +2785,11 @@ int mp_snapshot(MpEngine* e, void* buf, uint64_t bytes) {
     MpStatesView r;   // (read only: nothing is written back)
     memcpy(&r, buf, sizeof r);
     return states_view(e, r);
+  }
+  if (buf && bytes == sizeof(MpEgoLayer)) {
+    MpEgoLayer r;   // (read only: nothing is written back)
+    memcpy(&r, buf, sizeof r);
+    return ego_layer_request(e, r);
   }
   if (buf && bytes == sizeof(MpStateLayout)) return state_layout(e, (MpStateLayout*)buf);
   if (buf && bytes == sizeof(MpStatesCheck)) {

@@ -274,6 +274,30 @@ def states_view_request(L, handle, **fields) -> MpStatesView:
   return req
 
 
+# EGO_LAYER, the layer view in the avatar's own frame (include/mp_engine.h: MpEgoLayer), carried by
+# mp_snapshot
+MP_EGO_DRAW, MP_EGO_REGISTER, MP_EGO_HOST = 1, 2, 3
+OBS_EGO_LAYER = -1   # no MpObsKind: the Python layers' handle for the leaf where leaves map to kinds
+
+
+class MpEgoLayer(ctypes.Structure):
+  _fields_ = [("struct_size", ctypes.c_uint32), ("op", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
+              ("bank", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("players", ctypes.c_void_p),
+              ("dst", ctypes.c_void_p), ("dst_bytes", ctypes.c_uint64), ("bank_rows", ctypes.c_int32),
+              ("count", ctypes.c_int32), ("slot_stride", ctypes.c_uint64), ("slots", ctypes.c_int32),
+              ("reserved", ctypes.c_int32), ("pack", ctypes.c_void_p), ("pack_len", ctypes.c_uint64),
+              ("cfg", ctypes.c_void_p), ("reserved2", ctypes.c_uint64 * 3)]
+
+
+def ego_layer_request(L, handle, op: int, **fields) -> MpEgoLayer:
+  """Runs one MpEgoLayer request on engine `handle` (None: the host form); raises like every call."""
+  req = MpEgoLayer(ctypes.sizeof(MpEgoLayer), int(op))
+  for k, v in fields.items():
+    setattr(req, k, v)
+  _check(L, L.mp_snapshot(handle, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpEgoLayer)")
+  return req
+
+
 # The layout of a record and the check of edited records (include/mp_engine.h: MpStateLayout,
 # MpStatesCheck), carried by mp_snapshot
 class MpStateField(ctypes.Structure):
@@ -451,6 +475,42 @@ def check_states_host(pack_bytes: bytes, rows, *, fingerprint: Optional[int] = N
   req.rows = None if idx is None else idx.ctypes.data
   req.out, req.out_bytes = out.ctypes.data, out.nbytes
   _check(L, L.mp_snapshot(None, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpStatesCheck)")
+  return out
+
+
+def ego_layer_host(pack_bytes: bytes, rows, players=None, *, which=None, fingerprint: Optional[int] = None,
+                   num_players: int = 0, dev: Optional[Dict[str, int]] = None) -> np.ndarray:
+  """EGO_LAYER of host rows (uint8 [M, S] array) by the library's host-only form (MP_EGO_HOST: the
+  kernels' own value function compiled for the host; no GPU needed).  `which`: the rows to draw, in
+  order, repeats allowed (default: all).  `players` None: int32 [R, P, VH, VW, L], every viewer of
+  each row; else R ints, and the result is int32 [R, VH, VW, L], the view of player players[i] of
+  the i-th drawn row.  `fingerprint`: the rows' (default: the pack's)."""
+  L = load_library()
+  bank = np.ascontiguousarray(rows, np.uint8)
+  if bank.ndim != 2 or bank.shape[0] < 1:
+    raise ValueError("ego_layer_host: rows must be a uint8 array [M, S]")
+  keep = _host_config(pack_bytes, num_players, dev)
+  layout = _layout_request(L, None, pack_bytes, num_players, dev)
+  if bank.shape[1] != layout.world_stride:
+    raise ValueError(f"ego_layer_host: rows of {bank.shape[1]} bytes, the pack's are {layout.world_stride}")
+  idx = None if which is None else np.ascontiguousarray(np.asarray(which).reshape(-1), np.int32)
+  ply = None if players is None else np.ascontiguousarray(np.asarray(players).reshape(-1), np.int32)
+  count = int(ply.size) if ply is not None else bank.shape[0] if idx is None else int(idx.size)
+  if count < 1:
+    raise ValueError("ego_layer_host: no rows to draw")
+  if idx is not None and int(idx.size) != count:
+    raise ValueError(f"ego_layer_host: which has {int(idx.size)} entries, players {count}")
+  from meltingpot_amd import lower, pack as pack_lib
+  hdr = pack_lib.loads(pack_bytes)["hdr"]
+  view = (int(hdr[lower.HDR_VF]) + int(hdr[lower.HDR_VB]) + 1, int(hdr[lower.HDR_VL]) + int(hdr[lower.HDR_VR]) + 1,
+          int(hdr[lower.HDR_L]))
+  out = np.zeros((count,) + ((layout.P,) if ply is None else ()) + view, np.int32)
+  ego_layer_request(L, None, MP_EGO_HOST, fingerprint=layout.fingerprint if fingerprint is None else int(fingerprint),
+                    pack=ctypes.addressof(keep[0]), pack_len=len(pack_bytes),
+                    cfg=ctypes.cast(ctypes.pointer(keep[1]), ctypes.c_void_p), bank=bank.ctypes.data,
+                    bank_rows=int(bank.shape[0]), rows=None if idx is None else idx.ctypes.data,
+                    players=None if ply is None else ply.ctypes.data, count=count, dst=out.ctypes.data,
+                    dst_bytes=out.nbytes)
   return out
 
 
@@ -2397,6 +2457,98 @@ class Engine:
                         dst_bytes=out.numel() * out.element_size())
     self._state_args = (bank, r, p, out)   # (kept until the next call: the launch may not have run yet)
     return out
+
+  @property
+  def ego_layer_shape(self):
+    """The shape of the EGO_LAYER leaf, [N, P, VH, VW, L] (OBS_LAYER's; int32)."""
+    return tuple(int(d) for d in self.shapes[OBS_LAYER][0])
+
+  def observe_ego_layer(self, bank=None, rows=None, players=None, fingerprint: Optional[int] = None, out=None):
+    """EGO_LAYER — the layer view in the avatar's own frame, cell for cell what "RGB" shows — of
+    rows of `bank` (a contiguous uint8 device tensor [M, S], as observe_states' bank), or of the
+    engine's worlds as they are now (`bank` None; `rows` are then world indices).  `rows`: the
+    rows to draw, in order, repeats allowed (None: rows 0 .. count - 1; all of them without
+    `players`).  `players` None: int32 [R, P, VH, VW, L]; else R ints, and the result is int32
+    [R, VH, VW, L], the view of player players[i] of row rows[i].  The ids are OBS_LAYER's, with
+    no facing encoded; for a viewer that faces north the view equals OBS_LAYER's.  Nothing of the
+    engine's is written and no device memory of the engine's is allocated.  A row or player index
+    out of range leaves its element as it was; the next synchronising call raises ValueError.
+    `fingerprint`: the rows' (default: this engine's).  Enqueued on the current stream."""
+    t = self._torch
+    S = int(self.info.world_state_bytes)
+    if bank is not None:
+      if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
+          bank.shape[1] != S or not bank.is_contiguous()):
+        raise ValueError(f"observe_ego_layer: bank must be a contiguous uint8 tensor [M, {S}]")
+      if bank.shape[0] < 1:
+        raise ValueError("observe_ego_layer: the bank has no rows")
+    there = self.N if bank is None else int(bank.shape[0])
+    p = None if players is None else self._device_ints(players, "players")
+    r = None if rows is None else self._device_ints(rows, "rows")
+    count = int(p.numel()) if p is not None else int(r.numel()) if r is not None else there
+    if count < 1:
+      raise ValueError("observe_ego_layer: no views to draw")
+    if r is not None and int(r.numel()) != count:
+      raise ValueError(f"observe_ego_layer: rows has {int(r.numel())} entries, players {count}")
+    shape = self.ego_layer_shape
+    shape = (count,) + (shape[1:] if p is None else shape[2:])
+    if out is None:
+      out = t.empty(shape, dtype=t.int32, device=self.device)
+    elif (not isinstance(out, t.Tensor) or out.dtype != t.int32 or tuple(out.shape) != shape or
+          not out.is_contiguous() or out.device != self.device):
+      raise ValueError(f"observe_ego_layer: out must be a contiguous int32 tensor of shape {shape} on {self.device}")
+    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    self.use_current_stream()
+    ego_layer_request(self._L, self._h, MP_EGO_DRAW, fingerprint=fp,
+                      bank=None if bank is None else bank.data_ptr(), bank_rows=0 if bank is None else there,
+                      rows=None if r is None else r.data_ptr(), players=None if p is None else p.data_ptr(),
+                      count=count, dst=out.data_ptr(), dst_bytes=out.numel() * out.element_size())
+    self._state_args = (bank, r, p, out)   # (kept until the next call: the launch may not have run yet)
+    return out
+
+  def bind_ego_layer(self, out):
+    """Registers `out`, a contiguous int32 device tensor of `ego_layer_shape`, as the EGO_LAYER
+    leaf: from now on every submission (reset, step, step_many in every form, a load) is followed
+    on the same stream by one launch that redraws every world's view into it.  None clears the
+    registration; the engine's launches are then what they were.  Returns `out`."""
+    t = self._torch
+    if out is None:
+      ego_layer_request(self._L, self._h, MP_EGO_REGISTER)
+      self._ego_layer = None
+      return None
+    shape = self.ego_layer_shape
+    if (not isinstance(out, t.Tensor) or out.dtype != t.int32 or tuple(out.shape) != shape or
+        not out.is_contiguous() or out.device != self.device):
+      raise ValueError(f"bind_ego_layer: out must be a contiguous int32 tensor of shape {shape} on {self.device}")
+    ego_layer_request(self._L, self._h, MP_EGO_REGISTER, dst=out.data_ptr(),
+                      dst_bytes=out.numel() * out.element_size())
+    self._ego_layer = out
+    return out
+
+  def bind_ego_layer_ring(self, tensor=None, slots: Optional[int] = None):
+    """The EGO_LAYER leaf as a rollout ring: `tensor` int32 [T, *ego_layer_shape] (allocated when
+    None, `slots` = T), T the engine's ring slots (`bind_ring` some kind first): the launch behind
+    a submission writes the slot that submission wrote.  Returns the tensor."""
+    t = self._torch
+    shape = self.ego_layer_shape
+    if tensor is None:
+      if not slots or slots < 1:
+        raise ValueError("bind_ego_layer_ring needs a tensor or a positive number of slots")
+      tensor = t.empty((int(slots),) + shape, dtype=t.int32, device=self.device)
+    if (not isinstance(tensor, t.Tensor) or tuple(tensor.shape[1:]) != shape or tensor.dtype != t.int32 or
+        tensor.dim() != len(shape) + 1):
+      raise ValueError(f"an EGO_LAYER ring is int32 [T, {', '.join(map(str, shape))}]")
+    if slots is not None and int(slots) != tensor.shape[0]:
+      raise ValueError(f"{tensor.shape[0]} slots in the tensor, {slots} asked for")
+    if not tensor[0].is_contiguous() or tensor.device != self.device:
+      raise ValueError("the slots of a ring must be contiguous and on the engine's device")
+    block = int(np.prod(shape)) * 4
+    stride = tensor.stride(0) * 4 if tensor.shape[0] > 1 else block
+    T = int(tensor.shape[0])
+    ego_layer_request(self._L, self._h, MP_EGO_REGISTER, dst=tensor.data_ptr(),
+                      dst_bytes=(T - 1) * stride + block, slot_stride=stride, slots=T)
+    self._ego_layer = tensor
+    return tensor
 
   def counters(self) -> Dict[str, int]:
     out = np.zeros(len(COUNTER_NAMES), np.uint64)

@@ -981,6 +981,12 @@ class Substrate:
                        "one-world form already returns fresh numpy arrays every step")
     if _leaves is not None and not self._batched:
       raise ValueError("caller-provided leaves need a batched substrate")
+    # "EGO_LAYER": a leaf behind a registration of its own (MpEgoLayer), not an engine kind
+    ego = "EGO_LAYER" in config.individual_observation_names
+    if ego and not self._batched:
+      raise ValueError("\"EGO_LAYER\" needs a batched substrate (device tensors): build it with "
+                       "num_worlds > 1; the one-world form returns numpy arrays and refuses it as it "
+                       "refuses a rollout ring")
     self._submissions = 0
     self._check_device_actions = bool(check_device_actions)
     if not self._roles:
@@ -1025,11 +1031,11 @@ class Substrate:
                           "NUM_OTHERS_WHO_ATE_THIS_STEP": E.OBS_AUX4})
     names = (list(config.individual_observation_names) +
              list(config.global_observation_names) + ["COLLECTIVE_REWARD"])
-    unknown = [n for n in names if n not in self._kinds]
+    unknown = [n for n in names if n not in self._kinds and not (ego and n == "EGO_LAYER")]
     if unknown:
       raise ValueError(f"observations {unknown} are not produced by the engine for "
-                       f"{config.name!r} (it offers {sorted(self._kinds)})")
-    kinds = {n: self._kinds[n] for n in names}
+                       f"{config.name!r} (it offers {sorted(self._kinds) + ['EGO_LAYER']})")
+    kinds = {n: self._kinds[n] for n in names if n in self._kinds}
     kinds.update({"#reward": E.OBS_REWARD, "#discount": E.OBS_DISCOUNT,
                   "#step_type": E.OBS_STEP_TYPE})
     # (None: the engine allocates the leaf itself)
@@ -1058,6 +1064,18 @@ class Substrate:
           layout[n][3]).view(layout[n][2])
       bound = {n: self._eng.bind(kinds[n], view(self._blob, n)) for n in kinds}
       self._host_views = {n: view(self._host, n).numpy() for n in kinds}
+    if ego:
+      # the layer view in the avatar's own frame: redrawn behind every submission by a launch of
+      # its own, into this tensor or into the ring slot the submission wrote
+      t = self._eng._torch
+      shape = self._eng.ego_layer_shape
+      given = None if _leaves is None else _leaves("EGO_LAYER", shape, t.int32, self._eng.device)
+      if self._T:
+        bound["EGO_LAYER"] = self._eng.bind_ego_layer_ring(given, slots=self._T)
+      else:
+        bound["EGO_LAYER"] = self._eng.bind_ego_layer(
+            given if given is not None else t.zeros(shape, dtype=t.int32, device=self._eng.device))
+    self._ego = ego
     self._obs = {n: bound[n] for n in names}
     self._reward = bound["#reward"]
     self._discount = bound["#discount"]
@@ -1290,8 +1308,11 @@ class Substrate:
     """The leaves `observe_states` can draw from saved states, with their engine kinds: "RGB"
     (at this substrate's rgb_pool), "WORLD.RGB" (at its world_rgb_pool), "LAYER",
     "READY_TO_SHOOT", "POSITION", "ORIENTATION" and, where the level has one, "INVENTORY"."""
-    return {n: self._kinds[n] for n in self._STATE_LEAVES
-            if n != "INVENTORY" or int(self._eng.info.num_resources) > 0}
+    leaves = {n: self._kinds[n] for n in self._STATE_LEAVES
+              if n != "INVENTORY" or int(self._eng.info.num_resources) > 0}
+    if getattr(self, "_ego", False):   # (a substrate built with the leaf also draws it from saved states)
+      leaves["EGO_LAYER"] = engine_lib.OBS_EGO_LAYER
+    return leaves
 
   def _state_leaves(self, observations) -> Dict[str, int]:
     """`observations` of an observe_states call as name -> kind (None: those among this
@@ -1334,13 +1355,38 @@ class Substrate:
       raise ValueError("observe_states takes the WorldStates of save_state or step_many(states=True)")
     states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
     self._eng.use_current_stream()
+    ego = leaves.pop("EGO_LAYER", None) is not None
     if players is None:
-      return {n: self._eng.observe_states(states.data, k, rows=rows, fingerprint=states.fingerprint)
-              for n, k in leaves.items()}
+      out = {n: self._eng.observe_states(states.data, k, rows=rows, fingerprint=states.fingerprint)
+             for n, k in leaves.items()}
+      if ego:
+        out["EGO_LAYER"] = self._eng.observe_ego_layer(states.data, rows=rows, fingerprint=states.fingerprint)
+      return out
     p = self._eng._device_ints(players, "players")
     r = None if rows is None else self._eng._device_ints(rows, "rows")
-    return {n: self._eng.observe_views(states.data, k, p, rows=r, fingerprint=states.fingerprint)
-            for n, k in leaves.items() if n != "WORLD.RGB"}
+    out = {n: self._eng.observe_views(states.data, k, p, rows=r, fingerprint=states.fingerprint)
+           for n, k in leaves.items() if n != "WORLD.RGB"}
+    if ego:
+      out["EGO_LAYER"] = self._eng.observe_ego_layer(states.data, rows=r, players=p, fingerprint=states.fingerprint)
+    return out
+
+  def observe_ego_layer(self, states: Optional[WorldStates] = None, rows=None, players=None):
+    """"EGO_LAYER" — the layer view in the avatar's own frame: cell (i, j) names the sprites under
+    cell (i, j) of "RGB", where "LAYER" (the reference's "N.LAYER") keeps north up whichever way
+    the avatar faces — of saved states, or of this substrate's worlds as they are now (`states`
+    None; `rows` are then world indices).  int32 [R, P, VH, VW, L], or [R, VH, VW, L] with
+    `players` (R ints: the view of player players[i] of row rows[i]).  The ids are "LAYER"'s: no
+    facing is encoded, so avatar q's facing in viewer p's frame is (ORIENTATION[q] -
+    ORIENTATION[p]) & 3, and oriented beams and kitchen inventories keep their absolute ids.  Any
+    batched substrate draws it, with or without the leaf.  Ordered on the current stream; no host
+    synchronisation."""
+    self._eng.use_current_stream()
+    if states is None:
+      return self._eng.observe_ego_layer(None, rows=rows, players=players)
+    if not isinstance(states, WorldStates):
+      raise ValueError("observe_ego_layer takes the WorldStates of save_state or step_many(states=True)")
+    states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
+    return self._eng.observe_ego_layer(states.data, rows=rows, players=players, fingerprint=states.fingerprint)
 
   # dmlab2d properties (wrappers/base.py:64-84): Melting Pot's levels register none —
   # the calls exist and answer like dmlab2d does for an unknown key
@@ -1426,7 +1472,8 @@ class Substrate:
   def step_leaves(self) -> Dict[str, int]:
     """The leaves `step_many(observations=...)` can stack per step: this substrate's own
     observation names other than the pixel ones, with their engine kinds."""
-    return {n: self._kinds[n] for n in self._obs if self._kinds[n] not in engine_lib.PIXEL_KINDS}
+    return {n: self._kinds[n] for n in self._obs
+            if n in self._kinds and self._kinds[n] not in engine_lib.PIXEL_KINDS}
 
   def _many_leaves(self, observations) -> Dict[str, int]:
     """`observations` of a step_many call as name -> kind (True: every leaf of `step_leaves`)."""
@@ -1439,6 +1486,10 @@ class Substrate:
       observations = (observations,)
     leaves = {}
     for n in observations:
+      if n == "EGO_LAYER":
+        raise ValueError("step_many: \"EGO_LAYER\" has no per-step rows (it is drawn by a launch behind the "
+                         "submission, from the final records): call step_many(states=True) and draw "
+                         "observe_states(result.states, (\"EGO_LAYER\",)) or observe_ego_layer(result.states)")
       if n not in offered:
         what = ("a pixel leaf: step_many draws no intermediate frames (step with rollout_length=T does)"
                 if n in self._obs else "no leaf of this substrate")
@@ -1669,6 +1720,11 @@ def layer_spec(pack_bytes: bytes) -> Array:
                np.int32, "LAYER")
 
 
+def ego_layer_spec(pack_bytes: bytes) -> Array:
+  """"EGO_LAYER" of a pack: "LAYER"'s shape and dtype, the window turned with the avatar."""
+  return Array(layer_spec(pack_bytes).shape, np.int32, "EGO_LAYER")
+
+
 def observation_spec_of(config: SubstrateConfig, pack_bytes: bytes, rgb_pool: int = 1,
                         world_rgb_pool: int = 1) -> Dict[str, Array]:
   """One player's observation spec of a `Substrate` built from `config` and `pack_bytes` with
@@ -1684,6 +1740,8 @@ def observation_spec_of(config: SubstrateConfig, pack_bytes: bytes, rgb_pool: in
     spec["WORLD.RGB"] = Array((h // k, w // k, c), spec["WORLD.RGB"].dtype, "WORLD.RGB")
   if "LAYER" in config.individual_observation_names:
     spec["LAYER"] = layer_spec(pack_bytes)
+  if "EGO_LAYER" in config.individual_observation_names:
+    spec["EGO_LAYER"] = ego_layer_spec(pack_bytes)
   return spec
 
 
@@ -1702,6 +1760,8 @@ def select_observations(config: SubstrateConfig, pack_bytes: bytes,
       spec[n] = _EXTRA_SPECS[n]
   if "LAYER" in individual:
     spec["LAYER"] = layer_spec(pack_bytes)
+  if "EGO_LAYER" in individual:
+    spec["EGO_LAYER"] = ego_layer_spec(pack_bytes)
   wanted = set(individual) | set(global_observations)
   return individual, list(global_observations), {n: sp for n, sp in spec.items() if n in wanted}
 
@@ -1835,7 +1895,7 @@ def check_config_against_pack(config: SubstrateConfig, pack_bytes: bytes, num_pl
   want = {"RGB": ((int(hdr[lower.HDR_VF]) + int(hdr[lower.HDR_VB]) + 1) * S,
                   (int(hdr[lower.HDR_VL]) + int(hdr[lower.HDR_VR]) + 1) * S, 3),
           "WORLD.RGB": (int(hdr[lower.HDR_H]) * S, int(hdr[lower.HDR_W]) * S, 3),
-          "LAYER": layer_spec(pack_bytes).shape}
+          "LAYER": layer_spec(pack_bytes).shape, "EGO_LAYER": layer_spec(pack_bytes).shape}
   for n, shape in want.items():
     if n in config.timestep_spec and tuple(config.timestep_spec[n].shape) != shape:
       raise ValueError(
@@ -2154,6 +2214,21 @@ class MixtureSubstrate:
     for m, states, off, n in zip(self._members, states_per_member, self._offsets, self._counts):
       m.set_episode_starts(states, None if states is None else rows[off:off + n], fresh=fresh, check=check)
     return rows
+
+  def observe_ego_layer(self):
+    """`Substrate.observe_ego_layer()` of the worlds as they are now: ONE int32 [N, P, VH, VW, L]
+    device tensor of which every member draws its slice (saved states are a member's own: draw
+    them with that member's fingerprint)."""
+    eng = self._members[0]._eng
+    t = eng._torch
+    out = t.empty((self._N,) + tuple(eng.ego_layer_shape[1:]), dtype=t.int32, device=eng.device)
+    for m, off, n in zip(self._members, self._offsets, self._counts):
+      if tuple(m._eng.ego_layer_shape[1:]) != tuple(out.shape[1:]):
+        raise ValueError(f"observe_ego_layer: one member's view is {tuple(out.shape[1:])}, another's "
+                         f"{tuple(m._eng.ego_layer_shape[1:])}")
+      m._eng.use_current_stream()
+      m._eng.observe_ego_layer(None, out=out[off:off + n])
+    return out
 
   def event_columns(self):
     return self._members[0].event_columns()
