@@ -884,6 +884,90 @@ typedef struct {
   uint64_t reserved;       /* 0 */
 } MpStatesHash;
 
+/* Do two PLAYERS see the same thing?  MpStatesHash says whether two worlds are one state; it hashes
+ * absolute map bytes, so it is neither egocentric nor limited to a viewer's window.  MpViewHash is
+ * the hash of what one player observes — its EGO_LAYER (MpEgoLayer) — worked out on the device
+ * from the record, without drawing the view: 8 bytes a viewer.  Per-agent novelty counts
+ * (torch.unique(h, return_counts=True)), information-set keys of the acting player, dropping
+ * duplicate (step, world, player) views from a replay buffer, "did my view change?" for frame
+ * skip.  Rides mp_snapshot, recognised by its size: `bytes` = sizeof(MpViewHash), `host_buf` a
+ * HOST MpViewHash with struct_size set to it.  include/mp_view_hash.h wraps it as inline C
+ * functions.
+ *
+ * The function.  For a record (a bank row or a live world) and a viewer p let E be the viewer's
+ * EGO_LAYER, int32 [VH][VW][L], exactly as MpEgoLayer defines it (a dead or off-grid viewer: every
+ * word OutOfBounds), and e = (vy * VW + vx) * L + l.  With fmix64 the one MpStatesHash spells out:
+ *   v_e = classes ? classes[E_e] : E_e,
+ *   c_e = fmix64((u64)(e + 1) << 32 | (u32)v_e)   for every e whose layer l is included,
+ *   V   = fmix64(sum_e c_e mod 2^64).
+ * Layer l is included iff bit l of layer_mask is set; layer_mask == 0 means every layer.  Words
+ * that are 0 are included like any other.  `classes` is an optional int32 table with one entry
+ * per possible id, 0 .. the largest id the viewers' value tables hold: classes_len must equal
+ * num_ids, which every request that gets as far as the tables writes back into the caller's
+ * struct (count == 0 with a NULL dst, MP_VIEWHASH_DRAW or MP_VIEWHASH_HOST, asks for nothing
+ * else).  fmix64 is a bijection, so the properties of the state hash hold:
+ *   - changing one included word always changes V;
+ *   - changing an excluded layer, or a cell outside the viewer's window, never changes V;
+ *   - with `classes`, two ids of one class are indistinguishable by construction.
+ * Hashes compare only within one fingerprint and one (layer_mask, classes) choice.
+ *
+ * MP_VIEWHASH_DRAW: element i of `dst` belongs to row rows[i] (NULL: row i) of `bank` (device
+ *   uint8 [bank_rows][S], 16-byte aligned); a NULL bank means the engine's own worlds as they are
+ *   now (rows[] are then world indices, bank_rows is ignored, the engine must have been reset).
+ *   players == NULL: dst is u64 [count][P], V of every viewer of each row; otherwise players is
+ *   device int32 [count] and dst is u64 [count], V of player players[i] of row rows[i].  Rows and
+ *   (row, player) pairs may repeat and `count` has no relation to the engine's N.  `dst` is
+ *   8-byte aligned; `classes` is a DEVICE int32 [classes_len] or NULL.  Stream-ordered, no
+ *   synchronisation, no allocation; nothing of the engine's is written.  A rows[i] that is no
+ *   row (no world) or a players[i] outside [0, P) is never used as an index: element i of dst is
+ *   left as it was — every such element — and the next synchronising call returns MP_ERR_INVALID
+ *   once, naming MpViewHash, rows[i] or players[i] and the value (of several such indices one is
+ *   reported); the engine stays usable.
+ * MP_VIEWHASH_REGISTER: `dst` names a device u64 [N][P] (slots == 0), or a ring: slot s is at dst
+ *   + s * slot_stride bytes, and `slots` must equal the engine's ring slots (mp_bind_output_ring),
+ *   as MP_EGO_REGISTER.  While registered, every submission (reset, step, step_fields, every
+ *   K-step request, a load) is followed on the same stream by ONE launch that rewrites all N * P
+ *   hashes from the records, into dst or into the ring slot that submission wrote; `classes` (a
+ *   DEVICE table the caller keeps alive and may rewrite between submissions) and layer_mask are
+ *   the registration's.  mp_tune's probe submissions do not write it.  A NULL dst clears the
+ *   registration: the engine's launches are then what they were.  An engine without a
+ *   registration issues exactly the launches it issued before.
+ * MP_VIEWHASH_HOST (eng == NULL; pack, pack_len, cfg as for mp_create): MP_VIEWHASH_DRAW of HOST
+ *   rows into a HOST dst with a HOST `classes`, computed by the library without a device (bank
+ *   must not be NULL).  A bad index returns MP_ERR_INVALID at once, naming it; the elements before
+ *   it are written.
+ *
+ * Refused before any launch, the engine left as it was — MP_ERR_INVALID: what MpEgoLayer refuses
+ * (with 8-byte alignment of dst and of a ring's stride); a layer_mask bit that names no layer;
+ * classes_len != num_ids with a table, != 0 without one; a class table that is not 4-byte aligned
+ * or not the engine's device's.  MP_ERR_UNSUPPORTED: where MpEgoLayer returns it (a record whose
+ * render planes, beside the viewers' value tables, do not fit one wave's share of the LDS); more
+ * than 64 layers. */
+enum { MP_VIEWHASH_DRAW = 1, MP_VIEWHASH_REGISTER = 2, MP_VIEWHASH_HOST = 3 };
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(MpViewHash) */
+  int32_t op;              /* MP_VIEWHASH_* */
+  uint64_t fingerprint;    /* in (draw, host): the rows' */
+  const void* bank;        /* uint8 [bank_rows][S]; NULL (draw): the engine's worlds */
+  const int32_t* rows;     /* int32 [count], NULL = rows 0 .. count - 1 */
+  const int32_t* players;  /* int32 [count], NULL = every viewer of each row */
+  void* dst;               /* u64: see the op */
+  uint64_t dst_bytes;
+  int32_t bank_rows;
+  int32_t count;
+  uint64_t slot_stride;    /* MP_VIEWHASH_REGISTER with a ring: bytes between two slots */
+  int32_t slots;           /* MP_VIEWHASH_REGISTER: 0, or the ring's slots */
+  int32_t classes_len;     /* 0 without classes, else num_ids */
+  const void* pack;        /* MP_VIEWHASH_HOST */
+  uint64_t pack_len;
+  const MpConfig* cfg;
+  uint64_t layer_mask;     /* bit l = layer l; 0 = every layer */
+  const int32_t* classes;  /* int32 [classes_len] or NULL (host form: a HOST table) */
+  int32_t num_ids;         /* out: the length a class table must have */
+  int32_t reserved;        /* 0 */
+  uint64_t reserved2[3];   /* 0 */
+} MpViewHash;
+
 /* Action sequences: K steps of every world in ONE submission, bit-identical to K calls of the
  * single-step entry points (mp_step, or mp_step_fields with fields = 1) with the same actions,
  * which also hands back the transition of every one of the K steps.  For planners that fork a
@@ -1525,7 +1609,8 @@ int mp_box_fill(MpEngine* eng, MpObsKind kind, int32_t reps, MpBoxFill* out);
  * world or position + 1, word 10 = the index or row, word 11 = what: 1 a load's src[], 2 a save's
  * world list, 3 an MpStatesObserve's rows[], 4 | rule << 8 a row an MpStatesCheck filter refused,
  * 5 an MpStatesCheck's rows[], 6 an MpStatesHash's rows[] or world list, 7 an MpStatesView's
- * rows[], 8 an MpStatesView's players[], 11 an MpEgoLayer's rows[], 12 an MpEgoLayer's players[]
+ * rows[], 8 an MpStatesView's players[], 11 an MpEgoLayer's rows[], 12 an MpEgoLayer's players[], 13 an
+ * MpViewHash's rows[], 14 an MpViewHash's players[] (9 and 10 are MpStepListed's worlds[])
  * — whose three words belong together); of several such reports
  * of one launch the three words may belong to different ones.  Words 12-15: the refused row of a checked load once more, claimed by ONE
  * refused world of the launch (word 12 = world + 1, 13 = the row, 14 = the rule, 15 = the offset

@@ -619,6 +619,104 @@ def hash_states_host(pack_bytes: bytes, rows, which=None, planes=None, fields=No
   return out
 
 
+# The hash of each player's view (include/mp_engine.h: MpViewHash), carried by mp_snapshot
+MP_VIEWHASH_DRAW, MP_VIEWHASH_REGISTER, MP_VIEWHASH_HOST = 1, 2, 3
+
+
+class MpViewHash(ctypes.Structure):
+  _fields_ = [("struct_size", ctypes.c_uint32), ("op", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
+              ("bank", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("players", ctypes.c_void_p),
+              ("dst", ctypes.c_void_p), ("dst_bytes", ctypes.c_uint64), ("bank_rows", ctypes.c_int32),
+              ("count", ctypes.c_int32), ("slot_stride", ctypes.c_uint64), ("slots", ctypes.c_int32),
+              ("classes_len", ctypes.c_int32), ("pack", ctypes.c_void_p), ("pack_len", ctypes.c_uint64),
+              ("cfg", ctypes.c_void_p), ("layer_mask", ctypes.c_uint64), ("classes", ctypes.c_void_p),
+              ("num_ids", ctypes.c_int32), ("reserved", ctypes.c_int32), ("reserved2", ctypes.c_uint64 * 3)]
+
+
+def view_hash_request(L, handle, op: int, **fields) -> MpViewHash:
+  """Runs one MpViewHash request on engine `handle` (None: the host form); raises like every call.
+  The returned request's `num_ids` is the length a class table must have."""
+  req = MpViewHash(ctypes.sizeof(MpViewHash), int(op))
+  for k, v in fields.items():
+    setattr(req, k, v)
+  _check(L, L.mp_snapshot(handle, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpViewHash)")
+  return req
+
+
+def view_layer_mask(layers, num_layers: int) -> int:
+  """MpViewHash.layer_mask of `layers`: None (every layer: 0) or an iterable of layer indices.
+  ValueError for an index the view has not, and for an empty choice."""
+  if layers is None:
+    return 0
+  if isinstance(layers, (int, np.integer)) and not isinstance(layers, bool):
+    layers = (layers,)
+  mask = 0
+  for l in layers:
+    if isinstance(l, bool) or not isinstance(l, (int, np.integer)) or not 0 <= int(l) < num_layers:
+      raise ValueError(f"hash_views: {l!r} is no layer of the view (it has {num_layers})")
+    mask |= 1 << int(l)
+  if mask == 0:
+    raise ValueError("hash_views: layers includes no layer (None means every layer)")
+  return mask
+
+
+def _view_classes(classes, num_ids: int) -> np.ndarray:
+  """`classes` as the contiguous int32 [num_ids] host table of an MpViewHash request."""
+  a = np.asarray(classes)
+  if a.ndim != 1 or a.size != num_ids or not np.issubdtype(a.dtype, np.integer):
+    raise ValueError(f"hash_views: classes must be {num_ids} integers, one per layer id (num_layer_ids); got "
+                     f"{a.dtype} {a.shape}")
+  return np.ascontiguousarray(a, np.int32)
+
+
+def num_layer_ids_host(pack_bytes: bytes, *, num_players: int = 0, dev: Optional[Dict[str, int]] = None) -> int:
+  """The number of ids "LAYER" and "EGO_LAYER" can hold for this pack, 1 + the largest: the length of
+  a `classes` table of `hash_views_host` (an MpViewHash question without an engine: no GPU needed)."""
+  keep = _host_config(pack_bytes, num_players, dev)
+  req = view_hash_request(load_library(), None, MP_VIEWHASH_HOST, pack=ctypes.addressof(keep[0]),
+                          pack_len=len(pack_bytes), cfg=ctypes.cast(ctypes.pointer(keep[1]), ctypes.c_void_p))
+  return int(req.num_ids)
+
+
+def hash_views_host(pack_bytes: bytes, rows, players=None, *, which=None, layers=None, classes=None,
+                    fingerprint: Optional[int] = None, num_players: int = 0,
+                    dev: Optional[Dict[str, int]] = None) -> np.ndarray:
+  """The 64-bit hash (the u64's bits, int64) of each player's view of host rows (uint8 [M, S]
+  array) by the library's host-only form (MP_VIEWHASH_HOST: the kernels' own function compiled for
+  the host; no GPU needed).  `which`: the rows to hash, in order, repeats allowed (default: all).
+  `players` None: int64 [R, P], every viewer of each row; else R ints, and the result is int64 [R],
+  the hash of player players[i] of the i-th row.  `layers`: the layer indices that count (None:
+  all); `classes`: int32 [num_layer_ids_host(pack)] mapping every id to its class (None: the ids
+  themselves).  `fingerprint`: the rows' (default: the pack's)."""
+  L = load_library()
+  bank = np.ascontiguousarray(rows, np.uint8)
+  if bank.ndim != 2 or bank.shape[0] < 1:
+    raise ValueError("hash_views_host: rows must be a uint8 array [M, S]")
+  keep = _host_config(pack_bytes, num_players, dev)
+  layout = _layout_request(L, None, pack_bytes, num_players, dev)
+  if bank.shape[1] != layout.world_stride:
+    raise ValueError(f"hash_views_host: rows of {bank.shape[1]} bytes, the pack's are {layout.world_stride}")
+  idx = None if which is None else np.ascontiguousarray(np.asarray(which).reshape(-1), np.int32)
+  ply = None if players is None else np.ascontiguousarray(np.asarray(players).reshape(-1), np.int32)
+  count = int(ply.size) if ply is not None else bank.shape[0] if idx is None else int(idx.size)
+  if count < 1:
+    raise ValueError("hash_views_host: no rows to hash")
+  if idx is not None and int(idx.size) != count:
+    raise ValueError(f"hash_views_host: which has {int(idx.size)} entries, players {count}")
+  cls = None if classes is None else _view_classes(classes, num_layer_ids_host(pack_bytes, num_players=num_players,
+                                                                               dev=dev))
+  out = np.zeros((count,) + ((layout.P,) if ply is None else ()), np.int64)
+  view_hash_request(L, None, MP_VIEWHASH_HOST,
+                    fingerprint=layout.fingerprint if fingerprint is None else int(fingerprint),
+                    pack=ctypes.addressof(keep[0]), pack_len=len(pack_bytes),
+                    cfg=ctypes.cast(ctypes.pointer(keep[1]), ctypes.c_void_p), bank=bank.ctypes.data,
+                    bank_rows=int(bank.shape[0]), rows=None if idx is None else idx.ctypes.data,
+                    players=None if ply is None else ply.ctypes.data, count=count,
+                    layer_mask=view_layer_mask(layers, layout.L), classes=None if cls is None else cls.ctypes.data,
+                    classes_len=0 if cls is None else int(cls.size), dst=out.ctypes.data, dst_bytes=out.nbytes)
+  return out
+
+
 # Action sequences (include/mp_engine.h: MpStepMany), carried by mp_restore
 STEP_MANY_MAX = 4096   # MP_STEP_MANY_MAX
 # the five kinds step_many returns by name, in MpStepMany.per_step's order
@@ -2549,6 +2647,108 @@ class Engine:
                       dst_bytes=(T - 1) * stride + block, slot_stride=stride, slots=T)
     self._ego_layer = tensor
     return tensor
+
+  @property
+  def num_layer_ids(self) -> int:
+    """The number of ids OBS_LAYER and EGO_LAYER can hold, 1 + the largest: the length of a
+    `classes` table of `hash_views`."""
+    if getattr(self, "_num_layer_ids", None) is None:
+      self._num_layer_ids = int(view_hash_request(self._L, self._h, MP_VIEWHASH_DRAW).num_ids)
+    return self._num_layer_ids
+
+  def _view_classes(self, classes):
+    """`classes` of a hash_views call as a contiguous int32 [num_layer_ids] device tensor (a device
+    tensor of that form is taken as it is), or None."""
+    if classes is None:
+      return None
+    t = self._torch
+    if (isinstance(classes, t.Tensor) and classes.dtype == t.int32 and classes.device == self.device and
+        classes.is_contiguous() and tuple(classes.shape) == (self.num_layer_ids,)):
+      return classes
+    host = classes.cpu().numpy() if isinstance(classes, t.Tensor) else classes
+    return t.from_numpy(_view_classes(host, self.num_layer_ids)).to(self.device)
+
+  def hash_views(self, bank=None, rows=None, players=None, layers=None, classes=None, out=None,
+                 fingerprint: Optional[int] = None):
+    """int64 device tensor: the 64-bit hash (the u64's bits) of what each player sees — of its
+    EGO_LAYER, `observe_ego_layer`'s view — in rows of `bank` (a contiguous uint8 device tensor
+    [M, S]), or in the engine's worlds as they are now (`bank` None; `rows` are then world
+    indices), worked out from the records by one launch without drawing a view.  `rows`: the rows
+    to hash, in order, repeats allowed (None: rows 0 .. count - 1; all of them without `players`).
+    `players` None: int64 [R, P]; else R ints, and the result is int64 [R], the hash of player
+    players[i] of row rows[i].  `layers`: the layer indices that count (None: all).  `classes`:
+    `num_layer_ids` ints mapping every id to its class — two ids of one class hash alike — (None:
+    the ids themselves); a contiguous int32 device tensor is read where it lies.  Two views hash
+    alike iff they agree in every included word (up to a 2^-64 collision); a cell outside the
+    window and an excluded layer never count.  `torch.unique(h, return_counts=True)` is the
+    per-agent novelty count.  Nothing of the engine's is written and no device memory of the
+    engine's is allocated.  A row or player index out of range leaves its element as it was; the
+    next synchronising call raises ValueError.  Hashes compare only within one fingerprint and
+    one choice of layers and classes.  Enqueued on the current stream."""
+    t = self._torch
+    S = int(self.info.world_state_bytes)
+    if bank is not None:
+      if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
+          bank.shape[1] != S or not bank.is_contiguous()):
+        raise ValueError(f"hash_views: bank must be a contiguous uint8 tensor [M, {S}]")
+      if bank.shape[0] < 1:
+        raise ValueError("hash_views: the bank has no rows")
+    there = self.N if bank is None else int(bank.shape[0])
+    p = None if players is None else self._device_ints(players, "players")
+    r = None if rows is None else self._device_ints(rows, "rows")
+    count = int(p.numel()) if p is not None else int(r.numel()) if r is not None else there
+    if count < 1:
+      raise ValueError("hash_views: no views to hash")
+    if r is not None and int(r.numel()) != count:
+      raise ValueError(f"hash_views: rows has {int(r.numel())} entries, players {count}")
+    mask = view_layer_mask(layers, int(self.info.num_layers))
+    cls = self._view_classes(classes)
+    shape = (count, self.P) if p is None else (count,)
+    if out is None:
+      out = t.empty(shape, dtype=t.int64, device=self.device)
+    elif (not isinstance(out, t.Tensor) or out.dtype != t.int64 or tuple(out.shape) != shape or
+          not out.is_contiguous() or out.device != self.device):
+      raise ValueError(f"hash_views: out must be a contiguous int64 tensor of shape {shape} on {self.device}")
+    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    self.use_current_stream()
+    view_hash_request(self._L, self._h, MP_VIEWHASH_DRAW, fingerprint=fp,
+                      bank=None if bank is None else bank.data_ptr(), bank_rows=0 if bank is None else there,
+                      rows=None if r is None else r.data_ptr(), players=None if p is None else p.data_ptr(),
+                      count=count, layer_mask=mask, classes=None if cls is None else cls.data_ptr(),
+                      classes_len=0 if cls is None else int(cls.numel()), dst=out.data_ptr(),
+                      dst_bytes=out.numel() * 8)
+    self._view_hash_args = (bank, r, p, cls, out)   # (kept until the next call: the launch may not have run yet)
+    return out
+
+  def bind_view_hash(self, out, layers=None, classes=None):
+    """Registers `out` — a contiguous int64 device tensor [N, P], or [T, N, P] with T the engine's
+    ring slots (`bind_ring` some kind first) — as the view hashes: from now on every submission
+    (reset, step, step_many in every form, a load) is followed on the same stream by one launch
+    that rewrites every viewer's `hash_views` value into it, or into the ring slot the submission
+    wrote.  `layers`, `classes`: as `hash_views` takes them; the engine keeps the class table alive.
+    None clears the registration; the engine's launches are then what they were.  Returns `out`."""
+    t = self._torch
+    if out is None:
+      view_hash_request(self._L, self._h, MP_VIEWHASH_REGISTER)
+      self._view_hash = None
+      return None
+    shape = (self.N, self.P)
+    ring = isinstance(out, t.Tensor) and out.dim() == 3
+    if (not isinstance(out, t.Tensor) or out.dtype != t.int64 or tuple(out.shape[-2:]) != shape or
+        out.dim() not in (2, 3) or not (out[0] if ring else out).is_contiguous() or out.device != self.device):
+      raise ValueError(f"bind_view_hash: out must be an int64 tensor of shape {shape} or [T, {self.N}, {self.P}] "
+                       f"with contiguous slots on {self.device}")
+    mask = view_layer_mask(layers, int(self.info.num_layers))
+    cls = self._view_classes(classes)
+    block = self.N * self.P * 8
+    T = int(out.shape[0]) if ring else 0
+    stride = (out.stride(0) * 8 if T > 1 else block) if ring else 0
+    view_hash_request(self._L, self._h, MP_VIEWHASH_REGISTER, dst=out.data_ptr(),
+                      dst_bytes=(T - 1) * stride + block if ring else block, slot_stride=stride, slots=T,
+                      layer_mask=mask, classes=None if cls is None else cls.data_ptr(),
+                      classes_len=0 if cls is None else int(cls.numel()))
+    self._view_hash = (out, cls)
+    return out
 
   def counters(self) -> Dict[str, int]:
     out = np.zeros(len(COUNTER_NAMES), np.uint64)

@@ -1204,6 +1204,77 @@ class Substrate:
     self._eng.use_current_stream()
     return self._eng.hash_worlds(worlds, planes=planes, fields=_hash_fields(fields))
 
+  def _view_layers(self, layers):
+    """`layers` of a hash_views call as layer indices: names of `state_layout().layer_names` or
+    indices (None: every layer).  Unknown names are a ValueError."""
+    if layers is None:
+      return None
+    if isinstance(layers, (str, int, np.integer)):
+      layers = (layers,)
+    names = list(self.state_layout().layer_names)
+    picked = []
+    for l in layers:
+      if isinstance(l, str):
+        if l not in names:
+          raise ValueError(f"hash_views: {l!r} is no layer of this level (it has {names})")
+        l = names.index(l)
+      picked.append(l)
+    return picked
+
+  def hash_views(self, states: Optional[WorldStates] = None, rows=None, players=None, layers=None, classes=None):
+    """Do two players see the same thing?  int64 [R, P] device tensor (or [R] with `players`, R
+    ints: player players[i] of row rows[i]): a 64-bit hash of what each player observes — its
+    "EGO_LAYER", the layer view in the avatar's own frame — in saved states, or in this
+    substrate's worlds as they are now (`states` None; `rows` are then world indices).  The hash
+    is worked out on the device from the records; no view is drawn.  Equal hashes mean equal views
+    (up to a 2^-64 collision), different hashes always mean different views; what lies outside a
+    player's window never counts, and a dead player's view is all out-of-bounds.
+    `layers`: the layers that count, by name (`state_layout().layer_names`) or index (None: all);
+    `classes`: `num_layer_ids` ints mapping every "LAYER" id to a class, so that ids of one class
+    hash alike (e.g. every avatar colour to one "an avatar").  Per-agent novelty is
+    `torch.unique(h, return_counts=True)`; an information-set key is h[w, acting_player]; "did my
+    view change?" is h != h_before.  Hashes compare only within one fingerprint and one choice of
+    layers and classes.  Nothing of this substrate changes; no host synchronisation."""
+    if not self._batched:
+      raise ValueError("hash_views needs a batched substrate (device tensors): build it with num_worlds > 1")
+    self._eng.use_current_stream()
+    layers = self._view_layers(layers)
+    if states is None:
+      return self._eng.hash_views(None, rows=rows, players=players, layers=layers, classes=classes)
+    if not isinstance(states, WorldStates):
+      raise ValueError("hash_views takes the WorldStates of save_state or step_many(states=True)")
+    states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
+    return self._eng.hash_views(states.data, rows=rows, players=players, layers=layers, classes=classes,
+                                fingerprint=states.fingerprint)
+
+  @property
+  def num_layer_ids(self) -> int:
+    """The number of ids "LAYER" can hold: the length of `hash_views`' `classes`."""
+    return self._eng.num_layer_ids
+
+  def set_view_hashes(self, layers="all", classes=None, out=None):
+    """Keeps `hash_views()` of the worlds current on the device: returns an int64 [N, P] device
+    tensor — [T, N, P] on a substrate built with rollout_length=T — that one launch rewrites behind
+    every reset, step, step_many and load_state, in the ring slot the submission wrote.
+    `layers` ("all": every layer), `classes`: as `hash_views` takes them.  `set_view_hashes(None)`
+    clears the registration, as `set_episode_stats(None)` does: the launches are then what they
+    were.  There are no per-step rows in `step_many`: call step_many(states=True) and
+    hash_views(result.states)."""
+    if not self._batched:
+      raise ValueError("set_view_hashes needs a batched substrate (device tensors): build it with num_worlds > 1")
+    self._eng.use_current_stream()
+    if layers is None:
+      self._eng.bind_view_hash(None)
+      return None
+    layers = None if isinstance(layers, str) and layers == "all" else self._view_layers(layers)
+    t = self._eng._torch
+    shape = ((self._T,) if self._T else ()) + (self._eng.N, self._eng.P)
+    if out is None:
+      out = t.zeros(shape, dtype=t.int64, device=self._eng.device)
+    elif not isinstance(out, t.Tensor) or tuple(out.shape) != shape:
+      raise ValueError(f"set_view_hashes: out must be an int64 device tensor of shape {shape}")
+    return self._eng.bind_view_hash(out, layers=layers, classes=classes)
+
   def load_state(self, states: WorldStates, src, check: Optional[bool] = None) -> TimeStep:
     """World w continues from row src[w] of `states` (-1: world w is left as it is), as the
     world the row was saved from would: same seed, episode, step and future under the same
@@ -2228,6 +2299,33 @@ class MixtureSubstrate:
                          f"{tuple(m._eng.ego_layer_shape[1:])}")
       m._eng.use_current_stream()
       m._eng.observe_ego_layer(None, out=out[off:off + n])
+    return out
+
+  def hash_views(self, layers=None, classes=None):
+    """`Substrate.hash_views()` of the worlds as they are now: ONE int64 [N, P] device tensor of
+    which every member writes its slice.  A hash compares only with hashes of the SAME member: the
+    members' fingerprints differ."""
+    eng = self._members[0]._eng
+    t = eng._torch
+    out = t.empty((self._N, self._P), dtype=t.int64, device=eng.device)
+    for m, off, n in zip(self._members, self._offsets, self._counts):
+      m._eng.use_current_stream()
+      m._eng.hash_views(None, layers=m._view_layers(layers), classes=classes, out=out[off:off + n])
+    return out
+
+  def set_view_hashes(self, layers="all", classes=None):
+    """`Substrate.set_view_hashes` for the mixture: ONE int64 [N, P] device tensor ([T, N, P] with
+    rollout_length=T) of which member i registers its slice in place.  None clears every member's
+    registration."""
+    if layers is None:
+      for m in self._members:
+        m.set_view_hashes(None)
+      return None
+    eng = self._members[0]._eng
+    t = eng._torch
+    out = t.zeros(((self._T,) if self._T else ()) + (self._N, self._P), dtype=t.int64, device=eng.device)
+    for m, off, n in zip(self._members, self._offsets, self._counts):
+      m.set_view_hashes(layers, classes, out=out[:, off:off + n] if self._T else out[off:off + n])
     return out
 
   def event_columns(self):

@@ -1,0 +1,351 @@
+"""The hash of each player's view on the GPU (MpViewHash; Engine.hash_views / bind_view_hash,
+Substrate.hash_views / set_view_hashes, MixtureSubstrate's): both kernels against the numpy model
+of tests/view_hash_model.py (EGO_LAYER from tests/ego_layer_model.py, uint64 numpy arithmetic) and
+against the library's host twin, sampled views and unaligned destinations, indices out of range,
+the registered tensor behind every kind of submission with and without a rollout ring, the
+documented per-step route through step_many(states=True), and the mixture's shared tensor.  Every
+comparison is exact integer equality."""
+import numpy as np
+import pytest
+import torch
+
+import util
+import view_hash_model as VM
+from meltingpot_amd import engine, substrate
+from meltingpot_amd import pack as pack_lib
+
+pytestmark = pytest.mark.gpu
+
+E = engine
+N = 6
+SEED = 5   # (chosen with the CPU oracle: all four facings and dead viewers within 25 random steps of clean_up)
+KITCHEN = "collaborative_cooking__cramped"
+MATRIX = "prisoners_dilemma_in_the_matrix__repeated"
+
+
+def _no_faults(eng):
+  # (words 10 and 11 keep the index and the code of the last report; word 9 claims the next)
+  assert not eng.fault_words()[:10].any(), eng.fault_words()[:10]
+
+
+def _same(got, want, what):
+  got = got.cpu().numpy() if isinstance(got, torch.Tensor) else got
+  want = want.cpu().numpy() if isinstance(want, torch.Tensor) else want
+  assert got.shape == want.shape and got.dtype == want.dtype == np.int64, (what, got.shape, want.shape)
+  assert np.array_equal(got, want), (what, np.argwhere(got != want)[:4].tolist())
+
+
+def _fields(eng, bank):
+  layout = substrate.SubstrateStateLayout(eng.state_layout(), pack_lib.loads(eng.pack_bytes))
+  return substrate.StateFields(bank, layout)
+
+
+def _model(eng, bank, layers=None, classes=None):
+  return VM.of_fields(eng.pack_bytes, _fields(eng, bank), layers, classes)
+
+
+PLAYERS = {"commons_harvest__open": 16}   # (the others: the level's default roles)
+
+
+def _build(name, **kw):
+  cfg = substrate.get_config(name)
+  roles = ("default",) * PLAYERS[name] if name in PLAYERS else cfg.default_player_roles
+  return substrate.build_from_config(cfg, roles=roles, num_worlds=N, env_seed=SEED, **kw)
+
+
+def _actions(rng, eng, *shape):
+  a = util.random_actions(rng, 1, int(np.prod(shape)), eng.P, eng.num_actions)
+  return torch.from_numpy(a.reshape(shape + (eng.P,))).to(eng.device)
+
+
+# ---- 1. live worlds, saved rows, the model and the host twin ---------------------------------------
+@pytest.mark.parametrize("name", ["clean_up", KITCHEN, MATRIX, "commons_harvest__open"])
+def test_live_worlds_saved_rows_the_model_and_the_host_twin_agree(name):
+  env = _build(name)
+  eng = env.engine
+  P = env.num_players
+  assert P == {"clean_up": 7, "commons_harvest__open": 16}.get(name, 2)
+  env.reset()
+  rng = np.random.default_rng(SEED)
+  res = env.step_many(_actions(rng, eng, 25, N), states=True)
+  bank = res.states.data
+  f = _fields(eng, bank)
+  assert set(np.unique(f.orientation.cpu().numpy()[:, :P]).tolist()) == {0, 1, 2, 3}
+  if name == "clean_up":
+    assert bool((f.alive.cpu().numpy()[:, :P] == 0).any())
+  want = _model(eng, bank)
+  assert want.shape == (25 * N, P)
+  live = env.hash_views()
+  assert live.dtype == torch.int64 and tuple(live.shape) == (N, P)
+  _same(live, want[-N:], (name, "live worlds against the model"))
+  _same(env.hash_views(env.save_state()), live, (name, "save_state"))
+  _same(env.hash_views(res.states), want, (name, "every row against the model"))
+  host = E.hash_views_host(eng.pack_bytes, bank.cpu().numpy(), fingerprint=eng.state_fingerprint)
+  _same(host, want, (name, "the host twin"))
+  # layers by name and index, and a class table that merges two ids
+  names = env.state_layout().layer_names
+  L = len(names)
+  picked = [names[L - 1], 0]
+  _same(env.hash_views(layers=picked), _model(eng, bank[-N:], layers=[0, L - 1]), (name, "layers"))
+  n = env.num_layer_ids
+  assert n == VM.num_ids(eng.pack_bytes, P) == eng.num_layer_ids
+  ids = np.unique(VM.EM.of_fields(eng.pack_bytes, f))
+  ids = ids[ids > 0]
+  classes = np.arange(n, dtype=np.int32)
+  classes[ids[1]] = classes[ids[0]]
+  merged = env.hash_views(res.states, classes=classes)
+  _same(merged, _model(eng, bank, classes=classes), (name, "classes"))
+  assert not torch.equal(merged, env.hash_views(res.states))
+  dev_classes = torch.from_numpy(classes).to(eng.device)
+  _same(env.hash_views(res.states, rows=[3, 0], players=[P - 1, 0], layers=[0], classes=dev_classes),
+        _model(eng, bank, layers=[0], classes=classes)[[3, 0], [P - 1, 0]], (name, "classes, layers, views"))
+  with pytest.raises(ValueError, match="classes must be %d integers" % n):
+    env.hash_views(classes=classes[:-1])
+  with pytest.raises(ValueError, match=r"classes_len %d" % (n - 1)):
+    E.view_hash_request(eng._L, eng._h, E.MP_VIEWHASH_DRAW, fingerprint=eng.state_fingerprint, count=N,
+                        dst=live.data_ptr(), dst_bytes=live.numel() * 8, classes=dev_classes.data_ptr(),
+                        classes_len=n - 1)
+  eng.sync()
+  _no_faults(eng)
+  env.close()
+
+
+# ---- 2. sampled views -------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["clean_up", "commons_harvest__open"])
+def test_sampled_views_repeats_and_destinations_off_a_16_byte_line(name):
+  env = _build(name)
+  eng = env.engine
+  P = env.num_players
+  env.reset()
+  rng = np.random.default_rng(SEED)
+  for k in range(4):
+    env.step(_actions(rng, eng, N))
+  bank = env.save_state().data
+  want = _model(eng, bank)
+  count = 3 * N + 1   # R > N
+  r = rng.integers(0, N, size=count).astype(np.int32)
+  r[1] = r[0]
+  p = rng.integers(0, P, size=count).astype(np.int32)
+  p[1] = p[0]
+  for src in (bank, None):   # rows of a bank; world indices of the live worlds
+    every = eng.hash_views(src, rows=r)
+    assert tuple(every.shape) == (count, P)
+    _same(every, want[r], (name, "repeated rows"))
+    views = eng.hash_views(src, rows=r, players=p)
+    assert tuple(views.shape) == (count,)
+    _same(views, every[torch.arange(count), torch.from_numpy(p).long()], (name, "players="))
+    _same(views, want[r, p], (name, "players= against the model"))
+    # an out that starts 8-byte but not 16-byte aligned, and one that starts on a 16-byte line
+    for shift in (1, 2):
+      base = torch.full((count * P + 2,), -7, dtype=torch.int64, device=eng.device)
+      out = base[shift:shift + count * P].view(count, P)
+      assert out.data_ptr() % 16 == (8 if shift == 1 else 0)
+      assert eng.hash_views(src, rows=r, out=out) is out
+      _same(out, want[r], (name, "out", shift))
+      got = base.cpu().numpy()
+      assert (got[:shift] == -7).all() and (got[shift + count * P:] == -7).all()
+      base = torch.full((count + 2,), -7, dtype=torch.int64, device=eng.device)
+      out = base[shift:shift + count]
+      eng.hash_views(src, rows=r, players=p, out=out)
+      _same(out, want[r, p], (name, "views out", shift))
+      got = base.cpu().numpy()
+      assert (got[:shift] == -7).all() and (got[shift + count:] == -7).all()
+  eng.sync()
+  _no_faults(eng)
+  env.close()
+
+
+# ---- 3. bad indices ---------------------------------------------------------------------------------
+def test_an_index_out_of_range_leaves_its_element_and_is_reported():
+  eng = E.Engine(E.load_pack("clean_up"), N, device=0)
+  eng.reset()
+  bank = eng.save_worlds()
+  want = _model(eng, bank)
+  P = eng.P
+  fill = -7
+  out = torch.full((5, P), fill, dtype=torch.int64, device=eng.device)
+  eng.hash_views(bank, rows=[1, N, 0, -1, N + 40], out=out)
+  with pytest.raises(ValueError, match=r"MpViewHash: rows\[(1\] = 6|3\] = -1|4\] = 46) is not a row"):
+    eng.sync()
+  got = out.cpu().numpy()
+  assert np.array_equal(got[0], want[1]) and np.array_equal(got[2], want[0])
+  assert (got[[1, 3, 4]] == fill).all()
+  out = torch.full((4,), fill, dtype=torch.int64, device=eng.device)
+  eng.hash_views(bank, rows=[2, 2, 5, 1], players=[0, P, 6, -1], out=out)
+  with pytest.raises(ValueError, match=rf"MpViewHash: players\[(1\] = {P}|3\] = -1) is not a player"):
+    eng.sync()
+  got = out.cpu().numpy()
+  assert got[0] == want[2, 0] and got[2] == want[5, 6] and (got[[1, 3]] == fill).all()
+  # the live worlds: a world index out of range
+  out = torch.full((2, P), fill, dtype=torch.int64, device=eng.device)
+  eng.hash_views(None, rows=[N + 3, 4], out=out)
+  with pytest.raises(ValueError, match=r"MpViewHash: rows\[0\] = 9"):
+    eng.sync()
+  got = out.cpu().numpy()
+  assert (got[0] == fill).all() and np.array_equal(got[1], want[4])
+  # host-side refusals launch nothing, and the engine stays usable
+  with pytest.raises(ValueError, match="fingerprint"):
+    eng.hash_views(bank, fingerprint=1)
+  with pytest.raises(ValueError, match="without a row list"):
+    eng.hash_views(bank[:2], players=[0, 0, 0])
+  with pytest.raises(ValueError, match="device"):
+    E.view_hash_request(eng._L, eng._h, E.MP_VIEWHASH_REGISTER, dst=out.cpu().numpy().ctypes.data, dst_bytes=1 << 30)
+  fresh = E.Engine(E.load_pack("clean_up"), 2, device=0)
+  with pytest.raises(ValueError, match="never been reset"):
+    fresh.hash_views()
+  fresh.close()
+  eng.step(torch.zeros((N, P), dtype=torch.int32, device=eng.device))
+  _same(eng.hash_views(), _model(eng, eng.save_worlds()), "after the reports")
+  eng.sync()
+  _no_faults(eng)
+  eng.close()
+
+
+# ---- 4. the registered tensor ------------------------------------------------------------------------
+@pytest.mark.parametrize("T", [0, 4])
+def test_the_registered_tensor_follows_every_submission(T):
+  kw = dict(rollout_length=T) if T else {}
+  env, twin = _build("clean_up", **kw), _build("clean_up", **kw)
+  eng = env.engine
+  P = env.num_players
+  names = env.state_layout().layer_names
+  reg = env.set_view_hashes()
+  assert reg.dtype == torch.int64 and tuple(reg.shape) == ((T,) if T else ()) + (N, P)
+  fused = eng.fused
+  rng = np.random.default_rng(SEED)
+  history = {}   # ring slot -> what it was given
+
+  def check(what):
+    want = _model(eng, env.save_state().data)
+    _same(env.hash_views(), want, (what, "hash_views"))
+    if not T:
+      _same(reg, want, (what, "registered"))
+      return
+    _same(reg[env.slot], want, (what, "the submission's slot"))
+    history[env.slot] = want
+    for s, kept in history.items():   # slots written earlier keep what they held
+      _same(reg[s], kept, (what, "slot", s))
+
+  env.reset(); twin.reset()
+  check("reset")
+  a = _actions(rng, eng, N)
+  env.step(a); twin.step(a)
+  check("step")
+  if not T:
+    a, mask = _actions(rng, eng, N), torch.tensor([1, 0, 1, 1, 0, 1], dtype=torch.uint8, device=eng.device)
+    env.step(a, active=mask); twin.step(a, active=mask)
+    check("masked step")
+  a = _actions(rng, eng, 5, N)
+  env.step_many(a); twin.step_many(a)
+  check("step_many")
+  if not T:
+    stopped = [torch.zeros(N, dtype=torch.uint8, device=eng.device) for _ in range(2)]
+    env.step_many(a, until=("last", "reward"), stopped=stopped[0])
+    twin.step_many(a, until=("last", "reward"), stopped=stopped[1])
+    check("step_many(until=)")
+    worlds = [4, 0, 3]
+    a = _actions(rng, eng, 3, len(worlds))
+    env.step_many(a, worlds=worlds); twin.step_many(a, worlds=worlds)
+    check("step_many(worlds=)")
+  saved = env.save_state()
+  a = _actions(rng, eng, N)
+  env.step(a); twin.step(a)
+  check("step")
+  src = [2, -1, 0, 0, -1, 5]
+  env.load_state(saved, src); twin.load_state(substrate.WorldStates(saved.data, twin.engine.state_fingerprint), src)
+  check("load_state")
+  # the twin without the registration ends on identical records and identical leaves
+  assert torch.equal(eng.save_worlds(), twin.engine.save_worlds())
+  ours, theirs = env.observation(), twin.observation()
+  assert set(ours) == set(theirs)
+  for n in theirs:
+    assert torch.equal(ours[n], theirs[n]), n
+  # another choice of layers and classes replaces the registration
+  if not T:
+    classes = torch.arange(env.num_layer_ids, dtype=torch.int32, device=eng.device)
+    classes[1:] = 1
+    reg2 = env.set_view_hashes(layers=[names[0], 2], classes=classes)
+    a = _actions(rng, eng, N)
+    env.step(a); twin.step(a)
+    _same(reg2, _model(eng, env.save_state().data, layers=[0, 2], classes=classes.cpu().numpy()), "layers, classes")
+    _same(reg2, env.hash_views(layers=[0, 2], classes=classes), "layers, classes, drawn")
+    reg = reg2
+  # clearing the registration: the tensor is written no more, the engine's launches are its own
+  frozen = reg.clone()
+  assert env.set_view_hashes(None) is None
+  assert eng.fused == fused == twin.engine.fused
+  a = _actions(rng, eng, N)
+  env.step(a); twin.step(a)
+  assert torch.equal(reg, frozen)
+  assert torch.equal(eng.save_worlds(), twin.engine.save_worlds())
+  for e in (eng, twin.engine):
+    e.sync()
+    _no_faults(e)
+  env.close()
+  twin.close()
+
+
+def test_tune_does_not_write_the_registered_tensor():
+  eng = E.Engine(E.load_pack("clean_up"), N, device=0)
+  eng.bind(E.OBS_WORLD_RGB)
+  reg = eng.bind_view_hash(torch.full((N, eng.P), -7, dtype=torch.int64, device=eng.device))
+  eng.tune()
+  assert bool((reg == -7).all())
+  eng.reset()
+  _same(reg, _model(eng, eng.save_worlds()), "after the reset")
+  eng.sync()
+  _no_faults(eng)
+  eng.close()
+
+
+# ---- 5. per step, through step_many(states=True) -----------------------------------------------------
+def test_the_states_of_step_many_hash_to_the_registered_tensor_of_the_step_loop():
+  K = 6
+  env, loop = _build("clean_up"), _build("clean_up")
+  eng = env.engine
+  P = env.num_players
+  reg = loop.set_view_hashes()
+  env.reset(); loop.reset()
+  A = _actions(np.random.default_rng(SEED + 1), eng, K, N)
+  res = env.step_many(A, states=True)
+  got = env.hash_views(res.states)
+  assert tuple(got.shape) == (K * N, P)
+  got = got.reshape(K, N, P)
+  for k in range(K):
+    loop.step(A[k])
+    _same(got[k], reg, ("step", k))
+  assert len(torch.unique(got)) > K   # (the views change from step to step and differ between players)
+  for e in (eng, loop.engine):
+    e.sync()
+    _no_faults(e)
+  env.close()
+  loop.close()
+
+
+# ---- 6. mixture --------------------------------------------------------------------------------------
+def test_a_mixture_of_two_kitchens_shares_one_tensor():
+  names = [KITCHEN, "collaborative_cooking__ring"]
+  for T in (0, 2):
+    kw = dict(rollout_length=T) if T else {}
+    mix = substrate.build_mixture(names, num_worlds=[3, 4], env_seed=SEED, **kw)
+    P = mix.num_players
+    dev = mix._members[0].engine.device
+    reg = mix.set_view_hashes()
+    assert tuple(reg.shape) == ((T,) if T else ()) + (7, P) and reg.dtype == torch.int64
+    mix.reset()
+    A = torch.from_numpy(util.random_actions(np.random.default_rng(SEED), 5, 7, P, mix.action_spec()[0].num_values)).to(dev)
+    for k in range(5):
+      mix.step(A[k])
+    whole = mix.hash_views()
+    assert tuple(whole.shape) == (7, P)
+    now = reg[mix.slot] if T else reg
+    _same(now, whole, (T, "registered"))
+    for i, m in enumerate(mix._members):
+      sl = mix.member_slice(i)
+      own = m.hash_views()
+      _same(whole[sl], own, (T, i, "the member's own call"))
+      _same(own, _model(m.engine, m.save_state().data), (T, i, "model"))
+      m.engine.sync()
+      _no_faults(m.engine)
+    assert mix.set_view_hashes(None) is None
+    mix.close()
