@@ -968,6 +968,97 @@ typedef struct {
   uint64_t reserved2[3];   /* 0 */
 } MpViewHash;
 
+/* What a conv net reads of a player's view.  EGO_LAYER (MpEgoLayer) is int32 sprite ids, and every
+ * learner turns it into a channels-first stack of 0/1 planes ("wall here", "apple here", "another
+ * avatar here") before its first convolution: a gather through an id -> class table, a one-hot, a
+ * reduction over the layers and a permute.  MpEgoPlanes writes those planes themselves, uint8,
+ * from the record, without drawing the int32 view, and adds what the ids do not carry: where the
+ * others face.  Rides mp_snapshot, recognised by its size: `bytes` = sizeof(MpEgoPlanes),
+ * `host_buf` a HOST MpEgoPlanes with struct_size set to it.  include/mp_ego_planes.h wraps it as
+ * inline C functions.
+ *
+ * The class table.  `classes` is int32 [classes_len], one entry per possible id, 0 .. the largest
+ * id the viewers' value tables hold: classes_len must equal num_ids, which every request that gets
+ * as far as the tables writes back into the caller's struct (count == 0 with a NULL dst,
+ * MP_EGOPLANES_DRAW or MP_EGOPLANES_HOST, asks for nothing else).  Every entry lies in
+ * [-1, num_classes), and 1 <= num_classes = C <= 64.
+ *
+ * The planes.  For a record (a bank row or a live world) and a viewer p let E be the viewer's
+ * EGO_LAYER, int32 [VH][VW][L], exactly as MpEgoLayer defines it (a cell off the map, and every
+ * cell of a dead viewer: OutOfBounds).  The viewer's block is uint8 [C'][VH][VW], C' = C, or C + 4
+ * with `facing`; every byte is 0 or 1:
+ *   class plane c < C:   out[c][i][j] = 1 iff some layer l with bit l of layer_mask set (0: every
+ *     layer) has classes[E[i][j][l]] == c.  Class -1 sets nothing.
+ *   facing plane C + d, d in 0 .. 3:   out[C + d][i][j] = 1 iff the viewer is alive, window cell
+ *     (i, j) maps to a cell (x, y) ON the map — by the turned offset and the torus wrap of
+ *     EGO_LAYER — and some living avatar q < P has (ax[q], ay[q]) == (x, y) and
+ *     ((aori[q] - aori[p]) & 3) == d.  The viewer sees itself at (vf, vl) with d = 0.  On a torus
+ *     whose window is larger than the map an avatar appears in every window cell that maps to its
+ *     cell.  A dead viewer's facing planes are 0.  layer_mask and classes have no influence here.
+ *
+ * MP_EGOPLANES_DRAW: element i of `dst` belongs to row rows[i] (NULL: row i) of `bank` (device
+ *   uint8 [bank_rows][S], 16-byte aligned); a NULL bank means the engine's own worlds as they are
+ *   now (rows[] are then world indices, bank_rows is ignored, the engine must have been reset).
+ *   players == NULL: dst is uint8 [count][P][C'][VH][VW]; otherwise players is device int32 [count]
+ *   and dst is uint8 [count][C'][VH][VW], the planes of player players[i] of row rows[i].  Rows and
+ *   (row, player) pairs may repeat and `count` has no relation to the engine's N.  `dst` may start
+ *   on ANY byte (C' * VH * VW is odd for most packs, and a mixture hands each member a slice of
+ *   one tensor); no byte outside the count blocks is written.  `classes` is a DEVICE table.
+ *   Stream-ordered, no synchronisation, no allocation; nothing of the engine's is written.  A
+ *   rows[i] that is no row (no world) or a players[i] outside [0, P) is never used as an index:
+ *   element i of dst is left as it was — every such element — and the next synchronising call
+ *   returns MP_ERR_INVALID once, naming MpEgoPlanes, rows[i] or players[i] and the value (of
+ *   several such indices one is reported); the engine stays usable.  An entry of the device table
+ *   outside [-1, num_classes) counts as -1 and is reported the same way, naming classes[id].
+ * MP_EGOPLANES_REGISTER: `dst` names a device uint8 [N][P][C'][VH][VW] (slots == 0), or a ring:
+ *   slot s is at dst + s * slot_stride bytes, and `slots` must equal the engine's ring slots
+ *   (mp_bind_output_ring), as MP_EGO_REGISTER.  While registered, every submission (reset, step,
+ *   step_fields, every K-step request, a load) is followed on the same stream by ONE launch that
+ *   rewrites all N blocks from the records, into dst or into the ring slot that submission wrote
+ *   (behind the view-hash launch); `classes` (a DEVICE table the caller keeps alive and may rewrite
+ *   between submissions), layer_mask, num_classes and facing are the registration's.  mp_tune's
+ *   probe submissions do not write it.  A NULL dst clears the registration: the engine's launches
+ *   are then what they were.  An engine without a registration issues exactly the launches it
+ *   issued before.
+ * MP_EGOPLANES_HOST (eng == NULL; pack, pack_len, cfg as for mp_create): MP_EGOPLANES_DRAW of HOST
+ *   rows into a HOST dst with a HOST `classes`, computed by the library without a device (bank
+ *   must not be NULL).  A bad index returns MP_ERR_INVALID at once, naming it; the elements before
+ *   it are written.  An entry outside [-1, num_classes) is refused before anything is written.
+ *
+ * Refused before any launch, the engine left as it was — MP_ERR_INVALID: a NULL classes;
+ * classes_len != num_ids; num_classes outside [1, 64]; facing other than 0 or 1; a short
+ * dst_bytes or slot_stride; a host pointer where a device one is needed; a fingerprint that is
+ * not the engine's (the pack's); an engine never reset (a NULL bank); a layer_mask bit that names
+ * no layer; misaligned bank, rows, players or classes.  MP_ERR_UNSUPPORTED: a record whose render
+ * planes, beside the viewers' value tables and the bit planes of one viewer, do not fit one wave's
+ * share of the LDS; more than 64 layers. */
+enum { MP_EGOPLANES_DRAW = 1, MP_EGOPLANES_REGISTER = 2, MP_EGOPLANES_HOST = 3 };
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(MpEgoPlanes) */
+  int32_t op;              /* MP_EGOPLANES_* */
+  uint64_t fingerprint;    /* in (draw, host): the rows' */
+  const void* bank;        /* uint8 [bank_rows][S]; NULL (draw): the engine's worlds */
+  const int32_t* rows;     /* int32 [count], NULL = rows 0 .. count - 1 */
+  const int32_t* players;  /* int32 [count], NULL = every viewer of each row */
+  void* dst;               /* uint8: see the op */
+  uint64_t dst_bytes;
+  int32_t bank_rows;
+  int32_t count;
+  uint64_t slot_stride;    /* MP_EGOPLANES_REGISTER with a ring: bytes between two slots */
+  int32_t slots;           /* MP_EGOPLANES_REGISTER: 0, or the ring's slots */
+  int32_t classes_len;     /* num_ids */
+  const void* pack;        /* MP_EGOPLANES_HOST */
+  uint64_t pack_len;
+  const MpConfig* cfg;
+  uint64_t layer_mask;     /* bit l = layer l; 0 = every layer */
+  const int32_t* classes;  /* int32 [classes_len] (host form: a HOST table) */
+  int32_t num_ids;         /* out: the length a class table must have */
+  int32_t num_classes;     /* C, 1 .. 64 */
+  int32_t facing;          /* 1: the four facing planes behind the class planes */
+  int32_t reserved;        /* 0 */
+  uint64_t reserved2[3];   /* 0 */
+} MpEgoPlanes;
+
 /* Action sequences: K steps of every world in ONE submission, bit-identical to K calls of the
  * single-step entry points (mp_step, or mp_step_fields with fields = 1) with the same actions,
  * which also hands back the transition of every one of the K steps.  For planners that fork a
@@ -1610,7 +1701,9 @@ int mp_box_fill(MpEngine* eng, MpObsKind kind, int32_t reps, MpBoxFill* out);
  * world list, 3 an MpStatesObserve's rows[], 4 | rule << 8 a row an MpStatesCheck filter refused,
  * 5 an MpStatesCheck's rows[], 6 an MpStatesHash's rows[] or world list, 7 an MpStatesView's
  * rows[], 8 an MpStatesView's players[], 11 an MpEgoLayer's rows[], 12 an MpEgoLayer's players[], 13 an
- * MpViewHash's rows[], 14 an MpViewHash's players[] (9 and 10 are MpStepListed's worlds[])
+ * MpViewHash's rows[], 14 an MpViewHash's players[], 15 an MpEgoPlanes' rows[], 16 an MpEgoPlanes'
+ * players[], 17 an entry of an MpEgoPlanes' device class table (word 9 = the id + 1, word 10 = the
+ * entry) (9 and 10 are MpStepListed's worlds[])
  * — whose three words belong together); of several such reports
  * of one launch the three words may belong to different ones.  Words 12-15: the refused row of a checked load once more, claimed by ONE
  * refused world of the launch (word 12 = world + 1, 13 = the row, 14 = the rule, 15 = the offset

@@ -33,6 +33,7 @@
 #include "episode_stats.h"
 #include "ego_layer.h"
 #include "view_hash.h"
+#include "ego_planes.h"
 
 // frame.hip
 constexpr int kFaultWords = 64 + 4 * 16 * 64 * 2;   // fault words + the timeline build's log
@@ -195,6 +196,16 @@ struct MpEngine {
   const int32_t* vh_classes = nullptr;
   int32_t num_layer_ids = 0;   // 1 + the largest id of d_layer_lut: the length of a class table
   bool hashing_views() const { return vh_dst && !ring_hold && !layer_hold; }
+  // The registered class and facing planes (an MpEgoPlanes request; ego_planes.h): while set, every
+  // submission is followed by one launch that rewrites every viewer's planes, uint8
+  // [N][P][C'][VH][VW].  ep_slots > 0: a ring, slot s at ep_dst + s * ep_stride bytes.  ep_classes:
+  // the caller's device table.  mp_tune's probes do not write it.
+  uint8_t* ep_dst = nullptr;
+  uint64_t ep_stride = 0, ep_mask = 0;
+  int ep_slots = 0;
+  const int32_t* ep_classes = nullptr;
+  int32_t ep_num_classes = 0, ep_facing = 0;
+  bool drawing_planes() const { return ep_dst && !ring_hold && !layer_hold; }
   // The engine's choice (MpConfig.unfused = 0): one launch, always.  (Round 2 drew
   // views under 64 KB a world — the two-player games — in a second launch: a CU
   // then has 64 worlds to step for 2 us of drawing each, and with 4-8 feeders the
@@ -438,6 +449,16 @@ int sync_and_check(MpEngine* e, const char* who) {
                   who, what == kFaultViewHashRow ? "rows" : "players", at, (int)index,
                   what == kFaultViewHashRow ? "not a row of the bank (with no bank: no world of this engine)"
                                             : "not a player of this engine", at);
+    if (what == kFaultEgoPlanesRow || what == kFaultEgoPlanesPlayer)
+      return fail(MP_ERR_INVALID,
+                  "%s: MpEgoPlanes: %s[%u] = %d is %s; element %u of the destination was left as it was",
+                  who, what == kFaultEgoPlanesRow ? "rows" : "players", at, (int)index,
+                  what == kFaultEgoPlanesRow ? "not a row of the bank (with no bank: no world of this engine)"
+                                             : "not a player of this engine", at);
+    if (what == kFaultEgoPlanesClass)
+      return fail(MP_ERR_INVALID,
+                  "%s: MpEgoPlanes: classes[%u] = %d is outside [-1, num_classes); the entry counted as -1",
+                  who, at, (int)index);
     if (what == kFaultListedWorld || what == kFaultListedRepeat)
       return fail(MP_ERR_INVALID,
                   "%s: MpStepListed: worlds[%u] = %d %s; the entry ran nothing and element %u of every per-call "
@@ -578,6 +599,20 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
     a.layer_mask = e->vh_mask;
     a.classes = e->vh_classes; a.num_classes = e->vh_classes ? e->num_layer_ids : 0;
     view_hash::launch(a, view_hash::plan_of(a.g, e->N, e->num_cus), e->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  if (e->drawing_planes()) {
+    // the planes launch: every viewer's class and facing planes, from the records this submission left
+    ego_planes::Args a = {};
+    a.g = ego_layer::window_of(e->t);
+    a.src = e->d_state; a.src_rows = e->N; a.count = e->N;
+    a.stride = e->t.world_stride; a.grid_pad = e->t.grid_pad;
+    a.dst = e->ep_slots > 0 ? e->ep_dst + (uint64_t)(slot % e->ep_slots) * e->ep_stride : e->ep_dst;
+    a.lut = e->d_layer_lut; a.fault = e->t.fault;
+    a.layer_mask = e->ep_mask;
+    a.classes = e->ep_classes; a.num_ids = e->num_layer_ids;
+    a.num_classes = e->ep_num_classes; a.facing = e->ep_facing;
+    ego_planes::launch(a, ego_planes::plan_of(a.g, ego_planes::planes_of(a), e->N, e->num_cus), e->stream);
     HIP_TRY(hipGetLastError());
   }
   return MP_OK;
@@ -1128,6 +1163,8 @@ int plan_views(MpEngine* e, const MpDevOptions* dev) {
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the EGO_LAYER kernels failed: %d", rc);
   if (int rc = view_hash::prepare())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the view-hash kernels failed: %d", rc);
+  if (int rc = ego_planes::prepare())
+    return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the ego-planes kernels failed: %d", rc);
   if (int rc = prepare_step_starts())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the episode-start kernels failed: %d", rc);
   if (int rc = prepare_step_active())
@@ -2878,7 +2915,198 @@ static int view_hash_request(MpEngine* e, MpViewHash* out) {
   return MP_OK;
 }
 
-static_assert(sizeof(MpViewHash) == 152 && sizeof(MpViewHash) != sizeof(MpStepMany) &&
+// An MpEgoPlanes request (include/mp_engine.h; carried by mp_snapshot; `e` is NULL for the host
+// form): writes every viewer's class and facing planes of bank rows or of the engine's worlds (one
+// launch), registers or clears the tensor behind every submission (no launch), or applies the
+// function to host rows.  Everything is checked first.  `out` is the caller's struct: num_ids is
+// written back.
+static int ego_planes_request(MpEngine* e, MpEgoPlanes* out) {
+  static const char kWho[] = "MpEgoPlanes";
+  MpEgoPlanes r;
+  memcpy(&r, out, sizeof r);
+  if (r.struct_size != sizeof(MpEgoPlanes))
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpEgoPlanes));
+  if (r.op != MP_EGOPLANES_DRAW && r.op != MP_EGOPLANES_REGISTER && r.op != MP_EGOPLANES_HOST)
+    return fail(MP_ERR_INVALID, "%s: unknown op %d", kWho, r.op);
+  if (r.op == MP_EGOPLANES_HOST ? e != nullptr : e == nullptr)
+    return fail(MP_ERR_INVALID, "%s: %s", kWho, e ? "MP_EGOPLANES_HOST takes no engine" : "NULL engine");
+  if (r.reserved != 0 || r.reserved2[0] != 0 || r.reserved2[1] != 0 || r.reserved2[2] != 0)
+    return fail(MP_ERR_INVALID, "%s: the reserved words must be 0", kWho);
+  if (r.op == MP_EGOPLANES_HOST && (!r.pack || !r.cfg))
+    return fail(MP_ERR_INVALID, "%s: MP_EGOPLANES_HOST needs the pack and its config (NULL pack or cfg)", kWho);
+  if (r.op == MP_EGOPLANES_REGISTER && !r.dst) {   // clears the registration: the engine's launches are what they were
+    e->ep_dst = nullptr;
+    e->ep_stride = 0; e->ep_mask = 0;
+    e->ep_slots = 0;
+    e->ep_classes = nullptr;
+    e->ep_num_classes = 0; e->ep_facing = 0;
+    out->num_ids = e->num_layer_ids;
+    return MP_OK;
+  }
+  // the tables and the fingerprint: the engine's, or the pack's by the host stage
+  HostStage h;
+  std::vector<int32_t> host_lut;
+  const DevTables* t;
+  uint64_t fingerprint;
+  int32_t num_ids;
+  if (e) {
+    t = &e->t;
+    fingerprint = e->fingerprint;
+    num_ids = e->num_layer_ids;
+  } else {
+    if (int rc = host_stage(r.pack, r.pack_len, r.cfg, &h)) return rc;
+    t = &h.d.t;
+    fingerprint = state_fingerprint(h.pack, h.d.t);
+    // (upload_layer_lut's table, from the pack as the host stage left it)
+    const int32_t* ssprite = table<int32_t>(h.pack.data(), "state_sprite");
+    const int32_t* vmap = table<int32_t>(h.pack.data(), "view_sprite_map");
+    host_lut.assign((size_t)t->P * kLayerLutRow, 0);
+    for (int p = 0; p < t->P; ++p) {
+      const int32_t* remap = vmap + (size_t)p * t->nsprites;
+      int32_t* row = host_lut.data() + (size_t)p * kLayerLutRow;
+      for (int s = 1; s < t->nstates && s < 256; ++s) row[s] = ssprite[s] >= 0 ? 1 + remap[ssprite[s]] : 0;
+      row[256] = 1 + remap[0];
+    }
+    num_ids = view_hash::num_ids(host_lut.data(), t->P);
+  }
+  if (num_ids < 1)
+    return fail(MP_ERR_UNSUPPORTED, "%s: the pack's view tables hold a negative id", kWho);
+  out->num_ids = num_ids;
+  if (r.op != MP_EGOPLANES_REGISTER && r.count == 0 && !r.dst) return MP_OK;   // the question alone
+  if (!r.dst) return fail(MP_ERR_INVALID, "%s: NULL dst", kWho);
+  const ego_layer::Window g = ego_layer::window_of(*t);
+  if (g.L > 64) return fail(MP_ERR_UNSUPPORTED, "%s: %d layers; layer_mask names 64", kWho, g.L);
+  const uint64_t every = g.L == 64 ? ~0ull : (1ull << g.L) - 1ull;
+  if (r.layer_mask & ~every)
+    return fail(MP_ERR_INVALID, "%s: layer_mask %016llx has a bit that names no layer (the view has %d)", kWho,
+                (unsigned long long)r.layer_mask, g.L);
+  const uint64_t layer_mask = r.layer_mask ? r.layer_mask : every;
+  if (!r.classes) return fail(MP_ERR_INVALID, "%s: NULL classes: the planes are those of a class table", kWho);
+  if (r.classes_len != num_ids)
+    return fail(MP_ERR_INVALID, "%s: classes_len %d: a class table has one entry per id, %d of them", kWho,
+                r.classes_len, num_ids);
+  if ((uintptr_t)r.classes & 3)
+    return fail(MP_ERR_INVALID, "%s: classes %p is not 4-byte aligned", kWho, (const void*)r.classes);
+  if (r.num_classes < 1 || r.num_classes > ego_planes::kMaxClasses)
+    return fail(MP_ERR_INVALID, "%s: num_classes %d is outside [1, %d]", kWho, r.num_classes, ego_planes::kMaxClasses);
+  if (r.facing != 0 && r.facing != 1) return fail(MP_ERR_INVALID, "%s: facing %d is neither 0 nor 1", kWho, r.facing);
+  if ((t->grid_pad & 15) || (t->world_stride & 15) || (int64_t)g.L * g.HW > (int64_t)t->grid_pad)
+    return fail(MP_ERR_UNSUPPORTED, "%s: a record of %d bytes with %d bytes of planes is not read in 16-byte lines",
+                kWho, t->world_stride, t->grid_pad);
+  const int num_planes = r.num_classes + (r.facing ? 4 : 0);
+  const uint64_t view = (uint64_t)num_planes * (uint64_t)g.VH * (uint64_t)g.VW, world = (uint64_t)g.P * view;
+  if (view * (uint64_t)g.VH * (uint64_t)g.VW >= (1ull << 32))   // (a byte's plane is found with one multiply)
+    return fail(MP_ERR_UNSUPPORTED, "%s: a viewer's planes are %llu bytes", kWho, (unsigned long long)view);
+  if (r.op == MP_EGOPLANES_REGISTER) {
+    const uint64_t N = (uint64_t)e->N, block = N * world;
+    if (r.slots < 0) return fail(MP_ERR_INVALID, "%s: slots %d", kWho, r.slots);
+    if (r.slots > 0 && r.slots != e->ring_slots)
+      return fail(MP_ERR_INVALID, "%s: a ring of %d slots, the engine's ring has %d (mp_bind_output_ring; one "
+                  "position for all of them)", kWho, r.slots, e->ring_slots);
+    if (r.slots > 0 && r.slot_stride < block)
+      return fail(MP_ERR_INVALID, "%s: slot_stride %llu: a slot is %llu bytes", kWho,
+                  (unsigned long long)r.slot_stride, (unsigned long long)block);
+    const uint64_t need = r.slots > 0 ? (uint64_t)(r.slots - 1) * r.slot_stride + block : block;
+    if (r.dst_bytes < need)
+      return fail(MP_ERR_INVALID, "%s: the planes of %d worlds%s need %llu bytes, dst has %llu", kWho, e->N,
+                  r.slots > 0 ? " in every slot" : "", (unsigned long long)need, (unsigned long long)r.dst_bytes);
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = check_device_pointer(e, r.dst, "MpEgoPlanes (dst)")) return rc;
+    if (int rc = check_bank(e, r.dst, need, "MpEgoPlanes (dst)")) return rc;
+    if (int rc = check_bank(e, r.classes, (uint64_t)num_ids * 4, "MpEgoPlanes (classes)")) return rc;
+    const ego_planes::Plan p = ego_planes::plan_of(g, num_planes, e->N, e->num_cus);
+    if (p.waves < 1)
+      return fail(MP_ERR_UNSUPPORTED, "%s: the value tables and one wave's render and bit planes need %d B of LDS",
+                  kWho, p.lds);
+    e->ep_dst = (uint8_t*)r.dst;
+    e->ep_stride = r.slots > 0 ? r.slot_stride : 0;
+    e->ep_slots = r.slots;
+    e->ep_mask = layer_mask;
+    e->ep_classes = r.classes;
+    e->ep_num_classes = r.num_classes;
+    e->ep_facing = r.facing;
+    return MP_OK;
+  }
+  const bool live = r.op == MP_EGOPLANES_DRAW && !r.bank;
+  if (r.op == MP_EGOPLANES_HOST && !r.bank) return fail(MP_ERR_INVALID, "%s: NULL bank", kWho);
+  const int32_t src_rows = live ? e->N : r.bank_rows;
+  if (r.count < 1 || src_rows < 1)
+    return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", kWho, r.count, src_rows);
+  if (!r.rows && r.count > src_rows)
+    return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are drawn (count %d, there are %d "
+                "rows)", kWho, r.count, src_rows);
+  if (r.fingerprint != fingerprint)
+    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this %s (%016llx): they were "
+                "saved by an engine of another pack, player count or record layout", kWho,
+                (unsigned long long)r.fingerprint, e ? "engine's" : "pack's", (unsigned long long)fingerprint);
+  const uint64_t count = (uint64_t)r.count, need = count * (r.players ? view : world);
+  if (r.dst_bytes < need)
+    return fail(MP_ERR_INVALID, "%s: %d elements of %llu bytes need %llu bytes, dst has %llu", kWho, r.count,
+                (unsigned long long)(r.players ? view : world), (unsigned long long)need,
+                (unsigned long long)r.dst_bytes);
+  if (((uintptr_t)r.rows & 3) || ((uintptr_t)r.players & 3))
+    return fail(MP_ERR_INVALID, "%s: rows %p and players %p must be 4-byte aligned", kWho, (const void*)r.rows,
+                (const void*)r.players);
+  ego_planes::Args a = {};
+  a.g = g;
+  a.rows = r.rows; a.players = r.players; a.dst = (uint8_t*)r.dst;
+  a.src_rows = src_rows; a.count = r.count;
+  a.stride = t->world_stride; a.grid_pad = t->grid_pad;
+  a.layer_mask = layer_mask;
+  a.classes = r.classes; a.num_ids = num_ids;
+  a.num_classes = r.num_classes; a.facing = r.facing;
+  if (r.op == MP_EGOPLANES_HOST) {
+    for (int32_t id = 0; id < num_ids; ++id)
+      if (r.classes[id] < -1 || r.classes[id] >= r.num_classes)
+        return fail(MP_ERR_INVALID, "%s: classes[%d] = %d is outside [-1, num_classes = %d)", kWho, id,
+                    r.classes[id], r.num_classes);
+    a.src = (const uint8_t*)r.bank;
+    a.lut = host_lut.data();
+    uint32_t what = 0;
+    const int bad = ego_planes::host(a, &what);
+    if (bad >= 0)
+      return fail(MP_ERR_INVALID, "%s: %s[%d] = %d is %s; the elements from %d on were left as they were", kWho,
+                  what == kFaultEgoPlanesRow ? "rows" : "players", bad,
+                  what == kFaultEgoPlanesRow ? (r.rows ? r.rows[bad] : bad) : r.players[bad],
+                  what == kFaultEgoPlanesRow ? "not a row of the bank" : "not a player of this pack", bad);
+    return MP_OK;
+  }
+  if (live && !e->has_state)
+    return fail(MP_ERR_INVALID, "%s: the engine has never been reset; there is no state to draw", kWho);
+  if (!live && ((uintptr_t)r.bank & 15))   // (records are read in 16-byte lines)
+    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", kWho, r.bank);
+  HIP_TRY(hipSetDevice(e->device));
+  if (!live)
+    if (int rc = check_bank(e, r.bank, (uint64_t)r.bank_rows * (uint64_t)t->world_stride, "MpEgoPlanes (bank)"))
+      return rc;
+  if (r.rows)
+    if (int rc = check_bank(e, r.rows, count * 4, "MpEgoPlanes (rows)")) return rc;
+  if (r.players)
+    if (int rc = check_bank(e, r.players, count * 4, "MpEgoPlanes (players)")) return rc;
+  if (int rc = check_bank(e, r.classes, (uint64_t)num_ids * 4, "MpEgoPlanes (classes)")) return rc;
+  if (int rc = check_bank(e, r.dst, need, "MpEgoPlanes (dst)")) return rc;
+  const ego_planes::Plan p = ego_planes::plan_of(g, num_planes, r.count, e->num_cus);
+  if (p.waves < 1)
+    return fail(MP_ERR_UNSUPPORTED, "%s: the value tables and one wave's render and bit planes need %d B of LDS",
+                kWho, p.lds);
+  a.src = live ? e->d_state : (const uint8_t*)r.bank;
+  a.lut = e->d_layer_lut; a.fault = e->t.fault;
+  ego_planes::launch(a, p, e->stream);
+  HIP_TRY(hipGetLastError());
+  return MP_OK;
+}
+
+static_assert(sizeof(MpEgoPlanes) == 160 && sizeof(MpEgoPlanes) != sizeof(MpStepMany) &&
+                  sizeof(MpEgoPlanes) != sizeof(MpStateLayout) && sizeof(MpEgoPlanes) != sizeof(MpStepUntil) &&
+                  sizeof(MpEgoPlanes) != sizeof(MpStatesHash) && sizeof(MpEgoPlanes) != sizeof(MpStepActive) &&
+                  sizeof(MpEgoPlanes) != sizeof(MpStepListed) && sizeof(MpEgoPlanes) != sizeof(MpEpisodeStats) &&
+                  sizeof(MpEgoPlanes) != sizeof(MpStatesCheck) && sizeof(MpEgoPlanes) != sizeof(MpStatesView) &&
+                  sizeof(MpEgoPlanes) != sizeof(MpEpisodeStarts) && sizeof(MpEgoPlanes) != sizeof(MpStatesObserve) &&
+                  sizeof(MpEgoPlanes) != sizeof(MpWorldStates) && sizeof(MpEgoPlanes) != sizeof(MpKernelVariant) &&
+                  sizeof(MpEgoPlanes) != sizeof(MpStepTrajectory) && sizeof(MpEgoPlanes) != sizeof(MpEgoLayer) &&
+                  sizeof(MpEgoPlanes) != sizeof(MpViewHash) && sizeof(MpEgoPlanes) < 448,
+              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
+static_assert(sizeof(MpViewHash) == 152 &&sizeof(MpViewHash) != sizeof(MpStepMany) &&
                   sizeof(MpViewHash) != sizeof(MpStateLayout) && sizeof(MpViewHash) != sizeof(MpStepUntil) &&
                   sizeof(MpViewHash) != sizeof(MpStatesHash) && sizeof(MpViewHash) != sizeof(MpStepActive) &&
                   sizeof(MpViewHash) != sizeof(MpStepListed) && sizeof(MpViewHash) != sizeof(MpEpisodeStats) &&
@@ -3004,6 +3232,7 @@ int mp_snapshot(MpEngine* e, void* buf, uint64_t bytes) {
     return ego_layer_request(e, r);
   }
   if (buf && bytes == sizeof(MpViewHash)) return view_hash_request(e, (MpViewHash*)buf);   // (num_ids is written back)
+  if (buf && bytes == sizeof(MpEgoPlanes)) return ego_planes_request(e, (MpEgoPlanes*)buf);   // (likewise)
   if (buf && bytes == sizeof(MpStateLayout)) return state_layout(e, (MpStateLayout*)buf);
   if (buf && bytes == sizeof(MpStatesCheck)) {
     MpStatesCheck r;   // (read only: the verdicts go to r.out)

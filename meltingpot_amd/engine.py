@@ -16,7 +16,7 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-from typing import Dict, Optional, Sequence
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -714,6 +714,106 @@ def hash_views_host(pack_bytes: bytes, rows, players=None, *, which=None, layers
                     players=None if ply is None else ply.ctypes.data, count=count,
                     layer_mask=view_layer_mask(layers, layout.L), classes=None if cls is None else cls.ctypes.data,
                     classes_len=0 if cls is None else int(cls.size), dst=out.ctypes.data, dst_bytes=out.nbytes)
+  return out
+
+
+# Class-indicator feature planes of each player's view (include/mp_engine.h: MpEgoPlanes), carried
+# by mp_snapshot
+MP_EGOPLANES_DRAW, MP_EGOPLANES_REGISTER, MP_EGOPLANES_HOST = 1, 2, 3
+EGO_PLANES_MAX_CLASSES = 64
+
+
+class MpEgoPlanes(ctypes.Structure):
+  _fields_ = [("struct_size", ctypes.c_uint32), ("op", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
+              ("bank", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("players", ctypes.c_void_p),
+              ("dst", ctypes.c_void_p), ("dst_bytes", ctypes.c_uint64), ("bank_rows", ctypes.c_int32),
+              ("count", ctypes.c_int32), ("slot_stride", ctypes.c_uint64), ("slots", ctypes.c_int32),
+              ("classes_len", ctypes.c_int32), ("pack", ctypes.c_void_p), ("pack_len", ctypes.c_uint64),
+              ("cfg", ctypes.c_void_p), ("layer_mask", ctypes.c_uint64), ("classes", ctypes.c_void_p),
+              ("num_ids", ctypes.c_int32), ("num_classes", ctypes.c_int32), ("facing", ctypes.c_int32),
+              ("reserved", ctypes.c_int32), ("reserved2", ctypes.c_uint64 * 3)]
+
+
+def ego_planes_request(L, handle, op: int, **fields) -> MpEgoPlanes:
+  """Runs one MpEgoPlanes request on engine `handle` (None: the host form); raises like every call.
+  The returned request's `num_ids` is the length a class table must have."""
+  req = MpEgoPlanes(ctypes.sizeof(MpEgoPlanes), int(op))
+  for k, v in fields.items():
+    setattr(req, k, v)
+  _check(L, L.mp_snapshot(handle, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpEgoPlanes)")
+  return req
+
+
+def _plane_classes(classes, num_ids: int, num_classes) -> Tuple[np.ndarray, int]:
+  """(`classes` as the contiguous int32 [num_ids] host table of an MpEgoPlanes request, C).  C is
+  `num_classes`, by default 1 + the largest entry; every entry must lie in [-1, C), 1 <= C <= 64."""
+  a = np.asarray(classes)
+  if a.ndim != 1 or a.size != num_ids or not np.issubdtype(a.dtype, np.integer):
+    raise ValueError(f"ego_planes: classes must be {num_ids} integers, one per layer id (num_layer_ids); got "
+                     f"{a.dtype} {a.shape}")
+  C = int(a.max()) + 1 if num_classes is None else int(num_classes)
+  if not 1 <= C <= EGO_PLANES_MAX_CLASSES:
+    raise ValueError(f"ego_planes: num_classes {C} is outside [1, {EGO_PLANES_MAX_CLASSES}]"
+                     + (" (by default 1 + the largest entry of classes)" if num_classes is None else ""))
+  bad = np.nonzero((a < -1) | (a >= C))[0]
+  if bad.size:
+    raise ValueError(f"ego_planes: classes[{int(bad[0])}] = {int(a[bad[0]])} is outside [-1, num_classes = {C})")
+  return np.ascontiguousarray(a, np.int32), C
+
+
+def _view_window(pack_bytes: bytes) -> Tuple[int, int]:
+  """(VH, VW) of the pack's per-agent view."""
+  from . import lower, pack as pack_lib
+  hdr = pack_lib.loads(pack_bytes)["hdr"]
+  return (int(hdr[lower.HDR_VF]) + int(hdr[lower.HDR_VB]) + 1, int(hdr[lower.HDR_VL]) + int(hdr[lower.HDR_VR]) + 1)
+
+
+def layer_id_names_host(pack_bytes: bytes, *, num_players: int = 0, dev: Optional[Dict[str, int]] = None) -> Tuple[str, ...]:
+  """What every id of "LAYER" and "EGO_LAYER" shows: a tuple of `num_layer_ids_host(pack)` strings,
+  "" for id 0 (nothing) and the name of sprite i - 1 for id i ("OutOfBounds" is id 1).  No GPU."""
+  from . import pack as pack_lib
+  names = bytes(pack_lib.loads(pack_bytes)["sprite_names"]).split(b"\0")[:-1]
+  n = num_layer_ids_host(pack_bytes, num_players=num_players, dev=dev)
+  return ("",) + tuple(names[i].decode() if i < len(names) else "" for i in range(n - 1))
+
+
+def ego_planes_host(pack_bytes: bytes, rows, classes, players=None, *, which=None, layers=None, facing: bool = False,
+                    num_classes: Optional[int] = None, fingerprint: Optional[int] = None, num_players: int = 0,
+                    dev: Optional[Dict[str, int]] = None) -> np.ndarray:
+  """The class and facing planes of each player's view of host rows (uint8 [M, S] array) by the
+  library's host-only form (MP_EGOPLANES_HOST: the kernels' own functions compiled for the host;
+  no GPU needed): uint8 [R, P, C', VH, VW], or [R, C', VH, VW] with `players` (R ints: player
+  players[i] of the i-th row).  `classes`: `num_layer_ids_host(pack)` ints in [-1, C) mapping every
+  id to its class (-1: none); C = `num_classes`, by default 1 + the largest; C' = C + 4 with
+  `facing`.  `which`: the rows, in order, repeats allowed (default: all).  `layers`: the layer
+  indices that count (None: all).  `fingerprint`: the rows' (default: the pack's)."""
+  L = load_library()
+  bank = np.ascontiguousarray(rows, np.uint8)
+  if bank.ndim != 2 or bank.shape[0] < 1:
+    raise ValueError("ego_planes_host: rows must be a uint8 array [M, S]")
+  keep = _host_config(pack_bytes, num_players, dev)
+  layout = _layout_request(L, None, pack_bytes, num_players, dev)
+  if bank.shape[1] != layout.world_stride:
+    raise ValueError(f"ego_planes_host: rows of {bank.shape[1]} bytes, the pack's are {layout.world_stride}")
+  idx = None if which is None else np.ascontiguousarray(np.asarray(which).reshape(-1), np.int32)
+  ply = None if players is None else np.ascontiguousarray(np.asarray(players).reshape(-1), np.int32)
+  count = int(ply.size) if ply is not None else bank.shape[0] if idx is None else int(idx.size)
+  if count < 1:
+    raise ValueError("ego_planes_host: no rows to draw")
+  if idx is not None and int(idx.size) != count:
+    raise ValueError(f"ego_planes_host: which has {int(idx.size)} entries, players {count}")
+  cls, C = _plane_classes(classes, num_layer_ids_host(pack_bytes, num_players=num_players, dev=dev), num_classes)
+  mask = view_layer_mask(layers, layout.L)
+  hdr = _view_window(pack_bytes)
+  out = np.zeros((count,) + ((layout.P,) if ply is None else ()) + (C + (4 if facing else 0),) + hdr, np.uint8)
+  ego_planes_request(L, None, MP_EGOPLANES_HOST,
+                     fingerprint=layout.fingerprint if fingerprint is None else int(fingerprint),
+                     pack=ctypes.addressof(keep[0]), pack_len=len(pack_bytes),
+                     cfg=ctypes.cast(ctypes.pointer(keep[1]), ctypes.c_void_p), bank=bank.ctypes.data,
+                     bank_rows=int(bank.shape[0]), rows=None if idx is None else idx.ctypes.data,
+                     players=None if ply is None else ply.ctypes.data, count=count, layer_mask=mask,
+                     classes=cls.ctypes.data, classes_len=int(cls.size), num_classes=C, facing=int(bool(facing)),
+                     dst=out.ctypes.data, dst_bytes=out.nbytes)
   return out
 
 
@@ -2748,6 +2848,125 @@ class Engine:
                       layer_mask=mask, classes=None if cls is None else cls.data_ptr(),
                       classes_len=0 if cls is None else int(cls.numel()))
     self._view_hash = (out, cls)
+    return out
+
+  @property
+  def layer_id_names(self) -> Tuple[str, ...]:
+    """What every id of OBS_LAYER and EGO_LAYER shows: `num_layer_ids` strings, "" for id 0
+    (nothing) and the name of sprite i - 1 for id i ("OutOfBounds" is id 1) — what a `classes`
+    table is written by."""
+    if getattr(self, "_layer_id_names", None) is None:
+      from . import pack as pack_lib
+      names = bytes(pack_lib.loads(self.pack_bytes)["sprite_names"]).split(b"\0")[:-1]
+      self._layer_id_names = ("",) + tuple(names[i].decode() if i < len(names) else ""
+                                           for i in range(self.num_layer_ids - 1))
+    return self._layer_id_names
+
+  def _plane_classes(self, classes, num_classes):
+    """(`classes` of an ego-planes call as a contiguous int32 [num_layer_ids] device tensor, C).  A
+    device tensor of that form is read where it lies and is not checked here (the kernel takes an
+    entry outside [-1, C) as -1 and reports it); anything else is checked on the host."""
+    t = self._torch
+    if classes is None:
+      raise ValueError("ego_planes: classes is needed: one class (or -1) per layer id (num_layer_ids)")
+    if (isinstance(classes, t.Tensor) and classes.dtype == t.int32 and classes.device == self.device and
+        classes.is_contiguous() and tuple(classes.shape) == (self.num_layer_ids,)):
+      C = int(classes.max()) + 1 if num_classes is None else int(num_classes)
+      if not 1 <= C <= EGO_PLANES_MAX_CLASSES:
+        raise ValueError(f"ego_planes: num_classes {C} is outside [1, {EGO_PLANES_MAX_CLASSES}]")
+      return classes, C
+    host = classes.cpu().numpy() if isinstance(classes, t.Tensor) else classes
+    table, C = _plane_classes(host, self.num_layer_ids, num_classes)
+    return t.from_numpy(table).to(self.device), C
+
+  def ego_planes_shape(self, num_classes: int, facing: bool = False) -> Tuple[int, ...]:
+    """(N, P, C', VH, VW) of the planes of every viewer: C' = num_classes, + 4 with `facing`."""
+    N, P, VH, VW, _ = self.ego_layer_shape
+    return (N, P, int(num_classes) + (4 if facing else 0), VH, VW)
+
+  def observe_ego_planes(self, classes, bank=None, rows=None, players=None, layers=None, facing: bool = False,
+                         num_classes: Optional[int] = None, out=None, fingerprint: Optional[int] = None):
+    """uint8 device tensor [R, P, C', VH, VW] (or [R, C', VH, VW] with `players`, R ints: player
+    players[i] of row rows[i]): what a conv net reads of each player's view — channels-first 0/1
+    planes of its EGO_LAYER, written from the records by one launch without drawing the int32
+    view — in rows of `bank` (a contiguous uint8 device tensor [M, S]), or in the engine's worlds as
+    they are now (`bank` None; `rows` are then world indices).  `classes`: `num_layer_ids` ints in
+    [-1, C) mapping every id to its class (`layer_id_names` says which id is which sprite); class
+    plane c is 1 where some counted layer of the cell holds an id of class c, and -1 sets nothing.
+    C = `num_classes` (at most 64), by default 1 + the largest entry.  `layers`: the layer indices
+    that count (None: all).  `facing`: four more planes, C' = C + 4: plane C + d is 1 where a living
+    avatar stands that faces (ORIENTATION[q] - ORIENTATION[p]) & 3 == d in the viewer's frame (the
+    viewer itself: d = 0); a dead viewer's are 0.  `out`: a uint8 tensor of the result's shape that
+    may start on any byte.  A contiguous int32 device `classes` is read where it lies; an entry of
+    it outside [-1, C) counts as -1 and the next synchronising call raises ValueError.  A row or
+    player index out of range leaves its element as it was and is reported the same way.  Nothing
+    of the engine's is written.  Enqueued on the current stream."""
+    t = self._torch
+    S = int(self.info.world_state_bytes)
+    if bank is not None:
+      if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
+          bank.shape[1] != S or not bank.is_contiguous()):
+        raise ValueError(f"observe_ego_planes: bank must be a contiguous uint8 tensor [M, {S}]")
+      if bank.shape[0] < 1:
+        raise ValueError("observe_ego_planes: the bank has no rows")
+    there = self.N if bank is None else int(bank.shape[0])
+    p = None if players is None else self._device_ints(players, "players")
+    r = None if rows is None else self._device_ints(rows, "rows")
+    count = int(p.numel()) if p is not None else int(r.numel()) if r is not None else there
+    if count < 1:
+      raise ValueError("observe_ego_planes: no views to draw")
+    if r is not None and int(r.numel()) != count:
+      raise ValueError(f"observe_ego_planes: rows has {int(r.numel())} entries, players {count}")
+    mask = view_layer_mask(layers, int(self.info.num_layers))
+    cls, C = self._plane_classes(classes, num_classes)
+    shape = self.ego_planes_shape(C, facing)
+    shape = (count,) + (shape[1:] if p is None else shape[2:])
+    if out is None:
+      out = t.empty(shape, dtype=t.uint8, device=self.device)
+    elif (not isinstance(out, t.Tensor) or out.dtype != t.uint8 or tuple(out.shape) != shape or
+          not out.is_contiguous() or out.device != self.device):
+      raise ValueError(f"observe_ego_planes: out must be a contiguous uint8 tensor of shape {shape} on {self.device}")
+    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    self.use_current_stream()
+    ego_planes_request(self._L, self._h, MP_EGOPLANES_DRAW, fingerprint=fp,
+                       bank=None if bank is None else bank.data_ptr(), bank_rows=0 if bank is None else there,
+                       rows=None if r is None else r.data_ptr(), players=None if p is None else p.data_ptr(),
+                       count=count, layer_mask=mask, classes=cls.data_ptr(), classes_len=int(cls.numel()),
+                       num_classes=C, facing=int(bool(facing)), dst=out.data_ptr(), dst_bytes=out.numel())
+    self._ego_planes_args = (bank, r, p, cls, out)   # (kept until the next call: the launch may not have run yet)
+    return out
+
+  def bind_ego_planes(self, out, classes=None, layers=None, facing: bool = False, num_classes: Optional[int] = None):
+    """Registers `out` — a uint8 device tensor [N, P, C', VH, VW], or [T, N, P, C', VH, VW] with T
+    the engine's ring slots (`bind_ring` some kind first); it may start on any byte — as the planes
+    of the worlds: from now on every submission (reset, step, step_many in every form, a load) is
+    followed on the same stream by one launch that rewrites `observe_ego_planes(classes, ...)` of
+    every world into it, or into the ring slot the submission wrote.  `classes`, `layers`,
+    `facing`, `num_classes`: as `observe_ego_planes` takes them; the engine keeps the class table
+    alive.  None clears the registration; the engine's launches are then what they were.  Returns
+    `out`."""
+    t = self._torch
+    if out is None:
+      ego_planes_request(self._L, self._h, MP_EGOPLANES_REGISTER)
+      self._ego_planes = None
+      return None
+    mask = view_layer_mask(layers, int(self.info.num_layers))
+    cls, C = self._plane_classes(classes, num_classes)
+    shape = self.ego_planes_shape(C, facing)
+    ring = isinstance(out, t.Tensor) and out.dim() == len(shape) + 1
+    if (not isinstance(out, t.Tensor) or out.dtype != t.uint8 or tuple(out.shape[-len(shape):]) != shape or
+        out.dim() not in (len(shape), len(shape) + 1) or not (out[0] if ring else out).is_contiguous() or
+        out.device != self.device):
+      raise ValueError(f"bind_ego_planes: out must be a uint8 tensor of shape {shape} or [T, {', '.join(map(str, shape))}] "
+                       f"with contiguous slots on {self.device}")
+    block = int(np.prod(shape))
+    T = int(out.shape[0]) if ring else 0
+    stride = (out.stride(0) if T > 1 else block) if ring else 0
+    ego_planes_request(self._L, self._h, MP_EGOPLANES_REGISTER, dst=out.data_ptr(),
+                       dst_bytes=(T - 1) * stride + block if ring else block, slot_stride=stride, slots=T,
+                       layer_mask=mask, classes=cls.data_ptr(), classes_len=int(cls.numel()), num_classes=C,
+                       facing=int(bool(facing)))
+    self._ego_planes = (out, cls)
     return out
 
   def counters(self) -> Dict[str, int]:

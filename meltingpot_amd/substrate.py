@@ -26,6 +26,7 @@ from __future__ import annotations
 
 import dataclasses
 import enum
+import fnmatch
 import math
 import os
 from typing import Any, Callable, Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple
@@ -331,7 +332,7 @@ class SubstrateStateLayout:
   """`Engine.state_layout()` plus the pack's names: `layer_names` in plane order (the L render
   planes), `state_names` by state id with `state_id(name)`, `state_layers[state]` (the plane a
   state lives in, -1: never on the map), `avatar_states[p]` = (alive_state, wait_state) of player p, `avatar_layer`, `hidden_planes` (the level's private planes behind
-  the render planes).  Every attribute of the engine's layout (H, W, L, P, nstates, grid_planes,
+  the render planes), `sprite_names` by sprite index.  Every attribute of the engine's layout (H, W, L, P, nstates, grid_planes,
   grid_pad, world_stride, fields, fingerprint, describe(), ...) is reachable here too."""
 
   def __init__(self, layout, tables):
@@ -339,6 +340,7 @@ class SubstrateStateLayout:
     split = lambda name: tuple(n.decode() for n in bytes(tables[name]).split(b"\0")[:-1])
     self.layer_names = split("layer_names")[:layout.L]
     self.state_names = split("state_names")[:layout.nstates]
+    self.sprite_names = split("sprite_names")   # (by sprite index: id i of "LAYER" shows sprite i - 1)
     self.state_layers = tuple(int(v) for v in tables["state_layer"][:layout.nstates])   # (-1: never on the map)
     alive = [int(v) for v in tables["avatar_alive_state"]]
     wait = [int(v) for v in tables["avatar_wait_state"]]
@@ -1274,6 +1276,89 @@ class Substrate:
     elif not isinstance(out, t.Tensor) or tuple(out.shape) != shape:
       raise ValueError(f"set_view_hashes: out must be an int64 device tensor of shape {shape}")
     return self._eng.bind_view_hash(out, layers=layers, classes=classes)
+
+  @property
+  def layer_id_names(self) -> Tuple[str, ...]:
+    """What every id of "LAYER" and "EGO_LAYER" shows: `num_layer_ids` strings, "" for id 0
+    (nothing) and the name of sprite i - 1 for id i ("OutOfBounds" is id 1, then "OutOfView",
+    "Avatar1", "Self", ...)."""
+    return self._eng.layer_id_names
+
+  def layer_classes(self, groups) -> np.ndarray:
+    """A class table by name: int32 [num_layer_ids], class c for every id that `groups[c]` names and
+    -1 for every other id — `classes` of `observe_ego_planes`, `set_ego_planes` and `hash_views`.
+    A group is a name of `layer_id_names`, an `fnmatch` pattern, or an iterable of those:
+      env.layer_classes(["Self", "Avatar*", "Beam*", "Wall*", "OutOfBounds"])
+    ValueError for a pattern that matches no id, and for an id two groups match."""
+    names = self.layer_id_names
+    table = np.full(len(names), -1, np.int32)
+    if isinstance(groups, str):
+      groups = (groups,)
+    for c, group in enumerate(groups):
+      for pattern in ((group,) if isinstance(group, str) else tuple(group)):
+        if not isinstance(pattern, str):
+          raise ValueError(f"layer_classes: {pattern!r} is no name or pattern")
+        ids = [i for i, n in enumerate(names) if n and fnmatch.fnmatchcase(n, pattern)]
+        if not ids:
+          raise ValueError(f"layer_classes: {pattern!r} matches no id of this level (layer_id_names: "
+                           f"{[n for n in names if n]})")
+        for i in ids:
+          if table[i] not in (-1, c):
+            raise ValueError(f"layer_classes: id {i} ({names[i]!r}) is matched by class {int(table[i])} and by "
+                             f"class {c} ({pattern!r})")
+          table[i] = c
+    return table
+
+  def observe_ego_planes(self, classes, states: Optional[WorldStates] = None, rows=None, players=None, layers=None,
+                         facing: bool = False, num_classes: Optional[int] = None):
+    """What a conv net reads of each player's view: uint8 [R, P, C', VH, VW] device tensor (or
+    [R, C', VH, VW] with `players`, R ints: player players[i] of row rows[i]) of 0/1 planes of its
+    "EGO_LAYER", channels first, in saved states or in this substrate's worlds as they are now
+    (`states` None; `rows` are then world indices), written from the records by one launch.
+    `classes`: `num_layer_ids` ints in [-1, C) mapping every "LAYER" id to a class
+    (`layer_classes(groups)` writes one by name); plane c is 1 where some counted layer of the cell
+    holds an id of class c; -1 sets nothing; C = `num_classes`, by default 1 + the largest entry, at
+    most 64.  `layers`: the layers that count, by name or index (None: all).  `facing`: four more
+    planes, C' = C + 4: plane C + d is 1 where a living avatar stands whose facing in the viewer's
+    frame, (ORIENTATION[q] - ORIENTATION[p]) & 3, is d — the viewer itself: d = 0 — and a dead
+    viewer's are 0.  `planes.view(R * P, C', VH, VW).half()` feeds a convolution.  Nothing of this
+    substrate changes; no host synchronisation with a device or numpy `classes` and `num_classes`."""
+    if not self._batched:
+      raise ValueError("observe_ego_planes needs a batched substrate (device tensors): build it with num_worlds > 1")
+    self._eng.use_current_stream()
+    layers = self._view_layers(layers)
+    if states is None:
+      return self._eng.observe_ego_planes(classes, None, rows=rows, players=players, layers=layers, facing=facing,
+                                          num_classes=num_classes)
+    if not isinstance(states, WorldStates):
+      raise ValueError("observe_ego_planes takes the WorldStates of save_state or step_many(states=True)")
+    states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
+    return self._eng.observe_ego_planes(classes, states.data, rows=rows, players=players, layers=layers,
+                                        facing=facing, num_classes=num_classes, fingerprint=states.fingerprint)
+
+  def set_ego_planes(self, classes, layers="all", facing: bool = False, out=None, num_classes: Optional[int] = None):
+    """Keeps `observe_ego_planes(classes, ...)` of the worlds current on the device: returns a uint8
+    [N, P, C', VH, VW] device tensor — [T, N, P, C', VH, VW] on a substrate built with
+    rollout_length=T — that one launch rewrites behind every reset, step, step_many and load_state,
+    in the ring slot the submission wrote.  `layers` ("all": every layer), `facing`, `num_classes`:
+    as `observe_ego_planes` takes them.  `set_ego_planes(None)` clears the registration: the
+    launches are then what they were.  There are no per-step rows in `step_many`: call
+    step_many(states=True) and observe_ego_planes(classes, result.states)."""
+    if not self._batched:
+      raise ValueError("set_ego_planes needs a batched substrate (device tensors): build it with num_worlds > 1")
+    self._eng.use_current_stream()
+    if classes is None:
+      self._eng.bind_ego_planes(None)
+      return None
+    layers = None if isinstance(layers, str) and layers == "all" else self._view_layers(layers)
+    t = self._eng._torch
+    cls, C = self._eng._plane_classes(classes, num_classes)
+    shape = ((self._T,) if self._T else ()) + self._eng.ego_planes_shape(C, facing)
+    if out is None:
+      out = t.zeros(shape, dtype=t.uint8, device=self._eng.device)
+    elif not isinstance(out, t.Tensor) or tuple(out.shape) != shape:
+      raise ValueError(f"set_ego_planes: out must be a uint8 device tensor of shape {shape}")
+    return self._eng.bind_ego_planes(out, cls, layers=layers, facing=facing, num_classes=C)
 
   def load_state(self, states: WorldStates, src, check: Optional[bool] = None) -> TimeStep:
     """World w continues from row src[w] of `states` (-1: world w is left as it is), as the
@@ -2326,6 +2411,63 @@ class MixtureSubstrate:
     out = t.zeros(((self._T,) if self._T else ()) + (self._N, self._P), dtype=t.int64, device=eng.device)
     for m, off, n in zip(self._members, self._offsets, self._counts):
       m.set_view_hashes(layers, classes, out=out[:, off:off + n] if self._T else out[off:off + n])
+    return out
+
+  def layer_classes(self, groups) -> List[np.ndarray]:
+    """`Substrate.layer_classes(groups)` of every member, in order: the members of a mixture may
+    number the same sprites differently, so a table by name is one table a member — what
+    `observe_ego_planes` and `set_ego_planes` of the mixture take as `classes`."""
+    return [m.layer_classes(groups) for m in self._members]
+
+  def _planes_of_members(self, classes, num_classes, facing):
+    """((VH, VW), C, a class table per member): a mixture's planes are one tensor, so the members
+    must agree on (VH, VW) and C.  `classes`: one table for every member, or a list of one a member."""
+    shapes = {m._eng.ego_layer_shape[2:4] for m in self._members}
+    if len(shapes) != 1:
+      raise ValueError(f"ego planes of a mixture: the members' views differ ({sorted(shapes)} as (VH, VW))")
+    t = self._members[0]._eng._torch
+    per_member = (isinstance(classes, (list, tuple)) and len(classes) > 0 and
+                  all(isinstance(c, (np.ndarray, t.Tensor, list, tuple)) for c in classes))
+    tables = list(classes) if per_member else [classes] * len(self._members)
+    if len(tables) != len(self._members):
+      raise ValueError(f"ego planes of a mixture: {len(tables)} class tables for {len(self._members)} members")
+    if num_classes is None:
+      num_classes = 1 + max(int(c.max()) if isinstance(c, t.Tensor) else int(np.max(np.asarray(c))) for c in tables)
+    return next(iter(shapes)), int(num_classes), tables
+
+  def observe_ego_planes(self, classes, layers=None, facing: bool = False, num_classes: Optional[int] = None):
+    """`Substrate.observe_ego_planes(classes)` of the worlds as they are now: ONE uint8
+    [N, P, C', VH, VW] device tensor of which every member writes its slice.  The members must agree
+    on (VH, VW); `classes` is one table for all of them, or a list of one table a member
+    (`layer_classes(groups)`: members may number the same sprites differently)."""
+    (VH, VW), C, tables = self._planes_of_members(classes, num_classes, facing)
+    eng = self._members[0]._eng
+    t = eng._torch
+    out = t.empty((self._N, self._P, C + (4 if facing else 0), VH, VW), dtype=t.uint8, device=eng.device)
+    for m, off, n, table in zip(self._members, self._offsets, self._counts, tables):
+      if not m._batched:
+        raise ValueError("observe_ego_planes needs batched members (device tensors)")
+      m._eng.use_current_stream()
+      m._eng.observe_ego_planes(table, None, layers=m._view_layers(layers), facing=facing, num_classes=C,
+                                out=out[off:off + n])
+    return out
+
+  def set_ego_planes(self, classes, layers="all", facing: bool = False, num_classes: Optional[int] = None):
+    """`Substrate.set_ego_planes` for the mixture: ONE uint8 [N, P, C', VH, VW] device tensor
+    ([T, N, P, C', VH, VW] with rollout_length=T) of which member i registers its slice in place.
+    `classes`: as `observe_ego_planes` of the mixture takes it.  None clears every member's
+    registration."""
+    if classes is None:
+      for m in self._members:
+        m.set_ego_planes(None)
+      return None
+    (VH, VW), C, tables = self._planes_of_members(classes, num_classes, facing)
+    eng = self._members[0]._eng
+    t = eng._torch
+    out = t.zeros(((self._T,) if self._T else ()) + (self._N, self._P, C + (4 if facing else 0), VH, VW),
+                  dtype=t.uint8, device=eng.device)
+    for m, off, n, table in zip(self._members, self._offsets, self._counts, tables):
+      m.set_ego_planes(table, layers, facing, out=out[:, off:off + n] if self._T else out[off:off + n], num_classes=C)
     return out
 
   def event_columns(self):
