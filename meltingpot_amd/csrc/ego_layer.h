@@ -52,12 +52,11 @@ inline Window window_of(const DevTables& t) {
   return g;
 }
 
-// EGO_LAYER's value at window cell (vx, vy), layer l of viewer p.  `planes`: the record's render
-// planes [L][H][W]; `head`: the head of its tail, ax[16] ay[16] aori[16] aalive[16]; `lut`:
-// StepOutputs::layer_lut [P][kLayerLutRow].  The world offset of a window cell follows the
-// renderer's table; a cell off the map, and every cell of a dead viewer (A6), is OutOfBounds.
-MP_EGO_HD inline int32_t value(const Window& g, const uint8_t* planes, const uint8_t* head, const int32_t* lut,
-                               uint32_t p, uint32_t vx, uint32_t vy, uint32_t l) {
+// The cell of the map that window cell (vx, vy) of viewer p lies over.  `head`: the head of the
+// record's tail, ax[16] ay[16] aori[16] aalive[16].  The world offset of a window cell follows the
+// renderer's table (the turned offset, the torus wrap).  false: (*cx, *cy) is off the map.
+MP_EGO_HD inline bool turned_cell(const Window& g, const uint8_t* head, uint32_t p, uint32_t vx, uint32_t vy, int* cx,
+                                  int* cy) {
   const int vo = head[2 * MP_MAX_PLAYERS + p];
   const int dx = (int)vx - g.vl, dy = (int)vy - g.vf;   // right, down in the view's frame
   const int ax = vo == 0 ? dx : vo == 1 ? -dy : vo == 2 ? -dx : dy;
@@ -72,6 +71,31 @@ MP_EGO_HD inline int32_t value(const Window& g, const uint8_t* planes, const uin
   } else {
     in = x >= 0 && x < g.W && y >= 0 && y < g.H;
   }
+  *cx = x;
+  *cy = y;
+  return in;
+}
+
+// The cell of the map under window cell (vx, vy) of viewer p.  false: the cell is off the map or
+// the viewer is dead (A6) — EGO_LAYER's OutOfBounds — and (*cx, *cy) is (0, 0), a cell that may be
+// read before the answer is looked at.
+MP_EGO_HD inline bool cell_of(const Window& g, const uint8_t* head, uint32_t p, uint32_t vx, uint32_t vy, int* cx,
+                              int* cy) {
+  int x, y;
+  bool in = turned_cell(g, head, p, vx, vy, &x, &y);
+  in = in && head[3 * MP_MAX_PLAYERS + p];
+  *cx = in ? x : 0;
+  *cy = in ? y : 0;
+  return in;
+}
+
+// EGO_LAYER's value at window cell (vx, vy), layer l of viewer p.  `planes`: the record's render
+// planes [L][H][W]; `head`: as turned_cell's; `lut`: StepOutputs::layer_lut [P][kLayerLutRow].
+// A cell off the map, and every cell of a dead viewer, is OutOfBounds.
+MP_EGO_HD inline int32_t value(const Window& g, const uint8_t* planes, const uint8_t* head, const int32_t* lut,
+                               uint32_t p, uint32_t vx, uint32_t vy, uint32_t l) {
+  int x, y;
+  const bool in = turned_cell(g, head, p, vx, vy, &x, &y);
   const int s = in && head[3 * MP_MAX_PLAYERS + p] ? (int)planes[(int)l * g.HW + y * g.W + x] : 256;
   return lut[p * (uint32_t)kLayerLutRow + (uint32_t)s];
 }

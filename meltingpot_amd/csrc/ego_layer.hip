@@ -1,53 +1,33 @@
 // ego_layer.hip — EGO_LAYER (an MpEgoLayer request, include/mp_engine.h): the layer view in the
 // avatar's own frame, drawn from records where they lie — bank rows or the engine's worlds.  No
-// world is loaded, nothing of the engine's is written.  A unit of its own: k_frame, the step
-// kernels, state_obs.hip and state_view.hip compile to exactly what they compiled to before.
+// world is loaded, nothing of the engine's is written.  One of the three units of view_unit.h,
+// which has what they share: the staged record, the report of a skipped rows[] / players[]
+// index, the launch plan.
 //
 //   k_ego_layer_rows    every viewer of a row: one wave per row, the row's contiguous
 //                       [P][VH][VW][L] block (the registered leaf; a draw without players);
 //   k_ego_layer_views   one viewer of a row: one wave per (row, player), its [VH][VW][L] block.
-// Both are one body.  The wave stages what the value function reads of its record in LDS — the
-// render planes and the head of the tail (positions, orientations, who is alive), 16-byte loads,
-// eight of a lane in flight (state_view.hip, step_load.h) — and writes its block with
-// write_layer's store scheme (step_common.h): up to three dwords before the block's first 16-byte
-// boundary, 16-byte lane-contiguous chunks with four of a lane's values worked out before the
-// first store, then up to three dwords.  A dword's (viewer, window cell, layer) is split from its
-// index with magic_of / div_by; its value is ego_layer::value (ego_layer.h).  The 1 KB-a-viewer
-// value table is read from global memory and stays in the caches, as write_layer reads it.
-// An index of rows[] that is no row or of players[] outside [0, P) is never used as one: its
-// element of the destination stays as it was — every such element — and ONE of them is reported
-// through the fault words (FAULT_STATE_INDEX; the first to claim them).
-#include <stddef.h>
-
-#include "step_common.h"
-#include "ego_layer.h"
+// Both are one body.  The wave writes its block with write_layer's store scheme (step_common.h):
+// up to three dwords before the block's first 16-byte boundary, 16-byte lane-contiguous chunks
+// with four of a lane's values worked out before the first store, then up to three dwords.  A
+// dword's (viewer, window cell, layer) is split from its index with magic_of / div_by; its value
+// is ego_layer::value (ego_layer.h).  The 1 KB-a-viewer value table is read from global memory and
+// stays in the caches, as write_layer reads it.
+#include "view_unit.h"
 
 namespace ego_layer {
 
 namespace {
 
 using stepk::div_by;
-using stepk::issued;
 using stepk::magic_of;
 using stepk::wsync;
+using view_unit::kHead;
+using view_unit::kMaxWaves;
+using view_unit::planes_vec;
 
-constexpr int kLdsMax = 160 * 1024;
-constexpr int kMaxWaves = 16;
-constexpr int kHead = 4 * MP_MAX_PLAYERS;   // ax, ay, aori, aalive
-static_assert(offsetof(WorldTail, ax) == 0 && offsetof(WorldTail, ay) == MP_MAX_PLAYERS &&
-                  offsetof(WorldTail, aori) == 2 * MP_MAX_PLAYERS && offsetof(WorldTail, aalive) == 3 * MP_MAX_PLAYERS,
-              "the staged head of the tail is ax, ay, aori, aalive");
-
-// a wave's LDS: the render planes in whole 16-byte vectors, then the head
-__host__ __device__ inline int planes_vec(const Window& g) { return (g.L * g.HW + 15) >> 4; }
+// a wave's LDS: the render planes, then the head
 __host__ __device__ inline int per_wave(const Window& g) { return planes_vec(g) * 16 + kHead; }
-
-__device__ inline void report_index(uint32_t* fault, int lane, int at, int index, uint32_t what) {
-  if (lane == 0 && atomicCAS(&fault[FAULT_STATE_INDEX], 0u, (uint32_t)at + 1u) == 0u) {
-    fault[FAULT_STATE_INDEX + 1] = (uint32_t)index;
-    fault[FAULT_STATE_INDEX + 2] = what;
-  }
-}
 
 template <bool kAll>
 __device__ inline void ego_body(const Args& a, uint8_t* smem) {
@@ -64,35 +44,15 @@ __device__ inline void ego_body(const Args& a, uint8_t* smem) {
 
   for (int i = (int)blockIdx.x * waves + wave; i < a.count; i += (int)gridDim.x * waves) {
     const int r = __builtin_amdgcn_readfirstlane(a.rows ? a.rows[i] : i);
-    if (r < 0 || r >= a.src_rows) { report_index(a.fault, lane, i, r, kFaultEgoRow); continue; }
+    if (r < 0 || r >= a.src_rows) { view_unit::report_index(a.fault, lane, i, r, kFaultEgoRow); continue; }
     uint32_t p0 = 0u;
     if constexpr (!kAll) {
       const int p = __builtin_amdgcn_readfirstlane(a.players[i]);
-      if (p < 0 || p >= g.P) { report_index(a.fault, lane, i, p, kFaultEgoPlayer); continue; }
+      if (p < 0 || p >= g.P) { view_unit::report_index(a.fault, lane, i, p, kFaultEgoPlayer); continue; }
       p0 = (uint32_t)p;
     }
     wsync();   // (the element before this one has left the wave's LDS)
-    {
-      const uint4* src = reinterpret_cast<const uint4*>(a.src + (size_t)r * (size_t)a.stride);
-      uint4* out = reinterpret_cast<uint4*>(planes);
-      const uint4 hv = lane < kHead / 16 ? src[(a.grid_pad >> 4) + lane] : uint4{0u, 0u, 0u, 0u};
-      for (int i0 = 0; i0 < nvec; i0 += 8 * 64) {
-        uint4 v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const int j = i0 + k * 64 + lane;
-          v[k] = src[j < nvec ? j : nvec - 1];
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) issued(v[k]);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const int j = i0 + k * 64 + lane;
-          if (j < nvec) out[j] = v[k];
-        }
-      }
-      if (lane < kHead / 16) reinterpret_cast<uint4*>(head)[lane] = hv;
-    }
+    view_unit::stage_record(a.src + (size_t)r * (size_t)a.stride, a.grid_pad, nvec, lane, planes, head);
     wsync();
 
     auto val = [&](uint32_t e) -> int32_t {
@@ -138,62 +98,25 @@ __global__ __launch_bounds__(kMaxWaves * 64) void k_ego_layer_views(Args a) {
   ego_body<false>(a, smem);
 }
 
-Plan plan_of(const Window& g, int count, int num_cus) {
-  Plan p = {};
-  const int per = per_wave(g);
-  int fit = kLdsMax / per;
-  if (fit < 1) { p.lds = per; return p; }
-  if (fit > kMaxWaves) fit = kMaxWaves;
-  // every CU a workgroup before a workgroup gets more waves
-  const int cus = num_cus > 0 ? num_cus : 1;
-  int waves = (count + cus - 1) / cus;
-  if (waves < 4) waves = 4;
-  if (waves > fit) waves = fit;
-  if (waves > count) waves = count;
-  p.waves = waves;
-  p.groups = (count + waves - 1) / waves;
-  if (p.groups > 2 * cus) p.groups = 2 * cus;   // (a wave then draws several elements in turn)
-  p.lds = waves * per;
-  return p;
-}
+Plan plan_of(const Window& g, int count, int num_cus) { return view_unit::plan_of(0, per_wave(g), count, num_cus); }
 
 void launch(const Args& a, const Plan& p, hipStream_t stream) {
-  if (a.players)
-    hipLaunchKernelGGL(k_ego_layer_views, dim3((unsigned)p.groups), dim3((unsigned)p.waves * 64u), (size_t)p.lds,
-                       stream, a);
-  else
-    hipLaunchKernelGGL(k_ego_layer_rows, dim3((unsigned)p.groups), dim3((unsigned)p.waves * 64u), (size_t)p.lds,
-                       stream, a);
+  view_unit::launch(k_ego_layer_rows, k_ego_layer_views, a, p, stream);
 }
 
-int prepare() {
-  const void* k[2] = {reinterpret_cast<const void*>(&k_ego_layer_rows),
-                      reinterpret_cast<const void*>(&k_ego_layer_views)};
-  for (const void* f : k) {
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
-}
+int prepare() { return view_unit::prepare(k_ego_layer_rows, k_ego_layer_views); }
 
 int host(const Args& a, uint32_t* what) {
   const Window& g = a.g;
   const size_t per = (size_t)g.VH * g.VW * g.L;
-  for (int i = 0; i < a.count; ++i) {
-    const int r = a.rows ? a.rows[i] : i;
-    if (r < 0 || r >= a.src_rows) { *what = kFaultEgoRow; return i; }
-    const int p = a.players ? a.players[i] : 0;
-    if (p < 0 || p >= g.P) { *what = kFaultEgoPlayer; return i; }
-    const uint8_t* rec = a.src + (size_t)r * (size_t)a.stride;
-    const int np = a.players ? 1 : g.P;
-    int32_t* blk = a.dst + (size_t)i * np * per;
-    for (int q = 0; q < np; ++q)
-      for (int vy = 0; vy < g.VH; ++vy)
-        for (int vx = 0; vx < g.VW; ++vx)
-          for (int l = 0; l < g.L; ++l)
-            *blk++ = value(g, rec, rec + a.grid_pad, a.lut, (uint32_t)(p + q), (uint32_t)vx, (uint32_t)vy, (uint32_t)l);
-  }
-  return -1;
+  return view_unit::host_each(a, kFaultEgoRow, kFaultEgoPlayer, what,
+                              [&](int i, const uint8_t* rec, uint32_t p, int q, int np) {
+    int32_t* blk = a.dst + ((size_t)i * np + q) * per;
+    for (int vy = 0; vy < g.VH; ++vy)
+      for (int vx = 0; vx < g.VW; ++vx)
+        for (int l = 0; l < g.L; ++l)
+          *blk++ = value(g, rec, rec + a.grid_pad, a.lut, p, (uint32_t)vx, (uint32_t)vy, (uint32_t)l);
+  });
 }
 
 }  // namespace ego_layer

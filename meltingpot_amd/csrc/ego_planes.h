@@ -39,30 +39,7 @@ MP_EGO_HD inline int32_t class_of(int32_t entry, int32_t num_classes) {
   return (uint32_t)entry < (uint32_t)num_classes ? entry : -1;
 }
 
-// The cell of the map under window cell (vx, vy) of viewer p, found exactly as ego_layer::value
-// finds it (the turned offset, the torus wrap).  false: the cell is off the map or the viewer is
-// dead — EGO_LAYER's OutOfBounds — and (*cx, *cy) is (0, 0).
-MP_EGO_HD inline bool cell_of(const Window& g, const uint8_t* head, uint32_t p, uint32_t vx, uint32_t vy, int* cx,
-                              int* cy) {
-  const int vo = head[2 * MP_MAX_PLAYERS + p];
-  const int dx = (int)vx - g.vl, dy = (int)vy - g.vf;   // right, down in the view's frame
-  const int ax = vo == 0 ? dx : vo == 1 ? -dy : vo == 2 ? -dx : dy;
-  const int ay = vo == 0 ? dy : vo == 1 ? dx : vo == 2 ? -dy : -dx;
-  int x = (int)head[p] + ax, y = (int)head[MP_MAX_PLAYERS + p] + ay;
-  bool in;
-  if (g.torus) {
-    const uint32_t xx = (uint32_t)(x + g.ox), yy = (uint32_t)(y + g.oy);
-    x = (int)(xx - ego_layer::divm(xx, g.mW) * (uint32_t)g.W);
-    y = (int)(yy - ego_layer::divm(yy, g.mH) * (uint32_t)g.H);
-    in = true;
-  } else {
-    in = x >= 0 && x < g.W && y >= 0 && y < g.H;
-  }
-  in = in && head[3 * MP_MAX_PLAYERS + p];
-  *cx = in ? x : 0;
-  *cy = in ? y : 0;
-  return in;
-}
+using ego_layer::cell_of;
 
 // The classes of window cell (vx, vy) of viewer p: bit c is set iff a layer of `layer_mask` (never
 // 0 here: "every layer" is all ones) holds an id of class c.  `table`: the viewers' value tables
@@ -124,9 +101,7 @@ inline int planes_of(const Args& a) { return a.num_classes + (a.facing ? 4 : 0);
 // Geometry of a launch: waves a workgroup (one element each at a time), workgroups, dynamic LDS
 // (the workgroup's folded value tables, then every wave's render planes, head and bit planes).
 // waves == 0: the tables and one wave's share do not fit the LDS (`lds` = what they would take).
-struct Plan {
-  int32_t waves, groups, lds;
-};
+using ego_layer::Plan;
 Plan plan_of(const Window& g, int num_planes, int count, int num_cus);
 
 // k_ego_planes_rows (players == NULL) or k_ego_planes_views, on `stream`.

@@ -1,17 +1,16 @@
 // ego_planes.hip — class-indicator feature planes of a player's view (an MpEgoPlanes request,
 // include/mp_engine.h; ego_planes.h has the functions): uint8 [C'][VH][VW] of every viewer of bank
 // rows or of the engine's worlds, written from the records where they lie.  No int32 view is
-// drawn, no world is loaded, nothing of the engine's is written.  A unit of its own: ego_layer.hip,
-// view_hash.hip, the frame and the step kernels compile to exactly what they compiled to before.
+// drawn, no world is loaded, nothing of the engine's is written.  One of the three units of
+// view_unit.h, which has what they share: the staged record, the report of a skipped rows[] /
+// players[] index, the launch plan.
 //
 //   k_ego_planes_rows    every viewer of a row: one wave per row, the row's [P][C'][VH][VW] block
 //                        (the registered tensor; a draw without players);
 //   k_ego_planes_views   one viewer of a row: one wave per (row, player), its [C'][VH][VW] block.
-// Both are one body, modelled on view_hash.hip's.  The workgroup folds the class table into the
-// viewers' value tables in LDS once (class_of(classes[lut[p][s]]): a word's class then costs the
-// one LDS read that finds its id).  A wave stages what the value function reads of its record in
-// its share of the LDS — the render planes and the head of the tail, 16-byte loads, eight of a
-// lane in flight.  Then, a viewer at a time:
+// Both are one body.  The workgroup folds the class table into the viewers' value tables in LDS
+// once (class_of(classes[lut[p][s]]): a word's class then costs the one LDS read that finds its
+// id).  Then, a viewer of the wave's staged record at a time:
 //   cells   lane i owns window cells i, i + 64, ...: it ORs 1 << class over the counted layers
 //           into one u64 (ego_planes::cell_classes) and, with `facing`, finds the cell's avatars
 //           in the P head entries (cell_facing): a nibble.
@@ -25,13 +24,11 @@
 //           dword ((x * 0x00204081) & 0x01010101 for four bits).  Neighbouring lanes read the same
 //           or neighbouring dwords: no bank conflicts.  Byte stores run up to the block's first
 //           16-byte boundary and behind its last; no byte outside the block is written.
-// An index of rows[] that is no row or of players[] outside [0, P) is never used as one: its
-// element of the destination stays as it was — every such element — and ONE of them is reported
-// through the fault words (FAULT_STATE_INDEX; the first to claim them).  An entry of the class
-// table outside [-1, num_classes) counts as -1 and is reported the same way.
-#include <stddef.h>
+// An entry of the class table outside [-1, num_classes) counts as -1 and is reported as a skipped
+// index is (view_unit.h).
+#include <vector>
 
-#include "step_common.h"
+#include "view_unit.h"
 #include "ego_planes.h"
 
 namespace ego_planes {
@@ -39,32 +36,20 @@ namespace ego_planes {
 namespace {
 
 using stepk::div_by;
-using stepk::issued;
 using stepk::magic_of;
 using stepk::wsync;
+using view_unit::kHead;
+using view_unit::kMaxWaves;
+using view_unit::planes_vec;
+using view_unit::tables_bytes;
 
-constexpr int kLdsMax = 160 * 1024;
-constexpr int kMaxWaves = 16;
-constexpr int kHead = 4 * MP_MAX_PLAYERS;   // ax, ay, aori, aalive
-static_assert(offsetof(WorldTail, ax) == 0 && offsetof(WorldTail, ay) == MP_MAX_PLAYERS &&
-                  offsetof(WorldTail, aori) == 2 * MP_MAX_PLAYERS && offsetof(WorldTail, aalive) == 3 * MP_MAX_PLAYERS,
-              "the staged head of the tail is ax, ay, aori, aalive");
 static_assert(kMaxClasses == 64, "lane c of a wave keeps class plane c's ballot");
 
-// the workgroup's folded value tables in whole 16-byte vectors; a wave's LDS: the render planes in
-// whole 16-byte vectors, the head, then `np` bit planes of words64() u64 (in whole vectors too)
-__host__ __device__ inline int tables_bytes(const Window& g) { return ((g.P * kLayerLutRow * 4 + 15) >> 4) * 16; }
-__host__ __device__ inline int planes_vec(const Window& g) { return (g.L * g.HW + 15) >> 4; }
+// a wave's LDS, behind the workgroup's folded value tables: the render planes, the head, then `np`
+// bit planes of words64() u64 (in whole 16-byte vectors too)
 __host__ __device__ inline int words64(const Window& g) { return (g.VH * g.VW + 63) >> 6; }
 __host__ __device__ inline int per_wave(const Window& g, int np) {
   return planes_vec(g) * 16 + kHead + ((np * words64(g) * 8 + 15) >> 4) * 16;
-}
-
-__device__ inline void report(uint32_t* fault, int at, int index, uint32_t what) {
-  if (atomicCAS(&fault[FAULT_STATE_INDEX], 0u, (uint32_t)at + 1u) == 0u) {
-    fault[FAULT_STATE_INDEX + 1] = (uint32_t)index;
-    fault[FAULT_STATE_INDEX + 2] = what;
-  }
 }
 
 // four bits -> four bytes of 0 / 1, bit 0 in the lowest byte
@@ -86,7 +71,7 @@ __device__ inline void planes_body(const Args& a, uint8_t* smem) {
   if (blockIdx.x == 0)   // the caller's table may hold anything: one entry out of range is reported
     for (int j = tid; j < a.num_ids; j += (int)blockDim.x) {
       const int32_t c = a.classes[j];
-      if (c < -1 || c >= a.num_classes) report(a.fault, j, c, kFaultEgoPlanesClass);
+      if (c < -1 || c >= a.num_classes) view_unit::report(a.fault, j, c, kFaultEgoPlanesClass);
     }
   __syncthreads();   // (every thread of the workgroup meets it: before the element loop)
   smem += tables_bytes(g);
@@ -117,41 +102,15 @@ __device__ inline void planes_body(const Args& a, uint8_t* smem) {
 
   for (int i = (int)blockIdx.x * waves + wave; i < a.count; i += (int)gridDim.x * waves) {
     const int r = __builtin_amdgcn_readfirstlane(a.rows ? a.rows[i] : i);
-    if (r < 0 || r >= a.src_rows) {
-      if (lane == 0) report(a.fault, i, r, kFaultEgoPlanesRow);
-      continue;
-    }
+    if (r < 0 || r >= a.src_rows) { view_unit::report_index(a.fault, lane, i, r, kFaultEgoPlanesRow); continue; }
     uint32_t p0 = 0u;
     if constexpr (!kAll) {
       const int p = __builtin_amdgcn_readfirstlane(a.players[i]);
-      if (p < 0 || p >= g.P) {
-        if (lane == 0) report(a.fault, i, p, kFaultEgoPlanesPlayer);
-        continue;
-      }
+      if (p < 0 || p >= g.P) { view_unit::report_index(a.fault, lane, i, p, kFaultEgoPlanesPlayer); continue; }
       p0 = (uint32_t)p;
     }
     wsync();   // (the element before this one has left the wave's LDS)
-    {
-      const uint4* src = reinterpret_cast<const uint4*>(a.src + (size_t)r * (size_t)a.stride);
-      uint4* out = reinterpret_cast<uint4*>(planes);
-      const uint4 hv = lane < kHead / 16 ? src[(a.grid_pad >> 4) + lane] : uint4{0u, 0u, 0u, 0u};
-      for (int i0 = 0; i0 < nvec; i0 += 8 * 64) {
-        uint4 v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const int j = i0 + k * 64 + lane;
-          v[k] = src[j < nvec ? j : nvec - 1];
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) issued(v[k]);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const int j = i0 + k * 64 + lane;
-          if (j < nvec) out[j] = v[k];
-        }
-      }
-      if (lane < kHead / 16) reinterpret_cast<uint4*>(head)[lane] = hv;
-    }
+    view_unit::stage_record(a.src + (size_t)r * (size_t)a.stride, a.grid_pad, nvec, lane, planes, head);
 
     const uint32_t np = kAll ? P : 1u;
     for (uint32_t q = 0; q < np; ++q) {
@@ -211,78 +170,40 @@ __global__ __launch_bounds__(kMaxWaves * 64) void k_ego_planes_views(Args a) {
 }
 
 Plan plan_of(const Window& g, int num_planes, int count, int num_cus) {
-  Plan p = {};
-  const int per = per_wave(g, num_planes), cls = tables_bytes(g);
-  int fit = cls < kLdsMax ? (kLdsMax - cls) / per : 0;
-  if (fit < 1) { p.lds = cls + per; return p; }
-  if (fit > kMaxWaves) fit = kMaxWaves;
-  // every CU a workgroup before a workgroup gets more waves
-  const int cus = num_cus > 0 ? num_cus : 1;
-  int waves = (count + cus - 1) / cus;
-  if (waves < 4) waves = 4;
-  if (waves > fit) waves = fit;
-  if (waves > count) waves = count;
-  p.waves = waves;
-  p.groups = (count + waves - 1) / waves;
-  if (p.groups > 2 * cus) p.groups = 2 * cus;   // (a wave then writes several elements in turn)
-  p.lds = cls + waves * per;
-  return p;
+  return view_unit::plan_of(tables_bytes(g), per_wave(g, num_planes), count, num_cus);
 }
 
 void launch(const Args& a, const Plan& p, hipStream_t stream) {
-  if (a.players)
-    hipLaunchKernelGGL(k_ego_planes_views, dim3((unsigned)p.groups), dim3((unsigned)p.waves * 64u), (size_t)p.lds,
-                       stream, a);
-  else
-    hipLaunchKernelGGL(k_ego_planes_rows, dim3((unsigned)p.groups), dim3((unsigned)p.waves * 64u), (size_t)p.lds,
-                       stream, a);
+  view_unit::launch(k_ego_planes_rows, k_ego_planes_views, a, p, stream);
 }
 
-int prepare() {
-  const void* k[2] = {reinterpret_cast<const void*>(&k_ego_planes_rows),
-                      reinterpret_cast<const void*>(&k_ego_planes_views)};
-  for (const void* f : k) {
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
-}
+int prepare() { return view_unit::prepare(k_ego_planes_rows, k_ego_planes_views); }
 
 int host(const Args& a, uint32_t* what) {
   const Window& g = a.g;
   const int C = a.num_classes;
   const size_t cells = (size_t)g.VH * g.VW, n = (size_t)planes_of(a) * cells;
   // the folded value tables, as the workgroup builds them
-  int32_t* table = new int32_t[(size_t)g.P * kLayerLutRow];
+  std::vector<int32_t> table((size_t)g.P * kLayerLutRow);
   for (int j = 0; j < g.P * kLayerLutRow; ++j) {
     const int32_t id = a.lut[j];
     table[j] = (uint32_t)id < (uint32_t)a.num_ids ? class_of(a.classes[id], C) : -1;
   }
-  int bad = -1;
-  for (int i = 0; i < a.count && bad < 0; ++i) {
-    const int r = a.rows ? a.rows[i] : i;
-    if (r < 0 || r >= a.src_rows) { *what = kFaultEgoPlanesRow; bad = i; break; }
-    const int p = a.players ? a.players[i] : 0;
-    if (p < 0 || p >= g.P) { *what = kFaultEgoPlanesPlayer; bad = i; break; }
-    const uint8_t* rec = a.src + (size_t)r * (size_t)a.stride;
-    const int np = a.players ? 1 : g.P;
-    for (int q = 0; q < np; ++q) {
-      uint8_t* blk = a.dst + ((size_t)i * np + q) * n;
-      for (int vy = 0; vy < g.VH; ++vy)
-        for (int vx = 0; vx < g.VW; ++vx) {
-          const size_t cell = (size_t)vy * g.VW + vx;
-          const uint64_t m = cell_classes(g, rec, rec + a.grid_pad, table, a.layer_mask, (uint32_t)(p + q),
-                                          (uint32_t)vx, (uint32_t)vy);
-          for (int c = 0; c < C; ++c) blk[(size_t)c * cells + cell] = (uint8_t)((m >> c) & 1u);
-          if (a.facing) {
-            const uint32_t f = cell_facing(g, rec + a.grid_pad, (uint32_t)(p + q), (uint32_t)vx, (uint32_t)vy);
-            for (int d = 0; d < 4; ++d) blk[(size_t)(C + d) * cells + cell] = (uint8_t)((f >> d) & 1u);
-          }
+  return view_unit::host_each(a, kFaultEgoPlanesRow, kFaultEgoPlanesPlayer, what,
+                              [&](int i, const uint8_t* rec, uint32_t p, int q, int np) {
+    uint8_t* blk = a.dst + ((size_t)i * np + q) * n;
+    for (int vy = 0; vy < g.VH; ++vy)
+      for (int vx = 0; vx < g.VW; ++vx) {
+        const size_t cell = (size_t)vy * g.VW + vx;
+        const uint64_t m = cell_classes(g, rec, rec + a.grid_pad, table.data(), a.layer_mask, p, (uint32_t)vx,
+                                        (uint32_t)vy);
+        for (int c = 0; c < C; ++c) blk[(size_t)c * cells + cell] = (uint8_t)((m >> c) & 1u);
+        if (a.facing) {
+          const uint32_t f = cell_facing(g, rec + a.grid_pad, p, (uint32_t)vx, (uint32_t)vy);
+          for (int d = 0; d < 4; ++d) blk[(size_t)(C + d) * cells + cell] = (uint8_t)((f >> d) & 1u);
         }
-    }
-  }
-  delete[] table;
-  return bad;
+      }
+  });
 }
 
 }  // namespace ego_planes

@@ -179,33 +179,25 @@ struct MpEngine {
   episode_stats::Banks stats{};
   bool has_stats = false, stats_hold = false;
   bool folding() const { return has_stats && !stats_hold; }
-  // The registered EGO_LAYER leaf (an MpEgoLayer request; ego_layer.h): while set, every submission
-  // is followed by one launch that redraws every world's view.  ego_slots > 0: a ring, slot s at
-  // ego_dst + s * ego_stride bytes.  mp_tune's probes do not write it (ring_hold, layer_hold).
-  int32_t* ego_dst = nullptr;
-  uint64_t ego_stride = 0;
-  int ego_slots = 0;
-  bool drawing_ego() const { return ego_dst && !ring_hold && !layer_hold; }
-  // The registered view hashes (an MpViewHash request; view_hash.h): while set, every submission is
-  // followed by one launch that rewrites every viewer's hash, u64 [N][P].  vh_slots > 0: a ring,
-  // slot s at vh_dst + s * vh_stride bytes.  vh_classes: the caller's device table or NULL.
-  // mp_tune's probes do not write it.
-  uint64_t* vh_dst = nullptr;
-  uint64_t vh_stride = 0, vh_mask = 0;
-  int vh_slots = 0;
-  const int32_t* vh_classes = nullptr;
+  // A registered tensor of every viewer's window: while `dst` is set, every submission is followed
+  // by one launch that rewrites it from the records the submission left.  slots > 0: a ring, slot
+  // s at dst + s * stride bytes.  mask, classes (the caller's device table), num_classes, facing:
+  // what the unit has of them.
+  struct ViewRegistration {
+    void* dst = nullptr;
+    uint64_t stride = 0, mask = 0;
+    int slots = 0;
+    const int32_t* classes = nullptr;
+    int32_t num_classes = 0, facing = 0;
+    void* slot(int s) const { return slots > 0 ? (uint8_t*)dst + (uint64_t)(s % slots) * stride : dst; }
+  };
+  // ego: the EGO_LAYER leaf, int32 [N][P][VH][VW][L] (an MpEgoLayer request; ego_layer.h); vh: the
+  // view hashes, u64 [N][P] (MpViewHash; view_hash.h); ep: the class and facing planes, uint8
+  // [N][P][C'][VH][VW] (MpEgoPlanes; ego_planes.h).  mp_tune's probes write none of them
+  // (ring_hold, layer_hold).
+  ViewRegistration ego, vh, ep;
   int32_t num_layer_ids = 0;   // 1 + the largest id of d_layer_lut: the length of a class table
-  bool hashing_views() const { return vh_dst && !ring_hold && !layer_hold; }
-  // The registered class and facing planes (an MpEgoPlanes request; ego_planes.h): while set, every
-  // submission is followed by one launch that rewrites every viewer's planes, uint8
-  // [N][P][C'][VH][VW].  ep_slots > 0: a ring, slot s at ep_dst + s * ep_stride bytes.  ep_classes:
-  // the caller's device table.  mp_tune's probes do not write it.
-  uint8_t* ep_dst = nullptr;
-  uint64_t ep_stride = 0, ep_mask = 0;
-  int ep_slots = 0;
-  const int32_t* ep_classes = nullptr;
-  int32_t ep_num_classes = 0, ep_facing = 0;
-  bool drawing_planes() const { return ep_dst && !ring_hold && !layer_hold; }
+  bool viewing(const ViewRegistration& v) const { return v.dst && !ring_hold && !layer_hold; }
   // The engine's choice (MpConfig.unfused = 0): one launch, always.  (Round 2 drew
   // views under 64 KB a world — the two-player games — in a second launch: a CU
   // then has 64 worlds to step for 2 us of drawing each, and with 4-8 feeders the
@@ -573,46 +565,37 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
     launch_episode_stats(e->stats_cols, e->stats, r, false, e->stream);
     HIP_TRY(hipGetLastError());
   }
-  if (e->drawing_ego()) {
-    // the EGO_LAYER launch: every world's view, redrawn from the records this submission left
+  // the registered views: every world's, rewritten from the records this submission left
+  if (!e->viewing(e->ego) && !e->viewing(e->vh) && !e->viewing(e->ep)) return MP_OK;
+  const ego_layer::Window g = ego_layer::window_of(e->t);
+  auto worlds = [&](auto* a, const MpEngine::ViewRegistration& v) {   // what the three launches share
+    a->g = g;
+    a->src = e->d_state; a->src_rows = e->N; a->count = e->N;
+    a->stride = e->t.world_stride; a->grid_pad = e->t.grid_pad;
+    a->dst = static_cast<decltype(a->dst)>(v.slot(slot));
+    a->lut = e->d_layer_lut; a->fault = e->t.fault;
+  };
+  if (e->viewing(e->ego)) {   // EGO_LAYER
     ego_layer::Args a = {};
-    a.g = ego_layer::window_of(e->t);
-    a.src = e->d_state; a.src_rows = e->N; a.count = e->N;
-    a.stride = e->t.world_stride; a.grid_pad = e->t.grid_pad;
-    a.dst = e->ego_slots > 0
-                ? (int32_t*)((uint8_t*)e->ego_dst + (uint64_t)(slot % e->ego_slots) * e->ego_stride)
-                : e->ego_dst;
-    a.lut = e->d_layer_lut; a.fault = e->t.fault;
-    ego_layer::launch(a, ego_layer::plan_of(a.g, e->N, e->num_cus), e->stream);
+    worlds(&a, e->ego);
+    ego_layer::launch(a, ego_layer::plan_of(g, e->N, e->num_cus), e->stream);
     HIP_TRY(hipGetLastError());
   }
-  if (e->hashing_views()) {
-    // the view-hash launch: every viewer's hash, from the records this submission left
+  if (e->viewing(e->vh)) {   // every viewer's hash
     view_hash::Args a = {};
-    a.g = ego_layer::window_of(e->t);
-    a.src = e->d_state; a.src_rows = e->N; a.count = e->N;
-    a.stride = e->t.world_stride; a.grid_pad = e->t.grid_pad;
-    a.dst = e->vh_slots > 0
-                ? (uint64_t*)((uint8_t*)e->vh_dst + (uint64_t)(slot % e->vh_slots) * e->vh_stride)
-                : e->vh_dst;
-    a.lut = e->d_layer_lut; a.fault = e->t.fault;
-    a.layer_mask = e->vh_mask;
-    a.classes = e->vh_classes; a.num_classes = e->vh_classes ? e->num_layer_ids : 0;
-    view_hash::launch(a, view_hash::plan_of(a.g, e->N, e->num_cus), e->stream);
+    worlds(&a, e->vh);
+    a.layer_mask = e->vh.mask;
+    a.classes = e->vh.classes; a.num_classes = e->vh.classes ? e->num_layer_ids : 0;
+    view_hash::launch(a, view_hash::plan_of(g, e->N, e->num_cus), e->stream);
     HIP_TRY(hipGetLastError());
   }
-  if (e->drawing_planes()) {
-    // the planes launch: every viewer's class and facing planes, from the records this submission left
+  if (e->viewing(e->ep)) {   // every viewer's class and facing planes
     ego_planes::Args a = {};
-    a.g = ego_layer::window_of(e->t);
-    a.src = e->d_state; a.src_rows = e->N; a.count = e->N;
-    a.stride = e->t.world_stride; a.grid_pad = e->t.grid_pad;
-    a.dst = e->ep_slots > 0 ? e->ep_dst + (uint64_t)(slot % e->ep_slots) * e->ep_stride : e->ep_dst;
-    a.lut = e->d_layer_lut; a.fault = e->t.fault;
-    a.layer_mask = e->ep_mask;
-    a.classes = e->ep_classes; a.num_ids = e->num_layer_ids;
-    a.num_classes = e->ep_num_classes; a.facing = e->ep_facing;
-    ego_planes::launch(a, ego_planes::plan_of(a.g, ego_planes::planes_of(a), e->N, e->num_cus), e->stream);
+    worlds(&a, e->ep);
+    a.layer_mask = e->ep.mask;
+    a.classes = e->ep.classes; a.num_ids = e->num_layer_ids;
+    a.num_classes = e->ep.num_classes; a.facing = e->ep.facing;
+    ego_planes::launch(a, ego_planes::plan_of(g, ego_planes::planes_of(a), e->N, e->num_cus), e->stream);
     HIP_TRY(hipGetLastError());
   }
   return MP_OK;
@@ -1078,11 +1061,9 @@ int build_atlas(MpEngine* e, const MpDevOptions* dev, const DecodedPack& d) {
 // "N.LAYER"'s value of every (viewer, record byte) — what k_layer_view looks up per dword:
 // 1 + the viewer's remapped sprite of the state, 0 for state 0 and states without a sprite
 // (and bytes no state has); [256]: OutOfBounds (sprite 0), what an off-grid viewer sees.
-int upload_layer_lut(MpEngine* e) {
-  const DevTables& t = e->t;
-  const void* hp = e->pack.data();
-  const int32_t* ssprite = table<int32_t>(hp, "state_sprite");
-  const int32_t* vmap = table<int32_t>(hp, "view_sprite_map");
+std::vector<int32_t> layer_lut_rows(const void* pack, const DevTables& t) {
+  const int32_t* ssprite = table<int32_t>(pack, "state_sprite");
+  const int32_t* vmap = table<int32_t>(pack, "view_sprite_map");
   std::vector<int32_t> lut((size_t)t.P * kLayerLutRow, 0);
   for (int p = 0; p < t.P; ++p) {
     const int32_t* remap = vmap + (size_t)p * t.nsprites;
@@ -1091,6 +1072,12 @@ int upload_layer_lut(MpEngine* e) {
       row[s] = ssprite[s] >= 0 ? 1 + remap[ssprite[s]] : 0;
     row[256] = 1 + remap[0];
   }
+  return lut;
+}
+
+int upload_layer_lut(MpEngine* e) {
+  const DevTables& t = e->t;
+  const std::vector<int32_t> lut = layer_lut_rows(e->pack.data(), t);
   e->num_layer_ids = view_hash::num_ids(lut.data(), t.P);
   HIP_TRY(hipMalloc((void**)&e->d_layer_lut, lut.size() * 4));
   HIP_TRY(hipMemcpy(e->d_layer_lut, lut.data(), lut.size() * 4, hipMemcpyHostToDevice));
@@ -2613,374 +2600,378 @@ static int episode_stats_request(MpEngine* e, const MpEpisodeStats& r) {
   return MP_OK;
 }
 
-// An MpEgoLayer request (include/mp_engine.h; carried by mp_snapshot; `e` is NULL for the host
-// form): draws EGO_LAYER of bank rows or of the engine's worlds (one launch), registers or clears
-// the leaf (no launch), or applies the function to host rows.  Everything is checked first.
+// The requests about every viewer's window — MpEgoLayer, MpViewHash, MpEgoPlanes (include/mp_engine.h;
+// carried by mp_snapshot; `e` is NULL for the host form) — are one front and three tails.  Each
+// draws from bank rows or from the engine's worlds (one launch), registers or clears the tensor
+// behind every submission (no launch), or applies its function to host rows; everything is
+// checked first.  Their structs begin alike, and the front reads them through that beginning:
+struct ViewRequest {
+  uint32_t struct_size;
+  int32_t op;              // 1: draw, 2: register, 3: host (MP_EGO_*, MP_VIEWHASH_*, MP_EGOPLANES_*)
+  uint64_t fingerprint;
+  const void* bank;
+  const int32_t* rows;
+  const int32_t* players;
+  void* dst;
+  uint64_t dst_bytes;
+  int32_t bank_rows, count;
+  uint64_t slot_stride;
+  int32_t slots;
+  int32_t word76;          // MpEgoLayer: reserved; the other two: classes_len
+  const void* pack;
+  uint64_t pack_len;
+  const MpConfig* cfg;
+};
+enum { VIEW_DRAW = 1, VIEW_REGISTER = 2, VIEW_HOST = 3 };
+#define MP_VIEW_FIELD(T, f) (offsetof(T, f) == offsetof(ViewRequest, f))
+#define MP_VIEW_PREFIX(T)                                                                                      \
+  (MP_VIEW_FIELD(T, op) && MP_VIEW_FIELD(T, fingerprint) && MP_VIEW_FIELD(T, bank) && MP_VIEW_FIELD(T, rows) && \
+   MP_VIEW_FIELD(T, players) && MP_VIEW_FIELD(T, dst) && MP_VIEW_FIELD(T, dst_bytes) &&                        \
+   MP_VIEW_FIELD(T, bank_rows) && MP_VIEW_FIELD(T, count) && MP_VIEW_FIELD(T, slot_stride) &&                  \
+   MP_VIEW_FIELD(T, slots) && MP_VIEW_FIELD(T, pack) && MP_VIEW_FIELD(T, pack_len) && MP_VIEW_FIELD(T, cfg) && \
+   sizeof(T) >= sizeof(ViewRequest))
+static_assert(MP_VIEW_PREFIX(MpEgoLayer) && MP_VIEW_PREFIX(MpViewHash) && MP_VIEW_PREFIX(MpEgoPlanes),
+              "MpEgoLayer, MpViewHash and MpEgoPlanes share their leading fields");
+static_assert(MP_EGO_DRAW == VIEW_DRAW && MP_VIEWHASH_DRAW == VIEW_DRAW && MP_EGOPLANES_DRAW == VIEW_DRAW &&
+                  MP_EGO_REGISTER == VIEW_REGISTER && MP_VIEWHASH_REGISTER == VIEW_REGISTER &&
+                  MP_EGOPLANES_REGISTER == VIEW_REGISTER && MP_EGO_HOST == VIEW_HOST &&
+                  MP_VIEWHASH_HOST == VIEW_HOST && MP_EGOPLANES_HOST == VIEW_HOST,
+              "and the numbers of their ops");
+#undef MP_VIEW_PREFIX
+#undef MP_VIEW_FIELD
+static ViewRequest view_of(const void* request) {
+  ViewRequest q;
+  memcpy(&q, request, sizeof q);
+  return q;
+}
+
+// The words that differ in the three requests' messages.
+struct ViewWords {
+  const char* who;       // "MpEgoLayer"
+  const char* host_op;   // "MP_EGO_HOST"
+  const char* thing;     // a registration: "the leaf" of N worlds
+  const char* need;      // "needs" so many bytes
+  const char* drawn;     // rows are "drawn"
+  const char* draw;      // there is no state to "draw"
+};
+
+// The tables a request works with: the engine's, or the pack's by the host stage.
+struct ViewTables {
+  HostStage h;
+  std::vector<int32_t> host_lut;   // (host form) the viewers' value tables
+  const DevTables* t = nullptr;
+  uint64_t fingerprint = 0;
+  int32_t num_ids = 0;             // the length of a class table
+};
+
+// struct_size, op, engine, reserved words, pack: what is checked before the request is looked at.
+static int view_prologue(const MpEngine* e, const ViewRequest& q, const ViewWords& w, size_t size, bool reserved_zero) {
+  if (q.struct_size != size)
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", w.who, q.struct_size, size);
+  if (q.op != VIEW_DRAW && q.op != VIEW_REGISTER && q.op != VIEW_HOST)
+    return fail(MP_ERR_INVALID, "%s: unknown op %d", w.who, q.op);
+  if (q.op == VIEW_HOST ? e != nullptr : e == nullptr) {
+    if (e) return fail(MP_ERR_INVALID, "%s: %s takes no engine", w.who, w.host_op);
+    return fail(MP_ERR_INVALID, "%s: NULL engine", w.who);
+  }
+  if (!reserved_zero) return fail(MP_ERR_INVALID, "%s: the reserved words must be 0", w.who);
+  if (q.op == VIEW_HOST && (!q.pack || !q.cfg))
+    return fail(MP_ERR_INVALID, "%s: %s needs the pack and its config (NULL pack or cfg)", w.who, w.host_op);
+  return MP_OK;
+}
+
+static int view_tables(const MpEngine* e, const ViewRequest& q, ViewTables* v) {
+  if (e) {
+    v->t = &e->t;
+    v->fingerprint = e->fingerprint;
+    v->num_ids = e->num_layer_ids;
+    return MP_OK;
+  }
+  if (int rc = host_stage(q.pack, q.pack_len, q.cfg, &v->h)) return rc;
+  v->t = &v->h.d.t;
+  v->fingerprint = state_fingerprint(v->h.pack, v->h.d.t);
+  v->host_lut = layer_lut_rows(v->h.pack.data(), v->h.d.t);
+  v->num_ids = view_hash::num_ids(v->host_lut.data(), v->t->P);
+  return MP_OK;
+}
+
+// layer_mask as the kernels take it: 0 names every layer of the view.
+static int view_layer_mask(const ViewWords& w, const ego_layer::Window& g, uint64_t asked, uint64_t* layer_mask) {
+  if (g.L > 64) return fail(MP_ERR_UNSUPPORTED, "%s: %d layers; layer_mask names 64", w.who, g.L);
+  const uint64_t every = g.L == 64 ? ~0ull : (1ull << g.L) - 1ull;
+  if (asked & ~every)
+    return fail(MP_ERR_INVALID, "%s: layer_mask %016llx has a bit that names no layer (the view has %d)", w.who,
+                (unsigned long long)asked, g.L);
+  *layer_mask = asked ? asked : every;
+  return MP_OK;
+}
+
+static int view_record_lines(const ViewWords& w, const DevTables& t, const ego_layer::Window& g) {
+  if ((t.grid_pad & 15) || (t.world_stride & 15) || (int64_t)g.L * g.HW > (int64_t)t.grid_pad)
+    return fail(MP_ERR_UNSUPPORTED, "%s: a record of %d bytes with %d bytes of planes is not read in 16-byte lines",
+                w.who, t.world_stride, t.grid_pad);
+  return MP_OK;
+}
+
+// A registration's geometry: the ring, the bytes `dst` must hold (*need) with `world` bytes a world
+// and slots `align`-byte aligned (1: anywhere), and `dst` itself.
+static int view_register(MpEngine* e, const ViewRequest& q, const ViewWords& w, uint64_t world, unsigned align,
+                         uint64_t* need) {
+  const uint64_t block = (uint64_t)e->N * world;
+  if (q.slots < 0) return fail(MP_ERR_INVALID, "%s: slots %d", w.who, q.slots);
+  if (q.slots > 0 && q.slots != e->ring_slots)
+    return fail(MP_ERR_INVALID, "%s: a ring of %d slots, the engine's ring has %d (mp_bind_output_ring; one "
+                "position for all of them)", w.who, q.slots, e->ring_slots);
+  if (q.slots > 0 && (q.slot_stride < block || (q.slot_stride & (align - 1)))) {
+    char lie[48] = "";
+    if (align > 1) snprintf(lie, sizeof lie, ", and slots lie %u-byte aligned", align);
+    return fail(MP_ERR_INVALID, "%s: slot_stride %llu: a slot is %llu bytes%s", w.who,
+                (unsigned long long)q.slot_stride, (unsigned long long)block, lie);
+  }
+  *need = q.slots > 0 ? (uint64_t)(q.slots - 1) * q.slot_stride + block : block;
+  if (q.dst_bytes < *need)
+    return fail(MP_ERR_INVALID, "%s: %s of %d worlds%s %s %llu bytes, dst has %llu", w.who, w.thing, e->N,
+                q.slots > 0 ? " in every slot" : "", w.need, (unsigned long long)*need,
+                (unsigned long long)q.dst_bytes);
+  HIP_TRY(hipSetDevice(e->device));
+  char name[48];
+  snprintf(name, sizeof name, "%s (dst)", w.who);
+  if (int rc = check_device_pointer(e, q.dst, name)) return rc;
+  return check_bank(e, q.dst, *need, name);
+}
+
+static MpEngine::ViewRegistration registration_of(const ViewRequest& q) {
+  MpEngine::ViewRegistration v;
+  v.dst = q.dst;
+  v.stride = q.slots > 0 ? q.slot_stride : 0;
+  v.slots = q.slots;
+  return v;
+}
+
+// What a draw or a host call reads and how much it writes: `view` bytes an element with players[],
+// `world` without.
+struct ViewSource {
+  bool live;          // the engine's worlds
+  int32_t src_rows;
+  uint64_t need;      // bytes of dst
+};
+static int view_source(const MpEngine* e, const ViewRequest& q, const ViewWords& w, const ViewTables& v,
+                       uint64_t view, uint64_t world, ViewSource* s) {
+  s->live = q.op == VIEW_DRAW && !q.bank;
+  if (q.op == VIEW_HOST && !q.bank) return fail(MP_ERR_INVALID, "%s: NULL bank", w.who);
+  s->src_rows = s->live ? e->N : q.bank_rows;
+  if (q.count < 1 || s->src_rows < 1)
+    return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", w.who, q.count, s->src_rows);
+  if (!q.rows && q.count > s->src_rows)
+    return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are %s (count %d, there are %d "
+                "rows)", w.who, w.drawn, q.count, s->src_rows);
+  if (q.fingerprint != v.fingerprint)
+    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this %s (%016llx): they were "
+                "saved by an engine of another pack, player count or record layout", w.who,
+                (unsigned long long)q.fingerprint, e ? "engine's" : "pack's", (unsigned long long)v.fingerprint);
+  const uint64_t each = q.players ? view : world;
+  s->need = (uint64_t)q.count * each;
+  if (q.dst_bytes < s->need)
+    return fail(MP_ERR_INVALID, "%s: %d elements of %llu bytes need %llu bytes, dst has %llu", w.who, q.count,
+                (unsigned long long)each, (unsigned long long)s->need, (unsigned long long)q.dst_bytes);
+  if (((uintptr_t)q.rows & 3) || ((uintptr_t)q.players & 3))
+    return fail(MP_ERR_INVALID, "%s: rows %p and players %p must be 4-byte aligned", w.who, (const void*)q.rows,
+                (const void*)q.players);
+  return MP_OK;
+}
+
+// The fields every unit's Args has, of a draw or a host call.
+extern "C++" {
+template <class Args>
+static void view_args(Args* a, const ego_layer::Window& g, const ViewRequest& q, const ViewTables& v,
+                      const ViewSource& s) {
+  a->g = g;
+  a->rows = q.rows; a->players = q.players;
+  a->src_rows = s.src_rows; a->count = q.count;
+  a->stride = v.t->world_stride; a->grid_pad = v.t->grid_pad;
+}
+}
+
+// The host twin met an index out of range at position `bad` (`row`: of rows[], else of players[]).
+static int view_host_fault(const ViewRequest& q, const ViewWords& w, int bad, bool row) {
+  return fail(MP_ERR_INVALID, "%s: %s[%d] = %d is %s; the elements from %d on were left as they were", w.who,
+              row ? "rows" : "players", bad, row ? (q.rows ? q.rows[bad] : bad) : q.players[bad],
+              row ? "not a row of the bank" : "not a player of this pack", bad);
+}
+
+// A draw's device memory: the state or the bank, rows, players, a class table, dst.
+static int view_device_source(MpEngine* e, const ViewRequest& q, const ViewWords& w, const ViewSource& s,
+                              const void* classes, uint64_t classes_bytes) {
+  if (s.live && !e->has_state)
+    return fail(MP_ERR_INVALID, "%s: the engine has never been reset; there is no state to %s", w.who, w.draw);
+  if (!s.live && ((uintptr_t)q.bank & 15))   // (records are read in 16-byte lines)
+    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", w.who, q.bank);
+  HIP_TRY(hipSetDevice(e->device));
+  const uint64_t count = (uint64_t)q.count;
+  const struct { const char* what; const void* at; uint64_t bytes; } all[5] = {
+      {"bank", s.live ? nullptr : q.bank, (uint64_t)q.bank_rows * (uint64_t)e->t.world_stride},
+      {"rows", q.rows, count * 4},
+      {"players", q.players, count * 4},
+      {"classes", classes, classes_bytes},
+      {"dst", q.dst, s.need}};
+  char name[48];
+  for (const auto& k : all) {
+    if (!k.at) continue;
+    snprintf(name, sizeof name, "%s (%s)", w.who, k.what);
+    if (int rc = check_bank(e, k.at, k.bytes, name)) return rc;
+  }
+  return MP_OK;
+}
+
 static int ego_layer_request(MpEngine* e, const MpEgoLayer& r) {
-  static const char kWho[] = "MpEgoLayer";
-  if (r.struct_size != sizeof(MpEgoLayer))
-    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpEgoLayer));
-  if (r.op != MP_EGO_DRAW && r.op != MP_EGO_REGISTER && r.op != MP_EGO_HOST)
-    return fail(MP_ERR_INVALID, "%s: unknown op %d", kWho, r.op);
-  if (r.op == MP_EGO_HOST ? e != nullptr : e == nullptr)
-    return fail(MP_ERR_INVALID, "%s: %s", kWho, e ? "MP_EGO_HOST takes no engine" : "NULL engine");
-  if (r.reserved != 0 || r.reserved2[0] != 0 || r.reserved2[1] != 0 || r.reserved2[2] != 0)
-    return fail(MP_ERR_INVALID, "%s: the reserved words must be 0", kWho);
-  if (r.op == MP_EGO_HOST && (!r.pack || !r.cfg))
-    return fail(MP_ERR_INVALID, "%s: MP_EGO_HOST needs the pack and its config (NULL pack or cfg)", kWho);
+  static const ViewWords w = {"MpEgoLayer", "MP_EGO_HOST", "the leaf", "needs", "drawn", "draw"};
+  const char* const kWho = w.who;
+  const ViewRequest q = view_of(&r);
+  if (int rc = view_prologue(e, q, w, sizeof r,
+                             r.reserved == 0 && r.reserved2[0] == 0 && r.reserved2[1] == 0 && r.reserved2[2] == 0))
+    return rc;
   if (r.op == MP_EGO_REGISTER && !r.dst) {   // clears the registration: the engine's launches are what they were
-    e->ego_dst = nullptr;
-    e->ego_stride = 0;
-    e->ego_slots = 0;
+    e->ego = MpEngine::ViewRegistration{};
     return MP_OK;
   }
   if (!r.dst) return fail(MP_ERR_INVALID, "%s: NULL dst", kWho);
   if ((uintptr_t)r.dst & 3) return fail(MP_ERR_INVALID, "%s: dst %p is not 4-byte aligned", kWho, r.dst);
-  // the tables and the fingerprint: the engine's, or the pack's by the host stage
-  HostStage h;
-  std::vector<int32_t> host_lut;
-  const DevTables* t;
-  uint64_t fingerprint;
-  if (e) {
-    t = &e->t;
-    fingerprint = e->fingerprint;
-  } else {
-    if (int rc = host_stage(r.pack, r.pack_len, r.cfg, &h)) return rc;
-    t = &h.d.t;
-    fingerprint = state_fingerprint(h.pack, h.d.t);
-    // (upload_layer_lut's table, from the pack as the host stage left it)
-    const int32_t* ssprite = table<int32_t>(h.pack.data(), "state_sprite");
-    const int32_t* vmap = table<int32_t>(h.pack.data(), "view_sprite_map");
-    host_lut.assign((size_t)t->P * kLayerLutRow, 0);
-    for (int p = 0; p < t->P; ++p) {
-      const int32_t* remap = vmap + (size_t)p * t->nsprites;
-      int32_t* row = host_lut.data() + (size_t)p * kLayerLutRow;
-      for (int s = 1; s < t->nstates && s < 256; ++s) row[s] = ssprite[s] >= 0 ? 1 + remap[ssprite[s]] : 0;
-      row[256] = 1 + remap[0];
-    }
-  }
-  const ego_layer::Window g = ego_layer::window_of(*t);
+  ViewTables v;
+  if (int rc = view_tables(e, q, &v)) return rc;
+  const ego_layer::Window g = ego_layer::window_of(*v.t);
   const uint64_t view = (uint64_t)g.VH * (uint64_t)g.VW * (uint64_t)g.L * 4u, world = view * (uint64_t)g.P;
-  if ((t->grid_pad & 15) || (t->world_stride & 15) || (int64_t)g.L * g.HW > (int64_t)t->grid_pad)
-    return fail(MP_ERR_UNSUPPORTED, "%s: a record of %d bytes with %d bytes of planes is not read in 16-byte lines",
-                kWho, t->world_stride, t->grid_pad);
+  if (int rc = view_record_lines(w, *v.t, g)) return rc;
   if (r.op == MP_EGO_REGISTER) {
-    const uint64_t N = (uint64_t)e->N, block = N * world;
-    if (r.slots < 0) return fail(MP_ERR_INVALID, "%s: slots %d", kWho, r.slots);
-    if (r.slots > 0 && r.slots != e->ring_slots)
-      return fail(MP_ERR_INVALID, "%s: a ring of %d slots, the engine's ring has %d (mp_bind_output_ring; one "
-                  "position for all of them)", kWho, r.slots, e->ring_slots);
-    if (r.slots > 0 && (r.slot_stride < block || (r.slot_stride & 3)))
-      return fail(MP_ERR_INVALID, "%s: slot_stride %llu: a slot is %llu bytes, and slots lie 4-byte aligned", kWho,
-                  (unsigned long long)r.slot_stride, (unsigned long long)block);
-    const uint64_t need = r.slots > 0 ? (uint64_t)(r.slots - 1) * r.slot_stride + block : block;
-    if (r.dst_bytes < need)
-      return fail(MP_ERR_INVALID, "%s: the leaf of %d worlds%s needs %llu bytes, dst has %llu", kWho, e->N,
-                  r.slots > 0 ? " in every slot" : "", (unsigned long long)need, (unsigned long long)r.dst_bytes);
-    HIP_TRY(hipSetDevice(e->device));
-    if (int rc = check_device_pointer(e, r.dst, "MpEgoLayer (dst)")) return rc;
-    if (int rc = check_bank(e, r.dst, need, "MpEgoLayer (dst)")) return rc;
-    if (ego_layer::plan_of(g, e->N, e->num_cus).waves < 1)
-      return fail(MP_ERR_UNSUPPORTED, "%s: one wave's render planes need %d B of LDS", kWho,
-                  ego_layer::plan_of(g, e->N, e->num_cus).lds);
-    e->ego_dst = (int32_t*)r.dst;
-    e->ego_stride = r.slots > 0 ? r.slot_stride : 0;
-    e->ego_slots = r.slots;
+    uint64_t need;
+    if (int rc = view_register(e, q, w, world, 4, &need)) return rc;
+    const ego_layer::Plan p = ego_layer::plan_of(g, e->N, e->num_cus);
+    if (p.waves < 1)
+      return fail(MP_ERR_UNSUPPORTED, "%s: one wave's render planes need %d B of LDS", kWho, p.lds);
+    e->ego = registration_of(q);
     return MP_OK;
   }
-  const bool live = r.op == MP_EGO_DRAW && !r.bank;
-  if (r.op == MP_EGO_HOST && !r.bank) return fail(MP_ERR_INVALID, "%s: NULL bank", kWho);
-  const int32_t src_rows = live ? e->N : r.bank_rows;
-  if (r.count < 1 || src_rows < 1)
-    return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", kWho, r.count, src_rows);
-  if (!r.rows && r.count > src_rows)
-    return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are drawn (count %d, there are %d "
-                "rows)", kWho, r.count, src_rows);
-  if (r.fingerprint != fingerprint)
-    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this %s (%016llx): they were "
-                "saved by an engine of another pack, player count or record layout", kWho,
-                (unsigned long long)r.fingerprint, e ? "engine's" : "pack's", (unsigned long long)fingerprint);
-  const uint64_t count = (uint64_t)r.count, need = count * (r.players ? view : world);
-  if (r.dst_bytes < need)
-    return fail(MP_ERR_INVALID, "%s: %d elements of %llu bytes need %llu bytes, dst has %llu", kWho, r.count,
-                (unsigned long long)(r.players ? view : world), (unsigned long long)need,
-                (unsigned long long)r.dst_bytes);
-  if (((uintptr_t)r.rows & 3) || ((uintptr_t)r.players & 3))
-    return fail(MP_ERR_INVALID, "%s: rows %p and players %p must be 4-byte aligned", kWho, (const void*)r.rows,
-                (const void*)r.players);
+  ViewSource s;
+  if (int rc = view_source(e, q, w, v, view, world, &s)) return rc;
   ego_layer::Args a = {};
-  a.g = g;
-  a.rows = r.rows; a.players = r.players; a.dst = (int32_t*)r.dst;
-  a.src_rows = src_rows; a.count = r.count;
-  a.stride = t->world_stride; a.grid_pad = t->grid_pad;
+  view_args(&a, g, q, v, s);
+  a.dst = (int32_t*)r.dst;
   if (r.op == MP_EGO_HOST) {
     a.src = (const uint8_t*)r.bank;
-    a.lut = host_lut.data();
+    a.lut = v.host_lut.data();
     uint32_t what = 0;
     const int bad = ego_layer::host(a, &what);
-    if (bad >= 0)
-      return fail(MP_ERR_INVALID, "%s: %s[%d] = %d is %s; the elements from %d on were left as they were", kWho,
-                  what == kFaultEgoRow ? "rows" : "players", bad,
-                  what == kFaultEgoRow ? (r.rows ? r.rows[bad] : bad) : r.players[bad],
-                  what == kFaultEgoRow ? "not a row of the bank" : "not a player of this pack", bad);
-    return MP_OK;
+    return bad >= 0 ? view_host_fault(q, w, bad, what == kFaultEgoRow) : MP_OK;
   }
-  if (live && !e->has_state)
-    return fail(MP_ERR_INVALID, "%s: the engine has never been reset; there is no state to draw", kWho);
-  if (!live && ((uintptr_t)r.bank & 15))   // (records are read in 16-byte lines)
-    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", kWho, r.bank);
-  HIP_TRY(hipSetDevice(e->device));
-  if (!live)
-    if (int rc = check_bank(e, r.bank, (uint64_t)r.bank_rows * (uint64_t)t->world_stride, "MpEgoLayer (bank)"))
-      return rc;
-  if (r.rows)
-    if (int rc = check_bank(e, r.rows, count * 4, "MpEgoLayer (rows)")) return rc;
-  if (r.players)
-    if (int rc = check_bank(e, r.players, count * 4, "MpEgoLayer (players)")) return rc;
-  if (int rc = check_bank(e, r.dst, need, "MpEgoLayer (dst)")) return rc;
+  if (int rc = view_device_source(e, q, w, s, nullptr, 0)) return rc;
   const ego_layer::Plan p = ego_layer::plan_of(g, r.count, e->num_cus);
   if (p.waves < 1)
     return fail(MP_ERR_UNSUPPORTED, "%s: one wave's render planes need %d B of LDS", kWho, p.lds);
-  a.src = live ? e->d_state : (const uint8_t*)r.bank;
+  a.src = s.live ? e->d_state : (const uint8_t*)r.bank;
   a.lut = e->d_layer_lut; a.fault = e->t.fault;
   ego_layer::launch(a, p, e->stream);
   HIP_TRY(hipGetLastError());
   return MP_OK;
 }
 
-// An MpViewHash request (include/mp_engine.h; carried by mp_snapshot; `e` is NULL for the host
-// form): hashes every viewer's view of bank rows or of the engine's worlds (one launch), registers
-// or clears the tensor behind every submission (no launch), or applies the function to host rows.
-// Everything is checked first.  `r` is the caller's struct: num_ids is written back.
+// (`out` is the caller's struct: num_ids is written back)
 static int view_hash_request(MpEngine* e, MpViewHash* out) {
-  static const char kWho[] = "MpViewHash";
+  static const ViewWords w = {"MpViewHash", "MP_VIEWHASH_HOST", "the hashes", "need", "hashed", "hash"};
+  const char* const kWho = w.who;
   MpViewHash r;
   memcpy(&r, out, sizeof r);
-  if (r.struct_size != sizeof(MpViewHash))
-    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpViewHash));
-  if (r.op != MP_VIEWHASH_DRAW && r.op != MP_VIEWHASH_REGISTER && r.op != MP_VIEWHASH_HOST)
-    return fail(MP_ERR_INVALID, "%s: unknown op %d", kWho, r.op);
-  if (r.op == MP_VIEWHASH_HOST ? e != nullptr : e == nullptr)
-    return fail(MP_ERR_INVALID, "%s: %s", kWho, e ? "MP_VIEWHASH_HOST takes no engine" : "NULL engine");
-  if (r.reserved != 0 || r.reserved2[0] != 0 || r.reserved2[1] != 0 || r.reserved2[2] != 0)
-    return fail(MP_ERR_INVALID, "%s: the reserved words must be 0", kWho);
-  if (r.op == MP_VIEWHASH_HOST && (!r.pack || !r.cfg))
-    return fail(MP_ERR_INVALID, "%s: MP_VIEWHASH_HOST needs the pack and its config (NULL pack or cfg)", kWho);
+  const ViewRequest q = view_of(&r);
+  if (int rc = view_prologue(e, q, w, sizeof r,
+                             r.reserved == 0 && r.reserved2[0] == 0 && r.reserved2[1] == 0 && r.reserved2[2] == 0))
+    return rc;
   if (r.op == MP_VIEWHASH_REGISTER && !r.dst) {   // clears the registration: the engine's launches are what they were
-    e->vh_dst = nullptr;
-    e->vh_stride = 0; e->vh_mask = 0;
-    e->vh_slots = 0;
-    e->vh_classes = nullptr;
+    e->vh = MpEngine::ViewRegistration{};
     out->num_ids = e->num_layer_ids;
     return MP_OK;
   }
-  // the tables and the fingerprint: the engine's, or the pack's by the host stage
-  HostStage h;
-  std::vector<int32_t> host_lut;
-  const DevTables* t;
-  uint64_t fingerprint;
-  int32_t num_ids;
-  if (e) {
-    t = &e->t;
-    fingerprint = e->fingerprint;
-    num_ids = e->num_layer_ids;
-  } else {
-    if (int rc = host_stage(r.pack, r.pack_len, r.cfg, &h)) return rc;
-    t = &h.d.t;
-    fingerprint = state_fingerprint(h.pack, h.d.t);
-    // (upload_layer_lut's table, from the pack as the host stage left it)
-    const int32_t* ssprite = table<int32_t>(h.pack.data(), "state_sprite");
-    const int32_t* vmap = table<int32_t>(h.pack.data(), "view_sprite_map");
-    host_lut.assign((size_t)t->P * kLayerLutRow, 0);
-    for (int p = 0; p < t->P; ++p) {
-      const int32_t* remap = vmap + (size_t)p * t->nsprites;
-      int32_t* row = host_lut.data() + (size_t)p * kLayerLutRow;
-      for (int s = 1; s < t->nstates && s < 256; ++s) row[s] = ssprite[s] >= 0 ? 1 + remap[ssprite[s]] : 0;
-      row[256] = 1 + remap[0];
-    }
-    num_ids = view_hash::num_ids(host_lut.data(), t->P);
-  }
+  ViewTables v;
+  if (int rc = view_tables(e, q, &v)) return rc;
+  const int32_t num_ids = v.num_ids;
   if (num_ids < 1)
     return fail(MP_ERR_UNSUPPORTED, "%s: the pack's view tables hold a negative id", kWho);
   out->num_ids = num_ids;
   if (r.op != MP_VIEWHASH_REGISTER && r.count == 0 && !r.dst) return MP_OK;   // the question alone
   if (!r.dst) return fail(MP_ERR_INVALID, "%s: NULL dst", kWho);
   if ((uintptr_t)r.dst & 7) return fail(MP_ERR_INVALID, "%s: dst %p is not 8-byte aligned", kWho, r.dst);
-  const ego_layer::Window g = ego_layer::window_of(*t);
-  if (g.L > 64) return fail(MP_ERR_UNSUPPORTED, "%s: %d layers; layer_mask names 64", kWho, g.L);
-  const uint64_t every = g.L == 64 ? ~0ull : (1ull << g.L) - 1ull;
-  if (r.layer_mask & ~every)
-    return fail(MP_ERR_INVALID, "%s: layer_mask %016llx has a bit that names no layer (the view has %d)", kWho,
-                (unsigned long long)r.layer_mask, g.L);
-  const uint64_t layer_mask = r.layer_mask ? r.layer_mask : every;
+  const ego_layer::Window g = ego_layer::window_of(*v.t);
+  uint64_t layer_mask;
+  if (int rc = view_layer_mask(w, g, r.layer_mask, &layer_mask)) return rc;
   if (r.classes ? r.classes_len != num_ids : r.classes_len != 0)
     return fail(MP_ERR_INVALID, "%s: classes_len %d: a class table has one entry per id, %d of them (0 without "
                 "a table)", kWho, r.classes_len, num_ids);
   if ((uintptr_t)r.classes & 3)
     return fail(MP_ERR_INVALID, "%s: classes %p is not 4-byte aligned", kWho, (const void*)r.classes);
   const uint64_t world = (uint64_t)g.P * 8u;
-  if ((t->grid_pad & 15) || (t->world_stride & 15) || (int64_t)g.L * g.HW > (int64_t)t->grid_pad)
-    return fail(MP_ERR_UNSUPPORTED, "%s: a record of %d bytes with %d bytes of planes is not read in 16-byte lines",
-                kWho, t->world_stride, t->grid_pad);
+  if (int rc = view_record_lines(w, *v.t, g)) return rc;
   const int num_classes = r.classes ? num_ids : 0;
   if (r.op == MP_VIEWHASH_REGISTER) {
-    const uint64_t N = (uint64_t)e->N, block = N * world;
-    if (r.slots < 0) return fail(MP_ERR_INVALID, "%s: slots %d", kWho, r.slots);
-    if (r.slots > 0 && r.slots != e->ring_slots)
-      return fail(MP_ERR_INVALID, "%s: a ring of %d slots, the engine's ring has %d (mp_bind_output_ring; one "
-                  "position for all of them)", kWho, r.slots, e->ring_slots);
-    if (r.slots > 0 && (r.slot_stride < block || (r.slot_stride & 7)))
-      return fail(MP_ERR_INVALID, "%s: slot_stride %llu: a slot is %llu bytes, and slots lie 8-byte aligned", kWho,
-                  (unsigned long long)r.slot_stride, (unsigned long long)block);
-    const uint64_t need = r.slots > 0 ? (uint64_t)(r.slots - 1) * r.slot_stride + block : block;
-    if (r.dst_bytes < need)
-      return fail(MP_ERR_INVALID, "%s: the hashes of %d worlds%s need %llu bytes, dst has %llu", kWho, e->N,
-                  r.slots > 0 ? " in every slot" : "", (unsigned long long)need, (unsigned long long)r.dst_bytes);
-    HIP_TRY(hipSetDevice(e->device));
-    if (int rc = check_device_pointer(e, r.dst, "MpViewHash (dst)")) return rc;
-    if (int rc = check_bank(e, r.dst, need, "MpViewHash (dst)")) return rc;
+    uint64_t need;
+    if (int rc = view_register(e, q, w, world, 8, &need)) return rc;
     if (r.classes)
       if (int rc = check_bank(e, r.classes, (uint64_t)num_classes * 4, "MpViewHash (classes)")) return rc;
     const view_hash::Plan p = view_hash::plan_of(g, e->N, e->num_cus);
     if (p.waves < 1)
       return fail(MP_ERR_UNSUPPORTED, "%s: the value tables and one wave's render planes need %d B of LDS", kWho, p.lds);
-    e->vh_dst = (uint64_t*)r.dst;
-    e->vh_stride = r.slots > 0 ? r.slot_stride : 0;
-    e->vh_slots = r.slots;
-    e->vh_mask = layer_mask;
-    e->vh_classes = r.classes;
+    e->vh = registration_of(q);
+    e->vh.mask = layer_mask;
+    e->vh.classes = r.classes;
     return MP_OK;
   }
-  const bool live = r.op == MP_VIEWHASH_DRAW && !r.bank;
-  if (r.op == MP_VIEWHASH_HOST && !r.bank) return fail(MP_ERR_INVALID, "%s: NULL bank", kWho);
-  const int32_t src_rows = live ? e->N : r.bank_rows;
-  if (r.count < 1 || src_rows < 1)
-    return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", kWho, r.count, src_rows);
-  if (!r.rows && r.count > src_rows)
-    return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are hashed (count %d, there are %d "
-                "rows)", kWho, r.count, src_rows);
-  if (r.fingerprint != fingerprint)
-    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this %s (%016llx): they were "
-                "saved by an engine of another pack, player count or record layout", kWho,
-                (unsigned long long)r.fingerprint, e ? "engine's" : "pack's", (unsigned long long)fingerprint);
-  const uint64_t count = (uint64_t)r.count, need = count * (r.players ? 8u : world);
-  if (r.dst_bytes < need)
-    return fail(MP_ERR_INVALID, "%s: %d elements of %llu bytes need %llu bytes, dst has %llu", kWho, r.count,
-                (unsigned long long)(r.players ? 8u : world), (unsigned long long)need,
-                (unsigned long long)r.dst_bytes);
-  if (((uintptr_t)r.rows & 3) || ((uintptr_t)r.players & 3))
-    return fail(MP_ERR_INVALID, "%s: rows %p and players %p must be 4-byte aligned", kWho, (const void*)r.rows,
-                (const void*)r.players);
+  ViewSource s;
+  if (int rc = view_source(e, q, w, v, 8u, world, &s)) return rc;
   view_hash::Args a = {};
-  a.g = g;
-  a.rows = r.rows; a.players = r.players; a.dst = (uint64_t*)r.dst;
-  a.src_rows = src_rows; a.count = r.count;
-  a.stride = t->world_stride; a.grid_pad = t->grid_pad;
+  view_args(&a, g, q, v, s);
+  a.dst = (uint64_t*)r.dst;
   a.layer_mask = layer_mask;
   a.classes = r.classes; a.num_classes = num_classes;
   if (r.op == MP_VIEWHASH_HOST) {
     a.src = (const uint8_t*)r.bank;
-    a.lut = host_lut.data();
+    a.lut = v.host_lut.data();
     uint32_t what = 0;
     const int bad = view_hash::host(a, &what);
-    if (bad >= 0)
-      return fail(MP_ERR_INVALID, "%s: %s[%d] = %d is %s; the elements from %d on were left as they were", kWho,
-                  what == kFaultViewHashRow ? "rows" : "players", bad,
-                  what == kFaultViewHashRow ? (r.rows ? r.rows[bad] : bad) : r.players[bad],
-                  what == kFaultViewHashRow ? "not a row of the bank" : "not a player of this pack", bad);
-    return MP_OK;
+    return bad >= 0 ? view_host_fault(q, w, bad, what == kFaultViewHashRow) : MP_OK;
   }
-  if (live && !e->has_state)
-    return fail(MP_ERR_INVALID, "%s: the engine has never been reset; there is no state to hash", kWho);
-  if (!live && ((uintptr_t)r.bank & 15))   // (records are read in 16-byte lines)
-    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", kWho, r.bank);
-  HIP_TRY(hipSetDevice(e->device));
-  if (!live)
-    if (int rc = check_bank(e, r.bank, (uint64_t)r.bank_rows * (uint64_t)t->world_stride, "MpViewHash (bank)"))
-      return rc;
-  if (r.rows)
-    if (int rc = check_bank(e, r.rows, count * 4, "MpViewHash (rows)")) return rc;
-  if (r.players)
-    if (int rc = check_bank(e, r.players, count * 4, "MpViewHash (players)")) return rc;
-  if (r.classes)
-    if (int rc = check_bank(e, r.classes, (uint64_t)num_classes * 4, "MpViewHash (classes)")) return rc;
-  if (int rc = check_bank(e, r.dst, need, "MpViewHash (dst)")) return rc;
+  if (int rc = view_device_source(e, q, w, s, r.classes, (uint64_t)num_classes * 4)) return rc;
   const view_hash::Plan p = view_hash::plan_of(g, r.count, e->num_cus);
   if (p.waves < 1)
     return fail(MP_ERR_UNSUPPORTED, "%s: the value tables and one wave's render planes need %d B of LDS", kWho, p.lds);
-  a.src = live ? e->d_state : (const uint8_t*)r.bank;
+  a.src = s.live ? e->d_state : (const uint8_t*)r.bank;
   a.lut = e->d_layer_lut; a.fault = e->t.fault;
   view_hash::launch(a, p, e->stream);
   HIP_TRY(hipGetLastError());
   return MP_OK;
 }
 
-// An MpEgoPlanes request (include/mp_engine.h; carried by mp_snapshot; `e` is NULL for the host
-// form): writes every viewer's class and facing planes of bank rows or of the engine's worlds (one
-// launch), registers or clears the tensor behind every submission (no launch), or applies the
-// function to host rows.  Everything is checked first.  `out` is the caller's struct: num_ids is
-// written back.
+// (`out` is the caller's struct: num_ids is written back)
 static int ego_planes_request(MpEngine* e, MpEgoPlanes* out) {
-  static const char kWho[] = "MpEgoPlanes";
+  static const ViewWords w = {"MpEgoPlanes", "MP_EGOPLANES_HOST", "the planes", "need", "drawn", "draw"};
+  const char* const kWho = w.who;
   MpEgoPlanes r;
   memcpy(&r, out, sizeof r);
-  if (r.struct_size != sizeof(MpEgoPlanes))
-    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpEgoPlanes));
-  if (r.op != MP_EGOPLANES_DRAW && r.op != MP_EGOPLANES_REGISTER && r.op != MP_EGOPLANES_HOST)
-    return fail(MP_ERR_INVALID, "%s: unknown op %d", kWho, r.op);
-  if (r.op == MP_EGOPLANES_HOST ? e != nullptr : e == nullptr)
-    return fail(MP_ERR_INVALID, "%s: %s", kWho, e ? "MP_EGOPLANES_HOST takes no engine" : "NULL engine");
-  if (r.reserved != 0 || r.reserved2[0] != 0 || r.reserved2[1] != 0 || r.reserved2[2] != 0)
-    return fail(MP_ERR_INVALID, "%s: the reserved words must be 0", kWho);
-  if (r.op == MP_EGOPLANES_HOST && (!r.pack || !r.cfg))
-    return fail(MP_ERR_INVALID, "%s: MP_EGOPLANES_HOST needs the pack and its config (NULL pack or cfg)", kWho);
+  const ViewRequest q = view_of(&r);
+  if (int rc = view_prologue(e, q, w, sizeof r,
+                             r.reserved == 0 && r.reserved2[0] == 0 && r.reserved2[1] == 0 && r.reserved2[2] == 0))
+    return rc;
   if (r.op == MP_EGOPLANES_REGISTER && !r.dst) {   // clears the registration: the engine's launches are what they were
-    e->ep_dst = nullptr;
-    e->ep_stride = 0; e->ep_mask = 0;
-    e->ep_slots = 0;
-    e->ep_classes = nullptr;
-    e->ep_num_classes = 0; e->ep_facing = 0;
+    e->ep = MpEngine::ViewRegistration{};
     out->num_ids = e->num_layer_ids;
     return MP_OK;
   }
-  // the tables and the fingerprint: the engine's, or the pack's by the host stage
-  HostStage h;
-  std::vector<int32_t> host_lut;
-  const DevTables* t;
-  uint64_t fingerprint;
-  int32_t num_ids;
-  if (e) {
-    t = &e->t;
-    fingerprint = e->fingerprint;
-    num_ids = e->num_layer_ids;
-  } else {
-    if (int rc = host_stage(r.pack, r.pack_len, r.cfg, &h)) return rc;
-    t = &h.d.t;
-    fingerprint = state_fingerprint(h.pack, h.d.t);
-    // (upload_layer_lut's table, from the pack as the host stage left it)
-    const int32_t* ssprite = table<int32_t>(h.pack.data(), "state_sprite");
-    const int32_t* vmap = table<int32_t>(h.pack.data(), "view_sprite_map");
-    host_lut.assign((size_t)t->P * kLayerLutRow, 0);
-    for (int p = 0; p < t->P; ++p) {
-      const int32_t* remap = vmap + (size_t)p * t->nsprites;
-      int32_t* row = host_lut.data() + (size_t)p * kLayerLutRow;
-      for (int s = 1; s < t->nstates && s < 256; ++s) row[s] = ssprite[s] >= 0 ? 1 + remap[ssprite[s]] : 0;
-      row[256] = 1 + remap[0];
-    }
-    num_ids = view_hash::num_ids(host_lut.data(), t->P);
-  }
+  ViewTables v;
+  if (int rc = view_tables(e, q, &v)) return rc;
+  const int32_t num_ids = v.num_ids;
   if (num_ids < 1)
     return fail(MP_ERR_UNSUPPORTED, "%s: the pack's view tables hold a negative id", kWho);
   out->num_ids = num_ids;
   if (r.op != MP_EGOPLANES_REGISTER && r.count == 0 && !r.dst) return MP_OK;   // the question alone
   if (!r.dst) return fail(MP_ERR_INVALID, "%s: NULL dst", kWho);
-  const ego_layer::Window g = ego_layer::window_of(*t);
-  if (g.L > 64) return fail(MP_ERR_UNSUPPORTED, "%s: %d layers; layer_mask names 64", kWho, g.L);
-  const uint64_t every = g.L == 64 ? ~0ull : (1ull << g.L) - 1ull;
-  if (r.layer_mask & ~every)
-    return fail(MP_ERR_INVALID, "%s: layer_mask %016llx has a bit that names no layer (the view has %d)", kWho,
-                (unsigned long long)r.layer_mask, g.L);
-  const uint64_t layer_mask = r.layer_mask ? r.layer_mask : every;
+  const ego_layer::Window g = ego_layer::window_of(*v.t);
+  uint64_t layer_mask;
+  if (int rc = view_layer_mask(w, g, r.layer_mask, &layer_mask)) return rc;
   if (!r.classes) return fail(MP_ERR_INVALID, "%s: NULL classes: the planes are those of a class table", kWho);
   if (r.classes_len != num_ids)
     return fail(MP_ERR_INVALID, "%s: classes_len %d: a class table has one entry per id, %d of them", kWho,
@@ -2990,68 +2981,31 @@ static int ego_planes_request(MpEngine* e, MpEgoPlanes* out) {
   if (r.num_classes < 1 || r.num_classes > ego_planes::kMaxClasses)
     return fail(MP_ERR_INVALID, "%s: num_classes %d is outside [1, %d]", kWho, r.num_classes, ego_planes::kMaxClasses);
   if (r.facing != 0 && r.facing != 1) return fail(MP_ERR_INVALID, "%s: facing %d is neither 0 nor 1", kWho, r.facing);
-  if ((t->grid_pad & 15) || (t->world_stride & 15) || (int64_t)g.L * g.HW > (int64_t)t->grid_pad)
-    return fail(MP_ERR_UNSUPPORTED, "%s: a record of %d bytes with %d bytes of planes is not read in 16-byte lines",
-                kWho, t->world_stride, t->grid_pad);
+  if (int rc = view_record_lines(w, *v.t, g)) return rc;
   const int num_planes = r.num_classes + (r.facing ? 4 : 0);
   const uint64_t view = (uint64_t)num_planes * (uint64_t)g.VH * (uint64_t)g.VW, world = (uint64_t)g.P * view;
   if (view * (uint64_t)g.VH * (uint64_t)g.VW >= (1ull << 32))   // (a byte's plane is found with one multiply)
     return fail(MP_ERR_UNSUPPORTED, "%s: a viewer's planes are %llu bytes", kWho, (unsigned long long)view);
   if (r.op == MP_EGOPLANES_REGISTER) {
-    const uint64_t N = (uint64_t)e->N, block = N * world;
-    if (r.slots < 0) return fail(MP_ERR_INVALID, "%s: slots %d", kWho, r.slots);
-    if (r.slots > 0 && r.slots != e->ring_slots)
-      return fail(MP_ERR_INVALID, "%s: a ring of %d slots, the engine's ring has %d (mp_bind_output_ring; one "
-                  "position for all of them)", kWho, r.slots, e->ring_slots);
-    if (r.slots > 0 && r.slot_stride < block)
-      return fail(MP_ERR_INVALID, "%s: slot_stride %llu: a slot is %llu bytes", kWho,
-                  (unsigned long long)r.slot_stride, (unsigned long long)block);
-    const uint64_t need = r.slots > 0 ? (uint64_t)(r.slots - 1) * r.slot_stride + block : block;
-    if (r.dst_bytes < need)
-      return fail(MP_ERR_INVALID, "%s: the planes of %d worlds%s need %llu bytes, dst has %llu", kWho, e->N,
-                  r.slots > 0 ? " in every slot" : "", (unsigned long long)need, (unsigned long long)r.dst_bytes);
-    HIP_TRY(hipSetDevice(e->device));
-    if (int rc = check_device_pointer(e, r.dst, "MpEgoPlanes (dst)")) return rc;
-    if (int rc = check_bank(e, r.dst, need, "MpEgoPlanes (dst)")) return rc;
+    uint64_t need;
+    if (int rc = view_register(e, q, w, world, 1, &need)) return rc;
     if (int rc = check_bank(e, r.classes, (uint64_t)num_ids * 4, "MpEgoPlanes (classes)")) return rc;
     const ego_planes::Plan p = ego_planes::plan_of(g, num_planes, e->N, e->num_cus);
     if (p.waves < 1)
       return fail(MP_ERR_UNSUPPORTED, "%s: the value tables and one wave's render and bit planes need %d B of LDS",
                   kWho, p.lds);
-    e->ep_dst = (uint8_t*)r.dst;
-    e->ep_stride = r.slots > 0 ? r.slot_stride : 0;
-    e->ep_slots = r.slots;
-    e->ep_mask = layer_mask;
-    e->ep_classes = r.classes;
-    e->ep_num_classes = r.num_classes;
-    e->ep_facing = r.facing;
+    e->ep = registration_of(q);
+    e->ep.mask = layer_mask;
+    e->ep.classes = r.classes;
+    e->ep.num_classes = r.num_classes;
+    e->ep.facing = r.facing;
     return MP_OK;
   }
-  const bool live = r.op == MP_EGOPLANES_DRAW && !r.bank;
-  if (r.op == MP_EGOPLANES_HOST && !r.bank) return fail(MP_ERR_INVALID, "%s: NULL bank", kWho);
-  const int32_t src_rows = live ? e->N : r.bank_rows;
-  if (r.count < 1 || src_rows < 1)
-    return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", kWho, r.count, src_rows);
-  if (!r.rows && r.count > src_rows)
-    return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are drawn (count %d, there are %d "
-                "rows)", kWho, r.count, src_rows);
-  if (r.fingerprint != fingerprint)
-    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this %s (%016llx): they were "
-                "saved by an engine of another pack, player count or record layout", kWho,
-                (unsigned long long)r.fingerprint, e ? "engine's" : "pack's", (unsigned long long)fingerprint);
-  const uint64_t count = (uint64_t)r.count, need = count * (r.players ? view : world);
-  if (r.dst_bytes < need)
-    return fail(MP_ERR_INVALID, "%s: %d elements of %llu bytes need %llu bytes, dst has %llu", kWho, r.count,
-                (unsigned long long)(r.players ? view : world), (unsigned long long)need,
-                (unsigned long long)r.dst_bytes);
-  if (((uintptr_t)r.rows & 3) || ((uintptr_t)r.players & 3))
-    return fail(MP_ERR_INVALID, "%s: rows %p and players %p must be 4-byte aligned", kWho, (const void*)r.rows,
-                (const void*)r.players);
+  ViewSource s;
+  if (int rc = view_source(e, q, w, v, view, world, &s)) return rc;
   ego_planes::Args a = {};
-  a.g = g;
-  a.rows = r.rows; a.players = r.players; a.dst = (uint8_t*)r.dst;
-  a.src_rows = src_rows; a.count = r.count;
-  a.stride = t->world_stride; a.grid_pad = t->grid_pad;
+  view_args(&a, g, q, v, s);
+  a.dst = (uint8_t*)r.dst;
   a.layer_mask = layer_mask;
   a.classes = r.classes; a.num_ids = num_ids;
   a.num_classes = r.num_classes; a.facing = r.facing;
@@ -3061,128 +3015,52 @@ static int ego_planes_request(MpEngine* e, MpEgoPlanes* out) {
         return fail(MP_ERR_INVALID, "%s: classes[%d] = %d is outside [-1, num_classes = %d)", kWho, id,
                     r.classes[id], r.num_classes);
     a.src = (const uint8_t*)r.bank;
-    a.lut = host_lut.data();
+    a.lut = v.host_lut.data();
     uint32_t what = 0;
     const int bad = ego_planes::host(a, &what);
-    if (bad >= 0)
-      return fail(MP_ERR_INVALID, "%s: %s[%d] = %d is %s; the elements from %d on were left as they were", kWho,
-                  what == kFaultEgoPlanesRow ? "rows" : "players", bad,
-                  what == kFaultEgoPlanesRow ? (r.rows ? r.rows[bad] : bad) : r.players[bad],
-                  what == kFaultEgoPlanesRow ? "not a row of the bank" : "not a player of this pack", bad);
-    return MP_OK;
+    return bad >= 0 ? view_host_fault(q, w, bad, what == kFaultEgoPlanesRow) : MP_OK;
   }
-  if (live && !e->has_state)
-    return fail(MP_ERR_INVALID, "%s: the engine has never been reset; there is no state to draw", kWho);
-  if (!live && ((uintptr_t)r.bank & 15))   // (records are read in 16-byte lines)
-    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", kWho, r.bank);
-  HIP_TRY(hipSetDevice(e->device));
-  if (!live)
-    if (int rc = check_bank(e, r.bank, (uint64_t)r.bank_rows * (uint64_t)t->world_stride, "MpEgoPlanes (bank)"))
-      return rc;
-  if (r.rows)
-    if (int rc = check_bank(e, r.rows, count * 4, "MpEgoPlanes (rows)")) return rc;
-  if (r.players)
-    if (int rc = check_bank(e, r.players, count * 4, "MpEgoPlanes (players)")) return rc;
-  if (int rc = check_bank(e, r.classes, (uint64_t)num_ids * 4, "MpEgoPlanes (classes)")) return rc;
-  if (int rc = check_bank(e, r.dst, need, "MpEgoPlanes (dst)")) return rc;
+  if (int rc = view_device_source(e, q, w, s, r.classes, (uint64_t)num_ids * 4)) return rc;
   const ego_planes::Plan p = ego_planes::plan_of(g, num_planes, r.count, e->num_cus);
   if (p.waves < 1)
     return fail(MP_ERR_UNSUPPORTED, "%s: the value tables and one wave's render and bit planes need %d B of LDS",
                 kWho, p.lds);
-  a.src = live ? e->d_state : (const uint8_t*)r.bank;
+  a.src = s.live ? e->d_state : (const uint8_t*)r.bank;
   a.lut = e->d_layer_lut; a.fault = e->t.fault;
   ego_planes::launch(a, p, e->stream);
   HIP_TRY(hipGetLastError());
   return MP_OK;
 }
 
-static_assert(sizeof(MpEgoPlanes) == 160 && sizeof(MpEgoPlanes) != sizeof(MpStepMany) &&
-                  sizeof(MpEgoPlanes) != sizeof(MpStateLayout) && sizeof(MpEgoPlanes) != sizeof(MpStepUntil) &&
-                  sizeof(MpEgoPlanes) != sizeof(MpStatesHash) && sizeof(MpEgoPlanes) != sizeof(MpStepActive) &&
-                  sizeof(MpEgoPlanes) != sizeof(MpStepListed) && sizeof(MpEgoPlanes) != sizeof(MpEpisodeStats) &&
-                  sizeof(MpEgoPlanes) != sizeof(MpStatesCheck) && sizeof(MpEgoPlanes) != sizeof(MpStatesView) &&
-                  sizeof(MpEgoPlanes) != sizeof(MpEpisodeStarts) && sizeof(MpEgoPlanes) != sizeof(MpStatesObserve) &&
-                  sizeof(MpEgoPlanes) != sizeof(MpWorldStates) && sizeof(MpEgoPlanes) != sizeof(MpKernelVariant) &&
-                  sizeof(MpEgoPlanes) != sizeof(MpStepTrajectory) && sizeof(MpEgoPlanes) != sizeof(MpEgoLayer) &&
-                  sizeof(MpEgoPlanes) != sizeof(MpViewHash) && sizeof(MpEgoPlanes) < 448,
-              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
-static_assert(sizeof(MpViewHash) == 152 &&sizeof(MpViewHash) != sizeof(MpStepMany) &&
-                  sizeof(MpViewHash) != sizeof(MpStateLayout) && sizeof(MpViewHash) != sizeof(MpStepUntil) &&
-                  sizeof(MpViewHash) != sizeof(MpStatesHash) && sizeof(MpViewHash) != sizeof(MpStepActive) &&
-                  sizeof(MpViewHash) != sizeof(MpStepListed) && sizeof(MpViewHash) != sizeof(MpEpisodeStats) &&
-                  sizeof(MpViewHash) != sizeof(MpStatesCheck) && sizeof(MpViewHash) != sizeof(MpStatesView) &&
-                  sizeof(MpViewHash) != sizeof(MpEpisodeStarts) && sizeof(MpViewHash) != sizeof(MpStatesObserve) &&
-                  sizeof(MpViewHash) != sizeof(MpWorldStates) && sizeof(MpViewHash) != sizeof(MpKernelVariant) &&
-                  sizeof(MpViewHash) != sizeof(MpStepTrajectory) && sizeof(MpViewHash) != sizeof(MpEgoLayer) &&
-                  sizeof(MpViewHash) < 448,
-              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
-static_assert(sizeof(MpEgoLayer) == 128 && sizeof(MpEgoLayer) != sizeof(MpStepMany) &&
-                  sizeof(MpEgoLayer) != sizeof(MpStateLayout) && sizeof(MpEgoLayer) != sizeof(MpStepUntil) &&
-                  sizeof(MpEgoLayer) != sizeof(MpStatesHash) && sizeof(MpEgoLayer) != sizeof(MpStepActive) &&
-                  sizeof(MpEgoLayer) != sizeof(MpStepListed) && sizeof(MpEgoLayer) != sizeof(MpEpisodeStats) &&
-                  sizeof(MpEgoLayer) != sizeof(MpStatesCheck) && sizeof(MpEgoLayer) != sizeof(MpStatesView) &&
-                  sizeof(MpEgoLayer) != sizeof(MpEpisodeStarts) && sizeof(MpEgoLayer) != sizeof(MpStatesObserve) &&
-                  sizeof(MpEgoLayer) != sizeof(MpWorldStates) && sizeof(MpEgoLayer) != sizeof(MpKernelVariant) &&
-                  sizeof(MpEgoLayer) != sizeof(MpStepTrajectory) && sizeof(MpEgoLayer) < 448,
-              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
-static_assert(sizeof(MpEpisodeStats) == 224 && sizeof(MpEventColumn) == 32 && sizeof(MpStatsBank) == 32 &&
-                  sizeof(MpEpisodeStats) != sizeof(MpStepListed) && sizeof(MpEpisodeStats) != sizeof(MpStepUntil) &&
-                  sizeof(MpEpisodeStats) != sizeof(MpStepActive) && sizeof(MpEpisodeStats) != sizeof(MpStateLayout) &&
-                  sizeof(MpEpisodeStats) != sizeof(MpStepMany) && sizeof(MpEpisodeStats) < 448,
-              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
-static_assert(sizeof(MpStatesObserve) == 64 && sizeof(MpStatesObserve) != sizeof(MpKernelVariant) &&
-                  sizeof(MpStatesObserve) != sizeof(MpWorldStates) && sizeof(MpStatesObserve) != sizeof(MpStepMany) &&
-                  sizeof(MpStatesObserve) != sizeof(MpStepTrajectory),
-              "mp_snapshot / mp_restore tell their requests apart by size");
-static_assert(sizeof(MpKernelVariant) != sizeof(MpWorldStates) && sizeof(MpKernelVariant) != sizeof(MpStepMany) &&
-                  sizeof(MpStepTrajectory) != sizeof(MpKernelVariant) && sizeof(MpStepTrajectory) != sizeof(MpWorldStates) &&
-                  sizeof(MpStepTrajectory) != sizeof(MpStepMany) && sizeof(MpStepTrajectory) < 448,
-              "mp_snapshot / mp_restore tell their requests apart by size");
-static_assert(sizeof(MpStateLayout) == 120 && sizeof(MpStatesCheck) == 88 && sizeof(MpStateField) == 32,
+// mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes): the 17.
+constexpr size_t kRequestSizes[] = {
+    sizeof(MpKernelVariant), sizeof(MpWorldStates), sizeof(MpStatesObserve), sizeof(MpStepMany),
+    sizeof(MpStepTrajectory), sizeof(MpStateLayout), sizeof(MpStatesCheck), sizeof(MpStatesHash),
+    sizeof(MpEpisodeStarts), sizeof(MpStatesView), sizeof(MpStepActive), sizeof(MpStepUntil),
+    sizeof(MpStepListed), sizeof(MpEpisodeStats), sizeof(MpEgoLayer), sizeof(MpViewHash), sizeof(MpEgoPlanes)};
+constexpr bool request_sizes_tell_apart() {
+  for (size_t i = 0; i < sizeof kRequestSizes / sizeof kRequestSizes[0]; ++i) {
+    if (kRequestSizes[i] >= 448) return false;
+    for (size_t j = 0; j < i; ++j)
+      if (kRequestSizes[i] == kRequestSizes[j]) return false;
+  }
+  return true;
+}
+static_assert(request_sizes_tell_apart(), "two requests of one size, or one the size of a snapshot");
+static_assert(sizeof(MpEgoPlanes) == 160 && sizeof(MpViewHash) == 152 && sizeof(MpEgoLayer) == 128 &&
+                  sizeof(MpEpisodeStats) == 224 && sizeof(MpEventColumn) == 32 && sizeof(MpStatsBank) == 32 &&
+                  sizeof(MpStatesObserve) == 64 && sizeof(MpStateLayout) == 120 && sizeof(MpStatesCheck) == 88 &&
+                  sizeof(MpStateField) == 32 && sizeof(MpStatesHash) == 104 && sizeof(MpEpisodeStarts) == 72 &&
+                  sizeof(MpStatesView) == 80 && sizeof(MpStepActive) == 96 && sizeof(MpStepUntil) == 136 &&
+                  sizeof(MpStepListed) == 176,
               "the layouts include/mp_engine.h documents");
-#define MP_SIZE_DIFFERS(A)                                                                          \
-  (sizeof(A) != sizeof(MpStatesObserve) && sizeof(A) != sizeof(MpKernelVariant) &&                  \
-   sizeof(A) != sizeof(MpWorldStates) && sizeof(A) != sizeof(MpStepMany) && sizeof(A) != sizeof(MpStepTrajectory))
-static_assert(MP_SIZE_DIFFERS(MpStateLayout) && MP_SIZE_DIFFERS(MpStatesCheck) &&
-                  sizeof(MpStateLayout) != sizeof(MpStatesCheck) && sizeof(MpStateLayout) < 448 &&
-                  sizeof(MpStatesCheck) < 448,
-              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
-static_assert(sizeof(MpStatesHash) == 104 && MP_SIZE_DIFFERS(MpStatesHash) &&
-                  sizeof(MpStatesHash) != sizeof(MpStateLayout) && sizeof(MpStatesHash) != sizeof(MpStatesCheck),
-              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
-static_assert(sizeof(MpEpisodeStarts) == 72 && MP_SIZE_DIFFERS(MpEpisodeStarts) &&
-                  sizeof(MpEpisodeStarts) != sizeof(MpStateLayout) && sizeof(MpEpisodeStarts) != sizeof(MpStatesCheck) &&
-                  sizeof(MpEpisodeStarts) != sizeof(MpStatesHash),
-              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
-static_assert(sizeof(MpStatesView) == 80 && MP_SIZE_DIFFERS(MpStatesView) &&
-                  sizeof(MpStatesView) != sizeof(MpStateLayout) && sizeof(MpStatesView) != sizeof(MpStatesCheck) &&
-                  sizeof(MpStatesView) != sizeof(MpStatesHash) && sizeof(MpStatesView) != sizeof(MpEpisodeStarts),
-              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
-static_assert(sizeof(MpStepActive) == 96 && MP_SIZE_DIFFERS(MpStepActive) &&
-                  sizeof(MpStepActive) != sizeof(MpStateLayout) && sizeof(MpStepActive) != sizeof(MpStatesCheck) &&
-                  sizeof(MpStepActive) != sizeof(MpStatesHash) && sizeof(MpStepActive) != sizeof(MpEpisodeStarts) &&
-                  sizeof(MpStepActive) != sizeof(MpStatesView) && sizeof(MpStepActive) < 448,
-              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
-static_assert(sizeof(MpStepUntil) == 136 && MP_SIZE_DIFFERS(MpStepUntil) &&
-                  sizeof(MpStepUntil) != sizeof(MpStateLayout) && sizeof(MpStepUntil) != sizeof(MpStatesCheck) &&
-                  sizeof(MpStepUntil) != sizeof(MpStatesHash) && sizeof(MpStepUntil) != sizeof(MpEpisodeStarts) &&
-                  sizeof(MpStepUntil) != sizeof(MpStatesView) && sizeof(MpStepUntil) != sizeof(MpStepActive) &&
-                  sizeof(MpStepUntil) < 448,
-              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
 static_assert(offsetof(MpStepUntil, active_step_bytes) == offsetof(MpStepActive, active_step_bytes) &&
                   offsetof(MpStepUntil, stop) == offsetof(MpStepActive, reserved),
               "MpStepUntil's leading fields are MpStepActive's");
-static_assert(sizeof(MpStepListed) == 176 && MP_SIZE_DIFFERS(MpStepListed) &&
-                  sizeof(MpStepListed) != sizeof(MpStateLayout) && sizeof(MpStepListed) != sizeof(MpStatesCheck) &&
-                  sizeof(MpStepListed) != sizeof(MpStatesHash) && sizeof(MpStepListed) != sizeof(MpEpisodeStarts) &&
-                  sizeof(MpStepListed) != sizeof(MpStatesView) && sizeof(MpStepListed) != sizeof(MpStepActive) &&
-                  sizeof(MpStepListed) != sizeof(MpStepUntil) && sizeof(MpStepListed) < 448,
-              "mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes)");
 static_assert(offsetof(MpStepListed, gamma) == offsetof(MpStepUntil, gamma) &&
                   offsetof(MpStepListed, reserved) == offsetof(MpStepUntil, reserved) &&
                   offsetof(MpStepListed, worlds) == sizeof(MpStepUntil),
               "MpStepListed's leading fields are MpStepUntil's");
-#undef MP_SIZE_DIFFERS
 // An MpKernelVariant request (carried by mp_snapshot; `e` may be NULL: the host-only question).
 static int kernel_variant(const MpEngine* e, MpKernelVariant* r) {
   if (r->struct_size != sizeof(MpKernelVariant))

@@ -72,9 +72,7 @@ struct Args {
 // (the workgroup's copy of the viewers' value tables with the classes folded in, [P][kLayerLutRow],
 // then every wave's planes and head).  waves == 0: the tables and one wave's planes do not fit the
 // LDS (`lds` = what they would take).
-struct Plan {
-  int32_t waves, groups, lds;
-};
+using ego_layer::Plan;
 Plan plan_of(const Window& g, int count, int num_cus);
 
 // k_view_hash_rows (players == NULL) or k_view_hash_views, on `stream`.

@@ -1,29 +1,22 @@
 // view_hash.hip — the hash of a player's view (an MpViewHash request, include/mp_engine.h;
 // view_hash.h has the function): V of every viewer of bank rows or of the engine's worlds, worked
 // out from the records where they lie.  No view is drawn, no world is loaded, nothing of the
-// engine's is written.  A unit of its own: ego_layer.hip, state_hash.hip, the frame and the step
-// kernels compile to exactly what they compiled to before.
+// engine's is written.  One of the three units of view_unit.h, which has what they share: the
+// staged record, the report of a skipped rows[] / players[] index, the launch plan.
 //
 //   k_view_hash_rows    every viewer of a row: one wave per row, the row's u64 [P] block (the
 //                       registered tensor; a draw without players);
 //   k_view_hash_views   one viewer of a row: one wave per (row, player), one u64.
-// Both are one body, modelled on ego_layer.hip's.  The workgroup copies the viewers' value tables
-// [P][kLayerLutRow] into LDS once, through the class table when there is one (classes[lut[p][s]]:
-// the word function then finds a word's class with the one LDS read that finds its id, and no
-// global load waits in the chain of a word).  A wave stages what the value function reads of its
-// record in its share of the LDS — the render planes and the head of the tail, 16-byte loads,
-// eight of a lane in flight.  Lane i takes words i, i + 64, ... of a viewer, four of them at a
+// Both are one body.  The workgroup copies the viewers' value tables [P][kLayerLutRow] into LDS
+// once, through the class table when there is one (classes[lut[p][s]]: the word function then
+// finds a word's class with the one LDS read that finds its id, and no global load waits in the
+// chain of a word).  Lane i takes words i, i + 64, ... of a viewer, four of them at a
 // time: ego_layer::value on the folded table, fmix64, a u64 sum in registers; the lanes' sums meet
 // in state_hash::wave_sum (__shfl_xor, no LDS and no atomics).  k_view_hash_rows leaves viewer p's
 // V in lane p and stores the row's block when all P are there: a u64 before the block's first
 // 16-byte boundary, 16-byte stores of two neighbouring viewers, a u64 behind them.
 // k_view_hash_views stores its 8 bytes from lane 0.
-// An index of rows[] that is no row or of players[] outside [0, P) is never used as one: its
-// element of the destination stays as it was — every such element — and ONE of them is reported
-// through the fault words (FAULT_STATE_INDEX; the first to claim them).
-#include <stddef.h>
-
-#include "step_common.h"
+#include "view_unit.h"
 #include "view_hash.h"
 
 namespace view_hash {
@@ -33,30 +26,17 @@ namespace {
 using state_hash::fmix64;
 using state_hash::wave_sum;
 using stepk::div_by;
-using stepk::issued;
 using stepk::magic_of;
 using stepk::wsync;
+using view_unit::kHead;
+using view_unit::kMaxWaves;
+using view_unit::planes_vec;
+using view_unit::tables_bytes;
 
-constexpr int kLdsMax = 160 * 1024;
-constexpr int kMaxWaves = 16;
-constexpr int kHead = 4 * MP_MAX_PLAYERS;   // ax, ay, aori, aalive
-static_assert(offsetof(WorldTail, ax) == 0 && offsetof(WorldTail, ay) == MP_MAX_PLAYERS &&
-                  offsetof(WorldTail, aori) == 2 * MP_MAX_PLAYERS && offsetof(WorldTail, aalive) == 3 * MP_MAX_PLAYERS,
-              "the staged head of the tail is ax, ay, aori, aalive");
 static_assert(MP_MAX_PLAYERS <= 64, "lane p of a wave keeps viewer p's hash");
 
-// the workgroup's value tables in whole 16-byte vectors; a wave's LDS: the render planes in whole
-// 16-byte vectors, then the head
-__host__ __device__ inline int tables_bytes(const Window& g) { return ((g.P * kLayerLutRow * 4 + 15) >> 4) * 16; }
-__host__ __device__ inline int planes_vec(const Window& g) { return (g.L * g.HW + 15) >> 4; }
+// a wave's LDS, behind the workgroup's value tables: the render planes, then the head
 __host__ __device__ inline int per_wave(const Window& g) { return planes_vec(g) * 16 + kHead; }
-
-__device__ inline void report_index(uint32_t* fault, int lane, int at, int index, uint32_t what) {
-  if (lane == 0 && atomicCAS(&fault[FAULT_STATE_INDEX], 0u, (uint32_t)at + 1u) == 0u) {
-    fault[FAULT_STATE_INDEX + 1] = (uint32_t)index;
-    fault[FAULT_STATE_INDEX + 2] = what;
-  }
-}
 
 // lane `from`'s u64 (`from` < 64; called by all 64 lanes)
 __device__ inline uint64_t lane_u64(uint64_t v, int from) {
@@ -88,35 +68,15 @@ __device__ inline void hash_body(const Args& a, uint8_t* smem) {
 
   for (int i = (int)blockIdx.x * waves + wave; i < a.count; i += (int)gridDim.x * waves) {
     const int r = __builtin_amdgcn_readfirstlane(a.rows ? a.rows[i] : i);
-    if (r < 0 || r >= a.src_rows) { report_index(a.fault, lane, i, r, kFaultViewHashRow); continue; }
+    if (r < 0 || r >= a.src_rows) { view_unit::report_index(a.fault, lane, i, r, kFaultViewHashRow); continue; }
     uint32_t p0 = 0u;
     if constexpr (!kAll) {
       const int p = __builtin_amdgcn_readfirstlane(a.players[i]);
-      if (p < 0 || p >= g.P) { report_index(a.fault, lane, i, p, kFaultViewHashPlayer); continue; }
+      if (p < 0 || p >= g.P) { view_unit::report_index(a.fault, lane, i, p, kFaultViewHashPlayer); continue; }
       p0 = (uint32_t)p;
     }
     wsync();   // (the element before this one has left the wave's LDS)
-    {
-      const uint4* src = reinterpret_cast<const uint4*>(a.src + (size_t)r * (size_t)a.stride);
-      uint4* out = reinterpret_cast<uint4*>(planes);
-      const uint4 hv = lane < kHead / 16 ? src[(a.grid_pad >> 4) + lane] : uint4{0u, 0u, 0u, 0u};
-      for (int i0 = 0; i0 < nvec; i0 += 8 * 64) {
-        uint4 v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const int j = i0 + k * 64 + lane;
-          v[k] = src[j < nvec ? j : nvec - 1];
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) issued(v[k]);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const int j = i0 + k * 64 + lane;
-          if (j < nvec) out[j] = v[k];
-        }
-      }
-      if (lane < kHead / 16) reinterpret_cast<uint4*>(head)[lane] = hv;
-    }
+    view_unit::stage_record(a.src + (size_t)r * (size_t)a.stride, a.grid_pad, nvec, lane, planes, head);
     wsync();
 
     // this lane's share of viewer p's sum: words lane, lane + 64, ...
@@ -166,65 +126,28 @@ __global__ __launch_bounds__(kMaxWaves * 64) void k_view_hash_views(Args a) {
 }
 
 Plan plan_of(const Window& g, int count, int num_cus) {
-  Plan p = {};
-  const int per = per_wave(g), cls = tables_bytes(g);
-  int fit = cls < kLdsMax ? (kLdsMax - cls) / per : 0;
-  if (fit < 1) { p.lds = cls + per; return p; }
-  if (fit > kMaxWaves) fit = kMaxWaves;
-  // every CU a workgroup before a workgroup gets more waves
-  const int cus = num_cus > 0 ? num_cus : 1;
-  int waves = (count + cus - 1) / cus;
-  if (waves < 4) waves = 4;
-  if (waves > fit) waves = fit;
-  if (waves > count) waves = count;
-  p.waves = waves;
-  p.groups = (count + waves - 1) / waves;
-  if (p.groups > 2 * cus) p.groups = 2 * cus;   // (a wave then hashes several elements in turn)
-  p.lds = cls + waves * per;
-  return p;
+  return view_unit::plan_of(tables_bytes(g), per_wave(g), count, num_cus);
 }
 
 void launch(const Args& a, const Plan& p, hipStream_t stream) {
-  if (a.players)
-    hipLaunchKernelGGL(k_view_hash_views, dim3((unsigned)p.groups), dim3((unsigned)p.waves * 64u), (size_t)p.lds,
-                       stream, a);
-  else
-    hipLaunchKernelGGL(k_view_hash_rows, dim3((unsigned)p.groups), dim3((unsigned)p.waves * 64u), (size_t)p.lds,
-                       stream, a);
+  view_unit::launch(k_view_hash_rows, k_view_hash_views, a, p, stream);
 }
 
-int prepare() {
-  const void* k[2] = {reinterpret_cast<const void*>(&k_view_hash_rows),
-                      reinterpret_cast<const void*>(&k_view_hash_views)};
-  for (const void* f : k) {
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
-}
+int prepare() { return view_unit::prepare(k_view_hash_rows, k_view_hash_views); }
 
 int host(const Args& a, uint32_t* what) {
   const Window& g = a.g;
-  for (int i = 0; i < a.count; ++i) {
-    const int r = a.rows ? a.rows[i] : i;
-    if (r < 0 || r >= a.src_rows) { *what = kFaultViewHashRow; return i; }
-    const int p = a.players ? a.players[i] : 0;
-    if (p < 0 || p >= g.P) { *what = kFaultViewHashPlayer; return i; }
-    const uint8_t* rec = a.src + (size_t)r * (size_t)a.stride;
-    const int np = a.players ? 1 : g.P;
-    uint64_t* blk = a.dst + (size_t)i * np;
-    for (int q = 0; q < np; ++q) {
-      uint64_t sum = 0;
-      uint32_t e = 0;
-      for (int vy = 0; vy < g.VH; ++vy)
-        for (int vx = 0; vx < g.VW; ++vx)
-          for (int l = 0; l < g.L; ++l, ++e)
-            sum += term(g, rec, rec + a.grid_pad, a.lut, a.classes, a.layer_mask, (uint32_t)(p + q), e, (uint32_t)vx,
-                        (uint32_t)vy, (uint32_t)l);
-      blk[q] = fmix64(sum);
-    }
-  }
-  return -1;
+  return view_unit::host_each(a, kFaultViewHashRow, kFaultViewHashPlayer, what,
+                              [&](int i, const uint8_t* rec, uint32_t p, int q, int np) {
+    uint64_t sum = 0;
+    uint32_t e = 0;
+    for (int vy = 0; vy < g.VH; ++vy)
+      for (int vx = 0; vx < g.VW; ++vx)
+        for (int l = 0; l < g.L; ++l, ++e)
+          sum += term(g, rec, rec + a.grid_pad, a.lut, a.classes, a.layer_mask, p, e, (uint32_t)vx, (uint32_t)vy,
+                      (uint32_t)l);
+    a.dst[(size_t)i * np + q] = fmix64(sum);
+  });
 }
 
 }  // namespace view_hash

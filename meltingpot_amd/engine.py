@@ -478,6 +478,33 @@ def check_states_host(pack_bytes: bytes, rows, *, fingerprint: Optional[int] = N
   return out
 
 
+def _view_host_source(who: str, verb: str, pack_bytes: bytes, rows, players, which, fingerprint, num_players, dev):
+  """What ego_layer_host, hash_views_host and ego_planes_host marshal alike: the host bank, `which`
+  and `players` as int32 arrays, the count.  Returns (layout, the result's leading shape — (R,) or
+  (R, P) —, the request's source fields, what must stay alive over the call)."""
+  L = load_library()
+  bank = np.ascontiguousarray(rows, np.uint8)
+  if bank.ndim != 2 or bank.shape[0] < 1:
+    raise ValueError(f"{who}: rows must be a uint8 array [M, S]")
+  keep = _host_config(pack_bytes, num_players, dev)
+  layout = _layout_request(L, None, pack_bytes, num_players, dev)
+  if bank.shape[1] != layout.world_stride:
+    raise ValueError(f"{who}: rows of {bank.shape[1]} bytes, the pack's are {layout.world_stride}")
+  idx = None if which is None else np.ascontiguousarray(np.asarray(which).reshape(-1), np.int32)
+  ply = None if players is None else np.ascontiguousarray(np.asarray(players).reshape(-1), np.int32)
+  count = int(ply.size) if ply is not None else bank.shape[0] if idx is None else int(idx.size)
+  if count < 1:
+    raise ValueError(f"{who}: no rows to {verb}")
+  if idx is not None and int(idx.size) != count:
+    raise ValueError(f"{who}: which has {int(idx.size)} entries, players {count}")
+  fields = dict(fingerprint=layout.fingerprint if fingerprint is None else int(fingerprint),
+                pack=ctypes.addressof(keep[0]), pack_len=len(pack_bytes),
+                cfg=ctypes.cast(ctypes.pointer(keep[1]), ctypes.c_void_p), bank=bank.ctypes.data,
+                bank_rows=int(bank.shape[0]), rows=None if idx is None else idx.ctypes.data,
+                players=None if ply is None else ply.ctypes.data, count=count)
+  return layout, (count,) + ((layout.P,) if ply is None else ()), fields, (keep, bank, idx, ply)
+
+
 def ego_layer_host(pack_bytes: bytes, rows, players=None, *, which=None, fingerprint: Optional[int] = None,
                    num_players: int = 0, dev: Optional[Dict[str, int]] = None) -> np.ndarray:
   """EGO_LAYER of host rows (uint8 [M, S] array) by the library's host-only form (MP_EGO_HOST: the
@@ -485,32 +512,10 @@ def ego_layer_host(pack_bytes: bytes, rows, players=None, *, which=None, fingerp
   order, repeats allowed (default: all).  `players` None: int32 [R, P, VH, VW, L], every viewer of
   each row; else R ints, and the result is int32 [R, VH, VW, L], the view of player players[i] of
   the i-th drawn row.  `fingerprint`: the rows' (default: the pack's)."""
-  L = load_library()
-  bank = np.ascontiguousarray(rows, np.uint8)
-  if bank.ndim != 2 or bank.shape[0] < 1:
-    raise ValueError("ego_layer_host: rows must be a uint8 array [M, S]")
-  keep = _host_config(pack_bytes, num_players, dev)
-  layout = _layout_request(L, None, pack_bytes, num_players, dev)
-  if bank.shape[1] != layout.world_stride:
-    raise ValueError(f"ego_layer_host: rows of {bank.shape[1]} bytes, the pack's are {layout.world_stride}")
-  idx = None if which is None else np.ascontiguousarray(np.asarray(which).reshape(-1), np.int32)
-  ply = None if players is None else np.ascontiguousarray(np.asarray(players).reshape(-1), np.int32)
-  count = int(ply.size) if ply is not None else bank.shape[0] if idx is None else int(idx.size)
-  if count < 1:
-    raise ValueError("ego_layer_host: no rows to draw")
-  if idx is not None and int(idx.size) != count:
-    raise ValueError(f"ego_layer_host: which has {int(idx.size)} entries, players {count}")
-  from meltingpot_amd import lower, pack as pack_lib
-  hdr = pack_lib.loads(pack_bytes)["hdr"]
-  view = (int(hdr[lower.HDR_VF]) + int(hdr[lower.HDR_VB]) + 1, int(hdr[lower.HDR_VL]) + int(hdr[lower.HDR_VR]) + 1,
-          int(hdr[lower.HDR_L]))
-  out = np.zeros((count,) + ((layout.P,) if ply is None else ()) + view, np.int32)
-  ego_layer_request(L, None, MP_EGO_HOST, fingerprint=layout.fingerprint if fingerprint is None else int(fingerprint),
-                    pack=ctypes.addressof(keep[0]), pack_len=len(pack_bytes),
-                    cfg=ctypes.cast(ctypes.pointer(keep[1]), ctypes.c_void_p), bank=bank.ctypes.data,
-                    bank_rows=int(bank.shape[0]), rows=None if idx is None else idx.ctypes.data,
-                    players=None if ply is None else ply.ctypes.data, count=count, dst=out.ctypes.data,
-                    dst_bytes=out.nbytes)
+  layout, lead, src, _alive = _view_host_source("ego_layer_host", "draw", pack_bytes, rows, players, which,
+                                                fingerprint, num_players, dev)
+  out = np.zeros(lead + _view_window(pack_bytes) + (layout.L,), np.int32)
+  ego_layer_request(load_library(), None, MP_EGO_HOST, dst=out.ctypes.data, dst_bytes=out.nbytes, **src)
   return out
 
 
@@ -688,32 +693,14 @@ def hash_views_host(pack_bytes: bytes, rows, players=None, *, which=None, layers
   the hash of player players[i] of the i-th row.  `layers`: the layer indices that count (None:
   all); `classes`: int32 [num_layer_ids_host(pack)] mapping every id to its class (None: the ids
   themselves).  `fingerprint`: the rows' (default: the pack's)."""
-  L = load_library()
-  bank = np.ascontiguousarray(rows, np.uint8)
-  if bank.ndim != 2 or bank.shape[0] < 1:
-    raise ValueError("hash_views_host: rows must be a uint8 array [M, S]")
-  keep = _host_config(pack_bytes, num_players, dev)
-  layout = _layout_request(L, None, pack_bytes, num_players, dev)
-  if bank.shape[1] != layout.world_stride:
-    raise ValueError(f"hash_views_host: rows of {bank.shape[1]} bytes, the pack's are {layout.world_stride}")
-  idx = None if which is None else np.ascontiguousarray(np.asarray(which).reshape(-1), np.int32)
-  ply = None if players is None else np.ascontiguousarray(np.asarray(players).reshape(-1), np.int32)
-  count = int(ply.size) if ply is not None else bank.shape[0] if idx is None else int(idx.size)
-  if count < 1:
-    raise ValueError("hash_views_host: no rows to hash")
-  if idx is not None and int(idx.size) != count:
-    raise ValueError(f"hash_views_host: which has {int(idx.size)} entries, players {count}")
+  layout, lead, src, _alive = _view_host_source("hash_views_host", "hash", pack_bytes, rows, players, which,
+                                                fingerprint, num_players, dev)
   cls = None if classes is None else _view_classes(classes, num_layer_ids_host(pack_bytes, num_players=num_players,
                                                                                dev=dev))
-  out = np.zeros((count,) + ((layout.P,) if ply is None else ()), np.int64)
-  view_hash_request(L, None, MP_VIEWHASH_HOST,
-                    fingerprint=layout.fingerprint if fingerprint is None else int(fingerprint),
-                    pack=ctypes.addressof(keep[0]), pack_len=len(pack_bytes),
-                    cfg=ctypes.cast(ctypes.pointer(keep[1]), ctypes.c_void_p), bank=bank.ctypes.data,
-                    bank_rows=int(bank.shape[0]), rows=None if idx is None else idx.ctypes.data,
-                    players=None if ply is None else ply.ctypes.data, count=count,
-                    layer_mask=view_layer_mask(layers, layout.L), classes=None if cls is None else cls.ctypes.data,
-                    classes_len=0 if cls is None else int(cls.size), dst=out.ctypes.data, dst_bytes=out.nbytes)
+  out = np.zeros(lead, np.int64)
+  view_hash_request(load_library(), None, MP_VIEWHASH_HOST, layer_mask=view_layer_mask(layers, layout.L),
+                    classes=None if cls is None else cls.ctypes.data, classes_len=0 if cls is None else int(cls.size),
+                    dst=out.ctypes.data, dst_bytes=out.nbytes, **src)
   return out
 
 
@@ -787,33 +774,14 @@ def ego_planes_host(pack_bytes: bytes, rows, classes, players=None, *, which=Non
   id to its class (-1: none); C = `num_classes`, by default 1 + the largest; C' = C + 4 with
   `facing`.  `which`: the rows, in order, repeats allowed (default: all).  `layers`: the layer
   indices that count (None: all).  `fingerprint`: the rows' (default: the pack's)."""
-  L = load_library()
-  bank = np.ascontiguousarray(rows, np.uint8)
-  if bank.ndim != 2 or bank.shape[0] < 1:
-    raise ValueError("ego_planes_host: rows must be a uint8 array [M, S]")
-  keep = _host_config(pack_bytes, num_players, dev)
-  layout = _layout_request(L, None, pack_bytes, num_players, dev)
-  if bank.shape[1] != layout.world_stride:
-    raise ValueError(f"ego_planes_host: rows of {bank.shape[1]} bytes, the pack's are {layout.world_stride}")
-  idx = None if which is None else np.ascontiguousarray(np.asarray(which).reshape(-1), np.int32)
-  ply = None if players is None else np.ascontiguousarray(np.asarray(players).reshape(-1), np.int32)
-  count = int(ply.size) if ply is not None else bank.shape[0] if idx is None else int(idx.size)
-  if count < 1:
-    raise ValueError("ego_planes_host: no rows to draw")
-  if idx is not None and int(idx.size) != count:
-    raise ValueError(f"ego_planes_host: which has {int(idx.size)} entries, players {count}")
+  layout, lead, src, _alive = _view_host_source("ego_planes_host", "draw", pack_bytes, rows, players, which,
+                                                fingerprint, num_players, dev)
   cls, C = _plane_classes(classes, num_layer_ids_host(pack_bytes, num_players=num_players, dev=dev), num_classes)
   mask = view_layer_mask(layers, layout.L)
-  hdr = _view_window(pack_bytes)
-  out = np.zeros((count,) + ((layout.P,) if ply is None else ()) + (C + (4 if facing else 0),) + hdr, np.uint8)
-  ego_planes_request(L, None, MP_EGOPLANES_HOST,
-                     fingerprint=layout.fingerprint if fingerprint is None else int(fingerprint),
-                     pack=ctypes.addressof(keep[0]), pack_len=len(pack_bytes),
-                     cfg=ctypes.cast(ctypes.pointer(keep[1]), ctypes.c_void_p), bank=bank.ctypes.data,
-                     bank_rows=int(bank.shape[0]), rows=None if idx is None else idx.ctypes.data,
-                     players=None if ply is None else ply.ctypes.data, count=count, layer_mask=mask,
-                     classes=cls.ctypes.data, classes_len=int(cls.size), num_classes=C, facing=int(bool(facing)),
-                     dst=out.ctypes.data, dst_bytes=out.nbytes)
+  out = np.zeros(lead + (C + (4 if facing else 0),) + _view_window(pack_bytes), np.uint8)
+  ego_planes_request(load_library(), None, MP_EGOPLANES_HOST, layer_mask=mask, classes=cls.ctypes.data,
+                     classes_len=int(cls.size), num_classes=C, facing=int(bool(facing)), dst=out.ctypes.data,
+                     dst_bytes=out.nbytes, **src)
   return out
 
 
@@ -2656,6 +2624,51 @@ class Engine:
     self._state_args = (bank, r, p, out)   # (kept until the next call: the launch may not have run yet)
     return out
 
+  def _view_source(self, who: str, verb: str, bank, rows, players, fingerprint):
+    """What observe_ego_layer, hash_views and observe_ego_planes read: the checked `bank` (None: the
+    engine's worlds), `rows` and `players` as device ints, the count.  Returns (count, rows,
+    players, the request's source fields)."""
+    t = self._torch
+    S = int(self.info.world_state_bytes)
+    if bank is not None:
+      if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
+          bank.shape[1] != S or not bank.is_contiguous()):
+        raise ValueError(f"{who}: bank must be a contiguous uint8 tensor [M, {S}]")
+      if bank.shape[0] < 1:
+        raise ValueError(f"{who}: the bank has no rows")
+    there = self.N if bank is None else int(bank.shape[0])
+    p = None if players is None else self._device_ints(players, "players")
+    r = None if rows is None else self._device_ints(rows, "rows")
+    count = int(p.numel()) if p is not None else int(r.numel()) if r is not None else there
+    if count < 1:
+      raise ValueError(f"{who}: no views to {verb}")
+    if r is not None and int(r.numel()) != count:
+      raise ValueError(f"{who}: rows has {int(r.numel())} entries, players {count}")
+    fields = dict(fingerprint=self.state_fingerprint if fingerprint is None else int(fingerprint),
+                  bank=None if bank is None else bank.data_ptr(), bank_rows=0 if bank is None else there,
+                  rows=None if r is None else r.data_ptr(), players=None if p is None else p.data_ptr(), count=count)
+    return count, r, p, fields
+
+  def _view_out(self, who: str, out, shape, dtype):
+    """`out` of a draw of views: a new tensor, or the caller's once it has the shape, dtype and device."""
+    t = self._torch
+    if out is None:
+      return t.empty(shape, dtype=dtype, device=self.device)
+    if (not isinstance(out, t.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or
+        not out.is_contiguous() or out.device != self.device):
+      raise ValueError(f"{who}: out must be a contiguous {str(dtype).split('.')[-1]} tensor of shape {shape} on "
+                       f"{self.device}")
+    return out
+
+  @staticmethod
+  def _view_ring(out, ring: bool, block: int):
+    """The destination fields of a registration: `out` holds one block of `block` bytes, or with
+    `ring` T slots of one along its first axis."""
+    T = int(out.shape[0]) if ring else 0
+    stride = (out.stride(0) * out.element_size() if T > 1 else block) if ring else 0
+    return dict(dst=out.data_ptr(), dst_bytes=(T - 1) * stride + block if ring else block, slot_stride=stride,
+                slots=T)
+
   @property
   def ego_layer_shape(self):
     """The shape of the EGO_LAYER leaf, [N, P, VH, VW, L] (OBS_LAYER's; int32)."""
@@ -2672,35 +2685,12 @@ class Engine:
     engine's is written and no device memory of the engine's is allocated.  A row or player index
     out of range leaves its element as it was; the next synchronising call raises ValueError.
     `fingerprint`: the rows' (default: this engine's).  Enqueued on the current stream."""
-    t = self._torch
-    S = int(self.info.world_state_bytes)
-    if bank is not None:
-      if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
-          bank.shape[1] != S or not bank.is_contiguous()):
-        raise ValueError(f"observe_ego_layer: bank must be a contiguous uint8 tensor [M, {S}]")
-      if bank.shape[0] < 1:
-        raise ValueError("observe_ego_layer: the bank has no rows")
-    there = self.N if bank is None else int(bank.shape[0])
-    p = None if players is None else self._device_ints(players, "players")
-    r = None if rows is None else self._device_ints(rows, "rows")
-    count = int(p.numel()) if p is not None else int(r.numel()) if r is not None else there
-    if count < 1:
-      raise ValueError("observe_ego_layer: no views to draw")
-    if r is not None and int(r.numel()) != count:
-      raise ValueError(f"observe_ego_layer: rows has {int(r.numel())} entries, players {count}")
+    count, r, p, src = self._view_source("observe_ego_layer", "draw", bank, rows, players, fingerprint)
     shape = self.ego_layer_shape
     shape = (count,) + (shape[1:] if p is None else shape[2:])
-    if out is None:
-      out = t.empty(shape, dtype=t.int32, device=self.device)
-    elif (not isinstance(out, t.Tensor) or out.dtype != t.int32 or tuple(out.shape) != shape or
-          not out.is_contiguous() or out.device != self.device):
-      raise ValueError(f"observe_ego_layer: out must be a contiguous int32 tensor of shape {shape} on {self.device}")
-    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    out = self._view_out("observe_ego_layer", out, shape, self._torch.int32)
     self.use_current_stream()
-    ego_layer_request(self._L, self._h, MP_EGO_DRAW, fingerprint=fp,
-                      bank=None if bank is None else bank.data_ptr(), bank_rows=0 if bank is None else there,
-                      rows=None if r is None else r.data_ptr(), players=None if p is None else p.data_ptr(),
-                      count=count, dst=out.data_ptr(), dst_bytes=out.numel() * out.element_size())
+    ego_layer_request(self._L, self._h, MP_EGO_DRAW, dst=out.data_ptr(), dst_bytes=out.numel() * 4, **src)
     self._state_args = (bank, r, p, out)   # (kept until the next call: the launch may not have run yet)
     return out
 
@@ -2718,8 +2708,7 @@ class Engine:
     if (not isinstance(out, t.Tensor) or out.dtype != t.int32 or tuple(out.shape) != shape or
         not out.is_contiguous() or out.device != self.device):
       raise ValueError(f"bind_ego_layer: out must be a contiguous int32 tensor of shape {shape} on {self.device}")
-    ego_layer_request(self._L, self._h, MP_EGO_REGISTER, dst=out.data_ptr(),
-                      dst_bytes=out.numel() * out.element_size())
+    ego_layer_request(self._L, self._h, MP_EGO_REGISTER, **self._view_ring(out, False, out.numel() * 4))
     self._ego_layer = out
     return out
 
@@ -2740,11 +2729,7 @@ class Engine:
       raise ValueError(f"{tensor.shape[0]} slots in the tensor, {slots} asked for")
     if not tensor[0].is_contiguous() or tensor.device != self.device:
       raise ValueError("the slots of a ring must be contiguous and on the engine's device")
-    block = int(np.prod(shape)) * 4
-    stride = tensor.stride(0) * 4 if tensor.shape[0] > 1 else block
-    T = int(tensor.shape[0])
-    ego_layer_request(self._L, self._h, MP_EGO_REGISTER, dst=tensor.data_ptr(),
-                      dst_bytes=(T - 1) * stride + block, slot_stride=stride, slots=T)
+    ego_layer_request(self._L, self._h, MP_EGO_REGISTER, **self._view_ring(tensor, True, int(np.prod(shape)) * 4))
     self._ego_layer = tensor
     return tensor
 
@@ -2785,38 +2770,15 @@ class Engine:
     engine's is allocated.  A row or player index out of range leaves its element as it was; the
     next synchronising call raises ValueError.  Hashes compare only within one fingerprint and
     one choice of layers and classes.  Enqueued on the current stream."""
-    t = self._torch
-    S = int(self.info.world_state_bytes)
-    if bank is not None:
-      if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
-          bank.shape[1] != S or not bank.is_contiguous()):
-        raise ValueError(f"hash_views: bank must be a contiguous uint8 tensor [M, {S}]")
-      if bank.shape[0] < 1:
-        raise ValueError("hash_views: the bank has no rows")
-    there = self.N if bank is None else int(bank.shape[0])
-    p = None if players is None else self._device_ints(players, "players")
-    r = None if rows is None else self._device_ints(rows, "rows")
-    count = int(p.numel()) if p is not None else int(r.numel()) if r is not None else there
-    if count < 1:
-      raise ValueError("hash_views: no views to hash")
-    if r is not None and int(r.numel()) != count:
-      raise ValueError(f"hash_views: rows has {int(r.numel())} entries, players {count}")
+    count, r, p, src = self._view_source("hash_views", "hash", bank, rows, players, fingerprint)
     mask = view_layer_mask(layers, int(self.info.num_layers))
     cls = self._view_classes(classes)
-    shape = (count, self.P) if p is None else (count,)
-    if out is None:
-      out = t.empty(shape, dtype=t.int64, device=self.device)
-    elif (not isinstance(out, t.Tensor) or out.dtype != t.int64 or tuple(out.shape) != shape or
-          not out.is_contiguous() or out.device != self.device):
-      raise ValueError(f"hash_views: out must be a contiguous int64 tensor of shape {shape} on {self.device}")
-    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    out = self._view_out("hash_views", out, (count, self.P) if p is None else (count,), self._torch.int64)
     self.use_current_stream()
-    view_hash_request(self._L, self._h, MP_VIEWHASH_DRAW, fingerprint=fp,
-                      bank=None if bank is None else bank.data_ptr(), bank_rows=0 if bank is None else there,
-                      rows=None if r is None else r.data_ptr(), players=None if p is None else p.data_ptr(),
-                      count=count, layer_mask=mask, classes=None if cls is None else cls.data_ptr(),
+    view_hash_request(self._L, self._h, MP_VIEWHASH_DRAW, layer_mask=mask,
+                      classes=None if cls is None else cls.data_ptr(),
                       classes_len=0 if cls is None else int(cls.numel()), dst=out.data_ptr(),
-                      dst_bytes=out.numel() * 8)
+                      dst_bytes=out.numel() * 8, **src)
     self._view_hash_args = (bank, r, p, cls, out)   # (kept until the next call: the launch may not have run yet)
     return out
 
@@ -2840,13 +2802,10 @@ class Engine:
                        f"with contiguous slots on {self.device}")
     mask = view_layer_mask(layers, int(self.info.num_layers))
     cls = self._view_classes(classes)
-    block = self.N * self.P * 8
-    T = int(out.shape[0]) if ring else 0
-    stride = (out.stride(0) * 8 if T > 1 else block) if ring else 0
-    view_hash_request(self._L, self._h, MP_VIEWHASH_REGISTER, dst=out.data_ptr(),
-                      dst_bytes=(T - 1) * stride + block if ring else block, slot_stride=stride, slots=T,
-                      layer_mask=mask, classes=None if cls is None else cls.data_ptr(),
-                      classes_len=0 if cls is None else int(cls.numel()))
+    view_hash_request(self._L, self._h, MP_VIEWHASH_REGISTER, layer_mask=mask,
+                      classes=None if cls is None else cls.data_ptr(),
+                      classes_len=0 if cls is None else int(cls.numel()),
+                      **self._view_ring(out, ring, self.N * self.P * 8))
     self._view_hash = (out, cls)
     return out
 
@@ -2901,38 +2860,16 @@ class Engine:
     it outside [-1, C) counts as -1 and the next synchronising call raises ValueError.  A row or
     player index out of range leaves its element as it was and is reported the same way.  Nothing
     of the engine's is written.  Enqueued on the current stream."""
-    t = self._torch
-    S = int(self.info.world_state_bytes)
-    if bank is not None:
-      if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
-          bank.shape[1] != S or not bank.is_contiguous()):
-        raise ValueError(f"observe_ego_planes: bank must be a contiguous uint8 tensor [M, {S}]")
-      if bank.shape[0] < 1:
-        raise ValueError("observe_ego_planes: the bank has no rows")
-    there = self.N if bank is None else int(bank.shape[0])
-    p = None if players is None else self._device_ints(players, "players")
-    r = None if rows is None else self._device_ints(rows, "rows")
-    count = int(p.numel()) if p is not None else int(r.numel()) if r is not None else there
-    if count < 1:
-      raise ValueError("observe_ego_planes: no views to draw")
-    if r is not None and int(r.numel()) != count:
-      raise ValueError(f"observe_ego_planes: rows has {int(r.numel())} entries, players {count}")
+    count, r, p, src = self._view_source("observe_ego_planes", "draw", bank, rows, players, fingerprint)
     mask = view_layer_mask(layers, int(self.info.num_layers))
     cls, C = self._plane_classes(classes, num_classes)
     shape = self.ego_planes_shape(C, facing)
     shape = (count,) + (shape[1:] if p is None else shape[2:])
-    if out is None:
-      out = t.empty(shape, dtype=t.uint8, device=self.device)
-    elif (not isinstance(out, t.Tensor) or out.dtype != t.uint8 or tuple(out.shape) != shape or
-          not out.is_contiguous() or out.device != self.device):
-      raise ValueError(f"observe_ego_planes: out must be a contiguous uint8 tensor of shape {shape} on {self.device}")
-    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    out = self._view_out("observe_ego_planes", out, shape, self._torch.uint8)
     self.use_current_stream()
-    ego_planes_request(self._L, self._h, MP_EGOPLANES_DRAW, fingerprint=fp,
-                       bank=None if bank is None else bank.data_ptr(), bank_rows=0 if bank is None else there,
-                       rows=None if r is None else r.data_ptr(), players=None if p is None else p.data_ptr(),
-                       count=count, layer_mask=mask, classes=cls.data_ptr(), classes_len=int(cls.numel()),
-                       num_classes=C, facing=int(bool(facing)), dst=out.data_ptr(), dst_bytes=out.numel())
+    ego_planes_request(self._L, self._h, MP_EGOPLANES_DRAW, layer_mask=mask, classes=cls.data_ptr(),
+                       classes_len=int(cls.numel()), num_classes=C, facing=int(bool(facing)), dst=out.data_ptr(),
+                       dst_bytes=out.numel(), **src)
     self._ego_planes_args = (bank, r, p, cls, out)   # (kept until the next call: the launch may not have run yet)
     return out
 
@@ -2959,13 +2896,9 @@ class Engine:
         out.device != self.device):
       raise ValueError(f"bind_ego_planes: out must be a uint8 tensor of shape {shape} or [T, {', '.join(map(str, shape))}] "
                        f"with contiguous slots on {self.device}")
-    block = int(np.prod(shape))
-    T = int(out.shape[0]) if ring else 0
-    stride = (out.stride(0) if T > 1 else block) if ring else 0
-    ego_planes_request(self._L, self._h, MP_EGOPLANES_REGISTER, dst=out.data_ptr(),
-                       dst_bytes=(T - 1) * stride + block if ring else block, slot_stride=stride, slots=T,
-                       layer_mask=mask, classes=cls.data_ptr(), classes_len=int(cls.numel()), num_classes=C,
-                       facing=int(bool(facing)))
+    ego_planes_request(self._L, self._h, MP_EGOPLANES_REGISTER, layer_mask=mask, classes=cls.data_ptr(),
+                       classes_len=int(cls.numel()), num_classes=C, facing=int(bool(facing)),
+                       **self._view_ring(out, ring, int(np.prod(shape))))
     self._ego_planes = (out, cls)
     return out
 
