@@ -662,6 +662,64 @@ int check_bank(MpEngine* e, const void* ptr, uint64_t bytes, const char* who) {
   return MP_OK;
 }
 
+// The front of the requests that read rows of saved world states (MpStatesObserve, MpStatesView,
+// MpStatesCheck, MpStatesHash, MpEpisodeStarts, MP_STATES_SAVE / MP_STATES_LOAD and the three view
+// requests): each rule and its message once; a request calls them in its own order.
+// `bounded`: the rows come from a bank (or from the engine's worlds in its place), which has a row.
+int check_counts(const char* who, int32_t count, int32_t src_rows, bool bounded = true) {
+  if (count < 1 || (bounded && src_rows < 1))
+    return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", who, count, src_rows);
+  return MP_OK;
+}
+
+// Without a row list a request reads rows 0 .. count - 1.  `verb`: what it does to them; `bank`:
+// "the bank has" so many, else "there are"; `needs_list` and `tail`: MP_CHECK_FILTER's own.
+int check_row_list(const char* who, const int32_t* rows, int32_t count, int32_t src_rows, const char* verb,
+                   bool bank = true, bool needs_list = false, const char* tail = "") {
+  if (rows || (!needs_list && count <= src_rows)) return MP_OK;
+  return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are %s (count %d, %s %d rows)%s", who,
+              verb, count, bank ? "the bank has" : "there are", src_rows, tail);
+}
+
+// `whose`: "engine's" or "pack's".
+int check_fingerprint(const char* who, uint64_t rows, uint64_t own, const char* whose) {
+  if (rows == own) return MP_OK;
+  return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this %s (%016llx): they were "
+              "saved by an engine of another pack, player count or record layout", who, (unsigned long long)rows,
+              whose, (unsigned long long)own);
+}
+
+// *need: the bytes `count` elements of `each` bytes take of dst.
+int check_dst_bytes(const char* who, int32_t count, uint64_t each, uint64_t dst_bytes, uint64_t* need) {
+  *need = (uint64_t)count * each;
+  if (dst_bytes >= *need) return MP_OK;
+  return fail(MP_ERR_INVALID, "%s: %d elements of %llu bytes need %llu bytes, dst has %llu", who, count,
+              (unsigned long long)each, (unsigned long long)*need, (unsigned long long)dst_bytes);
+}
+
+int check_aligned(const char* who, const char* what, const void* at, uint64_t align) {
+  if ((uintptr_t)at % align == 0) return MP_OK;
+  return fail(MP_ERR_INVALID, "%s: %s %p is not %llu-byte aligned", who, what, at, (unsigned long long)align);
+}
+
+// A request's device memory: each extent (NULL: absent) aligned and inside one allocation of the
+// engine's device, one after the other.  check_bank's name is "who (what)", or `who` alone.
+struct Extent { const char* what; const void* at; uint64_t bytes; uint64_t align; };
+int check_extents(MpEngine* e, const char* who, const Extent* all, size_t n) {
+  HIP_TRY(hipSetDevice(e->device));
+  char name[64];
+  for (const Extent* x = all; x != all + n; ++x) {
+    if (!x->at) continue;
+    if (int rc = check_aligned(who, x->what, x->at, x->align)) return rc;
+    if (x->what) snprintf(name, sizeof name, "%s (%s)", who, x->what);
+    if (int rc = check_bank(e, x->at, x->bytes, x->what ? name : who)) return rc;
+  }
+  return MP_OK;
+}
+int check_extents(MpEngine* e, const char* who, std::initializer_list<Extent> all) {
+  return check_extents(e, who, all.begin(), all.size());
+}
+
 // One per-agent view at a time: MP_OBS_RGB or one pooled kind (the frame launch draws one of them
 // beside WORLD.RGB); a pooled view's buffer is 16-byte aligned (its span is staged by lines).
 int check_agent_view(MpEngine* e, int kind, const void* ptr, const char* who) {
@@ -2040,56 +2098,68 @@ static int grow_obs_buffer(uint8_t** buf, uint64_t* have, uint64_t need) {
   return MP_OK;
 }
 
-static int states_observe(MpEngine* e, const MpStatesObserve& r) {
-  static const char kWho[] = "MpStatesObserve";
+// What MpStatesObserve and MpStatesView check before they launch; the first is read as the second
+// without players.  `per_player`: MpStatesView's own rules (players, no MP_OBS_WORLD_RGB, and dst
+// of a pixel kind on any byte); else MpStatesObserve's (mp_observe's: a pooled span is staged by
+// 16-byte lines).  `size`: the request's own.
+struct StatesDraw {
+  bool pixel;
+  uint64_t per, need;   // bytes of an element, of dst
+};
+static int states_front(MpEngine* e, const char* kWho, const MpStatesView& r, size_t size, bool per_player,
+                        StatesDraw* d) {
   if (!e) return fail(MP_ERR_INVALID, "%s: NULL engine", kWho);
-  if (r.struct_size != sizeof(MpStatesObserve))
-    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpStatesObserve));
+  if (r.struct_size != size)
+    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, size);
+  if (r.reserved[0] || r.reserved[1]) return fail(MP_ERR_INVALID, "%s: the reserved words must be 0", kWho);
   if (!r.bank || !r.dst) return fail(MP_ERR_INVALID, "%s: NULL bank or dst", kWho);
-  if (r.count < 1 || r.bank_rows < 1)
-    return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", kWho, r.count, r.bank_rows);
-  if (!r.rows && r.count > r.bank_rows)
-    return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are drawn (count %d, the bank "
-                "has %d rows)", kWho, r.count, r.bank_rows);
-  if (r.fingerprint != e->fingerprint)
-    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this engine's (%016llx): "
-                "they were saved by an engine of another pack, player count or record layout", kWho,
-                (unsigned long long)r.fingerprint, (unsigned long long)e->fingerprint);
+  if (per_player && !r.players) return fail(MP_ERR_INVALID, "%s: NULL players", kWho);
+  if (int rc = check_counts(kWho, r.count, r.bank_rows)) return rc;
+  if (int rc = check_row_list(kWho, r.rows, r.count, r.bank_rows, "drawn")) return rc;
+  if (int rc = check_fingerprint(kWho, r.fingerprint, e->fingerprint, "engine's")) return rc;
   const int kind = r.kind;
   if (kind < 0 || kind >= MP_OBS_KINDS)
     return fail(MP_ERR_INVALID, "%s: kind %d is no observation kind", kWho, kind);
-  const bool pixel = MpEngine::is_pixel_kind(kind);
+  if (per_player && kind == MP_OBS_WORLD_RGB)
+    return fail(MP_ERR_INVALID, "%s: MP_OBS_WORLD_RGB is not a per-player kind (MpStatesObserve draws it)", kWho);
+  d->pixel = MpEngine::is_pixel_kind(kind);
   uint64_t elem = 1;   // what dst is aligned to
   switch (kind) {
     case MP_OBS_LAYER: case MP_OBS_POSITION: case MP_OBS_ORIENTATION: elem = 4; break;
     case MP_OBS_READY_TO_SHOOT: case MP_OBS_INVENTORY: elem = 8; break;
     default:
-      if (!pixel)
+      if (!d->pixel)
         return fail(MP_ERR_INVALID, "%s: kind %d is not a function of the record (a transition kind: what a "
                     "step or a reset reports, which no saved state holds)", kWho, kind);
   }
-  const bool pooled = MpEngine::pool_of(kind) > 1 || (kind == MP_OBS_WORLD_RGB && e->world_pool > 1);
-  if (pooled) elem = 16;   // (mp_observe's rule: a pooled span is staged by 16-byte lines)
-  const uint64_t per = mp_obs_bytes(e, (MpObsKind)kind) / (uint64_t)e->N;
-  if (per == 0)
+  const bool pooled =
+      !per_player && (MpEngine::pool_of(kind) > 1 || (kind == MP_OBS_WORLD_RGB && e->world_pool > 1));
+  if (pooled) elem = 16;
+  d->per = mp_obs_bytes(e, (MpObsKind)kind) / ((uint64_t)e->N * (per_player ? (uint64_t)e->t.P : 1u));
+  if (d->per == 0)
     return fail(MP_ERR_UNSUPPORTED, "%s: this substrate has no observation %d", kWho, kind);
-  const uint64_t count = (uint64_t)r.count, need = count * per;
-  if (r.dst_bytes < need)
-    return fail(MP_ERR_INVALID, "%s: %d elements of %llu bytes need %llu bytes, dst has %llu", kWho, r.count,
-                (unsigned long long)per, (unsigned long long)need, (unsigned long long)r.dst_bytes);
+  if (int rc = check_dst_bytes(kWho, r.count, d->per, r.dst_bytes, &d->need)) return rc;
   if ((uintptr_t)r.dst % elem)
     return fail(MP_ERR_INVALID, "%s: dst %p is not %llu-byte aligned%s", kWho, r.dst, (unsigned long long)elem,
                 pooled ? " (a pooled view's buffer)" : "");
-  if (r.rows && ((uintptr_t)r.rows & 3))
-    return fail(MP_ERR_INVALID, "%s: rows %p is not 4-byte aligned", kWho, (const void*)r.rows);
-  if ((uintptr_t)r.bank & 15)   // (records are read in 16-byte lines)
-    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", kWho, r.bank);
-  HIP_TRY(hipSetDevice(e->device));
-  const uint64_t S = (uint64_t)e->t.world_stride;
-  if (int rc = check_bank(e, r.bank, (uint64_t)r.bank_rows * S, "MpStatesObserve (bank)")) return rc;
-  if (r.rows)
-    if (int rc = check_bank(e, r.rows, count * 4, "MpStatesObserve (rows)")) return rc;
-  if (int rc = check_bank(e, r.dst, need, "MpStatesObserve (dst)")) return rc;
+  if (int rc = check_aligned(kWho, "rows", r.rows, 4)) return rc;
+  if (int rc = check_aligned(kWho, "players", r.players, 4)) return rc;
+  const uint64_t count = (uint64_t)r.count;   // (records are read in 16-byte lines)
+  return check_extents(e, kWho, {{"bank", r.bank, (uint64_t)r.bank_rows * (uint64_t)e->t.world_stride, 16},
+                                 {"rows", r.rows, count * 4, 1},
+                                 {"players", r.players, count * 4, 1},
+                                 {"dst", r.dst, d->need, 1}});
+}
+
+static int states_observe(MpEngine* e, const MpStatesObserve& r) {
+  static const char kWho[] = "MpStatesObserve";
+  const MpStatesView q = {r.struct_size, r.kind, r.fingerprint, r.bank, r.rows, nullptr, r.dst, r.dst_bytes,
+                          r.bank_rows, r.count, {0, 0}};
+  StatesDraw d;
+  if (int rc = states_front(e, kWho, q, sizeof r, false, &d)) return rc;
+  const int kind = r.kind;
+  const bool pixel = d.pixel;
+  const uint64_t per = d.per, count = (uint64_t)r.count, S = (uint64_t)e->t.world_stride;
   const uint8_t* bank = (const uint8_t*)r.bank;
   if (!pixel && kind != MP_OBS_LAYER) {
     launch_state_obs(e->t, e->sub, kind, bank, r.bank_rows, r.rows, r.count, r.dst, e->stream);
@@ -2145,60 +2215,12 @@ static int states_observe(MpEngine* e, const MpStatesObserve& r) {
 // of the engine's is written and no device memory is allocated or freed.
 static int states_view(MpEngine* e, const MpStatesView& r) {
   static const char kWho[] = "MpStatesView";
-  if (!e) return fail(MP_ERR_INVALID, "%s: NULL engine", kWho);
-  if (r.struct_size != sizeof(MpStatesView))
-    return fail(MP_ERR_INVALID, "%s: struct_size %u, expected %zu", kWho, r.struct_size, sizeof(MpStatesView));
-  if (r.reserved[0] || r.reserved[1]) return fail(MP_ERR_INVALID, "%s: the reserved words must be 0", kWho);
-  if (!r.bank || !r.dst) return fail(MP_ERR_INVALID, "%s: NULL bank or dst", kWho);
-  if (!r.players) return fail(MP_ERR_INVALID, "%s: NULL players", kWho);
-  if (r.count < 1 || r.bank_rows < 1)
-    return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", kWho, r.count, r.bank_rows);
-  if (!r.rows && r.count > r.bank_rows)
-    return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are drawn (count %d, the bank "
-                "has %d rows)", kWho, r.count, r.bank_rows);
-  if (r.fingerprint != e->fingerprint)
-    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this engine's (%016llx): "
-                "they were saved by an engine of another pack, player count or record layout", kWho,
-                (unsigned long long)r.fingerprint, (unsigned long long)e->fingerprint);
+  StatesDraw d;
+  if (int rc = states_front(e, kWho, r, sizeof r, true, &d)) return rc;
   const int kind = r.kind;
-  if (kind < 0 || kind >= MP_OBS_KINDS)
-    return fail(MP_ERR_INVALID, "%s: kind %d is no observation kind", kWho, kind);
-  if (kind == MP_OBS_WORLD_RGB)
-    return fail(MP_ERR_INVALID, "%s: MP_OBS_WORLD_RGB is not a per-player kind (MpStatesObserve draws it)", kWho);
-  const bool pixel = MpEngine::is_pixel_kind(kind);
-  uint64_t elem = 1;   // what dst is aligned to (a pixel kind, pooled or not: any byte)
-  switch (kind) {
-    case MP_OBS_LAYER: case MP_OBS_POSITION: case MP_OBS_ORIENTATION: elem = 4; break;
-    case MP_OBS_READY_TO_SHOOT: case MP_OBS_INVENTORY: elem = 8; break;
-    default:
-      if (!pixel)
-        return fail(MP_ERR_INVALID, "%s: kind %d is not a function of the record (a transition kind: what a "
-                    "step or a reset reports, which no saved state holds)", kWho, kind);
-  }
-  const uint64_t per = mp_obs_bytes(e, (MpObsKind)kind) / ((uint64_t)e->N * (uint64_t)e->t.P);
-  if (per == 0)
-    return fail(MP_ERR_UNSUPPORTED, "%s: this substrate has no observation %d", kWho, kind);
-  const uint64_t count = (uint64_t)r.count, need = count * per;
-  if (r.dst_bytes < need)
-    return fail(MP_ERR_INVALID, "%s: %d elements of %llu bytes need %llu bytes, dst has %llu", kWho, r.count,
-                (unsigned long long)per, (unsigned long long)need, (unsigned long long)r.dst_bytes);
-  if ((uintptr_t)r.dst % elem)
-    return fail(MP_ERR_INVALID, "%s: dst %p is not %llu-byte aligned", kWho, r.dst, (unsigned long long)elem);
-  if (r.rows && ((uintptr_t)r.rows & 3))
-    return fail(MP_ERR_INVALID, "%s: rows %p is not 4-byte aligned", kWho, (const void*)r.rows);
-  if ((uintptr_t)r.players & 3)
-    return fail(MP_ERR_INVALID, "%s: players %p is not 4-byte aligned", kWho, (const void*)r.players);
-  if ((uintptr_t)r.bank & 15)   // (records are read in 16-byte lines)
-    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", kWho, r.bank);
-  HIP_TRY(hipSetDevice(e->device));
-  const uint64_t S = (uint64_t)e->t.world_stride;
-  if (int rc = check_bank(e, r.bank, (uint64_t)r.bank_rows * S, "MpStatesView (bank)")) return rc;
-  if (r.rows)
-    if (int rc = check_bank(e, r.rows, count * 4, "MpStatesView (rows)")) return rc;
-  if (int rc = check_bank(e, r.players, count * 4, "MpStatesView (players)")) return rc;
-  if (int rc = check_bank(e, r.dst, need, "MpStatesView (dst)")) return rc;
+  const uint64_t per = d.per;
   const uint8_t* bank = (const uint8_t*)r.bank;
-  if (!pixel && kind != MP_OBS_LAYER) {
+  if (!d.pixel && kind != MP_OBS_LAYER) {
     launch_state_view_scalar(e->t, e->sub, kind, bank, r.bank_rows, r.rows, r.players, r.count, r.dst, e->stream);
     HIP_TRY(hipGetLastError());
     return MP_OK;
@@ -2273,11 +2295,10 @@ static int states_check(MpEngine* e, const MpStatesCheck& r) {
   if ((r.op == MP_CHECK_HOST) != (e == nullptr))
     return fail(MP_ERR_INVALID, "%s: MP_CHECK_HOST goes without an engine, the other forms with one", kWho);
   if (!r.bank || !r.out) return fail(MP_ERR_INVALID, "%s: NULL bank or out", kWho);
-  if (r.count < 1 || r.bank_rows < 1)
-    return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", kWho, r.count, r.bank_rows);
-  if (!r.rows && (r.op == MP_CHECK_FILTER || r.count > r.bank_rows))
-    return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are judged (count %d, the bank has "
-                "%d rows); a filter needs its src", kWho, r.count, r.bank_rows);
+  if (int rc = check_counts(kWho, r.count, r.bank_rows)) return rc;
+  if (int rc = check_row_list(kWho, r.rows, r.count, r.bank_rows, "judged", true, r.op == MP_CHECK_FILTER,
+                              "; a filter needs its src"))
+    return rc;
   const uint64_t count = (uint64_t)r.count, need = count * (r.op == MP_CHECK_FILTER ? 4u : 8u);
   if (r.out_bytes < need)
     return fail(MP_ERR_INVALID, "%s: %d verdicts need %llu bytes, out has %llu", kWho, r.count,
@@ -2296,21 +2317,15 @@ static int states_check(MpEngine* e, const MpStatesCheck& r) {
     check_rows_host(ck, (const uint8_t*)r.bank, r.bank_rows, r.rows, r.count, (int32_t*)r.out);
     return MP_OK;
   }
-  if (r.fingerprint != e->fingerprint)
-    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this engine's (%016llx): "
-                "they were saved by an engine of another pack, player count or record layout", kWho,
-                (unsigned long long)r.fingerprint, (unsigned long long)e->fingerprint);
+  if (int rc = check_fingerprint(kWho, r.fingerprint, e->fingerprint, "engine's")) return rc;
   if (r.op == MP_CHECK_FILTER && r.count != e->N)
     return fail(MP_ERR_INVALID, "%s: a filter takes the src of a load, one entry per world (count %d, the "
                 "engine has %d worlds)", kWho, r.count, e->N);
-  if ((uintptr_t)r.bank & 15)   // (records are read in 16-byte lines)
-    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", kWho, r.bank);
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = check_bank(e, r.bank, (uint64_t)r.bank_rows * (uint64_t)e->t.world_stride, "MpStatesCheck (bank)"))
+  // (records are read in 16-byte lines)
+  if (int rc = check_extents(e, kWho, {{"bank", r.bank, (uint64_t)r.bank_rows * (uint64_t)e->t.world_stride, 16},
+                                       {"rows", r.rows, count * 4, 1},
+                                       {"out", r.out, need, 1}}))
     return rc;
-  if (r.rows)
-    if (int rc = check_bank(e, r.rows, count * 4, "MpStatesCheck (rows)")) return rc;
-  if (int rc = check_bank(e, r.out, need, "MpStatesCheck (out)")) return rc;
   if (r.op == MP_CHECK_FILTER)
     launch_filter_states(e->d_check, (const uint8_t*)r.bank, r.bank_rows, r.rows, r.count, (int32_t*)r.out,
                          e->t.fault, e->stream);
@@ -2342,11 +2357,9 @@ static int states_hash(MpEngine* e, const MpStatesHash& r) {
   const bool rows_op = r.op == MP_HASH_ROWS || r.op == MP_HASH_HOST;
   if (rows_op && !r.bank) return fail(MP_ERR_INVALID, "%s: NULL bank", kWho);
   if (r.op != MP_HASH_MASK) {
-    if (r.count < 1 || (rows_op && r.bank_rows < 1))
-      return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", kWho, r.count, r.bank_rows);
-    if (rows_op && !r.rows && r.count > r.bank_rows)
-      return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are hashed (count %d, the bank has "
-                  "%d rows)", kWho, r.count, r.bank_rows);
+    if (int rc = check_counts(kWho, r.count, r.bank_rows, rows_op)) return rc;
+    if (rows_op)
+      if (int rc = check_row_list(kWho, r.rows, r.count, r.bank_rows, "hashed")) return rc;
     if (r.op == MP_HASH_WORLDS && !r.rows && r.count != e->N)
       return fail(MP_ERR_INVALID, "%s: without a world list every world is hashed (count %d, the engine has %d)",
                   kWho, r.count, e->N);
@@ -2380,10 +2393,8 @@ static int states_hash(MpEngine* e, const MpStatesHash& r) {
     state_hash::build_byte_mask(lay, spec, (uint8_t*)r.out);
     return MP_OK;
   }
-  if (rows_op && r.fingerprint != fingerprint)
-    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this %s (%016llx): they were "
-                "saved by an engine of another pack, player count or record layout", kWho,
-                (unsigned long long)r.fingerprint, e ? "engine's" : "pack's", (unsigned long long)fingerprint);
+  if (rows_op)
+    if (int rc = check_fingerprint(kWho, r.fingerprint, fingerprint, e ? "engine's" : "pack's")) return rc;
   if (r.op == MP_HASH_HOST) {
     std::vector<uint32_t> words((size_t)S / 4);
     state_hash::build_byte_mask(lay, spec, reinterpret_cast<uint8_t*>(words.data()));
@@ -2396,15 +2407,11 @@ static int states_hash(MpEngine* e, const MpStatesHash& r) {
   }
   if (r.op == MP_HASH_WORLDS && !e->has_state)
     return fail(MP_ERR_INVALID, "%s: the engine has never been reset; there is no state to hash", kWho);
-  if (rows_op && ((uintptr_t)r.bank & 15))   // (records are read in 16-byte lines)
-    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", kWho, r.bank);
-  HIP_TRY(hipSetDevice(e->device));
-  const uint64_t count = (uint64_t)r.count;
-  if (rows_op)
-    if (int rc = check_bank(e, r.bank, (uint64_t)r.bank_rows * S, "MpStatesHash (bank)")) return rc;
-  if (r.rows)
-    if (int rc = check_bank(e, r.rows, count * 4, "MpStatesHash (rows)")) return rc;
-  if (int rc = check_bank(e, r.out, count * 8, "MpStatesHash (out)")) return rc;
+  const uint64_t count = (uint64_t)r.count;   // (records are read in 16-byte lines)
+  if (int rc = check_extents(e, kWho, {{"bank", rows_op ? r.bank : nullptr, (uint64_t)r.bank_rows * S, 16},
+                                       {"rows", r.rows, count * 4, 1},
+                                       {"out", r.out, count * 8, 1}}))
+    return rc;
   const uint32_t* mask = e->d_hash_mask;
   if (spec.custom) {
     if (!state_hash::same_spec(spec, e->hash_custom)) {
@@ -2452,21 +2459,15 @@ static int episode_starts(MpEngine* e, const MpEpisodeStarts& r) {
   if (!r.rows) return fail(MP_ERR_INVALID, "%s: NULL rows", kWho);
   if (r.fresh != 0 && r.fresh != 1)
     return fail(MP_ERR_INVALID, "%s: fresh %d is neither 0 nor 1", kWho, r.fresh);
-  if (r.fingerprint != e->fingerprint)
-    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this engine's (%016llx): "
-                "they were saved by an engine of another pack, player count or record layout", kWho,
-                (unsigned long long)r.fingerprint, (unsigned long long)e->fingerprint);
-  if ((uintptr_t)r.bank & 15)   // (records are read in 16-byte lines)
-    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", kWho, r.bank);
+  if (int rc = check_fingerprint(kWho, r.fingerprint, e->fingerprint, "engine's")) return rc;
+  if (int rc = check_aligned(kWho, "bank", r.bank, 16)) return rc;   // (records are read in 16-byte lines)
   if (((uintptr_t)r.rows & 3) || ((uintptr_t)r.verdicts & 3))
     return fail(MP_ERR_INVALID, "%s: rows %p and verdicts %p must be 4-byte aligned", kWho, (const void*)r.rows,
                 (const void*)r.verdicts);
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = check_bank(e, r.bank, (uint64_t)r.bank_rows * (uint64_t)e->t.world_stride, "MpEpisodeStarts (bank)"))
+  if (int rc = check_extents(e, kWho, {{"bank", r.bank, (uint64_t)r.bank_rows * (uint64_t)e->t.world_stride, 1},
+                                       {"rows", r.rows, (uint64_t)e->N * 4, 1},
+                                       {"verdicts", r.verdicts, (uint64_t)r.bank_rows * 8, 1}}))
     return rc;
-  if (int rc = check_bank(e, r.rows, (uint64_t)e->N * 4, "MpEpisodeStarts (rows)")) return rc;
-  if (r.verdicts)
-    if (int rc = check_bank(e, r.verdicts, (uint64_t)r.bank_rows * 8, "MpEpisodeStarts (verdicts)")) return rc;
   e->starts.bank = (const uint8_t*)r.bank;
   e->starts.rows = r.rows;
   e->starts.verdicts = r.verdicts;
@@ -2549,10 +2550,8 @@ static int episode_stats_request(MpEngine* e, const MpEpisodeStats& r) {
     episode_stats_host(cols, b, rows);
     return MP_OK;
   }
-  HIP_TRY(hipSetDevice(e->device));
   // every tensor: device memory of the engine's device, aligned, its whole extent in one allocation
-  struct Tensor { const char* what; const void* at; uint64_t bytes; uint64_t align; };
-  std::vector<Tensor> all;
+  std::vector<Extent> all;
   if (r.op == MP_STATS_TALLY) {
     const uint64_t K = (uint64_t)r.steps, M = (uint64_t)r.count;
     all.push_back({"events", r.events, K * M * MP_EVENT_ROWS * 16u, 16});
@@ -2577,13 +2576,7 @@ static int episode_stats_request(MpEngine* e, const MpEpisodeStats& r) {
       if (PP) all.push_back({names[k][3], banks[k]->pairs, N * PP * elem, elem});
     }
   }
-  char name[64];
-  for (const Tensor& t : all) {
-    if ((uintptr_t)t.at % t.align)
-      return fail(MP_ERR_INVALID, "%s: %s %p is not %llu-byte aligned", kWho, t.what, t.at, (unsigned long long)t.align);
-    snprintf(name, sizeof name, "%s (%s)", kWho, t.what);
-    if (int rc = check_bank(e, t.at, t.bytes, name)) return rc;
-  }
+  if (int rc = check_extents(e, kWho, all.data(), all.size())) return rc;
   if (r.op == MP_STATS_TALLY) {
     episode_stats::Rows rows = {};
     rows.columns = r.count; rows.K = r.steps; rows.P = (int)P;
@@ -2760,20 +2753,10 @@ static int view_source(const MpEngine* e, const ViewRequest& q, const ViewWords&
   s->live = q.op == VIEW_DRAW && !q.bank;
   if (q.op == VIEW_HOST && !q.bank) return fail(MP_ERR_INVALID, "%s: NULL bank", w.who);
   s->src_rows = s->live ? e->N : q.bank_rows;
-  if (q.count < 1 || s->src_rows < 1)
-    return fail(MP_ERR_INVALID, "%s: count %d, bank_rows %d: both must be at least 1", w.who, q.count, s->src_rows);
-  if (!q.rows && q.count > s->src_rows)
-    return fail(MP_ERR_INVALID, "%s: without a row list rows 0 .. count - 1 are %s (count %d, there are %d "
-                "rows)", w.who, w.drawn, q.count, s->src_rows);
-  if (q.fingerprint != v.fingerprint)
-    return fail(MP_ERR_INVALID, "%s: the rows' state fingerprint %016llx is not this %s (%016llx): they were "
-                "saved by an engine of another pack, player count or record layout", w.who,
-                (unsigned long long)q.fingerprint, e ? "engine's" : "pack's", (unsigned long long)v.fingerprint);
-  const uint64_t each = q.players ? view : world;
-  s->need = (uint64_t)q.count * each;
-  if (q.dst_bytes < s->need)
-    return fail(MP_ERR_INVALID, "%s: %d elements of %llu bytes need %llu bytes, dst has %llu", w.who, q.count,
-                (unsigned long long)each, (unsigned long long)s->need, (unsigned long long)q.dst_bytes);
+  if (int rc = check_counts(w.who, q.count, s->src_rows)) return rc;
+  if (int rc = check_row_list(w.who, q.rows, q.count, s->src_rows, w.drawn, false)) return rc;
+  if (int rc = check_fingerprint(w.who, q.fingerprint, v.fingerprint, e ? "engine's" : "pack's")) return rc;
+  if (int rc = check_dst_bytes(w.who, q.count, q.players ? view : world, q.dst_bytes, &s->need)) return rc;
   if (((uintptr_t)q.rows & 3) || ((uintptr_t)q.players & 3))
     return fail(MP_ERR_INVALID, "%s: rows %p and players %p must be 4-byte aligned", w.who, (const void*)q.rows,
                 (const void*)q.players);
@@ -2804,23 +2787,12 @@ static int view_device_source(MpEngine* e, const ViewRequest& q, const ViewWords
                               const void* classes, uint64_t classes_bytes) {
   if (s.live && !e->has_state)
     return fail(MP_ERR_INVALID, "%s: the engine has never been reset; there is no state to %s", w.who, w.draw);
-  if (!s.live && ((uintptr_t)q.bank & 15))   // (records are read in 16-byte lines)
-    return fail(MP_ERR_INVALID, "%s: bank %p is not 16-byte aligned", w.who, q.bank);
-  HIP_TRY(hipSetDevice(e->device));
-  const uint64_t count = (uint64_t)q.count;
-  const struct { const char* what; const void* at; uint64_t bytes; } all[5] = {
-      {"bank", s.live ? nullptr : q.bank, (uint64_t)q.bank_rows * (uint64_t)e->t.world_stride},
-      {"rows", q.rows, count * 4},
-      {"players", q.players, count * 4},
-      {"classes", classes, classes_bytes},
-      {"dst", q.dst, s.need}};
-  char name[48];
-  for (const auto& k : all) {
-    if (!k.at) continue;
-    snprintf(name, sizeof name, "%s (%s)", w.who, k.what);
-    if (int rc = check_bank(e, k.at, k.bytes, name)) return rc;
-  }
-  return MP_OK;
+  const uint64_t count = (uint64_t)q.count, bank = (uint64_t)q.bank_rows * (uint64_t)e->t.world_stride;
+  return check_extents(e, w.who, {{"bank", s.live ? nullptr : q.bank, bank, 16},   // (records are read in 16-byte lines)
+                                  {"rows", q.rows, count * 4, 1},
+                                  {"players", q.players, count * 4, 1},
+                                  {"classes", classes, classes_bytes, 1},
+                                  {"dst", q.dst, s.need, 1}});
 }
 
 static int ego_layer_request(MpEngine* e, const MpEgoLayer& r) {
@@ -3193,10 +3165,9 @@ static int save_worlds(MpEngine* e, const int32_t* worlds, int32_t count, void* 
                 count, (unsigned long long)stride, (unsigned long long)bytes, (unsigned long long)dst_bytes);
   if (!e->has_state)
     return fail(MP_ERR_INVALID, "MP_STATES_SAVE: the engine has never been reset; there is no state to save");
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = check_bank(e, dst, bytes, "MP_STATES_SAVE")) return rc;
-  if (worlds)
-    if (int rc = check_bank(e, worlds, (uint64_t)count * 4, "MP_STATES_SAVE (world list)")) return rc;
+  if (int rc = check_extents(e, "MP_STATES_SAVE", {{nullptr, dst, bytes, 1},
+                                                   {"world list", worlds, (uint64_t)count * 4, 1}}))
+    return rc;
   hipLaunchKernelGGL(k_save_worlds, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, e->stream, e->t,
                      (const uint8_t*)e->d_state, e->N, worlds, (int)count, (uint8_t*)dst);
   HIP_TRY(hipGetLastError());
@@ -3207,14 +3178,10 @@ static int load_worlds(MpEngine* e, const void* bank, int32_t bank_rows, const i
                        uint64_t fingerprint) {
   if (!e || !bank || !src || bank_rows <= 0)
     return fail(MP_ERR_INVALID, "MP_STATES_LOAD: NULL engine, bank or src, or an empty bank");
-  if (fingerprint != e->fingerprint)
-    return fail(MP_ERR_INVALID, "MP_STATES_LOAD: the rows' state fingerprint %016llx is not this engine's "
-                "(%016llx): they were saved by an engine of another pack, player count or record layout",
-                (unsigned long long)fingerprint, (unsigned long long)e->fingerprint);
-  HIP_TRY(hipSetDevice(e->device));
-  if (int rc = check_bank(e, bank, (uint64_t)bank_rows * (uint64_t)e->t.world_stride, "MP_STATES_LOAD"))
+  if (int rc = check_fingerprint("MP_STATES_LOAD", fingerprint, e->fingerprint, "engine's")) return rc;
+  const uint64_t bytes = (uint64_t)bank_rows * (uint64_t)e->t.world_stride;
+  if (int rc = check_extents(e, "MP_STATES_LOAD", {{nullptr, bank, bytes, 1}, {"src", src, (uint64_t)e->N * 4, 1}}))
     return rc;
-  if (int rc = check_bank(e, src, (uint64_t)e->N * 4, "MP_STATES_LOAD (src)")) return rc;
   e->touched = true;
   e->has_state = true;
   return submit(e, STEP_MODE_LOAD, nullptr, nullptr, (const uint8_t*)bank, src, bank_rows);

@@ -221,16 +221,28 @@ class MpWorldStates(ctypes.Structure):
               ("count", ctypes.c_int32), ("bank_rows", ctypes.c_int32)]
 
 
+def _send(L, handle, req, carrier: str = "mp_snapshot", label: Optional[str] = None):
+  """Sends the request struct `req` to engine `handle` (None: a host form) through `carrier`,
+  "mp_snapshot" or "mp_restore", and returns it (with its outputs); raises like every call."""
+  _check(L, getattr(L, carrier)(handle, ctypes.addressof(req), ctypes.sizeof(req)),
+         f"{carrier} ({label or type(req).__name__})")
+  return req
+
+
+def _request(L, handle, struct, head, fields, carrier: str = "mp_snapshot", label: Optional[str] = None):
+  """One request of type `struct`: struct_size, then `head` in the order of its fields, then `fields`."""
+  req = struct(ctypes.sizeof(struct), *head)
+  for k, v in fields.items():
+    setattr(req, k, v)
+  return _send(L, handle, req, carrier, label)
+
+
 def world_states_request(L, handle, op: int, **fields) -> MpWorldStates:
   """Runs one MpWorldStates request on engine `handle` (MP_STATES_LOAD through mp_restore, the
   others through mp_snapshot) and returns it (with its outputs); raises like every call."""
-  req = MpWorldStates(ctypes.sizeof(MpWorldStates), op)
-  for k, v in fields.items():
-    setattr(req, k, v)
-  call = L.mp_restore if op == MP_STATES_LOAD else L.mp_snapshot
-  _check(L, call(handle, ctypes.addressof(req), ctypes.sizeof(req)),
-         "mp_restore (MP_STATES_LOAD)" if op == MP_STATES_LOAD else "mp_snapshot (MpWorldStates)")
-  return req
+  if op == MP_STATES_LOAD:
+    return _request(L, handle, MpWorldStates, (op,), fields, "mp_restore", "MP_STATES_LOAD")
+  return _request(L, handle, MpWorldStates, (op,), fields)
 
 
 # Observations of bank rows (include/mp_engine.h: MpStatesObserve), carried by mp_snapshot
@@ -248,12 +260,7 @@ STATE_OBS_KINDS = PIXEL_KINDS + (OBS_LAYER, OBS_READY_TO_SHOOT, OBS_POSITION, OB
 
 def states_observe_request(L, handle, **fields) -> MpStatesObserve:
   """Runs one MpStatesObserve request on engine `handle`; raises like every call."""
-  req = MpStatesObserve(ctypes.sizeof(MpStatesObserve))
-  for k, v in fields.items():
-    setattr(req, k, v)
-  _check(L, L.mp_snapshot(handle, ctypes.addressof(req), ctypes.sizeof(req)),
-         "mp_snapshot (MpStatesObserve)")
-  return req
+  return _request(L, handle, MpStatesObserve, (), fields)
 
 
 # Sampled (row, player) views of bank rows (include/mp_engine.h: MpStatesView), carried by mp_snapshot
@@ -266,12 +273,7 @@ class MpStatesView(ctypes.Structure):
 
 def states_view_request(L, handle, **fields) -> MpStatesView:
   """Runs one MpStatesView request on engine `handle`; raises like every call."""
-  req = MpStatesView(ctypes.sizeof(MpStatesView))
-  for k, v in fields.items():
-    setattr(req, k, v)
-  _check(L, L.mp_snapshot(handle, ctypes.addressof(req), ctypes.sizeof(req)),
-         "mp_snapshot (MpStatesView)")
-  return req
+  return _request(L, handle, MpStatesView, (), fields)
 
 
 # EGO_LAYER, the layer view in the avatar's own frame (include/mp_engine.h: MpEgoLayer), carried by
@@ -291,11 +293,7 @@ class MpEgoLayer(ctypes.Structure):
 
 def ego_layer_request(L, handle, op: int, **fields) -> MpEgoLayer:
   """Runs one MpEgoLayer request on engine `handle` (None: the host form); raises like every call."""
-  req = MpEgoLayer(ctypes.sizeof(MpEgoLayer), int(op))
-  for k, v in fields.items():
-    setattr(req, k, v)
-  _check(L, L.mp_snapshot(handle, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpEgoLayer)")
-  return req
+  return _request(L, handle, MpEgoLayer, (int(op),), fields)
 
 
 # The layout of a record and the check of edited records (include/mp_engine.h: MpStateLayout,
@@ -427,7 +425,7 @@ def _layout_request(L, handle, pack_bytes=None, num_players: int = 0, dev=None) 
   if handle is None:
     keep = _host_config(pack_bytes, num_players, dev)
     req.pack, req.pack_len, req.cfg = ctypes.addressof(keep[0]), len(pack_bytes), ctypes.pointer(keep[1])
-  _check(L, L.mp_snapshot(handle, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpStateLayout)")
+  _send(L, handle, req)
   return StateLayout(req, fields[:req.num_fields])
 
 
@@ -455,18 +453,8 @@ def check_states_host(pack_bytes: bytes, rows, *, fingerprint: Optional[int] = N
   pack, by the library's host-only check (MP_CHECK_HOST: the kernel's own rule functions compiled
   for the host; no GPU needed).  `which`: the rows to judge (default: all).  `fingerprint`: the
   rows' (default: the pack's)."""
-  L = load_library()
-  bank = np.ascontiguousarray(rows, np.uint8)
-  if bank.ndim != 2 or bank.shape[0] < 1:
-    raise ValueError("check_states_host: rows must be a uint8 array [M, S]")
-  keep = _host_config(pack_bytes, num_players, dev)
-  layout = _layout_request(L, None, pack_bytes, num_players, dev)
-  if bank.shape[1] != layout.world_stride:
-    raise ValueError(f"check_states_host: rows of {bank.shape[1]} bytes, the pack's are {layout.world_stride}")
-  idx = None if which is None else np.ascontiguousarray(np.asarray(which).reshape(-1), np.int32)
-  count = bank.shape[0] if idx is None else int(idx.size)
-  if count < 1:
-    raise ValueError("check_states_host: no rows to judge")
+  layout, keep, bank, idx, _, count = _host_source("check_states_host", "judge", pack_bytes, rows, which, None,
+                                                   num_players, dev)
   out = np.zeros((count, 2), np.int32)
   req = MpStatesCheck(ctypes.sizeof(MpStatesCheck), MP_CHECK_HOST,
                       layout.fingerprint if fingerprint is None else int(fingerprint))
@@ -474,20 +462,19 @@ def check_states_host(pack_bytes: bytes, rows, *, fingerprint: Optional[int] = N
   req.bank, req.bank_rows, req.count = bank.ctypes.data, int(bank.shape[0]), count
   req.rows = None if idx is None else idx.ctypes.data
   req.out, req.out_bytes = out.ctypes.data, out.nbytes
-  _check(L, L.mp_snapshot(None, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpStatesCheck)")
+  _send(load_library(), None, req)
   return out
 
 
-def _view_host_source(who: str, verb: str, pack_bytes: bytes, rows, players, which, fingerprint, num_players, dev):
-  """What ego_layer_host, hash_views_host and ego_planes_host marshal alike: the host bank, `which`
-  and `players` as int32 arrays, the count.  Returns (layout, the result's leading shape — (R,) or
-  (R, P) —, the request's source fields, what must stay alive over the call)."""
-  L = load_library()
+def _host_source(who: str, verb: str, pack_bytes: bytes, rows, which, players, num_players, dev):
+  """What the host forms marshal alike: the host bank, `which` and `players` as int32 arrays (or
+  None), the count.  Returns (layout, the pack and config to keep alive over the call, bank, which,
+  players, count)."""
   bank = np.ascontiguousarray(rows, np.uint8)
   if bank.ndim != 2 or bank.shape[0] < 1:
     raise ValueError(f"{who}: rows must be a uint8 array [M, S]")
   keep = _host_config(pack_bytes, num_players, dev)
-  layout = _layout_request(L, None, pack_bytes, num_players, dev)
+  layout = _layout_request(load_library(), None, pack_bytes, num_players, dev)
   if bank.shape[1] != layout.world_stride:
     raise ValueError(f"{who}: rows of {bank.shape[1]} bytes, the pack's are {layout.world_stride}")
   idx = None if which is None else np.ascontiguousarray(np.asarray(which).reshape(-1), np.int32)
@@ -495,6 +482,14 @@ def _view_host_source(who: str, verb: str, pack_bytes: bytes, rows, players, whi
   count = int(ply.size) if ply is not None else bank.shape[0] if idx is None else int(idx.size)
   if count < 1:
     raise ValueError(f"{who}: no rows to {verb}")
+  return layout, keep, bank, idx, ply, count
+
+
+def _view_host_source(who: str, verb: str, pack_bytes: bytes, rows, players, which, fingerprint, num_players, dev):
+  """What ego_layer_host, hash_views_host and ego_planes_host marshal alike: the host bank, `which`
+  and `players` as int32 arrays, the count.  Returns (layout, the result's leading shape — (R,) or
+  (R, P) —, the request's source fields, what must stay alive over the call)."""
+  layout, keep, bank, idx, ply, count = _host_source(who, verb, pack_bytes, rows, which, players, num_players, dev)
   if idx is not None and int(idx.size) != count:
     raise ValueError(f"{who}: which has {int(idx.size)} entries, players {count}")
   fields = dict(fingerprint=layout.fingerprint if fingerprint is None else int(fingerprint),
@@ -584,7 +579,7 @@ def state_hash_mask(pack_bytes: bytes, planes=None, fields=None, num_players: in
   req = _hash_request(MP_HASH_MASK, hash_spec(layout, planes, fields))
   req.pack, req.pack_len, req.cfg = ctypes.addressof(keep[0]), len(pack_bytes), ctypes.pointer(keep[1])
   req.out, req.out_bytes = out.ctypes.data, out.nbytes
-  _check(L, L.mp_snapshot(None, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpStatesHash)")
+  _send(L, None, req)
   return out
 
 
@@ -597,18 +592,8 @@ def hash_states_host(pack_bytes: bytes, rows, which=None, planes=None, fields=No
   the bank raises ValueError and leaves its element of `out` as it was.  `planes`, `fields`: the
   spec (`hash_spec`; both None: "the state").  `fingerprint`: the rows' (default: the pack's).
   Hashes compare only between rows of one fingerprint, hashed with one spec."""
-  L = load_library()
-  bank = np.ascontiguousarray(rows, np.uint8)
-  if bank.ndim != 2 or bank.shape[0] < 1:
-    raise ValueError("hash_states_host: rows must be a uint8 array [M, S]")
-  keep = _host_config(pack_bytes, num_players, dev)
-  layout = _layout_request(L, None, pack_bytes, num_players, dev)
-  if bank.shape[1] != layout.world_stride:
-    raise ValueError(f"hash_states_host: rows of {bank.shape[1]} bytes, the pack's are {layout.world_stride}")
-  idx = None if which is None else np.ascontiguousarray(np.asarray(which).reshape(-1), np.int32)
-  count = bank.shape[0] if idx is None else int(idx.size)
-  if count < 1:
-    raise ValueError("hash_states_host: no rows to hash")
+  layout, keep, bank, idx, _, count = _host_source("hash_states_host", "hash", pack_bytes, rows, which, None,
+                                                   num_players, dev)
   if out is None:
     out = np.zeros(count, np.int64)
   elif (not isinstance(out, np.ndarray) or out.dtype != np.int64 or out.shape != (count,) or
@@ -620,7 +605,7 @@ def hash_states_host(pack_bytes: bytes, rows, which=None, planes=None, fields=No
   req.bank, req.bank_rows, req.count = bank.ctypes.data, int(bank.shape[0]), count
   req.rows = None if idx is None else idx.ctypes.data
   req.out, req.out_bytes = out.ctypes.data, out.nbytes
-  _check(L, L.mp_snapshot(None, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpStatesHash)")
+  _send(load_library(), None, req)
   return out
 
 
@@ -641,11 +626,7 @@ class MpViewHash(ctypes.Structure):
 def view_hash_request(L, handle, op: int, **fields) -> MpViewHash:
   """Runs one MpViewHash request on engine `handle` (None: the host form); raises like every call.
   The returned request's `num_ids` is the length a class table must have."""
-  req = MpViewHash(ctypes.sizeof(MpViewHash), int(op))
-  for k, v in fields.items():
-    setattr(req, k, v)
-  _check(L, L.mp_snapshot(handle, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpViewHash)")
-  return req
+  return _request(L, handle, MpViewHash, (int(op),), fields)
 
 
 def view_layer_mask(layers, num_layers: int) -> int:
@@ -724,11 +705,7 @@ class MpEgoPlanes(ctypes.Structure):
 def ego_planes_request(L, handle, op: int, **fields) -> MpEgoPlanes:
   """Runs one MpEgoPlanes request on engine `handle` (None: the host form); raises like every call.
   The returned request's `num_ids` is the length a class table must have."""
-  req = MpEgoPlanes(ctypes.sizeof(MpEgoPlanes), int(op))
-  for k, v in fields.items():
-    setattr(req, k, v)
-  _check(L, L.mp_snapshot(handle, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpEgoPlanes)")
-  return req
+  return _request(L, handle, MpEgoPlanes, (int(op),), fields)
 
 
 def _plane_classes(classes, num_ids: int, num_classes) -> Tuple[np.ndarray, int]:
@@ -1074,6 +1051,13 @@ class MpEpisodeStarts(ctypes.Structure):
               ("bank_rows", ctypes.c_int32), ("reserved", ctypes.c_int32), ("reserved2", ctypes.c_uint64 * 3)]
 
 
+def _is_bank(bank, state_bytes: int) -> bool:
+  """Whether `bank` is a contiguous uint8 tensor [M, state_bytes]."""
+  import torch
+  return (isinstance(bank, torch.Tensor) and bank.dtype == torch.uint8 and bank.dim() == 2 and
+          int(bank.shape[1]) == int(state_bytes) and bank.is_contiguous())
+
+
 def check_episode_starts(bank, rows, verdicts, num_worlds: int, state_bytes: int, device) -> int:
   """The argument rules of Engine.set_episode_starts, without an engine: `bank` a contiguous uint8
   tensor [M, state_bytes] with M >= 1, `rows` a contiguous int32 tensor [num_worlds], `verdicts`
@@ -1084,8 +1068,7 @@ def check_episode_starts(bank, rows, verdicts, num_worlds: int, state_bytes: int
     return x.device.type == device.type and (device.index is None or x.device.index == device.index)
   def describe(x):
     return f"{getattr(x, 'dtype', type(x).__name__)} {tuple(getattr(x, 'shape', ()))}"
-  if (not isinstance(bank, torch.Tensor) or bank.dtype != torch.uint8 or bank.dim() != 2 or
-      int(bank.shape[1]) != int(state_bytes) or not bank.is_contiguous()):
+  if not _is_bank(bank, state_bytes):
     raise ValueError(f"set_episode_starts: bank must be a contiguous uint8 tensor [M, {int(state_bytes)}] "
                      f"(got {describe(bank)})")
   M = int(bank.shape[0])
@@ -1307,7 +1290,7 @@ def episode_stats_host(stats, step_type, reward, events, columns=(), pairs=(), a
   req.events = host(events, np.int32, (K, n, EVENT_ROWS, 4), "events")
   req.active = host(active, np.uint8, (K, n), "active")
   req.ran = host(ran, np.int32, (n,), "ran")
-  _check(L, L.mp_restore(None, ctypes.addressof(req), ctypes.sizeof(req)), "mp_restore (MpEpisodeStats)")
+  _send(L, None, req, "mp_restore")
   return stats
 
 
@@ -1472,7 +1455,7 @@ def pack_fields(pack_bytes: bytes, *, num_players: int = 0, dev: Optional[Dict[s
   req = MpKernelVariant(ctypes.sizeof(MpKernelVariant), 0, ctypes.addressof(buf), len(pack_bytes),
                         ctypes.pointer(cfg), ctypes.addressof(out) if out else None,
                         len(out) if out else 0)
-  _check(L, L.mp_snapshot(None, ctypes.addressof(req), ctypes.sizeof(req)), "mp_snapshot (MpKernelVariant)")
+  _send(L, None, req)
   return req.variant, (out.value.decode() if out else "")
 
 
@@ -2172,8 +2155,7 @@ class Engine:
     if listed:
       req.worlds = wl.data_ptr()
       req.count = C
-    _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
-           f"mp_restore ({type(req).__name__})")
+    _send(self._L, self._h, req, "mp_restore")
     self._state_args = (actions, result, mask, wl if listed else None)   # (kept until the next call: the launch may not have run yet)
     return result
 
@@ -2229,6 +2211,35 @@ class Engine:
       raise ValueError(f"{what} must hold integers (got {a.dtype})")
     return t.from_numpy(np.ascontiguousarray(a.reshape(-1), np.int32)).to(self.device)
 
+  def _rows(self, values, what: str):
+    """None, or `values` as `_device_ints` gives them."""
+    return None if values is None else self._device_ints(values, what)
+
+  def _bank(self, who: str, bank) -> int:
+    """M of `bank`, which must be a contiguous uint8 tensor [M, S] with M >= 1."""
+    S = int(self.info.world_state_bytes)
+    if not _is_bank(bank, S):
+      raise ValueError(f"{who}: bank must be a contiguous uint8 tensor [M, {S}]")
+    if bank.shape[0] < 1:
+      raise ValueError(f"{who}: the bank has no rows")
+    return int(bank.shape[0])
+
+  def _fingerprint(self, fingerprint: Optional[int]) -> int:
+    """The rows' fingerprint: the caller's, by default this engine's."""
+    return self.state_fingerprint if fingerprint is None else int(fingerprint)
+
+  def _out(self, who: str, out, shape, dtype, *, torch_name: bool = False, anywhere: bool = False):
+    """`out` of a request: a new tensor, or the caller's once it is contiguous and has the shape, the
+    dtype and (unless `anywhere`) the device.  `torch_name`: the message says "torch.int32", not "int32"."""
+    t = self._torch
+    if out is None:
+      return t.empty(shape, dtype=dtype, device=self.device)
+    if (not isinstance(out, t.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or
+        not out.is_contiguous() or not (anywhere or out.device == self.device)):
+      raise ValueError(f"{who}: out must be a contiguous {dtype if torch_name else str(dtype).split('.')[-1]} "
+                       f"tensor of shape {shape}" + ("" if anywhere else f" on {self.device}"))
+    return out
+
   def save_worlds(self, worlds=None, out=None):
     """Row i of a uint8 [M, S] device tensor = the record of world worlds[i] (None: every world,
     M = N); S = info.world_state_bytes.  `out`: the tensor to write (allocated when None).
@@ -2236,15 +2247,11 @@ class Engine:
     t = self._torch
     self.use_current_stream()
     S = int(self.info.world_state_bytes)
-    w = None if worlds is None else self._device_ints(worlds, "worlds")
+    w = self._rows(worlds, "worlds")
     M = self.N if w is None else int(w.numel())
     if M < 1:
       raise ValueError("save_worlds: no worlds to save")
-    if out is None:
-      out = t.empty((M, S), dtype=t.uint8, device=self.device)
-    elif (not isinstance(out, t.Tensor) or out.dtype != t.uint8 or tuple(out.shape) != (M, S) or
-          not out.is_contiguous()):
-      raise ValueError(f"save_worlds: out must be a contiguous uint8 tensor of shape {(M, S)}")
+    out = self._out("save_worlds", out, (M, S), t.uint8, anywhere=True)
     world_states_request(self._L, self._h, MP_STATES_SAVE, worlds=None if w is None else w.data_ptr(),
                          count=M, bank=out.data_ptr(), bank_bytes=out.numel())
     self._state_args = w   # (kept until the next call: the launch may not have run yet)
@@ -2263,46 +2270,30 @@ class Engine:
     rows to judge, in order, repeats allowed (None: every row).  Nothing of the engine's is
     written.  `fingerprint`: the rows' (default: this engine's).  Enqueued on the current stream;
     does not synchronise."""
-    t = self._torch
-    S = int(self.info.world_state_bytes)
-    if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
-        bank.shape[1] != S or not bank.is_contiguous()):
-      raise ValueError(f"check_states: bank must be a contiguous uint8 tensor [M, {S}]")
-    if bank.shape[0] < 1:
-      raise ValueError("check_states: the bank has no rows")
-    r = None if rows is None else self._device_ints(rows, "rows")
-    count = int(bank.shape[0]) if r is None else int(r.numel())
+    M = self._bank("check_states", bank)
+    r = self._rows(rows, "rows")
+    count = M if r is None else int(r.numel())
     if count < 1:
       raise ValueError("check_states: no rows to judge")
-    if out is None:
-      out = t.empty((count, 2), dtype=t.int32, device=self.device)
-    elif (not isinstance(out, t.Tensor) or out.dtype != t.int32 or tuple(out.shape) != (count, 2) or
-          not out.is_contiguous() or out.device != self.device):
-      raise ValueError(f"check_states: out must be a contiguous int32 tensor of shape {(count, 2)} on {self.device}")
-    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    out = self._out("check_states", out, (count, 2), self._torch.int32)
+    fp = self._fingerprint(fingerprint)
     self.use_current_stream()
     req = MpStatesCheck(ctypes.sizeof(MpStatesCheck), MP_CHECK_ROWS, fp)
-    req.bank, req.bank_rows, req.count = bank.data_ptr(), int(bank.shape[0]), count
+    req.bank, req.bank_rows, req.count = bank.data_ptr(), M, count
     req.rows = None if r is None else r.data_ptr()
     req.out, req.out_bytes = out.data_ptr(), out.numel() * 4
-    _check(self._L, self._L.mp_snapshot(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
-           "mp_snapshot (MpStatesCheck)")
+    _send(self._L, self._h, req)
     self._check_args = (bank, r, out)   # (kept until the next call: the launch may not have run yet)
     return out
 
   def _hash(self, what: str, op: int, bank, index, out, planes, fields, fingerprint: int):
     """One MpStatesHash request (`index`: the rows or worlds, or None; `bank`: None for the
     engine's own records)."""
-    t = self._torch
-    r = None if index is None else self._device_ints(index, "rows" if bank is not None else "worlds")
+    r = self._rows(index, "rows" if bank is not None else "worlds")
     count = (int(bank.shape[0]) if bank is not None else self.N) if r is None else int(r.numel())
     if count < 1:
       raise ValueError(f"{what}: nothing to hash")
-    if out is None:
-      out = t.empty((count,), dtype=t.int64, device=self.device)
-    elif (not isinstance(out, t.Tensor) or out.dtype != t.int64 or tuple(out.shape) != (count,) or
-          not out.is_contiguous() or out.device != self.device):
-      raise ValueError(f"{what}: out must be a contiguous int64 tensor of shape {(count,)} on {self.device}")
+    out = self._out(what, out, (count,), self._torch.int64)
     spec = hash_spec(self.state_layout(), planes, fields)
     self.use_current_stream()
     req = _hash_request(op, spec, fingerprint)
@@ -2311,8 +2302,7 @@ class Engine:
     req.count = count
     req.rows = None if r is None else r.data_ptr()
     req.out, req.out_bytes = out.data_ptr(), count * 8
-    _check(self._L, self._L.mp_snapshot(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
-           "mp_snapshot (MpStatesHash)")
+    _send(self._L, self._h, req)
     self._hash_args = (bank, r, out)   # (kept until the next call: the launch may not have run yet)
     return out
 
@@ -2329,15 +2319,8 @@ class Engine:
     repeated custom spec only enqueue.  Nothing of the engine's is written.  Hashes compare only
     between rows of one fingerprint, hashed with one spec.  `fingerprint`: the rows' (default:
     this engine's).  Enqueued on the current stream; does not synchronise."""
-    t = self._torch
-    S = int(self.info.world_state_bytes)
-    if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
-        bank.shape[1] != S or not bank.is_contiguous()):
-      raise ValueError(f"hash_states: bank must be a contiguous uint8 tensor [M, {S}]")
-    if bank.shape[0] < 1:
-      raise ValueError("hash_states: the bank has no rows")
-    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
-    return self._hash("hash_states", MP_HASH_ROWS, bank, rows, out, planes, fields, fp)
+    self._bank("hash_states", bank)
+    return self._hash("hash_states", MP_HASH_ROWS, bank, rows, out, planes, fields, self._fingerprint(fingerprint))
 
   def hash_worlds(self, worlds=None, out=None, planes=None, fields=None):
     """int64 [M] device tensor: `hash_states` of the records of `worlds` (None: every world, M =
@@ -2352,30 +2335,23 @@ class Engine:
     first (`check_states`' rules, one more launch) and a world whose row is malformed is left as
     it is; the next synchronising call (`sync`) raises ValueError naming the world, the row and
     the rule.  Enqueued on the current stream."""
-    t = self._torch
-    S = int(self.info.world_state_bytes)
-    if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
-        bank.shape[1] != S or not bank.is_contiguous()):
-      raise ValueError(f"load_worlds: bank must be a contiguous uint8 tensor [M, {S}]")
-    if bank.shape[0] < 1:
-      raise ValueError("load_worlds: the bank has no rows")
+    M = self._bank("load_worlds", bank)
     s = self._device_ints(src, "src")
     if s.numel() != self.N:
       raise ValueError(f"load_worlds: src must have {self.N} entries (got {s.numel()})")
-    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    fp = self._fingerprint(fingerprint)
     self.use_current_stream()
     if check:
-      checked = t.empty_like(s)
+      checked = self._torch.empty_like(s)
       req = MpStatesCheck(ctypes.sizeof(MpStatesCheck), MP_CHECK_FILTER, fp)
-      req.bank, req.bank_rows, req.count = bank.data_ptr(), int(bank.shape[0]), self.N
+      req.bank, req.bank_rows, req.count = bank.data_ptr(), M, self.N
       req.rows, req.out, req.out_bytes = s.data_ptr(), checked.data_ptr(), self.N * 4
-      _check(self._L, self._L.mp_snapshot(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
-             "mp_snapshot (MpStatesCheck)")
+      _send(self._L, self._h, req)
       loaded = checked
     else:
       loaded = s
-    world_states_request(self._L, self._h, MP_STATES_LOAD, bank=bank.data_ptr(),
-                         bank_rows=int(bank.shape[0]), src=loaded.data_ptr(), fingerprint=fp)
+    world_states_request(self._L, self._h, MP_STATES_LOAD, bank=bank.data_ptr(), bank_rows=M,
+                         src=loaded.data_ptr(), fingerprint=fp)
     self._state_args = (s, loaded)   # (kept until the next call: the launches may not have run yet)
 
   # -- episode starts (include/mp_engine.h: an MpEpisodeStarts request) --
@@ -2397,20 +2373,18 @@ class Engine:
     M = check_episode_starts(bank, rows, verdicts, self.N, int(self.info.world_state_bytes), self.device)
     if not isinstance(fresh, (bool, np.bool_)):
       raise ValueError(f"set_episode_starts: fresh must be True or False (got {fresh!r})")
-    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    fp = self._fingerprint(fingerprint)
     req = MpEpisodeStarts(ctypes.sizeof(MpEpisodeStarts), 1 if fresh else 0, fp)
     req.bank, req.rows, req.bank_rows = bank.data_ptr(), rows.data_ptr(), M
     req.verdicts = None if verdicts is None else verdicts.data_ptr()
-    _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
-           "mp_restore (MpEpisodeStarts)")
+    _send(self._L, self._h, req, "mp_restore")
     self._episode_starts = {"bank": bank, "rows": rows, "verdicts": verdicts, "fresh": bool(fresh),
                             "fingerprint": fp}
 
   def clear_episode_starts(self):
     """Episodes start from the level's own map again; the engine's launches are what they were."""
     req = MpEpisodeStarts(ctypes.sizeof(MpEpisodeStarts))
-    _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
-           "mp_restore (MpEpisodeStarts)")
+    _send(self._L, self._h, req, "mp_restore")
     self._episode_starts = None
 
   @property
@@ -2463,8 +2437,7 @@ class Engine:
             raise ValueError(f"set_episode_stats: out.{key}{'' if sub is None else '[' + repr(sub) + ']'} must be "
                              f"a contiguous {dtype} tensor of shape {shape} on {self.device}")
     req = _stats_request(MP_STATS_REGISTER, cols, len(names), pcols, len(pnames), out.arrays, self._torch_ptr)
-    _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
-           "mp_restore (MpEpisodeStats)")
+    _send(self._L, self._h, req, "mp_restore")
     self._stats = out
     self._stats_scratch = {}
     return out
@@ -2472,8 +2445,7 @@ class Engine:
   def clear_episode_stats(self):
     """No statistics launch any more: the engine issues exactly the launches it issued before."""
     req = MpEpisodeStats(ctypes.sizeof(MpEpisodeStats), MP_STATS_CLEAR)
-    _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
-           "mp_restore (MpEpisodeStats)")
+    _send(self._L, self._h, req, "mp_restore")
     self._stats = None
     self._stats_scratch = {}
 
@@ -2531,8 +2503,7 @@ class Engine:
     req.events, req.steps, req.count = ev.data_ptr(), K, M
     req.active = None if active is None else active.data_ptr()
     req.ran = None if ran is None else ran.data_ptr()
-    _check(self._L, self._L.mp_restore(self._h, ctypes.addressof(req), ctypes.sizeof(req)),
-           "mp_restore (MpEpisodeStats)")
+    _send(self._L, self._h, req, "mp_restore")
     self._tally_args = (ev, active, ran, out, pout)   # (kept until the next call: the launch may not have run yet)
     return (out, pout) if pnames else out
 
@@ -2546,31 +2517,19 @@ class Engine:
     OBS_POSITION, OBS_ORIENTATION, OBS_INVENTORY — equal to what observe() / a load_worlds of the
     row gives; the transition kinds are not functions of a record and are refused.
     `fingerprint`: the rows' (default: this engine's).  Enqueued on the current stream."""
-    t = self._torch
-    S = int(self.info.world_state_bytes)
-    if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
-        bank.shape[1] != S or not bank.is_contiguous()):
-      raise ValueError(f"observe_states: bank must be a contiguous uint8 tensor [M, {S}]")
-    if bank.shape[0] < 1:
-      raise ValueError("observe_states: the bank has no rows")
+    M = self._bank("observe_states", bank)
     if isinstance(kind, bool) or not isinstance(kind, (int, np.integer)) or int(kind) not in self.shapes:
       raise ValueError(f"observe_states: {kind!r} is no observation kind")
     kind = int(kind)
-    r = None if rows is None else self._device_ints(rows, "rows")
-    count = int(bank.shape[0]) if r is None else int(r.numel())
+    r = self._rows(rows, "rows")
+    count = M if r is None else int(r.numel())
     if count < 1:
       raise ValueError("observe_states: no rows to draw")
     shape, dtype = self.shapes[kind]
-    shape = (count,) + tuple(int(d) for d in shape[1:])
-    if out is None:
-      out = t.empty(shape, dtype=dtype, device=self.device)
-    elif (not isinstance(out, t.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or
-          not out.is_contiguous() or out.device != self.device):
-      raise ValueError(f"observe_states: out must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
-    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    out = self._out("observe_states", out, (count,) + tuple(int(d) for d in shape[1:]), dtype, torch_name=True)
     self.use_current_stream()
-    states_observe_request(self._L, self._h, kind=kind, fingerprint=fp, bank=bank.data_ptr(),
-                           bank_rows=int(bank.shape[0]), rows=None if r is None else r.data_ptr(),
+    states_observe_request(self._L, self._h, kind=kind, fingerprint=self._fingerprint(fingerprint),
+                           bank=bank.data_ptr(), bank_rows=M, rows=None if r is None else r.data_ptr(),
                            count=count, dst=out.data_ptr(), dst_bytes=out.numel() * out.element_size())
     self._state_args = (bank, r, out)   # (kept until the next call: the launch may not have run yet)
     return out
@@ -2587,13 +2546,7 @@ class Engine:
     engine's is written and no device memory of the engine's is allocated.  A row or player index
     out of range leaves its element as it was; the next synchronising call raises ValueError.
     `fingerprint`: the rows' (default: this engine's).  Enqueued on the current stream."""
-    t = self._torch
-    S = int(self.info.world_state_bytes)
-    if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
-        bank.shape[1] != S or not bank.is_contiguous()):
-      raise ValueError(f"observe_views: bank must be a contiguous uint8 tensor [M, {S}]")
-    if bank.shape[0] < 1:
-      raise ValueError("observe_views: the bank has no rows")
+    M = self._bank("observe_views", bank)
     if isinstance(kind, bool) or not isinstance(kind, (int, np.integer)) or int(kind) not in self.shapes:
       raise ValueError(f"observe_views: {kind!r} is no observation kind")
     kind = int(kind)
@@ -2602,23 +2555,17 @@ class Engine:
     if players is None:
       raise ValueError("observe_views: players is required")
     p = self._device_ints(players, "players")
-    r = None if rows is None else self._device_ints(rows, "rows")
+    r = self._rows(rows, "rows")
     count = int(p.numel())
     if count < 1:
       raise ValueError("observe_views: no views to draw")
     if r is not None and int(r.numel()) != count:
       raise ValueError(f"observe_views: rows has {int(r.numel())} entries, players {count}")
     shape, dtype = self.shapes[kind]
-    shape = (count,) + tuple(int(d) for d in shape[2:])
-    if out is None:
-      out = t.empty(shape, dtype=dtype, device=self.device)
-    elif (not isinstance(out, t.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or
-          not out.is_contiguous() or out.device != self.device):
-      raise ValueError(f"observe_views: out must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
-    fp = self.state_fingerprint if fingerprint is None else int(fingerprint)
+    out = self._out("observe_views", out, (count,) + tuple(int(d) for d in shape[2:]), dtype, torch_name=True)
     self.use_current_stream()
-    states_view_request(self._L, self._h, kind=kind, fingerprint=fp, bank=bank.data_ptr(),
-                        bank_rows=int(bank.shape[0]), rows=None if r is None else r.data_ptr(),
+    states_view_request(self._L, self._h, kind=kind, fingerprint=self._fingerprint(fingerprint),
+                        bank=bank.data_ptr(), bank_rows=M, rows=None if r is None else r.data_ptr(),
                         players=p.data_ptr(), count=count, dst=out.data_ptr(),
                         dst_bytes=out.numel() * out.element_size())
     self._state_args = (bank, r, p, out)   # (kept until the next call: the launch may not have run yet)
@@ -2628,37 +2575,18 @@ class Engine:
     """What observe_ego_layer, hash_views and observe_ego_planes read: the checked `bank` (None: the
     engine's worlds), `rows` and `players` as device ints, the count.  Returns (count, rows,
     players, the request's source fields)."""
-    t = self._torch
-    S = int(self.info.world_state_bytes)
-    if bank is not None:
-      if (not isinstance(bank, t.Tensor) or bank.dtype != t.uint8 or bank.dim() != 2 or
-          bank.shape[1] != S or not bank.is_contiguous()):
-        raise ValueError(f"{who}: bank must be a contiguous uint8 tensor [M, {S}]")
-      if bank.shape[0] < 1:
-        raise ValueError(f"{who}: the bank has no rows")
-    there = self.N if bank is None else int(bank.shape[0])
-    p = None if players is None else self._device_ints(players, "players")
-    r = None if rows is None else self._device_ints(rows, "rows")
+    there = self.N if bank is None else self._bank(who, bank)
+    p = self._rows(players, "players")
+    r = self._rows(rows, "rows")
     count = int(p.numel()) if p is not None else int(r.numel()) if r is not None else there
     if count < 1:
       raise ValueError(f"{who}: no views to {verb}")
     if r is not None and int(r.numel()) != count:
       raise ValueError(f"{who}: rows has {int(r.numel())} entries, players {count}")
-    fields = dict(fingerprint=self.state_fingerprint if fingerprint is None else int(fingerprint),
-                  bank=None if bank is None else bank.data_ptr(), bank_rows=0 if bank is None else there,
+    fields = dict(fingerprint=self._fingerprint(fingerprint), bank=None if bank is None else bank.data_ptr(),
+                  bank_rows=0 if bank is None else there,
                   rows=None if r is None else r.data_ptr(), players=None if p is None else p.data_ptr(), count=count)
     return count, r, p, fields
-
-  def _view_out(self, who: str, out, shape, dtype):
-    """`out` of a draw of views: a new tensor, or the caller's once it has the shape, dtype and device."""
-    t = self._torch
-    if out is None:
-      return t.empty(shape, dtype=dtype, device=self.device)
-    if (not isinstance(out, t.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or
-        not out.is_contiguous() or out.device != self.device):
-      raise ValueError(f"{who}: out must be a contiguous {str(dtype).split('.')[-1]} tensor of shape {shape} on "
-                       f"{self.device}")
-    return out
 
   @staticmethod
   def _view_ring(out, ring: bool, block: int):
@@ -2688,7 +2616,7 @@ class Engine:
     count, r, p, src = self._view_source("observe_ego_layer", "draw", bank, rows, players, fingerprint)
     shape = self.ego_layer_shape
     shape = (count,) + (shape[1:] if p is None else shape[2:])
-    out = self._view_out("observe_ego_layer", out, shape, self._torch.int32)
+    out = self._out("observe_ego_layer", out, shape, self._torch.int32)
     self.use_current_stream()
     ego_layer_request(self._L, self._h, MP_EGO_DRAW, dst=out.data_ptr(), dst_bytes=out.numel() * 4, **src)
     self._state_args = (bank, r, p, out)   # (kept until the next call: the launch may not have run yet)
@@ -2704,10 +2632,7 @@ class Engine:
       ego_layer_request(self._L, self._h, MP_EGO_REGISTER)
       self._ego_layer = None
       return None
-    shape = self.ego_layer_shape
-    if (not isinstance(out, t.Tensor) or out.dtype != t.int32 or tuple(out.shape) != shape or
-        not out.is_contiguous() or out.device != self.device):
-      raise ValueError(f"bind_ego_layer: out must be a contiguous int32 tensor of shape {shape} on {self.device}")
+    out = self._out("bind_ego_layer", out, self.ego_layer_shape, t.int32)
     ego_layer_request(self._L, self._h, MP_EGO_REGISTER, **self._view_ring(out, False, out.numel() * 4))
     self._ego_layer = out
     return out
@@ -2773,7 +2698,7 @@ class Engine:
     count, r, p, src = self._view_source("hash_views", "hash", bank, rows, players, fingerprint)
     mask = view_layer_mask(layers, int(self.info.num_layers))
     cls = self._view_classes(classes)
-    out = self._view_out("hash_views", out, (count, self.P) if p is None else (count,), self._torch.int64)
+    out = self._out("hash_views", out, (count, self.P) if p is None else (count,), self._torch.int64)
     self.use_current_stream()
     view_hash_request(self._L, self._h, MP_VIEWHASH_DRAW, layer_mask=mask,
                       classes=None if cls is None else cls.data_ptr(),
@@ -2865,7 +2790,7 @@ class Engine:
     cls, C = self._plane_classes(classes, num_classes)
     shape = self.ego_planes_shape(C, facing)
     shape = (count,) + (shape[1:] if p is None else shape[2:])
-    out = self._view_out("observe_ego_planes", out, shape, self._torch.uint8)
+    out = self._out("observe_ego_planes", out, shape, self._torch.uint8)
     self.use_current_stream()
     ego_planes_request(self._L, self._h, MP_EGOPLANES_DRAW, layer_mask=mask, classes=cls.data_ptr(),
                        classes_len=int(cls.numel()), num_classes=C, facing=int(bool(facing)), dst=out.data_ptr(),
