@@ -1484,10 +1484,16 @@ typedef struct {
  *       running.returns[p] += r[p] (one f64 add a step, in step order), running.length += 1,
  *       running.counts / pairs += tally(E);
  *       if st == LAST: last := running, total += running, episodes += 1, open := 0
- *   otherwise nothing (a frozen world on LAST, a row loaded from a finished episode, an episode not
- *   seen from its FIRST).
+ *   otherwise nothing (a frozen world on LAST, a row loaded from a finished episode into a world
+ *   with no open episode, an episode not seen from its FIRST).
  *   dropped += E's header `dropped`, on every step that ran.
- * An episode cut short by mp_reset or a load is dropped: its running is zeroed, nothing is counted.
+ * An episode cut short by mp_reset, or by a load of a row that is not finished, is dropped: both
+ * write FIRST, its running is zeroed, nothing is counted.  The exception, which follows from the
+ * rule as it stands: a load of a row saved from a FINISHED episode writes LAST with zero rewards and
+ * no events, so in a world whose episode is open it takes the "otherwise, if open" branch — the open
+ * episode is closed as if that load were its last step: running.length += 1, last := running,
+ * total += running, episodes += 1, open := 0.  A caller that loads finished rows over running
+ * episodes and wants them left out subtracts `last` of those worlds from `total` after the load.
  * One wave owns a world's statistics and walks its steps in order; there is no global atomic, so
  * every value is bitwise reproducible.
  *

@@ -15,7 +15,11 @@ K-step calls with a persistent `stopped`, per-step state rows that become banks,
 starts whose `rows` are rewritten in place, and four read-only classes that draw, hash and check
 saved states; there the twin runs the other form of every new K-step call (see `_Side`).  The
 model does not state fresh=True starts: it says which worlds it speaks for (`ModelEngine.exact`),
-and the runner compares those."""
+and the runner compares those.  The UNIT programs (UNIT_COMMITTED) add listed steps (worlds=, with
+entries that are no world or repeat one), episode statistics registered and cleared, the three view
+units (EGO_LAYER, the view hashes, the planes) registered and cleared, and reads of them; the twin
+registers nothing, folds the statistics on the host from what its single steps left, and runs a
+list as the masked request over all worlds."""
 import zlib
 
 import numpy as np
@@ -135,6 +139,81 @@ STATE_SEEDS = [2001, 2005, 2001, 2007, 2005, 2003, 2000, 2002, 2001, 2003, 2000,
 STATE_COMMITTED = list(zip(STATE_SEEDS, STATE_PROFILES))
 
 
+# ---- the unit programs: listed steps, episode statistics and the three registered view units
+UNIT_MUTATING = ("step_listed", "many_listed", "stats_set", "stats_clear", "units_set", "units_clear")
+UNIT_READ_ONLY = ("unit_rows",)
+UNIT_ALL_MUTATING = MUTATING + UNIT_MUTATING
+UNIT_CLASSES = STATE_CLASSES + UNIT_MUTATING + UNIT_READ_ONLY
+LISTED_CLASSES = ("step_listed", "many_listed")
+UNIT_STEP_CLASSES = ALL_STEP_CLASSES + LISTED_CLASSES
+# what a rollout ring refuses (masks, stops, lists), and the registered starts, whose twin is a host
+# loop of single steps that would turn the twin's ring K times where the engine's turns once
+RING_REFUSED = ("step_active", "many_active", "many_until", "unstop", "step_many_states", "starts_set",
+                "starts_rows", "starts_clear") + LISTED_CLASSES
+UNIT_RING_CLASSES = tuple(c for c in UNIT_CLASSES if c not in RING_REFUSED)
+# (80, where the state set has 70: the statistics' totals must hold finished episodes at the end of a
+# program, so its last registration is followed by UNIT_STATS_TAIL ops at least)
+UNIT_MIN_OPS, UNIT_MAX_OPS, UNIT_MAX_WORLD_STEPS = 80, 110, 260
+UNIT_STATS_TAIL = 18                                     # ops behind the last stats_set
+UNIT_LAST_STATS_SET = UNIT_MIN_OPS - UNIT_STATS_TAIL     # no stats_set is drawn behind this op
+UNIT_LAST_STATS_CLEAR = UNIT_LAST_STATS_SET - 7          # ... and no stats_clear behind this one
+UNIT_STATS_LIFE, UNIT_STARTS_LIFE = 6, 8                 # ops a registration lives at least
+UNIT_NAMES = ("ego", "hash", "planes")
+PAIR_COLUMNS = ("interaction.row_player_idx>col_player_idx", "gift.gifter_index>receipient_index",
+                "extraction_pair.player_a>player_b", "sanctioning.source>target", "zap.source>target")
+NO_BEAM = ("coins", "collaborative_cooking__cramped")
+FILL = 0xA5   # the byte the runner fills a listed call's tensors with before the call
+
+
+def _unit_profiles():
+  out = []
+  for li, pack in enumerate(LEVEL_PACKS):
+    hdr = pack_lib.loads(E.load_pack(pack))["hdr"]
+    default_p = int(hdr[20]) or int(hdr[7])
+    fewer = "in_the_matrix" not in pack and pack != "coins"
+    base = dict(pack=pack, stock=False, rich=True, auto_reset=True, frames=LONG_EPISODES.get(pack, EPISODE_FRAMES))
+    out.append(dict(base, name=f"{pack}-units-n6", n=6, ring=0, world_pool=1, unfused=True if li % 2 else None,
+                    num_players=max(1, default_p - 1) if fewer else 0, views=(E.OBS_RGB,), classes=UNIT_CLASSES))
+    if li % 2 == 0:   # form 1: no ring, WORLD.RGB pooled by 8 and LAYER bound
+      out.append(dict(base, name=f"{pack}-units-n23", n=23, ring=0, world_pool=8, unfused=None, num_players=0,
+                      views=(E.OBS_WORLD_RGB, E.OBS_LAYER), classes=UNIT_CLASSES))
+    else:             # form 2: a ring, which refuses a list: the first op behind the reset asks for one
+      out.append(dict(base, name=f"{pack}-units-n23", n=23, ring=RING_SLOTS, world_pool=1, unfused=None,
+                      num_players=0, views=(E.OBS_RGB,), classes=UNIT_RING_CLASSES))
+  out.append(dict(name="stock_clean_up-units-n23", pack="clean_up", stock=True, rich=False, n=23, ring=0,
+                  world_pool=1, auto_reset=True, unfused=None, num_players=0, views=(E.OBS_WORLD_RGB,),
+                  frames=0, classes=UNIT_CLASSES))
+  return out
+
+
+UNIT_PROFILES = _unit_profiles()
+# (program seed, profile): searched on the model alone (tests/tools/search_unit_programs.py)
+UNIT_SEEDS = [3002, 3000, 3018, 3012, 3000, 3008, 3015, 3014, 3003, 3001, 3050, 3000, 3003, 3000, 3009, 3018, 3002,
+              3003, 3000]
+UNIT_COMMITTED = list(zip(UNIT_SEEDS, UNIT_PROFILES))
+
+
+def is_unit_profile(profile):
+  return "-units-" in profile["name"]
+
+
+def level_columns(profile):
+  """(the level's default columns, {column: [filters "key=value" it can take]}, its pair column)."""
+  import episode_stats_model
+  hdr = pack_lib.loads(E.load_pack(profile["pack"]))["hdr"]
+  columns = E.level_event_columns(int(hdr[1]))
+  filters = {}
+  for name in columns:
+    event, key = name.split(".")
+    known = episode_stats_model.EVENTS.get(event, (0, {}))[1]
+    keys = [k for k in known if k not in E.EVENT_PLAYER_KEYS and k in E.EVENT_FIELDS[event]]
+    filters[name] = [f"{k}={v}" for k in keys for v in range(0, min(3, known[k][2] + 1))]
+  # (every level's rules list the zap, but two of them have no beam: no two-player event there)
+  events = {n.split(".")[0] for n in columns} - ({"zap"} if profile["pack"] in NO_BEAM else set())
+  pair = next((p for p in PAIR_COLUMNS if p.split(".")[0] in events), None)
+  return columns, filters, pair
+
+
 def rich_pack(name, raw):
   """The level's variant that pays often, where the parity tests have one; else the pack itself."""
   if name == "clean_up":
@@ -191,8 +270,13 @@ def _geometry(profile):
   spec = np.asarray(t["action_spec"]).reshape(-1, 3)[:A]
   R = ((len(t["mx_states"]) - 8) // 2 if "mx_states" in t else int(t["gr_i32"][7]) if "gr_i32" in t else 0)
   kinds = [E.OBS_LAYER, E.OBS_POSITION, E.OBS_ORIENTATION, E.OBS_READY_TO_SHOOT] + ([E.OBS_INVENTORY] if R else [])
-  return dict(N=profile["n"], P=P, A=A, nact=len(np.asarray(t["action_table"]).reshape(-1, 4)),
-              lo=spec[:, 0].astype(np.int32), hi=spec[:, 1].astype(np.int32), row_kinds=kinds)
+  g = dict(N=profile["n"], P=P, A=A, nact=len(np.asarray(t["action_table"]).reshape(-1, 4)),
+           lo=spec[:, 0].astype(np.int32), hi=spec[:, 1].astype(np.int32), row_kinds=kinds)
+  if is_unit_profile(profile):
+    import ego_layer_model
+    g.update(ids=E.num_layer_ids_host(profile_pack(profile), num_players=profile["num_players"]),
+             L=ego_layer_model.geometry(E.load_pack(profile["pack"]))[2], columns=level_columns(profile))
+  return g
 
 
 def _ids(rng, g, shape, bad=0.0):
@@ -220,8 +304,12 @@ class _Gen:
     self.registered = None     # the rows of the bank a registration names
     self.rows_of = None        # ... of the last `rows` tensor handed out (it outlives a clear)
     self.wide_reads = 0
-    w = ACTION_WEIGHTS.get(profile["pack"]) if profile.get("rich") or "states" in profile["name"] else None
-    if "states" in profile["name"] and w is None:
+    later = "states" in profile["name"] or is_unit_profile(profile)
+    w = ACTION_WEIGHTS.get(profile["pack"]) if profile.get("rich") or later else None
+    self.wide_unit_reads = 0
+    self.set_at = {"stats": -100, "starts": -100}   # the op of the last stats_set / starts_set
+    self.stats_live, self.units_live, self.listed_first = False, set(), bool(profile["ring"]) and is_unit_profile(profile)
+    if later and w is None:
       w = [1, 4] + [1] * (g["nact"] - 2)
     self.weights = None if w is None else np.asarray(w, np.float64) / sum(w)
     assert self.weights is None or len(self.weights) == g["nact"], profile["name"]
@@ -231,6 +319,8 @@ class _Gen:
     return (c == ops[-1]["op"] or (c in ("load", "starts_set", "observe_rows", "observe_views", "check") and not self.banks) or
             (c == "restore" and not self.have_snap) or (c in ALL_STEP_CLASSES and budget < 1) or
             (c == "starts_clear" and self.registered is None) or (c == "starts_rows" and self.rows_of is None) or
+            (c == "stats_clear" and not self.stats_live) or (c == "units_clear" and not self.units_live) or
+            (c in LISTED_CLASSES and budget < 1) or
             (c == "step_host" and not self.host_run_done and (budget < HOST_RUN or len(ops) + HOST_RUN > length)))
 
   def ids(self, shape, bad=0.0):
@@ -243,10 +333,11 @@ class _Gen:
       a = np.where(rng.random(shape) < bad, out, a).astype(np.int32)
     return a
 
-  def _many(self, c, ks, weights):
-    """The action block of a K-step op: K, plain / repeat / slice, ids or raw fields."""
+  def _many(self, c, ks, weights, cols=None):
+    """The action block of a K-step op: K, plain / repeat / slice, ids or raw fields (`cols`: its
+    columns, the entries of a list; None: the worlds)."""
     rng, g = self.rng, self.g
-    N, P = g["N"], g["P"]
+    N, P = cols or g["N"], g["P"]
     ks = [k for k in ks if k <= self.budget]
     p = np.array(weights[:len(ks)], np.float64)
     K = int(rng.choice(ks, p=p / p.sum()))
@@ -412,8 +503,109 @@ class _Gen:
       b = int(rng.integers(len(self.banks)))
       ops.append(dict(op=c, bank=b, row=int(rng.integers(self.banks[b])), player=int(rng.integers(P)),
                       field=str(rng.choice(["orientation", "avatar_x"]))))
+    # ---- the unit classes
+    elif c == "step_listed":
+      worlds, bad = self._list()
+      ops.append(dict(op=c, worlds=worlds, bad=bad, actions=self.ids((len(worlds), P), bad=0.01)))
+      self.budget -= 1
+    elif c == "many_listed":
+      worlds, bad = self._list()
+      M = len(worlds)
+      op = self._many(c, STATE_K, [1, 2, 4, 4, 1], cols=M)
+      op.update(worlds=worlds, bad=bad)
+      K = op["K"]
+      form = str(rng.choice(["none", "km", "m"], p=[0.4, 0.4, 0.2]))
+      op["active"] = None if form == "none" else (rng.random((K, M) if form == "km" else (M,)) < 0.7).astype(np.uint8)
+      op["observations"] = self._row_kinds() if rng.random() < 0.4 else None
+      op["until"] = UNTILS[int(rng.integers(len(UNTILS)))] if rng.random() < 0.6 else None
+      op["returns"] = bool(op["until"] is not None and rng.random() < 0.7)
+      op["gamma"] = float(rng.choice(GAMMAS)) if op["returns"] else 1.0
+      op["use_stopped"] = op["until"] is not None   # (the persistent `stopped` [N], by world)
+      ops.append(op)
+    elif c == "stats_set":
+      columns, filters, pair = g["columns"]
+      how = str(rng.choice(["default", "none", "subset"], p=[0.4, 0.15, 0.45])) if columns else "none"
+      if how == "subset":
+        pick = rng.random(len(columns)) < 0.6
+        pick[rng.integers(len(pick))] = True
+        chosen = [n for n, p in zip(columns, pick) if p]
+        able = [n for n in chosen if filters[n]]
+        if able:   # one [key=value] filter where the level has a filterable payload
+          n = able[int(rng.integers(len(able)))]
+          chosen[chosen.index(n)] = f"{n}[{filters[n][int(rng.integers(len(filters[n])))]}]"
+        cols = tuple(chosen)
+      else:
+        cols = "default" if how == "default" else ()
+      ops.append(dict(op=c, columns=cols, pairs=(pair,) if pair else ()))
+      self.stats_live = True
+    elif c == "stats_clear":
+      ops.append(dict(op=c))
+      self.stats_live = False
+    elif c == "units_set":
+      pick = rng.random(3) < 0.6
+      pick[rng.integers(3)] = True
+      ids, L = g["ids"], g["L"]
+      op = dict(op=c, units=tuple(n for n, p in zip(UNIT_NAMES, pick) if p))
+
+      def layers():
+        if rng.random() < 0.5:
+          return None
+        keep = rng.random(L) < 0.6
+        keep[rng.integers(L)] = True
+        return tuple(int(i) for i in np.nonzero(keep)[0])
+      if "hash" in op["units"]:
+        both = bool(rng.random() < 0.6)   # drawn layers and a drawn class table, or neither
+        op["hash"] = dict(layers=layers() if both else None,
+                          classes=rng.integers(0, 4, size=ids).astype(np.int32) if both else None)
+      if "planes" in op["units"]:
+        C = int(rng.integers(2, 6))
+        table = rng.integers(-1, C, size=ids).astype(np.int32)
+        table[rng.integers(ids)] = -1
+        table[rng.integers(ids)] = C - 1 if rng.random() < 0.5 else 0
+        given = bool(rng.random() < 0.5)
+        op["planes"] = dict(classes=table, layers=layers(), facing=bool(rng.random() < 0.6),
+                            num_classes=C if given else None, offset=int(rng.integers(0, 16)))
+      ops.append(op)
+      self.units_live |= set(op["units"])
+    elif c == "units_clear":
+      name = sorted(self.units_live)[int(rng.integers(len(self.units_live)))]
+      ops.append(dict(op=c, unit=name))
+      self.units_live.discard(name)
+    elif c == "unit_rows":
+      unit = str(rng.choice(UNIT_NAMES))
+      b = int(rng.integers(-1, len(self.banks)))   # -1: the live worlds
+      there = N if b < 0 else self.banks[b]
+      wide = self.wide_unit_reads == 0   # one read of a program has more rows than worlds
+      self.wide_unit_reads += 1
+      count = N + 2 if wide else int(rng.integers(1, min(N, 6) + 1))
+      rows = self._pick_rows(count, there)
+      op = dict(op=c, unit=unit, bank=b, rows=rows,
+                players=rng.integers(0, P, size=count).astype(np.int32) if rng.random() < 0.5 else None)
+      if unit == "hash":
+        op["params"] = dict(layers=None, classes=rng.integers(0, 3, size=g["ids"]).astype(np.int32)
+                            if rng.random() < 0.5 else None)
+      if unit == "planes":
+        C = int(rng.integers(1, 5))
+        table = rng.integers(-1, C, size=g["ids"]).astype(np.int32)
+        op["params"] = dict(classes=table, layers=None, facing=bool(rng.random() < 0.5), num_classes=C)
+        op["offset"] = int(rng.integers(0, 16))
+      ops.append(op)
     else:
       raise ValueError(c)
+
+  def _list(self):
+    """(worlds int32 [M], bad): the list of a listed op; about one in four carries one entry outside
+    [0, N) and one that repeats an earlier entry's world."""
+    rng, N = self.rng, self.g["N"]
+    M = N if rng.random() < 0.3 else int(rng.integers(1, N + 1))
+    worlds = rng.choice(N, size=M, replace=False).astype(np.int32)
+    bad = bool(M >= 3 and rng.random() < 0.25)
+    if bad:
+      three = sorted(rng.choice(M, size=3, replace=False).tolist())
+      out = three.pop(int(rng.integers(3)))
+      worlds[three[1]] = worlds[three[0]]
+      worlds[out] = int(rng.choice([-1, -7, N, N + 5]))
+    return worlds, bad
 
   def _start_rows(self, rows_in_bank):
     """`rows` of a registration: valid indices and -1s, several worlds on one row."""
@@ -442,29 +634,73 @@ def required_pairs():
   return pairs + [(a, r) for a in NEW_MUTATING for r in READ_ONLY]
 
 
+def required_unit_pairs():
+  """The adjacencies the unit programs owe: every ordered pair of distinct mutating classes with a
+  unit class in it, and unit_rows behind every mutating unit class."""
+  pairs = [(a, b) for a in UNIT_ALL_MUTATING for b in UNIT_ALL_MUTATING
+           if a != b and (a in UNIT_MUTATING or b in UNIT_MUTATING)]
+  return pairs + [(a, r) for a in UNIT_MUTATING for r in UNIT_READ_ONLY]
+
+
 def assigned_pairs(profile):
   """The share of `required_pairs` that the program of `profile` must hold: the generator steers
   its draws toward them, deterministically."""
+  if is_unit_profile(profile):
+    # a pair with a class a ring refuses goes round the profiles without one, the others round all
+    names = [p["name"] for p in UNIT_PROFILES]
+    free = [p["name"] for p in UNIT_PROFILES if not p["ring"]]
+    out, at = [], [0, 0]
+    for pair in required_unit_pairs():
+      refused = any(c in RING_REFUSED for c in pair)
+      pool = free if refused else names
+      if pool[at[refused] % len(pool)] == profile["name"]:
+        out.append(pair)
+      at[refused] += 1
+    return out
   i = [p["name"] for p in STATE_PROFILES].index(profile["name"])
   return required_pairs()[i::len(STATE_PROFILES)]
 
 
-def _attempt_states(rng, profile, g):
-  """A program over STATE_CLASSES; None if this draw misses a class, a pair or the host run."""
-  gen = _Gen(rng, profile, g, STATE_MAX_OPS, STATE_MAX_WORLD_STEPS)
+def _attempt_states(rng, profile, g, min_ops=STATE_MIN_OPS, max_ops=STATE_MAX_OPS, steps=STATE_MAX_WORLD_STEPS):
+  """A program over the profile's classes (STATE_CLASSES, or the unit programs'); None if this draw
+  misses a class, a pair or the host run."""
+  gen = _Gen(rng, profile, g, max_ops, steps)
   todo = set(assigned_pairs(profile))
   classes = profile["classes"]
-  while len(gen.ops) < STATE_MAX_OPS:
-    seen = {op["op"] for op in gen.ops}
-    if len(gen.ops) >= STATE_MIN_OPS and not todo and seen == set(classes) and gen.host_run_done:
+  refused = []
+  if gen.listed_first:   # a ring refuses a list: one listed call, which must raise and change nothing
+    worlds, bad = gen._list()
+    refused = [dict(op="step_listed", worlds=worlds, bad=bad, refused=True,
+                    actions=gen.ids((len(worlds), g["P"])))]
+    gen.ops += refused
+  while len(gen.ops) < max_ops:
+    seen = {op["op"] for op in gen.ops[len(refused) + 1:]} | {"reset_all"}
+    if len(gen.ops) >= min_ops and not todo and seen == set(classes) and gen.host_run_done:
       break
     allowed = [c for c in classes if not gen.blocked(c)]
     prev = gen.ops[-1]["op"]
+    unit = is_unit_profile(profile)
+    if unit:
+      # the statistics stay registered over the last part of a program, so that its totals hold
+      # finished episodes at the end; a registration of either kind lives a few ops at least
+      at = len(gen.ops)
+      allowed = [c for c in allowed if (prev, c) in todo or not (
+          (c == "stats_clear" and (at >= UNIT_LAST_STATS_CLEAR or at - gen.set_at["stats"] < UNIT_STATS_LIFE)) or
+          (c == "stats_set" and at > UNIT_LAST_STATS_SET) or
+          (c == "starts_clear" and at - gen.set_at["starts"] < UNIT_STARTS_LIFE))]
     closing = [c for c in allowed if (prev, c) in todo]      # an owed pair that this draw completes
     opening = [c for c in allowed if any(a == c for a, _ in todo)]
     missing = [c for c in allowed if c not in seen]
-    if closing:
+    skipping = [c for c in allowed if c in ("step_active", "many_active", "many_until") + LISTED_CLASSES]
+    favoured = [c for c in allowed if c in UNIT_MUTATING + UNIT_READ_ONLY]
+    if unit and len(gen.ops) >= UNIT_LAST_STATS_SET and not gen.stats_live and prev != "stats_set":
+      c = "stats_set"
+    elif closing:
       c = str(rng.choice(closing))
+    elif unit and prev == "restore" and skipping and gen.units_live and rng.random() < 0.6:
+      c = str(rng.choice(skipping))   # (a restore, then a step that skips worlds, a unit registered)
+    elif unit and favoured and rng.random() < 0.3:
+      c = str(rng.choice(favoured))
     elif opening and rng.random() < 0.6:
       c = str(rng.choice(opening))
     elif missing and rng.random() < 0.5:
@@ -473,17 +709,19 @@ def _attempt_states(rng, profile, g):
       c = str(rng.choice(allowed))
     before = len(gen.ops)
     gen.draw(c)
+    if c in ("stats_set", "starts_set"):
+      gen.set_at[c.split("_")[0]] = before
     todo.discard((prev, c))
     for a, b in zip(gen.ops[before:-1], gen.ops[before + 1:]):   # (a run of host steps)
       todo.discard((a["op"], b["op"]))
-  seen = {op["op"] for op in gen.ops}
+  seen = {op["op"] for op in gen.ops if not op.get("refused")}
   if todo or seen != set(classes) or not gen.host_run_done:
     return None
   return gen.ops
 
 
 def world_steps(program):
-  return sum(op.get("K", 1) for op in program if op["op"] in ALL_STEP_CLASSES)
+  return sum(op.get("K", 1) for op in program if op["op"] in UNIT_STEP_CLASSES and not op.get("refused"))
 
 
 def longest_host_run(program):
@@ -501,8 +739,12 @@ def make_program(seed, profile):
   states = set(profile["classes"]) != set(OP_CLASSES)
   for attempt in range(1000):
     rng = np.random.default_rng([int(seed), zlib.crc32(profile["name"].encode()), attempt])
-    ops = _attempt_states(rng, profile, g) if states else _attempt(rng, profile, g)
-    if ops is not None and {op["op"] for op in ops} == set(profile["classes"]) and longest_host_run(ops) >= HOST_RUN:
+    if is_unit_profile(profile):
+      ops = _attempt_states(rng, profile, g, UNIT_MIN_OPS, UNIT_MAX_OPS, UNIT_MAX_WORLD_STEPS)
+    else:
+      ops = _attempt_states(rng, profile, g) if states else _attempt(rng, profile, g)
+    held = set() if ops is None else {op["op"] for op in ops if not op.get("refused")}
+    if ops is not None and held == set(profile["classes"]) and longest_host_run(ops) >= HOST_RUN:
       prog = Program(ops)
       prog.seed, prog.profile = int(seed), profile
       return prog
@@ -647,6 +889,10 @@ class _Side:
     self.read = None       # what the last read-only op returned
     self.reg = None        # the registration: {"bank", "fresh"}
     self.start_rows = None
+    self.stats = None      # the statistics registration: the engine's EpisodeStats (the model's Model)
+    self.hstats = None     # the twin's: {"columns", "pairs", "arrays"}, folded on the host
+    self.units = {}        # the registered view units: name -> {"out", "wide", "lo", "params"}
+    self.raised = None     # what a refused op raised
     n = eng.N
     if self.real and not twin:
       import torch
@@ -667,8 +913,23 @@ class _Side:
     raw = self.eng.save_worlds()[:, lay.grid_pad + off:lay.grid_pad + off + elem * count].cpu().numpy()
     return np.ascontiguousarray(raw).view({1: np.uint8, 4: np.int32, 8: np.uint64}[elem])
 
+  def _twin_fold(self, ran=None):
+    """The twin registers no statistics: it reads what its submission left on the host and folds it
+    through the library's host form (`ran`: bool [N], the worlds that ran; None: all)."""
+    if self.hstats is None:
+      return
+    eng, h = self.eng, self.hstats
+    ran = np.ones(eng.N, bool) if ran is None else np.asarray(ran) != 0
+    events = eng.observe_host(E.OBS_EVENTS)[None] if h["columns"] or h["pairs"] else None
+    E.episode_stats_host(h["arrays"], eng.observe_host(E.OBS_STEP_TYPE)[None], eng.observe_host(E.OBS_REWARD)[None],
+                         events, h["columns"], h["pairs"], active=ran[None].astype(np.uint8))
+
   def _twin_step(self, block, m, fields):
     """One step of the twin: `block` [N, P(, A)] on the host, `m` bool [N] or None."""
+    self._twin_one(block, m, fields)
+    self._twin_fold(m)
+
+  def _twin_one(self, block, m, fields):
     eng = self.eng
     done = self._tail("done")[:, 0] != 0 if self.reg else None
     if m is None:
@@ -764,31 +1025,246 @@ class _Side:
         kw["stopped"] = self.stopped
     if c == "step_many_states":
       kw.update(states=True, hashes=True)
+    fold = self.twin and self.hstats is not None   # (a ring profile: the K rows, folded on the host)
+    if fold:
+      kw["events"] = True
     res = dict(eng.step_many(acts, **kw))
     if c == "many_until" and op["use_stopped"] and res["stopped"] is not self.stopped:
       raise Mismatch("step_many did not hand back the caller's `stopped`")
+    if fold:
+      h = self.hstats
+      E.episode_stats_host(h["arrays"], _host(res["step_type"]), _host(res["reward"]),
+                           _host(res["events"]) if h["columns"] or h["pairs"] else None, h["columns"], h["pairs"])
+      if op.get("observations") is None:
+        del res["events"]
     return res
 
+  # ---- the unit classes
+  def _filled(self, shape, dtype):
+    """A tensor of `shape` whose every byte is FILL."""
+    if self.real:
+      import torch
+      size = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+      return torch.full((size,), FILL, dtype=torch.uint8, device=self.eng.device).view(dtype).view(tuple(shape))
+    return np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, FILL, np.uint8).view(dtype).reshape(shape)
+
+  def _listed(self, op):
+    """A listed op as the engine's own call, every per-call tensor filled beforehand: a bad entry's
+    elements must keep their bytes."""
+    eng, many = self.eng, op["op"] == "many_listed"
+    M = len(op["worlds"])
+    worlds = self.dev(op["worlds"])
+    if not many:
+      eng.step(self.dev(op["actions"]), worlds=worlds)
+      return None
+    acts = self.dev(op["actions"])
+    if op["form"] == "slice":
+      acts = acts[:, op["lo"]:op["lo"] + M]
+    K = op["K"]
+    kw = dict(fields=op["fields"], repeat=K if op["form"] == "repeat" else None, worlds=worlds)
+    keys = ["reward", "collective_reward", "step_type", "discount"]
+    if op["observations"] is not None:
+      kw.update(events=True, observations=op["observations"])
+      keys += ["events"] + list(op["observations"])
+    if op["active"] is not None:
+      kw["active"] = self.dev(op["active"])
+    out = {}
+    for key in keys:
+      if self.real:
+        _, per_world, dtype = E.step_row(eng.shapes, key)
+      else:
+        shape, dtype = eng.shapes[E.STEP_MANY_NAMES.get(key, key)]
+        per_world = tuple(shape[1:])
+      out[key] = self._filled((K, M) + tuple(per_world), dtype)
+    if op["until"] is not None:
+      kw.update(until=op["until"], gamma=op["gamma"], stopped=self.stopped, returns=op["returns"])
+      import torch
+      out["ran"] = self._filled((M,), torch.int32 if self.real else np.int32)
+      if op["returns"]:
+        out["returns"] = self._filled((M, eng.P), torch.float64 if self.real else np.float64)
+    res = dict(eng.step_many(acts, out=out, **kw))
+    if op["until"] is not None and res["stopped"] is not self.stopped:
+      raise Mismatch("step_many(worlds=) did not hand back the caller's `stopped`")
+    return {k: np.array(_host(v)) for k, v in res.items()}
+
+  def _twin_listed(self, op):
+    """The twin's form of a listed op: the masked request over all N worlds of the defining identity,
+    as the host loop of masked single steps; ran / returns gathered by entry."""
+    n, M = self.eng.N, len(op["worlds"])
+    many = op["op"] == "many_listed"
+    K = op["K"] if many else 1
+    blocks = op_blocks(op, M) if many else [op["actions"]]
+    act = None if not many or op["active"] is None else np.broadcast_to(op["active"] != 0, (K, M))
+    full = np.zeros((K, n) + blocks[0].shape[1:], np.int32)
+    mask = np.zeros((K, n), np.uint8)
+    owners, seen = [], set()
+    for i, w in enumerate(op["worlds"].tolist()):
+      if 0 <= w < n and w not in seen:
+        seen.add(w)
+        owners.append((i, w))
+        full[:, w] = np.stack([b[i] for b in blocks])
+        mask[:, w] = 1 if act is None else act[:, i]
+    until = op.get("until")
+    res = self._twin_loop(dict(op="many_until" if until is not None else "many_active", K=K, form="plain",
+                               fields=bool(op.get("fields")), actions=full, lo=0, mask=mask, mask_form="kn", mlo=0,
+                               until=until, returns=op.get("returns", False), gamma=op.get("gamma", 1.0),
+                               use_stopped=True))
+    out = {}
+    for key, value in res.items():
+      if key == "stopped":
+        out[key] = value
+        continue
+      g = np.full((M,) + value.shape[1:], 0, value.dtype)
+      g.view(np.uint8)[...] = FILL
+      for i, w in owners:
+        g[i] = value[w]
+      out[key] = g
+    return out
+
+  def _unit_tensor(self, shape, dtype, lo=0):
+    """(out, wide): a zeroed destination of a registration that starts `lo` bytes into a wider
+    buffer of FILL bytes (uint8 only), on the engine's device; the model's is a numpy array."""
+    if not self.real:
+      return np.zeros(shape, dtype), None
+    import torch
+    tdtype = {np.int32: torch.int32, np.int64: torch.int64, np.uint8: torch.uint8}[dtype]
+    if dtype is not np.uint8:
+      return torch.zeros(tuple(shape), dtype=tdtype, device=self.eng.device), None
+    size = int(np.prod(shape))
+    wide = torch.full((size + 48,), FILL, dtype=torch.uint8, device=self.eng.device)
+    out = wide[lo:lo + size].view(tuple(shape))
+    out.zero_()
+    return out, wide
+
+  def _units_set(self, op, ring):
+    eng = self.eng
+    lead = (ring,) if ring else ()
+    for name in op["units"]:
+      params = dict(op.get(name, {}))
+      lo = params.pop("offset", 0)
+      if name == "ego":
+        out, wide = self._unit_tensor(lead + tuple(eng.ego_layer_shape), np.int32)
+        eng.bind_ego_layer_ring(out) if ring else eng.bind_ego_layer(out)
+      elif name == "hash":
+        out, wide = self._unit_tensor(lead + (eng.N, eng.P), np.int64)
+        eng.bind_view_hash(out, **params)
+      else:
+        table = params["classes"]
+        C = int(table.max()) + 1 if params["num_classes"] is None else params["num_classes"]
+        out, wide = self._unit_tensor(lead + tuple(eng.ego_planes_shape(C, params["facing"])), np.uint8, lo)
+        eng.bind_ego_planes(out, **params)
+      self.units[name] = dict(out=out, wide=wide, lo=lo, params=params)
+
+  def _units_clear(self, name):
+    eng = self.eng
+    {"ego": eng.bind_ego_layer, "hash": eng.bind_view_hash, "planes": eng.bind_ego_planes}[name](None)
+    del self.units[name]
+
+  def unit_value(self, name):
+    """The registered tensor of unit `name` on the host; raises if a guard byte around it changed."""
+    u = self.units[name]
+    if u["wide"] is not None:
+      guard = u["wide"].cpu().numpy()
+      size = guard.size - 48
+      if (guard[:u["lo"]] != FILL).any() or (guard[u["lo"] + size:] != FILL).any():
+        raise Mismatch(f"registered {name}: a guard byte around the destination (offset {u['lo']}) was written")
+    return np.array(_host(u["out"]))
+
+  def _unit_rows(self, op):
+    eng, unit = self.eng, op["unit"]
+    bank = None if op["bank"] < 0 else self.banks[op["bank"]]
+    kw = dict(bank=bank, rows=self._ints(op["rows"]), players=None if op["players"] is None else self._ints(op["players"]))
+    if unit == "ego":
+      return np.array(_host(eng.observe_ego_layer(**kw)))
+    if unit == "hash":
+      return np.array(_host(eng.hash_views(**kw, **op["params"])))
+    params = op["params"]
+    if not self.real:
+      return np.array(eng.observe_ego_planes(params["classes"], **kw, layers=params["layers"], facing=params["facing"],
+                                             num_classes=params["num_classes"]))
+    # the planes' `out` may start on any byte: inside a wider buffer, with guard bytes around it
+    import torch
+    shape = eng.ego_planes_shape(params["num_classes"], params["facing"])
+    shape = (len(op["rows"]),) + tuple(shape[1:] if op["players"] is None else shape[2:])
+    size, lo = int(np.prod(shape)), op["offset"]
+    wide = torch.full((size + 48,), FILL, dtype=torch.uint8, device=eng.device)
+    eng.observe_ego_planes(params["classes"], **kw, layers=params["layers"], facing=params["facing"],
+                           num_classes=params["num_classes"], out=wide[lo:lo + size].view(shape))
+    guard = wide.cpu().numpy()
+    if (guard[:lo] != FILL).any() or (guard[lo + size:] != FILL).any():
+      raise Mismatch(f"observe_ego_planes: a guard byte around `out` (offset {lo}) was written")
+    return guard[lo:lo + size].reshape(shape).copy()
+
   def apply(self, op, ring, views=True):
+    """Applies `op`.  A refused op (a list handed to an engine with a ring) must raise, which is kept
+    in `raised`; the twin, which would run the masked form, leaves it out."""
+    self.raised = None
+    if not op.get("refused"):
+      return self._apply(op, ring, views)
+    self.rows = self.read = None
+    if not self.twin:
+      try:
+        self._apply(op, ring, views)
+      except (ValueError, E.EngineError) as e:
+        self.raised = e
+
+  def _apply(self, op, ring, views=True):
     eng, c = self.eng, op["op"]
     self.rows = self.read = None
-    looped = self.twin and (self.reg is not None or c in NEW_STEP_CLASSES)
+    # (a twin that folds statistics on the host runs single steps, but for a ring, which a K-step
+    # call turns once: there it folds the K rows of its own step_many)
+    looped = self.twin and (self.reg is not None or c in NEW_STEP_CLASSES or (self.hstats is not None and not ring))
     if c == "reset_all":
       eng.reset()
+      if self.twin:
+        self._twin_fold()
     elif c == "masked_reset":
       eng.reset(None, op["mask"])
+      if self.twin:
+        self._twin_fold(op["mask"])
     elif c == "masked_reseed":
       eng.reset(op["seeds"], op["mask"])
+      if self.twin:
+        self._twin_fold(op["mask"])
+    elif c in LISTED_CLASSES:
+      self.rows = self._twin_listed(op) if self.twin else self._listed(op)
+      if not self.rows:
+        self.rows = None
+    elif c == "stats_set":
+      if self.twin:
+        cols = tuple(eng.event_columns()) if isinstance(op["columns"], str) else tuple(op["columns"])
+        self.hstats = dict(columns=cols, pairs=tuple(op["pairs"]),
+                           arrays=E.numpy_episode_stats(eng.N, eng.P, len(cols), len(op["pairs"])))
+      else:
+        self.stats = eng.set_episode_stats(op["columns"], op["pairs"])
+    elif c == "stats_clear":
+      self.stats = self.hstats = None
+      if not self.twin:
+        eng.clear_episode_stats()
+    elif c == "units_set":
+      if not self.twin:
+        self._units_set(op, ring)
+    elif c == "units_clear":
+      if not self.twin:
+        self._units_clear(op["unit"])
+    elif c == "unit_rows":
+      self.read = self._unit_rows(op)
     elif c in ("step_dev", "step_host") and looped:
       self._twin_step(op["actions"], None, False)
     elif c == "step_fields" and looped:
       self._twin_step(op["fields"], None, True)
     elif c == "step_dev":
       eng.step(self.dev(op["actions"]))
+      if self.twin:
+        self._twin_fold()
     elif c == "step_host":
       eng.step(op["actions"])
+      if self.twin:
+        self._twin_fold()
     elif c == "step_fields":
       eng.step_fields(op["fields"] if op["host"] else self.dev(op["fields"]))
+      if self.twin:
+        self._twin_fold()
     elif c == "step_active" and looped:
       self._twin_step(op["actions"], op["mask"] != 0, False)
     elif c == "step_active":
@@ -823,6 +1299,8 @@ class _Side:
       self.banks.append(eng.save_worlds(op["worlds"]))
     elif c == "load":
       eng.load_worlds(self.banks[op["bank"]], op["src"])
+      if self.twin:
+        self._twin_fold(op["src"] >= 0)
     elif c == "snapshot":
       self.snap = eng.snapshot()
     elif c == "restore":
@@ -883,10 +1361,20 @@ class _Side:
     return verdicts, _host(eng.check_states(clone)), clone.cpu().numpy()
 
 
-def _check_faults(eng, where):
-  words = np.asarray(eng.fault_words()[:6])
-  if words.any():
-    raise FaultStop(f"{where}: fault words {words.tolist()}; nothing more is launched")
+LISTED_FAULTS = (9, 10)   # word 11 of a bad entry of a list: not a world / repeats an earlier entry's
+
+
+def _check_faults(eng, where, listed=False):
+  """Stops the run on any fault word (the first 18, and 32..35 of a skipped registered start) before
+  anything more is launched.  `listed`: a list with bad entries has been handed over, whose report
+  leaves words 9..11 (position + 1, value, what): those alone may be set, with `what` one of
+  LISTED_FAULTS."""
+  words = np.asarray(eng.fault_words())
+  seen = np.concatenate([words[:18], words[32:36]]).astype(np.int64)
+  if listed and (words[11] & 255) in LISTED_FAULTS:
+    seen[9:12] = 0
+  if seen.any():
+    raise FaultStop(f"{where}: fault words {words[:18].tolist()} {words[32:36].tolist()}; nothing more is launched")
 
 
 def _bits(x):
@@ -895,7 +1383,8 @@ def _bits(x):
   return x.view(np.int64) if x.dtype == np.float64 else x
 
 
-def compare_with_model(eng, model, rows, model_rows, fail, worlds=None, row_worlds=None, record_worlds=None):
+def compare_with_model(eng, model, rows, model_rows, fail, worlds=None, row_worlds=None, record_worlds=None,
+                       stopped_worlds=None, listed=False):
   """Everything the model speaks about, engine against model; `fail(kind, text)` raises.
   `worlds`: the worlds the model speaks for (None: all) — the reported world is an index into it;
   `row_worlds`: those it spoke for through the whole call, whose per-step rows compare;
@@ -919,8 +1408,9 @@ def compare_with_model(eng, model, rows, model_rows, fail, worlds=None, row_worl
   for key in rows or ():
     if key in skip:
       continue
-    if key in ("stopped", "ran", "returns"):   # [N] or [N, P]
-      d = first_difference(key, _bits(of(rows[key], 0, row_worlds)), _bits(of(model_rows[key], 0, row_worlds)))
+    if key in ("stopped", "ran", "returns"):   # [N] or [N, P] (a list: `stopped` by world, the others by entry)
+      which = stopped_worlds if listed and key == "stopped" else row_worlds   # (a list: `stopped` is by world)
+      d = first_difference(key, _bits(of(rows[key], 0, which)), _bits(of(model_rows[key], 0, which)))
     else:
       d = first_difference(key, of(rows[key], 1, row_worlds), of(model_rows[key], 1, row_worlds), leading=("step", "world"))
     if d:
@@ -987,6 +1477,118 @@ def compare_reads(op, side, model_side, twin_side, fail):
     host = E.check_states_host(profile_pack(side.profile), clone, num_players=side.profile["num_players"])
     if not np.array_equal(broken, host) or not broken.any():
       fail("check", f"a row with {op['field']} broken: device verdict {broken.tolist()}, host {host.tolist()}")
+
+
+SUBMISSIONS = ("reset_all", "masked_reset", "masked_reseed", "load") + UNIT_STEP_CLASSES
+
+
+def _stats_bytes(stats):
+  """{name: numpy array} of an EpisodeStats, a statistics dict or the model's Model."""
+  import episode_stats_model
+  arrays = stats.arrays() if callable(getattr(stats, "arrays", None)) else getattr(stats, "arrays", stats)
+  return {k: np.array(v) for k, v in episode_stats_model.flatten(arrays).items()}
+
+
+def compare_stats(op, side, model_side, twin_side, before, fail):
+  """The statistics tensors, bit for bit: against the model's for the worlds it has spoken for since
+  the registration, against the twin's host fold (`episode_stats_host` of what the twin's steps left)
+  for every world, and unchanged by an op that is no submission."""
+  if side.stats is None:
+    return
+  got = _stats_bytes(side.stats)
+  model = model_side.eng
+  keep = np.nonzero(model.stats_exact)[0]
+  want = _stats_bytes(model.stats)
+  if got.keys() != want.keys():
+    fail("statistics", f"tensors {sorted(got)} != {sorted(want)}")
+  for key in want:
+    if got[key].dtype != want[key].dtype:
+      fail(f"statistics {key}", f"dtype {got[key].dtype} != {want[key].dtype}")
+    d = first_difference(key, _bits(got[key][keep]), _bits(want[key][keep]))
+    if d:
+      fail(f"statistics {key}", d + f" (of worlds {keep.tolist()})")
+  if twin_side is not None and twin_side.hstats is not None:
+    for key, want in _stats_bytes(twin_side.hstats["arrays"]).items():
+      d = first_difference(key, _bits(got[key]), _bits(want))
+      if d:
+        fail(f"twin: statistics {key} against episode_stats_host of the twin's steps", d)
+  if before is not None and (op["op"] not in SUBMISSIONS or op.get("refused")) and op["op"] != "stats_set":
+    for key in got:
+      if got[key].tobytes() != before[key].tobytes():
+        fail(f"statistics {key}", "changed by an op that is no submission")
+
+
+def _unit_host(side, name, params, rows, players=None, which=None):
+  """Unit `name` by the library's host form on host rows (uint8 [R, S])."""
+  pack, np_ = profile_pack(side.profile), side.profile["num_players"]
+  fp = side.eng.state_fingerprint
+  if name == "ego":
+    return E.ego_layer_host(pack, rows, players, which=which, num_players=np_, fingerprint=fp)
+  if name == "hash":
+    return E.hash_views_host(pack, rows, players, which=which, num_players=np_, fingerprint=fp, **params)
+  return E.ego_planes_host(pack, rows, params["classes"], players, which=which, layers=params["layers"],
+                           facing=params["facing"], num_classes=params["num_classes"], num_players=np_, fingerprint=fp)
+
+
+def compare_units(op, side, model_side, before, fail):
+  """Every registered tensor: after a submission the unit's function of ALL N records as they are
+  now, in a ring in the slot the submission wrote with the other slots unchanged — by the model for
+  the worlds it speaks for, by the library's host form on the engine's own save_worlds() for all —
+  and after any other op unchanged."""
+  if not side.units:
+    return
+  eng, model = side.eng, model_side.eng
+  submitted = op["op"] in SUBMISSIONS and not op.get("refused")
+  rows = eng.save_worlds().cpu().numpy() if side.real and submitted else None
+  for name, u in side.units.items():
+    got = side.unit_value(name)
+    fresh = op["op"] == "units_set" and name in op["units"]   # (a new tensor, zeroed)
+    if name in before and not submitted and not fresh and got.tobytes() != before[name].tobytes():
+      fail(f"registered {name}", "changed by an op that is no submission")
+    if fresh and got.any():
+      fail(f"registered {name}", "written by its registration")
+    ring = side.profile["ring"]
+    want = model_side.unit_value(name)
+    speaks = model.unit_speaks(name) if hasattr(model, "unit_speaks") else np.ones(got.shape[:2 if ring else 1], bool)
+    lead = ("slot", "world") if ring else ("world",)
+    g, w = got[speaks], want[speaks]
+    if not np.array_equal(g, w):
+      at = np.argwhere(speaks)[np.argwhere((g != w).reshape(len(g), -1).any(1))[0][0]]
+      fail(f"registered {name} (last slot {eng.ring['last']})",
+           f"{', '.join(f'{n} {int(v)}' for n, v in zip(lead, at))} differs from the model's")
+    if rows is not None:
+      host = _unit_host(side, name, u["params"], rows)
+      last = got[eng.ring["last"]] if ring else got
+      d = first_difference(name, last, host)
+      if d:
+        fail(f"registered {name} against the host form of save_worlds()", d)
+      if ring and name in before and not fresh:
+        others = [t for t in range(ring) if t != eng.ring["last"]]
+        if got[others].tobytes() != before[name][others].tobytes():
+          fail(f"registered {name}", f"a slot other than {eng.ring['last']} was written")
+
+
+def compare_unit_rows(op, side, model_side, twin_side, fail):
+  """A unit_rows read: against the model's for the rows it speaks for, against the library's host
+  form of the same rows, and against the twin's."""
+  model, name = model_side.eng, op["unit"]
+  if op["bank"] < 0:
+    keep = np.asarray(model.exact)[op["rows"]] if hasattr(model, "exact") else np.ones(len(op["rows"]), bool)
+  else:
+    keep = np.array([model_side.banks[op["bank"]][int(i)].get("exact", True) for i in op["rows"]])
+  d = first_difference(name, side.read[keep], model_side.read[keep], leading=("row",))
+  if d:
+    fail(f"unit_rows {name}", d)
+  if side.real:
+    bank = side.eng.save_worlds() if op["bank"] < 0 else side.banks[op["bank"]]
+    host = _unit_host(side, name, op.get("params", {}), bank.cpu().numpy(), op["players"], which=op["rows"])
+    d = first_difference(name, side.read, host, leading=("row",))
+    if d:
+      fail(f"unit_rows {name} against the host form", d)
+  if twin_side is not None:
+    d = first_difference(name, side.read, twin_side.read, leading=("row",))
+    if d:
+      fail(f"twin: unit_rows {name}", d)
 
 
 def compare_views_with_model(eng, model, fail, kinds=engine_model.VIEW_KINDS, worlds=None):
@@ -1064,6 +1666,12 @@ def _cover(cover, op, model_side, taken_before):
       cover["a row with a dead avatar among the drawn rows"] += 1
 
 
+def _final_cover(cover, model):
+  if model.stats is not None:
+    cover["non-zero total.counts at the end"] += int(model.stats.total["counts"].any())
+    cover["non-zero total.pairs at the end"] += int(model.stats.total["pairs"].any())
+
+
 def run_program(program, engine, model, twin=None, stop_after=None, cover=None):
   """Applies each op of `program` (its first `stop_after`, if given) to `engine`, `model` and
   `twin`, comparing after every op; raises Mismatch / FaultStop naming seed, profile, op and kind.
@@ -1079,6 +1687,7 @@ def run_program(program, engine, model, twin=None, stop_after=None, cover=None):
   cover = collections.Counter() if cover is None else cover
   locate = None
   ran = 0
+  bad_lists = False
   for i, op in enumerate(program[:stop_after]):
     where = f"program seed {program.seed}, profile {profile['name']}, op {i}: {short_form(op)}"
 
@@ -1088,13 +1697,31 @@ def run_program(program, engine, model, twin=None, stop_after=None, cover=None):
     op = resolve(op, model_side)
     taken_before = model.cover["registered start"] if hasattr(model, "cover") else 0
     exact_before = model.speaks.copy() if hasattr(model, "speaks") else None
+    units_before = {name: side.unit_value(name) for name in side.units}
+    stats_before = None if side.stats is None else _stats_bytes(side.stats)
     for k, s in enumerate(sides):
       s.apply(op, ring, views=k < 2)   # (the twin binds no view)
     if op["op"] == "step_many_states":
       model_side.states_banks[len(model_side.banks) - 1] = True
+    if op.get("refused"):   # a list handed to an engine with a ring: refused, and nothing changes
+      for s in sides[:2]:
+        if s.raised is None or "ring" not in str(s.raised):
+          fail("a list under a ring", f"not refused ({s.raised!r})")
+    if op.get("bad") and not op.get("refused") and side.real:
+      # bad entries: the next synchronising call raises ValueError once, naming one of them
+      bad_lists = True
+      try:
+        engine.dump()
+      except ValueError as e:
+        named = [i for i in range(len(op["worlds"])) if f"worlds[{i}] = {int(op['worlds'][i])} " in str(e)]
+        owned = {i for i, _ in engine_model.ModelEngine._owners(engine, op["worlds"])}
+        if "MpStepListed" not in str(e) or not named or named[0] in owned:
+          fail("bad entries", f"the error names none of them: {e}")
+      else:
+        fail("bad entries", "the next synchronising call raised nothing")
     # (dump synchronises; a fault word ends the run before anything else is launched)
     engine.dump()
-    _check_faults(engine, where)
+    _check_faults(engine, where, bad_lists)
     if twin is not None:
       twin.dump()
       _check_faults(twin, where + " (twin)")
@@ -1104,7 +1731,17 @@ def run_program(program, engine, model, twin=None, stop_after=None, cover=None):
     # restarted from a row — but its rows of the steps before that are not the model's)
     both = None if exact is None or (exact & exact_before).all() else np.nonzero(exact & exact_before)[0]
     records = None if exact is None or model.exact.all() else np.nonzero(model.exact)[0]
-    compare_with_model(engine, model, side.rows, model_side.rows, fail, worlds, both, records)
+    if op["op"] in LISTED_CLASSES and both is not None:
+      # per-call tensors by ENTRY: those whose world the model spoke for, and the bad ones
+      entries = np.array([i for i, w in enumerate(op["worlds"].tolist()) if not 0 <= w < engine.N or w in set(both.tolist())],
+                         np.int64)
+      compare_with_model(engine, model, side.rows, model_side.rows, fail, worlds, entries, records, stopped_worlds=both, listed=True)
+    else:
+      compare_with_model(engine, model, side.rows, model_side.rows, fail, worlds, both, records)
+    if hasattr(model, "stats_exact"):
+      model.stats_exact &= model.speaks
+    compare_units(op, side, model_side, units_before, fail)
+    compare_stats(op, side, model_side, twin_side, stats_before, fail)
     if both is not None:
       # a `stopped` byte decided while the model did not speak for its world is the engine's to say
       # (the twin checks it): the model's side takes it over, so that the world compares again once
@@ -1118,21 +1755,24 @@ def run_program(program, engine, model, twin=None, stop_after=None, cover=None):
       compare_views_with_model(engine, model, fail, worlds=records)
     if op["op"] in READ_ONLY:
       compare_reads(op, side, model_side, twin_side, fail)
+    if op["op"] == "unit_rows":
+      compare_unit_rows(op, side, model_side, twin_side, fail)
     if hasattr(model, "cover"):
       _cover(cover, op, model_side, taken_before)
     if twin is not None:
       if locate is None:   # (world 0 still has its first seed: it locates the counters' bytes)
         locate = engine.save_worlds().clone()
       compare_with_twin(engine, twin, locate, fail)
-      if op["op"] in NEW_STEP_CLASSES:
+      if op["op"] in NEW_STEP_CLASSES or op["op"] == "many_listed":
         compare_many_with_twin(op, side, twin_side, locate, fail)
       if not np.array_equal(_host(side.stopped), twin_side.stopped):
         fail("twin: the caller's `stopped`", f"{_host(side.stopped).tolist()} != {twin_side.stopped.tolist()}")
     ran += 1
   if ran:
     compare_views_with_model(engine, model, fail, worlds=records)
-    _check_faults(engine, "end of program")
+    _check_faults(engine, "end of program", bad_lists)
   if hasattr(model, "cover"):
+    _final_cover(cover, model)
     cover.update(model.cover)
     cover["inexact worlds at the end"] += int((~model.exact).sum())
   return ran
@@ -1154,6 +1794,7 @@ def program_cover(program):
       if op["op"] == "step_many_states":
         side.states_banks[len(side.banks) - 1] = True
       _cover(cover, op, side, taken_before)
+    _final_cover(cover, model)
     cover.update(model.cover)
     cover["inexact worlds at the end"] += int((~model.exact).sum())
   finally:
@@ -1179,6 +1820,29 @@ REWARD_CONDITIONS = (
     "returns with gamma != 1 paid after the first step the world ran",
     "non-zero reward on the step that leaves LAST",
 )
+
+
+# what the model's runs of a level's two unit programs must contain
+UNIT_COVER_CONDITIONS = (
+    "a listed call with bad entries, statistics registered",
+    "a listed call names a world paused on LAST",
+    "a listed until= call meets a stopped byte set under a different list",
+    "a listed call with a registered start inside step k >= 1",
+    "an episode finishes after an open one was cut",
+    "an episode finishes inside step k >= 1 of a K-step call, statistics registered",
+    "restore while statistics are registered",
+    "restore changed a record, then a step skipped that world, a unit registered",
+    "a registered view at orientation 0",
+    "a registered view at orientation 1",
+    "a registered view at orientation 2",
+    "a registered view at orientation 3",
+    "units_clear followed by submissions of every slot",
+    "stats_set over a live registration",
+    "non-zero total.counts at the end",
+    "non-zero total.pairs at the end",
+)
+UNIT_DEAD_VIEWER = "a registered view of a dead viewer"
+UNIT_OFF_THE_MAP = "a registered window cell off the map"
 
 
 # ------------------------------------------------------------------------- engines of a profile

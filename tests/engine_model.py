@@ -29,7 +29,17 @@ What it models, after mp_engine.h:
     its next active step; `stopped` and `rows` are the caller's arrays, read and written in place;
   * a registered start: the level's reset and on top of it what a load of the row writes.
     fresh=True is NOT modelled (the oracle takes no state): `exact` says which worlds the model
-    speaks for.
+    speaks for;
+  * a listed request (worlds=) as MpStepListed's identity: the masked request over all N worlds with
+    the actions scattered by owning entry (the lowest that names a world), every per-call tensor
+    gathered by entry on top of what it held, `stopped` by world;
+  * the episode statistics (MpEpisodeStats): a tests/episode_stats_model.Model fed, per world and per
+    step that ran (a reset's mask, a load's rows, the steps a mask, a stop or a list let run), the
+    STEP_TYPE, REWARD and EVENTS the model says that step left;
+  * the registered view units (EGO_LAYER, view hashes, planes): behind every submission the unit's
+    function of ALL N records, from the oracles' dumps through tests/ego_layer_model.py,
+    view_hash_model.py and ego_planes_model.py, into the tensor or the ring slot of the submission;
+    a restore, being no launch, writes none.
 It says nothing about the kinds under the carry rule that no record holds (AUX0 - AUX4, ZAP_MATRIX,
 INTERACTION_INVENTORIES, INTERACTION_REWARDS, MATRIX_CUMULANTS): the twin engine of
 api_programs.run_program covers those."""
@@ -41,7 +51,11 @@ import numpy as np
 from meltingpot_amd import engine as E
 from oracle import oracle as oracle_lib
 from oracle_engine import OracleBatchEngine
+import ego_layer_model
+import ego_planes_model
+import episode_stats_model
 import util
+import view_hash_model
 
 TRANSITION_KINDS = (E.OBS_REWARD, E.OBS_COLLECTIVE_REWARD, E.OBS_STEP_TYPE, E.OBS_DISCOUNT, E.OBS_EVENTS)
 RECORD_SCALARS = (E.OBS_POSITION, E.OBS_ORIENTATION, E.OBS_READY_TO_SHOOT, E.OBS_INVENTORY)
@@ -124,6 +138,19 @@ class ModelEngine:
     self.cover = collections.Counter()      # what a run contained (tests/test_api_programs_cpu.py)
     self._step_starts = []                  # (world, row index or -1) of the restarts of this step
     self._replays = {}   # row_key -> the oracle its log was replayed into
+    # episode statistics (MpEpisodeStats): a tests/episode_stats_model.Model while registered, and the
+    # worlds the model has spoken for ever since the registration
+    self.stats = None
+    self.stats_exact = np.zeros(self.N, bool)
+    self._credit = None      # a listed call: {world: entry} of the owning entries
+    self._stop_list = {}     # world -> the list of the listed call that set its `stopped` byte
+    # world -> what its statistics must hold when the episode begun behind a cut finishes: the cut
+    # one's sums nowhere (see _cut)
+    self._after_cut = {}
+    # registered view units: name ("ego" / "hash" / "planes") -> {"out", "ring", "exact", params}
+    self.units = {}
+    self._since_clear = None   # submissions since the last units_clear
+    self._restored = np.zeros(self.N, bool)   # record changed by a restore, no submission ran it yet
 
   # -- the interface the runner drives on both sides (numpy in, numpy out here)
   def to_device(self, a):
@@ -265,6 +292,198 @@ class ModelEngine:
             target[w] = value[w]
         else:
           target[...] = value
+    self._draw_units()
+    if self._since_clear is not None and self.units:
+      self._since_clear += 1
+      if self._since_clear == max(2, self._slots):
+        self.cover["units_clear followed by submissions of every slot"] += 1
+
+  # -- registered view units: one launch behind every submission, over ALL worlds
+  def _unit_worlds(self):
+    """The worlds a submission's unit launch redraws: all of them, skipped and unlisted included."""
+    return range(self.N)
+
+  def _draw_units(self):
+    if not self.units:
+      return
+    worlds = list(self._unit_worlds())
+    dumps = [self._o[w].dump() for w in worlds]
+    for name, u in self.units.items():
+      value = self._unit_value(name, u, dumps)
+      target = u["out"][self._slot] if u["ring"] else u["out"]
+      exact = u["exact"][self._slot] if u["ring"] else u["exact"]
+      for i, w in enumerate(worlds):
+        target[w] = value[i]
+        exact[w] = self.exact[w]
+    avat = np.stack([d[1] for d in dumps])[:, :self.P]
+    live = avat[:, :, 3] != 0
+    if (~live).any():
+      self.cover["a registered view of a dead viewer"] += 1
+    for o in set(avat[:, :, 2][live].tolist()):
+      self.cover[f"a registered view at orientation {int(o)}"] += 1
+    H, W, _, (vl, vr, vf, vb), torus = ego_layer_model.geometry(self.pack_bytes)
+    # the window's extent on the map's axes, by the viewer's orientation: (left, right, up, down)
+    extent = np.array([(vl, vr, vf, vb), (vb, vf, vl, vr), (vr, vl, vb, vf), (vf, vb, vr, vl)])
+    x, y, e = avat[:, :, 0][live], avat[:, :, 1][live], extent[avat[:, :, 2][live] & 3]
+    if not torus and ((x - e[:, 0] < 0) | (x + e[:, 1] >= W) | (y - e[:, 2] < 0) | (y + e[:, 3] >= H)).any():
+      self.cover["a registered window cell off the map"] += 1
+    skipped = self._restored.copy()
+    if self._touched is not None and self.units:
+      skipped[list(self._touched)] = False
+      if skipped.any():
+        self.cover["restore changed a record, then a step skipped that world, a unit registered"] += 1
+    self._restored[:] = False
+
+  def _unit_value(self, name, u, dumps):
+    """The function of unit `name` of the records `dumps` (oracle dumps): [len(dumps), P, ...]."""
+    P = self.P
+    grid = np.stack([d[0] for d in dumps])
+    avat = np.stack([d[1] for d in dumps])[:, :P]
+    ax, ay, ori, alive = (avat[:, :, i] for i in range(4))
+    if name == "planes":
+      return ego_planes_model.planes(self.pack_bytes, grid, ax, ay, ori, alive, u["classes"], u["num_classes"],
+                                     u["layers"], u["facing"])
+    ego = ego_layer_model.ego_layer(self.pack_bytes, grid, ax, ay, ori, alive)
+    if name == "ego":
+      return ego
+    return view_hash_model.view_hash(ego, u["layers"], u["classes"])
+
+  @property
+  def ego_layer_shape(self):
+    return tuple(self.shapes[E.OBS_LAYER][0])
+
+  def ego_planes_shape(self, num_classes, facing=False):
+    N, P, VH, VW, _ = self.ego_layer_shape
+    return (N, P, int(num_classes) + (4 if facing else 0), VH, VW)
+
+  def _register(self, name, out, base_ndim, **params):
+    if out is None:
+      self.units.pop(name, None)
+      self._since_clear = 0
+      return None
+    ring = out.ndim == base_ndim + 1
+    assert not ring or out.shape[0] == self._slots, "a unit's ring has the engine's slots"
+    if self.units:
+      self.cover["a unit registered beside a live one"] += 1
+    self.units[name] = dict(params, out=out, ring=ring, exact=np.zeros(out.shape[:1 + int(ring)], bool))
+    return out
+
+  def bind_ego_layer(self, out):
+    return self._register("ego", out, 5)
+
+  def bind_ego_layer_ring(self, tensor=None, slots=None):
+    return self._register("ego", tensor, 5)
+
+  def bind_view_hash(self, out, layers=None, classes=None):
+    return self._register("hash", out, 2, layers=layers, classes=classes)
+
+  def bind_ego_planes(self, out, classes=None, layers=None, facing=False, num_classes=None):
+    return self._register("planes", out, 5, classes=classes, layers=layers, facing=facing, num_classes=num_classes)
+
+  def unit_speaks(self, name):
+    """bool [N] ([T, N] of a ring): the elements of the registered tensor the model states — a world
+    it spoke for when the launch that drew the element ran."""
+    return self.units[name]["exact"]
+
+  def _unit_read(self, name, params, bank, rows, players):
+    if bank is None:
+      idx = range(self.N) if rows is None else [int(i) for i in np.asarray(rows)]
+      oracles = [self._o[i] for i in idx]
+    else:
+      count = len(bank) if players is None else len(np.asarray(players))
+      idx = range(count) if rows is None else [int(i) for i in np.asarray(rows)]
+      oracles = [self._replayed(bank[i]) for i in idx]
+    value = self._unit_value(name, params, [o.dump() for o in oracles])
+    return value if players is None else value[np.arange(len(value)), np.asarray(players)]
+
+  def observe_ego_layer(self, bank=None, rows=None, players=None):
+    return self._unit_read("ego", {}, bank, rows, players)
+
+  def hash_views(self, bank=None, rows=None, players=None, layers=None, classes=None):
+    return self._unit_read("hash", dict(layers=layers, classes=classes), bank, rows, players)
+
+  def observe_ego_planes(self, classes, bank=None, rows=None, players=None, layers=None, facing=False, num_classes=None):
+    return self._unit_read("planes", dict(classes=classes, layers=layers, facing=facing, num_classes=num_classes),
+                           bank, rows, players)
+
+  # -- episode statistics
+  def set_episode_stats(self, columns="default", pairs=()):
+    if self.stats is not None:
+      self.cover["stats_set over a live registration"] += 1
+    if isinstance(columns, str) and columns == "default":
+      columns = E.level_event_columns(int(self._o[0].tables["hdr"][1]))
+    self.stats = episode_stats_model.Model(self.N, self.P, columns, pairs)
+    self.stats_exact = self.speaks.copy()
+    self._after_cut = {}
+    return self.stats
+
+  def clear_episode_stats(self):
+    self.stats = None
+
+  def event_columns(self):
+    return E.level_event_columns(int(self._o[0].tables["hdr"][1]))
+
+  def _stats_world(self, w):
+    """The world whose statistics a step of world w is folded into: w (a list: worlds[i], not i)."""
+    return w
+
+  def _fold(self, w, cut=None):
+    """World w ran a step (a reset, a load): what it left is folded into the statistics."""
+    st = self.stats
+    if st is None:
+      return
+    v = self._stats_world(w)
+    if cut and st.open[v]:
+      self._cut(v, cut)
+    one = np.zeros(self.N, bool)
+    one[v] = True
+    shift = lambda kind: np.roll(self._target(kind), v - w, axis=0) if v != w else self._target(kind)
+    events = shift(E.OBS_EVENTS) if st.columns or st.pairs else None
+    before = int(st.episodes[v])
+    step_type = shift(E.OBS_STEP_TYPE)
+    st.step(step_type, shift(E.OBS_REWARD), events, ran=one)
+    own = self._after_cut.get(v)
+    if own is not None and int(step_type[v]) != 0:   # (the new episode's own sums, kept apart from the model's)
+      own["returns"] = own["returns"] + np.asarray(shift(E.OBS_REWARD)[v], np.float64)
+      own["length"] += 1
+    elif own is not None and not cut:
+      # (a FIRST with no cut in front: a restore put the world on a finished record and it restarted;
+      # the episode that will finish is the one that begins here)
+      own["returns"], own["length"] = np.zeros(self.P), 0
+    if st.episodes[v] > before:
+      if self._in_many >= 1:
+        self.cover["an episode finishes inside step k >= 1 of a K-step call, statistics registered"] += 1
+      if own is not None:
+        self._finished_after_cut(v, self._after_cut.pop(v))
+
+  def _cut(self, v, how):
+    """An open episode of world v is cut by a reset or a load (`how`: "reset", "masked reset", "load").
+    Where the cut writes FIRST the episode is dropped: `running` is zeroed and nothing of it is
+    counted.  A masked reset or a load that does so is remembered with the world's totals as they
+    are, for `_finished_after_cut`.  (A load of a finished row writes LAST: by the rule it closes
+    the open episode, which is no dropped cut.)"""
+    self._after_cut.pop(v, None)
+    if how != "reset" and int(self._target(E.OBS_STEP_TYPE)[v]) == 0:
+      st = self.stats
+      self.cover["an open episode cut by a load or a masked reset, statistics registered"] += 1
+      self._after_cut[v] = {"returns": np.zeros(self.P), "length": 0, "cut": st.running["returns"][v].copy(),
+                            "cut_length": int(st.running["length"][v]), "total": st.total["returns"][v].copy(),
+                            "total_length": int(st.total["length"][v]), "episodes": int(st.episodes[v])}
+
+  def _finished_after_cut(self, v, own):
+    """The episode world v began behind a cut has finished: `last` holds that episode alone and
+    `total` grew by it alone — the cut one's sums are in neither."""
+    st = self.stats
+    assert st.last["returns"][v].tobytes() == own["returns"].tobytes() and st.last["length"][v] == own["length"], \
+        f"world {v}: `last` is not the episode begun behind the cut"
+    assert st.total["returns"][v].tobytes() == (own["total"] + own["returns"]).tobytes(), \
+        f"world {v}: `total.returns` holds more than the episodes that finished (cut sums {own['cut']})"
+    assert st.total["length"][v] == own["total_length"] + own["length"] and st.episodes[v] == own["episodes"] + 1, \
+        f"world {v}: `total.length` / `episodes` count the cut episode (length {own['cut_length']})"
+    self.cover["an episode finishes after an open one was cut"] += 1
+
+  def stats_arrays(self):
+    return None if self.stats is None else self.stats.arrays()
 
   def _reset_world(self, w):
     self._o[w].reset()
@@ -287,6 +506,7 @@ class ModelEngine:
       if seeds is not None:
         self._reseed(w, seeds[w])
       self._reset_world(w)
+      self._fold(w, cut="reset" if mask is None else "masked reset")
     self._end()
 
   def _start_row(self, w):
@@ -321,6 +541,13 @@ class ModelEngine:
     self._step_starts = []
 
   def _advance(self, w, entry, auto_reset=None):
+    """One step of world w (see `_advance_world`), folded into the statistics if it ran."""
+    ran = self._advance_world(w, entry, auto_reset)
+    if ran:
+      self._fold(w)
+    return ran
+
+  def _advance_world(self, w, entry, auto_reset=None):
     """One step of world w; `entry`: ("step", ids [P]) or ("fields", f [P, A]).  False: a world
     never reset, which runs nothing."""
     o = self._o[w]
@@ -355,8 +582,112 @@ class ModelEngine:
       self.cover["non-zero reward on the step that leaves LAST"] += 1
     return True
 
-  def step(self, actions, active=None):
-    """active: a mask [N]; a world outside it is not touched (it writes nothing)."""
+  # -- a listed request: the masked request over all N worlds, gathered by entry
+  def _owners(self, worlds):
+    """[(entry, world)] of the entries that own their world: in range, and the lowest entry that
+    names it."""
+    seen, out = set(), []
+    for i, w in enumerate(np.asarray(worlds).tolist()):
+      if 0 <= w < self.N and w not in seen:
+        seen.add(w)
+        out.append((i, int(w)))
+    return out
+
+  def _stopped_at(self, i, w):
+    """The element of `stopped` that entry i of a list, which names world w, reads and writes."""
+    return w
+
+  def _bad_ran(self, before):
+    """What a bad entry's element of `ran` holds after the call: what it held."""
+    return before
+
+  def _listed(self, a, worlds, out, kw):
+    worlds = np.asarray(worlds)
+    if self._slots:
+      raise E.EngineError("MpStepListed: refused with a rollout ring bound")   # (MP_ERR_UNSUPPORTED)
+    M = len(worlds)
+    assert worlds.ndim == 1 and 1 <= M <= self.N
+    repeat, fields = kw.get("repeat"), kw.get("fields", False)
+    K = int(repeat) if repeat is not None else a.shape[0]
+    per = (self.P, self.num_action_fields) if fields else (self.P,)
+    a = np.broadcast_to(a, (K, M) + per) if repeat is not None else a.reshape((K, M) + per)
+    owners = self._owners(worlds)
+    full = np.zeros((K, self.N) + per, np.int32)
+    mask = np.zeros((K, self.N), bool)
+    active = kw.pop("active", None)
+    act = None if active is None else np.broadcast_to(np.asarray(active) != 0, (K, M))
+    for i, w in owners:
+      full[:, w] = a[:, i]
+      mask[:, w] = True if act is None else act[:, i]
+    stopped = kw.pop("stopped", None)
+    inner = None
+    if stopped is not None:
+      inner = np.zeros(self.N, np.uint8)
+      for i, w in owners:
+        inner[w] = stopped[self._stopped_at(i, w)]
+    bad = M - len(owners)
+    if bad:
+      self.cover["a listed call with a repeated and an out-of-range entry"] += 1
+      if self.stats is not None:
+        self.cover["a listed call with bad entries, statistics registered"] += 1
+    restarts = self.cover["paused on LAST, restarts in a later active step"]
+    name = tuple(worlds.tolist())
+    if inner is not None and any(inner[w] and self._stop_list.get(w, name) != name for _, w in owners):
+      self.cover["a listed until= call meets a stopped byte set under a different list"] += 1
+    was = None if inner is None else inner.copy()
+    taken = self.cover["registered start inside step k >= 1 of a K-step call"]
+    self._credit = {w: i for i, w in owners}
+    try:
+      res = self.step_many(full, **dict(kw, repeat=None, active=mask, stopped=inner))
+    finally:
+      self._credit = None
+    if self.cover["paused on LAST, restarts in a later active step"] > restarts:
+      self.cover["a listed call names a world paused on LAST"] += 1   # (which restarted in it)
+    if self.cover["registered start inside step k >= 1 of a K-step call"] > taken:
+      self.cover["a listed call with a registered start inside step k >= 1"] += 1
+    if stopped is not None:
+      for i, w in owners:
+        if inner[w] and not was[w]:
+          self._stop_list[w] = name
+        stopped[self._stopped_at(i, w)] = inner[w]
+      res["stopped"] = stopped
+    out = out or {}
+    gathered = {}
+    for key, value in res.items():
+      if key == "stopped":
+        gathered[key] = value
+        continue
+      by_entry = key in ("ran", "returns")
+      if key == "states":
+        rows = [[out[key][k][i] if key in out else None for i in range(M)] for k in range(K)]
+        for i, w in owners:
+          for k in range(K):
+            rows[k][i] = value[k][w]
+        gathered[key] = rows
+        continue
+      shape = ((M,) if by_entry else (K, M)) + value.shape[1 if by_entry else 2:]
+      g = np.array(out[key]) if key in out else np.zeros(shape, value.dtype)
+      assert g.shape == shape and g.dtype == value.dtype, (key, g.shape, shape, g.dtype, value.dtype)
+      if key == "ran":
+        owned = {i for i, _ in owners}
+        for i in range(M):
+          if i not in owned:
+            g[i] = self._bad_ran(g[i])
+      for i, w in owners:
+        if by_entry:
+          g[i] = value[w]
+        else:
+          g[:, i] = value[:, w]
+      gathered[key] = g
+    return gathered
+
+  def step(self, actions, active=None, worlds=None):
+    """active: a mask [N]; a world outside it is not touched (it writes nothing).
+    worlds: a list of M worlds, actions [M, P]: the K = 1 listed request of step_many."""
+    if worlds is not None:
+      a = np.asarray(actions, np.int32)
+      self.step_many(a[None], keep=(), active=active, worlds=worlds)
+      return
     a = np.asarray(actions, np.int32).reshape(self.N, self.P)
     self._begin(masked=active is not None)
     for w in range(self.N):
@@ -402,7 +733,8 @@ class ModelEngine:
 
   def step_many(self, actions, *, repeat=None, fields=False, events=False, observations=(),
                 keep=("reward", "collective_reward", "step_type", "discount"), active=None,
-                until=None, stop=None, stopped=None, returns=False, gamma=1.0, states=False, hashes=False):
+                until=None, stop=None, stopped=None, returns=False, gamma=1.0, states=False, hashes=False,
+                worlds=None, out=None):
     """The loop over single steps as ONE submission; returns the per-step rows under the keys of
     `engine.Engine.step_many` (a row of LAYER is the function of the records after that step).
     active: a mask [K, N] or [N]: world w runs step k only where it is non-zero.
@@ -414,6 +746,12 @@ class ModelEngine:
     states: "states", a list of K lists of the N worlds' rows (`_row`) after every step — each is a
     bank like save_worlds'.  hashes: "hashes" int64 [K, N], `hash_states` of those rows."""
     a = np.asarray(actions, np.int32)
+    if worlds is not None:
+      # worlds: a list of M worlds; everything per world has M columns, by entry, but `stopped` [N];
+      # out: what a bad entry's elements of the rows, `ran` and `returns` held before the call
+      return self._listed(a, worlds, out, dict(repeat=repeat, fields=fields, events=events, observations=observations,
+                                               keep=keep, active=active, until=until, stop=stop, stopped=stopped,
+                                               returns=returns, gamma=gamma, states=states, hashes=hashes))
     K = int(repeat) if repeat is not None else a.shape[0]
     if stop is None:
       names = () if until is None else (until,) if isinstance(until, str) else tuple(until)
@@ -449,6 +787,8 @@ class ModelEngine:
         reason = self._stops(w, stop)
         if reason:
           stopped[w] = reason
+          if self._credit is None:
+            self._stop_list.pop(w, None)   # (set by a call without a list)
           if k + 1 < K and (mask is None or mask[k + 1:, w].any()):
             for bit, name in ((E.MP_STOP_LAST, "LAST"), (E.MP_STOP_REWARD, "REWARD")):
               if reason & bit:
@@ -530,6 +870,7 @@ class ModelEngine:
         continue
       self._become(w, row)
       self._wrote_load(w, row)
+      self._fold(w, cut="load")
     self._end()
 
   def snapshot(self):
@@ -539,7 +880,11 @@ class ModelEngine:
     """mp_restore puts the records back (counters included: they live in the records); it is no
     launch, so no output buffer, bound view or ring slot is written."""
     rows, bad = snap
+    if self.stats is not None:
+      self.cover["restore while statistics are registered"] += 1
     for w, row in enumerate(rows):
+      if self.units and self.row_key(row) != self.row_key(self._row(w)):
+        self._restored[w] = True
       self._become(w, row)
     self._bad = bad.copy()
 

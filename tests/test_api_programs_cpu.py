@@ -3,7 +3,10 @@ model against an independent restatement of itself, and the runner against delib
 models — each must be reported at the first op where it can show.  For the STATE programs also:
 the first set's programs are op for op what they were (CRCs), every adjacency with a new class is
 held, and the model's own runs contain the crossings the programs are there for (printed under
-`pytest -s`; profiles/r24_state_programs.md)."""
+`pytest -s`; profiles/r24_state_programs.md).  For the UNIT programs the same again: the state set is
+pinned by CRCs too, every adjacency with a unit class is held, each level's two programs contain the
+crossings of listed steps, statistics and view units (exemptions listed by name), and eight more
+wrong models are reported at their first op (profiles/r31_unit_programs.md)."""
 import collections
 import functools
 import zlib
@@ -144,8 +147,11 @@ class ScratchModel(ModelEngine):
         self._hist[w].append(("reset", None if seeds is None else int(seeds[w])))
     super().reset(seeds, mask)
 
-  def step(self, actions, active=None):
+  def step(self, actions, active=None, worlds=None):
     a = np.asarray(actions, np.int32)
+    if worlds is not None:
+      self.step_many(a[None], keep=(), active=active, worlds=worlds)
+      return
     for w in range(self.N):
       if active is None or active[w]:
         self._hist[w].append(("step", a[w].copy()))
@@ -160,11 +166,43 @@ class ScratchModel(ModelEngine):
 
   def step_many(self, actions, *, repeat=None, fields=False, events=False, observations=(),
                 keep=("reward", "collective_reward", "step_type", "discount"), active=None, until=None,
-                stopped=None, returns=False, gamma=1.0, states=False, hashes=False):
+                stopped=None, returns=False, gamma=1.0, states=False, hashes=False, worlds=None, out=None):
     """The defining identity, unrolled: the loop of step(A[k], active=M[k] & (stopped == 0)) with
-    `stopped` updated on the "host" from what each step left."""
+    `stopped` updated on the "host" from what each step left.  A list (worlds=) is the identity of
+    MpStepListed, restated: the world's owner is its first entry; the full request gets the caller's
+    `stopped` itself (an unlisted world is masked out, so its byte stays), and every other per-call
+    tensor is gathered by entry on top of what `out` held."""
     assert not self._slots
     a = np.asarray(actions, np.int32)
+    if worlds is not None:
+      names = [int(w) for w in worlds]
+      M = len(names)
+      owner = {}
+      for i in reversed(range(M)):
+        if 0 <= names[i] < self.N:
+          owner[names[i]] = i
+      K = int(repeat) if repeat is not None else a.shape[0]
+      blocks = [a if repeat is not None else a[k] for k in range(K)]
+      full = np.zeros((K, self.N) + blocks[0].shape[1:], np.int32)
+      mask = np.zeros((K, self.N), np.uint8)
+      for w, i in owner.items():
+        for k in range(K):
+          full[k, w] = blocks[k][i]
+          mask[k, w] = 1 if active is None else (np.asarray(active)[k, i] if np.ndim(active) == 2 else np.asarray(active)[i]) != 0
+      res = self.step_many(full, fields=fields, events=events, observations=observations, keep=keep, active=mask,
+                           until=until, stopped=stopped, returns=returns, gamma=gamma)
+      got = {}
+      for key, value in res.items():
+        if key == "stopped":
+          got[key] = value
+          continue
+        axis = 0 if key in ("ran", "returns") else 1
+        shape = value.shape[:axis] + (M,) + value.shape[axis + 1:]
+        g = np.array(out[key]) if out and key in out else np.zeros(shape, value.dtype)
+        for w, i in owner.items():
+          g[(slice(None),) * axis + (i,)] = value[(slice(None),) * axis + (w,)]
+        got[key] = g
+      return got
     K = int(repeat) if repeat is not None else a.shape[0]
     keys = list(keep) + (["events"] if events else []) + [int(k) for k in observations]
     rows = {key: [] for key in keys}
@@ -630,6 +668,339 @@ def test_the_runner_reports_a_wrong_state_model_at_its_first_op(wrong, classes, 
   prog = _state_program(name)
   profile = prog.profile
   right, bad = _state_trace(prog, ap.make_model(profile)), _state_trace(prog, ap.make_model(profile, wrong))
+  first = next((i for i, (x, y) in enumerate(zip(right, bad)) if not _equal(x, y)), None)
+  assert first is not None, "this program never shows the wrong model: choose another"
+  assert prog[first]["op"] in classes, (first, prog[first]["op"])
+  with pytest.raises(ap.Mismatch) as err:
+    ap.run_program(prog, ap.make_model(profile, wrong), ap.make_model(profile))
+  text = str(err.value)
+  assert f"program seed {prog.seed}, profile {name}, op {first}: {prog[first]['op']}" in text, text
+  print(wrong.__name__, "->", text[:300])
+  # a prefix that stops short of the op passes
+  assert ap.run_program(prog, ap.make_model(profile, wrong), ap.make_model(profile), stop_after=first) == first
+
+
+# ================================================================== the unit programs
+# the state set pinned like the first: CRC-32 of every program's short forms and of its arguments' bytes
+STATE_SET_CRCS = [
+    3816710759, 4143868851, 217564662, 3440129169, 3437300365, 698209822, 2511290929, 4040866472, 596609386,
+    3793023513, 1785998425, 3175777831, 696836456, 1997367625, 3823030810, 3758347594, 4222190984, 3078957703,
+    2818926858]
+STATE_SET_BYTES_CRCS = [
+    691786250, 2652828220, 2620479898, 1658825342, 4229507520, 797941129, 171602092, 3414761698, 623677607,
+    1590449189, 2444314014, 2489661867, 2185322165, 4027376909, 2679954219, 721275784, 537908407, 2502742082,
+    3080636833]
+
+
+def test_the_state_set_is_op_for_op_what_it_was():
+  programs = [_state_program(n) for n in STATE_IDS]
+  assert [zlib.crc32("\n".join(ap.short_form(op) for op in prog).encode()) for prog in programs] == STATE_SET_CRCS
+  assert [_bytes_crc(prog) for prog in programs] == STATE_SET_BYTES_CRCS
+
+
+UNIT_IDS = [p["name"] for _, p in ap.UNIT_COMMITTED]
+# the bounds of a unit program: the state set's, but 80 ops at least — with 70 the search did not find
+# totals that hold finished episodes at the end on coins and territory (their episodes are 33 frames), so
+# the last stats_set of a program is followed by UNIT_STATS_TAIL ops
+assert (ap.UNIT_MIN_OPS, ap.UNIT_MAX_OPS, ap.UNIT_MAX_WORLD_STEPS) == (80, 110, 260)
+assert ap.UNIT_LAST_STATS_CLEAR < ap.UNIT_LAST_STATS_SET == ap.UNIT_MIN_OPS - ap.UNIT_STATS_TAIL
+
+
+@functools.lru_cache(maxsize=None)
+def _unit_program(name):
+  seed, profile = next((s, p) for s, p in ap.UNIT_COMMITTED if p["name"] == name)
+  return ap.make_program(seed, profile)
+
+
+@functools.lru_cache(maxsize=None)
+def _unit_cover(name):
+  return ap.program_cover(_unit_program(name))
+
+
+def test_the_unit_set_is_the_one_the_issue_names():
+  profiles = [p for _, p in ap.UNIT_COMMITTED]
+  assert len(set(UNIT_IDS)) == len(profiles) == 2 * len(ap.LEVEL_PACKS) + 1 == 19
+  assert not set(UNIT_IDS) & (set(STATE_IDS) | {p["name"] for _, p in ap.COMMITTED})
+  rings = 0
+  for li, pack in enumerate(ap.LEVEL_PACKS):
+    small, large = (next(p for p in profiles if p["name"] == f"{pack}-units-n{n}") for n in (6, 23))
+    assert small["n"] == 6 and not small["ring"] and small["classes"] == ap.UNIT_CLASSES
+    assert all(p["rich"] and p["auto_reset"] and p["frames"] == ap.LONG_EPISODES.get(pack, ap.EPISODE_FRAMES)
+               for p in (small, large))
+    assert bool(small["num_players"]) == ("in_the_matrix" not in pack and pack != "coins")
+    if small["num_players"]:
+      assert small["num_players"] == ap._geometry(large)["P"] - 1
+    assert large["n"] == 23
+    if large["ring"]:
+      rings += 1
+      assert large["ring"] == ap.RING_SLOTS and not set(large["classes"]) & set(ap.RING_REFUSED)
+      assert set(large["classes"]) | set(ap.RING_REFUSED) == set(ap.UNIT_CLASSES)
+      first = _unit_program(large["name"])[1]
+      assert first["op"] == "step_listed" and first["refused"]
+    else:
+      assert large["world_pool"] == 8 and set(large["views"]) == {E.OBS_WORLD_RGB, E.OBS_LAYER}
+      assert large["classes"] == ap.UNIT_CLASSES
+    assert bool(large["ring"]) == bool(li % 2)   # the two forms alternate by level
+  assert rings == 4
+  stock = [p for p in profiles if p["stock"]]
+  assert len(stock) == 1 and ap.profile_pack(stock[0]) == E.load_pack("clean_up") and stock[0]["classes"] == ap.UNIT_CLASSES
+  ops = [op for name in UNIT_IDS for op in _unit_program(name)]
+  listed = [op for op in ops if op["op"] in ap.LISTED_CLASSES and not op.get("refused")]
+  share = sum(op["bad"] for op in listed) / len(listed)
+  assert 0.1 < share < 0.4, share   # about one in four carries bad entries
+  many = [op for op in listed if op["op"] == "many_listed"]
+  assert {op["form"] for op in many} == {"plain", "repeat", "slice"} and {op["fields"] for op in many} == {False, True}
+  assert {None if op["active"] is None else op["active"].ndim for op in many} == {None, 1, 2}
+  assert {op["until"] for op in many} == set(ap.UNTILS) | {None}
+  assert any(op["observations"] for op in many) and any(op["returns"] and op["gamma"] != 1.0 for op in many)
+  sets = [op for op in ops if op["op"] == "stats_set"]
+  assert {"default", ()} <= {op["columns"] for op in sets} and any("[" in "".join(op["columns"]) for op in sets)
+  units = [op for op in ops if op["op"] == "units_set"]
+  assert {n for op in units for n in op["units"]} == set(ap.UNIT_NAMES)
+  assert {op["hash"]["classes"] is None for op in units if "hash" in op["units"]} == {False, True}
+  planes = [op["planes"] for op in units if "planes" in op["units"]]
+  assert {p["facing"] for p in planes} == {False, True} and {p["num_classes"] is None for p in planes} == {False, True}
+  assert all((p["classes"] == -1).any() for p in planes) and len({p["offset"] for p in planes}) > 4
+  reads = [op for op in ops if op["op"] == "unit_rows"]
+  assert {op["unit"] for op in reads} == set(ap.UNIT_NAMES) and {op["bank"] < 0 for op in reads} == {False, True}
+  assert {op["players"] is None for op in reads} == {False, True}
+
+
+@pytest.mark.parametrize("name", UNIT_IDS)
+def test_unit_programs_are_deterministic_and_within_bounds(name):
+  seed, profile = next((s, p) for s, p in ap.UNIT_COMMITTED if p["name"] == name)
+  prog, again = _unit_program(name), ap.make_program(seed, profile)
+  assert len(prog) == len(again) and all(_equal(a, b) for a, b in zip(prog, again))   # (an op may nest a dict)
+  assert prog[0]["op"] == "reset_all"
+  assert {op["op"] for op in prog if not op.get("refused")} == set(profile["classes"])
+  assert ap.UNIT_MIN_OPS <= len(prog) <= ap.UNIT_MAX_OPS
+  assert ap.world_steps(prog) <= ap.UNIT_MAX_WORLD_STEPS
+  assert ap.longest_host_run(prog) >= ap.HOST_RUN
+  adjacent = {(a["op"], b["op"]) for a, b in zip(prog[:-1], prog[1:])}
+  assert set(ap.assigned_pairs(profile)) <= adjacent
+  g = ap._geometry(profile)
+  N, P, A = g["N"], g["P"], g["A"]
+  banks, wide, live = [], 0, set()
+  for op in prog:
+    c = op["op"]
+    if c in ("save", "step_many_states"):
+      banks.append(len(op["worlds"]) if c == "save" else op["K"] * N)
+    if c in ap.LISTED_CLASSES:
+      w = op["worlds"]
+      M = len(w)
+      assert w.dtype == np.int32 and 1 <= M <= N
+      inside = w[(w >= 0) & (w < N)]
+      assert op["bad"] == (len(inside) < M) == (len(set(inside.tolist())) < len(inside))   # both kinds, or neither
+      E.check_step_listed(w, N, P)
+      if c == "step_listed":
+        assert op["actions"].shape == (M, P)
+      else:
+        K = op["K"]
+        assert K in ap.STATE_K
+        lead = () if op["form"] == "repeat" else (K,)
+        E.check_step_listed(w, N, P, actions=np.zeros(lead + (M, P) + ((A,) if op["fields"] else ()), np.int32),
+                            repeat=K if op["form"] == "repeat" else None, num_fields=A if op["fields"] else None,
+                            active=op["active"])
+        assert op["actions"].shape == lead + (M + 3 if op["form"] == "slice" else M, P) + ((A,) if op["fields"] else ())
+        if op["until"] is not None:
+          E.check_step_until(N, P, until=op["until"], gamma=op["gamma"])
+        assert op["returns"] or op["gamma"] == 1.0
+    if c == "stats_set":
+      cols = g["columns"][0] if op["columns"] == "default" else op["columns"]
+      for name_ in tuple(cols) + tuple(op["pairs"]):
+        E.parse_event_column(name_)
+      assert len(op["pairs"]) == (0 if profile["pack"] in ap.NO_BEAM else 1)
+    if c == "units_set":
+      assert op["units"] and set(op["units"]) <= set(ap.UNIT_NAMES)
+      live |= set(op["units"])
+      if "planes" in op["units"]:
+        p = op["planes"]
+        C = int(p["classes"].max()) + 1 if p["num_classes"] is None else p["num_classes"]
+        assert p["classes"].shape == (g["ids"],) and p["classes"].min() == -1 and p["classes"].max() < C <= 64
+        assert 0 <= p["offset"] <= 15
+      if "hash" in op["units"]:
+        h = op["hash"]
+        assert (h["layers"] is None and h["classes"] is None) or h["classes"].shape == (g["ids"],)
+    if c == "units_clear":
+      assert op["unit"] in live
+      live.discard(op["unit"])
+    if c == "unit_rows":
+      there = N if op["bank"] < 0 else banks[op["bank"]]
+      assert op["rows"].min() >= 0 and op["rows"].max() < there
+      assert op["players"] is None or (len(op["players"]) == len(op["rows"]) and op["players"].max() < P)
+      wide += len(op["rows"]) > N
+  assert wide == 1, "one unit read of a program has more rows than worlds"
+
+
+def test_every_pair_with_a_unit_class_is_adjacent_somewhere():
+  programs = [_unit_program(n) for n in UNIT_IDS]
+  table = ap.pair_counts(programs, ap.UNIT_CLASSES)
+  print(ap.format_pair_table(table, ap.UNIT_CLASSES))
+  print("unit programs: ops", sum(len(p) for p in programs), "world-steps", sum(ap.world_steps(p) for p in programs))
+  idx = {c: i for i, c in enumerate(ap.UNIT_CLASSES)}
+  missing = [(a, b) for a, b in ap.required_unit_pairs() if table[idx[a], idx[b]] == 0]
+  assert not missing, missing
+  assert len(ap.required_unit_pairs()) == 27 * 26 - 21 * 20 + 6
+
+
+# what a level cannot hold by its rules (at most two a level; none of the listed-step conditions, nor
+# the restore-then-skip one)
+UNIT_EXEMPT = {pack: [] for pack in ap.LEVEL_PACKS}
+for _pack in ap.LEVEL_PACKS:
+  if _pack not in states_recipe.DEAD_AVATARS + ("territory__inside_out",):
+    UNIT_EXEMPT[_pack].append((ap.UNIT_DEAD_VIEWER, "no rule of the level takes an avatar off the map"))
+  if _pack in ap.NO_BEAM:
+    UNIT_EXEMPT[_pack].append(("non-zero total.pairs at the end", "the level has no two-player event: no pair column"))
+# (an interaction takes two players who have both collected a resource and then meet and fire: six
+# worlds of the programs' weighted random play held none in 300 steps with no episode end at all, more
+# than the 260 world-steps of a whole program — no MAXFRAMES and no bound near the set's reaches one)
+UNIT_EXEMPT["prisoners_dilemma_in_the_matrix__repeated"].append(
+    ("non-zero total.pairs at the end", "random play does not reach an interaction within a program's world-steps"))
+NEVER_EXEMPT = tuple(k for k in ap.UNIT_COVER_CONDITIONS if "listed" in k or "skipped that world" in k)
+
+
+def _unit_level_cover(pack):
+  total = collections.Counter()
+  for n in (6, 23):
+    total.update(_unit_cover(f"{pack}-units-n{n}"))
+  return total
+
+
+def test_the_models_runs_hold_the_unit_crossings_on_every_level():
+  import ego_layer_model
+  conditions = ap.UNIT_COVER_CONDITIONS + (ap.UNIT_DEAD_VIEWER, ap.UNIT_OFF_THE_MAP)
+  print("| level | " + " | ".join(conditions) + " |")
+  print("|---|" + "---|" * len(conditions))
+  covers = {pack: _unit_level_cover(pack) for pack in ap.LEVEL_PACKS}
+  for pack, cover in covers.items():
+    print(f"| {pack} | " + " | ".join(str(cover[k]) for k in conditions) + " |")
+  assert len(NEVER_EXEMPT) == 5
+  for pack, cover in covers.items():
+    exempt = [k for k, _ in UNIT_EXEMPT[pack]]
+    assert len(exempt) <= 2 and not set(exempt) & set(NEVER_EXEMPT)
+    torus = ego_layer_model.geometry(E.load_pack(pack))[4]
+    for k in conditions:
+      if k in exempt or (k == ap.UNIT_OFF_THE_MAP and torus):
+        continue
+      assert cover[k] > 0, (pack, k)
+
+
+def test_the_model_equals_its_restatement_on_a_unit_program():
+  prog = _unit_program("clean_up-units-n6")
+  profile = prog.profile
+  a, b = ap.make_model(profile), ap.make_model(profile, ScratchModel)
+  assert ap.run_program(prog, a, b) == len(prog)
+  a.close(); b.close()
+
+
+def test_a_ring_unit_program_runs_model_against_model():
+  prog = _unit_program("coins-units-n23")
+  profile = prog.profile
+  assert profile["ring"] == ap.RING_SLOTS
+  a, b = ap.make_model(profile), ap.make_model(profile)
+  assert ap.run_program(prog, a, b) == len(prog)
+  assert a.ring["slots"] == ap.RING_SLOTS and a.units
+  a.close(); b.close()
+
+
+# ---- the runner against wrong models of the unit classes
+class SkippedWorldsViewIsLeftAlone(ModelEngine):
+  """(as a bound LAYER's element is)"""
+  def _unit_worlds(self):
+    return range(self.N) if self._touched is None else sorted(self._touched)
+
+
+class RestoreRedrawsTheUnits(ModelEngine):
+  def restore(self, snap):
+    super().restore(snap)
+    self._draw_units()
+
+
+class RepeatedEntryStepsItsWorldTwice(ModelEngine):
+  def _listed(self, a, worlds, out, kw):
+    res = super()._listed(a, worlds, out, dict(kw))
+    worlds = np.asarray(worlds)
+    owned = {i for i, _ in self._owners(worlds)}
+    again = [i for i, w in enumerate(worlds.tolist()) if 0 <= w < self.N and i not in owned]
+    if again:
+      act = kw.get("active")
+      super()._listed(a[again] if kw.get("repeat") is not None else a[:, again], worlds[again], None,
+                      dict(kw, active=None if act is None else np.asarray(act)[..., again], stopped=None, until=None,
+                           returns=False, keep=(), events=False, observations=()))
+    return res
+
+
+class StoppedIsIndexedByEntry(ModelEngine):
+  def _stopped_at(self, i, w):
+    return i
+
+
+class BadEntrysRanIsZero(ModelEngine):
+  def _bad_ran(self, before):
+    return 0
+
+
+class LoadCutCountsIntoTotal(ModelEngine):
+  def _cut(self, v, how):
+    super()._cut(v, how)
+    if how == "load":
+      st = self.stats
+      for key in st.running:
+        st.total[key][v] = st.total[key][v] + st.running[key][v]
+
+  def _finished_after_cut(self, v, own):   # (the right model asserts here that the cut sums are nowhere)
+    pass
+
+
+class StatisticsFoldASkippedStep(ModelEngine):
+  def _skipped(self, w, by_mask=True):
+    super()._skipped(w, by_mask)
+    if self._started[w]:
+      self._fold(w)
+
+
+class ListedStatisticsGoToTheEntry(ModelEngine):
+  def _stats_world(self, w):
+    return w if self._credit is None else self._credit[w]
+
+
+SKIPPING = ("step_active", "many_active", "many_until", "step_many_states") + ap.LISTED_CLASSES
+# (wrong model, op classes at which it can first show, the unit program that shows it)
+WRONG_UNIT_MODELS = [
+    (SkippedWorldsViewIsLeftAlone, SKIPPING, "clean_up-units-n6"),
+    (RestoreRedrawsTheUnits, ("restore",), "clean_up-units-n6"),
+    (RepeatedEntryStepsItsWorldTwice, ap.LISTED_CLASSES, "clean_up-units-n6"),
+    (StoppedIsIndexedByEntry, ("many_listed",), "clean_up-units-n6"),
+    (BadEntrysRanIsZero, ("many_listed",), "commons_harvest__open-units-n6"),
+    (LoadCutCountsIntoTotal, ("load",), "clean_up-units-n6"),
+    (StatisticsFoldASkippedStep, SKIPPING, "clean_up-units-n6"),
+    (ListedStatisticsGoToTheEntry, ap.LISTED_CLASSES, "clean_up-units-n6"),
+]
+
+
+def _unit_trace(program, model):
+  """What the runner looks at, after every op, of a model run alone: the state trace's, the
+  statistics and the registered tensors."""
+  import episode_stats_model
+  side = ap._Side(model)
+  side.profile, side.states_banks = program.profile, {}
+  out = []
+  for op in program:
+    op = ap.resolve(op, side)
+    side.apply(op, program.profile["ring"])
+    stats = None if model.stats is None else {k: np.array(ap._bits(v)) for k, v in
+                                              episode_stats_model.flatten(model.stats.arrays()).items()}
+    out.append((model.dump(), [model.observe_host(k) for k in model.scalar_kinds], side.rows, side.read,
+                side.stopped.copy(), model.counters(), {k: np.array(v) for k, v in model._bound.items()},
+                stats, {n: np.array(u["out"]) for n, u in side.units.items()}))
+  return out
+
+
+@pytest.mark.parametrize("wrong,classes,name", WRONG_UNIT_MODELS, ids=[w[0].__name__ for w in WRONG_UNIT_MODELS])
+def test_the_runner_reports_a_wrong_unit_model_at_its_first_op(wrong, classes, name):
+  prog = _unit_program(name)
+  profile = prog.profile
+  right, bad = _unit_trace(prog, ap.make_model(profile)), _unit_trace(prog, ap.make_model(profile, wrong))
   first = next((i for i, (x, y) in enumerate(zip(right, bad)) if not _equal(x, y)), None)
   assert first is not None, "this program never shows the wrong model: choose another"
   assert prog[first]["op"] in classes, (first, prog[first]["op"])

@@ -15,7 +15,17 @@ that become banks, registered episode starts whose `rows` are rewritten on the d
 saved states (observe_states, observe_views, the hashes, check_states) — two programs per level with
 6 and 23 worlds (a last workgroup of 2 and of 3) on the levels' variants that pay often, and one on
 the committed clean_up pack.  There the twin runs the other form of every new K-step call, the host
-loop of masked single steps, and performs a registration's defining identity with load_worlds."""
+loop of masked single steps, and performs a registration's defining identity with load_worlds.
+
+The third test runs the UNIT programs (api_programs.UNIT_COMMITTED): the state classes plus listed
+steps (with entries that are no world and entries that repeat one, in tensors filled beforehand),
+episode statistics registered, re-registered and cleared, and the three view units (EGO_LAYER, the
+view hashes, the planes) registered in any subset, in place or as rings, and read from bank rows and
+live worlds.  After every op the statistics tensors equal the model's fold bit for bit and the
+library's host fold of what the twin's single steps left; every registered tensor equals the model's
+function of all N records and the library's host form of save_worlds(), and changes only behind a
+submission.  The twin registers nothing, so everything it is compared on shows that a registration
+changes no record and no output."""
 import pytest
 
 import api_programs as ap
@@ -54,5 +64,33 @@ def test_state_program(seed, profile):
     else:
       assert eng.plan["stock"] == engine.KERNEL_GENERIC
     assert ap.run_program(program, eng, model, twin) == len(program)
+  finally:
+    eng.close(); twin.close(); model.close()
+
+
+@pytest.mark.parametrize("seed,profile", ap.UNIT_COMMITTED, ids=[p["name"] for _, p in ap.UNIT_COMMITTED])
+def test_unit_program(seed, profile):
+  import collections
+  program = ap.make_program(seed, profile)
+  eng, twin = ap.make_engines(profile)
+  model = ap.make_model(profile)
+  cover = collections.Counter()
+  try:
+    if profile["stock"]:
+      assert eng.plan["stock"] == engine.KERNEL_STOCK
+      assert twin.plan["stock"] == engine.KERNEL_GENERIC
+    else:
+      assert eng.plan["stock"] == engine.KERNEL_GENERIC
+    assert ap.run_program(program, eng, model, twin, cover=cover) == len(program)
+    print("cover", profile["name"], dict(sorted(cover.items())))
+    if profile["ring"]:
+      assert eng.ring["slots"] == ap.RING_SLOTS
+    # (the runner has stopped on any other word after every op: only a bad entry's report was ever set)
+    words = eng.fault_words()[:18].copy()
+    if any(op.get("bad") and not op.get("refused") for op in program):
+      assert (words[11] & 255) in ap.LISTED_FAULTS + (0,), words
+      words[9:12] = 0
+    assert not words.any(), eng.fault_words()[:18]
+    assert not twin.fault_words()[:18].any()
   finally:
     eng.close(); twin.close(); model.close()
