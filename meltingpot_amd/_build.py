@@ -21,9 +21,9 @@ LIB_PATH = os.path.join(LIB_DIR, "libmp_engine.so")
 # likewise; step_starts.hip: the single-step kernels with registered episode starts, a unit of its own
 # so that step_kernels.hip's are what they were; state_view.hip: the renderer of one (row, player)
 # view, likewise; step_active.hip and step_until.hip: the K-step kernels under a device mask and with
-# stop conditions, one unit each so that every unit has one caller of each level's step; both
-# instantiate the one body of step_masked.h; step_listed.hip: the K-step kernels of a world list, a
-# unit with its own copy of that body; episode_stats.hip: the launch behind every submission of an
+# stop conditions, and step_listed.hip: the K-step kernels of a world list, one unit each so that every
+# unit has one caller of each level's step; all three instantiate the one body of step_masked.h;
+# episode_stats.hip: the launch behind every submission of an
 # engine with registered episode statistics, which includes no step header; ego_layer.hip: the
 # EGO_LAYER draw and the launch behind every submission of an engine with the leaf registered;
 # view_hash.hip: the hash of every player's view, likewise a draw and a launch behind every submission;

@@ -64,11 +64,11 @@ __global__ __launch_bounds__(kWaves * 64) void k_episode_stats(const Columns sc,
   // which world, and did it run anything at all?
   int w = i;
   bool live = true;
-  if (r.worlds) {   // (run_many_listed's liveness test: a world, and this entry's tag in its claim word)
+  if (r.worlds) {   // (a listed step's liveness test, step_masked.h: a world, and this entry's tag in its claim word)
     w = __builtin_amdgcn_readfirstlane(r.worlds[i]);
     if (w < 0 || w >= r.num_worlds) { live = false; w = 0; }
     else {
-      const unsigned long long tag = ((unsigned long long)r.generation << 32) | (unsigned long long)(~(uint32_t)i);
+      const unsigned long long tag = listed_tag(r.generation, i);
       live = r.claim[w] == tag;
     }
   }

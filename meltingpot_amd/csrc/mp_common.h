@@ -457,5 +457,13 @@ enum { FAULT_STATE_INDEX = 9 };
 // words 32-35 = world + 1, rows[world], the rule of the row's verdict (0: a bad index), its offset word.
 constexpr int kFaultStartWorld = 32;
 
+// The claim word of world w in an MpStepListed request (step_listed.h: ListArgs): the tag of the
+// entry i that owns it.  The claim launch takes the maximum, so within a generation the lowest i
+// wins, and a newer generation beats every older one.  One definition for the claim kernel, the
+// step kernels' entry resolution and k_episode_stats.
+__host__ __device__ inline unsigned long long listed_tag(uint32_t generation, int i) {
+  return ((unsigned long long)generation << 32) | (unsigned long long)(~(uint32_t)i);
+}
+
 
 #endif  // MP_COMMON_H_

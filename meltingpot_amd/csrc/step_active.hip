@@ -1,6 +1,7 @@
 // step_active.hip — the K-step kernels under a device mask (MpStepActive, include/mp_engine.h):
 // in step k world w runs only where active[k][w] != 0, and is not touched otherwise.  The body is
-// run_many_masked<.., Until = false> (step_masked.h).  A unit of its own: the families of
+// run_many_masked<.., Until = false> (step_masked.h: one body for this family, step_until.hip's and
+// step_listed.hip's).  A unit of its own: the families of
 // step_many.hip, step_kernels.hip and step_starts.hip keep one caller of each level's step in
 // their unit (step_starts.hip says why).
 #include "step_levels.h"

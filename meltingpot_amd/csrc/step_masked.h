@@ -1,14 +1,23 @@
 // step_masked.h — the one body of the K-step kernels under a device mask (MpStepActive,
-// step_active.hip: Until = false) and of those with stop conditions besides (MpStepUntil,
-// step_until.hip: Until = true).  Each of the two units instantiates it for its own kernel family,
-// one caller of each level's step in a unit (step_starts.hip says why).
+// step_active.hip: Until = false), of those with stop conditions besides (MpStepUntil,
+// step_until.hip: Until = true) and of those of a world list (MpStepListed, step_listed.hip:
+// Until and Listed).  Each of the three units instantiates it for its own kernel family, one
+// caller of each level's step in a unit (step_starts.hip says why).
 #ifndef MP_STEP_MASKED_H_
 #define MP_STEP_MASKED_H_
 
+#include "step_listed.h"
 #include "step_rows.h"
-#include "step_until.h"
 
 namespace stepk {
+
+// An entry the launch skips; one of a launch's is named (state_view.hip reports the same way).
+__device__ inline void report_entry(const DevTables& t, int lane, int i, int value, uint32_t what) {
+  if (lane == 0 && atomicCAS(&t.fault[FAULT_STATE_INDEX], 0u, (uint32_t)i + 1u) == 0u) {
+    t.fault[FAULT_STATE_INDEX + 1] = (uint32_t)value;
+    t.fault[FAULT_STATE_INDEX + 2] = what;
+  }
+}
 
 // run_many (step_many.hip; step_rows.h documents the rows, the carry rule and the fences) under a
 // mask, and with a stop state where Until.  ONE family for every request: which rows are asked for
@@ -61,20 +70,62 @@ namespace stepk {
 //    rounded on its own (__dmul_rn, __dadd_rn: no FMA), each lane its player's sum.
 //  * a stopped world with no rows asked for leaves the loop: nothing more is written for it.
 // ran counts the steps of a started world (a world never reset runs nothing and never stops).
-template <class Tables, class Sites, bool Until>
+//
+// The list (Listed, always with Until) gives the wave TWO indices where the others have one:
+//  * the world w = worlds[i], a wave-uniform load in front of everything, for the record, the
+//    in-place buffers, next_orders, `stopped` and the registration's rows[];
+//  * the column i, the wave's own number, for the actions, the mask, the per-step rows, ran and
+//    returns.  The rows of the five kinds and of r.fin are reached through bases shifted by
+//    d = i - w worlds (row_of, step_rows.h), the level kinds, LAYER, the state row and the hash row
+//    by i itself.
+// A wave whose entry is no world, or whose world's claim word holds another entry's tag
+// (listed_tag, mp_common.h; k_claim_listed, step_listed.hip, ran in front of this launch), is a
+// wave past the end of the list: it takes part in load_tables and the barrier and returns, having
+// written nothing but the report (report_entry).  Without Listed w is i, d is 0, and a wave is live
+// where w < num_worlds.
+template <class Tables, class Sites, bool Until, bool Listed = false>
 __device__ inline void run_many_masked(const DevTables& t, const Tables& c, const StepArgs& args0,
                                        const ManyArgs& m, const StepRows& r, int extra,
                                        const StateRows& sp, const HashRows& hp, const StartArgs& st,
-                                       const ActiveArgs& am, const UntilArgs* um = nullptr) {
+                                       const ActiveArgs& am, const UntilArgs* um = nullptr,
+                                       const ListArgs* la = nullptr) {
+  static_assert(Until || !Listed, "a world list comes with the stop state (MpStepListed)");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int w = blockIdx.x * ((int)blockDim.x >> 6) + wave;
+  const int i = blockIdx.x * ((int)blockDim.x >> 6) + wave;
   uint8_t* tables = smem;
   const int per_world = t.world_stride + scratch_bytes(t) + extra;
   uint8_t* mine = smem + tables_bytes(t) + wave * per_world;
-  const bool live = w < args0.num_worlds;
-  World wd = make_world(t, mine, tables, mine + t.world_stride, args0.state, live ? w : 0, lane);
+  bool live;
+  int w;
+  if constexpr (Listed) {
+    live = i < la->count;
+    w = 0;
+    if (live) {
+      w = __builtin_amdgcn_readfirstlane(la->worlds[i]);
+      if (w < 0 || w >= args0.num_worlds) {
+        report_entry(t, lane, i, w, kFaultListedWorld);
+        live = false;
+        w = 0;
+      } else {
+        const unsigned long long tag = listed_tag(la->generation, i);
+        const unsigned long long own = la->claim[w];
+        const uint32_t own_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)own);
+        const uint32_t own_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(own >> 32));
+        if ((((unsigned long long)own_hi << 32) | own_lo) != tag) {
+          report_entry(t, lane, i, w, kFaultListedRepeat);
+          live = false;
+          w = 0;
+        }
+      }
+    }
+  } else {
+    w = i;
+    live = w < args0.num_worlds;
+  }
+  const long long d = Listed ? (long long)i - (long long)w : 0;
+  World wd = make_world(t, mine, tables, mine + t.world_stride, args0.state, (Listed || live) ? w : 0, lane);
   wd.next_orders = args0.next_orders;
   const int K = m.steps;
   const bool record_rows = r.layer || sp.row || hp.row;
@@ -86,12 +137,12 @@ __device__ inline void run_many_masked(const DevTables& t, const Tables& c, cons
   bool any = false;              // is there an active step at all?
   Sites sites = Sites();
   if (live) {
-    act_id = fetch_action_id(t, args0.actions, args0.mode, w, lane);
+    act_id = fetch_action_id(t, args0.actions, args0.mode, i, lane);
     if (column) {
       for (int j = 0, k = lane; k < K; ++j, k += 64)
-        bits |= (unsigned long long)(am.active[(long long)k * am.step + w] != 0) << j;
+        bits |= (unsigned long long)(am.active[(long long)k * am.step + i] != 0) << j;
     } else {
-      bits = (!Until || am.active) ? am.active[w] != 0 : 1;
+      bits = (!Until || am.active) ? am.active[i] != 0 : 1;
     }
     if constexpr (Until)   // (stopped on entry: a world with no active step, whatever the mask says)
       if (um->stopped && __builtin_amdgcn_readfirstlane((int)um->stopped[w]) != 0) bits = 0;
@@ -108,8 +159,8 @@ __device__ inline void run_many_masked(const DevTables& t, const Tables& c, cons
   if (!live) return;
   if constexpr (Until) {
     if (!any) {   // (nothing runs: the counts are known now)
-      if (um->ran && lane == 0) um->ran[w] = 0;
-      if (um->returns && lane < t.P) um->returns[(size_t)w * t.P + lane] = 0.0;
+      if (um->ran && lane == 0) um->ran[i] = 0;
+      if (um->returns && lane < t.P) um->returns[(size_t)i * t.P + lane] = 0.0;
     }
   }
   if (!any && !record_rows) {
@@ -118,10 +169,10 @@ __device__ inline void run_many_masked(const DevTables& t, const Tables& c, cons
     const WorldTail* gt = reinterpret_cast<const WorldTail*>(wd.gw + t.grid_pad);
     if (!__builtin_amdgcn_readfirstlane((int)gt->started)) return;
     for (int k = 0; k < K; ++k) {
-      const StepOutputs to = outputs_of_row(args0.out, m, r, k);
+      const StepOutputs to = outputs_of_row(args0.out, m, r, k, d, t.P);
       carry_five(t, m, to, args0.out, w, lane);
       carry_fin(t, r, to, args0.out, w, lane);
-      copy_level_rows(r, k, w, lane);
+      copy_level_rows(r, k, w, i, lane);
     }
     return;
   }
@@ -138,7 +189,7 @@ __device__ inline void run_many_masked(const DevTables& t, const Tables& c, cons
   for (int k = 0; k < K; ++k) {
     int next_id = 0;
     if (k + 1 < K)
-      next_id = fetch_action_id(t, args0.actions + (long long)(k + 1) * m.actions_step, args0.mode, w, lane);
+      next_id = fetch_action_id(t, args0.actions + (long long)(k + 1) * m.actions_step, args0.mode, i, lane);
     if constexpr (Until) {
       if (owing) {   // the step before's reward, loaded behind that step
         ret = __dadd_rn(ret, __dmul_rn(g, owed));
@@ -163,7 +214,7 @@ __device__ inline void run_many_masked(const DevTables& t, const Tables& c, cons
     wd.lane = lane_k;
     const WorldTail* tl = reinterpret_cast<const WorldTail*>(wd.rec + t.grid_pad);
     const StepOutputs prev = args.out;   // row k - 1, or the in-place buffers
-    args.out = outputs_of_row(args0.out, m, r, k);
+    args.out = outputs_of_row(args0.out, m, r, k, d, t.P);
     if (on) {
       // (dispatch()'s frozen path, which this step is going to take)
       const bool frozen = __builtin_amdgcn_readfirstlane((int)(tl->started && tl->done)) && !args0.auto_reset;
@@ -200,20 +251,20 @@ __device__ inline void run_many_masked(const DevTables& t, const Tables& c, cons
     if (sp.row || hp.row || r.layer || r.n_level) {
       wsync();   // the record in LDS is final; the step's stores to the level kinds come before the loads below
       if (__builtin_amdgcn_readfirstlane((int)tl->started)) {
-        copy_level_rows(r, k, w, lane_k);
+        copy_level_rows(r, k, w, i, lane_k);
         if (r.layer) {
           StepOutputs lo = args0.out;
           lo.layer = reinterpret_cast<int32_t*>(r.layer + (long long)k * r.layer_bytes);
           lo.layer_lut = r.layer_lut;
-          write_layer(t, wd.rec, lo, w, lane_k);
+          write_layer(t, wd.rec, lo, i, lane_k);
         }
         if (sp.row)
-          store_record(t, wd.rec, sp.row + (long long)k * sp.bytes + (size_t)w * t.world_stride, lane_k);
+          store_record(t, wd.rec, sp.row + (long long)k * sp.bytes + (size_t)i * t.world_stride, lane_k);
         if (hp.row) {
           const uint64_t sum =
               state_hash::wave_sum(state_hash::hash_share(hp.mask, wd.rec, t.world_stride >> 4, lane_k, 64));
           if (lane_k == 0)
-            reinterpret_cast<uint64_t*>(hp.row + (long long)k * hp.bytes)[w] = state_hash::fmix64(sum);
+            reinterpret_cast<uint64_t*>(hp.row + (long long)k * hp.bytes)[i] = state_hash::fmix64(sum);
         }
       }
     }
@@ -222,8 +273,8 @@ __device__ inline void run_many_masked(const DevTables& t, const Tables& c, cons
   if (!any) return;   // (only the rows wanted the record: the in-place buffers are what they were)
   if constexpr (Until) {
     if (owing) ret = __dadd_rn(ret, __dmul_rn(g, owed));
-    if (um->ran && lane == 0) um->ran[w] = n_ran;
-    if (um->returns && lane < t.P) um->returns[(size_t)w * t.P + lane] = ret;
+    if (um->ran && lane == 0) um->ran[i] = n_ran;
+    if (um->returns && lane < t.P) um->returns[(size_t)i * t.P + lane] = ret;
     if (um->stopped && halted != 0 && lane == 0) um->stopped[w] = (uint8_t)halted;
   }
   wsync();

@@ -1,6 +1,7 @@
 // step_rows.h — the per-step rows of the K-step kernels, device side: where row k of a kind lies,
 // what a row holds when a step does not write the kind (the carry rule), and the copy of the level
-// kinds behind a step.  run_many_masked (step_masked.h) uses all of them.  run_many
+// kinds behind a step.  run_many_masked (step_masked.h) uses all of them, under a world list with
+// a shift and a column that tell the wave's world from its place in the rows.  run_many
 // (step_many.hip) uses row_of ONLY: it keeps the frozen carry, the level copy and the final copy
 // written out, a second copy of the carry rule, because its row families ran slower with the calls
 // (profiles/r23_kstep_refactor.md).  A change to carry_fin, carry_five or copy_level_rows is made
@@ -67,24 +68,31 @@
 
 namespace stepk {
 
+// Row k of a kind, or the in-place buffer where no rows are asked for.  `shift` (bytes) is for a wave
+// whose world w writes column i != w of the rows (a world list, step_masked.h): the level code
+// (step_world, finish(), load_world) and the carry helpers below index every output by w, so the
+// row's base is moved by (i - w) worlds' elements and element w of it is column i.  The in-place
+// buffers stay by world.
 template <class T>
-__device__ inline T* row_of(uint8_t* base, long long bytes, int k, T* in_place) {
-  return base ? reinterpret_cast<T*>(base + (long long)k * bytes) : in_place;
+__device__ inline T* row_of(uint8_t* base, long long bytes, int k, T* in_place, long long shift = 0) {
+  return base ? reinterpret_cast<T*>(base + (long long)k * bytes + shift) : in_place;
 }
 
 // The outputs of step k: row k of every kind of the five and of r.fin that is asked for, the
-// in-place buffer of the others.
-__device__ inline StepOutputs outputs_of_row(const StepOutputs& in_place, const ManyArgs& m, const StepRows& r, int k) {
+// in-place buffer of the others.  d = i - w worlds (row_of's shift; P players a world), 0 where
+// world w is column w.
+__device__ inline StepOutputs outputs_of_row(const StepOutputs& in_place, const ManyArgs& m, const StepRows& r, int k,
+                                             long long d = 0, int P = 0) {
   StepOutputs o = in_place;
-  o.reward = row_of(m.row[0], m.row_bytes[0], k, in_place.reward);
-  o.collective = row_of(m.row[1], m.row_bytes[1], k, in_place.collective);
-  o.step_type = row_of(m.row[2], m.row_bytes[2], k, in_place.step_type);
-  o.discount = row_of(m.row[3], m.row_bytes[3], k, in_place.discount);
-  o.events = row_of(m.row[4], m.row_bytes[4], k, in_place.events);
-  o.ready = row_of(r.fin[0], r.fin_bytes[0], k, in_place.ready);
-  o.aux0 = row_of(r.fin[1], r.fin_bytes[1], k, in_place.aux0);
-  o.position = row_of(r.fin[2], r.fin_bytes[2], k, in_place.position);
-  o.orientation = row_of(r.fin[3], r.fin_bytes[3], k, in_place.orientation);
+  o.reward = row_of(m.row[0], m.row_bytes[0], k, in_place.reward, d * P * 8);
+  o.collective = row_of(m.row[1], m.row_bytes[1], k, in_place.collective, d * 8);
+  o.step_type = row_of(m.row[2], m.row_bytes[2], k, in_place.step_type, d * 4);
+  o.discount = row_of(m.row[3], m.row_bytes[3], k, in_place.discount, d * 8);
+  o.events = row_of(m.row[4], m.row_bytes[4], k, in_place.events, d * (MP_EVENT_ROWS * 16));
+  o.ready = row_of(r.fin[0], r.fin_bytes[0], k, in_place.ready, d * P * 8);
+  o.aux0 = row_of(r.fin[1], r.fin_bytes[1], k, in_place.aux0, d * P * 8);
+  o.position = row_of(r.fin[2], r.fin_bytes[2], k, in_place.position, d * P * 8);
+  o.orientation = row_of(r.fin[3], r.fin_bytes[3], k, in_place.orientation, d * P * 4);
   return o;
 }
 
@@ -127,12 +135,13 @@ __device__ inline void carry_five(const DevTables& t, const ManyArgs& m, const S
   }
 }
 
-// The level kinds of world w (StepRows::level): the in-place buffer -> row k.
-__device__ inline void copy_level_rows(const StepRows& r, int k, int w, int lane) {
-  for (int i = 0; i < r.n_level; ++i) {
-    const long long n = r.level[i].count;
-    const double* src = r.level[i].src + (size_t)w * n;
-    double* dst = reinterpret_cast<double*>(r.level[i].row + (long long)k * r.level[i].bytes) + (size_t)w * n;
+// The level kinds of world w (StepRows::level): world w's slice of the in-place buffer -> column
+// `col` of row k (col = w but under a world list).
+__device__ inline void copy_level_rows(const StepRows& r, int k, int w, int col, int lane) {
+  for (int l = 0; l < r.n_level; ++l) {
+    const long long n = r.level[l].count;
+    const double* src = r.level[l].src + (size_t)w * n;
+    double* dst = reinterpret_cast<double*>(r.level[l].row + (long long)k * r.level[l].bytes) + (size_t)col * n;
     for (int j = lane; j < n; j += 64) dst[j] = src[j];
   }
 }

@@ -2,8 +2,8 @@
 // masked request of step_active.hip in which a world that ends its episode, or is paid, stops
 // there for the rest of the launch, and which hands back how many steps each world ran and the
 // discounted sum of its rewards over them.  The body is run_many_masked<.., Until = true>
-// (step_masked.h).  A unit of its own: every other family keeps one caller of each level's step in
-// its unit (step_starts.hip says why).
+// (step_masked.h), which step_listed.hip's kernels share.  A unit of its own: every other family
+// keeps one caller of each level's step in its unit (step_starts.hip says why).
 #include "step_levels.h"
 #include "step_masked.h"
 

@@ -169,6 +169,44 @@ def test_mask_until_returns_and_stopped_against_the_twin(name):
   _close(a, b)
 
 
+@pytest.mark.parametrize("name", ["clean_up", R.MATRIX])
+def test_an_entry_that_runs_nothing_carries_its_rows_to_its_own_column(name):
+  """Eight worlds, worlds = [5, 2, 7], K = 3, entry 1's column of the mask all zero, and no row that
+  needs the record (the five kinds, the level's kinds of READY_TO_SHOOT, AUX0, POSITION and
+  ORIENTATION, and on the matrix pack one level kind): the wave of entry 1 loads no record and writes
+  column 1 of every row from world 2's in-place buffers — where the shifted row bases and the level
+  copy's column meet with no step run."""
+  n, worlds, steps = 8, [5, 2, 7], 3
+  obs = _obs_kinds(name)
+  fin = tuple(k for k in (E.OBS_READY_TO_SHOOT, E.OBS_AUX0, E.OBS_POSITION, E.OBS_ORIENTATION) if k in obs)
+  level = tuple(k for k in (E.OBS_INTERACTION_REWARDS,) if k in obs)
+  assert fin and (level or name != R.MATRIX), (name, obs)
+  a, b = [engine.Engine(R.pack(name), n, device=0, debug_observations=True) for _ in range(2)]
+  A = torch.from_numpy(R.actions(a.P, a.num_actions, n=n)).to(a.device)
+  for e in (a, b):
+    e.reset()
+    e.step_many(A[:3])           # (the in-place buffers hold something to carry)
+  before = _snapshot(a, obs)
+  idx = torch.tensor(worlds, device=a.device)
+  mine = A[3:3 + steps, idx].contiguous()
+  active = torch.ones((steps, 3), dtype=torch.uint8, device=a.device)
+  active[:, 1] = 0
+  full = torch.zeros_like(A[:steps])
+  full[:, idx] = mine
+  mask = torch.zeros((steps, n), dtype=torch.uint8, device=a.device)
+  mask[:, idx] = active
+  got = a.step_many(mine, worlds=worlds, active=active, events=True, observations=fin + level)
+  ref = b.step_many(full, active=mask, events=True, observations=fin + level)
+  assert set(got) == set(ref) and all(key in got for key, _ in _keys(fin + level)), (name, sorted(map(str, got)))
+  _gathered(got, ref, worlds, name)
+  for key, _ in _keys(fin + level):     # (and without the twin: every row of entry 1 is world 2's buffer)
+    for k in range(steps):
+      _same(got[key][k][1:2], before[key][2:3], key, (name, "carried", k))
+  _same_engines(a, b, obs, name)
+  _untouched(a, before, obs, [0, 1, 2, 3, 4, 6], name)
+  _close(a, b)
+
+
 def test_seventy_steps_with_lengths_through_the_substrate():
   """K = 70 by repeat=70: steps past 64 are the second bit of a lane's part of the mask column."""
   config = substrate.get_config(COMMONS)
