@@ -1059,6 +1059,91 @@ typedef struct {
   uint64_t reserved2[3];   /* 0 */
 } MpEgoPlanes;
 
+/* Whom does a player see, and whom could it zap?  EGO_LAYER, the view hashes and the planes
+ * describe CELLS; MpAvatarIds describes PLAYERS: the reference's per-avatar observations
+ * AVATAR_IDS_IN_VIEW (AvatarIdsInViewObservation, avatar_library.lua:1204-1264) and
+ * AVATAR_IDS_IN_RANGE_TO_ZAP (AvatarIdsInRangeToZapObservation, :1267-1315, on
+ * Zapper:getWhoZappable, :780-824), two int32 0/1 vectors over the player slots, worked out from
+ * the record alone.  Attention and communication masks, opponent-model targets, "is a zap worth its
+ * cooldown", and counting who could have zapped whom and did not.  Rides mp_snapshot, recognised by
+ * its size: `bytes` = sizeof(MpAvatarIds), `host_buf` a HOST MpAvatarIds with struct_size set to
+ * it.  include/mp_avatar_ids.h wraps it as inline C functions.
+ *
+ * The definition.  P is the player count; a record's head is ax, ay, aori, aalive.
+ *   IN_VIEW[p][q] = 1 iff viewer p is alive, avatar q is alive, and some cell (vx, vy) of p's
+ *     window lies over q's cell: the cell EGO_LAYER (MpEgoLayer) shows there, by the turned offset
+ *     and the torus wrap.  It is 1 at q == p for a living viewer (the reference's rectangle holds
+ *     the avatar's own cell), and 0 or 1 even where a torus smaller than the window shows q more
+ *     than once.  A dead viewer's row is all 0 (the reference leaves that case undefined; the
+ *     facing planes of MpEgoPlanes do the same).  Only the avatar layer counts: in every committed
+ *     pack avatars live on avatar_layer alone, so the reference's `layers` argument has no
+ *     counterpart.
+ *   IN_RANGE[p][q] is the reference's rays, literally, on the avatar's own layer.  The pack's zap
+ *     footprint (the Zapper's beamLength and beamRadius) is a list of cells (lat, fw, pred): cell j
+ *     of living p lies at pos + lat * right(ori) + fw * forward(ori), under the map's topology as a
+ *     step's beam applies it.  A cell STOPS its ray when it lies off the map or when its byte of
+ *     the avatar_layer plane is not 0.  Cell j is REACHED when it is on the map and no cell of
+ *     pred(j) stops.  IN_RANGE[p][q] = 1 iff some reached cell holds q's avatar state.  Readiness
+ *     plays no part: a cooldown does not enter.  BLOCKERS ON OTHER LAYERS PLAY NO PART either:
+ *     getWhoZappable casts on self.gameObject:getLayer() only.  This is the reference's
+ *     observation, not a prediction of the next beam on levels whose beam blockers lie elsewhere.
+ *     A dead p's row is all 0 (:1289-1291).  A level without a Zapper (coins, the kitchens, the
+ *     matrix games, coop_mining, gift_refinements) refuses dst_zap with MP_ERR_INVALID, naming the
+ *     level's family; IN_VIEW works on every level.
+ *
+ * `dst` takes IN_VIEW and `dst_zap` IN_RANGE; either may be NULL, not both.  One launch writes
+ * both.
+ * MP_AVATARIDS_DRAW: element i belongs to row rows[i] (NULL: row i) of `bank` (device uint8
+ *   [bank_rows][S], 16-byte aligned); a NULL bank means the engine's own worlds as they are now
+ *   (rows[] are then world indices, bank_rows is ignored, the engine must have been reset).
+ *   players == NULL: each destination is int32 [count][P][P], row p the vector of viewer p;
+ *   otherwise players is device int32 [count] and each is int32 [count][P], the vector of player
+ *   players[i] of row rows[i].  Rows and (row, player) pairs may repeat and `count` has no
+ *   relation to the engine's N.  Destinations are 4-byte aligned.  Stream-ordered, no
+ *   synchronisation, no allocation; nothing of the engine's is written.  A rows[i] that is no row
+ *   (no world) or a players[i] outside [0, P) is never used as an index: element i of both
+ *   destinations is left as it was — every such element — and the next synchronising call returns
+ *   MP_ERR_INVALID once, naming MpAvatarIds, rows[i] or players[i] and the value (of several such
+ *   indices one is reported); the engine stays usable.
+ * MP_AVATARIDS_REGISTER: `dst` and `dst_zap` name device int32 [N][P][P] tensors (slots == 0), or
+ *   rings: slot s is at + s * slot_stride bytes of each, and `slots` must equal the engine's ring
+ *   slots (mp_bind_output_ring), as MP_EGO_REGISTER.  While registered, every submission (reset,
+ *   step, step_fields, every K-step request, a load) is followed on the same stream by ONE launch
+ *   that rewrites them from the records, into the tensors or into the ring slot that submission
+ *   wrote (behind the planes' launch).  mp_tune's probe submissions do not write them.  Both NULL
+ *   clears the registration: the engine's launches are then what they were.  An engine without a
+ *   registration issues exactly the launches it issued before.
+ * MP_AVATARIDS_HOST (eng == NULL; pack, pack_len, cfg as for mp_create): MP_AVATARIDS_DRAW of HOST
+ *   rows into HOST destinations, computed by the library without a device (bank must not be
+ *   NULL).  A bad index returns MP_ERR_INVALID at once, naming it; the elements before it are
+ *   written.
+ *
+ * Refused before any launch, the engine left as it was — MP_ERR_INVALID: what MpEgoLayer refuses,
+ * for either destination (dst_zap_bytes is dst_zap's size); dst_zap on a level without a Zapper.
+ * MP_ERR_UNSUPPORTED: a record whose avatar_layer plane does not fit one wave's share of the LDS. */
+enum { MP_AVATARIDS_DRAW = 1, MP_AVATARIDS_REGISTER = 2, MP_AVATARIDS_HOST = 3 };
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(MpAvatarIds) */
+  int32_t op;              /* MP_AVATARIDS_* */
+  uint64_t fingerprint;    /* in (draw, host): the rows' */
+  const void* bank;        /* uint8 [bank_rows][S]; NULL (draw): the engine's worlds */
+  const int32_t* rows;     /* int32 [count], NULL = rows 0 .. count - 1 */
+  const int32_t* players;  /* int32 [count], NULL = every viewer of each row */
+  void* dst;               /* IN_VIEW, int32: see the op; NULL: not asked for */
+  uint64_t dst_bytes;
+  int32_t bank_rows;
+  int32_t count;
+  uint64_t slot_stride;    /* MP_AVATARIDS_REGISTER with a ring: bytes between two slots (of both) */
+  int32_t slots;           /* MP_AVATARIDS_REGISTER: 0, or the ring's slots */
+  int32_t reserved;        /* 0 */
+  const void* pack;        /* MP_AVATARIDS_HOST */
+  uint64_t pack_len;
+  const MpConfig* cfg;
+  void* dst_zap;           /* IN_RANGE, int32, the shape of dst; NULL: not asked for */
+  uint64_t dst_zap_bytes;
+  uint64_t reserved2[3];   /* 0 */
+} MpAvatarIds;
+
 /* Action sequences: K steps of every world in ONE submission, bit-identical to K calls of the
  * single-step entry points (mp_step, or mp_step_fields with fields = 1) with the same actions,
  * which also hands back the transition of every one of the K steps.  For planners that fork a
@@ -1709,7 +1794,7 @@ int mp_box_fill(MpEngine* eng, MpObsKind kind, int32_t reps, MpBoxFill* out);
  * rows[], 8 an MpStatesView's players[], 11 an MpEgoLayer's rows[], 12 an MpEgoLayer's players[], 13 an
  * MpViewHash's rows[], 14 an MpViewHash's players[], 15 an MpEgoPlanes' rows[], 16 an MpEgoPlanes'
  * players[], 17 an entry of an MpEgoPlanes' device class table (word 9 = the id + 1, word 10 = the
- * entry) (9 and 10 are MpStepListed's worlds[])
+ * entry), 18 an MpAvatarIds' rows[], 19 an MpAvatarIds' players[] (9 and 10 are MpStepListed's worlds[])
  * — whose three words belong together); of several such reports
  * of one launch the three words may belong to different ones.  Words 12-15: the refused row of a checked load once more, claimed by ONE
  * refused world of the launch (word 12 = world + 1, 13 = the row, 14 = the rule, 15 = the offset

@@ -27,13 +27,14 @@ LIB_PATH = os.path.join(LIB_DIR, "libmp_engine.so")
 # engine with registered episode statistics, which includes no step header; ego_layer.hip: the
 # EGO_LAYER draw and the launch behind every submission of an engine with the leaf registered;
 # view_hash.hip: the hash of every player's view, likewise a draw and a launch behind every submission;
-# ego_planes.hip: the class and facing planes of every player's view, likewise; these three take what they
+# ego_planes.hip: the class and facing planes of every player's view, likewise; avatar_ids.hip: whom every player
+# sees and could zap, likewise; these four take what they
 # share — the staged record, the launch plan, the host twin's loop — from view_unit.h.  The six step units take the nine levels from
 # step_levels.h and the K-step ones their row helpers from step_rows.h)
-SOURCES = ("mp_engine.hip", "pack_decode.hip", "step_kernels.hip", "step_starts.hip", "step_many.hip", "step_active.hip", "step_until.hip", "step_listed.hip", "state_obs.hip", "state_view.hip", "state_check.hip", "state_hash.hip", "episode_stats.hip", "ego_layer.hip", "view_hash.hip", "ego_planes.hip", "frame.hip", "frame_wpool2.hip",
+SOURCES = ("mp_engine.hip", "pack_decode.hip", "step_kernels.hip", "step_starts.hip", "step_many.hip", "step_active.hip", "step_until.hip", "step_listed.hip", "state_obs.hip", "state_view.hip", "state_check.hip", "state_hash.hip", "episode_stats.hip", "ego_layer.hip", "view_hash.hip", "ego_planes.hip", "avatar_ids.hip", "frame.hip", "frame_wpool2.hip",
            "frame_wpool4.hip", "frame_wpool8.hip", "frame_stock.hip")
 HEADERS = ("mp_common.h", "stock.h", "stock_clean_up.h", "pack_decode.h", "frame_kernel.h", "frame_wpool.h", "step_common.h", "step_clean_up.h", "step_commons.h",
-           "step_territory.h", "step_coins.h", "step_matrix.h", "step_coop.h", "step_gift.h", "step_cook.h", "step_mushroom.h", "step_load.h", "step_one.h", "step_levels.h", "step_rows.h", "step_masked.h", "step_many.h", "step_until.h", "step_listed.h", "state_obs.h", "state_obs_rules.h", "state_view.h", "state_check.h", "state_hash.h", "episode_stats.h", "ego_layer.h", "view_hash.h", "ego_planes.h", "view_unit.h", "../../include/mp_engine.h",
+           "step_territory.h", "step_coins.h", "step_matrix.h", "step_coop.h", "step_gift.h", "step_cook.h", "step_mushroom.h", "step_load.h", "step_one.h", "step_levels.h", "step_rows.h", "step_masked.h", "step_many.h", "step_until.h", "step_listed.h", "state_obs.h", "state_obs_rules.h", "state_view.h", "state_check.h", "state_hash.h", "episode_stats.h", "ego_layer.h", "view_hash.h", "ego_planes.h", "avatar_ids.h", "view_unit.h", "../../include/mp_engine.h",
            "../../include/mp_pack.h", "exports.map")
 ARCH = "gfx950"
 

@@ -34,6 +34,7 @@
 #include "ego_layer.h"
 #include "view_hash.h"
 #include "ego_planes.h"
+#include "avatar_ids.h"
 
 // frame.hip
 constexpr int kFaultWords = 64 + 4 * 16 * 64 * 2;   // fault words + the timeline build's log
@@ -193,9 +194,10 @@ struct MpEngine {
   };
   // ego: the EGO_LAYER leaf, int32 [N][P][VH][VW][L] (an MpEgoLayer request; ego_layer.h); vh: the
   // view hashes, u64 [N][P] (MpViewHash; view_hash.h); ep: the class and facing planes, uint8
-  // [N][P][C'][VH][VW] (MpEgoPlanes; ego_planes.h).  mp_tune's probes write none of them
-  // (ring_hold, layer_hold).
-  ViewRegistration ego, vh, ep;
+  // [N][P][C'][VH][VW] (MpEgoPlanes; ego_planes.h); av and avz: AVATAR_IDS_IN_VIEW and
+  // AVATAR_IDS_IN_RANGE_TO_ZAP, int32 [N][P][P] each, written by one launch (MpAvatarIds;
+  // avatar_ids.h).  mp_tune's probes write none of them (ring_hold, layer_hold).
+  ViewRegistration ego, vh, ep, av, avz;
   int32_t num_layer_ids = 0;   // 1 + the largest id of d_layer_lut: the length of a class table
   bool viewing(const ViewRegistration& v) const { return v.dst && !ring_hold && !layer_hold; }
   // The engine's choice (MpConfig.unfused = 0): one launch, always.  (Round 2 drew
@@ -451,6 +453,12 @@ int sync_and_check(MpEngine* e, const char* who) {
       return fail(MP_ERR_INVALID,
                   "%s: MpEgoPlanes: classes[%u] = %d is outside [-1, num_classes); the entry counted as -1",
                   who, at, (int)index);
+    if (what == kFaultAvatarIdsRow || what == kFaultAvatarIdsPlayer)
+      return fail(MP_ERR_INVALID,
+                  "%s: MpAvatarIds: %s[%u] = %d is %s; element %u of the destination was left as it was",
+                  who, what == kFaultAvatarIdsRow ? "rows" : "players", at, (int)index,
+                  what == kFaultAvatarIdsRow ? "not a row of the bank (with no bank: no world of this engine)"
+                                             : "not a player of this engine", at);
     if (what == kFaultListedWorld || what == kFaultListedRepeat)
       return fail(MP_ERR_INVALID,
                   "%s: MpStepListed: worlds[%u] = %d %s; the entry ran nothing and element %u of every per-call "
@@ -476,6 +484,31 @@ int sync_and_check(MpEngine* e, const char* who) {
                        "left as it was", who, at, (int)index, at);
   }
   return MP_OK;
+}
+
+// The level's Zapper (avatar_library.lua:570-763), NULL on a level without one, and the name of
+// the level's family for the refusal.
+const ZapRules* zap_rules_of(const SubstrateTables& sub) {
+  switch (sub.substrate) {
+    case MPK_SUBSTRATE_CLEAN_UP: return &sub.cu.zap;
+    case MPK_SUBSTRATE_COMMONS_HARVEST: return &sub.ch.zap;
+    case MPK_SUBSTRATE_TERRITORY: return &sub.tr.zap;
+    case MPK_SUBSTRATE_EXTERNALITY_MUSHROOMS: return &sub.em.zap;
+    default: return nullptr;
+  }
+}
+const char* family_name(const SubstrateTables& sub) {
+  static const char* const kNames[] = {"?", "clean_up", "commons_harvest", "territory", "coins", "*_in_the_matrix",
+                                       "coop_mining", "gift_refinements", "collaborative_cooking",
+                                       "externality_mushrooms"};
+  return sub.substrate >= 1 && sub.substrate <= 9 ? kNames[sub.substrate] : kNames[0];
+}
+// What an MpAvatarIds launch has of the pack: where the avatar_layer plane lies, and (with a
+// Zapper) the footprint and the states' avatars (`sinfo`: the step tables' first 256 words).
+void avatar_ids_tables(avatar_ids::Args* a, const DevTables& t, const ZapRules* zap, const uint32_t* sinfo) {
+  a->plane_at = t.avatar_layer * t.H * t.W;
+  a->sinfo = sinfo;
+  if (zap) a->shape = zap->shape;
 }
 
 // Draw-only launch: the views of the records as they are.
@@ -566,7 +599,8 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
     HIP_TRY(hipGetLastError());
   }
   // the registered views: every world's, rewritten from the records this submission left
-  if (!e->viewing(e->ego) && !e->viewing(e->vh) && !e->viewing(e->ep)) return MP_OK;
+  if (!e->viewing(e->ego) && !e->viewing(e->vh) && !e->viewing(e->ep) && !e->viewing(e->av) && !e->viewing(e->avz))
+    return MP_OK;
   const ego_layer::Window g = ego_layer::window_of(e->t);
   auto worlds = [&](auto* a, const MpEngine::ViewRegistration& v) {   // what the three launches share
     a->g = g;
@@ -596,6 +630,15 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
     a.classes = e->ep.classes; a.num_ids = e->num_layer_ids;
     a.num_classes = e->ep.num_classes; a.facing = e->ep.facing;
     ego_planes::launch(a, ego_planes::plan_of(g, ego_planes::planes_of(a), e->N, e->num_cus), e->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  if (e->viewing(e->av) || e->viewing(e->avz)) {   // whom every viewer sees and could zap
+    avatar_ids::Args a = {};
+    worlds(&a, e->av);
+    a.dst = (int32_t*)(e->av.dst ? e->av.slot(slot) : nullptr);
+    a.dst_zap = (int32_t*)(e->avz.dst ? e->avz.slot(slot) : nullptr);
+    avatar_ids_tables(&a, e->t, zap_rules_of(e->sub), (const uint32_t*)e->t.step_blob);
+    avatar_ids::launch(a, avatar_ids::plan_of(g, a.plane_at, e->N, e->num_cus), e->stream);
     HIP_TRY(hipGetLastError());
   }
   return MP_OK;
@@ -1208,6 +1251,8 @@ int plan_views(MpEngine* e, const MpDevOptions* dev) {
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the EGO_LAYER kernels failed: %d", rc);
   if (int rc = view_hash::prepare())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the view-hash kernels failed: %d", rc);
+  if (int rc = avatar_ids::prepare())
+    return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the avatar-ids kernels failed: %d", rc);
   if (int rc = ego_planes::prepare())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the ego-planes kernels failed: %d", rc);
   if (int rc = prepare_step_starts())
@@ -2593,8 +2638,8 @@ static int episode_stats_request(MpEngine* e, const MpEpisodeStats& r) {
   return MP_OK;
 }
 
-// The requests about every viewer's window — MpEgoLayer, MpViewHash, MpEgoPlanes (include/mp_engine.h;
-// carried by mp_snapshot; `e` is NULL for the host form) — are one front and three tails.  Each
+// The requests about every viewer's window — MpEgoLayer, MpViewHash, MpEgoPlanes, MpAvatarIds
+// (include/mp_engine.h; carried by mp_snapshot; `e` is NULL for the host form) — are one front and four tails.  Each
 // draws from bank rows or from the engine's worlds (one launch), registers or clears the tensor
 // behind every submission (no launch), or applies its function to host rows; everything is
 // checked first.  Their structs begin alike, and the front reads them through that beginning:
@@ -2623,8 +2668,11 @@ enum { VIEW_DRAW = 1, VIEW_REGISTER = 2, VIEW_HOST = 3 };
    MP_VIEW_FIELD(T, bank_rows) && MP_VIEW_FIELD(T, count) && MP_VIEW_FIELD(T, slot_stride) &&                  \
    MP_VIEW_FIELD(T, slots) && MP_VIEW_FIELD(T, pack) && MP_VIEW_FIELD(T, pack_len) && MP_VIEW_FIELD(T, cfg) && \
    sizeof(T) >= sizeof(ViewRequest))
-static_assert(MP_VIEW_PREFIX(MpEgoLayer) && MP_VIEW_PREFIX(MpViewHash) && MP_VIEW_PREFIX(MpEgoPlanes),
-              "MpEgoLayer, MpViewHash and MpEgoPlanes share their leading fields");
+static_assert(MP_VIEW_PREFIX(MpEgoLayer) && MP_VIEW_PREFIX(MpViewHash) && MP_VIEW_PREFIX(MpEgoPlanes) &&
+                  MP_VIEW_PREFIX(MpAvatarIds),
+              "MpEgoLayer, MpViewHash, MpEgoPlanes and MpAvatarIds share their leading fields");
+static_assert(MP_AVATARIDS_DRAW == VIEW_DRAW && MP_AVATARIDS_REGISTER == VIEW_REGISTER && MP_AVATARIDS_HOST == VIEW_HOST,
+              "and MpAvatarIds the numbers of their ops");
 static_assert(MP_EGO_DRAW == VIEW_DRAW && MP_VIEWHASH_DRAW == VIEW_DRAW && MP_EGOPLANES_DRAW == VIEW_DRAW &&
                   MP_EGO_REGISTER == VIEW_REGISTER && MP_VIEWHASH_REGISTER == VIEW_REGISTER &&
                   MP_EGOPLANES_REGISTER == VIEW_REGISTER && MP_EGO_HOST == VIEW_HOST &&
@@ -3004,12 +3052,84 @@ static int ego_planes_request(MpEngine* e, MpEgoPlanes* out) {
   return MP_OK;
 }
 
-// mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes): the 17.
+// Two destinations of one shape, either may be absent: the front's checks run once for each that
+// is there, on a copy of the request's beginning that names it as `dst`.
+static int avatar_ids_request(MpEngine* e, const MpAvatarIds& r) {
+  static const ViewWords w = {"MpAvatarIds", "MP_AVATARIDS_HOST", "a leaf", "needs", "drawn", "draw"};
+  const char* const kWho = w.who;
+  const ViewRequest q = view_of(&r);
+  if (int rc = view_prologue(e, q, w, sizeof r,
+                             r.reserved == 0 && r.reserved2[0] == 0 && r.reserved2[1] == 0 && r.reserved2[2] == 0))
+    return rc;
+  if (r.op == MP_AVATARIDS_REGISTER && !r.dst && !r.dst_zap) {   // clears the registration: the engine's launches are what they were
+    e->av = e->avz = MpEngine::ViewRegistration{};
+    return MP_OK;
+  }
+  if (!r.dst && !r.dst_zap) return fail(MP_ERR_INVALID, "%s: NULL dst and NULL dst_zap", kWho);
+  if (((uintptr_t)r.dst | (uintptr_t)r.dst_zap) & 3)
+    return fail(MP_ERR_INVALID, "%s: dst %p and dst_zap %p must be 4-byte aligned", kWho, r.dst, r.dst_zap);
+  ViewTables v;
+  if (int rc = view_tables(e, q, &v)) return rc;
+  const SubstrateTables& sub = e ? e->sub : v.h.d.sub;
+  const ZapRules* zap = zap_rules_of(sub);
+  if (r.dst_zap && !zap)
+    return fail(MP_ERR_INVALID, "%s: %s has no Zapper: there is no AVATAR_IDS_IN_RANGE_TO_ZAP on this level "
+                "(AVATAR_IDS_IN_VIEW works on every level)", kWho, family_name(sub));
+  if (r.dst_zap && (zap->shape.n < 1 || zap->shape.n > 16))
+    return fail(MP_ERR_UNSUPPORTED, "%s: a zap footprint of %d cells", kWho, zap->shape.n);
+  const ego_layer::Window g = ego_layer::window_of(*v.t);
+  const uint64_t view = (uint64_t)g.P * 4u, world = view * (uint64_t)g.P;
+  if (int rc = view_record_lines(w, *v.t, g)) return rc;
+  if (v.t->avatar_layer < 0 || v.t->avatar_layer >= g.L)
+    return fail(MP_ERR_UNSUPPORTED, "%s: avatar_layer %d is no render plane", kWho, v.t->avatar_layer);
+  ViewRequest qv = q, qz = q;   // the request as IN_VIEW's alone, as IN_RANGE's alone
+  qz.dst = r.dst_zap; qz.dst_bytes = r.dst_zap_bytes;
+  avatar_ids::Args a = {};
+  avatar_ids_tables(&a, *v.t, r.dst_zap ? zap : nullptr,
+                    e ? (const uint32_t*)e->t.step_blob : (const uint32_t*)v.h.d.step_blob.data());
+  if (r.op == MP_AVATARIDS_REGISTER) {
+    uint64_t need;
+    if (r.dst) if (int rc = view_register(e, qv, w, world, 4, &need)) return rc;
+    if (r.dst_zap) if (int rc = view_register(e, qz, w, world, 4, &need)) return rc;
+    const avatar_ids::Plan p = avatar_ids::plan_of(g, a.plane_at, e->N, e->num_cus);
+    if (p.waves < 1)
+      return fail(MP_ERR_UNSUPPORTED, "%s: one wave's avatar plane needs %d B of LDS", kWho, p.lds);
+    e->av = r.dst ? registration_of(qv) : MpEngine::ViewRegistration{};
+    e->avz = r.dst_zap ? registration_of(qz) : MpEngine::ViewRegistration{};
+    return MP_OK;
+  }
+  ViewSource s, sz;
+  if (r.dst) if (int rc = view_source(e, qv, w, v, view, world, &s)) return rc;
+  if (r.dst_zap) if (int rc = view_source(e, qz, w, v, view, world, &sz)) return rc;
+  if (!r.dst) s = sz;
+  view_args(&a, g, q, v, s);
+  a.dst = (int32_t*)r.dst;
+  a.dst_zap = (int32_t*)r.dst_zap;
+  if (r.op == MP_AVATARIDS_HOST) {
+    a.src = (const uint8_t*)r.bank;
+    uint32_t what = 0;
+    const int bad = avatar_ids::host(a, &what);
+    return bad >= 0 ? view_host_fault(q, w, bad, what == kFaultAvatarIdsRow) : MP_OK;
+  }
+  if (r.dst) if (int rc = view_device_source(e, qv, w, s, nullptr, 0)) return rc;
+  if (r.dst_zap) if (int rc = view_device_source(e, qz, w, s, nullptr, 0)) return rc;
+  const avatar_ids::Plan p = avatar_ids::plan_of(g, a.plane_at, r.count, e->num_cus);
+  if (p.waves < 1)
+    return fail(MP_ERR_UNSUPPORTED, "%s: one wave's avatar plane needs %d B of LDS", kWho, p.lds);
+  a.src = s.live ? e->d_state : (const uint8_t*)r.bank;
+  a.fault = e->t.fault;
+  avatar_ids::launch(a, p, e->stream);
+  HIP_TRY(hipGetLastError());
+  return MP_OK;
+}
+
+// mp_snapshot / mp_restore tell their requests apart by size (a snapshot is >= 448 bytes): the 18.
 constexpr size_t kRequestSizes[] = {
     sizeof(MpKernelVariant), sizeof(MpWorldStates), sizeof(MpStatesObserve), sizeof(MpStepMany),
     sizeof(MpStepTrajectory), sizeof(MpStateLayout), sizeof(MpStatesCheck), sizeof(MpStatesHash),
     sizeof(MpEpisodeStarts), sizeof(MpStatesView), sizeof(MpStepActive), sizeof(MpStepUntil),
-    sizeof(MpStepListed), sizeof(MpEpisodeStats), sizeof(MpEgoLayer), sizeof(MpViewHash), sizeof(MpEgoPlanes)};
+    sizeof(MpStepListed), sizeof(MpEpisodeStats), sizeof(MpEgoLayer), sizeof(MpViewHash), sizeof(MpEgoPlanes),
+    sizeof(MpAvatarIds)};
 constexpr bool request_sizes_tell_apart() {
   for (size_t i = 0; i < sizeof kRequestSizes / sizeof kRequestSizes[0]; ++i) {
     if (kRequestSizes[i] >= 448) return false;
@@ -3019,7 +3139,7 @@ constexpr bool request_sizes_tell_apart() {
   return true;
 }
 static_assert(request_sizes_tell_apart(), "two requests of one size, or one the size of a snapshot");
-static_assert(sizeof(MpEgoPlanes) == 160 && sizeof(MpViewHash) == 152 && sizeof(MpEgoLayer) == 128 &&
+static_assert(sizeof(MpAvatarIds) == 144 && sizeof(MpEgoPlanes) == 160 && sizeof(MpViewHash) == 152 && sizeof(MpEgoLayer) == 128 &&
                   sizeof(MpEpisodeStats) == 224 && sizeof(MpEventColumn) == 32 && sizeof(MpStatsBank) == 32 &&
                   sizeof(MpStatesObserve) == 64 && sizeof(MpStateLayout) == 120 && sizeof(MpStatesCheck) == 88 &&
                   sizeof(MpStateField) == 32 && sizeof(MpStatesHash) == 104 && sizeof(MpEpisodeStarts) == 72 &&
@@ -3083,6 +3203,11 @@ int mp_snapshot(MpEngine* e, void* buf, uint64_t bytes) {
   }
   if (buf && bytes == sizeof(MpViewHash)) return view_hash_request(e, (MpViewHash*)buf);   // (num_ids is written back)
   if (buf && bytes == sizeof(MpEgoPlanes)) return ego_planes_request(e, (MpEgoPlanes*)buf);   // (likewise)
+  if (buf && bytes == sizeof(MpAvatarIds)) {
+    MpAvatarIds r;   // (read only: nothing is written back)
+    memcpy(&r, buf, sizeof r);
+    return avatar_ids_request(e, r);
+  }
   if (buf && bytes == sizeof(MpStateLayout)) return state_layout(e, (MpStateLayout*)buf);
   if (buf && bytes == sizeof(MpStatesCheck)) {
     MpStatesCheck r;   // (read only: the verdicts go to r.out)

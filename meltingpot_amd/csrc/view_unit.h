@@ -4,7 +4,8 @@
 // in its share of the LDS — the render planes and the head of the tail (positions, orientations,
 // who is alive) — and the unit's own body works on that.  Here: the LDS layout, the staging loop,
 // the report of a skipped rows[] / players[] index, the launch plan, launch and prepare, and the
-// host twin's element loop.  Included by those three units only.
+// host twin's element loop.  Included by those three units and by avatar_ids.hip,
+// which stages one plane of the record with the same loop.
 #ifndef MP_VIEW_UNIT_H_INTERNAL_
 #define MP_VIEW_UNIT_H_INTERNAL_
 

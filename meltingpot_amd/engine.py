@@ -280,6 +280,7 @@ def states_view_request(L, handle, **fields) -> MpStatesView:
 # mp_snapshot
 MP_EGO_DRAW, MP_EGO_REGISTER, MP_EGO_HOST = 1, 2, 3
 OBS_EGO_LAYER = -1   # no MpObsKind: the Python layers' handle for the leaf where leaves map to kinds
+OBS_AVATAR_IDS = -2  # likewise: "AVATAR_IDS_IN_VIEW" and "AVATAR_IDS_IN_RANGE_TO_ZAP"
 
 
 class MpEgoLayer(ctypes.Structure):
@@ -760,6 +761,54 @@ def ego_planes_host(pack_bytes: bytes, rows, classes, players=None, *, which=Non
                      classes_len=int(cls.size), num_classes=C, facing=int(bool(facing)), dst=out.ctypes.data,
                      dst_bytes=out.nbytes, **src)
   return out
+
+
+# Whom each player sees and whom it could zap (include/mp_engine.h: MpAvatarIds), carried by mp_snapshot
+MP_AVATARIDS_DRAW, MP_AVATARIDS_REGISTER, MP_AVATARIDS_HOST = 1, 2, 3
+
+
+class MpAvatarIds(ctypes.Structure):
+  _fields_ = [("struct_size", ctypes.c_uint32), ("op", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
+              ("bank", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("players", ctypes.c_void_p),
+              ("dst", ctypes.c_void_p), ("dst_bytes", ctypes.c_uint64), ("bank_rows", ctypes.c_int32),
+              ("count", ctypes.c_int32), ("slot_stride", ctypes.c_uint64), ("slots", ctypes.c_int32),
+              ("reserved", ctypes.c_int32), ("pack", ctypes.c_void_p), ("pack_len", ctypes.c_uint64),
+              ("cfg", ctypes.c_void_p), ("dst_zap", ctypes.c_void_p), ("dst_zap_bytes", ctypes.c_uint64),
+              ("reserved2", ctypes.c_uint64 * 3)]
+
+
+def avatar_ids_request(L, handle, op: int, **fields) -> MpAvatarIds:
+  """Runs one MpAvatarIds request on engine `handle` (None: the host form); raises like every call."""
+  return _request(L, handle, MpAvatarIds, (int(op),), fields)
+
+
+def has_zapper(pack_bytes: bytes) -> bool:
+  """Does the pack's level carry the reference's Zapper (clean_up, commons_harvest, territory,
+  externality_mushrooms)?  Without one there is no AVATAR_IDS_IN_RANGE_TO_ZAP."""
+  from . import pack as pack_lib
+  return "zapper_i32" in pack_lib.loads(pack_bytes)
+
+
+def avatar_ids_host(pack_bytes: bytes, rows, players=None, *, which=None, view: bool = True, zap: bool = True,
+                    fingerprint: Optional[int] = None, num_players: int = 0, dev: Optional[Dict[str, int]] = None):
+  """AVATAR_IDS_IN_VIEW and AVATAR_IDS_IN_RANGE_TO_ZAP of host rows (uint8 [M, S] array) by the
+  library's host-only form (MP_AVATARIDS_HOST: the kernels' own functions compiled for the host; no
+  GPU needed).  Returns (in_view, in_range): int32 [R, P, P] each, row p the 0/1 vector of viewer p
+  over the player slots, or [R, P] with `players` (R ints: player players[i] of the i-th row);
+  None in the place of one not asked for (`view`, `zap`).  `which`: the rows, in order, repeats
+  allowed (default: all).  A level without a Zapper raises ValueError for `zap`.  `fingerprint`:
+  the rows' (default: the pack's)."""
+  if not view and not zap:
+    raise ValueError("avatar_ids_host: neither view nor zap is asked for")
+  layout, lead, src, _alive = _view_host_source("avatar_ids_host", "draw", pack_bytes, rows, players, which,
+                                                fingerprint, num_players, dev)
+  out_v = np.zeros(lead + (layout.P,), np.int32) if view else None
+  out_z = np.zeros(lead + (layout.P,), np.int32) if zap else None
+  avatar_ids_request(load_library(), None, MP_AVATARIDS_HOST,
+                     dst=None if out_v is None else out_v.ctypes.data, dst_bytes=0 if out_v is None else out_v.nbytes,
+                     dst_zap=None if out_z is None else out_z.ctypes.data,
+                     dst_zap_bytes=0 if out_z is None else out_z.nbytes, **src)
+  return out_v, out_z
 
 
 # Action sequences (include/mp_engine.h: MpStepMany), carried by mp_restore
@@ -2826,6 +2875,84 @@ class Engine:
                        **self._view_ring(out, ring, int(np.prod(shape))))
     self._ego_planes = (out, cls)
     return out
+
+  @property
+  def has_zapper(self) -> bool:
+    """Whether the level carries a Zapper: without one there is no AVATAR_IDS_IN_RANGE_TO_ZAP."""
+    if getattr(self, "_has_zapper", None) is None:
+      self._has_zapper = has_zapper(self.pack_bytes)
+    return self._has_zapper
+
+  @property
+  def avatar_ids_shape(self) -> Tuple[int, int, int]:
+    """(N, P, P): the shape of AVATAR_IDS_IN_VIEW and of AVATAR_IDS_IN_RANGE_TO_ZAP (int32)."""
+    return (self.N, self.P, self.P)
+
+  def observe_avatar_ids(self, bank=None, rows=None, players=None, view: bool = True, zap: bool = True, out=None,
+                         fingerprint: Optional[int] = None):
+    """(AVATAR_IDS_IN_VIEW, AVATAR_IDS_IN_RANGE_TO_ZAP) — whom each player sees, and whom a zap it
+    fired now could reach — of rows of `bank` (a contiguous uint8 device tensor [M, S]), or of the
+    engine's worlds as they are now (`bank` None; `rows` are then world indices), written from the
+    records by ONE launch.  int32 device tensors [R, P, P], row p the 0/1 vector of viewer p over
+    the player slots; with `players` (R ints) [R, P], the vector of player players[i] of row
+    rows[i].  `view`, `zap`: which of the two to work out; the other's place holds None.  `out`: a
+    pair of tensors (or None) to write.  IN_VIEW: both alive and q's cell under p's window (1 at q
+    == p).  IN_RANGE: the reference's rays on the avatars' own layer — blockers of other layers and
+    the cooldown play no part; a level without a Zapper raises ValueError.  A dead player's row is
+    0.  Nothing of the engine's is written.  A row or player index out of range leaves its element
+    as it was; the next synchronising call raises ValueError.  Enqueued on the current stream."""
+    if not view and not zap:
+      raise ValueError("observe_avatar_ids: neither view nor zap is asked for")
+    count, r, p, src = self._view_source("observe_avatar_ids", "draw", bank, rows, players, fingerprint)
+    shape = (count, self.P, self.P) if p is None else (count, self.P)
+    given = (None, None) if out is None else tuple(out)
+    if len(given) != 2:
+      raise ValueError("observe_avatar_ids: out is a pair (in_view, in_range); None where one is not asked for")
+    t = self._torch
+    out_v = self._out("observe_avatar_ids", given[0], shape, t.int32) if view else None
+    out_z = self._out("observe_avatar_ids", given[1], shape, t.int32) if zap else None
+    self.use_current_stream()
+    avatar_ids_request(self._L, self._h, MP_AVATARIDS_DRAW,
+                       dst=None if out_v is None else out_v.data_ptr(),
+                       dst_bytes=0 if out_v is None else out_v.numel() * 4,
+                       dst_zap=None if out_z is None else out_z.data_ptr(),
+                       dst_zap_bytes=0 if out_z is None else out_z.numel() * 4, **src)
+    self._avatar_ids_args = (bank, r, p, out_v, out_z)   # (kept until the next call: the launch may not have run yet)
+    return out_v, out_z
+
+  def bind_avatar_ids(self, view=None, zap=None):
+    """Registers `view` (AVATAR_IDS_IN_VIEW) and `zap` (AVATAR_IDS_IN_RANGE_TO_ZAP) — contiguous
+    int32 device tensors [N, P, P], or [T, N, P, P] with T the engine's ring slots (`bind_ring`
+    some kind first); either may be None — : from now on every submission (reset, step, step_many
+    in every form, a load) is followed on the same stream by ONE launch that rewrites
+    `observe_avatar_ids()` of every world into them, or into the ring slot the submission wrote.
+    Both None clears the registration; the engine's launches are then what they were.  Returns
+    (view, zap)."""
+    t = self._torch
+    if view is None and zap is None:
+      avatar_ids_request(self._L, self._h, MP_AVATARIDS_REGISTER)
+      self._avatar_ids = None
+      return None, None
+    shape = self.avatar_ids_shape
+    first = view if view is not None else zap
+    ring = isinstance(first, t.Tensor) and first.dim() == 4
+    for o in (view, zap):
+      if o is None:
+        continue
+      if (not isinstance(o, t.Tensor) or o.dtype != t.int32 or tuple(o.shape[-3:]) != shape or
+          o.dim() != (4 if ring else 3) or not (o[0] if ring else o).is_contiguous() or o.device != self.device or
+          (ring and (o.shape[0] != first.shape[0] or (o.shape[0] > 1 and o.stride(0) != first.stride(0))))):
+        raise ValueError(f"bind_avatar_ids: view and zap must be int32 tensors of shape {shape} or "
+                         f"[T, {', '.join(map(str, shape))}] with contiguous slots (of one stride) on {self.device}")
+    block = int(np.prod(shape)) * 4
+    f = self._view_ring(first, ring, block)
+    avatar_ids_request(self._L, self._h, MP_AVATARIDS_REGISTER,
+                       dst=None if view is None else view.data_ptr(), dst_bytes=0 if view is None else f["dst_bytes"],
+                       dst_zap=None if zap is None else zap.data_ptr(),
+                       dst_zap_bytes=0 if zap is None else f["dst_bytes"], slot_stride=f["slot_stride"],
+                       slots=f["slots"])
+    self._avatar_ids = (view, zap)
+    return view, zap
 
   def counters(self) -> Dict[str, int]:
     out = np.zeros(len(COUNTER_NAMES), np.uint64)

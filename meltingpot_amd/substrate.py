@@ -989,6 +989,14 @@ class Substrate:
       raise ValueError("\"EGO_LAYER\" needs a batched substrate (device tensors): build it with "
                        "num_worlds > 1; the one-world form returns numpy arrays and refuses it as it "
                        "refuses a rollout ring")
+    # "AVATAR_IDS_IN_VIEW", "AVATAR_IDS_IN_RANGE_TO_ZAP": two leaves behind one registration (MpAvatarIds)
+    ids = tuple(n for n in AVATAR_IDS_NAMES if n in config.individual_observation_names)
+    if ids and not self._batched:
+      raise ValueError(f"{list(ids)} need a batched substrate (device tensors): build it with num_worlds > 1; "
+                       "the one-world form returns numpy arrays and refuses them as it refuses \"EGO_LAYER\"")
+    if AVATAR_IDS_NAMES[1] in ids and not engine_lib.has_zapper(pack_bytes):
+      raise ValueError(f"\"{AVATAR_IDS_NAMES[1]}\": {config.name!r} has no Zapper, so no zap could reach anybody "
+                       f"(\"{AVATAR_IDS_NAMES[0]}\" works on every level)")
     self._submissions = 0
     self._check_device_actions = bool(check_device_actions)
     if not self._roles:
@@ -1033,10 +1041,10 @@ class Substrate:
                           "NUM_OTHERS_WHO_ATE_THIS_STEP": E.OBS_AUX4})
     names = (list(config.individual_observation_names) +
              list(config.global_observation_names) + ["COLLECTIVE_REWARD"])
-    unknown = [n for n in names if n not in self._kinds and not (ego and n == "EGO_LAYER")]
+    unknown = [n for n in names if n not in self._kinds and not (ego and n == "EGO_LAYER") and n not in ids]
     if unknown:
       raise ValueError(f"observations {unknown} are not produced by the engine for "
-                       f"{config.name!r} (it offers {sorted(self._kinds) + ['EGO_LAYER']})")
+                       f"{config.name!r} (it offers {sorted(self._kinds) + ['EGO_LAYER'] + list(AVATAR_IDS_NAMES)})")
     kinds = {n: self._kinds[n] for n in names if n in self._kinds}
     kinds.update({"#reward": E.OBS_REWARD, "#discount": E.OBS_DISCOUNT,
                   "#step_type": E.OBS_STEP_TYPE})
@@ -1077,7 +1085,18 @@ class Substrate:
       else:
         bound["EGO_LAYER"] = self._eng.bind_ego_layer(
             given if given is not None else t.zeros(shape, dtype=t.int32, device=self._eng.device))
+    if ids:
+      # whom every player sees and could zap: rewritten behind every submission by ONE launch, into
+      # these tensors or into the ring slot the submission wrote
+      t = self._eng._torch
+      shape = self._eng.avatar_ids_shape
+      for n in ids:
+        given = None if _leaves is None else _leaves(n, shape, t.int32, self._eng.device)
+        bound[n] = given if given is not None else t.zeros(((self._T,) if self._T else ()) + shape, dtype=t.int32,
+                                                            device=self._eng.device)
+      self._eng.bind_avatar_ids(bound.get(AVATAR_IDS_NAMES[0]), bound.get(AVATAR_IDS_NAMES[1]))
     self._ego = ego
+    self._ids = ids
     self._obs = {n: bound[n] for n in names}
     self._reward = bound["#reward"]
     self._discount = bound["#discount"]
@@ -1468,6 +1487,10 @@ class Substrate:
               if n != "INVENTORY" or int(self._eng.info.num_resources) > 0}
     if getattr(self, "_ego", False):   # (a substrate built with the leaf also draws it from saved states)
       leaves["EGO_LAYER"] = engine_lib.OBS_EGO_LAYER
+    if getattr(self, "_ids", ()):   # (likewise; drawn by a request of their own, MpAvatarIds: no engine kind)
+      leaves[AVATAR_IDS_NAMES[0]] = engine_lib.OBS_AVATAR_IDS
+      if self._eng.has_zapper:
+        leaves[AVATAR_IDS_NAMES[1]] = engine_lib.OBS_AVATAR_IDS
     return leaves
 
   def _state_leaves(self, observations) -> Dict[str, int]:
@@ -1512,19 +1535,57 @@ class Substrate:
     states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
     self._eng.use_current_stream()
     ego = leaves.pop("EGO_LAYER", None) is not None
+    ids = [leaves.pop(n, None) is not None for n in AVATAR_IDS_NAMES]
+
+    def avatar_ids(out, r, p):   # both leaves by one launch
+      if any(ids):
+        got = self._eng.observe_avatar_ids(states.data, rows=r, players=p, view=ids[0], zap=ids[1],
+                                           fingerprint=states.fingerprint)
+        out.update({n: v for n, v in zip(AVATAR_IDS_NAMES, got) if v is not None})
+      return out
+
     if players is None:
       out = {n: self._eng.observe_states(states.data, k, rows=rows, fingerprint=states.fingerprint)
              for n, k in leaves.items()}
       if ego:
         out["EGO_LAYER"] = self._eng.observe_ego_layer(states.data, rows=rows, fingerprint=states.fingerprint)
-      return out
+      return avatar_ids(out, rows, None)
     p = self._eng._device_ints(players, "players")
     r = None if rows is None else self._eng._device_ints(rows, "rows")
     out = {n: self._eng.observe_views(states.data, k, p, rows=r, fingerprint=states.fingerprint)
            for n, k in leaves.items() if n != "WORLD.RGB"}
     if ego:
       out["EGO_LAYER"] = self._eng.observe_ego_layer(states.data, rows=r, players=p, fingerprint=states.fingerprint)
-    return out
+    return avatar_ids(out, r, p)
+
+  def observe_avatar_ids(self, states: Optional[WorldStates] = None, rows=None, players=None, view: bool = True,
+                         zap: Optional[bool] = None):
+    """("AVATAR_IDS_IN_VIEW", "AVATAR_IDS_IN_RANGE_TO_ZAP") — the reference's per-avatar
+    observations of whom a player sees and whom a zap it fired now could reach — of saved states,
+    or of this substrate's worlds as they are now (`states` None; `rows` are then world indices).
+    int32 [R, P, P] each, row p the 0/1 vector of player p over the player slots, or [R, P] with
+    `players` (R ints: the vector of player players[i] of row rows[i]).  IN_VIEW: both alive and
+    q's cell under p's window (1 at q == p).  IN_RANGE: the reference's rays on the avatars' own
+    layer, whatever the cooldown — beam blockers of OTHER layers play no part, as in the reference,
+    so on a level with such blockers this is the observation, not a prediction of the next beam.
+    `zap` None: where the level has a Zapper; True on a level without one raises ValueError, and
+    None stands in the pair for the one not worked out.  Any batched substrate draws them, with or
+    without the leaves.  Ordered on the current stream; no host synchronisation."""
+    if not self._batched:
+      raise ValueError("observe_avatar_ids needs a batched substrate (device tensors): build it with num_worlds > 1")
+    if zap is None:
+      zap = self._eng.has_zapper
+    if zap and not self._eng.has_zapper:
+      raise ValueError(f"observe_avatar_ids: {self._config.name!r} has no Zapper, so there is no "
+                       f"\"{AVATAR_IDS_NAMES[1]}\" (\"{AVATAR_IDS_NAMES[0]}\" works on every level)")
+    self._eng.use_current_stream()
+    if states is None:
+      return self._eng.observe_avatar_ids(None, rows=rows, players=players, view=view, zap=zap)
+    if not isinstance(states, WorldStates):
+      raise ValueError("observe_avatar_ids takes the WorldStates of save_state or step_many(states=True)")
+    states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
+    return self._eng.observe_avatar_ids(states.data, rows=rows, players=players, view=view, zap=zap,
+                                        fingerprint=states.fingerprint)
 
   def observe_ego_layer(self, states: Optional[WorldStates] = None, rows=None, players=None):
     """"EGO_LAYER" — the layer view in the avatar's own frame: cell (i, j) names the sprites under
@@ -1642,6 +1703,10 @@ class Substrate:
       observations = (observations,)
     leaves = {}
     for n in observations:
+      if n in AVATAR_IDS_NAMES:
+        raise ValueError(f"step_many: \"{n}\" has no per-step rows (it is written by a launch behind the "
+                         "submission): take step_many(states=True), then "
+                         f"observe_states(result.states, (\"{n}\",)) or observe_avatar_ids(result.states)")
       if n == "EGO_LAYER":
         raise ValueError("step_many: \"EGO_LAYER\" has no per-step rows (it is drawn by a launch behind the "
                          "submission, from the final records): call step_many(states=True) and draw "
@@ -1788,7 +1853,7 @@ class Substrate:
 
   def observation_spec(self) -> List[Mapping[str, Array]]:
     spec = observation_spec_of(self._config, self._eng.pack_bytes, self._rgb_pool,
-                               self._world_rgb_pool)
+                               self._world_rgb_pool, len(self._roles))
     return [dict(spec) for _ in self._roles]
 
   def action_spec(self) -> List[DiscreteArray]:
@@ -1876,15 +1941,25 @@ def layer_spec(pack_bytes: bytes) -> Array:
                np.int32, "LAYER")
 
 
+# the reference's per-avatar observations of players (avatar_library.lua:1204-1315; MpAvatarIds)
+AVATAR_IDS_NAMES = ("AVATAR_IDS_IN_VIEW", "AVATAR_IDS_IN_RANGE_TO_ZAP")
+
+
+def avatar_ids_specs(names: Sequence[str], num_players: int) -> Dict[str, Array]:
+  """The specs of those of AVATAR_IDS_NAMES among `names`: a 0/1 int32 vector over the player slots."""
+  return {n: Array((int(num_players),), np.int32, n) for n in AVATAR_IDS_NAMES if n in names}
+
+
 def ego_layer_spec(pack_bytes: bytes) -> Array:
   """"EGO_LAYER" of a pack: "LAYER"'s shape and dtype, the window turned with the avatar."""
   return Array(layer_spec(pack_bytes).shape, np.int32, "EGO_LAYER")
 
 
 def observation_spec_of(config: SubstrateConfig, pack_bytes: bytes, rgb_pool: int = 1,
-                        world_rgb_pool: int = 1) -> Dict[str, Array]:
+                        world_rgb_pool: int = 1, num_players: Optional[int] = None) -> Dict[str, Array]:
   """One player's observation spec of a `Substrate` built from `config` and `pack_bytes` with
-  these pooling factors (what its `observation_spec()` hands out per player)."""
+  these pooling factors (what its `observation_spec()` hands out per player).  `num_players`: the
+  length of the AVATAR_IDS_* vectors (default: the config's default roles)."""
   spec = dict(config.timestep_spec)
   spec["COLLECTIVE_REWARD"] = Array((), np.float64, "COLLECTIVE_REWARD")
   if rgb_pool > 1 and "RGB" in spec:
@@ -1898,6 +1973,8 @@ def observation_spec_of(config: SubstrateConfig, pack_bytes: bytes, rgb_pool: in
     spec["LAYER"] = layer_spec(pack_bytes)
   if "EGO_LAYER" in config.individual_observation_names:
     spec["EGO_LAYER"] = ego_layer_spec(pack_bytes)
+  spec.update(avatar_ids_specs(config.individual_observation_names,
+                               len(config.default_player_roles) if num_players is None else num_players))
   return spec
 
 
@@ -1918,6 +1995,7 @@ def select_observations(config: SubstrateConfig, pack_bytes: bytes,
     spec["LAYER"] = layer_spec(pack_bytes)
   if "EGO_LAYER" in individual:
     spec["EGO_LAYER"] = ego_layer_spec(pack_bytes)
+  spec.update(avatar_ids_specs(individual, len(config.default_player_roles)))
   wanted = set(individual) | set(global_observations)
   return individual, list(global_observations), {n: sp for n, sp in spec.items() if n in wanted}
 
@@ -2133,7 +2211,7 @@ def leaf_bytes_per_world(config: SubstrateConfig, pack_bytes: bytes, num_players
                          rgb_pool: int = 1, world_rgb_pool: int = 1) -> Dict[str, int]:
   """Bytes of one world of every leaf a batched `Substrate` of `config` binds (the
   observations, "COLLECTIVE_REWARD" and the "#reward", "#discount", "#step_type" leaves)."""
-  spec = observation_spec_of(config, pack_bytes, rgb_pool, world_rgb_pool)
+  spec = observation_spec_of(config, pack_bytes, rgb_pool, world_rgb_pool, num_players)
   out = {}
   for n, sp in spec.items():
     count = num_players if n in config.individual_observation_names else 1
@@ -2384,6 +2462,26 @@ class MixtureSubstrate:
                          f"{tuple(m._eng.ego_layer_shape[1:])}")
       m._eng.use_current_stream()
       m._eng.observe_ego_layer(None, out=out[off:off + n])
+    return out
+
+  def observe_avatar_ids(self, view: bool = True, zap: Optional[bool] = None):
+    """`Substrate.observe_avatar_ids()` of the worlds as they are now: ONE int32 [N, P, P] device
+    tensor each, of which every member writes its slice.  `zap` None: where every member has a
+    Zapper; True raises ValueError if one has none."""
+    eng = self._members[0]._eng
+    t = eng._torch
+    have = all(m._eng.has_zapper for m in self._members)
+    if zap and not have:
+      lacking = [n for n, m in zip(self._names, self._members) if not m._eng.has_zapper]
+      raise ValueError(f"observe_avatar_ids: {lacking} have no Zapper, so there is no \"{AVATAR_IDS_NAMES[1]}\"")
+    zap = have if zap is None else bool(zap)
+    if not view and not zap:
+      raise ValueError("observe_avatar_ids: neither view nor zap is asked for")
+    shape = (self._N, self._P, self._P)
+    out = tuple(t.empty(shape, dtype=t.int32, device=eng.device) if want else None for want in (view, zap))
+    for m, off, n in zip(self._members, self._offsets, self._counts):
+      m._eng.use_current_stream()
+      m._eng.observe_avatar_ids(None, view=view, zap=zap, out=tuple(None if o is None else o[off:off + n] for o in out))
     return out
 
   def hash_views(self, layers=None, classes=None):
