@@ -24,11 +24,6 @@
 
 #include "ego_layer.h"
 
-// DevTables::fault word FAULT_STATE_INDEX + 2 of an index an MpAvatarIds launch skipped (15 to 17:
-// ego_planes.h)
-constexpr uint32_t kFaultAvatarIdsRow = 18u;
-constexpr uint32_t kFaultAvatarIdsPlayer = 19u;
-
 namespace avatar_ids {
 
 using ego_layer::Window;

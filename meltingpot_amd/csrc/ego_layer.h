@@ -16,13 +16,6 @@
 #define MP_EGO_HD
 #endif
 
-// DevTables::fault word FAULT_STATE_INDEX + 2 of an index an MpEgoLayer draw skipped: a rows[]
-// index that is no row of the bank (no world of the engine), a players[] index that is no player
-// (mp_common.h; 3: state_obs.h, 4 and 5: state_check.h, 6: state_hash.h, 7 and 8: state_view.h,
-// 9 and 10: step_listed.h)
-constexpr uint32_t kFaultEgoRow = 11u;
-constexpr uint32_t kFaultEgoPlayer = 12u;
-
 namespace ego_layer {
 
 // The window and the map: what the value function needs of DevTables, with the reciprocals of

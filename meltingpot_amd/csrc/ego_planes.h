@@ -21,13 +21,6 @@
 
 #include "ego_layer.h"
 
-// DevTables::fault word FAULT_STATE_INDEX + 2 of what an MpEgoPlanes launch skipped (13 and 14:
-// view_hash.h): a rows[] index, a players[] index, and an entry of a DEVICE class table outside
-// [-1, num_classes) (word 9 = the id + 1, word 10 = the entry; it counted as -1)
-constexpr uint32_t kFaultEgoPlanesRow = 15u;
-constexpr uint32_t kFaultEgoPlanesPlayer = 16u;
-constexpr uint32_t kFaultEgoPlanesClass = 17u;
-
 namespace ego_planes {
 
 using ego_layer::Window;

@@ -447,12 +447,35 @@ enum { STEP_MODE_STEP = 0, STEP_MODE_RESET = 1, STEP_MODE_FIELDS = 2, STEP_MODE_
 // another layout are refused.  Bump it with any change to what a record holds or means.
 #define MP_RECORD_LAYOUT_VERSION 1u
 
-// DevTables::fault words of the world-state entry points (mp_save_worlds / mp_load_worlds): an
-// index outside its range that a launch skipped — word 9 = world (or row) + 1, word 10 = the
-// index, word 11 = 1 for a load's src[], 2 for a save's world list (3: state_obs.h; 4, 5 and
-// words 12-15, a checked load's refused row: state_check.h).  The next synchronising call
-// reports it (MP_ERR_INVALID) and clears it.
+// DevTables::fault words of an index outside its range that a launch skipped — word 9 = the
+// position in the request's list (a world, a row, an entry) + 1, word 10 = the index, word 11 =
+// which list of which request it was, an IndexFault.  The next synchronising call reports it
+// (MP_ERR_INVALID; mp_engine.hip: sync_and_check) and clears it.
 enum { FAULT_STATE_INDEX = 9 };
+// The values of word FAULT_STATE_INDEX + 2, all of them: a new report takes the next number here.
+enum IndexFault : uint32_t {
+  kFaultLoadSrc = 1u,            // MP_STATES_LOAD: src[] names no row of the bank (step_load.h)
+  kFaultSaveWorld = 2u,          // MP_STATES_SAVE: worlds[] names no world
+  kFaultObserveRow = 3u,         // MpStatesObserve: rows[] names no row of the bank
+  // MpStatesCheck's own (state_check.h, where words 12-15 of a refusal are): a row a checked load
+  // refused, as kFaultCheckRefused | rule << 8, and a rows[] index of a check that is no row
+  kFaultCheckRefused = 4u,
+  kFaultCheckRow = 5u,
+  kFaultHashRow = 6u,            // MpStatesHash: rows[] (or worlds[]) names no row of the bank
+  kFaultViewRow = 7u,            // MpStatesView: rows[] names no row, players[] no player
+  kFaultViewPlayer = 8u,
+  kFaultListedWorld = 9u,        // MpStepListed: worlds[] names no world, or a world an earlier entry names
+  kFaultListedRepeat = 10u,
+  kFaultEgoRow = 11u,            // MpEgoLayer: rows[] names no row (no world of the engine), players[] no player
+  kFaultEgoPlayer = 12u,
+  kFaultViewHashRow = 13u,       // MpViewHash: likewise
+  kFaultViewHashPlayer = 14u,
+  kFaultEgoPlanesRow = 15u,      // MpEgoPlanes: likewise, and an entry of a DEVICE class table outside
+  kFaultEgoPlanesPlayer = 16u,   // [-1, num_classes) (word 9 = the id + 1, word 10 = the entry; it counted as -1)
+  kFaultEgoPlanesClass = 17u,
+  kFaultAvatarIdsRow = 18u,      // MpAvatarIds: as MpEgoLayer
+  kFaultAvatarIdsPlayer = 19u,
+};
 // ... and of a registered episode start a stepping launch skipped (step_load.h: report_start):
 // words 32-35 = world + 1, rows[world], the rule of the row's verdict (0: a bad index), its offset word.
 constexpr int kFaultStartWorld = 32;

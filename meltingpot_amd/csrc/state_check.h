@@ -311,7 +311,7 @@ __host__ __device__ inline void verdict_of(uint64_t key, int32_t* rule, int32_t*
 
 }  // namespace state_check
 
-// DevTables::fault word FAULT_STATE_INDEX + 2 (mp_common.h) of the check's own reports: a row a
+// The check's own reports through DevTables::fault (mp_common.h: FAULT_STATE_INDEX, IndexFault): a row a
 // checked load refused (word 9 = world + 1, word 10 = the row, word 11 = kFaultCheckRefused |
 // rule << 8), and a rows[] index of a check that is no row of the bank (word 9 = position + 1,
 // word 10 = the index, word 11 = kFaultCheckRow).  The load that follows a filter reports the
@@ -320,8 +320,7 @@ __host__ __device__ inline void verdict_of(uint64_t key, int32_t* rule, int32_t*
 // rule, 15 = the offset word.  Of several refused worlds of one launch ONE claims word 12 (a
 // compare-and-swap from 0) and writes the other three: the four words name one world.  Words
 // 9-11 are plain stores, as everywhere: theirs may belong to different worlds.
-constexpr uint32_t kFaultCheckRefused = 4u;
-constexpr uint32_t kFaultCheckRow = 5u;
+// kFaultCheckWorld is that word's offset in DevTables::fault, not a code of IndexFault.
 constexpr int kFaultCheckWorld = 12;
 
 struct DecodedPack;

@@ -131,10 +131,6 @@ __device__ inline uint64_t wave_sum(uint64_t v) {
 
 }  // namespace state_hash
 
-// DevTables::fault word FAULT_STATE_INDEX + 2 of a hash's own report: a rows[] (or worlds[]) index
-// that is no row of the bank (word 9 = position + 1, word 10 = the index).
-constexpr uint32_t kFaultHashRow = 6u;
-
 struct DecodedPack;
 // The layout of a decoded pack's rows (host pointers: host_stage's decode); no HIP call.
 state_hash::Layout hash_layout_of(const DecodedPack& d);

@@ -5,10 +5,6 @@
 
 #include "mp_common.h"
 
-// DevTables::fault word FAULT_STATE_INDEX + 2 of a rows[] index an MpStatesObserve launch skipped
-// (1: a load's src[], 2: a save's world list; mp_common.h)
-constexpr uint32_t kFaultObserveRow = 3u;
-
 // Elements of a gathered view (a pixel kind, LAYER) whose rows[] index was out of range are kept
 // aside while the draw runs and put back after it; a request keeps this many.
 constexpr int kObsStashSlots = 8;

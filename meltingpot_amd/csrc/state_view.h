@@ -5,12 +5,6 @@
 
 #include "mp_common.h"
 
-// DevTables::fault word FAULT_STATE_INDEX + 2 of an index an MpStatesView launch skipped: a rows[]
-// index that is no row of the bank, a players[] index that is no player (mp_common.h; 3: state_obs.h,
-// 4 and 5: state_check.h, 6: state_hash.h)
-constexpr uint32_t kFaultViewRow = 7u;
-constexpr uint32_t kFaultViewPlayer = 8u;
-
 // Geometry of a k_state_view launch (state_view_plan): waves a workgroup (one view each at a
 // time), workgroups, dynamic LDS.  waves == 0: one wave's share does not fit the LDS (`lds` = what
 // it would take).

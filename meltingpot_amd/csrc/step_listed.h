@@ -18,12 +18,6 @@ struct ListArgs {
   uint32_t generation;
 };
 
-// DevTables::fault word FAULT_STATE_INDEX + 2 of an entry a listed launch skipped (word 9 = entry
-// + 1, word 10 = worlds[entry]; mp_common.h; 3: state_obs.h, 4 and 5: state_check.h, 6:
-// state_hash.h, 7 and 8: state_view.h): a value that is no world, a world an earlier entry names.
-constexpr uint32_t kFaultListedWorld = 9u;
-constexpr uint32_t kFaultListedRepeat = 10u;
-
 // The claim launch and then the step kernels: ceil(count / worlds per group) workgroups.
 void launch_step_listed(const DevTables& t, const SubstrateTables& s, const stepk::StepArgs& args,
                         const StepManyLaunch& l, const UntilArgs& u, const ListArgs& list,

@@ -126,7 +126,7 @@ __device__ inline void load_world(const DevTables& t, const Tables& c, const Wor
   const int r = __builtin_amdgcn_readfirstlane(args.src[w]);
   if (r == -1) return;   // as a masked reset leaves a world outside its mask
   if (r < -1 || r >= args.bank_rows) {   // never dereferenced: reported, the world left alone
-    report_state_index(t, lane, w, r, 1);
+    report_state_index(t, lane, w, r, kFaultLoadSrc);
     return;
   }
   uint8_t* rec = wd.rec;

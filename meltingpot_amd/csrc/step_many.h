@@ -1,5 +1,5 @@
 // step_many.h — what the host hands the K-step kernels (step_many.hip) besides StepArgs, and the
-// one description of a per-step row that the host's check (mp_engine.hip: step_request) reads.
+// one description of a per-step row that the host's check (engine_requests.hip: step_request) reads.
 #ifndef MP_STEP_MANY_H_INTERNAL_
 #define MP_STEP_MANY_H_INTERNAL_
 

@@ -19,11 +19,6 @@
 #include "ego_layer.h"
 #include "state_hash.h"
 
-// DevTables::fault word FAULT_STATE_INDEX + 2 of an index an MpViewHash draw skipped (11 and 12:
-// ego_layer.h)
-constexpr uint32_t kFaultViewHashRow = 13u;
-constexpr uint32_t kFaultViewHashPlayer = 14u;
-
 namespace view_hash {
 
 using ego_layer::Window;

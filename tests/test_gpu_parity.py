@@ -1135,7 +1135,7 @@ def _stock_plan(which, views):
 
 TUNER_PLANS = [
     # (name, MpDevOptions, expectation on MpInfo.plan_*) — mp_tune's five candidates
-    # (csrc/mp_engine.hip mp_tune), each FORCED: with MpConfig.dev the plan is the caller's
+    # (csrc/mp_place.hip mp_tune), each FORCED: with MpConfig.dev the plan is the caller's
     # and mp_tune keeps it
     ("stock ring", lambda B, NB, F: {"static_pct": 100},
      lambda p, B, NB, F: p["batch_worlds"] == B and p["ring_batches"] == NB and

@@ -7,6 +7,10 @@ be pinned, on a GPU:
     python tests/tools/make_state_request_refusals.py          # every case
     python tests/tools/make_state_request_refusals.py --cpu    # only the cases that need no device
 
+Both also write tests/golden/request_dispatch.json, the same pairs for `dispatch_cases`: every
+request's size through each of the two carriers with a NULL engine, a size no request has, and a
+NULL buffer — which handler, if any, a (carrier, size) pair reaches.  No device is needed.
+
 Every case is refused on the host before any launch (a few are accepted without a launch and pin
 that: code 0, empty text).  A case breaks the one or two rules its name says; every other pointer
 of its request is device memory large enough for it.  The list is this module's `cpu_cases` and
@@ -25,6 +29,13 @@ sys.path.insert(0, ROOT)
 from meltingpot_amd import engine as E  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "state_request_refusals.json")
+DISPATCH = os.path.join(ROOT, "tests", "golden", "request_dispatch.json")
+CARRIERS = ("mp_snapshot", "mp_restore")
+# the 18 requests the two carriers tell apart by size
+REQUESTS = (E.MpKernelVariant, E.MpWorldStates, E.MpStatesObserve, E.MpStepMany, E.MpStepTrajectory, E.MpStateLayout,
+            E.MpStatesCheck, E.MpStatesHash, E.MpEpisodeStarts, E.MpStatesView, E.MpStepActive, E.MpStepUntil,
+            E.MpStepListed, E.MpEpisodeStats, E.MpEgoLayer, E.MpViewHash, E.MpEgoPlanes, E.MpAvatarIds)
+ODD_SIZE = 8   # a buffer no request is the size of
 N, BANK_ROWS = 2, 3
 VIEWS = {"ego_layer": E.MpEgoLayer, "view_hash": E.MpViewHash, "ego_planes": E.MpEgoPlanes}
 
@@ -36,10 +47,16 @@ def normalise(text: str) -> str:
   return text[:text.index(cut) + len(cut)] if cut in text else text
 
 
-def send(L, carrier: str, handle, req):
-  """[return code, normalised text] of one request, read the way engine._check reads it."""
-  rc = getattr(L, carrier)(handle, ctypes.addressof(req), ctypes.sizeof(req))
+def send_bytes(L, carrier: str, handle, address, size: int):
+  """[return code, normalised text] of `size` bytes at `address` (None: a NULL buffer), read the way
+  engine._check reads it."""
+  rc = getattr(L, carrier)(handle, address, size)
   return [int(rc), normalise((L.mp_last_error() or b"").decode()) if rc else ""]
+
+
+def send(L, carrier: str, handle, req):
+  """`send_bytes` of one request."""
+  return send_bytes(L, carrier, handle, ctypes.addressof(req), ctypes.sizeof(req))
 
 
 def make(struct, **fields):
@@ -488,6 +505,25 @@ def gpu_cases(c: DeviceCtx):
   return out
 
 
+def dispatch_cases():
+  """[(name, carrier, request or None, size)], all with a NULL engine: each request, zero but for its
+  struct_size, through each carrier; ODD_SIZE bytes; a NULL buffer of a request's size."""
+  sizes = [ctypes.sizeof(s) for s in REQUESTS]
+  assert len(set(sizes)) == len(REQUESTS) == 18 and ODD_SIZE not in sizes
+  out = []
+  for carrier in CARRIERS:
+    for struct in REQUESTS:
+      out.append((f"{struct.__name__}/{carrier}", carrier, make(struct), ctypes.sizeof(struct)))
+    out.append((f"odd_size/{carrier}", carrier, (ctypes.c_uint8 * ODD_SIZE)(), ODD_SIZE))
+    out.append((f"null_buffer/{carrier}", carrier, None, ctypes.sizeof(E.MpStatesObserve)))
+  return out
+
+
+def replay_dispatch(L, cases):
+  return {name: send_bytes(L, carrier, None, None if req is None else ctypes.addressof(req), size)
+          for name, carrier, req, size in cases}
+
+
 def replay(L, cases):
   return {name: send(L, carrier, handle, req) for name, carrier, handle, req in cases}
 
@@ -519,6 +555,11 @@ def main():
     f.write("\n")
   refused = sum(1 for rc, _ in got.values() if rc)
   print(GOLDEN, len(got), "cases,", refused, "refused,", os.path.getsize(GOLDEN), "bytes")
+  dispatch = replay_dispatch(E.load_library(), dispatch_cases())
+  with open(DISPATCH, "w") as f:
+    json.dump(dict(sorted(dispatch.items())), f, indent=1)
+    f.write("\n")
+  print(DISPATCH, len(dispatch), "cases,", os.path.getsize(DISPATCH), "bytes")
 
 
 if __name__ == "__main__":
