@@ -16,7 +16,7 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -221,15 +221,20 @@ class MpWorldStates(ctypes.Structure):
               ("count", ctypes.c_int32), ("bank_rows", ctypes.c_int32)]
 
 
-def _send(L, handle, req, carrier: str = "mp_snapshot", label: Optional[str] = None):
-  """Sends the request struct `req` to engine `handle` (None: a host form) through `carrier`,
-  "mp_snapshot" or "mp_restore", and returns it (with its outputs); raises like every call."""
+_SNAPSHOT, _RESTORE = "mp_snapshot", "mp_restore"   # the two carriers of a request
+
+
+def _send(L, handle, req, carrier: Optional[str] = None, label: Optional[str] = None):
+  """Sends the request struct `req` to engine `handle` (None: a host form) through its carrier in
+  REQUESTS (through `carrier`, for the one request that has both), and returns it (with its
+  outputs); raises like every call."""
+  carrier = carrier or _CARRIER[type(req)]
   _check(L, getattr(L, carrier)(handle, ctypes.addressof(req), ctypes.sizeof(req)),
          f"{carrier} ({label or type(req).__name__})")
   return req
 
 
-def _request(L, handle, struct, head, fields, carrier: str = "mp_snapshot", label: Optional[str] = None):
+def _request(L, handle, struct, head, fields, carrier: Optional[str] = None, label: Optional[str] = None):
   """One request of type `struct`: struct_size, then `head` in the order of its fields, then `fields`."""
   req = struct(ctypes.sizeof(struct), *head)
   for k, v in fields.items():
@@ -241,8 +246,8 @@ def world_states_request(L, handle, op: int, **fields) -> MpWorldStates:
   """Runs one MpWorldStates request on engine `handle` (MP_STATES_LOAD through mp_restore, the
   others through mp_snapshot) and returns it (with its outputs); raises like every call."""
   if op == MP_STATES_LOAD:
-    return _request(L, handle, MpWorldStates, (op,), fields, "mp_restore", "MP_STATES_LOAD")
-  return _request(L, handle, MpWorldStates, (op,), fields)
+    return _request(L, handle, MpWorldStates, (op,), fields, _RESTORE, "MP_STATES_LOAD")
+  return _request(L, handle, MpWorldStates, (op,), fields, _SNAPSHOT)
 
 
 # Observations of bank rows (include/mp_engine.h: MpStatesObserve), carried by mp_snapshot
@@ -283,13 +288,19 @@ OBS_EGO_LAYER = -1   # no MpObsKind: the Python layers' handle for the leaf wher
 OBS_AVATAR_IDS = -2  # likewise: "AVATAR_IDS_IN_VIEW" and "AVATAR_IDS_IN_RANGE_TO_ZAP"
 
 
-class MpEgoLayer(ctypes.Structure):
-  _fields_ = [("struct_size", ctypes.c_uint32), ("op", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
+# What MpEgoLayer, MpViewHash, MpEgoPlanes and MpAvatarIds begin with (csrc/engine_views.hip:
+# ViewRequest): the head, one int32 of the request's own, then the host form's pack
+_VIEW_HEAD = [("struct_size", ctypes.c_uint32), ("op", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
               ("bank", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("players", ctypes.c_void_p),
               ("dst", ctypes.c_void_p), ("dst_bytes", ctypes.c_uint64), ("bank_rows", ctypes.c_int32),
-              ("count", ctypes.c_int32), ("slot_stride", ctypes.c_uint64), ("slots", ctypes.c_int32),
-              ("reserved", ctypes.c_int32), ("pack", ctypes.c_void_p), ("pack_len", ctypes.c_uint64),
-              ("cfg", ctypes.c_void_p), ("reserved2", ctypes.c_uint64 * 3)]
+              ("count", ctypes.c_int32), ("slot_stride", ctypes.c_uint64), ("slots", ctypes.c_int32)]
+_VIEW_PACK = [("pack", ctypes.c_void_p), ("pack_len", ctypes.c_uint64), ("cfg", ctypes.c_void_p)]
+_VIEW_CLASSES = (_VIEW_HEAD + [("classes_len", ctypes.c_int32)] + _VIEW_PACK +
+                 [("layer_mask", ctypes.c_uint64), ("classes", ctypes.c_void_p), ("num_ids", ctypes.c_int32)])
+
+
+class MpEgoLayer(ctypes.Structure):
+  _fields_ = _VIEW_HEAD + [("reserved", ctypes.c_int32)] + _VIEW_PACK + [("reserved2", ctypes.c_uint64 * 3)]
 
 
 def ego_layer_request(L, handle, op: int, **fields) -> MpEgoLayer:
@@ -615,13 +626,7 @@ MP_VIEWHASH_DRAW, MP_VIEWHASH_REGISTER, MP_VIEWHASH_HOST = 1, 2, 3
 
 
 class MpViewHash(ctypes.Structure):
-  _fields_ = [("struct_size", ctypes.c_uint32), ("op", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
-              ("bank", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("players", ctypes.c_void_p),
-              ("dst", ctypes.c_void_p), ("dst_bytes", ctypes.c_uint64), ("bank_rows", ctypes.c_int32),
-              ("count", ctypes.c_int32), ("slot_stride", ctypes.c_uint64), ("slots", ctypes.c_int32),
-              ("classes_len", ctypes.c_int32), ("pack", ctypes.c_void_p), ("pack_len", ctypes.c_uint64),
-              ("cfg", ctypes.c_void_p), ("layer_mask", ctypes.c_uint64), ("classes", ctypes.c_void_p),
-              ("num_ids", ctypes.c_int32), ("reserved", ctypes.c_int32), ("reserved2", ctypes.c_uint64 * 3)]
+  _fields_ = _VIEW_CLASSES + [("reserved", ctypes.c_int32), ("reserved2", ctypes.c_uint64 * 3)]
 
 
 def view_hash_request(L, handle, op: int, **fields) -> MpViewHash:
@@ -693,14 +698,8 @@ EGO_PLANES_MAX_CLASSES = 64
 
 
 class MpEgoPlanes(ctypes.Structure):
-  _fields_ = [("struct_size", ctypes.c_uint32), ("op", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
-              ("bank", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("players", ctypes.c_void_p),
-              ("dst", ctypes.c_void_p), ("dst_bytes", ctypes.c_uint64), ("bank_rows", ctypes.c_int32),
-              ("count", ctypes.c_int32), ("slot_stride", ctypes.c_uint64), ("slots", ctypes.c_int32),
-              ("classes_len", ctypes.c_int32), ("pack", ctypes.c_void_p), ("pack_len", ctypes.c_uint64),
-              ("cfg", ctypes.c_void_p), ("layer_mask", ctypes.c_uint64), ("classes", ctypes.c_void_p),
-              ("num_ids", ctypes.c_int32), ("num_classes", ctypes.c_int32), ("facing", ctypes.c_int32),
-              ("reserved", ctypes.c_int32), ("reserved2", ctypes.c_uint64 * 3)]
+  _fields_ = _VIEW_CLASSES + [("num_classes", ctypes.c_int32), ("facing", ctypes.c_int32),
+                              ("reserved", ctypes.c_int32), ("reserved2", ctypes.c_uint64 * 3)]
 
 
 def ego_planes_request(L, handle, op: int, **fields) -> MpEgoPlanes:
@@ -768,13 +767,8 @@ MP_AVATARIDS_DRAW, MP_AVATARIDS_REGISTER, MP_AVATARIDS_HOST = 1, 2, 3
 
 
 class MpAvatarIds(ctypes.Structure):
-  _fields_ = [("struct_size", ctypes.c_uint32), ("op", ctypes.c_int32), ("fingerprint", ctypes.c_uint64),
-              ("bank", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("players", ctypes.c_void_p),
-              ("dst", ctypes.c_void_p), ("dst_bytes", ctypes.c_uint64), ("bank_rows", ctypes.c_int32),
-              ("count", ctypes.c_int32), ("slot_stride", ctypes.c_uint64), ("slots", ctypes.c_int32),
-              ("reserved", ctypes.c_int32), ("pack", ctypes.c_void_p), ("pack_len", ctypes.c_uint64),
-              ("cfg", ctypes.c_void_p), ("dst_zap", ctypes.c_void_p), ("dst_zap_bytes", ctypes.c_uint64),
-              ("reserved2", ctypes.c_uint64 * 3)]
+  _fields_ = (_VIEW_HEAD + [("reserved", ctypes.c_int32)] + _VIEW_PACK +
+              [("dst_zap", ctypes.c_void_p), ("dst_zap_bytes", ctypes.c_uint64), ("reserved2", ctypes.c_uint64 * 3)])
 
 
 def avatar_ids_request(L, handle, op: int, **fields) -> MpAvatarIds:
@@ -919,11 +913,8 @@ def check_step_many(shape, dtype, num_worlds: int, num_players: int, *, repeat=N
 
 # ... under a device mask that says, per step and per world, whether the world runs (MpStepActive)
 class MpStepActive(ctypes.Structure):
-  _fields_ = [("struct_size", ctypes.c_uint32), ("steps", ctypes.c_int32),
-              ("fields", ctypes.c_int32), ("num_rows", ctypes.c_int32),
-              ("actions", ctypes.c_void_p), ("actions_step_bytes", ctypes.c_uint64),
-              ("rows", ctypes.POINTER(MpStepRow)), ("active", ctypes.c_void_p),
-              ("active_step_bytes", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 5)]
+  _fields_ = MpStepTrajectory._fields_ + [("active", ctypes.c_void_p), ("active_step_bytes", ctypes.c_uint64),
+                                          ("reserved", ctypes.c_uint64 * 5)]
 
 
 def check_step_active(active, steps: int, num_worlds: int):
@@ -963,13 +954,11 @@ STOP_NAMES = {"last": MP_STOP_LAST, "reward": MP_STOP_REWARD}
 
 
 class MpStepUntil(ctypes.Structure):
-  _fields_ = [("struct_size", ctypes.c_uint32), ("steps", ctypes.c_int32),
-              ("fields", ctypes.c_int32), ("num_rows", ctypes.c_int32),
-              ("actions", ctypes.c_void_p), ("actions_step_bytes", ctypes.c_uint64),
-              ("rows", ctypes.POINTER(MpStepRow)), ("active", ctypes.c_void_p),
-              ("active_step_bytes", ctypes.c_uint64), ("stop", ctypes.c_uint32), ("pad", ctypes.c_uint32),
-              ("stopped", ctypes.c_void_p), ("ran", ctypes.c_void_p), ("returns", ctypes.c_void_p),
-              ("gamma", ctypes.c_double), ("reserved", ctypes.c_uint64 * 5)]
+  # (MpStepActive without its `reserved`, where the new fields begin)
+  _fields_ = MpStepActive._fields_[:-1] + [("stop", ctypes.c_uint32), ("pad", ctypes.c_uint32),
+                                           ("stopped", ctypes.c_void_p), ("ran", ctypes.c_void_p),
+                                           ("returns", ctypes.c_void_p), ("gamma", ctypes.c_double),
+                                           ("reserved", ctypes.c_uint64 * 5)]
 
 
 def check_step_until(num_worlds: int, num_players: int, *, until=None, stopped=None, ran=None,
@@ -1166,6 +1155,41 @@ class MpEpisodeStats(ctypes.Structure):
               ("reserved2", ctypes.c_uint64 * 2)]
 
 
+class Request(NamedTuple):
+  """One request that mp_snapshot and mp_restore tell apart by its size: its mirror, the carriers
+  that take it, and whether its handler is reached without an engine."""
+  struct: type
+  snapshot: bool
+  restore: bool
+  null_engine: bool
+
+
+# The 18 requests, in the order and with the flags of csrc/engine_requests.hip's kRequests
+# (tests/test_request_abi_cpu.py holds the two tables, and every mirror above, to the library).
+REQUESTS = (
+    Request(MpKernelVariant, True, False, True),
+    Request(MpWorldStates, True, True, False),    # (world_states_request: the carrier follows the op)
+    Request(MpStatesObserve, True, False, True),
+    Request(MpStatesView, True, False, True),
+    Request(MpEgoLayer, True, False, True),
+    Request(MpViewHash, True, False, True),
+    Request(MpEgoPlanes, True, False, True),
+    Request(MpAvatarIds, True, False, True),
+    Request(MpStateLayout, True, False, True),
+    Request(MpStatesCheck, True, False, True),
+    Request(MpStatesHash, True, False, True),
+    Request(MpStepMany, False, True, True),
+    Request(MpStepTrajectory, False, True, True),
+    Request(MpEpisodeStarts, False, True, True),
+    Request(MpStepActive, False, True, True),
+    Request(MpStepUntil, False, True, True),
+    Request(MpStepListed, False, True, True),
+    Request(MpEpisodeStats, False, True, True),
+)
+# mirror -> its carrier, for the requests that have one
+_CARRIER = {q.struct: _SNAPSHOT if q.snapshot else _RESTORE for q in REQUESTS if q.snapshot != q.restore}
+
+
 _FULL = 0xFFFFFFFF
 # event name -> payload key -> (payload: 0 a / 1 b, shift, mask): where each key of EVENT_TYPES lies
 # in a raw event row (gift's two roles are the host's: they are no payload)
@@ -1339,7 +1363,7 @@ def episode_stats_host(stats, step_type, reward, events, columns=(), pairs=(), a
   req.events = host(events, np.int32, (K, n, EVENT_ROWS, 4), "events")
   req.active = host(active, np.uint8, (K, n), "active")
   req.ran = host(ran, np.int32, (n,), "ran")
-  _send(L, None, req, "mp_restore")
+  _send(L, None, req)
   return stats
 
 
@@ -2204,7 +2228,7 @@ class Engine:
     if listed:
       req.worlds = wl.data_ptr()
       req.count = C
-    _send(self._L, self._h, req, "mp_restore")
+    _send(self._L, self._h, req)
     self._state_args = (actions, result, mask, wl if listed else None)   # (kept until the next call: the launch may not have run yet)
     return result
 
@@ -2426,14 +2450,14 @@ class Engine:
     req = MpEpisodeStarts(ctypes.sizeof(MpEpisodeStarts), 1 if fresh else 0, fp)
     req.bank, req.rows, req.bank_rows = bank.data_ptr(), rows.data_ptr(), M
     req.verdicts = None if verdicts is None else verdicts.data_ptr()
-    _send(self._L, self._h, req, "mp_restore")
+    _send(self._L, self._h, req)
     self._episode_starts = {"bank": bank, "rows": rows, "verdicts": verdicts, "fresh": bool(fresh),
                             "fingerprint": fp}
 
   def clear_episode_starts(self):
     """Episodes start from the level's own map again; the engine's launches are what they were."""
     req = MpEpisodeStarts(ctypes.sizeof(MpEpisodeStarts))
-    _send(self._L, self._h, req, "mp_restore")
+    _send(self._L, self._h, req)
     self._episode_starts = None
 
   @property
@@ -2486,7 +2510,7 @@ class Engine:
             raise ValueError(f"set_episode_stats: out.{key}{'' if sub is None else '[' + repr(sub) + ']'} must be "
                              f"a contiguous {dtype} tensor of shape {shape} on {self.device}")
     req = _stats_request(MP_STATS_REGISTER, cols, len(names), pcols, len(pnames), out.arrays, self._torch_ptr)
-    _send(self._L, self._h, req, "mp_restore")
+    _send(self._L, self._h, req)
     self._stats = out
     self._stats_scratch = {}
     return out
@@ -2494,7 +2518,7 @@ class Engine:
   def clear_episode_stats(self):
     """No statistics launch any more: the engine issues exactly the launches it issued before."""
     req = MpEpisodeStats(ctypes.sizeof(MpEpisodeStats), MP_STATS_CLEAR)
-    _send(self._L, self._h, req, "mp_restore")
+    _send(self._L, self._h, req)
     self._stats = None
     self._stats_scratch = {}
 
@@ -2552,7 +2576,7 @@ class Engine:
     req.events, req.steps, req.count = ev.data_ptr(), K, M
     req.active = None if active is None else active.data_ptr()
     req.ran = None if ran is None else ran.data_ptr()
-    _send(self._L, self._h, req, "mp_restore")
+    _send(self._L, self._h, req)
     self._tally_args = (ev, active, ran, out, pout)   # (kept until the next call: the launch may not have run yet)
     return (out, pout) if pnames else out
 

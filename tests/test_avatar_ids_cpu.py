@@ -1,5 +1,5 @@
-"""AVATAR_IDS_IN_VIEW and AVATAR_IDS_IN_RANGE_TO_ZAP (the MpAvatarIds request) without a GPU: the C
-struct against its ctypes mirror, the unchanged C ABI, the kernels in the code object, and the
+"""AVATAR_IDS_IN_VIEW and AVATAR_IDS_IN_RANGE_TO_ZAP (the MpAvatarIds request) without a GPU (its
+struct, wrappers and kernels: tests/test_request_abi_cpu.py): the
 library's host twin held to the numpy model (tests/avatar_ids_model.py) on real rows (the fixture
 of tests/states_recipe.py's recipe, and CPU-oracle worlds under random play with beams) and on the
 hand-placed rows of tests/avatar_ids_rows.py, whose expected bits are also stated here one by one.
@@ -7,9 +7,7 @@ IN_VIEW is tied to EGO_LAYER: q is in p's view exactly when q's avatar sprite sh
 layer of p's `ego_layer_host`.  Every comparison is exact equality."""
 import ctypes
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,15 +16,10 @@ import avatar_ids_model as M
 import avatar_ids_rows as HR
 import states_recipe as R
 import view_hash_model as VM
-from meltingpot_amd import _build, substrate
+from meltingpot_amd import substrate
 from meltingpot_amd import engine as E
 from meltingpot_amd import pack as pack_lib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-FIELDS = ("struct_size", "op", "fingerprint", "bank", "rows", "players", "dst", "dst_bytes", "bank_rows",
-          "count", "slot_stride", "slots", "reserved", "pack", "pack_len", "cfg", "dst_zap", "dst_zap_bytes",
-          "reserved2")
 LEVELS = HR.LEVELS
 PLAYERS = {"clean_up": 7, "commons_harvest__open": 16, "territory__rooms": 9, "externality_mushrooms__dense": 5}
 NO_ZAPPER = ("coins", "collaborative_cooking__cramped")
@@ -41,50 +34,6 @@ def real_rows(name):
 
 
 # ---- structure ---------------------------------------------------------------------------------
-def test_the_header_names_the_request_and_the_abi_is_what_it_was(tmp_path):
-  header = open(os.path.join(ROOT, "include", "mp_engine.h")).read()
-  assert "} MpAvatarIds;" in header
-  assert "MP_AVATARIDS_DRAW = 1, MP_AVATARIDS_REGISTER = 2, MP_AVATARIDS_HOST = 3" in header
-  assert re.search(r"#define MP_ABI_VERSION 8\b", header) and re.search(r"MP_OBS_KINDS\s*=\s*24", header)
-  assert E.load_library().mp_abi_version() == 8 == E.MP_ABI_VERSION
-  out = subprocess.run(["nm", "-D", "--defined-only", _build.build_engine()], capture_output=True, text=True,
-                       check=True).stdout
-  names = {line.split()[-1] for line in out.splitlines()
-           if line.split() and line.split()[-2] in ("T", "D", "B", "R")}
-  assert names == set(E.ABI_SYMBOLS) and len(names) == 30
-  # the C struct is the ctypes mirror, and the wrappers compile as C99
-  src = tmp_path / "ids.c"
-  prints = "\n".join(f'  printf("{f} %zu\\n", offsetof(MpAvatarIds, {f}));' for f in FIELDS)
-  src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "mp_avatar_ids.h"\n'
-                 "int main(void) {\n"
-                 '  printf("sizeof %zu\\n", sizeof(MpAvatarIds));\n' + prints + "\n"
-                 '  printf("rc %d\\n", mp_avatar_ids_draw(NULL, NULL, 0, NULL, NULL, 0, NULL, 0, NULL, 0, 0));\n'
-                 '  printf("rc2 %d\\n", mp_avatar_ids_register(NULL, NULL, 0, NULL, 0, 0, 0));\n'
-                 '  printf("rc3 %d\\n", mp_avatar_ids_host(NULL, 0, NULL, NULL, 0, NULL, NULL, 0, NULL, 0, NULL, 0, 0));\n'
-                 "  return 0;\n}\n")
-  exe = tmp_path / "ids"
-  subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                  _build.LIB_PATH, f"-Wl,-rpath,{os.path.dirname(_build.LIB_PATH)}"], check=True)
-  got = dict(line.split() for line in
-             subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
-  assert int(got["sizeof"]) == ctypes.sizeof(E.MpAvatarIds) == 144
-  assert [f for f, _ in E.MpAvatarIds._fields_] == list(FIELDS)
-  for f in FIELDS:
-    assert int(got[f]) == getattr(E.MpAvatarIds, f).offset, f
-  assert int(got["rc"]) == int(got["rc2"]) == int(got["rc3"]) == E.MP_ERR_INVALID
-  # a size no other request has
-  others = (E.MpStatesObserve, E.MpStatesView, E.MpStatesHash, E.MpStateLayout, E.MpStatesCheck, E.MpKernelVariant,
-            E.MpWorldStates, E.MpStepMany, E.MpStepTrajectory, E.MpEpisodeStarts, E.MpEpisodeStats, E.MpEgoLayer,
-            E.MpStepActive, E.MpStepUntil, E.MpStepListed, E.MpViewHash, E.MpEgoPlanes)
-  assert ctypes.sizeof(E.MpAvatarIds) not in [ctypes.sizeof(c) for c in others]
-  assert ctypes.sizeof(E.MpAvatarIds) < 448   # (no engine's snapshot is that small)
-
-
-def test_the_kernels_are_in_the_code_object():
-  blob = open(_build.build_engine(), "rb").read()
-  assert b"k_avatar_ids_rows" in blob and b"k_avatar_ids_views" in blob
-
-
 def test_the_model_s_footprint_and_the_levels():
   """9 cells for the stock Zapper (length 3, radius 1), 6 for territory's (length 2): P * nc > 64
   on commons_harvest__open, so a wave takes several rounds there."""

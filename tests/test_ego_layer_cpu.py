@@ -1,12 +1,10 @@
-"""EGO_LAYER (the MpEgoLayer request) without a GPU: the C struct against its ctypes mirror, the
-unchanged C ABI, the kernels in the code object, and the library's host twin held to the numpy
+"""EGO_LAYER (the MpEgoLayer request) without a GPU (its struct, wrappers and kernels:
+tests/test_request_abi_cpu.py): the library's host twin held to the numpy
 model (tests/ego_layer_model.py) and — for every viewer that faces north — to the oracle's layer
 view, on the real rows of tests/golden/state_rows.npz (saved on a GPU by the recipe of
 tests/states_recipe.py).  The Python refusals run on the CPU oracle behind the engine interface."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,14 +13,11 @@ import torch
 import ego_layer_model as M
 import states_recipe as R
 import util
-from meltingpot_amd import _build, substrate
+from meltingpot_amd import substrate
 from meltingpot_amd import engine as E
 from oracle_engine import OracleBatchEngine
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-FIELDS = ("struct_size", "op", "fingerprint", "bank", "rows", "players", "dst", "dst_bytes", "bank_rows",
-          "count", "slot_stride", "slots", "reserved", "pack", "pack_len", "cfg", "reserved2")
 PACKS = ("clean_up", "commons_harvest__open", "coins", "collaborative_cooking__cramped",
          "prisoners_dilemma_in_the_matrix__repeated")
 
@@ -35,47 +30,6 @@ def fields_of(name, rows):
   from meltingpot_amd import pack as pack_lib
   layout = substrate.SubstrateStateLayout(E.state_layout(R.pack(name)), pack_lib.loads(R.pack(name)))
   return substrate.StateFields(torch.from_numpy(np.ascontiguousarray(rows)), layout)
-
-
-# ---- structure ---------------------------------------------------------------------------------
-def test_the_header_names_the_request_and_the_abi_is_what_it_was(tmp_path):
-  header = open(os.path.join(ROOT, "include", "mp_engine.h")).read()
-  assert "} MpEgoLayer;" in header and "MP_EGO_DRAW = 1, MP_EGO_REGISTER = 2, MP_EGO_HOST = 3" in header
-  assert re.search(r"#define MP_ABI_VERSION 8\b", header) and re.search(r"MP_OBS_KINDS\s*=\s*24", header)
-  assert E.load_library().mp_abi_version() == 8 == E.MP_ABI_VERSION
-  out = subprocess.run(["nm", "-D", "--defined-only", _build.build_engine()], capture_output=True, text=True,
-                       check=True).stdout
-  names = {line.split()[-1] for line in out.splitlines()
-           if line.split() and line.split()[-2] in ("T", "D", "B", "R")}
-  assert names == set(E.ABI_SYMBOLS) and len(names) == 30
-  # the C struct is the ctypes mirror, and the wrappers compile as C99
-  src = tmp_path / "ego.c"
-  prints = "\n".join(f'  printf("{f} %zu\\n", offsetof(MpEgoLayer, {f}));' for f in FIELDS)
-  src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "mp_ego_layer.h"\n'
-                 "int main(void) {\n"
-                 '  printf("sizeof %zu\\n", sizeof(MpEgoLayer));\n' + prints + "\n"
-                 '  printf("rc %d\\n", mp_ego_layer_draw(NULL, NULL, 0, NULL, NULL, 0, NULL, 0, 0));\n'
-                 '  printf("rc2 %d\\n", mp_ego_layer_register(NULL, NULL, 0, 0, 0));\n'
-                 '  printf("rc3 %d\\n", mp_ego_layer_host(NULL, 0, NULL, NULL, 0, NULL, NULL, 0, NULL, 0, 0));\n'
-                 "  return 0;\n}\n")
-  exe = tmp_path / "ego"
-  subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                  _build.LIB_PATH, f"-Wl,-rpath,{os.path.dirname(_build.LIB_PATH)}"], check=True)
-  got = dict(line.split() for line in
-             subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
-  assert int(got["sizeof"]) == ctypes.sizeof(E.MpEgoLayer) == 128
-  assert [f for f, _ in E.MpEgoLayer._fields_] == list(FIELDS)
-  for f in FIELDS:
-    assert int(got[f]) == getattr(E.MpEgoLayer, f).offset, f
-  assert int(got["rc"]) == int(got["rc2"]) == int(got["rc3"]) == E.MP_ERR_INVALID
-  others = (E.MpStatesObserve, E.MpStatesView, E.MpStatesHash, E.MpStateLayout, E.MpStatesCheck, E.MpKernelVariant,
-            E.MpWorldStates, E.MpStepMany, E.MpStepTrajectory, E.MpEpisodeStarts, E.MpEpisodeStats)
-  assert ctypes.sizeof(E.MpEgoLayer) not in [ctypes.sizeof(c) for c in others]
-
-
-def test_the_kernels_are_in_the_code_object():
-  blob = open(_build.build_engine(), "rb").read()
-  assert b"k_ego_layer_rows" in blob and b"k_ego_layer_views" in blob
 
 
 # ---- the host twin -------------------------------------------------------------------------------

@@ -1,6 +1,5 @@
-"""Episode statistics (MpEpisodeStats) without a GPU: include/mp_episode_stats.h compiles as C99 and as
-C++17 and the request has the size and offsets of the ctypes mirror, a size no other request has;
-the library exports what it exported; the new kernel is in the code object; requests without an
+"""Episode statistics (MpEpisodeStats) without a GPU (the request's layout and wrappers:
+tests/test_request_abi_cpu.py): the new kernel is in the code object; requests without an
 engine are refused by the library's own checks; column names parse; and the rule's host form —
 the library's own functions compiled for the host — equals the numpy model
 (tests/episode_stats_model.py) on oracle trajectories with several episodes per world, under a
@@ -8,7 +7,6 @@ random mask, and on crafted event rows at the count boundaries."""
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,84 +20,6 @@ E = engine
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASSETS = os.path.join(ROOT, "meltingpot_amd", "assets")
 PACKS = sorted(f[:-4] for f in os.listdir(ASSETS) if f.endswith(".mpk"))
-FIELDS = ("op", "num_columns", "num_pairs", "columns", "pairs", "open", "episodes", "dropped", "running", "last",
-          "total", "steps", "count", "num_players", "reserved", "step_type", "reward", "events", "active", "ran",
-          "reserved2")
-
-PROGRAM = r'''
-#include <stddef.h>
-#include <stdio.h>
-#include "mp_episode_stats.h"
-int main(void) {
-  /* (no engine: the wrappers answer MP_ERR_INVALID with the library's message) */
-  MpEpisodeStats s;
-  MpEventColumn c = mp_event_column(MP_EVENT_ZAP, 1, 0, 0xffffffffu);
-  memset(&s, 0, sizeof s);
-  int a = mp_set_episode_stats(NULL, &s);
-  int b = mp_clear_episode_stats(NULL);
-  int d = mp_tally_events(NULL, &c, 1, NULL, 0, NULL, 1, 1, NULL, NULL, NULL, NULL);
-  int e = mp_episode_stats_host(&s);   /* (steps 0: refused) */
-  printf("%u %u %u", (unsigned)sizeof(MpEpisodeStats), (unsigned)sizeof(MpEventColumn), (unsigned)sizeof(MpStatsBank));
-  printf(" %u %u %u %u %u %u %u %u", (unsigned)offsetof(MpEpisodeStats, op), (unsigned)offsetof(MpEpisodeStats, num_columns),
-         (unsigned)offsetof(MpEpisodeStats, num_pairs), (unsigned)offsetof(MpEpisodeStats, columns),
-         (unsigned)offsetof(MpEpisodeStats, pairs), (unsigned)offsetof(MpEpisodeStats, open),
-         (unsigned)offsetof(MpEpisodeStats, episodes), (unsigned)offsetof(MpEpisodeStats, dropped));
-  printf(" %u %u %u %u %u %u %u", (unsigned)offsetof(MpEpisodeStats, running), (unsigned)offsetof(MpEpisodeStats, last),
-         (unsigned)offsetof(MpEpisodeStats, total), (unsigned)offsetof(MpEpisodeStats, steps),
-         (unsigned)offsetof(MpEpisodeStats, count), (unsigned)offsetof(MpEpisodeStats, num_players),
-         (unsigned)offsetof(MpEpisodeStats, reserved));
-  printf(" %u %u %u %u %u %u", (unsigned)offsetof(MpEpisodeStats, step_type), (unsigned)offsetof(MpEpisodeStats, reward),
-         (unsigned)offsetof(MpEpisodeStats, events), (unsigned)offsetof(MpEpisodeStats, active),
-         (unsigned)offsetof(MpEpisodeStats, ran), (unsigned)offsetof(MpEpisodeStats, reserved2));
-  printf(" %u %u %u %u %u %u %u %u %u", (unsigned)offsetof(MpEventColumn, player_payload),
-         (unsigned)offsetof(MpEventColumn, player_shift), (unsigned)offsetof(MpEventColumn, filter_payload),
-         (unsigned)offsetof(MpEventColumn, filter_shift), (unsigned)offsetof(MpEventColumn, player_mask),
-         (unsigned)offsetof(MpEventColumn, filter_mask), (unsigned)offsetof(MpEventColumn, filter_value),
-         (unsigned)offsetof(MpEventColumn, other_shift), (unsigned)offsetof(MpEventColumn, other_mask));
-  printf(" %d %d %d %d\n", a, b, d, e);
-  return 0;
-}
-'''
-
-
-@pytest.mark.parametrize("compiler, std, suffix", [("gcc", "-std=c99", "c"), ("g++", "-std=c++17", "cc")])
-def test_the_header_compiles_and_has_the_size_of_the_mirror(tmp_path, compiler, std, suffix):
-  src = tmp_path / f"stats.{suffix}"
-  src.write_text(PROGRAM)
-  exe = tmp_path / "stats"
-  subprocess.run([compiler, std, "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                  _build.build_engine(), f"-Wl,-rpath,{os.path.dirname(_build.LIB_PATH)}"], check=True)
-  out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()
-  M, C = E.MpEpisodeStats, E.MpEventColumn
-  column_fields = ("player_payload", "player_shift", "filter_payload", "filter_shift", "player_mask", "filter_mask",
-                   "filter_value", "other_shift", "other_mask")
-  assert out == [str(ctypes.sizeof(M)), str(ctypes.sizeof(C)), str(ctypes.sizeof(E.MpStatsBank))] + \
-      [str(getattr(M, name).offset) for name in FIELDS] + [str(getattr(C, name).offset) for name in column_fields] + \
-      [str(E.MP_ERR_INVALID)] * 4
-
-
-def test_request_size_differs_from_every_other_request():
-  others = [ctypes.sizeof(c) for c in (E.MpStatesHash, E.MpStateLayout, E.MpStatesCheck, E.MpStatesObserve,
-                                       E.MpStatesView, E.MpKernelVariant, E.MpWorldStates, E.MpStepMany,
-                                       E.MpStepTrajectory, E.MpEpisodeStarts, E.MpStepActive, E.MpStepUntil,
-                                       E.MpStepListed)]
-  assert sorted(others) == [40, 48, 56, 64, 72, 80, 88, 96, 104, 112, 120, 136, 176]
-  mine = ctypes.sizeof(E.MpEpisodeStats)
-  assert mine == 224 and mine not in others and mine < 448   # (a snapshot is >= 448 bytes)
-  assert ctypes.sizeof(E.MpEventColumn) == 32 and ctypes.sizeof(E.MpStatsBank) == 32
-
-
-def test_the_abi_is_what_it_was():
-  L = E.load_library()
-  assert L.mp_abi_version() == 8
-  assert len(E.ABI_SYMBOLS) == 30   # (the request rides mp_restore)
-  out = subprocess.run(["nm", "-D", "--defined-only", _build.build_engine()], capture_output=True, text=True,
-                       check=True).stdout
-  exported = sorted(line.split()[-1] for line in out.splitlines()
-                    if line.split() and line.split()[-2] in ("T", "D", "B", "R"))
-  assert exported == sorted(E.ABI_SYMBOLS)
-
-
 def test_the_new_kernel_is_in_the_code_object():
   blob = open(_build.build_engine(), "rb").read()
   assert b"k_episode_stats" in blob

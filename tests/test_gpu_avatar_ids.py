@@ -29,11 +29,6 @@ VIEW, ZAP = substrate.AVATAR_IDS_NAMES
 PLAYERS = {"clean_up": 7, "commons_harvest__open": 16, "territory__rooms": 9, "externality_mushrooms__dense": 5}
 
 
-def _no_faults(eng):
-  # (words 10 and 11 keep the index and the code of the last report; word 9 claims the next)
-  assert not eng.fault_words()[:10].any(), eng.fault_words()[:10]
-
-
 def _same(got, want, what):
   got = got.cpu().numpy() if isinstance(got, torch.Tensor) else got
   want = want.cpu().numpy() if isinstance(want, torch.Tensor) else want
@@ -67,7 +62,7 @@ def case(name):
   hand = torch.from_numpy(HR.hand_rows(name)[0]).to(eng.device)
   bank = torch.cat([played, hand]).contiguous()
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   eng.close()
   host = E.avatar_ids_host(pack, bank.cpu().numpy())
   alive = substrate.StateFields(played.cpu(), substrate.SubstrateStateLayout(E.state_layout(pack), pack_lib.loads(pack))).alive
@@ -110,7 +105,7 @@ def test_both_kernels_equal_the_host_twin(name):
   got = eng.observe_avatar_ids(bank, rows=r, players=p)
   _same(got[0], want_v[r, p], (name, "sampled views")); _same(got[1], want_z[r, p], (name, "sampled views, zap"))
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   eng.close()
 
 
@@ -134,7 +129,7 @@ def test_waves_that_take_several_elements_in_turn():
   eng.observe_avatar_ids(bank, rows=r, players=p, out=out)
   _same(out[0], want_v[r, p], "IN_VIEW, views"); _same(out[1], want_z[r, p], "IN_RANGE, views")
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   eng.close()
 
 
@@ -199,7 +194,7 @@ def test_an_index_out_of_range_is_skipped_and_reported():
   got = eng.observe_avatar_ids()
   _same(got[0], now[0], "after the reports"); _same(got[1], now[1], "after the reports, zap")
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   eng.close()
 
 
@@ -226,7 +221,7 @@ def test_a_level_without_a_zapper(name):
   with pytest.raises(ValueError, match=rf"'{name}' has no Zapper"):
     substrate.build_from_config(leafy, roles=cfg.default_player_roles, num_worlds=6, env_seed=SEED)
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   env.close()
 
 
@@ -332,7 +327,7 @@ def test_the_leaves_follow_every_submission(T):
   assert torch.equal(eng.save_worlds(), twin.engine.save_worlds())
   for e in (eng, twin.engine):
     e.sync()
-    _no_faults(e)
+    util.no_faults(e)
   env.close()
   twin.close()
 
@@ -353,7 +348,7 @@ def test_one_leaf_alone_and_build_substrate():
   with pytest.raises(ValueError, match="need a batched substrate"):
     substrate.build_from_config(_leaf_config(), roles=cfg.default_player_roles, num_worlds=1)
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   env.close()
 
 
@@ -367,7 +362,7 @@ def test_tune_does_not_write_the_registered_leaves():
   want = _twin(eng)
   _same(view, want[0], "after the reset"); _same(zap, want[1], "after the reset, zap")
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   eng.close()
 
 
@@ -393,7 +388,7 @@ def test_a_mixture_of_two_commons_harvest_layouts_shares_the_leaves():
       want = _twin(m.engine)
       _same(whole[0][sl], want[0], (T, i, "the member's slice")); _same(whole[1][sl], want[1], (T, i, "the member's slice, zap"))
       m.engine.sync()
-      _no_faults(m.engine)
+      util.no_faults(m.engine)
     mix.close()
 
 
@@ -448,5 +443,5 @@ def test_in_range_is_who_a_zap_fired_now_hits():
     shadowed += r in tags["shadow"] and in_range[i, 0, 1] == 1 and in_range[i, 0, 2] == 0
   assert some >= len(tags["footprint"]) and shadowed == len(tags["shadow"]) == 4
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   eng.close()

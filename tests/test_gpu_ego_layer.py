@@ -21,10 +21,6 @@ N = 6
 SEED = 5   # (chosen with the CPU oracle: all four facings and dead viewers within 25 random steps)
 
 
-def _no_faults(eng):
-  assert not eng.fault_words()[:10].any(), eng.fault_words()[:10]
-
-
 def _same(got, want, what):
   got = got.cpu().numpy() if isinstance(got, torch.Tensor) else got
   assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape)
@@ -97,7 +93,7 @@ def test_both_kernels_equal_the_model(name, players):
   _same(env.observe_ego_layer(res.states, rows=worlds, players=viewers), want[worlds, viewers],
         (name, "Substrate views"))
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   env.close()
 
 
@@ -131,7 +127,7 @@ def test_edited_windows_and_tori(variant):
   _same(lay, north[-N:], "the bound LAYER")
   _same(eng.observe_ego_layer(), want[-N:], "live worlds")
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   eng.close()
 
 
@@ -178,7 +174,7 @@ def test_equal_stacks_have_equal_pixels_and_the_north_window_does_not():
         failed_north += not _stacks_decide_pixels(north[r, p], rgb[r, p], avatar_layer)
   assert failed_north > 0   # (the power of the check: the north window does not name what RGB shows)
   env.engine.sync()
-  _no_faults(env.engine)
+  util.no_faults(env.engine)
   env.close()
 
 
@@ -259,7 +255,7 @@ def test_the_leaf_follows_every_submission(T):
   assert torch.equal(eng.save_worlds(), twin.engine.save_worlds())
   for e in (eng, twin.engine):
     e.sync()
-    _no_faults(e)
+    util.no_faults(e)
   env.close()
   twin.close()
 
@@ -285,7 +281,7 @@ def test_build_substrate_names_the_leaf_beside_pooled_views():
   _same(ts.observation["LAYER"], _model(eng, bank, north=True), "LAYER")
   assert tuple(ts.observation["RGB"].shape[2:]) == (11, 11, 3)
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   env.close()
 
 
@@ -307,7 +303,7 @@ def test_tune_does_not_write_the_leaf():
     else:
       assert bool((leaf == -7).all())
     eng.sync()
-    _no_faults(eng)
+    util.no_faults(eng)
     eng.close()
 
 
@@ -334,7 +330,7 @@ def test_a_mixture_shares_one_leaf():
       assert torch.equal(leaf[sl], own), (T, i)
       _same(own, _model(m.engine, m.save_state().data), (T, i, "model"))
       m.engine.sync()
-      _no_faults(m.engine)
+      util.no_faults(m.engine)
     assert not torch.equal(leaf[mix.member_slice(0)], leaf[mix.member_slice(1)])
     mix.close()
 
@@ -381,5 +377,5 @@ def test_an_index_out_of_range_leaves_its_element_and_is_reported():
   eng.step(torch.zeros((N, P), dtype=torch.int32, device=eng.device))
   _same(eng.observe_ego_layer(), _model(eng, eng.save_worlds()), "after the reports")
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   eng.close()

@@ -35,11 +35,6 @@ KITCHEN_GROUPS = ["Self", "Avatar*", "OutOfBounds", "*tomato*", "*dish*"]
 FILL = 0xA5
 
 
-def _no_faults(eng):
-  # (words 10 and 11 keep the index and the code of the last report; word 9 claims the next)
-  assert not eng.fault_words()[:10].any(), eng.fault_words()[:10]
-
-
 def _same(got, want, what):
   got = got.cpu().numpy() if isinstance(got, torch.Tensor) else got
   want = want.cpu().numpy() if isinstance(want, torch.Tensor) else want
@@ -154,7 +149,7 @@ def test_live_worlds_saved_rows_the_model_and_the_host_twin_agree(name):
   _both_kernels(eng, bank[-2 * N:], _model(eng, bank[-2 * N:], table64, 64, facing=True), table64, (name, "C = 64"),
                 facing=True, num_classes=64)
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   env.close()
 
 
@@ -203,7 +198,7 @@ def test_edited_windows_and_tori(variant):
   host = E.ego_planes_host(eng.pack_bytes, bank.cpu().numpy(), classes, facing=True, fingerprint=eng.state_fingerprint)
   _same(host, want, "the host twin")
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   eng.close()
 
 
@@ -252,7 +247,7 @@ def test_repeated_rows_sampled_views_and_destinations_on_any_byte(name):
     got = base.cpu().numpy()
     assert (got[:shift] == FILL).all() and (got[shift + n:] == FILL).all()
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   env.close()
 
 
@@ -332,7 +327,7 @@ def test_an_index_or_class_out_of_range_is_skipped_and_reported():
   _same(eng.observe_ego_planes(classes, facing=True), _model(eng, eng.save_worlds(), classes, C, facing=True),
         "after the reports")
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   eng.close()
 
 
@@ -421,7 +416,7 @@ def test_the_registered_tensor_follows_every_submission(T):
   assert torch.equal(eng.save_worlds(), twin.engine.save_worlds())
   for e in (eng, twin.engine):
     e.sync()
-    _no_faults(e)
+    util.no_faults(e)
   env.close()
   twin.close()
 
@@ -440,7 +435,7 @@ def test_tune_does_not_write_the_registered_tensor():
   _same(reg, _model(eng, eng.save_worlds(), classes, 7, facing=True), "after the reset")
   assert int(base[0]) == FILL
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   eng.close()
 
 
@@ -473,7 +468,7 @@ def test_a_mixture_of_two_kitchens_shares_one_tensor():
       _same(whole[sl], own, (T, i, "the member's own call"))
       _same(own, _model(m.engine, m.save_state().data, classes[i], C, facing=True), (T, i, "model"))
       m.engine.sync()
-      _no_faults(m.engine)
+      util.no_faults(m.engine)
     # one table for every member is taken as it is
     shared = mix.observe_ego_planes(classes[0], num_classes=C)
     _same(shared[mix.member_slice(1)], mix._members[1].observe_ego_planes(classes[0], num_classes=C), (T, "one table"))

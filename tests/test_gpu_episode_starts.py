@@ -29,10 +29,6 @@ SCALARS = (E.OBS_REWARD, E.OBS_COLLECTIVE_REWARD, E.OBS_STEP_TYPE, E.OBS_DISCOUN
 MATRIX_KINDS = (E.OBS_INVENTORY, E.OBS_INTERACTION_INVENTORIES, E.OBS_INTERACTION_REWARDS)
 
 
-def _no_faults(eng):
-  assert not eng.fault_words()[:40].any(), eng.fault_words()[:40]
-
-
 def _actions(eng):
   w = np.ones(eng.num_actions)
   w[min(7, eng.num_actions - 1)] = 4
@@ -170,7 +166,7 @@ def test_step_and_step_many_against_the_oracle(name):
         types.append(m.observe_host(E.OBS_STEP_TYPE))
     _coverage(name, types, rows, info)
     e.sync()
-    _no_faults(e)
+    util.no_faults(e, words=40)
     e.close(); m.close()
 
 
@@ -194,7 +190,7 @@ def test_a_rollout_ring_against_the_oracle(name):
     for kind in kinds:
       assert np.array_equal(rings[kind][slot].cpu().numpy(), mrings[kind][slot]), (name, k, kind)
   e.sync()
-  _no_faults(e)
+  util.no_faults(e, words=40)
   e.close(); m.close()
 
 
@@ -258,7 +254,7 @@ def test_a_step_is_step_then_load_worlds(name, fresh):
     assert h[0] != h[1], name
   for e in (a, b):
     e.sync()
-    _no_faults(e)
+    util.no_faults(e, words=40)
     e.close()
 
 
@@ -294,7 +290,7 @@ def test_step_many_is_the_loop_of_steps(name):
   _coverage(name, got["step_type"].cpu().numpy(), rows, info)
   for e in (a, b, c):
     e.sync()
-    _no_faults(e)
+    util.no_faults(e, words=40)
     e.close()
 
 
@@ -312,7 +308,7 @@ def test_step_many_rows_one_family_at_a_time():
       assert torch.equal(value, ref[key]), (kw, key)
     assert torch.equal(e.save_worlds(), full.save_worlds()), kw
     e.sync()
-    _no_faults(e)
+    util.no_faults(e, words=40)
     e.close()
   full.close()
 
@@ -442,7 +438,7 @@ def test_clearing_returns_the_engine_to_what_it_was():
   assert torch.equal(a._bound[E.OBS_WORLD_RGB], b._bound[E.OBS_WORLD_RGB])
   for e in (a, b):
     e.sync()
-    _no_faults(e)
+    util.no_faults(e, words=40)
     e.close()
 
 
@@ -468,7 +464,7 @@ def test_reset_masked_reset_and_load_are_what_they_were():
   assert a.episode_starts is not None and not a.fused   # configuration, not part of a record
   for e in (a, b):
     e.sync()
-    _no_faults(e)
+    util.no_faults(e, words=40)
     e.close()
 
 
@@ -482,7 +478,7 @@ def test_tune_leaves_the_records_and_the_registration():
   a.tune()
   assert torch.equal(a.save_worlds(), before) and a.episode_starts is not None and not a.fused
   a.sync()
-  _no_faults(a)
+  util.no_faults(a, words=40)
   a.close()
 
 

@@ -34,11 +34,6 @@ def _pack(name):
   return util.patch_pack(E.load_pack(name), MAXFRAMES=MAXFRAMES)
 
 
-def _no_faults(eng):
-  eng.sync()
-  assert not eng.fault_words()[:6].any(), eng.fault_words()[:6]
-
-
 def _actions(rng, name, shape, device):
   slots = CLEAN_SLOTS if name == "clean_up" else util.ZAP_HEAVY_SLOTS
   return torch.from_numpy(slots[rng.integers(0, 16, size=shape)].astype(np.int32)).to(device)
@@ -222,8 +217,8 @@ def test_the_identity(name, n, auto_reset):
   assert got["episodes"].min() >= (3 if auto_reset else 1), got["episodes"]
   assert got["total.counts"].sum() > 0 and got["total.pairs"].sum() > 0
   assert (got["dropped"] == 0).all()
-  _no_faults(a)
-  _no_faults(b.e)
+  util.no_faults(a, sync=True)
+  util.no_faults(b.e, sync=True)
   a.close()
   b.e.close()
 
@@ -276,8 +271,8 @@ def test_columns_empty_needs_no_events_row_and_a_request_without_its_rows_is_ref
       shape, dtype=getattr(torch, dtype))))
   with pytest.raises(ValueError):
     b.set_episode_stats((), out=host)
-  _no_faults(a)
-  _no_faults(b)
+  util.no_faults(a, sync=True)
+  util.no_faults(b, sync=True)
   a.close()
   b.close()
 
@@ -330,7 +325,7 @@ def test_the_fused_frame_launch_and_a_ring_give_the_same_statistics():
   now = model.flatten(stats[1].arrays)
   assert all(frozen[k].tobytes() == now[k].tobytes() for k in frozen), "a cleared registration is not written"
   for e in engines + (never,):
-    _no_faults(e)
+    util.no_faults(e, sync=True)
     e.close()
 
 
@@ -357,7 +352,7 @@ def test_a_substrate_with_a_rollout_ring_and_a_one_world_substrate():
   plain.set_episode_stats(None)
   assert plain.engine.episode_stats is None
   for env in (ring, plain):
-    _no_faults(env.engine)
+    util.no_faults(env.engine, sync=True)
     env.close()
   single = substrate.build("clean_up", roles=cfg.default_player_roles)
   with pytest.raises(ValueError, match="num_worlds"):
@@ -413,7 +408,7 @@ def test_tally_events_on_crafted_rows_and_on_a_real_result():
     e.tally_events(r["events"][:, :, :5])
   with pytest.raises(ValueError):
     e.tally_events(r["events"], ("nothing.player",))
-  _no_faults(e)
+  util.no_faults(e, sync=True)
   e.close()
 
 
@@ -444,6 +439,6 @@ def test_a_mixture_registers_each_member_its_slice():
   mix.set_episode_stats(None)
   assert all(e.episode_stats is None for e in mix.engines)
   for e in mix.engines + alone.engines:
-    _no_faults(e)
+    util.no_faults(e, sync=True)
   mix.close()
   alone.close()

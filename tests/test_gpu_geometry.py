@@ -24,10 +24,6 @@ FEW_VIEWS = [(1, engine.OBS_RGB, True), (8, engine.OBS_RGB_POOL8, False)]
 IDS = [geometry.variant_id(v) for v in geometry.ACCEPTED]
 
 
-def _no_faults(eng):
-  assert not eng.fault_words()[:6].any(), eng.fault_words()[:6]
-
-
 def _asymmetric(v):
   view = v.get("view")
   return view is not None and (view[0] != view[1] or view[2] != view[3])
@@ -110,7 +106,7 @@ def _run(v, n, steps, setups=ALL_VIEWS, dev=None, unfused=None, seed=0, looks=()
           assert np.array_equal(host[agent][w], want), ("RGB", agent, s, w)
           if layer:
             assert np.array_equal(host[engine.OBS_LAYER][w], layers[w]), ("LAYER", s, w)
-        _no_faults(e)
+        util.no_faults(e)
     if _asymmetric(v):
       assert faced.all(), "an avatar did not face all four ways"
   finally:
@@ -182,7 +178,7 @@ def test_layer_alone_on_the_largest_map():
       assert np.array_equal(grid[w], og) and np.array_equal(avat[w], oa), w
       assert np.array_equal(glob[w], ogl), w
       assert np.array_equal(got[w], np.stack([o.layer_view(p) for p in range(o.P)])), w
-    _no_faults(e)
+    util.no_faults(e)
   finally:
     for o in oracles:
       o.close()
@@ -233,7 +229,7 @@ def test_ticket_division_past_two_to_the_32():
       want = engine.pool_rgb(np.stack([o.render_agent(p) for p in range(P)]), 8)
       assert not (want[P - 1, -1] == 201).all(), w   # (the sentinel is not what the row holds)
       assert np.array_equal(got[i], want), w
-    _no_faults(e)
+    util.no_faults(e)
   finally:
     for o in oracles:
       o.close()

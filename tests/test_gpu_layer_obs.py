@@ -23,10 +23,6 @@ PACKS = sorted(f[:-4] for f in os.listdir(ASSETS) if f.endswith(".mpk"))
 POOL_OF = {k: f for f, k in engine.OBS_RGB_POOL.items()}
 
 
-def _no_faults(eng):
-  assert not eng.fault_words()[:6].any(), eng.fault_words()[:6]
-
-
 def _layers(oracles):
   return np.stack([np.stack([o.layer_view(p) for p in range(o.P)]) for o in oracles])
 
@@ -91,7 +87,7 @@ def _run(name, n, steps, looks, seed=0, pack=None, weights=None, agent=None, wor
           host = bufs[engine.OBS_WORLD_RGB].cpu().numpy()
           for w, o in enumerate(oracles):
             assert np.array_equal(host[w], engine.pool_rgb(o.render_world(), world_pool)), (name, s, w)
-      _no_faults(e)
+      util.no_faults(e)
   finally:
     for o in oracles:
       o.close()
@@ -187,7 +183,7 @@ def test_benchmarked_size():
         assert np.array_equal(lay[w].cpu().numpy(), want[(w, s)][0]), (with_world, s, w)
         if with_world:
           assert np.array_equal(wv[w].cpu().numpy(), want[(w, s)][1]), (with_world, s, w)
-    _no_faults(e)
+    util.no_faults(e)
     e.close()
     del lay, wv
     torch.cuda.empty_cache()
@@ -235,7 +231,7 @@ def test_layer_ring(name, pixels):
     for w, o in enumerate(oracles):
       o.step(acts[0, w])
     assert np.array_equal(ring[(steps + 1) % T].cpu().numpy(), _layers(oracles))
-    _no_faults(e)
+    util.no_faults(e)
   finally:
     for o in oracles:
       o.close()
@@ -261,7 +257,7 @@ def test_layer_ring_tuned_before_use():
   for w, o in enumerate(oracles):
     o.step(a[w])
   assert np.array_equal(ring[1].cpu().numpy(), _layers(oracles))
-  _no_faults(e)
+  util.no_faults(e)
   for o in oracles:
     o.close()
   e.close()
@@ -311,7 +307,7 @@ def test_build_substrate_with_layer():
         ring = env.rollout["observation"]["LAYER"]
         assert tuple(ring.shape) == (T, n, 7) + spec["LAYER"].shape
         assert torch.equal(ring[env.slot], ts.observation["LAYER"])
-      _no_faults(env.engine)
+      util.no_faults(env.engine)
     finally:
       env.close()
       for o in refs:
@@ -352,7 +348,7 @@ def test_symbolic_only_substrate_beside_pooled_views():
       for w, o in enumerate(oracles):
         o.step(a[w])
     for env in envs:
-      _no_faults(env.engine)
+      util.no_faults(env.engine)
   finally:
     for env in envs:
       env.close()

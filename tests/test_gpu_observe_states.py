@@ -37,10 +37,6 @@ def _same_leaf(kind, got, want, what):
     assert tuple(a[0]) == tuple(b[0]) and sorted(map(tuple, a[1:1 + n].tolist())) == sorted(map(tuple, b[1:1 + n].tolist())), what
 
 
-def _no_faults(eng):
-  assert not eng.fault_words()[:10].any(), eng.fault_words()[:10]
-
-
 # 1. against the launches that wrote the rows
 @pytest.mark.parametrize("name", recipe.PACKS)
 def test_rows_are_drawn_as_the_launches_that_wrote_them_drew_them(name):
@@ -61,7 +57,7 @@ def test_rows_are_drawn_as_the_launches_that_wrote_them_drew_them(name):
     _same(e.observe_states(road["all"][13:14], kind), road["all_views"][kind][13:14], (name, kind, "one row"))
     _same(e.observe_states(road["all"], kind, rows=[13]), road["all_views"][kind][13:14], (name, kind, "rows=[13]"))
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -82,7 +78,7 @@ def test_pooled_kinds_equal_pool_rgb_of_the_full_views(name, world_pool):
       assert np.array_equal(got.cpu().numpy(), pooled[rows]), (name, kind, count)
     assert np.array_equal(e.observe_states(road["all"], kind).cpu().numpy(), pooled), (name, kind, "contiguous")
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -153,7 +149,7 @@ def test_the_engine_is_left_as_it_was():
       _same_leaf(k, bufs[k], twin_bufs[k], ("step", s, k))
   assert np.array_equal(e.snapshot(), twin.snapshot()) and e.counters() == twin.counters()
   assert e.ring == twin.ring
-  _no_faults(e)
+  util.no_faults(e)
   e.close(); twin.close()
 
 
@@ -195,7 +191,7 @@ def test_rows_of_another_engine_are_drawn_and_rows_of_another_level_refused():
     _same(small.observe_states(road["all"], kind, rows=rows), road["all_views"][kind].flip(0),
           ("25 gathered rows on 2 worlds", kind))
   small.sync()
-  _no_faults(small)
+  util.no_faults(small)
   # rows of another level
   foreign = engine.Engine(recipe.pack("coins"), 2, device=0)
   foreign.reset()
@@ -270,7 +266,7 @@ def test_refusals_happen_on_the_host_and_leave_everything_alone():
   # nothing was launched: dst and the engine are as they were
   e.sync()
   assert bool((dst == 0xAB).all()) and np.array_equal(e.snapshot(), snap)
-  _no_faults(e)
+  util.no_faults(e)
   # a rows[i] outside the bank is never read: its element stays, the next sync() says so, once
   bad = torch.tensor([3, 99, 1, -1, 3], dtype=torch.int32, device=e.device)
   keep = torch.tensor([0, 2, 4], device=e.device)
@@ -305,5 +301,5 @@ def test_refusals_happen_on_the_host_and_leave_everything_alone():
       _same(out[i], blank, ("beyond the eighth", kind, i))
   e.sync()
   assert np.array_equal(e.snapshot(), snap)
-  _no_faults(e)
+  util.no_faults(e)
   e.close()

@@ -36,10 +36,6 @@ def _same_leaf(kind, got, want, what):
     assert tuple(a[0]) == tuple(b[0]) and sorted(map(tuple, a[1:1 + n].tolist())) == sorted(map(tuple, b[1:1 + n].tolist())), what
 
 
-def _no_faults(eng):
-  assert not eng.fault_words()[:10].any(), eng.fault_words()[:10]
-
-
 def _player_kinds(road):
   return tuple(k for k in road["kinds"] if k != E.OBS_WORLD_RGB)
 
@@ -91,7 +87,7 @@ def test_sampled_views_are_what_the_step_launches_drew(name):
           (name, kind, "rows=None"))
     _same(e.observe_views(road["all"], kind, [P - 1] * R_ALL), full[:, P - 1], (name, kind, "rows=None, 25"))
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -124,7 +120,7 @@ def test_pooled_views_equal_pool_rgb_of_the_full_views(name):
     assert np.array_equal(host[at:at + want.size].reshape(want.shape), want), (name, at)
     assert (host[:at] == 0xAB).all() and (host[at + want.size:] == 0xAB).all(), (name, at)
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -164,7 +160,7 @@ def test_geometries_against_observe_states_and_the_oracle(v):
     got[kind] = e.observe_views(bank, kind, players, rows)
     _same(got[kind], whole[torch.arange(count), torch.from_numpy(players)], (v, kind))
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   oracles = util.make_oracles(blob, 2)
   try:
     for w, o in enumerate(oracles):
@@ -229,7 +225,7 @@ def test_the_engine_is_left_as_it_was():
       _same_leaf(k, bufs[k], twin_bufs[k], ("step", s, k))
   assert np.array_equal(e.snapshot(), twin.snapshot()) and e.counters() == twin.counters()
   assert e.ring == twin.ring
-  _no_faults(e)
+  util.no_faults(e)
   e.close(); twin.close()
 
 
@@ -249,7 +245,7 @@ def test_rows_of_another_engine_are_drawn_and_rows_of_another_level_refused():
     _same(e.observe_views(bank, kind, players, rows, fingerprint=other.state_fingerprint),
           bufs[kind][rows, players], ("travel", kind))
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   foreign = engine.Engine(recipe.pack("coins"), 2, device=0)
   foreign.reset()
   frows = foreign.save_worlds()
@@ -340,7 +336,7 @@ def test_refusals_happen_on_the_host_and_leave_everything_alone():
   # nothing was launched: dst and the engine are as they were
   e.sync()
   assert bool((dst == 0xAB).all()) and np.array_equal(e.snapshot(), snap)
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -369,14 +365,14 @@ def test_bad_indices_leave_their_elements_alone_and_are_reported_once():
       with pytest.raises(ValueError, match=r"MpStatesView: " + message):
         e.sync()
       e.sync()   # reported once
-      _no_faults(e)
+      util.no_faults(e)
       for i in bad:   # EVERY such element, however many
         assert bool((out[i] == 7).all()), (kind, i)
       want = e.observe_views(bank, kind, [players[i] for i in good], [rows[i] for i in good])
       _same(out[good], want, ("the elements whose indices are a row and a player", kind))
   e.sync()
   assert np.array_equal(e.snapshot(), snap)
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 

@@ -19,10 +19,6 @@ PACKS = sorted(f[:-4] for f in os.listdir(ASSETS) if f.endswith(".mpk"))
 KS = (2, 4, 8)
 
 
-def _no_faults(eng):
-  assert not eng.fault_words()[:6].any(), eng.fault_words()[:6]
-
-
 def _run_against_oracle(name, n, steps, views, dev=None, seed=0, looks=()):
   """Engines (one per entry of `views`: a tuple of kinds bound together) stepped with the same
   random actions as n oracles; state, rewards and every bound view compared at each step in
@@ -65,7 +61,7 @@ def _run_against_oracle(name, n, steps, views, dev=None, seed=0, looks=()):
               pk = {kk: f for f, kk in engine.OBS_RGB_POOL.items()}[k]
               want = engine.pool_rgb(full[w], pk)
             assert np.array_equal(v[w], want), (name, k, s, w)
-        _no_faults(e)
+        util.no_faults(e)
   finally:
     for o in oracles:
       o.close()
@@ -103,7 +99,7 @@ def _pooled_vs_full(name, n, steps, dev_list):
   for s in range(steps):
     full.step(acts[s])
     want.append(engine.pool_rgb(rgb.cpu().numpy(), 8))
-  _no_faults(full)
+  util.no_faults(full)
   full.close()
   del rgb
   torch.cuda.empty_cache()
@@ -116,7 +112,7 @@ def _pooled_vs_full(name, n, steps, dev_list):
     for s in range(steps):
       e.step(acts[s])
       assert np.array_equal(out.cpu().numpy(), want[s]), (name, dev, tune, s)
-    _no_faults(e)
+    util.no_faults(e)
     e.close()
 
 
@@ -156,7 +152,7 @@ def test_observe_pooled_without_a_bound_view(name):
     got = e.observe(engine.OBS_RGB_POOL[k]).cpu().numpy()
     assert np.array_equal(got, engine.pool_rgb(full, k)), (name, k)
   assert np.array_equal(e.observe(engine.OBS_RGB).cpu().numpy(), full)
-  _no_faults(e)
+  util.no_faults(e)
   for o in oracles:
     o.close()
   e.close()
@@ -191,8 +187,8 @@ def test_rollout_ring_pooled():
   ring = a.rollout["observation"]["RGB"]
   for t in range(steps + 1 - T, steps + 1):
     assert np.array_equal(ring[t % T].cpu().numpy(), seen[t].cpu().numpy()), t
-  _no_faults(a.engine)
-  _no_faults(b.engine)
+  util.no_faults(a.engine)
+  util.no_faults(b.engine)
   a.close()
   b.close()
 
@@ -206,7 +202,7 @@ def test_api_shape_and_spec():
   spec = env.observation_spec()[0]["RGB"]
   assert spec.shape == (11, 11, 3) and spec.dtype == np.uint8
   assert "WORLD.RGB" in ts.observation
-  _no_faults(env.engine)
+  util.no_faults(env.engine)
   env.close()
 
 
@@ -231,7 +227,7 @@ def test_conformance_with_rgb_pool(name):
     rgb = env.observation_spec()[0]["RGB"]
     full = factory.timestep_spec().observation["RGB"]
     assert rgb.shape == (full.shape[0] // 8, full.shape[1] // 8, 3)
-    _no_faults(env.engine)
+    util.no_faults(env.engine)
 
 
 def test_switching_the_agent_view_beside_a_tuned_ring():
@@ -261,7 +257,7 @@ def test_switching_the_agent_view_beside_a_tuned_ring():
     full = np.stack([o.render_agent(p) for p in range(e.P)])
     assert np.array_equal(got[w], engine.pool_rgb(full, 8)), w
     assert np.array_equal(world[w], o.render_world()), w
-  _no_faults(e)
+  util.no_faults(e)
   e.unbind(engine.OBS_RGB_POOL8)
   rgb = e.bind(engine.OBS_RGB)
   e.step(torch.from_numpy(acts[0]).to(e.device))
@@ -270,7 +266,7 @@ def test_switching_the_agent_view_beside_a_tuned_ring():
   got = rgb.cpu().numpy()
   for w, o in enumerate(oracles):
     assert np.array_equal(got[w], np.stack([o.render_agent(p) for p in range(e.P)])), w
-  _no_faults(e)
+  util.no_faults(e)
   for o in oracles:
     o.close()
   e.close()

@@ -21,10 +21,6 @@ KS = (2, 4, 8)
 POOL_OF = {k: f for f, k in engine.OBS_RGB_POOL.items()}
 
 
-def _no_faults(eng):
-  assert not eng.fault_words()[:6].any(), eng.fault_words()[:6]
-
-
 def _run_against_oracle(name, n, steps, setups, dev=None, seed=0, looks=(), unfused=None):
   """One engine per entry of `setups` — (world_pool, per-agent kind or None) — WORLD.RGB and that
   per-agent view bound together, stepped with the same random actions as n oracles; state,
@@ -74,7 +70,7 @@ def _run_against_oracle(name, n, steps, setups, dev=None, seed=0, looks=(), unfu
           if agent is not None:
             want = agents[w] if agent == engine.OBS_RGB else engine.pool_rgb(agents[w], POOL_OF[agent])
             assert np.array_equal(host[agent][w], want), (name, kw, agent, s, w)
-        _no_faults(e)
+        util.no_faults(e)
   finally:
     for o in oracles:
       o.close()
@@ -136,7 +132,7 @@ def test_benchmarked_sizes_world_pooled_equals_pooled_full(name, n):
     full.step(acts[s])
     want_w.append({k: _pool_dev(wf, k) for k in KS})
     want_a.append(_pool_dev(af, 8))
-  _no_faults(full)
+  util.no_faults(full)
   full.close()
   del wf, af
   torch.cuda.empty_cache()
@@ -153,7 +149,7 @@ def test_benchmarked_sizes_world_pooled_equals_pooled_full(name, n):
       assert torch.equal(out, want_w[s][kw]), (name, kw, agent, s)
       if a is not None:
         assert torch.equal(a, want_a[s]), (name, kw, agent, s)
-    _no_faults(e)
+    util.no_faults(e)
     e.close()
     del out, a
     torch.cuda.empty_cache()
@@ -184,7 +180,7 @@ def test_observe_world_pooled_without_a_bound_view(name):
     got = e.observe(engine.OBS_WORLD_RGB).cpu().numpy()
     assert got.shape == (n, world.shape[1] // k, world.shape[2] // k, 3)
     assert np.array_equal(got, engine.pool_rgb(world, k)), (name, k)
-    _no_faults(e)
+    util.no_faults(e)
     e.close()
   for o in oracles:
     o.close()
@@ -212,7 +208,7 @@ def test_rollout_ring_of_pooled_world(name, kw):
   got = ring.cpu().numpy()
   for t in range(steps + 1 - T, steps + 1):
     assert np.array_equal(got[t % T], seen[t]), t
-  _no_faults(e)
+  util.no_faults(e)
   for o in oracles:
     o.close()
   e.close()
@@ -238,7 +234,7 @@ def test_placed_pooled_world_view():
   got = out.cpu().numpy()
   for w, o in enumerate(oracles):
     assert np.array_equal(got[w], engine.pool_rgb(o.render_world(), 2)), w
-  _no_faults(e)
+  util.no_faults(e)
   for o in oracles:
     o.close()
   e.close()
@@ -260,7 +256,7 @@ def test_box_fill_and_misaligned_buffers_are_refused():
   with pytest.raises(ValueError, match="world_pool"):
     e.box_fill(engine.OBS_WORLD_RGB)
   e.reset()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -274,20 +270,20 @@ def test_api_shapes_and_spec():
   spec = env.observation_spec()[0]
   assert spec["WORLD.RGB"].shape == (84, 120, 3) and spec["WORLD.RGB"].dtype == np.uint8
   assert spec["RGB"].shape == (11, 11, 3)
-  _no_faults(env.engine)
+  util.no_faults(env.engine)
   env.close()
   one = substrate.build("clean_up", roles=roles, world_rgb_pool=8)
   ts = one.reset()
   ts = one.step([0] * 7)
   for obs in ts.observation:
     assert obs["WORLD.RGB"].shape == (21, 30, 3) and obs["RGB"].shape == (88, 88, 3)
-  _no_faults(one.engine)
+  util.no_faults(one.engine)
   one.close()
   ringed = substrate.build("clean_up", roles=roles, num_worlds=4, world_rgb_pool=4, rollout_length=3)
   ringed.reset()
   ringed.step(torch.zeros((4, 7), dtype=torch.int32, device="cuda"))
   assert tuple(ringed.rollout["observation"]["WORLD.RGB"].shape) == (3, 4, 42, 60, 3)
-  _no_faults(ringed.engine)
+  util.no_faults(ringed.engine)
   ringed.close()
 
 
@@ -313,4 +309,4 @@ def test_conformance_with_world_rgb_pool(name):
     full = factory.timestep_spec().observation
     assert spec["WORLD.RGB"].shape == (full["WORLD.RGB"].shape[0] // 8, full["WORLD.RGB"].shape[1] // 8, 3)
     assert spec["RGB"].shape == (full["RGB"].shape[0] // 4, full["RGB"].shape[1] // 4, 3)
-    _no_faults(env.engine)
+    util.no_faults(env.engine)

@@ -22,10 +22,6 @@ E = engine
 N = R.N
 
 
-def _no_faults(eng):
-  assert not eng.fault_words()[:6].any(), eng.fault_words()[:6]
-
-
 def _clean(eng, verdicts, what):
   v = verdicts.cpu().numpy()
   lay = eng.state_layout()
@@ -53,7 +49,7 @@ def test_rows_the_engine_produces_pass(name):
   e.load_worlds(bank, [7, -1, 12, 24, 0])
   _clean(e, e.check_states(e.save_worlds()), "load")
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
   # frozen worlds: no auto-reset, eight steps past the end of the episode
   e = engine.Engine(R.pack(name), N, device=0, auto_reset=False)
@@ -61,7 +57,7 @@ def test_rows_the_engine_produces_pass(name):
   many = e.step_many(A, states=True)["states"]
   _clean(e, e.check_states(many[-3:].reshape(3 * N, -1)), "frozen")
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -164,7 +160,7 @@ def test_checked_load_refuses_the_malformed_row_only(name, ring):
   eng.sync()
   env.step(A[0]); twin.step(A[0])
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   assert torch.equal(_tail_free(eng, env.save_state().data[1:2]), _tail_free(eng, twin.save_state().data[1:2]))
   env.close(); twin.close()
 
@@ -227,14 +223,14 @@ def test_a_moved_avatar_passes_loads_and_steps(name):
   noop = np.zeros((2, P), np.int32)
   env.step(noop); twin.step(noop)
   eng.sync(); twin._eng.sync()
-  _no_faults(eng); _no_faults(twin._eng)
+  util.no_faults(eng); util.no_faults(twin._eng)
   for k in range(1, 9):
     env.step(A[k]); twin.step(A[k])
   a, b = env.save_state().data, twin.save_state().data
   assert torch.equal(a, b)
   assert not env.check_states(env.save_state()).cpu().numpy().any()
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   env.close(); twin.close()
 
 
@@ -269,7 +265,7 @@ def test_an_edited_seed_needs_the_orders_cache_cleared():
   assert not torch.equal(edited[0, :planes], plain[0, :planes])   # another continuation
   assert torch.equal(_tail_free(env._eng, edited[1:2]), _tail_free(env._eng, plain[1:2]))   # world 1: untouched
   env._eng.sync()
-  _no_faults(env._eng)
+  util.no_faults(env._eng)
   env.close()
 
 
@@ -292,5 +288,5 @@ def test_a_check_changes_nothing_of_the_engine():
   for k, v in before[3].items():
     assert torch.equal(v, after[3][k]), k
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()

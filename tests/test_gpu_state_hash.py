@@ -22,10 +22,6 @@ N = R.N
 SENTINEL = -0x0123456789ABCDEF
 
 
-def _no_faults(eng):
-  assert not eng.fault_words()[:10].any(), eng.fault_words()[:10]
-
-
 def _stepped(name, n=N, steps=20, seed=7, **kw):
   """An engine on the recipe's pack after `steps` seeded random steps (one launch; the recipe's
   episodes end at step 16, so the worlds are four steps into their second episode)."""
@@ -78,7 +74,7 @@ def test_device_hashes_are_the_host_forms(name):
   assert e._L.mp_snapshot(e._h, ctypes.addressof(req), ctypes.sizeof(req)) == 0
   assert np.array_equal(mask, C.numpy_mask(lay, planes=(lay.grid_planes - 1,)))
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -96,7 +92,7 @@ def test_the_arena_with_three_of_its_players():
   spec = dict(planes=(lay.avatar_layer,), fields=("player_block", "ax"))
   assert np.array_equal(e.hash_worlds(**spec).cpu().numpy(), C.numpy_hash(rows, C.numpy_mask(lay, **spec)))
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -145,7 +141,7 @@ def test_invariances_of_the_default_spec():
   got = edited(later)
   assert got[3] != h[3] and torch.equal(got[[0, 1, 2, 4]], h[[0, 1, 2, 4]])
   eng.sync(); twin._eng.sync()
-  _no_faults(eng); _no_faults(twin._eng)
+  util.no_faults(eng); util.no_faults(twin._eng)
   env.close(); twin.close()
 
 
@@ -169,7 +165,7 @@ def test_distinct_hashes_count_distinct_masked_rows():
   same = inverse.cpu().numpy()
   assert all((same[i] == same[j]) == (src[i] == src[j]) for i in range(n) for j in range(0, n, 7))
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -221,7 +217,7 @@ def test_a_custom_spec_is_a_cell():
   with pytest.raises(ValueError, match="no grid plane"):
     env.hash_worlds(planes=(lay.grid_planes,))
   env._eng.sync()
-  _no_faults(env._eng)
+  util.no_faults(env._eng)
   env.close()
 
 
@@ -246,7 +242,7 @@ def test_a_row_index_outside_the_bank_keeps_its_element():
   e.step(np.zeros((N, e.P), np.int32))
   assert torch.equal(e.hash_worlds(), e.hash_states(e.save_worlds()))
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -313,7 +309,7 @@ def test_refusals_launch_nothing():
   with pytest.raises(ValueError, match="out must be"):
     e.hash_states(bank, out=out)
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -338,5 +334,5 @@ def test_a_hash_changes_nothing_of_the_engine():
   for k, v in before[3].items():
     assert torch.equal(v, after[3][k]), k
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import states_recipe as R
+import util
 from engine_model import ModelEngine
 from meltingpot_amd import engine, substrate
 from test_gpu_episode_starts import PIXEL_PACKS, _plan, _same_as_model, _same_events
@@ -41,11 +42,6 @@ def _mask():
 
 
 MASK = _mask()
-
-
-def _no_faults(eng):
-  eng.sync()
-  assert not eng.fault_words()[:6].any(), eng.fault_words()[:6]
 
 
 def _obs_kinds(name):
@@ -101,7 +97,7 @@ def _all_rows(obs):
 
 def _close(*engines):
   for e in engines:
-    _no_faults(e)
+    util.no_faults(e, sync=True)
     e.close()
 
 

@@ -23,10 +23,6 @@ END = 16 - AHEAD - 1  # so row END is the episode's LAST step (16) and row END +
 SENTINEL = -0x0123456789ABCDEF
 
 
-def _no_faults(eng):
-  assert not eng.fault_words()[:10].any(), eng.fault_words()[:10]
-
-
 def _engines(name, count, **kw):
   """`count` engines of the recipe's pack, each AHEAD steps into the recipe's actions."""
   out = []
@@ -60,7 +56,7 @@ def test_hash_rows_equal_the_hashes_of_the_state_rows_and_of_the_loop(name, auto
   assert a.counters() == b.counters() == c.counters()
   for e in (a, b, c):
     e.sync()
-    _no_faults(e)
+    util.no_faults(e)
     e.close()
 
 
@@ -88,7 +84,7 @@ def test_a_world_never_reset_writes_no_hash_rows():
     b.step(A[k])
     assert torch.equal(out[k, live], b.hash_worlds(live)), k
   a.sync()
-  _no_faults(a)
+  util.no_faults(a)
   a.close(); b.close()
 
 
@@ -104,7 +100,7 @@ def test_hashes_states_and_layer_in_one_call_are_the_separate_calls(name):
   assert torch.equal(a.hash_states(both["states"].view(K * N, -1)).view(K, N), hashes)
   for e in (a, b, c, d):
     e.sync()
-    _no_faults(e)
+    util.no_faults(e)
     e.close()
 
 
@@ -123,7 +119,7 @@ def test_the_hash_row_changes_nothing_else():
     assert torch.equal(abufs[kind], bbufs[kind]), kind
   for e in (a, b):
     e.sync()
-    _no_faults(e)
+    util.no_faults(e)
     e.close()
 
 
@@ -211,5 +207,5 @@ def test_hash_row_refusals_launch_nothing():
     e.step_many(A, out={"hashes": torch.zeros((Ks, N + 1), dtype=torch.int64, device=e.device)})
   for eng in (e, twin):
     eng.sync()
-    _no_faults(eng)
+    util.no_faults(eng)
     eng.close()

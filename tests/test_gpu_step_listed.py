@@ -15,11 +15,12 @@ import pytest
 import torch
 
 import states_recipe as R
+import util
 from engine_model import ModelEngine
 from meltingpot_amd import engine, substrate
 from test_gpu_episode_starts import PIXEL_PACKS, _plan, _same_as_model, _same_events
 from test_gpu_step_active import (KITCHEN, _actions, _all_rows, _close, _engine, _keys, _leaves,
-                                  _no_faults, _obs_kinds, _same, _same_engines, _same_leaves)
+                                  _obs_kinds, _same, _same_engines, _same_leaves)
 
 pytestmark = pytest.mark.gpu
 
@@ -235,7 +236,7 @@ def test_seventy_steps_with_lengths_through_the_substrate():
   assert torch.equal(a.hash_worlds(), b.hash_worlds()) and a.engine.counters() == b.engine.counters()
   assert tuple(r.timestep.step_type.shape) == (N,) and torch.equal(r.timestep.reward, t.timestep.reward)
   for env in (a, b):
-    _no_faults(env.engine)
+    util.no_faults(env.engine, sync=True)
     env.close()
 
 
@@ -535,5 +536,5 @@ def test_substrate_surface():
   b.load_state(picked, [-1, 0, 1, -1, -1])
   assert torch.equal(b.hash_worlds()[[1, 2]], r.hashes[5, [0, 2]])
   for env in (a, b):
-    _no_faults(env.engine)
+    util.no_faults(env.engine, sync=True)
     env.close()

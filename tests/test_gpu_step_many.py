@@ -29,10 +29,6 @@ FIVE = {"reward": E.OBS_REWARD, "collective_reward": E.OBS_COLLECTIVE_REWARD,
         "step_type": E.OBS_STEP_TYPE, "discount": E.OBS_DISCOUNT, "events": E.OBS_EVENTS}
 
 
-def _no_faults(eng):
-  assert not eng.fault_words()[:6].any(), eng.fault_words()[:6]
-
-
 def _engine(pack, n, kinds=SCALARS, **kw):
   e = engine.Engine(pack, n, device=0, **kw)
   bufs = {k: e.bind(k) for k in kinds}
@@ -85,7 +81,7 @@ def _same_engines(a, abufs, b, bbufs, what):
   _same_bufs(abufs, bbufs, what)
   assert torch.equal(a.save_worlds(), b.save_worlds()), what
   assert a.counters() == b.counters(), what
-  _no_faults(a); _no_faults(b)
+  util.no_faults(a); util.no_faults(b)
 
 
 def _supported(pack):
@@ -146,7 +142,7 @@ def test_sixty_steps_in_one_launch_match_the_oracle(name):
     assert np.array_equal(glob[w], ogl), (name, w)
     o.close()
   assert np.array_equal(bufs[E.OBS_REWARD].cpu().numpy(), rew[K - 1])
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -361,7 +357,7 @@ def test_forks_of_one_state_run_different_sequences():
       acts[3] = B[k, j]
       src.step(acts)
       assert torch.equal(sbufs[E.OBS_REWARD][3], got[k, j]), (j, k)
-  _no_faults(src); _no_faults(fork)
+  util.no_faults(src); util.no_faults(fork)
   src.close(); fork.close()
 
 
@@ -397,7 +393,7 @@ def test_at_size_sampled_worlds_match_the_oracle():
     og, oa, ogl = o.dump()
     assert np.array_equal(grid[w], og) and np.array_equal(avat[w], oa) and np.array_equal(glob[w], ogl), w
     o.close()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 

@@ -22,10 +22,6 @@ N, K = recipe.N, recipe.STEPS
 ENV_SEED = 0x5EED0123456789AB
 
 
-def _no_faults(eng):
-  assert not eng.fault_words()[:10].any(), eng.fault_words()[:10]
-
-
 def _pair(name, kinds=(), **kw):
   a = engine.Engine(recipe.pack(name), N, device=0, **kw)
   b = engine.Engine(recipe.pack(name), N, device=0, **kw)
@@ -68,7 +64,7 @@ def test_state_rows_equal_the_saves_of_the_loop(name, auto):
   assert torch.equal(a.save_worlds(), b.save_worlds()) and torch.equal(a.save_worlds(), plain.save_worlds())
   assert a.counters() == b.counters() == plain.counters()
   for eng in (a, b, plain):
-    _no_faults(eng)
+    util.no_faults(eng)
     eng.close()
 
 
@@ -87,7 +83,7 @@ def test_a_world_never_reset_writes_no_state_rows():
   for k in range(6):
     b.step(A[k])
     assert torch.equal(out[k, live], b.save_worlds(live)), k
-  _no_faults(a)
+  util.no_faults(a)
   a.close(); b.close()
 
 
@@ -107,7 +103,7 @@ def test_state_rows_draw_what_the_observation_rows_hold(name):
     picked = torch.stack([got[kind][k, w] for k, w in ((16, 2), (3, 4), (15, 0), (23, 1))])
     assert torch.equal(e.observe_states(bank, kind, rows=rows), picked), (name, kind, "rows")
   e.sync()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -242,7 +238,7 @@ def test_state_row_refusals_launch_nothing():
     assert torch.equal(buf[k * block:(k + 1) * block].view(N, S), twin.save_worlds()), k
   with pytest.raises(ValueError, match="states"):
     e.step_many(A, out={"states": torch.zeros((Ks, N, S + 1), dtype=torch.uint8, device=e.device)})
-  _no_faults(e)
+  util.no_faults(e)
   e.close(); twin.close()
 
 

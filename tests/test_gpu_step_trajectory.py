@@ -31,10 +31,6 @@ MP_EVENT_INTERACTION = 11
 MP_ERR_UNSUPPORTED = -5
 
 
-def _no_faults(eng):
-  assert not eng.fault_words()[:6].any(), eng.fault_words()[:6]
-
-
 def _engine(pack, n, kinds=(), **kw):
   e = engine.Engine(pack, n, device=0, **kw)
   bufs = {k: e.bind(k) for k in kinds}
@@ -110,7 +106,7 @@ def _same_engines(a, b, kinds, what):
           b._bound[kind] if kind in b._bound else b.observe(kind), kind, (what, "final"))
   assert torch.equal(a.save_worlds(), b.save_worlds()), what
   assert a.counters() == b.counters(), what
-  _no_faults(a); _no_faults(b)
+  util.no_faults(a); util.no_faults(b)
 
 
 def _many(e, A, kinds, **kw):
@@ -308,7 +304,7 @@ def test_sixty_steps_of_rows_match_the_oracle(name):
         assert np.array_equal(got[E.OBS_INVENTORY][k, w], inv), at
         assert np.array_equal(got[E.OBS_INTERACTION_INVENTORIES][k, w], inter), at
     o.close()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -531,7 +527,7 @@ def test_engine_ring_of_level_kinds():
     changed = changed or bool((got[E.OBS_INVENTORY][0] != got[E.OBS_INVENTORY][K - 1]).any())
   assert changed, "no inventory changed in 60 steps: the slots cannot be told apart"
   assert torch.equal(a.save_worlds(), b.save_worlds())
-  _no_faults(a)
+  util.no_faults(a)
   a.close(); b.close()
 
 
@@ -692,5 +688,5 @@ def test_at_size_sampled_worlds_match_the_oracle():
       assert np.array_equal(rows[E.OBS_READY_TO_SHOOT][k, i], o.ready_to_shoot()), (w, k)
       assert np.array_equal(rows[E.OBS_POSITION][k, i], o.dump()[1][:, :2]), (w, k)
     o.close()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()

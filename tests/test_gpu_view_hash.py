@@ -23,11 +23,6 @@ KITCHEN = "collaborative_cooking__cramped"
 MATRIX = "prisoners_dilemma_in_the_matrix__repeated"
 
 
-def _no_faults(eng):
-  # (words 10 and 11 keep the index and the code of the last report; word 9 claims the next)
-  assert not eng.fault_words()[:10].any(), eng.fault_words()[:10]
-
-
 def _same(got, want, what):
   got = got.cpu().numpy() if isinstance(got, torch.Tensor) else got
   want = want.cpu().numpy() if isinstance(want, torch.Tensor) else want
@@ -106,7 +101,7 @@ def test_live_worlds_saved_rows_the_model_and_the_host_twin_agree(name):
                         dst=live.data_ptr(), dst_bytes=live.numel() * 8, classes=dev_classes.data_ptr(),
                         classes_len=n - 1)
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   env.close()
 
 
@@ -151,7 +146,7 @@ def test_sampled_views_repeats_and_destinations_off_a_16_byte_line(name):
       got = base.cpu().numpy()
       assert (got[:shift] == -7).all() and (got[shift + count:] == -7).all()
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   env.close()
 
 
@@ -197,7 +192,7 @@ def test_an_index_out_of_range_leaves_its_element_and_is_reported():
   eng.step(torch.zeros((N, P), dtype=torch.int32, device=eng.device))
   _same(eng.hash_views(), _model(eng, eng.save_worlds()), "after the reports")
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   eng.close()
 
 
@@ -280,7 +275,7 @@ def test_the_registered_tensor_follows_every_submission(T):
   assert torch.equal(eng.save_worlds(), twin.engine.save_worlds())
   for e in (eng, twin.engine):
     e.sync()
-    _no_faults(e)
+    util.no_faults(e)
   env.close()
   twin.close()
 
@@ -294,7 +289,7 @@ def test_tune_does_not_write_the_registered_tensor():
   eng.reset()
   _same(reg, _model(eng, eng.save_worlds()), "after the reset")
   eng.sync()
-  _no_faults(eng)
+  util.no_faults(eng)
   eng.close()
 
 
@@ -317,7 +312,7 @@ def test_the_states_of_step_many_hash_to_the_registered_tensor_of_the_step_loop(
   assert len(torch.unique(got)) > K   # (the views change from step to step and differ between players)
   for e in (eng, loop.engine):
     e.sync()
-    _no_faults(e)
+    util.no_faults(e)
   env.close()
   loop.close()
 
@@ -346,6 +341,6 @@ def test_a_mixture_of_two_kitchens_shares_one_tensor():
       _same(whole[sl], own, (T, i, "the member's own call"))
       _same(own, _model(m.engine, m.save_state().data), (T, i, "model"))
       m.engine.sync()
-      _no_faults(m.engine)
+      util.no_faults(m.engine)
     assert mix.set_view_hashes(None) is None
     mix.close()

@@ -27,10 +27,6 @@ GROUP_B = (E.OBS_REWARD, E.OBS_AUX0, E.OBS_STEP_TYPE, E.OBS_DISCOUNT, E.OBS_COLL
 LATEST_INTERACTION = (E.OBS_INTERACTION_INVENTORIES, E.OBS_INTERACTION_REWARDS)
 
 
-def _no_faults(eng):
-  assert not eng.fault_words()[:6].any(), eng.fault_words()[:6]
-
-
 def _engine(pack, n, kinds=SCALARS, **kw):
   e = engine.Engine(pack, n, device=0, **kw)
   bufs = {k: e.bind(k) for k in kinds}
@@ -125,7 +121,7 @@ def test_fork_equals_continuation_in_this_engine_and_another():
       eng.step(B[s])
       _same(out, ref[s], range(n), range(n), ("step", s))
     assert torch.equal(_no_counters(eng.save_worlds()), _no_counters(ref_state))
-    _no_faults(eng)
+    util.no_faults(eng)
   e.close(); e2.close()
 
 
@@ -169,7 +165,7 @@ def test_permuted_and_duplicated_loads_match_the_oracle_of_the_source():
     for p in range(P):
       assert np.array_equal(rgb[w, p], o.render_agent(p)), (w, p)
     o.close()
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -225,7 +221,7 @@ def test_what_the_load_launch_writes():
   assert torch.equal(_no_counters(after, bank)[loaded], _no_counters(bank)[src[loaded].astype(np.int64)])
   for kind in kinds:
     _same({kind: got[kind]}, {kind: reset[kind]}, left, left, ("left", kind))
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 
@@ -257,7 +253,7 @@ def _continuation(name, n, k, cont, kinds, pack=None, seed=0, load_src=None, **k
   for s in range(cont):
     e.step(B[s][torch.as_tensor(src.astype(np.int64), device=e.device)])
     _same(keep, ref[s], range(n), src, (name, "step", s))
-  _no_faults(e)
+  util.no_faults(e)
   return e, bufs, src, at_save, at_load
 
 
@@ -345,7 +341,7 @@ def test_a_load_writes_the_ring_slot_a_masked_reset_writes():
       assert torch.equal(rgb[w], ring[E.OBS_RGB][prev][src[w]]), w
     else:
       assert torch.equal(rgb[w], trgb[w]), w
-  _no_faults(e)
+  util.no_faults(e)
   e.close(); twin.close()
 
 
@@ -375,7 +371,7 @@ def test_finished_rows_load_finished_and_auto_reset_like_their_source():
       _same(bufs, ref[i], range(n), src, (auto, s))
     if auto:
       assert (ref[0][E.OBS_STEP_TYPE] == 0).all()
-    _no_faults(e)
+    util.no_faults(e)
     e.close()
 
 
@@ -405,7 +401,7 @@ def test_counters_are_the_work_this_engine_did():
   assert c["world_steps"] == n * 16, c
   assert c["agent_steps"] == n * P * 16, c
   assert c["episodes"] == n, c
-  _no_faults(e)
+  util.no_faults(e)
   e.close(); other.close()
 
 
@@ -478,7 +474,7 @@ def test_refusals_and_out_of_range_indices():
     e.step(A[s]); twin.step(A[s])
   _same(bufs, tb, range(n), range(n), "after refusals")
   assert torch.equal(e.save_worlds(), twin.save_worlds())
-  _no_faults(e)
+  util.no_faults(e)
   e.close(); twin.close()
 
 
@@ -524,7 +520,7 @@ def test_at_size_every_world_matches_the_oracle_of_its_source():
     assert np.array_equal(rew[w], orew), (w, s)
     if s in sample:
       assert np.array_equal(wrgb[w], views[k + steps]), (w, s)
-  _no_faults(e)
+  util.no_faults(e)
   e.close()
 
 

@@ -48,23 +48,6 @@ def verdicts(name, rows, **kw):
 
 
 # ---- structure ---------------------------------------------------------------------------------
-def test_request_sizes_abi_and_exports():
-  sizes = [ctypes.sizeof(c) for c in (E.MpStateLayout, E.MpStatesCheck, E.MpStatesObserve, E.MpKernelVariant,
-                                      E.MpWorldStates, E.MpStepMany, E.MpStepTrajectory)]
-  assert len(set(sizes)) == len(sizes), sizes
-  assert ctypes.sizeof(E.MpStateLayout) == 120 and ctypes.sizeof(E.MpStatesCheck) == 88
-  assert max(sizes) < 448   # (no engine's snapshot is that small)
-  L = E.load_library()
-  assert L.mp_abi_version() == 8 == E.MP_ABI_VERSION
-  assert len(E.ABI_SYMBOLS) == 30
-  import subprocess
-  from meltingpot_amd import _build
-  out = subprocess.run(["nm", "-D", "--defined-only", _build.LIB_PATH], capture_output=True, text=True, check=True)
-  exported = sorted(l.split()[-1] for l in out.stdout.splitlines() if " T " in l and l.split()[-1].startswith("mp_"))
-  assert exported == sorted(E.ABI_SYMBOLS)
-  assert E.OBS_RGB_POOL8 + 1 == 24   # MP_OBS_KINDS
-
-
 @pytest.mark.parametrize("name", R.PACKS)
 def test_layout_agrees_with_the_pack(name):
   lay, t = layout(name), tables(name)

@@ -1,86 +1,16 @@
-"""Stepping some of the worlds (MpStepActive) without a GPU: include/mp_step_active.h compiles as
-C99 and as C++17 and its request has the size and the offsets the library and the ctypes mirror
-expect, distinct from every other request's; the mask check of Engine.step / Engine.step_many
-refuses bad dtypes, ranks, shapes and strides; the library exports what it exported; the new kernel
-family is in the code object; a request without an engine is refused by the library's own checks."""
+"""Stepping some of the worlds (MpStepActive) without a GPU: the mask check of Engine.step /
+Engine.step_many refuses bad dtypes, ranks, shapes and strides; a request without an engine is
+refused by the library's own checks.  (The request's layout, wrappers and kernels:
+tests/test_request_abi_cpu.py.)"""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from meltingpot_amd import _build, engine
+from meltingpot_amd import engine
 
 E = engine
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LEVELS = ("clean_up", "commons", "coins", "territory", "matrix", "coop", "gift", "cook", "mushroom")
-
-PROGRAM = r'''
-#include <stddef.h>
-#include <stdio.h>
-#include "mp_step_active.h"
-int main(void) {
-  /* (no engine: both wrappers answer MP_ERR_INVALID with the library's message) */
-  int a = mp_step_many_active(NULL, NULL, 4, 0, 0, NULL, 0, NULL, 0);
-  int b = mp_step_active(NULL, NULL, 0, NULL);
-  printf("%u %u %u %u %d %d\n", (unsigned)sizeof(MpStepActive), (unsigned)offsetof(MpStepActive, active),
-         (unsigned)offsetof(MpStepActive, active_step_bytes), (unsigned)offsetof(MpStepActive, reserved), a, b);
-  return 0;
-}
-'''
-
-
-@pytest.mark.parametrize("compiler, std, suffix", [("gcc", "-std=c99", "c"), ("g++", "-std=c++17", "cc")])
-def test_the_header_compiles_and_has_the_size_of_the_mirror(tmp_path, compiler, std, suffix):
-  src = tmp_path / f"active.{suffix}"
-  src.write_text(PROGRAM)
-  exe = tmp_path / "active"
-  subprocess.run([compiler, std, "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                  _build.build_engine(), f"-Wl,-rpath,{os.path.dirname(_build.LIB_PATH)}"], check=True)
-  out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()
-  M = E.MpStepActive
-  assert out == [str(ctypes.sizeof(M)), str(M.active.offset), str(M.active_step_bytes.offset),
-                 str(M.reserved.offset), str(E.MP_ERR_INVALID), str(E.MP_ERR_INVALID)]
-
-
-def test_the_mirror_has_the_documented_layout():
-  M = E.MpStepActive
-  assert ctypes.sizeof(M) == 96
-  offsets = {name: getattr(M, name).offset for name, _ in M._fields_}
-  assert offsets == {"struct_size": 0, "steps": 4, "fields": 8, "num_rows": 12, "actions": 16,
-                     "actions_step_bytes": 24, "rows": 32, "active": 40, "active_step_bytes": 48, "reserved": 56}
-  # the seven fields in front are MpStepTrajectory's
-  T = E.MpStepTrajectory
-  for name, _ in T._fields_:
-    assert getattr(T, name).offset == offsets[name] and getattr(T, name).size == getattr(M, name).size, name
-
-
-def test_request_size_differs_from_every_other_request():
-  others = [ctypes.sizeof(c) for c in (E.MpStatesHash, E.MpStateLayout, E.MpStatesCheck, E.MpStatesObserve,
-                                       E.MpStatesView, E.MpKernelVariant, E.MpWorldStates, E.MpStepMany,
-                                       E.MpStepTrajectory, E.MpEpisodeStarts)]
-  assert sorted(others) == [40, 48, 56, 64, 72, 80, 88, 104, 112, 120]
-  mine = ctypes.sizeof(E.MpStepActive)
-  assert mine == 96 and mine not in others and mine < 448   # (a snapshot is >= 448 bytes)
-
-
-def test_the_library_exports_what_it_exported():
-  assert len(E.ABI_SYMBOLS) == 30   # (the request rides mp_restore)
-  out = subprocess.run(["nm", "-D", "--defined-only", _build.build_engine()], capture_output=True, text=True,
-                       check=True).stdout
-  exported = sorted(line.split()[-1] for line in out.splitlines()
-                    if line.split() and line.split()[-2] in ("T", "D", "B", "R"))
-  assert exported == sorted(E.ABI_SYMBOLS)
-
-
-def test_the_new_kernel_family_is_in_the_code_object():
-  blob = open(_build.build_engine(), "rb").read()
-  for level in LEVELS:
-    assert f"k_many_active_{level}".encode() in blob, level
-
-
 def test_the_mask_check_without_a_gpu():
   K, N = 6, 5
   check = E.check_step_active

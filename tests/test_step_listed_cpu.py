@@ -1,93 +1,15 @@
-"""Stepping a device list of worlds (MpStepListed) without a GPU: include/mp_step_listed.h compiles as
-C99 and as C++17 and its request has the size and the offsets the library and the ctypes mirror
-expect, MpStepUntil's fields in front at its offsets and a size no other request has; the argument
-check of worlds= accepts and refuses what it should; the library exports what it exported; the new
-kernel family is in the code object; a request without an engine is refused by the library's own
-checks."""
+"""Stepping a device list of worlds (MpStepListed) without a GPU: the argument check of worlds=
+accepts and refuses what it should; a request without an engine is refused by the library's own
+checks.  (The request's layout, wrappers and kernels: tests/test_request_abi_cpu.py.)"""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from meltingpot_amd import _build, engine
+from meltingpot_amd import engine
 
 E = engine
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LEVELS = ("clean_up", "commons", "coins", "territory", "matrix", "coop", "gift", "cook", "mushroom")
-TAIL = ("gamma", "reserved", "worlds", "count", "reserved2", "reserved3")
-
-PROGRAM = r'''
-#include <stddef.h>
-#include <stdio.h>
-#include "mp_step_listed.h"
-int main(void) {
-  /* (no engine: both wrappers answer MP_ERR_INVALID with the library's message) */
-  int a = mp_step_many_listed(NULL, NULL, 3, NULL, 4, 0, 0, NULL, 0, NULL, 0, MP_STOP_LAST, NULL, NULL, NULL, 0.97);
-  int b = mp_step_listed(NULL, NULL, 3, NULL, 0);
-  printf("%u %u %u %u %u %u %u %d %d\n", (unsigned)sizeof(MpStepListed), (unsigned)offsetof(MpStepListed, gamma),
-         (unsigned)offsetof(MpStepListed, reserved), (unsigned)offsetof(MpStepListed, worlds),
-         (unsigned)offsetof(MpStepListed, count), (unsigned)offsetof(MpStepListed, reserved2),
-         (unsigned)offsetof(MpStepListed, reserved3), a, b);
-  return 0;
-}
-'''
-
-
-@pytest.mark.parametrize("compiler, std, suffix", [("gcc", "-std=c99", "c"), ("g++", "-std=c++17", "cc")])
-def test_the_header_compiles_and_has_the_size_of_the_mirror(tmp_path, compiler, std, suffix):
-  src = tmp_path / f"listed.{suffix}"
-  src.write_text(PROGRAM)
-  exe = tmp_path / "listed"
-  subprocess.run([compiler, std, "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                  _build.build_engine(), f"-Wl,-rpath,{os.path.dirname(_build.LIB_PATH)}"], check=True)
-  out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()
-  M = E.MpStepListed
-  assert out == [str(ctypes.sizeof(M))] + [str(getattr(M, name).offset) for name in TAIL] + \
-      [str(E.MP_ERR_INVALID), str(E.MP_ERR_INVALID)]
-
-
-def test_the_mirror_has_the_documented_layout():
-  M, U = E.MpStepListed, E.MpStepUntil
-  assert ctypes.sizeof(M) == 176
-  # MpStepUntil's fields in front, at its offsets; the list begins where that struct ends
-  for name, _ in U._fields_:
-    assert getattr(U, name).offset == getattr(M, name).offset and getattr(U, name).size == getattr(M, name).size, name
-  assert M.worlds.offset == ctypes.sizeof(U) == 136
-  assert (M.count.offset, M.reserved2.offset, M.reserved3.offset) == (144, 148, 152)
-
-
-def test_request_size_differs_from_every_other_request():
-  others = [ctypes.sizeof(c) for c in (E.MpStatesHash, E.MpStateLayout, E.MpStatesCheck, E.MpStatesObserve,
-                                       E.MpStatesView, E.MpKernelVariant, E.MpWorldStates, E.MpStepMany,
-                                       E.MpStepTrajectory, E.MpEpisodeStarts, E.MpStepActive, E.MpStepUntil)]
-  assert sorted(others) == [40, 48, 56, 64, 72, 80, 88, 96, 104, 112, 120, 136]
-  mine = ctypes.sizeof(E.MpStepListed)
-  assert mine not in others and mine < 448   # (a snapshot is >= 448 bytes)
-
-
-def test_the_abi_is_what_it_was():
-  L = E.load_library()
-  assert L.mp_abi_version() == 8
-  assert len(E.ABI_SYMBOLS) == 30   # (the request rides mp_restore)
-  out = subprocess.run(["nm", "-D", "--defined-only", _build.build_engine()], capture_output=True, text=True,
-                       check=True).stdout
-  exported = sorted(line.split()[-1] for line in out.splitlines()
-                    if line.split() and line.split()[-2] in ("T", "D", "B", "R"))
-  assert exported == sorted(E.ABI_SYMBOLS)
-
-
-def test_the_new_kernel_family_is_in_the_code_object():
-  blob = open(_build.build_engine(), "rb").read()
-  assert b"k_claim_listed" in blob
-  for level in LEVELS:
-    assert f"k_many_listed_{level}".encode() in blob, level
-    # (the masked and the stopping requests keep their own)
-    assert f"k_many_until_{level}".encode() in blob and f"k_many_active_{level}".encode() in blob, level
-
-
 def test_the_argument_check_without_a_gpu():
   N, P, M, K = 5, 3, 3, 4
   check = E.check_step_listed

@@ -1,28 +1,20 @@
-"""The hash of each player's view (the MpViewHash request) without a GPU: the C struct against its
-ctypes mirror, the unchanged C ABI, the kernels in the code object, and the library's host twin
+"""The hash of each player's view (the MpViewHash request) without a GPU (its struct, wrappers and
+kernels: tests/test_request_abi_cpu.py): the library's host twin
 held to the numpy model (tests/view_hash_model.py: EGO_LAYER from tests/ego_layer_model.py, plain
 uint64 arithmetic) on records written from the CPU oracle.  Every comparison is exact integer
 equality.  The Python refusals run on the CPU oracle behind the engine interface."""
 import ctypes
 import functools
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import ego_layer_model as EM
 import view_hash_model as VM
-from meltingpot_amd import _build, substrate
+from meltingpot_amd import substrate
 from meltingpot_amd import engine as E
 from oracle_engine import OracleBatchEngine
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-FIELDS = ("struct_size", "op", "fingerprint", "bank", "rows", "players", "dst", "dst_bytes", "bank_rows",
-          "count", "slot_stride", "slots", "classes_len", "pack", "pack_len", "cfg", "layer_mask", "classes",
-          "num_ids", "reserved", "reserved2")
 KITCHEN = "collaborative_cooking__cramped"
 MATRIX = "prisoners_dilemma_in_the_matrix__repeated"
 LEVELS = ("clean_up", KITCHEN, MATRIX)
@@ -47,51 +39,6 @@ def fields_of(pack, rows):
 
 
 # ---- structure ---------------------------------------------------------------------------------
-def test_the_header_names_the_request_and_the_abi_is_what_it_was(tmp_path):
-  header = open(os.path.join(ROOT, "include", "mp_engine.h")).read()
-  assert "} MpViewHash;" in header
-  assert "MP_VIEWHASH_DRAW = 1, MP_VIEWHASH_REGISTER = 2, MP_VIEWHASH_HOST = 3" in header
-  assert re.search(r"#define MP_ABI_VERSION 8\b", header) and re.search(r"MP_OBS_KINDS\s*=\s*24", header)
-  assert E.load_library().mp_abi_version() == 8 == E.MP_ABI_VERSION
-  out = subprocess.run(["nm", "-D", "--defined-only", _build.build_engine()], capture_output=True, text=True,
-                       check=True).stdout
-  names = {line.split()[-1] for line in out.splitlines()
-           if line.split() and line.split()[-2] in ("T", "D", "B", "R")}
-  assert names == set(E.ABI_SYMBOLS) and len(names) == 30
-  # the C struct is the ctypes mirror, and the wrappers compile as C99
-  src = tmp_path / "vh.c"
-  prints = "\n".join(f'  printf("{f} %zu\\n", offsetof(MpViewHash, {f}));' for f in FIELDS)
-  src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "mp_view_hash.h"\n'
-                 "int main(void) {\n"
-                 '  printf("sizeof %zu\\n", sizeof(MpViewHash));\n' + prints + "\n"
-                 '  printf("rc %d\\n", mp_view_hash_draw(NULL, NULL, 0, NULL, NULL, 0, 0, NULL, 0, NULL, 0, 0));\n'
-                 '  printf("rc2 %d\\n", mp_view_hash_register(NULL, NULL, 0, 0, 0, 0, NULL, 0));\n'
-                 '  printf("rc3 %d\\n", mp_view_hash_host(NULL, 0, NULL, NULL, 0, NULL, NULL, 0, 0, NULL, 0, NULL, 0, 0));\n'
-                 '  printf("rc4 %d\\n", mp_view_hash_num_ids(NULL, NULL, 0, NULL, NULL));\n'
-                 "  return 0;\n}\n")
-  exe = tmp_path / "vh"
-  subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                  _build.LIB_PATH, f"-Wl,-rpath,{os.path.dirname(_build.LIB_PATH)}"], check=True)
-  got = dict(line.split() for line in
-             subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
-  assert int(got["sizeof"]) == ctypes.sizeof(E.MpViewHash) == 152
-  assert [f for f, _ in E.MpViewHash._fields_] == list(FIELDS)
-  for f in FIELDS:
-    assert int(got[f]) == getattr(E.MpViewHash, f).offset, f
-  assert int(got["rc"]) == int(got["rc2"]) == int(got["rc3"]) == int(got["rc4"]) == E.MP_ERR_INVALID
-  # a size no other request has
-  others = (E.MpStatesObserve, E.MpStatesView, E.MpStatesHash, E.MpStateLayout, E.MpStatesCheck, E.MpKernelVariant,
-            E.MpWorldStates, E.MpStepMany, E.MpStepTrajectory, E.MpEpisodeStarts, E.MpEpisodeStats, E.MpEgoLayer,
-            E.MpStepActive, E.MpStepUntil, E.MpStepListed)
-  assert ctypes.sizeof(E.MpViewHash) not in [ctypes.sizeof(c) for c in others]
-  assert ctypes.sizeof(E.MpViewHash) < 448   # (no engine's snapshot is that small)
-
-
-def test_the_kernels_are_in_the_code_object():
-  blob = open(_build.build_engine(), "rb").read()
-  assert b"k_view_hash_rows" in blob and b"k_view_hash_views" in blob
-
-
 def test_the_models_fmix64_is_the_published_one():
   M64 = (1 << 64) - 1
 

@@ -1,5 +1,6 @@
 """World states as device data (mp_state_fingerprint / mp_save_worlds / mp_load_worlds) on the
-host side: the header declares the entry points next to an unchanged ABI version, NULL and empty
+host side: the header declares the entry points (the request's layout and the wrappers' answers:
+tests/test_request_abi_cpu.py), NULL and empty
 arguments are refused before a device is looked for, and `substrate.WorldStates` checks what it
 holds and selects rows."""
 import ctypes
@@ -21,16 +22,7 @@ def _header():
 
 
 def test_header_declares_the_world_state_request_and_keeps_abi_8():
-  text = _header()
-  assert re.search(r"enum\s*\{\s*MP_STATES_FINGERPRINT = 1, MP_STATES_SAVE = 2, MP_STATES_LOAD = 3\s*\}", text)
-  body = text[text.index("typedef struct {\n  uint32_t struct_size;    /* = sizeof(MpWorldStates)"):]
-  body = body[:body.index("} MpWorldStates;")]
-  fields = re.findall(r"^\s+(?:const\s+)?\w+\*?\s+(\w+);", body, re.M)
-  assert fields == [f for f, _ in engine.MpWorldStates._fields_]
-  assert ctypes.sizeof(engine.MpWorldStates) == 56
-  assert re.search(r"#define MP_ABI_VERSION 8\b", text)
-  L = engine.load_library()
-  assert L.mp_abi_version() == engine.MP_ABI_VERSION == 8
+  """The wrappers' header declares the three entry points.  (What it held of the layout and the ABI version: tests/test_request_abi_cpu.py.)"""
   wrappers = open(os.path.join(ROOT, "include", "mp_world_states.h")).read()
   assert re.search(r"static inline uint64_t mp_state_fingerprint\(MpEngine\* eng\)", wrappers)
   assert re.search(r"static inline int mp_save_worlds\(MpEngine\* eng, const int32_t\* worlds_device, "
@@ -40,15 +32,9 @@ def test_header_declares_the_world_state_request_and_keeps_abi_8():
 
 
 def test_the_world_states_add_no_exported_symbol():
-  """The operations ride on mp_snapshot / mp_restore: the library exports what it exported."""
-  import subprocess
-  from meltingpot_amd import _build
-  out = subprocess.run(["nm", "-D", "--defined-only", _build.build_engine()], capture_output=True,
-                       text=True, check=True).stdout
-  names = {line.split()[-1] for line in out.splitlines()
-           if line.split() and line.split()[-2] in ("T", "D", "B", "R")}
-  assert names == set(engine.ABI_SYMBOLS) and len(names) == 30
-  assert not {"mp_state_fingerprint", "mp_save_worlds", "mp_load_worlds"} & names
+  """The operations ride on mp_snapshot / mp_restore: they are no symbols of the ABI (which
+  tests/test_cabi_cpu.py holds to what the library exports)."""
+  assert not {"mp_state_fingerprint", "mp_save_worlds", "mp_load_worlds"} & set(engine.ABI_SYMBOLS)
 
 
 def test_header_lists_every_observation_kind_in_exactly_one_load_group():
@@ -78,26 +64,6 @@ def test_null_and_empty_arguments_are_invalid_without_a_device():
   assert L.mp_snapshot(None, ctypes.addressof(req), ctypes.sizeof(req)) == engine.MP_ERR_INVALID
   assert L.mp_restore(None, ctypes.addressof(req), ctypes.sizeof(req)) == engine.MP_ERR_INVALID
   assert L.mp_snapshot(None, None, ctypes.sizeof(req)) == engine.MP_ERR_INVALID
-
-
-def test_the_c_wrappers_compile_and_link_against_the_library(tmp_path):
-  """include/mp_world_states.h as a C caller uses it: compiled with gcc, linked against the
-  library, called with NULL / empty arguments (MP_ERR_INVALID, no device touched)."""
-  import subprocess
-  from meltingpot_amd import _build
-  lib = _build.build_engine()
-  src = tmp_path / "w.c"
-  src.write_text('#include <stdio.h>\n#include "mp_world_states.h"\n'
-                 "int main(void) {\n"
-                 '  printf("%llu %d %d %d\\n", (unsigned long long)mp_state_fingerprint(NULL),\n'
-                 "         mp_save_worlds(NULL, NULL, 4, NULL, 0), mp_load_worlds(NULL, NULL, 1, NULL, 0),\n"
-                 "         (int)sizeof(MpWorldStates));\n"
-                 "  return 0;\n}\n")
-  exe = tmp_path / "w"
-  subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
-                  "-o", str(exe), lib, f"-Wl,-rpath,{os.path.dirname(lib)}"], check=True)
-  out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()
-  assert out == ["0", str(engine.MP_ERR_INVALID), str(engine.MP_ERR_INVALID), "56"]
 
 
 def test_world_states_refuse_wrong_dtype_shape_and_fingerprint():

@@ -31,10 +31,6 @@ from meltingpot_amd import engine as E  # noqa: E402
 GOLDEN = os.path.join(ROOT, "tests", "golden", "state_request_refusals.json")
 DISPATCH = os.path.join(ROOT, "tests", "golden", "request_dispatch.json")
 CARRIERS = ("mp_snapshot", "mp_restore")
-# the 18 requests the two carriers tell apart by size
-REQUESTS = (E.MpKernelVariant, E.MpWorldStates, E.MpStatesObserve, E.MpStepMany, E.MpStepTrajectory, E.MpStateLayout,
-            E.MpStatesCheck, E.MpStatesHash, E.MpEpisodeStarts, E.MpStatesView, E.MpStepActive, E.MpStepUntil,
-            E.MpStepListed, E.MpEpisodeStats, E.MpEgoLayer, E.MpViewHash, E.MpEgoPlanes, E.MpAvatarIds)
 ODD_SIZE = 8   # a buffer no request is the size of
 N, BANK_ROWS = 2, 3
 VIEWS = {"ego_layer": E.MpEgoLayer, "view_hash": E.MpViewHash, "ego_planes": E.MpEgoPlanes}
@@ -508,11 +504,11 @@ def gpu_cases(c: DeviceCtx):
 def dispatch_cases():
   """[(name, carrier, request or None, size)], all with a NULL engine: each request, zero but for its
   struct_size, through each carrier; ODD_SIZE bytes; a NULL buffer of a request's size."""
-  sizes = [ctypes.sizeof(s) for s in REQUESTS]
-  assert len(set(sizes)) == len(REQUESTS) == 18 and ODD_SIZE not in sizes
+  requests = [q.struct for q in E.REQUESTS]
+  assert ODD_SIZE not in [ctypes.sizeof(s) for s in requests]
   out = []
   for carrier in CARRIERS:
-    for struct in REQUESTS:
+    for struct in requests:
       out.append((f"{struct.__name__}/{carrier}", carrier, make(struct), ctypes.sizeof(struct)))
     out.append((f"odd_size/{carrier}", carrier, (ctypes.c_uint8 * ODD_SIZE)(), ODD_SIZE))
     out.append((f"null_buffer/{carrier}", carrier, None, ctypes.sizeof(E.MpStatesObserve)))

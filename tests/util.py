@@ -85,6 +85,15 @@ def replay_parallel(pack_bytes, acts, looks=(), sample=(), world_view=True, offs
           pr.kill()
 
 
+def no_faults(eng, words=10, sync=False):
+  """Asserts that engine `eng` has reported no fault: its first `words` fault words are zero, after
+  a sync if asked.  Ten words hold every report (word 8: the matrix reward report, word 9: the count
+  of index reports; words 10 and 11 keep the index and the code of the last one)."""
+  if sync:
+    eng.sync()
+  assert not eng.fault_words()[:words].any(), eng.fault_words()[:words]
+
+
 def pack_tables(pack_bytes):
   from meltingpot_amd import pack
   return pack.loads(pack_bytes)
