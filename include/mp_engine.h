@@ -690,6 +690,26 @@ typedef struct {
  * engine's or whose stride is short of a slot or no multiple of 4; nonzero reserved words.
  * MP_ERR_UNSUPPORTED: a record whose render planes do not fit one wave's share of the LDS. */
 enum { MP_EGO_DRAW = 1, MP_EGO_REGISTER = 2, MP_EGO_HOST = 3 };
+/* WORLD.LAYER: the same request with the WORLD in place of the viewers — the layer view of the whole
+ * map, which the reference builds on every step to render "WORLD.RGB" from and throws away
+ * (base_simulation.lua:348-360, worldLayerView through worldSpriteMap).
+ *
+ * The world's value table.  Wt[s] = 1 + view_sprite_map[P][state_sprite[s]] for 1 <= s <
+ * min(nstates, 256) with state_sprite[s] >= 0, else 0: row P of the pack's view_sprite_map is the
+ * world's.  num_world_ids = 1 + max(Wt).  The ids are numbered like "LAYER"'s: id i is sprite
+ * i - 1, after the WORLD's sprite map and no viewer's.
+ * Definition.  For a record (a bank row or a live world) WORLD.LAYER is int32 [H][W][L], north up:
+ * out[y][x][l] = Wt[planes[l][y][x]].  No cell is off the map, so OutOfBounds never occurs.  A
+ * dead avatar is on no plane and shows nowhere.
+ *
+ * The ops are those of MP_EGO_DRAW, MP_EGO_REGISTER and MP_EGO_HOST in every word above, with these
+ * differences: `players` must be NULL (MP_ERR_INVALID otherwise); an element of dst is one record's
+ * [H][W][L] (4-byte aligned), a registration's tensor int32 [N][H][W][L]; the registration is one
+ * of its own beside EGO_LAYER's, its launch follows those of the viewers' registrations behind
+ * every submission, and a NULL dst clears it alone.  A bad rows[i] is reported as above, naming
+ * MpEgoLayer (MP_EGO_WORLD_DRAW).  MP_ERR_UNSUPPORTED also for more than 64 layers.  There is no
+ * inline wrapper for these ops: a C caller fills the struct itself and hands it to mp_snapshot. */
+enum { MP_EGO_WORLD_DRAW = 4, MP_EGO_WORLD_REGISTER = 5, MP_EGO_WORLD_HOST = 6 };
 typedef struct {
   uint32_t struct_size;    /* = sizeof(MpEgoLayer) */
   int32_t op;              /* MP_EGO_* */
@@ -1033,6 +1053,29 @@ typedef struct {
  * planes, beside the viewers' value tables and the bit planes of one viewer, do not fit one wave's
  * share of the LDS; more than 64 layers. */
 enum { MP_EGOPLANES_DRAW = 1, MP_EGOPLANES_REGISTER = 2, MP_EGOPLANES_HOST = 3 };
+/* The world planes: the same request with the WORLD in place of the viewers — the critic's input of
+ * a centralised-critic method, a world model's global state.
+ *
+ * The class table.  `classes` is int32 [num_world_ids] (see MP_EGO_WORLD_DRAW: the ids of the
+ * world's value table), entries in [-1, C), 1 <= C <= 64.  classes_len must equal num_world_ids,
+ * which these ops write back into num_ids (count == 0 with a NULL dst asks for nothing else).
+ * The planes.  With WL the record's WORLD.LAYER, an element is uint8 [C'][H][W], C' = C, or C + 4
+ * with `facing`; every byte is 0 or 1:
+ *   class plane c < C:   out[c][y][x] = 1 iff some layer l with bit l of layer_mask set (0: every
+ *     layer) has classes[WL[y][x][l]] == c.  Class -1 sets nothing.
+ *   facing plane C + d:  out[C + d][y][x] = 1 iff some living avatar q < P stands on (x, y) with
+ *     aori[q] == d.  This is ABSOLUTE facing, 0 = N: there is no viewer.
+ *
+ * The ops are those of MP_EGOPLANES_DRAW, MP_EGOPLANES_REGISTER and MP_EGOPLANES_HOST in every word
+ * above, with these differences: `players` must be NULL (MP_ERR_INVALID otherwise); an element of
+ * dst is one record's [C'][H][W] and may start on any byte, a registration's tensor uint8
+ * [N][C'][H][W]; the registration is one of its own beside the viewers' planes, its launch is the
+ * last behind every submission, and a NULL dst clears it alone.  A bad rows[i] and an entry of the
+ * device class table outside [-1, C) (it counts as -1) are reported as above, naming MpEgoPlanes
+ * (MP_EGOPLANES_WORLD_DRAW).  MP_ERR_UNSUPPORTED: a record whose render planes and one u64 a cell
+ * do not fit one wave's share of the LDS; more than 64 layers.  There is no inline wrapper for these
+ * ops: a C caller fills the struct itself and hands it to mp_snapshot. */
+enum { MP_EGOPLANES_WORLD_DRAW = 4, MP_EGOPLANES_WORLD_REGISTER = 5, MP_EGOPLANES_WORLD_HOST = 6 };
 typedef struct {
   uint32_t struct_size;    /* = sizeof(MpEgoPlanes) */
   int32_t op;              /* MP_EGOPLANES_* */

@@ -38,17 +38,18 @@ LIB_PATH = os.path.join(LIB_DIR, "libmp_engine.so")
 # behind every submission of an engine with the leaf registered; view_hash.hip: the hash of every
 # player's view, likewise a draw and a launch behind every submission; ego_planes.hip: the class
 # and facing planes of every player's view, likewise; avatar_ids.hip: whom every player sees and
-# could zap, likewise; these four take what they share — the staged record, the launch plan, the
+# could zap, likewise; world_view.hip: WORLD.LAYER and the world planes, the whole map in place of the
+# viewers' windows, likewise; these five take what they share — the staged record, the launch plan, the
 # host twin's loop — from view_unit.h.  The six step units take the nine levels from step_levels.h
 # and the K-step ones their row helpers from step_rows.h.
 SOURCES = ("frame.hip", "frame_wpool2.hip", "frame_wpool4.hip", "frame_wpool8.hip", "frame_stock.hip",
            "step_many.hip", "step_active.hip", "step_until.hip", "step_listed.hip", "step_kernels.hip",
            "step_starts.hip", "state_obs.hip", "state_view.hip", "state_check.hip", "state_hash.hip",
-           "episode_stats.hip", "ego_layer.hip", "view_hash.hip", "ego_planes.hip", "avatar_ids.hip",
+           "episode_stats.hip", "ego_layer.hip", "view_hash.hip", "ego_planes.hip", "avatar_ids.hip", "world_view.hip",
            "mp_engine.hip", "engine_atlas.hip", "engine_requests.hip", "engine_views.hip", "engine_outputs.hip",
            "mp_place.hip", "pack_decode.hip")
 HEADERS = ("mp_common.h", "engine_state.h", "stock.h", "stock_clean_up.h", "pack_decode.h", "frame_kernel.h", "frame_wpool.h", "step_common.h", "step_clean_up.h", "step_commons.h",
-           "step_territory.h", "step_coins.h", "step_matrix.h", "step_coop.h", "step_gift.h", "step_cook.h", "step_mushroom.h", "step_load.h", "step_one.h", "step_levels.h", "step_rows.h", "step_masked.h", "step_many.h", "step_until.h", "step_listed.h", "state_obs.h", "state_obs_rules.h", "state_view.h", "state_check.h", "state_hash.h", "episode_stats.h", "ego_layer.h", "view_hash.h", "ego_planes.h", "avatar_ids.h", "view_unit.h", "../../include/mp_engine.h",
+           "step_territory.h", "step_coins.h", "step_matrix.h", "step_coop.h", "step_gift.h", "step_cook.h", "step_mushroom.h", "step_load.h", "step_one.h", "step_levels.h", "step_rows.h", "step_masked.h", "step_many.h", "step_until.h", "step_listed.h", "state_obs.h", "state_obs_rules.h", "state_view.h", "state_check.h", "state_hash.h", "episode_stats.h", "ego_layer.h", "view_hash.h", "ego_planes.h", "avatar_ids.h", "view_unit.h", "world_view.h", "../../include/mp_engine.h",
            "../../include/mp_pack.h", "exports.map")
 ARCH = "gfx950"
 

@@ -176,8 +176,11 @@ struct MpEngine {
   // [N][P][C'][VH][VW] (MpEgoPlanes; ego_planes.h); av and avz: AVATAR_IDS_IN_VIEW and
   // AVATAR_IDS_IN_RANGE_TO_ZAP, int32 [N][P][P] each, written by one launch (MpAvatarIds;
   // avatar_ids.h).  mp_tune's probes write none of them (ring_hold, layer_hold).
-  ViewRegistration ego, vh, ep, av, avz;
+  // wl: the WORLD.LAYER leaf, int32 [N][H][W][L]; wp: the world planes, uint8 [N][C'][H][W] (the
+  // world ops of MpEgoLayer and MpEgoPlanes; world_view.h), written behind those.
+  ViewRegistration ego, vh, ep, av, avz, wl, wp;
   int32_t num_layer_ids = 0;   // 1 + the largest id of d_layer_lut: the length of a class table
+  int32_t num_world_ids = 0;   // 1 + the largest id of d_world_lut: the length of a world planes' class table
   bool viewing(const ViewRegistration& v) const { return v.dst && !ring_hold && !layer_hold; }
   // The engine's choice (MpConfig.unfused = 0): one launch, always.  (Round 2 drew
   // views under 64 KB a world — the two-player games — in a second launch: a CU
@@ -197,6 +200,7 @@ struct MpEngine {
   uint8_t* d_obs_stash = nullptr;
   uint64_t obs_stash_bytes = 0;
   int32_t* d_layer_lut = nullptr;  // StepOutputs::layer_lut [P][kLayerLutRow]
+  int32_t* d_world_lut = nullptr;  // the world's value table [kLayerLutRow] (world_view.h)
   // An MpStatesCheck request's view of the pack (state_check.h): built by mp_create's host stage,
   // and its copy in device memory for k_check_states
   state_check::CheckTables check = {};
@@ -250,6 +254,7 @@ int host_stage(const void* pack, uint64_t pack_len, const MpConfig* cfg, HostSta
 int build_atlas(MpEngine* e, const MpDevOptions* dev, const DecodedPack& d);
 uint64_t state_fingerprint(const std::vector<uint8_t>& pack, const DevTables& t);
 std::vector<int32_t> layer_lut_rows(const void* pack, const DevTables& t);
+std::vector<int32_t> world_lut_row(const void* pack, const DevTables& t);
 uint64_t pack_hash(const std::vector<uint8_t>& pack);
 int select_kernels(const std::vector<uint8_t>& pack, const DecodedPack& d, const MpDevOptions* dev);
 const ZapRules* zap_rules_of(const SubstrateTables& sub);

@@ -1,6 +1,7 @@
 // engine_views.hip — the requests about every viewer's window: MpEgoLayer, MpViewHash, MpEgoPlanes
-// and MpAvatarIds (include/mp_engine.h), one front and four tails.  engine_requests.hip's table
-// carries them.
+// and MpAvatarIds (include/mp_engine.h), one front and four tails, and the world ops of the first
+// and the third (WORLD.LAYER, the world planes: the whole map in place of the windows), two more
+// tails on the same front.  engine_requests.hip's table carries them.
 #include <string.h>
 
 #include <vector>
@@ -10,6 +11,7 @@
 #include "view_hash.h"
 #include "ego_planes.h"
 #include "avatar_ids.h"
+#include "world_view.h"
 
 // The requests about every viewer's window — MpEgoLayer, MpViewHash, MpEgoPlanes, MpAvatarIds
 // (include/mp_engine.h; carried by mp_snapshot; `e` is NULL for the host form) — are one front and four tails.  Each
@@ -51,6 +53,10 @@ static_assert(MP_EGO_DRAW == VIEW_DRAW && MP_VIEWHASH_DRAW == VIEW_DRAW && MP_EG
                   MP_EGOPLANES_REGISTER == VIEW_REGISTER && MP_EGO_HOST == VIEW_HOST &&
                   MP_VIEWHASH_HOST == VIEW_HOST && MP_EGOPLANES_HOST == VIEW_HOST,
               "and the numbers of their ops");
+static_assert(MP_EGO_WORLD_DRAW == VIEW_DRAW + 3 && MP_EGO_WORLD_REGISTER == VIEW_REGISTER + 3 &&
+                  MP_EGO_WORLD_HOST == VIEW_HOST + 3 && MP_EGOPLANES_WORLD_DRAW == VIEW_DRAW + 3 &&
+                  MP_EGOPLANES_WORLD_REGISTER == VIEW_REGISTER + 3 && MP_EGOPLANES_WORLD_HOST == VIEW_HOST + 3,
+              "the world ops of MpEgoLayer and MpEgoPlanes are their ops + 3");
 #undef MP_VIEW_PREFIX
 #undef MP_VIEW_FIELD
 static ViewRequest view_of(const void* request) {
@@ -94,7 +100,8 @@ static int view_prologue(const MpEngine* e, const ViewRequest& q, const ViewWord
   return MP_OK;
 }
 
-static int view_tables(const MpEngine* e, const ViewRequest& q, ViewTables* v) {
+// (`viewers` false: the world ops, which read none of the viewers' value tables)
+static int view_tables(const MpEngine* e, const ViewRequest& q, ViewTables* v, bool viewers = true) {
   if (e) {
     v->t = &e->t;
     v->fingerprint = e->fingerprint;
@@ -104,6 +111,7 @@ static int view_tables(const MpEngine* e, const ViewRequest& q, ViewTables* v) {
   if (int rc = host_stage(q.pack, q.pack_len, q.cfg, &v->h)) return rc;
   v->t = &v->h.d.t;
   v->fingerprint = state_fingerprint(v->h.pack, v->h.d.t);
+  if (!viewers) return MP_OK;
   v->host_lut = layer_lut_rows(v->h.pack.data(), v->h.d.t);
   v->num_ids = view_hash::num_ids(v->host_lut.data(), v->t->P);
   return MP_OK;
@@ -214,7 +222,170 @@ static int view_device_source(MpEngine* e, const ViewRequest& q, const ViewWords
                                   {"dst", q.dst, s.need, 1}});
 }
 
+// ---- the world ops: the whole map in place of the viewers' windows (world_view.h) ----------------
+// The front reads a world op as the op it is the twin of (q.op - 3); `players` must be NULL.
+constexpr int kWorldOps = 3;
+static bool world_op(int32_t op) { return op > VIEW_HOST && op <= VIEW_HOST + kWorldOps; }
+
+// The world's value table and the length of a class table: the engine's, or the pack's.
+struct WorldTable {
+  std::vector<int32_t> host;
+  const int32_t* lut = nullptr;   // (an engine: device memory)
+  int32_t num_ids = 0;
+};
+static void world_table(const MpEngine* e, const ViewTables& v, WorldTable* wt) {
+  if (e) { wt->lut = e->d_world_lut; wt->num_ids = e->num_world_ids; return; }
+  wt->host = world_lut_row(v.h.pack.data(), *v.t);
+  wt->lut = wt->host.data();
+  wt->num_ids = world_view::num_ids(wt->lut);
+}
+
+static int world_geometry(const ViewWords& w, const DevTables& t, const ego_layer::Window& g) {
+  if (int rc = view_record_lines(w, t, g)) return rc;
+  if ((uint64_t)g.HW * (uint64_t)g.L * (uint64_t)g.L >= (1ull << 32))   // (a word's cell is found with one multiply)
+    return fail(MP_ERR_UNSUPPORTED, "%s: a map of %d cells and %d layers", w.who, g.HW, g.L);
+  return MP_OK;
+}
+
+static int world_layer_request(MpEngine* e, const MpEgoLayer& r) {
+  static const ViewWords w = {"MpEgoLayer", "MP_EGO_WORLD_HOST", "the WORLD.LAYER leaf", "needs", "drawn", "draw"};
+  const char* const kWho = w.who;
+  ViewRequest q = view_of(&r);
+  q.op -= kWorldOps;
+  if (int rc = view_prologue(e, q, w, sizeof r,
+                             r.reserved == 0 && r.reserved2[0] == 0 && r.reserved2[1] == 0 && r.reserved2[2] == 0))
+    return rc;
+  if (r.players) return fail(MP_ERR_INVALID, "%s: the world ops take no players (players must be NULL)", kWho);
+  if (q.op == VIEW_REGISTER && !r.dst) {   // clears the registration: the engine's launches are what they were
+    e->wl = MpEngine::ViewRegistration{};
+    return MP_OK;
+  }
+  if (!r.dst) return fail(MP_ERR_INVALID, "%s: NULL dst", kWho);
+  if ((uintptr_t)r.dst & 3) return fail(MP_ERR_INVALID, "%s: dst %p is not 4-byte aligned", kWho, r.dst);
+  ViewTables v;
+  if (int rc = view_tables(e, q, &v, false)) return rc;
+  WorldTable wt;
+  world_table(e, v, &wt);
+  const ego_layer::Window g = ego_layer::window_of(*v.t);
+  const uint64_t world = (uint64_t)g.HW * (uint64_t)g.L * 4u;
+  if (g.L > 64) return fail(MP_ERR_UNSUPPORTED, "%s: %d layers; the world ops take 64", kWho, g.L);
+  if (int rc = world_geometry(w, *v.t, g)) return rc;
+  if (q.op == VIEW_REGISTER) {
+    uint64_t need;
+    if (int rc = view_register(e, q, w, world, 4, &need)) return rc;
+    if (world_view::layer_plan(g, e->N, e->num_cus).waves < 1)
+      return fail(MP_ERR_UNSUPPORTED, "%s: one wave's render planes need %d B of LDS", kWho,
+                  world_view::layer_plan(g, e->N, e->num_cus).lds);
+    e->wl = registration_of(q);
+    return MP_OK;
+  }
+  ViewSource s;
+  if (int rc = view_source(e, q, w, v, world, world, &s)) return rc;
+  world_view::LayerArgs a = {};
+  view_args(&a, g, q, v, s);
+  a.dst = (int32_t*)r.dst;
+  a.lut = wt.lut;
+  if (q.op == VIEW_HOST) {
+    a.src = (const uint8_t*)r.bank;
+    const int bad = world_view::host(a);
+    return bad >= 0 ? view_host_fault(q, w, bad, true) : MP_OK;
+  }
+  if (int rc = view_device_source(e, q, w, s, nullptr, 0)) return rc;
+  const world_view::Plan p = world_view::layer_plan(g, r.count, e->num_cus);
+  if (p.waves < 1)
+    return fail(MP_ERR_UNSUPPORTED, "%s: one wave's render planes need %d B of LDS", kWho, p.lds);
+  a.src = s.live ? e->d_state : (const uint8_t*)r.bank;
+  a.fault = e->t.fault;
+  world_view::launch(a, p, e->stream);
+  HIP_TRY(hipGetLastError());
+  return MP_OK;
+}
+
+// (`out` is the caller's struct: num_ids — the world's — is written back)
+static int world_planes_request(MpEngine* e, MpEgoPlanes* out) {
+  static const ViewWords w = {"MpEgoPlanes", "MP_EGOPLANES_WORLD_HOST", "the world planes", "need", "drawn", "draw"};
+  const char* const kWho = w.who;
+  MpEgoPlanes r;
+  memcpy(&r, out, sizeof r);
+  ViewRequest q = view_of(&r);
+  q.op -= kWorldOps;
+  if (int rc = view_prologue(e, q, w, sizeof r,
+                             r.reserved == 0 && r.reserved2[0] == 0 && r.reserved2[1] == 0 && r.reserved2[2] == 0))
+    return rc;
+  if (r.players) return fail(MP_ERR_INVALID, "%s: the world ops take no players (players must be NULL)", kWho);
+  if (q.op == VIEW_REGISTER && !r.dst) {   // clears the registration: the engine's launches are what they were
+    e->wp = MpEngine::ViewRegistration{};
+    out->num_ids = e->num_world_ids;
+    return MP_OK;
+  }
+  ViewTables v;
+  if (int rc = view_tables(e, q, &v, false)) return rc;
+  WorldTable wt;
+  world_table(e, v, &wt);
+  const int32_t num_ids = wt.num_ids;
+  out->num_ids = num_ids;
+  if (q.op != VIEW_REGISTER && r.count == 0 && !r.dst) return MP_OK;   // the question alone
+  if (!r.dst) return fail(MP_ERR_INVALID, "%s: NULL dst", kWho);
+  const ego_layer::Window g = ego_layer::window_of(*v.t);
+  uint64_t layer_mask;
+  if (int rc = view_layer_mask(w, g, r.layer_mask, &layer_mask)) return rc;
+  if (!r.classes) return fail(MP_ERR_INVALID, "%s: NULL classes: the planes are those of a class table", kWho);
+  if (r.classes_len != num_ids)
+    return fail(MP_ERR_INVALID, "%s: classes_len %d: a class table of the world has one entry per id of the world's "
+                "sprite map, %d of them", kWho, r.classes_len, num_ids);
+  if ((uintptr_t)r.classes & 3)
+    return fail(MP_ERR_INVALID, "%s: classes %p is not 4-byte aligned", kWho, (const void*)r.classes);
+  if (r.num_classes < 1 || r.num_classes > ego_planes::kMaxClasses)
+    return fail(MP_ERR_INVALID, "%s: num_classes %d is outside [1, %d]", kWho, r.num_classes, ego_planes::kMaxClasses);
+  if (r.facing != 0 && r.facing != 1) return fail(MP_ERR_INVALID, "%s: facing %d is neither 0 nor 1", kWho, r.facing);
+  if (int rc = world_geometry(w, *v.t, g)) return rc;
+  const int num_planes = r.num_classes + (r.facing ? 4 : 0);
+  const uint64_t world = (uint64_t)num_planes * (uint64_t)g.HW;
+  if (q.op == VIEW_REGISTER) {
+    uint64_t need;
+    if (int rc = view_register(e, q, w, world, 1, &need)) return rc;
+    if (int rc = check_bank(e, r.classes, (uint64_t)num_ids * 4, "MpEgoPlanes (classes)")) return rc;
+    const world_view::Plan p = world_view::planes_plan(g, r.num_classes, e->N, e->num_cus);
+    if (p.waves < 1)
+      return fail(MP_ERR_UNSUPPORTED, "%s: one wave's render planes and class masks need %d B of LDS", kWho, p.lds);
+    e->wp = registration_of(q);
+    e->wp.mask = layer_mask;
+    e->wp.classes = r.classes;
+    e->wp.num_classes = r.num_classes;
+    e->wp.facing = r.facing;
+    return MP_OK;
+  }
+  ViewSource s;
+  if (int rc = view_source(e, q, w, v, world, world, &s)) return rc;
+  world_view::PlanesArgs a = {};
+  view_args(&a, g, q, v, s);
+  a.dst = (uint8_t*)r.dst;
+  a.lut = wt.lut;
+  a.layer_mask = layer_mask;
+  a.classes = r.classes; a.num_ids = num_ids;
+  a.num_classes = r.num_classes; a.facing = r.facing;
+  if (q.op == VIEW_HOST) {
+    for (int32_t id = 0; id < num_ids; ++id)
+      if (r.classes[id] < -1 || r.classes[id] >= r.num_classes)
+        return fail(MP_ERR_INVALID, "%s: classes[%d] = %d is outside [-1, num_classes = %d)", kWho, id,
+                    r.classes[id], r.num_classes);
+    a.src = (const uint8_t*)r.bank;
+    const int bad = world_view::host(a);
+    return bad >= 0 ? view_host_fault(q, w, bad, true) : MP_OK;
+  }
+  if (int rc = view_device_source(e, q, w, s, r.classes, (uint64_t)num_ids * 4)) return rc;
+  const world_view::Plan p = world_view::planes_plan(g, r.num_classes, r.count, e->num_cus);
+  if (p.waves < 1)
+    return fail(MP_ERR_UNSUPPORTED, "%s: one wave's render planes and class masks need %d B of LDS", kWho, p.lds);
+  a.src = s.live ? e->d_state : (const uint8_t*)r.bank;
+  a.fault = e->t.fault;
+  world_view::launch(a, p, e->stream);
+  HIP_TRY(hipGetLastError());
+  return MP_OK;
+}
+
 int ego_layer_request(MpEngine* e, const MpEgoLayer& r) {
+  if (world_op(r.op)) return world_layer_request(e, r);
   static const ViewWords w = {"MpEgoLayer", "MP_EGO_HOST", "the leaf", "needs", "drawn", "draw"};
   const char* const kWho = w.who;
   const ViewRequest q = view_of(&r);
@@ -339,6 +510,7 @@ int view_hash_request(MpEngine* e, MpViewHash* out) {
 
 // (`out` is the caller's struct: num_ids is written back)
 int ego_planes_request(MpEngine* e, MpEgoPlanes* out) {
+  if (world_op(out->op)) return world_planes_request(e, out);
   static const ViewWords w = {"MpEgoPlanes", "MP_EGOPLANES_HOST", "the planes", "need", "drawn", "draw"};
   const char* const kWho = w.who;
   MpEgoPlanes r;

@@ -475,6 +475,9 @@ enum IndexFault : uint32_t {
   kFaultEgoPlanesClass = 17u,
   kFaultAvatarIdsRow = 18u,      // MpAvatarIds: as MpEgoLayer
   kFaultAvatarIdsPlayer = 19u,
+  kFaultWorldLayerRow = 20u,     // MpEgoLayer's world ops (WORLD.LAYER): rows[] names no row (no world of the engine)
+  kFaultWorldPlanesRow = 21u,    // MpEgoPlanes' world ops: likewise, and an entry of a DEVICE class table outside
+  kFaultWorldPlanesClass = 22u,  // [-1, num_classes), as kFaultEgoPlanesClass
 };
 // ... and of a registered episode start a stepping launch skipped (step_load.h: report_start):
 // words 32-35 = world + 1, rows[world], the rule of the row's verdict (0: a bad index), its offset word.

@@ -18,6 +18,7 @@
 #include "ego_layer.h"
 #include "view_hash.h"
 #include "ego_planes.h"
+#include "world_view.h"
 
 thread_local std::string g_error;
 
@@ -76,6 +77,9 @@ constexpr IndexPairReport kIndexPairReports[] = {
     {kFaultViewHashRow, kFaultViewHashPlayer, "MpViewHash", kNoRowOrWorld, kNoPlayer},
     {kFaultEgoPlanesRow, kFaultEgoPlanesPlayer, "MpEgoPlanes", kNoRowOrWorld, kNoPlayer},
     {kFaultAvatarIdsRow, kFaultAvatarIdsPlayer, "MpAvatarIds", kNoRowOrWorld, kNoPlayer},
+    // (the world ops take no players[]: one code each)
+    {kFaultWorldLayerRow, kFaultWorldLayerRow, "MpEgoLayer (MP_EGO_WORLD_DRAW)", kNoRowOrWorld, kNoPlayer},
+    {kFaultWorldPlanesRow, kFaultWorldPlanesRow, "MpEgoPlanes (MP_EGOPLANES_WORLD_DRAW)", kNoRowOrWorld, kNoPlayer},
 };
 
 }  // namespace
@@ -140,6 +144,10 @@ int sync_and_check(MpEngine* e, const char* who) {
         return fail(MP_ERR_INVALID,
                     "%s: MpEgoPlanes: classes[%u] = %d is outside [-1, num_classes); the entry counted as -1",
                     who, at, (int)index);
+      case kFaultWorldPlanesClass:
+        return fail(MP_ERR_INVALID,
+                    "%s: MpEgoPlanes (MP_EGOPLANES_WORLD_DRAW): classes[%u] = %d is outside [-1, num_classes); the "
+                    "entry counted as -1", who, at, (int)index);
       case kFaultListedWorld:
       case kFaultListedRepeat:
         return fail(MP_ERR_INVALID,
@@ -284,7 +292,8 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
     HIP_TRY(hipGetLastError());
   }
   // the registered views: every world's, rewritten from the records this submission left
-  if (!e->viewing(e->ego) && !e->viewing(e->vh) && !e->viewing(e->ep) && !e->viewing(e->av) && !e->viewing(e->avz))
+  if (!e->viewing(e->ego) && !e->viewing(e->vh) && !e->viewing(e->ep) && !e->viewing(e->av) && !e->viewing(e->avz) &&
+      !e->viewing(e->wl) && !e->viewing(e->wp))
     return MP_OK;
   const ego_layer::Window g = ego_layer::window_of(e->t);
   auto worlds = [&](auto* a, const MpEngine::ViewRegistration& v) {   // what the three launches share
@@ -324,6 +333,23 @@ int submit(MpEngine* e, int mode, const int32_t* actions, const uint8_t* mask,
     a.dst_zap = (int32_t*)(e->avz.dst ? e->avz.slot(slot) : nullptr);
     avatar_ids_tables(&a, e->t, zap_rules_of(e->sub), (const uint32_t*)e->t.step_blob);
     avatar_ids::launch(a, avatar_ids::plan_of(g, a.plane_at, e->N, e->num_cus), e->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  if (e->viewing(e->wl)) {   // WORLD.LAYER
+    world_view::LayerArgs a = {};
+    worlds(&a, e->wl);
+    a.lut = e->d_world_lut;
+    world_view::launch(a, world_view::layer_plan(g, e->N, e->num_cus), e->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  if (e->viewing(e->wp)) {   // the world's class and facing planes
+    world_view::PlanesArgs a = {};
+    worlds(&a, e->wp);
+    a.lut = e->d_world_lut;
+    a.layer_mask = e->wp.mask;
+    a.classes = e->wp.classes; a.num_ids = e->num_world_ids;
+    a.num_classes = e->wp.num_classes; a.facing = e->wp.facing;
+    world_view::launch(a, world_view::planes_plan(g, a.num_classes, e->N, e->num_cus), e->stream);
     HIP_TRY(hipGetLastError());
   }
   return MP_OK;
@@ -614,6 +640,18 @@ std::vector<int32_t> layer_lut_rows(const void* pack, const DevTables& t) {
   return lut;
 }
 
+// The WORLD's value table (world_view.h): a viewer's row through row P of view_sprite_map, the map
+// "WORLD.RGB" is rendered through (frame.hip: build_world_images).  [256] stays 0: no cell of the
+// whole map is off it.
+std::vector<int32_t> world_lut_row(const void* pack, const DevTables& t) {
+  const int32_t* ssprite = table<int32_t>(pack, "state_sprite");
+  const int32_t* remap = table<int32_t>(pack, "view_sprite_map") + (size_t)t.P * t.nsprites;
+  std::vector<int32_t> row((size_t)kLayerLutRow, 0);
+  for (int s = 1; s < t.nstates && s < 256; ++s)
+    row[s] = ssprite[s] >= 0 ? 1 + remap[ssprite[s]] : 0;
+  return row;
+}
+
 // FNV-1a of a pack's bytes (stock.h: MP_STOCK_*_PACK_HASH).
 uint64_t pack_hash(const std::vector<uint8_t>& pack) {
   uint64_t h = 0xcbf29ce484222325ull;
@@ -639,6 +677,10 @@ int upload_layer_lut(MpEngine* e) {
   e->num_layer_ids = view_hash::num_ids(lut.data(), t.P);
   HIP_TRY(hipMalloc((void**)&e->d_layer_lut, lut.size() * 4));
   HIP_TRY(hipMemcpy(e->d_layer_lut, lut.data(), lut.size() * 4, hipMemcpyHostToDevice));
+  const std::vector<int32_t> wt = world_lut_row(e->pack.data(), t);
+  e->num_world_ids = world_view::num_ids(wt.data());
+  HIP_TRY(hipMalloc((void**)&e->d_world_lut, wt.size() * 4));
+  HIP_TRY(hipMemcpy(e->d_world_lut, wt.data(), wt.size() * 4, hipMemcpyHostToDevice));
   return MP_OK;
 }
 
@@ -695,6 +737,8 @@ int plan_views(MpEngine* e, const MpDevOptions* dev) {
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the avatar-ids kernels failed: %d", rc);
   if (int rc = ego_planes::prepare())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the ego-planes kernels failed: %d", rc);
+  if (int rc = world_view::prepare())
+    return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the world-view kernels failed: %d", rc);
   if (int rc = prepare_step_starts())
     return fail(MP_ERR_HIP, "mp_create: hipFuncSetAttribute(max dynamic LDS) of the episode-start kernels failed: %d", rc);
   if (int rc = prepare_step_active())
@@ -885,7 +929,7 @@ void mp_destroy(MpEngine* e) {
   if (e->h_fault) (void)hipHostFree(e->h_fault);
   void* bufs[] = {e->d_pack, e->d_extra, e->d_stepblob, e->d_debug, e->d_state, e->d_scalars,
                   e->d_actions, e->d_fields, e->d_mask, e->d_seeds, e->d_atlas, e->d_ctr, e->d_claim,
-                  e->d_layer_lut, e->d_obs_rows, e->d_obs_stash, e->d_check, e->d_hash_mask,
+                  e->d_layer_lut, e->d_world_lut, e->d_obs_rows, e->d_obs_stash, e->d_check, e->d_hash_mask,
                   e->d_hash_custom, e->d_listed_claim};
   for (void* b : bufs)
     if (b) (void)hipFree(b);

@@ -762,6 +762,79 @@ def ego_planes_host(pack_bytes: bytes, rows, classes, players=None, *, which=Non
   return out
 
 
+# WORLD.LAYER and the world planes: the world ops of MpEgoLayer and MpEgoPlanes (include/mp_engine.h),
+# the whole map in place of the viewers' windows
+MP_EGO_WORLD_DRAW, MP_EGO_WORLD_REGISTER, MP_EGO_WORLD_HOST = 4, 5, 6
+MP_EGOPLANES_WORLD_DRAW, MP_EGOPLANES_WORLD_REGISTER, MP_EGOPLANES_WORLD_HOST = 4, 5, 6
+OBS_WORLD_LAYER = -3   # no MpObsKind: the Python layers' handle for the "WORLD.LAYER" leaf
+
+
+def _world_map(pack_bytes: bytes) -> Tuple[int, int]:
+  """(H, W) of the pack's map."""
+  from . import lower, pack as pack_lib
+  hdr = pack_lib.loads(pack_bytes)["hdr"]
+  return int(hdr[lower.HDR_H]), int(hdr[lower.HDR_W])
+
+
+def _world_host_source(who: str, pack_bytes: bytes, rows, which, fingerprint, num_players, dev):
+  layout, lead, src, alive = _view_host_source(who, "draw", pack_bytes, rows, None, which, fingerprint,
+                                               num_players, dev)
+  return layout, lead[:1], src, alive
+
+
+def num_world_layer_ids_host(pack_bytes: bytes, *, num_players: int = 0, dev: Optional[Dict[str, int]] = None) -> int:
+  """The number of ids "WORLD.LAYER" can hold for this pack, 1 + the largest: the length of a
+  `classes` table of `world_planes_host` (an MpEgoPlanes question without an engine: no GPU needed)."""
+  keep = _host_config(pack_bytes, num_players, dev)
+  req = ego_planes_request(load_library(), None, MP_EGOPLANES_WORLD_HOST, pack=ctypes.addressof(keep[0]),
+                           pack_len=len(pack_bytes), cfg=ctypes.cast(ctypes.pointer(keep[1]), ctypes.c_void_p))
+  return int(req.num_ids)
+
+
+def world_layer_id_names_host(pack_bytes: bytes, *, num_players: int = 0,
+                              dev: Optional[Dict[str, int]] = None) -> Tuple[str, ...]:
+  """What every id of "WORLD.LAYER" shows: "" for id 0 (nothing) and the name of sprite i - 1 for id
+  i, after the WORLD's sprite map.  No GPU."""
+  from . import pack as pack_lib
+  names = bytes(pack_lib.loads(pack_bytes)["sprite_names"]).split(b"\0")[:-1]
+  n = num_world_layer_ids_host(pack_bytes, num_players=num_players, dev=dev)
+  return ("",) + tuple(names[i].decode() if i < len(names) else "" for i in range(n - 1))
+
+
+def world_layer_host(pack_bytes: bytes, rows, *, which=None, fingerprint: Optional[int] = None,
+                     num_players: int = 0, dev: Optional[Dict[str, int]] = None) -> np.ndarray:
+  """WORLD.LAYER — the layer view of the whole map, int32 [R, H, W, L], north up — of host rows
+  (uint8 [M, S] array) by the library's host-only form (MP_EGO_WORLD_HOST: the kernel's own value
+  function compiled for the host; no GPU needed).  `which`: the rows to draw, in order, repeats
+  allowed (default: all).  `fingerprint`: the rows' (default: the pack's)."""
+  layout, lead, src, _alive = _world_host_source("world_layer_host", pack_bytes, rows, which, fingerprint,
+                                                 num_players, dev)
+  out = np.zeros(lead + _world_map(pack_bytes) + (layout.L,), np.int32)
+  ego_layer_request(load_library(), None, MP_EGO_WORLD_HOST, dst=out.ctypes.data, dst_bytes=out.nbytes, **src)
+  return out
+
+
+def world_planes_host(pack_bytes: bytes, rows, classes, *, which=None, layers=None, facing: bool = False,
+                      num_classes: Optional[int] = None, fingerprint: Optional[int] = None, num_players: int = 0,
+                      dev: Optional[Dict[str, int]] = None) -> np.ndarray:
+  """The class and facing planes of the whole map of host rows (uint8 [M, S] array) by the
+  library's host-only form (MP_EGOPLANES_WORLD_HOST; no GPU needed): uint8 [R, C', H, W].  `classes`:
+  `num_world_layer_ids_host(pack)` ints in [-1, C) mapping every id of "WORLD.LAYER" to its class
+  (-1: none); C = `num_classes`, by default 1 + the largest; C' = C + 4 with `facing` (plane C + d:
+  a living avatar that faces d stands there, 0 = N).  `which`: the rows, in order, repeats allowed
+  (default: all).  `layers`: the layer indices that count (None: all)."""
+  layout, lead, src, _alive = _world_host_source("world_planes_host", pack_bytes, rows, which, fingerprint,
+                                                 num_players, dev)
+  cls, C = _plane_classes(classes, num_world_layer_ids_host(pack_bytes, num_players=num_players, dev=dev),
+                          num_classes)
+  mask = view_layer_mask(layers, layout.L)
+  out = np.zeros(lead + (C + (4 if facing else 0),) + _world_map(pack_bytes), np.uint8)
+  ego_planes_request(load_library(), None, MP_EGOPLANES_WORLD_HOST, layer_mask=mask, classes=cls.ctypes.data,
+                     classes_len=int(cls.size), num_classes=C, facing=int(bool(facing)), dst=out.ctypes.data,
+                     dst_bytes=out.nbytes, **src)
+  return out
+
+
 # Whom each player sees and whom it could zap (include/mp_engine.h: MpAvatarIds), carried by mp_snapshot
 MP_AVATARIDS_DRAW, MP_AVATARIDS_REGISTER, MP_AVATARIDS_HOST = 1, 2, 3
 
@@ -2898,6 +2971,146 @@ class Engine:
                        classes_len=int(cls.numel()), num_classes=C, facing=int(bool(facing)),
                        **self._view_ring(out, ring, int(np.prod(shape))))
     self._ego_planes = (out, cls)
+    return out
+
+  # ---- the world camera: WORLD.LAYER and the world planes (the world ops of MpEgoLayer, MpEgoPlanes)
+
+  @property
+  def world_layer_shape(self):
+    """The shape of the WORLD.LAYER leaf, [N, H, W, L] (int32)."""
+    info = self.info   # (MpInfo, read at creation: nothing is parsed or asked per call)
+    return (self.N, int(info.map_h), int(info.map_w), int(info.num_layers))
+
+  def observe_world_layer(self, bank=None, rows=None, out=None, fingerprint: Optional[int] = None):
+    """WORLD.LAYER — the layer view of the whole map, what "WORLD.RGB" is rendered from: int32
+    [R, H, W, L], north up — of rows of `bank` (a contiguous uint8 device tensor [M, S], as
+    observe_states' bank), or of the engine's worlds as they are now (`bank` None; `rows` are then
+    world indices).  `rows`: the rows to draw, in order, repeats allowed (None: all of them).  Id i
+    is sprite i - 1 after the WORLD's sprite map (`world_layer_id_names`); no cell is off the map
+    and a dead avatar shows nowhere.  `(layer == id).sum()` counts things on the map.  Nothing of
+    the engine's is written.  A row index out of range leaves its element as it was; the next
+    synchronising call raises ValueError.  Enqueued on the current stream."""
+    count, r, _, src = self._view_source("observe_world_layer", "draw", bank, rows, None, fingerprint)
+    out = self._out("observe_world_layer", out, (count,) + self.world_layer_shape[1:], self._torch.int32)
+    self.use_current_stream()
+    ego_layer_request(self._L, self._h, MP_EGO_WORLD_DRAW, dst=out.data_ptr(), dst_bytes=out.numel() * 4, **src)
+    self._state_args = (bank, r, None, out)   # (kept until the next call: the launch may not have run yet)
+    return out
+
+  def bind_world_layer(self, out):
+    """Registers `out` — a contiguous int32 device tensor of `world_layer_shape`, or [T, N, H, W, L]
+    with T the engine's ring slots (`bind_ring` some kind first) — as the WORLD.LAYER leaf: from now
+    on every submission (reset, step, step_many in every form, a load) is followed on the same
+    stream by one launch that redraws every world's map into it, or into the ring slot the
+    submission wrote.  None clears the registration; the engine's launches are then what they
+    were.  Returns `out`."""
+    t = self._torch
+    if out is None:
+      ego_layer_request(self._L, self._h, MP_EGO_WORLD_REGISTER)
+      self._world_layer = None
+      return None
+    shape = self.world_layer_shape
+    ring = isinstance(out, t.Tensor) and out.dim() == len(shape) + 1
+    if (not isinstance(out, t.Tensor) or out.dtype != t.int32 or tuple(out.shape[-len(shape):]) != shape or
+        out.dim() not in (len(shape), len(shape) + 1) or not (out[0] if ring else out).is_contiguous() or
+        out.device != self.device):
+      raise ValueError(f"bind_world_layer: out must be an int32 tensor of shape {shape} or "
+                       f"[T, {', '.join(map(str, shape))}] with contiguous slots on {self.device}")
+    ego_layer_request(self._L, self._h, MP_EGO_WORLD_REGISTER, **self._view_ring(out, ring, int(np.prod(shape)) * 4))
+    self._world_layer = out
+    return out
+
+  @property
+  def num_world_layer_ids(self) -> int:
+    """The number of ids WORLD.LAYER can hold, 1 + the largest: the length of a `classes` table of
+    `observe_world_planes`."""
+    if getattr(self, "_num_world_layer_ids", None) is None:
+      self._num_world_layer_ids = int(ego_planes_request(self._L, self._h, MP_EGOPLANES_WORLD_DRAW).num_ids)
+    return self._num_world_layer_ids
+
+  @property
+  def world_layer_id_names(self) -> Tuple[str, ...]:
+    """What every id of WORLD.LAYER shows: `num_world_layer_ids` strings, "" for id 0 (nothing) and
+    the name of sprite i - 1 for id i, after the WORLD's sprite map."""
+    if getattr(self, "_world_layer_id_names", None) is None:
+      from . import pack as pack_lib
+      names = bytes(pack_lib.loads(self.pack_bytes)["sprite_names"]).split(b"\0")[:-1]
+      self._world_layer_id_names = ("",) + tuple(names[i].decode() if i < len(names) else ""
+                                                 for i in range(self.num_world_layer_ids - 1))
+    return self._world_layer_id_names
+
+  def _world_plane_classes(self, classes, num_classes):
+    """`_plane_classes` over the world's ids."""
+    t = self._torch
+    n = self.num_world_layer_ids
+    if classes is None:
+      raise ValueError("world_planes: classes is needed: one class (or -1) per id of WORLD.LAYER "
+                       "(num_world_layer_ids)")
+    if (isinstance(classes, t.Tensor) and classes.dtype == t.int32 and classes.device == self.device and
+        classes.is_contiguous() and tuple(classes.shape) == (n,)):
+      C = int(classes.max()) + 1 if num_classes is None else int(num_classes)
+      if not 1 <= C <= EGO_PLANES_MAX_CLASSES:
+        raise ValueError(f"world_planes: num_classes {C} is outside [1, {EGO_PLANES_MAX_CLASSES}]")
+      return classes, C
+    host = classes.cpu().numpy() if isinstance(classes, t.Tensor) else classes
+    table, C = _plane_classes(host, n, num_classes)
+    return t.from_numpy(table).to(self.device), C
+
+  def world_planes_shape(self, num_classes: int, facing: bool = False) -> Tuple[int, ...]:
+    """(N, C', H, W) of the world planes: C' = num_classes, + 4 with `facing`."""
+    N, H, W, _ = self.world_layer_shape
+    return (N, int(num_classes) + (4 if facing else 0), H, W)
+
+  def observe_world_planes(self, classes, bank=None, rows=None, layers=None, facing: bool = False,
+                           num_classes: Optional[int] = None, out=None, fingerprint: Optional[int] = None):
+    """uint8 device tensor [R, C', H, W]: the whole map as channels-first 0/1 planes — a centralised
+    critic's input (`planes.half()`) — written from the records by one launch, in rows of `bank` (a
+    contiguous uint8 device tensor [M, S]) or in the engine's worlds as they are now (`bank` None;
+    `rows` are then world indices).  `classes`: `num_world_layer_ids` ints in [-1, C) mapping every
+    id of WORLD.LAYER to its class (`world_layer_id_names` says which id is which sprite); class
+    plane c is 1 where some counted layer of the cell holds an id of class c, -1 sets nothing.
+    C = `num_classes` (at most 64), by default 1 + the largest entry.  `layers`: the layer indices
+    that count (None: all).  `facing`: four more planes, C' = C + 4: plane C + d is 1 where a living
+    avatar stands that faces d (absolute, 0 = N).  `out`: a uint8 tensor of the result's shape that
+    may start on any byte.  A contiguous int32 device `classes` is read where it lies; an entry of
+    it outside [-1, C) counts as -1 and the next synchronising call raises ValueError, as it does
+    for a row index out of range, whose element is left as it was.  Enqueued on the current stream."""
+    count, r, _, src = self._view_source("observe_world_planes", "draw", bank, rows, None, fingerprint)
+    mask = view_layer_mask(layers, int(self.info.num_layers))
+    cls, C = self._world_plane_classes(classes, num_classes)
+    out = self._out("observe_world_planes", out, (count,) + self.world_planes_shape(C, facing)[1:], self._torch.uint8)
+    self.use_current_stream()
+    ego_planes_request(self._L, self._h, MP_EGOPLANES_WORLD_DRAW, layer_mask=mask, classes=cls.data_ptr(),
+                       classes_len=int(cls.numel()), num_classes=C, facing=int(bool(facing)), dst=out.data_ptr(),
+                       dst_bytes=out.numel(), **src)
+    self._world_planes_args = (bank, r, cls, out)   # (kept until the next call: the launch may not have run yet)
+    return out
+
+  def bind_world_planes(self, out, classes=None, layers=None, facing: bool = False, num_classes: Optional[int] = None):
+    """Registers `out` — a uint8 device tensor [N, C', H, W], or [T, N, C', H, W] with T the engine's
+    ring slots (`bind_ring` some kind first); it may start on any byte — as the world planes: from
+    now on every submission is followed on the same stream by one launch that rewrites
+    `observe_world_planes(classes, ...)` of every world into it, or into the ring slot the
+    submission wrote.  The engine keeps the class table alive.  None clears the registration; the
+    engine's launches are then what they were.  Returns `out`."""
+    t = self._torch
+    if out is None:
+      ego_planes_request(self._L, self._h, MP_EGOPLANES_WORLD_REGISTER)
+      self._world_planes = None
+      return None
+    mask = view_layer_mask(layers, int(self.info.num_layers))
+    cls, C = self._world_plane_classes(classes, num_classes)
+    shape = self.world_planes_shape(C, facing)
+    ring = isinstance(out, t.Tensor) and out.dim() == len(shape) + 1
+    if (not isinstance(out, t.Tensor) or out.dtype != t.uint8 or tuple(out.shape[-len(shape):]) != shape or
+        out.dim() not in (len(shape), len(shape) + 1) or not (out[0] if ring else out).is_contiguous() or
+        out.device != self.device):
+      raise ValueError(f"bind_world_planes: out must be a uint8 tensor of shape {shape} or "
+                       f"[T, {', '.join(map(str, shape))}] with contiguous slots on {self.device}")
+    ego_planes_request(self._L, self._h, MP_EGOPLANES_WORLD_REGISTER, layer_mask=mask, classes=cls.data_ptr(),
+                       classes_len=int(cls.numel()), num_classes=C, facing=int(bool(facing)),
+                       **self._view_ring(out, ring, int(np.prod(shape))))
+    self._world_planes = (out, cls)
     return out
 
   @property

@@ -997,6 +997,12 @@ class Substrate:
     if AVATAR_IDS_NAMES[1] in ids and not engine_lib.has_zapper(pack_bytes):
       raise ValueError(f"\"{AVATAR_IDS_NAMES[1]}\": {config.name!r} has no Zapper, so no zap could reach anybody "
                        f"(\"{AVATAR_IDS_NAMES[0]}\" works on every level)")
+    # "WORLD.LAYER": a global leaf behind a registration of its own (MpEgoLayer's world ops)
+    wl = "WORLD.LAYER" in config.global_observation_names
+    if wl and not self._batched:
+      raise ValueError("\"WORLD.LAYER\" needs a batched substrate (device tensors): build it with "
+                       "num_worlds > 1; the one-world form returns numpy arrays and refuses it as it "
+                       "refuses \"EGO_LAYER\"")
     self._submissions = 0
     self._check_device_actions = bool(check_device_actions)
     if not self._roles:
@@ -1041,10 +1047,12 @@ class Substrate:
                           "NUM_OTHERS_WHO_ATE_THIS_STEP": E.OBS_AUX4})
     names = (list(config.individual_observation_names) +
              list(config.global_observation_names) + ["COLLECTIVE_REWARD"])
-    unknown = [n for n in names if n not in self._kinds and not (ego and n == "EGO_LAYER") and n not in ids]
+    unknown = [n for n in names if n not in self._kinds and not (ego and n == "EGO_LAYER") and n not in ids and
+               not (wl and n == "WORLD.LAYER")]
     if unknown:
       raise ValueError(f"observations {unknown} are not produced by the engine for "
-                       f"{config.name!r} (it offers {sorted(self._kinds) + ['EGO_LAYER'] + list(AVATAR_IDS_NAMES)})")
+                       f"{config.name!r} (it offers {sorted(self._kinds) + ['EGO_LAYER'] + list(AVATAR_IDS_NAMES)}"
+                       " and the global \"WORLD.LAYER\")")
     kinds = {n: self._kinds[n] for n in names if n in self._kinds}
     kinds.update({"#reward": E.OBS_REWARD, "#discount": E.OBS_DISCOUNT,
                   "#step_type": E.OBS_STEP_TYPE})
@@ -1095,8 +1103,18 @@ class Substrate:
         bound[n] = given if given is not None else t.zeros(((self._T,) if self._T else ()) + shape, dtype=t.int32,
                                                             device=self._eng.device)
       self._eng.bind_avatar_ids(bound.get(AVATAR_IDS_NAMES[0]), bound.get(AVATAR_IDS_NAMES[1]))
+    if wl:
+      # the layer view of the whole map: redrawn behind every submission by a launch of its own, into
+      # this tensor or into the ring slot the submission wrote
+      t = self._eng._torch
+      shape = self._eng.world_layer_shape
+      given = None if _leaves is None else _leaves("WORLD.LAYER", shape, t.int32, self._eng.device)
+      bound["WORLD.LAYER"] = self._eng.bind_world_layer(
+          given if given is not None else t.zeros(((self._T,) if self._T else ()) + shape, dtype=t.int32,
+                                                  device=self._eng.device))
     self._ego = ego
     self._ids = ids
+    self._wl = wl
     self._obs = {n: bound[n] for n in names}
     self._reward = bound["#reward"]
     self._discount = bound["#discount"]
@@ -1309,24 +1327,85 @@ class Substrate:
     A group is a name of `layer_id_names`, an `fnmatch` pattern, or an iterable of those:
       env.layer_classes(["Self", "Avatar*", "Beam*", "Wall*", "OutOfBounds"])
     ValueError for a pattern that matches no id, and for an id two groups match."""
-    names = self.layer_id_names
-    table = np.full(len(names), -1, np.int32)
-    if isinstance(groups, str):
-      groups = (groups,)
-    for c, group in enumerate(groups):
-      for pattern in ((group,) if isinstance(group, str) else tuple(group)):
-        if not isinstance(pattern, str):
-          raise ValueError(f"layer_classes: {pattern!r} is no name or pattern")
-        ids = [i for i, n in enumerate(names) if n and fnmatch.fnmatchcase(n, pattern)]
-        if not ids:
-          raise ValueError(f"layer_classes: {pattern!r} matches no id of this level (layer_id_names: "
-                           f"{[n for n in names if n]})")
-        for i in ids:
-          if table[i] not in (-1, c):
-            raise ValueError(f"layer_classes: id {i} ({names[i]!r}) is matched by class {int(table[i])} and by "
-                             f"class {c} ({pattern!r})")
-          table[i] = c
-    return table
+    return _classes_by_name("layer_classes", "layer_id_names", self.layer_id_names, groups)
+
+  # -- the world camera: "WORLD.LAYER" and the world planes ------------------------------------
+  def _world_source(self, who: str, states):
+    """(bank, fingerprint) of a world-view call: `states` checked, or (None, None) for the worlds."""
+    if not self._batched:
+      raise ValueError(f"{who} needs a batched substrate (device tensors): build it with num_worlds > 1")
+    self._eng.use_current_stream()
+    if states is None:
+      return None, None
+    if not isinstance(states, WorldStates):
+      raise ValueError(f"{who} takes the WorldStates of save_state or step_many(states=True)")
+    states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
+    return states.data, states.fingerprint
+
+  def observe_world_layer(self, states: Optional[WorldStates] = None, rows=None):
+    """"WORLD.LAYER" — the layer view of the whole map, what "WORLD.RGB" is rendered from — of saved
+    states, or of this substrate's worlds as they are now (`states` None; `rows` are then world
+    indices): int32 [R, H, W, L], north up.  Id i is sprite i - 1 after the WORLD's sprite map
+    (`world_layer_id_names`); a dead avatar shows nowhere.  `(layer == id).sum((1, 2, 3))` counts
+    things on the map.  Any batched substrate draws it, with or without the leaf.  Ordered on the
+    current stream; no host synchronisation."""
+    bank, fingerprint = self._world_source("observe_world_layer", states)
+    return self._eng.observe_world_layer(bank, rows=rows, fingerprint=fingerprint)
+
+  @property
+  def num_world_layer_ids(self) -> int:
+    """The number of ids "WORLD.LAYER" can hold: the length of `observe_world_planes`' `classes`."""
+    return self._eng.num_world_layer_ids
+
+  @property
+  def world_layer_id_names(self) -> Tuple[str, ...]:
+    """What every id of "WORLD.LAYER" shows: `num_world_layer_ids` strings, "" for id 0 (nothing)
+    and the name of sprite i - 1 for id i, after the WORLD's sprite map."""
+    return self._eng.world_layer_id_names
+
+  def world_layer_classes(self, groups) -> np.ndarray:
+    """`layer_classes` over the world's names: int32 [num_world_layer_ids], class c for every id
+    that `groups[c]` names and -1 for every other — `classes` of `observe_world_planes` and
+    `set_world_planes`."""
+    return _classes_by_name("world_layer_classes", "world_layer_id_names", self.world_layer_id_names, groups)
+
+  def observe_world_planes(self, classes, states: Optional[WorldStates] = None, rows=None, layers=None,
+                           facing: bool = False, num_classes: Optional[int] = None, out=None):
+    """The whole map as a centralised critic reads it: uint8 [R, C', H, W] device tensor of 0/1
+    planes of "WORLD.LAYER", channels first, in saved states or in this substrate's worlds as they
+    are now (`states` None; `rows` are then world indices), written from the records by one launch.
+    `classes`: `num_world_layer_ids` ints in [-1, C) (`world_layer_classes(groups)` writes one by
+    name); plane c is 1 where some counted layer of the cell holds an id of class c; -1 sets
+    nothing; C = `num_classes`, by default 1 + the largest entry, at most 64.  `layers`: the layers
+    that count, by name or index (None: all).  `facing`: four more planes, C' = C + 4: plane C + d
+    is 1 where a living avatar stands that faces d (absolute, 0 = N).  `planes.half()` is the
+    critic's input.  `out`: a uint8 tensor of the result's shape; it may start on any byte."""
+    bank, fingerprint = self._world_source("observe_world_planes", states)
+    return self._eng.observe_world_planes(classes, bank, rows=rows, layers=self._view_layers(layers), facing=facing,
+                                          num_classes=num_classes, out=out, fingerprint=fingerprint)
+
+  def set_world_planes(self, classes, layers="all", facing: bool = False, out=None, num_classes: Optional[int] = None):
+    """Keeps `observe_world_planes(classes, ...)` of the worlds current on the device: returns a
+    uint8 [N, C', H, W] device tensor — [T, N, C', H, W] on a substrate built with rollout_length=T
+    — that one launch rewrites behind every reset, step, step_many and load_state, in the ring slot
+    the submission wrote.  `set_world_planes(None)` clears the registration: the launches are then
+    what they were.  There are no per-step rows in `step_many`: call step_many(states=True) and
+    observe_world_planes(classes, result.states)."""
+    if not self._batched:
+      raise ValueError("set_world_planes needs a batched substrate (device tensors): build it with num_worlds > 1")
+    self._eng.use_current_stream()
+    if classes is None:
+      self._eng.bind_world_planes(None)
+      return None
+    layers = None if isinstance(layers, str) and layers == "all" else self._view_layers(layers)
+    t = self._eng._torch
+    cls, C = self._eng._world_plane_classes(classes, num_classes)
+    shape = ((self._T,) if self._T else ()) + self._eng.world_planes_shape(C, facing)
+    if out is None:
+      out = t.zeros(shape, dtype=t.uint8, device=self._eng.device)
+    elif not isinstance(out, t.Tensor) or tuple(out.shape) != shape:
+      raise ValueError(f"set_world_planes: out must be a uint8 device tensor of shape {shape}")
+    return self._eng.bind_world_planes(out, cls, layers=layers, facing=facing, num_classes=C)
 
   def observe_ego_planes(self, classes, states: Optional[WorldStates] = None, rows=None, players=None, layers=None,
                          facing: bool = False, num_classes: Optional[int] = None):
@@ -1487,6 +1566,8 @@ class Substrate:
               if n != "INVENTORY" or int(self._eng.info.num_resources) > 0}
     if getattr(self, "_ego", False):   # (a substrate built with the leaf also draws it from saved states)
       leaves["EGO_LAYER"] = engine_lib.OBS_EGO_LAYER
+    if getattr(self, "_wl", False):   # (likewise: the whole map, one block a row)
+      leaves["WORLD.LAYER"] = engine_lib.OBS_WORLD_LAYER
     if getattr(self, "_ids", ()):   # (likewise; drawn by a request of their own, MpAvatarIds: no engine kind)
       leaves[AVATAR_IDS_NAMES[0]] = engine_lib.OBS_AVATAR_IDS
       if self._eng.has_zapper:
@@ -1529,12 +1610,16 @@ class Substrate:
       if "WORLD.RGB" in named:
         raise ValueError("observe_states: \"WORLD.RGB\" is one image per world, not per player: it cannot be "
                          "drawn with players=; draw it in a call of its own")
+      if "WORLD.LAYER" in named:
+        raise ValueError("observe_states: \"WORLD.LAYER\" is one map per world, not per player: it cannot be "
+                         "drawn with players=; draw it in a call of its own")
     leaves = self._state_leaves(observations)
     if not isinstance(states, WorldStates):
       raise ValueError("observe_states takes the WorldStates of save_state or step_many(states=True)")
     states.check(self._eng.state_fingerprint, self._eng.info.world_state_bytes)
     self._eng.use_current_stream()
     ego = leaves.pop("EGO_LAYER", None) is not None
+    world_layer = leaves.pop("WORLD.LAYER", None) is not None   # (left out with players=, as "WORLD.RGB")
     ids = [leaves.pop(n, None) is not None for n in AVATAR_IDS_NAMES]
 
     def avatar_ids(out, r, p):   # both leaves by one launch
@@ -1549,6 +1634,8 @@ class Substrate:
              for n, k in leaves.items()}
       if ego:
         out["EGO_LAYER"] = self._eng.observe_ego_layer(states.data, rows=rows, fingerprint=states.fingerprint)
+      if world_layer:
+        out["WORLD.LAYER"] = self._eng.observe_world_layer(states.data, rows=rows, fingerprint=states.fingerprint)
       return avatar_ids(out, rows, None)
     p = self._eng._device_ints(players, "players")
     r = None if rows is None else self._eng._device_ints(rows, "rows")
@@ -1711,6 +1798,10 @@ class Substrate:
         raise ValueError("step_many: \"EGO_LAYER\" has no per-step rows (it is drawn by a launch behind the "
                          "submission, from the final records): call step_many(states=True) and draw "
                          "observe_states(result.states, (\"EGO_LAYER\",)) or observe_ego_layer(result.states)")
+      if n == "WORLD.LAYER":
+        raise ValueError("step_many: \"WORLD.LAYER\" has no per-step rows (it is drawn by a launch behind the "
+                         "submission, from the final records): call step_many(states=True) and draw "
+                         "observe_states(result.states, (\"WORLD.LAYER\",)) or observe_world_layer(result.states)")
       if n not in offered:
         what = ("a pixel leaf: step_many draws no intermediate frames (step with rollout_length=T does)"
                 if n in self._obs else "no leaf of this substrate")
@@ -1931,6 +2022,36 @@ _EXTRA_SPECS = {"POSITION": Array((2,), np.int32, "POSITION"),
                 "NUM_OTHERS_WHO_ATE_THIS_STEP": Array((), np.float64, "NUM_OTHERS_WHO_ATE_THIS_STEP")}
 
 
+def _classes_by_name(who: str, listed: str, names, groups) -> np.ndarray:
+  """A class table over `names` (one per id, "" for an id nothing names): class c for every id a
+  name or `fnmatch` pattern of `groups[c]` matches, -1 for every other."""
+  table = np.full(len(names), -1, np.int32)
+  if isinstance(groups, str):
+    groups = (groups,)
+  for c, group in enumerate(groups):
+    for pattern in ((group,) if isinstance(group, str) else tuple(group)):
+      if not isinstance(pattern, str):
+        raise ValueError(f"{who}: {pattern!r} is no name or pattern")
+      ids = [i for i, n in enumerate(names) if n and fnmatch.fnmatchcase(n, pattern)]
+      if not ids:
+        raise ValueError(f"{who}: {pattern!r} matches no id of this level ({listed}: "
+                         f"{[n for n in names if n]})")
+      for i in ids:
+        if table[i] not in (-1, c):
+          raise ValueError(f"{who}: id {i} ({names[i]!r}) is matched by class {int(table[i])} and by "
+                           f"class {c} ({pattern!r})")
+        table[i] = c
+  return table
+
+
+def world_layer_spec(pack_bytes: bytes) -> Array:
+  """"WORLD.LAYER" of a pack: the whole map as int32 sprite ids, one per render layer — (H, W, L);
+  0 is nothing, 1 + k sprite k of the world's sprite map."""
+  from meltingpot_amd import lower, pack as pack_lib
+  hdr = pack_lib.loads(pack_bytes)["hdr"]
+  return Array((int(hdr[lower.HDR_H]), int(hdr[lower.HDR_W]), int(hdr[lower.HDR_L])), np.int32, "WORLD.LAYER")
+
+
 def layer_spec(pack_bytes: bytes) -> Array:
   """"LAYER" of a pack (avatar_library.lua:246-257, A17): the player's window with orientation
   'N' as int32 sprite ids, one per render layer — (VH, VW, L); 0 is nothing, 1 + k sprite k."""
@@ -1961,6 +2082,8 @@ def observation_spec_of(config: SubstrateConfig, pack_bytes: bytes, rgb_pool: in
   these pooling factors (what its `observation_spec()` hands out per player).  `num_players`: the
   length of the AVATAR_IDS_* vectors (default: the config's default roles)."""
   spec = dict(config.timestep_spec)
+  if "WORLD.LAYER" in config.global_observation_names:   # (beside "WORLD.RGB", among the global leaves)
+    spec["WORLD.LAYER"] = world_layer_spec(pack_bytes)
   spec["COLLECTIVE_REWARD"] = Array((), np.float64, "COLLECTIVE_REWARD")
   if rgb_pool > 1 and "RGB" in spec:
     h, w, c = spec["RGB"].shape
@@ -1995,6 +2118,8 @@ def select_observations(config: SubstrateConfig, pack_bytes: bytes,
     spec["LAYER"] = layer_spec(pack_bytes)
   if "EGO_LAYER" in individual:
     spec["EGO_LAYER"] = ego_layer_spec(pack_bytes)
+  if "WORLD.LAYER" in global_observations:
+    spec["WORLD.LAYER"] = world_layer_spec(pack_bytes)
   spec.update(avatar_ids_specs(individual, len(config.default_player_roles)))
   wanted = set(individual) | set(global_observations)
   return individual, list(global_observations), {n: sp for n, sp in spec.items() if n in wanted}
@@ -2129,7 +2254,8 @@ def check_config_against_pack(config: SubstrateConfig, pack_bytes: bytes, num_pl
   want = {"RGB": ((int(hdr[lower.HDR_VF]) + int(hdr[lower.HDR_VB]) + 1) * S,
                   (int(hdr[lower.HDR_VL]) + int(hdr[lower.HDR_VR]) + 1) * S, 3),
           "WORLD.RGB": (int(hdr[lower.HDR_H]) * S, int(hdr[lower.HDR_W]) * S, 3),
-          "LAYER": layer_spec(pack_bytes).shape, "EGO_LAYER": layer_spec(pack_bytes).shape}
+          "LAYER": layer_spec(pack_bytes).shape, "EGO_LAYER": layer_spec(pack_bytes).shape,
+          "WORLD.LAYER": world_layer_spec(pack_bytes).shape}
   for n, shape in want.items():
     if n in config.timestep_spec and tuple(config.timestep_spec[n].shape) != shape:
       raise ValueError(
